@@ -5,6 +5,11 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds
+the bounded CPU baseline and the GPU-vs-CPU pixel comparison on a sample of the same
+frame.  --dump-outputs DIR writes the last timed step's frame and path counts as .npy
+files, so that two builds can be compared output for output.
+
 A "step" is one whole frame of BASELINE config 4, the configuration the metric is
 quoted on: scenes/gpu_showcase.json at 1920x1080, 1024 spp, max depth 8 (the reference's
 own scene file; there are no weights or datasets, and nothing synthetic).  The
@@ -56,6 +61,29 @@ CONFIGS = {
 }
 
 
+DUMP_BYTES = 60 * 10 ** 6     # --dump-outputs writes at most this much in all
+DUMP_COUNTS = ("samples", "segments", "exit_scans", "draws")
+
+
+def dump_outputs(out_dir: str, frame, counts) -> None:
+    """What the last timed step computed: the RGBA8 frame as float32 (H, W, 4) and its path counts (DUMP_COUNTS, summed
+    over ranks) as float64.  A frame too large for DUMP_BYTES is written as a fixed, seeded sample of its pixels (k, 4)
+    with their row-major indices."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    img = frame.cpu().numpy()
+    h, w, _ = img.shape
+    budget = DUMP_BYTES - 4096  # .npy headers and the counts
+    if h * w * 16 <= budget:
+        np.save(os.path.join(out_dir, "frame_rgba8.npy"), img.astype(np.float32))
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(h * w, budget // (16 + 8), replace=False))
+        np.save(os.path.join(out_dir, "frame_rgba8.npy"), img.reshape(-1, 4)[idx].astype(np.float32))
+        np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "path_counts.npy"), np.asarray(counts, np.float64))
+
+
 def host_cpu_quota() -> int:
     """CPUs this process may actually use: the cgroup quota if there is one, else the affinity mask."""
     n = len(os.sched_getaffinity(0))
@@ -83,13 +111,19 @@ def main() -> int:
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--spp-chunk", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the bounded CPU baseline and the GPU-vs-CPU pixel comparison (N = 1); a plain run times the frame only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the bounded CPU-baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)")
     pre, _ = ap.parse_known_args()
     if pre.config:  # the config's scene, size, spp and depth become the defaults: an explicit --spp (the short PMC passes) still wins
         sc_, w_, h_, spp_, d_ = CONFIGS[pre.config]
         ap.set_defaults(scene=sc_, width=w_, height=h_, spp=spp_, depth=d_)
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
     config_id = next((k for k, v in CONFIGS.items() if (v[0], v[1], v[2], v[4]) == (args.scene, args.width, args.height, args.depth)), None)
     config_full = config_id is not None and CONFIGS[config_id][3] == args.spp  # (the PMC passes run a config at a fraction of its spp)
 
@@ -222,6 +256,12 @@ def main() -> int:
         dist.all_gather(busy_all, busy)
     busy_ms = [float(b.item()) for b in busy_all]
     segments, samples, exits = (float(x) for x in tot.tolist())
+    last_counts = None
+    if args.dump_outputs is not None:
+        lc = torch.tensor([float(getattr(stats[-1], k)) for k in DUMP_COUNTS], dtype=torch.float64, device=red_dev)
+        if world > 1:
+            dist.all_reduce(lc, op=dist.ReduceOp.SUM)
+        last_counts = lc.tolist()
 
     out = None
     if rank == 0:
@@ -330,7 +370,9 @@ def main() -> int:
                               "raygen_ms_per_step": sum(s.raygen_ms for s in stats) / steps,
                               "resolve_ms_per_step": resolve_ms / steps},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, frame, last_counts)
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import ora  # CPU restatement of the reference engine: the timed baseline only
 
             import numpy as np

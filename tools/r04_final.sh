@@ -9,7 +9,7 @@ if [ "$WHAT" = bench ]; then
   timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/gpu_tests_$TAG.log 2>&1
   rc=$?; echo "pytest rc=$rc"; tail -3 $O/gpu_tests_$TAG.log; [ $rc -eq 0 ] || exit 1
   timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" || exit 1
-  timeout -k 10 400 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -5 $O/${TAG}_bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -5 $O/${TAG}_bench.err; exit 1; }
   for C in C2 C3 C5; do
     c=$(echo $C | tr C c)
     case $C in C2) ST="--steps 20 --warmup 3";; C3) ST="--steps 5 --warmup 1";; C5) ST="--steps 1 --warmup 1";; esac
