@@ -190,6 +190,47 @@ func flatten(sc *scene.Scene) (*C.pt_scene, func()) {
 	}
 }
 
+// fogEnabled: PATHTRACER_GPU_FOG=1 (true / on / yes) draws the scene's fog block the way the GL backend does
+// (gpu.go:1125-1341); without it fog is ignored, like the CPU engine ignores it (scene.go:100).
+func fogEnabled() bool {
+	switch os.Getenv("PATHTRACER_GPU_FOG") {
+	case "1", "true", "TRUE", "True", "on", "ON", "yes", "YES":
+		return true
+	}
+	return false
+}
+
+// setFog hands sc.Fog to the context (pt_set_fog), or turns fog off.  pt_fog holds no pointers.
+func setFog(sc *scene.Scene) error {
+	if !fogEnabled() || sc.Fog == nil {
+		if rc := C.pt_set_fog(ctx, nil); rc != C.PT_OK {
+			return lastError("pt_set_fog")
+		}
+		return nil
+	}
+	f := sc.Fog
+	var cf C.pt_fog
+	cf.density = C.double(f.Density)
+	set3(&cf.color, f.Color.R, f.Color.G, f.Color.B)
+	cf.scatter = C.double(f.Scatter)
+	cf.sigma_s = C.double(f.SigmaS)
+	cf.sigma_a = C.double(f.SigmaA)
+	cf.g = C.double(f.G)
+	cf.hetero_strength = C.double(f.HeteroStrength)
+	cf.noise_scale = C.double(f.NoiseScale)
+	cf.noise_octaves = C.int32_t(f.NoiseOctaves)
+	if f.AffectSky {
+		cf.affect_sky = 1
+	}
+	if f.GPUVolumetric {
+		cf.gpu_volumetric = 1
+	}
+	if rc := C.pt_set_fog(ctx, &cf); rc != C.PT_OK {
+		return lastError("pt_set_fog")
+	}
+	return nil
+}
+
 // Render renders sc into img on the MI355X and calls progress() every ~10% of the samples and once
 // at the end (the cadence of gpu.go:2209-2212, :2229, :2523-2525).  On any error the caller
 // (engine.renderIntoGPU) falls back to the CPU renderer exactly as it does for the GL backend.
@@ -214,6 +255,9 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 	}
 	cs, free := flatten(sc)
 	defer free()
+	if err := setFog(sc); err != nil {
+		return err
+	}
 	pc := C.pt_config{width: C.int32_t(cfg.Width), height: C.int32_t(cfg.Height),
 		samples_per_px: C.int32_t(cfg.SamplesPerPx), max_depth: C.int32_t(cfg.MaxDepth), seed: C.uint64_t(seed)}
 	pix := (*C.uint8_t)(unsafe.Pointer(&img.Pix[0]))

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 3
+#define PT_ABI_VERSION 4
 
 /* status codes; pt_last_error() holds the text (thread-local) */
 enum {
@@ -260,6 +260,45 @@ typedef struct pt_post_config {
 } pt_post_config;
 int32_t pt_post_process(pt_ctx *ctx, const pt_post_config *post, const double *accum, int32_t samples_per_px, uint8_t *rgba,
                         int32_t stride, int32_t width, int32_t height);
+
+/*
+ * Fog (ABI 4): the scene's fog block (scene.Fog, internal/scene/scene.go:101-131) as the reference's OpenGL backend draws it
+ * (internal/engine/gpu/gpu.go:1125-1341): a sky blended towards the fog colour (affect_sky) and single-scattered light from
+ * the emissive spheres along each sample's primary ray (gpu_volumetric), added to the sample radiance.  Not part of the CPU
+ * engine's image, so it is off unless asked for.  The model, restated in FP64, is documented in csrc/pt_fog.h and DESIGN.md.
+ *   pt_set_fog(ctx, &fog) : later renders on ctx (every entry point) use this block; pt_set_fog(ctx, NULL) turns fog off
+ *                           (the default).  The block is copied.
+ *   pt_fog_last_stats     : what the fog kernel did in the last finished frame of ctx (zeros when it did not run).
+ * Scenes on the bounding-volume-hierarchy path (more than 128 spheres or 128 boxes) refuse gpu_volumetric with
+ * PT_ERR_INVALID; affect_sky alone works on every scene.  Segment and draw counts (pt_stats, nseg / ndraw) stay those of the
+ * surface paths: the fog term draws from a stream of its own.
+ */
+typedef struct pt_fog {
+    double density;
+    double color[3];
+    double scatter;
+    double sigma_s;
+    double sigma_a;
+    double g;
+    double hetero_strength;
+    double noise_scale;
+    int32_t noise_octaves;
+    int32_t affect_sky;     /* 0 or 1 */
+    int32_t gpu_volumetric; /* 0 or 1 */
+    int32_t reserved;
+} pt_fog;
+
+typedef struct pt_fog_stats {
+    double fog_ms;          /* device time inside fog_kernel (longest device) */
+    int32_t fog_launches;
+    int32_t reserved;
+    uint64_t shadow_rays;   /* light samples that reached the occlusion test */
+    uint64_t draws;         /* fog-stream draws */
+    uint64_t steps;         /* march steps taken (sigma_s > 0 and sigma_t > 0) */
+} pt_fog_stats;
+
+int32_t pt_set_fog(pt_ctx *ctx, const pt_fog *fog);
+int32_t pt_fog_last_stats(pt_ctx *ctx, pt_fog_stats *out);
 
 /*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the

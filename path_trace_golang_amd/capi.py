@@ -17,7 +17,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PTCORE_LIB") or os.path.join(PKG, "libptcore.so")  # PTCORE_LIB: another build of the same ABI (A/B runs)
 
-PT_ABI_VERSION = 3
+PT_ABI_VERSION = 4
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_ERR_NOMEM, PT_ERR_STATE = range(6)
 PT_MAT_LAMBERT, PT_MAT_METAL, PT_MAT_DIELECTRIC, PT_MAT_EMISSIVE, PT_MAT_MIRROR = range(5)
 PT_OBJ_UNKNOWN, PT_OBJ_SPHERE, PT_OBJ_PLANE, PT_OBJ_BOX, PT_OBJ_SPHERE_LIGHT = -1, 0, 1, 2, 3
@@ -62,6 +62,21 @@ class PtPostConfig(C.Structure):
                 ("smooth", C.c_int32), ("smooth_radius", C.c_int32), ("smooth_strength", C.c_double)]
 
 
+class PtFog(C.Structure):  # scene.Fog (internal/scene/scene.go:101-131), raw fields; resolved inside libptcore
+    _fields_ = [("density", C.c_double), ("color", _d3), ("scatter", C.c_double), ("sigma_s", C.c_double),
+                ("sigma_a", C.c_double), ("g", C.c_double), ("hetero_strength", C.c_double),
+                ("noise_scale", C.c_double), ("noise_octaves", C.c_int32), ("affect_sky", C.c_int32),
+                ("gpu_volumetric", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PtFogStats(C.Structure):
+    _fields_ = [("fog_ms", C.c_double), ("fog_launches", C.c_int32), ("reserved", C.c_int32),
+                ("shadow_rays", C.c_uint64), ("draws", C.c_uint64), ("steps", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class PtShard(C.Structure):
     _fields_ = [("index", C.c_int32), ("count", C.c_int32)]
 
@@ -103,6 +118,8 @@ SYMBOLS = [
     ("pt_untile_device", C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp,
                                       _vp]),
     ("pt_post_process", C.c_int32, [_vp, C.POINTER(PtPostConfig), _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32]),
+    ("pt_set_fog", C.c_int32, [_vp, C.POINTER(PtFog)]),
+    ("pt_fog_last_stats", C.c_int32, [_vp, C.POINTER(PtFogStats)]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),

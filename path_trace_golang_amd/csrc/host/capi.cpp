@@ -59,6 +59,15 @@ const pt_scene *pth_scene_flat(void *h) { return &static_cast<Handle *>(h)->flat
 
 int pth_scene_has_sky(void *h) { return static_cast<Handle *>(h)->sc->SkyPtr ? 1 : 0; }
 int pth_scene_has_fog(void *h) { return static_cast<Handle *>(h)->sc->FogPtr ? 1 : 0; }
+// The scene's fog block as pt_set_fog receives it; 0 when the scene has none.
+int pth_scene_fog(void *h, pt_fog *out) {
+    const auto &sc = *static_cast<Handle *>(h)->sc;
+    if (!sc.FogPtr) return 0;
+    pthost::engine::FlattenFog(*sc.FogPtr, *out);
+    return 1;
+}
+void pth_set_fog(int on) { pthost::engine::hip::SetFog(on != 0); }
+int pth_get_fog(void) { return pthost::engine::hip::GetFog() ? 1 : 0; }
 
 // scene.Save to a string; the pointer stays valid until the next call on the same handle
 const char *pth_scene_encode(void *h) {

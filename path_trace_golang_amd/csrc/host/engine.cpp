@@ -2,6 +2,7 @@
 
 #include <dlfcn.h>
 
+#include <cctype>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -57,12 +58,14 @@ struct Core {
     decltype(&pt_step) step = nullptr;
     decltype(&pt_read) read = nullptr;
     decltype(&pt_end) end = nullptr;
+    decltype(&pt_set_fog) set_fog = nullptr;
     std::string error;  // sticky load error, like the reference's cached GL init failure (gpu.go:279-286)
 };
 
 Core g_core;
 pt_ctx *g_ctx = nullptr;
 std::vector<int> g_devices;
+int g_fog = -1;  // -1: not set yet, PATHTRACER_GPU_FOG decides
 std::mutex g_mu;  // requests are serialised, like the reference's single GL worker (gpu.go:2534-2546)
 
 std::string self_dir() {
@@ -103,7 +106,7 @@ bool load_core() {
     if (!(sym(h, "pt_abi_version", c.abi_version, err) && sym(h, "pt_last_error", c.last_error, err) &&
           sym(h, "pt_create", c.create, err) && sym(h, "pt_destroy", c.destroy, err) && sym(h, "pt_render", c.render, err) &&
           sym(h, "pt_begin", c.begin, err) && sym(h, "pt_step", c.step, err) && sym(h, "pt_read", c.read, err) &&
-          sym(h, "pt_end", c.end, err))) {
+          sym(h, "pt_end", c.end, err) && sym(h, "pt_set_fog", c.set_fog, err))) {
         g_core.error = err;
         dlclose(h);
         return false;
@@ -141,6 +144,21 @@ void set3(double *d, const scene::Vec3 &v) { d[0] = v.X; d[1] = v.Y; d[2] = v.Z;
 void set3(double *d, const scene::Color &c) { d[0] = c.R; d[1] = c.G; d[2] = c.B; }
 
 }  // namespace
+
+void FlattenFog(const scene::Fog &f, pt_fog &out) {
+    std::memset(&out, 0, sizeof out);
+    out.density = f.Density;
+    set3(out.color, f.Col);
+    out.scatter = f.Scatter;
+    out.sigma_s = f.SigmaS;
+    out.sigma_a = f.SigmaA;
+    out.g = f.G;
+    out.hetero_strength = f.HeteroStrength;
+    out.noise_scale = f.NoiseScale;
+    out.noise_octaves = f.NoiseOctaves;
+    out.affect_sky = f.AffectSky ? 1 : 0;
+    out.gpu_volumetric = f.GPUVolumetric ? 1 : 0;
+}
 
 // Flattens scene.Scene into the C ABI's plain structs.  Exposed for tests through capi.cpp.
 void FlattenScene(const scene::Scene &sc, std::vector<pt_material> &materials, std::vector<pt_object> &objects,
@@ -204,6 +222,24 @@ void SetDevices(const std::vector<int> &ordinals) {
     g_devices = ordinals;
 }
 
+bool FogFromEnv() {
+    const char *e = std::getenv("PATHTRACER_GPU_FOG");
+    if (!e) return false;
+    std::string v(e);
+    for (char &ch : v) ch = (char)std::tolower((unsigned char)ch);
+    return v == "1" || v == "true" || v == "on" || v == "yes";
+}
+
+void SetFog(bool on) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_fog = on ? 1 : 0;
+}
+
+bool GetFog() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_fog < 0 ? FogFromEnv() : g_fog == 1;
+}
+
 void Shutdown() {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_ctx && g_core.handle) g_core.destroy(g_ctx);
@@ -223,6 +259,12 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     }
     Flat flat;
     FlattenScene(sc, flat.materials, flat.objects, flat.sc);
+    {  // the scene's fog block when asked for (SetFog / PATHTRACER_GPU_FOG), else off
+        const bool fog_on = (g_fog < 0 ? FogFromEnv() : g_fog == 1) && sc.FogPtr;
+        pt_fog fog;
+        if (fog_on) FlattenFog(*sc.FogPtr, fog);
+        if (g_core.set_fog(g_ctx, fog_on ? &fog : nullptr) != PT_OK) return std::string("pt_set_fog: ") + g_core.last_error();
+    }
     pt_config pc;
     std::memset(&pc, 0, sizeof pc);
     pc.width = cfg.Width;

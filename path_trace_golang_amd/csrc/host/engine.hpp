@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "../../../include/ptcore.h"
 #include "scene.hpp"
 
 namespace pthost {
@@ -41,8 +42,16 @@ namespace hip {
 std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, const std::function<void()> &progress,
                    Stats *stats = nullptr);
 void SetDevices(const std::vector<int> &ordinals);  // HIP ordinals used by Render (default: device 0)
+// Whether Render draws the scene's fog block (pt_set_fog; off by default, like the CPU engine, which ignores fog).  The
+// initial value is PATHTRACER_GPU_FOG (FogFromEnv).
+void SetFog(bool on);
+bool GetFog();
+bool FogFromEnv();  // PATHTRACER_GPU_FOG = 1 / true / on / yes
 void Shutdown();                                    // releases the process-wide context
 }  // namespace hip
+
+// scene.Fog flattened into the C ABI's pt_fog (raw fields; libptcore resolves them).
+void FlattenFog(const scene::Fog &f, pt_fog &out);
 
 // RenderInto (renderer.go:34-41).  BackendGPU goes to hip::Render.  The CPU branch is the reference's
 // own Go renderer and is not shipped: selecting it, or a GPU failure (where the reference falls back

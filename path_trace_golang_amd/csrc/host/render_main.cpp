@@ -7,7 +7,9 @@
 // util.go:25-42 hard-wire two presets): -width -height -spp -depth override the mode preset,
 // -seed selects the sample streams (also env PATHTRACER_SEED), -devices N uses N GPUs (0..N-1),
 // -scene-settings applies the editor's scene-settings override (internal/ui/app.go:60-75) before them;
-// without it scene.settings is ignored exactly as main.go:52 does.
+// without it scene.settings is ignored exactly as main.go:52 does.  -fog draws the scene's fog block the way the
+// reference's OpenGL backend does (sky blend, volumetric in-scatter; also env PATHTRACER_GPU_FOG=1); without it fog is
+// ignored like the CPU engine ignores it.
 #include <cerrno>
 #include <chrono>
 #include <cstdarg>
@@ -45,6 +47,7 @@ struct Flags {
     bool gpu = false;
     bool headless = false;
     bool scene_settings = false;
+    bool fog = false;
     std::string out = "output.png";
     int width = 0, height = 0, spp = -1, depth = -1, devices = 1;
     unsigned long long seed = 1;
@@ -55,6 +58,7 @@ void usage() {
                  "Usage of render:\n"
                  "  -depth int\n    \tmax path depth (default: the mode preset)\n"
                  "  -devices int\n    \tnumber of GPUs to tile the image over (default 1)\n"
+                 "  -fog\n    \tdraw the scene's fog block like the reference's GPU backend (default false, or PATHTRACER_GPU_FOG)\n"
                  "  -gpu\n    \tuse GPU backend for rendering (if available)\n"
                  "  -headless\n    \trender without UI and save PNG\n"
                  "  -height int\n    \timage height (default: the mode preset)\n"
@@ -87,14 +91,14 @@ int parse(int argc, char **argv, Flags &f) {
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         if (name == "h" || name == "help") { usage(); return 0; }
-        if (name == "gpu" || name == "headless" || name == "scene-settings") {
+        if (name == "gpu" || name == "headless" || name == "scene-settings" || name == "fog") {
             bool b = true;
             if (has_val && !parse_bool(val, b)) {
                 std::fprintf(stderr, "invalid boolean value \"%s\" for -%s: parse error\n", val.c_str(), name.c_str());
                 usage();
                 return 2;
             }
-            (name == "gpu" ? f.gpu : name == "headless" ? f.headless : f.scene_settings) = b;
+            (name == "gpu" ? f.gpu : name == "headless" ? f.headless : name == "fog" ? f.fog : f.scene_settings) = b;
             continue;
         }
         static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices"};
@@ -151,6 +155,8 @@ int render_headless(const Flags &f) {
     if (f.height > 0) s.Height = f.height;
     if (f.spp >= 0) s.SamplesPerPx = f.spp;
     if (f.depth >= 0) s.MaxDepth = f.depth;
+    engine::hip::SetFog(f.fog);
+    if (f.fog) logf("fog: drawing the scene's fog block (%s)", sc->FogPtr ? "present" : "absent: nothing to draw");
     try {
         if (f.devices > 1) {
             std::vector<int> ords;
@@ -183,6 +189,7 @@ int main(int argc, char **argv) {
     logf("pathtracer: starting main()");
     Flags f;
     if (const char *e = std::getenv("PATHTRACER_SEED")) f.seed = std::strtoull(e, nullptr, 10);
+    f.fog = engine::hip::FogFromEnv();
     int rc = parse(argc, argv, f);
     if (rc >= 0) return rc;
     logf("flags: scene=%s mode=%s headless=%s out=%s", f.scene.c_str(), f.mode.c_str(), f.headless ? "true" : "false",

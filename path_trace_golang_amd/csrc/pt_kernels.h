@@ -35,6 +35,8 @@
 //                   to the running sum (renderer.go:186), and on request finishes the
 //                   pixel: 1/spp, sqrt gamma, *255.999, clamp, truncate (renderer.go:190-221).
 //   untile_kernel   tile-major -> row-major frame.
+//   fog_kernel      opt-in (pt_set_fog): the fog's in-scatter term of every job (pt_fog.h), added into its radiance record
+//                   between a chunk's last trace pass and resolve_kernel.
 //
 // FP64 throughout; built with -ffp-contract=off so every product and sum rounds
 // exactly as the reference's Go code does on amd64.
@@ -43,6 +45,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_device.h"
+#include "pt_fog.h"
 #include "pt_math.h"
 
 namespace ptk {
@@ -2989,6 +2992,61 @@ __global__ __launch_bounds__(PT_BLOCK) void post_smooth_kernel(const uint8_t *__
         out |= ((uint32_t)(o + 0.5) & 0xffu) << (8 * c);
     }
     reinterpret_cast<uint32_t *>(dst)[i] = out;
+}
+
+// The fog's in-scatter term (pt_fog.h) of every job of a chunk, added in place to the job's radiance record after the chunk's
+// last trace pass and before resolve_kernel: L = L_path + L_fog, one add per channel, path first.  One lane per job; the
+// primary ray is read back from the ray-generation buffers, which no trace form writes.  Every loop of the term -- the 24
+// march steps, the lights, the objects -- has a wave-uniform trip count, so objects, lights and the parameters come in by
+// scalar loads and the lanes never diverge per object; a shadow ray's object loop is left by ballot once every active lane is
+// occluded.
+struct FogArgs {
+    ptf::FogParams P;
+    const DevObj *objs;
+    const ptf::FogLight *lights;
+    const double *ray;                // [6][njobs]
+    const uint16_t *ray_ndraw;        // 0xffff: pixel outside the frame
+    double *L;                        // [njobs][4]
+    unsigned long long *counters;     // [3]: shadow rays, draws, march steps
+    uint64_t fog_key;                 // ptm::seed_key(seed ^ PTF_STREAM_SALT)
+    int32_t nobj, nlight;
+    uint32_t njobs, S, s0;
+    int32_t width, height, ntx, shard_index, shard_count;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void fog_kernel(const FogArgs A) {
+    const uint32_t job = blockIdx.x * PT_BLOCK + threadIdx.x;
+    ptf::FogCount cnt = {0u, 0u, 0u};
+    if (job < A.njobs && A.ray_ndraw[job] != 0xffffu) {
+        // job -> (tile, sub-block, sample, pixel) as in raygen_kernel
+        const uint32_t p = job & 63u;
+        const uint32_t q = job >> 6;
+        const uint32_t blk = q / A.S;
+        const uint32_t sl = q - blk * A.S;
+        const uint32_t lt = blk >> 4, sb = blk & 15u;
+        const uint32_t t = (uint32_t)A.shard_index + lt * (uint32_t)A.shard_count;
+        const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
+        const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
+        const uint32_t y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+        const size_t nj = A.njobs;
+        const double o[3] = {A.ray[job], A.ray[nj + job], A.ray[2 * nj + job]};
+        const double d[3] = {A.ray[3 * nj + job], A.ray[4 * nj + job], A.ray[5 * nj + job]};
+        const uint64_t rs = ptm::stream_init(A.fog_key, (uint64_t)y * (uint64_t)(uint32_t)A.width + x, (uint64_t)(A.s0 + sl));
+        double f[3];
+        ptf::fog_inscatter(A.P, A.objs, A.nobj, A.lights, A.nlight, o, d, rs, cnt, f);
+        double4 *rec = reinterpret_cast<double4 *>(A.L) + job;
+        double4 l = *rec;
+        l.x = l.x + f[0];
+        l.y = l.y + f[1];
+        l.z = l.z + f[2];
+        *rec = l;
+    }
+    const uint32_t sr = wave_sum(cnt.shadow_rays), dr = wave_sum(cnt.draws), st = wave_sum(cnt.steps);
+    if ((threadIdx.x & 63u) == 0u && (sr | dr | st) != 0u) {
+        atomicAdd(A.counters + 0, (unsigned long long)sr);
+        atomicAdd(A.counters + 1, (unsigned long long)dr);
+        atomicAdd(A.counters + 2, (unsigned long long)st);
+    }
 }
 
 }  // namespace ptk

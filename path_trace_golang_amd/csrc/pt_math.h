@@ -127,6 +127,20 @@ PT_HD void sincos_pos(double x, double *s, double *c) {
     *c = csign ? -cv : cv;
 }
 
+// math.Sin for the signed range |x| < 2^29, on sincos_pos (the fog's hash, pt_fog.h).  Go switches to its Payne-Hanek
+// reduction at 2^29; that branch is not restated: larger arguments, infinities and NaN return NaN, which the callers
+// test for before they get here.
+PT_HD double go_sin(double x) {
+    if (x == 0 || is_nan(x)) return x;  // +-0 keep their sign
+    if (is_inf(x)) return qnan();
+    const bool neg = x < 0;
+    if (neg) x = -x;
+    if (x >= 536870912.0) return qnan();
+    double s, c;
+    sincos_pos(x, &s, &c);
+    return neg ? -s : s;
+}
+
 // math.Tan for 0 < x < 2^29 (camera set-up, host side).
 PT_HD double tan_pos(double x) {
     uint64_t j = (uint64_t)(x * PTM_4_OVER_PI);

@@ -119,8 +119,10 @@ struct Device {
     size_t q_cap = 0;
     DevBuf<unsigned long long> counters;
     DevBuf<unsigned long long> prof;
-    std::vector<EventPair> ev_trace, ev_resolve, ev_raygen, ev_glass;
-    size_t n_trace = 0, n_resolve = 0, n_raygen = 0, n_glass = 0;
+    std::vector<EventPair> ev_trace, ev_resolve, ev_raygen, ev_glass, ev_fog;
+    size_t n_trace = 0, n_resolve = 0, n_raygen = 0, n_glass = 0, n_fog = 0;
+    DevBuf<ptf::FogLight> fog_lights;        // the frame's light list (fog on)
+    DevBuf<unsigned long long> fog_counters; // [3] shadow rays, draws, march steps of the frame
     std::vector<char> trace_is_split;  // per trace launch of the frame: the split form?
     hipEvent_t ev_first = nullptr, ev_last = nullptr;
     bool first_recorded = false;
@@ -156,6 +158,9 @@ struct Frame {
     bool has_glass = false;  // some object is dielectric
     bool primary_pass = false;  // BVH scans: the first segment of every path by primary_bvh_kernel (pt_primary.h), the rest through the continuation queue
     int scan = 0;  // ptk::SCAN_* used for this frame
+    bool fog_vol = false;  // fog_kernel runs after every chunk (pt_set_fog with gpu_volumetric, max_depth > 0)
+    ptf::FogParams fog{};
+    std::vector<ptf::FogLight> fog_lights;
     std::chrono::steady_clock::time_point t0;
 };
 
@@ -235,6 +240,11 @@ struct pt_ctx {
     unsigned long long last_mismatches = 0;
     bool profile_sections = false;  // PTCORE_PROFILE=1: diagnostic kernel build with per-section counters
     unsigned long long last_profile[3 * ptk::SEC_COUNT] = {};
+    // fog (pt_set_fog): off by default; the raw block as given
+    bool fog_on = false;
+    pt_fog fog_raw{};
+    pt_fog_stats fog_last{};
+    int fog_pending = 0;  // the last frame's fog counters are still on the device: 1 = every device, 2 = devs[0] only
 };
 
 namespace {
@@ -635,7 +645,7 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     d.nlocal = tiles_of_shard(fr.ntx * fr.nty, shard);
     d.nslots = (uint32_t)d.nlocal * 1024u;
     d.acc_started = false;
-    d.n_trace = d.n_resolve = d.n_raygen = d.n_glass = 0;
+    d.n_trace = d.n_resolve = d.n_raygen = d.n_glass = d.n_fog = 0;
     d.first_recorded = false;
     std::memset(d.pass_log_prev, 0, sizeof d.pass_log_prev);  // the device counters are cleared below, once per frame
     if (d.scene_gen != sd.gen) {
@@ -674,6 +684,14 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     HIP_TRY(d.queue.reserve(8));
     HIP_TRY(d.counters.reserve(48));
     HIP_TRY(hipMemsetAsync(d.counters.p, 0, 48 * sizeof(unsigned long long), d.stream));
+    if (fr.fog_vol) {
+        HIP_TRY(d.fog_counters.reserve(3));
+        HIP_TRY(hipMemsetAsync(d.fog_counters.p, 0, 3 * sizeof(unsigned long long), d.stream));
+        HIP_TRY(d.fog_lights.reserve(std::max<size_t>(1, fr.fog_lights.size())));
+        if (!fr.fog_lights.empty())  // (pageable source: the copy is complete when the call returns)
+            HIP_TRY(hipMemcpyAsync(d.fog_lights.p, fr.fog_lights.data(), fr.fog_lights.size() * sizeof(ptf::FogLight), hipMemcpyHostToDevice,
+                                   d.stream));
+    }
     if (ctx->profile_sections) {
         HIP_TRY(d.prof.reserve(3 * ptk::SEC_COUNT));
         HIP_TRY(hipMemsetAsync(d.prof.p, 0, 3 * ptk::SEC_COUNT * sizeof(unsigned long long), d.stream));
@@ -1209,6 +1227,34 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         }
         }
     }
+    if (fr.fog_vol) {  // the fog's in-scatter term into the chunk's radiance records (pt_fog.h)
+        if (int32_t rc = dev_events(d, d.ev_fog, d.n_fog + 1)) return rc;
+        ptk::FogArgs FA;
+        std::memset(&FA, 0, sizeof FA);
+        FA.P = fr.fog;
+        FA.objs = d.objs.p;
+        FA.lights = d.fog_lights.p;
+        FA.ray = d.ray.p;
+        FA.ray_ndraw = d.ray_ndraw.p;
+        FA.L = d.L.p;
+        FA.counters = d.fog_counters.p;
+        FA.fog_key = ptm::seed_key(fr.cfg.seed ^ PTF_STREAM_SALT);
+        FA.nobj = fr.nobj;
+        FA.nlight = (int32_t)fr.fog_lights.size();
+        FA.njobs = F.njobs;
+        FA.S = S;
+        FA.s0 = s0;
+        FA.width = fr.cfg.width;
+        FA.height = fr.cfg.height;
+        FA.ntx = fr.ntx;
+        FA.shard_index = d.shard.index;
+        FA.shard_count = d.shard.count;
+        EventPair &ef = d.ev_fog[d.n_fog++];
+        HIP_TRY(hipEventRecord(ef.a, d.stream));
+        hipLaunchKernelGGL(ptk::fog_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ef.b, d.stream));
+    }
     ptk::ResolveArgs R;
     std::memset(&R, 0, sizeof R);
     R.L = d.L.p;
@@ -1527,6 +1573,8 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
     Frame &fr = ctx->frame;
     fr = Frame();
     fr.cfg = *cfg;
+    std::memset(&ctx->fog_last, 0, sizeof ctx->fog_last);
+    ctx->fog_pending = 0;
     fr.nobj = sd.Fs.nobj;
     fr.nmat = sd.Fs.nmat;
     fr.scan = sd.scan;
@@ -1553,7 +1601,24 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
         fr.shade_lds_bytes = (size_t)sd.Fs.nmat * sizeof(DevMat) + (sd.Fs.world_in_lds ? (size_t)sd.Fs.nobj * sizeof(DevObj) : 0);
     }
     fr.cam = new_camera(scene->camera, cfg->width, cfg->height);
-    fr.sky = make_sky(scene->sky);
+    {
+        pt_sky sky = scene->sky;
+        if (ctx->fog_on) {
+            fr.fog = ptf::fog_resolve(ctx->fog_raw);
+            if (fr.fog.volumetric && (sd.scan == ptk::SCAN_BVH || sd.scan == ptk::SCAN_VERIFY_BVH))
+                return fail(PT_ERR_INVALID, "fog: gpu_volumetric is not available for scenes on the BVH path (more than 128 spheres or "
+                                            "128 boxes); affect_sky alone is");
+            if (ptf::fog_sky_applies(fr.fog))  // applyFog(bg, 50), gpu.go:1392-1393, as a rewrite of the sky constants
+                for (double *c : {sky.background, sky.color, sky.horizon, sky.zenith}) ptf::fog_sky_rewrite(fr.fog, c);
+            fr.fog_vol = ptf::fog_volumetric(fr.fog, cfg->max_depth);
+            if (fr.fog_vol)  // the emissive spheres, in object order
+                for (int32_t i = 0; i < scene->num_objects; i++) {
+                    ptf::FogLight l;
+                    if (ptf::fog_light_of(*scene, i, l)) fr.fog_lights.push_back(l);
+                }
+        }
+        fr.sky = make_sky(sky);
+    }
     fr.ntx = (cfg->width + 31) / 32;
     fr.nty = (cfg->height + 31) / 32;
     fr.stats_on = (cfg->flags & PT_FLAG_PIXEL_STATS) != 0;
@@ -1596,6 +1661,36 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
     fr.done_spp = 0;
     fr.t0 = std::chrono::steady_clock::now();
     fr.open = true;
+    return PT_OK;
+}
+
+// Reads the fog counters and fog_kernel times of the last frame into ctx->fog_last (waits for the devices' streams).
+int32_t collect_fog(pt_ctx *ctx) {
+    if (!ctx->fog_pending) return PT_OK;
+    const bool first_only = ctx->fog_pending == 2;
+    ctx->fog_pending = 0;
+    pt_fog_stats fs;
+    std::memset(&fs, 0, sizeof fs);
+    for (size_t i = 0; i < ctx->devs.size() && !(first_only && i > 0); i++) {
+        Device &d = ctx->devs[i];
+        if (d.n_fog == 0) continue;
+        HIP_TRY(hipSetDevice(d.ordinal));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        unsigned long long c[3] = {};
+        HIP_TRY(hipMemcpy(c, d.fog_counters.p, sizeof c, hipMemcpyDeviceToHost));
+        fs.shadow_rays += c[0];
+        fs.draws += c[1];
+        fs.steps += c[2];
+        double ms = 0;
+        for (size_t k = 0; k < d.n_fog; k++) {
+            float m = 0;
+            HIP_TRY(hipEventElapsedTime(&m, d.ev_fog[k].a, d.ev_fog[k].b));
+            ms += m;
+        }
+        fs.fog_ms = std::max(fs.fog_ms, ms);
+        fs.fog_launches += (int32_t)d.n_fog;
+    }
+    ctx->fog_last = fs;
     return PT_OK;
 }
 
@@ -1658,6 +1753,22 @@ int32_t rccl_open(pt_ctx *ctx) {
 extern "C" {
 
 int32_t pt_abi_version(void) { return PT_ABI_VERSION; }
+
+int32_t pt_set_fog(pt_ctx *ctx, const pt_fog *fog) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_fog while a frame is open");
+    ctx->fog_on = fog != nullptr;
+    if (fog) ctx->fog_raw = *fog;
+    else std::memset(&ctx->fog_raw, 0, sizeof ctx->fog_raw);
+    return PT_OK;
+}
+
+int32_t pt_fog_last_stats(pt_ctx *ctx, pt_fog_stats *out) {
+    if (!ctx || !out) return fail(PT_ERR_INVALID, "null argument");
+    if (int32_t rc = collect_fog(ctx)) return rc;
+    *out = ctx->fog_last;
+    return PT_OK;
+}
 
 const char *pt_last_error(void) { return g_last_error.c_str(); }
 
@@ -1779,6 +1890,8 @@ void pt_destroy(pt_ctx *ctx) {
         for (EventPair &e : d.ev_trace) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (EventPair &e : d.ev_resolve) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (EventPair &e : d.ev_raygen) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+        for (EventPair &e : d.ev_fog) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+        d.fog_lights.release(); d.fog_counters.release();
         if (d.ev_first) (void)hipEventDestroy(d.ev_first);
         if (d.ev_last) (void)hipEventDestroy(d.ev_last);
         if (d.own_stream) (void)hipStreamDestroy(d.own_stream);
@@ -2154,6 +2267,10 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
     }
     fill_stats_common(ctx, &st);
     ctx->frame.open = false;
+    if (ctx->frame.fog_vol) {
+        ctx->fog_pending = 1;
+        if (int32_t r = collect_fog(ctx)) rc = rc != PT_OK ? rc : r;
+    }
     if (stats) *stats = st;
     return rc;
 }
@@ -2206,10 +2323,12 @@ int32_t pt_render_tiles_device(pt_ctx *ctx, const pt_scene *scene, const pt_conf
     if (rc == PT_OK)
         rc = dev_finish(ctx, d, cfg->samples_per_px, static_cast<uint8_t *>(d_tiles_rgba), static_cast<double *>(d_tiles_accum),
                         nullptr, nullptr);
+    if (rc == PT_OK && fr.fog_vol) ctx->fog_pending = 2;  // collected now with stats, else when pt_fog_last_stats asks
     if (rc == PT_OK && stats) {
         pt_stats st;
         std::memset(&st, 0, sizeof st);
         rc = dev_collect(d, &st, 0);
+        if (rc == PT_OK) rc = collect_fog(ctx);
         fill_stats_common(ctx, &st);
         st.num_devices = 1;
         *stats = st;

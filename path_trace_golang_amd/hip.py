@@ -89,6 +89,40 @@ class FlatScene:
         self.c = s
 
 
+def pt_fog(fog: scn.Fog) -> capi.PtFog:
+    """scene.Fog flattened into the C ABI's pt_fog: the raw fields, resolved inside libptcore (gpu.go:2024-2096)."""
+    f = capi.PtFog()
+    f.density = fog.density
+    f.color[:] = fog.color.as_list()
+    f.scatter = fog.scatter
+    f.sigma_s = fog.sigma_s
+    f.sigma_a = fog.sigma_a
+    f.g = fog.g
+    f.hetero_strength = fog.hetero_strength
+    f.noise_scale = fog.noise_scale
+    f.noise_octaves = int(fog.noise_octaves)
+    f.affect_sky = 1 if fog.affect_sky else 0
+    f.gpu_volumetric = 1 if fog.gpu_volumetric else 0
+    return f
+
+
+def set_fog(ctx: capi.Context, fog: Optional[scn.Fog]) -> None:
+    """pt_set_fog: `fog` for the later renders on ctx, None = off."""
+    L = capi.load()
+    if fog is None:
+        capi.check(L.pt_set_fog(ctx.handle, None))
+    else:
+        f = pt_fog(fog)
+        capi.check(L.pt_set_fog(ctx.handle, C.byref(f)))
+
+
+def fog_last_stats(ctx: Optional[capi.Context] = None) -> dict:
+    """pt_fog_last_stats of ctx: fog_ms, fog_launches, shadow_rays, draws, steps of its last frame."""
+    st = capi.PtFogStats()
+    capi.check(capi.load().pt_fog_last_stats((ctx or context()).handle, C.byref(st)))
+    return st.as_dict()
+
+
 def pt_config(cfg: RenderConfig) -> capi.PtConfig:
     return capi.PtConfig(cfg.width, cfg.height, cfg.samples_per_px, cfg.max_depth, cfg.seed & 0xFFFFFFFFFFFFFFFF,
                          cfg.spp_chunk, cfg.flags)
@@ -120,8 +154,12 @@ def _ptr(a: Optional[np.ndarray]):
 
 def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[], None]] = None,
            accum: Optional[np.ndarray] = None, nseg: Optional[np.ndarray] = None,
-           ndraw: Optional[np.ndarray] = None, ctx: Optional[capi.Context] = None) -> dict:
+           ndraw: Optional[np.ndarray] = None, ctx: Optional[capi.Context] = None, fog: bool = False) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
+
+    With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
+    draws it (sky blend, volumetric in-scatter; pt_set_fog in include/ptcore.h); otherwise fog is off for the call, which
+    is the CPU engine's image.  (A FlatScene carries no fog block: pass the Scene.)
 
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
@@ -137,6 +175,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     if img.strides[2] != 1 or img.strides[1] != 4:
         raise ValueError("img rows must be contiguous RGBA")
     flat = sc if isinstance(sc, FlatScene) else FlatScene(sc)  # callers that render one scene repeatedly flatten it once
+    set_fog(ctx, getattr(sc, "fog", None) if fog else None)
     pc = pt_config(cfg)
     st = capi.PtStats()
     if accum is not None and (accum.dtype != np.float64 or accum.shape != (cfg.height, cfg.width, 3)
@@ -211,6 +250,20 @@ class PostConfig:
         except (KeyError, ValueError):
             pass
         return cfg
+
+
+@dataclass
+class FogConfig:
+    """Whether `render` draws the scene's fog block (off by default: the CPU engine ignores fog)."""
+    enabled: bool = False
+
+    @classmethod
+    def from_env(cls, environ=None) -> "FogConfig":
+        """PATHTRACER_GPU_FOG=1 (or true / on / yes) turns it on, like the PATHTRACER_GPU_* switches of PostConfig."""
+        import os
+
+        env = os.environ if environ is None else environ
+        return cls(enabled=env.get("PATHTRACER_GPU_FOG", "").lower() in ("1", "true", "on", "yes"))
 
 
 def post_process(img: np.ndarray, post: PostConfig, accum: Optional[np.ndarray] = None, samples_per_px: int = 1,
