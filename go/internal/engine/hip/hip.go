@@ -26,6 +26,7 @@ import (
 	"os"
 	"runtime"
 	"strconv"
+	"strings"
 	"sync"
 	"unsafe"
 
@@ -231,6 +232,40 @@ func setFog(sc *scene.Scene) error {
 	return nil
 }
 
+// glShading: PATHTRACER_GPU_SHADING=gl (any case) renders with the GL backend's estimator (gpu.go:1300-1732) instead of
+// the CPU engine's; a "sample" is then a pass of 16 paths and the image is the GL finish (DESIGN 3.8).
+func glShading() bool {
+	return strings.EqualFold(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_SHADING")), "gl")
+}
+
+// setShading selects the context's shading model (pt_set_shading).  For GL shading it hands over the per-material fields
+// only that model reads; the table is copied by the call.
+func setShading(sc *scene.Scene) error {
+	if !glShading() {
+		if rc := C.pt_set_shading(ctx, nil); rc != C.PT_OK {
+			return lastError("pt_set_shading")
+		}
+		return nil
+	}
+	n := len(sc.Materials)
+	var tab *C.pt_gl_material
+	if n > 0 {
+		tab = (*C.pt_gl_material)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.pt_gl_material{}))))
+		defer C.free(unsafe.Pointer(tab))
+		gm := unsafe.Slice(tab, n)
+		for i, m := range sc.Materials {
+			gm[i].reflectivity = C.double(m.Reflectivity)
+			set3(&gm[i].tint, m.Tint.R, m.Tint.G, m.Tint.B)
+			gm[i].absorption_scale = C.double(m.AbsorptionScale)
+		}
+	}
+	s := C.pt_shading{model: C.PT_SHADING_GL, num_materials: C.int32_t(n), materials: tab}
+	if rc := C.pt_set_shading(ctx, &s); rc != C.PT_OK {
+		return lastError("pt_set_shading")
+	}
+	return nil
+}
+
 // Render renders sc into img on the MI355X and calls progress() every ~10% of the samples and once
 // at the end (the cadence of gpu.go:2209-2212, :2229, :2523-2525).  On any error the caller
 // (engine.renderIntoGPU) falls back to the CPU renderer exactly as it does for the GL backend.
@@ -256,6 +291,9 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 	cs, free := flatten(sc)
 	defer free()
 	if err := setFog(sc); err != nil {
+		return err
+	}
+	if err := setShading(sc); err != nil {
 		return err
 	}
 	pc := C.pt_config{width: C.int32_t(cfg.Width), height: C.int32_t(cfg.Height),

@@ -301,6 +301,50 @@ int32_t pt_set_fog(pt_ctx *ctx, const pt_fog *fog);
 int32_t pt_fog_last_stats(pt_ctx *ctx, pt_fog_stats *out);
 
 /*
+ * GL shading (additive to ABI 4): the estimator of the reference's OpenGL compute shader (rayColor and main,
+ * internal/engine/gpu/gpu.go:1300-1732) as a second shading model, restated in FP64 in csrc/pt_glshade.h:
+ * next-event estimation over the emissive objects, GGX rough metals, smoothness / reflectivity, glass tint and absorption,
+ * 16 stratified paths per pass.  Not the CPU engine's image, so it is off unless asked for.
+ *   pt_set_shading(ctx, &s) : later renders on ctx (every entry point) use model s.model; NULL = PT_SHADING_CPU (the default).
+ *                             The block and its material table are copied.
+ *   pt_shading_last_stats   : what the GL kernel did in the last finished frame of ctx (zeros when it did not run).
+ * In GL mode a "sample" is a pass: spp, spp_chunk and pt_step count passes.  A pass adds its 16 paths WITHOUT dividing by
+ * 16 (the shader as its host drives it), so accum / passes is GL's linear value, and the 8-bit image is the tone-mapped
+ * finish of pt_post_process(tonemap = 1) on accum.  pt_stats.samples, segments and draws count GL paths, closest-hit scans
+ * and draws; trace_ms is the GL kernel's time.  A GL render returns PT_ERR_INVALID without launching anything when the
+ * scene's material count differs from num_materials, with PT_FLAG_PIXEL_STATS, and for scenes on the bounding-volume-
+ * hierarchy path (more than 128 spheres or 128 boxes).
+ */
+enum { PT_SHADING_CPU = 0, PT_SHADING_GL = 1 };
+
+/* scene.Material fields only the GL model reads (scene.go:41-63), one entry per scene material, raw */
+typedef struct pt_gl_material {
+    double reflectivity;
+    double tint[3];
+    double absorption_scale;
+} pt_gl_material;
+
+typedef struct pt_shading {
+    int32_t model;         /* PT_SHADING_* */
+    int32_t num_materials; /* entries of `materials` (GL model) */
+    const pt_gl_material *materials;
+} pt_shading;
+
+typedef struct pt_shading_stats {
+    double gl_ms;          /* device time inside gl_trace_kernel (longest device) */
+    int32_t gl_launches;
+    int32_t reserved;
+    uint64_t paths;        /* GL paths traced (16 per pixel and pass) */
+    uint64_t segments;     /* closest-hit scans of the main loop */
+    uint64_t shadow_rays;  /* NEE shadow rays traced (after the distance and cosine tests) */
+    uint64_t probe_rays;   /* rough-metal reflect-direction probes */
+    uint64_t draws;        /* main-stream draws (the fog stream's are in pt_fog_stats) */
+} pt_shading_stats;
+
+int32_t pt_set_shading(pt_ctx *ctx, const pt_shading *s);
+int32_t pt_shading_last_stats(pt_ctx *ctx, pt_shading_stats *out);
+
+/*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the
  * environment at pt_create, the trace kernel runs a build that counts, per code
  * section, wave executions, active lanes and shader-clock cycles.  Copies up to n

@@ -77,6 +77,25 @@ class PtFogStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class PtGlMaterial(C.Structure):  # scene.Material fields only GL shading reads (scene.go:41-63), raw
+    _fields_ = [("reflectivity", C.c_double), ("tint", _d3), ("absorption_scale", C.c_double)]
+
+
+class PtShading(C.Structure):
+    _fields_ = [("model", C.c_int32), ("num_materials", C.c_int32), ("materials", C.POINTER(PtGlMaterial))]
+
+
+class PtShadingStats(C.Structure):
+    _fields_ = [("gl_ms", C.c_double), ("gl_launches", C.c_int32), ("reserved", C.c_int32), ("paths", C.c_uint64),
+                ("segments", C.c_uint64), ("shadow_rays", C.c_uint64), ("probe_rays", C.c_uint64), ("draws", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+PT_SHADING_CPU, PT_SHADING_GL = 0, 1
+
+
 class PtShard(C.Structure):
     _fields_ = [("index", C.c_int32), ("count", C.c_int32)]
 
@@ -120,6 +139,8 @@ SYMBOLS = [
     ("pt_post_process", C.c_int32, [_vp, C.POINTER(PtPostConfig), _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32]),
     ("pt_set_fog", C.c_int32, [_vp, C.POINTER(PtFog)]),
     ("pt_fog_last_stats", C.c_int32, [_vp, C.POINTER(PtFogStats)]),
+    ("pt_set_shading", C.c_int32, [_vp, C.POINTER(PtShading)]),          # additive to ABI 4 (see has())
+    ("pt_shading_last_stats", C.c_int32, [_vp, C.POINTER(PtShadingStats)]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
@@ -146,13 +167,25 @@ def load():
                               "(there is no fallback renderer)" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for name, res, args in SYMBOLS:
-            f = getattr(L, name)  # AttributeError if the symbol is not exported
+            f = getattr(L, name, None)
+            if f is None:
+                if name in ADDITIVE:  # a library from before these entry points (PTCORE_LIB A/B runs): has() says no
+                    continue
+                getattr(L, name)  # AttributeError: the symbol is not exported
             f.restype = res
             f.argtypes = args
         if L.pt_abi_version() != PT_ABI_VERSION:
             raise ImportError("libptcore.so ABI %d != binding %d" % (L.pt_abi_version(), PT_ABI_VERSION))
         _lib = L
     return _lib
+
+
+ADDITIVE = ("pt_set_shading", "pt_shading_last_stats")  # added within ABI 4: detected by presence
+
+
+def has(name: str) -> bool:
+    """Does the loaded libptcore.so export `name` (the ADDITIVE entry points may be missing from an older build)?"""
+    return getattr(load(), name, None) is not None
 
 
 def check(rc: int) -> None:

@@ -68,6 +68,15 @@ int pth_scene_fog(void *h, pt_fog *out) {
 }
 void pth_set_fog(int on) { pthost::engine::hip::SetFog(on != 0); }
 int pth_get_fog(void) { return pthost::engine::hip::GetFog() ? 1 : 0; }
+void pth_set_shading(int model) { pthost::engine::hip::SetShading(model); }
+int pth_get_shading(void) { return pthost::engine::hip::GetShading(); }
+// The scene's pt_gl_material table; returns the entry count, writes at most `cap` entries.
+int pth_scene_gl_materials(void *h, pt_gl_material *out, int cap) {
+    std::vector<pt_gl_material> v;
+    pthost::engine::FlattenGlMaterials(*static_cast<Handle *>(h)->sc, v);
+    for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = v[(size_t)i];
+    return (int)v.size();
+}
 
 // scene.Save to a string; the pointer stays valid until the next call on the same handle
 const char *pth_scene_encode(void *h) {

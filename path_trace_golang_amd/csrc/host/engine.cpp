@@ -59,6 +59,7 @@ struct Core {
     decltype(&pt_read) read = nullptr;
     decltype(&pt_end) end = nullptr;
     decltype(&pt_set_fog) set_fog = nullptr;
+    decltype(&pt_set_shading) set_shading = nullptr;  // optional (additive to ABI 4): null in an older build
     std::string error;  // sticky load error, like the reference's cached GL init failure (gpu.go:279-286)
 };
 
@@ -66,6 +67,7 @@ Core g_core;
 pt_ctx *g_ctx = nullptr;
 std::vector<int> g_devices;
 int g_fog = -1;  // -1: not set yet, PATHTRACER_GPU_FOG decides
+int g_shading = -1;  // -1: not set yet, PATHTRACER_GPU_SHADING decides; else PT_SHADING_*
 std::mutex g_mu;  // requests are serialised, like the reference's single GL worker (gpu.go:2534-2546)
 
 std::string self_dir() {
@@ -111,6 +113,7 @@ bool load_core() {
         dlclose(h);
         return false;
     }
+    c.set_shading = reinterpret_cast<decltype(c.set_shading)>(dlsym(h, "pt_set_shading"));
     if (c.abi_version() != PT_ABI_VERSION) {
         g_core.error = "libptcore.so ABI version mismatch";
         dlclose(h);
@@ -144,6 +147,17 @@ void set3(double *d, const scene::Vec3 &v) { d[0] = v.X; d[1] = v.Y; d[2] = v.Z;
 void set3(double *d, const scene::Color &c) { d[0] = c.R; d[1] = c.G; d[2] = c.B; }
 
 }  // namespace
+
+void FlattenGlMaterials(const scene::Scene &sc, std::vector<pt_gl_material> &out) {
+    out.clear();
+    for (const scene::Material &m : sc.Materials) {
+        pt_gl_material g;
+        g.reflectivity = m.Reflectivity;
+        set3(g.tint, m.Tint);
+        g.absorption_scale = m.AbsorptionScale;
+        out.push_back(g);
+    }
+}
 
 void FlattenFog(const scene::Fog &f, pt_fog &out) {
     std::memset(&out, 0, sizeof out);
@@ -222,6 +236,24 @@ void SetDevices(const std::vector<int> &ordinals) {
     g_devices = ordinals;
 }
 
+int ShadingFromEnv() {
+    const char *e = std::getenv("PATHTRACER_GPU_SHADING");
+    if (!e) return PT_SHADING_CPU;
+    std::string v(e);
+    for (char &ch : v) ch = (char)std::tolower((unsigned char)ch);
+    return v == "gl" ? PT_SHADING_GL : PT_SHADING_CPU;
+}
+
+void SetShading(int model) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_shading = model == PT_SHADING_GL ? PT_SHADING_GL : PT_SHADING_CPU;
+}
+
+int GetShading() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_shading < 0 ? ShadingFromEnv() : g_shading;
+}
+
 bool FogFromEnv() {
     const char *e = std::getenv("PATHTRACER_GPU_FOG");
     if (!e) return false;
@@ -264,6 +296,23 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         pt_fog fog;
         if (fog_on) FlattenFog(*sc.FogPtr, fog);
         if (g_core.set_fog(g_ctx, fog_on ? &fog : nullptr) != PT_OK) return std::string("pt_set_fog: ") + g_core.last_error();
+    }
+    std::vector<pt_gl_material> gl_mats;
+    {  // the shading model (SetShading / PATHTRACER_GPU_SHADING): the CPU engine unless GL is asked for
+        const int model = g_shading < 0 ? ShadingFromEnv() : g_shading;
+        if (model == PT_SHADING_GL && !g_core.set_shading) return "GL shading: libptcore.so lacks pt_set_shading";
+        if (g_core.set_shading) {
+            pt_shading sh;
+            std::memset(&sh, 0, sizeof sh);
+            sh.model = model;
+            if (model == PT_SHADING_GL) {
+                FlattenGlMaterials(sc, gl_mats);
+                sh.num_materials = (int32_t)gl_mats.size();
+                sh.materials = gl_mats.data();
+            }
+            if (g_core.set_shading(g_ctx, model == PT_SHADING_GL ? &sh : nullptr) != PT_OK)
+                return std::string("pt_set_shading: ") + g_core.last_error();
+        }
     }
     pt_config pc;
     std::memset(&pc, 0, sizeof pc);

@@ -47,11 +47,18 @@ void SetDevices(const std::vector<int> &ordinals);  // HIP ordinals used by Rend
 void SetFog(bool on);
 bool GetFog();
 bool FogFromEnv();  // PATHTRACER_GPU_FOG = 1 / true / on / yes
+// The shading model Render uses (pt_set_shading): PT_SHADING_CPU (the CPU engine, default) or PT_SHADING_GL (the OpenGL
+// backend's estimator).  The initial value is PATHTRACER_GPU_SHADING (ShadingFromEnv).
+void SetShading(int model);
+int GetShading();
+int ShadingFromEnv();  // PATHTRACER_GPU_SHADING = gl (any case) -> PT_SHADING_GL, else PT_SHADING_CPU
 void Shutdown();                                    // releases the process-wide context
 }  // namespace hip
 
 // scene.Fog flattened into the C ABI's pt_fog (raw fields; libptcore resolves them).
 void FlattenFog(const scene::Fog &f, pt_fog &out);
+// The scene's pt_gl_material table (reflectivity, tint, absorption_scale per material, raw) for pt_set_shading.
+void FlattenGlMaterials(const scene::Scene &sc, std::vector<pt_gl_material> &out);
 
 // RenderInto (renderer.go:34-41).  BackendGPU goes to hip::Render.  The CPU branch is the reference's
 // own Go renderer and is not shipped: selecting it, or a GPU failure (where the reference falls back

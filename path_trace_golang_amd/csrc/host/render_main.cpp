@@ -48,6 +48,7 @@ struct Flags {
     bool headless = false;
     bool scene_settings = false;
     bool fog = false;
+    std::string shading = "cpu";
     std::string out = "output.png";
     int width = 0, height = 0, spp = -1, depth = -1, devices = 1;
     unsigned long long seed = 1;
@@ -68,6 +69,8 @@ void usage() {
                  "  -scene-settings\n    \tlet the scene file's settings block override the mode preset (the editor's rule); with -mode final this also\n"
                  "    \tapplies the editor's Final button (x4 samples, x2 depth, internal/ui/app.go:73-75), which in the editor is\n"
                  "    \tindependent of the preset\n"
+                 "  -shading string\n    \tshading model: cpu (the CPU engine) or gl (the reference's GPU shader, DESIGN 3.8) (default \"cpu\", or\n"
+                 "    \tPATHTRACER_GPU_SHADING)\n"
                  "  -seed uint\n    \tsample-stream seed (default 1, or PATHTRACER_SEED)\n"
                  "  -spp int\n    \tsamples per pixel (default: the mode preset)\n"
                  "  -width int\n    \timage width (default: the mode preset)\n");
@@ -101,7 +104,7 @@ int parse(int argc, char **argv, Flags &f) {
             (name == "gpu" ? f.gpu : name == "headless" ? f.headless : name == "fog" ? f.fog : f.scene_settings) = b;
             continue;
         }
-        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices"};
+        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading"};
         bool ok = false;
         for (const char *k : known) ok = ok || name == k;
         if (!ok) {
@@ -120,6 +123,14 @@ int parse(int argc, char **argv, Flags &f) {
         if (name == "scene") f.scene = val;
         else if (name == "mode") f.mode = val;
         else if (name == "out") f.out = val;
+        else if (name == "shading") {
+            if (val != "cpu" && val != "gl") {
+                std::fprintf(stderr, "invalid value \"%s\" for flag -shading: want cpu or gl\n", val.c_str());
+                usage();
+                return 2;
+            }
+            f.shading = val;
+        }
         else {
             char *end = nullptr;
             errno = 0;
@@ -156,6 +167,8 @@ int render_headless(const Flags &f) {
     if (f.spp >= 0) s.SamplesPerPx = f.spp;
     if (f.depth >= 0) s.MaxDepth = f.depth;
     engine::hip::SetFog(f.fog);
+    engine::hip::SetShading(f.shading == "gl" ? PT_SHADING_GL : PT_SHADING_CPU);
+    if (f.shading == "gl") logf("shading: gl (the reference's GPU shader; spp counts passes of 16 paths)");
     if (f.fog) logf("fog: drawing the scene's fog block (%s)", sc->FogPtr ? "present" : "absent: nothing to draw");
     try {
         if (f.devices > 1) {
@@ -190,6 +203,7 @@ int main(int argc, char **argv) {
     Flags f;
     if (const char *e = std::getenv("PATHTRACER_SEED")) f.seed = std::strtoull(e, nullptr, 10);
     f.fog = engine::hip::FogFromEnv();
+    f.shading = engine::hip::ShadingFromEnv() == PT_SHADING_GL ? "gl" : "cpu";
     int rc = parse(argc, argv, f);
     if (rc >= 0) return rc;
     logf("flags: scene=%s mode=%s headless=%s out=%s", f.scene.c_str(), f.mode.c_str(), f.headless ? "true" : "false",

@@ -316,17 +316,10 @@ PT_HD void volume_light(const FogParams &p, const ptd::DevObj *objs, int32_t nob
     }
 }
 
-// The in-scatter term of one (pixel, sample) along its primary ray (orig, dir), gpu.go:1311-1341.  `rs` is the sample's fog
-// stream.  Adds nothing unless fog_volumetric() holds (the caller checks).
-PT_HD void fog_inscatter(const FogParams &p, const ptd::DevObj *objs, int32_t nobj, const FogLight *lights, int32_t nlight,
-                         const double orig[3], const double dir[3], uint64_t rs, FogCount &cnt, double L[3]) {
+// The march of gpu.go:1319-1340: 24 steps over [0, tmax] along the unit direction u from orig.  `rs` is the sample's fog stream.
+PT_HD void fog_march(const FogParams &p, const ptd::DevObj *objs, int32_t nobj, const FogLight *lights, int32_t nlight,
+                     const double orig[3], const double u[3], double tmax, uint64_t rs, FogCount &cnt, double L[3]) {
     L[0] = L[1] = L[2] = 0;
-    double t_hit;
-    const bool hit = closest_hit(objs, nobj, make_fray(orig[0], orig[1], orig[2], dir[0], dir[1], dir[2]), t_hit);
-    const double len = ptm::f_sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
-    const double u[3] = {dir[0] / len, dir[1] / len, dir[2] / len};
-    double tmax = PTF_TMAX;
-    if (hit && t_hit * len < PTF_TMAX) tmax = t_hit * len;
     const double step = tmax / PTF_STEPS;
     if (!(step > 0)) return;  // gpu.go:1325 (a zero-length direction)
     for (int i = 0; i < PTF_STEPS; i++) {
@@ -341,6 +334,19 @@ PT_HD void fog_inscatter(const FogParams &p, const ptd::DevObj *objs, int32_t no
         volume_light(p, objs, nobj, lights, nlight, px, py, pz, u, rs, cnt, ls);
         for (int c = 0; c < 3; c++) L[c] += p.color[c] * ls[c] * ss * tr * step;
     }
+}
+
+// The in-scatter term of one (pixel, sample) along its primary ray (orig, dir), gpu.go:1311-1341, on the CPU engine's ray and
+// its closest hit.  `rs` is the sample's fog stream.  Adds nothing unless fog_volumetric() holds (the caller checks).
+PT_HD void fog_inscatter(const FogParams &p, const ptd::DevObj *objs, int32_t nobj, const FogLight *lights, int32_t nlight,
+                         const double orig[3], const double dir[3], uint64_t rs, FogCount &cnt, double L[3]) {
+    double t_hit;
+    const bool hit = closest_hit(objs, nobj, make_fray(orig[0], orig[1], orig[2], dir[0], dir[1], dir[2]), t_hit);
+    const double len = ptm::f_sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
+    const double u[3] = {dir[0] / len, dir[1] / len, dir[2] / len};
+    double tmax = PTF_TMAX;
+    if (hit && t_hit * len < PTF_TMAX) tmax = t_hit * len;
+    fog_march(p, objs, nobj, lights, nlight, orig, u, tmax, rs, cnt, L);
 }
 
 }  // namespace ptf

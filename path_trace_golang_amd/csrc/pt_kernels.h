@@ -35,6 +35,9 @@
 //                   to the running sum (renderer.go:186), and on request finishes the
 //                   pixel: 1/spp, sqrt gamma, *255.999, clamp, truncate (renderer.go:190-221).
 //   untile_kernel   tile-major -> row-major frame.
+//   gl_trace_kernel opt-in (pt_set_shading, GL model): one pass of GL shading (pt_glshade.h) per job, 16 paths with their own
+//                   camera rays, the pass sum written into the job's radiance record; replaces ray generation and the trace
+//                   kernels for the frame.  resolve_kernel then finishes with GL's tone map (gl_spp).
 //   fog_kernel      opt-in (pt_set_fog): the fog's in-scatter term of every job (pt_fog.h), added into its radiance record
 //                   between a chunk's last trace pass and resolve_kernel.
 //
@@ -46,6 +49,7 @@
 
 #include "pt_device.h"
 #include "pt_fog.h"
+#include "pt_glshade.h"
 #include "pt_math.h"
 
 namespace ptk {
@@ -2726,7 +2730,10 @@ struct ResolveArgs {
     int32_t have_chunk;      // 0: no chunk to add (pure finish, pt_read)
     double inv_samples;      // 1/spp_done
     int32_t width, height, ntx, shard_index, shard_count;
+    int32_t gl_spp;          // GL shading: spp_done, and the finish is GL's tone map (post_tonemap_kernel); 0: the CPU engine's
 };
+
+__device__ __forceinline__ uint32_t tonemap_pack(double cx, double cy, double cz, int32_t spp);
 
 __global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) {
     const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
@@ -2768,7 +2775,9 @@ __global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) 
         const size_t pix = (size_t)lt * 1024u + ly * 32u + lx;
         if (R.tiles_rgba) {
             uint32_t packed = 0;
-            if (inside) {
+            if (inside && R.gl_spp) {
+                packed = tonemap_pack(cx, cy, cz, R.gl_spp);
+            } else if (inside) {
                 // renderer.go:190-221
                 const double r = ptm::f_sqrt(cx * R.inv_samples) * 255.999;
                 const double g = ptm::f_sqrt(cy * R.inv_samples) * 255.999;
@@ -2895,15 +2904,14 @@ __device__ __forceinline__ float aces_tonemap(float x) {
     return (float)r;
 }
 
-// gpu.go:2309-2350: clamp, ACES, sqrt gamma, uint8(g*255.0 + 0.5) in float32 arithmetic
-__global__ __launch_bounds__(PT_BLOCK) void post_tonemap_kernel(const double *__restrict__ accum, int32_t spp,
-                                                                  uint8_t *__restrict__ rgba, int32_t npix) {
-    const int32_t i = blockIdx.x * PT_BLOCK + threadIdx.x;
-    if (i >= npix) return;
+// gpu.go:2309-2350: clamp, ACES, sqrt gamma, uint8(g*255.0 + 0.5) in float32 arithmetic, for one pixel's sum over spp
+// (also the finish of GL shading in resolve_kernel)
+__device__ __forceinline__ uint32_t tonemap_pack(double cx, double cy, double cz, int32_t spp) {
+    const double sum[3] = {cx, cy, cz};
     uint32_t packed = 255u << 24;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        float lin = (float)(accum[(size_t)i * 3 + c] / (double)spp);
+        float lin = (float)(sum[c] / (double)spp);
         if (lin < 0) lin = 0;
         const float tm = aces_tonemap(lin);
         float g = (float)ptm::f_sqrt((double)tm);
@@ -2912,7 +2920,14 @@ __global__ __launch_bounds__(PT_BLOCK) void post_tonemap_kernel(const double *__
         v = v + 0.5f;
         packed |= ((uint32_t)v & 0xffu) << (8 * c);
     }
-    reinterpret_cast<uint32_t *>(rgba)[i] = packed;
+    return packed;
+}
+
+__global__ __launch_bounds__(PT_BLOCK) void post_tonemap_kernel(const double *__restrict__ accum, int32_t spp,
+                                                                  uint8_t *__restrict__ rgba, int32_t npix) {
+    const int32_t i = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (i >= npix) return;
+    reinterpret_cast<uint32_t *>(rgba)[i] = tonemap_pack(accum[(size_t)i * 3], accum[(size_t)i * 3 + 1], accum[(size_t)i * 3 + 2], spp);
 }
 
 // gpu.go:2355-2439: 3x3 bilateral filter on the 8-bit image (spatial sigma_s, range sigma_r in sRGB 0..1)
@@ -3046,6 +3061,64 @@ __global__ __launch_bounds__(PT_BLOCK) void fog_kernel(const FogArgs A) {
         atomicAdd(A.counters + 0, (unsigned long long)sr);
         atomicAdd(A.counters + 1, (unsigned long long)dr);
         atomicAdd(A.counters + 2, (unsigned long long)st);
+    }
+}
+
+// One GL-shading pass per job (pt_glshade.h): pixel (x, y) of the job as in raygen_kernel, pass s0 + sample, the 16 strata
+// traced in k order by this lane and their sum written into the job's radiance record, which resolve_kernel adds in pass
+// order.  The lane makes its own camera rays (no ray-generation kernel runs in GL mode).  Every object, light and march loop
+// has a wave-uniform trip count, so objects and materials come in by scalar loads; a shadow ray's object loop is left by
+// ballot once every active lane is occluded.  Jobs of pixels outside the frame do nothing (resolve_kernel skips them).
+struct GlArgs {
+    ptg::GlScene S;
+    double *L;                     // [njobs][4]
+    unsigned long long *counters;  // [48] the frame's counters: [0] segments, [2] draws, [3] samples (pt_stats)
+    unsigned long long *gl_counters;   // [5] paths, segments, shadow rays, probe rays, draws
+    unsigned long long *fog_counters;  // [3] shadow rays, draws, march steps (fog on)
+    uint64_t key, fog_key;
+    uint32_t njobs, nS, s0;
+    int32_t ntx, shard_index, shard_count;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void gl_trace_kernel(const GlArgs A) {
+    const uint32_t job = blockIdx.x * PT_BLOCK + threadIdx.x;
+    ptg::GlCount cnt = {0u, 0u, 0u, 0u, 0u};
+    ptf::FogCount fc = {0u, 0u, 0u};
+    if (job < A.njobs) {
+        const uint32_t p = job & 63u;
+        const uint32_t q = job >> 6;
+        const uint32_t blk = q / A.nS;
+        const uint32_t sl = q - blk * A.nS;
+        const uint32_t lt = blk >> 4, sb = blk & 15u;
+        const uint32_t t = (uint32_t)A.shard_index + lt * (uint32_t)A.shard_count;
+        const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
+        const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
+        const uint32_t y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+        if (x < (uint32_t)A.S.width && y < (uint32_t)A.S.height) {
+            double col[3];
+            ptg::gl_pass(A.S, A.key, A.fog_key, (int32_t)x, (int32_t)y, A.s0 + sl, cnt, fc, col);
+            reinterpret_cast<double4 *>(A.L)[job] = make_double4(col[0], col[1], col[2], 0.0);
+        }
+    }
+    const uint32_t pa = wave_sum(cnt.paths), sg = wave_sum(cnt.segments), sr = wave_sum(cnt.shadow_rays),
+                   pr = wave_sum(cnt.probe_rays), dr = wave_sum(cnt.draws);
+    if ((threadIdx.x & 63u) == 0u && pa != 0u) {
+        atomicAdd(A.gl_counters + 0, (unsigned long long)pa);
+        atomicAdd(A.gl_counters + 1, (unsigned long long)sg);
+        atomicAdd(A.gl_counters + 2, (unsigned long long)sr);
+        atomicAdd(A.gl_counters + 3, (unsigned long long)pr);
+        atomicAdd(A.gl_counters + 4, (unsigned long long)dr);
+        atomicAdd(A.counters + 0, (unsigned long long)sg);
+        atomicAdd(A.counters + 2, (unsigned long long)dr);
+        atomicAdd(A.counters + 3, (unsigned long long)pa);
+    }
+    if (A.fog_counters) {
+        const uint32_t fs = wave_sum(fc.shadow_rays), fd = wave_sum(fc.draws), ft = wave_sum(fc.steps);
+        if ((threadIdx.x & 63u) == 0u && (fs | fd | ft) != 0u) {
+            atomicAdd(A.fog_counters + 0, (unsigned long long)fs);
+            atomicAdd(A.fog_counters + 1, (unsigned long long)fd);
+            atomicAdd(A.fog_counters + 2, (unsigned long long)ft);
+        }
     }
 }
 

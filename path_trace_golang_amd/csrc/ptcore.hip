@@ -123,6 +123,10 @@ struct Device {
     size_t n_trace = 0, n_resolve = 0, n_raygen = 0, n_glass = 0, n_fog = 0;
     DevBuf<ptf::FogLight> fog_lights;        // the frame's light list (fog on)
     DevBuf<unsigned long long> fog_counters; // [3] shadow rays, draws, march steps of the frame
+    DevBuf<ptg::GlObj> gl_objs;              // GL shading: the frame's objects, materials and light list
+    DevBuf<ptg::GlMat> gl_mats;
+    DevBuf<int32_t> gl_lights;
+    DevBuf<unsigned long long> gl_counters;  // [5] paths, segments, shadow rays, probe rays, draws of the frame
     std::vector<char> trace_is_split;  // per trace launch of the frame: the split form?
     hipEvent_t ev_first = nullptr, ev_last = nullptr;
     bool first_recorded = false;
@@ -161,6 +165,12 @@ struct Frame {
     bool fog_vol = false;  // fog_kernel runs after every chunk (pt_set_fog with gpu_volumetric, max_depth > 0)
     ptf::FogParams fog{};
     std::vector<ptf::FogLight> fog_lights;
+    bool gl = false;  // GL shading (pt_set_shading): gl_trace_kernel replaces ray generation and the trace kernels
+    std::vector<ptg::GlObj> gl_objs;
+    std::vector<ptg::GlMat> gl_mats;
+    std::vector<int32_t> gl_lights;
+    ptg::GlCam gl_cam{};
+    ptg::GlSky gl_sky{};
     std::chrono::steady_clock::time_point t0;
 };
 
@@ -245,6 +255,11 @@ struct pt_ctx {
     pt_fog fog_raw{};
     pt_fog_stats fog_last{};
     int fog_pending = 0;  // the last frame's fog counters are still on the device: 1 = every device, 2 = devs[0] only
+    // shading model (pt_set_shading): the CPU engine by default; GL with one pt_gl_material per scene material
+    int32_t shading_model = PT_SHADING_CPU;
+    std::vector<pt_gl_material> gl_extras;
+    pt_shading_stats shading_last{};
+    int shading_pending = 0;  // as fog_pending, for the GL counters
 };
 
 namespace {
@@ -692,6 +707,18 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
             HIP_TRY(hipMemcpyAsync(d.fog_lights.p, fr.fog_lights.data(), fr.fog_lights.size() * sizeof(ptf::FogLight), hipMemcpyHostToDevice,
                                    d.stream));
     }
+    if (fr.gl) {  // (pageable sources: each copy is complete when the call returns)
+        HIP_TRY(d.gl_counters.reserve(5));
+        HIP_TRY(hipMemsetAsync(d.gl_counters.p, 0, 5 * sizeof(unsigned long long), d.stream));
+        HIP_TRY(d.gl_objs.reserve(std::max<size_t>(1, fr.gl_objs.size())));
+        HIP_TRY(d.gl_mats.reserve(fr.gl_mats.size()));
+        HIP_TRY(d.gl_lights.reserve(std::max<size_t>(1, fr.gl_lights.size())));
+        if (!fr.gl_objs.empty())
+            HIP_TRY(hipMemcpyAsync(d.gl_objs.p, fr.gl_objs.data(), fr.gl_objs.size() * sizeof(ptg::GlObj), hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemcpyAsync(d.gl_mats.p, fr.gl_mats.data(), fr.gl_mats.size() * sizeof(ptg::GlMat), hipMemcpyHostToDevice, d.stream));
+        if (!fr.gl_lights.empty())
+            HIP_TRY(hipMemcpyAsync(d.gl_lights.p, fr.gl_lights.data(), fr.gl_lights.size() * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+    }
     if (ctx->profile_sections) {
         HIP_TRY(d.prof.reserve(3 * ptk::SEC_COUNT));
         HIP_TRY(hipMemsetAsync(d.prof.p, 0, 3 * ptk::SEC_COUNT * sizeof(unsigned long long), d.stream));
@@ -1095,7 +1122,46 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         bind(B.cont, d.cq_d, d.cq_rs, d.cq_u32);
         B.glass.count = qw + 1;
     }
-    {  // ray generation, then the trace passes (which also handle max_depth <= 0: black samples, camera draws counted)
+    if (fr.gl) {  // GL shading: one pass per job, camera rays made in the kernel (pt_glshade.h)
+        ptk::GlArgs GA;
+        std::memset(&GA, 0, sizeof GA);
+        ptg::GlScene &GS = GA.S;
+        GS.objs = d.gl_objs.p;
+        GS.mats = d.gl_mats.p;
+        GS.lights = d.gl_lights.p;
+        GS.nobj = (int32_t)fr.gl_objs.size();
+        GS.nlight = (int32_t)fr.gl_lights.size();
+        GS.sky = fr.gl_sky;
+        GS.cam = fr.gl_cam;
+        GS.max_depth = fr.cfg.max_depth;
+        GS.width = fr.cfg.width;
+        GS.height = fr.cfg.height;
+        GS.fog_on = fr.fog_vol ? 1 : 0;
+        GS.fog = fr.fog;
+        GS.fog_objs = d.objs.p;
+        GS.fog_lights = d.fog_lights.p;
+        GS.fog_nobj = fr.nobj;
+        GS.fog_nlight = (int32_t)fr.fog_lights.size();
+        GA.L = d.L.p;
+        GA.counters = d.counters.p;
+        GA.gl_counters = d.gl_counters.p;
+        GA.fog_counters = fr.fog_vol ? d.fog_counters.p : nullptr;
+        GA.key = ptm::seed_key(fr.cfg.seed ^ PTG_STREAM_SALT);
+        GA.fog_key = ptm::seed_key(fr.cfg.seed ^ PTF_STREAM_SALT);
+        GA.njobs = F.njobs;
+        GA.nS = S;
+        GA.s0 = s0;
+        GA.ntx = fr.ntx;
+        GA.shard_index = d.shard.index;
+        GA.shard_count = d.shard.count;
+        if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
+        d.trace_is_split[d.n_trace] = 0;
+        EventPair &e = d.ev_trace[d.n_trace++];
+        HIP_TRY(hipEventRecord(e.a, d.stream));
+        hipLaunchKernelGGL(ptk::gl_trace_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, GA);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(e.b, d.stream));
+    } else {  // ray generation, then the trace passes (which also handle max_depth <= 0: black samples, camera draws counted)
         HIP_TRY(hipMemsetAsync(qw, 0, 8 * sizeof(unsigned int), d.stream));
         const size_t lds = fr.lds_bytes;
         const uint32_t waves_needed = (F.njobs + 63u) / 64u;
@@ -1227,7 +1293,7 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         }
         }
     }
-    if (fr.fog_vol) {  // the fog's in-scatter term into the chunk's radiance records (pt_fog.h)
+    if (fr.fog_vol && !fr.gl) {  // the fog's in-scatter term into the chunk's radiance records (pt_fog.h; GL shading adds it itself)
         if (int32_t rc = dev_events(d, d.ev_fog, d.n_fog + 1)) return rc;
         ptk::FogArgs FA;
         std::memset(&FA, 0, sizeof FA);
@@ -1304,6 +1370,7 @@ int32_t dev_finish(pt_ctx *ctx, Device &d, int32_t spp_done, uint8_t *tiles_rgba
     R.finish = 1;
     R.have_chunk = 0;
     R.inv_samples = 1.0 / (double)spp_done;  // renderer.go:97
+    R.gl_spp = fr.gl ? std::max(1, spp_done) : 0;  // GL shading: tone-mapped finish of accum / passes
     R.width = fr.cfg.width;
     R.height = fr.cfg.height;
     R.ntx = fr.ntx;
@@ -1575,6 +1642,8 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
     fr.cfg = *cfg;
     std::memset(&ctx->fog_last, 0, sizeof ctx->fog_last);
     ctx->fog_pending = 0;
+    std::memset(&ctx->shading_last, 0, sizeof ctx->shading_last);
+    ctx->shading_pending = 0;
     fr.nobj = sd.Fs.nobj;
     fr.nmat = sd.Fs.nmat;
     fr.scan = sd.scan;
@@ -1618,6 +1687,24 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
                 }
         }
         fr.sky = make_sky(sky);
+        if (ctx->shading_model == PT_SHADING_GL) {
+            if (cfg->flags & PT_FLAG_PIXEL_STATS) return fail(PT_ERR_INVALID, "GL shading: PT_FLAG_PIXEL_STATS is not available");
+            if (sd.scan == ptk::SCAN_BVH || sd.scan == ptk::SCAN_VERIFY_BVH)
+                return fail(PT_ERR_INVALID, "GL shading is not available for scenes on the BVH path (more than 128 spheres or 128 boxes)");
+            if ((int32_t)ctx->gl_extras.size() != scene->num_materials)
+                return fail(PT_ERR_INVALID, "GL shading: " + std::to_string(ctx->gl_extras.size()) + " material entries for a scene with " +
+                                                std::to_string(scene->num_materials) + " materials");
+            fr.gl = true;
+            const int32_t nmat = scene->num_materials;
+            fr.gl_mats.assign((size_t)std::max(1, nmat), ptg::GlMat{});  // no materials: one zero material for every object
+            for (int32_t i = 0; i < nmat; i++) fr.gl_mats[(size_t)i] = ptg::gl_material(scene->materials[i], ctx->gl_extras[(size_t)i]);
+            for (int32_t i = 0; i < scene->num_objects; i++) {
+                fr.gl_objs.push_back(ptg::gl_object(scene->objects[i], nmat));
+                if (ptg::gl_is_light(*scene, i)) fr.gl_lights.push_back(i);
+            }
+            fr.gl_cam = ptg::gl_camera(scene->camera, cfg->width, cfg->height);
+            fr.gl_sky = ptg::gl_sky(sky);
+        }
     }
     fr.ntx = (cfg->width + 31) / 32;
     fr.nty = (cfg->height + 31) / 32;
@@ -1673,7 +1760,7 @@ int32_t collect_fog(pt_ctx *ctx) {
     std::memset(&fs, 0, sizeof fs);
     for (size_t i = 0; i < ctx->devs.size() && !(first_only && i > 0); i++) {
         Device &d = ctx->devs[i];
-        if (d.n_fog == 0) continue;
+        if (d.n_fog == 0 && !(ctx->frame.gl && d.n_trace > 0)) continue;  // GL shading: the term ran inside gl_trace_kernel
         HIP_TRY(hipSetDevice(d.ordinal));
         HIP_TRY(hipStreamSynchronize(d.stream));
         unsigned long long c[3] = {};
@@ -1691,6 +1778,38 @@ int32_t collect_fog(pt_ctx *ctx) {
         fs.fog_launches += (int32_t)d.n_fog;
     }
     ctx->fog_last = fs;
+    return PT_OK;
+}
+
+// Reads the GL counters and gl_trace_kernel times of the last frame into ctx->shading_last (waits for the devices' streams).
+int32_t collect_shading(pt_ctx *ctx) {
+    if (!ctx->shading_pending) return PT_OK;
+    const bool first_only = ctx->shading_pending == 2;
+    ctx->shading_pending = 0;
+    pt_shading_stats ss;
+    std::memset(&ss, 0, sizeof ss);
+    for (size_t i = 0; i < ctx->devs.size() && !(first_only && i > 0); i++) {
+        Device &d = ctx->devs[i];
+        if (d.n_trace == 0 || !d.gl_counters.p) continue;
+        HIP_TRY(hipSetDevice(d.ordinal));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        unsigned long long c[5] = {};
+        HIP_TRY(hipMemcpy(c, d.gl_counters.p, sizeof c, hipMemcpyDeviceToHost));
+        ss.paths += c[0];
+        ss.segments += c[1];
+        ss.shadow_rays += c[2];
+        ss.probe_rays += c[3];
+        ss.draws += c[4];
+        double ms = 0;
+        for (size_t k = 0; k < d.n_trace; k++) {
+            float m = 0;
+            HIP_TRY(hipEventElapsedTime(&m, d.ev_trace[k].a, d.ev_trace[k].b));
+            ms += m;
+        }
+        ss.gl_ms = std::max(ss.gl_ms, ms);
+        ss.gl_launches += (int32_t)d.n_trace;
+    }
+    ctx->shading_last = ss;
     return PT_OK;
 }
 
@@ -1767,6 +1886,25 @@ int32_t pt_fog_last_stats(pt_ctx *ctx, pt_fog_stats *out) {
     if (!ctx || !out) return fail(PT_ERR_INVALID, "null argument");
     if (int32_t rc = collect_fog(ctx)) return rc;
     *out = ctx->fog_last;
+    return PT_OK;
+}
+
+int32_t pt_set_shading(pt_ctx *ctx, const pt_shading *s) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_shading while a frame is open");
+    if (s && s->model != PT_SHADING_CPU && s->model != PT_SHADING_GL) return fail(PT_ERR_INVALID, "unknown shading model");
+    if (s && s->model == PT_SHADING_GL && (s->num_materials < 0 || (s->num_materials > 0 && !s->materials)))
+        return fail(PT_ERR_INVALID, "GL shading needs num_materials >= 0 entries in materials");
+    ctx->shading_model = s ? s->model : PT_SHADING_CPU;
+    ctx->gl_extras.clear();
+    if (s && s->model == PT_SHADING_GL) ctx->gl_extras.assign(s->materials, s->materials + s->num_materials);
+    return PT_OK;
+}
+
+int32_t pt_shading_last_stats(pt_ctx *ctx, pt_shading_stats *out) {
+    if (!ctx || !out) return fail(PT_ERR_INVALID, "null argument");
+    if (int32_t rc = collect_shading(ctx)) return rc;
+    *out = ctx->shading_last;
     return PT_OK;
 }
 
@@ -1892,6 +2030,7 @@ void pt_destroy(pt_ctx *ctx) {
         for (EventPair &e : d.ev_raygen) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (EventPair &e : d.ev_fog) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         d.fog_lights.release(); d.fog_counters.release();
+        d.gl_objs.release(); d.gl_mats.release(); d.gl_lights.release(); d.gl_counters.release();
         if (d.ev_first) (void)hipEventDestroy(d.ev_first);
         if (d.ev_last) (void)hipEventDestroy(d.ev_last);
         if (d.own_stream) (void)hipStreamDestroy(d.own_stream);
@@ -2271,6 +2410,10 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
         ctx->fog_pending = 1;
         if (int32_t r = collect_fog(ctx)) rc = rc != PT_OK ? rc : r;
     }
+    if (ctx->frame.gl) {
+        ctx->shading_pending = 1;
+        if (int32_t r = collect_shading(ctx)) rc = rc != PT_OK ? rc : r;
+    }
     if (stats) *stats = st;
     return rc;
 }
@@ -2324,11 +2467,13 @@ int32_t pt_render_tiles_device(pt_ctx *ctx, const pt_scene *scene, const pt_conf
         rc = dev_finish(ctx, d, cfg->samples_per_px, static_cast<uint8_t *>(d_tiles_rgba), static_cast<double *>(d_tiles_accum),
                         nullptr, nullptr);
     if (rc == PT_OK && fr.fog_vol) ctx->fog_pending = 2;  // collected now with stats, else when pt_fog_last_stats asks
+    if (rc == PT_OK && fr.gl) ctx->shading_pending = 2;
     if (rc == PT_OK && stats) {
         pt_stats st;
         std::memset(&st, 0, sizeof st);
         rc = dev_collect(d, &st, 0);
         if (rc == PT_OK) rc = collect_fog(ctx);
+        if (rc == PT_OK) rc = collect_shading(ctx);
         fill_stats_common(ctx, &st);
         st.num_devices = 1;
         *stats = st;

@@ -59,14 +59,16 @@ def new_image(w: int, h: int) -> np.ndarray:
 
 
 def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
-                progress: Optional[Callable[[], None]] = None) -> dict:
-    """RenderInto, renderer.go:34-41."""
+                progress: Optional[Callable[[], None]] = None, shading: Optional[str] = None) -> dict:
+    """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
+    DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu"."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
             "this package implements only the GPU branch of RenderInto")
     gcfg = hip.RenderConfig(cfg.width, cfg.height, cfg.samples_per_px, cfg.max_depth, cfg.seed)
-    return hip.render(sc, gcfg, img, progress)
+    model = shading if shading is not None else hip.ShadingConfig.from_env().model
+    return hip.render(sc, gcfg, img, progress, shading=model)
 
 
 def render(sc: scn.Scene, cfg: RenderConfig) -> np.ndarray:

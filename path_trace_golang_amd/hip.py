@@ -123,6 +123,46 @@ def fog_last_stats(ctx: Optional[capi.Context] = None) -> dict:
     return st.as_dict()
 
 
+SHADING_MODELS = {"cpu": capi.PT_SHADING_CPU, "gl": capi.PT_SHADING_GL}
+
+
+def gl_materials(sc) -> "C.Array":
+    """The pt_gl_material table of a scene: per material its raw reflectivity, tint and absorption_scale (scene.go:41-63), in
+    material order; resolved inside libptcore (gpu.go:1840-1898)."""
+    mats = sc.materials
+    arr = (capi.PtGlMaterial * max(1, len(mats)))()
+    for i, m in enumerate(mats):
+        arr[i].reflectivity = m.reflectivity
+        arr[i].tint[:] = m.tint.as_list()
+        arr[i].absorption_scale = m.absorption_scale
+    return arr
+
+
+def set_shading(ctx: capi.Context, shading: str = "cpu", sc=None) -> None:
+    """pt_set_shading: "cpu" (the CPU engine, the default) or "gl" (the OpenGL backend's estimator, which needs the Scene `sc`
+    for its per-material fields) for the later renders on ctx."""
+    L = capi.load()
+    if shading not in SHADING_MODELS:
+        raise ValueError("shading must be one of %s" % sorted(SHADING_MODELS))
+    if not capi.has("pt_set_shading"):
+        raise RuntimeError("this libptcore.so has no pt_set_shading (rebuild it)")
+    if shading == "cpu":
+        capi.check(L.pt_set_shading(ctx.handle, None))
+        return
+    if sc is None or isinstance(sc, FlatScene):
+        raise ValueError("GL shading needs the Scene (its materials' reflectivity, tint and absorption_scale)")
+    arr = gl_materials(sc)
+    s = capi.PtShading(capi.PT_SHADING_GL, len(sc.materials), C.cast(arr, C.POINTER(capi.PtGlMaterial)))
+    capi.check(L.pt_set_shading(ctx.handle, C.byref(s)))
+
+
+def shading_last_stats(ctx: Optional[capi.Context] = None) -> dict:
+    """pt_shading_last_stats of ctx: gl_ms, gl_launches, paths, segments, shadow_rays, probe_rays, draws of its last frame."""
+    st = capi.PtShadingStats()
+    capi.check(capi.load().pt_shading_last_stats((ctx or context()).handle, C.byref(st)))
+    return st.as_dict()
+
+
 def pt_config(cfg: RenderConfig) -> capi.PtConfig:
     return capi.PtConfig(cfg.width, cfg.height, cfg.samples_per_px, cfg.max_depth, cfg.seed & 0xFFFFFFFFFFFFFFFF,
                          cfg.spp_chunk, cfg.flags)
@@ -154,12 +194,16 @@ def _ptr(a: Optional[np.ndarray]):
 
 def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[], None]] = None,
            accum: Optional[np.ndarray] = None, nseg: Optional[np.ndarray] = None,
-           ndraw: Optional[np.ndarray] = None, ctx: Optional[capi.Context] = None, fog: bool = False) -> dict:
+           ndraw: Optional[np.ndarray] = None, ctx: Optional[capi.Context] = None, fog: bool = False,
+           shading: str = "cpu") -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
     draws it (sky blend, volumetric in-scatter; pt_set_fog in include/ptcore.h); otherwise fog is off for the call, which
     is the CPU engine's image.  (A FlatScene carries no fog block: pass the Scene.)
+
+    shading="gl" renders with the OpenGL backend's estimator (pt_set_shading): samples_per_px counts passes of
+    16 paths each, accum holds the sum of the pass sums, and img is GL's tone-mapped finish.  It needs the Scene.
 
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
@@ -176,6 +220,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
         raise ValueError("img rows must be contiguous RGBA")
     flat = sc if isinstance(sc, FlatScene) else FlatScene(sc)  # callers that render one scene repeatedly flatten it once
     set_fog(ctx, getattr(sc, "fog", None) if fog else None)
+    if shading != "cpu" or capi.has("pt_set_shading"):
+        set_shading(ctx, shading, sc)
     pc = pt_config(cfg)
     st = capi.PtStats()
     if accum is not None and (accum.dtype != np.float64 or accum.shape != (cfg.height, cfg.width, 3)
@@ -264,6 +310,21 @@ class FogConfig:
 
         env = os.environ if environ is None else environ
         return cls(enabled=env.get("PATHTRACER_GPU_FOG", "").lower() in ("1", "true", "on", "yes"))
+
+
+@dataclass
+class ShadingConfig:
+    """Which estimator `render` uses: "cpu" (the CPU engine, default) or "gl" (the OpenGL backend's shader)."""
+    model: str = "cpu"
+
+    @classmethod
+    def from_env(cls, environ=None) -> "ShadingConfig":
+        """PATHTRACER_GPU_SHADING=gl (or cpu; case-insensitive, anything else is cpu), like the other PATHTRACER_GPU_* switches."""
+        import os
+
+        env = os.environ if environ is None else environ
+        v = env.get("PATHTRACER_GPU_SHADING", "").strip().lower()
+        return cls(model=v if v in SHADING_MODELS else "cpu")
 
 
 def post_process(img: np.ndarray, post: PostConfig, accum: Optional[np.ndarray] = None, samples_per_px: int = 1,

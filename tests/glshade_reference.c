@@ -1,0 +1,625 @@
+/*
+ * glshade_reference.c -- TEST INFRASTRUCTURE ONLY: an independent CPU restatement of GL shading
+ * (path_trace_golang_amd/csrc/pt_glshade.h: the reference's OpenGL compute shader, rayColor and main,
+ * internal/engine/gpu/gpu.go:1300-1732, host packing :1829-2010, in FP64), written against the CPU oracle
+ * (oracle/libptoracle.so) and no product header.  It keeps GLSL's shape: full hit records from every intersection test,
+ * hitWorld as the shader writes it, and the draws in the order the shader makes them.  The fog term reuses the fog tests'
+ * own restatement (tests/fog_reference.c, compiled into this file) with GL's march length.
+ *
+ *   gr_material   the host packing of one material (gpu.go:1840-1898)
+ *   gr_pass_many  the sum of one pass (16 strata) of (x, y, pass) jobs, with counters
+ *   gr_render     a whole frame: per pixel the passes in order, accum = their sum, rgba = ora_post_process(tonemap = 1)
+ */
+#include "fog_reference.c"
+
+#define GR_SALT 0x474C5F5348414445ULL /* ASCII "GL_SHADE" */
+#define GR_PI 3.14159265359           /* const float PI of the shader */
+
+/* the raw GL-only material fields (pt_gl_material in include/ptcore.h, restated) */
+typedef struct {
+    double reflectivity, tint[3], absorption_scale;
+} gr_extra;
+
+typedef struct {
+    int typ;
+    double rough, ior, smooth, refl, albedo[3], emit[3], absorption[3], abs_scale, tint[3];
+} gr_mat;
+
+typedef struct {
+    int typ; /* 0 sphere, 1 plane, 2 box */
+    int mat;
+    double pos[3], size[3];
+} gr_obj;
+
+typedef struct {
+    double p[3], normal[3], t;
+    int mat, obj, front;
+} gr_hit;
+
+typedef struct {
+    gr_mat *mats;
+    gr_obj *objs;
+    int *lights;
+    int nobj, nlight, depth, w, h;
+    int sky_type; /* 2 gradient, 1 solid / background */
+    double sky_color[3], horizon[3], zenith[3];
+    double cam_origin[3], cam_llc[3], cam_h[3], cam_v[3], cam_u[3], cam_vv[3], lens;
+    uint64_t seed;
+    int fog_on;
+    fr_params fog;
+    fr_world fw;
+    uint64_t cnt[5]; /* paths, segments, shadow rays, probes, draws */
+    uint32_t fcnt[3];
+} gr_ctx;
+
+static double vmax(double x, double y) { return x < y ? y : x; } /* GLSL max */
+static double vmin(double x, double y) { return y < x ? y : x; } /* GLSL min */
+static double dot(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+static void vnorm(double v[3]) {
+    double l = sqrt(dot(v, v));
+    v[0] = v[0] / l;
+    v[1] = v[1] / l;
+    v[2] = v[2] / l;
+}
+static void vcross(const double a[3], const double b[3], double o[3]) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+static void vreflect(const double v[3], const double n[3], double o[3]) {
+    double vn = dot(v, n);
+    for (int i = 0; i < 3; i++) o[i] = v[i] - 2.0 * vn * n[i];
+}
+static double rnd(gr_ctx *c, uint64_t *st) {
+    c->cnt[4]++;
+    return ora_stream_next(st);
+}
+
+void gr_material(const ora_material *m, const gr_extra *x, double out[19]) {
+    double s = m->smoothness;
+    if (s == 0 && m->type == 1) s = 1.0 - m->rough;
+    s = s < 0 ? 0 : (s > 1 ? 1 : s);
+    double r = x->reflectivity;
+    if (r == 0 && m->type == 1) r = 1.0;
+    r = r < 0 ? 0 : (r > 1 ? 1 : r);
+    double as = x->absorption_scale;
+    if (as == 0 && m->type == 2) as = 0.01;
+    double t[3] = {x->tint[0], x->tint[1], x->tint[2]};
+    if (t[0] == 0 && t[1] == 0 && t[2] == 0 && m->type == 2) t[0] = t[1] = t[2] = 1.0;
+    double v[19] = {(double)m->type, m->rough, m->ior, s, r, m->albedo[0], m->albedo[1], m->albedo[2],
+                    m->emit[0] * m->power, m->emit[1] * m->power, m->emit[2] * m->power,
+                    m->absorption[0], m->absorption[1], m->absorption[2], as, t[0], t[1], t[2], 0};
+    memcpy(out, v, sizeof v);
+}
+
+static void set_face(const double dir[3], gr_hit *h, const double out[3]) {
+    h->front = dot(dir, out) < 0.0;
+    for (int i = 0; i < 3; i++) h->normal[i] = h->front ? out[i] : -out[i];
+}
+
+static int hit_sphere(const double c[3], double radius, const double o[3], const double d[3], double tmin, double tmax, gr_hit *h) {
+    double oc[3] = {o[0] - c[0], o[1] - c[1], o[2] - c[2]};
+    double a = dot(d, d), hb = dot(oc, d), cc = dot(oc, oc) - radius * radius;
+    double disc = hb * hb - a * cc;
+    if (disc < 1e-8) return 0;
+    double sq = sqrt(disc);
+    double root = (-hb - sq) / a;
+    if (root < tmin || root > tmax) {
+        root = (-hb + sq) / a;
+        if (root < tmin || root > tmax) return 0;
+    }
+    h->t = root;
+    for (int i = 0; i < 3; i++) h->p[i] = o[i] + root * d[i];
+    double out[3];
+    for (int i = 0; i < 3; i++) out[i] = (h->p[i] - c[i]) / radius;
+    set_face(d, h, out);
+    return 1;
+}
+
+static int hit_plane(const double pt[3], const double o[3], const double d[3], double tmin, double tmax, gr_hit *h) {
+    const double n[3] = {0.0, 1.0, 0.0};
+    double denom = dot(n, d);
+    if (fabs(denom) < 1e-6) return 0;
+    double pm[3] = {pt[0] - o[0], pt[1] - o[1], pt[2] - o[2]};
+    double t = dot(pm, n) / denom;
+    if (t < tmin || t > tmax) return 0;
+    h->t = t;
+    for (int i = 0; i < 3; i++) h->p[i] = o[i] + t * d[i];
+    set_face(d, h, n);
+    return 1;
+}
+
+static int hit_box(const double bmin[3], const double bmax[3], const double o[3], const double d[3], double tmin, double tmax,
+                   gr_hit *h, int find_exit) {
+    double t0 = tmin, t1 = tmax;
+    for (int i = 0; i < 3; i++) {
+        double inv = 1.0 / d[i];
+        double tn = (bmin[i] - o[i]) * inv, tf = (bmax[i] - o[i]) * inv;
+        if (inv < 0.0) { double s = tn; tn = tf; tf = s; }
+        t0 = vmax(t0, tn);
+        t1 = vmin(t1, tf);
+        if (t1 <= t0) return 0;
+    }
+    double t = find_exit ? t1 : t0;
+    if (t < tmin || t > tmax) return 0;
+    h->t = t;
+    for (int i = 0; i < 3; i++) h->p[i] = o[i] + t * d[i];
+    double c[3], hs[3], lp[3], al[3], out[3] = {0, 0, 0};
+    for (int i = 0; i < 3; i++) {
+        c[i] = (bmin[i] + bmax[i]) * 0.5;
+        hs[i] = (bmax[i] - bmin[i]) * 0.5;
+        lp[i] = h->p[i] - c[i];
+        al[i] = fabs(lp[i]);
+    }
+#define SGN(x) ((x) > 0 ? 1.0 : ((x) < 0 ? -1.0 : 0.0))
+    if (fabs(al[0] - hs[0]) < 1e-4) out[0] = SGN(lp[0]);
+    else if (fabs(al[1] - hs[1]) < 1e-4) out[1] = SGN(lp[1]);
+    else out[2] = SGN(lp[2]);
+#undef SGN
+    if (find_exit) for (int i = 0; i < 3; i++) out[i] = -out[i];
+    set_face(d, h, out);
+    return 1;
+}
+
+static void box_of(const gr_obj *ob, double bmin[3], double bmax[3]) {
+    for (int i = 0; i < 3; i++) {
+        double hs = 0.5 * ob->size[i];
+        bmin[i] = ob->pos[i] - hs;
+        bmax[i] = ob->pos[i] + hs;
+    }
+}
+
+static int hit_obj(const gr_obj *ob, const double o[3], const double d[3], double tmin, double tmax, gr_hit *h) {
+    if (ob->typ == 0) return hit_sphere(ob->pos, ob->size[0], o, d, tmin, tmax, h);
+    if (ob->typ == 1) return hit_plane(ob->pos, o, d, tmin, tmax, h);
+    double bmin[3], bmax[3];
+    box_of(ob, bmin, bmax);
+    return hit_box(bmin, bmax, o, d, tmin, tmax, h, 0);
+}
+
+/* hitWorld, gpu.go:708-738 (skip = -1), and the main loop's scan that skips currentGlassObject (:1346-1380) */
+static int hit_world(const gr_ctx *c, const double o[3], const double d[3], double tmin, double tmax, int skip, gr_hit *out) {
+    int any = 0;
+    double closest = tmax;
+    gr_hit tmp;
+    for (int i = 0; i < c->nobj; i++) {
+        if (i == skip) continue;
+        if (hit_obj(&c->objs[i], o, d, tmin, closest, &tmp)) {
+            any = 1;
+            closest = tmp.t;
+            *out = tmp;
+            out->mat = c->objs[i].mat;
+            out->obj = i;
+        }
+    }
+    return any;
+}
+
+static void single_light(gr_ctx *c, int li, const gr_hit *h, const double albedo[3], uint64_t *st, double out[3]) {
+    out[0] = out[1] = out[2] = 0;
+    const gr_obj *ob = &c->objs[li];
+    if (ob->typ != 0) return;
+    double u1 = rnd(c, st), u2 = rnd(c, st);
+    double z = 1.0 - 2.0 * u1;
+    double r = sqrt(vmax(0.0, 1.0 - z * z));
+    double phi = 2.0 * GR_PI * u2;
+    double ln[3] = {r * ora_cos(phi), r * ora_sin(phi), z};
+    vnorm(ln);
+    double lp[3];
+    for (int i = 0; i < 3; i++) lp[i] = ob->pos[i] + ob->size[0] * ln[i];
+    double pdf = 1.0 / (4.0 * GR_PI * ob->size[0] * ob->size[0]);
+    if (pdf <= 0.0) return;
+    double tl[3] = {lp[0] - h->p[0], lp[1] - h->p[1], lp[2] - h->p[2]};
+    double dsq = dot(tl, tl);
+    if (dsq <= 1e-6) return;
+    double dist = sqrt(dsq);
+    double wi[3] = {tl[0] / dist, tl[1] / dist, tl[2] / dist}, nwi[3] = {-wi[0], -wi[1], -wi[2]};
+    /* the cosine tests before the shadow ray (same result as after it) */
+    double cs = vmax(0.0, dot(h->normal, wi)), cl = vmax(0.0, dot(ln, nwi));
+    if (cs <= 0.0 || cl <= 0.0) return;
+    double so[3];
+    for (int i = 0; i < 3; i++) so[i] = h->p[i] + h->normal[i] * 0.001;
+    c->cnt[2]++;
+    gr_hit sh;
+    if (hit_world(c, so, wi, 0.001, dist - 0.002, -1, &sh)) return;
+    const gr_mat *m = &c->mats[ob->mat];
+    if (m->typ != 3) return;
+    double ids = 1.0 / vmax(1e-6, dsq), ip = 1.0 / vmax(1e-6, pdf);
+    double g = (cs * cl) * ids;
+    double v[3];
+    for (int i = 0; i < 3; i++) {
+        double f = albedo[i] / GR_PI;
+        v[i] = f * m->emit[i] * g * ip;
+    }
+    double lum = v[0] * 0.2126 + v[1] * 0.7152 + v[2] * 0.0722;
+    if (lum > 500.0) {
+        double sc = 500.0 / vmax(lum, 1e-6);
+        for (int i = 0; i < 3; i++) v[i] *= sc;
+    }
+    memcpy(out, v, sizeof v);
+}
+
+static void direct(gr_ctx *c, const gr_hit *h, const double albedo[3], uint64_t *st, double out[3]) {
+    out[0] = out[1] = out[2] = 0;
+    int n = c->nlight;
+    if (n == 0) return;
+    double tot[3] = {0, 0, 0}, v[3];
+    if (n > 8) {
+        double scale = (double)n / 8.0;
+        int start = (int)(rnd(c, st) * (double)n) % n;
+        for (int j = 0; j < 8; j++) {
+            single_light(c, c->lights[(start + j) % n], h, albedo, st, v);
+            for (int k = 0; k < 3; k++) tot[k] += v[k];
+        }
+        for (int k = 0; k < 3; k++) tot[k] *= scale;
+    } else {
+        for (int i = 0; i < n; i++) {
+            single_light(c, c->lights[i], h, albedo, st, v);
+            for (int k = 0; k < 3; k++) tot[k] += v[k];
+        }
+    }
+    double inv = 1.0 / (double)n;
+    for (int k = 0; k < 3; k++) out[k] = tot[k] * inv;
+}
+
+static void path(gr_ctx *c, double o[3], double d[3], uint64_t *st, double L[3]) {
+    double thr[3] = {1, 1, 1};
+    int depth = c->depth, glass = -1;
+    double acc_travel = 0.0;
+    while (depth > 0) {
+        c->cnt[1]++;
+        gr_hit h;
+        if (!hit_world(c, o, d, 0.001, 1e20, glass, &h)) {
+            double bg[3];
+            if (c->sky_type == 2) {
+                double u[3] = {d[0], d[1], d[2]};
+                vnorm(u);
+                double t = (u[1] + 1.0) * 0.5;
+                t = vmin(vmax(t, 0.0), 1.0);
+                for (int i = 0; i < 3; i++) bg[i] = c->horizon[i] * (1.0 - t) + c->zenith[i] * t;
+            } else {
+                memcpy(bg, c->sky_color, sizeof bg);
+            }
+            for (int i = 0; i < 3; i++) L[i] += thr[i] * bg[i];
+            return;
+        }
+        const gr_mat *m = &c->mats[h.mat];
+        if (m->typ == 3) {
+            for (int i = 0; i < 3; i++) L[i] += thr[i] * m->emit[i];
+            return; /* deviation: the shader's newDir is undefined here */
+        }
+        double nd[3], att[3] = {m->albedo[0], m->albedo[1], m->albedo[2]};
+        if (m->typ == 0) {
+            double r1 = rnd(c, st), r2 = rnd(c, st);
+            double phi = 6.28318530718 * r1, ct = sqrt(r2), sn = sqrt(1.0 - r2);
+            double u[3] = {0, 0, 0}, v[3];
+            if (fabs(h.normal[0]) > 0.9) u[1] = 1.0; else u[0] = 1.0;
+            vnorm(u);
+            vcross(h.normal, u, v);
+            vnorm(v);
+            double cp = ora_cos(phi), sp = ora_sin(phi);
+            double l0 = sn * cp, l1 = sn * sp, l2 = ct;
+            for (int i = 0; i < 3; i++) nd[i] = l0 * u[i] + l1 * v[i] + l2 * h.normal[i];
+            vnorm(nd);
+            double dl[3];
+            direct(c, &h, m->albedo, st, dl);
+            for (int i = 0; i < 3; i++) L[i] += thr[i] * dl[i];
+        } else if (m->typ == 1 || m->typ == 4) {
+            double view[3] = {d[0], d[1], d[2]};
+            vnorm(view);
+            double mr = m->smooth > 0.0 ? 1.0 - m->smooth : m->rough;
+            double er = m->refl > 0.0 ? m->refl : 1.0;
+            int rough = m->typ == 1 && mr > 1e-4;
+            if (rough) {
+                double a = mr * mr, a2 = a * a;
+                double r1 = rnd(c, st), r2 = rnd(c, st);
+                double ct = sqrt((1.0 - r2) / (1.0 + (a2 - 1.0) * r2));
+                double sn = sqrt(1.0 - ct * ct);
+                double phi = 2.0 * GR_PI * r1;
+                double up[3] = {0, 0, 0}, tg[3], bt[3], hv[3];
+                if (fabs(h.normal[2]) < 0.999) up[2] = 1.0; else up[0] = 1.0;
+                vcross(up, h.normal, tg);
+                vnorm(tg);
+                vcross(h.normal, tg, bt);
+                double h0 = sn * ora_cos(phi), h1 = sn * ora_sin(phi), h2 = ct;
+                for (int i = 0; i < 3; i++) hv[i] = h0 * tg[i] + h1 * bt[i] + h2 * h.normal[i];
+                vnorm(hv);
+                double iv[3] = {-view[0], -view[1], -view[2]};
+                vreflect(iv, hv, nd);
+                if (dot(nd, h.normal) <= 0.0) vreflect(iv, h.normal, nd);
+                vnorm(nd);
+                double sw = 1.0 / (1.0 + a * 2.0);
+                sw = vmin(vmax(sw, 0.1), 0.9);
+                double dw = 1.0 - sw, dd[3];
+                direct(c, &h, m->albedo, st, dd);
+                for (int i = 0; i < 3; i++) L[i] += thr[i] * dd[i] * dw * er * 0.5;
+                for (int i = 0; i < 3; i++) att[i] = m->albedo[i] * (sw * er + dw * 0.3);
+            } else {
+                vreflect(view, h.normal, nd);
+                if (fabs(dot(nd, nd) - 1.0) > 1e-4) vnorm(nd);
+                for (int i = 0; i < 3; i++) att[i] = m->albedo[i] * er;
+            }
+            int scattered = !(dot(nd, h.normal) <= 1e-6);
+            if (scattered && rough) {
+                double rd[3], ro[3];
+                vreflect(view, h.normal, rd);
+                for (int i = 0; i < 3; i++) ro[i] = h.p[i] + h.normal[i] * 0.001;
+                c->cnt[3]++;
+                gr_hit rh;
+                if (hit_world(c, ro, rd, 0.001, 1e20, -1, &rh) && c->mats[rh.mat].typ == 3) {
+                    double dsq = rh.t * rh.t, nrd[3] = {-rd[0], -rd[1], -rd[2]};
+                    double cl = vmax(0.0, dot(rh.normal, nrd));
+                    for (int i = 0; i < 3; i++) {
+                        double dr = c->mats[rh.mat].emit[i] * cl / dsq;
+                        L[i] += thr[i] * dr * m->albedo[i] * 0.5;
+                    }
+                }
+            }
+        } else { /* dielectric */
+            att[0] = att[1] = att[2] = 1.0;
+            double ud[3] = {d[0], d[1], d[2]};
+            vnorm(ud);
+            double nu[3] = {-ud[0], -ud[1], -ud[2]};
+            double ct = vmin(dot(nu, h.normal), 1.0);
+            double s2 = 1.0 - ct * ct;
+            double sn = s2 > 0.0 ? sqrt(s2) : 0.0;
+            int entering = h.front;
+            double inv = 1.0 / m->ior;
+            double eta = entering ? inv : m->ior, rel = entering ? m->ior : inv;
+            if (eta * sn > 1.0) {
+                vreflect(ud, h.normal, nd);
+            } else {
+                double r0 = (rel - 1.0) / (rel + 1.0);
+                r0 = r0 * r0;
+                double x = 1.0 - ct;
+                double rp = r0 + (1.0 - r0) * (x * x * x * x * x);
+                if (!entering) rp = vmax(rp, 0.05);
+                if (rnd(c, st) < rp) {
+                    vreflect(ud, h.normal, nd);
+                } else {
+                    /* refractVec */
+                    double c2 = vmin(dot(nu, h.normal), 1.0);
+                    double q = 1.0 - c2 * c2;
+                    if (eta * eta * q > 1.0) {
+                        vreflect(ud, h.normal, nd);
+                    } else {
+                        double perp[3];
+                        for (int i = 0; i < 3; i++) perp[i] = eta * (ud[i] + c2 * h.normal[i]);
+                        double par = sqrt(1.0 - vmin(dot(perp, perp), 1.0));
+                        for (int i = 0; i < 3; i++) nd[i] = perp[i] + -par * h.normal[i];
+                    }
+                    if (entering) {
+                        glass = h.obj;
+                        double travel = 0.0;
+                        const gr_obj *ob = &c->objs[h.obj];
+                        double eo[3];
+                        for (int i = 0; i < 3; i++) eo[i] = h.p[i] + nd[i] * 0.001;
+                        if (ob->typ == 2) {
+                            double bmin[3], bmax[3];
+                            box_of(ob, bmin, bmax);
+                            gr_hit eh;
+                            if (hit_box(bmin, bmax, eo, nd, 0.001, 1e20, &eh, 1)) travel = eh.t;
+                        } else if (ob->typ == 0) {
+                            double r2 = ob->size[0] * ob->size[0];
+                            double oc[3] = {eo[0] - ob->pos[0], eo[1] - ob->pos[1], eo[2] - ob->pos[2]};
+                            double hb = dot(oc, nd), cc = dot(oc, oc) - r2;
+                            double disc = hb * hb - cc;
+                            if (disc > 0.0) {
+                                double sq = sqrt(disc);
+                                double et = vmax(-hb - sq, -hb + sq);
+                                if (et > 0.001) travel = et;
+                            }
+                        }
+                        if (travel > 0.0) {
+                            acc_travel = travel;
+                            for (int i = 0; i < 3; i++) att[i] *= 0.1 + ora_exp(-(m->absorption[i] * m->abs_scale * travel)) * 0.9;
+                            if (m->tint[0] > 0.0 || m->tint[1] > 0.0 || m->tint[2] > 0.0)
+                                for (int i = 0; i < 3; i++) att[i] *= m->tint[i];
+                        }
+                    } else {
+                        glass = -1;
+                        if (acc_travel > 0.0) {
+                            for (int i = 0; i < 3; i++) att[i] *= 0.1 + ora_exp(-(m->absorption[i] * m->abs_scale * acc_travel)) * 0.9;
+                            if (m->tint[0] > 0.0 || m->tint[1] > 0.0 || m->tint[2] > 0.0)
+                                for (int i = 0; i < 3; i++) att[i] *= m->tint[i];
+                        }
+                        acc_travel = 0.0;
+                    }
+                }
+            }
+            vnorm(nd);
+        }
+        if (depth <= 3) {
+            double mc = vmax(att[0], vmax(att[1], att[2]));
+            if (mc < 1e-6) return;
+            double rr = vmin(mc, 0.95);
+            if (rnd(c, st) > rr) return;
+            for (int i = 0; i < 3; i++) att[i] /= rr;
+        }
+        for (int i = 0; i < 3; i++) {
+            thr[i] *= att[i];
+            o[i] = h.p[i] + h.normal[i] * 0.001;
+            d[i] = nd[i];
+        }
+        depth--;
+    }
+}
+
+static void pass_sum(gr_ctx *c, int x, int y, uint32_t pass, double col[3]) {
+    col[0] = col[1] = col[2] = 0;
+    uint64_t pix = (uint64_t)y * (uint64_t)c->w + (uint64_t)x;
+    for (int sy = 0; sy < 4; sy++)
+        for (int sx = 0; sx < 4; sx++) {
+            uint64_t sample = (uint64_t)pass * 16u + (uint64_t)(sy * 4 + sx);
+            uint64_t st = ora_stream_init(c->seed ^ GR_SALT, pix, sample);
+            c->cnt[0]++;
+            double jx = rnd(c, &st), jy = rnd(c, &st);
+            double su = ((double)sx + jx) / 4.0, sv = ((double)sy + jy) / 4.0;
+            double u = ((double)x + su) / (double)(c->w - 1);
+            double fy = (double)(c->h - 1 - y);
+            double v = (fy + sv) / (double)(c->h - 1);
+            double o[3], d[3];
+            if (c->lens > 0.0) {
+                double p[3] = {0, 0, 1};
+                for (int t = 0; t < 16; t++) {
+                    double a = rnd(c, &st), b = rnd(c, &st), e = rnd(c, &st);
+                    double q[3] = {2.0 * a - 1.0, 2.0 * b - 1.0, 2.0 * e - 1.0};
+                    if (dot(q, q) >= 1.0) continue;
+                    memcpy(p, q, sizeof p);
+                    break;
+                }
+                double rx = c->lens * p[0], ry = c->lens * p[1], off[3];
+                for (int i = 0; i < 3; i++) off[i] = c->cam_u[i] * rx + c->cam_vv[i] * ry;
+                for (int i = 0; i < 3; i++) {
+                    d[i] = c->cam_llc[i] + u * c->cam_h[i] + v * c->cam_v[i] - c->cam_origin[i] - off[i];
+                    o[i] = c->cam_origin[i] + off[i];
+                }
+            } else {
+                for (int i = 0; i < 3; i++) {
+                    d[i] = c->cam_llc[i] + u * c->cam_h[i] + v * c->cam_v[i] - c->cam_origin[i];
+                    o[i] = c->cam_origin[i];
+                }
+            }
+            vnorm(d);
+            double L[3] = {0, 0, 0};
+            if (c->fog_on && c->depth > 0) {
+                gr_hit fh;
+                double tmax = 40.0;
+                if (hit_world(c, o, d, 0.001, tmax, -1, &fh)) tmax = fh.t;
+                double step = tmax / 24;
+                if (step > 0) { /* fog_reference.c's march, with GL's length and unit direction */
+                    uint64_t frs = ora_stream_init(c->seed ^ FOG_SALT, pix, sample);
+                    for (int i = 0; i < 24; i++) {
+                        double t = ((double)i + 0.5) * step;
+                        double pos[3] = {o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t};
+                        double sgt;
+                        double ss = medium(&c->fog, pos[0], pos[1], pos[2], &sgt);
+                        if (sgt <= 0 || ss <= 0) continue;
+                        c->fcnt[2]++;
+                        double tr = ora_exp(-sgt * t), ls[3];
+                        volume_light(&c->fog, &c->fw, pos, d, &frs, c->fcnt, ls);
+                        for (int k = 0; k < 3; k++) L[k] += c->fog.color[k] * ls[k] * ss * tr * step;
+                    }
+                }
+            }
+            path(c, o, d, &st, L);
+            for (int i = 0; i < 3; i++) col[i] += L[i];
+        }
+}
+
+/* set-up of the frame: materials, objects, light list, camera, sky (fog's affect_sky applied to the sky first) */
+static void ctx_open(gr_ctx *c, const ora_scene *sc, const gr_extra *ex, int w, int h, int depth, uint64_t seed, const fr_fog *fog) {
+    memset(c, 0, sizeof *c);
+    int nm = sc->nmaterials, no = sc->nobjects;
+    c->mats = (gr_mat *)calloc((size_t)(nm > 0 ? nm : 1), sizeof(gr_mat));
+    for (int i = 0; i < nm; i++) {
+        double v[19];
+        gr_material(&sc->materials[i], &ex[i], v);
+        gr_mat *m = &c->mats[i];
+        m->typ = (int)v[0]; m->rough = v[1]; m->ior = v[2]; m->smooth = v[3]; m->refl = v[4];
+        for (int k = 0; k < 3; k++) {
+            m->albedo[k] = v[5 + k]; m->emit[k] = v[8 + k]; m->absorption[k] = v[11 + k]; m->tint[k] = v[15 + k];
+        }
+        m->abs_scale = v[14];
+    }
+    c->objs = (gr_obj *)calloc((size_t)(no > 0 ? no : 1), sizeof(gr_obj));
+    c->lights = (int *)calloc((size_t)(no > 0 ? no : 1), sizeof(int));
+    for (int i = 0; i < no; i++) {
+        const ora_object *o = &sc->objects[i];
+        gr_obj *g = &c->objs[i];
+        g->typ = o->type == 1 ? 1 : (o->type == 2 ? 2 : 0);
+        g->mat = (o->material >= 0 && o->material < nm) ? o->material : 0;
+        memcpy(g->pos, o->position, sizeof g->pos);
+        memcpy(g->size, o->size, sizeof g->size);
+        if (nm > 0) {
+            const ora_material *m = &sc->materials[g->mat];
+            if (m->type == 3 && (m->emit[0] > 0 || m->emit[1] > 0 || m->emit[2] > 0)) c->lights[c->nlight++] = i;
+        }
+    }
+    c->nobj = no;
+    c->depth = depth;
+    c->w = w;
+    c->h = h;
+    c->seed = seed;
+    ora_sky sky = sc->sky;
+    if (fog) {
+        fr_sky(fog, &sky);
+        fr_resolve(fog, &c->fog);
+        c->fog_on = c->fog.volumetric;
+        world_build(sc, &c->fw);
+    }
+    c->sky_type = sky.sky_type == 1 ? 2 : 1;
+    for (int i = 0; i < 3; i++) {
+        c->sky_color[i] = sky.sky_type == 2 ? sky.color[i] : sky.background[i];
+        c->horizon[i] = sky.horizon[i];
+        c->zenith[i] = sky.zenith[i];
+    }
+    /* buildCamera's constants, gpu.go:1110-1124 */
+    const ora_camera *cam = &sc->camera;
+    double aspect = cam->aspect_ratio != 0 ? cam->aspect_ratio : (double)w / (double)h;
+    double theta = cam->fov * 3.14159265359 / 180.0;
+    double hh = ora_tan(theta * 0.5);
+    double vh = 2.0 * hh, vw = aspect * vh;
+    double ow[3] = {cam->position[0] - cam->target[0], cam->position[1] - cam->target[1], cam->position[2] - cam->target[2]};
+    double wv[3] = {ow[0], ow[1], ow[2]}, uv[3], vv[3];
+    vnorm(wv);
+    vcross(cam->up, wv, uv);
+    vnorm(uv);
+    vcross(wv, uv, vv);
+    double fd = cam->focus_dist != 0 ? cam->focus_dist : sqrt(dot(ow, ow));
+    for (int i = 0; i < 3; i++) {
+        c->cam_origin[i] = cam->position[i];
+        c->cam_h[i] = vw * fd * uv[i];
+        c->cam_v[i] = vh * fd * vv[i];
+        c->cam_u[i] = uv[i];
+        c->cam_vv[i] = vv[i];
+    }
+    for (int i = 0; i < 3; i++) c->cam_llc[i] = c->cam_origin[i] - 0.5 * c->cam_h[i] - 0.5 * c->cam_v[i] - wv[i] * fd;
+    c->lens = cam->aperture * 0.5;
+}
+
+static void ctx_close(gr_ctx *c) {
+    free(c->mats);
+    free(c->objs);
+    free(c->lights);
+    if (c->fw.objs) world_free(&c->fw);
+}
+
+/* jobs[3i] = x, y, pass; out[3i] = the pass sum; cnt[8i] = paths, segments, shadow rays, probes, draws, fog shadow rays,
+ * fog draws, fog steps */
+void gr_pass_many(const ora_scene *sc, const gr_extra *ex, int32_t w, int32_t h, int32_t depth, uint64_t seed, const fr_fog *fog,
+                  int64_t n, const int32_t *jobs, double *out, uint64_t *cnt) {
+    gr_ctx c;
+    ctx_open(&c, sc, ex, w, h, depth, seed, fog);
+    for (int64_t i = 0; i < n; i++) {
+        memset(c.cnt, 0, sizeof c.cnt);
+        memset(c.fcnt, 0, sizeof c.fcnt);
+        pass_sum(&c, jobs[3 * i], jobs[3 * i + 1], (uint32_t)jobs[3 * i + 2], out + 3 * i);
+        for (int k = 0; k < 5; k++) cnt[8 * i + k] = c.cnt[k];
+        for (int k = 0; k < 3; k++) cnt[8 * i + 5 + k] = c.fcnt[k];
+    }
+    ctx_close(&c);
+}
+
+/* a whole frame; stats = paths, segments, shadow rays, probes, draws, fog shadow rays, fog draws, fog steps */
+void gr_render(const ora_scene *sc, const gr_extra *ex, int32_t w, int32_t h, int32_t passes, int32_t depth, uint64_t seed,
+               const fr_fog *fog, uint8_t *rgba, double *accum, uint64_t stats[8]) {
+    gr_ctx c;
+    ctx_open(&c, sc, ex, w, h, depth, seed, fog);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            double sum[3] = {0, 0, 0}, col[3];
+            for (int p = 0; p < passes; p++) {
+                pass_sum(&c, x, y, (uint32_t)p, col);
+                for (int k = 0; k < 3; k++) sum[k] += col[k];
+            }
+            memcpy(accum + 3 * ((size_t)y * (size_t)w + (size_t)x), sum, sizeof sum);
+        }
+    ora_post_config post;
+    memset(&post, 0, sizeof post);
+    post.tonemap = 1;
+    ora_post_process(&post, accum, passes > 0 ? passes : 1, rgba, 4 * w, w, h);
+    for (int k = 0; k < 5; k++) stats[k] = c.cnt[k];
+    for (int k = 0; k < 3; k++) stats[5 + k] = c.fcnt[k];
+    ctx_close(&c);
+}
