@@ -393,3 +393,35 @@ void fr_inscatter_many(const ora_scene *sc, const fr_fog *raw, int32_t max_depth
     }
     world_free(&w);
 }
+
+/* the pieces of the term one at a time (the device probe, test_device_math_gpu.py): p[i] = {x, y, z} */
+void fr_hash31_many(const double *p, double *out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) out[i] = hash31(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+}
+void fr_noise_many(const fr_fog *raw, const double *p, double *out, int64_t n) {
+    fr_params q;
+    fr_resolve(raw, &q);
+    for (int64_t i = 0; i < n; i++) out[i] = volume_noise(&q, p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+}
+void fr_phase_many(const double *ct, const double *g, double *out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) out[i] = phase_hg(ct[i], g[i]);
+}
+
+/* the oracle's scalar routines over arrays (a million ctypes calls would take minutes): which = 0 ora_sin, 1 ora_cos,
+ * 2 ora_tan, 3 ora_exp; 0 ora_pow, 1 ora_min, 2 ora_max */
+void fr_ora_unary_many(int which, const double *x, double *out, int64_t n) {
+    for (int64_t i = 0; i < n; i++)
+        out[i] = which == 0 ? ora_sin(x[i]) : which == 1 ? ora_cos(x[i]) : which == 2 ? ora_tan(x[i]) : ora_exp(x[i]);
+}
+void fr_ora_binary_many(int which, const double *a, const double *b, double *out, int64_t n) {
+    for (int64_t i = 0; i < n; i++)
+        out[i] = which == 0 ? ora_pow(a[i], b[i]) : which == 1 ? ora_min(a[i], b[i]) : ora_max(a[i], b[i]);
+}
+/* keys[i] = {seed, pixel, sample}: state0[i] = ora_stream_init, out[i][0..ndraw) = that many ora_stream_next */
+void fr_ora_streams(const uint64_t *keys, int32_t ndraw, uint64_t *state0, double *out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) {
+        uint64_t s = ora_stream_init(keys[3 * i], keys[3 * i + 1], keys[3 * i + 2]);
+        state0[i] = s;
+        for (int32_t k = 0; k < ndraw; k++) out[i * ndraw + k] = ora_stream_next(&s);
+    }
+}

@@ -23,6 +23,16 @@ SHIM = r"""
 #include "pt_fog.h"
 extern "C" {
 void shim_sin_many(const double *x, double *out, int64_t n) { for (int64_t i = 0; i < n; i++) out[i] = ptm::go_sin(x[i]); }
+void shim_hash31_many(const double *p, double *out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) out[i] = ptf::hash31(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+}
+void shim_noise_many(const pt_fog *raw, const double *p, double *out, int64_t n) {
+    const ptf::FogParams q = ptf::fog_resolve(*raw);
+    for (int64_t i = 0; i < n; i++) out[i] = ptf::volume_noise(q, p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+}
+void shim_phase_many(const double *ct, const double *g, double *out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) out[i] = ptf::phase_hg(ct[i], g[i]);
+}
 void shim_resolve_flat(const pt_fog *raw, double out[13]) {
     ptf::FogParams p = ptf::fog_resolve(*raw);
     double v[13] = {p.density, p.scatter, p.sigma_s, p.sigma_a, p.g, p.hetero, p.noise_scale, p.color[0], p.color[1], p.color[2],
@@ -104,6 +114,12 @@ def reference():
         L.fr_inscatter_many.argtypes = [_vp, _vp, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp]
         L.fr_render.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
         L.fr_render.restype = C.c_int
+        L.fr_hash31_many.argtypes = [_vp, _vp, C.c_int64]
+        L.fr_noise_many.argtypes = [_vp, _vp, _vp, C.c_int64]
+        L.fr_phase_many.argtypes = [_vp, _vp, _vp, C.c_int64]
+        L.fr_ora_unary_many.argtypes = [C.c_int, _vp, _vp, C.c_int64]
+        L.fr_ora_binary_many.argtypes = [C.c_int, _vp, _vp, _vp, C.c_int64]
+        L.fr_ora_streams.argtypes = [_vp, C.c_int32, _vp, _vp, C.c_int64]
         _libs["ref"] = L
     return _libs["ref"]
 
@@ -123,6 +139,9 @@ def product_host():
         L.shim_resolve_flat.argtypes = [_vp, _vp]
         L.shim_sky.argtypes = [_vp, _vp]
         L.shim_inscatter_many.argtypes = [_vp, _vp, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp]
+        L.shim_hash31_many.argtypes = [_vp, _vp, C.c_int64]
+        L.shim_noise_many.argtypes = [_vp, _vp, _vp, C.c_int64]
+        L.shim_phase_many.argtypes = [_vp, _vp, _vp, C.c_int64]
         _libs["shim"] = L
     return _libs["shim"]
 

@@ -55,7 +55,8 @@ def _sins(x: np.ndarray):
     return a, b
 
 
-def test_go_sin_equals_go_sin_bit_for_bit_over_the_range():
+def sin_range_arguments() -> np.ndarray:
+    """The arguments of the range test (also what test_device_math_gpu.py gives the device): |x| < 2^29."""
     rng = np.random.default_rng(7)
     lim = 2.0 ** 29
     parts = [
@@ -65,14 +66,11 @@ def test_go_sin_equals_go_sin_bit_for_bit_over_the_range():
         rng.uniform(-2 * math.pi, 2 * math.pi, 50_000),
     ]
     x = np.concatenate(parts)
-    x = x[np.abs(x) < lim]
-    assert x.size >= 1_000_000
-    a, b = _sins(x)
-    bad = np.flatnonzero(_bits(a) != _bits(b))
-    assert bad.size == 0, (x[bad[:5]], a[bad[:5]], b[bad[:5]])
+    return x[np.abs(x) < lim]
 
 
-def test_go_sin_special_arguments():
+def sin_special_arguments() -> np.ndarray:
+    """Signed zeros, subnormals, +-3 ulp around k pi/4 for k < 200, the top of the range."""
     tiny = np.array([0.0, -0.0, 5e-324, -5e-324, 2.2250738585072009e-308, -2.2250738585072014e-308, 1e-300, 2.0 ** -28])
     edges = []
     for k in range(1, 200):
@@ -83,7 +81,19 @@ def test_go_sin_special_arguments():
                 v = np.nextafter(v, np.inf if d > 0 else -np.inf)
             edges += [v, -v]
     top = np.nextafter(2.0 ** 29, 0.0)
-    x = np.concatenate([tiny, np.array(edges), np.array([top, -top, 1.0, -1.0])])
+    return np.concatenate([tiny, np.array(edges), np.array([top, -top, 1.0, -1.0])])
+
+
+def test_go_sin_equals_go_sin_bit_for_bit_over_the_range():
+    x = sin_range_arguments()
+    assert x.size >= 1_000_000
+    a, b = _sins(x)
+    bad = np.flatnonzero(_bits(a) != _bits(b))
+    assert bad.size == 0, (x[bad[:5]], a[bad[:5]], b[bad[:5]])
+
+
+def test_go_sin_special_arguments():
+    x = sin_special_arguments()
     a, b = _sins(x)
     assert np.array_equal(_bits(a), _bits(b))
     assert math.copysign(1.0, a[1]) == -1.0  # -0 keeps its sign
@@ -208,6 +218,49 @@ def test_scene_fog_blocks_use_every_light():
     _, _, ca, _ = _terms(oc, fs.fog_of_scene(_doc("gpu_showcase")["fog"]), 8, rays, keys)
     # seven emissive spheres: two draws per light and march step taken
     assert np.array_equal(ca[:, 1], ca[:, 2] * 14)
+
+
+# ---------------------------------------------------------------- the term on random scenes
+
+def fuzz_scene(i, tmp_dir):
+    """Case i of fuzz_support.host_fuzz_case as (case, scene.Scene, hip.FlatScene, ora.Scene, PtFog)."""
+    import glshade_support as gs
+    from fuzz_support import host_fuzz_case
+
+    case = host_fuzz_case(i)
+    sc, flat, oc = gs.scene_pair(case["doc"], str(tmp_dir), "fuzz%d" % i)
+    return case, sc, flat, oc, fs.fog_of_scene(case["doc"]["fog"])
+
+
+FUZZ_SCENES, FUZZ_RAYS = 64, 600
+
+
+def test_inscatter_term_matches_reference_on_random_scenes(tmp_path):
+    """The host build against the restatement on the generator's scenes (overlapping, nested, coincident, half-grid geometry,
+    missing material ids, 1..150 objects, 0 / 1 / 8 / 9 / 12 lights) with random fog blocks: this is what says the inputs of
+    the GPU fuzz are clean -- a disagreement there then belongs to the device."""
+    total = nonzero = shadow = steps = nans = volumetric = 0
+    sizes, lights = set(), set()
+    for i in range(FUZZ_SCENES):
+        case, sc, flat, oc, fog = fuzz_scene(i, tmp_path)
+        rays, keys = _rays(oc, FUZZ_RAYS, np.random.default_rng([31, i]), 8)
+        La, Lb, ca, cb = _terms(oc, fog, case["depth"], rays, keys)
+        bad = np.flatnonzero(np.any(_bits(La) != _bits(Lb), axis=1) | np.any(ca != cb, axis=1))
+        assert bad.size == 0, (i, bad[:3], La[bad[:3]], Lb[bad[:3]], ca[bad[:3]], cb[bad[:3]])
+        total += FUZZ_RAYS
+        nans += int(np.count_nonzero(np.isnan(La)))
+        nonzero += int(np.count_nonzero(np.any(La != 0, axis=1)))
+        shadow += int(ca[:, 0].sum())
+        steps += int(ca[:, 2].sum())
+        volumetric += int(fog.gpu_volumetric)
+        sizes.add(case["nobj"])
+        lights.add(int(ca[:, 1].max()) // 48 if ca[:, 2].max() == 24 else -1)  # draws = 2 per light and step
+    assert FUZZ_SCENES >= 60 and total >= 30_000
+    assert min(sizes) == 1 and max(sizes) == 150
+    assert nans == 0
+    assert nonzero > total // 10 and shadow > total and steps > total  # the comparison is not over zeros
+    assert {0, 1, 8, 9, 12} <= lights, lights
+    assert FUZZ_SCENES // 2 < volumetric < FUZZ_SCENES  # mostly, not always, volumetric
 
 
 # ---------------------------------------------------------------- ABI and host layers

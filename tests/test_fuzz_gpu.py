@@ -7,40 +7,9 @@ import numpy as np
 import pytest
 
 from conftest import render_vs_oracle
+from fuzz_support import MAT_KINDS, random_doc as _random_doc  # noqa: F401  (the generator is shared with the fog and GL fuzz)
 
 pytestmark = pytest.mark.gpu
-
-MAT_KINDS = ["lambert", "metal", "dielectric", "emissive", "mirror"]
-
-
-def _random_doc(rng, nobj):
-    mats = []
-    for i in range(rng.integers(1, 8)):
-        k = MAT_KINDS[int(rng.integers(len(MAT_KINDS)))]
-        m = {"id": "m%d" % i, "type": k, "albedo": dict(zip("rgb", rng.uniform(0.1, 1.0, 3).round(3).tolist())),
-             "rough": float(rng.choice([0.0, 0.0, 0.05, 0.5, 1.0])), "ior": float(rng.choice([0.0, 1.1, 1.5, 2.4])),
-             "emit": dict(zip("rgb", rng.uniform(0.2, 1.0, 3).round(3).tolist())), "power": float(rng.uniform(1, 8)),
-             "absorption": dict(zip("rgb", rng.choice([0.0, 0.0, 0.2, 1.0], 3).tolist())),
-             "smoothness": float(rng.choice([0.0, 0.0, 0.7, 1.0]))}
-        mats.append(m)
-    objs = []
-    grid = lambda lo, hi: float(rng.integers(lo * 2, hi * 2 + 1)) / 2.0  # half-unit grid: coincident faces are common
-    for i in range(nobj):
-        kind = rng.choice(["sphere", "box", "box", "sphere", "sphere_light", "plane"], p=[0.3, 0.25, 0.15, 0.15, 0.1, 0.05])
-        pos = {"x": grid(-3, 3), "y": grid(0, 4), "z": grid(-3, 3)}
-        if kind == "box":
-            size = {"x": grid(0, 3), "y": grid(0, 3), "z": grid(0, 3)}
-        else:
-            size = {"x": float(rng.choice([0.25, 0.5, 1.0, 1.5])), "y": 0, "z": 0}
-        objs.append({"id": "o%d" % i, "type": str(kind), "position": pos, "size": size,
-                     "material_id": "m%d" % int(rng.integers(len(mats) + 1))})  # sometimes a missing id
-    cam = {"position": {"x": grid(-2, 2), "y": grid(1, 3), "z": 7.0}, "target": {"x": 0, "y": 1.5, "z": 0},
-           "up": {"x": 0, "y": 1, "z": 0}, "fov": float(rng.choice([35, 60, 90])), "aperture": float(rng.choice([0, 0, 0.2])),
-           "focus_dist": float(rng.choice([0, 7])), "aspect_ratio": float(rng.choice([0, 1.7777778]))}
-    sky = [None, {"type": "gradient", "horizon": {"r": 1, "g": 1, "b": 1}, "zenith": {"r": 0.3, "g": 0.5, "b": 1}},
-           {"type": "solid", "color": {"r": 0.7, "g": 0.8, "b": 0.9}}][int(rng.integers(3))]
-    return {"camera": cam, "objects": objs, "materials": mats, "sky": sky, "background": {"r": 0.1, "g": 0.1, "b": 0.15}}
-
 
 @pytest.fixture(scope="module")
 def contexts():

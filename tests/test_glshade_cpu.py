@@ -73,6 +73,55 @@ def test_host_build_equals_restatement_on_synthetic_scenes(name, tmp_path):
         assert totals[3] > 0  # rough-metal probes
 
 
+FUZZ_SCENES, FUZZ_JOBS, FUZZ_W, FUZZ_H, FUZZ_PASSES = 64, 400, 33, 20, 3
+
+
+def test_host_build_equals_restatement_on_random_scenes(tmp_path):
+    """The generator's scenes (fuzz_support.host_fuzz_case: overlapping, nested, coincident geometry, missing material ids,
+    1..150 objects, 0 / 1 / 8 / 9 / 12 lights, GL extras), depths 1 / 3 / 7 / 12, half of them with the random fog block:
+    the inputs of the GPU fuzz are clean when the host build and the restatement agree on them."""
+    from test_fog_cpu import fuzz_scene
+
+    totals = np.zeros(8, np.uint64)
+    n = with_fog = nans = 0
+    sizes, depths, nlights = set(), set(), set()
+    for i in range(FUZZ_SCENES):
+        case, sc, flat, o, fog = fuzz_scene(i, tmp_path)
+        jobs = _jobs(FUZZ_JOBS, FUZZ_W, FUZZ_H, FUZZ_PASSES, 500 + i)
+        ex = gs.extras(sc)
+        f = fog if case["fog"] else None
+        a, ca = gs.ref_passes(o, ex, FUZZ_W, FUZZ_H, case["depth"], SEED, jobs, f)
+        b, cb = gs.host_passes(flat, ex, FUZZ_W, FUZZ_H, case["depth"], SEED, jobs, f)
+        bad = np.flatnonzero((a.view(np.uint64) != b.view(np.uint64)).any(1) | (ca != cb).any(1))
+        assert bad.size == 0, (i, jobs[bad[:3]], a[bad[:3]], b[bad[:3]], ca[bad[:3]], cb[bad[:3]])
+        totals += ca.sum(0)
+        n += FUZZ_JOBS
+        with_fog += FUZZ_JOBS if case["fog"] else 0
+        nans += int(np.count_nonzero(np.isnan(b)))
+        sizes.add(case["nobj"])
+        depths.add(case["depth"])
+        nlights.add(sum(1 for k in range(len(sc.objects)) if _is_gl_light(sc, flat, k)))
+    assert FUZZ_SCENES >= 60 and n >= 20_000 and with_fog * 2 == n
+    assert min(sizes) == 1 and max(sizes) == 150 and {1, 12} <= depths
+    assert nans == 0
+    assert totals[0] == 16 * n and totals[1] > totals[0]  # every path, and bounces
+    assert totals[2] > n and totals[3] > 0 and totals[4] > 0  # shadow rays, rough-metal probes, draws
+    assert totals[5] > 0 and totals[7] > 0  # the fog term's shadow rays and march steps
+    assert {0, 1, 8, 9, 12} <= nlights, nlights
+
+
+def _is_gl_light(sc, flat, k):
+    """gl_is_light restated on the flattened scene: the material (index 0 for a missing id) is emissive with some emit > 0."""
+    from path_trace_golang_amd import capi
+
+    nmat = len(sc.materials)
+    if nmat == 0:
+        return False
+    mi = flat.objects[k].material
+    m = flat.materials[mi if 0 <= mi < nmat else 0]
+    return m.type == capi.PT_MAT_EMISSIVE and max(m.emit) > 0
+
+
 def test_synthetic_scenes_have_the_corners_they_are_for(tmp_path):
     docs = gs.synthetic_docs()
     sc, flat, _ = gs.scene_pair(docs["edge"], str(tmp_path), "edge")

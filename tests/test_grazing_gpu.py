@@ -161,3 +161,89 @@ def test_the_probes_do_graze(oracle):
         o = oracle.render(oracle.Scene(doc), 64, 36, 1, 1, seed=9)
         hit = float((o["accum"].sum(axis=2) == 0).mean())  # depth 1: a hit contributes nothing, a miss the sky
         assert 0.02 < hit < 0.98, (name, hit)
+
+
+# ---------------------------------------------------------------- axis-parallel rays from beyond the origin bound
+#
+# clip_ray32 (pt_kernels.h) never clips a ray with a direction component that is exactly 0 (its error term is infinite then),
+# and past origin_bound = 4 B such a ray takes the untrusted path that sends every record to the narrow phase.  That is meant
+# to be safe; these cameras check that it is: 5 scene sizes out on each axis, looking exactly along it at the shipped scenes,
+# once through a 10 m window and once through a needle so thin that the target's own coordinates absorb the screen offset
+# and two components of EVERY primary ray are exactly 0.
+
+AXES = {"+x": (1, 0, 0), "-x": (-1, 0, 0), "+y": (0, 1, 0), "-y": (0, -1, 0), "+z": (0, 0, 1), "-z": (0, 0, -1)}
+
+
+def _scene_bound_at_most(doc):
+    """An upper bound of the library's scene bound B: every finite object lies inside [-b, b]^3."""
+    b = 1.0
+    for o in doc["objects"]:
+        if o.get("type") == "plane":
+            continue
+        p, s = o.get("position", {}), o.get("size", {})
+        b = max(b, max(abs(p.get(k, 0.0)) for k in "xyz") + max(abs(s.get(k, 0.0)) for k in "xyz"))
+    return b
+
+
+def _axis_cameras(doc):
+    """{name: (camera, needle)}: from 5 B out on each axis towards a point near the scene camera's target."""
+    b = _scene_bound_at_most(doc)
+    t = doc["camera"].get("target", {})
+    target = np.array([t.get("x", 0.0) + 0.37, t.get("y", 0.0) + 0.23, t.get("z", 0.0) + 0.41])  # no zero coordinate
+    cams = {}
+    for name, axis in AXES.items():
+        pos = target - 5.0 * b * np.array(axis, float)  # looking along +axis from the far side
+        for needle in (False, True):
+            cam = _cam(tuple(pos), tuple(target), 5.0 * b * 2.0 ** -70 if needle else 5.0)
+            if axis[1] != 0:
+                cam["up"] = V(0, 0, -1)
+            cams[name + (" needle" if needle else " window")] = (cam, needle, b)
+    return cams
+
+
+def _shipped_doc(name):
+    import json
+
+    from conftest import scene_path
+
+    with open(scene_path(name)) as f:
+        return json.load(f)
+
+
+def test_axis_cameras_are_axis_parallel_and_outside_the_origin_bound(oracle):
+    import ctypes as C
+
+    from conftest import SCENE_NAMES
+
+    rng = np.random.default_rng(5)
+    u, v = rng.random(4000), rng.random(4000)
+    for scene_name in SCENE_NAMES:
+        doc = _shipped_doc(scene_name)
+        for name, (cam, needle, b) in _axis_cameras(doc).items():
+            axis = np.array(AXES[name.split()[0]], float)
+            oc = oracle.Scene({**doc, "camera": cam})
+            c = np.zeros(22)
+            oracle.lib().ora_camera_setup(C.byref(oc.c.camera), 32, 20, c.ctypes.data_as(C.POINTER(C.c_double)))
+            assert np.max(np.abs(c[0:3])) > 4.0 * b, (scene_name, name)  # outside origin_bound (and clip_bound = 3.5 B)
+            d = c[3:6] + c[6:9] * u[:, None] + c[9:12] * v[:, None] - c[0:3]  # camera.go:64-69 without a lens
+            along = d @ axis
+            assert np.all(along > 0), (scene_name, name)
+            if needle:  # every ray: the two other components exactly 0
+                assert np.all(d[:, axis == 0] == 0.0), (scene_name, name)
+
+
+def test_axis_parallel_far_cameras_match_oracle(gpu_ctx, oracle):
+    from conftest import SCENE_NAMES
+    from path_trace_golang_amd import scene
+
+    w, h, spp, depth, seed = 32, 20, 2, 5, 13
+    frames = 0
+    for scene_name in SCENE_NAMES:
+        doc = _shipped_doc(scene_name)
+        for name, (cam, needle, b) in _axis_cameras(doc).items():
+            d = {**doc, "camera": cam}
+            o = oracle.render(oracle.Scene(d), w, h, spp, depth, seed=seed)
+            assert o["stats"]["segments"] >= w * h * spp, (scene_name, name)
+            render_vs_oracle(gpu_ctx, scene.Scene.decode(d), o, w, h, spp, depth, seed, tag=(scene_name, name))
+            frames += 1
+    assert frames == len(SCENE_NAMES) * 12
