@@ -372,6 +372,17 @@ int64_t pt_debug_div_selftest(pt_ctx *ctx, int32_t millions, uint64_t seed);
  * child boxes not inside the parent's box, planes kept outside the tree}. */
 int32_t pt_debug_bvh_check(const pt_scene *scene, int32_t out[8]);
 
+/* Diagnostics only: replaces the primary rays of later frames on ctx.  `rays` is [n][6] doubles (origin x y z, direction x y z),
+ * the ray of pixel (x, y), sample s at index (y*width + x)*samples_per_px + s; the table is copied.  rays == NULL or n == 0 clears
+ * it (the default: the camera's rays).  While a table is set, every chunk's ray generation still runs -- stream state and draw
+ * counts are the camera's -- and a small kernel then overwrites the rays, so the chosen rays go through the shipped trace
+ * kernels of every form (split, nested, all-in-one, grouped, hierarchy with its primary pass, wavefront, walk32) untouched.  A
+ * frame whose width*height*samples_per_px differs from n fails with PT_ERR_INVALID; with fog on (pt_set_fog), GL shading
+ * (pt_set_shading) or several devices in the context it fails with PT_ERR_STATE.  Nothing is launched in either case and the
+ * context stays usable.  Any double is a legal component (zeros, subnormals, infinities, NaN): such rays take the reference's
+ * own scan. */
+int32_t pt_debug_set_primary_rays(pt_ctx *ctx, const double *rays, int64_t n);
+
 /* Diagnostics only: how a context that holds several devices collects the tiles of a frame on devices[0]: 0 = one
  * hipMemcpyPeerAsync per peer (the default), 1 = grouped ncclSend / ncclRecv through librccl.so (PTCORE_GATHER=rccl at
  * pt_create; the library is dlopen'ed then and only then). */

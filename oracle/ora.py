@@ -90,6 +90,15 @@ def lib():
         L.ora_sample.restype = None
         L.ora_sample.argtypes = [C.POINTER(OraScene), C.POINTER(OraConfig), C.c_int32, C.c_int32, C.c_int32, dp,
                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        u32p = C.POINTER(C.c_uint32)
+        L.ora_primary_ray.restype = None
+        L.ora_primary_ray.argtypes = [C.POINTER(OraScene), C.POINTER(OraConfig), C.c_int32, C.c_int32, C.c_int32, dp, dp]
+        L.ora_sample_ray.restype = None
+        L.ora_sample_ray.argtypes = [C.POINTER(OraScene), C.POINTER(OraConfig), C.c_int32, C.c_int32, C.c_int32, dp, dp, dp,
+                                     u32p, u32p]
+        L.ora_sample_rays.restype = None
+        L.ora_sample_rays.argtypes = [C.POINTER(OraScene), C.POINTER(OraConfig), C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("ora_sin", "ora_cos", "ora_tan", "ora_exp"):
             f = getattr(L, name)
             f.restype = C.c_double
@@ -240,6 +249,42 @@ def sample(scene: Scene, width: int, height: int, spp: int, depth: int, seed: in
     a, b = C.c_uint32(), C.c_uint32()
     L.ora_sample(C.byref(scene.c), C.byref(cfg), x, y, s, out, C.byref(a), C.byref(b))
     return list(out), a.value, b.value
+
+
+def primary_ray(scene: Scene, width: int, height: int, spp: int, depth: int, seed: int, x: int, y: int, s: int):
+    """The ray sample_once traces for (x, y, s): (origin, direction) as two lists."""
+    L = lib()
+    cfg = OraConfig(width, height, spp, depth, seed, 1, 0)
+    o, d = (C.c_double * 3)(), (C.c_double * 3)()
+    L.ora_primary_ray(C.byref(scene.c), C.byref(cfg), x, y, s, o, d)
+    return list(o), list(d)
+
+
+def sample_ray(scene: Scene, width: int, height: int, spp: int, depth: int, seed: int, x: int, y: int, s: int, orig, dir_):
+    """`sample` with the primary ray replaced by (orig, dir_) after the camera draws."""
+    L = lib()
+    cfg = OraConfig(width, height, spp, depth, seed, 1, 0)
+    d3 = C.c_double * 3
+    out = d3()
+    a, b = C.c_uint32(), C.c_uint32()
+    L.ora_sample_ray(C.byref(scene.c), C.byref(cfg), x, y, s, d3(*orig), d3(*dir_), out, C.byref(a), C.byref(b))
+    return list(out), a.value, b.value
+
+
+def sample_rays(scene: Scene, width: int, height: int, spp: int, depth: int, seed: int, rays):
+    """A whole frame of chosen primary rays: rays float64 [width*height*spp, 6] (origin, direction), the ray of pixel (x, y),
+    sample s at (y*width + x)*spp + s.  Returns (rgb f64 [n, 3], nseg u32 [n], ndraw u32 [n]), one row per sample."""
+    L = lib()
+    rays = np.ascontiguousarray(rays, dtype=np.float64)
+    n = width * height * spp
+    assert rays.shape == (n, 6)
+    cfg = OraConfig(width, height, spp, depth, seed, 1, 0)
+    rgb = np.zeros((n, 3))
+    nseg = np.zeros(n, np.uint32)
+    ndraw = np.zeros(n, np.uint32)
+    L.ora_sample_rays(C.byref(scene.c), C.byref(cfg), 0, 0, 0, n, rays.ctypes.data, rgb.ctypes.data,
+                      nseg.ctypes.data, ndraw.ctypes.data)
+    return rgb, nseg, ndraw
 
 
 def hit(kind: int, a, b, radius, orig, dir_, tmin, tmax):

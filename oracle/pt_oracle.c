@@ -805,23 +805,35 @@ static void frame_init(frame *f, const ora_scene *sc, const ora_config *cfg, hit
     f->heightMinus1 = (double)(cfg->height - 1);    /* renderer.go:98 */
 }
 
-/* one iteration of the sample loop, renderer.go:181-187 */
-static vec3 sample_once(const frame *f, int x, int y, int s, uint32_t *nseg, uint32_t *nexit, uint32_t *ndraw) {
-    randSource rng;
-    rng.state = ora_stream_init(f->cfg->seed, (uint64_t)y * (uint64_t)f->cfg->width + (uint64_t)x, (uint64_t)s);
-    rng.draws = 0;
+/* the head of one iteration of the sample loop, renderer.go:181-184: the stream of (pixel, sample), u, v, camera.getRay */
+static ray primary_ray(const frame *f, int x, int y, int s, randSource *rng) {
+    rng->state = ora_stream_init(f->cfg->seed, (uint64_t)y * (uint64_t)f->cfg->width + (uint64_t)x, (uint64_t)s);
+    rng->draws = 0;
     double flipY = f->heightMinus1 - (double)y;
-    double u = ((double)x + Float64(&rng)) * f->invWidth;
-    double vv = (flipY + Float64(&rng)) * f->invHeight;
-    ray r = getRay(&f->cam, &rng, u, vv);
+    double u = ((double)x + Float64(rng)) * f->invWidth;
+    double vv = (flipY + Float64(rng)) * f->invHeight;
+    return getRay(&f->cam, rng, u, vv);
+}
+
+/* one iteration of the sample loop, renderer.go:181-187; with `replace` the ray getRay returned is dropped for that one
+ * (test hook: the camera draws have happened, so stream and counts are those of the sample) */
+static vec3 sample_once_with(const frame *f, int x, int y, int s, const ray *replace, uint32_t *nseg, uint32_t *nexit,
+                             uint32_t *ndraw) {
+    randSource rng;
+    ray r = primary_ray(f, x, y, s, &rng);
+    if (replace) r = *replace;
     tracer tr = {f->world, f->nworld, &f->sc->sky, 0, 0};
     hitRecord rec;
     memset(&rec, 0, sizeof rec);
-    vec3 c = rayColorOpt(&tr, r, f->cfg->max_depth, &rng, &rec);
+    vec3 c = rayColorOpt(&tr, r, f->cfg->max_depth, &rng, &rec); /* renderer.go:185 */
     *nseg += tr.segments;
     *nexit += tr.exit_scans;
     *ndraw += rng.draws;
     return c;
+}
+
+static vec3 sample_once(const frame *f, int x, int y, int s, uint32_t *nseg, uint32_t *nexit, uint32_t *ndraw) {
+    return sample_once_with(f, x, y, s, NULL, nseg, nexit, ndraw);
 }
 
 void ora_sample(const ora_scene *sc, const ora_config *cfg, int32_t x, int32_t y, int32_t s, double out_rgb[3],
@@ -834,6 +846,50 @@ void ora_sample(const ora_scene *sc, const ora_config *cfg, int32_t x, int32_t y
     out_rgb[0] = col.x; out_rgb[1] = col.y; out_rgb[2] = col.z;
     if (nseg) *nseg = a;
     if (ndraw) *ndraw = c;
+    free(world);
+}
+
+/* ---- test hooks: the sample loop with chosen primary rays (tests/ray_inject_support.py) ---- */
+
+void ora_primary_ray(const ora_scene *sc, const ora_config *cfg, int32_t x, int32_t y, int32_t s, double orig[3], double dir[3]) {
+    frame f;
+    f.sc = sc; f.cfg = cfg; f.world = NULL; f.nworld = 0; /* the ray needs the camera alone */
+    f.cam = newCamera(&sc->camera, cfg->width, cfg->height);
+    f.invWidth = 1.0 / (double)(cfg->width - 1);   /* renderer.go:95 */
+    f.invHeight = 1.0 / (double)(cfg->height - 1); /* renderer.go:96 */
+    f.heightMinus1 = (double)(cfg->height - 1);    /* renderer.go:98 */
+    randSource rng;
+    ray r = primary_ray(&f, x, y, s, &rng);
+    orig[0] = r.orig.x; orig[1] = r.orig.y; orig[2] = r.orig.z;
+    dir[0] = r.dir.x; dir[1] = r.dir.y; dir[2] = r.dir.z;
+}
+
+void ora_sample_ray(const ora_scene *sc, const ora_config *cfg, int32_t x, int32_t y, int32_t s, const double orig[3],
+                    const double dir[3], double out_rgb[3], uint32_t *nseg, uint32_t *ndraw) {
+    const double row[6] = {orig[0], orig[1], orig[2], dir[0], dir[1], dir[2]};
+    ora_sample_rays(sc, cfg, x, y, s, 1, row, out_rgb, nseg, ndraw);
+}
+
+/* n samples in table order from (x, y, s) on: s fastest, then x, then y -- ray k of a whole-frame table has index
+ * (y*width + x)*spp + s.  rays is [n][6] (origin, direction), out_rgb [n][3]. */
+void ora_sample_rays(const ora_scene *sc, const ora_config *cfg, int32_t x, int32_t y, int32_t s, int64_t n, const double *rays,
+                     double *out_rgb, uint32_t *nseg, uint32_t *ndraw) {
+    hittable *world = (hittable *)calloc((size_t)(sc->nobjects > 0 ? sc->nobjects : 1), sizeof(hittable));
+    frame f;
+    frame_init(&f, sc, cfg, world);
+    const int64_t spp = cfg->spp > 0 ? cfg->spp : 1;
+    int64_t k0 = ((int64_t)y * cfg->width + x) * spp + s;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t k = k0 + i, pix = k / spp;
+        ray r;
+        r.orig = v(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
+        r.dir = v(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+        uint32_t a = 0, b = 0, c = 0;
+        vec3 col = sample_once_with(&f, (int)(pix % cfg->width), (int)(pix / cfg->width), (int)(k % spp), &r, &a, &b, &c);
+        out_rgb[3 * i] = col.x; out_rgb[3 * i + 1] = col.y; out_rgb[3 * i + 2] = col.z;
+        if (nseg) nseg[i] = a;
+        if (ndraw) ndraw[i] = c;
+    }
     free(world);
 }
 

@@ -106,6 +106,18 @@ int ora_render_window(const ora_scene *sc, const ora_config *cfg, int32_t x0, in
 void ora_sample(const ora_scene *sc, const ora_config *cfg, int32_t x, int32_t y, int32_t s,
                 double out_rgb[3], uint32_t *nseg, uint32_t *ndraw);
 
+/* Test hooks for chosen primary rays.  ora_primary_ray: the ray sample_once traces for (x, y, s), i.e. what camera.getRay
+ * returned (renderer.go:181-184).  ora_sample_ray: ora_sample with that ray replaced by (orig, dir) after getRay -- the camera
+ * draws still happen, so the stream and the draw count line up with a renderer that generated a ray and dropped it.
+ * ora_sample_rays: the same for n consecutive samples in table order from (x, y, s) on (s fastest, then x, then y: ray k of a
+ * whole-frame table has index (y*width + x)*spp + s); rays is [n][6] (origin, direction), out_rgb [n][3], nseg / ndraw [n] or
+ * NULL. */
+void ora_primary_ray(const ora_scene *sc, const ora_config *cfg, int32_t x, int32_t y, int32_t s, double orig[3], double dir[3]);
+void ora_sample_ray(const ora_scene *sc, const ora_config *cfg, int32_t x, int32_t y, int32_t s, const double orig[3],
+                    const double dir[3], double out_rgb[3], uint32_t *nseg, uint32_t *ndraw);
+void ora_sample_rays(const ora_scene *sc, const ora_config *cfg, int32_t x, int32_t y, int32_t s, int64_t n, const double *rays,
+                     double *out_rgb, uint32_t *nseg, uint32_t *ndraw);
+
 /* ---- unit-level entry points for KATs ---- */
 double ora_sin(double x);   /* Go math.Sin (Cephes), pure-Go path */
 double ora_cos(double x);

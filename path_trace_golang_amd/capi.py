@@ -146,6 +146,7 @@ SYMBOLS = [
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
     ("pt_debug_bvh_check", C.c_int32, [C.POINTER(PtScene), C.POINTER(C.c_int32)]),
     ("pt_debug_gather_mode", C.c_int32, [_vp]),
+    ("pt_debug_set_primary_rays", C.c_int32, [_vp, C.POINTER(C.c_double), C.c_int64]),  # additive to ABI 4 (see has())
 ]
 
 
@@ -180,7 +181,7 @@ def load():
     return _lib
 
 
-ADDITIVE = ("pt_set_shading", "pt_shading_last_stats")  # added within ABI 4: detected by presence
+ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_rays")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:
@@ -219,6 +220,20 @@ class Context:
         if self._h:
             load().pt_destroy(self._h)
             self._h = _vp()
+
+    def set_primary_rays(self, rays=None) -> None:
+        """pt_debug_set_primary_rays: `rays` (float64 [n, 6]: origin, direction; the ray of pixel (x, y), sample s at
+        (y*width + x)*spp + s) replaces the camera's primary rays in the later frames of this context; None clears."""
+        L = load()
+        if rays is None:
+            check(L.pt_debug_set_primary_rays(self._h, None, 0))
+            return
+        import numpy as np
+
+        a = np.ascontiguousarray(rays, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 6:
+            raise ValueError("rays must be [n, 6]")
+        check(L.pt_debug_set_primary_rays(self._h, a.ctypes.data_as(C.POINTER(C.c_double)), a.shape[0]))
 
     def __enter__(self):
         return self

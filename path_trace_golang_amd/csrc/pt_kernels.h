@@ -31,6 +31,7 @@
 //   raygen_kernel / raygen_lens_kernel   one thread per job: stream init, pixel jitter and camera.getRay
 //                   (camera.go:60-74, renderer.go:181-184) as a coherent pre-pass of every chunk; with a thin lens a
 //                   lane walks a column of four jobs so that a wave does not wait for its unluckiest rejection loop.
+//   inject_rays_kernel   diagnostics (pt_debug_set_primary_rays): overwrites the primary rays of a chunk with the caller's table.
 //   resolve_kernel  per pixel slot, adds the chunk's sample radiances IN SAMPLE ORDER
 //                   to the running sum (renderer.go:186), and on request finishes the
 //                   pixel: 1/spp, sqrt gamma, *255.999, clamp, truncate (renderer.go:190-221).
@@ -1321,6 +1322,22 @@ __device__ __forceinline__ void store_radiance(double *L, size_t job, double x, 
     reinterpret_cast<double4 *>(L)[job] = make_double4(x, y, z, 0.0);
 }
 
+// The job -> (pixel, sample) map of a chunk, shared by everything that reads or writes the primary-ray planes: row q = job >> 6 of 64
+// consecutive jobs is sample sl of the chunk for the 8x8 sub-block blk = q / S (16 sub-blocks per 32x32 tile, the shard's tiles in
+// order), and lane p = job & 63 is the pixel inside that sub-block.  A wave is one 8x8 pixel block of one sample.
+__device__ __forceinline__ void block_pixel(const DevFrame &F, uint32_t blk, uint32_t p, uint32_t &x, uint32_t &y) {
+    const uint32_t lt = blk >> 4, sb = blk & 15u;
+    const uint32_t t = (uint32_t)F.shard_index + lt * (uint32_t)F.shard_count;
+    const uint32_t ty = t / (uint32_t)F.ntx, tx = t - ty * (uint32_t)F.ntx;
+    x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
+    y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+}
+__device__ __forceinline__ void job_pixel(const DevFrame &F, uint32_t q, uint32_t p, uint32_t &x, uint32_t &y, uint32_t &sl) {
+    const uint32_t blk = q / F.S;
+    sl = q - blk * F.S;
+    block_pixel(F, blk, p, x, y);
+}
+
 // Ray generation pre-pass: one thread per job of the chunk, all lanes busy and neighbouring
 // lanes on neighbouring pixels.  Per job: stream init, u then v (renderer.go:182-183),
 // camera.getRay with the lens rejection loop (camera.go:60-74, math.go:74-84).  Writes the primary
@@ -1334,13 +1351,8 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_kernel(const DevFrame F, cons
     // job -> (tile, sub-block, sample, pixel)
     const uint32_t p = myjob & 63u;
     const uint32_t q = __builtin_amdgcn_readfirstlane(myjob >> 6);  // the wave's row of 64 jobs: tile, sub-block and sample are wave-uniform (scalar unit)
-    const uint32_t blk = q / F.S;
-    const uint32_t sl = q - blk * F.S;
-    const uint32_t lt = blk >> 4, sb = blk & 15u;
-    const uint32_t t = (uint32_t)F.shard_index + lt * (uint32_t)F.shard_count;
-    const uint32_t ty = t / (uint32_t)F.ntx, tx = t - ty * (uint32_t)F.ntx;
-    const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
-    const uint32_t y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+    uint32_t x, y, sl;
+    job_pixel(F, q, p, x, y, sl);
     if (!(x < (uint32_t)F.width && y < (uint32_t)F.height)) {
         ray_ndraw[myjob] = 0xffffu;
         return;
@@ -1404,6 +1416,23 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_kernel(const DevFrame F, cons
     ray_ndraw[myjob] = (uint16_t)(nd < 0xfffeu ? nd : 0xfffeu);
 }
 
+// Diagnostics (pt_debug_set_primary_rays): replaces the primary rays ray generation left in the six planes by the caller's table,
+// [W*H*spp][6] doubles (origin, direction) indexed (y*W + x)*spp + sample.  Runs right after the ray-generation launch of a chunk;
+// jobs whose pixel lies outside the frame (0xffff) are left alone, and so are the stream state and the draw count: the camera draws
+// have happened, the ray they made is dropped.
+__global__ __launch_bounds__(PT_BLOCK) void inject_rays_kernel(const DevFrame F, const double *__restrict__ table, uint64_t nrays, uint32_t spp,
+                                                                 double *__restrict__ ray, const uint16_t *__restrict__ ray_ndraw) {
+    const uint32_t myjob = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (myjob >= F.njobs || ray_ndraw[myjob] == 0xffffu) return;
+    uint32_t x, y, sl;
+    job_pixel(F, myjob >> 6, myjob & 63u, x, y, sl);
+    const uint64_t k = ((uint64_t)y * (uint64_t)(uint32_t)F.width + (uint64_t)x) * spp + (uint64_t)(F.s0 + sl);
+    if (F.s0 + sl >= spp || k >= nrays) return;  // (the host refuses a frame whose size differs from the table's)
+    const double *r = table + 6 * k;
+    const size_t nj = F.njobs;
+    for (int c = 0; c < 6; c++) ray[(size_t)c * nj + myjob] = r[c];
+}
+
 // Ray generation for a thin-lens camera (lens_radius > 0).  The lens sample is a rejection loop (randomInUnitSphere,
 // math.go:74-84: 1.9 attempts on average, the unluckiest of 64 lanes needs 6-7), and in raygen_kernel a wave waits for its
 // unluckiest lane on every job: 2.75 ms of a 4.4 ms launch.  Here a wave owns PT_RG_ROWS rows of 64 jobs and a lane walks
@@ -1437,13 +1466,8 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_lens_kernel(const DevFrame F,
         if (myjob < F.njobs) {
             const uint32_t p = lane;
             const uint32_t q = row0 + (uint32_t)k;
-            const uint32_t blk = q / F.S;
-            const uint32_t sl = q - blk * F.S;
-            const uint32_t lt = blk >> 4, sb = blk & 15u;
-            const uint32_t t = (uint32_t)F.shard_index + lt * (uint32_t)F.shard_count;
-            const uint32_t ty = t / (uint32_t)F.ntx, tx = t - ty * (uint32_t)F.ntx;
-            const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
-            const uint32_t y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+            uint32_t x, y, sl;
+            job_pixel(F, q, p, x, y, sl);
             if (x < (uint32_t)F.width && y < (uint32_t)F.height) {
                 const uint64_t pixel = (uint64_t)y * (uint64_t)(uint32_t)F.width + (uint64_t)x;
                 uint64_t rs = ptm::stream_init(F.seed_key, pixel, (uint64_t)(F.s0 + sl));
@@ -1548,11 +1572,8 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_lens_pool_kernel(const DevFra
             const uint32_t p = lane;
             uint32_t sl = sl0 + k, blk = blk0;  // row0 + k = blk * S + sl
             while (sl >= F.S) { sl -= F.S; blk++; }
-            const uint32_t lt = blk >> 4, sb = blk & 15u;
-            const uint32_t t = (uint32_t)F.shard_index + lt * (uint32_t)F.shard_count;
-            const uint32_t ty = t / (uint32_t)F.ntx, tx = t - ty * (uint32_t)F.ntx;
-            const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
-            const uint32_t y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+            uint32_t x, y;
+            block_pixel(F, blk, p, x, y);
             if (x < (uint32_t)F.width && y < (uint32_t)F.height) {
                 const uint64_t pixel = (uint64_t)y * (uint64_t)(uint32_t)F.width + (uint64_t)x;
                 uint64_t rs = ptm::stream_init(F.seed_key, pixel, (uint64_t)(F.s0 + sl));

@@ -182,6 +182,15 @@ __global__ __launch_bounds__(PT_BLOCK, PT_WALK_WAVES) void wf_walk32_kernel(cons
                         const float tl = (float)(tmin - ts);
                         tminf = __builtin_fmaxf(tl - (__builtin_fabsf(tl) * 1e-2f + 1e-6f), 0.0f);  // a little below tMin - ts
                         tmin_hi = __builtin_fmaxf(tl, 0.0f) * 1.01f + 1e-6f;                        // a little above
+                        // A slab whose parameters are NaN or infinite constrains nothing (an infinite reciprocal: a zero or
+                        // FP32-subnormal direction component; a product past FLT_MAX).  That is on the safe side for a node, which
+                        // only lists one candidate more, but not for a core: a ray PARALLEL to a slab of the core and outside it
+                        // would count as piercing the core and tmaxf would shrink to a hit that does not exist.  With every
+                        // reciprocal so small that no product with a centre, a half extent or the origin (all within
+                        // origin_bound) can leave the finite range, all three slabs are really tested; any other ray takes no
+                        // bound from a core: with tmin_hi = inf no slot counts as left after tMin or as entered from outside.
+                        const float aiv_max = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ivx), __builtin_fabsf(ivy)), __builtin_fabsf(ivz));
+                        if (!(aiv_max * (4.0f * F.origin_bound) < 3.0e38f)) tmin_hi = __builtin_inff();
                         float tmx = __builtin_inff();
                         if (MODE == 0 && F.planes_y) {
                             // a plane with the normal (0, 1, 0) is certainly hit at t = (py - oy) / dy when |dy| is clear of the

@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -96,6 +97,8 @@ struct Device {
     DevBuf<double> ray;
     DevBuf<unsigned long long> ray_rng;
     DevBuf<uint16_t> ray_ndraw;
+    DevBuf<double> inject;            // pt_debug_set_primary_rays: the table's device copy
+    uint64_t inject_gen = 0;          // generation of the table it holds (0 = none)
     DevBuf<uint32_t> job_seg, job_draw;
     DevBuf<double> acc;
     DevBuf<uint32_t> acc_seg, acc_draw;
@@ -260,6 +263,9 @@ struct pt_ctx {
     std::vector<pt_gl_material> gl_extras;
     pt_shading_stats shading_last{};
     int shading_pending = 0;  // as fog_pending, for the GL counters
+    // pt_debug_set_primary_rays: [n][6] rays that replace ray generation's (empty = none, the default)
+    std::vector<double> inject_rays;
+    uint64_t inject_gen = 0;  // bumped by every call that sets a table
 };
 
 namespace {
@@ -1181,6 +1187,17 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
                                d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(eg.b, d.stream));
+        if (!ctx->inject_rays.empty()) {  // pt_debug_set_primary_rays: the table's rays over ray generation's
+            if (d.inject_gen != ctx->inject_gen) {
+                HIP_TRY(hipStreamSynchronize(d.stream));
+                HIP_TRY(d.inject.reserve(ctx->inject_rays.size()));
+                HIP_TRY(hipMemcpy(d.inject.p, ctx->inject_rays.data(), ctx->inject_rays.size() * sizeof(double), hipMemcpyHostToDevice));
+                d.inject_gen = ctx->inject_gen;
+            }
+            hipLaunchKernelGGL(ptk::inject_rays_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, F, d.inject.p,
+                               (uint64_t)(ctx->inject_rays.size() / 6), (uint32_t)fr.cfg.samples_per_px, d.ray.p, d.ray_ndraw.p);
+            HIP_TRY(hipGetLastError());
+        }
         if (fr.wavefront) {
             if (int32_t rc = dev_step_wavefront(ctx, d, F, B)) return rc;
         } else {
@@ -1638,6 +1655,15 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
     if (int32_t rc = scene_prepare(ctx, scene)) return rc;
     const SceneData &sd = ctx->sd;
     Frame &fr = ctx->frame;
+    if (!ctx->inject_rays.empty()) {  // pt_debug_set_primary_rays: refuse what the table does not cover before anything is launched
+        if (ctx->fog_on) return fail(PT_ERR_STATE, "injected primary rays: not available with fog on (pt_set_fog)");
+        if (ctx->shading_model != PT_SHADING_CPU) return fail(PT_ERR_STATE, "injected primary rays: not available with GL shading (pt_set_shading)");
+        if (ctx->devs.size() != 1) return fail(PT_ERR_STATE, "injected primary rays: not available on a context with several devices");
+        const uint64_t want = (uint64_t)cfg->width * (uint64_t)cfg->height * (uint64_t)std::max(0, cfg->samples_per_px);
+        if (want != ctx->inject_rays.size() / 6)
+            return fail(PT_ERR_INVALID, "injected primary rays: the table holds " + std::to_string(ctx->inject_rays.size() / 6) + " rays, the frame needs width*height*samples_per_px = " +
+                                            std::to_string(want));
+    }
     fr = Frame();
     fr.cfg = *cfg;
     std::memset(&ctx->fog_last, 0, sizeof ctx->fog_last);
@@ -2013,7 +2039,7 @@ void pt_destroy(pt_ctx *ctx) {
     for (Device &d : ctx->devs) {
         if (hipSetDevice(d.ordinal) != hipSuccess) continue;
         if (d.own_stream) (void)hipStreamSynchronize(d.own_stream);
-        d.ray.release(); d.ray_rng.release(); d.ray_ndraw.release();
+        d.ray.release(); d.ray_rng.release(); d.ray_ndraw.release(); d.inject.release();
         d.objs.release(); d.mats.release(); d.bsph.release(); d.bbox.release(); d.plane_idx.release(); d.bvh_nodes.release(); d.bvh_objs.release(); d.bvh_cores.release(); d.L.release(); d.job_seg.release(); d.job_draw.release();
         d.prof.release();
         d.bsph_diel.release(); d.bbox_diel.release();
@@ -2211,6 +2237,25 @@ int64_t pt_debug_scan_mismatches(pt_ctx *ctx) {
                      (int)(s[0] >> 32), v[0], (int)(uint32_t)s[0], v[1], s[3], v[2], v[3], v[4], v[5], v[6], v[7]);
     }
     return (int64_t)g_mismatches;
+}
+
+int32_t pt_debug_set_primary_rays(pt_ctx *ctx, const double *rays, int64_t n) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (n < 0) return fail(PT_ERR_INVALID, "pt_debug_set_primary_rays: n is negative");
+    if (n > (int64_t)1 << 31) return fail(PT_ERR_INVALID, "pt_debug_set_primary_rays: more than 2^31 rays");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_debug_set_primary_rays while a frame is open");
+    if (!rays || n == 0) {  // back to ray generation's own rays (the device copy is kept for a later table)
+        ctx->inject_rays.clear();
+        return PT_OK;
+    }
+    try {
+        ctx->inject_rays.assign(rays, rays + 6 * (size_t)n);
+    } catch (const std::bad_alloc &) {
+        ctx->inject_rays.clear();
+        return fail(PT_ERR_NOMEM, "pt_debug_set_primary_rays: out of host memory");
+    }
+    ctx->inject_gen++;
+    return PT_OK;
 }
 
 int32_t pt_shard_tiles(int32_t width, int32_t height, const pt_shard *shard, int32_t *ntiles_local, int32_t *ntiles_x,
