@@ -3,7 +3,8 @@
 //
 // Reference flags kept verbatim: -scene -mode -gpu -headless -out.
 // Additive flags: -width -height -spp -depth (override the mode preset), -seed, -devices,
-// -scene-settings (the editor's scene-settings override, internal/ui/app.go:60-75; off = main.go:52).
+// -scene-settings (the editor's scene-settings override, internal/ui/app.go:60-75; off = main.go:52),
+// -noise -noise-step (render until the frame noise is at or below the target, -spp being the cap; DESIGN 3.9).
 package main
 
 import (
@@ -31,6 +32,8 @@ func main() {
 	seed := flag.Uint64("seed", 1, "sample-stream seed")
 	devices := flag.Int("devices", 1, "number of GPUs to tile the image over")
 	sceneSettings := flag.Bool("scene-settings", false, "let the scene file's settings block override the mode preset")
+	noise := flag.Float64("noise", 0, "render until the frame noise is at or below this target, -spp being the cap (0 = off, or PATHTRACER_GPU_NOISE)")
+	noiseStep := flag.Int("noise-step", 16, "samples per pixel between two noise checks (or PATHTRACER_GPU_NOISE_STEP)")
 	flag.Parse()
 	log.Printf("flags: scene=%s mode=%s headless=%v out=%s\n", *scenePath, *mode, *headless, *output)
 
@@ -38,6 +41,11 @@ func main() {
 		engine.SetBackend(engine.BackendGPU) // RenderInto -> renderIntoGPU -> hip.Render (see INTEGRATION.md)
 		hip.SetDevices(*devices)
 		hip.SetSeed(*seed)
+		noiseGiven := false
+		flag.Visit(func(f *flag.Flag) { noiseGiven = noiseGiven || f.Name == "noise" || f.Name == "noise-step" })
+		if noiseGiven { // else the environment decides
+			hip.SetNoiseTarget(*noise, *noiseStep)
+		}
 	} else {
 		engine.SetBackend(engine.BackendCPU)
 	}
@@ -82,6 +90,11 @@ func main() {
 	if err != nil {
 		log.Println("headless render error:", fmt.Errorf("render scene: %w", err))
 		os.Exit(1)
+	}
+	if *useGPU {
+		if n, z := hip.LastFrame(); z > 0 {
+			log.Printf("rendered %dx%d, %d of at most %d spp (noise %.6g)\n", s.Width, s.Height, n, s.SamplesPerPx, z)
+		}
 	}
 	if err := engine.SavePNG(*output, img); err != nil {
 		log.Println("headless render error:", fmt.Errorf("save png: %w", err))

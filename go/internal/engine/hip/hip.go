@@ -47,6 +47,12 @@ var (
 	initErr error // sticky, like gpu.go:279-286
 	devices = 1
 	seed    = uint64(1)
+
+	noiseSet    bool // false: PATHTRACER_GPU_NOISE / PATHTRACER_GPU_NOISE_STEP decide
+	noiseTarget float64
+	noiseStep   = 16
+	lastSpp     int     // samples per pixel of the last frame Render finished
+	lastNoise   float64 // its frame noise (0 without a noise target)
 )
 
 // SetDevices selects how many GPUs (ordinals 0..n-1) the frame is tiled over.
@@ -68,6 +74,42 @@ func SetDevices(n int) {
 
 // SetSeed selects the sample streams (the CPU engine seeds from the clock, random.go:14-16).
 func SetSeed(s uint64) { seed = s }
+
+// SetNoiseTarget makes Render stop at the first check where the frame noise (pt_noise_estimate, DESIGN 3.9) is at or below
+// target, checking every step samples per pixel, with cfg.SamplesPerPx as the cap.  target <= 0 turns the rule off.
+func SetNoiseTarget(target float64, step int) {
+	mu.Lock()
+	defer mu.Unlock()
+	noiseSet = true
+	noiseTarget = target
+	if step >= 1 {
+		noiseStep = step
+	} else {
+		noiseStep = 16
+	}
+}
+
+// LastFrame reports the samples per pixel the last Render finished with and, when a noise target was set, its noise.
+func LastFrame() (spp int, noise float64) {
+	mu.Lock()
+	defer mu.Unlock()
+	return lastSpp, lastNoise
+}
+
+// noiseRule: the target and step in force (SetNoiseTarget, else the environment; 0 = off).
+func noiseRule() (float64, int) {
+	if noiseSet {
+		return noiseTarget, noiseStep
+	}
+	target, step := 0.0, 16
+	if v, err := strconv.ParseFloat(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_NOISE")), 64); err == nil && v > 0 {
+		target = v
+	}
+	if v, err := strconv.Atoi(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_NOISE_STEP"))); err == nil && v >= 1 {
+		step = v
+	}
+	return target, step
+}
 
 func lastError(what string) error {
 	return fmt.Errorf("%s: %s", what, C.GoString(C.pt_last_error()))
@@ -296,13 +338,27 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 	if err := setShading(sc); err != nil {
 		return err
 	}
+	target, nstep := noiseRule()
+	toNoise := target > 0
+	var on C.int32_t
+	if toNoise {
+		on = 1
+	}
+	if rc := C.pt_set_moments(ctx, on); rc != C.PT_OK {
+		return lastError("pt_set_moments")
+	}
+	lastSpp, lastNoise = 0, 0
 	pc := C.pt_config{width: C.int32_t(cfg.Width), height: C.int32_t(cfg.Height),
 		samples_per_px: C.int32_t(cfg.SamplesPerPx), max_depth: C.int32_t(cfg.MaxDepth), seed: C.uint64_t(seed)}
 	pix := (*C.uint8_t)(unsafe.Pointer(&img.Pix[0]))
+	if toNoise {
+		return renderToNoise(cs, &pc, cfg, img, pix, progress, target, nstep)
+	}
 	if progress == nil {
 		if rc := C.pt_render(ctx, cs, &pc, pix, C.int32_t(img.Stride), nil, nil, nil, nil); rc != C.PT_OK {
 			return lastError("pt_render")
 		}
+		lastSpp = cfg.SamplesPerPx
 		return nil
 	}
 	if rc := C.pt_begin(ctx, cs, &pc); rc != C.PT_OK {
@@ -336,6 +392,59 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 	}
 	if err == nil {
 		progress()
+		lastSpp = int(done)
+	}
+	return err
+}
+
+// renderToNoise: pt_begin with cfg.SamplesPerPx as the cap, then steps of nstep samples with a noise check after each;
+// stops at the first check with at least 2 samples done and noise <= target.  The image is that of a frame of the
+// samples done.  Called with mu held on a locked OS thread.
+func renderToNoise(cs *C.pt_scene, pc *C.pt_config, cfg RenderConfig, img *image.RGBA, pix *C.uint8_t, progress func(),
+	target float64, nstep int) error {
+	if rc := C.pt_begin(ctx, cs, pc); rc != C.PT_OK {
+		return lastError("pt_begin")
+	}
+	var done C.int32_t
+	var nz C.pt_noise
+	var err error
+	for int(done) < cfg.SamplesPerPx {
+		n := cfg.SamplesPerPx - int(done)
+		if nstep < n {
+			n = nstep
+		}
+		if rc := C.pt_step(ctx, C.int32_t(n), &done); rc != C.PT_OK {
+			err = lastError("pt_step")
+			break
+		}
+		if progress != nil {
+			if rc := C.pt_read(ctx, pix, C.int32_t(img.Stride), nil); rc != C.PT_OK {
+				err = lastError("pt_read")
+				break
+			}
+			progress()
+		}
+		if rc := C.pt_noise_estimate(ctx, &nz); rc != C.PT_OK {
+			err = lastError("pt_noise_estimate")
+			break
+		}
+		if int(done) >= 2 && float64(nz.noise) <= target {
+			break
+		}
+	}
+	if err == nil && (progress == nil || cfg.SamplesPerPx <= 0) {
+		if rc := C.pt_read(ctx, pix, C.int32_t(img.Stride), nil); rc != C.PT_OK {
+			err = lastError("pt_read")
+		}
+	}
+	if rc := C.pt_end(ctx, nil); rc != C.PT_OK && err == nil {
+		err = lastError("pt_end")
+	}
+	if err == nil {
+		if progress != nil {
+			progress()
+		}
+		lastSpp, lastNoise = int(done), float64(nz.noise)
 	}
 	return err
 }

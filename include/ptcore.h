@@ -345,6 +345,40 @@ int32_t pt_set_shading(pt_ctx *ctx, const pt_shading *s);
 int32_t pt_shading_last_stats(pt_ctx *ctx, pt_shading_stats *out);
 
 /*
+ * Second moments and the frame noise figure (additive to ABI 4).  Off unless asked for: with moments off
+ * nothing is allocated or launched.
+ *   pt_set_moments(ctx, on) : default 0; later frames on ctx (pt_begin ... pt_end, pt_render) also collect, per pixel and
+ *                             channel, Q = the sum over the samples done of L*L, next to accum's S = the sum of L.  L is the
+ *                             radiance the pixel receives (fog included; in GL mode a pass sum).  48 B per pixel on the
+ *                             devices, outside PTCORE_L_BUDGET_MB.  pt_render_tiles_device neither collects moments nor fails.
+ *   pt_read_moments         : m2 = width*height*3 doubles, row-major like accum: Q.
+ *   pt_noise_estimate       : the noise of the frame, computed on the device.  With n = samples done, per pixel
+ *                                 m_c = S_c / n                                   (c = r, g, b)
+ *                                 v_c = max(0, Q_c / n - m_c * m_c) / (n - 1)     variance of the pixel's mean
+ *                                 e2  = ((v_r + v_g + v_b) / 3) / max((m_r + m_g + m_b) / 3, 0.01)^2
+ *                             and noise = sqrt(sum of e2 / pixels), max_pixel = the largest e2, pixels = width*height.  A
+ *                             pixel whose e2 is NaN or infinite contributes 0 and is counted in bad_pixels.  With n < 2
+ *                             noise and max_pixel are +inf.  The sum is taken over a fixed tree (per block on the device,
+ *                             blocks and devices in order on the host): the same bits every time for one context shape.
+ * Both reads are valid between pt_begin and pt_end once a step has run, and after pt_end / pt_render until the next frame
+ * opens on ctx; otherwise, and for a frame rendered with moments off, they return PT_ERR_STATE (the context stays usable).
+ * A host that wants "render until the noise is at or below T" steps a pt_begin frame whose samples_per_px is the cap and
+ * stops at the first check with n >= 2 and noise <= T; the image at the stop is the image of a frame of n samples.
+ */
+typedef struct pt_noise {
+    double noise;
+    double max_pixel;
+    uint64_t pixels;
+    uint64_t bad_pixels;
+    int32_t spp; /* samples done (n) */
+    int32_t reserved;
+} pt_noise;
+
+int32_t pt_set_moments(pt_ctx *ctx, int32_t on);
+int32_t pt_read_moments(pt_ctx *ctx, double *m2);
+int32_t pt_noise_estimate(pt_ctx *ctx, pt_noise *out);
+
+/*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the
  * environment at pt_create, the trace kernel runs a build that counts, per code
  * section, wave executions, active lanes and shader-clock cycles.  Copies up to n

@@ -96,6 +96,14 @@ class PtShadingStats(C.Structure):
 PT_SHADING_CPU, PT_SHADING_GL = 0, 1
 
 
+class PtNoise(C.Structure):  # pt_noise: the frame noise figure of pt_noise_estimate (the metric is stated in include/ptcore.h)
+    _fields_ = [("noise", C.c_double), ("max_pixel", C.c_double), ("pixels", C.c_uint64), ("bad_pixels", C.c_uint64),
+                ("spp", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class PtShard(C.Structure):
     _fields_ = [("index", C.c_int32), ("count", C.c_int32)]
 
@@ -141,6 +149,9 @@ SYMBOLS = [
     ("pt_fog_last_stats", C.c_int32, [_vp, C.POINTER(PtFogStats)]),
     ("pt_set_shading", C.c_int32, [_vp, C.POINTER(PtShading)]),          # additive to ABI 4 (see has())
     ("pt_shading_last_stats", C.c_int32, [_vp, C.POINTER(PtShadingStats)]),
+    ("pt_set_moments", C.c_int32, [_vp, C.c_int32]),                     # additive to ABI 4 (see has())
+    ("pt_read_moments", C.c_int32, [_vp, C.POINTER(C.c_double)]),
+    ("pt_noise_estimate", C.c_int32, [_vp, C.POINTER(PtNoise)]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
@@ -181,7 +192,8 @@ def load():
     return _lib
 
 
-ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_rays")  # added within ABI 4: detected by presence
+ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_rays", "pt_set_moments", "pt_read_moments",
+            "pt_noise_estimate")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:

@@ -60,6 +60,8 @@ struct Core {
     decltype(&pt_end) end = nullptr;
     decltype(&pt_set_fog) set_fog = nullptr;
     decltype(&pt_set_shading) set_shading = nullptr;  // optional (additive to ABI 4): null in an older build
+    decltype(&pt_set_moments) set_moments = nullptr;  // optional, as set_shading (the noise target needs all three)
+    decltype(&pt_noise_estimate) noise_estimate = nullptr;
     std::string error;  // sticky load error, like the reference's cached GL init failure (gpu.go:279-286)
 };
 
@@ -68,6 +70,9 @@ pt_ctx *g_ctx = nullptr;
 std::vector<int> g_devices;
 int g_fog = -1;  // -1: not set yet, PATHTRACER_GPU_FOG decides
 int g_shading = -1;  // -1: not set yet, PATHTRACER_GPU_SHADING decides; else PT_SHADING_*
+bool g_noise_set = false;  // false: PATHTRACER_GPU_NOISE / _STEP decide
+double g_noise_target = 0;
+int g_noise_step = 16;
 std::mutex g_mu;  // requests are serialised, like the reference's single GL worker (gpu.go:2534-2546)
 
 std::string self_dir() {
@@ -114,6 +119,8 @@ bool load_core() {
         return false;
     }
     c.set_shading = reinterpret_cast<decltype(c.set_shading)>(dlsym(h, "pt_set_shading"));
+    c.set_moments = reinterpret_cast<decltype(c.set_moments)>(dlsym(h, "pt_set_moments"));
+    c.noise_estimate = reinterpret_cast<decltype(c.noise_estimate)>(dlsym(h, "pt_noise_estimate"));
     if (c.abi_version() != PT_ABI_VERSION) {
         g_core.error = "libptcore.so ABI version mismatch";
         dlclose(h);
@@ -272,6 +279,44 @@ bool GetFog() {
     return g_fog < 0 ? FogFromEnv() : g_fog == 1;
 }
 
+void NoiseFromEnv(double &target, int &step) {
+    target = 0;
+    step = 16;
+    if (const char *e = std::getenv("PATHTRACER_GPU_NOISE")) {
+        char *end = nullptr;
+        const double v = std::strtod(e, &end);
+        if (end != e && *end == 0 && v > 0 && v <= 1.7976931348623157e308) target = v;
+    }
+    if (const char *e = std::getenv("PATHTRACER_GPU_NOISE_STEP")) {
+        char *end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end != e && *end == 0 && v >= 1 && v <= 0x7fffffffL) step = (int)v;
+    }
+}
+
+void SetNoiseTarget(double target, int step) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_noise_set = true;
+    g_noise_target = target > 0 ? target : 0;
+    g_noise_step = step >= 1 ? step : 16;
+}
+
+double GetNoiseTarget() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    double t;
+    int s;
+    NoiseFromEnv(t, s);
+    return g_noise_set ? g_noise_target : t;
+}
+
+int GetNoiseStep() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    double t;
+    int s;
+    NoiseFromEnv(t, s);
+    return g_noise_set ? g_noise_step : s;
+}
+
 void Shutdown() {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_ctx && g_core.handle) g_core.destroy(g_ctx);
@@ -314,6 +359,12 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
                 return std::string("pt_set_shading: ") + g_core.last_error();
         }
     }
+    double noise_target = g_noise_target;
+    int noise_step = g_noise_step;
+    if (!g_noise_set) NoiseFromEnv(noise_target, noise_step);
+    const bool to_noise = noise_target > 0;
+    if (to_noise && !(g_core.set_moments && g_core.noise_estimate)) return "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate";
+    if (g_core.set_moments && g_core.set_moments(g_ctx, to_noise ? 1 : 0) != PT_OK) return std::string("pt_set_moments: ") + g_core.last_error();
     pt_config pc;
     std::memset(&pc, 0, sizeof pc);
     pc.width = cfg.Width;
@@ -324,7 +375,28 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     pt_stats st;
     std::memset(&st, 0, sizeof st);
     std::string err;
-    if (!progress) {
+    int32_t spp_done = cfg.SamplesPerPx > 0 ? cfg.SamplesPerPx : 0;
+    pt_noise nz;
+    std::memset(&nz, 0, sizeof nz);
+    if (to_noise) {  // render until the noise target, SamplesPerPx as the cap; the check follows every step
+        if (g_core.begin(g_ctx, &flat.sc, &pc) != PT_OK) return std::string("pt_begin: ") + g_core.last_error();
+        int32_t done = 0;
+        while (err.empty() && done < cfg.SamplesPerPx) {
+            const int32_t left = cfg.SamplesPerPx - done;
+            if (g_core.step(g_ctx, noise_step < left ? noise_step : left, &done) != PT_OK) { err = std::string("pt_step: ") + g_core.last_error(); break; }
+            if (progress) {
+                if (g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK) { err = std::string("pt_read: ") + g_core.last_error(); break; }
+                progress();
+            }
+            if (g_core.noise_estimate(g_ctx, &nz) != PT_OK) { err = std::string("pt_noise_estimate: ") + g_core.last_error(); break; }
+            if (done >= 2 && nz.noise <= noise_target) break;
+        }
+        if (err.empty() && (!progress || cfg.SamplesPerPx <= 0) && g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK)
+            err = std::string("pt_read: ") + g_core.last_error();
+        if (g_core.end(g_ctx, &st) != PT_OK && err.empty()) err = std::string("pt_end: ") + g_core.last_error();
+        if (err.empty() && progress) progress();
+        spp_done = done;
+    } else if (!progress) {
         if (g_core.render(g_ctx, &flat.sc, &pc, img.Pix.data(), img.Stride, nullptr, nullptr, nullptr, &st) != PT_OK)
             err = std::string("pt_render: ") + g_core.last_error();
     } else {
@@ -346,6 +418,8 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         stats->samples = st.samples; stats->segments = st.segments; stats->exit_scans = st.exit_scans; stats->draws = st.draws;
         stats->seconds = st.seconds; stats->trace_ms = st.trace_ms; stats->resolve_ms = st.resolve_ms;
         stats->device_ms = st.device_ms; stats->num_devices = st.num_devices; stats->spp_chunk = st.spp_chunk;
+        stats->spp_done = spp_done;
+        stats->noise = to_noise ? nz.noise : 0;
     }
     return err;
 }

@@ -34,6 +34,8 @@ struct Stats {
     uint64_t samples = 0, segments = 0, exit_scans = 0, draws = 0;
     double seconds = 0, trace_ms = 0, resolve_ms = 0, device_ms = 0;
     int num_devices = 0, spp_chunk = 0;
+    int spp_done = 0;   // samples per pixel actually rendered (below SamplesPerPx when a noise target stopped the frame)
+    double noise = 0;   // frame noise at the stop (pt_noise_estimate); 0 when no noise target was set
 };
 
 namespace hip {
@@ -52,6 +54,13 @@ bool FogFromEnv();  // PATHTRACER_GPU_FOG = 1 / true / on / yes
 void SetShading(int model);
 int GetShading();
 int ShadingFromEnv();  // PATHTRACER_GPU_SHADING = gl (any case) -> PT_SHADING_GL, else PT_SHADING_CPU
+// The stop rule of Render: target > 0 renders until the frame noise (pt_noise_estimate) is at or below target,
+// checking every `step` samples per pixel, with cfg.SamplesPerPx as the cap; target <= 0 (the default) renders SamplesPerPx
+// samples.  The initial value is PATHTRACER_GPU_NOISE / PATHTRACER_GPU_NOISE_STEP (NoiseFromEnv).
+void SetNoiseTarget(double target, int step = 16);
+double GetNoiseTarget();
+int GetNoiseStep();
+void NoiseFromEnv(double &target, int &step);  // PATHTRACER_GPU_NOISE = float > 0 (else 0: off), _STEP = int >= 1 (else 16)
 void Shutdown();                                    // releases the process-wide context
 }  // namespace hip
 

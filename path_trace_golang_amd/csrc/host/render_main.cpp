@@ -9,7 +9,8 @@
 // -scene-settings applies the editor's scene-settings override (internal/ui/app.go:60-75) before them;
 // without it scene.settings is ignored exactly as main.go:52 does.  -fog draws the scene's fog block the way the
 // reference's OpenGL backend does (sky blend, volumetric in-scatter; also env PATHTRACER_GPU_FOG=1); without it fog is
-// ignored like the CPU engine ignores it.
+// ignored like the CPU engine ignores it.  -noise T renders until the frame noise (pt_noise_estimate) is at or
+// below T, checking every -noise-step samples, with -spp as the cap (also env PATHTRACER_GPU_NOISE, PATHTRACER_GPU_NOISE_STEP).
 #include <cerrno>
 #include <chrono>
 #include <cstdarg>
@@ -52,6 +53,8 @@ struct Flags {
     std::string out = "output.png";
     int width = 0, height = 0, spp = -1, depth = -1, devices = 1;
     unsigned long long seed = 1;
+    double noise = 0;
+    int noise_step = 16;
 };
 
 void usage() {
@@ -64,6 +67,9 @@ void usage() {
                  "  -headless\n    \trender without UI and save PNG\n"
                  "  -height int\n    \timage height (default: the mode preset)\n"
                  "  -mode string\n    \trender mode: preview or final (default \"preview\")\n"
+                 "  -noise float\n    \trender until the frame noise is at or below this target, -spp being the cap (default 0 = off, or\n"
+                 "    \tPATHTRACER_GPU_NOISE)\n"
+                 "  -noise-step int\n    \tsamples per pixel between two noise checks (default 16, or PATHTRACER_GPU_NOISE_STEP)\n"
                  "  -out string\n    \toutput PNG file for headless render (default \"output.png\")\n"
                  "  -scene string\n    \tpath to scene JSON file (default \"scenes/example_simple.json\")\n"
                  "  -scene-settings\n    \tlet the scene file's settings block override the mode preset (the editor's rule); with -mode final this also\n"
@@ -104,7 +110,7 @@ int parse(int argc, char **argv, Flags &f) {
             (name == "gpu" ? f.gpu : name == "headless" ? f.headless : name == "fog" ? f.fog : f.scene_settings) = b;
             continue;
         }
-        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading"};
+        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading", "noise", "noise-step"};
         bool ok = false;
         for (const char *k : known) ok = ok || name == k;
         if (!ok) {
@@ -131,6 +137,17 @@ int parse(int argc, char **argv, Flags &f) {
             }
             f.shading = val;
         }
+        else if (name == "noise") {
+            char *end = nullptr;
+            errno = 0;
+            const double v = std::strtod(val.c_str(), &end);
+            if (errno || end == val.c_str() || *end || !(v >= 0)) {
+                std::fprintf(stderr, "invalid value \"%s\" for flag -noise: parse error\n", val.c_str());
+                usage();
+                return 2;
+            }
+            f.noise = v;
+        }
         else {
             char *end = nullptr;
             errno = 0;
@@ -145,6 +162,7 @@ int parse(int argc, char **argv, Flags &f) {
             else if (name == "spp") f.spp = (int)n;
             else if (name == "depth") f.depth = (int)n;
             else if (name == "devices") f.devices = (int)n;
+            else if (name == "noise-step") f.noise_step = n >= 1 && n <= 0x7fffffffLL ? (int)n : 16;
             else f.seed = (unsigned long long)n;
         }
     }
@@ -168,6 +186,7 @@ int render_headless(const Flags &f) {
     if (f.depth >= 0) s.MaxDepth = f.depth;
     engine::hip::SetFog(f.fog);
     engine::hip::SetShading(f.shading == "gl" ? PT_SHADING_GL : PT_SHADING_CPU);
+    engine::hip::SetNoiseTarget(f.noise, f.noise_step);
     if (f.shading == "gl") logf("shading: gl (the reference's GPU shader; spp counts passes of 16 paths)");
     if (f.fog) logf("fog: drawing the scene's fog block (%s)", sc->FogPtr ? "present" : "absent: nothing to draw");
     try {
@@ -184,8 +203,13 @@ int render_headless(const Flags &f) {
         auto t0 = std::chrono::steady_clock::now();
         engine::RenderInto(*sc, cfg, img, nullptr, &st);
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        logf("rendered %dx%d, %d spp, depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, %.1f M samples/s", cfg.Width,
-             cfg.Height, cfg.SamplesPerPx, cfg.MaxDepth, st.num_devices, dt, st.segments / dt / 1e6, st.samples / dt / 1e6);
+        if (f.noise > 0)
+            logf("rendered %dx%d, %d of at most %d spp (noise %.6g, target %.6g), depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, "
+                 "%.1f M samples/s", cfg.Width, cfg.Height, st.spp_done, cfg.SamplesPerPx, st.noise, f.noise, cfg.MaxDepth, st.num_devices, dt,
+                 st.segments / dt / 1e6, st.samples / dt / 1e6);
+        else
+            logf("rendered %dx%d, %d spp, depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, %.1f M samples/s", cfg.Width,
+                 cfg.Height, cfg.SamplesPerPx, cfg.MaxDepth, st.num_devices, dt, st.segments / dt / 1e6, st.samples / dt / 1e6);
         engine::SavePNG(f.out, img);
     } catch (const std::exception &e) {
         logf("headless render error: %s", e.what());
@@ -204,6 +228,7 @@ int main(int argc, char **argv) {
     if (const char *e = std::getenv("PATHTRACER_SEED")) f.seed = std::strtoull(e, nullptr, 10);
     f.fog = engine::hip::FogFromEnv();
     f.shading = engine::hip::ShadingFromEnv() == PT_SHADING_GL ? "gl" : "cpu";
+    engine::hip::NoiseFromEnv(f.noise, f.noise_step);
     int rc = parse(argc, argv, f);
     if (rc >= 0) return rc;
     logf("flags: scene=%s mode=%s headless=%s out=%s", f.scene.c_str(), f.mode.c_str(), f.headless ? "true" : "false",

@@ -36,6 +36,8 @@
 //                   to the running sum (renderer.go:186), and on request finishes the
 //                   pixel: 1/spp, sqrt gamma, *255.999, clamp, truncate (renderer.go:190-221).
 //   untile_kernel   tile-major -> row-major frame.
+//   moments_kernel  opt-in (pt_set_moments): per pixel slot the running sum of the squared sample radiances, after every
+//                   chunk's resolve add; noise_kernel reduces both sums to the frame noise figure (pt_noise_estimate).
 //   gl_trace_kernel opt-in (pt_set_shading, GL model): one pass of GL shading (pt_glshade.h) per job, 16 paths with their own
 //                   camera rays, the pass sum written into the job's radiance record; replaces ray generation and the trace
 //                   kernels for the frame.  resolve_kernel then finishes with GL's tone map (gl_spp).
@@ -2854,6 +2856,142 @@ __global__ __launch_bounds__(PT_BLOCK) void untile_kernel(const UntileArgs U) {
     }
     if (U.u32a) U.u32a[o] = U.tiles_u32a[pix];
     if (U.u32b) U.u32b[o] = U.tiles_u32b[pix];
+}
+
+// Second moments (pt_set_moments): per accumulation slot the running sum of the squares of the sample radiances, next to
+// resolve_kernel's running sum of the radiances themselves.  Same slot -> (tile, sub-block, pixel) map and the same walk
+// over the chunk's records in sample order as resolve_kernel, which stays as it is: this kernel reads the records a second
+// time, right after the chunk's resolve add (so after fog_kernel and gl_trace_kernel: the squares are those of the
+// radiance the pixel receives).  finish = 1 writes the sums tile-major with zeros outside the frame, the layout of
+// tiles_accum, for untile_kernel.
+struct MomentsArgs {
+    const double *L;         // [njobs][4]: r, g, b, 0
+    double *m2;              // [3][nslots]
+    double *tiles_m2;        // [nlocal][32][32][3] or null (no finish)
+    uint32_t nslots;         // nlocal*1024
+    uint32_t S;
+    int32_t first;           // 1: the running sum starts at zero
+    int32_t finish;          // 1: write tiles_m2
+    int32_t have_chunk;      // 0: no chunk to add (pure finish)
+    int32_t width, height, ntx, shard_index, shard_count;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void moments_kernel(const MomentsArgs M) {
+    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (slot >= M.nslots) return;
+    const uint32_t blk = slot >> 6, p = slot & 63u;
+    const uint32_t lt = blk >> 4, sb = blk & 15u;
+    const uint32_t t = (uint32_t)M.shard_index + lt * (uint32_t)M.shard_count;
+    const uint32_t ty = t / (uint32_t)M.ntx, tx = t - ty * (uint32_t)M.ntx;
+    const uint32_t lx = (sb & 3u) * 8u + (p & 7u), ly = (sb >> 2) * 8u + (p >> 3);
+    const uint32_t x = tx * 32u + lx, y = ty * 32u + ly;
+    const bool inside = x < (uint32_t)M.width && y < (uint32_t)M.height;
+
+    double qx = 0, qy = 0, qz = 0;
+    if (inside) {
+        if (!M.first) {
+            qx = M.m2[slot];
+            qy = M.m2[(size_t)M.nslots + slot];
+            qz = M.m2[2 * (size_t)M.nslots + slot];
+        }
+        if (M.have_chunk) {
+            const size_t base = (size_t)blk * M.S * 64u + p;
+            for (uint32_t s = 0; s < M.S; s++) {  // in sample order, like the sum itself
+                const double4 l = reinterpret_cast<const double4 *>(M.L)[base + (size_t)s * 64u];
+                qx += l.x * l.x;
+                qy += l.y * l.y;
+                qz += l.z * l.z;
+            }
+            M.m2[slot] = qx;
+            M.m2[(size_t)M.nslots + slot] = qy;
+            M.m2[2 * (size_t)M.nslots + slot] = qz;
+        }
+    }
+    if (M.finish) {
+        const size_t pix = (size_t)lt * 1024u + ly * 32u + lx;
+        M.tiles_m2[3 * pix] = inside ? qx : 0.0;
+        M.tiles_m2[3 * pix + 1] = inside ? qy : 0.0;
+        M.tiles_m2[3 * pix + 2] = inside ? qz : 0.0;
+    }
+}
+
+// Frame noise (pt_noise_estimate, the metric of include/ptcore.h): per slot inside the frame, with n samples done, sums S
+// (resolve_kernel's) and Q (moments_kernel's):
+//   m_c = S_c / n,  v_c = max(0, Q_c / n - m_c * m_c) / (n - 1),  e2 = ((v_r + v_g + v_b) / 3) / max((m_r + m_g + m_b) / 3, 0.01)^2
+// A slot whose e2 is NaN or infinite adds nothing and counts as bad.  A block reduces over a fixed tree -- xor butterfly
+// inside each wave, then the four waves in order through LDS -- and writes one partial; the host adds the partials in
+// block order.  No atomics, so the figure is the same bits every time for one context shape.
+struct NoisePartial {
+    double sum;              // sum of e2 over the block's good slots
+    double max;              // largest e2 among them
+    unsigned long long bad;
+};
+
+struct NoiseArgs {
+    const double *acc;       // [3][nslots]
+    const double *m2;        // [3][nslots]
+    NoisePartial *partial;   // [gridDim.x]
+    uint32_t nslots;
+    int32_t n;               // samples done, >= 2
+    int32_t width, height, ntx, shard_index, shard_count;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void noise_kernel(const NoiseArgs A) {
+    __shared__ double s_sum[PT_BLOCK / PT_WAVE], s_max[PT_BLOCK / PT_WAVE];
+    __shared__ uint32_t s_bad[PT_BLOCK / PT_WAVE];
+    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    double e2 = 0.0;
+    uint32_t bad = 0;
+    if (slot < A.nslots) {
+        const uint32_t blk = slot >> 6, p = slot & 63u;
+        const uint32_t lt = blk >> 4, sb = blk & 15u;
+        const uint32_t t = (uint32_t)A.shard_index + lt * (uint32_t)A.shard_count;
+        const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
+        const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u), y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+        if (x < (uint32_t)A.width && y < (uint32_t)A.height) {
+            const double n = (double)A.n, n1 = (double)(A.n - 1);
+            double msum = 0.0, vsum = 0.0;
+            for (uint32_t c = 0; c < 3u; c++) {
+                const double m = A.acc[c * (size_t)A.nslots + slot] / n;
+                double d = A.m2[c * (size_t)A.nslots + slot] / n - m * m;
+                if (d < 0.0) d = 0.0;  // (a NaN stays a NaN)
+                msum += m;
+                vsum += d / n1;
+            }
+            double den = msum / 3.0;
+            if (den < 0.01) den = 0.01;
+            e2 = (vsum / 3.0) / (den * den);
+            if (!(e2 - e2 == 0.0)) {  // NaN or infinite
+                e2 = 0.0;
+                bad = 1;
+            }
+        }
+    }
+    double sum = e2, mx = e2;
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off, 64);
+        const double o = __shfl_xor(mx, off, 64);
+        mx = o > mx ? o : mx;
+        bad += __shfl_xor(bad, off, 64);
+    }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) {
+        s_sum[wave] = sum;
+        s_max[wave] = mx;
+        s_bad[wave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        NoisePartial r;
+        r.sum = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+        r.max = s_max[0];
+        r.bad = s_bad[0];
+        for (int w = 1; w < PT_BLOCK / PT_WAVE; w++) {
+            r.max = s_max[w] > r.max ? s_max[w] : r.max;
+            r.bad += s_bad[w];
+        }
+        A.partial[blockIdx.x] = r;
+    }
 }
 
 // Self-test of div_shared against the compiler's IEEE division: `per_thread` operand pairs per thread, exponents drawn

@@ -102,6 +102,9 @@ struct Device {
     DevBuf<uint32_t> job_seg, job_draw;
     DevBuf<double> acc;
     DevBuf<uint32_t> acc_seg, acc_draw;
+    DevBuf<double> m2;                // pt_set_moments: [3][nslots] running sums of squares (allocated only then)
+    DevBuf<double> tiles_m2;          // ... and their tile-major copy for the gather
+    DevBuf<ptk::NoisePartial> noise_part;  // pt_noise_estimate: one partial per block of noise_kernel
     DevBuf<uint8_t> tiles_rgba;
     DevBuf<double> tiles_accum;
     DevBuf<uint32_t> tiles_seg, tiles_draw;
@@ -122,8 +125,8 @@ struct Device {
     size_t q_cap = 0;
     DevBuf<unsigned long long> counters;
     DevBuf<unsigned long long> prof;
-    std::vector<EventPair> ev_trace, ev_resolve, ev_raygen, ev_glass, ev_fog;
-    size_t n_trace = 0, n_resolve = 0, n_raygen = 0, n_glass = 0, n_fog = 0;
+    std::vector<EventPair> ev_trace, ev_resolve, ev_raygen, ev_glass, ev_fog, ev_moments;
+    size_t n_trace = 0, n_resolve = 0, n_raygen = 0, n_glass = 0, n_fog = 0, n_moments = 0;
     DevBuf<ptf::FogLight> fog_lights;        // the frame's light list (fog on)
     DevBuf<unsigned long long> fog_counters; // [3] shadow rays, draws, march steps of the frame
     DevBuf<ptg::GlObj> gl_objs;              // GL shading: the frame's objects, materials and light list
@@ -169,6 +172,7 @@ struct Frame {
     ptf::FogParams fog{};
     std::vector<ptf::FogLight> fog_lights;
     bool gl = false;  // GL shading (pt_set_shading): gl_trace_kernel replaces ray generation and the trace kernels
+    bool moments = false;  // pt_set_moments: moments_kernel runs after every chunk's resolve add (pt_begin / pt_render frames only)
     std::vector<ptg::GlObj> gl_objs;
     std::vector<ptg::GlMat> gl_mats;
     std::vector<int32_t> gl_lights;
@@ -217,6 +221,8 @@ struct pt_ctx {
     DevBuf<uint32_t> g_tiles_seg, g_tiles_draw;
     DevBuf<uint8_t> f_rgba;
     DevBuf<double> f_accum;
+    DevBuf<double> g_tiles_m2, f_m2;  // pt_read_moments: the gathered tiles and the row-major frame of the second moments
+    bool moments_on = false;          // pt_set_moments
     DevBuf<uint32_t> f_seg, f_draw;
     size_t l_budget_bytes = (size_t)48 << 30;  // per-chunk job buffers (radiance, primary rays, path-state queues): a sixth of the 288 GB
     // A context that renders frame after frame of one shape (a UI, an animation: gpu.go:2534-2546 is called once per frame) grows its
@@ -666,7 +672,7 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     d.nlocal = tiles_of_shard(fr.ntx * fr.nty, shard);
     d.nslots = (uint32_t)d.nlocal * 1024u;
     d.acc_started = false;
-    d.n_trace = d.n_resolve = d.n_raygen = d.n_glass = d.n_fog = 0;
+    d.n_trace = d.n_resolve = d.n_raygen = d.n_glass = d.n_fog = d.n_moments = 0;
     d.first_recorded = false;
     std::memset(d.pass_log_prev, 0, sizeof d.pass_log_prev);  // the device counters are cleared below, once per frame
     if (d.scene_gen != sd.gen) {
@@ -731,6 +737,7 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     }
     const size_t ns = std::max<uint32_t>(1, d.nslots);
     HIP_TRY(d.acc.reserve(3 * ns));
+    if (fr.moments) HIP_TRY(d.m2.reserve(3 * ns));
     if (fr.stats_on) {
         HIP_TRY(d.acc_seg.reserve(ns));
         HIP_TRY(d.acc_draw.reserve(ns));
@@ -1363,7 +1370,50 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e.b, d.stream));
+    if (fr.moments) {  // the squares of the same records, in the same order (pt_set_moments)
+        if (int32_t rc = dev_events(d, d.ev_moments, d.n_moments + 1)) return rc;
+        ptk::MomentsArgs M;
+        std::memset(&M, 0, sizeof M);
+        M.L = d.L.p;
+        M.m2 = d.m2.p;
+        M.nslots = d.nslots;
+        M.S = S;
+        M.first = R.first;
+        M.have_chunk = 1;
+        M.width = fr.cfg.width;
+        M.height = fr.cfg.height;
+        M.ntx = fr.ntx;
+        M.shard_index = d.shard.index;
+        M.shard_count = d.shard.count;
+        EventPair &em = d.ev_moments[d.n_moments++];
+        HIP_TRY(hipEventRecord(em.a, d.stream));
+        hipLaunchKernelGGL(ptk::moments_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, M);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(em.b, d.stream));
+    }
     d.acc_started = true;
+    return PT_OK;
+}
+
+// Writes this device's second moments tile-major (zeros outside the frame), the layout of tiles_accum.
+int32_t dev_finish_moments(pt_ctx *ctx, Device &d, double *tiles_m2) {
+    const Frame &fr = ctx->frame;
+    if (d.nlocal == 0) return PT_OK;
+    HIP_TRY(hipSetDevice(d.ordinal));
+    ptk::MomentsArgs M;
+    std::memset(&M, 0, sizeof M);
+    M.m2 = d.m2.p;
+    M.tiles_m2 = tiles_m2;
+    M.nslots = d.nslots;
+    M.first = d.acc_started ? 0 : 1;
+    M.finish = 1;
+    M.width = fr.cfg.width;
+    M.height = fr.cfg.height;
+    M.ntx = fr.ntx;
+    M.shard_index = d.shard.index;
+    M.shard_count = d.shard.count;
+    hipLaunchKernelGGL(ptk::moments_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, M);
+    HIP_TRY(hipGetLastError());
     return PT_OK;
 }
 
@@ -2049,12 +2099,14 @@ void pt_destroy(pt_ctx *ctx) {
         d.cand_ids.release(); d.cand_n.release(); d.slow_list.release();
         for (EventPair &e : d.ev_glass) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         d.acc.release(); d.acc_seg.release(); d.acc_draw.release(); d.tiles_rgba.release();
+        d.m2.release(); d.tiles_m2.release(); d.noise_part.release();
         d.tiles_accum.release(); d.tiles_seg.release(); d.tiles_draw.release(); d.queue.release();
         d.counters.release();
         for (EventPair &e : d.ev_trace) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (EventPair &e : d.ev_resolve) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (EventPair &e : d.ev_raygen) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (EventPair &e : d.ev_fog) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+        for (EventPair &e : d.ev_moments) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         d.fog_lights.release(); d.fog_counters.release();
         d.gl_objs.release(); d.gl_mats.release(); d.gl_lights.release(); d.gl_counters.release();
         if (d.ev_first) (void)hipEventDestroy(d.ev_first);
@@ -2062,6 +2114,7 @@ void pt_destroy(pt_ctx *ctx) {
         if (d.own_stream) (void)hipStreamDestroy(d.own_stream);
     }
     if (!ctx->devs.empty() && hipSetDevice(ctx->devs[0].ordinal) == hipSuccess) {
+        ctx->g_tiles_m2.release(); ctx->f_m2.release();
         ctx->g_tiles_rgba.release(); ctx->g_tiles_accum.release(); ctx->g_tiles_seg.release();
         ctx->g_tiles_draw.release(); ctx->f_rgba.release(); ctx->f_accum.release(); ctx->f_seg.release();
         ctx->f_draw.release();
@@ -2278,6 +2331,7 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
     const int32_t ntiles = ((cfg->width + 31) / 32) * ((cfg->height + 31) / 32);
     const uint32_t max_slots = (uint32_t)tiles_of_shard(ntiles, pt_shard{0, ndev}) * 1024u;
     if (int32_t rc = frame_open(ctx, scene, cfg, max_slots)) return rc;
+    ctx->frame.moments = ctx->moments_on;
     for (int32_t i = 0; i < ndev; i++) {
         if (int32_t rc = dev_begin(ctx, ctx->devs[(size_t)i], pt_shard{i, ndev}, nullptr)) {
             ctx->frame.open = false;
@@ -2451,6 +2505,21 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
     }
     fill_stats_common(ctx, &st);
     ctx->frame.open = false;
+    if (ctx->frame.moments && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) {
+        double mm = 0;
+        size_t launches = 0;
+        for (Device &d : ctx->devs) {
+            double ms = 0;
+            for (size_t k = 0; k < d.n_moments && hipSetDevice(d.ordinal) == hipSuccess; k++) {
+                float m = 0;
+                if (hipEventElapsedTime(&m, d.ev_moments[k].a, d.ev_moments[k].b) == hipSuccess) ms += m;
+            }
+            mm = std::max(mm, ms);
+            launches += d.n_moments;
+        }
+        std::fprintf(stderr, "ptcore: moments_kernel %.3f ms in %zu launches (resolve_kernel %.3f ms in %d)\n", mm, launches, st.resolve_ms,
+                     st.resolve_launches);
+    }
     if (ctx->frame.fog_vol) {
         ctx->fog_pending = 1;
         if (int32_t r = collect_fog(ctx)) rc = rc != PT_OK ? rc : r;
@@ -2485,6 +2554,131 @@ int32_t pt_render(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uint
     }
     if (stats) *stats = st;
     return rc != PT_OK ? rc : rc2;
+}
+
+int32_t pt_set_moments(pt_ctx *ctx, int32_t on) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_moments while a frame is open");
+    ctx->moments_on = on != 0;
+    return PT_OK;
+}
+
+// The frame whose sums pt_read_moments / pt_noise_estimate read: the open one, or the last one finished on ctx (its sums stay
+// on the devices until the next frame opens), with at least one step done and moments collected.
+static int32_t moments_frame(pt_ctx *ctx, const char *who) {
+    const Frame &fr = ctx->frame;
+    if (fr.done_spp <= 0 || fr.chunk == 0)
+        return fail(PT_ERR_STATE, std::string(who) + ": no frame with samples on this context (pt_step or pt_render first)");
+    if (!fr.moments) return fail(PT_ERR_STATE, std::string(who) + ": the frame was rendered with moments off (pt_set_moments)");
+    return PT_OK;
+}
+
+// as read_frame: every device's tiles gathered on device 0 (peer copies, or the grouped RCCL exchange), untiled, copied to the host
+int32_t pt_read_moments(pt_ctx *ctx, double *m2) {
+    if (!ctx || !m2) return fail(PT_ERR_INVALID, "null argument");
+    if (int32_t rc = moments_frame(ctx, "pt_read_moments")) return rc;
+    Frame &fr = ctx->frame;
+    const int32_t W = fr.cfg.width, H = fr.cfg.height;
+    const int32_t ndev = (int32_t)ctx->devs.size();
+    const size_t ntiles = (size_t)fr.ntx * (size_t)fr.nty;
+    Device &d0 = ctx->devs[0];
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    HIP_TRY(ctx->g_tiles_m2.reserve(ntiles * 3072));
+    size_t before = 0;
+    for (int32_t i = 0; i < ndev; i++) {
+        Device &d = ctx->devs[(size_t)i];
+        if (d.nlocal == 0) continue;
+        const size_t nt = (size_t)d.nlocal;
+        if (i == 0 && !ctx->rccl.lib) {
+            if (int32_t rc = dev_finish_moments(ctx, d, ctx->g_tiles_m2.p + before * 3072)) return rc;
+        } else {
+            HIP_TRY(hipSetDevice(d.ordinal));
+            HIP_TRY(d.tiles_m2.reserve(nt * 3072));
+            if (int32_t rc = dev_finish_moments(ctx, d, d.tiles_m2.p)) return rc;
+            if (!ctx->rccl.lib)
+                HIP_TRY(hipMemcpyPeerAsync(ctx->g_tiles_m2.p + before * 3072, d0.ordinal, d.tiles_m2.p, d.ordinal,
+                                           nt * 3072 * sizeof(double), d.stream));
+        }
+        before += nt;
+    }
+    if (ctx->rccl.lib) {
+        const pt_ctx::Rccl &R = ctx->rccl;
+        RCCL_TRY(R.GroupStart());
+        size_t off = 0;
+        for (int32_t i = 0; i < ndev; i++) {
+            Device &d = ctx->devs[(size_t)i];
+            if (d.nlocal == 0) continue;
+            const size_t nt = (size_t)d.nlocal;
+            RCCL_TRY(R.Send(d.tiles_m2.p, nt * 3072, ncclDouble, 0, R.comms[(size_t)i], d.stream));
+            RCCL_TRY(R.Recv(ctx->g_tiles_m2.p + off * 3072, nt * 3072, ncclDouble, i, R.comms[0], d0.stream));
+            off += nt;
+        }
+        RCCL_TRY(R.GroupEnd());
+    }
+    for (int32_t i = 1; i < ndev; i++) {
+        HIP_TRY(hipSetDevice(ctx->devs[(size_t)i].ordinal));
+        HIP_TRY(hipStreamSynchronize(ctx->devs[(size_t)i].stream));
+    }
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    HIP_TRY(ctx->f_m2.reserve((size_t)W * H * 3));
+    ptk::UntileArgs U;
+    std::memset(&U, 0, sizeof U);
+    U.tiles_accum = ctx->g_tiles_m2.p;  // the layout of tiles_accum
+    U.accum = ctx->f_m2.p;
+    U.width = W; U.height = H; U.ntx = fr.ntx; U.nty = fr.nty; U.stride = W * 4; U.shard_count = ndev;
+    hipLaunchKernelGGL(ptk::untile_kernel, dim3((unsigned)fr.ntx, (unsigned)fr.nty, 4), dim3(PT_BLOCK), 0, d0.stream, U);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(m2, ctx->f_m2.p, (size_t)W * H * 3 * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+    HIP_TRY(hipStreamSynchronize(d0.stream));
+    return PT_OK;
+}
+
+int32_t pt_noise_estimate(pt_ctx *ctx, pt_noise *out) {
+    if (!ctx || !out) return fail(PT_ERR_INVALID, "null argument");
+    if (int32_t rc = moments_frame(ctx, "pt_noise_estimate")) return rc;
+    const Frame &fr = ctx->frame;
+    pt_noise r;
+    std::memset(&r, 0, sizeof r);
+    r.spp = fr.done_spp;
+    r.pixels = (uint64_t)fr.cfg.width * (uint64_t)fr.cfg.height;
+    if (fr.done_spp < 2) {  // no variance estimate from one sample
+        r.noise = r.max_pixel = INFINITY;
+        *out = r;
+        return PT_OK;
+    }
+    double sum = 0.0;
+    std::vector<ptk::NoisePartial> part;
+    for (Device &d : ctx->devs) {  // partials in block order, devices in order
+        if (d.nlocal == 0) continue;
+        HIP_TRY(hipSetDevice(d.ordinal));
+        const uint32_t grid = (d.nslots + PT_BLOCK - 1) / PT_BLOCK;
+        HIP_TRY(d.noise_part.reserve(grid));
+        ptk::NoiseArgs A;
+        std::memset(&A, 0, sizeof A);
+        A.acc = d.acc.p;
+        A.m2 = d.m2.p;
+        A.partial = d.noise_part.p;
+        A.nslots = d.nslots;
+        A.n = fr.done_spp;
+        A.width = fr.cfg.width;
+        A.height = fr.cfg.height;
+        A.ntx = fr.ntx;
+        A.shard_index = d.shard.index;
+        A.shard_count = d.shard.count;
+        hipLaunchKernelGGL(ptk::noise_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A);
+        HIP_TRY(hipGetLastError());
+        part.resize(grid);
+        HIP_TRY(hipMemcpyAsync(part.data(), d.noise_part.p, grid * sizeof(ptk::NoisePartial), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        for (const ptk::NoisePartial &p : part) {
+            sum += p.sum;
+            r.max_pixel = std::max(r.max_pixel, p.max);
+            r.bad_pixels += p.bad;
+        }
+    }
+    r.noise = std::sqrt(sum / (double)r.pixels);
+    *out = r;
+    return PT_OK;
 }
 
 int32_t pt_render_tiles_device(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, const pt_shard *shard,

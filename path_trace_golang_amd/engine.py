@@ -59,16 +59,23 @@ def new_image(w: int, h: int) -> np.ndarray:
 
 
 def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
-                progress: Optional[Callable[[], None]] = None, shading: Optional[str] = None) -> dict:
+                progress: Optional[Callable[[], None]] = None, shading: Optional[str] = None,
+                moments: Optional[np.ndarray] = None, noise: Optional[float] = None, noise_step: Optional[int] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
-    DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu"."""
+    DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
+    `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
+    cap; noise None takes PATHTRACER_GPU_NOISE / PATHTRACER_GPU_NOISE_STEP (hip.NoiseConfig.from_env), off by default."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
             "this package implements only the GPU branch of RenderInto")
     gcfg = hip.RenderConfig(cfg.width, cfg.height, cfg.samples_per_px, cfg.max_depth, cfg.seed)
     model = shading if shading is not None else hip.ShadingConfig.from_env().model
-    return hip.render(sc, gcfg, img, progress, shading=model)
+    ncfg = hip.NoiseConfig.from_env()
+    if noise is None and ncfg.enabled:
+        noise = ncfg.target
+    return hip.render(sc, gcfg, img, progress, shading=model, moments=moments, noise=noise,
+                      noise_step=noise_step if noise_step is not None else ncfg.step)
 
 
 def render(sc: scn.Scene, cfg: RenderConfig) -> np.ndarray:

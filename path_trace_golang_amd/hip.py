@@ -163,6 +163,50 @@ def shading_last_stats(ctx: Optional[capi.Context] = None) -> dict:
     return st.as_dict()
 
 
+def set_moments(ctx: capi.Context, on: bool) -> None:
+    """pt_set_moments: later frames on ctx collect the per-pixel second moments (off by default)."""
+    if not capi.has("pt_set_moments"):
+        if on:
+            raise RuntimeError("this libptcore.so has no pt_set_moments (rebuild it)")
+        return
+    capi.check(capi.load().pt_set_moments(ctx.handle, 1 if on else 0))
+
+
+def read_moments(ctx: capi.Context, m2: np.ndarray) -> None:
+    """pt_read_moments into m2 (contiguous float64 [H, W, 3]): per pixel and channel the sum over the samples done of L*L."""
+    if m2.dtype != np.float64 or m2.ndim != 3 or m2.shape[2] != 3 or not m2.flags.c_contiguous:
+        raise ValueError("moments must be contiguous float64 [H, W, 3]")
+    capi.check(capi.load().pt_read_moments(ctx.handle, m2.ctypes.data_as(C.POINTER(C.c_double))))
+
+
+def noise_estimate(ctx: Optional[capi.Context] = None) -> dict:
+    """pt_noise_estimate of ctx's open or last frame: noise, max_pixel, pixels, bad_pixels, spp."""
+    n = capi.PtNoise()
+    capi.check(capi.load().pt_noise_estimate((ctx or context()).handle, C.byref(n)))
+    return n.as_dict()
+
+
+def noise_estimate_host(accum: np.ndarray, m2: np.ndarray, n: int) -> dict:
+    """The metric of pt_noise_estimate (include/ptcore.h) in NumPy, from the sums a frame returns: accum = per pixel the sum
+    of the sample radiances, m2 = the sum of their squares, n = samples done.
+        m_c = S_c / n;  v_c = max(0, Q_c / n - m_c^2) / (n - 1);  e2 = mean_c(v_c) / max(mean_c(m_c), 0.01)^2
+        noise = sqrt(sum(e2) / pixels); a pixel with a NaN or infinite e2 contributes 0 and counts as bad; n < 2: +inf."""
+    S = np.asarray(accum, np.float64).reshape(-1, 3)
+    Q = np.asarray(m2, np.float64).reshape(-1, 3)
+    pixels = S.shape[0]
+    if n < 2:
+        return {"noise": float("inf"), "max_pixel": float("inf"), "pixels": pixels, "bad_pixels": 0, "spp": int(n)}
+    with np.errstate(all="ignore"):
+        m = S / float(n)
+        v = np.maximum(Q / float(n) - m * m, 0.0) / float(n - 1)
+        den = np.maximum((m[:, 0] + m[:, 1] + m[:, 2]) / 3.0, 0.01)
+        e2 = ((v[:, 0] + v[:, 1] + v[:, 2]) / 3.0) / (den * den)
+    good = np.isfinite(e2)
+    e2 = np.where(good, e2, 0.0)
+    return {"noise": float(np.sqrt(e2.sum() / pixels)), "max_pixel": float(e2.max()) if pixels else 0.0, "pixels": pixels,
+            "bad_pixels": int(pixels - np.count_nonzero(good)), "spp": int(n)}
+
+
 def pt_config(cfg: RenderConfig) -> capi.PtConfig:
     return capi.PtConfig(cfg.width, cfg.height, cfg.samples_per_px, cfg.max_depth, cfg.seed & 0xFFFFFFFFFFFFFFFF,
                          cfg.spp_chunk, cfg.flags)
@@ -195,7 +239,8 @@ def _ptr(a: Optional[np.ndarray]):
 def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[], None]] = None,
            accum: Optional[np.ndarray] = None, nseg: Optional[np.ndarray] = None,
            ndraw: Optional[np.ndarray] = None, ctx: Optional[capi.Context] = None, fog: bool = False,
-           shading: str = "cpu") -> dict:
+           shading: str = "cpu", moments: Optional[np.ndarray] = None, noise: Optional[float] = None,
+           noise_step: int = 16) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -204,6 +249,12 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
 
     shading="gl" renders with the OpenGL backend's estimator (pt_set_shading): samples_per_px counts passes of
     16 paths each, accum holds the sum of the pass sums, and img is GL's tone-mapped finish.  It needs the Scene.
+
+    moments (float64 [H, W, 3]) receives the per-pixel second moments (pt_set_moments).  noise=T renders until
+    the frame noise (pt_noise_estimate) is at or below T: samples are added noise_step at a time, the check follows every
+    step, and the frame stops at the first check with at least 2 samples done and noise <= T, or at the cap
+    cfg.samples_per_px; progress() is called after each step.  The image is that of a frame of the samples done.  With either
+    argument the returned dict gains spp_done and noise; without them moments are off for the call.
 
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
@@ -222,6 +273,11 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     set_fog(ctx, getattr(sc, "fog", None) if fog else None)
     if shading != "cpu" or capi.has("pt_set_shading"):
         set_shading(ctx, shading, sc)
+    want_moments = moments is not None or noise is not None
+    set_moments(ctx, want_moments)
+    if moments is not None and (moments.dtype != np.float64 or moments.shape != (cfg.height, cfg.width, 3)
+                                or not moments.flags.c_contiguous):
+        raise ValueError("moments must be contiguous float64 [H, W, 3]")
     pc = pt_config(cfg)
     st = capi.PtStats()
     if accum is not None and (accum.dtype != np.float64 or accum.shape != (cfg.height, cfg.width, 3)
@@ -231,27 +287,57 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
         if a is not None and (a.dtype != np.uint32 or a.shape != (cfg.height, cfg.width) or not a.flags.c_contiguous):
             raise ValueError("nseg/ndraw must be contiguous uint32 [H, W]")
     stride = int(img.strides[0])
-    if progress is None:
+
+    def with_moments(d: dict) -> dict:  # after pt_end: the sums stay readable until the next frame opens
+        if want_moments and cfg.samples_per_px > 0:
+            if moments is not None:
+                read_moments(ctx, moments)
+            d.update(noise=noise_estimate(ctx)["noise"])
+        elif want_moments:
+            d.update(noise=float("inf"))
+        return d
+
+    if progress is None and noise is None:
         capi.check(L.pt_render(ctx.handle, C.byref(flat.c), C.byref(pc), _ptr(img), stride, _ptr(accum), _ptr(nseg),
                                _ptr(ndraw), C.byref(st)))
-        return st.as_dict()
+        d = st.as_dict()
+        if want_moments:
+            d["spp_done"] = max(0, cfg.samples_per_px)
+        return with_moments(d)
     if nseg is not None or ndraw is not None:
-        raise ValueError("per-pixel stats are only available without a progress callback")
+        raise ValueError("per-pixel stats are only available without a progress callback and without a noise target")
     capi.check(L.pt_begin(ctx.handle, C.byref(flat.c), C.byref(pc)))
+    done = C.c_int32(0)
     try:
-        step = max(1, cfg.samples_per_px // 10)
-        done = C.c_int32(0)
-        while done.value < cfg.samples_per_px:
-            capi.check(L.pt_step(ctx.handle, step, C.byref(done)))
-            capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
-            progress()
-        if cfg.samples_per_px <= 0:
-            capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
+        if noise is not None:  # render until the noise target, cfg.samples_per_px as the cap
+            nz = capi.PtNoise()
+            while done.value < cfg.samples_per_px:
+                capi.check(L.pt_step(ctx.handle, max(1, min(int(noise_step), cfg.samples_per_px - done.value)), C.byref(done)))
+                if progress is not None:
+                    capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
+                    progress()
+                capi.check(L.pt_noise_estimate(ctx.handle, C.byref(nz)))
+                if done.value >= 2 and nz.noise <= noise:
+                    break
+            if progress is None or cfg.samples_per_px <= 0:
+                capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
+        else:
+            step = max(1, cfg.samples_per_px // 10)
+            while done.value < cfg.samples_per_px:
+                capi.check(L.pt_step(ctx.handle, step, C.byref(done)))
+                capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
+                progress()
+            if cfg.samples_per_px <= 0:
+                capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
     finally:
         rc = L.pt_end(ctx.handle, C.byref(st))
     capi.check(rc)
-    progress()
-    return st.as_dict()
+    if progress is not None:
+        progress()
+    d = st.as_dict()
+    if want_moments:
+        d["spp_done"] = done.value
+    return with_moments(d)
 
 
 @dataclass
@@ -310,6 +396,40 @@ class FogConfig:
 
         env = os.environ if environ is None else environ
         return cls(enabled=env.get("PATHTRACER_GPU_FOG", "").lower() in ("1", "true", "on", "yes"))
+
+
+@dataclass
+class NoiseConfig:
+    """The stop rule of `render`: target 0 = off (render cfg.samples_per_px samples), else render until the frame noise is at or
+    below it, checking every `step` samples, with cfg.samples_per_px as the cap."""
+    target: float = 0.0
+    step: int = 16
+
+    @classmethod
+    def from_env(cls, environ=None) -> "NoiseConfig":
+        """PATHTRACER_GPU_NOISE=<float > 0> and PATHTRACER_GPU_NOISE_STEP=<int >= 1>; anything else keeps the default."""
+        import math
+        import os
+
+        env = os.environ if environ is None else environ
+        cfg = cls()
+        try:
+            f = float(env["PATHTRACER_GPU_NOISE"])
+            if f > 0 and math.isfinite(f):
+                cfg.target = f
+        except (KeyError, ValueError):
+            pass
+        try:
+            i = int(env["PATHTRACER_GPU_NOISE_STEP"])
+            if i >= 1:
+                cfg.step = i
+        except (KeyError, ValueError):
+            pass
+        return cfg
+
+    @property
+    def enabled(self) -> bool:
+        return self.target > 0
 
 
 @dataclass
