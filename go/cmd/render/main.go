@@ -4,7 +4,8 @@
 // Reference flags kept verbatim: -scene -mode -gpu -headless -out.
 // Additive flags: -width -height -spp -depth (override the mode preset), -seed, -devices,
 // -scene-settings (the editor's scene-settings override, internal/ui/app.go:60-75; off = main.go:52),
-// -noise -noise-step (render until the frame noise is at or below the target, -spp being the cap; DESIGN 3.9).
+// -noise -noise-step (render until the frame noise is at or below the target, -spp being the cap; DESIGN 3.9),
+// -adaptive -min-spp (with -noise: every 8x8 block stops at the target by itself; DESIGN 3.10).
 package main
 
 import (
@@ -34,6 +35,8 @@ func main() {
 	sceneSettings := flag.Bool("scene-settings", false, "let the scene file's settings block override the mode preset")
 	noise := flag.Float64("noise", 0, "render until the frame noise is at or below this target, -spp being the cap (0 = off, or PATHTRACER_GPU_NOISE)")
 	noiseStep := flag.Int("noise-step", 16, "samples per pixel between two noise checks (or PATHTRACER_GPU_NOISE_STEP)")
+	adaptive := flag.Bool("adaptive", false, "with -noise: stop every 8x8 block at the target by itself (or PATHTRACER_GPU_ADAPTIVE)")
+	minSpp := flag.Int("min-spp", 0, "with -adaptive: samples every block gets before the first check (or PATHTRACER_GPU_ADAPTIVE_MIN_SPP)")
 	flag.Parse()
 	log.Printf("flags: scene=%s mode=%s headless=%v out=%s\n", *scenePath, *mode, *headless, *output)
 
@@ -45,6 +48,11 @@ func main() {
 		flag.Visit(func(f *flag.Flag) { noiseGiven = noiseGiven || f.Name == "noise" || f.Name == "noise-step" })
 		if noiseGiven { // else the environment decides
 			hip.SetNoiseTarget(*noise, *noiseStep)
+		}
+		adaptiveGiven := false
+		flag.Visit(func(f *flag.Flag) { adaptiveGiven = adaptiveGiven || f.Name == "adaptive" || f.Name == "min-spp" })
+		if adaptiveGiven { // else the environment decides
+			hip.SetAdaptive(*adaptive, *minSpp)
 		}
 	} else {
 		engine.SetBackend(engine.BackendCPU)
@@ -92,7 +100,11 @@ func main() {
 		os.Exit(1)
 	}
 	if *useGPU {
-		if n, z := hip.LastFrame(); z > 0 {
+		if a := hip.LastAdaptive(); a.Blocks > 0 {
+			n, z := hip.LastFrame()
+			log.Printf("rendered %dx%d, %d to %d of at most %d spp per 8x8 block (adaptive: %d of %d blocks still above the target; frame noise %.6g)\n",
+				s.Width, s.Height, a.SppMin, n, s.SamplesPerPx, a.ActiveBlocks, a.Blocks, z)
+		} else if n, z := hip.LastFrame(); z > 0 {
 			log.Printf("rendered %dx%d, %d of at most %d spp (noise %.6g)\n", s.Width, s.Height, n, s.SamplesPerPx, z)
 		}
 	}

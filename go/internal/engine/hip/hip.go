@@ -53,7 +53,19 @@ var (
 	noiseStep   = 16
 	lastSpp     int     // samples per pixel of the last frame Render finished
 	lastNoise   float64 // its frame noise (0 without a noise target)
+
+	adaptiveSet    bool // false: PATHTRACER_GPU_ADAPTIVE / PATHTRACER_GPU_ADAPTIVE_MIN_SPP decide
+	adaptiveOn     bool
+	adaptiveMinSpp int
+	lastAdaptive   AdaptiveState // pt_adaptive_state of the last frame (zero unless it was adaptive)
 )
+
+// AdaptiveState mirrors struct pt_adaptive_state: the block table of an adaptive frame.
+type AdaptiveState struct {
+	Blocks, ActiveBlocks, Samples uint64
+	SppMin, SppMax                int
+	WorstActive                   float64
+}
 
 // SetDevices selects how many GPUs (ordinals 0..n-1) the frame is tiled over.
 // The tiles of a frame are collected on device 0 by peer copies over xGMI, or -- with
@@ -87,6 +99,42 @@ func SetNoiseTarget(target float64, step int) {
 	} else {
 		noiseStep = 16
 	}
+}
+
+// SetAdaptive makes the noise target the target of every 8x8 block (pt_set_adaptive, DESIGN 3.10): blocks stop one by one and
+// each pixel keeps the samples its block got; minSpp samples every block gets before the first check.  It takes effect together
+// with a noise target.
+func SetAdaptive(on bool, minSpp int) {
+	mu.Lock()
+	defer mu.Unlock()
+	adaptiveSet, adaptiveOn = true, on
+	if minSpp < 0 {
+		minSpp = 0
+	}
+	adaptiveMinSpp = minSpp
+}
+
+// LastAdaptive reports the block table of the last frame Render finished (the zero value unless it was adaptive).
+func LastAdaptive() AdaptiveState {
+	mu.Lock()
+	defer mu.Unlock()
+	return lastAdaptive
+}
+
+// adaptiveRule: whether adaptive sampling is in force and its min_spp (SetAdaptive, else the environment).
+func adaptiveRule() (bool, int) {
+	if adaptiveSet {
+		return adaptiveOn, adaptiveMinSpp
+	}
+	on, minSpp := false, 0
+	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_ADAPTIVE"))) {
+	case "1", "true", "on", "yes":
+		on = true
+	}
+	if v, err := strconv.Atoi(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_ADAPTIVE_MIN_SPP"))); err == nil && v >= 0 {
+		minSpp = v
+	}
+	return on, minSpp
 }
 
 // LastFrame reports the samples per pixel the last Render finished with and, when a noise target was set, its noise.
@@ -347,12 +395,22 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 	if rc := C.pt_set_moments(ctx, on); rc != C.PT_OK {
 		return lastError("pt_set_moments")
 	}
-	lastSpp, lastNoise = 0, 0
+	adaptive, minSpp := adaptiveRule()
+	adaptive = adaptive && toNoise // the noise target is the blocks' target
+	if adaptive {
+		ad := C.pt_adaptive{target: C.double(target), min_spp: C.int32_t(minSpp), step: C.int32_t(nstep)}
+		if rc := C.pt_set_adaptive(ctx, &ad); rc != C.PT_OK {
+			return lastError("pt_set_adaptive")
+		}
+	} else if rc := C.pt_set_adaptive(ctx, nil); rc != C.PT_OK {
+		return lastError("pt_set_adaptive")
+	}
+	lastSpp, lastNoise, lastAdaptive = 0, 0, AdaptiveState{}
 	pc := C.pt_config{width: C.int32_t(cfg.Width), height: C.int32_t(cfg.Height),
 		samples_per_px: C.int32_t(cfg.SamplesPerPx), max_depth: C.int32_t(cfg.MaxDepth), seed: C.uint64_t(seed)}
 	pix := (*C.uint8_t)(unsafe.Pointer(&img.Pix[0]))
 	if toNoise {
-		return renderToNoise(cs, &pc, cfg, img, pix, progress, target, nstep)
+		return renderToNoise(cs, &pc, cfg, img, pix, progress, target, nstep, adaptive)
 	}
 	if progress == nil {
 		if rc := C.pt_render(ctx, cs, &pc, pix, C.int32_t(img.Stride), nil, nil, nil, nil); rc != C.PT_OK {
@@ -399,9 +457,10 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 
 // renderToNoise: pt_begin with cfg.SamplesPerPx as the cap, then steps of nstep samples with a noise check after each;
 // stops at the first check with at least 2 samples done and noise <= target.  The image is that of a frame of the
-// samples done.  Called with mu held on a locked OS thread.
+// samples done.  With adaptive the blocks stop inside pt_step and the loop ends when a step adds nothing.  Called with mu held
+// on a locked OS thread.
 func renderToNoise(cs *C.pt_scene, pc *C.pt_config, cfg RenderConfig, img *image.RGBA, pix *C.uint8_t, progress func(),
-	target float64, nstep int) error {
+	target float64, nstep int, adaptive bool) error {
 	if rc := C.pt_begin(ctx, cs, pc); rc != C.PT_OK {
 		return lastError("pt_begin")
 	}
@@ -413,8 +472,12 @@ func renderToNoise(cs *C.pt_scene, pc *C.pt_config, cfg RenderConfig, img *image
 		if nstep < n {
 			n = nstep
 		}
+		before := done
 		if rc := C.pt_step(ctx, C.int32_t(n), &done); rc != C.PT_OK {
 			err = lastError("pt_step")
+			break
+		}
+		if adaptive && done == before { // every block has stopped
 			break
 		}
 		if progress != nil {
@@ -428,8 +491,14 @@ func renderToNoise(cs *C.pt_scene, pc *C.pt_config, cfg RenderConfig, img *image
 			err = lastError("pt_noise_estimate")
 			break
 		}
-		if int(done) >= 2 && float64(nz.noise) <= target {
+		if !adaptive && int(done) >= 2 && float64(nz.noise) <= target {
 			break
+		}
+	}
+	var as C.struct_pt_adaptive_state
+	if adaptive && err == nil {
+		if rc := C.pt_adaptive_state(ctx, &as); rc != C.PT_OK {
+			err = lastError("pt_adaptive_state")
 		}
 	}
 	if err == nil && (progress == nil || cfg.SamplesPerPx <= 0) {
@@ -445,6 +514,10 @@ func renderToNoise(cs *C.pt_scene, pc *C.pt_config, cfg RenderConfig, img *image
 			progress()
 		}
 		lastSpp, lastNoise = int(done), float64(nz.noise)
+		if adaptive {
+			lastAdaptive = AdaptiveState{Blocks: uint64(as.blocks), ActiveBlocks: uint64(as.active_blocks), Samples: uint64(as.samples),
+				SppMin: int(as.spp_min), SppMax: int(as.spp_max), WorstActive: float64(as.worst_active)}
+		}
 	}
 	return err
 }

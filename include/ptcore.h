@@ -379,6 +379,53 @@ int32_t pt_read_moments(pt_ctx *ctx, double *m2);
 int32_t pt_noise_estimate(pt_ctx *ctx, pt_noise *out);
 
 /*
+ * Adaptive sampling (additive to ABI 4): 8x8 pixel blocks stop when their own noise reaches a target.  Off unless
+ * asked for.
+ *   pt_set_adaptive(ctx, &a) : later frames on ctx (pt_begin ... pt_end, pt_render) are adaptive; NULL = off (the default).  Such
+ *                              frames collect second moments whether or not pt_set_moments asked for them.
+ * The unit is one 8x8 sub-block of a 32x32 tile.  A block with no pixel inside the frame is never sampled and has count 0.  With
+ * e2 the per-pixel quantity of pt_noise_estimate, taken with the pixel's own n, a block's noise is b = sqrt(sum of e2 / k) over its
+ * k pixels inside the frame (a NaN or infinite e2 adds 0 and still counts in k).  At the end of every pt_step, once the samples
+ * done reach max(min_spp, 2), every still-active block with b <= target becomes inactive and stays so for the rest of the frame;
+ * later steps trace the active blocks only.  All active blocks hold `done` samples, an inactive block keeps the count it stopped
+ * at.  pt_step returns `done`; once no block is active it adds nothing and keeps returning the last value.  Which blocks stop
+ * depends on the sizes of the steps, and on nothing else: not on spp_chunk, the buffer budget, the device count or the scan form.
+ * pt_read / pt_end / pt_render normalise each pixel by its own count; accum and the moments stay raw sums, so a block stopped at
+ * n holds exactly the pixels of a plain n-sample frame.  pt_render steps internally, `step` samples at a time (values < 1 count
+ * as 1), up to samples_per_px, and stops early when no block is active.  pt_stats.samples is the sum of the counts;
+ * pt_noise_estimate uses each pixel's own n and reports spp = the largest count; PT_FLAG_PIXEL_STATS gives the nseg / ndraw of each
+ * pixel's first n samples.
+ * Known bias: a block can stop while it is still missing rare bright paths (its variance estimate has not seen them either);
+ * min_spp is the guard against that.  Neighbouring blocks do not keep each other alive.
+ *   pt_adaptive_state       : the block table of the open or last frame.
+ *   pt_read_sample_counts   : spp = width*height uint32, row-major: the samples each pixel holds.
+ * Both are valid when pt_read_moments is (and return PT_ERR_STATE otherwise, also for a frame that was not adaptive).
+ * pt_render_tiles_device neither adapts nor fails.  An adaptive frame is refused with PT_ERR_STATE, before anything is launched and
+ * with the context left usable, together with GL shading (pt_set_shading), with injected primary rays
+ * (pt_debug_set_primary_rays) and on a context created with PTCORE_PIPELINE=wavefront or walk32 (the adaptive job map exists for
+ * the default pipeline only).  Thin-lens cameras take the one-job-per-lane ray generation in adaptive frames.
+ */
+typedef struct pt_adaptive {
+    double target;
+    int32_t min_spp;
+    int32_t step; /* used by pt_render only */
+} pt_adaptive;
+
+/* (the struct and the function that fills it share their name: C keeps struct tags apart from functions, a typedef name it would
+ * not, so this one struct is spelled with its tag) */
+struct pt_adaptive_state {
+    uint64_t blocks;        /* blocks with a pixel inside the frame */
+    uint64_t active_blocks;
+    uint64_t samples;       /* sum of the in-frame pixels' counts */
+    int32_t spp_min, spp_max;
+    double worst_active;    /* largest block noise among active blocks at the last check, 0 if none */
+};
+
+int32_t pt_set_adaptive(pt_ctx *ctx, const pt_adaptive *a);
+int32_t pt_adaptive_state(pt_ctx *ctx, struct pt_adaptive_state *out);
+int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp);
+
+/*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the
  * environment at pt_create, the trace kernel runs a build that counts, per code
  * section, wave executions, active lanes and shader-clock cycles.  Copies up to n

@@ -104,6 +104,18 @@ class PtNoise(C.Structure):  # pt_noise: the frame noise figure of pt_noise_esti
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class PtAdaptive(C.Structure):  # pt_adaptive: block noise target, samples before the first check, pt_render's step
+    _fields_ = [("target", C.c_double), ("min_spp", C.c_int32), ("step", C.c_int32)]
+
+
+class PtAdaptiveState(C.Structure):  # struct pt_adaptive_state: the block table of an adaptive frame
+    _fields_ = [("blocks", C.c_uint64), ("active_blocks", C.c_uint64), ("samples", C.c_uint64), ("spp_min", C.c_int32),
+                ("spp_max", C.c_int32), ("worst_active", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PtShard(C.Structure):
     _fields_ = [("index", C.c_int32), ("count", C.c_int32)]
 
@@ -152,6 +164,9 @@ SYMBOLS = [
     ("pt_set_moments", C.c_int32, [_vp, C.c_int32]),                     # additive to ABI 4 (see has())
     ("pt_read_moments", C.c_int32, [_vp, C.POINTER(C.c_double)]),
     ("pt_noise_estimate", C.c_int32, [_vp, C.POINTER(PtNoise)]),
+    ("pt_set_adaptive", C.c_int32, [_vp, C.POINTER(PtAdaptive)]),         # additive to ABI 4 (see has())
+    ("pt_adaptive_state", C.c_int32, [_vp, C.POINTER(PtAdaptiveState)]),
+    ("pt_read_sample_counts", C.c_int32, [_vp, C.POINTER(C.c_uint32)]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
@@ -193,7 +208,7 @@ def load():
 
 
 ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_rays", "pt_set_moments", "pt_read_moments",
-            "pt_noise_estimate")  # added within ABI 4: detected by presence
+            "pt_noise_estimate", "pt_set_adaptive", "pt_adaptive_state", "pt_read_sample_counts")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:

@@ -62,6 +62,8 @@ struct Core {
     decltype(&pt_set_shading) set_shading = nullptr;  // optional (additive to ABI 4): null in an older build
     decltype(&pt_set_moments) set_moments = nullptr;  // optional, as set_shading (the noise target needs all three)
     decltype(&pt_noise_estimate) noise_estimate = nullptr;
+    decltype(&pt_set_adaptive) set_adaptive = nullptr;  // optional, as set_shading (adaptive sampling needs both)
+    int32_t (*adaptive_state)(pt_ctx *, struct pt_adaptive_state *) = nullptr;
     std::string error;  // sticky load error, like the reference's cached GL init failure (gpu.go:279-286)
 };
 
@@ -73,6 +75,8 @@ int g_shading = -1;  // -1: not set yet, PATHTRACER_GPU_SHADING decides; else PT
 bool g_noise_set = false;  // false: PATHTRACER_GPU_NOISE / _STEP decide
 double g_noise_target = 0;
 int g_noise_step = 16;
+int g_adaptive = -1;  // -1: not set yet, PATHTRACER_GPU_ADAPTIVE / _MIN_SPP decide
+int g_adaptive_min_spp = 0;
 std::mutex g_mu;  // requests are serialised, like the reference's single GL worker (gpu.go:2534-2546)
 
 std::string self_dir() {
@@ -121,6 +125,8 @@ bool load_core() {
     c.set_shading = reinterpret_cast<decltype(c.set_shading)>(dlsym(h, "pt_set_shading"));
     c.set_moments = reinterpret_cast<decltype(c.set_moments)>(dlsym(h, "pt_set_moments"));
     c.noise_estimate = reinterpret_cast<decltype(c.noise_estimate)>(dlsym(h, "pt_noise_estimate"));
+    c.set_adaptive = reinterpret_cast<decltype(c.set_adaptive)>(dlsym(h, "pt_set_adaptive"));
+    c.adaptive_state = reinterpret_cast<decltype(c.adaptive_state)>(dlsym(h, "pt_adaptive_state"));
     if (c.abi_version() != PT_ABI_VERSION) {
         g_core.error = "libptcore.so ABI version mismatch";
         dlclose(h);
@@ -317,6 +323,43 @@ int GetNoiseStep() {
     return g_noise_set ? g_noise_step : s;
 }
 
+void AdaptiveFromEnv(bool &on, int &min_spp) {
+    on = false;
+    min_spp = 0;
+    if (const char *e = std::getenv("PATHTRACER_GPU_ADAPTIVE")) {
+        std::string v(e);
+        for (char &ch : v) ch = (char)std::tolower((unsigned char)ch);
+        on = v == "1" || v == "true" || v == "on" || v == "yes";
+    }
+    if (const char *e = std::getenv("PATHTRACER_GPU_ADAPTIVE_MIN_SPP")) {
+        char *end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end != e && *end == 0 && v >= 0 && v <= 0x7fffffffL) min_spp = (int)v;
+    }
+}
+
+void SetAdaptive(bool on, int min_spp) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_adaptive = on ? 1 : 0;
+    g_adaptive_min_spp = min_spp >= 0 ? min_spp : 0;
+}
+
+bool GetAdaptive() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    bool on;
+    int m;
+    AdaptiveFromEnv(on, m);
+    return g_adaptive < 0 ? on : g_adaptive == 1;
+}
+
+int GetAdaptiveMinSpp() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    bool on;
+    int m;
+    AdaptiveFromEnv(on, m);
+    return g_adaptive < 0 ? m : g_adaptive_min_spp;
+}
+
 void Shutdown() {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_ctx && g_core.handle) g_core.destroy(g_ctx);
@@ -365,6 +408,21 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     const bool to_noise = noise_target > 0;
     if (to_noise && !(g_core.set_moments && g_core.noise_estimate)) return "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate";
     if (g_core.set_moments && g_core.set_moments(g_ctx, to_noise ? 1 : 0) != PT_OK) return std::string("pt_set_moments: ") + g_core.last_error();
+    bool adaptive = g_adaptive == 1;
+    int min_spp = g_adaptive_min_spp;
+    if (g_adaptive < 0) AdaptiveFromEnv(adaptive, min_spp);
+    adaptive = adaptive && to_noise;  // the noise target is the blocks' target; without one there is nothing to adapt to
+    if (adaptive && !(g_core.set_adaptive && g_core.adaptive_state)) return "adaptive sampling: libptcore.so lacks pt_set_adaptive / pt_adaptive_state";
+    if (g_core.set_adaptive) {
+        pt_adaptive ad;
+        std::memset(&ad, 0, sizeof ad);
+        ad.target = noise_target;
+        ad.min_spp = min_spp;
+        ad.step = noise_step;
+        if (g_core.set_adaptive(g_ctx, adaptive ? &ad : nullptr) != PT_OK) return std::string("pt_set_adaptive: ") + g_core.last_error();
+    }
+    struct pt_adaptive_state as;
+    std::memset(&as, 0, sizeof as);
     pt_config pc;
     std::memset(&pc, 0, sizeof pc);
     pc.width = cfg.Width;
@@ -382,15 +440,17 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         if (g_core.begin(g_ctx, &flat.sc, &pc) != PT_OK) return std::string("pt_begin: ") + g_core.last_error();
         int32_t done = 0;
         while (err.empty() && done < cfg.SamplesPerPx) {
-            const int32_t left = cfg.SamplesPerPx - done;
+            const int32_t left = cfg.SamplesPerPx - done, before = done;
             if (g_core.step(g_ctx, noise_step < left ? noise_step : left, &done) != PT_OK) { err = std::string("pt_step: ") + g_core.last_error(); break; }
+            if (adaptive && done == before) break;  // every block has stopped: the step added nothing
             if (progress) {
                 if (g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK) { err = std::string("pt_read: ") + g_core.last_error(); break; }
                 progress();
             }
             if (g_core.noise_estimate(g_ctx, &nz) != PT_OK) { err = std::string("pt_noise_estimate: ") + g_core.last_error(); break; }
-            if (done >= 2 && nz.noise <= noise_target) break;
+            if (!adaptive && done >= 2 && nz.noise <= noise_target) break;  // (adaptive: the blocks stop inside pt_step)
         }
+        if (adaptive && err.empty() && g_core.adaptive_state(g_ctx, &as) != PT_OK) err = std::string("pt_adaptive_state: ") + g_core.last_error();
         if (err.empty() && (!progress || cfg.SamplesPerPx <= 0) && g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK)
             err = std::string("pt_read: ") + g_core.last_error();
         if (g_core.end(g_ctx, &st) != PT_OK && err.empty()) err = std::string("pt_end: ") + g_core.last_error();
@@ -420,6 +480,10 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         stats->device_ms = st.device_ms; stats->num_devices = st.num_devices; stats->spp_chunk = st.spp_chunk;
         stats->spp_done = spp_done;
         stats->noise = to_noise ? nz.noise : 0;
+        stats->adaptive = adaptive;
+        stats->blocks = as.blocks;
+        stats->active_blocks = as.active_blocks;
+        stats->spp_min = as.spp_min;
     }
     return err;
 }

@@ -36,6 +36,9 @@ struct Stats {
     int num_devices = 0, spp_chunk = 0;
     int spp_done = 0;   // samples per pixel actually rendered (below SamplesPerPx when a noise target stopped the frame)
     double noise = 0;   // frame noise at the stop (pt_noise_estimate); 0 when no noise target was set
+    bool adaptive = false;  // the frame was adaptive (SetAdaptive): spp_done is the largest count, samples the sum of the counts
+    uint64_t blocks = 0, active_blocks = 0;  // pt_adaptive_state of the frame: 8x8 blocks inside it, those still above the target
+    int spp_min = 0;
 };
 
 namespace hip {
@@ -61,6 +64,13 @@ void SetNoiseTarget(double target, int step = 16);
 double GetNoiseTarget();
 int GetNoiseStep();
 void NoiseFromEnv(double &target, int &step);  // PATHTRACER_GPU_NOISE = float > 0 (else 0: off), _STEP = int >= 1 (else 16)
+// Adaptive sampling: with a noise target set, that target is the one of every 8x8 block (pt_set_adaptive) instead of
+// the frame's: blocks stop one by one, the frame ends when none is active or at the cap.  min_spp = samples every block gets before
+// the first check.  The initial value is PATHTRACER_GPU_ADAPTIVE / PATHTRACER_GPU_ADAPTIVE_MIN_SPP (AdaptiveFromEnv).
+void SetAdaptive(bool on, int min_spp = 0);
+bool GetAdaptive();
+int GetAdaptiveMinSpp();
+void AdaptiveFromEnv(bool &on, int &min_spp);  // PATHTRACER_GPU_ADAPTIVE = 1 / true / on / yes, _MIN_SPP = int >= 0 (else 0)
 void Shutdown();                                    // releases the process-wide context
 }  // namespace hip
 

@@ -11,6 +11,8 @@
 // reference's OpenGL backend does (sky blend, volumetric in-scatter; also env PATHTRACER_GPU_FOG=1); without it fog is
 // ignored like the CPU engine ignores it.  -noise T renders until the frame noise (pt_noise_estimate) is at or
 // below T, checking every -noise-step samples, with -spp as the cap (also env PATHTRACER_GPU_NOISE, PATHTRACER_GPU_NOISE_STEP).
+// -adaptive makes T the target of every 8x8 block (pt_set_adaptive): blocks stop one by one, each pixel keeps the
+// samples its block got; -min-spp N samples every block at least N times first (also env PATHTRACER_GPU_ADAPTIVE, _MIN_SPP).
 #include <cerrno>
 #include <chrono>
 #include <cstdarg>
@@ -55,17 +57,22 @@ struct Flags {
     unsigned long long seed = 1;
     double noise = 0;
     int noise_step = 16;
+    bool adaptive = false;
+    int min_spp = 0;
 };
 
 void usage() {
     std::fprintf(stderr,
                  "Usage of render:\n"
+                 "  -adaptive\n    \twith -noise: stop every 8x8 block at the target by itself (default false, or PATHTRACER_GPU_ADAPTIVE)\n"
                  "  -depth int\n    \tmax path depth (default: the mode preset)\n"
                  "  -devices int\n    \tnumber of GPUs to tile the image over (default 1)\n"
                  "  -fog\n    \tdraw the scene's fog block like the reference's GPU backend (default false, or PATHTRACER_GPU_FOG)\n"
                  "  -gpu\n    \tuse GPU backend for rendering (if available)\n"
                  "  -headless\n    \trender without UI and save PNG\n"
                  "  -height int\n    \timage height (default: the mode preset)\n"
+                 "  -min-spp int\n    \twith -adaptive: samples every block gets before the first check (default 0, or\n"
+                 "    \tPATHTRACER_GPU_ADAPTIVE_MIN_SPP)\n"
                  "  -mode string\n    \trender mode: preview or final (default \"preview\")\n"
                  "  -noise float\n    \trender until the frame noise is at or below this target, -spp being the cap (default 0 = off, or\n"
                  "    \tPATHTRACER_GPU_NOISE)\n"
@@ -100,17 +107,17 @@ int parse(int argc, char **argv, Flags &f) {
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         if (name == "h" || name == "help") { usage(); return 0; }
-        if (name == "gpu" || name == "headless" || name == "scene-settings" || name == "fog") {
+        if (name == "gpu" || name == "headless" || name == "scene-settings" || name == "fog" || name == "adaptive") {
             bool b = true;
             if (has_val && !parse_bool(val, b)) {
                 std::fprintf(stderr, "invalid boolean value \"%s\" for -%s: parse error\n", val.c_str(), name.c_str());
                 usage();
                 return 2;
             }
-            (name == "gpu" ? f.gpu : name == "headless" ? f.headless : name == "fog" ? f.fog : f.scene_settings) = b;
+            (name == "gpu" ? f.gpu : name == "headless" ? f.headless : name == "fog" ? f.fog : name == "adaptive" ? f.adaptive : f.scene_settings) = b;
             continue;
         }
-        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading", "noise", "noise-step"};
+        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading", "noise", "noise-step", "min-spp"};
         bool ok = false;
         for (const char *k : known) ok = ok || name == k;
         if (!ok) {
@@ -163,6 +170,7 @@ int parse(int argc, char **argv, Flags &f) {
             else if (name == "depth") f.depth = (int)n;
             else if (name == "devices") f.devices = (int)n;
             else if (name == "noise-step") f.noise_step = n >= 1 && n <= 0x7fffffffLL ? (int)n : 16;
+            else if (name == "min-spp") f.min_spp = n >= 0 && n <= 0x7fffffffLL ? (int)n : 0;
             else f.seed = (unsigned long long)n;
         }
     }
@@ -187,6 +195,8 @@ int render_headless(const Flags &f) {
     engine::hip::SetFog(f.fog);
     engine::hip::SetShading(f.shading == "gl" ? PT_SHADING_GL : PT_SHADING_CPU);
     engine::hip::SetNoiseTarget(f.noise, f.noise_step);
+    engine::hip::SetAdaptive(f.adaptive, f.min_spp);
+    if (f.adaptive && !(f.noise > 0)) logf("adaptive: no -noise target given, nothing to adapt to (a plain frame)");
     if (f.shading == "gl") logf("shading: gl (the reference's GPU shader; spp counts passes of 16 paths)");
     if (f.fog) logf("fog: drawing the scene's fog block (%s)", sc->FogPtr ? "present" : "absent: nothing to draw");
     try {
@@ -203,7 +213,12 @@ int render_headless(const Flags &f) {
         auto t0 = std::chrono::steady_clock::now();
         engine::RenderInto(*sc, cfg, img, nullptr, &st);
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (f.noise > 0)
+        if (st.adaptive)
+            logf("rendered %dx%d, %d to %d of at most %d spp per 8x8 block (adaptive: block target %.6g, %llu of %llu blocks still above it; "
+                 "frame noise %.6g), depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, %.1f M samples/s", cfg.Width, cfg.Height, st.spp_min,
+                 st.spp_done, cfg.SamplesPerPx, f.noise, (unsigned long long)st.active_blocks, (unsigned long long)st.blocks, st.noise,
+                 cfg.MaxDepth, st.num_devices, dt, st.segments / dt / 1e6, st.samples / dt / 1e6);
+        else if (f.noise > 0)
             logf("rendered %dx%d, %d of at most %d spp (noise %.6g, target %.6g), depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, "
                  "%.1f M samples/s", cfg.Width, cfg.Height, st.spp_done, cfg.SamplesPerPx, st.noise, f.noise, cfg.MaxDepth, st.num_devices, dt,
                  st.segments / dt / 1e6, st.samples / dt / 1e6);
@@ -229,6 +244,7 @@ int main(int argc, char **argv) {
     f.fog = engine::hip::FogFromEnv();
     f.shading = engine::hip::ShadingFromEnv() == PT_SHADING_GL ? "gl" : "cpu";
     engine::hip::NoiseFromEnv(f.noise, f.noise_step);
+    engine::hip::AdaptiveFromEnv(f.adaptive, f.min_spp);
     int rc = parse(argc, argv, f);
     if (rc >= 0) return rc;
     logf("flags: scene=%s mode=%s headless=%s out=%s", f.scene.c_str(), f.mode.c_str(), f.headless ? "true" : "false",

@@ -1418,6 +1418,84 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_kernel(const DevFrame F, cons
     ray_ndraw[myjob] = (uint16_t)(nd < 0xfffeu ? nd : 0xfffeu);
 }
 
+// Adaptive sampling (pt_set_adaptive): raygen_kernel for a chunk whose jobs are those of the active 8x8 blocks only,
+// F.njobs = nact * 64 * S: row q belongs to compact block q / S, whose block index is active[q / S].  A kernel of its own, so that
+// raygen_kernel stays the code it was; thin-lens cameras take this form too in adaptive frames (the rejection loop per lane).
+__global__ __launch_bounds__(PT_BLOCK) void raygen_adaptive_kernel(const DevFrame F, const DevCamera cam, double *__restrict__ ray,
+                                                                     unsigned long long *__restrict__ ray_rng,
+                                                                     uint16_t *__restrict__ ray_ndraw,
+                                                                     const uint32_t *__restrict__ active) {
+    const uint32_t myjob = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (myjob >= F.njobs) return;
+    // job -> (tile, sub-block, sample, pixel)
+    const uint32_t p = myjob & 63u;
+    const uint32_t q = __builtin_amdgcn_readfirstlane(myjob >> 6);  // the wave's row of 64 jobs: tile, sub-block and sample are wave-uniform (scalar unit)
+    uint32_t x, y;
+    const uint32_t cblk = q / F.S, sl = q - cblk * F.S;
+    block_pixel(F, active[cblk], p, x, y);  // wave-uniform index: a scalar load
+    if (!(x < (uint32_t)F.width && y < (uint32_t)F.height)) {
+        ray_ndraw[myjob] = 0xffffu;
+        return;
+    }
+    uint32_t nd = 0;
+    const uint64_t pixel = (uint64_t)y * (uint64_t)(uint32_t)F.width + (uint64_t)x;
+    uint64_t rs = ptm::stream_init(F.seed_key, pixel, (uint64_t)(F.s0 + sl));
+#define RG_DRAW(var) const double var = ptm::stream_next(rs); nd++;
+    RG_DRAW(xi_u)
+    RG_DRAW(xi_v)
+    const double u = ((double)x + xi_u) * F.inv_width;
+    const double vv = ((F.height_m1 - (double)y) + xi_v) * F.inv_height;
+    const double tx_ = cam.lower_left[0] + cam.horizontal[0] * u;
+    const double ty_ = cam.lower_left[1] + cam.horizontal[1] * u;
+    const double tz_ = cam.lower_left[2] + cam.horizontal[2] * u;
+    const double ax = tx_ + cam.vertical[0] * vv;
+    const double ay = ty_ + cam.vertical[1] * vv;
+    const double az = tz_ + cam.vertical[2] * vv;
+    double ox, oy, oz, dx, dy, dz;
+    if (cam.lens_radius > 0) {
+        double rx, ry, rz;
+        for (;;) {  // randomInUnitSphere
+            RG_DRAW(d0)
+            RG_DRAW(d1)
+            RG_DRAW(d2)
+            rx = d0 * 2 - 1;
+            ry = d1 * 2 - 1;
+            rz = d2 * 2 - 1;
+            const double lenSq = rx * rx + ry * ry + rz * rz;
+            if (lenSq >= 1.0) continue;
+            break;
+        }
+        rx = rx * cam.lens_radius;
+        ry = ry * cam.lens_radius;
+        const double offx = cam.u[0] * rx + cam.v[0] * ry;
+        const double offy = cam.u[1] * rx + cam.v[1] * ry;
+        const double offz = cam.u[2] * rx + cam.v[2] * ry;
+        ox = cam.origin[0] + offx;
+        oy = cam.origin[1] + offy;
+        oz = cam.origin[2] + offz;
+        dx = (ax - cam.origin[0]) - offx;
+        dy = (ay - cam.origin[1]) - offy;
+        dz = (az - cam.origin[2]) - offz;
+    } else {
+        ox = cam.origin[0];
+        oy = cam.origin[1];
+        oz = cam.origin[2];
+        dx = ax - cam.origin[0];
+        dy = ay - cam.origin[1];
+        dz = az - cam.origin[2];
+    }
+#undef RG_DRAW
+    const size_t nj = F.njobs;
+    ray[myjob] = ox;
+    ray[nj + myjob] = oy;
+    ray[2 * nj + myjob] = oz;
+    ray[3 * nj + myjob] = dx;
+    ray[4 * nj + myjob] = dy;
+    ray[5 * nj + myjob] = dz;
+    ray_rng[myjob] = rs;
+    ray_ndraw[myjob] = (uint16_t)(nd < 0xfffeu ? nd : 0xfffeu);
+}
+
 // Diagnostics (pt_debug_set_primary_rays): replaces the primary rays ray generation left in the six planes by the caller's table,
 // [W*H*spp][6] doubles (origin, direction) indexed (y*W + x)*spp + sample.  Runs right after the ray-generation launch of a chunk;
 // jobs whose pixel lies outside the frame (0xffff) are left alone, and so are the stream state and the draw count: the camera draws
@@ -2758,9 +2836,28 @@ struct ResolveArgs {
 
 __device__ __forceinline__ uint32_t tonemap_pack(double cx, double cy, double cz, int32_t spp);
 
-__global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) {
-    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
-    if (slot >= R.nslots) return;
+// The tables of an adaptive frame (pt_set_adaptive), per device: active[c] = block index of compact block c (ascending),
+// blk_spp[b] = samples block b holds.  Job buffers are compact (row (c * S + s) of 64 jobs), acc / m2 keep their full-frame slots.
+struct AdaptTable {
+    const uint32_t *active;   // [nact]
+    const uint32_t *blk_spp;  // [nslots / 64]
+    uint32_t nact;
+};
+
+// (ADAPT: resolve_adaptive_kernel below.  Its add runs over the nact * 64 slots of the active blocks, its finish over every slot with
+// 1 / n of the slot's own block.)
+template <bool ADAPT>
+__device__ __forceinline__ void resolve_body(const ResolveArgs &R, const AdaptTable &T) {
+    uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    uint32_t cblk;  // the block's rows in the job buffers start at cblk * S
+    if (ADAPT && R.have_chunk) {
+        if (slot >= T.nact * 64u) return;
+        cblk = __builtin_amdgcn_readfirstlane(slot >> 6);
+        slot = T.active[cblk] * 64u + (slot & 63u);  // wave-uniform index: a scalar load
+    } else {
+        if (slot >= R.nslots) return;
+        cblk = slot >> 6;
+    }
     const uint32_t blk = slot >> 6, p = slot & 63u;
     const uint32_t lt = blk >> 4, sb = blk & 15u;
     const uint32_t t = (uint32_t)R.shard_index + lt * (uint32_t)R.shard_count;
@@ -2779,7 +2876,7 @@ __global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) 
             if (R.acc_seg) { nseg = R.acc_seg[slot]; ndraw = R.acc_draw[slot]; }
         }
         if (R.have_chunk) {
-            const size_t base = (size_t)blk * R.S * 64u + p;
+            const size_t base = (size_t)cblk * R.S * 64u + p;
             for (uint32_t s = 0; s < R.S; s++) {  // col = col.add(sample), renderer.go:186, in sample order
                 const size_t j = base + (size_t)s * 64u;
                 const double4 l = reinterpret_cast<const double4 *>(R.L)[j];
@@ -2802,9 +2899,10 @@ __global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) 
                 packed = tonemap_pack(cx, cy, cz, R.gl_spp);
             } else if (inside) {
                 // renderer.go:190-221
-                const double r = ptm::f_sqrt(cx * R.inv_samples) * 255.999;
-                const double g = ptm::f_sqrt(cy * R.inv_samples) * 255.999;
-                const double b = ptm::f_sqrt(cz * R.inv_samples) * 255.999;
+                const double inv_samples = ADAPT ? 1.0 / (double)T.blk_spp[blk] : R.inv_samples;
+                const double r = ptm::f_sqrt(cx * inv_samples) * 255.999;
+                const double g = ptm::f_sqrt(cy * inv_samples) * 255.999;
+                const double b = ptm::f_sqrt(cz * inv_samples) * 255.999;
                 packed = quantise(r) | (quantise(g) << 8) | (quantise(b) << 16) | (255u << 24);
             }
             reinterpret_cast<uint32_t *>(R.tiles_rgba)[pix] = packed;
@@ -2820,6 +2918,10 @@ __global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) 
         }
     }
 }
+
+__global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) { resolve_body<false>(R, AdaptTable{nullptr, nullptr, 0u}); }
+
+__global__ __launch_bounds__(PT_BLOCK) void resolve_adaptive_kernel(const ResolveArgs R, const AdaptTable T) { resolve_body<true>(R, T); }
 
 struct UntileArgs {
     const uint8_t *tiles_rgba;   // concatenated per shard: shard k holds its tiles in local order
@@ -2876,9 +2978,18 @@ struct MomentsArgs {
     int32_t width, height, ntx, shard_index, shard_count;
 };
 
-__global__ __launch_bounds__(PT_BLOCK) void moments_kernel(const MomentsArgs M) {
-    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
-    if (slot >= M.nslots) return;
+template <bool ADAPT>
+__device__ __forceinline__ void moments_body(const MomentsArgs &M, const AdaptTable &T) {
+    uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    uint32_t cblk;  // as in resolve_body
+    if (ADAPT && M.have_chunk) {
+        if (slot >= T.nact * 64u) return;
+        cblk = __builtin_amdgcn_readfirstlane(slot >> 6);
+        slot = T.active[cblk] * 64u + (slot & 63u);
+    } else {
+        if (slot >= M.nslots) return;
+        cblk = slot >> 6;
+    }
     const uint32_t blk = slot >> 6, p = slot & 63u;
     const uint32_t lt = blk >> 4, sb = blk & 15u;
     const uint32_t t = (uint32_t)M.shard_index + lt * (uint32_t)M.shard_count;
@@ -2895,7 +3006,7 @@ __global__ __launch_bounds__(PT_BLOCK) void moments_kernel(const MomentsArgs M) 
             qz = M.m2[2 * (size_t)M.nslots + slot];
         }
         if (M.have_chunk) {
-            const size_t base = (size_t)blk * M.S * 64u + p;
+            const size_t base = (size_t)cblk * M.S * 64u + p;
             for (uint32_t s = 0; s < M.S; s++) {  // in sample order, like the sum itself
                 const double4 l = reinterpret_cast<const double4 *>(M.L)[base + (size_t)s * 64u];
                 qx += l.x * l.x;
@@ -2914,6 +3025,10 @@ __global__ __launch_bounds__(PT_BLOCK) void moments_kernel(const MomentsArgs M) 
         M.tiles_m2[3 * pix + 2] = inside ? qz : 0.0;
     }
 }
+
+__global__ __launch_bounds__(PT_BLOCK) void moments_kernel(const MomentsArgs M) { moments_body<false>(M, AdaptTable{nullptr, nullptr, 0u}); }
+
+__global__ __launch_bounds__(PT_BLOCK) void moments_adaptive_kernel(const MomentsArgs M, const AdaptTable T) { moments_body<true>(M, T); }
 
 // Frame noise (pt_noise_estimate, the metric of include/ptcore.h): per slot inside the frame, with n samples done, sums S
 // (resolve_kernel's) and Q (moments_kernel's):
@@ -2936,7 +3051,9 @@ struct NoiseArgs {
     int32_t width, height, ntx, shard_index, shard_count;
 };
 
-__global__ __launch_bounds__(PT_BLOCK) void noise_kernel(const NoiseArgs A) {
+// (ADAPT: noise_adaptive_kernel below -- every slot with the n of its own block)
+template <bool ADAPT>
+__device__ __forceinline__ void noise_body(const NoiseArgs &A, const uint32_t *__restrict__ blk_spp) {
     __shared__ double s_sum[PT_BLOCK / PT_WAVE], s_max[PT_BLOCK / PT_WAVE];
     __shared__ uint32_t s_bad[PT_BLOCK / PT_WAVE];
     const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
@@ -2949,7 +3066,8 @@ __global__ __launch_bounds__(PT_BLOCK) void noise_kernel(const NoiseArgs A) {
         const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
         const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u), y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
         if (x < (uint32_t)A.width && y < (uint32_t)A.height) {
-            const double n = (double)A.n, n1 = (double)(A.n - 1);
+            const int32_t ni = ADAPT ? (int32_t)blk_spp[blk] : A.n;
+            const double n = (double)ni, n1 = (double)(ni - 1);
             double msum = 0.0, vsum = 0.0;
             for (uint32_t c = 0; c < 3u; c++) {
                 const double m = A.acc[c * (size_t)A.nslots + slot] / n;
@@ -2992,6 +3110,149 @@ __global__ __launch_bounds__(PT_BLOCK) void noise_kernel(const NoiseArgs A) {
         }
         A.partial[blockIdx.x] = r;
     }
+}
+
+__global__ __launch_bounds__(PT_BLOCK) void noise_kernel(const NoiseArgs A) { noise_body<false>(A, nullptr); }
+
+__global__ __launch_bounds__(PT_BLOCK) void noise_adaptive_kernel(const NoiseArgs A, const uint32_t *__restrict__ blk_spp) { noise_body<true>(A, blk_spp); }
+
+// ------------------------------------------------------------------------------------------------------------
+// Adaptive sampling (pt_set_adaptive): the check that ends every pt_step of an adaptive frame.
+//
+// block_noise_kernel: one wave per active block, one lane per pixel.  With n = the samples the active blocks hold, a lane inside the
+// frame computes the e2 of include/ptcore.h (a NaN or infinite e2 adds 0), the wave adds them over the xor butterfly of noise_kernel
+// and lane 0 writes  blk_spp[block] = n,  noise[c] = b = sqrt(sum / k)  (k = the block's pixels inside the frame) and
+// keep[c] = 0 when the check decides (decide != 0) and b <= target, else 1.  No atomics: the same bits for every chunk size,
+// device count and scan form, since acc and m2 are.
+struct BlockNoiseArgs {
+    const double *acc;       // [3][nslots]
+    const double *m2;        // [3][nslots]
+    const uint32_t *active;  // [nact]
+    uint32_t *blk_spp;       // [nslots / 64]
+    uint32_t *keep;          // [nact]
+    double *noise;           // [nact]
+    double target;
+    uint32_t nslots, nact;
+    int32_t n;               // samples the active blocks hold
+    int32_t decide;          // 0: n is below max(min_spp, 2), every block stays active
+    int32_t width, height, ntx, shard_index, shard_count;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void block_noise_kernel(const BlockNoiseArgs A) {
+    const uint32_t c = __builtin_amdgcn_readfirstlane((blockIdx.x * PT_BLOCK + threadIdx.x) >> 6);
+    if (c >= A.nact) return;  // (wave-uniform)
+    const uint32_t blk = A.active[c], p = threadIdx.x & 63u;
+    const uint32_t lt = blk >> 4, sb = blk & 15u;
+    const uint32_t t = (uint32_t)A.shard_index + lt * (uint32_t)A.shard_count;
+    const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
+    const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u), y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+    const bool inside = x < (uint32_t)A.width && y < (uint32_t)A.height;
+    const uint32_t slot = blk * 64u + p;
+    double e2 = 0.0;
+    if (inside && A.n >= 2) {
+        const double n = (double)A.n, n1 = (double)(A.n - 1);
+        double msum = 0.0, vsum = 0.0;
+        for (uint32_t ch = 0; ch < 3u; ch++) {
+            const double m = A.acc[ch * (size_t)A.nslots + slot] / n;
+            double d = A.m2[ch * (size_t)A.nslots + slot] / n - m * m;
+            if (d < 0.0) d = 0.0;  // (a NaN stays a NaN)
+            msum += m;
+            vsum += d / n1;
+        }
+        double den = msum / 3.0;
+        if (den < 0.01) den = 0.01;
+        e2 = (vsum / 3.0) / (den * den);
+        if (!(e2 - e2 == 0.0)) e2 = 0.0;  // NaN or infinite
+    }
+    const uint32_t k = (uint32_t)__popcll(__ballot(inside));
+    double sum = e2;
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    if (p == 0u) {
+        const double b = A.n >= 2 ? ptm::f_sqrt(sum / (double)k) : INFINITY;  // (k >= 1: only blocks with a pixel inside the frame are ever active)
+        A.blk_spp[blk] = (uint32_t)A.n;
+        A.noise[c] = b;
+        A.keep[c] = (A.decide && b <= A.target) ? 0u : 1u;
+    }
+}
+
+// compact_kernel: the next active list, in order.  One block of 1024 threads walks the list in strips of 1024 entries: a kept entry's
+// place is the kept entries of the strips before it + those of the waves before its wave (wave totals through LDS) + its rank
+// inside its wave (ballot + mbcnt).  No atomics.  Thread 0 writes the new length and the largest noise among the kept blocks to
+// `res`, which the host reads back once per pt_step to size the next launches.
+struct AdaptResult {
+    uint32_t nact;
+    uint32_t reserved;
+    double worst;
+};
+
+struct CompactArgs {
+    const uint32_t *active;  // [nact]
+    const uint32_t *keep;    // [nact]
+    const double *noise;     // [nact]
+    uint32_t *next;          // [nact] (another buffer than active)
+    AdaptResult *res;
+    uint32_t nact;
+};
+
+#define PT_COMPACT_BLOCK 1024
+__global__ __launch_bounds__(PT_COMPACT_BLOCK) void compact_kernel(const CompactArgs A) {
+    constexpr uint32_t NW = PT_COMPACT_BLOCK / PT_WAVE;
+    __shared__ uint32_t s_cnt[NW];
+    __shared__ double s_max[NW];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t base = 0;
+    double worst = 0.0;
+    for (uint32_t i0 = 0; i0 < A.nact; i0 += PT_COMPACT_BLOCK) {  // (uniform trip count: every thread reaches the barriers)
+        const uint32_t i = i0 + tid;
+        const bool kept = i < A.nact && A.keep[i] != 0u;
+        const uint64_t m = __ballot(kept);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (lane == 0u) s_cnt[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < NW; w++) {
+            const uint32_t n = s_cnt[w];
+            before += w < wave ? n : 0u;
+            total += n;
+        }
+        if (kept) {
+            A.next[base + before + rank] = A.active[i];  // base + before + rank <= i < nact
+            const double b = A.noise[i];
+            worst = b > worst ? b : worst;
+        }
+        base += total;
+        __syncthreads();
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(worst, off, 64);
+        worst = o > worst ? o : worst;
+    }
+    if (lane == 0u) s_max[wave] = worst;
+    __syncthreads();
+    if (tid == 0u) {
+        double mx = s_max[0];
+        for (uint32_t w = 1; w < NW; w++) mx = s_max[w] > mx ? s_max[w] : mx;
+        AdaptResult r;
+        r.nact = base;
+        r.reserved = 0u;
+        r.worst = mx;
+        *A.res = r;
+    }
+}
+
+// The per-pixel sample counts of an adaptive frame, tile-major with zeros outside the frame (the layout of tiles_seg), for
+// untile_kernel's u32a plane.
+__global__ __launch_bounds__(PT_BLOCK) void counts_tiles_kernel(const uint32_t *__restrict__ blk_spp, uint32_t *__restrict__ tiles_u32, uint32_t nslots,
+                                                                  int32_t width, int32_t height, int32_t ntx, int32_t shard_index, int32_t shard_count) {
+    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (slot >= nslots) return;
+    const uint32_t blk = slot >> 6, p = slot & 63u;
+    const uint32_t lt = blk >> 4, sb = blk & 15u;
+    const uint32_t t = (uint32_t)shard_index + lt * (uint32_t)shard_count;
+    const uint32_t ty = t / (uint32_t)ntx, tx = t - ty * (uint32_t)ntx;
+    const uint32_t lx = (sb & 3u) * 8u + (p & 7u), ly = (sb >> 2) * 8u + (p >> 3);
+    const bool inside = tx * 32u + lx < (uint32_t)width && ty * 32u + ly < (uint32_t)height;
+    tiles_u32[(size_t)lt * 1024u + ly * 32u + lx] = inside ? blk_spp[blk] : 0u;
 }
 
 // Self-test of div_shared against the compiler's IEEE division: `per_thread` operand pairs per thread, exponents drawn
@@ -3188,15 +3449,17 @@ struct FogArgs {
     int32_t width, height, ntx, shard_index, shard_count;
 };
 
-__global__ __launch_bounds__(PT_BLOCK) void fog_kernel(const FogArgs A) {
+template <bool ADAPT>
+__device__ __forceinline__ void fog_body(const FogArgs &A, const uint32_t *__restrict__ active) {
     const uint32_t job = blockIdx.x * PT_BLOCK + threadIdx.x;
     ptf::FogCount cnt = {0u, 0u, 0u};
     if (job < A.njobs && A.ray_ndraw[job] != 0xffffu) {
         // job -> (tile, sub-block, sample, pixel) as in raygen_kernel
         const uint32_t p = job & 63u;
         const uint32_t q = job >> 6;
-        const uint32_t blk = q / A.S;
-        const uint32_t sl = q - blk * A.S;
+        const uint32_t cblk = q / A.S;
+        const uint32_t sl = q - cblk * A.S;
+        const uint32_t blk = ADAPT ? active[__builtin_amdgcn_readfirstlane(cblk)] : cblk;  // (every lane of a wave holds the same row q)
         const uint32_t lt = blk >> 4, sb = blk & 15u;
         const uint32_t t = (uint32_t)A.shard_index + lt * (uint32_t)A.shard_count;
         const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
@@ -3222,6 +3485,10 @@ __global__ __launch_bounds__(PT_BLOCK) void fog_kernel(const FogArgs A) {
         atomicAdd(A.counters + 2, (unsigned long long)st);
     }
 }
+
+__global__ __launch_bounds__(PT_BLOCK) void fog_kernel(const FogArgs A) { fog_body<false>(A, nullptr); }
+
+__global__ __launch_bounds__(PT_BLOCK) void fog_adaptive_kernel(const FogArgs A, const uint32_t *__restrict__ active) { fog_body<true>(A, active); }
 
 // One GL-shading pass per job (pt_glshade.h): pixel (x, y) of the job as in raygen_kernel, pass s0 + sample, the 16 strata
 // traced in k order by this lane and their sum written into the job's radiance record, which resolve_kernel adds in pass

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -105,6 +106,13 @@ struct Device {
     DevBuf<double> m2;                // pt_set_moments: [3][nslots] running sums of squares (allocated only then)
     DevBuf<double> tiles_m2;          // ... and their tile-major copy for the gather
     DevBuf<ptk::NoisePartial> noise_part;  // pt_noise_estimate: one partial per block of noise_kernel
+    // pt_set_adaptive (allocated only then): the active list (two buffers, the check compacts from one into the other), the
+    // samples per block, the check's per-block decision and noise, and the word the host reads back after every check
+    DevBuf<uint32_t> act[2], blk_spp, blk_keep;
+    DevBuf<double> blk_noise;
+    DevBuf<ptk::AdaptResult> ad_res;
+    int act_cur = 0;                  // which of act[] holds the current list
+    uint32_t nact = 0;                // its length
     DevBuf<uint8_t> tiles_rgba;
     DevBuf<double> tiles_accum;
     DevBuf<uint32_t> tiles_seg, tiles_draw;
@@ -125,8 +133,8 @@ struct Device {
     size_t q_cap = 0;
     DevBuf<unsigned long long> counters;
     DevBuf<unsigned long long> prof;
-    std::vector<EventPair> ev_trace, ev_resolve, ev_raygen, ev_glass, ev_fog, ev_moments;
-    size_t n_trace = 0, n_resolve = 0, n_raygen = 0, n_glass = 0, n_fog = 0, n_moments = 0;
+    std::vector<EventPair> ev_trace, ev_resolve, ev_raygen, ev_glass, ev_fog, ev_moments, ev_check;
+    size_t n_trace = 0, n_resolve = 0, n_raygen = 0, n_glass = 0, n_fog = 0, n_moments = 0, n_check = 0;
     DevBuf<ptf::FogLight> fog_lights;        // the frame's light list (fog on)
     DevBuf<unsigned long long> fog_counters; // [3] shadow rays, draws, march steps of the frame
     DevBuf<ptg::GlObj> gl_objs;              // GL shading: the frame's objects, materials and light list
@@ -173,6 +181,9 @@ struct Frame {
     std::vector<ptf::FogLight> fog_lights;
     bool gl = false;  // GL shading (pt_set_shading): gl_trace_kernel replaces ray generation and the trace kernels
     bool moments = false;  // pt_set_moments: moments_kernel runs after every chunk's resolve add (pt_begin / pt_render frames only)
+    bool adaptive = false; // pt_set_adaptive: the frame's jobs are those of the active blocks, a check ends every pt_step (implies moments)
+    pt_adaptive ad{};
+    double worst_active = 0.0;  // largest block noise among the blocks the last check kept
     std::vector<ptg::GlObj> gl_objs;
     std::vector<ptg::GlMat> gl_mats;
     std::vector<int32_t> gl_lights;
@@ -223,6 +234,8 @@ struct pt_ctx {
     DevBuf<double> f_accum;
     DevBuf<double> g_tiles_m2, f_m2;  // pt_read_moments: the gathered tiles and the row-major frame of the second moments
     bool moments_on = false;          // pt_set_moments
+    bool adaptive_on = false;         // pt_set_adaptive
+    pt_adaptive adaptive{};
     DevBuf<uint32_t> f_seg, f_draw;
     size_t l_budget_bytes = (size_t)48 << 30;  // per-chunk job buffers (radiance, primary rays, path-state queues): a sixth of the 288 GB
     // A context that renders frame after frame of one shape (a UI, an animation: gpu.go:2534-2546 is called once per frame) grows its
@@ -557,6 +570,16 @@ int32_t validate(const pt_scene *scene, const pt_config *cfg) {
 
 // ---------------------------------------------------------------- per-device frame
 
+// Pixels of 8x8 block `blk` of a shard (16 per 32x32 tile, the shard's tiles in order: the map of ptk::block_pixel) that lie inside the frame.
+uint32_t block_pixels(const Frame &fr, const pt_shard &sh, uint32_t blk) {
+    const uint32_t lt = blk >> 4, sb = blk & 15u;
+    const uint32_t t = (uint32_t)sh.index + lt * (uint32_t)sh.count;
+    const uint32_t ty = t / (uint32_t)fr.ntx, tx = t - ty * (uint32_t)fr.ntx;
+    const int64_t x0 = (int64_t)tx * 32 + (sb & 3u) * 8, y0 = (int64_t)ty * 32 + (sb >> 2) * 8;
+    const int64_t w = std::min<int64_t>(8, (int64_t)fr.cfg.width - x0), h = std::min<int64_t>(8, (int64_t)fr.cfg.height - y0);
+    return w > 0 && h > 0 ? (uint32_t)(w * h) : 0u;
+}
+
 using TraceFn = void (*)(const TraceArgs);
 
 // The shipping instantiations are <false,false,*,*>; STATS adds per-pixel counters, PROF the section profile.
@@ -672,7 +695,7 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     d.nlocal = tiles_of_shard(fr.ntx * fr.nty, shard);
     d.nslots = (uint32_t)d.nlocal * 1024u;
     d.acc_started = false;
-    d.n_trace = d.n_resolve = d.n_raygen = d.n_glass = d.n_fog = d.n_moments = 0;
+    d.n_trace = d.n_resolve = d.n_raygen = d.n_glass = d.n_fog = d.n_moments = d.n_check = 0;
     d.first_recorded = false;
     std::memset(d.pass_log_prev, 0, sizeof d.pass_log_prev);  // the device counters are cleared below, once per frame
     if (d.scene_gen != sd.gen) {
@@ -738,6 +761,23 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     const size_t ns = std::max<uint32_t>(1, d.nslots);
     HIP_TRY(d.acc.reserve(3 * ns));
     if (fr.moments) HIP_TRY(d.m2.reserve(3 * ns));
+    if (fr.adaptive) {  // every block with a pixel inside the frame starts active, in block order
+        std::vector<uint32_t> act;
+        for (uint32_t blk = 0; blk < d.nslots / 64u; blk++)
+            if (block_pixels(fr, d.shard, blk) > 0) act.push_back(blk);
+        const size_t nb = std::max<size_t>(1, d.nslots / 64u);
+        HIP_TRY(d.act[0].reserve(nb));
+        HIP_TRY(d.act[1].reserve(nb));
+        HIP_TRY(d.blk_spp.reserve(nb));
+        HIP_TRY(d.blk_keep.reserve(nb));
+        HIP_TRY(d.blk_noise.reserve(nb));
+        HIP_TRY(d.ad_res.reserve(1));
+        HIP_TRY(hipMemsetAsync(d.blk_spp.p, 0, nb * sizeof(uint32_t), d.stream));
+        if (!act.empty())  // (pageable source: the copy is complete when the call returns)
+            HIP_TRY(hipMemcpyAsync(d.act[0].p, act.data(), act.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+        d.act_cur = 0;
+        d.nact = (uint32_t)act.size();
+    }
     if (fr.stats_on) {
         HIP_TRY(d.acc_seg.reserve(ns));
         HIP_TRY(d.acc_draw.reserve(ns));
@@ -1063,6 +1103,7 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
 int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     Frame &fr = ctx->frame;
     if (d.nlocal == 0 || S == 0) return PT_OK;
+    if (fr.adaptive && d.nact == 0) return PT_OK;  // every block of this device has stopped
     HIP_TRY(hipSetDevice(d.ordinal));
     DevFrame F = fr.F;
     F.shard_index = d.shard.index;
@@ -1070,7 +1111,8 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     F.nlocal = d.nlocal;
     F.s0 = s0;
     F.S = S;
-    F.njobs = d.nslots * S;
+    F.njobs = (fr.adaptive ? d.nact * 64u : d.nslots) * S;  // adaptive: the active blocks' jobs only, compact
+    const ptk::AdaptTable AT{d.act[d.act_cur].p, d.blk_spp.p, d.nact};
     // jobs a wave claims per pop of the item cursor: 256, and 512 for the bitmask scans once a pass holds 128 samples per pixel
     // or more (same-box sweeps, profiles/r02_claim_sweep.txt: C4 at 265 spp per pass 664 / 653 / 654 / 659 / 673 ms for 256 / 512 /
     // 1024 / 2048 / 4096, at 79 spp per pass 677 / 675 / 678 ms; the BVH path loses 3 % at 512 and 7 % at 1024)
@@ -1183,7 +1225,10 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         HIP_TRY(hipEventRecord(eg.a, d.stream));
         const char *rg_form = std::getenv("PTCORE_RAYGEN");  // A/B: "column" = round 2's walk down a lane's column, "simple" = one job per lane
         const bool rg_simple = std::getenv("PTCORE_RAYGEN_SIMPLE") || (rg_form && !std::strcmp(rg_form, "simple"));
-        if (fr.cam.lens_radius > 0 && !rg_simple && !(rg_form && !std::strcmp(rg_form, "column")))  // thin lens: the rejection loop over a wave's pool of jobs
+        if (fr.adaptive)
+            hipLaunchKernelGGL(ptk::raygen_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, F, fr.cam,
+                               d.ray.p, d.ray_rng.p, d.ray_ndraw.p, AT.active);
+        else if (fr.cam.lens_radius > 0 && !rg_simple && !(rg_form && !std::strcmp(rg_form, "column")))  // thin lens: the rejection loop over a wave's pool of jobs
             hipLaunchKernelGGL(ptk::raygen_lens_pool_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_POOL_ROWS - 1) / (PT_BLOCK * PT_RG_POOL_ROWS)), dim3(PT_BLOCK), 0,
                                d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
         else if (fr.cam.lens_radius > 0 && !rg_simple)
@@ -1341,7 +1386,8 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         FA.shard_count = d.shard.count;
         EventPair &ef = d.ev_fog[d.n_fog++];
         HIP_TRY(hipEventRecord(ef.a, d.stream));
-        hipLaunchKernelGGL(ptk::fog_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA);
+        if (fr.adaptive) hipLaunchKernelGGL(ptk::fog_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA, AT.active);
+        else hipLaunchKernelGGL(ptk::fog_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ef.b, d.stream));
     }
@@ -1367,7 +1413,9 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     R.shard_count = d.shard.count;
     EventPair &e = d.ev_resolve[d.n_resolve++];
     HIP_TRY(hipEventRecord(e.a, d.stream));
-    hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
+    const uint32_t add_grid = ((fr.adaptive ? d.nact * 64u : d.nslots) + PT_BLOCK - 1) / PT_BLOCK;
+    if (fr.adaptive) hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R, AT);
+    else hipLaunchKernelGGL(ptk::resolve_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e.b, d.stream));
     if (fr.moments) {  // the squares of the same records, in the same order (pt_set_moments)
@@ -1387,11 +1435,56 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         M.shard_count = d.shard.count;
         EventPair &em = d.ev_moments[d.n_moments++];
         HIP_TRY(hipEventRecord(em.a, d.stream));
-        hipLaunchKernelGGL(ptk::moments_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, M);
+        if (fr.adaptive) hipLaunchKernelGGL(ptk::moments_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M, AT);
+        else hipLaunchKernelGGL(ptk::moments_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(em.b, d.stream));
     }
     d.acc_started = true;
+    return PT_OK;
+}
+
+// The check that ends a pt_step of an adaptive frame, on one device: block_noise_kernel (counts, noise, decision per active block),
+// then compact_kernel into the other list buffer.  The result word is read by the caller once the stream has drained.
+int32_t dev_adaptive_check(pt_ctx *ctx, Device &d, ptk::AdaptResult *host_res) {
+    const Frame &fr = ctx->frame;
+    if (d.nlocal == 0 || d.nact == 0) return PT_OK;
+    HIP_TRY(hipSetDevice(d.ordinal));
+    ptk::BlockNoiseArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.acc = d.acc.p;
+    A.m2 = d.m2.p;
+    A.active = d.act[d.act_cur].p;
+    A.blk_spp = d.blk_spp.p;
+    A.keep = d.blk_keep.p;
+    A.noise = d.blk_noise.p;
+    A.target = fr.ad.target;
+    A.nslots = d.nslots;
+    A.nact = d.nact;
+    A.n = fr.done_spp;
+    A.decide = fr.done_spp >= std::max(fr.ad.min_spp, 2) ? 1 : 0;
+    A.width = fr.cfg.width;
+    A.height = fr.cfg.height;
+    A.ntx = fr.ntx;
+    A.shard_index = d.shard.index;
+    A.shard_count = d.shard.count;
+    if (int32_t rc = dev_events(d, d.ev_check, d.n_check + 1)) return rc;
+    EventPair &ec = d.ev_check[d.n_check++];
+    HIP_TRY(hipEventRecord(ec.a, d.stream));
+    hipLaunchKernelGGL(ptk::block_noise_kernel, dim3((d.nact * 64u + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, A);
+    HIP_TRY(hipGetLastError());
+    ptk::CompactArgs K;
+    std::memset(&K, 0, sizeof K);
+    K.active = d.act[d.act_cur].p;
+    K.keep = d.blk_keep.p;
+    K.noise = d.blk_noise.p;
+    K.next = d.act[d.act_cur ^ 1].p;
+    K.res = d.ad_res.p;
+    K.nact = d.nact;
+    hipLaunchKernelGGL(ptk::compact_kernel, dim3(1), dim3(PT_COMPACT_BLOCK), 0, d.stream, K);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ec.b, d.stream));
+    HIP_TRY(hipMemcpyAsync(host_res, d.ad_res.p, sizeof *host_res, hipMemcpyDeviceToHost, d.stream));
     return PT_OK;
 }
 
@@ -1446,7 +1539,11 @@ int32_t dev_finish(pt_ctx *ctx, Device &d, int32_t spp_done, uint8_t *tiles_rgba
     if (int32_t rc = dev_events(d, d.ev_resolve, d.n_resolve + 1)) return rc;
     EventPair &e = d.ev_resolve[d.n_resolve++];
     HIP_TRY(hipEventRecord(e.a, d.stream));
-    hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
+    if (fr.adaptive)  // every pixel by the count of its own block
+        hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R,
+                           ptk::AdaptTable{d.act[d.act_cur].p, d.blk_spp.p, d.nact});
+    else
+        hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e.b, d.stream));
     HIP_TRY(hipEventRecord(d.ev_last, d.stream));
@@ -2100,6 +2197,7 @@ void pt_destroy(pt_ctx *ctx) {
         for (EventPair &e : d.ev_glass) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         d.acc.release(); d.acc_seg.release(); d.acc_draw.release(); d.tiles_rgba.release();
         d.m2.release(); d.tiles_m2.release(); d.noise_part.release();
+        d.act[0].release(); d.act[1].release(); d.blk_spp.release(); d.blk_keep.release(); d.blk_noise.release(); d.ad_res.release();
         d.tiles_accum.release(); d.tiles_seg.release(); d.tiles_draw.release(); d.queue.release();
         d.counters.release();
         for (EventPair &e : d.ev_trace) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -2107,6 +2205,7 @@ void pt_destroy(pt_ctx *ctx) {
         for (EventPair &e : d.ev_raygen) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (EventPair &e : d.ev_fog) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (EventPair &e : d.ev_moments) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+        for (EventPair &e : d.ev_check) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         d.fog_lights.release(); d.fog_counters.release();
         d.gl_objs.release(); d.gl_mats.release(); d.gl_lights.release(); d.gl_counters.release();
         if (d.ev_first) (void)hipEventDestroy(d.ev_first);
@@ -2327,11 +2426,19 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
     if (int32_t rc = validate(scene, cfg)) return rc;
     if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_begin: a frame is already open");
+    if (ctx->adaptive_on) {  // refused before anything is launched; the context stays as it was
+        if (ctx->shading_model != PT_SHADING_CPU) return fail(PT_ERR_STATE, "adaptive sampling: not available with GL shading (pt_set_shading)");
+        if (!ctx->inject_rays.empty()) return fail(PT_ERR_STATE, "adaptive sampling: not available with injected primary rays (pt_debug_set_primary_rays)");
+        if (ctx->pipeline == 1 || ctx->pipeline == 2)
+            return fail(PT_ERR_STATE, "adaptive sampling: not available with PTCORE_PIPELINE=wavefront or walk32 (the default pipeline only)");
+    }
     const int32_t ndev = (int32_t)ctx->devs.size();
     const int32_t ntiles = ((cfg->width + 31) / 32) * ((cfg->height + 31) / 32);
     const uint32_t max_slots = (uint32_t)tiles_of_shard(ntiles, pt_shard{0, ndev}) * 1024u;
     if (int32_t rc = frame_open(ctx, scene, cfg, max_slots)) return rc;
-    ctx->frame.moments = ctx->moments_on;
+    ctx->frame.adaptive = ctx->adaptive_on;
+    ctx->frame.ad = ctx->adaptive;
+    ctx->frame.moments = ctx->moments_on || ctx->adaptive_on;
     for (int32_t i = 0; i < ndev; i++) {
         if (int32_t rc = dev_begin(ctx, ctx->devs[(size_t)i], pt_shard{i, ndev}, nullptr)) {
             ctx->frame.open = false;
@@ -2346,6 +2453,12 @@ int32_t pt_step(pt_ctx *ctx, int32_t nspp, int32_t *done_spp) {
     Frame &fr = ctx->frame;
     int32_t left = fr.cfg.samples_per_px - fr.done_spp;
     int32_t todo = std::max(0, std::min(nspp, left));
+    if (fr.adaptive) {  // nothing is added once every block has stopped
+        uint64_t nact = 0;
+        for (const Device &d : ctx->devs) nact += d.nlocal ? d.nact : 0u;
+        if (nact == 0) todo = 0;
+    }
+    const bool check = fr.adaptive && todo > 0;
     while (todo > 0) {
         const uint32_t S = std::min<uint32_t>((uint32_t)todo, fr.chunk);
         for (Device &d : ctx->devs)
@@ -2353,9 +2466,24 @@ int32_t pt_step(pt_ctx *ctx, int32_t nspp, int32_t *done_spp) {
         fr.done_spp += (int32_t)S;
         todo -= (int32_t)S;
     }
+    std::vector<ptk::AdaptResult> res(check ? ctx->devs.size() : 0);
+    if (check)  // the blocks at or below the target leave the active lists
+        for (size_t i = 0; i < ctx->devs.size(); i++)
+            if (int32_t rc = dev_adaptive_check(ctx, ctx->devs[i], &res[i])) return rc;
     for (Device &d : ctx->devs) {
         HIP_TRY(hipSetDevice(d.ordinal));
         HIP_TRY(hipStreamSynchronize(d.stream));
+    }
+    if (check) {
+        fr.worst_active = 0.0;
+        for (size_t i = 0; i < ctx->devs.size(); i++) {
+            Device &d = ctx->devs[i];
+            if (d.nlocal == 0 || d.nact == 0) continue;
+            if (res[i].nact > d.nact) return fail(PT_ERR_STATE, "internal: the adaptive check returned a longer active list");
+            d.nact = res[i].nact;
+            d.act_cur ^= 1;
+            if (d.nact) fr.worst_active = std::max(fr.worst_active, res[i].worst);
+        }
     }
     if (done_spp) *done_spp = fr.done_spp;
     return PT_OK;
@@ -2520,6 +2648,21 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
         std::fprintf(stderr, "ptcore: moments_kernel %.3f ms in %zu launches (resolve_kernel %.3f ms in %d)\n", mm, launches, st.resolve_ms,
                      st.resolve_launches);
     }
+    if (ctx->frame.adaptive && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) {
+        double cm = 0;
+        size_t launches = 0;
+        for (Device &d : ctx->devs) {
+            double ms = 0;
+            for (size_t k = 0; k < d.n_check && hipSetDevice(d.ordinal) == hipSuccess; k++) {
+                float m = 0;
+                if (hipEventElapsedTime(&m, d.ev_check[k].a, d.ev_check[k].b) == hipSuccess) ms += m;
+            }
+            cm = std::max(cm, ms);
+            launches += d.n_check;
+        }
+        std::fprintf(stderr, "ptcore: adaptive check %.3f ms in %zu launches of block_noise_kernel + compact_kernel (resolve_kernel %.3f ms in %d)\n", cm,
+                     launches, st.resolve_ms, st.resolve_launches);
+    }
     if (ctx->frame.fog_vol) {
         ctx->fog_pending = 1;
         if (int32_t r = collect_fog(ctx)) rc = rc != PT_OK ? rc : r;
@@ -2541,7 +2684,16 @@ int32_t pt_render(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uint
     const auto t0 = clk::now();
     if (int32_t rc = pt_begin(ctx, scene, cfg)) return rc;
     const auto t1 = clk::now();
-    int32_t rc = pt_step(ctx, cfg->samples_per_px, nullptr);
+    int32_t rc = PT_OK;
+    if (ctx->frame.adaptive) {  // `step` samples at a time, until the cap or until no block is active
+        const int32_t step = std::max(1, ctx->frame.ad.step);
+        for (int32_t done = 0, before = -1; rc == PT_OK && done < cfg->samples_per_px && done != before;) {
+            before = done;
+            rc = pt_step(ctx, step, &done);
+        }
+    } else {
+        rc = pt_step(ctx, cfg->samples_per_px, nullptr);
+    }
     const auto t2 = clk::now();
     if (rc == PT_OK) rc = read_frame(ctx, rgba, stride, accum, nseg, ndraw);
     const auto t3 = clk::now();
@@ -2563,6 +2715,17 @@ int32_t pt_set_moments(pt_ctx *ctx, int32_t on) {
     return PT_OK;
 }
 
+int32_t pt_set_adaptive(pt_ctx *ctx, const pt_adaptive *a) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_adaptive while a frame is open");
+    if (a && !(a->target >= 0.0)) return fail(PT_ERR_INVALID, "pt_set_adaptive: target must be >= 0");
+    if (a && a->min_spp < 0) return fail(PT_ERR_INVALID, "pt_set_adaptive: min_spp must be >= 0");
+    ctx->adaptive_on = a != nullptr;
+    if (a) ctx->adaptive = *a;
+    else std::memset(&ctx->adaptive, 0, sizeof ctx->adaptive);
+    return PT_OK;
+}
+
 // The frame whose sums pt_read_moments / pt_noise_estimate read: the open one, or the last one finished on ctx (its sums stay
 // on the devices until the next frame opens), with at least one step done and moments collected.
 static int32_t moments_frame(pt_ctx *ctx, const char *who) {
@@ -2570,6 +2733,89 @@ static int32_t moments_frame(pt_ctx *ctx, const char *who) {
     if (fr.done_spp <= 0 || fr.chunk == 0)
         return fail(PT_ERR_STATE, std::string(who) + ": no frame with samples on this context (pt_step or pt_render first)");
     if (!fr.moments) return fail(PT_ERR_STATE, std::string(who) + ": the frame was rendered with moments off (pt_set_moments)");
+    return PT_OK;
+}
+
+static int32_t adaptive_frame(pt_ctx *ctx, const char *who) {
+    if (int32_t rc = moments_frame(ctx, who)) return rc;
+    if (!ctx->frame.adaptive) return fail(PT_ERR_STATE, std::string(who) + ": the frame was rendered with adaptive sampling off (pt_set_adaptive)");
+    return PT_OK;
+}
+
+int32_t pt_adaptive_state(pt_ctx *ctx, struct pt_adaptive_state *out) {
+    if (!ctx || !out) return fail(PT_ERR_INVALID, "null argument");
+    if (int32_t rc = adaptive_frame(ctx, "pt_adaptive_state")) return rc;
+    const Frame &fr = ctx->frame;
+    struct pt_adaptive_state r;
+    std::memset(&r, 0, sizeof r);
+    r.spp_min = INT32_MAX;
+    std::vector<uint32_t> spp;
+    for (Device &d : ctx->devs) {
+        if (d.nlocal == 0) continue;
+        HIP_TRY(hipSetDevice(d.ordinal));
+        spp.resize(d.nslots / 64u);
+        HIP_TRY(hipMemcpyAsync(spp.data(), d.blk_spp.p, spp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        for (uint32_t blk = 0; blk < (uint32_t)spp.size(); blk++) {
+            const uint32_t k = block_pixels(fr, d.shard, blk);
+            if (k == 0) continue;
+            r.blocks++;
+            r.samples += (uint64_t)k * spp[blk];
+            r.spp_min = std::min(r.spp_min, (int32_t)spp[blk]);
+            r.spp_max = std::max(r.spp_max, (int32_t)spp[blk]);
+        }
+        r.active_blocks += d.nact;
+    }
+    if (r.blocks == 0) r.spp_min = 0;
+    r.worst_active = r.active_blocks ? fr.worst_active : 0.0;
+    *out = r;
+    return PT_OK;
+}
+
+// the counts plane: per device tile-major (counts_tiles_kernel), gathered on device 0 by peer copies, through untile_kernel's u32a plane
+int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp) {
+    if (!ctx || !spp) return fail(PT_ERR_INVALID, "null argument");
+    if (int32_t rc = adaptive_frame(ctx, "pt_read_sample_counts")) return rc;
+    Frame &fr = ctx->frame;
+    const int32_t W = fr.cfg.width, H = fr.cfg.height;
+    const int32_t ndev = (int32_t)ctx->devs.size();
+    const size_t ntiles = (size_t)fr.ntx * (size_t)fr.nty;
+    Device &d0 = ctx->devs[0];
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    HIP_TRY(ctx->g_tiles_seg.reserve(ntiles * 1024));
+    size_t before = 0;
+    for (int32_t i = 0; i < ndev; i++) {
+        Device &d = ctx->devs[(size_t)i];
+        if (d.nlocal == 0) continue;
+        const size_t nt = (size_t)d.nlocal;
+        HIP_TRY(hipSetDevice(d.ordinal));
+        uint32_t *dst = ctx->g_tiles_seg.p + before * 1024;
+        if (i != 0) {
+            HIP_TRY(d.tiles_seg.reserve(nt * 1024));
+            dst = d.tiles_seg.p;
+        }
+        hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p, dst, d.nslots, W, H,
+                           fr.ntx, d.shard.index, d.shard.count);
+        HIP_TRY(hipGetLastError());
+        if (i != 0)
+            HIP_TRY(hipMemcpyPeerAsync(ctx->g_tiles_seg.p + before * 1024, d0.ordinal, d.tiles_seg.p, d.ordinal, nt * 1024 * sizeof(uint32_t), d.stream));
+        before += nt;
+    }
+    for (int32_t i = 1; i < ndev; i++) {
+        HIP_TRY(hipSetDevice(ctx->devs[(size_t)i].ordinal));
+        HIP_TRY(hipStreamSynchronize(ctx->devs[(size_t)i].stream));
+    }
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    HIP_TRY(ctx->f_seg.reserve((size_t)W * H));
+    ptk::UntileArgs U;
+    std::memset(&U, 0, sizeof U);
+    U.tiles_u32a = ctx->g_tiles_seg.p;
+    U.u32a = ctx->f_seg.p;
+    U.width = W; U.height = H; U.ntx = fr.ntx; U.nty = fr.nty; U.stride = W * 4; U.shard_count = ndev;
+    hipLaunchKernelGGL(ptk::untile_kernel, dim3((unsigned)fr.ntx, (unsigned)fr.nty, 4), dim3(PT_BLOCK), 0, d0.stream, U);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(spp, ctx->f_seg.p, (size_t)W * H * sizeof(uint32_t), hipMemcpyDeviceToHost, d0.stream));
+    HIP_TRY(hipStreamSynchronize(d0.stream));
     return PT_OK;
 }
 
@@ -2665,7 +2911,8 @@ int32_t pt_noise_estimate(pt_ctx *ctx, pt_noise *out) {
         A.ntx = fr.ntx;
         A.shard_index = d.shard.index;
         A.shard_count = d.shard.count;
-        hipLaunchKernelGGL(ptk::noise_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A);
+        if (fr.adaptive) hipLaunchKernelGGL(ptk::noise_adaptive_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A, d.blk_spp.p);  // every pixel with its own n
+        else hipLaunchKernelGGL(ptk::noise_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A);
         HIP_TRY(hipGetLastError());
         part.resize(grid);
         HIP_TRY(hipMemcpyAsync(part.data(), d.noise_part.p, grid * sizeof(ptk::NoisePartial), hipMemcpyDeviceToHost, d.stream));

@@ -207,6 +207,75 @@ def noise_estimate_host(accum: np.ndarray, m2: np.ndarray, n: int) -> dict:
             "bad_pixels": int(pixels - np.count_nonzero(good)), "spp": int(n)}
 
 
+def set_adaptive(ctx: capi.Context, target: Optional[float] = None, min_spp: int = 0, step: int = 16) -> None:
+    """pt_set_adaptive: later frames on ctx stop every 8x8 block whose own noise is at or below `target` (checked at the end of
+    every pt_step once max(min_spp, 2) samples are done); `step` is what pt_render adds per step.  target=None turns it off."""
+    if not capi.has("pt_set_adaptive"):
+        if target is not None:
+            raise RuntimeError("this libptcore.so has no pt_set_adaptive (rebuild it)")
+        return
+    if target is None:
+        capi.check(capi.load().pt_set_adaptive(ctx.handle, None))
+        return
+    a = capi.PtAdaptive(float(target), int(min_spp), int(step))
+    capi.check(capi.load().pt_set_adaptive(ctx.handle, C.byref(a)))
+
+
+def adaptive_state(ctx: Optional[capi.Context] = None) -> dict:
+    """pt_adaptive_state of ctx's open or last frame: blocks, active_blocks, samples, spp_min, spp_max, worst_active."""
+    st = capi.PtAdaptiveState()
+    capi.check(capi.load().pt_adaptive_state((ctx or context()).handle, C.byref(st)))
+    return st.as_dict()
+
+
+def read_sample_counts(ctx: capi.Context, spp: np.ndarray) -> None:
+    """pt_read_sample_counts into spp (contiguous uint32 [H, W]): the samples each pixel of the adaptive frame holds."""
+    if spp.dtype != np.uint32 or spp.ndim != 2 or not spp.flags.c_contiguous:
+        raise ValueError("sample counts must be contiguous uint32 [H, W]")
+    capi.check(capi.load().pt_read_sample_counts(ctx.handle, spp.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+
+def adaptive_plan_host(samples: np.ndarray, target: float, step: int, min_spp: int, cap: int) -> np.ndarray:
+    """The count map an adaptive frame ends with, in NumPy, from per-sample radiances: samples = float64 [H, W, >= cap, 3].
+    Samples are added `step` at a time up to `cap`; after every step with done >= max(min_spp, 2) each still-active 8x8 block
+    (aligned to the frame's origin, cut at its right and bottom edges) whose noise b = sqrt(sum of e2 / k) over its k pixels is at
+    or below `target` stops (e2 = the per-pixel quantity of noise_estimate_host with n = done; a NaN or infinite e2 adds 0).
+    Returns int32 [ceil(H / 8), ceil(W / 8)]: the samples each block holds at the end."""
+    l = np.asarray(samples, np.float64)
+    H, W = l.shape[0], l.shape[1]
+    if l.ndim != 4 or l.shape[3] != 3 or l.shape[2] < cap:
+        raise ValueError("samples must be [H, W, >= cap, 3]")
+    step = max(1, int(step))
+    nby, nbx = (H + 7) // 8, (W + 7) // 8
+    counts = np.zeros((nby, nbx), np.int32)
+    active = np.ones((nby, nbx), bool)
+    S = np.zeros((H, W, 3))
+    Q = np.zeros((H, W, 3))
+    done = 0
+    while done < cap and active.any():
+        n = min(step, cap - done)
+        for s in range(done, done + n):  # in sample order, like the device sums
+            S = S + l[:, :, s]
+            Q = Q + l[:, :, s] * l[:, :, s]
+        done += n
+        counts[active] = done
+        if done < max(int(min_spp), 2):
+            continue
+        with np.errstate(all="ignore"):
+            m = S / float(done)
+            v = np.maximum(Q / float(done) - m * m, 0.0) / float(done - 1)
+            den = np.maximum((m[..., 0] + m[..., 1] + m[..., 2]) / 3.0, 0.01)
+            e2 = ((v[..., 0] + v[..., 1] + v[..., 2]) / 3.0) / (den * den)
+        e2 = np.where(np.isfinite(e2), e2, 0.0)
+        for by in range(nby):
+            for bx in range(nbx):
+                if active[by, bx]:
+                    blk = e2[by * 8:by * 8 + 8, bx * 8:bx * 8 + 8]
+                    if np.sqrt(blk.sum() / blk.size) <= target:
+                        active[by, bx] = False
+    return counts
+
+
 def pt_config(cfg: RenderConfig) -> capi.PtConfig:
     return capi.PtConfig(cfg.width, cfg.height, cfg.samples_per_px, cfg.max_depth, cfg.seed & 0xFFFFFFFFFFFFFFFF,
                          cfg.spp_chunk, cfg.flags)
@@ -240,7 +309,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            accum: Optional[np.ndarray] = None, nseg: Optional[np.ndarray] = None,
            ndraw: Optional[np.ndarray] = None, ctx: Optional[capi.Context] = None, fog: bool = False,
            shading: str = "cpu", moments: Optional[np.ndarray] = None, noise: Optional[float] = None,
-           noise_step: int = 16) -> dict:
+           noise_step: int = 16, adaptive: bool = False, min_spp: int = 0, counts: Optional[np.ndarray] = None) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -255,6 +324,11 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     step, and the frame stops at the first check with at least 2 samples done and noise <= T, or at the cap
     cfg.samples_per_px; progress() is called after each step.  The image is that of a frame of the samples done.  With either
     argument the returned dict gains spp_done and noise; without them moments are off for the call.
+
+    adaptive=True (with noise=T) makes T the target of every 8x8 block instead of the frame's (pt_set_adaptive):
+    samples are added noise_step at a time, after each step (once max(min_spp, 2) samples are done) the blocks at or below T stop,
+    and the frame ends when no block is active or at the cap.  Every pixel is normalised by its own count; counts (uint32
+    [H, W]) receives them, and the returned dict gains "adaptive": the pt_adaptive_state of the frame (spp_done is its spp_max).
 
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
@@ -273,6 +347,12 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     set_fog(ctx, getattr(sc, "fog", None) if fog else None)
     if shading != "cpu" or capi.has("pt_set_shading"):
         set_shading(ctx, shading, sc)
+    if adaptive and noise is None:
+        raise ValueError("adaptive needs the block noise target (noise=)")
+    if counts is not None and (not adaptive or counts.dtype != np.uint32 or counts.shape != (cfg.height, cfg.width)
+                               or not counts.flags.c_contiguous):
+        raise ValueError("counts needs adaptive=True and a contiguous uint32 [H, W] array")
+    set_adaptive(ctx, noise if adaptive else None, min_spp, noise_step)
     want_moments = moments is not None or noise is not None
     set_moments(ctx, want_moments)
     if moments is not None and (moments.dtype != np.float64 or moments.shape != (cfg.height, cfg.width, 3)
@@ -293,11 +373,16 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
             if moments is not None:
                 read_moments(ctx, moments)
             d.update(noise=noise_estimate(ctx)["noise"])
+            if adaptive:
+                d["adaptive"] = adaptive_state(ctx)
+                d["spp_done"] = d["adaptive"]["spp_max"]
+                if counts is not None:
+                    read_sample_counts(ctx, counts)
         elif want_moments:
             d.update(noise=float("inf"))
         return d
 
-    if progress is None and noise is None:
+    if progress is None and (noise is None or adaptive):  # (an adaptive frame steps inside pt_render)
         capi.check(L.pt_render(ctx.handle, C.byref(flat.c), C.byref(pc), _ptr(img), stride, _ptr(accum), _ptr(nseg),
                                _ptr(ndraw), C.byref(st)))
         d = st.as_dict()
@@ -309,7 +394,17 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     capi.check(L.pt_begin(ctx.handle, C.byref(flat.c), C.byref(pc)))
     done = C.c_int32(0)
     try:
-        if noise is not None:  # render until the noise target, cfg.samples_per_px as the cap
+        if adaptive:  # the blocks stop inside pt_step; the frame ends when a step adds nothing
+            before = -1
+            while done.value < cfg.samples_per_px and done.value != before:
+                before = done.value
+                capi.check(L.pt_step(ctx.handle, max(1, int(noise_step)), C.byref(done)))
+                if done.value != before:
+                    capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
+                    progress()
+            if cfg.samples_per_px <= 0:
+                capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
+        elif noise is not None:  # render until the noise target, cfg.samples_per_px as the cap
             nz = capi.PtNoise()
             while done.value < cfg.samples_per_px:
                 capi.check(L.pt_step(ctx.handle, max(1, min(int(noise_step), cfg.samples_per_px - done.value)), C.byref(done)))
@@ -430,6 +525,30 @@ class NoiseConfig:
     @property
     def enabled(self) -> bool:
         return self.target > 0
+
+
+@dataclass
+class AdaptiveConfig:
+    """Whether the noise target of NoiseConfig is that of every 8x8 block (adaptive sampling) instead of the
+    frame's, and the samples every block gets before the first check."""
+    enabled: bool = False
+    min_spp: int = 0
+
+    @classmethod
+    def from_env(cls, environ=None) -> "AdaptiveConfig":
+        """PATHTRACER_GPU_ADAPTIVE=1 (or true / on / yes) and PATHTRACER_GPU_ADAPTIVE_MIN_SPP=<int >= 0>; it takes effect
+        together with PATHTRACER_GPU_NOISE, whose value is then the block target."""
+        import os
+
+        env = os.environ if environ is None else environ
+        cfg = cls(enabled=env.get("PATHTRACER_GPU_ADAPTIVE", "").lower() in ("1", "true", "on", "yes"))
+        try:
+            i = int(env["PATHTRACER_GPU_ADAPTIVE_MIN_SPP"])
+            if i >= 0:
+                cfg.min_spp = i
+        except (KeyError, ValueError):
+            pass
+        return cfg
 
 
 @dataclass

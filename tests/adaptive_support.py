@@ -1,0 +1,124 @@
+"""Helpers of the adaptive-sampling tests (test_adaptive_cpu.py, test_adaptive_gpu.py): the case the issue fixes, a plain-Python
+restatement of the block rule on per-sample radiances (independent of hip.adaptive_plan_host), and the self-consistency check
+that needs no oracle: every block of an adaptive frame is bit-equal to the same block of a plain frame of the block's count."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from moments_support import H, W
+
+# scene, depth, seed, cap, step, min_spp, target: example_simple at 40 x 24 = 3 x 5 blocks of 8 x 8
+CASE = ("example_simple", 4, 1, 64, 8, 0, 0.25)
+CASE_MAP = [[48, 32, 16, 24, 40], [64, 64, 48, 64, 64], [40, 64, 32, 32, 40]]
+CASE_SAMPLES = 43008  # of 61440
+
+
+def plan_restated(l: np.ndarray, target: float, step: int, min_spp: int, cap: int):
+    """The block rule of include/ptcore.h, block by block and pixel by pixel in plain Python floats.  l = [H, W, >= cap, 3].
+    Returns (counts [nby][nbx], checks): checks = every (by, bx, done, b) the rule looked at, in order."""
+    h, w = l.shape[0], l.shape[1]
+    nby, nbx = (h + 7) // 8, (w + 7) // 8
+    counts = [[0] * nbx for _ in range(nby)]
+    checks = []
+    for by in range(nby):
+        for bx in range(nbx):
+            pix = [(y, x) for y in range(by * 8, min(by * 8 + 8, h)) for x in range(bx * 8, min(bx * 8 + 8, w))]
+            S = {p: [0.0, 0.0, 0.0] for p in pix}
+            Q = {p: [0.0, 0.0, 0.0] for p in pix}
+            done = 0
+            while done < cap:
+                n = min(step, cap - done)
+                for s in range(done, done + n):
+                    for (y, x) in pix:
+                        for c in range(3):
+                            v = float(l[y, x, s, c])
+                            S[(y, x)][c] += v
+                            Q[(y, x)][c] += v * v
+                done += n
+                counts[by][bx] = done
+                if done < max(min_spp, 2):
+                    continue
+                total = 0.0
+                for p in pix:
+                    m = [S[p][c] / done for c in range(3)]
+                    d = [Q[p][c] / done - m[c] * m[c] for c in range(3)]
+                    v = [(0.0 if dc < 0.0 else dc) / (done - 1) for dc in d]
+                    den = (m[0] + m[1] + m[2]) / 3.0
+                    den = 0.01 if den < 0.01 else den
+                    e2 = ((v[0] + v[1] + v[2]) / 3.0) / (den * den)
+                    if not (math.isnan(e2) or math.isinf(e2)):
+                        total += e2
+                b = math.sqrt(total / len(pix))
+                checks.append((by, bx, done, b))
+                if b <= target:
+                    break
+    return counts, checks
+
+
+def expand(block_counts, w: int = W, h: int = H) -> np.ndarray:
+    """Block counts [nby][nbx] as the per-pixel plane pt_read_sample_counts returns, uint32 [h, w]."""
+    a = np.asarray(block_counts, np.uint32)
+    return np.repeat(np.repeat(a, 8, axis=0), 8, axis=1)[:h, :w].copy()
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def render_adaptive(ctx, sc, w, h, cap, depth, seed, target, step, min_spp=0, chunk=0, flags=0, progress=None, **kw):
+    """One adaptive frame through hip.render: (img, acc, m2, counts, nseg, ndraw, st)."""
+    from path_trace_golang_amd import hip
+
+    img = np.zeros((h, w, 4), np.uint8)
+    acc = np.zeros((h, w, 3))
+    m2 = np.zeros((h, w, 3))
+    counts = np.full((h, w), 0xFFFFFFFF, np.uint32)
+    nseg = np.zeros((h, w), np.uint32) if flags else None
+    ndraw = np.zeros((h, w), np.uint32) if flags else None
+    st = hip.render(sc, hip.RenderConfig(w, h, cap, depth, seed, chunk, flags), img, progress, acc, nseg, ndraw, ctx=ctx, moments=m2,
+                    noise=target, noise_step=step, adaptive=True, min_spp=min_spp, counts=counts, **kw)
+    return img, acc, m2, counts, nseg, ndraw, st
+
+
+def check_state(st: dict, counts: np.ndarray, cap: int):
+    """pt_adaptive_state and pt_stats of a frame against its counts plane."""
+    h, w = counts.shape
+    blocks = ((h + 7) // 8) * ((w + 7) // 8)
+    a = st["adaptive"]
+    total = int(counts.astype(np.uint64).sum())
+    assert a["blocks"] == blocks
+    assert a["samples"] == total and st["samples"] == total  # pt_adaptive_state.samples and pt_stats.samples
+    assert a["spp_min"] == int(counts.min()) and a["spp_max"] == int(counts.max()) == st["spp_done"]
+    assert 0 <= a["active_blocks"] <= blocks
+    if a["active_blocks"]:
+        assert a["spp_max"] == cap  # the frame went on until no block was active, or to the cap
+        assert a["worst_active"] > 0
+    else:
+        assert a["worst_active"] == 0
+    # a block's pixels share one count
+    blk = counts[::8, ::8]
+    assert np.array_equal(expand(blk, w, h), counts)
+
+
+def check_self_consistent(ctx, sc, w, h, cap, depth, seed, target, step, min_spp=0, chunk=0, min_distinct=2, **kw):
+    """An adaptive frame on ctx, then for each distinct count n a plain n-sample frame of the same context: the blocks that hold n
+    samples are bit-equal in rgba, accum and m2.  Returns (counts, st)."""
+    from path_trace_golang_amd import hip
+
+    img, acc, m2, counts, _, _, st = render_adaptive(ctx, sc, w, h, cap, depth, seed, target, step, min_spp, chunk, **kw)
+    assert counts.min() >= 1 and counts.max() <= cap  # zeros nowhere inside the frame
+    check_state(st, counts, cap)
+    distinct = sorted(set(int(v) for v in np.unique(counts)))
+    assert len(distinct) >= min_distinct, distinct
+    for n in distinct:
+        pi = np.zeros((h, w, 4), np.uint8)
+        pa = np.zeros((h, w, 3))
+        pm = np.zeros((h, w, 3))
+        hip.render(sc, hip.RenderConfig(w, h, n, depth, seed, chunk), pi, None, pa, ctx=ctx, moments=pm, **kw)
+        sel = counts == n
+        assert np.array_equal(img[sel], pi[sel]), ("rgba", n)
+        assert np.array_equal(bits(acc)[sel], bits(pa)[sel]), ("accum", n)
+        assert np.array_equal(bits(m2)[sel], bits(pm)[sel]), ("m2", n)
+    return counts, st
