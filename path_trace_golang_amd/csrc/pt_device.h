@@ -122,6 +122,15 @@ struct DevSky {
     double c1[3];      // gradient: zenith
 };
 
+// What the slot -> pixel map (ptk::block_pixel in pt_kernels.h) needs to know of a frame and of one shard of it: shard
+// `shard_index` of `shard_count` owns the tiles t = shard_index + lt * shard_count (lt = 0, 1, ...) of the ntx-wide tile grid.
+// Every kernel that works per slot or per job gets one (ptcore.hip: tile_geom()); DevFrame carries the same five fields.
+struct TileGeom {
+    int32_t width, height;
+    int32_t ntx;
+    int32_t shard_index, shard_count;
+};
+
 struct DevFrame {
     int32_t width, height;
     int32_t max_depth;

@@ -1324,15 +1324,39 @@ __device__ __forceinline__ void store_radiance(double *L, size_t job, double x, 
     reinterpret_cast<double4 *>(L)[job] = make_double4(x, y, z, 0.0);
 }
 
-// The job -> (pixel, sample) map of a chunk, shared by everything that reads or writes the primary-ray planes: row q = job >> 6 of 64
-// consecutive jobs is sample sl of the chunk for the 8x8 sub-block blk = q / S (16 sub-blocks per 32x32 tile, the shard's tiles in
-// order), and lane p = job & 63 is the pixel inside that sub-block.  A wave is one 8x8 pixel block of one sample.
-__device__ __forceinline__ void block_pixel(const DevFrame &F, uint32_t blk, uint32_t p, uint32_t &x, uint32_t &y) {
+// The slot -> pixel map, once.  A shard's slots are its tiles in order, 16 sub-blocks of 8x8 pixels per 32x32 tile, 64 pixels per
+// sub-block: slot = blk * 64 + p, blk = lt * 16 + sb.  Tile lt of the shard is tile t = shard_index + lt * shard_count of the frame's
+// ntx-wide grid; (lx, ly) is the pixel inside the tile, (x, y) in the frame, `inside` whether the frame holds it (edge tiles are ragged) and
+// pix = lt * 1024 + ly * 32 + lx its place in the shard's tile-major planes (tiles_rgba, tiles_accum, ...).  Everything that works per slot
+// or per job computes through block_pixel; what a caller does not use costs nothing.  untile_kernel below holds the inverse.
+struct Pixel {
+    uint32_t x, y, lt, lx, ly;
+    bool inside;
+    size_t pix;
+};
+__device__ __forceinline__ Pixel block_pixel(const TileGeom &G, uint32_t blk, uint32_t p) {
     const uint32_t lt = blk >> 4, sb = blk & 15u;
-    const uint32_t t = (uint32_t)F.shard_index + lt * (uint32_t)F.shard_count;
-    const uint32_t ty = t / (uint32_t)F.ntx, tx = t - ty * (uint32_t)F.ntx;
-    x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
-    y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+    const uint32_t t = (uint32_t)G.shard_index + lt * (uint32_t)G.shard_count;
+    const uint32_t ty = t / (uint32_t)G.ntx, tx = t - ty * (uint32_t)G.ntx;
+    Pixel r;
+    r.lt = lt;
+    r.lx = (sb & 3u) * 8u + (p & 7u);
+    r.ly = (sb >> 2) * 8u + (p >> 3);
+    r.x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
+    r.y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+    r.inside = r.x < (uint32_t)G.width && r.y < (uint32_t)G.height;
+    r.pix = (size_t)lt * 1024u + r.ly * 32u + r.lx;
+    return r;
+}
+__device__ __forceinline__ Pixel slot_pixel(const TileGeom &G, uint32_t slot) { return block_pixel(G, slot >> 6, slot & 63u); }
+
+// The job -> (pixel, sample) map of a chunk, shared by everything that reads or writes the primary-ray planes: row q = job >> 6 of 64
+// consecutive jobs is sample sl of the chunk for the 8x8 sub-block blk = q / S, and lane p = job & 63 is the pixel inside that sub-block.
+// A wave is one 8x8 pixel block of one sample.  (DevFrame's entry to the map above: its five fields, in registers.)
+__device__ __forceinline__ void block_pixel(const DevFrame &F, uint32_t blk, uint32_t p, uint32_t &x, uint32_t &y) {
+    const Pixel q = block_pixel(TileGeom{F.width, F.height, F.ntx, F.shard_index, F.shard_count}, blk, p);
+    x = q.x;
+    y = q.y;
 }
 __device__ __forceinline__ void job_pixel(const DevFrame &F, uint32_t q, uint32_t p, uint32_t &x, uint32_t &y, uint32_t &sl) {
     const uint32_t blk = q / F.S;
@@ -2830,7 +2854,7 @@ struct ResolveArgs {
     int32_t finish;          // 1: write tiles_rgba / tiles_accum
     int32_t have_chunk;      // 0: no chunk to add (pure finish, pt_read)
     double inv_samples;      // 1/spp_done
-    int32_t width, height, ntx, shard_index, shard_count;
+    TileGeom G;
     int32_t gl_spp;          // GL shading: spp_done, and the finish is GL's tone map (post_tonemap_kernel); 0: the CPU engine's
 };
 
@@ -2844,27 +2868,33 @@ struct AdaptTable {
     uint32_t nact;
 };
 
+// The slot a thread of resolve_body / moments_body works on, and cblk: the slot's rows in the job buffers start at cblk * S.  One thread
+// per slot of the shard -- but where an adaptive frame adds a chunk, one per slot of the nact active blocks: compact row cblk is block
+// active[cblk].  false: the thread has no slot.
+template <bool ADAPT>
+__device__ __forceinline__ bool chunk_slot(int32_t have_chunk, const AdaptTable &T, uint32_t nslots, uint32_t &slot, uint32_t &cblk) {
+    slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (ADAPT && have_chunk) {
+        if (slot >= T.nact * 64u) return false;
+        cblk = __builtin_amdgcn_readfirstlane(slot >> 6);
+        slot = T.active[cblk] * 64u + (slot & 63u);  // wave-uniform index: a scalar load
+    } else {
+        if (slot >= nslots) return false;
+        cblk = slot >> 6;
+    }
+    return true;
+}
+
 // (ADAPT: resolve_adaptive_kernel below.  Its add runs over the nact * 64 slots of the active blocks, its finish over every slot with
 // 1 / n of the slot's own block.)
 template <bool ADAPT>
 __device__ __forceinline__ void resolve_body(const ResolveArgs &R, const AdaptTable &T) {
-    uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
-    uint32_t cblk;  // the block's rows in the job buffers start at cblk * S
-    if (ADAPT && R.have_chunk) {
-        if (slot >= T.nact * 64u) return;
-        cblk = __builtin_amdgcn_readfirstlane(slot >> 6);
-        slot = T.active[cblk] * 64u + (slot & 63u);  // wave-uniform index: a scalar load
-    } else {
-        if (slot >= R.nslots) return;
-        cblk = slot >> 6;
-    }
+    uint32_t slot, cblk;
+    if (!chunk_slot<ADAPT>(R.have_chunk, T, R.nslots, slot, cblk)) return;
     const uint32_t blk = slot >> 6, p = slot & 63u;
-    const uint32_t lt = blk >> 4, sb = blk & 15u;
-    const uint32_t t = (uint32_t)R.shard_index + lt * (uint32_t)R.shard_count;
-    const uint32_t ty = t / (uint32_t)R.ntx, tx = t - ty * (uint32_t)R.ntx;
-    const uint32_t lx = (sb & 3u) * 8u + (p & 7u), ly = (sb >> 2) * 8u + (p >> 3);
-    const uint32_t x = tx * 32u + lx, y = ty * 32u + ly;
-    const bool inside = x < (uint32_t)R.width && y < (uint32_t)R.height;
+    const Pixel px = block_pixel(R.G, blk, p);
+    const bool inside = px.inside;
+    const size_t pix = px.pix;
 
     double cx = 0, cy = 0, cz = 0;
     uint32_t nseg = 0, ndraw = 0;
@@ -2892,7 +2922,6 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs &R, const AdaptTa
         }
     }
     if (R.finish) {
-        const size_t pix = (size_t)lt * 1024u + ly * 32u + lx;
         if (R.tiles_rgba) {
             uint32_t packed = 0;
             if (inside && R.gl_spp) {
@@ -2923,6 +2952,10 @@ __global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) 
 
 __global__ __launch_bounds__(PT_BLOCK) void resolve_adaptive_kernel(const ResolveArgs R, const AdaptTable T) { resolve_body<true>(R, T); }
 
+// The inverse of block_pixel, over the tiles of every shard at once: pixel (x, y) lies in tile t, which shard k = t % shard_count holds as its
+// tile lt = t / shard_count, at pix = lt * 1024 + ly * 32 + lx of that shard's planes -- block_pixel's pix, with t = k + lt * shard_count.
+// The shards' planes stand one behind the other: packed, or shard_stride_tiles tiles apart (a caller's buffer with room for the largest
+// shard each, pt_untile_device).  Only this side knows of that stride: a forward kernel writes one shard's planes from their start.
 struct UntileArgs {
     const uint8_t *tiles_rgba;   // concatenated per shard: shard k holds its tiles in local order
     const double *tiles_accum;   // or null
@@ -2975,28 +3008,16 @@ struct MomentsArgs {
     int32_t first;           // 1: the running sum starts at zero
     int32_t finish;          // 1: write tiles_m2
     int32_t have_chunk;      // 0: no chunk to add (pure finish)
-    int32_t width, height, ntx, shard_index, shard_count;
+    TileGeom G;
 };
 
 template <bool ADAPT>
 __device__ __forceinline__ void moments_body(const MomentsArgs &M, const AdaptTable &T) {
-    uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
-    uint32_t cblk;  // as in resolve_body
-    if (ADAPT && M.have_chunk) {
-        if (slot >= T.nact * 64u) return;
-        cblk = __builtin_amdgcn_readfirstlane(slot >> 6);
-        slot = T.active[cblk] * 64u + (slot & 63u);
-    } else {
-        if (slot >= M.nslots) return;
-        cblk = slot >> 6;
-    }
-    const uint32_t blk = slot >> 6, p = slot & 63u;
-    const uint32_t lt = blk >> 4, sb = blk & 15u;
-    const uint32_t t = (uint32_t)M.shard_index + lt * (uint32_t)M.shard_count;
-    const uint32_t ty = t / (uint32_t)M.ntx, tx = t - ty * (uint32_t)M.ntx;
-    const uint32_t lx = (sb & 3u) * 8u + (p & 7u), ly = (sb >> 2) * 8u + (p >> 3);
-    const uint32_t x = tx * 32u + lx, y = ty * 32u + ly;
-    const bool inside = x < (uint32_t)M.width && y < (uint32_t)M.height;
+    uint32_t slot, cblk;
+    if (!chunk_slot<ADAPT>(M.have_chunk, T, M.nslots, slot, cblk)) return;
+    const uint32_t p = slot & 63u;
+    const Pixel px = slot_pixel(M.G, slot);
+    const bool inside = px.inside;
 
     double qx = 0, qy = 0, qz = 0;
     if (inside) {
@@ -3019,7 +3040,7 @@ __device__ __forceinline__ void moments_body(const MomentsArgs &M, const AdaptTa
         }
     }
     if (M.finish) {
-        const size_t pix = (size_t)lt * 1024u + ly * 32u + lx;
+        const size_t pix = px.pix;
         M.tiles_m2[3 * pix] = inside ? qx : 0.0;
         M.tiles_m2[3 * pix + 1] = inside ? qy : 0.0;
         M.tiles_m2[3 * pix + 2] = inside ? qz : 0.0;
@@ -3048,8 +3069,26 @@ struct NoiseArgs {
     NoisePartial *partial;   // [gridDim.x]
     uint32_t nslots;
     int32_t n;               // samples done, >= 2
-    int32_t width, height, ntx, shard_index, shard_count;
+    TileGeom G;
 };
+
+// The e2 above of one slot with n samples; bad: it came out NaN or infinite, and is returned as 0.
+__device__ __forceinline__ double pixel_e2(const double *__restrict__ acc, const double *__restrict__ m2, uint32_t nslots, uint32_t slot, int32_t ni, bool &bad) {
+    const double n = (double)ni, n1 = (double)(ni - 1);
+    double msum = 0.0, vsum = 0.0;
+    for (uint32_t c = 0; c < 3u; c++) {
+        const double m = acc[c * (size_t)nslots + slot] / n;
+        double d = m2[c * (size_t)nslots + slot] / n - m * m;
+        if (d < 0.0) d = 0.0;  // (a NaN stays a NaN)
+        msum += m;
+        vsum += d / n1;
+    }
+    double den = msum / 3.0;
+    if (den < 0.01) den = 0.01;
+    const double e2 = (vsum / 3.0) / (den * den);
+    bad = !(e2 - e2 == 0.0);  // NaN or infinite
+    return bad ? 0.0 : e2;
+}
 
 // (ADAPT: noise_adaptive_kernel below -- every slot with the n of its own block)
 template <bool ADAPT>
@@ -3059,31 +3098,10 @@ __device__ __forceinline__ void noise_body(const NoiseArgs &A, const uint32_t *_
     const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
     double e2 = 0.0;
     uint32_t bad = 0;
-    if (slot < A.nslots) {
-        const uint32_t blk = slot >> 6, p = slot & 63u;
-        const uint32_t lt = blk >> 4, sb = blk & 15u;
-        const uint32_t t = (uint32_t)A.shard_index + lt * (uint32_t)A.shard_count;
-        const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
-        const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u), y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
-        if (x < (uint32_t)A.width && y < (uint32_t)A.height) {
-            const int32_t ni = ADAPT ? (int32_t)blk_spp[blk] : A.n;
-            const double n = (double)ni, n1 = (double)(ni - 1);
-            double msum = 0.0, vsum = 0.0;
-            for (uint32_t c = 0; c < 3u; c++) {
-                const double m = A.acc[c * (size_t)A.nslots + slot] / n;
-                double d = A.m2[c * (size_t)A.nslots + slot] / n - m * m;
-                if (d < 0.0) d = 0.0;  // (a NaN stays a NaN)
-                msum += m;
-                vsum += d / n1;
-            }
-            double den = msum / 3.0;
-            if (den < 0.01) den = 0.01;
-            e2 = (vsum / 3.0) / (den * den);
-            if (!(e2 - e2 == 0.0)) {  // NaN or infinite
-                e2 = 0.0;
-                bad = 1;
-            }
-        }
+    if (slot < A.nslots && slot_pixel(A.G, slot).inside) {
+        bool b;
+        e2 = pixel_e2(A.acc, A.m2, A.nslots, slot, ADAPT ? (int32_t)blk_spp[slot >> 6] : A.n, b);
+        bad = b ? 1u : 0u;
     }
     double sum = e2, mx = e2;
     for (int off = 32; off > 0; off >>= 1) {
@@ -3135,35 +3153,17 @@ struct BlockNoiseArgs {
     uint32_t nslots, nact;
     int32_t n;               // samples the active blocks hold
     int32_t decide;          // 0: n is below max(min_spp, 2), every block stays active
-    int32_t width, height, ntx, shard_index, shard_count;
+    TileGeom G;
 };
 
 __global__ __launch_bounds__(PT_BLOCK) void block_noise_kernel(const BlockNoiseArgs A) {
     const uint32_t c = __builtin_amdgcn_readfirstlane((blockIdx.x * PT_BLOCK + threadIdx.x) >> 6);
     if (c >= A.nact) return;  // (wave-uniform)
     const uint32_t blk = A.active[c], p = threadIdx.x & 63u;
-    const uint32_t lt = blk >> 4, sb = blk & 15u;
-    const uint32_t t = (uint32_t)A.shard_index + lt * (uint32_t)A.shard_count;
-    const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
-    const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u), y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
-    const bool inside = x < (uint32_t)A.width && y < (uint32_t)A.height;
-    const uint32_t slot = blk * 64u + p;
+    const bool inside = block_pixel(A.G, blk, p).inside;
     double e2 = 0.0;
-    if (inside && A.n >= 2) {
-        const double n = (double)A.n, n1 = (double)(A.n - 1);
-        double msum = 0.0, vsum = 0.0;
-        for (uint32_t ch = 0; ch < 3u; ch++) {
-            const double m = A.acc[ch * (size_t)A.nslots + slot] / n;
-            double d = A.m2[ch * (size_t)A.nslots + slot] / n - m * m;
-            if (d < 0.0) d = 0.0;  // (a NaN stays a NaN)
-            msum += m;
-            vsum += d / n1;
-        }
-        double den = msum / 3.0;
-        if (den < 0.01) den = 0.01;
-        e2 = (vsum / 3.0) / (den * den);
-        if (!(e2 - e2 == 0.0)) e2 = 0.0;  // NaN or infinite
-    }
+    bool bad;  // (not counted here: a NaN or infinite e2 adds 0)
+    if (inside && A.n >= 2) e2 = pixel_e2(A.acc, A.m2, A.nslots, blk * 64u + p, A.n, bad);
     const uint32_t k = (uint32_t)__popcll(__ballot(inside));
     double sum = e2;
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
@@ -3243,16 +3243,11 @@ __global__ __launch_bounds__(PT_COMPACT_BLOCK) void compact_kernel(const Compact
 // The per-pixel sample counts of an adaptive frame, tile-major with zeros outside the frame (the layout of tiles_seg), for
 // untile_kernel's u32a plane.
 __global__ __launch_bounds__(PT_BLOCK) void counts_tiles_kernel(const uint32_t *__restrict__ blk_spp, uint32_t *__restrict__ tiles_u32, uint32_t nslots,
-                                                                  int32_t width, int32_t height, int32_t ntx, int32_t shard_index, int32_t shard_count) {
+                                                                  const TileGeom G) {
     const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
     if (slot >= nslots) return;
-    const uint32_t blk = slot >> 6, p = slot & 63u;
-    const uint32_t lt = blk >> 4, sb = blk & 15u;
-    const uint32_t t = (uint32_t)shard_index + lt * (uint32_t)shard_count;
-    const uint32_t ty = t / (uint32_t)ntx, tx = t - ty * (uint32_t)ntx;
-    const uint32_t lx = (sb & 3u) * 8u + (p & 7u), ly = (sb >> 2) * 8u + (p >> 3);
-    const bool inside = tx * 32u + lx < (uint32_t)width && ty * 32u + ly < (uint32_t)height;
-    tiles_u32[(size_t)lt * 1024u + ly * 32u + lx] = inside ? blk_spp[blk] : 0u;
+    const Pixel px = slot_pixel(G, slot);
+    tiles_u32[px.pix] = px.inside ? blk_spp[slot >> 6] : 0u;
 }
 
 // Self-test of div_shared against the compiler's IEEE division: `per_thread` operand pairs per thread, exponents drawn
@@ -3446,7 +3441,7 @@ struct FogArgs {
     uint64_t fog_key;                 // ptm::seed_key(seed ^ PTF_STREAM_SALT)
     int32_t nobj, nlight;
     uint32_t njobs, S, s0;
-    int32_t width, height, ntx, shard_index, shard_count;
+    TileGeom G;
 };
 
 template <bool ADAPT>
@@ -3460,15 +3455,11 @@ __device__ __forceinline__ void fog_body(const FogArgs &A, const uint32_t *__res
         const uint32_t cblk = q / A.S;
         const uint32_t sl = q - cblk * A.S;
         const uint32_t blk = ADAPT ? active[__builtin_amdgcn_readfirstlane(cblk)] : cblk;  // (every lane of a wave holds the same row q)
-        const uint32_t lt = blk >> 4, sb = blk & 15u;
-        const uint32_t t = (uint32_t)A.shard_index + lt * (uint32_t)A.shard_count;
-        const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
-        const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
-        const uint32_t y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
+        const Pixel px = block_pixel(A.G, blk, p);
         const size_t nj = A.njobs;
         const double o[3] = {A.ray[job], A.ray[nj + job], A.ray[2 * nj + job]};
         const double d[3] = {A.ray[3 * nj + job], A.ray[4 * nj + job], A.ray[5 * nj + job]};
-        const uint64_t rs = ptm::stream_init(A.fog_key, (uint64_t)y * (uint64_t)(uint32_t)A.width + x, (uint64_t)(A.s0 + sl));
+        const uint64_t rs = ptm::stream_init(A.fog_key, (uint64_t)px.y * (uint64_t)(uint32_t)A.G.width + px.x, (uint64_t)(A.s0 + sl));
         double f[3];
         ptf::fog_inscatter(A.P, A.objs, A.nobj, A.lights, A.nlight, o, d, rs, cnt, f);
         double4 *rec = reinterpret_cast<double4 *>(A.L) + job;
@@ -3503,7 +3494,7 @@ struct GlArgs {
     unsigned long long *fog_counters;  // [3] shadow rays, draws, march steps (fog on)
     uint64_t key, fog_key;
     uint32_t njobs, nS, s0;
-    int32_t ntx, shard_index, shard_count;
+    int32_t ntx, shard_index, shard_count;  // with S.width and S.height (stored once, there) the TileGeom of the shard
 };
 
 __global__ __launch_bounds__(PT_BLOCK) void gl_trace_kernel(const GlArgs A) {
@@ -3515,14 +3506,10 @@ __global__ __launch_bounds__(PT_BLOCK) void gl_trace_kernel(const GlArgs A) {
         const uint32_t q = job >> 6;
         const uint32_t blk = q / A.nS;
         const uint32_t sl = q - blk * A.nS;
-        const uint32_t lt = blk >> 4, sb = blk & 15u;
-        const uint32_t t = (uint32_t)A.shard_index + lt * (uint32_t)A.shard_count;
-        const uint32_t ty = t / (uint32_t)A.ntx, tx = t - ty * (uint32_t)A.ntx;
-        const uint32_t x = tx * 32u + (sb & 3u) * 8u + (p & 7u);
-        const uint32_t y = ty * 32u + (sb >> 2) * 8u + (p >> 3);
-        if (x < (uint32_t)A.S.width && y < (uint32_t)A.S.height) {
+        const Pixel px = block_pixel(TileGeom{A.S.width, A.S.height, A.ntx, A.shard_index, A.shard_count}, blk, p);
+        if (px.inside) {
             double col[3];
-            ptg::gl_pass(A.S, A.key, A.fog_key, (int32_t)x, (int32_t)y, A.s0 + sl, cnt, fc, col);
+            ptg::gl_pass(A.S, A.key, A.fog_key, (int32_t)px.x, (int32_t)px.y, A.s0 + sl, cnt, fc, col);
             reinterpret_cast<double4 *>(A.L)[job] = make_double4(col[0], col[1], col[2], 0.0);
         }
     }

@@ -640,6 +640,35 @@ int32_t dev_events(Device &d, std::vector<EventPair> &v, size_t need) {
     return PT_OK;
 }
 
+// One timed launch on d's stream: takes the next event pair of `v` (making it if the list is short), records a, runs `launch` -- one kernel
+// launch, or several that are timed as one --, checks hipGetLastError and records b.  The pair is v[n - 1] afterwards.
+template <typename Launch>
+int32_t timed(Device &d, std::vector<EventPair> &v, size_t &n, Launch &&launch) {
+    if (int32_t rc = dev_events(d, v, n + 1)) return rc;
+    const EventPair e = v[n++];
+    HIP_TRY(hipEventRecord(e.a, d.stream));
+    launch();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e.b, d.stream));
+    return PT_OK;
+}
+
+// Milliseconds between a and b, added up over the first n pairs of `v` (their device is current and has finished them); `flagged`: the
+// share of the pairs i with flag[i] set.
+int32_t sum_ms(const std::vector<EventPair> &v, size_t n, double &sum, const std::vector<char> *flag = nullptr, double *flagged = nullptr) {
+    sum = 0;
+    for (size_t i = 0; i < n; i++) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, v[i].a, v[i].b));
+        sum += ms;
+        if (flag && i < flag->size() && (*flag)[i]) *flagged += ms;
+    }
+    return PT_OK;
+}
+
+// The shard of the open frame that device d renders, for the slot -> pixel map of the kernels (ptk::block_pixel).
+TileGeom tile_geom(const Frame &fr, const Device &d) { return TileGeom{fr.cfg.width, fr.cfg.height, fr.ntx, d.shard.index, d.shard.count}; }
+
 #define PT_GLASS_MAX_BLOCKS_PER_CU 8
 
 size_t walk32_lds_bytes() { return 0; }  // the stacks are static LDS of the kernel
@@ -945,16 +974,6 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
     // together leave at most 2 x grid_pass x 4 waves x PT_CONT_BLOCK slots empty, which is what queue_slack() allocates.
     const uint32_t grid_pass = std::max(1u, std::min((uint32_t)(d.num_cu * PT_WF_PASS_BLOCKS_PER_CU), blocks_all));
     const int levels = std::max(0, fr.cfg.max_depth);
-    if (int32_t rc = dev_events(d, d.ev_trace, d.n_trace + 4 * (size_t)levels + 1)) return rc;
-    if (int32_t rc = dev_events(d, d.ev_glass, d.n_glass + 3 * (size_t)levels + 2)) return rc;
-    auto timed = [&](std::vector<EventPair> &v, size_t &n, auto &&launch) -> int32_t {
-        EventPair &e = v[n++];
-        HIP_TRY(hipEventRecord(e.a, d.stream));
-        launch();
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e.b, d.stream));
-        return PT_OK;
-    };
     // walk32 (pt_walk32.h): the FP32 walk lists candidates, the FP64 traversal answers the few entries the walk hands over
     const bool walk32 = fr.walk32 && bvh;
     const bool walk_diag = std::getenv("PTCORE_WALK_STATS") != nullptr;
@@ -979,7 +998,7 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
         if (walk32) {
             HIP_TRY(hipMemsetAsync(qw + 6, 0, sizeof(unsigned int), d.stream));
             const ptk::Walk32Args K = walk_args();
-            if (int32_t rc = timed(d.ev_trace, d.n_trace, [&] {
+            if (int32_t rc = timed(d, d.ev_trace, d.n_trace, [&] {
                     if (walk_diag) {
                         if (mode == 0) hipLaunchKernelGGL((ptk::wf_walk32_kernel<0, true>), dim3(grid_walk), dim3(PT_BLOCK), walk32_lds_bytes(), d.stream, K);
                         else hipLaunchKernelGGL((ptk::wf_walk32_kernel<1, true>), dim3(grid_walk), dim3(PT_BLOCK), walk32_lds_bytes(), d.stream, K);
@@ -989,19 +1008,18 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
                 return rc;
             // the entries the walk handed over, through the FP64 traversal (their number lives on the device)
             HIP_TRY(hipMemsetAsync(qw, 0, sizeof(unsigned int), d.stream));
-            if (int32_t rc = dev_events(d, d.ev_trace, d.n_trace + 1)) return rc;
             if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
             d.trace_is_split[d.n_trace] = 0;
             ptk::WfArgs S = A;
             S.perm = d.slow_list.p;
             S.n_sorted = qw + 6;
             const uint32_t grid_slow = std::max(1u, std::min(grid_scan, (uint32_t)d.num_cu));
-            return timed(d.ev_trace, d.n_trace, [&] {
+            return timed(d, d.ev_trace, d.n_trace, [&] {
                 if (mode == 0) hipLaunchKernelGGL((ptk::wf_traverse_kernel<0, false>), dim3(grid_slow), dim3(PT_BLOCK), lds_scan, d.stream, S);
                 else hipLaunchKernelGGL((ptk::wf_traverse_kernel<1, false>), dim3(grid_slow), dim3(PT_BLOCK), lds_scan, d.stream, S);
             });
         }
-        return timed(d.ev_trace, d.n_trace, [&] {
+        return timed(d, d.ev_trace, d.n_trace, [&] {
             if (bvh) {
                 if (mode == 0) {
                     if (verify) hipLaunchKernelGGL((ptk::wf_traverse_kernel<0, true>), dim3(grid_scan), dim3(PT_BLOCK), lds_scan, d.stream, A);
@@ -1025,7 +1043,7 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
     A.qin = qa;
     A.qout = qb;
     A.qexit = qe;
-    if (int32_t rc = timed(d.ev_glass, d.n_glass, [&] {
+    if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
             if (stats) hipLaunchKernelGGL(ptk::wf_init_kernel<true>, dim3(std::min(blocks_all, (uint32_t)d.num_cu * 8u)), dim3(PT_BLOCK), 0, d.stream, A);
             else hipLaunchKernelGGL(ptk::wf_init_kernel<false>, dim3(std::min(blocks_all, (uint32_t)d.num_cu * 8u)), dim3(PT_BLOCK), 0, d.stream, A);
         }))
@@ -1042,7 +1060,7 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
             A.bin_count = d.wf_bins.p;
             A.bin_key = d.wf_key.p;
             HIP_TRY(hipMemsetAsync(d.wf_bins.p, 0, (PT_WF_BINS + 1) * sizeof(uint32_t), d.stream));
-            if (int32_t rc = timed(d.ev_glass, d.n_glass, [&] {
+            if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
                     hipLaunchKernelGGL(ptk::wf_bin_count_kernel, dim3(grid_pass), dim3(PT_BLOCK), 0, d.stream, A);
                     hipLaunchKernelGGL(ptk::wf_bin_scan_kernel, dim3(1), dim3(1024), 0, d.stream, A);
                     hipLaunchKernelGGL(ptk::wf_bin_scatter_kernel, dim3(grid_pass), dim3(PT_BLOCK), 0, d.stream, A, d.wf_perm.p);
@@ -1055,7 +1073,7 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
         A.perm = nullptr;
         HIP_TRY(hipMemsetAsync(cur_out.count, 0, sizeof(unsigned int), d.stream));
         HIP_TRY(hipMemsetAsync(qe.count, 0, sizeof(unsigned int), d.stream));
-        if (int32_t rc = timed(d.ev_glass, d.n_glass, [&] {
+        if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
                 if (walk32) {
                     const ptk::Walk32Args K = walk_args();
                     if (stats) {
@@ -1072,7 +1090,7 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
         if (fr.has_glass) {
             A.qin = qe;
             if (int32_t rc = scan_pass(1)) return rc;
-            if (int32_t rc = timed(d.ev_glass, d.n_glass, [&] {
+            if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
                     if (walk32) {
                         const ptk::Walk32Args K = walk_args();
                         if (stats) {
@@ -1113,6 +1131,7 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     F.S = S;
     F.njobs = (fr.adaptive ? d.nact * 64u : d.nslots) * S;  // adaptive: the active blocks' jobs only, compact
     const ptk::AdaptTable AT{d.act[d.act_cur].p, d.blk_spp.p, d.nact};
+    const TileGeom G = tile_geom(fr, d);
     // jobs a wave claims per pop of the item cursor: 256, and 512 for the bitmask scans once a pass holds 128 samples per pixel
     // or more (same-box sweeps, profiles/r02_claim_sweep.txt: C4 at 265 spp per pass 664 / 653 / 654 / 659 / 673 ms for 256 / 512 /
     // 1024 / 2048 / 4096, at 79 spp per pass 677 / 675 / 678 ms; the BVH path loses 3 % at 512 and 7 % at 1024)
@@ -1145,9 +1164,6 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     }
 
     const int rounds = fr.split_rounds;
-    if (int32_t rc = dev_events(d, d.ev_trace, d.n_trace + (size_t)rounds + 2)) return rc;
-    if (int32_t rc = dev_events(d, d.ev_glass, d.n_glass + (size_t)rounds + 1)) return rc;
-    if (int32_t rc = dev_events(d, d.ev_resolve, d.n_resolve + 1)) return rc;
     if (!d.first_recorded) {
         HIP_TRY(hipEventRecord(d.ev_first, d.stream));
         d.first_recorded = true;
@@ -1189,8 +1205,8 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         GS.sky = fr.gl_sky;
         GS.cam = fr.gl_cam;
         GS.max_depth = fr.cfg.max_depth;
-        GS.width = fr.cfg.width;
-        GS.height = fr.cfg.height;
+        GS.width = G.width;
+        GS.height = G.height;
         GS.fog_on = fr.fog_vol ? 1 : 0;
         GS.fog = fr.fog;
         GS.fog_objs = d.objs.p;
@@ -1206,39 +1222,36 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         GA.njobs = F.njobs;
         GA.nS = S;
         GA.s0 = s0;
-        GA.ntx = fr.ntx;
-        GA.shard_index = d.shard.index;
-        GA.shard_count = d.shard.count;
+        GA.ntx = G.ntx;  // (the frame size is GS's)
+        GA.shard_index = G.shard_index;
+        GA.shard_count = G.shard_count;
         if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
         d.trace_is_split[d.n_trace] = 0;
-        EventPair &e = d.ev_trace[d.n_trace++];
-        HIP_TRY(hipEventRecord(e.a, d.stream));
-        hipLaunchKernelGGL(ptk::gl_trace_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, GA);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e.b, d.stream));
+        if (int32_t rc = timed(d, d.ev_trace, d.n_trace, [&] {
+                hipLaunchKernelGGL(ptk::gl_trace_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, GA);
+            }))
+            return rc;
     } else {  // ray generation, then the trace passes (which also handle max_depth <= 0: black samples, camera draws counted)
         HIP_TRY(hipMemsetAsync(qw, 0, 8 * sizeof(unsigned int), d.stream));
         const size_t lds = fr.lds_bytes;
         const uint32_t waves_needed = (F.njobs + 63u) / 64u;
-        if (int32_t rc = dev_events(d, d.ev_raygen, d.n_raygen + 1)) return rc;
-        EventPair &eg = d.ev_raygen[d.n_raygen++];
-        HIP_TRY(hipEventRecord(eg.a, d.stream));
         const char *rg_form = std::getenv("PTCORE_RAYGEN");  // A/B: "column" = round 2's walk down a lane's column, "simple" = one job per lane
         const bool rg_simple = std::getenv("PTCORE_RAYGEN_SIMPLE") || (rg_form && !std::strcmp(rg_form, "simple"));
-        if (fr.adaptive)
-            hipLaunchKernelGGL(ptk::raygen_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, F, fr.cam,
-                               d.ray.p, d.ray_rng.p, d.ray_ndraw.p, AT.active);
-        else if (fr.cam.lens_radius > 0 && !rg_simple && !(rg_form && !std::strcmp(rg_form, "column")))  // thin lens: the rejection loop over a wave's pool of jobs
-            hipLaunchKernelGGL(ptk::raygen_lens_pool_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_POOL_ROWS - 1) / (PT_BLOCK * PT_RG_POOL_ROWS)), dim3(PT_BLOCK), 0,
-                               d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
-        else if (fr.cam.lens_radius > 0 && !rg_simple)
-            hipLaunchKernelGGL(ptk::raygen_lens_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_ROWS - 1) / (PT_BLOCK * PT_RG_ROWS)), dim3(PT_BLOCK), 0,
-                               d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
-        else
-            hipLaunchKernelGGL(ptk::raygen_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, F, fr.cam,
-                               d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(eg.b, d.stream));
+        if (int32_t rc = timed(d, d.ev_raygen, d.n_raygen, [&] {
+                if (fr.adaptive)
+                    hipLaunchKernelGGL(ptk::raygen_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, F, fr.cam,
+                                       d.ray.p, d.ray_rng.p, d.ray_ndraw.p, AT.active);
+                else if (fr.cam.lens_radius > 0 && !rg_simple && !(rg_form && !std::strcmp(rg_form, "column")))  // thin lens: the rejection loop over a wave's pool of jobs
+                    hipLaunchKernelGGL(ptk::raygen_lens_pool_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_POOL_ROWS - 1) / (PT_BLOCK * PT_RG_POOL_ROWS)), dim3(PT_BLOCK), 0,
+                                       d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
+                else if (fr.cam.lens_radius > 0 && !rg_simple)
+                    hipLaunchKernelGGL(ptk::raygen_lens_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_ROWS - 1) / (PT_BLOCK * PT_RG_ROWS)), dim3(PT_BLOCK), 0,
+                                       d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
+                else
+                    hipLaunchKernelGGL(ptk::raygen_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, F, fr.cam,
+                                       d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
+            }))
+            return rc;
         if (!ctx->inject_rays.empty()) {  // pt_debug_set_primary_rays: the table's rays over ray generation's
             if (d.inject_gen != ctx->inject_gen) {
                 HIP_TRY(hipStreamSynchronize(d.stream));
@@ -1266,12 +1279,12 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
             grid = std::max(1u, std::min(grid, (waves_needed + 3u) / 4u));
             if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
             d.trace_is_split[d.n_trace] = split ? 1 : 0;
-            EventPair &e = d.ev_trace[d.n_trace++];
-            HIP_TRY(hipEventRecord(e.a, d.stream));
-            hipLaunchKernelGGL(pick_trace(fr.stats_on, ctx->profile_sections, fr.scan, split ? (int)ptk::FORM_SPLIT : fr.tail_form),
-                               dim3(grid), dim3(PT_BLOCK), lds, d.stream, A);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(e.b, d.stream));
+            if (int32_t rc = timed(d, d.ev_trace, d.n_trace, [&] {
+                    hipLaunchKernelGGL(pick_trace(fr.stats_on, ctx->profile_sections, fr.scan, split ? (int)ptk::FORM_SPLIT : fr.tail_form),
+                                       dim3(grid), dim3(PT_BLOCK), lds, d.stream, A);
+                }))
+                return rc;
+            const EventPair &e = d.ev_trace[d.n_trace - 1];
             if (timeline) {
                 HIP_TRY(hipStreamSynchronize(d.stream));
                 const uint32_t nw = std::min(grid * 4u, 65536u);
@@ -1312,11 +1325,9 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
             const uint32_t pgrid = std::max(1u, std::min((uint32_t)(d.num_cu * d.blocks_per_cu_primary), (F.njobs + PT_BLOCK - 1) / PT_BLOCK));  // same bound as queue_slack()
             if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
             d.trace_is_split[d.n_trace] = 0;
-            EventPair &e = d.ev_trace[d.n_trace++];
-            HIP_TRY(hipEventRecord(e.a, d.stream));
-            hipLaunchKernelGGL(pick_primary(fr.stats_on, fr.scan), dim3(pgrid), dim3(PT_BLOCK), 0, d.stream, A);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(e.b, d.stream));
+            if (int32_t rc = timed(d, d.ev_trace, d.n_trace, [&] { hipLaunchKernelGGL(pick_primary(fr.stats_on, fr.scan), dim3(pgrid), dim3(PT_BLOCK), 0, d.stream, A); }))
+                return rc;
+            const EventPair &e = d.ev_trace[d.n_trace - 1];
             if (pass_log) {
                 HIP_TRY(hipStreamSynchronize(d.stream));
                 unsigned long long c[48];
@@ -1342,16 +1353,13 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
                 B.cont.count = c_out;
                 if (int32_t rc = launch_trace(true, r == 0)) return rc;
                 if (!fr.has_glass) break;  // nothing can have entered the glass queue: the frame is done
-                EventPair &e = d.ev_glass[d.n_glass++];
-                HIP_TRY(hipEventRecord(e.a, d.stream));
-                {
-                    ptk::GlassArgs GA;
-                    GA.F = F;
-                    GA.B = B;
-                    hipLaunchKernelGGL(pick_glass(fr.stats_on, fr.scan), dim3(glass_grid), dim3(PT_BLOCK), fr.glass_lds_bytes, d.stream, GA);
-                }
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(e.b, d.stream));
+                if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
+                        ptk::GlassArgs GA;
+                        GA.F = F;
+                        GA.B = B;
+                        hipLaunchKernelGGL(pick_glass(fr.stats_on, fr.scan), dim3(glass_grid), dim3(PT_BLOCK), fr.glass_lds_bytes, d.stream, GA);
+                    }))
+                    return rc;
             }
             if (fr.has_glass) {
                 HIP_TRY(hipMemsetAsync(qw, 0, sizeof(unsigned int), d.stream));
@@ -1363,7 +1371,6 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         }
     }
     if (fr.fog_vol && !fr.gl) {  // the fog's in-scatter term into the chunk's radiance records (pt_fog.h; GL shading adds it itself)
-        if (int32_t rc = dev_events(d, d.ev_fog, d.n_fog + 1)) return rc;
         ptk::FogArgs FA;
         std::memset(&FA, 0, sizeof FA);
         FA.P = fr.fog;
@@ -1379,17 +1386,12 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         FA.njobs = F.njobs;
         FA.S = S;
         FA.s0 = s0;
-        FA.width = fr.cfg.width;
-        FA.height = fr.cfg.height;
-        FA.ntx = fr.ntx;
-        FA.shard_index = d.shard.index;
-        FA.shard_count = d.shard.count;
-        EventPair &ef = d.ev_fog[d.n_fog++];
-        HIP_TRY(hipEventRecord(ef.a, d.stream));
-        if (fr.adaptive) hipLaunchKernelGGL(ptk::fog_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA, AT.active);
-        else hipLaunchKernelGGL(ptk::fog_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ef.b, d.stream));
+        FA.G = G;
+        if (int32_t rc = timed(d, d.ev_fog, d.n_fog, [&] {
+                if (fr.adaptive) hipLaunchKernelGGL(ptk::fog_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA, AT.active);
+                else hipLaunchKernelGGL(ptk::fog_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA);
+            }))
+            return rc;
     }
     ptk::ResolveArgs R;
     std::memset(&R, 0, sizeof R);
@@ -1406,20 +1408,14 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     R.finish = 0;
     R.have_chunk = 1;
     R.inv_samples = 0;
-    R.width = fr.cfg.width;
-    R.height = fr.cfg.height;
-    R.ntx = fr.ntx;
-    R.shard_index = d.shard.index;
-    R.shard_count = d.shard.count;
-    EventPair &e = d.ev_resolve[d.n_resolve++];
-    HIP_TRY(hipEventRecord(e.a, d.stream));
+    R.G = G;
     const uint32_t add_grid = ((fr.adaptive ? d.nact * 64u : d.nslots) + PT_BLOCK - 1) / PT_BLOCK;
-    if (fr.adaptive) hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R, AT);
-    else hipLaunchKernelGGL(ptk::resolve_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e.b, d.stream));
+    if (int32_t rc = timed(d, d.ev_resolve, d.n_resolve, [&] {
+            if (fr.adaptive) hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R, AT);
+            else hipLaunchKernelGGL(ptk::resolve_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R);
+        }))
+        return rc;
     if (fr.moments) {  // the squares of the same records, in the same order (pt_set_moments)
-        if (int32_t rc = dev_events(d, d.ev_moments, d.n_moments + 1)) return rc;
         ptk::MomentsArgs M;
         std::memset(&M, 0, sizeof M);
         M.L = d.L.p;
@@ -1428,17 +1424,12 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         M.S = S;
         M.first = R.first;
         M.have_chunk = 1;
-        M.width = fr.cfg.width;
-        M.height = fr.cfg.height;
-        M.ntx = fr.ntx;
-        M.shard_index = d.shard.index;
-        M.shard_count = d.shard.count;
-        EventPair &em = d.ev_moments[d.n_moments++];
-        HIP_TRY(hipEventRecord(em.a, d.stream));
-        if (fr.adaptive) hipLaunchKernelGGL(ptk::moments_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M, AT);
-        else hipLaunchKernelGGL(ptk::moments_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(em.b, d.stream));
+        M.G = G;
+        if (int32_t rc = timed(d, d.ev_moments, d.n_moments, [&] {
+                if (fr.adaptive) hipLaunchKernelGGL(ptk::moments_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M, AT);
+                else hipLaunchKernelGGL(ptk::moments_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M);
+            }))
+            return rc;
     }
     d.acc_started = true;
     return PT_OK;
@@ -1463,16 +1454,7 @@ int32_t dev_adaptive_check(pt_ctx *ctx, Device &d, ptk::AdaptResult *host_res) {
     A.nact = d.nact;
     A.n = fr.done_spp;
     A.decide = fr.done_spp >= std::max(fr.ad.min_spp, 2) ? 1 : 0;
-    A.width = fr.cfg.width;
-    A.height = fr.cfg.height;
-    A.ntx = fr.ntx;
-    A.shard_index = d.shard.index;
-    A.shard_count = d.shard.count;
-    if (int32_t rc = dev_events(d, d.ev_check, d.n_check + 1)) return rc;
-    EventPair &ec = d.ev_check[d.n_check++];
-    HIP_TRY(hipEventRecord(ec.a, d.stream));
-    hipLaunchKernelGGL(ptk::block_noise_kernel, dim3((d.nact * 64u + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, A);
-    HIP_TRY(hipGetLastError());
+    A.G = tile_geom(fr, d);
     ptk::CompactArgs K;
     std::memset(&K, 0, sizeof K);
     K.active = d.act[d.act_cur].p;
@@ -1481,9 +1463,11 @@ int32_t dev_adaptive_check(pt_ctx *ctx, Device &d, ptk::AdaptResult *host_res) {
     K.next = d.act[d.act_cur ^ 1].p;
     K.res = d.ad_res.p;
     K.nact = d.nact;
-    hipLaunchKernelGGL(ptk::compact_kernel, dim3(1), dim3(PT_COMPACT_BLOCK), 0, d.stream, K);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ec.b, d.stream));
+    if (int32_t rc = timed(d, d.ev_check, d.n_check, [&] {  // the two as one
+            hipLaunchKernelGGL(ptk::block_noise_kernel, dim3((d.nact * 64u + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, A);
+            hipLaunchKernelGGL(ptk::compact_kernel, dim3(1), dim3(PT_COMPACT_BLOCK), 0, d.stream, K);
+        }))
+        return rc;
     HIP_TRY(hipMemcpyAsync(host_res, d.ad_res.p, sizeof *host_res, hipMemcpyDeviceToHost, d.stream));
     return PT_OK;
 }
@@ -1500,11 +1484,7 @@ int32_t dev_finish_moments(pt_ctx *ctx, Device &d, double *tiles_m2) {
     M.nslots = d.nslots;
     M.first = d.acc_started ? 0 : 1;
     M.finish = 1;
-    M.width = fr.cfg.width;
-    M.height = fr.cfg.height;
-    M.ntx = fr.ntx;
-    M.shard_index = d.shard.index;
-    M.shard_count = d.shard.count;
+    M.G = tile_geom(fr, d);
     hipLaunchKernelGGL(ptk::moments_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, M);
     HIP_TRY(hipGetLastError());
     return PT_OK;
@@ -1531,21 +1511,15 @@ int32_t dev_finish(pt_ctx *ctx, Device &d, int32_t spp_done, uint8_t *tiles_rgba
     R.have_chunk = 0;
     R.inv_samples = 1.0 / (double)spp_done;  // renderer.go:97
     R.gl_spp = fr.gl ? std::max(1, spp_done) : 0;  // GL shading: tone-mapped finish of accum / passes
-    R.width = fr.cfg.width;
-    R.height = fr.cfg.height;
-    R.ntx = fr.ntx;
-    R.shard_index = d.shard.index;
-    R.shard_count = d.shard.count;
-    if (int32_t rc = dev_events(d, d.ev_resolve, d.n_resolve + 1)) return rc;
-    EventPair &e = d.ev_resolve[d.n_resolve++];
-    HIP_TRY(hipEventRecord(e.a, d.stream));
-    if (fr.adaptive)  // every pixel by the count of its own block
-        hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R,
-                           ptk::AdaptTable{d.act[d.act_cur].p, d.blk_spp.p, d.nact});
-    else
-        hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e.b, d.stream));
+    R.G = tile_geom(fr, d);
+    if (int32_t rc = timed(d, d.ev_resolve, d.n_resolve, [&] {
+            if (fr.adaptive)  // every pixel by the count of its own block
+                hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R,
+                                   ptk::AdaptTable{d.act[d.act_cur].p, d.blk_spp.p, d.nact});
+            else
+                hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
+        }))
+        return rc;
     HIP_TRY(hipEventRecord(d.ev_last, d.stream));
     return PT_OK;
 }
@@ -1579,33 +1553,15 @@ int32_t dev_collect(Device &d, pt_stats *st, int slot) {
     st->split_finished += c[18];
     if (d.prof.p && slot == 0)
         HIP_TRY(hipMemcpy(g_profile_scratch, d.prof.p, sizeof g_profile_scratch, hipMemcpyDeviceToHost));
-    double tr = 0, rs = 0, trs = 0, gl = 0;
-    for (size_t i = 0; i < d.n_trace; i++) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, d.ev_trace[i].a, d.ev_trace[i].b));
-        tr += ms;
-        if (i < d.trace_is_split.size() && d.trace_is_split[i]) trs += ms;
-    }
-    for (size_t i = 0; i < d.n_glass; i++) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, d.ev_glass[i].a, d.ev_glass[i].b));
-        gl += ms;
-    }
+    double tr = 0, rs = 0, trs = 0, gl = 0, rg = 0;
+    if (int32_t rc = sum_ms(d.ev_trace, d.n_trace, tr, &d.trace_is_split, &trs)) return rc;
+    if (int32_t rc = sum_ms(d.ev_glass, d.n_glass, gl)) return rc;
+    if (int32_t rc = sum_ms(d.ev_resolve, d.n_resolve, rs)) return rc;
+    if (int32_t rc = sum_ms(d.ev_raygen, d.n_raygen, rg)) return rc;
     st->glass_ms = std::max(st->glass_ms, gl);
     st->trace_split_ms = std::max(st->trace_split_ms, trs);
     st->glass_launches += (int32_t)d.n_glass;
     for (size_t i = 0; i < d.n_trace && i < d.trace_is_split.size(); i++) st->trace_split_launches += d.trace_is_split[i] ? 1 : 0;
-    for (size_t i = 0; i < d.n_resolve; i++) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, d.ev_resolve[i].a, d.ev_resolve[i].b));
-        rs += ms;
-    }
-    double rg = 0;
-    for (size_t i = 0; i < d.n_raygen; i++) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, d.ev_raygen[i].a, d.ev_raygen[i].b));
-        rg += ms;
-    }
     st->raygen_ms = std::max(st->raygen_ms, rg);
     float span = 0;
     if (d.first_recorded) HIP_TRY(hipEventElapsedTime(&span, d.ev_first, d.ev_last));
@@ -1942,11 +1898,7 @@ int32_t collect_fog(pt_ctx *ctx) {
         fs.draws += c[1];
         fs.steps += c[2];
         double ms = 0;
-        for (size_t k = 0; k < d.n_fog; k++) {
-            float m = 0;
-            HIP_TRY(hipEventElapsedTime(&m, d.ev_fog[k].a, d.ev_fog[k].b));
-            ms += m;
-        }
+        if (int32_t rc = sum_ms(d.ev_fog, d.n_fog, ms)) return rc;
         fs.fog_ms = std::max(fs.fog_ms, ms);
         fs.fog_launches += (int32_t)d.n_fog;
     }
@@ -1974,11 +1926,7 @@ int32_t collect_shading(pt_ctx *ctx) {
         ss.probe_rays += c[3];
         ss.draws += c[4];
         double ms = 0;
-        for (size_t k = 0; k < d.n_trace; k++) {
-            float m = 0;
-            HIP_TRY(hipEventElapsedTime(&m, d.ev_trace[k].a, d.ev_trace[k].b));
-            ms += m;
-        }
+        if (int32_t rc = sum_ms(d.ev_trace, d.n_trace, ms)) return rc;
         ss.gl_ms = std::max(ss.gl_ms, ms);
         ss.gl_launches += (int32_t)d.n_trace;
     }
@@ -2039,6 +1987,122 @@ int32_t rccl_open(pt_ctx *ctx) {
         const ncclResult_t r_ = (expr);                                                                  \
         if (r_ != ncclSuccess) return fail(PT_ERR_HIP, std::string(#expr ": ") + ctx->rccl.GetErrorString(r_)); \
     } while (0)
+
+// The gather: every device writes its tiles of some per-pixel planes, the tiles reach devices[0], untile_kernel turns them into
+// row-major frames there, the frames go to the host.  A plane is one such quantity: its kind (element type, elements per tile, the
+// UntileArgs pair it goes through), its three buffers -- the device's tiles, every shard's tiles one behind the other on devices[0], the
+// frame on devices[0]; each as a function that reserves n elements and returns the pointer -- and where on the host it goes.
+enum PlaneKind { PLANE_RGBA, PLANE_F64X3, PLANE_U32A, PLANE_U32B };
+const struct { size_t per_tile, elem; ncclDataType_t type; } plane_kinds[] = {
+    {4096, 1, ncclUint8}, {3072, sizeof(double), ncclDouble}, {1024, sizeof(uint32_t), ncclUint32}, {1024, sizeof(uint32_t), ncclUint32}};
+
+template <typename Owner, auto Member>
+void *reserved(Owner &o, size_t n, hipError_t &e) {
+    e = (o.*Member).reserve(n);
+    return (o.*Member).p;
+}
+
+struct Plane {
+    bool on;                                          // false: left out of this gather
+    PlaneKind kind;
+    void *(*tiles)(Device &, size_t, hipError_t &);
+    void *(*gathered)(pt_ctx &, size_t, hipError_t &);
+    void *(*frame)(pt_ctx &, size_t, hipError_t &);
+    void *host;                                       // or null: gathered and untiled, not copied
+    size_t host_stride;                               // bytes per row; 0: rows back to back
+};
+
+// fill(d, dst) has device d write its tiles of plane k to dst[k] (null for a plane that is off), on d's stream.  devices[0] fills the
+// gather buffers themselves; the others fill their own buffers, which a peer copy on the same stream takes over.  With RCCL loaded every
+// device, devices[0] too, fills its own buffers and one group of sends and receives moves all planes of all devices: the sends on the
+// devices' streams, the matching receives on devices[0]'s -- one group, so that the sends and receives of this one process pair up without
+// deadlock (ncclGather is this same pattern; the counts differ per rank here).
+template <size_t N, typename Fill>
+int32_t gather_planes(pt_ctx *ctx, const Plane (&planes)[N], Fill &&fill) {
+    const Frame &fr = ctx->frame;
+    const size_t W = (size_t)fr.cfg.width, H = (size_t)fr.cfg.height;
+    const size_t ndev = ctx->devs.size(), ntiles = (size_t)fr.ntx * (size_t)fr.nty;
+    const pt_ctx::Rccl &R = ctx->rccl;
+    Device &d0 = ctx->devs[0];
+    auto bytes = [&](size_t k, size_t tiles) { return tiles * plane_kinds[planes[k].kind].per_tile * plane_kinds[planes[k].kind].elem; };
+    hipError_t e = hipSuccess;
+    char *g[N] = {};
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    for (size_t k = 0; k < N; k++) {
+        if (!planes[k].on) continue;
+        g[k] = static_cast<char *>(planes[k].gathered(*ctx, ntiles * plane_kinds[planes[k].kind].per_tile, e));
+        HIP_TRY(e);
+    }
+    std::vector<void *> own(ndev * N, nullptr);  // RCCL: what device i sends for plane k
+    size_t before = 0;
+    for (size_t i = 0; i < ndev; i++) {
+        Device &d = ctx->devs[i];
+        if (d.nlocal == 0) continue;
+        const size_t nt = (size_t)d.nlocal;
+        const bool direct = i == 0 && !R.lib;
+        void **dst = &own[i * N];
+        HIP_TRY(hipSetDevice(d.ordinal));
+        for (size_t k = 0; k < N; k++) {
+            if (!planes[k].on) continue;
+            dst[k] = direct ? g[k] + bytes(k, before) : planes[k].tiles(d, nt * plane_kinds[planes[k].kind].per_tile, e);
+            HIP_TRY(e);
+        }
+        if (int32_t rc = fill(d, dst)) return rc;
+        if (!direct && !R.lib)  // gather over xGMI: peer DMA into devices[0]'s buffer, ordered on the source stream
+            for (size_t k = 0; k < N; k++)
+                if (planes[k].on) HIP_TRY(hipMemcpyPeerAsync(g[k] + bytes(k, before), d0.ordinal, dst[k], d.ordinal, bytes(k, nt), d.stream));
+        before += nt;
+    }
+    if (R.lib) {
+        RCCL_TRY(R.GroupStart());
+        size_t off = 0;
+        for (size_t i = 0; i < ndev; i++) {
+            Device &d = ctx->devs[i];
+            if (d.nlocal == 0) continue;
+            const size_t nt = (size_t)d.nlocal;
+            for (size_t k = 0; k < N; k++) {
+                if (!planes[k].on) continue;
+                const size_t count = nt * plane_kinds[planes[k].kind].per_tile;
+                RCCL_TRY(R.Send(own[i * N + k], count, plane_kinds[planes[k].kind].type, 0, R.comms[i], d.stream));
+                RCCL_TRY(R.Recv(g[k] + bytes(k, off), count, plane_kinds[planes[k].kind].type, (int)i, R.comms[0], d0.stream));
+            }
+            off += nt;
+        }
+        RCCL_TRY(R.GroupEnd());
+    }
+    for (size_t i = 1; i < ndev; i++) {
+        HIP_TRY(hipSetDevice(ctx->devs[i].ordinal));
+        HIP_TRY(hipStreamSynchronize(ctx->devs[i].stream));
+    }
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    ptk::UntileArgs U;
+    std::memset(&U, 0, sizeof U);
+    U.width = (int32_t)W; U.height = (int32_t)H; U.ntx = fr.ntx; U.nty = fr.nty; U.stride = (int32_t)W * 4; U.shard_count = (int32_t)ndev;
+    char *f[N] = {};
+    for (size_t k = 0; k < N; k++) {
+        if (!planes[k].on) continue;
+        f[k] = static_cast<char *>(planes[k].frame(*ctx, W * H * (plane_kinds[planes[k].kind].per_tile / 1024), e));
+        HIP_TRY(e);
+        switch (planes[k].kind) {
+            case PLANE_RGBA: U.tiles_rgba = reinterpret_cast<uint8_t *>(g[k]); U.rgba = reinterpret_cast<uint8_t *>(f[k]); break;
+            case PLANE_F64X3: U.tiles_accum = reinterpret_cast<double *>(g[k]); U.accum = reinterpret_cast<double *>(f[k]); break;
+            case PLANE_U32A: U.tiles_u32a = reinterpret_cast<uint32_t *>(g[k]); U.u32a = reinterpret_cast<uint32_t *>(f[k]); break;
+            case PLANE_U32B: U.tiles_u32b = reinterpret_cast<uint32_t *>(g[k]); U.u32b = reinterpret_cast<uint32_t *>(f[k]); break;
+        }
+    }
+    hipLaunchKernelGGL(ptk::untile_kernel, dim3((unsigned)fr.ntx, (unsigned)fr.nty, 4), dim3(PT_BLOCK), 0, d0.stream, U);
+    HIP_TRY(hipGetLastError());
+    for (size_t k = 0; k < N; k++) {
+        if (!planes[k].on || !planes[k].host) continue;
+        const size_t row = W * (plane_kinds[planes[k].kind].per_tile / 1024) * plane_kinds[planes[k].kind].elem;
+        if (planes[k].host_stride)
+            HIP_TRY(hipMemcpy2DAsync(planes[k].host, planes[k].host_stride, f[k], row, row, H, hipMemcpyDeviceToHost, d0.stream));
+        else
+            HIP_TRY(hipMemcpyAsync(planes[k].host, f[k], row * H, hipMemcpyDeviceToHost, d0.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(d0.stream));
+    return PT_OK;
+}
 
 }  // namespace
 
@@ -2489,127 +2553,23 @@ int32_t pt_step(pt_ctx *ctx, int32_t nspp, int32_t *done_spp) {
     return PT_OK;
 }
 
-// gathers every device's tiles on device 0, untiles, copies to host
+// the frame so far: rgba (always gathered; copied when asked for), the sums, the per-pixel counters
 static int32_t read_frame(pt_ctx *ctx, uint8_t *rgba, int32_t stride, double *accum, uint32_t *nseg, uint32_t *ndraw) {
     Frame &fr = ctx->frame;
-    const int32_t W = fr.cfg.width, H = fr.cfg.height;
-    if (rgba && stride < W * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
-    const int32_t ndev = (int32_t)ctx->devs.size();
-    const size_t ntiles = (size_t)fr.ntx * (size_t)fr.nty;
+    if (rgba && stride < fr.cfg.width * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
     const bool want_stats = fr.stats_on && (nseg || ndraw);
-    Device &d0 = ctx->devs[0];
-    HIP_TRY(hipSetDevice(d0.ordinal));
-    HIP_TRY(ctx->g_tiles_rgba.reserve(ntiles * 4096));
-    if (accum) HIP_TRY(ctx->g_tiles_accum.reserve(ntiles * 1024 * 3));
-    if (want_stats) {
-        HIP_TRY(ctx->g_tiles_seg.reserve(ntiles * 1024));
-        HIP_TRY(ctx->g_tiles_draw.reserve(ntiles * 1024));
-    }
     const int32_t spp_done = fr.done_spp;
-    size_t before = 0;
-    for (int32_t i = 0; i < ndev; i++) {
-        Device &d = ctx->devs[(size_t)i];
-        if (d.nlocal == 0) continue;
-        const size_t nt = (size_t)d.nlocal;
-        if (i == 0 && !ctx->rccl.lib) {
-            // device 0 resolves straight into the gather buffer
-            if (int32_t rc = dev_finish(ctx, d, spp_done, ctx->g_tiles_rgba.p + before * 4096,
-                                        accum ? ctx->g_tiles_accum.p + before * 3072 : nullptr,
-                                        want_stats ? ctx->g_tiles_seg.p + before * 1024 : nullptr,
-                                        want_stats ? ctx->g_tiles_draw.p + before * 1024 : nullptr))
-                return rc;
-        } else {
-            HIP_TRY(hipSetDevice(d.ordinal));
-            HIP_TRY(d.tiles_rgba.reserve(nt * 4096));
-            if (accum) HIP_TRY(d.tiles_accum.reserve(nt * 3072));
-            if (want_stats) {
-                HIP_TRY(d.tiles_seg.reserve(nt * 1024));
-                HIP_TRY(d.tiles_draw.reserve(nt * 1024));
-            }
-            if (int32_t rc = dev_finish(ctx, d, spp_done, d.tiles_rgba.p, accum ? d.tiles_accum.p : nullptr,
-                                        want_stats ? d.tiles_seg.p : nullptr, want_stats ? d.tiles_draw.p : nullptr))
-                return rc;
-            if (ctx->rccl.lib) {  // the exchange itself follows the loop, all devices in one RCCL group
-                before += nt;
-                continue;
-            }
-            // gather over xGMI: peer DMA into device 0's buffer, ordered on the source stream
-            HIP_TRY(hipMemcpyPeerAsync(ctx->g_tiles_rgba.p + before * 4096, d0.ordinal, d.tiles_rgba.p, d.ordinal,
-                                       nt * 4096, d.stream));
-            if (accum)
-                HIP_TRY(hipMemcpyPeerAsync(ctx->g_tiles_accum.p + before * 3072, d0.ordinal, d.tiles_accum.p, d.ordinal,
-                                           nt * 3072 * sizeof(double), d.stream));
-            if (want_stats) {
-                HIP_TRY(hipMemcpyPeerAsync(ctx->g_tiles_seg.p + before * 1024, d0.ordinal, d.tiles_seg.p, d.ordinal,
-                                           nt * 1024 * sizeof(uint32_t), d.stream));
-                HIP_TRY(hipMemcpyPeerAsync(ctx->g_tiles_draw.p + before * 1024, d0.ordinal, d.tiles_draw.p, d.ordinal,
-                                           nt * 1024 * sizeof(uint32_t), d.stream));
-            }
-        }
-        before += nt;
-    }
-    if (ctx->rccl.lib) {
-        // RCCL gather of the per-tile framebuffers: every device (devices[0] too: its own share travels the same way) sends its
-        // tiles to rank 0 on its stream, rank 0 posts the matching receives on its stream -- one group, so that the sends and
-        // receives of this one process pair up without deadlock (ncclGather is this same pattern; the counts differ per rank here)
-        const pt_ctx::Rccl &R = ctx->rccl;
-        RCCL_TRY(R.GroupStart());
-        size_t off = 0;
-        for (int32_t i = 0; i < ndev; i++) {
-            Device &d = ctx->devs[(size_t)i];
-            if (d.nlocal == 0) continue;
-            const size_t nt = (size_t)d.nlocal;
-            RCCL_TRY(R.Send(d.tiles_rgba.p, nt * 4096, ncclUint8, 0, R.comms[(size_t)i], d.stream));
-            RCCL_TRY(R.Recv(ctx->g_tiles_rgba.p + off * 4096, nt * 4096, ncclUint8, i, R.comms[0], d0.stream));
-            if (accum) {
-                RCCL_TRY(R.Send(d.tiles_accum.p, nt * 3072, ncclDouble, 0, R.comms[(size_t)i], d.stream));
-                RCCL_TRY(R.Recv(ctx->g_tiles_accum.p + off * 3072, nt * 3072, ncclDouble, i, R.comms[0], d0.stream));
-            }
-            if (want_stats) {
-                RCCL_TRY(R.Send(d.tiles_seg.p, nt * 1024, ncclUint32, 0, R.comms[(size_t)i], d.stream));
-                RCCL_TRY(R.Recv(ctx->g_tiles_seg.p + off * 1024, nt * 1024, ncclUint32, i, R.comms[0], d0.stream));
-                RCCL_TRY(R.Send(d.tiles_draw.p, nt * 1024, ncclUint32, 0, R.comms[(size_t)i], d.stream));
-                RCCL_TRY(R.Recv(ctx->g_tiles_draw.p + off * 1024, nt * 1024, ncclUint32, i, R.comms[0], d0.stream));
-            }
-            off += nt;
-        }
-        RCCL_TRY(R.GroupEnd());
-        ctx->rccl.gathers++;
-    }
-    for (int32_t i = 1; i < ndev; i++) {
-        HIP_TRY(hipSetDevice(ctx->devs[(size_t)i].ordinal));
-        HIP_TRY(hipStreamSynchronize(ctx->devs[(size_t)i].stream));
-    }
-    HIP_TRY(hipSetDevice(d0.ordinal));
-    HIP_TRY(ctx->f_rgba.reserve((size_t)W * H * 4));
-    if (accum) HIP_TRY(ctx->f_accum.reserve((size_t)W * H * 3));
-    if (want_stats) {
-        HIP_TRY(ctx->f_seg.reserve((size_t)W * H));
-        HIP_TRY(ctx->f_draw.reserve((size_t)W * H));
-    }
-    ptk::UntileArgs U;
-    std::memset(&U, 0, sizeof U);
-    U.tiles_rgba = ctx->g_tiles_rgba.p;
-    U.tiles_accum = accum ? ctx->g_tiles_accum.p : nullptr;
-    U.tiles_u32a = want_stats ? ctx->g_tiles_seg.p : nullptr;
-    U.tiles_u32b = want_stats ? ctx->g_tiles_draw.p : nullptr;
-    U.rgba = ctx->f_rgba.p;
-    U.accum = accum ? ctx->f_accum.p : nullptr;
-    U.u32a = want_stats ? ctx->f_seg.p : nullptr;
-    U.u32b = want_stats ? ctx->f_draw.p : nullptr;
-    U.width = W; U.height = H; U.ntx = fr.ntx; U.nty = fr.nty; U.stride = W * 4; U.shard_count = ndev;
-    hipLaunchKernelGGL(ptk::untile_kernel, dim3((unsigned)fr.ntx, (unsigned)fr.nty, 4), dim3(PT_BLOCK), 0, d0.stream, U);
-    HIP_TRY(hipGetLastError());
-    if (rgba)
-        HIP_TRY(hipMemcpy2DAsync(rgba, (size_t)stride, ctx->f_rgba.p, (size_t)W * 4, (size_t)W * 4, (size_t)H,
-                                 hipMemcpyDeviceToHost, d0.stream));
-    if (accum)
-        HIP_TRY(hipMemcpyAsync(accum, ctx->f_accum.p, (size_t)W * H * 3 * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
-    if (want_stats && nseg)
-        HIP_TRY(hipMemcpyAsync(nseg, ctx->f_seg.p, (size_t)W * H * sizeof(uint32_t), hipMemcpyDeviceToHost, d0.stream));
-    if (want_stats && ndraw)
-        HIP_TRY(hipMemcpyAsync(ndraw, ctx->f_draw.p, (size_t)W * H * sizeof(uint32_t), hipMemcpyDeviceToHost, d0.stream));
-    HIP_TRY(hipStreamSynchronize(d0.stream));
+    const Plane planes[] = {
+        {true, PLANE_RGBA, reserved<Device, &Device::tiles_rgba>, reserved<pt_ctx, &pt_ctx::g_tiles_rgba>, reserved<pt_ctx, &pt_ctx::f_rgba>, rgba, (size_t)stride},
+        {accum != nullptr, PLANE_F64X3, reserved<Device, &Device::tiles_accum>, reserved<pt_ctx, &pt_ctx::g_tiles_accum>, reserved<pt_ctx, &pt_ctx::f_accum>, accum, 0},
+        {want_stats, PLANE_U32A, reserved<Device, &Device::tiles_seg>, reserved<pt_ctx, &pt_ctx::g_tiles_seg>, reserved<pt_ctx, &pt_ctx::f_seg>, nseg, 0},
+        {want_stats, PLANE_U32B, reserved<Device, &Device::tiles_draw>, reserved<pt_ctx, &pt_ctx::g_tiles_draw>, reserved<pt_ctx, &pt_ctx::f_draw>, ndraw, 0}};
+    if (int32_t rc = gather_planes(ctx, planes, [&](Device &d, void *const *dst) {
+            return dev_finish(ctx, d, spp_done, static_cast<uint8_t *>(dst[0]), static_cast<double *>(dst[1]), static_cast<uint32_t *>(dst[2]),
+                              static_cast<uint32_t *>(dst[3]));
+        }))
+        return rc;
+    if (ctx->rccl.lib) ctx->rccl.gathers++;
     return PT_OK;
 }
 
@@ -2638,10 +2598,7 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
         size_t launches = 0;
         for (Device &d : ctx->devs) {
             double ms = 0;
-            for (size_t k = 0; k < d.n_moments && hipSetDevice(d.ordinal) == hipSuccess; k++) {
-                float m = 0;
-                if (hipEventElapsedTime(&m, d.ev_moments[k].a, d.ev_moments[k].b) == hipSuccess) ms += m;
-            }
+            if (hipSetDevice(d.ordinal) == hipSuccess) (void)sum_ms(d.ev_moments, d.n_moments, ms);
             mm = std::max(mm, ms);
             launches += d.n_moments;
         }
@@ -2653,10 +2610,7 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
         size_t launches = 0;
         for (Device &d : ctx->devs) {
             double ms = 0;
-            for (size_t k = 0; k < d.n_check && hipSetDevice(d.ordinal) == hipSuccess; k++) {
-                float m = 0;
-                if (hipEventElapsedTime(&m, d.ev_check[k].a, d.ev_check[k].b) == hipSuccess) ms += m;
-            }
+            if (hipSetDevice(d.ordinal) == hipSuccess) (void)sum_ms(d.ev_check, d.n_check, ms);
             cm = std::max(cm, ms);
             launches += d.n_check;
         }
@@ -2772,111 +2726,27 @@ int32_t pt_adaptive_state(pt_ctx *ctx, struct pt_adaptive_state *out) {
     return PT_OK;
 }
 
-// the counts plane: per device tile-major (counts_tiles_kernel), gathered on device 0 by peer copies, through untile_kernel's u32a plane
+// the counts plane: per device tile-major by counts_tiles_kernel, through untile_kernel's u32a plane (the buffers of read_frame's nseg)
 int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp) {
     if (!ctx || !spp) return fail(PT_ERR_INVALID, "null argument");
     if (int32_t rc = adaptive_frame(ctx, "pt_read_sample_counts")) return rc;
-    Frame &fr = ctx->frame;
-    const int32_t W = fr.cfg.width, H = fr.cfg.height;
-    const int32_t ndev = (int32_t)ctx->devs.size();
-    const size_t ntiles = (size_t)fr.ntx * (size_t)fr.nty;
-    Device &d0 = ctx->devs[0];
-    HIP_TRY(hipSetDevice(d0.ordinal));
-    HIP_TRY(ctx->g_tiles_seg.reserve(ntiles * 1024));
-    size_t before = 0;
-    for (int32_t i = 0; i < ndev; i++) {
-        Device &d = ctx->devs[(size_t)i];
-        if (d.nlocal == 0) continue;
-        const size_t nt = (size_t)d.nlocal;
-        HIP_TRY(hipSetDevice(d.ordinal));
-        uint32_t *dst = ctx->g_tiles_seg.p + before * 1024;
-        if (i != 0) {
-            HIP_TRY(d.tiles_seg.reserve(nt * 1024));
-            dst = d.tiles_seg.p;
-        }
-        hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p, dst, d.nslots, W, H,
-                           fr.ntx, d.shard.index, d.shard.count);
+    const Plane planes[] = {
+        {true, PLANE_U32A, reserved<Device, &Device::tiles_seg>, reserved<pt_ctx, &pt_ctx::g_tiles_seg>, reserved<pt_ctx, &pt_ctx::f_seg>, spp, 0}};
+    return gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
+        hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p,
+                           static_cast<uint32_t *>(dst[0]), d.nslots, tile_geom(ctx->frame, d));
         HIP_TRY(hipGetLastError());
-        if (i != 0)
-            HIP_TRY(hipMemcpyPeerAsync(ctx->g_tiles_seg.p + before * 1024, d0.ordinal, d.tiles_seg.p, d.ordinal, nt * 1024 * sizeof(uint32_t), d.stream));
-        before += nt;
-    }
-    for (int32_t i = 1; i < ndev; i++) {
-        HIP_TRY(hipSetDevice(ctx->devs[(size_t)i].ordinal));
-        HIP_TRY(hipStreamSynchronize(ctx->devs[(size_t)i].stream));
-    }
-    HIP_TRY(hipSetDevice(d0.ordinal));
-    HIP_TRY(ctx->f_seg.reserve((size_t)W * H));
-    ptk::UntileArgs U;
-    std::memset(&U, 0, sizeof U);
-    U.tiles_u32a = ctx->g_tiles_seg.p;
-    U.u32a = ctx->f_seg.p;
-    U.width = W; U.height = H; U.ntx = fr.ntx; U.nty = fr.nty; U.stride = W * 4; U.shard_count = ndev;
-    hipLaunchKernelGGL(ptk::untile_kernel, dim3((unsigned)fr.ntx, (unsigned)fr.nty, 4), dim3(PT_BLOCK), 0, d0.stream, U);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(spp, ctx->f_seg.p, (size_t)W * H * sizeof(uint32_t), hipMemcpyDeviceToHost, d0.stream));
-    HIP_TRY(hipStreamSynchronize(d0.stream));
-    return PT_OK;
+        return PT_OK;
+    });
 }
 
-// as read_frame: every device's tiles gathered on device 0 (peer copies, or the grouped RCCL exchange), untiled, copied to the host
+// the second moments, in the layout of accum
 int32_t pt_read_moments(pt_ctx *ctx, double *m2) {
     if (!ctx || !m2) return fail(PT_ERR_INVALID, "null argument");
     if (int32_t rc = moments_frame(ctx, "pt_read_moments")) return rc;
-    Frame &fr = ctx->frame;
-    const int32_t W = fr.cfg.width, H = fr.cfg.height;
-    const int32_t ndev = (int32_t)ctx->devs.size();
-    const size_t ntiles = (size_t)fr.ntx * (size_t)fr.nty;
-    Device &d0 = ctx->devs[0];
-    HIP_TRY(hipSetDevice(d0.ordinal));
-    HIP_TRY(ctx->g_tiles_m2.reserve(ntiles * 3072));
-    size_t before = 0;
-    for (int32_t i = 0; i < ndev; i++) {
-        Device &d = ctx->devs[(size_t)i];
-        if (d.nlocal == 0) continue;
-        const size_t nt = (size_t)d.nlocal;
-        if (i == 0 && !ctx->rccl.lib) {
-            if (int32_t rc = dev_finish_moments(ctx, d, ctx->g_tiles_m2.p + before * 3072)) return rc;
-        } else {
-            HIP_TRY(hipSetDevice(d.ordinal));
-            HIP_TRY(d.tiles_m2.reserve(nt * 3072));
-            if (int32_t rc = dev_finish_moments(ctx, d, d.tiles_m2.p)) return rc;
-            if (!ctx->rccl.lib)
-                HIP_TRY(hipMemcpyPeerAsync(ctx->g_tiles_m2.p + before * 3072, d0.ordinal, d.tiles_m2.p, d.ordinal,
-                                           nt * 3072 * sizeof(double), d.stream));
-        }
-        before += nt;
-    }
-    if (ctx->rccl.lib) {
-        const pt_ctx::Rccl &R = ctx->rccl;
-        RCCL_TRY(R.GroupStart());
-        size_t off = 0;
-        for (int32_t i = 0; i < ndev; i++) {
-            Device &d = ctx->devs[(size_t)i];
-            if (d.nlocal == 0) continue;
-            const size_t nt = (size_t)d.nlocal;
-            RCCL_TRY(R.Send(d.tiles_m2.p, nt * 3072, ncclDouble, 0, R.comms[(size_t)i], d.stream));
-            RCCL_TRY(R.Recv(ctx->g_tiles_m2.p + off * 3072, nt * 3072, ncclDouble, i, R.comms[0], d0.stream));
-            off += nt;
-        }
-        RCCL_TRY(R.GroupEnd());
-    }
-    for (int32_t i = 1; i < ndev; i++) {
-        HIP_TRY(hipSetDevice(ctx->devs[(size_t)i].ordinal));
-        HIP_TRY(hipStreamSynchronize(ctx->devs[(size_t)i].stream));
-    }
-    HIP_TRY(hipSetDevice(d0.ordinal));
-    HIP_TRY(ctx->f_m2.reserve((size_t)W * H * 3));
-    ptk::UntileArgs U;
-    std::memset(&U, 0, sizeof U);
-    U.tiles_accum = ctx->g_tiles_m2.p;  // the layout of tiles_accum
-    U.accum = ctx->f_m2.p;
-    U.width = W; U.height = H; U.ntx = fr.ntx; U.nty = fr.nty; U.stride = W * 4; U.shard_count = ndev;
-    hipLaunchKernelGGL(ptk::untile_kernel, dim3((unsigned)fr.ntx, (unsigned)fr.nty, 4), dim3(PT_BLOCK), 0, d0.stream, U);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(m2, ctx->f_m2.p, (size_t)W * H * 3 * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
-    HIP_TRY(hipStreamSynchronize(d0.stream));
-    return PT_OK;
+    const Plane planes[] = {
+        {true, PLANE_F64X3, reserved<Device, &Device::tiles_m2>, reserved<pt_ctx, &pt_ctx::g_tiles_m2>, reserved<pt_ctx, &pt_ctx::f_m2>, m2, 0}};
+    return gather_planes(ctx, planes, [&](Device &d, void *const *dst) { return dev_finish_moments(ctx, d, static_cast<double *>(dst[0])); });
 }
 
 int32_t pt_noise_estimate(pt_ctx *ctx, pt_noise *out) {
@@ -2906,11 +2776,7 @@ int32_t pt_noise_estimate(pt_ctx *ctx, pt_noise *out) {
         A.partial = d.noise_part.p;
         A.nslots = d.nslots;
         A.n = fr.done_spp;
-        A.width = fr.cfg.width;
-        A.height = fr.cfg.height;
-        A.ntx = fr.ntx;
-        A.shard_index = d.shard.index;
-        A.shard_count = d.shard.count;
+        A.G = tile_geom(fr, d);
         if (fr.adaptive) hipLaunchKernelGGL(ptk::noise_adaptive_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A, d.blk_spp.p);  // every pixel with its own n
         else hipLaunchKernelGGL(ptk::noise_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A);
         HIP_TRY(hipGetLastError());

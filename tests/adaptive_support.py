@@ -122,3 +122,57 @@ def check_self_consistent(ctx, sc, w, h, cap, depth, seed, target, step, min_spp
         assert np.array_equal(bits(acc)[sel], bits(pa)[sel]), ("accum", n)
         assert np.array_equal(bits(m2)[sel], bits(pm)[sel]), ("m2", n)
     return counts, st
+
+
+# ---------------------------------------------------------------- the gather check (one tile map, one gather)
+GATHER_W, GATHER_H, GATHER_SPP = 70, 45, 8  # 3 x 2 tiles, ragged on both edges; 6 tiles = 2, 2, 1, 1 on four devices, none for the seventh
+GATHER_PLANES = ("rgba", "accum", "nseg", "ndraw", "m2", "ad_rgba", "ad_accum", "ad_nseg", "ad_ndraw", "ad_m2", "ad_counts")
+_gather_ref = []
+
+
+def gather_frames(ctx, sc=None) -> dict:
+    """Every plane a context gathers, of two frames of the case's scene at 70 x 45 with pixel stats and moments on: a plain frame of 8
+    samples, and the case's adaptive frame (its cap, step and target), whose blocks must end with different counts and some of them
+    active.  Also the pt_noise_estimate fields of both ("noise", "ad_noise") and the adaptive frame's pt_adaptive_state ("ad_state")."""
+    from conftest import scene_path
+    from path_trace_golang_amd import capi, hip, scene
+
+    name, depth, seed, cap, step, min_spp, target = CASE
+    w, h = GATHER_W, GATHER_H
+    sc = sc or scene.load(scene_path(name))
+    d = {"rgba": np.zeros((h, w, 4), np.uint8), "accum": np.zeros((h, w, 3)), "m2": np.zeros((h, w, 3)),
+         "nseg": np.zeros((h, w), np.uint32), "ndraw": np.zeros((h, w), np.uint32)}
+    hip.render(sc, hip.RenderConfig(w, h, GATHER_SPP, depth, seed, 0, capi.PT_FLAG_PIXEL_STATS), d["rgba"], None, d["accum"], d["nseg"],
+               d["ndraw"], ctx=ctx, moments=d["m2"])
+    d["noise"] = hip.noise_estimate(ctx)
+    (d["ad_rgba"], d["ad_accum"], d["ad_m2"], d["ad_counts"], d["ad_nseg"], d["ad_ndraw"], st) = render_adaptive(
+        ctx, sc, w, h, cap, depth, seed, target, step, min_spp, flags=capi.PT_FLAG_PIXEL_STATS)
+    d["ad_noise"] = hip.noise_estimate(ctx)
+    d["ad_state"] = st["adaptive"]
+    # the target stops some blocks and not others
+    assert d["ad_counts"].min() < cap and 0 < d["ad_state"]["active_blocks"] < d["ad_state"]["blocks"] == 54, d["ad_state"]
+    assert d["nseg"].min() > 0 and np.all(d["m2"] >= 0) and np.any(d["m2"] > 0)
+    return d
+
+
+def gather_reference() -> dict:
+    """gather_frames of a one-device context that gathers by itself (no PTCORE_GATHER), made once per process and read-only."""
+    import os
+
+    from path_trace_golang_amd import capi
+
+    if not _gather_ref:
+        assert "PTCORE_GATHER" not in os.environ
+        with capi.Context(ndev=1) as ctx:
+            d = gather_frames(ctx)
+        for k in GATHER_PLANES:
+            d[k].setflags(write=False)
+        _gather_ref.append(d)
+    return _gather_ref[0]
+
+
+def assert_same_planes(got: dict, ref: dict, tag=""):
+    for k in GATHER_PLANES:
+        a, b = got[k], ref[k]
+        assert a.dtype == b.dtype and a.shape == b.shape, (tag, k)
+        assert np.array_equal(a.view(np.uint64) if a.dtype == np.float64 else a, b.view(np.uint64) if b.dtype == np.float64 else b), (tag, k)

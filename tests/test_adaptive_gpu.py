@@ -156,6 +156,46 @@ def test_target_zero_is_the_plain_frame_and_a_huge_target_stops_at_the_first_che
         assert np.all(counts == 2)   # one sample gives no variance estimate
 
 
+def test_the_check_and_the_frame_noise_share_one_metric():
+    """block_noise_kernel (through compact_kernel: pt_adaptive_state's worst_active) and noise_kernel (pt_noise_estimate's max_pixel)
+    against noise_estimate_host's per-pixel e2 of the frame's own sums, after each of two steps of a frame whose blocks all stay
+    active (target 0): the largest block noise, and the largest pixel.  The tolerance is test_noise_estimate_matches_the_host_formula's."""
+    from path_trace_golang_amd import capi, hip
+
+    name, depth, seed, _, step, min_spp, _ = ad.CASE
+    w, h = ad.GATHER_W, ad.GATHER_H
+    L = capi.load()
+    flat = hip.FlatScene(_scene(name))
+    pc = hip.pt_config(hip.RenderConfig(w, h, 2 * step, depth, seed))
+    img = np.zeros((h, w, 4), np.uint8)
+    acc = np.zeros((h, w, 3))
+    m2 = np.zeros((h, w, 3))
+    done = C.c_int32(0)
+    with capi.Context(ndev=1) as ctx:
+        hip.set_adaptive(ctx, 0.0, min_spp, step)
+        capi.check(L.pt_begin(ctx.handle, C.byref(flat.c), C.byref(pc)))
+        for k in (1, 2):
+            capi.check(L.pt_step(ctx.handle, step, C.byref(done)))
+            n = done.value
+            assert n == k * step
+            capi.check(L.pt_read(ctx.handle, img.ctypes.data_as(C.c_void_p), w * 4, acc.ctypes.data_as(C.c_void_p)))
+            hip.read_moments(ctx, m2)
+            state = hip.adaptive_state(ctx)
+            nz = hip.noise_estimate(ctx)
+            assert state["active_blocks"] == state["blocks"] == 54 and nz["bad_pixels"] == 0
+            block, pixel = [], []
+            for y in range(0, h, 8):
+                for x in range(0, w, 8):
+                    b = hip.noise_estimate_host(acc[y:y + 8, x:x + 8], m2[y:y + 8, x:x + 8], n)  # noise = sqrt(sum of e2 / the block's pixels)
+                    block.append(b["noise"])
+                    pixel.append(b["max_pixel"])
+            print("n = %d: worst_active %.17g (host %.17g), max_pixel %.17g (host %.17g)" % (n, state["worst_active"], max(block),
+                                                                                             nz["max_pixel"], max(pixel)))
+            assert max(block) > 0 and abs(state["worst_active"] - max(block)) <= 1e-9 * max(block)
+            assert abs(nz["max_pixel"] - max(pixel)) <= 1e-9 * max(pixel)
+        capi.check(L.pt_end(ctx.handle, None))
+
+
 # ---------------------------------------------------------------- 3. self-consistency
 @pytest.mark.parametrize("chunk", [3, 5])
 def test_the_map_does_not_depend_on_the_chunk(case_ref, chunk):

@@ -218,6 +218,21 @@ def test_moments_on_two_virtual_devices(inv_ref):
     assert (nz["max_pixel"], nz["pixels"], nz["bad_pixels"], nz["spp"]) == (ref["max_pixel"], 960, 0, n)
 
 
+@pytest.mark.parametrize("ndev", [4, 7], ids=["2+2+1+1 tiles", "a device without a tile"])
+def test_uneven_shards_gather_the_planes_of_one_device(ndev):
+    """70 x 45 = 6 tiles over 4 and over 7 virtual devices (peer copies of unequal length, and none at all from the seventh): every
+    plane a context gathers -- rgba, the sums, the counters, the second moments, the sample counts of an adaptive frame -- has the
+    bits of the one-device context's."""
+    import adaptive_support as ad
+    from path_trace_golang_amd import capi
+
+    ref = ad.gather_reference()
+    with capi.Context(devices=[0] * ndev) as ctx:
+        got = ad.gather_frames(ctx)
+    ad.assert_same_planes(got, ref, ndev)
+    assert got["ad_state"]["active_blocks"] == ref["ad_state"]["active_blocks"] and got["ad_state"]["samples"] == ref["ad_state"]["samples"]
+
+
 # ---------------------------------------------------------------- 5. the noise figure
 def test_noise_estimate_matches_the_host_formula(inv_ref):
     from path_trace_golang_amd import capi, hip

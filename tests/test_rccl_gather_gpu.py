@@ -30,6 +30,26 @@ def test_one_rank_rccl_gather_gives_the_oracle_frame(monkeypatch, oracle):
         assert L.pt_debug_gather_mode(ctx.handle) == 0
 
 
+def test_every_plane_travels_through_rccl_as_it_does_without(monkeypatch):
+    """rgba, the sums, both counter planes, the second moments and the sample counts of an adaptive frame, gathered through the
+    one-rank group and by the context itself: the same bits, and the same pt_noise_estimate and pt_adaptive_state."""
+    import torch  # noqa: F401  (as above)
+
+    import adaptive_support as ad
+    from path_trace_golang_amd import capi
+
+    L = capi.load()
+    monkeypatch.setenv("PTCORE_GATHER", "rccl")
+    with capi.Context(ndev=1) as ctx:
+        assert L.pt_debug_gather_mode(ctx.handle) == 1
+        got = ad.gather_frames(ctx)
+    monkeypatch.delenv("PTCORE_GATHER")
+    ref = ad.gather_reference()
+    ad.assert_same_planes(got, ref, "rccl")
+    assert got["noise"] == ref["noise"] and got["ad_noise"] == ref["ad_noise"] and got["ad_state"] == ref["ad_state"]
+    assert ref["noise"]["pixels"] == 70 * 45 and ref["noise"]["spp"] == 8 and ref["noise"]["bad_pixels"] == 0
+
+
 def test_rccl_refuses_one_gpu_listed_twice_and_bad_values_are_errors(monkeypatch):
     from path_trace_golang_amd import capi
 
