@@ -55,28 +55,108 @@ int32_t fail(int32_t code, const std::string &msg) {
             return fail(PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
     } while (0)
 
+// Set by pt_destroy while it lets go of memory and events whose device could not be made current: they are left alone then, as they
+// always were, not freed under another device.
+thread_local bool g_leave_device_memory = false;
+
+// (untyped, for DevBuf and for the rows of pass_plan)
+void dev_release(void **p, size_t *cap) {
+    if (*p && !g_leave_device_memory) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+}
+hipError_t dev_reserve(void **p, size_t *cap, size_t n, size_t size) {
+    if (n <= *cap) return hipSuccess;
+    dev_release(p, cap);
+    hipError_t e = hipMalloc(p, n * size);
+    if (e == hipSuccess) *cap = n;
+    return e;
+}
+
+// Device memory that grows on request and frees itself: move-only, and a move-assignment hands the old memory to the source, which
+// frees it when it dies.  Its device must be current then (pt_destroy sees to that).
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;  // elements
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }
+    ~DevBuf() { release(); }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }
+    hipError_t reserve(size_t n) { return dev_reserve(reinterpret_cast<void **>(&p), &cap, n, sizeof(T)); }
+    void release() { dev_release(reinterpret_cast<void **>(&p), &cap); }
+};
+
+// The per-pass buffers of a device, the one list of them (pass_plan): what need_bytes() prices, what dev_begin reserves (and releases
+// when the device is short of memory) and what dev_held_bytes() adds up all follow from it.  A row is one buffer and does not depend on
+// the frame: what its length goes by, its elements of `size` bytes per job or per queue entry (`elems_stats` more with pixel stats),
+// and the forms of the loop that use it.  (wf_bins, of fixed size, is not here.)
+enum PassPer {
+    PER_JOB,    // the jobs of a pass: pixel slots x samples
+    PER_ENTRY,  // the entries of a path-state queue: one per job + queue_slack()
+    PER_EXTRA   // the same, for what rides along with the queues (dev_begin's first guess at a pass that fits leaves these out)
+};
+enum PassWhen : unsigned { WHEN_Q_GLASS = 1, WHEN_Q_CONT = 2, WHEN_Q_PATH_B = 4, WHEN_WF_SORT = 8, WHEN_WALK32 = 16 };  // 0: every frame
+struct PassBuf {
+    void **p;     // the DevBuf's pointer and capacity
+    size_t *cap;
+    size_t size;
+    PassPer per;
+    size_t elems, elems_stats;
+    unsigned when;
+    template <typename T>
+    PassBuf(DevBuf<T> &b, PassPer per_, size_t elems_, size_t elems_stats_, unsigned when_)
+        : p(reinterpret_cast<void **>(&b.p)), cap(&b.cap), size(sizeof(T)), per(per_), elems(elems_), elems_stats(elems_stats_), when(when_) {}
+    // elements per job / entry in a frame of the forms `have` (frame_forms): 0 = the frame does not use the buffer
+    size_t used(unsigned have, bool stats) const { return (when & ~have) ? 0 : elems + (stats ? elems_stats : 0); }
 };
 
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
+};
+
+// The event pairs of one kind of timed launch (timed, sum_ms): made when first needed, used again by every frame; the first n are
+// those of the running frame.  Owns its events the way DevBuf owns its memory.
+struct EventList {
+    std::vector<EventPair> v;
+    size_t n = 0;
+    EventList() = default;
+    EventList(EventList &&o) noexcept { swap(o); }
+    EventList &operator=(EventList &&o) noexcept { swap(o); return *this; }
+    ~EventList() {
+        if (g_leave_device_memory) return;
+        for (EventPair &e : v) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+    }
+    void swap(EventList &o) { v.swap(o.v); std::swap(n, o.n); }
+};
+enum EventKind { EV_TRACE, EV_RESOLVE, EV_RAYGEN, EV_GLASS, EV_FOG, EV_MOMENTS, EV_CHECK, EV_KINDS };
+
+// Storage of one path-state queue (PathQueue, pt_device.h): per entry 10 doubles, the stream state and 4 words -- job, depth, hit
+// object, answer -- or 6 with pixel stats (+ the job's two counters); every plane of `u` is as long as the queue.
+struct QueueBuf {
+    DevBuf<double> d;
+    DevBuf<unsigned long long> rs;
+    DevBuf<uint32_t> u;
+    // its rows of pass_plan: 80 + 8 + 4 x 4 = 104 B per entry, 112 B with pixel stats
+    void plan(std::vector<PassBuf> &rows, unsigned when) {
+        rows.insert(rows.end(), {{d, PER_ENTRY, 10, 0, when}, {rs, PER_ENTRY, 1, 0, when}, {u, PER_ENTRY, 4, 2, when}});
+    }
+    // the queue as the kernels take it: `cap` entries (what the buffers were reserved for), appended at *count
+    PathQueue bind(size_t cap, bool stats, unsigned int *count) const {
+        PathQueue q{};
+        q.d = d.p;
+        q.rs = rs.p;
+        q.job = u.p;
+        q.depth = reinterpret_cast<int32_t *>(u.p + cap);
+        q.best = reinterpret_cast<int32_t *>(u.p + 2 * cap);
+        q.hit = reinterpret_cast<int32_t *>(u.p + 3 * cap);
+        q.jseg = stats ? u.p + 4 * cap : nullptr;
+        q.jdraw = stats ? u.p + 5 * cap : nullptr;
+        q.count = count;
+        q.cap = (uint32_t)cap;
+        return q;
+    }
 };
 
 // One device's share of a frame.
@@ -119,13 +199,9 @@ struct Device {
     DevBuf<unsigned int> queue;       // [0] item cursor of the running trace pass, [1] glass count, [2],[3] continuation counts (ping-pong), [4] always 0
     DevBuf<BroadSphere> bsph_diel;    // broad-phase records of the dielectric objects only
     DevBuf<BroadBox> bbox_diel;
-    // path-state queues of the split passes (one entry per job of a chunk at most)
-    DevBuf<double> gq_d, cq_d;
-    DevBuf<unsigned long long> gq_rs, cq_rs;
-    DevBuf<uint32_t> gq_u32, cq_u32;  // job, depth, best, hit, jseg, jdraw planes
-    DevBuf<double> xq_d;              // third queue of the wavefront form (gq = exit queue, cq / xq = the two path queues)
-    DevBuf<unsigned long long> xq_rs;
-    DevBuf<uint32_t> xq_u32;
+    // path-state queues (one entry per job of a chunk at most, + queue_slack): the split form's glass queue = the wavefront form's
+    // exit queue; the continuation queue = the wavefront form's path queue A; its path queue B
+    QueueBuf q_glass, q_cont, q_path_b;
     int blocks_per_cu_wf = 0;
     int blocks_per_cu_walk = 0;        // wf_walk32_kernel (PTCORE_PIPELINE=walk32)
     DevBuf<uint32_t> cand_ids, cand_n, slow_list;  // walk32: candidate lists of the running level, entries left to the FP64 traversal
@@ -133,8 +209,7 @@ struct Device {
     size_t q_cap = 0;
     DevBuf<unsigned long long> counters;
     DevBuf<unsigned long long> prof;
-    std::vector<EventPair> ev_trace, ev_resolve, ev_raygen, ev_glass, ev_fog, ev_moments, ev_check;
-    size_t n_trace = 0, n_resolve = 0, n_raygen = 0, n_glass = 0, n_fog = 0, n_moments = 0, n_check = 0;
+    EventList ev[EV_KINDS];
     DevBuf<ptf::FogLight> fog_lights;        // the frame's light list (fog on)
     DevBuf<unsigned long long> fog_counters; // [3] shadow rays, draws, march steps of the frame
     DevBuf<ptg::GlObj> gl_objs;              // GL shading: the frame's objects, materials and light list
@@ -629,23 +704,49 @@ GlassFn pick_glass(bool stats, int scan) {
     return stats ? glass_kernel<true, false, false> : glass_kernel<false, false, false>;
 }
 
-int32_t dev_events(Device &d, std::vector<EventPair> &v, size_t need) {
-    while (v.size() < need) {
+// The wavefront form's kernels (pt_wavefront.h, pt_walk32.h).  mode: 0 = closest hit, 1 = exit search.  The compiler emits the
+// instantiations in the order this file first names them: the tables stand, and list their kernels, in the order that keeps the code
+// object what it was when dev_begin and dev_step_wavefront named them (profiles/host_plan_kernel_regs.txt).
+using WfFn = void (*)(const ptk::WfArgs);
+using Walk32Fn = void (*)(const ptk::Walk32Args);
+WfFn pick_wf_scan0(bool bvh) { return bvh ? ptk::wf_traverse_kernel<0, false> : ptk::wf_scan_flat_kernel<0, false>; }  // dev_begin's occupancy probe
+Walk32Fn pick_wf_walk32(int mode, bool diag) {
+    if (mode == 0 && !diag) return ptk::wf_walk32_kernel<0>;
+    if (diag) return mode == 0 ? ptk::wf_walk32_kernel<0, true> : ptk::wf_walk32_kernel<1, true>;
+    return ptk::wf_walk32_kernel<1>;
+}
+WfFn pick_wf_traverse(int mode, bool verify) {
+    if (!verify) return mode == 0 ? ptk::wf_traverse_kernel<0, false> : ptk::wf_traverse_kernel<1, false>;
+    return mode == 0 ? ptk::wf_traverse_kernel<0, true> : ptk::wf_traverse_kernel<1, true>;
+}
+WfFn pick_wf_scan_flat(int mode, bool verify) {
+    if (verify) return mode == 0 ? ptk::wf_scan_flat_kernel<0, true> : ptk::wf_scan_flat_kernel<1, true>;
+    return mode == 0 ? ptk::wf_scan_flat_kernel<0, false> : ptk::wf_scan_flat_kernel<1, false>;
+}
+WfFn pick_wf_init(bool stats) { return stats ? ptk::wf_init_kernel<true> : ptk::wf_init_kernel<false>; }
+Walk32Fn pick_wf_shade32(bool stats, bool verify) {
+    return stats ? (verify ? ptk::wf_shade32_kernel<true, true> : ptk::wf_shade32_kernel<true, false>)
+                 : (verify ? ptk::wf_shade32_kernel<false, true> : ptk::wf_shade32_kernel<false, false>);
+}
+WfFn pick_wf_shade(bool stats) { return stats ? ptk::wf_shade_kernel<true> : ptk::wf_shade_kernel<false>; }
+Walk32Fn pick_wf_exit32(bool stats, bool verify) {
+    return stats ? (verify ? ptk::wf_exit32_kernel<true, true> : ptk::wf_exit32_kernel<true, false>)
+                 : (verify ? ptk::wf_exit32_kernel<false, true> : ptk::wf_exit32_kernel<false, false>);
+}
+WfFn pick_wf_exit(bool stats) { return stats ? ptk::wf_exit_kernel<true> : ptk::wf_exit_kernel<false>; }
+
+// One timed launch on d's stream: takes the next event pair of d.ev[kind] (making it if the list is short), records a, runs `launch` --
+// one kernel launch, or several that are timed as one --, checks hipGetLastError and records b.  The pair is v[n - 1] afterwards.
+template <typename Launch>
+int32_t timed(Device &d, EventKind kind, Launch &&launch) {
+    EventList &l = d.ev[kind];
+    if (l.v.size() <= l.n) {
         EventPair e;
         HIP_TRY(hipEventCreate(&e.a));
         HIP_TRY(hipEventCreate(&e.b));
-        v.push_back(e);
+        l.v.push_back(e);
     }
-    (void)d;
-    return PT_OK;
-}
-
-// One timed launch on d's stream: takes the next event pair of `v` (making it if the list is short), records a, runs `launch` -- one kernel
-// launch, or several that are timed as one --, checks hipGetLastError and records b.  The pair is v[n - 1] afterwards.
-template <typename Launch>
-int32_t timed(Device &d, std::vector<EventPair> &v, size_t &n, Launch &&launch) {
-    if (int32_t rc = dev_events(d, v, n + 1)) return rc;
-    const EventPair e = v[n++];
+    const EventPair e = l.v[l.n++];
     HIP_TRY(hipEventRecord(e.a, d.stream));
     launch();
     HIP_TRY(hipGetLastError());
@@ -653,16 +754,43 @@ int32_t timed(Device &d, std::vector<EventPair> &v, size_t &n, Launch &&launch) 
     return PT_OK;
 }
 
-// Milliseconds between a and b, added up over the first n pairs of `v` (their device is current and has finished them); `flagged`: the
-// share of the pairs i with flag[i] set.
-int32_t sum_ms(const std::vector<EventPair> &v, size_t n, double &sum, const std::vector<char> *flag = nullptr, double *flagged = nullptr) {
+// A timed launch of a trace pass (EV_TRACE), marked as the split form or not for pt_stats.trace_split_ms / trace_split_launches.
+template <typename Launch>
+int32_t timed_trace(Device &d, bool split, Launch &&launch) {
+    const size_t i = d.ev[EV_TRACE].n;
+    if (d.trace_is_split.size() <= i) d.trace_is_split.resize(i + 1);
+    d.trace_is_split[i] = split ? 1 : 0;
+    return timed(d, EV_TRACE, launch);
+}
+
+// Milliseconds between a and b, added up over the pairs the frame took from `l` (their device is current and has finished them);
+// `flagged`: the share of the pairs i with flag[i] set.
+int32_t sum_ms(const EventList &l, double &sum, const std::vector<char> *flag = nullptr, double *flagged = nullptr) {
     sum = 0;
-    for (size_t i = 0; i < n; i++) {
+    for (size_t i = 0; i < l.n; i++) {
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, v[i].a, v[i].b));
+        HIP_TRY(hipEventElapsedTime(&ms, l.v[i].a, l.v[i].b));
         sum += ms;
         if (flag && i < flag->size() && (*flag)[i]) *flagged += ms;
     }
+    return PT_OK;
+}
+
+// A host table on device d: room for it (for `room` elements at least, never none: the kernels get a valid pointer for an empty
+// table too) and, unless it is empty, the copy on d's stream.  (Pageable source: the copy is complete when the call returns.)
+template <typename T>
+int32_t upload(Device &d, DevBuf<T> &buf, const std::vector<T> &src, size_t room = 1) {
+    HIP_TRY(buf.reserve(std::max(room, src.size())));
+    if (!src.empty()) HIP_TRY(hipMemcpyAsync(buf.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, d.stream));
+    return PT_OK;
+}
+
+// Blocks of `kernel` that a CU holds with `lds` bytes of dynamic LDS per block: at least 1, at most `cap`.
+template <typename Kernel>
+int32_t occupancy(Kernel kernel, size_t lds, int cap, int &blocks_per_cu) {
+    int nb = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, PT_BLOCK, lds));
+    blocks_per_cu = std::max(1, std::min(nb, cap));
     return PT_OK;
 }
 
@@ -695,11 +823,36 @@ size_t queue_slack(const pt_ctx *ctx, const Device &d, size_t njobs_max) {
     return writer_blocks * (PT_BLOCK / PT_WAVE) * PT_CONT_BLOCK;
 }
 
-// bytes of job buffers a device holds right now
-size_t dev_held_bytes(const Device &d) {
-    return d.L.cap * sizeof(double) + d.ray.cap * sizeof(double) + d.ray_rng.cap * 8 + d.ray_ndraw.cap * 2 + (d.job_seg.cap + d.job_draw.cap) * 4 +
-           (d.gq_d.cap + d.cq_d.cap + d.xq_d.cap) * sizeof(double) + (d.gq_rs.cap + d.cq_rs.cap + d.xq_rs.cap) * 8 +
-           (d.gq_u32.cap + d.cq_u32.cap + d.xq_u32.cap + d.wf_perm.cap + d.wf_key.cap + d.cand_ids.cap + d.cand_n.cap + d.slow_list.cap) * 4;
+// The forms of the loop a frame runs, as far as the per-pass buffers go (PassWhen).  Path-state queues: three in the wavefront
+// form, the continuation queue alone behind the primary pass of the BVH path, glass and continuation queue for the split rounds of
+// a scene with glass.
+unsigned frame_forms(const pt_ctx *ctx) {
+    const Frame &fr = ctx->frame;
+    const unsigned queues = fr.wavefront ? WHEN_Q_GLASS | WHEN_Q_CONT | WHEN_Q_PATH_B : fr.primary_pass ? WHEN_Q_CONT
+                            : (fr.split_rounds > 0 && fr.has_glass) ? WHEN_Q_GLASS | WHEN_Q_CONT : 0u;
+    return queues | (fr.wavefront && ctx->wf_sort ? WHEN_WF_SORT : 0u) | (fr.walk32 ? WHEN_WALK32 : 0u);
+}
+
+std::vector<PassBuf> pass_plan(Device &d) {
+    std::vector<PassBuf> plan = {
+        // 90 B per job: radiance record, primary ray, stream state, draw count; + 8 B with pixel stats
+        {d.L, PER_JOB, 4, 0, 0}, {d.ray, PER_JOB, 6, 0, 0}, {d.ray_rng, PER_JOB, 1, 0, 0}, {d.ray_ndraw, PER_JOB, 1, 0, 0},
+        {d.job_seg, PER_JOB, 0, 1, 0}, {d.job_draw, PER_JOB, 0, 1, 0}};
+    d.q_glass.plan(plan, WHEN_Q_GLASS);
+    d.q_cont.plan(plan, WHEN_Q_CONT);
+    d.q_path_b.plan(plan, WHEN_Q_PATH_B);
+    // ray sorting of the wavefront form: 8 B per entry; walk32: (PT_CAND_MAX + 2) x 4 B per entry
+    plan.insert(plan.end(), {{d.wf_perm, PER_EXTRA, 1, 0, WHEN_WF_SORT}, {d.wf_key, PER_EXTRA, 1, 0, WHEN_WF_SORT},
+                             {d.cand_ids, PER_EXTRA, PT_CAND_MAX, 0, WHEN_WALK32}, {d.cand_n, PER_EXTRA, 1, 0, WHEN_WALK32},
+                             {d.slow_list, PER_EXTRA, 1, 0, WHEN_WALK32}});
+    return plan;
+}
+
+// bytes of per-pass buffers a device holds right now (capacities: buffers never shrink, a frame may need less than is held)
+size_t dev_held_bytes(Device &d) {
+    size_t held = 0;
+    for (const PassBuf &b : pass_plan(d)) held += *b.cap * b.size;
+    return held;
 }
 
 // the samples per pass were chosen from the buffer budget (not forced by pt_config.spp_chunk)
@@ -716,47 +869,26 @@ void balance_chunk(Frame &fr) {
 int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t stream) {
     Frame &fr = ctx->frame;
     const SceneData &sd = ctx->sd;
-    const std::vector<DevObj> &world = sd.world;
-    const std::vector<DevMat> &mats = sd.mats;
     HIP_TRY(hipSetDevice(d.ordinal));
     d.stream = stream ? stream : d.own_stream;
     d.shard = shard;
     d.nlocal = tiles_of_shard(fr.ntx * fr.nty, shard);
     d.nslots = (uint32_t)d.nlocal * 1024u;
     d.acc_started = false;
-    d.n_trace = d.n_resolve = d.n_raygen = d.n_glass = d.n_fog = d.n_moments = d.n_check = 0;
+    for (EventList &l : d.ev) l.n = 0;
     d.first_recorded = false;
     std::memset(d.pass_log_prev, 0, sizeof d.pass_log_prev);  // the device counters are cleared below, once per frame
     if (d.scene_gen != sd.gen) {
-        HIP_TRY(d.objs.reserve(std::max<size_t>(1, world.size())));
-        HIP_TRY(d.mats.reserve(mats.size()));
-        if (!world.empty())
-            HIP_TRY(hipMemcpyAsync(d.objs.p, world.data(), world.size() * sizeof(DevObj), hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(hipMemcpyAsync(d.mats.p, mats.data(), mats.size() * sizeof(DevMat), hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(d.bsph.reserve(std::max<size_t>(1, sd.bsph.size())));
-        HIP_TRY(d.bbox.reserve(std::max<size_t>(1, sd.bbox.size())));
-        HIP_TRY(d.plane_idx.reserve(std::max<size_t>(1, sd.plane_idx.size())));
-        if (!sd.bsph.empty())
-            HIP_TRY(hipMemcpyAsync(d.bsph.p, sd.bsph.data(), sd.bsph.size() * sizeof(BroadSphere), hipMemcpyHostToDevice, d.stream));
-        if (!sd.bbox.empty())
-            HIP_TRY(hipMemcpyAsync(d.bbox.p, sd.bbox.data(), sd.bbox.size() * sizeof(BroadBox), hipMemcpyHostToDevice, d.stream));
-        if (!sd.plane_idx.empty())
-            HIP_TRY(hipMemcpyAsync(d.plane_idx.p, sd.plane_idx.data(), sd.plane_idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(d.bsph_diel.reserve(std::max<size_t>(1, sd.bsph_diel.size())));
-        HIP_TRY(d.bbox_diel.reserve(std::max<size_t>(1, sd.bbox_diel.size())));
-        if (!sd.bsph_diel.empty())
-            HIP_TRY(hipMemcpyAsync(d.bsph_diel.p, sd.bsph_diel.data(), sd.bsph_diel.size() * sizeof(BroadSphere), hipMemcpyHostToDevice, d.stream));
-        if (!sd.bbox_diel.empty())
-            HIP_TRY(hipMemcpyAsync(d.bbox_diel.p, sd.bbox_diel.data(), sd.bbox_diel.size() * sizeof(BroadBox), hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(d.bvh_nodes.reserve(std::max<size_t>(1, sd.bvh_nodes.size())));
-        HIP_TRY(d.bvh_objs.reserve(std::max<size_t>(1, sd.bvh_objs.size())));
-        if (!sd.bvh_nodes.empty())
-            HIP_TRY(hipMemcpyAsync(d.bvh_nodes.p, sd.bvh_nodes.data(), sd.bvh_nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice, d.stream));
-        if (!sd.bvh_objs.empty())
-            HIP_TRY(hipMemcpyAsync(d.bvh_objs.p, sd.bvh_objs.data(), sd.bvh_objs.size() * sizeof(BvhObj), hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(d.bvh_cores.reserve(std::max<size_t>(1, sd.bvh_cores.size())));
-        if (!sd.bvh_cores.empty())
-            HIP_TRY(hipMemcpyAsync(d.bvh_cores.p, sd.bvh_cores.data(), sd.bvh_cores.size() * sizeof(BvhNode), hipMemcpyHostToDevice, d.stream));
+        if (int32_t rc = upload(d, d.objs, sd.world)) return rc;
+        if (int32_t rc = upload(d, d.mats, sd.mats)) return rc;
+        if (int32_t rc = upload(d, d.bsph, sd.bsph)) return rc;
+        if (int32_t rc = upload(d, d.bbox, sd.bbox)) return rc;
+        if (int32_t rc = upload(d, d.plane_idx, sd.plane_idx)) return rc;
+        if (int32_t rc = upload(d, d.bsph_diel, sd.bsph_diel)) return rc;
+        if (int32_t rc = upload(d, d.bbox_diel, sd.bbox_diel)) return rc;
+        if (int32_t rc = upload(d, d.bvh_nodes, sd.bvh_nodes)) return rc;
+        if (int32_t rc = upload(d, d.bvh_objs, sd.bvh_objs)) return rc;
+        if (int32_t rc = upload(d, d.bvh_cores, sd.bvh_cores)) return rc;
         HIP_TRY(hipStreamSynchronize(d.stream));
         d.scene_gen = sd.gen;
     }
@@ -766,22 +898,14 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     if (fr.fog_vol) {
         HIP_TRY(d.fog_counters.reserve(3));
         HIP_TRY(hipMemsetAsync(d.fog_counters.p, 0, 3 * sizeof(unsigned long long), d.stream));
-        HIP_TRY(d.fog_lights.reserve(std::max<size_t>(1, fr.fog_lights.size())));
-        if (!fr.fog_lights.empty())  // (pageable source: the copy is complete when the call returns)
-            HIP_TRY(hipMemcpyAsync(d.fog_lights.p, fr.fog_lights.data(), fr.fog_lights.size() * sizeof(ptf::FogLight), hipMemcpyHostToDevice,
-                                   d.stream));
+        if (int32_t rc = upload(d, d.fog_lights, fr.fog_lights)) return rc;
     }
-    if (fr.gl) {  // (pageable sources: each copy is complete when the call returns)
+    if (fr.gl) {
         HIP_TRY(d.gl_counters.reserve(5));
         HIP_TRY(hipMemsetAsync(d.gl_counters.p, 0, 5 * sizeof(unsigned long long), d.stream));
-        HIP_TRY(d.gl_objs.reserve(std::max<size_t>(1, fr.gl_objs.size())));
-        HIP_TRY(d.gl_mats.reserve(fr.gl_mats.size()));
-        HIP_TRY(d.gl_lights.reserve(std::max<size_t>(1, fr.gl_lights.size())));
-        if (!fr.gl_objs.empty())
-            HIP_TRY(hipMemcpyAsync(d.gl_objs.p, fr.gl_objs.data(), fr.gl_objs.size() * sizeof(ptg::GlObj), hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(hipMemcpyAsync(d.gl_mats.p, fr.gl_mats.data(), fr.gl_mats.size() * sizeof(ptg::GlMat), hipMemcpyHostToDevice, d.stream));
-        if (!fr.gl_lights.empty())
-            HIP_TRY(hipMemcpyAsync(d.gl_lights.p, fr.gl_lights.data(), fr.gl_lights.size() * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+        if (int32_t rc = upload(d, d.gl_objs, fr.gl_objs)) return rc;
+        if (int32_t rc = upload(d, d.gl_mats, fr.gl_mats)) return rc;
+        if (int32_t rc = upload(d, d.gl_lights, fr.gl_lights)) return rc;
     }
     if (ctx->profile_sections) {
         HIP_TRY(d.prof.reserve(3 * ptk::SEC_COUNT));
@@ -795,15 +919,13 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
         for (uint32_t blk = 0; blk < d.nslots / 64u; blk++)
             if (block_pixels(fr, d.shard, blk) > 0) act.push_back(blk);
         const size_t nb = std::max<size_t>(1, d.nslots / 64u);
-        HIP_TRY(d.act[0].reserve(nb));
+        if (int32_t rc = upload(d, d.act[0], act, nb)) return rc;
         HIP_TRY(d.act[1].reserve(nb));
         HIP_TRY(d.blk_spp.reserve(nb));
         HIP_TRY(d.blk_keep.reserve(nb));
         HIP_TRY(d.blk_noise.reserve(nb));
         HIP_TRY(d.ad_res.reserve(1));
         HIP_TRY(hipMemsetAsync(d.blk_spp.p, 0, nb * sizeof(uint32_t), d.stream));
-        if (!act.empty())  // (pageable source: the copy is complete when the call returns)
-            HIP_TRY(hipMemcpyAsync(d.act[0].p, act.data(), act.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
         d.act_cur = 0;
         d.nact = (uint32_t)act.size();
     }
@@ -817,52 +939,43 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     }
     // occupancy of the kernels of this frame for the scene's LDS footprint (before the buffers: the queue slack depends on it)
     const size_t lds = fr.lds_bytes;
-    int nb = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pick_trace(fr.stats_on, ctx->profile_sections, fr.scan, fr.tail_form), PT_BLOCK, lds));
-    d.blocks_per_cu = std::max(1, std::min(nb, ctx->max_blocks_per_cu));
+    const int max_bpc = ctx->max_blocks_per_cu;
+    if (int32_t rc = occupancy(pick_trace(fr.stats_on, ctx->profile_sections, fr.scan, fr.tail_form), lds, max_bpc, d.blocks_per_cu)) return rc;
     d.blocks_per_cu_split = d.blocks_per_cu;
     d.blocks_per_cu_glass = 1;
     if (fr.wavefront) {
         const bool bvh = fr.scan == ptk::SCAN_BVH || fr.scan == ptk::SCAN_VERIFY_BVH;
-        if (bvh) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ptk::wf_traverse_kernel<0, false>, PT_BLOCK, lds));
-        else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ptk::wf_scan_flat_kernel<0, false>, PT_BLOCK, lds));
-        d.blocks_per_cu_wf = std::max(1, std::min(nb, ctx->max_blocks_per_cu));
+        if (int32_t rc = occupancy(pick_wf_scan0(bvh), lds, max_bpc, d.blocks_per_cu_wf)) return rc;
         if (fr.walk32) {
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ptk::wf_walk32_kernel<0>, PT_BLOCK, walk32_lds_bytes()));
-            d.blocks_per_cu_walk = std::max(1, std::min(nb, ctx->max_blocks_per_cu));
+            if (int32_t rc = occupancy(pick_wf_walk32(0, false), walk32_lds_bytes(), max_bpc, d.blocks_per_cu_walk)) return rc;
             if (std::getenv("PTCORE_VERBOSE")) std::fprintf(stderr, "ptcore: walk32: %d blocks per CU for the FP32 walk, %d for the FP64 traversal of the slow list\n", d.blocks_per_cu_walk, d.blocks_per_cu_wf);
         }
     }
-    if (fr.primary_pass) {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pick_primary(fr.stats_on, fr.scan), PT_BLOCK, 0));
-        d.blocks_per_cu_primary = std::max(1, std::min(nb, 8));
-    }
+    if (fr.primary_pass)
+        if (int32_t rc = occupancy(pick_primary(fr.stats_on, fr.scan), 0, 8, d.blocks_per_cu_primary)) return rc;
     if (fr.split_rounds > 0) {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pick_trace(fr.stats_on, ctx->profile_sections, fr.scan, ptk::FORM_SPLIT), PT_BLOCK, lds));
-        d.blocks_per_cu_split = std::max(1, std::min(nb, ctx->max_blocks_per_cu));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pick_glass(fr.stats_on, fr.scan), PT_BLOCK, fr.glass_lds_bytes));
-        d.blocks_per_cu_glass = std::max(1, std::min(nb, PT_GLASS_MAX_BLOCKS_PER_CU));
+        if (int32_t rc = occupancy(pick_trace(fr.stats_on, ctx->profile_sections, fr.scan, ptk::FORM_SPLIT), lds, max_bpc, d.blocks_per_cu_split)) return rc;
+        if (int32_t rc = occupancy(pick_glass(fr.stats_on, fr.scan), fr.glass_lds_bytes, PT_GLASS_MAX_BLOCKS_PER_CU, d.blocks_per_cu_glass)) return rc;
     }
-    // per-pass buffers: 90 B per job (radiance record, primary ray, stream state, draw count; + 8 B with pixel stats) and, for the
-    // forms that park paths in HBM, two or three path-state queues
-    const bool queues = fr.wavefront || (fr.split_rounds > 0 && fr.has_glass) || fr.primary_pass;
-    const size_t nqueues = !queues ? 0 : fr.wavefront ? 3 : fr.primary_pass ? 1 : 2;  // (the primary pass of the BVH path fills the continuation queue only)
-    const size_t qplanes = fr.stats_on ? 6 : 4;
-    const size_t qentry = 10 * sizeof(double) + sizeof(unsigned long long) + qplanes * sizeof(uint32_t);
-    const size_t job_bytes = 4 * sizeof(double) + 6 * sizeof(double) + sizeof(unsigned long long) + sizeof(uint16_t) +
-                             (fr.stats_on ? 2 * sizeof(uint32_t) : 0);
+    // per-pass buffers (pass_plan): 90 B per job and, for the forms that park paths in HBM, one to three path-state queues with one
+    // entry per job at most, plus the slots the waves of the writing passes reserve in windows and may leave empty
+    const std::vector<PassBuf> plan = pass_plan(d);
+    const unsigned forms = frame_forms(ctx);
+    const bool queues = (forms & WHEN_Q_CONT) != 0;  // (every form with queues has that one)
     auto queue_cap = [&](size_t njobs_max) { return njobs_max + queue_slack(ctx, d, njobs_max); };
     auto need_bytes = [&](uint32_t chunk) {
-        const size_t nj = (size_t)ns * chunk;
-        return nj * job_bytes + nqueues * queue_cap(nj) * qentry + (fr.wavefront && ctx->wf_sort ? 2 * queue_cap(nj) * sizeof(uint32_t) : 0) +
-               (fr.walk32 ? (PT_CAND_MAX + 2) * queue_cap(nj) * sizeof(uint32_t) : 0);
+        const size_t nj = (size_t)ns * chunk, nq = queue_cap(nj);
+        size_t need = 0;
+        for (const PassBuf &b : plan) need += (b.per == PER_JOB ? nj : nq) * b.used(forms, fr.stats_on) * b.size;
+        return need;
     };
-    auto held_bytes = [&]() { return dev_held_bytes(d); };
     // The budget covers everything a pass holds, the window slack of the queues included: when the queues push the total over it,
     // the samples per pass shrink (a frame is cut into more passes; pixels do not depend on that).
     if (cfg_chunk_free(fr) && need_bytes(fr.chunk) > fr.budget_bytes) {
-        const size_t fixed = need_bytes(1) > (size_t)ns * (job_bytes + nqueues * qentry) ? need_bytes(1) - (size_t)ns * (job_bytes + nqueues * qentry) : 0;
-        const size_t per = (size_t)ns * (job_bytes + nqueues * qentry);
+        size_t per = 0;  // per sample of the pass without the slack: the jobs and one queue entry per job
+        for (const PassBuf &b : plan)
+            if (b.per != PER_EXTRA) per += (size_t)ns * b.used(forms, fr.stats_on) * b.size;
+        const size_t fixed = need_bytes(1) > per ? need_bytes(1) - per : 0;
         fr.chunk = (uint32_t)std::max<size_t>(1, fr.budget_bytes > fixed ? (fr.budget_bytes - fixed) / per : 1);
         while (fr.chunk > 1 && need_bytes(fr.chunk) > fr.budget_bytes) fr.chunk -= std::max(1u, fr.chunk / 64u);
         balance_chunk(fr);
@@ -871,7 +984,7 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     // seconds of hipMalloc / hipFree per frame when two processes share one GPU) -- until the device shows room for it again.
     if (d.bytes_cap && need_bytes(fr.chunk) > d.bytes_cap) {
         size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + held_bytes() >= need_bytes(fr.chunk) + need_bytes(fr.chunk) / 16) {
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + dev_held_bytes(d) >= need_bytes(fr.chunk) + need_bytes(fr.chunk) / 16) {
             d.bytes_cap = 0;  // whatever took the memory is gone: back to the full size
         } else {
             while (fr.chunk > 1 && need_bytes(fr.chunk) > d.bytes_cap) fr.chunk = std::max<uint32_t>(1, fr.chunk / 2);
@@ -881,50 +994,20 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     // (the ordered accumulation makes the pixels independent of the chunk size)
     for (;;) {
         const size_t njobs_max = (size_t)ns * fr.chunk;
-        hipError_t e = d.L.reserve(4 * njobs_max);
-        if (e == hipSuccess) e = d.ray.reserve(6 * njobs_max);
-        if (e == hipSuccess) e = d.ray_rng.reserve(njobs_max);
-        if (e == hipSuccess) e = d.ray_ndraw.reserve(njobs_max);
-        if (e == hipSuccess && fr.stats_on) e = d.job_seg.reserve(njobs_max);
-        if (e == hipSuccess && fr.stats_on) e = d.job_draw.reserve(njobs_max);
-        if (queues) {  // path-state queues: 10 doubles + stream state + job, depth, hit object, answer (+ 2 counters) per entry
-            // one entry per job at most, plus the slots the waves of the writing passes reserve in windows and may leave empty
-            size_t qcap = queue_cap(njobs_max);
-            // PTCORE_DEBUG_QUEUE_CAP=<entries> (tests only): queues too small for the frame, to show that an overflow fails the
-            // frame with PT_ERR_STATE instead of writing outside them
-            if (const char *dbg = std::getenv("PTCORE_DEBUG_QUEUE_CAP")) qcap = (size_t)std::max(64L, std::atol(dbg));
-            if (!fr.primary_pass) {
-                if (e == hipSuccess) e = d.gq_d.reserve(10 * qcap);
-                if (e == hipSuccess) e = d.gq_rs.reserve(qcap);
-                if (e == hipSuccess) e = d.gq_u32.reserve(qplanes * qcap);
-            }
-            if (e == hipSuccess) e = d.cq_d.reserve(10 * qcap);
-            if (e == hipSuccess) e = d.cq_rs.reserve(qcap);
-            if (e == hipSuccess) e = d.cq_u32.reserve(qplanes * qcap);
-            if (fr.wavefront) {
-                if (e == hipSuccess) e = d.xq_d.reserve(10 * qcap);
-                if (e == hipSuccess) e = d.xq_rs.reserve(qcap);
-                if (e == hipSuccess) e = d.xq_u32.reserve(qplanes * qcap);
-                if (ctx->wf_sort) {
-                    if (e == hipSuccess) e = d.wf_perm.reserve(qcap);
-                    if (e == hipSuccess) e = d.wf_key.reserve(qcap);
-                    if (e == hipSuccess) e = d.wf_bins.reserve(PT_WF_BINS + 8);
-                }
-                if (fr.walk32) {
-                    if (e == hipSuccess) e = d.cand_ids.reserve((size_t)PT_CAND_MAX * qcap);
-                    if (e == hipSuccess) e = d.cand_n.reserve(qcap);
-                    if (e == hipSuccess) e = d.slow_list.reserve(qcap);
-                }
-            }
-            d.q_cap = qcap;
-        }
+        size_t qcap = queues ? queue_cap(njobs_max) : 0;
+        // PTCORE_DEBUG_QUEUE_CAP=<entries> (tests only): queues too small for the frame, to show that an overflow fails the
+        // frame with PT_ERR_STATE instead of writing outside them
+        if (const char *dbg = queues ? std::getenv("PTCORE_DEBUG_QUEUE_CAP") : nullptr) qcap = (size_t)std::max(64L, std::atol(dbg));
+        hipError_t e = hipSuccess;
+        for (const PassBuf &b : plan)
+            if (const size_t n = (b.per == PER_JOB ? njobs_max : qcap) * b.used(forms, fr.stats_on))
+                if (e == hipSuccess) e = dev_reserve(b.p, b.cap, n, b.size);
+        if (e == hipSuccess && fr.wavefront && ctx->wf_sort) e = d.wf_bins.reserve(PT_WF_BINS + 8);
+        if (queues) d.q_cap = qcap;
         if (e == hipSuccess) break;
         (void)hipGetLastError();
         if (e != hipErrorOutOfMemory || fr.chunk <= 1) return fail(PT_ERR_HIP, std::string("job buffers: ") + hipGetErrorString(e));
-        d.L.release(); d.ray.release(); d.ray_rng.release(); d.ray_ndraw.release(); d.job_seg.release(); d.job_draw.release();
-        d.gq_d.release(); d.cq_d.release(); d.gq_rs.release(); d.cq_rs.release(); d.gq_u32.release(); d.cq_u32.release();
-        d.xq_d.release(); d.xq_rs.release(); d.xq_u32.release(); d.wf_perm.release(); d.wf_key.release();
-        d.cand_ids.release(); d.cand_n.release(); d.slow_list.release();
+        for (const PassBuf &b : plan) dev_release(b.p, b.cap);
         fr.chunk = std::max<uint32_t>(1, fr.chunk / 2);
         d.bytes_cap = need_bytes(fr.chunk);
         if (std::getenv("PTCORE_VERBOSE")) std::fprintf(stderr, "ptcore: device %d is short of memory, samples per pass reduced to %u\n", d.ordinal, fr.chunk);
@@ -940,24 +1023,8 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
     const bool verify = fr.scan == ptk::SCAN_VERIFY_BVH || fr.scan == ptk::SCAN_VERIFY;
     const bool stats = fr.stats_on;
     unsigned int *qw = d.queue.p;
-    const size_t cap = d.q_cap;
-    auto bind = [&](PathQueue &q, DevBuf<double> &qd, DevBuf<unsigned long long> &qrs, DevBuf<uint32_t> &qu, unsigned int *count) {
-        std::memset(&q, 0, sizeof q);
-        q.d = qd.p;
-        q.rs = qrs.p;
-        q.job = qu.p;
-        q.depth = reinterpret_cast<int32_t *>(qu.p + cap);
-        q.best = reinterpret_cast<int32_t *>(qu.p + 2 * cap);
-        q.hit = reinterpret_cast<int32_t *>(qu.p + 3 * cap);
-        q.jseg = stats ? qu.p + 4 * cap : nullptr;
-        q.jdraw = stats ? qu.p + 5 * cap : nullptr;
-        q.count = count;
-        q.cap = (uint32_t)cap;
-    };
-    PathQueue qa, qb, qe;
-    bind(qa, d.cq_d, d.cq_rs, d.cq_u32, qw + 1);
-    bind(qb, d.xq_d, d.xq_rs, d.xq_u32, qw + 2);
-    bind(qe, d.gq_d, d.gq_rs, d.gq_u32, qw + 3);
+    const PathQueue qa = d.q_cont.bind(d.q_cap, stats, qw + 1), qb = d.q_path_b.bind(d.q_cap, stats, qw + 2);
+    const PathQueue qe = d.q_glass.bind(d.q_cap, stats, qw + 3);
     ptk::WfArgs A;
     std::memset(&A, 0, sizeof A);
     A.F = F;
@@ -967,6 +1034,7 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
     A.B = B;
     A.cursor = qw;
     const size_t lds_scan = fr.lds_bytes, lds_shade = fr.shade_lds_bytes, lds_mat = (size_t)F.nmat * sizeof(DevMat);
+    const dim3 block(PT_BLOCK);
     const uint32_t blocks_all = (F.njobs + PT_BLOCK - 1) / PT_BLOCK;
     const uint32_t grid_scan = std::max(1u, std::min((uint32_t)(d.num_cu * d.blocks_per_cu_wf), blocks_all));
     // shading passes: PT_WF_PASS_BLOCKS_PER_CU blocks per CU.  Their waves append to the next level's queue in windows of
@@ -993,59 +1061,37 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
     const uint32_t grid_walk = std::max(1u, std::min((uint32_t)(d.num_cu * std::max(1, d.blocks_per_cu_walk)), blocks_all));
     auto scan_pass = [&](int mode) -> int32_t {
         HIP_TRY(hipMemsetAsync(qw, 0, sizeof(unsigned int), d.stream));
-        if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
-        d.trace_is_split[d.n_trace] = 0;
-        if (walk32) {
-            HIP_TRY(hipMemsetAsync(qw + 6, 0, sizeof(unsigned int), d.stream));
-            const ptk::Walk32Args K = walk_args();
-            if (int32_t rc = timed(d, d.ev_trace, d.n_trace, [&] {
-                    if (walk_diag) {
-                        if (mode == 0) hipLaunchKernelGGL((ptk::wf_walk32_kernel<0, true>), dim3(grid_walk), dim3(PT_BLOCK), walk32_lds_bytes(), d.stream, K);
-                        else hipLaunchKernelGGL((ptk::wf_walk32_kernel<1, true>), dim3(grid_walk), dim3(PT_BLOCK), walk32_lds_bytes(), d.stream, K);
-                    } else if (mode == 0) hipLaunchKernelGGL((ptk::wf_walk32_kernel<0>), dim3(grid_walk), dim3(PT_BLOCK), walk32_lds_bytes(), d.stream, K);
-                    else hipLaunchKernelGGL((ptk::wf_walk32_kernel<1>), dim3(grid_walk), dim3(PT_BLOCK), walk32_lds_bytes(), d.stream, K);
-                }))
-                return rc;
-            // the entries the walk handed over, through the FP64 traversal (their number lives on the device)
-            HIP_TRY(hipMemsetAsync(qw, 0, sizeof(unsigned int), d.stream));
-            if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
-            d.trace_is_split[d.n_trace] = 0;
-            ptk::WfArgs S = A;
-            S.perm = d.slow_list.p;
-            S.n_sorted = qw + 6;
-            const uint32_t grid_slow = std::max(1u, std::min(grid_scan, (uint32_t)d.num_cu));
-            return timed(d, d.ev_trace, d.n_trace, [&] {
-                if (mode == 0) hipLaunchKernelGGL((ptk::wf_traverse_kernel<0, false>), dim3(grid_slow), dim3(PT_BLOCK), lds_scan, d.stream, S);
-                else hipLaunchKernelGGL((ptk::wf_traverse_kernel<1, false>), dim3(grid_slow), dim3(PT_BLOCK), lds_scan, d.stream, S);
+        if (!walk32)
+            return timed_trace(d, false, [&] {
+                hipLaunchKernelGGL(bvh ? pick_wf_traverse(mode, verify) : pick_wf_scan_flat(mode, verify), dim3(grid_scan), block, lds_scan, d.stream, A);
             });
-        }
-        return timed(d, d.ev_trace, d.n_trace, [&] {
-            if (bvh) {
-                if (mode == 0) {
-                    if (verify) hipLaunchKernelGGL((ptk::wf_traverse_kernel<0, true>), dim3(grid_scan), dim3(PT_BLOCK), lds_scan, d.stream, A);
-                    else hipLaunchKernelGGL((ptk::wf_traverse_kernel<0, false>), dim3(grid_scan), dim3(PT_BLOCK), lds_scan, d.stream, A);
-                } else {
-                    if (verify) hipLaunchKernelGGL((ptk::wf_traverse_kernel<1, true>), dim3(grid_scan), dim3(PT_BLOCK), lds_scan, d.stream, A);
-                    else hipLaunchKernelGGL((ptk::wf_traverse_kernel<1, false>), dim3(grid_scan), dim3(PT_BLOCK), lds_scan, d.stream, A);
-                }
-            } else {
-                if (mode == 0) {
-                    if (verify) hipLaunchKernelGGL((ptk::wf_scan_flat_kernel<0, true>), dim3(grid_scan), dim3(PT_BLOCK), lds_scan, d.stream, A);
-                    else hipLaunchKernelGGL((ptk::wf_scan_flat_kernel<0, false>), dim3(grid_scan), dim3(PT_BLOCK), lds_scan, d.stream, A);
-                } else {
-                    if (verify) hipLaunchKernelGGL((ptk::wf_scan_flat_kernel<1, true>), dim3(grid_scan), dim3(PT_BLOCK), lds_scan, d.stream, A);
-                    else hipLaunchKernelGGL((ptk::wf_scan_flat_kernel<1, false>), dim3(grid_scan), dim3(PT_BLOCK), lds_scan, d.stream, A);
-                }
-            }
+        HIP_TRY(hipMemsetAsync(qw + 6, 0, sizeof(unsigned int), d.stream));
+        const ptk::Walk32Args K = walk_args();
+        if (int32_t rc = timed_trace(d, false, [&] {
+                hipLaunchKernelGGL(pick_wf_walk32(mode, walk_diag), dim3(grid_walk), block, walk32_lds_bytes(), d.stream, K);
+            }))
+            return rc;
+        // the entries the walk handed over, through the FP64 traversal (their number lives on the device)
+        HIP_TRY(hipMemsetAsync(qw, 0, sizeof(unsigned int), d.stream));
+        ptk::WfArgs S = A;
+        S.perm = d.slow_list.p;
+        S.n_sorted = qw + 6;
+        const uint32_t grid_slow = std::max(1u, std::min(grid_scan, (uint32_t)d.num_cu));
+        return timed_trace(d, false, [&] { hipLaunchKernelGGL(pick_wf_traverse(mode, false), dim3(grid_slow), block, lds_scan, d.stream, S); });
+    };
+    // a level's shading pass and its exit pass: the exact tests of the walk's candidates in front with walk32
+    auto shade_pass = [&](Walk32Fn with_walk, WfFn plain, size_t lds_plain) {
+        return timed(d, EV_GLASS, [&] {
+            if (walk32) hipLaunchKernelGGL(with_walk, dim3(grid_pass), block, lds_mat, d.stream, walk_args());
+            else hipLaunchKernelGGL(plain, dim3(grid_pass), block, lds_plain, d.stream, A);
         });
     };
     // fresh jobs -> queue A
     A.qin = qa;
     A.qout = qb;
     A.qexit = qe;
-    if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
-            if (stats) hipLaunchKernelGGL(ptk::wf_init_kernel<true>, dim3(std::min(blocks_all, (uint32_t)d.num_cu * 8u)), dim3(PT_BLOCK), 0, d.stream, A);
-            else hipLaunchKernelGGL(ptk::wf_init_kernel<false>, dim3(std::min(blocks_all, (uint32_t)d.num_cu * 8u)), dim3(PT_BLOCK), 0, d.stream, A);
+    if (int32_t rc = timed(d, EV_GLASS, [&] {
+            hipLaunchKernelGGL(pick_wf_init(stats), dim3(std::min(blocks_all, (uint32_t)d.num_cu * 8u)), block, 0, d.stream, A);
         }))
         return rc;
     PathQueue cur_in = qa, cur_out = qb;
@@ -1060,10 +1106,10 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
             A.bin_count = d.wf_bins.p;
             A.bin_key = d.wf_key.p;
             HIP_TRY(hipMemsetAsync(d.wf_bins.p, 0, (PT_WF_BINS + 1) * sizeof(uint32_t), d.stream));
-            if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
-                    hipLaunchKernelGGL(ptk::wf_bin_count_kernel, dim3(grid_pass), dim3(PT_BLOCK), 0, d.stream, A);
+            if (int32_t rc = timed(d, EV_GLASS, [&] {
+                    hipLaunchKernelGGL(ptk::wf_bin_count_kernel, dim3(grid_pass), block, 0, d.stream, A);
                     hipLaunchKernelGGL(ptk::wf_bin_scan_kernel, dim3(1), dim3(1024), 0, d.stream, A);
-                    hipLaunchKernelGGL(ptk::wf_bin_scatter_kernel, dim3(grid_pass), dim3(PT_BLOCK), 0, d.stream, A, d.wf_perm.p);
+                    hipLaunchKernelGGL(ptk::wf_bin_scatter_kernel, dim3(grid_pass), block, 0, d.stream, A, d.wf_perm.p);
                 }))
                 return rc;
             A.perm = d.wf_perm.p;
@@ -1073,37 +1119,11 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
         A.perm = nullptr;
         HIP_TRY(hipMemsetAsync(cur_out.count, 0, sizeof(unsigned int), d.stream));
         HIP_TRY(hipMemsetAsync(qe.count, 0, sizeof(unsigned int), d.stream));
-        if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
-                if (walk32) {
-                    const ptk::Walk32Args K = walk_args();
-                    if (stats) {
-                        if (verify) hipLaunchKernelGGL((ptk::wf_shade32_kernel<true, true>), dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, K);
-                        else hipLaunchKernelGGL((ptk::wf_shade32_kernel<true, false>), dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, K);
-                    } else {
-                        if (verify) hipLaunchKernelGGL((ptk::wf_shade32_kernel<false, true>), dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, K);
-                        else hipLaunchKernelGGL((ptk::wf_shade32_kernel<false, false>), dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, K);
-                    }
-                } else if (stats) hipLaunchKernelGGL(ptk::wf_shade_kernel<true>, dim3(grid_pass), dim3(PT_BLOCK), lds_shade, d.stream, A);
-                else hipLaunchKernelGGL(ptk::wf_shade_kernel<false>, dim3(grid_pass), dim3(PT_BLOCK), lds_shade, d.stream, A);
-            }))
-            return rc;
+        if (int32_t rc = shade_pass(pick_wf_shade32(stats, verify), pick_wf_shade(stats), lds_shade)) return rc;
         if (fr.has_glass) {
             A.qin = qe;
             if (int32_t rc = scan_pass(1)) return rc;
-            if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
-                    if (walk32) {
-                        const ptk::Walk32Args K = walk_args();
-                        if (stats) {
-                            if (verify) hipLaunchKernelGGL((ptk::wf_exit32_kernel<true, true>), dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, K);
-                            else hipLaunchKernelGGL((ptk::wf_exit32_kernel<true, false>), dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, K);
-                        } else {
-                            if (verify) hipLaunchKernelGGL((ptk::wf_exit32_kernel<false, true>), dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, K);
-                            else hipLaunchKernelGGL((ptk::wf_exit32_kernel<false, false>), dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, K);
-                        }
-                    } else if (stats) hipLaunchKernelGGL(ptk::wf_exit_kernel<true>, dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, A);
-                    else hipLaunchKernelGGL(ptk::wf_exit_kernel<false>, dim3(grid_pass), dim3(PT_BLOCK), lds_mat, d.stream, A);
-                }))
-                return rc;
+            if (int32_t rc = shade_pass(pick_wf_exit32(stats, verify), pick_wf_exit(stats), lds_mat)) return rc;
         }
         std::swap(cur_in, cur_out);
         // deep presets (the "final" mode asks for 80 levels): stop as soon as no path is left
@@ -1114,6 +1134,257 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
             if (left == 0) break;
         }
     }
+    return PT_OK;
+}
+
+// ---- dev_step's stages, in the order they run.  F is the chunk's DevFrame (F.s0, F.S, F.njobs), G the device's tile map.
+
+// GL shading: one pass per job, camera rays made in the kernel (pt_glshade.h)
+int32_t step_gl(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G) {
+    const Frame &fr = ctx->frame;
+    ptk::GlArgs GA;
+    std::memset(&GA, 0, sizeof GA);
+    ptg::GlScene &GS = GA.S;
+    GS.objs = d.gl_objs.p;
+    GS.mats = d.gl_mats.p;
+    GS.lights = d.gl_lights.p;
+    GS.nobj = (int32_t)fr.gl_objs.size();
+    GS.nlight = (int32_t)fr.gl_lights.size();
+    GS.sky = fr.gl_sky;
+    GS.cam = fr.gl_cam;
+    GS.max_depth = fr.cfg.max_depth;
+    GS.width = G.width;
+    GS.height = G.height;
+    GS.fog_on = fr.fog_vol ? 1 : 0;
+    GS.fog = fr.fog;
+    GS.fog_objs = d.objs.p;
+    GS.fog_lights = d.fog_lights.p;
+    GS.fog_nobj = fr.nobj;
+    GS.fog_nlight = (int32_t)fr.fog_lights.size();
+    GA.L = d.L.p;
+    GA.counters = d.counters.p;
+    GA.gl_counters = d.gl_counters.p;
+    GA.fog_counters = fr.fog_vol ? d.fog_counters.p : nullptr;
+    GA.key = ptm::seed_key(fr.cfg.seed ^ PTG_STREAM_SALT);
+    GA.fog_key = ptm::seed_key(fr.cfg.seed ^ PTF_STREAM_SALT);
+    GA.njobs = F.njobs;
+    GA.nS = F.S;
+    GA.s0 = F.s0;
+    GA.ntx = G.ntx;  // (the frame size is GS's)
+    GA.shard_index = G.shard_index;
+    GA.shard_count = G.shard_count;
+    return timed_trace(d, false, [&] { hipLaunchKernelGGL(ptk::gl_trace_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, GA); });
+}
+
+// Ray generation (`active`: the adaptive frame's list of blocks), then pt_debug_set_primary_rays' table over its rays
+int32_t step_raygen(pt_ctx *ctx, Device &d, const DevFrame &F, const uint32_t *active) {
+    const Frame &fr = ctx->frame;
+    const dim3 block(PT_BLOCK), per_job((F.njobs + PT_BLOCK - 1) / PT_BLOCK);
+    const char *rg_form = std::getenv("PTCORE_RAYGEN");  // A/B: "column" = round 2's walk down a lane's column, "simple" = one job per lane
+    const bool rg_simple = std::getenv("PTCORE_RAYGEN_SIMPLE") || (rg_form && !std::strcmp(rg_form, "simple"));
+    if (int32_t rc = timed(d, EV_RAYGEN, [&] {
+            if (fr.adaptive)
+                hipLaunchKernelGGL(ptk::raygen_adaptive_kernel, per_job, block, 0, d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p, active);
+            else if (fr.cam.lens_radius > 0 && !rg_simple && !(rg_form && !std::strcmp(rg_form, "column")))  // thin lens: the rejection loop over a wave's pool of jobs
+                hipLaunchKernelGGL(ptk::raygen_lens_pool_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_POOL_ROWS - 1) / (PT_BLOCK * PT_RG_POOL_ROWS)), block, 0,
+                                   d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
+            else if (fr.cam.lens_radius > 0 && !rg_simple)
+                hipLaunchKernelGGL(ptk::raygen_lens_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_ROWS - 1) / (PT_BLOCK * PT_RG_ROWS)), block, 0,
+                                   d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
+            else
+                hipLaunchKernelGGL(ptk::raygen_kernel, per_job, block, 0, d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
+        }))
+        return rc;
+    if (ctx->inject_rays.empty()) return PT_OK;
+    if (d.inject_gen != ctx->inject_gen) {
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        HIP_TRY(d.inject.reserve(ctx->inject_rays.size()));
+        HIP_TRY(hipMemcpy(d.inject.p, ctx->inject_rays.data(), ctx->inject_rays.size() * sizeof(double), hipMemcpyHostToDevice));
+        d.inject_gen = ctx->inject_gen;
+    }
+    hipLaunchKernelGGL(ptk::inject_rays_kernel, per_job, block, 0, d.stream, F, d.inject.p, (uint64_t)(ctx->inject_rays.size() / 6),
+                       (uint32_t)fr.cfg.samples_per_px, d.ray.p, d.ray_ndraw.p);
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
+// PTCORE_DEBUG_TIMELINE (diagnostics): when each wave of the trace launch just timed retired; serialises the stream
+int32_t print_timeline(Device &d, const char *pass, int form, uint32_t grid) {
+    const EventPair &e = d.ev[EV_TRACE].v[d.ev[EV_TRACE].n - 1];
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    const uint32_t nw = std::min(grid * 4u, 65536u);
+    std::vector<unsigned long long> t(nw);
+    HIP_TRY(hipMemcpy(t.data(), d.prof.p, nw * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::sort(t.begin(), t.end());
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e.a, e.b));
+    auto back = [&](double q) { return (double)(t[nw - 1] - t[(size_t)(q * (nw - 1))]) * 1e-5; };  // ms before the last wave
+    double mean = 0;
+    for (auto v : t) mean += (double)(t[nw - 1] - v);
+    std::fprintf(stderr, "ptcore timeline: %s form %d  %.3f ms, %u waves; before the last wave retired: first %.3f ms, 1 %% %.3f, 10 %% %.3f, 25 %% %.3f, 50 %% %.3f, 75 %% %.3f, 90 %% %.3f, 99 %% %.3f; mean %.3f ms\n",
+                 pass, form, ms, nw, back(0.0), back(0.01), back(0.10), back(0.25), back(0.50), back(0.75), back(0.90), back(0.99), mean / nw * 1e-5);
+    return PT_OK;
+}
+
+// PTCORE_DEBUG_PASS_LOG=1 (diagnostics): what the trace pass just timed did (`pass` null: the primary pass); serialises the stream
+int32_t print_pass_log(Device &d, const char *pass, uint32_t grid) {
+    const EventPair &e = d.ev[EV_TRACE].v[d.ev[EV_TRACE].n - 1];
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    unsigned long long c[48];
+    HIP_TRY(hipMemcpy(c, d.counters.p, sizeof c, hipMemcpyDeviceToHost));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e.a, e.b));
+    const unsigned long long *prev = d.pass_log_prev;
+    if (pass)
+        std::fprintf(stderr, "ptcore pass: %s grid %u  %.3f ms  segments +%llu  exit scans +%llu  parked +%llu  ended here +%llu  continuations in +%llu  -> %.1f Mseg/s\n",
+                     pass, grid, ms, c[0] - prev[0], c[1] - prev[1], c[5] - prev[5], c[18] - prev[18], c[7] - prev[7], (double)(c[0] - prev[0]) / (ms * 1e3));
+    else
+        std::fprintf(stderr, "ptcore pass: primary<wave> grid %u  %.3f ms  segments shaded %llu  handed on %llu  wave-level node visits %llu over %llu blocks of 64 jobs (%llu more handed over unwalked)\n",
+                     grid, ms, c[0] - prev[0], c[6], c[40], c[41], c[42]);
+    std::memcpy(d.pass_log_prev, c, sizeof d.pass_log_prev);
+    return PT_OK;
+}
+
+// The trace schedule of the all-in-one loop and its split forms.  Queue words: [0] item cursor of the running trace pass, [1] glass
+// entries, [2],[3] continuation entries (one is read by a trace pass while glass_kernel fills the other), [4] stays 0 (a first pass
+// starts from no continuations)
+int32_t step_trace(pt_ctx *ctx, Device &d, const DevFrame &F, TraceBuffers &B, bool timeline) {
+    const Frame &fr = ctx->frame;
+    unsigned int *qw = d.queue.p;
+    const dim3 block(PT_BLOCK);
+    const int rounds = fr.split_rounds;
+    const uint32_t waves_needed = (F.njobs + 63u) / 64u, blocks_all = (F.njobs + PT_BLOCK - 1) / PT_BLOCK;
+    const bool pass_log = std::getenv("PTCORE_DEBUG_PASS_LOG") != nullptr;
+    auto launch_trace = [&](bool split, bool first) -> int32_t {
+        TraceArgs A;
+        A.F = F;
+        A.F.fresh = first ? F.njobs : 0u;
+        A.sky = fr.sky;
+        A.B = B;
+        uint32_t grid = (uint32_t)(d.num_cu * (split ? d.blocks_per_cu_split : d.blocks_per_cu));
+        // (later passes: the item count lives on the device; no pass holds more items than the chunk has jobs, which is also
+        // the bound queue_slack() assumes)
+        grid = std::max(1u, std::min(grid, (waves_needed + 3u) / 4u));
+        const int form = split ? (int)ptk::FORM_SPLIT : fr.tail_form;
+        if (int32_t rc = timed_trace(d, split, [&] {
+                hipLaunchKernelGGL(pick_trace(fr.stats_on, ctx->profile_sections, fr.scan, form), dim3(grid), block, fr.lds_bytes, d.stream, A);
+            }))
+            return rc;
+        if (timeline)
+            if (int32_t rc = print_timeline(d, split ? "trace<split>" : "trace<tail>", split ? 1 : fr.tail_form, grid)) return rc;
+        if (pass_log) return print_pass_log(d, split ? "trace<split>" : "trace<all-in-one>", grid);
+        return PT_OK;
+    };
+    if (fr.primary_pass) {
+        // BVH scenes: the first segment of every path by the wave-cooperative kernel (pt_primary.h); what goes on -- and what that
+        // kernel is not meant for, unshaded -- reaches the per-lane loop through the continuation queue
+        B.cont_in = qw + 2;
+        B.cont.count = qw + 2;
+        TraceArgs A;
+        A.F = F;
+        A.F.fresh = 0u;
+        A.sky = fr.sky;
+        A.B = B;
+        const uint32_t pgrid = std::max(1u, std::min((uint32_t)(d.num_cu * d.blocks_per_cu_primary), blocks_all));  // same bound as queue_slack()
+        if (int32_t rc = timed_trace(d, false, [&] { hipLaunchKernelGGL(pick_primary(fr.stats_on, fr.scan), dim3(pgrid), block, 0, d.stream, A); }))
+            return rc;
+        if (pass_log)
+            if (int32_t rc = print_pass_log(d, nullptr, pgrid)) return rc;
+        return launch_trace(false, false);
+    }
+    if (rounds == 0) return launch_trace(false, true);
+    // Split passes: trace (dielectric hits -> glass queue), glass (-> continuation queue), `rounds` times; what is
+    // still under way then (paths with more than `rounds` dielectric bounces) finishes in the all-in-one form.
+    const uint32_t glass_grid = std::max(1u, std::min((uint32_t)(d.num_cu * d.blocks_per_cu_glass), blocks_all));  // same bound as queue_slack()
+    for (int r = 0; r < rounds; r++) {
+        if (r > 0) HIP_TRY(hipMemsetAsync(qw, 0, 2 * sizeof(unsigned int), d.stream));  // cursor and glass count
+        unsigned int *c_in = r == 0 ? qw + 4 : qw + 2 + (r & 1), *c_out = qw + 2 + ((r + 1) & 1);
+        HIP_TRY(hipMemsetAsync(c_out, 0, sizeof(unsigned int), d.stream));
+        B.cont_in = c_in;
+        B.cont.count = c_out;
+        if (int32_t rc = launch_trace(true, r == 0)) return rc;
+        if (!fr.has_glass) return PT_OK;  // nothing can have entered the glass queue: the frame is done
+        ptk::GlassArgs GA;
+        GA.F = F;
+        GA.B = B;
+        if (int32_t rc = timed(d, EV_GLASS, [&] {
+                hipLaunchKernelGGL(pick_glass(fr.stats_on, fr.scan), dim3(glass_grid), block, fr.glass_lds_bytes, d.stream, GA);
+            }))
+            return rc;
+    }
+    HIP_TRY(hipMemsetAsync(qw, 0, sizeof(unsigned int), d.stream));
+    B.cont_in = qw + 2 + (rounds & 1);
+    B.cont.count = qw + 5;  // unused by the all-in-one form
+    return launch_trace(false, false);
+}
+
+// The fog's in-scatter term into the chunk's radiance records (pt_fog.h)
+int32_t step_fog(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G, const uint32_t *active) {
+    const Frame &fr = ctx->frame;
+    ptk::FogArgs FA;
+    std::memset(&FA, 0, sizeof FA);
+    FA.P = fr.fog;
+    FA.objs = d.objs.p;
+    FA.lights = d.fog_lights.p;
+    FA.ray = d.ray.p;
+    FA.ray_ndraw = d.ray_ndraw.p;
+    FA.L = d.L.p;
+    FA.counters = d.fog_counters.p;
+    FA.fog_key = ptm::seed_key(fr.cfg.seed ^ PTF_STREAM_SALT);
+    FA.nobj = fr.nobj;
+    FA.nlight = (int32_t)fr.fog_lights.size();
+    FA.njobs = F.njobs;
+    FA.S = F.S;
+    FA.s0 = F.s0;
+    FA.G = G;
+    return timed(d, EV_FOG, [&] {
+        if (fr.adaptive) hipLaunchKernelGGL(ptk::fog_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA, active);
+        else hipLaunchKernelGGL(ptk::fog_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA);
+    });
+}
+
+// The chunk's radiance records into the running sums (resolve_kernel), and their squares, in the same order (pt_set_moments)
+int32_t step_accumulate(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G, const ptk::AdaptTable &AT) {
+    const Frame &fr = ctx->frame;
+    ptk::ResolveArgs R;
+    std::memset(&R, 0, sizeof R);
+    R.L = d.L.p;
+    R.job_seg = fr.stats_on ? d.job_seg.p : nullptr;
+    R.job_draw = fr.stats_on ? d.job_draw.p : nullptr;
+    R.acc = d.acc.p;
+    R.acc_seg = fr.stats_on ? d.acc_seg.p : nullptr;
+    R.acc_draw = fr.stats_on ? d.acc_draw.p : nullptr;
+    R.nslots = d.nslots;
+    R.njobs = F.njobs;
+    R.S = F.S;
+    R.first = d.acc_started ? 0 : 1;
+    R.finish = 0;
+    R.have_chunk = 1;
+    R.inv_samples = 0;
+    R.G = G;
+    const uint32_t add_grid = ((fr.adaptive ? d.nact * 64u : d.nslots) + PT_BLOCK - 1) / PT_BLOCK;
+    if (int32_t rc = timed(d, EV_RESOLVE, [&] {
+            if (fr.adaptive) hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R, AT);
+            else hipLaunchKernelGGL(ptk::resolve_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R);
+        }))
+        return rc;
+    if (fr.moments) {
+        ptk::MomentsArgs M;
+        std::memset(&M, 0, sizeof M);
+        M.L = d.L.p;
+        M.m2 = d.m2.p;
+        M.nslots = d.nslots;
+        M.S = F.S;
+        M.first = R.first;
+        M.have_chunk = 1;
+        M.G = G;
+        if (int32_t rc = timed(d, EV_MOMENTS, [&] {
+                if (fr.adaptive) hipLaunchKernelGGL(ptk::moments_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M, AT);
+                else hipLaunchKernelGGL(ptk::moments_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M);
+            }))
+            return rc;
+    }
+    d.acc_started = true;
     return PT_OK;
 }
 
@@ -1135,10 +1406,9 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     // jobs a wave claims per pop of the item cursor: 256, and 512 for the bitmask scans once a pass holds 128 samples per pixel
     // or more (same-box sweeps, profiles/r02_claim_sweep.txt: C4 at 265 spp per pass 664 / 653 / 654 / 659 / 673 ms for 256 / 512 /
     // 1024 / 2048 / 4096, at 79 spp per pass 677 / 675 / 678 ms; the BVH path loses 3 % at 512 and 7 % at 1024)
-    {
-        const bool bvh_scan = fr.scan == ptk::SCAN_BVH || fr.scan == ptk::SCAN_VERIFY_BVH;
-        F.claim = ctx->claim ? ctx->claim : (!bvh_scan && S >= 128u) ? 512u : 256u;
-    }
+    const bool bvh_scan = fr.scan == ptk::SCAN_BVH || fr.scan == ptk::SCAN_VERIFY_BVH;
+    F.claim = ctx->claim ? ctx->claim : (!bvh_scan && S >= 128u) ? 512u : 256u;
+    unsigned int *qw = d.queue.p;
     TraceBuffers B;
     B.objs = d.objs.p;
     B.mats = d.mats.p;
@@ -1154,7 +1424,7 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     B.ray_ndraw = d.ray_ndraw.p;
     B.job_seg = fr.stats_on ? d.job_seg.p : nullptr;
     B.job_draw = fr.stats_on ? d.job_draw.p : nullptr;
-    B.queue = d.queue.p;
+    B.queue = qw;
     B.counters = d.counters.p;
     B.prof = ctx->profile_sections ? d.prof.p : nullptr;
     const bool timeline = !ctx->profile_sections && std::getenv("PTCORE_DEBUG_TIMELINE") != nullptr;  // diagnostics: when each wave of a trace launch retires
@@ -1162,277 +1432,31 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         HIP_TRY(d.prof.reserve(65536));
         B.prof = d.prof.p;
     }
-
-    const int rounds = fr.split_rounds;
+    B.cont_in = qw + 4;
+    B.bsph_diel = d.bsph_diel.p;
+    B.bbox_diel = d.bbox_diel.p;
+    // the queues of the split passes and of the primary pass (step_trace sets where the continuation queue's entries are counted)
+    std::memset(&B.glass, 0, sizeof B.glass);
+    std::memset(&B.cont, 0, sizeof B.cont);
+    if (fr.split_rounds > 0) B.glass = d.q_glass.bind(d.q_cap, fr.stats_on, nullptr);
+    if (fr.split_rounds > 0 || fr.primary_pass) {
+        B.cont = d.q_cont.bind(d.q_cap, fr.stats_on, nullptr);
+        B.glass.count = qw + 1;
+    }
     if (!d.first_recorded) {
         HIP_TRY(hipEventRecord(d.ev_first, d.stream));
         d.first_recorded = true;
     }
-    // queue words: [0] item cursor of the running trace pass, [1] glass entries, [2],[3] continuation entries (one is
-    // read by a trace pass while glass_kernel fills the other), [4] stays 0 (a first pass starts from no continuations)
-    unsigned int *qw = d.queue.p;
-    B.cont_in = qw + 4;
-    B.bsph_diel = d.bsph_diel.p;
-    B.bbox_diel = d.bbox_diel.p;
-    std::memset(&B.glass, 0, sizeof B.glass);
-    std::memset(&B.cont, 0, sizeof B.cont);
-    if (rounds > 0 || fr.primary_pass) {
-        const size_t cap = d.q_cap;
-        auto bind = [&](PathQueue &q, DevBuf<double> &qd, DevBuf<unsigned long long> &qrs, DevBuf<uint32_t> &qu) {
-            q.d = qd.p;
-            q.rs = qrs.p;
-            q.job = qu.p;
-            q.depth = reinterpret_cast<int32_t *>(qu.p + cap);
-            q.best = reinterpret_cast<int32_t *>(qu.p + 2 * cap);
-            q.hit = reinterpret_cast<int32_t *>(qu.p + 3 * cap);
-            q.jseg = fr.stats_on ? qu.p + 4 * cap : nullptr;
-            q.jdraw = fr.stats_on ? qu.p + 5 * cap : nullptr;
-            q.cap = (uint32_t)cap;
-        };
-        if (rounds > 0) bind(B.glass, d.gq_d, d.gq_rs, d.gq_u32);
-        bind(B.cont, d.cq_d, d.cq_rs, d.cq_u32);
-        B.glass.count = qw + 1;
-    }
-    if (fr.gl) {  // GL shading: one pass per job, camera rays made in the kernel (pt_glshade.h)
-        ptk::GlArgs GA;
-        std::memset(&GA, 0, sizeof GA);
-        ptg::GlScene &GS = GA.S;
-        GS.objs = d.gl_objs.p;
-        GS.mats = d.gl_mats.p;
-        GS.lights = d.gl_lights.p;
-        GS.nobj = (int32_t)fr.gl_objs.size();
-        GS.nlight = (int32_t)fr.gl_lights.size();
-        GS.sky = fr.gl_sky;
-        GS.cam = fr.gl_cam;
-        GS.max_depth = fr.cfg.max_depth;
-        GS.width = G.width;
-        GS.height = G.height;
-        GS.fog_on = fr.fog_vol ? 1 : 0;
-        GS.fog = fr.fog;
-        GS.fog_objs = d.objs.p;
-        GS.fog_lights = d.fog_lights.p;
-        GS.fog_nobj = fr.nobj;
-        GS.fog_nlight = (int32_t)fr.fog_lights.size();
-        GA.L = d.L.p;
-        GA.counters = d.counters.p;
-        GA.gl_counters = d.gl_counters.p;
-        GA.fog_counters = fr.fog_vol ? d.fog_counters.p : nullptr;
-        GA.key = ptm::seed_key(fr.cfg.seed ^ PTG_STREAM_SALT);
-        GA.fog_key = ptm::seed_key(fr.cfg.seed ^ PTF_STREAM_SALT);
-        GA.njobs = F.njobs;
-        GA.nS = S;
-        GA.s0 = s0;
-        GA.ntx = G.ntx;  // (the frame size is GS's)
-        GA.shard_index = G.shard_index;
-        GA.shard_count = G.shard_count;
-        if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
-        d.trace_is_split[d.n_trace] = 0;
-        if (int32_t rc = timed(d, d.ev_trace, d.n_trace, [&] {
-                hipLaunchKernelGGL(ptk::gl_trace_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, GA);
-            }))
-            return rc;
+    if (fr.gl) {
+        if (int32_t rc = step_gl(ctx, d, F, G)) return rc;
     } else {  // ray generation, then the trace passes (which also handle max_depth <= 0: black samples, camera draws counted)
         HIP_TRY(hipMemsetAsync(qw, 0, 8 * sizeof(unsigned int), d.stream));
-        const size_t lds = fr.lds_bytes;
-        const uint32_t waves_needed = (F.njobs + 63u) / 64u;
-        const char *rg_form = std::getenv("PTCORE_RAYGEN");  // A/B: "column" = round 2's walk down a lane's column, "simple" = one job per lane
-        const bool rg_simple = std::getenv("PTCORE_RAYGEN_SIMPLE") || (rg_form && !std::strcmp(rg_form, "simple"));
-        if (int32_t rc = timed(d, d.ev_raygen, d.n_raygen, [&] {
-                if (fr.adaptive)
-                    hipLaunchKernelGGL(ptk::raygen_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, F, fr.cam,
-                                       d.ray.p, d.ray_rng.p, d.ray_ndraw.p, AT.active);
-                else if (fr.cam.lens_radius > 0 && !rg_simple && !(rg_form && !std::strcmp(rg_form, "column")))  // thin lens: the rejection loop over a wave's pool of jobs
-                    hipLaunchKernelGGL(ptk::raygen_lens_pool_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_POOL_ROWS - 1) / (PT_BLOCK * PT_RG_POOL_ROWS)), dim3(PT_BLOCK), 0,
-                                       d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
-                else if (fr.cam.lens_radius > 0 && !rg_simple)
-                    hipLaunchKernelGGL(ptk::raygen_lens_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_ROWS - 1) / (PT_BLOCK * PT_RG_ROWS)), dim3(PT_BLOCK), 0,
-                                       d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
-                else
-                    hipLaunchKernelGGL(ptk::raygen_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, F, fr.cam,
-                                       d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
-            }))
-            return rc;
-        if (!ctx->inject_rays.empty()) {  // pt_debug_set_primary_rays: the table's rays over ray generation's
-            if (d.inject_gen != ctx->inject_gen) {
-                HIP_TRY(hipStreamSynchronize(d.stream));
-                HIP_TRY(d.inject.reserve(ctx->inject_rays.size()));
-                HIP_TRY(hipMemcpy(d.inject.p, ctx->inject_rays.data(), ctx->inject_rays.size() * sizeof(double), hipMemcpyHostToDevice));
-                d.inject_gen = ctx->inject_gen;
-            }
-            hipLaunchKernelGGL(ptk::inject_rays_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, F, d.inject.p,
-                               (uint64_t)(ctx->inject_rays.size() / 6), (uint32_t)fr.cfg.samples_per_px, d.ray.p, d.ray_ndraw.p);
-            HIP_TRY(hipGetLastError());
-        }
-        if (fr.wavefront) {
-            if (int32_t rc = dev_step_wavefront(ctx, d, F, B)) return rc;
-        } else {
-        const bool pass_log = std::getenv("PTCORE_DEBUG_PASS_LOG") != nullptr;
-        auto launch_trace = [&](bool split, bool first) -> int32_t {
-            TraceArgs A;
-            A.F = F;
-            A.F.fresh = first ? F.njobs : 0u;
-            A.sky = fr.sky;
-            A.B = B;
-            uint32_t grid = (uint32_t)(d.num_cu * (split ? d.blocks_per_cu_split : d.blocks_per_cu));
-            // (later passes: the item count lives on the device; no pass holds more items than the chunk has jobs, which is also
-            // the bound queue_slack() assumes)
-            grid = std::max(1u, std::min(grid, (waves_needed + 3u) / 4u));
-            if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
-            d.trace_is_split[d.n_trace] = split ? 1 : 0;
-            if (int32_t rc = timed(d, d.ev_trace, d.n_trace, [&] {
-                    hipLaunchKernelGGL(pick_trace(fr.stats_on, ctx->profile_sections, fr.scan, split ? (int)ptk::FORM_SPLIT : fr.tail_form),
-                                       dim3(grid), dim3(PT_BLOCK), lds, d.stream, A);
-                }))
-                return rc;
-            const EventPair &e = d.ev_trace[d.n_trace - 1];
-            if (timeline) {
-                HIP_TRY(hipStreamSynchronize(d.stream));
-                const uint32_t nw = std::min(grid * 4u, 65536u);
-                std::vector<unsigned long long> t(nw);
-                HIP_TRY(hipMemcpy(t.data(), d.prof.p, nw * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                std::sort(t.begin(), t.end());
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, e.a, e.b));
-                auto back = [&](double q) { return (double)(t[nw - 1] - t[(size_t)(q * (nw - 1))]) * 1e-5; };  // ms before the last wave
-                std::fprintf(stderr, "ptcore timeline: %s form %d  %.3f ms, %u waves; before the last wave retired: first %.3f ms, 1 %% %.3f, 10 %% %.3f, 25 %% %.3f, 50 %% %.3f, 75 %% %.3f, 90 %% %.3f, 99 %% %.3f; mean %.3f ms\n",
-                             split ? "trace<split>" : "trace<tail>", split ? 1 : fr.tail_form, ms, nw, back(0.0), back(0.01), back(0.10), back(0.25), back(0.50), back(0.75), back(0.90), back(0.99),
-                             [&] { double a = 0; for (auto v : t) a += (double)(t[nw - 1] - v); return a / nw * 1e-5; }());
-            }
-            if (pass_log) {  // PTCORE_DEBUG_PASS_LOG=1 (diagnostics): what every trace pass did; serialises the stream
-                HIP_TRY(hipStreamSynchronize(d.stream));
-                unsigned long long c[24];
-                HIP_TRY(hipMemcpy(c, d.counters.p, sizeof c, hipMemcpyDeviceToHost));
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, e.a, e.b));
-                unsigned long long *prev = d.pass_log_prev;
-                std::fprintf(stderr, "ptcore pass: %s grid %u  %.3f ms  segments +%llu  exit scans +%llu  parked +%llu  ended here +%llu  continuations in +%llu  -> %.1f Mseg/s\n",
-                             split ? "trace<split>" : "trace<all-in-one>", grid, ms, c[0] - prev[0], c[1] - prev[1], c[5] - prev[5], c[18] - prev[18],
-                             c[7] - prev[7], (double)(c[0] - prev[0]) / (ms * 1e3));
-                std::memcpy(prev, c, sizeof c);
-            }
-            return PT_OK;
-        };
-        if (fr.primary_pass) {
-            // BVH scenes: the first segment of every path by the wave-cooperative kernel (pt_primary.h); what goes on -- and what that
-            // kernel is not meant for, unshaded -- reaches the per-lane loop through the continuation queue
-            B.cont_in = qw + 2;
-            B.cont.count = qw + 2;
-            TraceArgs A;
-            A.F = F;
-            A.F.fresh = 0u;
-            A.sky = fr.sky;
-            A.B = B;
-            const uint32_t pgrid = std::max(1u, std::min((uint32_t)(d.num_cu * d.blocks_per_cu_primary), (F.njobs + PT_BLOCK - 1) / PT_BLOCK));  // same bound as queue_slack()
-            if (d.trace_is_split.size() <= d.n_trace) d.trace_is_split.resize(d.n_trace + 1);
-            d.trace_is_split[d.n_trace] = 0;
-            if (int32_t rc = timed(d, d.ev_trace, d.n_trace, [&] { hipLaunchKernelGGL(pick_primary(fr.stats_on, fr.scan), dim3(pgrid), dim3(PT_BLOCK), 0, d.stream, A); }))
-                return rc;
-            const EventPair &e = d.ev_trace[d.n_trace - 1];
-            if (pass_log) {
-                HIP_TRY(hipStreamSynchronize(d.stream));
-                unsigned long long c[48];
-                HIP_TRY(hipMemcpy(c, d.counters.p, sizeof c, hipMemcpyDeviceToHost));
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, e.a, e.b));
-                std::fprintf(stderr, "ptcore pass: primary<wave> grid %u  %.3f ms  segments shaded %llu  handed on %llu  wave-level node visits %llu over %llu blocks of 64 jobs (%llu more handed over unwalked)\n",
-                             pgrid, ms, c[0] - d.pass_log_prev[0], c[6], c[40], c[41], c[42]);
-                std::memcpy(d.pass_log_prev, c, sizeof d.pass_log_prev);
-            }
-            if (int32_t rc = launch_trace(false, false)) return rc;
-        } else if (rounds == 0) {
-            if (int32_t rc = launch_trace(false, true)) return rc;
-        } else {
-            // Split passes: trace (dielectric hits -> glass queue), glass (-> continuation queue), `rounds` times; what is
-            // still under way then (paths with more than `rounds` dielectric bounces) finishes in the all-in-one form.
-            const uint32_t glass_grid = std::max(1u, std::min((uint32_t)(d.num_cu * d.blocks_per_cu_glass), (F.njobs + PT_BLOCK - 1) / PT_BLOCK));  // same bound as queue_slack()
-            for (int r = 0; r < rounds; r++) {
-                if (r > 0) HIP_TRY(hipMemsetAsync(qw, 0, 2 * sizeof(unsigned int), d.stream));  // cursor and glass count
-                unsigned int *c_in = r == 0 ? qw + 4 : qw + 2 + (r & 1), *c_out = qw + 2 + ((r + 1) & 1);
-                HIP_TRY(hipMemsetAsync(c_out, 0, sizeof(unsigned int), d.stream));
-                B.cont_in = c_in;
-                B.cont.count = c_out;
-                if (int32_t rc = launch_trace(true, r == 0)) return rc;
-                if (!fr.has_glass) break;  // nothing can have entered the glass queue: the frame is done
-                if (int32_t rc = timed(d, d.ev_glass, d.n_glass, [&] {
-                        ptk::GlassArgs GA;
-                        GA.F = F;
-                        GA.B = B;
-                        hipLaunchKernelGGL(pick_glass(fr.stats_on, fr.scan), dim3(glass_grid), dim3(PT_BLOCK), fr.glass_lds_bytes, d.stream, GA);
-                    }))
-                    return rc;
-            }
-            if (fr.has_glass) {
-                HIP_TRY(hipMemsetAsync(qw, 0, sizeof(unsigned int), d.stream));
-                B.cont_in = qw + 2 + (rounds & 1);
-                B.cont.count = qw + 5;  // unused by the all-in-one form
-                if (int32_t rc = launch_trace(false, false)) return rc;
-            }
-        }
-        }
+        if (int32_t rc = step_raygen(ctx, d, F, AT.active)) return rc;
+        if (int32_t rc = fr.wavefront ? dev_step_wavefront(ctx, d, F, B) : step_trace(ctx, d, F, B, timeline)) return rc;
+        if (fr.fog_vol)  // (GL shading adds the term itself)
+            if (int32_t rc = step_fog(ctx, d, F, G, AT.active)) return rc;
     }
-    if (fr.fog_vol && !fr.gl) {  // the fog's in-scatter term into the chunk's radiance records (pt_fog.h; GL shading adds it itself)
-        ptk::FogArgs FA;
-        std::memset(&FA, 0, sizeof FA);
-        FA.P = fr.fog;
-        FA.objs = d.objs.p;
-        FA.lights = d.fog_lights.p;
-        FA.ray = d.ray.p;
-        FA.ray_ndraw = d.ray_ndraw.p;
-        FA.L = d.L.p;
-        FA.counters = d.fog_counters.p;
-        FA.fog_key = ptm::seed_key(fr.cfg.seed ^ PTF_STREAM_SALT);
-        FA.nobj = fr.nobj;
-        FA.nlight = (int32_t)fr.fog_lights.size();
-        FA.njobs = F.njobs;
-        FA.S = S;
-        FA.s0 = s0;
-        FA.G = G;
-        if (int32_t rc = timed(d, d.ev_fog, d.n_fog, [&] {
-                if (fr.adaptive) hipLaunchKernelGGL(ptk::fog_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA, AT.active);
-                else hipLaunchKernelGGL(ptk::fog_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA);
-            }))
-            return rc;
-    }
-    ptk::ResolveArgs R;
-    std::memset(&R, 0, sizeof R);
-    R.L = d.L.p;
-    R.job_seg = B.job_seg;
-    R.job_draw = B.job_draw;
-    R.acc = d.acc.p;
-    R.acc_seg = fr.stats_on ? d.acc_seg.p : nullptr;
-    R.acc_draw = fr.stats_on ? d.acc_draw.p : nullptr;
-    R.nslots = d.nslots;
-    R.njobs = F.njobs;
-    R.S = S;
-    R.first = d.acc_started ? 0 : 1;
-    R.finish = 0;
-    R.have_chunk = 1;
-    R.inv_samples = 0;
-    R.G = G;
-    const uint32_t add_grid = ((fr.adaptive ? d.nact * 64u : d.nslots) + PT_BLOCK - 1) / PT_BLOCK;
-    if (int32_t rc = timed(d, d.ev_resolve, d.n_resolve, [&] {
-            if (fr.adaptive) hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R, AT);
-            else hipLaunchKernelGGL(ptk::resolve_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R);
-        }))
-        return rc;
-    if (fr.moments) {  // the squares of the same records, in the same order (pt_set_moments)
-        ptk::MomentsArgs M;
-        std::memset(&M, 0, sizeof M);
-        M.L = d.L.p;
-        M.m2 = d.m2.p;
-        M.nslots = d.nslots;
-        M.S = S;
-        M.first = R.first;
-        M.have_chunk = 1;
-        M.G = G;
-        if (int32_t rc = timed(d, d.ev_moments, d.n_moments, [&] {
-                if (fr.adaptive) hipLaunchKernelGGL(ptk::moments_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M, AT);
-                else hipLaunchKernelGGL(ptk::moments_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M);
-            }))
-            return rc;
-    }
-    d.acc_started = true;
-    return PT_OK;
+    return step_accumulate(ctx, d, F, G, AT);
 }
 
 // The check that ends a pt_step of an adaptive frame, on one device: block_noise_kernel (counts, noise, decision per active block),
@@ -1463,7 +1487,7 @@ int32_t dev_adaptive_check(pt_ctx *ctx, Device &d, ptk::AdaptResult *host_res) {
     K.next = d.act[d.act_cur ^ 1].p;
     K.res = d.ad_res.p;
     K.nact = d.nact;
-    if (int32_t rc = timed(d, d.ev_check, d.n_check, [&] {  // the two as one
+    if (int32_t rc = timed(d, EV_CHECK, [&] {  // the two as one
             hipLaunchKernelGGL(ptk::block_noise_kernel, dim3((d.nact * 64u + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, A);
             hipLaunchKernelGGL(ptk::compact_kernel, dim3(1), dim3(PT_COMPACT_BLOCK), 0, d.stream, K);
         }))
@@ -1512,7 +1536,7 @@ int32_t dev_finish(pt_ctx *ctx, Device &d, int32_t spp_done, uint8_t *tiles_rgba
     R.inv_samples = 1.0 / (double)spp_done;  // renderer.go:97
     R.gl_spp = fr.gl ? std::max(1, spp_done) : 0;  // GL shading: tone-mapped finish of accum / passes
     R.G = tile_geom(fr, d);
-    if (int32_t rc = timed(d, d.ev_resolve, d.n_resolve, [&] {
+    if (int32_t rc = timed(d, EV_RESOLVE, [&] {
             if (fr.adaptive)  // every pixel by the count of its own block
                 hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R,
                                    ptk::AdaptTable{d.act[d.act_cur].p, d.blk_spp.p, d.nact});
@@ -1554,22 +1578,23 @@ int32_t dev_collect(Device &d, pt_stats *st, int slot) {
     if (d.prof.p && slot == 0)
         HIP_TRY(hipMemcpy(g_profile_scratch, d.prof.p, sizeof g_profile_scratch, hipMemcpyDeviceToHost));
     double tr = 0, rs = 0, trs = 0, gl = 0, rg = 0;
-    if (int32_t rc = sum_ms(d.ev_trace, d.n_trace, tr, &d.trace_is_split, &trs)) return rc;
-    if (int32_t rc = sum_ms(d.ev_glass, d.n_glass, gl)) return rc;
-    if (int32_t rc = sum_ms(d.ev_resolve, d.n_resolve, rs)) return rc;
-    if (int32_t rc = sum_ms(d.ev_raygen, d.n_raygen, rg)) return rc;
+    const size_t n_trace = d.ev[EV_TRACE].n;
+    if (int32_t rc = sum_ms(d.ev[EV_TRACE], tr, &d.trace_is_split, &trs)) return rc;
+    if (int32_t rc = sum_ms(d.ev[EV_GLASS], gl)) return rc;
+    if (int32_t rc = sum_ms(d.ev[EV_RESOLVE], rs)) return rc;
+    if (int32_t rc = sum_ms(d.ev[EV_RAYGEN], rg)) return rc;
     st->glass_ms = std::max(st->glass_ms, gl);
     st->trace_split_ms = std::max(st->trace_split_ms, trs);
-    st->glass_launches += (int32_t)d.n_glass;
-    for (size_t i = 0; i < d.n_trace && i < d.trace_is_split.size(); i++) st->trace_split_launches += d.trace_is_split[i] ? 1 : 0;
+    st->glass_launches += (int32_t)d.ev[EV_GLASS].n;
+    for (size_t i = 0; i < n_trace && i < d.trace_is_split.size(); i++) st->trace_split_launches += d.trace_is_split[i] ? 1 : 0;
     st->raygen_ms = std::max(st->raygen_ms, rg);
     float span = 0;
     if (d.first_recorded) HIP_TRY(hipEventElapsedTime(&span, d.ev_first, d.ev_last));
     st->trace_ms = std::max(st->trace_ms, tr);
     st->resolve_ms = std::max(st->resolve_ms, rs);
     st->device_ms = std::max(st->device_ms, (double)span);
-    st->trace_launches += (int32_t)d.n_trace;
-    st->resolve_launches += (int32_t)d.n_resolve;
+    st->trace_launches += (int32_t)n_trace;
+    st->resolve_launches += (int32_t)d.ev[EV_RESOLVE].n;
     if (slot < 8) st->per_device_ms[slot] = span;
     return PT_OK;
 }
@@ -1852,7 +1877,9 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
     // chunk of samples per pass: bounded by the L budget and by 2^31 jobs
     uint32_t chunk = cfg->spp_chunk > 0 ? (uint32_t)cfg->spp_chunk : 0;
     const uint32_t slots = std::max(1u, max_slots);
-    // per job: 32 B radiance record + 58 B primary ray, and with split passes two path-state queues of 100 B per entry
+    // per job: 32 B radiance record + 58 B primary ray, and with split passes two path-state queues of 100 B per entry.  A first guess,
+    // coarser than the plan on purpose (no window slack, no pixel stats): dev_begin prices the pass from pass_plan() and shrinks it
+    // where the guess was too large.
     const size_t job_bytes = 90 + (fr.wavefront ? 330 + (fr.walk32 ? 4 * (PT_CAND_MAX + 2) : 0) : fr.split_rounds > 0 && fr.has_glass ? 220 : fr.primary_pass ? 110 : 0);
     fr.budget_bytes = ctx->l_budget_bytes;
     if (ctx->auto_grow && ctx->grown_budget_bytes > fr.budget_bytes && !ctx->devs.empty()) {
@@ -1889,7 +1916,7 @@ int32_t collect_fog(pt_ctx *ctx) {
     std::memset(&fs, 0, sizeof fs);
     for (size_t i = 0; i < ctx->devs.size() && !(first_only && i > 0); i++) {
         Device &d = ctx->devs[i];
-        if (d.n_fog == 0 && !(ctx->frame.gl && d.n_trace > 0)) continue;  // GL shading: the term ran inside gl_trace_kernel
+        if (d.ev[EV_FOG].n == 0 && !(ctx->frame.gl && d.ev[EV_TRACE].n > 0)) continue;  // GL shading: the term ran inside gl_trace_kernel
         HIP_TRY(hipSetDevice(d.ordinal));
         HIP_TRY(hipStreamSynchronize(d.stream));
         unsigned long long c[3] = {};
@@ -1898,9 +1925,9 @@ int32_t collect_fog(pt_ctx *ctx) {
         fs.draws += c[1];
         fs.steps += c[2];
         double ms = 0;
-        if (int32_t rc = sum_ms(d.ev_fog, d.n_fog, ms)) return rc;
+        if (int32_t rc = sum_ms(d.ev[EV_FOG], ms)) return rc;
         fs.fog_ms = std::max(fs.fog_ms, ms);
-        fs.fog_launches += (int32_t)d.n_fog;
+        fs.fog_launches += (int32_t)d.ev[EV_FOG].n;
     }
     ctx->fog_last = fs;
     return PT_OK;
@@ -1915,7 +1942,7 @@ int32_t collect_shading(pt_ctx *ctx) {
     std::memset(&ss, 0, sizeof ss);
     for (size_t i = 0; i < ctx->devs.size() && !(first_only && i > 0); i++) {
         Device &d = ctx->devs[i];
-        if (d.n_trace == 0 || !d.gl_counters.p) continue;
+        if (d.ev[EV_TRACE].n == 0 || !d.gl_counters.p) continue;
         HIP_TRY(hipSetDevice(d.ordinal));
         HIP_TRY(hipStreamSynchronize(d.stream));
         unsigned long long c[5] = {};
@@ -1926,9 +1953,9 @@ int32_t collect_shading(pt_ctx *ctx) {
         ss.probe_rays += c[3];
         ss.draws += c[4];
         double ms = 0;
-        if (int32_t rc = sum_ms(d.ev_trace, d.n_trace, ms)) return rc;
+        if (int32_t rc = sum_ms(d.ev[EV_TRACE], ms)) return rc;
         ss.gl_ms = std::max(ss.gl_ms, ms);
-        ss.gl_launches += (int32_t)d.n_trace;
+        ss.gl_launches += (int32_t)d.ev[EV_TRACE].n;
     }
     ctx->shading_last = ss;
     return PT_OK;
@@ -2247,42 +2274,21 @@ void pt_destroy(pt_ctx *ctx) {
         // (the library stays mapped: RCCL keeps threads and device state of its own that a dlclose would pull away under them)
         ctx->rccl.lib = nullptr;
     }
+    // each device's memory and events are freed with that device current, after its stream has drained: Device() takes them over
+    // in the assignment and dies with them there.  Then the context's own planes, which live on the first device, with the context.
+    const int first = ctx->devs.empty() ? 0 : ctx->devs[0].ordinal;
     for (Device &d : ctx->devs) {
-        if (hipSetDevice(d.ordinal) != hipSuccess) continue;
-        if (d.own_stream) (void)hipStreamSynchronize(d.own_stream);
-        d.ray.release(); d.ray_rng.release(); d.ray_ndraw.release(); d.inject.release();
-        d.objs.release(); d.mats.release(); d.bsph.release(); d.bbox.release(); d.plane_idx.release(); d.bvh_nodes.release(); d.bvh_objs.release(); d.bvh_cores.release(); d.L.release(); d.job_seg.release(); d.job_draw.release();
-        d.prof.release();
-        d.bsph_diel.release(); d.bbox_diel.release();
-        d.gq_d.release(); d.cq_d.release(); d.gq_rs.release(); d.cq_rs.release(); d.gq_u32.release(); d.cq_u32.release();
-        d.xq_d.release(); d.xq_rs.release(); d.xq_u32.release();
-        d.wf_perm.release(); d.wf_key.release(); d.wf_bins.release();
-        d.cand_ids.release(); d.cand_n.release(); d.slow_list.release();
-        for (EventPair &e : d.ev_glass) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        d.acc.release(); d.acc_seg.release(); d.acc_draw.release(); d.tiles_rgba.release();
-        d.m2.release(); d.tiles_m2.release(); d.noise_part.release();
-        d.act[0].release(); d.act[1].release(); d.blk_spp.release(); d.blk_keep.release(); d.blk_noise.release(); d.ad_res.release();
-        d.tiles_accum.release(); d.tiles_seg.release(); d.tiles_draw.release(); d.queue.release();
-        d.counters.release();
-        for (EventPair &e : d.ev_trace) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        for (EventPair &e : d.ev_resolve) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        for (EventPair &e : d.ev_raygen) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        for (EventPair &e : d.ev_fog) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        for (EventPair &e : d.ev_moments) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        for (EventPair &e : d.ev_check) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        d.fog_lights.release(); d.fog_counters.release();
-        d.gl_objs.release(); d.gl_mats.release(); d.gl_lights.release(); d.gl_counters.release();
-        if (d.ev_first) (void)hipEventDestroy(d.ev_first);
-        if (d.ev_last) (void)hipEventDestroy(d.ev_last);
-        if (d.own_stream) (void)hipStreamDestroy(d.own_stream);
+        g_leave_device_memory = hipSetDevice(d.ordinal) != hipSuccess;
+        const hipStream_t own = g_leave_device_memory ? nullptr : d.own_stream;
+        if (own) (void)hipStreamSynchronize(own);
+        if (d.ev_first && !g_leave_device_memory) (void)hipEventDestroy(d.ev_first);
+        if (d.ev_last && !g_leave_device_memory) (void)hipEventDestroy(d.ev_last);
+        d = Device();
+        if (own) (void)hipStreamDestroy(own);
     }
-    if (!ctx->devs.empty() && hipSetDevice(ctx->devs[0].ordinal) == hipSuccess) {
-        ctx->g_tiles_m2.release(); ctx->f_m2.release();
-        ctx->g_tiles_rgba.release(); ctx->g_tiles_accum.release(); ctx->g_tiles_seg.release();
-        ctx->g_tiles_draw.release(); ctx->f_rgba.release(); ctx->f_accum.release(); ctx->f_seg.release();
-        ctx->f_draw.release();
-    }
+    g_leave_device_memory = hipSetDevice(first) != hipSuccess;
     delete ctx;
+    g_leave_device_memory = false;
 }
 
 int32_t pt_post_process(pt_ctx *ctx, const pt_post_config *post, const double *accum, int32_t spp, uint8_t *rgba, int32_t stride,
@@ -2593,30 +2599,20 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
     }
     fill_stats_common(ctx, &st);
     ctx->frame.open = false;
-    if (ctx->frame.moments && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) {
-        double mm = 0;
+    auto report = [&](EventKind kind, const char *what) {  // PTCORE_VERBOSE: the slowest device's time in the launches of one kind
+        double worst = 0;
         size_t launches = 0;
         for (Device &d : ctx->devs) {
             double ms = 0;
-            if (hipSetDevice(d.ordinal) == hipSuccess) (void)sum_ms(d.ev_moments, d.n_moments, ms);
-            mm = std::max(mm, ms);
-            launches += d.n_moments;
+            if (hipSetDevice(d.ordinal) == hipSuccess) (void)sum_ms(d.ev[kind], ms);
+            worst = std::max(worst, ms);
+            launches += d.ev[kind].n;
         }
-        std::fprintf(stderr, "ptcore: moments_kernel %.3f ms in %zu launches (resolve_kernel %.3f ms in %d)\n", mm, launches, st.resolve_ms,
-                     st.resolve_launches);
-    }
-    if (ctx->frame.adaptive && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) {
-        double cm = 0;
-        size_t launches = 0;
-        for (Device &d : ctx->devs) {
-            double ms = 0;
-            if (hipSetDevice(d.ordinal) == hipSuccess) (void)sum_ms(d.ev_check, d.n_check, ms);
-            cm = std::max(cm, ms);
-            launches += d.n_check;
-        }
-        std::fprintf(stderr, "ptcore: adaptive check %.3f ms in %zu launches of block_noise_kernel + compact_kernel (resolve_kernel %.3f ms in %d)\n", cm,
-                     launches, st.resolve_ms, st.resolve_launches);
-    }
+        std::fprintf(stderr, "ptcore: %s %.3f ms in %zu launches%s (resolve_kernel %.3f ms in %d)\n", what, worst, launches,
+                     kind == EV_CHECK ? " of block_noise_kernel + compact_kernel" : "", st.resolve_ms, st.resolve_launches);
+    };
+    if (ctx->frame.moments && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_MOMENTS, "moments_kernel");
+    if (ctx->frame.adaptive && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_CHECK, "adaptive check");
     if (ctx->frame.fog_vol) {
         ctx->fog_pending = 1;
         if (int32_t r = collect_fog(ctx)) rc = rc != PT_OK ? rc : r;

@@ -1,6 +1,7 @@
 """Job-buffer budget (PTCORE_L_BUDGET_MB, DESIGN 8 "Passes per frame"): the samples per pass follow from it, the frame does not
 (ordered accumulation); a device that cannot give the budget halves the pass until the buffers fit and keeps that size for the
-frames that follow instead of trying the full budget again on every frame."""
+frames that follow instead of trying the full budget again on every frame.  The per-pass memory plan behind it (pass_plan in
+csrc/ptcore.hip: what a job and a queue entry cost in each form of the loop) is pinned through pt_stats.spp_chunk."""
 import numpy as np
 import pytest
 
@@ -107,3 +108,75 @@ def test_a_context_grows_its_job_buffers_on_the_second_frame_of_one_shape(monkey
             img = np.zeros((h, w, 4), np.uint8)
             chunks.append(hip.render(sc, hip.RenderConfig(w, h, spp, depth, 4), img, ctx=ctx)["spp_chunk"])
         assert chunks[0] == chunks[1] == frames[0][1] and np.array_equal(img, frames[0][0])
+
+
+# ---------------------------------------------------------------- the per-pass memory plan, through spp_chunk
+#
+# 70 x 45 frames: 3 x 2 tiles with both edges ragged, 6144 pixel slots.  What a sample of a pass costs (dev_begin):
+#   90 B per job, 98 B with pixel stats; 104 B per queue entry (80 + 8 + 4 x 4 planes), 112 B with pixel stats (6 planes);
+#   a queue holds one entry per job + the window slack of queue_slack(): 24 blocks x 4 waves x 1024 slots per writer pass
+#   and sample here, where num_cu x blocks per CU >= 240 (an MI355X has 256 CUs).
+# The expected samples per pass follow frame_open's first guess, dev_begin's shrink loop and balance_chunk by hand:
+#   no queues        4 MiB / (6144 x 90 B) = 7.6 -> 7; with stats 7 x 6144 x 98 B is over 4 MiB, 6 fit, 20 spp in 4 passes -> 5
+#   split, 2 queues  6144 x 90 + 2 x 104448 x 104 = 22 278 144 B per sample: 3 fit in 80 MiB, 4 (89 112 576 B) do not;
+#                    with stats 6144 x 98 + 2 x 104448 x 112 = 23 998 464 B: 3 again
+#   primary pass, 1  552 960 + 104448 x 104 = 11 415 552 B per sample: 3 fit in 40 MiB
+#   wavefront, 3     two writer passes, twice the slack: 552 960 + 3 x 202752 x 104 = 63 811 584 B per sample: 3 fit in 200 MiB
+_W, _H = 70, 45
+PLAN_CASES = {  # name: (scene, environment, budget MiB, spp, depth, pixel stats, spp_chunk, trace_launches or None, has queues)
+    "no_queues": ("example_simple", {"PTCORE_SPLIT_ROUNDS": "0"}, 4, 20, 4, False, 7, 3, False),
+    "no_queues_stats": ("example_simple", {"PTCORE_SPLIT_ROUNDS": "0"}, 4, 20, 4, True, 5, 4, False),
+    "split": ("gpu_showcase", {}, 80, 10, 8, False, 3, None, True),
+    "split_stats": ("gpu_showcase", {}, 80, 10, 8, True, 3, None, True),
+    # the same two, the budget a MiB either side of three samples (66 834 432 B = 63.7 MiB; with stats 71 995 392 B = 68.7 MiB):
+    # a queue entry priced one 4-byte plane higher or lower (626 688 entries in a pass of three samples) moves one of each pair
+    "split_64": ("gpu_showcase", {}, 64, 10, 8, False, 3, None, True),
+    "split_63": ("gpu_showcase", {}, 63, 10, 8, False, 2, None, True),
+    "split_stats_69": ("gpu_showcase", {}, 69, 10, 8, True, 3, None, True),
+    "split_stats_68": ("gpu_showcase", {}, 68, 10, 8, True, 2, None, True),
+    "primary": ("synth_300_6", {}, 40, 10, 8, False, 3, None, True),
+    "wavefront": ("gpu_showcase", {"PTCORE_PIPELINE": "wavefront"}, 200, 10, 8, False, 3, None, True),
+}
+_reference = {}  # (scene, environment, spp, depth) -> the frame under the default budget, rendered once
+
+
+def _small_frame(monkeypatch, name, env, budget_mb, spp, depth, stats):
+    from path_trace_golang_amd import capi, hip, scene, synth
+
+    for k in ("PTCORE_SPLIT_ROUNDS", "PTCORE_PIPELINE", "PTCORE_L_BUDGET_MB"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    if budget_mb is not None:
+        monkeypatch.setenv("PTCORE_L_BUDGET_MB", str(budget_mb))
+    sc = hip.FlatScene(synth.make_scene(300, 6) if name == "synth_300_6" else scene.load(scene_path(name)))
+    img = np.zeros((_H, _W, 4), np.uint8)
+    acc = np.zeros((_H, _W, 3))
+    nseg, ndraw = (np.zeros((_H, _W), np.uint32), np.zeros((_H, _W), np.uint32)) if stats else (None, None)
+    with capi.Context(ndev=1) as ctx:  # the budget is read by pt_create
+        st = hip.render(sc, hip.RenderConfig(_W, _H, spp, depth, 7, 0, capi.PT_FLAG_PIXEL_STATS if stats else 0), img, None, acc, nseg,
+                        ndraw, ctx=ctx)
+    return st, img, acc
+
+
+@pytest.mark.parametrize("case", list(PLAN_CASES))
+def test_the_samples_per_pass_follow_the_memory_plan(monkeypatch, case):
+    import torch
+
+    name, env, budget_mb, spp, depth, stats, chunk, launches, queues = PLAN_CASES[case]
+    if queues:  # the window slack is 24 blocks per sample only with that many writer blocks on the device
+        assert torch.cuda.get_device_properties(0).multi_processor_count >= 240
+    key = (name, tuple(sorted(env.items())), spp, depth)
+    if key not in _reference:
+        _reference[key] = _small_frame(monkeypatch, name, env, None, spp, depth, False)
+    st_ref, img_ref, acc_ref = _reference[key]
+    st, img, acc = _small_frame(monkeypatch, name, env, budget_mb, spp, depth, stats)
+    print(case, "spp_chunk", st["spp_chunk"], "trace_launches", st["trace_launches"], "default budget:", st_ref["spp_chunk"])
+    assert st_ref["spp_chunk"] == spp
+    assert st["spp_chunk"] == chunk
+    if launches is not None:
+        assert st["trace_launches"] == launches
+    for k in ("samples", "segments", "exit_scans", "draws"):
+        assert st[k] == st_ref[k], k
+    assert np.array_equal(img, img_ref)
+    assert np.array_equal(acc, acc_ref, equal_nan=True)  # same additions in the same order, whatever the pass size
