@@ -1369,86 +1369,67 @@ __device__ __forceinline__ void job_pixel(const DevFrame &F, uint32_t q, uint32_
 // camera.getRay with the lens rejection loop (camera.go:60-74, math.go:74-84).  Writes the primary
 // ray (6 doubles, SoA), the stream state after the draws, and the number of draws used (0xffff marks a
 // job whose pixel lies outside the frame).
-__global__ __launch_bounds__(PT_BLOCK) void raygen_kernel(const DevFrame F, const DevCamera cam, double *__restrict__ ray,
-                                                            unsigned long long *__restrict__ ray_rng,
-                                                            uint16_t *__restrict__ ray_ndraw) {
-    const uint32_t myjob = blockIdx.x * PT_BLOCK + threadIdx.x;
-    if (myjob >= F.njobs) return;
-    // job -> (tile, sub-block, sample, pixel)
-    const uint32_t p = myjob & 63u;
-    const uint32_t q = __builtin_amdgcn_readfirstlane(myjob >> 6);  // the wave's row of 64 jobs: tile, sub-block and sample are wave-uniform (scalar unit)
-    uint32_t x, y, sl;
-    job_pixel(F, q, p, x, y, sl);
-    if (!(x < (uint32_t)F.width && y < (uint32_t)F.height)) {
-        ray_ndraw[myjob] = 0xffffu;
-        return;
-    }
-    uint32_t nd = 0;
+//
+// The camera arithmetic stands ONCE, in the three pieces below; every form of ray generation (raygen_kernel and its adaptive twin,
+// raygen_lens_kernel, raygen_lens_pool_kernel) is built from them, so an expression that must round like the reference's camera is
+// corrected in one place for all three PTCORE_RAYGEN forms.  All values travel in registers.
+
+// A job's camera sample up to the lens: the stream state after the u and v draws (two draws) and the point on the focus plane.
+struct CameraSample {
+    uint64_t rs;
+    double ax, ay, az;
+};
+__device__ __forceinline__ CameraSample camera_sample(const DevFrame &F, const DevCamera &cam, uint32_t x, uint32_t y, uint32_t sl) {
+    CameraSample c;
     const uint64_t pixel = (uint64_t)y * (uint64_t)(uint32_t)F.width + (uint64_t)x;
-    uint64_t rs = ptm::stream_init(F.seed_key, pixel, (uint64_t)(F.s0 + sl));
-#define RG_DRAW(var) const double var = ptm::stream_next(rs); nd++;
-    RG_DRAW(xi_u)
-    RG_DRAW(xi_v)
+    c.rs = ptm::stream_init(F.seed_key, pixel, (uint64_t)(F.s0 + sl));
+    const double xi_u = ptm::stream_next(c.rs);
+    const double xi_v = ptm::stream_next(c.rs);
     const double u = ((double)x + xi_u) * F.inv_width;
     const double vv = ((F.height_m1 - (double)y) + xi_v) * F.inv_height;
     const double tx_ = cam.lower_left[0] + cam.horizontal[0] * u;
     const double ty_ = cam.lower_left[1] + cam.horizontal[1] * u;
     const double tz_ = cam.lower_left[2] + cam.horizontal[2] * u;
-    const double ax = tx_ + cam.vertical[0] * vv;
-    const double ay = ty_ + cam.vertical[1] * vv;
-    const double az = tz_ + cam.vertical[2] * vv;
-    double ox, oy, oz, dx, dy, dz;
-    if (cam.lens_radius > 0) {
-        double rx, ry, rz;
-        for (;;) {  // randomInUnitSphere
-            RG_DRAW(d0)
-            RG_DRAW(d1)
-            RG_DRAW(d2)
-            rx = d0 * 2 - 1;
-            ry = d1 * 2 - 1;
-            rz = d2 * 2 - 1;
-            const double lenSq = rx * rx + ry * ry + rz * rz;
-            if (lenSq >= 1.0) continue;
-            break;
-        }
-        rx = rx * cam.lens_radius;
-        ry = ry * cam.lens_radius;
-        const double offx = cam.u[0] * rx + cam.v[0] * ry;
-        const double offy = cam.u[1] * rx + cam.v[1] * ry;
-        const double offz = cam.u[2] * rx + cam.v[2] * ry;
-        ox = cam.origin[0] + offx;
-        oy = cam.origin[1] + offy;
-        oz = cam.origin[2] + offz;
-        dx = (ax - cam.origin[0]) - offx;
-        dy = (ay - cam.origin[1]) - offy;
-        dz = (az - cam.origin[2]) - offz;
-    } else {
-        ox = cam.origin[0];
-        oy = cam.origin[1];
-        oz = cam.origin[2];
-        dx = ax - cam.origin[0];
-        dy = ay - cam.origin[1];
-        dz = az - cam.origin[2];
-    }
-#undef RG_DRAW
+    c.ax = tx_ + cam.vertical[0] * vv;
+    c.ay = ty_ + cam.vertical[1] * vv;
+    c.az = tz_ + cam.vertical[2] * vv;
+    return c;
+}
+// The primary ray through the focus-plane point a: from the camera's origin (pinhole), or from the lens point of an accepted
+// sample (rx, ry) of randomInUnitSphere, not yet scaled by the lens radius (camera.go:60-74).
+__device__ __forceinline__ RayD pinhole_ray(const DevCamera &cam, double ax, double ay, double az) {
+    return RayD{cam.origin[0], cam.origin[1], cam.origin[2], ax - cam.origin[0], ay - cam.origin[1], az - cam.origin[2]};
+}
+__device__ __forceinline__ RayD lens_ray(const DevCamera &cam, double ax, double ay, double az, double rx, double ry) {
+    rx = rx * cam.lens_radius;
+    ry = ry * cam.lens_radius;
+    const double offx = cam.u[0] * rx + cam.v[0] * ry;
+    const double offy = cam.u[1] * rx + cam.v[1] * ry;
+    const double offz = cam.u[2] * rx + cam.v[2] * ry;
+    return RayD{cam.origin[0] + offx,        cam.origin[1] + offy,        cam.origin[2] + offz,
+                (ax - cam.origin[0]) - offx, (ay - cam.origin[1]) - offy, (az - cam.origin[2]) - offz};
+}
+// What ray generation leaves per job: the six ray planes, the stream state after the camera's draws and their number (saturating
+// below the 0xffff of a job outside the frame).
+__device__ __forceinline__ void store_primary(const DevFrame &F, double *__restrict__ ray, unsigned long long *__restrict__ ray_rng,
+                                              uint16_t *__restrict__ ray_ndraw, uint32_t job, const RayD &r, uint64_t rs, uint32_t nd) {
     const size_t nj = F.njobs;
-    ray[myjob] = ox;
-    ray[nj + myjob] = oy;
-    ray[2 * nj + myjob] = oz;
-    ray[3 * nj + myjob] = dx;
-    ray[4 * nj + myjob] = dy;
-    ray[5 * nj + myjob] = dz;
-    ray_rng[myjob] = rs;
-    ray_ndraw[myjob] = (uint16_t)(nd < 0xfffeu ? nd : 0xfffeu);
+    ray[job] = r.ox;
+    ray[nj + job] = r.oy;
+    ray[2 * nj + job] = r.oz;
+    ray[3 * nj + job] = r.dx;
+    ray[4 * nj + job] = r.dy;
+    ray[5 * nj + job] = r.dz;
+    ray_rng[job] = rs;
+    ray_ndraw[job] = (uint16_t)(nd < 0xfffeu ? nd : 0xfffeu);
 }
 
-// Adaptive sampling (pt_set_adaptive): raygen_kernel for a chunk whose jobs are those of the active 8x8 blocks only,
-// F.njobs = nact * 64 * S: row q belongs to compact block q / S, whose block index is active[q / S].  A kernel of its own, so that
-// raygen_kernel stays the code it was; thin-lens cameras take this form too in adaptive frames (the rejection loop per lane).
-__global__ __launch_bounds__(PT_BLOCK) void raygen_adaptive_kernel(const DevFrame F, const DevCamera cam, double *__restrict__ ray,
-                                                                     unsigned long long *__restrict__ ray_rng,
-                                                                     uint16_t *__restrict__ ray_ndraw,
-                                                                     const uint32_t *__restrict__ active) {
+// ADAPT (adaptive sampling, pt_set_adaptive): the chunk's jobs are those of the active 8x8 blocks only,
+// F.njobs = nact * 64 * S: row q belongs to compact block q / S, whose block index is active[q / S].
+template <bool ADAPT>
+__device__ __forceinline__ void raygen_body(const DevFrame &F, const DevCamera &cam, double *__restrict__ ray,
+                                            unsigned long long *__restrict__ ray_rng, uint16_t *__restrict__ ray_ndraw,
+                                            const uint32_t *__restrict__ active) {
     const uint32_t myjob = blockIdx.x * PT_BLOCK + threadIdx.x;
     if (myjob >= F.njobs) return;
     // job -> (tile, sub-block, sample, pixel)
@@ -1456,32 +1437,20 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_adaptive_kernel(const DevFram
     const uint32_t q = __builtin_amdgcn_readfirstlane(myjob >> 6);  // the wave's row of 64 jobs: tile, sub-block and sample are wave-uniform (scalar unit)
     uint32_t x, y;
     const uint32_t cblk = q / F.S, sl = q - cblk * F.S;
-    block_pixel(F, active[cblk], p, x, y);  // wave-uniform index: a scalar load
+    block_pixel(F, ADAPT ? active[cblk] : cblk, p, x, y);  // (ADAPT: a wave-uniform index, a scalar load)
     if (!(x < (uint32_t)F.width && y < (uint32_t)F.height)) {
         ray_ndraw[myjob] = 0xffffu;
         return;
     }
-    uint32_t nd = 0;
-    const uint64_t pixel = (uint64_t)y * (uint64_t)(uint32_t)F.width + (uint64_t)x;
-    uint64_t rs = ptm::stream_init(F.seed_key, pixel, (uint64_t)(F.s0 + sl));
-#define RG_DRAW(var) const double var = ptm::stream_next(rs); nd++;
-    RG_DRAW(xi_u)
-    RG_DRAW(xi_v)
-    const double u = ((double)x + xi_u) * F.inv_width;
-    const double vv = ((F.height_m1 - (double)y) + xi_v) * F.inv_height;
-    const double tx_ = cam.lower_left[0] + cam.horizontal[0] * u;
-    const double ty_ = cam.lower_left[1] + cam.horizontal[1] * u;
-    const double tz_ = cam.lower_left[2] + cam.horizontal[2] * u;
-    const double ax = tx_ + cam.vertical[0] * vv;
-    const double ay = ty_ + cam.vertical[1] * vv;
-    const double az = tz_ + cam.vertical[2] * vv;
-    double ox, oy, oz, dx, dy, dz;
+    const CameraSample c = camera_sample(F, cam, x, y, sl);
+    uint64_t rs = c.rs;
+    uint32_t nd = 2;
+    RayD r;
     if (cam.lens_radius > 0) {
         double rx, ry, rz;
         for (;;) {  // randomInUnitSphere
-            RG_DRAW(d0)
-            RG_DRAW(d1)
-            RG_DRAW(d2)
+            const double d0 = ptm::stream_next(rs), d1 = ptm::stream_next(rs), d2 = ptm::stream_next(rs);
+            nd += 3;
             rx = d0 * 2 - 1;
             ry = d1 * 2 - 1;
             rz = d2 * 2 - 1;
@@ -1489,35 +1458,24 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_adaptive_kernel(const DevFram
             if (lenSq >= 1.0) continue;
             break;
         }
-        rx = rx * cam.lens_radius;
-        ry = ry * cam.lens_radius;
-        const double offx = cam.u[0] * rx + cam.v[0] * ry;
-        const double offy = cam.u[1] * rx + cam.v[1] * ry;
-        const double offz = cam.u[2] * rx + cam.v[2] * ry;
-        ox = cam.origin[0] + offx;
-        oy = cam.origin[1] + offy;
-        oz = cam.origin[2] + offz;
-        dx = (ax - cam.origin[0]) - offx;
-        dy = (ay - cam.origin[1]) - offy;
-        dz = (az - cam.origin[2]) - offz;
+        r = lens_ray(cam, c.ax, c.ay, c.az, rx, ry);
     } else {
-        ox = cam.origin[0];
-        oy = cam.origin[1];
-        oz = cam.origin[2];
-        dx = ax - cam.origin[0];
-        dy = ay - cam.origin[1];
-        dz = az - cam.origin[2];
+        r = pinhole_ray(cam, c.ax, c.ay, c.az);
     }
-#undef RG_DRAW
-    const size_t nj = F.njobs;
-    ray[myjob] = ox;
-    ray[nj + myjob] = oy;
-    ray[2 * nj + myjob] = oz;
-    ray[3 * nj + myjob] = dx;
-    ray[4 * nj + myjob] = dy;
-    ray[5 * nj + myjob] = dz;
-    ray_rng[myjob] = rs;
-    ray_ndraw[myjob] = (uint16_t)(nd < 0xfffeu ? nd : 0xfffeu);
+    store_primary(F, ray, ray_rng, ray_ndraw, myjob, r, rs, nd);
+}
+__global__ __launch_bounds__(PT_BLOCK) void raygen_kernel(const DevFrame F, const DevCamera cam, double *__restrict__ ray,
+                                                            unsigned long long *__restrict__ ray_rng,
+                                                            uint16_t *__restrict__ ray_ndraw) {
+    raygen_body<false>(F, cam, ray, ray_rng, ray_ndraw, nullptr);
+}
+// The adaptive form is the same body with the block index read from the active list; thin-lens cameras take this form too in
+// adaptive frames (the rejection loop per lane).  raygen_kernel does not see the list: its instantiation is the code it was.
+__global__ __launch_bounds__(PT_BLOCK) void raygen_adaptive_kernel(const DevFrame F, const DevCamera cam, double *__restrict__ ray,
+                                                                     unsigned long long *__restrict__ ray_rng,
+                                                                     uint16_t *__restrict__ ray_ndraw,
+                                                                     const uint32_t *__restrict__ active) {
+    raygen_body<true>(F, cam, ray, ray_rng, ray_ndraw, active);
 }
 
 // Diagnostics (pt_debug_set_primary_rays): replaces the primary rays ray generation left in the six planes by the caller's table,
@@ -1573,19 +1531,11 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_lens_kernel(const DevFrame F,
             uint32_t x, y, sl;
             job_pixel(F, q, p, x, y, sl);
             if (x < (uint32_t)F.width && y < (uint32_t)F.height) {
-                const uint64_t pixel = (uint64_t)y * (uint64_t)(uint32_t)F.width + (uint64_t)x;
-                uint64_t rs = ptm::stream_init(F.seed_key, pixel, (uint64_t)(F.s0 + sl));
-                const double xi_u = ptm::stream_next(rs);
-                const double xi_v = ptm::stream_next(rs);
-                const double u = ((double)x + xi_u) * F.inv_width;
-                const double vv = ((F.height_m1 - (double)y) + xi_v) * F.inv_height;
-                const double tx_ = cam.lower_left[0] + cam.horizontal[0] * u;
-                const double ty_ = cam.lower_left[1] + cam.horizontal[1] * u;
-                const double tz_ = cam.lower_left[2] + cam.horizontal[2] * u;
-                s_ax[k][tid] = tx_ + cam.vertical[0] * vv;
-                s_ay[k][tid] = ty_ + cam.vertical[1] * vv;
-                s_az[k][tid] = tz_ + cam.vertical[2] * vv;
-                s_rs[k][tid] = rs;
+                const CameraSample c = camera_sample(F, cam, x, y, sl);
+                s_ax[k][tid] = c.ax;
+                s_ay[k][tid] = c.ay;
+                s_az[k][tid] = c.az;
+                s_rs[k][tid] = c.rs;
                 nd0 = 2;
             }
         }
@@ -1615,7 +1565,6 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_lens_kernel(const DevFrame F,
         }
     }
     // ---- C: lens offset, ray, coalesced stores
-    const size_t nj = F.njobs;
 #pragma unroll
     for (int k = 0; k < PT_RG_ROWS; k++) {
         const uint32_t myjob = (row0 + (uint32_t)k) * 64u + lane;
@@ -1625,19 +1574,8 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_lens_kernel(const DevFrame F,
             ray_ndraw[myjob] = 0xffffu;
             continue;
         }
-        const double rx = s_rx[k][tid] * cam.lens_radius;
-        const double ry = s_ry[k][tid] * cam.lens_radius;
-        const double offx = cam.u[0] * rx + cam.v[0] * ry;
-        const double offy = cam.u[1] * rx + cam.v[1] * ry;
-        const double offz = cam.u[2] * rx + cam.v[2] * ry;
-        ray[myjob] = cam.origin[0] + offx;
-        ray[nj + myjob] = cam.origin[1] + offy;
-        ray[2 * nj + myjob] = cam.origin[2] + offz;
-        ray[3 * nj + myjob] = (s_ax[k][tid] - cam.origin[0]) - offx;
-        ray[4 * nj + myjob] = (s_ay[k][tid] - cam.origin[1]) - offy;
-        ray[5 * nj + myjob] = (s_az[k][tid] - cam.origin[2]) - offz;
-        ray_rng[myjob] = s_rs[k][tid];
-        ray_ndraw[myjob] = (uint16_t)(nd < 0xfffeu ? nd : 0xfffeu);
+        store_primary(F, ray, ray_rng, ray_ndraw, myjob, lens_ray(cam, s_ax[k][tid], s_ay[k][tid], s_az[k][tid], s_rx[k][tid], s_ry[k][tid]),
+                      s_rs[k][tid], nd);
     }
 }
 
@@ -1679,19 +1617,11 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_lens_pool_kernel(const DevFra
             uint32_t x, y;
             block_pixel(F, blk, p, x, y);
             if (x < (uint32_t)F.width && y < (uint32_t)F.height) {
-                const uint64_t pixel = (uint64_t)y * (uint64_t)(uint32_t)F.width + (uint64_t)x;
-                uint64_t rs = ptm::stream_init(F.seed_key, pixel, (uint64_t)(F.s0 + sl));
-                const double xi_u = ptm::stream_next(rs);
-                const double xi_v = ptm::stream_next(rs);
-                const double u = ((double)x + xi_u) * F.inv_width;
-                const double vv = ((F.height_m1 - (double)y) + xi_v) * F.inv_height;
-                const double tx_ = cam.lower_left[0] + cam.horizontal[0] * u;
-                const double ty_ = cam.lower_left[1] + cam.horizontal[1] * u;
-                const double tz_ = cam.lower_left[2] + cam.horizontal[2] * u;
-                ax[k] = tx_ + cam.vertical[0] * vv;
-                ay[k] = ty_ + cam.vertical[1] * vv;
-                az[k] = tz_ + cam.vertical[2] * vv;
-                p_rs[k * 64u + lane] = rs;
+                const CameraSample c = camera_sample(F, cam, x, y, sl);
+                ax[k] = c.ax;
+                ay[k] = c.ay;
+                az[k] = c.az;
+                p_rs[k * 64u + lane] = c.rs;
                 nd0 = 2;
             }
         }
@@ -1741,7 +1671,6 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_lens_pool_kernel(const DevFra
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     // ---- C: lens offset, ray, coalesced stores (lockstep)
-    const size_t nj = F.njobs;
 #pragma unroll
     for (uint32_t k = 0; k < R; k++) {
         const uint32_t myjob = (row0 + k) * 64u + lane;
@@ -1751,25 +1680,34 @@ __global__ __launch_bounds__(PT_BLOCK) void raygen_lens_pool_kernel(const DevFra
             ray_ndraw[myjob] = 0xffffu;
             continue;
         }
-        const double rx = p_rx[k * 64u + lane] * cam.lens_radius;
-        const double ry = p_ry[k * 64u + lane] * cam.lens_radius;
-        const double offx = cam.u[0] * rx + cam.v[0] * ry;
-        const double offy = cam.u[1] * rx + cam.v[1] * ry;
-        const double offz = cam.u[2] * rx + cam.v[2] * ry;
-        ray[myjob] = cam.origin[0] + offx;
-        ray[nj + myjob] = cam.origin[1] + offy;
-        ray[2 * nj + myjob] = cam.origin[2] + offz;
-        ray[3 * nj + myjob] = (ax[k] - cam.origin[0]) - offx;
-        ray[4 * nj + myjob] = (ay[k] - cam.origin[1]) - offy;
-        ray[5 * nj + myjob] = (az[k] - cam.origin[2]) - offz;
-        ray_rng[myjob] = p_rs[k * 64u + lane];
-        ray_ndraw[myjob] = (uint16_t)nd;
+        store_primary(F, ray, ray_rng, ray_ndraw, myjob, lens_ray(cam, ax[k], ay[k], az[k], p_rx[k * 64u + lane], p_ry[k * 64u + lane]),
+                      p_rs[k * 64u + lane], nd);  // (nd saturated in the walk already)
     }
 }
 
 // ------------------------------------------------------------------------------------------------------------
 // Shading pieces shared by trace_kernel (all-in-one form) and glass_kernel.  Every expression is the reference's,
 // in the reference's association order.
+
+// The sky closure of a ray that hits nothing (renderer.go:56-92; the expressions of trace_kernel's sky branch, which stays inline there:
+// it reads through the laundered argument pointer).
+__device__ __forceinline__ void sky_radiance(const DevSky &sky, double dx, double dy, double dz, double &termx, double &termy, double &termz) {
+    if (sky.kind == 1) {
+        const double dirLen = ptm::f_sqrt(dx * dx + dy * dy + dz * dz);
+        if (dirLen == 0) {
+            termx = sky.c0[0]; termy = sky.c0[1]; termz = sky.c0[2];
+        } else {
+            double tt = (dy / dirLen + 1.0) * 0.5;
+            if (tt < 0) tt = 0;
+            if (tt > 1) tt = 1;
+            termx = sky.c0[0] * (1 - tt) + sky.c1[0] * tt;
+            termy = sky.c0[1] * (1 - tt) + sky.c1[1] * tt;
+            termz = sky.c0[2] * (1 - tt) + sky.c1[2] * tt;
+        }
+    } else {
+        termx = sky.c0[0]; termy = sky.c0[1]; termz = sky.c0[2];
+    }
+}
 
 // One draw of the sample stream (random.go:27-34) with the bookkeeping both kernels keep.
 template <bool STATS>

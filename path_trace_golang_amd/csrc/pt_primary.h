@@ -29,25 +29,6 @@
 
 namespace ptk {
 
-__device__ __forceinline__ void sky_radiance(const DevSky &sky, double dx, double dy, double dz, double &termx, double &termy, double &termz) {
-    // sky closure, renderer.go:56-92 (the expressions of trace_kernel's sky branch)
-    if (sky.kind == 1) {
-        const double dirLen = ptm::f_sqrt(dx * dx + dy * dy + dz * dz);
-        if (dirLen == 0) {
-            termx = sky.c0[0]; termy = sky.c0[1]; termz = sky.c0[2];
-        } else {
-            double tt = (dy / dirLen + 1.0) * 0.5;
-            if (tt < 0) tt = 0;
-            if (tt > 1) tt = 1;
-            termx = sky.c0[0] * (1 - tt) + sky.c1[0] * tt;
-            termy = sky.c0[1] * (1 - tt) + sky.c1[1] * tt;
-            termz = sky.c0[2] * (1 - tt) + sky.c1[2] * tt;
-        }
-    } else {
-        termx = sky.c0[0]; termy = sky.c0[1]; termz = sky.c0[2];
-    }
-}
-
 #ifndef PT_PRIMARY_WAVES
 #define PT_PRIMARY_WAVES 6  // blocks of 256 threads per CU the kernel is compiled for (84 VGPRs)
 #endif

@@ -432,190 +432,46 @@ __device__ __forceinline__ void exact_answer(const Walk32Args &K, ObjPtr g_obj, 
         scan_uniform(A.F, g_obj, r, MODE, b3, t3);
         if (best != b3 || (best >= 0 && !(tmax == t3))) {
             c_mismatch++;
-            unsigned long long *dbg = A.B.counters + 8;
-            dbg[0] = ((unsigned long long)(uint32_t)best << 32) | (uint32_t)b3;
-            dbg[1] = ptm::to_bits(tmax);
-            dbg[2] = ptm::to_bits(t3);
-            dbg[3] = (unsigned long long)MODE | ((unsigned long long)n << 8);
-            dbg[4] = ptm::to_bits(r.ox); dbg[5] = ptm::to_bits(r.oy); dbg[6] = ptm::to_bits(r.oz);
-            dbg[7] = ptm::to_bits(r.dx); dbg[8] = ptm::to_bits(r.dy); dbg[9] = ptm::to_bits(r.dz);
+            record_mismatch(A.B.counters, best, b3, tmax, t3, (unsigned long long)MODE | ((unsigned long long)n << 8), r);
         }
         best = b3;
         tmax = t3;
     }
 }
 
-// Exact tests + shading of every path in qin after its walk (wf_shade_kernel with the exact pass in front).
+// How the walk32 form answers an entry (the policy of shade_pass / exit_pass, pt_wavefront.h): the exact pass on the entry's ray, run
+// before the rest of the entry is read so that throughput and stream state are not alive during exact_candidates.  Owns the verify
+// modes' mismatch count.
+template <int MODE, bool VERIFY>
+struct ExactAnswer {
+    typedef const DevObj __attribute__((address_space(4))) *ConstObjPtr;
+    typedef const int32_t __attribute__((address_space(4))) *ConstIdxPtr;
+    static constexpr bool before_state = true;
+    const Walk32Args &K;
+    uint32_t c_mismatch = 0;
+    __device__ __forceinline__ void operator()(const PathQueue &, uint32_t i, const RayD &r, int &best, double &tmax) {
+        exact_answer<MODE, VERIFY>(K, (ConstObjPtr)(K.W.B.objs), (ConstIdxPtr)(K.W.B.plane_idx), i, r, best, tmax, c_mismatch);
+    }
+    __device__ __forceinline__ void flush(unsigned long long *counters, uint32_t lane) const {
+        if (VERIFY) flush_count(&counters[4], c_mismatch, lane);
+    }
+};
+
+// Exact tests + shading of every path in qin after its walk, and exact exit searches + their epilogue: the passes of pt_wavefront.h
+// with the exact pass as their answer.  Materials in LDS, objects from HBM / L2.
 template <bool STATS, bool VERIFY>
 __global__ __launch_bounds__(PT_BLOCK) void wf_shade32_kernel(const Walk32Args K) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const WfArgs &A = K.W;
-    const DevFrame &F = A.F;
-    const TraceBuffers &B = A.B;
-    const PathQueue &Q = A.qin;
     DevMat *lds_mat = reinterpret_cast<DevMat *>(smem);
-    {
-        const uint64_t *g1 = reinterpret_cast<const uint64_t *>(B.mats);
-        uint64_t *l1 = reinterpret_cast<uint64_t *>(lds_mat);
-        const int n1 = F.nmat * (int)(sizeof(DevMat) / 8);
-        for (int i = threadIdx.x; i < n1; i += PT_BLOCK) l1[i] = g1[i];
-        __syncthreads();
-    }
-    typedef const DevObj __attribute__((address_space(4))) *ConstObjPtr;
-    typedef const int32_t __attribute__((address_space(4))) *ConstIdxPtr;
-    typedef const uint32_t __attribute__((address_space(4))) *ConstU32Ptr;
-    const ConstObjPtr g_obj = (ConstObjPtr)(B.objs);
-    const ConstIdxPtr g_pl = (ConstIdxPtr)(B.plane_idx);
-    const uint32_t lane = threadIdx.x & (PT_WAVE - 1);
-    const uint32_t n_count = *(ConstU32Ptr)(Q.count);
-    const uint32_t n = n_count < Q.cap ? n_count : Q.cap;
-    const size_t qc = Q.cap;
-    uint32_t c_seg = 0, c_draw = 0, c_exit = 0, c_mismatch = 0;
-    QueueWindow w_out, w_exit;
-
-    for (uint32_t i0 = blockIdx.x * PT_BLOCK + (threadIdx.x & ~(PT_WAVE - 1u)); i0 < n; i0 += gridDim.x * PT_BLOCK) {
-        const uint32_t i = i0 + lane;
-        bool go_on = false, to_exit = false;
-        double ox = 0, oy = 0, oz = 0, dx = 0, dy = 0, dz = 0, Tx = 0, Ty = 0, Tz = 0;
-        uint64_t rs = 0;
-        uint32_t job = PT_HOLE, j_seg = 0, j_draw = 0;
-        int depth = 0, exit_mat = 0;
-        if (i < n) job = Q.job[i];
-        if (job != PT_HOLE) {
-            ox = Q.d[i]; oy = Q.d[qc + i]; oz = Q.d[2 * qc + i];
-            dx = Q.d[3 * qc + i]; dy = Q.d[4 * qc + i]; dz = Q.d[5 * qc + i];
-            int best = -1;
-            double tmax = 0;
-            exact_answer<0, VERIFY>(K, g_obj, g_pl, i, RayD{ox, oy, oz, dx, dy, dz}, best, tmax, c_mismatch);
-            Tx = Q.d[6 * qc + i]; Ty = Q.d[7 * qc + i]; Tz = Q.d[8 * qc + i];
-            rs = Q.rs[i];
-            depth = Q.depth[i];
-            if (STATS) { j_seg = Q.jseg[i]; j_draw = Q.jdraw[i]; }
-            c_seg++;
-            if (STATS) j_seg++;
-            bool finished = false;
-            double termx = 0, termy = 0, termz = 0, attx = 1, atty = 1, attz = 1;
-            if (best < 0) {
-                // sky closure, renderer.go:56-92
-                finished = true;
-                const DevSky &sky = A.sky;
-                if (sky.kind == 1) {
-                    const double dirLen = ptm::f_sqrt(dx * dx + dy * dy + dz * dz);
-                    if (dirLen == 0) {
-                        termx = sky.c0[0]; termy = sky.c0[1]; termz = sky.c0[2];
-                    } else {
-                        double tt = (dy / dirLen + 1.0) * 0.5;
-                        if (tt < 0) tt = 0;
-                        if (tt > 1) tt = 1;
-                        termx = sky.c0[0] * (1 - tt) + sky.c1[0] * tt;
-                        termy = sky.c0[1] * (1 - tt) + sky.c1[1] * tt;
-                        termz = sky.c0[2] * (1 - tt) + sky.c1[2] * tt;
-                    }
-                } else {
-                    termx = sky.c0[0]; termy = sky.c0[1]; termz = sky.c0[2];
-                }
-            } else {
-                bool exit_search = false;
-                shade_hit<STATS, true>(B.objs[best], lds_mat, tmax, ox, oy, oz, dx, dy, dz, rs, c_draw, j_draw, finished, termx, termy, termz, attx,
-                                       atty, attz, exit_search, exit_mat);
-                if (exit_search) {
-                    to_exit = true;
-                    c_exit++;
-                } else if (!finished) {
-                    finished = roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
-                    go_on = !finished;
-                }
-            }
-            if (finished) {
-                ptk::store_radiance(B.L, job, Tx * termx, Ty * termy, Tz * termz);
-                if (STATS) { B.job_seg[job] = j_seg; B.job_draw[job] = j_draw; }
-            }
-        }
-        const uint32_t s_out = window_push(w_out, A.qout.count, go_on, lane, PT_CONT_BLOCK);
-        if (go_on) queue_store(A.qout, s_out, ox, oy, oz, dx, dy, dz, Tx, Ty, Tz, rs, job, depth, -1, j_seg, j_draw, STATS, B.counters + 19);
-        const uint32_t s_ex = window_push(w_exit, A.qexit.count, to_exit, lane, PT_QUEUE_BLOCK);
-        if (to_exit) queue_store(A.qexit, s_ex, ox, oy, oz, dx, dy, dz, Tx, Ty, Tz, rs, job, depth, exit_mat, j_seg, j_draw, STATS, B.counters + 19);
-    }
-    window_close(w_out, A.qout, lane);
-    window_close(w_exit, A.qexit, lane);
-    const uint32_t w_seg = wave_sum(c_seg), w_draw = wave_sum(c_draw), w_ex = wave_sum(c_exit);
-    if (lane == 0) {
-        if (w_seg) atomicAdd(&B.counters[0], (unsigned long long)w_seg);
-        if (w_ex) atomicAdd(&B.counters[1], (unsigned long long)w_ex);
-        if (w_draw) atomicAdd(&B.counters[2], (unsigned long long)w_draw);
-    }
-    if (VERIFY) {
-        const uint32_t w_mis = wave_sum(c_mismatch);
-        if (lane == 0 && w_mis) atomicAdd(&B.counters[4], (unsigned long long)w_mis);
-    }
+    stage_lds(lds_mat, K.W.B.mats, K.W.F.nmat * (int)(sizeof(DevMat) / 8));
+    shade_pass<STATS>(K.W, K.W.B.objs, lds_mat, ExactAnswer<0, VERIFY>{K});
 }
-
-// Exact exit searches + their epilogue (wf_exit_kernel with the exact pass in front).
 template <bool STATS, bool VERIFY>
 __global__ __launch_bounds__(PT_BLOCK) void wf_exit32_kernel(const Walk32Args K) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const WfArgs &A = K.W;
-    const DevFrame &F = A.F;
-    const TraceBuffers &B = A.B;
-    const PathQueue &Q = A.qin;
     DevMat *lds_mat = reinterpret_cast<DevMat *>(smem);
-    {
-        const uint64_t *g1 = reinterpret_cast<const uint64_t *>(B.mats);
-        uint64_t *l1 = reinterpret_cast<uint64_t *>(lds_mat);
-        const int n1 = F.nmat * (int)(sizeof(DevMat) / 8);
-        for (int i = threadIdx.x; i < n1; i += PT_BLOCK) l1[i] = g1[i];
-        __syncthreads();
-    }
-    typedef const DevObj __attribute__((address_space(4))) *ConstObjPtr;
-    typedef const int32_t __attribute__((address_space(4))) *ConstIdxPtr;
-    typedef const uint32_t __attribute__((address_space(4))) *ConstU32Ptr;
-    const ConstObjPtr g_obj = (ConstObjPtr)(B.objs);
-    const ConstIdxPtr g_pl = (ConstIdxPtr)(B.plane_idx);
-    const uint32_t lane = threadIdx.x & (PT_WAVE - 1);
-    const uint32_t n_count = *(ConstU32Ptr)(Q.count);
-    const uint32_t n = n_count < Q.cap ? n_count : Q.cap;
-    const size_t qc = Q.cap;
-    uint32_t c_draw = 0, c_mismatch = 0;
-    QueueWindow w_out;
-    for (uint32_t i0 = blockIdx.x * PT_BLOCK + (threadIdx.x & ~(PT_WAVE - 1u)); i0 < n; i0 += gridDim.x * PT_BLOCK) {
-        const uint32_t i = i0 + lane;
-        bool go_on = false;
-        double ox = 0, oy = 0, oz = 0, dx = 0, dy = 0, dz = 0, Tx = 0, Ty = 0, Tz = 0;
-        uint64_t rs = 0;
-        uint32_t job = PT_HOLE, j_seg = 0, j_draw = 0;
-        int depth = 0;
-        if (i < n) job = Q.job[i];
-        if (job != PT_HOLE) {
-            ox = Q.d[i]; oy = Q.d[qc + i]; oz = Q.d[2 * qc + i];
-            dx = Q.d[3 * qc + i]; dy = Q.d[4 * qc + i]; dz = Q.d[5 * qc + i];
-            int ebest = -1;
-            double tmax = 0;
-            exact_answer<1, VERIFY>(K, g_obj, g_pl, i, RayD{ox, oy, oz, dx, dy, dz}, ebest, tmax, c_mismatch);
-            Tx = Q.d[6 * qc + i]; Ty = Q.d[7 * qc + i]; Tz = Q.d[8 * qc + i];
-            rs = Q.rs[i];
-            depth = Q.depth[i];
-            const int exit_mat = Q.best[i];
-            if (STATS) { j_seg = Q.jseg[i]; j_draw = Q.jdraw[i]; }
-            double attx = 1, atty = 1, attz = 1;
-            exit_post(lds_mat[exit_mat], ebest, tmax, ox, oy, oz, dx, dy, dz, attx, atty, attz);
-            const bool finished = roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
-            if (finished) {
-                ptk::store_radiance(B.L, job, Tx * 0.0, Ty * 0.0, Tz * 0.0);
-                if (STATS) { B.job_seg[job] = j_seg; B.job_draw[job] = j_draw; }
-            } else {
-                go_on = true;
-            }
-        }
-        const uint32_t s_out = window_push(w_out, A.qout.count, go_on, lane, PT_CONT_BLOCK);
-        if (go_on) queue_store(A.qout, s_out, ox, oy, oz, dx, dy, dz, Tx, Ty, Tz, rs, job, depth, -1, j_seg, j_draw, STATS, B.counters + 19);
-    }
-    window_close(w_out, A.qout, lane);
-    const uint32_t w_draw = wave_sum(c_draw);
-    if (lane == 0 && w_draw) atomicAdd(&B.counters[2], (unsigned long long)w_draw);
-    if (VERIFY) {
-        const uint32_t w_mis = wave_sum(c_mismatch);
-        if (lane == 0 && w_mis) atomicAdd(&B.counters[4], (unsigned long long)w_mis);
-    }
+    stage_lds(lds_mat, K.W.B.mats, K.W.F.nmat * (int)(sizeof(DevMat) / 8));
+    exit_pass<STATS>(K.W, lds_mat, ExactAnswer<1, VERIFY>{K});
 }
 
 }  // namespace ptk

@@ -63,83 +63,42 @@ __device__ __forceinline__ uint32_t wf_ray_key(const DevFrame &F, double ox, dou
     return (oct << 9) | cell;
 }
 
-// Counting sort of the entries of A.qin by key.  Every block owns one contiguous slice of the queue in passes 1 and 3
-// and keeps its histogram in LDS, so the global counters see one atomic per block and bin instead of one per ray
-// (a single address serves ~10^8 returning atomics a second on this chip: a popular bin would take longer than the
-// traversal it is meant to speed up).
-__device__ __forceinline__ void wf_slice(uint32_t n, uint32_t &lo, uint32_t &hi) {
-    const uint32_t per = (n + gridDim.x - 1) / gridDim.x;
-    lo = blockIdx.x * per < n ? blockIdx.x * per : n;
-    hi = lo + per < n ? lo + per : n;
-}
-// pass 1: key of every entry (PT_HOLE for a hole) and the histogram of the keys
-__global__ __launch_bounds__(PT_BLOCK) void wf_bin_count_kernel(const WfArgs A) {
-    __shared__ uint32_t hist[PT_WF_BINS];
+// The pieces every pass below shares.
+// Number of entries a pass walks: what the writers counted, never more than the queue holds.
+__device__ __forceinline__ uint32_t queue_len(const PathQueue &q) {
     typedef const uint32_t __attribute__((address_space(4))) *ConstU32Ptr;
-    const PathQueue &Q = A.qin;
-    const uint32_t n_count = *(ConstU32Ptr)(Q.count);
-    const uint32_t n = n_count < Q.cap ? n_count : Q.cap;
-    const size_t qc = Q.cap;
-    for (uint32_t k = threadIdx.x; k < PT_WF_BINS; k += PT_BLOCK) hist[k] = 0;
-    __syncthreads();
-    uint32_t lo, hi;
-    wf_slice(n, lo, hi);
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += PT_BLOCK) {
-        uint32_t key = PT_HOLE;
-        if (Q.job[i] != PT_HOLE) {
-            key = wf_ray_key(A.F, Q.d[i], Q.d[qc + i], Q.d[2 * qc + i], Q.d[3 * qc + i], Q.d[4 * qc + i], Q.d[5 * qc + i]);
-            atomicAdd(&hist[key], 1u);
-        }
-        A.bin_key[i] = key;
-    }
-    __syncthreads();
-    for (uint32_t k = threadIdx.x; k < PT_WF_BINS; k += PT_BLOCK)
-        if (hist[k]) atomicAdd(&A.bin_count[k], hist[k]);
+    const uint32_t n_count = *(ConstU32Ptr)(q.count);
+    return n_count < q.cap ? n_count : q.cap;
 }
-// pass 2: exclusive prefix sum of the histogram (one block), total -> bin_count[PT_WF_BINS]
-__global__ __launch_bounds__(1024) void wf_bin_scan_kernel(const WfArgs A) {
-    __shared__ uint32_t part[1024];
-    constexpr uint32_t PER = PT_WF_BINS / 1024u;
-    uint32_t loc[PER];
-    uint32_t s = 0;
-    for (uint32_t k = 0; k < PER; k++) {
-        loc[k] = s;
-        s += A.bin_count[threadIdx.x * PER + k];
-    }
-    part[threadIdx.x] = s;
+// Block-cooperative copy of n 8-byte words into LDS (the world, the materials), ending in the block's barrier.
+__device__ __forceinline__ void stage_lds(void *lds, const void *src, int n) {
+    const uint64_t *g = reinterpret_cast<const uint64_t *>(src);
+    uint64_t *l = reinterpret_cast<uint64_t *>(lds);
+    for (int i = threadIdx.x; i < n; i += PT_BLOCK) l[i] = g[i];
     __syncthreads();
-    for (uint32_t off = 1; off < 1024u; off <<= 1) {  // Hillis-Steele over the 1024 partial sums
-        const uint32_t v = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    const uint32_t base = part[threadIdx.x] - s;
-    for (uint32_t k = 0; k < PER; k++) A.bin_count[threadIdx.x * PER + k] = base + loc[k];
-    if (threadIdx.x == 1023u) A.bin_count[PT_WF_BINS] = part[1023];
 }
-// pass 3: the block reserves room for its slice in every bin (one atomic per bin), its entries take the places
-__global__ __launch_bounds__(PT_BLOCK) void wf_bin_scatter_kernel(const WfArgs A, uint32_t *perm) {
-    __shared__ uint32_t hist[PT_WF_BINS];
-    typedef const uint32_t __attribute__((address_space(4))) *ConstU32Ptr;
-    const uint32_t n_count = *(ConstU32Ptr)(A.qin.count);
-    const uint32_t n = n_count < A.qin.cap ? n_count : A.qin.cap;
-    for (uint32_t k = threadIdx.x; k < PT_WF_BINS; k += PT_BLOCK) hist[k] = 0;
-    __syncthreads();
-    uint32_t lo, hi;
-    wf_slice(n, lo, hi);
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += PT_BLOCK) {
-        const uint32_t key = A.bin_key[i];
-        if (key != PT_HOLE) atomicAdd(&hist[key], 1u);
-    }
-    __syncthreads();
-    for (uint32_t k = threadIdx.x; k < PT_WF_BINS; k += PT_BLOCK)
-        if (hist[k]) hist[k] = atomicAdd(&A.bin_count[k], hist[k]);  // from here on: next free place of the bin for this block
-    __syncthreads();
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += PT_BLOCK) {
-        const uint32_t key = A.bin_key[i];
-        if (key != PT_HOLE) perm[atomicAdd(&hist[key], 1u)] = i;
-    }
+// A lane's count -> one atomic per wave, none for a zero.
+__device__ __forceinline__ void flush_count(unsigned long long *counter, uint32_t c, uint32_t lane) {
+    const uint32_t w = wave_sum(c);
+    if (lane == 0 && w) atomicAdd(counter, (unsigned long long)w);
+}
+// Verify modes: one segment on which a scan and the reference's own loop (best2, tmax2) disagree, left in counters[8..17] for the host to
+// print; `tag` says who found it (the scan mode, plus what the caller knows).
+__device__ __forceinline__ void record_mismatch(unsigned long long *counters, int best, int best2, double tmax, double tmax2, unsigned long long tag,
+                                                const RayD &r) {
+    unsigned long long *dbg = counters + 8;
+    dbg[0] = ((unsigned long long)(uint32_t)best << 32) | (uint32_t)best2;
+    dbg[1] = ptm::to_bits(tmax);
+    dbg[2] = ptm::to_bits(tmax2);
+    dbg[3] = tag;
+    dbg[4] = ptm::to_bits(r.ox); dbg[5] = ptm::to_bits(r.oy); dbg[6] = ptm::to_bits(r.oz);
+    dbg[7] = ptm::to_bits(r.dx); dbg[8] = ptm::to_bits(r.dy); dbg[9] = ptm::to_bits(r.dz);
+}
+// A path ends: its radiance record and, with STATS, its segment and draw counts.
+template <bool STATS>
+__device__ __forceinline__ void store_path_end(const TraceBuffers &B, uint32_t job, double x, double y, double z, uint32_t j_seg, uint32_t j_draw) {
+    ptk::store_radiance(B.L, job, x, y, z);
+    if (STATS) { B.job_seg[job] = j_seg; B.job_draw[job] = j_draw; }
 }
 
 // One wave's window into a queue it appends to (block reservation: see trace_kernel's glass queue).
@@ -188,6 +147,96 @@ __device__ __forceinline__ void queue_store(const PathQueue &q, uint32_t slot, d
     if (stats) { q.jseg[slot] = j_seg; q.jdraw[slot] = j_draw; }
 }
 
+// queue_store's mirror, in the two parts a pass reads an entry in: the ray, which finds (or is all that is needed to find) the entry's
+// answer, and then the path state -- throughput, stream state, depth, the optional counts.  (The job id comes first: it tells a hole.)
+__device__ __forceinline__ RayD queue_load_ray(const PathQueue &q, uint32_t i) {
+    const size_t qc = q.cap;
+    return RayD{q.d[i], q.d[qc + i], q.d[2 * qc + i], q.d[3 * qc + i], q.d[4 * qc + i], q.d[5 * qc + i]};
+}
+__device__ __forceinline__ void queue_load_state(const PathQueue &q, uint32_t i, double &Tx, double &Ty, double &Tz, uint64_t &rs, int &depth,
+                                                 uint32_t &j_seg, uint32_t &j_draw, bool stats) {
+    const size_t qc = q.cap;
+    Tx = q.d[6 * qc + i]; Ty = q.d[7 * qc + i]; Tz = q.d[8 * qc + i];
+    rs = q.rs[i];
+    depth = q.depth[i];
+    if (stats) { j_seg = q.jseg[i]; j_draw = q.jdraw[i]; }
+}
+
+// Counting sort of the entries of A.qin by key.  Every block owns one contiguous slice of the queue in passes 1 and 3
+// and keeps its histogram in LDS, so the global counters see one atomic per block and bin instead of one per ray
+// (a single address serves ~10^8 returning atomics a second on this chip: a popular bin would take longer than the
+// traversal it is meant to speed up).
+__device__ __forceinline__ void wf_slice(uint32_t n, uint32_t &lo, uint32_t &hi) {
+    const uint32_t per = (n + gridDim.x - 1) / gridDim.x;
+    lo = blockIdx.x * per < n ? blockIdx.x * per : n;
+    hi = lo + per < n ? lo + per : n;
+}
+// pass 1: key of every entry (PT_HOLE for a hole) and the histogram of the keys
+__global__ __launch_bounds__(PT_BLOCK) void wf_bin_count_kernel(const WfArgs A) {
+    __shared__ uint32_t hist[PT_WF_BINS];
+    const PathQueue &Q = A.qin;
+    const uint32_t n = queue_len(Q);
+    const size_t qc = Q.cap;
+    for (uint32_t k = threadIdx.x; k < PT_WF_BINS; k += PT_BLOCK) hist[k] = 0;
+    __syncthreads();
+    uint32_t lo, hi;
+    wf_slice(n, lo, hi);
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += PT_BLOCK) {
+        uint32_t key = PT_HOLE;
+        if (Q.job[i] != PT_HOLE) {
+            key = wf_ray_key(A.F, Q.d[i], Q.d[qc + i], Q.d[2 * qc + i], Q.d[3 * qc + i], Q.d[4 * qc + i], Q.d[5 * qc + i]);
+            atomicAdd(&hist[key], 1u);
+        }
+        A.bin_key[i] = key;
+    }
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < PT_WF_BINS; k += PT_BLOCK)
+        if (hist[k]) atomicAdd(&A.bin_count[k], hist[k]);
+}
+// pass 2: exclusive prefix sum of the histogram (one block), total -> bin_count[PT_WF_BINS]
+__global__ __launch_bounds__(1024) void wf_bin_scan_kernel(const WfArgs A) {
+    __shared__ uint32_t part[1024];
+    constexpr uint32_t PER = PT_WF_BINS / 1024u;
+    uint32_t loc[PER];
+    uint32_t s = 0;
+    for (uint32_t k = 0; k < PER; k++) {
+        loc[k] = s;
+        s += A.bin_count[threadIdx.x * PER + k];
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024u; off <<= 1) {  // Hillis-Steele over the 1024 partial sums
+        const uint32_t v = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    const uint32_t base = part[threadIdx.x] - s;
+    for (uint32_t k = 0; k < PER; k++) A.bin_count[threadIdx.x * PER + k] = base + loc[k];
+    if (threadIdx.x == 1023u) A.bin_count[PT_WF_BINS] = part[1023];
+}
+// pass 3: the block reserves room for its slice in every bin (one atomic per bin), its entries take the places
+__global__ __launch_bounds__(PT_BLOCK) void wf_bin_scatter_kernel(const WfArgs A, uint32_t *perm) {
+    __shared__ uint32_t hist[PT_WF_BINS];
+    const uint32_t n = queue_len(A.qin);
+    for (uint32_t k = threadIdx.x; k < PT_WF_BINS; k += PT_BLOCK) hist[k] = 0;
+    __syncthreads();
+    uint32_t lo, hi;
+    wf_slice(n, lo, hi);
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += PT_BLOCK) {
+        const uint32_t key = A.bin_key[i];
+        if (key != PT_HOLE) atomicAdd(&hist[key], 1u);
+    }
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < PT_WF_BINS; k += PT_BLOCK)
+        if (hist[k]) hist[k] = atomicAdd(&A.bin_count[k], hist[k]);  // from here on: next free place of the bin for this block
+    __syncthreads();
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += PT_BLOCK) {
+        const uint32_t key = A.bin_key[i];
+        if (key != PT_HOLE) perm[atomicAdd(&hist[key], 1u)] = i;
+    }
+}
+
 // Fresh jobs -> queue entries (entry i = job i; a job whose pixel lies outside the frame is a hole).
 template <bool STATS>
 __global__ __launch_bounds__(PT_BLOCK) void wf_init_kernel(const WfArgs A) {
@@ -202,8 +251,7 @@ __global__ __launch_bounds__(PT_BLOCK) void wf_init_kernel(const WfArgs A) {
             c_samples++;
             c_draw += nd;
             if (F.max_depth <= 0) {  // rayColorOpt returns black before any scan (renderer.go:287-289)
-                ptk::store_radiance(B.L, i, 0.0, 0.0, 0.0);
-                if (STATS) { B.job_seg[i] = 0; B.job_draw[i] = nd; }
+                store_path_end<STATS>(B, i, 0.0, 0.0, 0.0, 0u, nd);
             } else {
                 job = i;
                 const size_t nj = F.njobs;
@@ -213,11 +261,8 @@ __global__ __launch_bounds__(PT_BLOCK) void wf_init_kernel(const WfArgs A) {
         }
         if (job == PT_HOLE && i < A.qin.cap) A.qin.job[i] = PT_HOLE;
     }
-    const uint32_t w_s = wave_sum(c_samples), w_d = wave_sum(c_draw);
-    if ((threadIdx.x & (PT_WAVE - 1)) == 0) {
-        if (w_d) atomicAdd(&B.counters[2], (unsigned long long)w_d);
-        if (w_s) atomicAdd(&B.counters[3], (unsigned long long)w_s);
-    }
+    flush_count(&B.counters[2], c_draw, threadIdx.x & (PT_WAVE - 1));
+    flush_count(&B.counters[3], c_samples, threadIdx.x & (PT_WAVE - 1));
     if (blockIdx.x == 0 && threadIdx.x == 0) *A.qin.count = F.njobs;
 }
 
@@ -245,8 +290,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_BVH_WAVES) void wf_traverse_kernel(con
     const ConstObjPtr g_obj = (ConstObjPtr)(B.objs);
     const ConstIdxPtr g_pl = (ConstIdxPtr)(B.plane_idx);
     const uint32_t lane = threadIdx.x & (PT_WAVE - 1);
-    const uint32_t n_count = *(ConstU32Ptr)(Q.count);
-    const uint32_t n_items = A.perm ? *(ConstU32Ptr)(A.n_sorted) : (n_count < Q.cap ? n_count : Q.cap);
+    const uint32_t n_items = A.perm ? *(ConstU32Ptr)(A.n_sorted) : queue_len(Q);
     const size_t qc = Q.cap;
 
     bool have = false;
@@ -321,13 +365,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_BVH_WAVES) void wf_traverse_kernel(con
                     scan_uniform(F, g_obj, ray, MODE, best2, tmax2);
                     if (best != best2 || (best >= 0 && !(tmax == tmax2))) {
                         c_mismatch++;
-                        unsigned long long *dbg = B.counters + 8;
-                        dbg[0] = ((unsigned long long)(uint32_t)best << 32) | (uint32_t)best2;
-                        dbg[1] = ptm::to_bits(tmax);
-                        dbg[2] = ptm::to_bits(tmax2);
-                        dbg[3] = (unsigned long long)MODE;
-                        dbg[4] = ptm::to_bits(ox); dbg[5] = ptm::to_bits(oy); dbg[6] = ptm::to_bits(oz);
-                        dbg[7] = ptm::to_bits(dx); dbg[8] = ptm::to_bits(dy); dbg[9] = ptm::to_bits(dz);
+                        record_mismatch(B.counters, best, best2, tmax, tmax2, (unsigned long long)MODE, ray);
                     }
                     best = best2;
                     tmax = tmax2;
@@ -363,10 +401,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_BVH_WAVES) void wf_traverse_kernel(con
             have = false;
         }
     }
-    if (VERIFY) {
-        const uint32_t w_mis = wave_sum(c_mismatch);
-        if (lane == 0 && w_mis) atomicAdd(&B.counters[4], (unsigned long long)w_mis);
-    }
+    if (VERIFY) flush_count(&B.counters[4], c_mismatch, lane);
 }
 
 // The flat scans as a pass: one path per lane (bitmask scan over <= 32 + 32 records; the wavefront form of the
@@ -379,34 +414,26 @@ __global__ __launch_bounds__(PT_BLOCK) void wf_scan_flat_kernel(const WfArgs A) 
     const PathQueue &Q = A.qin;
     DevObj *lds_obj = reinterpret_cast<DevObj *>(smem);
     int *lds_kidx = reinterpret_cast<int *>(smem + (size_t)F.nobj * sizeof(DevObj));
-    {
-        const uint64_t *g0 = reinterpret_cast<const uint64_t *>(B.objs);
-        uint64_t *l0 = reinterpret_cast<uint64_t *>(lds_obj);
-        const int n0 = F.nobj * (int)(sizeof(DevObj) / 8);
-        for (int i = threadIdx.x; i < n0; i += PT_BLOCK) l0[i] = g0[i];
-        for (int i = threadIdx.x; i < F.n_bsph; i += PT_BLOCK) lds_kidx[pt_record_slot(i, F.n_bsph)] = B.bsph[i].index;
-        for (int i = threadIdx.x; i < F.n_bbox; i += PT_BLOCK) lds_kidx[F.n_bsph + pt_record_slot(i, F.n_bbox)] = B.bbox[i].index;
-        __syncthreads();
-    }
+    for (int i = threadIdx.x; i < F.n_bsph; i += PT_BLOCK) lds_kidx[pt_record_slot(i, F.n_bsph)] = B.bsph[i].index;
+    for (int i = threadIdx.x; i < F.n_bbox; i += PT_BLOCK) lds_kidx[F.n_bsph + pt_record_slot(i, F.n_bbox)] = B.bbox[i].index;
+    stage_lds(lds_obj, B.objs, F.nobj * (int)(sizeof(DevObj) / 8));
     typedef const DevObj __attribute__((address_space(4))) *ConstObjPtr;
     typedef const BroadSphere __attribute__((address_space(4))) *ConstSphPtr;
     typedef const BroadBox __attribute__((address_space(4))) *ConstBoxPtr;
     typedef const int32_t __attribute__((address_space(4))) *ConstIdxPtr;
-    typedef const uint32_t __attribute__((address_space(4))) *ConstU32Ptr;
     const ConstObjPtr g_obj = (ConstObjPtr)(B.objs);
     const ConstIdxPtr g_pl = (ConstIdxPtr)(B.plane_idx);
     const BroadLists<ConstSphPtr, ConstBoxPtr> BL{(ConstSphPtr)B.bsph, (ConstBoxPtr)B.bbox, F.n_bsph, F.n_bbox, F.sph_all, F.box_all,
                                                   F.sph_diel, F.box_diel, lds_kidx, lds_kidx + F.n_bsph};
     const uint32_t lane = threadIdx.x & (PT_WAVE - 1);
-    const uint32_t n_count = *(ConstU32Ptr)(Q.count);
-    const uint32_t n = n_count < Q.cap ? n_count : Q.cap;
+    const uint32_t n = queue_len(Q);
     const size_t qc = Q.cap;
     uint32_t c_mismatch = 0;
     const ProfHooks ph{nullptr, nullptr, nullptr, lane, nullptr};
     for (uint32_t i0 = blockIdx.x * PT_BLOCK + (threadIdx.x & ~(PT_WAVE - 1u)); i0 < n; i0 += gridDim.x * PT_BLOCK) {
         const uint32_t i = i0 + lane;
         if (i < n && Q.job[i] != PT_HOLE) {
-            const RayD ray{Q.d[i], Q.d[qc + i], Q.d[2 * qc + i], Q.d[3 * qc + i], Q.d[4 * qc + i], Q.d[5 * qc + i]};
+            const RayD ray = queue_load_ray(Q, i);
             int best = -1;
             double tmax = 0;
             const double a_ = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
@@ -430,89 +457,61 @@ __global__ __launch_bounds__(PT_BLOCK) void wf_scan_flat_kernel(const WfArgs A) 
             Q.d[9 * qc + i] = tmax;
         }
     }
-    if (VERIFY) {
-        const uint32_t w_mis = wave_sum(c_mismatch);
-        if (lane == 0 && w_mis) atomicAdd(&B.counters[4], (unsigned long long)w_mis);
-    }
+    if (VERIFY) flush_count(&B.counters[4], c_mismatch, lane);
 }
 
-// Shading of every path in A.qin after its closest-hit pass.
-template <bool STATS>
-__global__ __launch_bounds__(PT_BLOCK) void wf_shade_kernel(const WfArgs A) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const DevFrame &F = A.F;
+// How the wavefront form answers an entry: wf_traverse_kernel (or wf_scan_flat_kernel) left hit and tmax in it.  (pt_walk32.h has the
+// other policy, the exact pass.)  A policy is called with the entry and its ray and flushes whatever it counted when the pass ends;
+// `before_state` says on which side of the entry's path state it is called, so that each form keeps the order of loads it had: here
+// the two planes are read with the rest of the entry, in walk32 the exact pass runs before throughput and stream state are alive.
+struct QueueAnswer {
+    static constexpr bool before_state = false;
+    __device__ __forceinline__ void operator()(const PathQueue &Q, uint32_t i, const RayD &, int &best, double &tmax) const {
+        best = Q.hit[i];  // (`best` of an exit-queue entry keeps the glass material)
+        tmax = Q.d[9 * (size_t)Q.cap + i];
+    }
+    __device__ __forceinline__ void flush(unsigned long long *, uint32_t) const {}
+};
+
+// Shading of every path in A.qin once its closest hit is known (renderer.go:303-319, :375-403): sky / emitted / scatter / roulette.  Paths that
+// go on are appended to A.qout, dielectric front-face hits to A.qexit.  `objs` is where a hit object is read from (the LDS copy of a flat
+// scene's world, or HBM / L2), `lds_mat` the staged materials.
+template <bool STATS, typename Answer>
+__device__ __forceinline__ void shade_pass(const WfArgs &A, const DevObj *objs, const DevMat *lds_mat, Answer answer) {
     const TraceBuffers &B = A.B;
     const PathQueue &Q = A.qin;
-    // small scenes: world and materials in LDS; BVH scenes: materials only (objects come from HBM / L2)
-    const bool world_in_lds = F.world_in_lds != 0;
-    DevObj *lds_obj = reinterpret_cast<DevObj *>(smem);
-    DevMat *lds_mat = reinterpret_cast<DevMat *>(smem + (world_in_lds ? (size_t)F.nobj * sizeof(DevObj) : 0));
-    {
-        if (world_in_lds) {
-            const uint64_t *g0 = reinterpret_cast<const uint64_t *>(B.objs);
-            uint64_t *l0 = reinterpret_cast<uint64_t *>(lds_obj);
-            const int n0 = F.nobj * (int)(sizeof(DevObj) / 8);
-            for (int i = threadIdx.x; i < n0; i += PT_BLOCK) l0[i] = g0[i];
-        }
-        const uint64_t *g1 = reinterpret_cast<const uint64_t *>(B.mats);
-        uint64_t *l1 = reinterpret_cast<uint64_t *>(lds_mat);
-        const int n1 = F.nmat * (int)(sizeof(DevMat) / 8);
-        for (int i = threadIdx.x; i < n1; i += PT_BLOCK) l1[i] = g1[i];
-        __syncthreads();
-    }
-    const DevObj *const s_obj = world_in_lds ? lds_obj : B.objs;
-    typedef const uint32_t __attribute__((address_space(4))) *ConstU32Ptr;
     const uint32_t lane = threadIdx.x & (PT_WAVE - 1);
-    const uint32_t n_count = *(ConstU32Ptr)(Q.count);
-    const uint32_t n = n_count < Q.cap ? n_count : Q.cap;
-    const size_t qc = Q.cap;
+    const uint32_t n = queue_len(Q);
     uint32_t c_seg = 0, c_draw = 0, c_exit = 0;
     QueueWindow w_out, w_exit;
 
     for (uint32_t i0 = blockIdx.x * PT_BLOCK + (threadIdx.x & ~(PT_WAVE - 1u)); i0 < n; i0 += gridDim.x * PT_BLOCK) {
         const uint32_t i = i0 + lane;
         bool go_on = false, to_exit = false;
-        double ox = 0, oy = 0, oz = 0, dx = 0, dy = 0, dz = 0, Tx = 0, Ty = 0, Tz = 0;
+        RayD r{0, 0, 0, 0, 0, 0};
+        double Tx = 0, Ty = 0, Tz = 0;
         uint64_t rs = 0;
         uint32_t job = PT_HOLE, j_seg = 0, j_draw = 0;
         int depth = 0, exit_mat = 0;
         if (i < n) job = Q.job[i];
         if (job != PT_HOLE) {
-            ox = Q.d[i]; oy = Q.d[qc + i]; oz = Q.d[2 * qc + i];
-            dx = Q.d[3 * qc + i]; dy = Q.d[4 * qc + i]; dz = Q.d[5 * qc + i];
-            Tx = Q.d[6 * qc + i]; Ty = Q.d[7 * qc + i]; Tz = Q.d[8 * qc + i];
-            const double tmax = Q.d[9 * qc + i];
-            rs = Q.rs[i];
-            depth = Q.depth[i];
-            const int best = Q.hit[i];
-            if (STATS) { j_seg = Q.jseg[i]; j_draw = Q.jdraw[i]; }
+            r = queue_load_ray(Q, i);
+            int best = -1;
+            double tmax = 0;
+            if (Answer::before_state) answer(Q, i, r, best, tmax);
+            queue_load_state(Q, i, Tx, Ty, Tz, rs, depth, j_seg, j_draw, STATS);
+            if (!Answer::before_state) answer(Q, i, r, best, tmax);
             c_seg++;
             if (STATS) j_seg++;
             bool finished = false;
             double termx = 0, termy = 0, termz = 0, attx = 1, atty = 1, attz = 1;
             if (best < 0) {
-                // sky closure, renderer.go:56-92
                 finished = true;
-                const DevSky &sky = A.sky;
-                if (sky.kind == 1) {
-                    const double dirLen = ptm::f_sqrt(dx * dx + dy * dy + dz * dz);
-                    if (dirLen == 0) {
-                        termx = sky.c0[0]; termy = sky.c0[1]; termz = sky.c0[2];
-                    } else {
-                        double tt = (dy / dirLen + 1.0) * 0.5;
-                        if (tt < 0) tt = 0;
-                        if (tt > 1) tt = 1;
-                        termx = sky.c0[0] * (1 - tt) + sky.c1[0] * tt;
-                        termy = sky.c0[1] * (1 - tt) + sky.c1[1] * tt;
-                        termz = sky.c0[2] * (1 - tt) + sky.c1[2] * tt;
-                    }
-                } else {
-                    termx = sky.c0[0]; termy = sky.c0[1]; termz = sky.c0[2];
-                }
+                sky_radiance(A.sky, r.dx, r.dy, r.dz, termx, termy, termz);
             } else {
                 bool exit_search = false;
-                shade_hit<STATS, true>(s_obj[best], lds_mat, tmax, ox, oy, oz, dx, dy, dz, rs, c_draw, j_draw, finished, termx, termy, termz, attx,
-                                       atty, attz, exit_search, exit_mat);
+                shade_hit<STATS, true>(objs[best], lds_mat, tmax, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, rs, c_draw, j_draw, finished, termx, termy,
+                                       termz, attx, atty, attz, exit_search, exit_mat);
                 if (exit_search) {
                     to_exit = true;
                     c_exit++;
@@ -521,84 +520,82 @@ __global__ __launch_bounds__(PT_BLOCK) void wf_shade_kernel(const WfArgs A) {
                     go_on = !finished;
                 }
             }
-            if (finished) {
-                ptk::store_radiance(B.L, job, Tx * termx, Ty * termy, Tz * termz);
-                if (STATS) { B.job_seg[job] = j_seg; B.job_draw[job] = j_draw; }
-            }
+            if (finished) store_path_end<STATS>(B, job, Tx * termx, Ty * termy, Tz * termz, j_seg, j_draw);
         }
         const uint32_t s_out = window_push(w_out, A.qout.count, go_on, lane, PT_CONT_BLOCK);
-        if (go_on) queue_store(A.qout, s_out, ox, oy, oz, dx, dy, dz, Tx, Ty, Tz, rs, job, depth, -1, j_seg, j_draw, STATS, B.counters + 19);
+        if (go_on) queue_store(A.qout, s_out, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, Tx, Ty, Tz, rs, job, depth, -1, j_seg, j_draw, STATS, B.counters + 19);
         const uint32_t s_ex = window_push(w_exit, A.qexit.count, to_exit, lane, PT_QUEUE_BLOCK);
-        if (to_exit) queue_store(A.qexit, s_ex, ox, oy, oz, dx, dy, dz, Tx, Ty, Tz, rs, job, depth, exit_mat, j_seg, j_draw, STATS, B.counters + 19);
+        if (to_exit)
+            queue_store(A.qexit, s_ex, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, Tx, Ty, Tz, rs, job, depth, exit_mat, j_seg, j_draw, STATS, B.counters + 19);
     }
     window_close(w_out, A.qout, lane);
     window_close(w_exit, A.qexit, lane);
-    const uint32_t w_seg = wave_sum(c_seg), w_draw = wave_sum(c_draw), w_ex = wave_sum(c_exit);
-    if (lane == 0) {
-        if (w_seg) atomicAdd(&B.counters[0], (unsigned long long)w_seg);
-        if (w_ex) atomicAdd(&B.counters[1], (unsigned long long)w_ex);
-        if (w_draw) atomicAdd(&B.counters[2], (unsigned long long)w_draw);
-    }
+    flush_count(&B.counters[0], c_seg, lane);
+    flush_count(&B.counters[1], c_exit, lane);
+    flush_count(&B.counters[2], c_draw, lane);
+    answer.flush(B.counters, lane);
 }
 
 // After the exit searches of a level (renderer.go:352-403): every entry of A.qin (the exit queue; `best` = the glass
-// material, `hit` / tmax = the answer of wf_traverse_kernel<1>) gets its attenuation, its origin moved to the exit
+// material, the policy's answer = where the way out ends) gets its attenuation, its origin moved to the exit
 // point and its roulette; survivors are appended to A.qout.
-template <bool STATS>
-__global__ __launch_bounds__(PT_BLOCK) void wf_exit_kernel(const WfArgs A) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const DevFrame &F = A.F;
+template <bool STATS, typename Answer>
+__device__ __forceinline__ void exit_pass(const WfArgs &A, const DevMat *lds_mat, Answer answer) {
     const TraceBuffers &B = A.B;
     const PathQueue &Q = A.qin;
-    DevMat *lds_mat = reinterpret_cast<DevMat *>(smem);
-    {
-        const uint64_t *g1 = reinterpret_cast<const uint64_t *>(B.mats);
-        uint64_t *l1 = reinterpret_cast<uint64_t *>(lds_mat);
-        const int n1 = F.nmat * (int)(sizeof(DevMat) / 8);
-        for (int i = threadIdx.x; i < n1; i += PT_BLOCK) l1[i] = g1[i];
-        __syncthreads();
-    }
-    typedef const uint32_t __attribute__((address_space(4))) *ConstU32Ptr;
     const uint32_t lane = threadIdx.x & (PT_WAVE - 1);
-    const uint32_t n_count = *(ConstU32Ptr)(Q.count);
-    const uint32_t n = n_count < Q.cap ? n_count : Q.cap;
-    const size_t qc = Q.cap;
+    const uint32_t n = queue_len(Q);
     uint32_t c_draw = 0;
     QueueWindow w_out;
     for (uint32_t i0 = blockIdx.x * PT_BLOCK + (threadIdx.x & ~(PT_WAVE - 1u)); i0 < n; i0 += gridDim.x * PT_BLOCK) {
         const uint32_t i = i0 + lane;
         bool go_on = false;
-        double ox = 0, oy = 0, oz = 0, dx = 0, dy = 0, dz = 0, Tx = 0, Ty = 0, Tz = 0;
+        RayD r{0, 0, 0, 0, 0, 0};
+        double Tx = 0, Ty = 0, Tz = 0;
         uint64_t rs = 0;
         uint32_t job = PT_HOLE, j_seg = 0, j_draw = 0;
         int depth = 0;
         if (i < n) job = Q.job[i];
         if (job != PT_HOLE) {
-            ox = Q.d[i]; oy = Q.d[qc + i]; oz = Q.d[2 * qc + i];
-            dx = Q.d[3 * qc + i]; dy = Q.d[4 * qc + i]; dz = Q.d[5 * qc + i];
-            Tx = Q.d[6 * qc + i]; Ty = Q.d[7 * qc + i]; Tz = Q.d[8 * qc + i];
-            const double tmax = Q.d[9 * qc + i];
-            rs = Q.rs[i];
-            depth = Q.depth[i];
+            r = queue_load_ray(Q, i);
+            int ebest = -1;
+            double tmax = 0;
+            if (Answer::before_state) answer(Q, i, r, ebest, tmax);
+            queue_load_state(Q, i, Tx, Ty, Tz, rs, depth, j_seg, j_draw, STATS);
+            if (!Answer::before_state) answer(Q, i, r, ebest, tmax);
             const int exit_mat = Q.best[i];
-            const int ebest = Q.hit[i];
-            if (STATS) { j_seg = Q.jseg[i]; j_draw = Q.jdraw[i]; }
             double attx = 1, atty = 1, attz = 1;
-            exit_post(lds_mat[exit_mat], ebest, tmax, ox, oy, oz, dx, dy, dz, attx, atty, attz);
-            const bool finished = roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
-            if (finished) {
-                ptk::store_radiance(B.L, job, Tx * 0.0, Ty * 0.0, Tz * 0.0);
-                if (STATS) { B.job_seg[job] = j_seg; B.job_draw[job] = j_draw; }
-            } else {
-                go_on = true;
-            }
+            exit_post(lds_mat[exit_mat], ebest, tmax, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, attx, atty, attz);
+            go_on = !roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
+            if (!go_on) store_path_end<STATS>(B, job, Tx * 0.0, Ty * 0.0, Tz * 0.0, j_seg, j_draw);
         }
         const uint32_t s_out = window_push(w_out, A.qout.count, go_on, lane, PT_CONT_BLOCK);
-        if (go_on) queue_store(A.qout, s_out, ox, oy, oz, dx, dy, dz, Tx, Ty, Tz, rs, job, depth, -1, j_seg, j_draw, STATS, B.counters + 19);
+        if (go_on) queue_store(A.qout, s_out, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, Tx, Ty, Tz, rs, job, depth, -1, j_seg, j_draw, STATS, B.counters + 19);
     }
     window_close(w_out, A.qout, lane);
-    const uint32_t w_draw = wave_sum(c_draw);
-    if (lane == 0 && w_draw) atomicAdd(&B.counters[2], (unsigned long long)w_draw);
+    flush_count(&B.counters[2], c_draw, lane);
+    answer.flush(B.counters, lane);
+}
+
+// The wavefront form of the two passes: small scenes keep world and materials in LDS; BVH scenes: materials only (objects come from
+// HBM / L2).
+template <bool STATS>
+__global__ __launch_bounds__(PT_BLOCK) void wf_shade_kernel(const WfArgs A) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const DevFrame &F = A.F;
+    const bool world_in_lds = F.world_in_lds != 0;
+    DevObj *lds_obj = reinterpret_cast<DevObj *>(smem);
+    DevMat *lds_mat = reinterpret_cast<DevMat *>(smem + (world_in_lds ? (size_t)F.nobj * sizeof(DevObj) : 0));
+    if (world_in_lds) stage_lds(lds_obj, A.B.objs, F.nobj * (int)(sizeof(DevObj) / 8));
+    stage_lds(lds_mat, A.B.mats, F.nmat * (int)(sizeof(DevMat) / 8));
+    shade_pass<STATS>(A, world_in_lds ? lds_obj : A.B.objs, lds_mat, QueueAnswer{});
+}
+template <bool STATS>
+__global__ __launch_bounds__(PT_BLOCK) void wf_exit_kernel(const WfArgs A) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    DevMat *lds_mat = reinterpret_cast<DevMat *>(smem);
+    stage_lds(lds_mat, A.B.mats, A.F.nmat * (int)(sizeof(DevMat) / 8));
+    exit_pass<STATS>(A, lds_mat, QueueAnswer{});
 }
 
 }  // namespace ptk

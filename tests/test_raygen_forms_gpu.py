@@ -12,7 +12,8 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("form", ["pool", "column", "simple"])
-@pytest.mark.parametrize("w,h,spp,chunk", [(96, 54, 5, 0), (33, 17, 9, 0), (70, 45, 11, 4), (1, 1, 130, 0)])
+@pytest.mark.parametrize("w,h,spp,chunk", [(96, 54, 5, 0), (33, 17, 9, 0), (70, 45, 11, 4), (1, 1, 130, 0),
+                                           (9, 9, 5, 2)])  # 9 x 9: one 8x8 block plus ragged edge blocks, a wave's pool or column mostly outside the frame
 def test_every_form_of_the_lens_walk_gives_the_oracle_frame(monkeypatch, oracle, form, w, h, spp, chunk):
     from path_trace_golang_amd import capi, scene
 

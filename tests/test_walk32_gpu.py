@@ -99,3 +99,24 @@ def test_full_size_frame_equals_the_all_in_one_loop(monkeypatch, gpu_ctx):
     st, img, acc, _, _, _ = _render(monkeypatch, sc, w, h, spp, depth, 2, scan="")
     assert st["segments"] == st_ref["segments"] and st["draws"] == st_ref["draws"]
     assert np.array_equal(img, ref) and np.array_equal(acc, acc_ref)
+
+
+GRADIENT_SKY = {"type": "gradient", "horizon": {"r": 0.6, "g": 0.7, "b": 0.9}, "zenith": {"r": 0.1, "g": 0.2, "b": 0.6}}
+
+
+@pytest.mark.parametrize("sky", [None, GRADIENT_SKY], ids=["no_sky", "gradient_sky"])
+def test_small_frame_in_both_builds(monkeypatch, oracle, sky):
+    """Through render_vs_oracle, which also runs the shipping build: the exact shade and exit passes without per-pixel counts, on a
+    ragged 33 x 17 frame over 300 objects, without a sky (the background colour) and with a gradient (the sky closure's other branch)."""
+    from conftest import render_vs_oracle
+    from path_trace_golang_amd import capi, scene, synth
+
+    w, h, spp, depth, seed = 33, 17, 3, 6, 5
+    doc = synth.make_scene(300, seed=5).encode()
+    doc["sky"] = sky
+    o = oracle.render(oracle.Scene(doc), w, h, spp, depth, seed=seed)
+    assert o["stats"]["exit_scans"] > 0  # the exit pass has entries
+    monkeypatch.setenv("PTCORE_PIPELINE", "walk32")
+    monkeypatch.setenv("PTCORE_SCAN", "bvh")
+    with capi.Context(ndev=1) as ctx:
+        render_vs_oracle(ctx, scene.Scene.decode(doc), o, w, h, spp, depth, seed, tag="walk32")

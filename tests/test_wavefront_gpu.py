@@ -76,3 +76,26 @@ def test_wavefront_full_size_frame_equals_the_all_in_one_loop(monkeypatch, gpu_c
     st, img, acc, _, _ = _render(monkeypatch, sc, w, h, spp, depth, 2, False)
     assert st["segments"] == st_ref["segments"] and st["draws"] == st_ref["draws"]
     assert np.array_equal(img, ref) and np.array_equal(acc, acc_ref)
+
+
+GRADIENT_SKY = {"type": "gradient", "horizon": {"r": 0.6, "g": 0.7, "b": 0.9}, "zenith": {"r": 0.1, "g": 0.2, "b": 0.6}}
+
+
+@pytest.mark.parametrize("sky", ["scene", None, GRADIENT_SKY], ids=["own_sky", "no_sky", "gradient_sky"])
+def test_flat_scene_on_a_small_frame_in_both_builds(monkeypatch, oracle, sky):
+    """metal_glass_room is a flat scene (world in LDS) with glass (the exit pass).  Through render_vs_oracle, which also runs the
+    shipping build: the instantiations of the shade and exit passes without per-pixel counts, on a ragged 33 x 17 frame, with the
+    scene's own solid sky, with none (the background colour) and with a gradient (the sky closure's other branch)."""
+    from conftest import render_vs_oracle
+    from path_trace_golang_amd import capi, scene
+
+    w, h, spp, depth, seed = 33, 17, 3, 6, 5
+    doc = scene.load(scene_path("metal_glass_room")).encode()
+    if sky != "scene":
+        doc["sky"] = sky
+    o = oracle.render(oracle.Scene(doc), w, h, spp, depth, seed=seed)
+    assert o["stats"]["exit_scans"] > 0  # the exit pass has entries
+    monkeypatch.setenv("PTCORE_PIPELINE", "wavefront")
+    monkeypatch.setenv("PTCORE_WF_SORT", "0")
+    with capi.Context(ndev=1) as ctx:
+        render_vs_oracle(ctx, scene.Scene.decode(doc), o, w, h, spp, depth, seed, tag="wavefront")
