@@ -17,6 +17,7 @@
 // coalesced L traffic) and a wave that claims a job range stays inside one block.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 namespace ptd {
@@ -95,6 +96,35 @@ inline int32_t bvh_node_base(const BvhNode &n) { return n.node_base; }
 inline int32_t bvh_obj_base(const BvhNode &n) { return n.obj_base; }
 inline double bvh_slot_lo(const BvhNode &n, int k, int s) { return (double)n.c[k][s] - (double)n.h[k][s]; }
 inline double bvh_slot_hi(const BvhNode &n, int k, int s) { return (double)n.c[k][s] + (double)n.h[k][s]; }
+
+#ifdef __HIPCC__
+#define PT_HOST_DEVICE __host__ __device__
+#else
+#define PT_HOST_DEVICE
+#endif
+// Dynamic LDS of a block that stages the world (the flat scans of trace_kernel, glass_kernel), as byte offsets.  The host sizes
+// the launch from the same struct the kernels take their pointers from:
+//   [0, mat)                DevObj objs[nobj]
+//   [mat, kidx)             DevMat mats[nmat]
+//   [kidx, kidx_diel)       int    record -> object index of the full lists (spheres, then boxes)
+//   [kidx_diel, world)      int    ... of the dielectric-only lists (exit searches)
+//   [rec, rec_diel)         DevObj the full records' objects once more, in record order (16-byte aligned)   } single-group
+//   [rec_diel, total)       DevObj ... and the dielectric records'                                           } scans only
+// `world` is what is staged without the record-order copies; `total` is what the launch asks for.
+struct LdsLayout {
+    size_t mat, kidx, kidx_diel, world, rec, rec_diel, total;
+    // trace_kernel: all four index tables, then the full records and the dielectric records
+    static PT_HOST_DEVICE constexpr LdsLayout trace(size_t nobj, size_t nmat, size_t n_bsph, size_t n_bbox, size_t n_dsph, size_t n_dbox, bool rec_order) {
+        const size_t mat = nobj * sizeof(DevObj), kidx = mat + nmat * sizeof(DevMat), kidx_diel = kidx + (n_bsph + n_bbox) * sizeof(int32_t);
+        const size_t world = kidx_diel + (n_dsph + n_dbox) * sizeof(int32_t), rec = (world + 15) & ~(size_t)15;
+        const size_t rec_diel = rec + (n_bsph + n_bbox) * sizeof(DevObj);
+        return LdsLayout{mat, kidx, kidx_diel, world, rec, rec_diel, rec_order ? rec_diel + (n_dsph + n_dbox) * sizeof(DevObj) : world};
+    }
+    // glass_kernel: the dielectric tables and records only, i.e. the trace shape without full lists
+    static PT_HOST_DEVICE constexpr LdsLayout glass(size_t nobj, size_t nmat, size_t n_dsph, size_t n_dbox, bool rec_order) {
+        return trace(nobj, nmat, 0, 0, n_dsph, n_dbox, rec_order);
+    }
+};
 
 // Object as stored in node order for the BVH path: the 80-byte DevObj plus its index in file order
 // (tie rules and the winner look-up use the original index).

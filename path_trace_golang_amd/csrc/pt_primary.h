@@ -65,10 +65,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_PRIMARY_WAVES) void primary_bvh_kernel
         uint32_t j_seg = 0, j_draw = nd;
         if (have) { c_samples++; c_draw += nd; }
         if (F.max_depth <= 0) {  // rayColorOpt returns black before any scan (renderer.go:287-289); the camera draws happened
-            if (have) {
-                store_radiance(B.L, job, 0.0, 0.0, 0.0);
-                if (STATS) { B.job_seg[job] = 0; B.job_draw[job] = nd; }
-            }
+            if (have) store_path_end<STATS>(&B, job, 0.0, 0.0, 0.0, 0u, nd);
             continue;
         }
         // ------------------------------------------------------------ is this a wave for the shared walk?
@@ -219,7 +216,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_PRIMARY_WAVES) void primary_bvh_kernel
                 double termx = 0, termy = 0, termz = 0;
                 if (best < 0) {
                     finished = true;
-                    sky_radiance(A.sky, dx, dy, dz, termx, termy, termz);
+                    sky_radiance(&A.sky, dx, dy, dz, termx, termy, termz);
                 } else {
                     double attx = 1, atty = 1, attz = 1;
                     bool exit_search = false;
@@ -230,15 +227,13 @@ __global__ __launch_bounds__(PT_BLOCK, PT_PRIMARY_WAVES) void primary_bvh_kernel
                     if (!finished) finished = roulette_advance<true>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, jd);
                     j_draw = jd;
                 }
-                if (finished) {
-                    store_radiance(B.L, job, Tx * termx, Ty * termy, Tz * termz);
-                    if (STATS) { B.job_seg[job] = j_seg; B.job_draw[job] = j_draw; }
-                } else {
-                    go_on = true;
-                }
+                if (finished) store_path_end<STATS>(&B, job, Tx * termx, Ty * termy, Tz * termz, j_seg, j_draw);
+                else go_on = true;
             }
         }
         // ------------------------------------------------------------ survivors -> continuation queue (as glass_kernel does)
+        // (hand-written, by slot: through window_reserve / queue_store of pt_kernels.h the STATS and VERIFY forms of this kernel, which sits at its 80
+        // VGPRs with 55 - 71 spilled SGPRs, spill 2 - 6 VGPRs to scratch: profiles/core_dedupe_kernel_regs.txt)
         const uint64_t pm = __ballot(go_on);
         if (pm != 0) {
             const uint32_t np = (uint32_t)__popcll(pm), room = q_end - q_cur;
@@ -276,20 +271,16 @@ __global__ __launch_bounds__(PT_BLOCK, PT_PRIMARY_WAVES) void primary_bvh_kernel
         }
     }
     for (uint32_t s = q_cur + lane; s < q_end && s < B.cont.cap; s += PT_WAVE) B.cont.job[s] = PT_HOLE;  // the rest of the window stays empty
-    const uint32_t w_seg = wave_sum(c_seg), w_draw = wave_sum(c_draw), w_samples = wave_sum(c_samples), w_cont = wave_sum(c_cont);
+    flush_count(&B.counters[0], c_seg, lane);
+    flush_count(&B.counters[2], c_draw, lane);
+    flush_count(&B.counters[3], c_samples, lane);
+    flush_count(&B.counters[6], c_cont, lane);
     if (lane == 0) {
-        if (w_seg) atomicAdd(&B.counters[0], (unsigned long long)w_seg);
-        if (w_draw) atomicAdd(&B.counters[2], (unsigned long long)w_draw);
-        if (w_samples) atomicAdd(&B.counters[3], (unsigned long long)w_samples);
-        if (w_cont) atomicAdd(&B.counters[6], (unsigned long long)w_cont);
         if (c_visits) atomicAdd(&B.counters[40], (unsigned long long)c_visits);  // wave-level node visits (diagnostics)
         if (c_coop) atomicAdd(&B.counters[41], (unsigned long long)c_coop);      // blocks of 64 jobs walked by the wave
         if (c_odd) atomicAdd(&B.counters[42], (unsigned long long)c_odd);        // ... handed over unshaded
     }
-    if (VERIFY) {
-        const uint32_t w_mis = wave_sum(c_mismatch);
-        if (lane == 0 && w_mis) atomicAdd(&B.counters[4], (unsigned long long)w_mis);
-    }
+    if (VERIFY) flush_count(&B.counters[4], c_mismatch, lane);
 }
 
 }  // namespace ptk

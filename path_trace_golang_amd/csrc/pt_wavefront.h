@@ -70,84 +70,9 @@ __device__ __forceinline__ uint32_t queue_len(const PathQueue &q) {
     const uint32_t n_count = *(ConstU32Ptr)(q.count);
     return n_count < q.cap ? n_count : q.cap;
 }
-// Block-cooperative copy of n 8-byte words into LDS (the world, the materials), ending in the block's barrier.
-__device__ __forceinline__ void stage_lds(void *lds, const void *src, int n) {
-    const uint64_t *g = reinterpret_cast<const uint64_t *>(src);
-    uint64_t *l = reinterpret_cast<uint64_t *>(lds);
-    for (int i = threadIdx.x; i < n; i += PT_BLOCK) l[i] = g[i];
-    __syncthreads();
-}
-// A lane's count -> one atomic per wave, none for a zero.
-__device__ __forceinline__ void flush_count(unsigned long long *counter, uint32_t c, uint32_t lane) {
-    const uint32_t w = wave_sum(c);
-    if (lane == 0 && w) atomicAdd(counter, (unsigned long long)w);
-}
-// Verify modes: one segment on which a scan and the reference's own loop (best2, tmax2) disagree, left in counters[8..17] for the host to
-// print; `tag` says who found it (the scan mode, plus what the caller knows).
-__device__ __forceinline__ void record_mismatch(unsigned long long *counters, int best, int best2, double tmax, double tmax2, unsigned long long tag,
-                                                const RayD &r) {
-    unsigned long long *dbg = counters + 8;
-    dbg[0] = ((unsigned long long)(uint32_t)best << 32) | (uint32_t)best2;
-    dbg[1] = ptm::to_bits(tmax);
-    dbg[2] = ptm::to_bits(tmax2);
-    dbg[3] = tag;
-    dbg[4] = ptm::to_bits(r.ox); dbg[5] = ptm::to_bits(r.oy); dbg[6] = ptm::to_bits(r.oz);
-    dbg[7] = ptm::to_bits(r.dx); dbg[8] = ptm::to_bits(r.dy); dbg[9] = ptm::to_bits(r.dz);
-}
-// A path ends: its radiance record and, with STATS, its segment and draw counts.
-template <bool STATS>
-__device__ __forceinline__ void store_path_end(const TraceBuffers &B, uint32_t job, double x, double y, double z, uint32_t j_seg, uint32_t j_draw) {
-    ptk::store_radiance(B.L, job, x, y, z);
-    if (STATS) { B.job_seg[job] = j_seg; B.job_draw[job] = j_draw; }
-}
+// (The staging copies, the queue window and entry store, flush_count, record_mismatch and store_path_end are pt_kernels.h's.)
 
-// One wave's window into a queue it appends to (block reservation: see trace_kernel's glass queue).
-struct QueueWindow {
-    uint32_t cur = 0, end = 0;
-};
-// Slots for the lanes with `push` set; lanes without get an unspecified value.
-__device__ __forceinline__ uint32_t window_push(QueueWindow &w, uint32_t *count, bool push, uint32_t lane, uint32_t block) {
-    const uint64_t pm = __ballot(push);
-    if (pm == 0) return 0;
-    const uint32_t np = (uint32_t)__popcll(pm), room = w.end - w.cur;
-    uint32_t nbase = 0;
-    if (np > room) {
-        if (lane == 0) nbase = atomicAdd(count, block);
-        nbase = __builtin_amdgcn_readfirstlane(nbase);
-    }
-    const uint32_t rank = lane_rank(pm);
-    const uint32_t slot = rank < room ? w.cur + rank : nbase + (rank - room);
-    if (np > room) {
-        w.cur = nbase + (np - room);
-        w.end = nbase + block;
-    } else {
-        w.cur += np;
-    }
-    return slot;
-}
-__device__ __forceinline__ void window_close(const QueueWindow &w, const PathQueue &q, uint32_t lane) {
-    for (uint32_t s = w.cur + lane; s < w.end && s < q.cap; s += PT_WAVE) q.job[s] = PT_HOLE;
-}
-
-__device__ __forceinline__ void queue_store(const PathQueue &q, uint32_t slot, double ox, double oy, double oz, double dx, double dy,
-                                            double dz, double Tx, double Ty, double Tz, uint64_t rs, uint32_t job, int depth, int best,
-                                            uint32_t j_seg, uint32_t j_draw, bool stats, unsigned long long *overflow) {
-    const size_t qc = q.cap;
-    if (slot >= q.cap) {  // cannot happen (the host sizes the queues for every path plus every window); never write outside,
-        atomicAdd(overflow, 1ull);  // and make the frame fail instead of losing a path quietly
-        return;
-    }
-    q.d[slot] = ox; q.d[qc + slot] = oy; q.d[2 * qc + slot] = oz;
-    q.d[3 * qc + slot] = dx; q.d[4 * qc + slot] = dy; q.d[5 * qc + slot] = dz;
-    q.d[6 * qc + slot] = Tx; q.d[7 * qc + slot] = Ty; q.d[8 * qc + slot] = Tz;
-    q.rs[slot] = rs;
-    q.job[slot] = job;
-    q.depth[slot] = depth;
-    q.best[slot] = best;
-    if (stats) { q.jseg[slot] = j_seg; q.jdraw[slot] = j_draw; }
-}
-
-// queue_store's mirror, in the two parts a pass reads an entry in: the ray, which finds (or is all that is needed to find) the entry's
+// The mirror of queue_store for one entry by its index, in the two parts a pass reads it in: the ray, which finds (or is all that is needed to find) the entry's
 // answer, and then the path state -- throughput, stream state, depth, the optional counts.  (The job id comes first: it tells a hole.)
 __device__ __forceinline__ RayD queue_load_ray(const PathQueue &q, uint32_t i) {
     const size_t qc = q.cap;
@@ -251,12 +176,12 @@ __global__ __launch_bounds__(PT_BLOCK) void wf_init_kernel(const WfArgs A) {
             c_samples++;
             c_draw += nd;
             if (F.max_depth <= 0) {  // rayColorOpt returns black before any scan (renderer.go:287-289)
-                store_path_end<STATS>(B, i, 0.0, 0.0, 0.0, 0u, nd);
+                store_path_end<STATS>(&B, i, 0.0, 0.0, 0.0, 0u, nd);
             } else {
                 job = i;
                 const size_t nj = F.njobs;
-                queue_store(A.qin, i, B.ray[i], B.ray[nj + i], B.ray[2 * nj + i], B.ray[3 * nj + i], B.ray[4 * nj + i], B.ray[5 * nj + i], 1.0,
-                            1.0, 1.0, B.ray_rng[i], i, F.max_depth, -1, 0u, nd, STATS, B.counters + 19);
+                queue_store<ENTRY_PLAIN, STATS>(&A.qin, &B, WindowPush::at(i), B.ray[i], B.ray[nj + i], B.ray[2 * nj + i], B.ray[3 * nj + i], B.ray[4 * nj + i],
+                                                B.ray[5 * nj + i], 1.0, 1.0, 1.0, 0.0, B.ray_rng[i], i, F.max_depth, -1, 0u, nd);
             }
         }
         if (job == PT_HOLE && i < A.qin.cap) A.qin.job[i] = PT_HOLE;
@@ -414,8 +339,7 @@ __global__ __launch_bounds__(PT_BLOCK) void wf_scan_flat_kernel(const WfArgs A) 
     const PathQueue &Q = A.qin;
     DevObj *lds_obj = reinterpret_cast<DevObj *>(smem);
     int *lds_kidx = reinterpret_cast<int *>(smem + (size_t)F.nobj * sizeof(DevObj));
-    for (int i = threadIdx.x; i < F.n_bsph; i += PT_BLOCK) lds_kidx[pt_record_slot(i, F.n_bsph)] = B.bsph[i].index;
-    for (int i = threadIdx.x; i < F.n_bbox; i += PT_BLOCK) lds_kidx[F.n_bsph + pt_record_slot(i, F.n_bbox)] = B.bbox[i].index;
+    stage_record_index(lds_kidx, B.bsph, B.bbox, F.n_bsph, F.n_bbox);
     stage_lds(lds_obj, B.objs, F.nobj * (int)(sizeof(DevObj) / 8));
     typedef const DevObj __attribute__((address_space(4))) *ConstObjPtr;
     typedef const BroadSphere __attribute__((address_space(4))) *ConstSphPtr;
@@ -507,7 +431,7 @@ __device__ __forceinline__ void shade_pass(const WfArgs &A, const DevObj *objs, 
             double termx = 0, termy = 0, termz = 0, attx = 1, atty = 1, attz = 1;
             if (best < 0) {
                 finished = true;
-                sky_radiance(A.sky, r.dx, r.dy, r.dz, termx, termy, termz);
+                sky_radiance(&A.sky, r.dx, r.dy, r.dz, termx, termy, termz);
             } else {
                 bool exit_search = false;
                 shade_hit<STATS, true>(objs[best], lds_mat, tmax, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, rs, c_draw, j_draw, finished, termx, termy,
@@ -520,16 +444,19 @@ __device__ __forceinline__ void shade_pass(const WfArgs &A, const DevObj *objs, 
                     go_on = !finished;
                 }
             }
-            if (finished) store_path_end<STATS>(B, job, Tx * termx, Ty * termy, Tz * termz, j_seg, j_draw);
+            if (finished) store_path_end<STATS>(&B, job, Tx * termx, Ty * termy, Tz * termz, j_seg, j_draw);
         }
-        const uint32_t s_out = window_push(w_out, A.qout.count, go_on, lane, PT_CONT_BLOCK);
-        if (go_on) queue_store(A.qout, s_out, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, Tx, Ty, Tz, rs, job, depth, -1, j_seg, j_draw, STATS, B.counters + 19);
-        const uint32_t s_ex = window_push(w_exit, A.qexit.count, to_exit, lane, PT_QUEUE_BLOCK);
-        if (to_exit)
-            queue_store(A.qexit, s_ex, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, Tx, Ty, Tz, rs, job, depth, exit_mat, j_seg, j_draw, STATS, B.counters + 19);
+        if (const uint64_t pm = __ballot(go_on)) {
+            const WindowPush wp = window_reserve(w_out, &A.qout, pm, lane, PT_CONT_BLOCK);
+            if (go_on) queue_store<ENTRY_PLAIN, STATS>(&A.qout, &B, WindowPush::at(wp.slot), r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, Tx, Ty, Tz, 0.0, rs, job, depth, -1, j_seg, j_draw);
+        }
+        if (const uint64_t pm = __ballot(to_exit)) {
+            const WindowPush wp = window_reserve(w_exit, &A.qexit, pm, lane, PT_QUEUE_BLOCK);
+            if (to_exit) queue_store<ENTRY_BEST, STATS>(&A.qexit, &B, WindowPush::at(wp.slot), r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, Tx, Ty, Tz, 0.0, rs, job, depth, exit_mat, j_seg, j_draw);
+        }
     }
-    window_close(w_out, A.qout, lane);
-    window_close(w_exit, A.qexit, lane);
+    window_close(w_out, &A.qout, lane);
+    window_close(w_exit, &A.qexit, lane);
     flush_count(&B.counters[0], c_seg, lane);
     flush_count(&B.counters[1], c_exit, lane);
     flush_count(&B.counters[2], c_draw, lane);
@@ -567,12 +494,14 @@ __device__ __forceinline__ void exit_pass(const WfArgs &A, const DevMat *lds_mat
             double attx = 1, atty = 1, attz = 1;
             exit_post(lds_mat[exit_mat], ebest, tmax, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, attx, atty, attz);
             go_on = !roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
-            if (!go_on) store_path_end<STATS>(B, job, Tx * 0.0, Ty * 0.0, Tz * 0.0, j_seg, j_draw);
+            if (!go_on) store_path_end<STATS>(&B, job, Tx * 0.0, Ty * 0.0, Tz * 0.0, j_seg, j_draw);
         }
-        const uint32_t s_out = window_push(w_out, A.qout.count, go_on, lane, PT_CONT_BLOCK);
-        if (go_on) queue_store(A.qout, s_out, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, Tx, Ty, Tz, rs, job, depth, -1, j_seg, j_draw, STATS, B.counters + 19);
+        if (const uint64_t pm = __ballot(go_on)) {
+            const WindowPush wp = window_reserve(w_out, &A.qout, pm, lane, PT_CONT_BLOCK);
+            if (go_on) queue_store<ENTRY_PLAIN, STATS>(&A.qout, &B, WindowPush::at(wp.slot), r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, Tx, Ty, Tz, 0.0, rs, job, depth, -1, j_seg, j_draw);
+        }
     }
-    window_close(w_out, A.qout, lane);
+    window_close(w_out, &A.qout, lane);
     flush_count(&B.counters[2], c_draw, lane);
     answer.flush(B.counters, lane);
 }

@@ -1634,7 +1634,7 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     // groups of 32; more -> BVH.  PTCORE_SCAN overrides.
     int scan = ctx->scan_mode;
     // the LDS copy of the world (objects + materials + record indices) must leave room for five blocks per CU
-    const size_t world_lds = sd.world.size() * sizeof(DevObj) + sd.mats.size() * sizeof(DevMat) + (sd.bsph.size() + sd.bbox.size() + sd.bsph_diel.size() + sd.bbox_diel.size()) * sizeof(int);
+    const size_t world_lds = LdsLayout::trace(sd.world.size(), sd.mats.size(), sd.bsph.size(), sd.bbox.size(), sd.bsph_diel.size(), sd.bbox_diel.size(), false).world;
     const bool wide_ok = F.broad_ok == 2 && world_lds <= 30 * 1024;
     if (scan < 0) scan = F.broad_ok == 1 ? ptk::SCAN_BROAD : wide_ok ? ptk::SCAN_BROAD_WIDE : ptk::SCAN_BVH;
     if ((scan == ptk::SCAN_BROAD || scan == ptk::SCAN_VERIFY) && F.broad_ok != 1) {
@@ -1754,16 +1754,11 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     if (const char *e = std::getenv("PTCORE_BVH_LDS_BUDGET")) lds_budget = (size_t)std::max(0, std::min(160 * 1024, std::atoi(e)));
     if (big && F.bvh_root == 0 && stack_bytes < lds_budget)
         F.bvh_lds_nodes = (int32_t)std::min<size_t>((lds_budget - stack_bytes) / sizeof(BvhNode), (size_t)F.bvh_main_nodes);
+    // single-group scans keep the records' objects a second time, in record order (LdsLayout, pt_device.h); glass_kernel the dielectric ones
+    const bool rec_order = scan == ptk::SCAN_BROAD || scan == ptk::SCAN_VERIFY;
     sd.lds_bytes = big ? stack_bytes + (size_t)F.bvh_lds_nodes * sizeof(BvhNode)
-                       : (size_t)F.nobj * sizeof(DevObj) + (size_t)F.nmat * sizeof(DevMat) +
-                             (size_t)(sd.bsph.size() + sd.bbox.size() + sd.bsph_diel.size() + sd.bbox_diel.size()) * sizeof(int);  // (+ the dielectric-only tables of FORM_NESTED)
-    // single-group scans keep the records' objects a second time, in record order (trace_kernel: lds_rec)
-    if (scan == ptk::SCAN_BROAD || scan == ptk::SCAN_VERIFY)
-        sd.lds_bytes = ((sd.lds_bytes + 15) & ~(size_t)15) + (sd.bsph.size() + sd.bbox.size() + sd.bsph_diel.size() + sd.bbox_diel.size()) * sizeof(DevObj);
-    sd.glass_lds_bytes = (size_t)F.nobj * sizeof(DevObj) + (size_t)F.nmat * sizeof(DevMat) +
-                         (size_t)(sd.bsph_diel.size() + sd.bbox_diel.size()) * sizeof(int);
-    if (scan == ptk::SCAN_BROAD || scan == ptk::SCAN_VERIFY)  // glass_kernel<*, *, false>: the dielectric records' objects in record order
-        sd.glass_lds_bytes = ((sd.glass_lds_bytes + 15) & ~(size_t)15) + (sd.bsph_diel.size() + sd.bbox_diel.size()) * sizeof(DevObj);
+                       : LdsLayout::trace((size_t)F.nobj, (size_t)F.nmat, sd.bsph.size(), sd.bbox.size(), sd.bsph_diel.size(), sd.bbox_diel.size(), rec_order).total;
+    sd.glass_lds_bytes = LdsLayout::glass((size_t)F.nobj, (size_t)F.nmat, sd.bsph_diel.size(), sd.bbox_diel.size(), rec_order).total;
     // PTCORE_BVH_LDS_PAD=<bytes>: unused LDS on top of the BVH plan (occupancy experiments: 4 blocks per CU fit 40 KiB each)
     if (const char *e = std::getenv("PTCORE_BVH_LDS_PAD"))
         if (big) sd.lds_bytes += (size_t)std::max(0, std::min(120 * 1024, std::atoi(e)));
