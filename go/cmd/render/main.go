@@ -6,6 +6,7 @@
 // -scene-settings (the editor's scene-settings override, internal/ui/app.go:60-75; off = main.go:52),
 // -noise -noise-step (render until the frame noise is at or below the target, -spp being the cap; DESIGN 3.9),
 // -adaptive -min-spp (with -noise: every 8x8 block stops at the target by itself; DESIGN 3.10).
+// -atrous -atrous-iters -features (the variance-guided a-trous filtered image and its first-hit feature samples; DESIGN 3.11).
 package main
 
 import (
@@ -37,6 +38,9 @@ func main() {
 	noiseStep := flag.Int("noise-step", 16, "samples per pixel between two noise checks (or PATHTRACER_GPU_NOISE_STEP)")
 	adaptive := flag.Bool("adaptive", false, "with -noise: stop every 8x8 block at the target by itself (or PATHTRACER_GPU_ADAPTIVE)")
 	minSpp := flag.Int("min-spp", 0, "with -adaptive: samples every block gets before the first check (or PATHTRACER_GPU_ADAPTIVE_MIN_SPP)")
+	atrous := flag.Bool("atrous", false, "write the variance-guided a-trous filtered image (or PATHTRACER_GPU_ATROUS)")
+	atrousIters := flag.Int("atrous-iters", 5, "with -atrous: iterations 0..6 (or PATHTRACER_GPU_ATROUS_ITERS)")
+	features := flag.Int("features", -1, "first-hit feature samples per pixel (default: 4 with -atrous where the scene allows them, else 0; or PATHTRACER_GPU_FEATURES)")
 	flag.Parse()
 	log.Printf("flags: scene=%s mode=%s headless=%v out=%s\n", *scenePath, *mode, *headless, *output)
 
@@ -53,6 +57,17 @@ func main() {
 		flag.Visit(func(f *flag.Flag) { adaptiveGiven = adaptiveGiven || f.Name == "adaptive" || f.Name == "min-spp" })
 		if adaptiveGiven { // else the environment decides
 			hip.SetAdaptive(*adaptive, *minSpp)
+		}
+		atrousGiven, featuresGiven := false, false
+		flag.Visit(func(f *flag.Flag) {
+			atrousGiven = atrousGiven || f.Name == "atrous" || f.Name == "atrous-iters"
+			featuresGiven = featuresGiven || f.Name == "features"
+		})
+		if atrousGiven { // else the environment decides
+			hip.SetAtrous(*atrous, *atrousIters)
+		}
+		if featuresGiven {
+			hip.SetFeatures(*features)
 		}
 	} else {
 		engine.SetBackend(engine.BackendCPU)

@@ -58,7 +58,24 @@ var (
 	adaptiveOn     bool
 	adaptiveMinSpp int
 	lastAdaptive   AdaptiveState // pt_adaptive_state of the last frame (zero unless it was adaptive)
+
+	atrousSet   bool // false: PATHTRACER_GPU_ATROUS / PATHTRACER_GPU_ATROUS_ITERS decide
+	atrousOn    bool
+	atrousIters = 5
+	featuresK   = -1         // -1: not said, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows)
+	lastAtrous  AtrousStats // pt_atrous_stats of the last frame (zero unless it was filtered)
 )
+
+// AtrousStats mirrors pt_atrous_stats: what the a-trous filter did to the last frame.
+type AtrousStats struct {
+	Ms          float64
+	Launches    int
+	Iterations  int
+	NoiseBefore float64
+	NoiseAfter  float64
+	BadPixels   uint64
+	Features    int // feature samples per pixel the frame collected
+}
 
 // AdaptiveState mirrors struct pt_adaptive_state: the block table of an adaptive frame.
 type AdaptiveState struct {
@@ -112,6 +129,78 @@ func SetAdaptive(on bool, minSpp int) {
 		minSpp = 0
 	}
 	adaptiveMinSpp = minSpp
+}
+
+// SetAtrous makes Render write the variance-guided a-trous filtered image (pt_atrous, DESIGN 3.11) instead of the plain finish:
+// moments are collected, and the first-hit feature planes too where the scene allows them.  iterations is 0..6.
+func SetAtrous(on bool, iterations int) {
+	mu.Lock()
+	defer mu.Unlock()
+	atrousSet, atrousOn = true, on
+	if iterations < 0 || iterations > 6 {
+		iterations = 5
+	}
+	atrousIters = iterations
+}
+
+// SetFeatures sets the first-hit feature samples per pixel (pt_set_features); k < 0 = not said.
+func SetFeatures(k int) {
+	mu.Lock()
+	defer mu.Unlock()
+	if k < 0 {
+		k = -1
+	}
+	featuresK = k
+}
+
+// LastAtrous reports the filter's figures for the last frame Render finished (the zero value unless it was filtered).
+func LastAtrous() AtrousStats {
+	mu.Lock()
+	defer mu.Unlock()
+	return lastAtrous
+}
+
+// atrousRule: whether the filter is in force and its iterations (SetAtrous, else the environment).
+func atrousRule() (bool, int) {
+	if atrousSet {
+		return atrousOn, atrousIters
+	}
+	on, iters := false, 5
+	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_ATROUS"))) {
+	case "1", "true", "on", "yes":
+		on = true
+	}
+	if v, err := strconv.Atoi(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_ATROUS_ITERS"))); err == nil && v >= 0 && v <= 6 {
+		iters = v
+	}
+	return on, iters
+}
+
+// featuresRule: the feature samples per pixel of the next frame.  Not said (SetFeatures, PATHTRACER_GPU_FEATURES): 4 under the
+// filter unless the frame would refuse them (GL shading, a scene on the BVH path), else 0.
+func featuresRule(sc *scene.Scene, atrous bool) int {
+	if featuresK >= 0 {
+		return featuresK
+	}
+	if v, err := strconv.Atoi(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_FEATURES"))); err == nil && v >= 0 {
+		return v
+	}
+	if !atrous || glShading() {
+		return 0
+	}
+	spheres, boxes := 0, 0
+	for _, o := range sc.Objects {
+		switch o.Type {
+		case scene.ObjectSphere, scene.ObjectSphereLight:
+			spheres++
+		case scene.ObjectBox:
+			boxes++
+		}
+	}
+	if scan := os.Getenv("PTCORE_SCAN"); spheres > 128 || boxes > 128 || scan == "bvh" || scan == "verify_bvh" {
+		return 0
+	}
+	return 4
 }
 
 // LastAdaptive reports the block table of the last frame Render finished (the zero value unless it was adaptive).
@@ -360,6 +449,34 @@ func setShading(sc *scene.Scene) error {
 // at the end (the cadence of gpu.go:2209-2212, :2229, :2523-2525).  On any error the caller
 // (engine.renderIntoGPU) falls back to the CPU renderer exactly as it does for the GL backend.
 func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func()) error {
+	err := renderFrame(sc, cfg, img, progress)
+	if err != nil || sc == nil || img == nil || len(img.Pix) == 0 {
+		return err
+	}
+	mu.Lock()
+	defer mu.Unlock()
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	lastAtrous = AtrousStats{}
+	if on, iters := atrousRule(); on && ctx != nil && img.Bounds().Dx() == cfg.Width && img.Bounds().Dy() == cfg.Height {
+		// the filtered image takes the place of the plain finish (the sums stay readable after pt_end)
+		ac := C.pt_atrous_config{iterations: C.int32_t(iters), sigma_l: 4, sigma_n: 0.1, sigma_z: 0.1, sigma_a: 0.2}
+		var st C.pt_atrous_stats
+		if rc := C.pt_atrous(ctx, &ac, (*C.uint8_t)(unsafe.Pointer(&img.Pix[0])), C.int32_t(img.Stride), nil, nil, &st); rc != C.PT_OK {
+			return lastError("pt_atrous")
+		}
+		lastAtrous = AtrousStats{Ms: float64(st.atrous_ms), Launches: int(st.launches), Iterations: int(st.iterations),
+			NoiseBefore: float64(st.noise_before), NoiseAfter: float64(st.noise_after), BadPixels: uint64(st.bad_pixels),
+			Features: featuresRule(sc, true)}
+		if progress != nil {
+			progress()
+		}
+	}
+	return nil
+}
+
+// renderFrame: the frame itself (Render adds the a-trous filter behind it when that is on).
+func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func()) error {
 	if sc == nil || img == nil {
 		return errors.New("hip.Render: nil scene or image")
 	}
@@ -388,8 +505,12 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 	}
 	target, nstep := noiseRule()
 	toNoise := target > 0
+	atrous, _ := atrousRule()
+	if rc := C.pt_set_features(ctx, C.int32_t(featuresRule(sc, atrous))); rc != C.PT_OK {
+		return lastError("pt_set_features")
+	}
 	var on C.int32_t
-	if toNoise {
+	if toNoise || atrous { // the filter reads the second moments
 		on = 1
 	}
 	if rc := C.pt_set_moments(ctx, on); rc != C.PT_OK {

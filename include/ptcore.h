@@ -426,6 +426,66 @@ int32_t pt_adaptive_state(pt_ctx *ctx, struct pt_adaptive_state *out);
 int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp);
 
 /*
+ * First-hit feature planes (additive to ABI 4): what each pixel looks at, for filters, picking and previews.  Off
+ * unless asked for: with k = 0 nothing is allocated or launched.
+ *   pt_set_features(ctx, k) : k = feature samples per pixel (0 = off, the default; k < 0 is PT_ERR_INVALID).  Later frames on ctx
+ *                             (pt_begin ... pt_end, pt_render) collect, per pixel and over its samples with index s < k, the first hit
+ *                             of the sample's primary ray -- the CPU engine's closest hit of the first segment -- as three raw sums
+ *                             of three doubles, added in sample order:
+ *                                 normal : the hit record's face-forward unit normal (a miss adds nothing)
+ *                                 albedo : the converted material's albedo (a missing material id is the zero material)
+ *                                 depth  : (sum of t * |direction|, samples that hit, feature samples taken = min(k, the pixel's count))
+ *                             72 B per pixel on the devices, outside PTCORE_L_BUDGET_MB.  pt_render_tiles_device neither collects
+ *                             nor fails.  A frame with k > 0 is refused with PT_ERR_INVALID, before anything is launched and with the
+ *                             context left usable, for scenes on the bounding-volume-hierarchy path (more than 128 spheres or 128
+ *                             boxes) and with GL shading (pt_set_shading).
+ *   pt_read_features        : normal / albedo / depth = width*height*3 doubles each, row-major, any of them NULL.  Valid exactly
+ *                             when pt_read_moments is (so the frame collects moments); PT_ERR_STATE otherwise and for a frame with k = 0.
+ *
+ * Variance-guided a-trous filter on linear radiance (additive to ABI 4; the model and its order of evaluation are
+ * stated in csrc/pt_atrous.h).  With c = S / n the pixel's mean and var the variance of that mean (the (v_r + v_g + v_b) / 3 of
+ * pt_noise_estimate, with the pixel's own n), `iterations` passes of a 5x5 B3-spline kernel at strides 1, 2, 4, ... weight tap j of
+ * pixel i by exp(-pen),
+ *     pen = |l_i - l_j| / (sigma_l * sqrt(var_i) + 1e-8) + max(0, 1 - N_i . N_j) / sigma_n
+ *         + |z_i - z_j| / (sigma_z * max(z_i, 1e-8)) + |A_i - A_j|^2 / sigma_a^2
+ * (l = the mean of the three channels of the current iteration; N, A, z = the feature sums over the samples that hit), and carry the
+ * variance along (var' = sum of w^2 var_j / (sum of w)^2).  A frame without features runs with the three feature terms off, whatever
+ * the sigmas.  A pixel whose mean or variance is NaN or infinite is passed through and never read as a tap (bad_pixels counts them).
+ *   rgba  : the CPU engine's finish of the filtered mean (sqrt, * 255.999, clamp, truncate, NaN -> 0, A = 255); may be NULL
+ *   mean  : optional width*height*3 doubles, the filtered mean;  var : optional width*height doubles, its variance
+ *   noise_before / noise_after : sqrt(sum of var / max(l, 0.01)^2 / pixels) of the input and of the output; noise_before is
+ *                                pt_noise_estimate's figure.  Reduced over a fixed tree: the same bits every time.
+ * cfg == NULL: 5 iterations, sigma_l 4, sigma_n 0.1, sigma_z 0.1, sigma_a 0.2.  NaN or negative sigmas, sigma_l <= 0 and iterations
+ * outside 0..6 are PT_ERR_INVALID.  Valid when pt_read_moments is -- also between two pt_steps, for previews -- and every pixel holds
+ * at least 2 samples; otherwise, and for a frame rendered with GL shading, PT_ERR_STATE.  A pure read: the sums, the counts and
+ * whatever a later pt_step or read sees stay as they are.  Runs on devices[0].
+ * Known limit: the weights are relative to each pixel's own noise, so the relative error falls while the plain, un-normalised squared
+ * error of a frame dominated by a few very bright pixels (emitters seen directly) can rise.
+ */
+typedef struct pt_atrous_config {
+    int32_t iterations;   /* 0..6; 0 = finish only */
+    int32_t reserved;
+    double sigma_l;       /* > 0: luminance, in standard deviations of the pixel's mean */
+    double sigma_n;       /* >= 0, 0 = term off: normal */
+    double sigma_z;       /* >= 0, 0 = term off: relative first-hit distance */
+    double sigma_a;       /* >= 0, 0 = term off: albedo */
+} pt_atrous_config;
+
+typedef struct pt_atrous_stats {
+    double atrous_ms;     /* device time first filter launch -> last filter launch complete (the gathers are not in it) */
+    int32_t launches;     /* prep + noise + iterations + noise + finish */
+    int32_t iterations;
+    double noise_before;
+    double noise_after;
+    uint64_t bad_pixels;
+} pt_atrous_stats;
+
+int32_t pt_set_features(pt_ctx *ctx, int32_t k);
+int32_t pt_read_features(pt_ctx *ctx, double *normal, double *albedo, double *depth);
+int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32_t stride, double *mean, double *var,
+                  pt_atrous_stats *stats);
+
+/*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the
  * environment at pt_create, the trace kernel runs a build that counts, per code
  * section, wave executions, active lanes and shader-clock cycles.  Copies up to n

@@ -116,6 +116,19 @@ class PtAdaptiveState(C.Structure):  # struct pt_adaptive_state: the block table
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PtAtrousConfig(C.Structure):  # pt_atrous_config: iterations and the four sigmas of the a-trous filter
+    _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("sigma_l", C.c_double), ("sigma_n", C.c_double),
+                ("sigma_z", C.c_double), ("sigma_a", C.c_double)]
+
+
+class PtAtrousStats(C.Structure):  # pt_atrous_stats
+    _fields_ = [("atrous_ms", C.c_double), ("launches", C.c_int32), ("iterations", C.c_int32), ("noise_before", C.c_double),
+                ("noise_after", C.c_double), ("bad_pixels", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PtShard(C.Structure):
     _fields_ = [("index", C.c_int32), ("count", C.c_int32)]
 
@@ -167,6 +180,10 @@ SYMBOLS = [
     ("pt_set_adaptive", C.c_int32, [_vp, C.POINTER(PtAdaptive)]),         # additive to ABI 4 (see has())
     ("pt_adaptive_state", C.c_int32, [_vp, C.POINTER(PtAdaptiveState)]),
     ("pt_read_sample_counts", C.c_int32, [_vp, C.POINTER(C.c_uint32)]),
+    ("pt_set_features", C.c_int32, [_vp, C.c_int32]),                     # additive to ABI 4 (see has())
+    ("pt_read_features", C.c_int32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("pt_atrous", C.c_int32, [_vp, C.POINTER(PtAtrousConfig), _vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(PtAtrousStats)]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
@@ -208,7 +225,8 @@ def load():
 
 
 ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_rays", "pt_set_moments", "pt_read_moments",
-            "pt_noise_estimate", "pt_set_adaptive", "pt_adaptive_state", "pt_read_sample_counts")  # added within ABI 4: detected by presence
+            "pt_noise_estimate", "pt_set_adaptive", "pt_adaptive_state", "pt_read_sample_counts", "pt_set_features",
+            "pt_read_features", "pt_atrous")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:

@@ -64,6 +64,8 @@ struct Core {
     decltype(&pt_noise_estimate) noise_estimate = nullptr;
     decltype(&pt_set_adaptive) set_adaptive = nullptr;  // optional, as set_shading (adaptive sampling needs both)
     int32_t (*adaptive_state)(pt_ctx *, struct pt_adaptive_state *) = nullptr;
+    decltype(&pt_set_features) set_features = nullptr;  // optional, as set_shading (the a-trous filter needs pt_atrous and moments)
+    decltype(&pt_atrous) atrous = nullptr;
     std::string error;  // sticky load error, like the reference's cached GL init failure (gpu.go:279-286)
 };
 
@@ -77,6 +79,9 @@ double g_noise_target = 0;
 int g_noise_step = 16;
 int g_adaptive = -1;  // -1: not set yet, PATHTRACER_GPU_ADAPTIVE / _MIN_SPP decide
 int g_adaptive_min_spp = 0;
+int g_atrous = -1;  // -1: not set yet, PATHTRACER_GPU_ATROUS / _ITERS decide
+int g_atrous_iters = 5;
+int g_features = -1;  // -1: not set yet, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows, else 0)
 std::mutex g_mu;  // requests are serialised, like the reference's single GL worker (gpu.go:2534-2546)
 
 std::string self_dir() {
@@ -127,6 +132,8 @@ bool load_core() {
     c.noise_estimate = reinterpret_cast<decltype(c.noise_estimate)>(dlsym(h, "pt_noise_estimate"));
     c.set_adaptive = reinterpret_cast<decltype(c.set_adaptive)>(dlsym(h, "pt_set_adaptive"));
     c.adaptive_state = reinterpret_cast<decltype(c.adaptive_state)>(dlsym(h, "pt_adaptive_state"));
+    c.set_features = reinterpret_cast<decltype(c.set_features)>(dlsym(h, "pt_set_features"));
+    c.atrous = reinterpret_cast<decltype(c.atrous)>(dlsym(h, "pt_atrous"));
     if (c.abi_version() != PT_ABI_VERSION) {
         g_core.error = "libptcore.so ABI version mismatch";
         dlclose(h);
@@ -360,6 +367,62 @@ int GetAdaptiveMinSpp() {
     return g_adaptive < 0 ? m : g_adaptive_min_spp;
 }
 
+void AtrousFromEnv(bool &on, int &iterations) {
+    on = false;
+    iterations = 5;
+    if (const char *e = std::getenv("PATHTRACER_GPU_ATROUS")) {
+        std::string v(e);
+        for (char &ch : v) ch = (char)std::tolower((unsigned char)ch);
+        on = v == "1" || v == "true" || v == "on" || v == "yes";
+    }
+    if (const char *e = std::getenv("PATHTRACER_GPU_ATROUS_ITERS")) {
+        char *end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end != e && *end == 0 && v >= 0 && v <= 6) iterations = (int)v;
+    }
+}
+
+int FeaturesFromEnv() {
+    if (const char *e = std::getenv("PATHTRACER_GPU_FEATURES")) {
+        char *end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end != e && *end == 0 && v >= 0 && v <= 0x7fffffffL) return (int)v;
+    }
+    return -1;
+}
+
+void SetAtrous(bool on, int iterations) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_atrous = on ? 1 : 0;
+    g_atrous_iters = iterations >= 0 && iterations <= 6 ? iterations : 5;
+}
+
+bool GetAtrous() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    bool on;
+    int it;
+    AtrousFromEnv(on, it);
+    return g_atrous < 0 ? on : g_atrous == 1;
+}
+
+int GetAtrousIterations() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    bool on;
+    int it;
+    AtrousFromEnv(on, it);
+    return g_atrous < 0 ? it : g_atrous_iters;
+}
+
+void SetFeatures(int k) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_features = k >= 0 ? k : -1;
+}
+
+int GetFeatures() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_features >= 0 ? g_features : FeaturesFromEnv();
+}
+
 void Shutdown() {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_ctx && g_core.handle) g_core.destroy(g_ctx);
@@ -386,8 +449,10 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         if (g_core.set_fog(g_ctx, fog_on ? &fog : nullptr) != PT_OK) return std::string("pt_set_fog: ") + g_core.last_error();
     }
     std::vector<pt_gl_material> gl_mats;
+    bool gl_model = false;
     {  // the shading model (SetShading / PATHTRACER_GPU_SHADING): the CPU engine unless GL is asked for
         const int model = g_shading < 0 ? ShadingFromEnv() : g_shading;
+        gl_model = model == PT_SHADING_GL;
         if (model == PT_SHADING_GL && !g_core.set_shading) return "GL shading: libptcore.so lacks pt_set_shading";
         if (g_core.set_shading) {
             pt_shading sh;
@@ -407,7 +472,28 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (!g_noise_set) NoiseFromEnv(noise_target, noise_step);
     const bool to_noise = noise_target > 0;
     if (to_noise && !(g_core.set_moments && g_core.noise_estimate)) return "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate";
-    if (g_core.set_moments && g_core.set_moments(g_ctx, to_noise ? 1 : 0) != PT_OK) return std::string("pt_set_moments: ") + g_core.last_error();
+    // the a-trous filter (SetAtrous / PATHTRACER_GPU_ATROUS) reads the moments, and the feature planes where the scene allows them
+    bool atrous = g_atrous == 1;
+    int atrous_iters = g_atrous_iters;
+    if (g_atrous < 0) AtrousFromEnv(atrous, atrous_iters);
+    if (atrous && !(g_core.atrous && g_core.set_moments)) return "a-trous filter: libptcore.so lacks pt_atrous / pt_set_moments";
+    int features = g_features >= 0 ? g_features : FeaturesFromEnv();
+    if (features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path), else off
+        features = 0;
+        if (atrous && !gl_model) {
+            size_t spheres = 0, boxes = 0;
+            for (const pt_object &o : flat.objects) {
+                spheres += o.type == PT_OBJ_SPHERE || o.type == PT_OBJ_SPHERE_LIGHT;
+                boxes += o.type == PT_OBJ_BOX;
+            }
+            const char *scan = std::getenv("PTCORE_SCAN");
+            const bool forced_bvh = scan && (!std::strcmp(scan, "bvh") || !std::strcmp(scan, "verify_bvh"));
+            if (spheres <= 128 && boxes <= 128 && !forced_bvh) features = 4;
+        }
+    }
+    if (features > 0 && !g_core.set_features) return "features: libptcore.so lacks pt_set_features";
+    if (g_core.set_features && g_core.set_features(g_ctx, features) != PT_OK) return std::string("pt_set_features: ") + g_core.last_error();
+    if (g_core.set_moments && g_core.set_moments(g_ctx, to_noise || atrous ? 1 : 0) != PT_OK) return std::string("pt_set_moments: ") + g_core.last_error();
     bool adaptive = g_adaptive == 1;
     int min_spp = g_adaptive_min_spp;
     if (g_adaptive < 0) AdaptiveFromEnv(adaptive, min_spp);
@@ -474,7 +560,18 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         if (g_core.end(g_ctx, &st) != PT_OK && err.empty()) err = std::string("pt_end: ") + g_core.last_error();
         if (err.empty()) progress();
     }
+    pt_atrous_stats ats;
+    std::memset(&ats, 0, sizeof ats);
+    if (atrous && err.empty()) {  // the filtered image takes the place of the plain finish (the sums stay readable after pt_end)
+        pt_atrous_config ac = {atrous_iters, 0, 4.0, 0.1, 0.1, 0.2};
+        if (g_core.atrous(g_ctx, &ac, img.Pix.data(), img.Stride, nullptr, nullptr, &ats) != PT_OK) err = std::string("pt_atrous: ") + g_core.last_error();
+    }
     if (stats && err.empty()) {
+        stats->atrous = atrous;
+        stats->features = features;
+        stats->atrous_ms = ats.atrous_ms;
+        stats->noise_before = ats.noise_before;
+        stats->noise_after = ats.noise_after;
         stats->samples = st.samples; stats->segments = st.segments; stats->exit_scans = st.exit_scans; stats->draws = st.draws;
         stats->seconds = st.seconds; stats->trace_ms = st.trace_ms; stats->resolve_ms = st.resolve_ms;
         stats->device_ms = st.device_ms; stats->num_devices = st.num_devices; stats->spp_chunk = st.spp_chunk;

@@ -39,6 +39,9 @@ struct Stats {
     bool adaptive = false;  // the frame was adaptive (SetAdaptive): spp_done is the largest count, samples the sum of the counts
     uint64_t blocks = 0, active_blocks = 0;  // pt_adaptive_state of the frame: 8x8 blocks inside it, those still above the target
     int spp_min = 0;
+    bool atrous = false;   // the image is the a-trous filtered one (SetAtrous); noise_before / noise_after are pt_atrous_stats' figures
+    int features = 0;      // feature samples per pixel the frame collected (pt_set_features)
+    double atrous_ms = 0, noise_before = 0, noise_after = 0;
 };
 
 namespace hip {
@@ -71,6 +74,17 @@ void SetAdaptive(bool on, int min_spp = 0);
 bool GetAdaptive();
 int GetAdaptiveMinSpp();
 void AdaptiveFromEnv(bool &on, int &min_spp);  // PATHTRACER_GPU_ADAPTIVE = 1 / true / on / yes, _MIN_SPP = int >= 0 (else 0)
+// The a-trous filter: Render turns moments on and, after the frame, replaces the image by pt_atrous's (the default
+// sigmas, `iterations` 0..6).  The initial value is PATHTRACER_GPU_ATROUS / PATHTRACER_GPU_ATROUS_ITERS (AtrousFromEnv).
+void SetAtrous(bool on, int iterations = 5);
+bool GetAtrous();
+int GetAtrousIterations();
+void AtrousFromEnv(bool &on, int &iterations);  // PATHTRACER_GPU_ATROUS = 1 / true / on / yes, _ITERS = int 0..6 (else 5)
+// First-hit feature planes (pt_set_features): k feature samples per pixel; k < 0 = not said (PATHTRACER_GPU_FEATURES, and without
+// it 4 under the filter where the scene allows features -- not with GL shading or on the BVH path -- else 0).
+void SetFeatures(int k);
+int GetFeatures();     // -1: not said
+int FeaturesFromEnv(); // PATHTRACER_GPU_FEATURES = int >= 0, else -1
 void Shutdown();                                    // releases the process-wide context
 }  // namespace hip
 

@@ -13,6 +13,9 @@
 // below T, checking every -noise-step samples, with -spp as the cap (also env PATHTRACER_GPU_NOISE, PATHTRACER_GPU_NOISE_STEP).
 // -adaptive makes T the target of every 8x8 block (pt_set_adaptive): blocks stop one by one, each pixel keeps the
 // samples its block got; -min-spp N samples every block at least N times first (also env PATHTRACER_GPU_ADAPTIVE, _MIN_SPP).
+// -atrous writes the variance-guided a-trous filtered image (pt_atrous) instead of the plain finish, -atrous-iters N
+// (0..6) sets its iterations and -features K the first-hit feature samples per pixel that guide it (default: 4 where the scene allows
+// them; also env PATHTRACER_GPU_ATROUS, PATHTRACER_GPU_ATROUS_ITERS, PATHTRACER_GPU_FEATURES).
 #include <cerrno>
 #include <chrono>
 #include <cstdarg>
@@ -59,14 +62,21 @@ struct Flags {
     int noise_step = 16;
     bool adaptive = false;
     int min_spp = 0;
+    bool atrous = false;
+    int atrous_iters = 5;
+    int features = -1;  // -1: not said
 };
 
 void usage() {
     std::fprintf(stderr,
                  "Usage of render:\n"
                  "  -adaptive\n    \twith -noise: stop every 8x8 block at the target by itself (default false, or PATHTRACER_GPU_ADAPTIVE)\n"
+                 "  -atrous\n    \twrite the variance-guided a-trous filtered image (DESIGN 3.11) (default false, or PATHTRACER_GPU_ATROUS)\n"
+                 "  -atrous-iters int\n    \twith -atrous: iterations 0..6 (default 5, or PATHTRACER_GPU_ATROUS_ITERS)\n"
                  "  -depth int\n    \tmax path depth (default: the mode preset)\n"
                  "  -devices int\n    \tnumber of GPUs to tile the image over (default 1)\n"
+                 "  -features int\n    \tfirst-hit feature samples per pixel (default: 4 with -atrous where the scene allows them, else 0; or\n"
+                 "    \tPATHTRACER_GPU_FEATURES)\n"
                  "  -fog\n    \tdraw the scene's fog block like the reference's GPU backend (default false, or PATHTRACER_GPU_FOG)\n"
                  "  -gpu\n    \tuse GPU backend for rendering (if available)\n"
                  "  -headless\n    \trender without UI and save PNG\n"
@@ -107,17 +117,17 @@ int parse(int argc, char **argv, Flags &f) {
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         if (name == "h" || name == "help") { usage(); return 0; }
-        if (name == "gpu" || name == "headless" || name == "scene-settings" || name == "fog" || name == "adaptive") {
+        if (name == "gpu" || name == "headless" || name == "scene-settings" || name == "fog" || name == "adaptive" || name == "atrous") {
             bool b = true;
             if (has_val && !parse_bool(val, b)) {
                 std::fprintf(stderr, "invalid boolean value \"%s\" for -%s: parse error\n", val.c_str(), name.c_str());
                 usage();
                 return 2;
             }
-            (name == "gpu" ? f.gpu : name == "headless" ? f.headless : name == "fog" ? f.fog : name == "adaptive" ? f.adaptive : f.scene_settings) = b;
+            (name == "gpu" ? f.gpu : name == "headless" ? f.headless : name == "fog" ? f.fog : name == "adaptive" ? f.adaptive : name == "atrous" ? f.atrous : f.scene_settings) = b;
             continue;
         }
-        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading", "noise", "noise-step", "min-spp"};
+        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading", "noise", "noise-step", "min-spp", "atrous-iters", "features"};
         bool ok = false;
         for (const char *k : known) ok = ok || name == k;
         if (!ok) {
@@ -171,6 +181,8 @@ int parse(int argc, char **argv, Flags &f) {
             else if (name == "devices") f.devices = (int)n;
             else if (name == "noise-step") f.noise_step = n >= 1 && n <= 0x7fffffffLL ? (int)n : 16;
             else if (name == "min-spp") f.min_spp = n >= 0 && n <= 0x7fffffffLL ? (int)n : 0;
+            else if (name == "atrous-iters") f.atrous_iters = n >= 0 && n <= 6 ? (int)n : 5;
+            else if (name == "features") f.features = n >= 0 && n <= 0x7fffffffLL ? (int)n : -1;
             else f.seed = (unsigned long long)n;
         }
     }
@@ -196,6 +208,8 @@ int render_headless(const Flags &f) {
     engine::hip::SetShading(f.shading == "gl" ? PT_SHADING_GL : PT_SHADING_CPU);
     engine::hip::SetNoiseTarget(f.noise, f.noise_step);
     engine::hip::SetAdaptive(f.adaptive, f.min_spp);
+    engine::hip::SetAtrous(f.atrous, f.atrous_iters);
+    engine::hip::SetFeatures(f.features);
     if (f.adaptive && !(f.noise > 0)) logf("adaptive: no -noise target given, nothing to adapt to (a plain frame)");
     if (f.shading == "gl") logf("shading: gl (the reference's GPU shader; spp counts passes of 16 paths)");
     if (f.fog) logf("fog: drawing the scene's fog block (%s)", sc->FogPtr ? "present" : "absent: nothing to draw");
@@ -225,6 +239,9 @@ int render_headless(const Flags &f) {
         else
             logf("rendered %dx%d, %d spp, depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, %.1f M samples/s", cfg.Width,
                  cfg.Height, cfg.SamplesPerPx, cfg.MaxDepth, st.num_devices, dt, st.segments / dt / 1e6, st.samples / dt / 1e6);
+        if (st.atrous)
+            logf("a-trous filter: %d iterations, %d feature samples per pixel, noise %.6g -> %.6g in %.3f ms", f.atrous_iters, st.features,
+                 st.noise_before, st.noise_after, st.atrous_ms);
         engine::SavePNG(f.out, img);
     } catch (const std::exception &e) {
         logf("headless render error: %s", e.what());
@@ -245,6 +262,8 @@ int main(int argc, char **argv) {
     f.shading = engine::hip::ShadingFromEnv() == PT_SHADING_GL ? "gl" : "cpu";
     engine::hip::NoiseFromEnv(f.noise, f.noise_step);
     engine::hip::AdaptiveFromEnv(f.adaptive, f.min_spp);
+    engine::hip::AtrousFromEnv(f.atrous, f.atrous_iters);
+    f.features = engine::hip::FeaturesFromEnv();
     int rc = parse(argc, argv, f);
     if (rc >= 0) return rc;
     logf("flags: scene=%s mode=%s headless=%s out=%s", f.scene.c_str(), f.mode.c_str(), f.headless ? "true" : "false",

@@ -1,0 +1,218 @@
+// pt_atrous.h -- first-hit feature planes (pt_set_features) and the variance-guided a-trous filter (pt_atrous), host + device.
+//
+// Opt-in per context; with both off nothing here is allocated or launched.  Everything is PT_HD and built from IEEE +,-,*,/, sqrt
+// and the Go routines of pt_math.h (compile with -ffp-contract=off), so the gfx950 kernels (feature_kernel, atrous_prep_kernel,
+// atrous_kernel, atrous_finish_kernel in pt_kernels.h) and a host build of this header give the same bits.  This comment is the
+// specification tests/atrous_reference.c restates.  Every sum below is written in its order of evaluation: a + b + c means (a + b) + c.
+//
+// FEATURES.  Per pixel, over its samples with index s < k, the first hit of the sample's primary ray (o, d): the CPU engine's closest
+// hit of the first segment -- exact FP64 tests, tMin 0.001, tMax = the closest t so far, objects in file order (ptf::closest_hit).
+// Three sums of three doubles, added in sample order from zero:
+//   normal += the hit record's face-forward normal (objects.go:17-24, :37-222): n_out if d . n_out < 0, else -n_out, with
+//             sphere  p = o + d*t per component, n_out = (p - centre) * (1 / radius)
+//             plane   n_out = the plane's normal, front face when denom = normal . d < 0
+//             box     p = o + d*t; of dxMin = p.x - min.x, dxMax = max.x - p.x, dyMin, dyMax, dzMin, dzMax the first strictly smallest
+//                     names the axis normal (-1,0,0), (1,0,0), (0,-1,0), ...
+//   albedo += the converted material's albedo (materials.go:28-55; emissive and missing materials: 0)
+//   depth  += (t * sqrt(d.x*d.x + d.y*d.y + d.z*d.z), 1, 0) on a hit, and depth[2] += 1 for every feature sample taken
+// A miss adds nothing to normal, albedo, depth[0] and depth[1].
+//
+// FILTER.  Inputs per in-frame pixel: its sample count n >= 2, the raw sums S (radiance) and Q (squared radiance) per channel, and --
+// when the frame has features -- the sums above.  Configuration: T iterations (0..6), sigma_l > 0, sigma_n, sigma_z, sigma_a >= 0; a
+// feature term is ON when its sigma is > 0 and the frame has features.
+//   Prep:  c_k = S_k / n;  m_k = Q_k / n - c_k * c_k, a negative m_k counts as 0 (a NaN stays);  v_k = m_k / (n - 1);
+//          var = (v_r + v_g + v_b) / 3.   The pixel is BAD when some c_k or var is NaN or infinite.
+//          With h = depth[1] (samples that hit): N = normal / h, A = albedo / h, z = depth[0] / h, per component; all 0 when h = 0
+//          or the frame has no features.  N is not renormalised.
+//   Iteration t = 0 .. T-1, step = 2^t, from (c, var) to (c', var'), all pixels at once (ping-pong):
+//          a bad pixel keeps its c and var.  A good pixel i = (x, y) visits its 25 taps j = (x + dx*step, y + dy*step), dy outer and
+//          dx inner, both from -2 to 2; a tap outside the frame or on a bad pixel is skipped.  With l = (c_r + c_g + c_b) / 3,
+//          B = [1/16, 1/4, 3/8, 1/4, 1/16]:
+//              pen = |l_i - l_j| / (sigma_l * sqrt(var_i) + 1e-8)
+//              if N on:  pen = pen + pos(1 - (N_i.x*N_j.x + N_i.y*N_j.y + N_i.z*N_j.z)) / sigma_n       pos(v) = v > 0 ? v : 0
+//              if z on:  pen = pen + |z_i - z_j| / (sigma_z * (z_i > 1e-8 ? z_i : 1e-8))
+//              if A on:  pen = pen + (dr*dr + dg*dg + db*db) / (sigma_a * sigma_a),  (dr, dg, db) = A_i - A_j
+//              w = (B[dy+2] * B[dx+2]) * go_exp(-pen);  a tap whose pen is > 745.2 has w = 0 (go_exp returns exactly 0 below
+//                  -745.133..., so skipping the call and the tap gives the same bits: every c_j and var_j of a tap is finite)
+//              sw = sw + w;  sd_k = sd_k + w * (c_j,k - c_i,k);  sv = sv + (w * w) * var_j           (all from 0)
+//          c'_k = c_i,k + sd_k / sw;  var' = sv / (sw * sw).   The centre tap has pen = 0 and w = 9/64, so sw > 0.  (The weighted
+//          mean sum(w c_j) / sum(w), taken about c_i: a constant image with zero variance is unchanged bit for bit.)
+//   Finish: byte_k = quantise(sqrt(c_k) * 255.999) -- the CPU engine's finish (renderer.go:190-221) of c as a 1-sample sum: below 0
+//          -> 0, above 255.999 -> 255.999, NaN -> 0, truncate; A = 255.
+//   Noise figure of a state (c, var): sqrt(sum over the pixels of e2 / pixels), e2 = var / den^2, den = l < 0.01 ? 0.01 : l; a NaN or
+//          infinite e2 adds 0.  Before the first iteration this is pt_noise_estimate's figure.  (The order of that one sum is the
+//          reduction tree's, not specified here: compare to 1e-9.)
+#pragma once
+
+#include <stdint.h>
+
+#include "pt_device.h"
+#include "pt_fog.h"
+#include "pt_math.h"
+
+namespace pta {
+
+#define PTA_MAX_ITERATIONS 6
+#define PTA_PEN_CUT 745.2  // go_exp(-pen) == 0 for every pen above this
+
+// ---------------------------------------------------------------- features
+
+// The first hit of the primary ray (o, d) against the world: false on a miss; n = the face-forward normal, a = the albedo of the
+// hit object's converted material, dist = t * |d|.
+PT_HD bool first_hit(const ptd::DevObj *objs, const ptd::DevMat *mats, int32_t nobj, const double o[3], const double d[3], double n[3],
+                     double a[3], double &dist) {
+    const ptf::FRay r = ptf::make_fray(o[0], o[1], o[2], d[0], d[1], d[2]);
+    double t;
+    int32_t best;
+    if (!ptf::closest_hit(objs, nobj, r, t, best)) return false;
+    const ptd::DevObj &ob = objs[best];
+    const int kind = ob.kind & 0xff;
+    double nx, ny, nz;
+    bool front;
+    if (kind == ptd::KIND_SPHERE) {
+        const double px = o[0] + d[0] * t, py = o[1] + d[1] * t, pz = o[2] + d[2] * t;
+        nx = (px - ob.a[0]) * ob.inv_radius;
+        ny = (py - ob.a[1]) * ob.inv_radius;
+        nz = (pz - ob.a[2]) * ob.inv_radius;
+        front = d[0] * nx + d[1] * ny + d[2] * nz < 0;
+    } else if (kind == ptd::KIND_PLANE) {
+        nx = ob.b[0]; ny = ob.b[1]; nz = ob.b[2];
+        front = ob.b[0] * d[0] + ob.b[1] * d[1] + ob.b[2] * d[2] < 0;
+    } else {
+        const double px = o[0] + d[0] * t, py = o[1] + d[1] * t, pz = o[2] + d[2] * t;
+        double m = px - ob.a[0];
+        nx = -1; ny = 0; nz = 0;
+        double v = ob.b[0] - px;
+        if (v < m) { m = v; nx = 1; ny = 0; nz = 0; }
+        v = py - ob.a[1];
+        if (v < m) { m = v; nx = 0; ny = -1; nz = 0; }
+        v = ob.b[1] - py;
+        if (v < m) { m = v; nx = 0; ny = 1; nz = 0; }
+        v = pz - ob.a[2];
+        if (v < m) { m = v; nx = 0; ny = 0; nz = -1; }
+        v = ob.b[2] - pz;
+        if (v < m) { nx = 0; ny = 0; nz = 1; }
+        front = d[0] * nx + d[1] * ny + d[2] * nz < 0;
+    }
+    n[0] = front ? nx : -nx;
+    n[1] = front ? ny : -ny;
+    n[2] = front ? nz : -nz;
+    const ptd::DevMat &mt = mats[ob.mat];
+    a[0] = mt.albedo[0]; a[1] = mt.albedo[1]; a[2] = mt.albedo[2];
+    dist = t * ptm::f_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    return true;
+}
+
+// ---------------------------------------------------------------- filter
+
+struct Params {
+    double sigma_l, sigma_n, sigma_z, sigma_a;
+    int32_t iterations;
+    int32_t n_on, z_on, a_on;  // the feature terms that are on (sigma > 0 and the frame has features)
+};
+
+// Guide record of a pixel, read-only through the iterations: N, A, z and the bad flag (as a double: 0 good, 1 bad).
+struct Guide {
+    double n[3], a[3], z, bad;
+};
+
+PT_HD bool finite(double x) { return x - x == 0.0; }
+
+// Prep of one pixel: S, Q raw sums, cnt samples (>= 2); fn / fa / fd the feature sums or null.
+PT_HD void prep_pixel(const double S[3], const double Q[3], uint32_t cnt, const double *fn, const double *fa, const double *fd,
+                      double c[3], double &var, Guide &g) {
+    const double n = (double)cnt, n1 = (double)(cnt - 1u);
+    double vsum = 0.0;
+    bool ok = true;
+    for (int k = 0; k < 3; k++) {
+        c[k] = S[k] / n;
+        double m = Q[k] / n - c[k] * c[k];
+        if (m < 0.0) m = 0.0;  // (a NaN stays a NaN)
+        vsum += m / n1;
+        ok = ok && finite(c[k]);
+    }
+    var = vsum / 3.0;
+    ok = ok && finite(var);
+    g.bad = ok ? 0.0 : 1.0;
+    const double h = fd ? fd[1] : 0.0;
+    if (h != 0.0) {
+        for (int k = 0; k < 3; k++) { g.n[k] = fn[k] / h; g.a[k] = fa[k] / h; }
+        g.z = fd[0] / h;
+    } else {
+        for (int k = 0; k < 3; k++) g.n[k] = g.a[k] = 0.0;
+        g.z = 0.0;
+    }
+}
+
+// One iteration at pixel (x, y) of a W x H frame: col [W*H][3], var [W*H], guide [W*H] -> the pixel's c', var'.
+PT_HD void filter_pixel(const Params &P, int32_t W, int32_t H, int32_t x, int32_t y, int32_t step, const double *__restrict__ col,
+                        const double *__restrict__ var, const Guide *__restrict__ guide, double co[3], double &vo) {
+    const size_t i = (size_t)y * (size_t)W + (size_t)x;
+    const Guide gi = guide[i];
+    const double ci0 = col[3 * i], ci1 = col[3 * i + 1], ci2 = col[3 * i + 2], vi = var[i];
+    if (gi.bad != 0.0) {
+        co[0] = ci0; co[1] = ci1; co[2] = ci2;
+        vo = vi;
+        return;
+    }
+    const double li = (ci0 + ci1 + ci2) / 3.0;
+    const double den_l = P.sigma_l * ptm::f_sqrt(vi) + 1e-8;
+    const double den_z = P.sigma_z * (gi.z > 1e-8 ? gi.z : 1e-8);
+    const double den_a = P.sigma_a * P.sigma_a;
+    const double B[5] = {0.0625, 0.25, 0.375, 0.25, 0.0625};
+    double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, sv = 0.0;
+    for (int dy = -2; dy <= 2; dy++) {
+        const int32_t yj = y + dy * step;
+        if (yj < 0 || yj >= H) continue;
+        for (int dx = -2; dx <= 2; dx++) {
+            const int32_t xj = x + dx * step;
+            if (xj < 0 || xj >= W) continue;
+            const size_t j = (size_t)yj * (size_t)W + (size_t)xj;
+            const Guide &gj = guide[j];
+            if (gj.bad != 0.0) continue;
+            const double cj0 = col[3 * j], cj1 = col[3 * j + 1], cj2 = col[3 * j + 2];
+            const double lj = (cj0 + cj1 + cj2) / 3.0;
+            double pen = ptm::f_abs(li - lj) / den_l;
+            if (P.n_on) {
+                const double q = 1.0 - (gi.n[0] * gj.n[0] + gi.n[1] * gj.n[1] + gi.n[2] * gj.n[2]);
+                pen = pen + (q > 0.0 ? q : 0.0) / P.sigma_n;
+            }
+            if (P.z_on) pen = pen + ptm::f_abs(gi.z - gj.z) / den_z;
+            if (P.a_on) {
+                const double dr = gi.a[0] - gj.a[0], dg = gi.a[1] - gj.a[1], db = gi.a[2] - gj.a[2];
+                pen = pen + (dr * dr + dg * dg + db * db) / den_a;
+            }
+            if (pen > PTA_PEN_CUT) continue;  // w = 0 exactly: adds nothing
+            const double w = (B[dy + 2] * B[dx + 2]) * ptm::go_exp(-pen);
+            sw = sw + w;
+            s0 = s0 + w * (cj0 - ci0);
+            s1 = s1 + w * (cj1 - ci1);
+            s2 = s2 + w * (cj2 - ci2);
+            sv = sv + (w * w) * var[j];
+        }
+    }
+    co[0] = ci0 + s0 / sw;
+    co[1] = ci1 + s1 / sw;
+    co[2] = ci2 + s2 / sw;
+    vo = sv / (sw * sw);
+}
+
+// The finish of one channel: the byte of the CPU engine for a mean c.
+PT_HD uint32_t finish_byte(double c) {
+    double v = ptm::f_sqrt(c) * 255.999;
+    if (v < 0) v = 0;
+    else if (v > 255.999) v = 255.999;
+    if (v != v) return 0;
+    return (uint32_t)v;
+}
+PT_HD uint32_t finish_pack(const double c[3]) { return finish_byte(c[0]) | (finish_byte(c[1]) << 8) | (finish_byte(c[2]) << 16) | (255u << 24); }
+
+// The noise term of one pixel; a NaN or infinite one is returned as 0.
+PT_HD double noise_term(const double c[3], double var) {
+    double den = (c[0] + c[1] + c[2]) / 3.0;
+    if (den < 0.01) den = 0.01;
+    const double e2 = var / (den * den);
+    return finite(e2) ? e2 : 0.0;
+}
+
+}  // namespace pta

@@ -247,19 +247,23 @@ PT_HD bool hit_object(const ptd::DevObj &o, const FRay &r, double tmin, double t
     return true;
 }
 
-// The CPU engine's closest hit of the first segment (renderer.go:297-302): t, or false when nothing is hit.
-PT_HD bool closest_hit(const ptd::DevObj *objs, int32_t nobj, const FRay &r, double &t_hit) {
+// The CPU engine's closest hit of the first segment (renderer.go:297-302): t and the object hit, or false when nothing is hit.
+PT_HD bool closest_hit(const ptd::DevObj *objs, int32_t nobj, const FRay &r, double &t_hit, int32_t &best) {
     double closest = ptm::max_float64();
-    bool any = false;
+    best = -1;
     for (int32_t i = 0; i < nobj; i++) {
         double t;
         if (hit_object(objs[i], r, 0.001, closest, t)) {
-            any = true;
+            best = i;
             closest = t;
         }
     }
     t_hit = closest;
-    return any;
+    return best >= 0;
+}
+PT_HD bool closest_hit(const ptd::DevObj *objs, int32_t nobj, const FRay &r, double &t_hit) {
+    int32_t best;
+    return closest_hit(objs, nobj, r, t_hit, best);
 }
 
 // Does any object hit the shadow ray in [0.001, tmax]?  On the device the object loop is left when no active lane is still

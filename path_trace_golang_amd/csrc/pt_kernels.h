@@ -43,6 +43,10 @@
 //                   kernels for the frame.  resolve_kernel then finishes with GL's tone map (gl_spp).
 //   fog_kernel      opt-in (pt_set_fog): the fog's in-scatter term of every job (pt_fog.h), added into its radiance record
 //                   between a chunk's last trace pass and resolve_kernel.
+//   feature_kernel  opt-in (pt_set_features): per pixel slot the running sums of the first-hit normal, albedo and distance of
+//                   the chunk's samples with index below k (pt_atrous.h), beside fog_kernel.
+//   atrous_prep_kernel / atrous_kernel / atrous_noise_kernel / atrous_finish_kernel   pt_atrous: the variance-guided a-trous
+//                   filter of pt_atrous.h over the gathered row-major planes on devices[0].
 //
 // FP64 throughout; built with -ffp-contract=off so every product and sum rounds
 // exactly as the reference's Go code does on amd64.
@@ -51,6 +55,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_device.h"
+#include "pt_atrous.h"
 #include "pt_fog.h"
 #include "pt_glshade.h"
 #include "pt_math.h"
@@ -3286,6 +3291,109 @@ __global__ __launch_bounds__(PT_BLOCK) void post_smooth_kernel(const uint8_t *__
     reinterpret_cast<uint32_t *>(dst)[i] = out;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// pt_atrous: the variance-guided a-trous filter (the model and its evaluation order: pt_atrous.h), over row-major planes of the whole
+// frame on devices[0].  One thread per pixel everywhere.  The colour (24 B) and variance (8 B) planes ping-pong between two buffers;
+// the guide record (64 B) is written once by the prep kernel and only read afterwards.  No atomics: the noise figure goes over
+// noise_kernel's tree (xor butterfly per wave, the four waves in order, the blocks in order on the host).
+struct AtrousPrepArgs {
+    const double *acc;       // [npix][3] raw sums S
+    const double *m2;        // [npix][3] raw sums Q
+    const uint32_t *cnt;     // [npix] the pixel's own count (adaptive frames) or null: n
+    const double *fn, *fa, *fd;  // [npix][3] feature sums, or null (no features)
+    double *col;             // [npix][3]
+    double *var;             // [npix]
+    pta::Guide *guide;       // [npix]
+    uint32_t npix, n;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void atrous_prep_kernel(const AtrousPrepArgs A) {
+    const uint32_t i = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (i >= A.npix) return;
+    const size_t i3 = 3 * (size_t)i;
+    const double S[3] = {A.acc[i3], A.acc[i3 + 1], A.acc[i3 + 2]};
+    const double Q[3] = {A.m2[i3], A.m2[i3 + 1], A.m2[i3 + 2]};
+    double c[3], var;
+    pta::Guide g;
+    pta::prep_pixel(S, Q, A.cnt ? A.cnt[i] : A.n, A.fn ? A.fn + i3 : nullptr, A.fa ? A.fa + i3 : nullptr, A.fd ? A.fd + i3 : nullptr, c, var, g);
+    A.col[i3] = c[0];
+    A.col[i3 + 1] = c[1];
+    A.col[i3 + 2] = c[2];
+    A.var[i] = var;
+    A.guide[i] = g;
+}
+
+struct AtrousArgs {
+    pta::Params P;
+    const double *col, *var;   // the iteration's input
+    const pta::Guide *guide;
+    double *col_out, *var_out;
+    int32_t W, H, step;
+};
+
+// One iteration: a block is 32 x 8 pixels (a wave = two rows of 32), so the taps of a wave's lanes at step 1 and 2 fall into the same
+// few rows of the planes.
+__global__ __launch_bounds__(PT_BLOCK) void atrous_kernel(const AtrousArgs A) {
+    const int32_t x = (int32_t)(blockIdx.x * 32u + (threadIdx.x & 31u));
+    const int32_t y = (int32_t)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    if (x >= A.W || y >= A.H) return;
+    double c[3], v;
+    pta::filter_pixel(A.P, A.W, A.H, x, y, A.step, A.col, A.var, A.guide, c, v);
+    const size_t i = (size_t)y * (size_t)A.W + (size_t)x;
+    A.col_out[3 * i] = c[0];
+    A.col_out[3 * i + 1] = c[1];
+    A.col_out[3 * i + 2] = c[2];
+    A.var_out[i] = v;
+}
+
+// The noise figure's partial sums of a state (col, var): NoisePartial.sum = the block's sum of e2, .max its largest e2, .bad its bad pixels.
+__global__ __launch_bounds__(PT_BLOCK) void atrous_noise_kernel(const double *__restrict__ col, const double *__restrict__ var, const pta::Guide *__restrict__ guide,
+                                                                  NoisePartial *__restrict__ partial, uint32_t npix) {
+    __shared__ double s_sum[PT_BLOCK / PT_WAVE], s_max[PT_BLOCK / PT_WAVE];
+    __shared__ uint32_t s_bad[PT_BLOCK / PT_WAVE];
+    const uint32_t i = blockIdx.x * PT_BLOCK + threadIdx.x;
+    double e2 = 0.0;
+    uint32_t bad = 0;
+    if (i < npix) {
+        const double c[3] = {col[3 * (size_t)i], col[3 * (size_t)i + 1], col[3 * (size_t)i + 2]};
+        e2 = pta::noise_term(c, var[i]);
+        bad = guide[i].bad != 0.0 ? 1u : 0u;
+    }
+    double sum = e2, mx = e2;
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off, 64);
+        const double o = __shfl_xor(mx, off, 64);
+        mx = o > mx ? o : mx;
+        bad += __shfl_xor(bad, off, 64);
+    }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) {
+        s_sum[wave] = sum;
+        s_max[wave] = mx;
+        s_bad[wave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        NoisePartial r;
+        r.sum = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+        r.max = s_max[0];
+        r.bad = s_bad[0];
+        for (int w = 1; w < PT_BLOCK / PT_WAVE; w++) {
+            r.max = s_max[w] > r.max ? s_max[w] : r.max;
+            r.bad += s_bad[w];
+        }
+        partial[blockIdx.x] = r;
+    }
+}
+
+// The filtered mean as the 8-bit image: W * 4 bytes per row.
+__global__ __launch_bounds__(PT_BLOCK) void atrous_finish_kernel(const double *__restrict__ col, uint8_t *__restrict__ rgba, uint32_t npix) {
+    const uint32_t i = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (i >= npix) return;
+    const double c[3] = {col[3 * (size_t)i], col[3 * (size_t)i + 1], col[3 * (size_t)i + 2]};
+    reinterpret_cast<uint32_t *>(rgba)[i] = pta::finish_pack(c);
+}
+
 // The fog's in-scatter term (pt_fog.h) of every job of a chunk, added in place to the job's radiance record after the chunk's
 // last trace pass and before resolve_kernel: L = L_path + L_fog, one add per channel, path first.  One lane per job; the
 // primary ray is read back from the ray-generation buffers, which no trace form writes.  Every loop of the term -- the 24
@@ -3342,6 +3450,63 @@ __device__ __forceinline__ void fog_body(const FogArgs &A, const uint32_t *__res
 __global__ __launch_bounds__(PT_BLOCK) void fog_kernel(const FogArgs A) { fog_body<false>(A, nullptr); }
 
 __global__ __launch_bounds__(PT_BLOCK) void fog_adaptive_kernel(const FogArgs A, const uint32_t *__restrict__ active) { fog_body<true>(A, active); }
+
+// First-hit feature sums (pt_set_features, pt_atrous.h): per accumulation slot nine running sums -- normal, albedo and (distance, samples
+// that hit, feature samples taken) -- over the slot's samples with global index below k.  One lane per slot, as resolve_kernel: a wave is
+// one 8x8 block, whose primary rays are coherent, and walks the chunk's first `take` = min(S, k - s0) samples in order, reading the rays
+// back from the ray-generation planes as fog_kernel does (so after the injected-ray overwrite).  The object loop has a wave-uniform trip
+// count: the objects come in by scalar loads.  No atomics.  (ADAPT: the slots of the active blocks through the block table; a block that
+// stopped at n < k keeps the n feature samples it holds.)
+struct FeatureArgs {
+    const DevObj *objs;
+    const DevMat *mats;
+    const double *ray;                // [6][njobs]
+    const uint16_t *ray_ndraw;        // 0xffff: pixel outside the frame
+    double *feat;                     // [9][nslots]
+    int32_t nobj;
+    int32_t first;                    // 1: the running sums start at zero
+    uint32_t nslots, njobs, S, take;
+};
+
+template <bool ADAPT>
+__device__ __forceinline__ void feature_body(const FeatureArgs &A, const AdaptTable &T) {
+    uint32_t slot, cblk;
+    if (!chunk_slot<ADAPT>(1, T, A.nslots, slot, cblk)) return;
+    const uint32_t p = slot & 63u;
+    const size_t base = (size_t)cblk * A.S * 64u + p;
+    if (A.ray_ndraw[base] == 0xffffu) return;  // outside the frame (the same for every sample of the slot)
+    double f[9];
+    for (uint32_t q = 0; q < 9u; q++) f[q] = A.first ? 0.0 : A.feat[q * (size_t)A.nslots + slot];
+    const size_t nj = A.njobs;
+    for (uint32_t s = 0; s < A.take; s++) {
+        const size_t job = base + (size_t)s * 64u;
+        const double o[3] = {A.ray[job], A.ray[nj + job], A.ray[2 * nj + job]};
+        const double d[3] = {A.ray[3 * nj + job], A.ray[4 * nj + job], A.ray[5 * nj + job]};
+        double n[3], a[3], dist;
+        if (pta::first_hit(A.objs, A.mats, A.nobj, o, d, n, a, dist)) {
+            f[0] += n[0]; f[1] += n[1]; f[2] += n[2];
+            f[3] += a[0]; f[4] += a[1]; f[5] += a[2];
+            f[6] += dist;
+            f[7] += 1.0;
+        }
+        f[8] += 1.0;
+    }
+    for (uint32_t q = 0; q < 9u; q++) A.feat[q * (size_t)A.nslots + slot] = f[q];
+}
+
+__global__ __launch_bounds__(PT_BLOCK) void feature_kernel(const FeatureArgs A) { feature_body<false>(A, AdaptTable{nullptr, nullptr, 0u}); }
+
+__global__ __launch_bounds__(PT_BLOCK) void feature_adaptive_kernel(const FeatureArgs A, const AdaptTable T) { feature_body<true>(A, T); }
+
+// One of the three feature planes (which = 0 normal, 1 albedo, 2 depth) tile-major with zeros outside the frame, the layout of
+// tiles_accum, for untile_kernel.
+__global__ __launch_bounds__(PT_BLOCK) void feature_tiles_kernel(const double *__restrict__ feat, double *__restrict__ tiles, uint32_t nslots, uint32_t which,
+                                                                   const TileGeom G) {
+    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (slot >= nslots) return;
+    const Pixel px = slot_pixel(G, slot);
+    for (uint32_t c = 0; c < 3u; c++) tiles[3 * px.pix + c] = px.inside ? feat[(3u * which + c) * (size_t)nslots + slot] : 0.0;
+}
 
 // One GL-shading pass per job (pt_glshade.h): pixel (x, y) of the job as in raygen_kernel, pass s0 + sample, the 16 strata
 // traced in k order by this lane and their sum written into the job's radiance record, which resolve_kernel adds in pass

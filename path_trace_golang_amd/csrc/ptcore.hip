@@ -130,7 +130,7 @@ struct EventList {
     }
     void swap(EventList &o) { v.swap(o.v); std::swap(n, o.n); }
 };
-enum EventKind { EV_TRACE, EV_RESOLVE, EV_RAYGEN, EV_GLASS, EV_FOG, EV_MOMENTS, EV_CHECK, EV_KINDS };
+enum EventKind { EV_TRACE, EV_RESOLVE, EV_RAYGEN, EV_GLASS, EV_FOG, EV_MOMENTS, EV_CHECK, EV_FEATURE, EV_KINDS };
 
 // Storage of one path-state queue (PathQueue, pt_device.h): per entry 10 doubles, the stream state and 4 words -- job, depth, hit
 // object, answer -- or 6 with pixel stats (+ the job's two counters); every plane of `u` is as long as the queue.
@@ -186,6 +186,8 @@ struct Device {
     DevBuf<double> m2;                // pt_set_moments: [3][nslots] running sums of squares (allocated only then)
     DevBuf<double> tiles_m2;          // ... and their tile-major copy for the gather
     DevBuf<ptk::NoisePartial> noise_part;  // pt_noise_estimate: one partial per block of noise_kernel
+    DevBuf<double> feat;              // pt_set_features: [9][nslots] running first-hit feature sums (allocated only then)
+    DevBuf<double> tiles_feat;        // ... and the tile-major copy of one plane of them for the gather
     // pt_set_adaptive (allocated only then): the active list (two buffers, the check compacts from one into the other), the
     // samples per block, the check's per-block decision and noise, and the word the host reads back after every check
     DevBuf<uint32_t> act[2], blk_spp, blk_keep;
@@ -258,6 +260,7 @@ struct Frame {
     bool moments = false;  // pt_set_moments: moments_kernel runs after every chunk's resolve add (pt_begin / pt_render frames only)
     bool adaptive = false; // pt_set_adaptive: the frame's jobs are those of the active blocks, a check ends every pt_step (implies moments)
     pt_adaptive ad{};
+    int32_t features = 0;  // pt_set_features: feature_kernel runs after the chunks that hold samples below this index (pt_begin / pt_render frames only)
     double worst_active = 0.0;  // largest block noise among the blocks the last check kept
     std::vector<ptg::GlObj> gl_objs;
     std::vector<ptg::GlMat> gl_mats;
@@ -310,6 +313,12 @@ struct pt_ctx {
     DevBuf<double> g_tiles_m2, f_m2;  // pt_read_moments: the gathered tiles and the row-major frame of the second moments
     bool moments_on = false;          // pt_set_moments
     bool adaptive_on = false;         // pt_set_adaptive
+    int32_t features_k = 0;           // pt_set_features: feature samples per pixel (0 = off)
+    DevBuf<double> g_tiles_feat, f_feat_n, f_feat_a, f_feat_d;  // pt_read_features / pt_atrous: one gathered plane, the three row-major frames
+    // pt_atrous (allocated on the first call): colour and variance ping-pong, the guide records, the noise partials
+    DevBuf<double> at_col[2], at_var[2];
+    DevBuf<pta::Guide> at_guide;
+    DevBuf<ptk::NoisePartial> at_part;
     pt_adaptive adaptive{};
     DevBuf<uint32_t> f_seg, f_draw;
     size_t l_budget_bytes = (size_t)48 << 30;  // per-chunk job buffers (radiance, primary rays, path-state queues): a sixth of the 288 GB
@@ -1343,6 +1352,29 @@ int32_t step_fog(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G, c
     });
 }
 
+// The first-hit features of the chunk's samples with index below k into their running sums (pt_set_features)
+int32_t step_features(pt_ctx *ctx, Device &d, const DevFrame &F, const ptk::AdaptTable &AT) {
+    const Frame &fr = ctx->frame;
+    ptk::FeatureArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.objs = d.objs.p;
+    A.mats = d.mats.p;
+    A.ray = d.ray.p;
+    A.ray_ndraw = d.ray_ndraw.p;
+    A.feat = d.feat.p;
+    A.nobj = fr.nobj;
+    A.first = F.s0 == 0 ? 1 : 0;
+    A.nslots = d.nslots;
+    A.njobs = F.njobs;
+    A.S = F.S;
+    A.take = std::min(F.S, (uint32_t)fr.features - F.s0);
+    const uint32_t grid = ((fr.adaptive ? d.nact * 64u : d.nslots) + PT_BLOCK - 1) / PT_BLOCK;
+    return timed(d, EV_FEATURE, [&] {
+        if (fr.adaptive) hipLaunchKernelGGL(ptk::feature_adaptive_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A, AT);
+        else hipLaunchKernelGGL(ptk::feature_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A);
+    });
+}
+
 // The chunk's radiance records into the running sums (resolve_kernel), and their squares, in the same order (pt_set_moments)
 int32_t step_accumulate(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G, const ptk::AdaptTable &AT) {
     const Frame &fr = ctx->frame;
@@ -1455,6 +1487,8 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
         if (int32_t rc = fr.wavefront ? dev_step_wavefront(ctx, d, F, B) : step_trace(ctx, d, F, B, timeline)) return rc;
         if (fr.fog_vol)  // (GL shading adds the term itself)
             if (int32_t rc = step_fog(ctx, d, F, G, AT.active)) return rc;
+        if (fr.features > 0 && s0 < (uint32_t)fr.features)  // (after the injected-ray overwrite: the rays that are traced)
+            if (int32_t rc = step_features(ctx, d, F, AT)) return rc;
     }
     return step_accumulate(ctx, d, F, G, AT);
 }
@@ -2504,8 +2538,25 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
     ctx->frame.adaptive = ctx->adaptive_on;
     ctx->frame.ad = ctx->adaptive;
     ctx->frame.moments = ctx->moments_on || ctx->adaptive_on;
+    if (ctx->features_k > 0) {  // refused before anything is launched; the context stays usable
+        const bool bvh = ctx->frame.scan == ptk::SCAN_BVH || ctx->frame.scan == ptk::SCAN_VERIFY_BVH;
+        if (bvh || ctx->frame.gl) {
+            ctx->frame.open = false;
+            return fail(PT_ERR_INVALID, bvh ? "features: not available for scenes on the BVH path (more than 128 spheres or 128 boxes): a linear "
+                                              "scan per feature sample"
+                                            : "features: not available with GL shading (pt_set_shading), where a sample is a pass of 16 paths");
+        }
+        ctx->frame.features = ctx->features_k;
+    }
     for (int32_t i = 0; i < ndev; i++) {
-        if (int32_t rc = dev_begin(ctx, ctx->devs[(size_t)i], pt_shard{i, ndev}, nullptr)) {
+        Device &d = ctx->devs[(size_t)i];
+        int32_t rc = dev_begin(ctx, d, pt_shard{i, ndev}, nullptr);
+        if (rc == PT_OK && ctx->frame.features > 0 && d.nlocal > 0) {  // outside PTCORE_L_BUDGET_MB, on the first frame that asks
+            hipError_t e = hipSetDevice(d.ordinal);
+            if (e == hipSuccess) e = d.feat.reserve(9 * (size_t)d.nslots);
+            if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("features: ") + hipGetErrorString(e));
+        }
+        if (rc) {
             ctx->frame.open = false;
             return rc;
         }
@@ -2608,6 +2659,7 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
     };
     if (ctx->frame.moments && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_MOMENTS, "moments_kernel");
     if (ctx->frame.adaptive && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_CHECK, "adaptive check");
+    if (ctx->frame.features > 0 && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_FEATURE, "feature_kernel");
     if (ctx->frame.fog_vol) {
         ctx->fog_pending = 1;
         if (int32_t r = collect_fog(ctx)) rc = rc != PT_OK ? rc : r;
@@ -2783,6 +2835,186 @@ int32_t pt_noise_estimate(pt_ctx *ctx, pt_noise *out) {
     r.noise = std::sqrt(sum / (double)r.pixels);
     *out = r;
     return PT_OK;
+}
+
+int32_t pt_set_features(pt_ctx *ctx, int32_t k) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_features while a frame is open");
+    if (k < 0) return fail(PT_ERR_INVALID, "pt_set_features: k must be >= 0");
+    ctx->features_k = k;
+    return PT_OK;
+}
+
+// one feature plane (0 normal, 1 albedo, 2 depth) through the gather, into the context's row-major frame and, when asked for, to the host
+static int32_t gather_feature(pt_ctx *ctx, uint32_t which, double *host) {
+    static void *(*const frames[3])(pt_ctx &, size_t, hipError_t &) = {reserved<pt_ctx, &pt_ctx::f_feat_n>, reserved<pt_ctx, &pt_ctx::f_feat_a>,
+                                                                       reserved<pt_ctx, &pt_ctx::f_feat_d>};
+    const Plane planes[] = {{true, PLANE_F64X3, reserved<Device, &Device::tiles_feat>, reserved<pt_ctx, &pt_ctx::g_tiles_feat>, frames[which], host, 0}};
+    return gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
+        hipLaunchKernelGGL(ptk::feature_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.feat.p,
+                           static_cast<double *>(dst[0]), d.nslots, which, tile_geom(ctx->frame, d));
+        HIP_TRY(hipGetLastError());
+        return PT_OK;
+    });
+}
+
+int32_t pt_read_features(pt_ctx *ctx, double *normal, double *albedo, double *depth) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (int32_t rc = moments_frame(ctx, "pt_read_features")) return rc;
+    const Frame &fr = ctx->frame;
+    if (fr.features <= 0) return fail(PT_ERR_STATE, "pt_read_features: the frame was rendered with features off (pt_set_features)");
+    double *const host[3] = {normal, albedo, depth};
+    for (uint32_t k = 0; k < 3u; k++)
+        if (host[k])
+            if (int32_t rc = gather_feature(ctx, k, host[k])) return rc;
+    return PT_OK;
+}
+
+int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32_t stride, double *mean, double *var, pt_atrous_stats *stats) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    pt_atrous_config c = {5, 0, 4.0, 0.1, 0.1, 0.2};
+    if (cfg) c = *cfg;
+    if (c.iterations < 0 || c.iterations > PTA_MAX_ITERATIONS) return fail(PT_ERR_INVALID, "pt_atrous: iterations must be 0..6");
+    if (!(c.sigma_l > 0.0) || !(c.sigma_n >= 0.0) || !(c.sigma_z >= 0.0) || !(c.sigma_a >= 0.0))
+        return fail(PT_ERR_INVALID, "pt_atrous: sigma_l must be > 0, sigma_n, sigma_z and sigma_a >= 0 (0 = term off)");
+    if (int32_t rc = moments_frame(ctx, "pt_atrous")) return rc;
+    Frame &fr = ctx->frame;
+    if (fr.gl) return fail(PT_ERR_STATE, "pt_atrous: not available for a frame rendered with GL shading (pt_set_shading)");
+    // (an adaptive block stops at two samples or more, so every pixel holds at least min(done, 2))
+    if (fr.done_spp < 2) return fail(PT_ERR_STATE, "pt_atrous: every pixel needs at least 2 samples");
+    const int32_t W = fr.cfg.width, H = fr.cfg.height;
+    if (rgba && stride < W * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    // the inputs as row-major planes on devices[0]: S, Q, the counts of an adaptive frame, the features of a frame that has them.  All
+    // reads: the sums, the block table and the event lists of the frame stay as they are.
+    {
+        const Plane planes[] = {
+            {true, PLANE_F64X3, reserved<Device, &Device::tiles_accum>, reserved<pt_ctx, &pt_ctx::g_tiles_accum>, reserved<pt_ctx, &pt_ctx::f_accum>, nullptr, 0}};
+        if (int32_t rc = gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
+                ptk::ResolveArgs R;
+                std::memset(&R, 0, sizeof R);
+                R.acc = d.acc.p;
+                R.tiles_accum = static_cast<double *>(dst[0]);
+                R.nslots = d.nslots;
+                R.first = d.acc_started ? 0 : 1;
+                R.finish = 1;
+                R.G = tile_geom(fr, d);
+                hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
+                HIP_TRY(hipGetLastError());
+                return PT_OK;
+            }))
+            return rc;
+    }
+    {
+        const Plane planes[] = {
+            {true, PLANE_F64X3, reserved<Device, &Device::tiles_m2>, reserved<pt_ctx, &pt_ctx::g_tiles_m2>, reserved<pt_ctx, &pt_ctx::f_m2>, nullptr, 0}};
+        if (int32_t rc = gather_planes(ctx, planes, [&](Device &d, void *const *dst) { return dev_finish_moments(ctx, d, static_cast<double *>(dst[0])); }))
+            return rc;
+    }
+    if (fr.adaptive) {
+        const Plane planes[] = {
+            {true, PLANE_U32A, reserved<Device, &Device::tiles_seg>, reserved<pt_ctx, &pt_ctx::g_tiles_seg>, reserved<pt_ctx, &pt_ctx::f_seg>, nullptr, 0}};
+        if (int32_t rc = gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
+                hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p,
+                                   static_cast<uint32_t *>(dst[0]), d.nslots, tile_geom(fr, d));
+                HIP_TRY(hipGetLastError());
+                return PT_OK;
+            }))
+            return rc;
+    }
+    const bool feat = fr.features > 0;
+    if (feat)
+        for (uint32_t k = 0; k < 3u; k++)
+            if (int32_t rc = gather_feature(ctx, k, nullptr)) return rc;
+    Device &d0 = ctx->devs[0];
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    const size_t npix = (size_t)W * (size_t)H;
+    const uint32_t grid1 = (uint32_t)((npix + PT_BLOCK - 1) / PT_BLOCK);
+    for (int k = 0; k < 2; k++) {
+        HIP_TRY(ctx->at_col[k].reserve(3 * npix));
+        HIP_TRY(ctx->at_var[k].reserve(npix));
+    }
+    HIP_TRY(ctx->at_guide.reserve(npix));
+    HIP_TRY(ctx->at_part.reserve(2 * (size_t)grid1));
+    HIP_TRY(ctx->f_rgba.reserve(npix * 4));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    HIP_TRY(hipEventCreate(&ev[0]));
+    if (hipError_t e = hipEventCreate(&ev[1]); e != hipSuccess) {
+        (void)hipEventDestroy(ev[0]);
+        return fail(PT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+    }
+    auto run = [&]() -> int32_t {
+        HIP_TRY(hipEventRecord(ev[0], d0.stream));
+        ptk::AtrousPrepArgs PA;
+        std::memset(&PA, 0, sizeof PA);
+        PA.acc = ctx->f_accum.p;
+        PA.m2 = ctx->f_m2.p;
+        PA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
+        PA.fn = feat ? ctx->f_feat_n.p : nullptr;
+        PA.fa = feat ? ctx->f_feat_a.p : nullptr;
+        PA.fd = feat ? ctx->f_feat_d.p : nullptr;
+        PA.col = ctx->at_col[0].p;
+        PA.var = ctx->at_var[0].p;
+        PA.guide = ctx->at_guide.p;
+        PA.npix = (uint32_t)npix;
+        PA.n = (uint32_t)fr.done_spp;
+        hipLaunchKernelGGL(ptk::atrous_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, PA);
+        hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[0].p, ctx->at_var[0].p, ctx->at_guide.p,
+                           ctx->at_part.p, (uint32_t)npix);
+        ptk::AtrousArgs A;
+        std::memset(&A, 0, sizeof A);
+        A.P.sigma_l = c.sigma_l; A.P.sigma_n = c.sigma_n; A.P.sigma_z = c.sigma_z; A.P.sigma_a = c.sigma_a;
+        A.P.iterations = c.iterations;
+        A.P.n_on = feat && c.sigma_n > 0.0;
+        A.P.z_on = feat && c.sigma_z > 0.0;
+        A.P.a_on = feat && c.sigma_a > 0.0;
+        A.guide = ctx->at_guide.p;
+        A.W = W;
+        A.H = H;
+        int cur = 0;
+        for (int32_t t = 0; t < c.iterations; t++, cur ^= 1) {
+            A.col = ctx->at_col[cur].p; A.var = ctx->at_var[cur].p;
+            A.col_out = ctx->at_col[cur ^ 1].p; A.var_out = ctx->at_var[cur ^ 1].p;
+            A.step = 1 << t;
+            hipLaunchKernelGGL(ptk::atrous_kernel, dim3((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8)), dim3(PT_BLOCK), 0, d0.stream, A);
+        }
+        hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[cur].p, ctx->at_var[cur].p, ctx->at_guide.p,
+                           ctx->at_part.p + grid1, (uint32_t)npix);
+        hipLaunchKernelGGL(ptk::atrous_finish_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[cur].p, ctx->f_rgba.p, (uint32_t)npix);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[1], d0.stream));
+        std::vector<ptk::NoisePartial> part(2 * (size_t)grid1);
+        HIP_TRY(hipMemcpyAsync(part.data(), ctx->at_part.p, part.size() * sizeof(ptk::NoisePartial), hipMemcpyDeviceToHost, d0.stream));
+        if (rgba) HIP_TRY(hipMemcpy2DAsync(rgba, (size_t)stride, ctx->f_rgba.p, (size_t)W * 4, (size_t)W * 4, (size_t)H, hipMemcpyDeviceToHost, d0.stream));
+        if (mean) HIP_TRY(hipMemcpyAsync(mean, ctx->at_col[cur].p, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+        if (var) HIP_TRY(hipMemcpyAsync(var, ctx->at_var[cur].p, npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+        HIP_TRY(hipStreamSynchronize(d0.stream));
+        if (stats) {
+            pt_atrous_stats st;
+            std::memset(&st, 0, sizeof st);
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            st.atrous_ms = ms;
+            st.launches = c.iterations + 4;
+            st.iterations = c.iterations;
+            double sum[2] = {0.0, 0.0};
+            for (int k = 0; k < 2; k++)
+                for (uint32_t b = 0; b < grid1; b++) sum[k] += part[(size_t)k * grid1 + b].sum;  // partials in block order
+            for (uint32_t b = 0; b < grid1; b++) st.bad_pixels += part[b].bad;
+            st.noise_before = std::sqrt(sum[0] / (double)npix);
+            st.noise_after = std::sqrt(sum[1] / (double)npix);
+            *stats = st;
+        }
+        return PT_OK;
+    };
+    const int32_t rc = run();
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    if (rc == PT_OK && std::getenv("PTCORE_VERBOSE"))
+        std::fprintf(stderr, "ptcore: pt_atrous %d iterations, %.3f ms host wall (gathers included)\n", c.iterations,
+                     std::chrono::duration<double, std::milli>(clk::now() - t0).count());
+    return rc;
 }
 
 int32_t pt_render_tiles_device(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, const pt_shard *shard,

@@ -61,14 +61,17 @@ def new_image(w: int, h: int) -> np.ndarray:
 def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 progress: Optional[Callable[[], None]] = None, shading: Optional[str] = None,
                 moments: Optional[np.ndarray] = None, noise: Optional[float] = None, noise_step: Optional[int] = None,
-                adaptive: Optional[bool] = None, min_spp: Optional[int] = None, counts: Optional[np.ndarray] = None) -> dict:
+                adaptive: Optional[bool] = None, min_spp: Optional[int] = None, counts: Optional[np.ndarray] = None,
+                features: Optional[int] = None, atrous: Optional["hip.AtrousConfig"] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
     cap; noise None takes PATHTRACER_GPU_NOISE / PATHTRACER_GPU_NOISE_STEP (hip.NoiseConfig.from_env), off by default.
     `adaptive`, `min_spp` and `counts` are hip.render's too: with a noise target, every 8x8 block stops at it by
     itself; None takes PATHTRACER_GPU_ADAPTIVE / PATHTRACER_GPU_ADAPTIVE_MIN_SPP (hip.AdaptiveConfig.from_env).  Without a
-    noise target adaptive has nothing to adapt to and the frame is a plain one."""
+    noise target adaptive has nothing to adapt to and the frame is a plain one.  `features` and `atrous` are hip.render's as well
+    (DESIGN 3.11): the first-hit feature samples per pixel and the a-trous filter that replaces the image; None takes
+    PATHTRACER_GPU_FEATURES and PATHTRACER_GPU_ATROUS / PATHTRACER_GPU_ATROUS_ITERS (hip.AtrousConfig.from_env), both off by default."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -81,7 +84,11 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     acfg = hip.AdaptiveConfig.from_env()
     if adaptive is None:
         adaptive = acfg.enabled
-    return hip.render(sc, gcfg, img, progress, shading=model, moments=moments, noise=noise,
+    if atrous is None:
+        atrous = hip.AtrousConfig.from_env()
+    if features is None:
+        features = hip.features_from_env()
+    return hip.render(sc, gcfg, img, progress, shading=model, features=features, atrous=atrous, moments=moments, noise=noise,
                       noise_step=noise_step if noise_step is not None else ncfg.step, adaptive=bool(adaptive) and noise is not None,
                       min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts)
 

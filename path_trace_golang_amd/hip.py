@@ -276,6 +276,124 @@ def adaptive_plan_host(samples: np.ndarray, target: float, step: int, min_spp: i
     return counts
 
 
+def set_features(ctx: capi.Context, k: int) -> None:
+    """pt_set_features: later frames on ctx collect the first-hit normal, albedo and distance of every pixel's first k samples
+    (DESIGN 3.11); 0 = off, the default."""
+    if not capi.has("pt_set_features"):
+        if k:
+            raise RuntimeError("this libptcore.so has no pt_set_features (rebuild it)")
+        return
+    capi.check(capi.load().pt_set_features(ctx.handle, int(k)))
+
+
+def read_features(ctx: capi.Context, normal: Optional[np.ndarray] = None, albedo: Optional[np.ndarray] = None,
+                  depth: Optional[np.ndarray] = None) -> None:
+    """pt_read_features into the arrays given (contiguous float64 [H, W, 3] each): the raw sums over the feature samples of the
+    face-forward normal, of the albedo and of (distance, samples that hit, feature samples taken)."""
+    for a in (normal, albedo, depth):
+        if a is not None and (a.dtype != np.float64 or a.ndim != 3 or a.shape[2] != 3 or not a.flags.c_contiguous):
+            raise ValueError("feature planes must be contiguous float64 [H, W, 3]")
+    p = [a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None for a in (normal, albedo, depth)]
+    capi.check(capi.load().pt_read_features(ctx.handle, *p))
+
+
+@dataclass
+class AtrousConfig:
+    """The a-trous filter of pt_atrous: iterations 0..6 and the four sigmas (a feature sigma of 0 turns its term
+    off); `features` = feature samples per pixel that `render` asks for (None: 4 where the scene allows them, else 0)."""
+    iterations: int = 5
+    sigma_l: float = 4.0
+    sigma_n: float = 0.1
+    sigma_z: float = 0.1
+    sigma_a: float = 0.2
+    features: Optional[int] = None
+
+    @classmethod
+    def from_env(cls, environ=None) -> Optional["AtrousConfig"]:
+        """PATHTRACER_GPU_ATROUS=1 (or true / on / yes) turns the filter on (None otherwise); PATHTRACER_GPU_ATROUS_ITERS=<0..6>
+        and PATHTRACER_GPU_FEATURES=<int >= 0> set the iterations and the feature samples, anything else keeps the default."""
+        import os
+
+        env = os.environ if environ is None else environ
+        if env.get("PATHTRACER_GPU_ATROUS", "").lower() not in ("1", "true", "on", "yes"):
+            return None
+        cfg = cls()
+        try:
+            i = int(env["PATHTRACER_GPU_ATROUS_ITERS"])
+            if 0 <= i <= 6:
+                cfg.iterations = i
+        except (KeyError, ValueError):
+            pass
+        k = features_from_env(env)
+        if k is not None:
+            cfg.features = k
+        return cfg
+
+    def c(self) -> capi.PtAtrousConfig:
+        return capi.PtAtrousConfig(int(self.iterations), 0, float(self.sigma_l), float(self.sigma_n), float(self.sigma_z),
+                                   float(self.sigma_a))
+
+
+def features_from_env(environ=None) -> Optional[int]:
+    """PATHTRACER_GPU_FEATURES=<int >= 0>: the feature samples per pixel, None when unset or not such a number."""
+    import os
+
+    env = os.environ if environ is None else environ
+    try:
+        k = int(env["PATHTRACER_GPU_FEATURES"])
+        return k if k >= 0 else None
+    except (KeyError, ValueError):
+        return None
+
+
+def atrous(ctx: capi.Context, cfg: Optional[AtrousConfig], img: Optional[np.ndarray], mean: Optional[np.ndarray] = None,
+           var: Optional[np.ndarray] = None) -> dict:
+    """pt_atrous on ctx's open or last frame (cfg None = the defaults): img (uint8 [H, W, 4] or None) receives the finished
+    filtered image, mean (float64 [H, W, 3]) and var (float64 [H, W]) the filtered mean and its variance.  Returns the
+    pt_atrous_stats: atrous_ms, launches, iterations, noise_before, noise_after, bad_pixels."""
+    if not capi.has("pt_atrous"):
+        raise RuntimeError("this libptcore.so has no pt_atrous (rebuild it)")
+    stride = 0
+    if img is not None:
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4 or img.strides[2] != 1 or img.strides[1] != 4:
+            raise ValueError("img must be uint8 [H, W, 4] with contiguous RGBA rows")
+        stride = int(img.strides[0])
+    if mean is not None and (mean.dtype != np.float64 or mean.ndim != 3 or mean.shape[2] != 3 or not mean.flags.c_contiguous):
+        raise ValueError("mean must be contiguous float64 [H, W, 3]")
+    if var is not None and (var.dtype != np.float64 or var.ndim != 2 or not var.flags.c_contiguous):
+        raise ValueError("var must be contiguous float64 [H, W]")
+    for a in (mean, var):
+        if a is not None and img is not None and a.shape[:2] != img.shape[:2]:
+            raise ValueError("mean / var must have the image's height and width")
+    c = cfg.c() if cfg is not None else None
+    st = capi.PtAtrousStats()
+    dp = C.POINTER(C.c_double)
+    capi.check(capi.load().pt_atrous(ctx.handle, C.byref(c) if c is not None else None, _ptr(img), stride,
+                                     mean.ctypes.data_as(dp) if mean is not None else None,
+                                     var.ctypes.data_as(dp) if var is not None else None, C.byref(st)))
+    return st.as_dict()
+
+
+_atrous = atrous  # (`render` has an argument of that name)
+
+
+def scene_allows_features(sc, shading: str = "cpu") -> bool:
+    """Does a frame of this scene accept pt_set_features(k > 0)?  Not with GL shading, and not on the bounding-volume-hierarchy
+    path (more than 128 spheres or 128 boxes, or PTCORE_SCAN=bvh)."""
+    import os
+
+    if shading != "cpu" or os.environ.get("PTCORE_SCAN", "") in ("bvh", "verify_bvh"):
+        return False
+    if isinstance(sc, FlatScene):
+        types = [sc.objects[i].type for i in range(sc.c.num_objects)]
+        ns = sum(t in (capi.PT_OBJ_SPHERE, capi.PT_OBJ_SPHERE_LIGHT) for t in types)
+        nb = sum(t == capi.PT_OBJ_BOX for t in types)
+    else:
+        ns = sum(o.type in (scn.OBJECT_SPHERE, scn.OBJECT_SPHERE_LIGHT) for o in sc.objects)
+        nb = sum(o.type == scn.OBJECT_BOX for o in sc.objects)
+    return ns <= 128 and nb <= 128
+
+
 def pt_config(cfg: RenderConfig) -> capi.PtConfig:
     return capi.PtConfig(cfg.width, cfg.height, cfg.samples_per_px, cfg.max_depth, cfg.seed & 0xFFFFFFFFFFFFFFFF,
                          cfg.spp_chunk, cfg.flags)
@@ -309,7 +427,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            accum: Optional[np.ndarray] = None, nseg: Optional[np.ndarray] = None,
            ndraw: Optional[np.ndarray] = None, ctx: Optional[capi.Context] = None, fog: bool = False,
            shading: str = "cpu", moments: Optional[np.ndarray] = None, noise: Optional[float] = None,
-           noise_step: int = 16, adaptive: bool = False, min_spp: int = 0, counts: Optional[np.ndarray] = None) -> dict:
+           noise_step: int = 16, adaptive: bool = False, min_spp: int = 0, counts: Optional[np.ndarray] = None,
+           features: Optional[int] = None, atrous: Optional["AtrousConfig"] = None) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -329,6 +448,12 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     samples are added noise_step at a time, after each step (once max(min_spp, 2) samples are done) the blocks at or below T stop,
     and the frame ends when no block is active or at the cap.  Every pixel is normalised by its own count; counts (uint32
     [H, W]) receives them, and the returned dict gains "adaptive": the pt_adaptive_state of the frame (spp_done is its spp_max).
+
+    features=k collects the first-hit feature planes over every pixel's first k samples (pt_set_features; read
+    them with read_features(ctx, ...) afterwards -- that needs moments on).  atrous=AtrousConfig() turns moments on, renders, and
+    then replaces img by the a-trous filtered image (pt_atrous); features then defaults to the config's value, or to 4 where the
+    scene allows features (scene_allows_features) and 0 where it does not.  The returned dict gains "atrous": the pt_atrous_stats.
+    Without the two arguments features are off for the call.
 
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
@@ -353,8 +478,13 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
                                or not counts.flags.c_contiguous):
         raise ValueError("counts needs adaptive=True and a contiguous uint32 [H, W] array")
     set_adaptive(ctx, noise if adaptive else None, min_spp, noise_step)
-    want_moments = moments is not None or noise is not None
+    want_moments = moments is not None or noise is not None or atrous is not None
     set_moments(ctx, want_moments)
+    if features is None:
+        features = 0
+        if atrous is not None:
+            features = atrous.features if atrous.features is not None else (4 if scene_allows_features(sc, shading) else 0)
+    set_features(ctx, features)
     if moments is not None and (moments.dtype != np.float64 or moments.shape != (cfg.height, cfg.width, 3)
                                 or not moments.flags.c_contiguous):
         raise ValueError("moments must be contiguous float64 [H, W, 3]")
@@ -373,6 +503,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
             if moments is not None:
                 read_moments(ctx, moments)
             d.update(noise=noise_estimate(ctx)["noise"])
+            if atrous is not None:  # the filtered image takes the place of the plain finish
+                d["atrous"] = _atrous(ctx, atrous, img)
             if adaptive:
                 d["adaptive"] = adaptive_state(ctx)
                 d["spp_done"] = d["adaptive"]["spp_max"]
