@@ -7,6 +7,7 @@
 // -noise -noise-step (render until the frame noise is at or below the target, -spp being the cap; DESIGN 3.9),
 // -adaptive -min-spp (with -noise: every 8x8 block stops at the target by itself; DESIGN 3.10).
 // -atrous -atrous-iters -features (the variance-guided a-trous filtered image and its first-hit feature samples; DESIGN 3.11).
+// -filtered-noise (with -atrous: render until the measured noise of the filtered frame is at or below the target; DESIGN 3.12).
 package main
 
 import (
@@ -41,6 +42,7 @@ func main() {
 	atrous := flag.Bool("atrous", false, "write the variance-guided a-trous filtered image (or PATHTRACER_GPU_ATROUS)")
 	atrousIters := flag.Int("atrous-iters", 5, "with -atrous: iterations 0..6 (or PATHTRACER_GPU_ATROUS_ITERS)")
 	features := flag.Int("features", -1, "first-hit feature samples per pixel (default: 4 with -atrous where the scene allows them, else 0; or PATHTRACER_GPU_FEATURES)")
+	filteredNoise := flag.Float64("filtered-noise", 0, "with -atrous: render until the measured noise of the filtered frame is at or below this target, checking every -noise-step samples, -spp being the cap (0 = off, or PATHTRACER_GPU_FILTERED_NOISE)")
 	flag.Parse()
 	log.Printf("flags: scene=%s mode=%s headless=%v out=%s\n", *scenePath, *mode, *headless, *output)
 
@@ -68,6 +70,11 @@ func main() {
 		}
 		if featuresGiven {
 			hip.SetFeatures(*features)
+		}
+		filteredGiven := false
+		flag.Visit(func(f *flag.Flag) { filteredGiven = filteredGiven || f.Name == "filtered-noise" })
+		if filteredGiven { // else the environment decides
+			hip.SetFilteredNoise(*filteredNoise)
 		}
 	} else {
 		engine.SetBackend(engine.BackendCPU)
@@ -119,6 +126,10 @@ func main() {
 			n, z := hip.LastFrame()
 			log.Printf("rendered %dx%d, %d to %d of at most %d spp per 8x8 block (adaptive: %d of %d blocks still above the target; frame noise %.6g)\n",
 				s.Width, s.Height, a.SppMin, n, s.SamplesPerPx, a.ActiveBlocks, a.Blocks, z)
+		} else if h := hip.LastHalves(); h.Launches > 0 {
+			n, _ := hip.LastFrame()
+			log.Printf("rendered %dx%d, %d of at most %d spp (filtered noise %.6g measured, %.6g propagated)\n", s.Width, s.Height, n, s.SamplesPerPx,
+				h.Noise, h.NoiseModel)
 		} else if n, z := hip.LastFrame(); z > 0 {
 			log.Printf("rendered %dx%d, %d of at most %d spp (noise %.6g)\n", s.Width, s.Height, n, s.SamplesPerPx, z)
 		}

@@ -23,6 +23,7 @@ import (
 	"errors"
 	"fmt"
 	"image"
+	"math"
 	"os"
 	"runtime"
 	"strconv"
@@ -64,7 +65,22 @@ var (
 	atrousIters = 5
 	featuresK   = -1         // -1: not said, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows)
 	lastAtrous  AtrousStats // pt_atrous_stats of the last frame (zero unless it was filtered)
+
+	filteredSet    bool        // false: PATHTRACER_GPU_FILTERED_NOISE decides
+	filteredTarget float64     // the noise target on the filtered frame (0 = off)
+	lastHalves     HalvesStats // pt_halves_stats of the last check of the last frame (zero unless that stop rule was in force)
 )
+
+// HalvesStats mirrors pt_halves_stats: the measured and the propagated noise of the filtered frame at the last check.
+type HalvesStats struct {
+	Ms         float64
+	Launches   int
+	Iterations int
+	Noise      float64 // measured: the two halves' difference
+	NoiseModel float64 // propagated: optimistic
+	BadPixels  uint64
+	SppMin     int
+}
 
 // AtrousStats mirrors pt_atrous_stats: what the a-trous filter did to the last frame.
 type AtrousStats struct {
@@ -141,6 +157,42 @@ func SetAtrous(on bool, iterations int) {
 		iterations = 5
 	}
 	atrousIters = iterations
+}
+
+// SetFilteredNoise puts the noise target on the filtered frame (DESIGN 3.12): with the filter on (SetAtrous) the frame collects the
+// half-buffer sums (pt_set_halves), samples are added a noise step at a time (SetNoiseTarget's step, or PATHTRACER_GPU_NOISE_STEP),
+// after every step with at least 4 samples done pt_atrous_halves runs with the filter's configuration, and the frame stops at the
+// first check whose measured noise is at or below target, cfg.SamplesPerPx being the cap.  The image is pt_atrous on the full sums.
+// target <= 0 turns the rule off.  It is ignored without the filter and is an error beside a frame noise target or GL shading.
+func SetFilteredNoise(target float64) {
+	mu.Lock()
+	defer mu.Unlock()
+	filteredSet = true
+	if target < 0 {
+		target = 0
+	}
+	filteredTarget = target
+}
+
+// LastHalves reports the figures of the last check of the last frame Render finished under SetFilteredNoise.
+func LastHalves() HalvesStats {
+	mu.Lock()
+	defer mu.Unlock()
+	return lastHalves
+}
+
+// filteredRule: the noise target on the filtered frame in force (SetFilteredNoise, else the environment; 0 = off, also without the filter).
+func filteredRule() float64 {
+	if on, _ := atrousRule(); !on {
+		return 0
+	}
+	if filteredSet {
+		return filteredTarget
+	}
+	if v, err := strconv.ParseFloat(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_FILTERED_NOISE")), 64); err == nil && v > 0 && !math.IsInf(v, 0) {
+		return v
+	}
+	return 0
 }
 
 // SetFeatures sets the first-hit feature samples per pixel (pt_set_features); k < 0 = not said.
@@ -505,7 +557,21 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 	}
 	target, nstep := noiseRule()
 	toNoise := target > 0
-	atrous, _ := atrousRule()
+	atrous, atrousN := atrousRule()
+	filtered := filteredRule()
+	if filtered > 0 && toNoise {
+		return errors.New("hip.Render: the filtered noise target excludes a frame noise target and adaptive sampling: one stop rule per frame")
+	}
+	if filtered > 0 && glShading() {
+		return errors.New("hip.Render: the filtered noise target is not available with GL shading")
+	}
+	var halvesOn C.int32_t
+	if filtered > 0 {
+		halvesOn = 1
+	}
+	if rc := C.pt_set_halves(ctx, halvesOn); rc != C.PT_OK {
+		return lastError("pt_set_halves")
+	}
 	if rc := C.pt_set_features(ctx, C.int32_t(featuresRule(sc, atrous))); rc != C.PT_OK {
 		return lastError("pt_set_features")
 	}
@@ -526,12 +592,15 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 	} else if rc := C.pt_set_adaptive(ctx, nil); rc != C.PT_OK {
 		return lastError("pt_set_adaptive")
 	}
-	lastSpp, lastNoise, lastAdaptive = 0, 0, AdaptiveState{}
+	lastSpp, lastNoise, lastAdaptive, lastHalves = 0, 0, AdaptiveState{}, HalvesStats{}
 	pc := C.pt_config{width: C.int32_t(cfg.Width), height: C.int32_t(cfg.Height),
 		samples_per_px: C.int32_t(cfg.SamplesPerPx), max_depth: C.int32_t(cfg.MaxDepth), seed: C.uint64_t(seed)}
 	pix := (*C.uint8_t)(unsafe.Pointer(&img.Pix[0]))
 	if toNoise {
 		return renderToNoise(cs, &pc, cfg, img, pix, progress, target, nstep, adaptive)
+	}
+	if filtered > 0 {
+		return renderToFilteredNoise(cs, &pc, cfg, img, pix, progress, filtered, nstep, atrousN)
 	}
 	if progress == nil {
 		if rc := C.pt_render(ctx, cs, &pc, pix, C.int32_t(img.Stride), nil, nil, nil, nil); rc != C.PT_OK {
@@ -572,6 +641,64 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 	if err == nil {
 		progress()
 		lastSpp = int(done)
+	}
+	return err
+}
+
+// renderToFilteredNoise: pt_begin with cfg.SamplesPerPx as the cap, then steps of nstep samples; after each step with at least 4
+// samples done pt_atrous_halves measures the noise of the filtered frame, and the loop stops at the first check at or below target.
+// Called with mu held on a locked OS thread.
+func renderToFilteredNoise(cs *C.pt_scene, pc *C.pt_config, cfg RenderConfig, img *image.RGBA, pix *C.uint8_t, progress func(),
+	target float64, nstep int, iters int) error {
+	if rc := C.pt_begin(ctx, cs, pc); rc != C.PT_OK {
+		return lastError("pt_begin")
+	}
+	ac := C.pt_atrous_config{iterations: C.int32_t(iters), sigma_l: 4, sigma_n: 0.1, sigma_z: 0.1, sigma_a: 0.2}
+	var done C.int32_t
+	var hs C.pt_halves_stats
+	var err error
+	for int(done) < cfg.SamplesPerPx {
+		n := cfg.SamplesPerPx - int(done)
+		if nstep < n {
+			n = nstep
+		}
+		if rc := C.pt_step(ctx, C.int32_t(n), &done); rc != C.PT_OK {
+			err = lastError("pt_step")
+			break
+		}
+		if progress != nil {
+			if rc := C.pt_read(ctx, pix, C.int32_t(img.Stride), nil); rc != C.PT_OK {
+				err = lastError("pt_read")
+				break
+			}
+			progress()
+		}
+		if int(done) < 4 { // each half needs two samples for its variance
+			continue
+		}
+		if rc := C.pt_atrous_halves(ctx, &ac, nil, nil, nil, &hs); rc != C.PT_OK {
+			err = lastError("pt_atrous_halves")
+			break
+		}
+		if float64(hs.noise) <= target {
+			break
+		}
+	}
+	if err == nil && (progress == nil || cfg.SamplesPerPx <= 0) {
+		if rc := C.pt_read(ctx, pix, C.int32_t(img.Stride), nil); rc != C.PT_OK {
+			err = lastError("pt_read")
+		}
+	}
+	if rc := C.pt_end(ctx, nil); rc != C.PT_OK && err == nil {
+		err = lastError("pt_end")
+	}
+	if err == nil {
+		if progress != nil {
+			progress()
+		}
+		lastSpp = int(done)
+		lastHalves = HalvesStats{Ms: float64(hs.atrous_ms), Launches: int(hs.launches), Iterations: int(hs.iterations), Noise: float64(hs.noise),
+			NoiseModel: float64(hs.noise_model), BadPixels: uint64(hs.bad_pixels), SppMin: int(hs.spp_min)}
 	}
 	return err
 }

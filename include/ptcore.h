@@ -486,6 +486,55 @@ int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32
                   pt_atrous_stats *stats);
 
 /*
+ * Half-buffer sums and the measured noise of the filtered frame (additive to ABI 4; the model and its order of
+ * evaluation are stated in csrc/pt_atrous.h, HALVES).  pt_atrous's noise_after is the model's own propagated variance and reports half
+ * to two thirds of the noise that is really left; the figure here is measured: the samples of every pixel are split into the even-
+ * indexed half A and the odd-indexed half B, each half is filtered as a frame of its own, and ((fA - fB) / 2)^2 estimates the variance of
+ * (fA + fB) / 2 with no assumption about the taps, since the halves share no sample.  Off unless asked for: with halves off nothing is
+ * allocated or launched.
+ *   pt_set_halves(ctx, on)  : default 0; later frames on ctx (pt_begin ... pt_end, pt_render) also collect, per pixel and channel, four
+ *                             raw sums, each added in sample order: SA = sum of L and QA = sum of L*L over the pixel's samples with an
+ *                             even 0-based index, SB and QB over the odd ones (L as in pt_set_moments: after the fog term).  96 B per
+ *                             pixel on the devices, outside PTCORE_L_BUDGET_MB.  Such frames collect second moments whether or not
+ *                             pt_set_moments asked.  pt_render_tiles_device neither collects nor fails.  PT_ERR_STATE while a frame
+ *                             is open.
+ *   pt_read_halves          : sa / qa / sb / qb = width*height*3 doubles each, row-major like accum, any of them NULL.  Valid exactly
+ *                             when pt_read_moments is; PT_ERR_STATE otherwise and for a frame rendered with halves off.
+ *   pt_atrous_halves        : with a pixel's count n, nA = (n + 1) / 2 and nB = n / 2: fA = pt_atrous's model on (SA, QA, nA) and the
+ *                             frame's feature planes, fB the same on (SB, QB, nB); per pixel mean = (fA + fB) / 2 and
+ *                             err = mean over the channels of ((fA - fB) / 2)^2.
+ *       mean       : optional width*height*3 doubles, the combined mean.  As an image it is somewhat worse than pt_atrous's (weights from
+ *                    half the samples are noisier): this call is the meter, pt_atrous makes the picture.
+ *       err        : optional width*height doubles.  A one-degree-of-freedom estimate per pixel: only meaningful averaged over many
+ *                    pixels, as `noise` does.
+ *       half_means : optional 2*width*height*3 doubles, fA then fB
+ *       noise      : sqrt(sum of err / max(l, 0.01)^2 / pixels), l = the mean of mean's three channels; a pixel that is bad in either
+ *                    half, or whose term is NaN or infinite, adds 0 and is counted in bad_pixels.  Reduced over a fixed tree: the
+ *                    same bits every time.
+ *       noise_model: the same figure with (varA' + varB') / 4, the halves' propagated variances, in place of err: the optimistic
+ *                    estimate, beside the measured one so that the gap is visible.
+ *   Neither figure sees the bias the filter adds.  cfg as for pt_atrous, with the same PT_ERR_INVALID refusals.  Valid when
+ *   pt_read_halves is and every in-frame pixel holds at least 4 samples, so that each half has a variance (an adaptive frame: set
+ *   min_spp >= 4); otherwise PT_ERR_STATE, with the smallest count named in the message, and PT_ERR_STATE for a frame rendered with GL
+ *   shading.  A pure read, also between two pt_steps; every refusal leaves the context usable.  Runs on devices[0].
+ */
+typedef struct pt_halves_stats {
+    double atrous_ms;     /* device time first launch -> last launch complete (the gathers are not in it) */
+    int32_t launches;     /* prep + iterations + combine */
+    int32_t iterations;
+    double noise;
+    double noise_model;
+    uint64_t bad_pixels;
+    int32_t spp_min;      /* the smallest count a pixel of the frame holds */
+    int32_t reserved;
+} pt_halves_stats;
+
+int32_t pt_set_halves(pt_ctx *ctx, int32_t on);
+int32_t pt_read_halves(pt_ctx *ctx, double *sa, double *qa, double *sb, double *qb);
+int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean, double *err, double *half_means,
+                         pt_halves_stats *stats);
+
+/*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the
  * environment at pt_create, the trace kernel runs a build that counts, per code
  * section, wave executions, active lanes and shader-clock cycles.  Copies up to n

@@ -129,6 +129,14 @@ class PtAtrousStats(C.Structure):  # pt_atrous_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PtHalvesStats(C.Structure):  # pt_halves_stats
+    _fields_ = [("atrous_ms", C.c_double), ("launches", C.c_int32), ("iterations", C.c_int32), ("noise", C.c_double),
+                ("noise_model", C.c_double), ("bad_pixels", C.c_uint64), ("spp_min", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class PtShard(C.Structure):
     _fields_ = [("index", C.c_int32), ("count", C.c_int32)]
 
@@ -184,6 +192,10 @@ SYMBOLS = [
     ("pt_read_features", C.c_int32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("pt_atrous", C.c_int32, [_vp, C.POINTER(PtAtrousConfig), _vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(PtAtrousStats)]),
+    ("pt_set_halves", C.c_int32, [_vp, C.c_int32]),                       # additive to ABI 4 (see has())
+    ("pt_read_halves", C.c_int32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("pt_atrous_halves", C.c_int32, [_vp, C.POINTER(PtAtrousConfig), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(PtHalvesStats)]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
@@ -226,7 +238,7 @@ def load():
 
 ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_rays", "pt_set_moments", "pt_read_moments",
             "pt_noise_estimate", "pt_set_adaptive", "pt_adaptive_state", "pt_read_sample_counts", "pt_set_features",
-            "pt_read_features", "pt_atrous")  # added within ABI 4: detected by presence
+            "pt_read_features", "pt_atrous", "pt_set_halves", "pt_read_halves", "pt_atrous_halves")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:

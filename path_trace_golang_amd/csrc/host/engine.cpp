@@ -66,6 +66,8 @@ struct Core {
     int32_t (*adaptive_state)(pt_ctx *, struct pt_adaptive_state *) = nullptr;
     decltype(&pt_set_features) set_features = nullptr;  // optional, as set_shading (the a-trous filter needs pt_atrous and moments)
     decltype(&pt_atrous) atrous = nullptr;
+    decltype(&pt_set_halves) set_halves = nullptr;  // optional, as set_shading (the filtered noise target needs both)
+    decltype(&pt_atrous_halves) atrous_halves = nullptr;
     std::string error;  // sticky load error, like the reference's cached GL init failure (gpu.go:279-286)
 };
 
@@ -81,6 +83,7 @@ int g_adaptive = -1;  // -1: not set yet, PATHTRACER_GPU_ADAPTIVE / _MIN_SPP dec
 int g_adaptive_min_spp = 0;
 int g_atrous = -1;  // -1: not set yet, PATHTRACER_GPU_ATROUS / _ITERS decide
 int g_atrous_iters = 5;
+double g_filtered_noise = -1;  // < 0: not set yet, PATHTRACER_GPU_FILTERED_NOISE decides
 int g_features = -1;  // -1: not set yet, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows, else 0)
 std::mutex g_mu;  // requests are serialised, like the reference's single GL worker (gpu.go:2534-2546)
 
@@ -134,6 +137,8 @@ bool load_core() {
     c.adaptive_state = reinterpret_cast<decltype(c.adaptive_state)>(dlsym(h, "pt_adaptive_state"));
     c.set_features = reinterpret_cast<decltype(c.set_features)>(dlsym(h, "pt_set_features"));
     c.atrous = reinterpret_cast<decltype(c.atrous)>(dlsym(h, "pt_atrous"));
+    c.set_halves = reinterpret_cast<decltype(c.set_halves)>(dlsym(h, "pt_set_halves"));
+    c.atrous_halves = reinterpret_cast<decltype(c.atrous_halves)>(dlsym(h, "pt_atrous_halves"));
     if (c.abi_version() != PT_ABI_VERSION) {
         g_core.error = "libptcore.so ABI version mismatch";
         dlclose(h);
@@ -413,6 +418,25 @@ int GetAtrousIterations() {
     return g_atrous < 0 ? it : g_atrous_iters;
 }
 
+double FilteredNoiseFromEnv() {
+    if (const char *e = std::getenv("PATHTRACER_GPU_FILTERED_NOISE")) {
+        char *end = nullptr;
+        const double v = std::strtod(e, &end);
+        if (end != e && *end == 0 && v > 0 && v <= 1.7976931348623157e308) return v;
+    }
+    return 0;
+}
+
+void SetFilteredNoise(double target) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_filtered_noise = target > 0 ? target : 0;
+}
+
+double GetFilteredNoise() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_filtered_noise < 0 ? FilteredNoiseFromEnv() : g_filtered_noise;
+}
+
 void SetFeatures(int k) {
     std::lock_guard<std::mutex> lk(g_mu);
     g_features = k >= 0 ? k : -1;
@@ -477,6 +501,13 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     int atrous_iters = g_atrous_iters;
     if (g_atrous < 0) AtrousFromEnv(atrous, atrous_iters);
     if (atrous && !(g_core.atrous && g_core.set_moments)) return "a-trous filter: libptcore.so lacks pt_atrous / pt_set_moments";
+    // a noise target on the filtered frame (SetFilteredNoise / PATHTRACER_GPU_FILTERED_NOISE): the half-buffer sums and pt_atrous_halves
+    const double filtered_target = atrous ? (g_filtered_noise < 0 ? FilteredNoiseFromEnv() : g_filtered_noise) : 0;
+    const bool to_filtered = filtered_target > 0;
+    if (to_filtered && to_noise) return "filtered noise target: excludes a frame noise target (-noise) and adaptive sampling: one stop rule per frame";
+    if (to_filtered && gl_model) return "filtered noise target: not available with GL shading";
+    if (to_filtered && !(g_core.set_halves && g_core.atrous_halves)) return "filtered noise target: libptcore.so lacks pt_set_halves / pt_atrous_halves";
+    if (g_core.set_halves && g_core.set_halves(g_ctx, to_filtered ? 1 : 0) != PT_OK) return std::string("pt_set_halves: ") + g_core.last_error();
     int features = g_features >= 0 ? g_features : FeaturesFromEnv();
     if (features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path), else off
         features = 0;
@@ -522,7 +553,29 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     int32_t spp_done = cfg.SamplesPerPx > 0 ? cfg.SamplesPerPx : 0;
     pt_noise nz;
     std::memset(&nz, 0, sizeof nz);
-    if (to_noise) {  // render until the noise target, SamplesPerPx as the cap; the check follows every step
+    pt_halves_stats hs;
+    std::memset(&hs, 0, sizeof hs);
+    if (to_filtered) {  // render until the measured noise of the filtered frame is at the target, SamplesPerPx as the cap
+        if (g_core.begin(g_ctx, &flat.sc, &pc) != PT_OK) return std::string("pt_begin: ") + g_core.last_error();
+        const pt_atrous_config ac = {atrous_iters, 0, 4.0, 0.1, 0.1, 0.2};
+        int32_t done = 0;
+        while (err.empty() && done < cfg.SamplesPerPx) {
+            const int32_t left = cfg.SamplesPerPx - done;
+            if (g_core.step(g_ctx, noise_step < left ? noise_step : left, &done) != PT_OK) { err = std::string("pt_step: ") + g_core.last_error(); break; }
+            if (progress) {
+                if (g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK) { err = std::string("pt_read: ") + g_core.last_error(); break; }
+                progress();
+            }
+            if (done < 4) continue;  // each half needs two samples for its variance
+            if (g_core.atrous_halves(g_ctx, &ac, nullptr, nullptr, nullptr, &hs) != PT_OK) { err = std::string("pt_atrous_halves: ") + g_core.last_error(); break; }
+            if (hs.noise <= filtered_target) break;
+        }
+        if (err.empty() && (!progress || cfg.SamplesPerPx <= 0) && g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK)
+            err = std::string("pt_read: ") + g_core.last_error();
+        if (g_core.end(g_ctx, &st) != PT_OK && err.empty()) err = std::string("pt_end: ") + g_core.last_error();
+        if (err.empty() && progress) progress();
+        spp_done = done;
+    } else if (to_noise) {  // render until the noise target, SamplesPerPx as the cap; the check follows every step
         if (g_core.begin(g_ctx, &flat.sc, &pc) != PT_OK) return std::string("pt_begin: ") + g_core.last_error();
         int32_t done = 0;
         while (err.empty() && done < cfg.SamplesPerPx) {
@@ -572,6 +625,9 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         stats->atrous_ms = ats.atrous_ms;
         stats->noise_before = ats.noise_before;
         stats->noise_after = ats.noise_after;
+        stats->to_filtered_noise = to_filtered;
+        stats->filtered_noise = hs.noise;
+        stats->noise_model = hs.noise_model;
         stats->samples = st.samples; stats->segments = st.segments; stats->exit_scans = st.exit_scans; stats->draws = st.draws;
         stats->seconds = st.seconds; stats->trace_ms = st.trace_ms; stats->resolve_ms = st.resolve_ms;
         stats->device_ms = st.device_ms; stats->num_devices = st.num_devices; stats->spp_chunk = st.spp_chunk;

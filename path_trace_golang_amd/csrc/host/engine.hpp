@@ -42,6 +42,8 @@ struct Stats {
     bool atrous = false;   // the image is the a-trous filtered one (SetAtrous); noise_before / noise_after are pt_atrous_stats' figures
     int features = 0;      // feature samples per pixel the frame collected (pt_set_features)
     double atrous_ms = 0, noise_before = 0, noise_after = 0;
+    bool to_filtered_noise = false;  // the stop rule was the measured noise of the filtered frame (SetFilteredNoise); spp_done is the count
+    double filtered_noise = 0, noise_model = 0;  // pt_halves_stats' noise and noise_model at the last check (0: no check ran)
 };
 
 namespace hip {
@@ -82,6 +84,14 @@ int GetAtrousIterations();
 void AtrousFromEnv(bool &on, int &iterations);  // PATHTRACER_GPU_ATROUS = 1 / true / on / yes, _ITERS = int 0..6 (else 5)
 // First-hit feature planes (pt_set_features): k feature samples per pixel; k < 0 = not said (PATHTRACER_GPU_FEATURES, and without
 // it 4 under the filter where the scene allows features -- not with GL shading or on the BVH path -- else 0).
+// A noise target on the filtered frame: with the filter on and target > 0, the frame collects the half-buffer sums
+// (pt_set_halves), samples are added GetNoiseStep() at a time, after every step with at least 4 samples done pt_atrous_halves runs
+// with the filter's configuration, and the frame stops at the first check whose measured noise is at or below target, SamplesPerPx
+// being the cap.  The image is pt_atrous on the full sums.  Ignored without the filter; a frame noise target (SetNoiseTarget) or
+// GL shading beside it is an error.  The initial value is PATHTRACER_GPU_FILTERED_NOISE (FilteredNoiseFromEnv).
+void SetFilteredNoise(double target);
+double GetFilteredNoise();
+double FilteredNoiseFromEnv();  // PATHTRACER_GPU_FILTERED_NOISE = float > 0, else 0: off
 void SetFeatures(int k);
 int GetFeatures();     // -1: not said
 int FeaturesFromEnv(); // PATHTRACER_GPU_FEATURES = int >= 0, else -1

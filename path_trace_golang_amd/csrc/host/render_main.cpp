@@ -15,7 +15,9 @@
 // samples its block got; -min-spp N samples every block at least N times first (also env PATHTRACER_GPU_ADAPTIVE, _MIN_SPP).
 // -atrous writes the variance-guided a-trous filtered image (pt_atrous) instead of the plain finish, -atrous-iters N
 // (0..6) sets its iterations and -features K the first-hit feature samples per pixel that guide it (default: 4 where the scene allows
-// them; also env PATHTRACER_GPU_ATROUS, PATHTRACER_GPU_ATROUS_ITERS, PATHTRACER_GPU_FEATURES).
+// them; also env PATHTRACER_GPU_ATROUS, PATHTRACER_GPU_ATROUS_ITERS, PATHTRACER_GPU_FEATURES).  -filtered-noise T (with -atrous)
+// renders until the measured noise of the filtered frame (pt_atrous_halves) is at or below T, checking every -noise-step
+// samples, with -spp as the cap (also env PATHTRACER_GPU_FILTERED_NOISE); it excludes -noise.
 #include <cerrno>
 #include <chrono>
 #include <cstdarg>
@@ -65,6 +67,7 @@ struct Flags {
     bool atrous = false;
     int atrous_iters = 5;
     int features = -1;  // -1: not said
+    double filtered_noise = 0;
 };
 
 void usage() {
@@ -77,6 +80,8 @@ void usage() {
                  "  -devices int\n    \tnumber of GPUs to tile the image over (default 1)\n"
                  "  -features int\n    \tfirst-hit feature samples per pixel (default: 4 with -atrous where the scene allows them, else 0; or\n"
                  "    \tPATHTRACER_GPU_FEATURES)\n"
+                 "  -filtered-noise float\n    \twith -atrous: render until the measured noise of the filtered frame (DESIGN 3.12) is at or below this\n"
+                 "    \ttarget, checking every -noise-step samples, -spp being the cap (default 0 = off, or PATHTRACER_GPU_FILTERED_NOISE)\n"
                  "  -fog\n    \tdraw the scene's fog block like the reference's GPU backend (default false, or PATHTRACER_GPU_FOG)\n"
                  "  -gpu\n    \tuse GPU backend for rendering (if available)\n"
                  "  -headless\n    \trender without UI and save PNG\n"
@@ -127,7 +132,7 @@ int parse(int argc, char **argv, Flags &f) {
             (name == "gpu" ? f.gpu : name == "headless" ? f.headless : name == "fog" ? f.fog : name == "adaptive" ? f.adaptive : name == "atrous" ? f.atrous : f.scene_settings) = b;
             continue;
         }
-        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading", "noise", "noise-step", "min-spp", "atrous-iters", "features"};
+        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading", "noise", "noise-step", "min-spp", "atrous-iters", "features", "filtered-noise"};
         bool ok = false;
         for (const char *k : known) ok = ok || name == k;
         if (!ok) {
@@ -154,16 +159,16 @@ int parse(int argc, char **argv, Flags &f) {
             }
             f.shading = val;
         }
-        else if (name == "noise") {
+        else if (name == "noise" || name == "filtered-noise") {
             char *end = nullptr;
             errno = 0;
             const double v = std::strtod(val.c_str(), &end);
             if (errno || end == val.c_str() || *end || !(v >= 0)) {
-                std::fprintf(stderr, "invalid value \"%s\" for flag -noise: parse error\n", val.c_str());
+                std::fprintf(stderr, "invalid value \"%s\" for flag -%s: parse error\n", val.c_str(), name.c_str());
                 usage();
                 return 2;
             }
-            f.noise = v;
+            (name == "noise" ? f.noise : f.filtered_noise) = v;
         }
         else {
             char *end = nullptr;
@@ -210,6 +215,8 @@ int render_headless(const Flags &f) {
     engine::hip::SetAdaptive(f.adaptive, f.min_spp);
     engine::hip::SetAtrous(f.atrous, f.atrous_iters);
     engine::hip::SetFeatures(f.features);
+    engine::hip::SetFilteredNoise(f.filtered_noise);
+    if (f.filtered_noise > 0 && !f.atrous) logf("filtered-noise: no -atrous given, nothing to measure (a plain frame)");
     if (f.adaptive && !(f.noise > 0)) logf("adaptive: no -noise target given, nothing to adapt to (a plain frame)");
     if (f.shading == "gl") logf("shading: gl (the reference's GPU shader; spp counts passes of 16 paths)");
     if (f.fog) logf("fog: drawing the scene's fog block (%s)", sc->FogPtr ? "present" : "absent: nothing to draw");
@@ -232,6 +239,10 @@ int render_headless(const Flags &f) {
                  "frame noise %.6g), depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, %.1f M samples/s", cfg.Width, cfg.Height, st.spp_min,
                  st.spp_done, cfg.SamplesPerPx, f.noise, (unsigned long long)st.active_blocks, (unsigned long long)st.blocks, st.noise,
                  cfg.MaxDepth, st.num_devices, dt, st.segments / dt / 1e6, st.samples / dt / 1e6);
+        else if (st.to_filtered_noise)
+            logf("rendered %dx%d, %d of at most %d spp (filtered noise %.6g measured, %.6g propagated, target %.6g), depth %d on %d GPU(s) in "
+                 "%.3f s: %.1f M segments/s, %.1f M samples/s", cfg.Width, cfg.Height, st.spp_done, cfg.SamplesPerPx, st.filtered_noise,
+                 st.noise_model, f.filtered_noise, cfg.MaxDepth, st.num_devices, dt, st.segments / dt / 1e6, st.samples / dt / 1e6);
         else if (f.noise > 0)
             logf("rendered %dx%d, %d of at most %d spp (noise %.6g, target %.6g), depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, "
                  "%.1f M samples/s", cfg.Width, cfg.Height, st.spp_done, cfg.SamplesPerPx, st.noise, f.noise, cfg.MaxDepth, st.num_devices, dt,
@@ -264,6 +275,7 @@ int main(int argc, char **argv) {
     engine::hip::AdaptiveFromEnv(f.adaptive, f.min_spp);
     engine::hip::AtrousFromEnv(f.atrous, f.atrous_iters);
     f.features = engine::hip::FeaturesFromEnv();
+    f.filtered_noise = engine::hip::FilteredNoiseFromEnv();
     int rc = parse(argc, argv, f);
     if (rc >= 0) return rc;
     logf("flags: scene=%s mode=%s headless=%s out=%s", f.scene.c_str(), f.mode.c_str(), f.headless ? "true" : "false",

@@ -42,6 +42,21 @@
 //   Noise figure of a state (c, var): sqrt(sum over the pixels of e2 / pixels), e2 = var / den^2, den = l < 0.01 ? 0.01 : l; a NaN or
 //          infinite e2 adds 0.  Before the first iteration this is pt_noise_estimate's figure.  (The order of that one sum is the
 //          reduction tree's, not specified here: compare to 1e-9.)
+//
+// HALVES (pt_set_halves, pt_atrous_halves).  Sample s of a pixel (its 0-based index within the pixel) belongs to half A when s is even
+// and to half B when it is odd.  Per pixel and channel four raw sums, each added in sample order from zero: SA = sum of L and
+// QA = sum of L*L over A, SB and QB over B, L the radiance record the frame's sum adds (after the fog term).  With the pixel's own
+// count n: nA = (n + 1) / 2 and nB = n / 2 in integer division; every pixel holds n >= 4.
+//   Each half is a frame of its own:  fA, varA' = FILTER (prep, T iterations) on (SA, QA, nA) and the frame's feature sums,
+//          fB, varB' = FILTER on (SB, QB, nB) and the same feature sums.  A pixel can be bad in one half only; a half passes its own
+//          bad pixels through and skips them as taps, exactly as FILTER says.
+//   Combine, per pixel:  mean_k = (fA_k + fB_k) * 0.5;  d_k = (fA_k - fB_k) * 0.5;  err = (d_r*d_r + d_g*d_g + d_b*d_b) / 3;
+//          l = (mean_r + mean_g + mean_b) / 3;  den = l < 0.01 ? 0.01 : l;  e2 = err / (den * den);
+//          e2_model = ((varA' + varB') * 0.25) / (den * den).
+//          err is a one-degree-of-freedom estimate of the variance of mean: meaningful only averaged over many pixels.
+//   Figures:  noise = sqrt(sum of e2 / pixels), noise_model = sqrt(sum of e2_model / pixels).  A pixel that is bad in either half, or
+//          whose e2 is NaN or infinite, adds 0 to both sums and is counted as bad; a NaN or infinite e2_model adds 0.  (The order of
+//          the two sums is the reduction tree's: compare to 1e-9.)  Neither figure sees the bias the filter adds.
 #pragma once
 
 #include <stdint.h>
@@ -213,6 +228,118 @@ PT_HD double noise_term(const double c[3], double var) {
     if (den < 0.01) den = 0.01;
     const double e2 = var / (den * den);
     return finite(e2) ? e2 : 0.0;
+}
+
+// ---------------------------------------------------------------- pair filter (HALVES above)
+
+// The plane-per-component layout of the pair filter, np = W * H doubles per plane: neighbouring pixels are neighbouring words.
+//   guide [8][np]: N.x, N.y, N.z, A.r, A.g, A.b, z and the bad mask as a double (0 good, 1 bad in half A, 2 bad in half B, 3 in both)
+//   col   [6][np]: half A's r, g, b, then half B's;   var [2][np]: half A's, half B's
+#define PTA_GUIDE_PLANES 8
+#define PTA_GUIDE_Z 6
+#define PTA_GUIDE_BAD 7
+
+// Prep of one pixel of both halves: the four raw sums, cnt = the pixel's own count (>= 2; nA = (cnt + 1) / 2, nB = cnt / 2), the feature
+// sums or null -> plane element i of guide, col and var.
+PT_HD void prep_pair_pixel(const double SA[3], const double QA[3], const double SB[3], const double QB[3], uint32_t cnt, const double *fn,
+                           const double *fa, const double *fd, size_t np, size_t i, double *guide, double *col, double *var) {
+    double c[3], v;
+    Guide g, gb;
+    prep_pixel(SA, QA, (cnt + 1u) / 2u, fn, fa, fd, c, v, g);
+    for (int k = 0; k < 3; k++) col[(size_t)k * np + i] = c[k];
+    var[i] = v;
+    prep_pixel(SB, QB, cnt / 2u, fn, fa, fd, c, v, gb);  // (the same N, A and z: they do not depend on the radiance sums)
+    for (int k = 0; k < 3; k++) col[(size_t)(3 + k) * np + i] = c[k];
+    var[np + i] = v;
+    for (int k = 0; k < 3; k++) { guide[(size_t)k * np + i] = g.n[k]; guide[(size_t)(3 + k) * np + i] = g.a[k]; }
+    guide[(size_t)PTA_GUIDE_Z * np + i] = g.z;
+    guide[(size_t)PTA_GUIDE_BAD * np + i] = g.bad + 2.0 * gb.bad;
+}
+
+// One iteration of both halves at pixel (x, y): filter_pixel on half A and on half B, bit for bit, with the guide record of a tap
+// loaded once and the three feature terms computed once.  co = half A's c' then half B's, vo = the two var'.
+PT_HD void filter_pair_pixel(const Params &P, int32_t W, int32_t H, int32_t x, int32_t y, int32_t step, const double *__restrict__ col,
+                             const double *__restrict__ var, const double *__restrict__ guide, double co[6], double vo[2]) {
+    const size_t np = (size_t)W * (size_t)H;
+    const size_t i = (size_t)y * (size_t)W + (size_t)x;
+    const int badi = (int)guide[(size_t)PTA_GUIDE_BAD * np + i];
+    double ci[6], vi[2];
+    for (int k = 0; k < 6; k++) co[k] = ci[k] = col[(size_t)k * np + i];
+    vo[0] = vi[0] = var[i];
+    vo[1] = vi[1] = var[np + i];
+    if (badi == 3) return;
+    const double gin0 = guide[i], gin1 = guide[np + i], gin2 = guide[2 * np + i];
+    const double gia0 = guide[3 * np + i], gia1 = guide[4 * np + i], gia2 = guide[5 * np + i];
+    const double giz = guide[(size_t)PTA_GUIDE_Z * np + i];
+    const double li[2] = {(ci[0] + ci[1] + ci[2]) / 3.0, (ci[3] + ci[4] + ci[5]) / 3.0};
+    const double den_l[2] = {P.sigma_l * ptm::f_sqrt(vi[0]) + 1e-8, P.sigma_l * ptm::f_sqrt(vi[1]) + 1e-8};
+    const double den_z = P.sigma_z * (giz > 1e-8 ? giz : 1e-8);
+    const double den_a = P.sigma_a * P.sigma_a;
+    const double B[5] = {0.0625, 0.25, 0.375, 0.25, 0.0625};
+    double sw[2] = {0.0, 0.0}, sv[2] = {0.0, 0.0}, sd[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int dy = -2; dy <= 2; dy++) {
+        const int32_t yj = y + dy * step;
+        if (yj < 0 || yj >= H) continue;
+        for (int dx = -2; dx <= 2; dx++) {
+            const int32_t xj = x + dx * step;
+            if (xj < 0 || xj >= W) continue;
+            const size_t j = (size_t)yj * (size_t)W + (size_t)xj;
+            const int skip = (int)guide[(size_t)PTA_GUIDE_BAD * np + j] | badi;  // bit h: the tap does not count in half h
+            if (skip == 3) continue;
+            double tn = 0.0, tz = 0.0, ta = 0.0;  // the feature terms, the same in both halves
+            if (P.n_on) {
+                const double q = 1.0 - (gin0 * guide[j] + gin1 * guide[np + j] + gin2 * guide[2 * np + j]);
+                tn = (q > 0.0 ? q : 0.0) / P.sigma_n;
+            }
+            if (P.z_on) tz = ptm::f_abs(giz - guide[(size_t)PTA_GUIDE_Z * np + j]) / den_z;
+            if (P.a_on) {
+                const double dr = gia0 - guide[3 * np + j], dg = gia1 - guide[4 * np + j], db = gia2 - guide[5 * np + j];
+                ta = (dr * dr + dg * dg + db * db) / den_a;
+            }
+            const double b = B[dy + 2] * B[dx + 2];
+            for (int h = 0; h < 2; h++) {
+                if (skip & (1 << h)) continue;
+                const double cj0 = col[(size_t)(3 * h) * np + j], cj1 = col[(size_t)(3 * h + 1) * np + j], cj2 = col[(size_t)(3 * h + 2) * np + j];
+                const double lj = (cj0 + cj1 + cj2) / 3.0;
+                double pen = ptm::f_abs(li[h] - lj) / den_l[h];
+                if (P.n_on) pen = pen + tn;  // ((lum + n) + z) + a, the order of filter_pixel
+                if (P.z_on) pen = pen + tz;
+                if (P.a_on) pen = pen + ta;
+                if (pen > PTA_PEN_CUT) continue;
+                const double w = b * ptm::go_exp(-pen);
+                sw[h] = sw[h] + w;
+                sd[3 * h] = sd[3 * h] + w * (cj0 - ci[3 * h]);
+                sd[3 * h + 1] = sd[3 * h + 1] + w * (cj1 - ci[3 * h + 1]);
+                sd[3 * h + 2] = sd[3 * h + 2] + w * (cj2 - ci[3 * h + 2]);
+                sv[h] = sv[h] + (w * w) * var[(size_t)h * np + j];
+            }
+        }
+    }
+    for (int h = 0; h < 2; h++) {
+        if (badi & (1 << h)) continue;
+        for (int k = 0; k < 3; k++) co[3 * h + k] = ci[3 * h + k] + sd[3 * h + k] / sw[h];
+        vo[h] = sv[h] / (sw[h] * sw[h]);
+    }
+}
+
+// The combine of one pixel: fA, fB the filtered halves, va, vb their propagated variances, bad = the pixel's bad mask -> mean, err and
+// the two noise terms (measured, model).  Returns whether the pixel counts as bad; a term that adds nothing is returned as 0.
+PT_HD bool combine_pixel(const double fA[3], const double fB[3], double va, double vb, int bad, double mean[3], double &err, double &e2,
+                         double &e2_model) {
+    double d[3];
+    for (int k = 0; k < 3; k++) {
+        mean[k] = (fA[k] + fB[k]) * 0.5;
+        d[k] = (fA[k] - fB[k]) * 0.5;
+    }
+    err = (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) / 3.0;
+    const double l = (mean[0] + mean[1] + mean[2]) / 3.0;
+    const double den = l < 0.01 ? 0.01 : l;
+    e2 = err / (den * den);
+    e2_model = ((va + vb) * 0.25) / (den * den);
+    const bool isbad = bad != 0 || !finite(e2);
+    if (isbad) e2 = 0.0;
+    if (isbad || !finite(e2_model)) e2_model = 0.0;
+    return isbad;
 }
 
 }  // namespace pta

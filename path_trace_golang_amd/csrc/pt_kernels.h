@@ -47,6 +47,10 @@
 //                   the chunk's samples with index below k (pt_atrous.h), beside fog_kernel.
 //   atrous_prep_kernel / atrous_kernel / atrous_noise_kernel / atrous_finish_kernel   pt_atrous: the variance-guided a-trous
 //                   filter of pt_atrous.h over the gathered row-major planes on devices[0].
+//   halves_kernel   opt-in (pt_set_halves): per pixel slot the running sums of the radiances and of their squares over the even-
+//                   and over the odd-indexed samples, after moments_kernel.
+//   atrous_pair_prep_kernel / atrous_pair_kernel / halves_combine_kernel   pt_atrous_halves: the filter on each half, both halves
+//                   in one launch over plane-per-component buffers, and the measured noise figure of their mean.
 //
 // FP64 throughout; built with -ffp-contract=off so every product and sum rounds
 // exactly as the reference's Go code does on amd64.
@@ -2918,6 +2922,70 @@ __global__ __launch_bounds__(PT_BLOCK) void moments_kernel(const MomentsArgs M) 
 
 __global__ __launch_bounds__(PT_BLOCK) void moments_adaptive_kernel(const MomentsArgs M, const AdaptTable T) { moments_body<true>(M, T); }
 
+// Half-buffer sums (pt_set_halves, pt_atrous.h HALVES): per accumulation slot twelve running sums -- SA, QA, SB, QB, three channels
+// each -- of the radiances and their squares over the slot's even-indexed (A) and odd-indexed (B) samples.  The walk of moments_kernel:
+// one lane per slot, the chunk's records in sample order, right after the chunk's resolve add.  Record s of the chunk is sample
+// s0 + s of its pixel -- in adaptive frames too, where every active block holds s0 samples -- so the half is wave-uniform.
+// finish = 1 writes plane `which` (0 SA, 1 QA, 2 SB, 3 QB) tile-major with zeros outside the frame, the layout of tiles_accum.
+struct HalvesArgs {
+    const double *L;         // [njobs][4]: r, g, b, 0
+    double *hv;              // [12][nslots]: SA, QA, SB, QB, three channel planes each
+    double *tiles;           // [nlocal][32][32][3] or null (no finish)
+    uint32_t nslots;         // nlocal*1024
+    uint32_t S, s0;          // the chunk's samples, and the index of its first one
+    int32_t first;           // 1: the running sums start at zero
+    int32_t finish;          // 1: write plane `which` to tiles
+    int32_t have_chunk;      // 0: no chunk to add (pure finish)
+    uint32_t which;
+    TileGeom G;
+};
+
+template <bool ADAPT>
+__device__ __forceinline__ void halves_body(const HalvesArgs &A, const AdaptTable &T) {
+    uint32_t slot, cblk;
+    if (!chunk_slot<ADAPT>(A.have_chunk, T, A.nslots, slot, cblk)) return;
+    const uint32_t p = slot & 63u;
+    const Pixel px = slot_pixel(A.G, slot);
+    const bool inside = px.inside;
+    const size_t ns = A.nslots;
+    if (A.have_chunk && inside) {
+        double sa[3] = {0, 0, 0}, qa[3] = {0, 0, 0}, sb[3] = {0, 0, 0}, qb[3] = {0, 0, 0};
+        if (!A.first)
+            for (uint32_t c = 0; c < 3u; c++) {
+                sa[c] = A.hv[c * ns + slot];
+                qa[c] = A.hv[(3u + c) * ns + slot];
+                sb[c] = A.hv[(6u + c) * ns + slot];
+                qb[c] = A.hv[(9u + c) * ns + slot];
+            }
+        const size_t base = (size_t)cblk * A.S * 64u + p;
+        for (uint32_t s = 0; s < A.S; s++) {  // in sample order, like the sum itself
+            const double4 l = reinterpret_cast<const double4 *>(A.L)[base + (size_t)s * 64u];
+            if (((A.s0 + s) & 1u) == 0u) {
+                sa[0] += l.x; sa[1] += l.y; sa[2] += l.z;
+                qa[0] += l.x * l.x; qa[1] += l.y * l.y; qa[2] += l.z * l.z;
+            } else {
+                sb[0] += l.x; sb[1] += l.y; sb[2] += l.z;
+                qb[0] += l.x * l.x; qb[1] += l.y * l.y; qb[2] += l.z * l.z;
+            }
+        }
+        for (uint32_t c = 0; c < 3u; c++) {
+            A.hv[c * ns + slot] = sa[c];
+            A.hv[(3u + c) * ns + slot] = qa[c];
+            A.hv[(6u + c) * ns + slot] = sb[c];
+            A.hv[(9u + c) * ns + slot] = qb[c];
+        }
+    }
+    if (A.finish) {
+        const size_t pix = px.pix;
+        const bool have = inside && !A.first;
+        for (uint32_t c = 0; c < 3u; c++) A.tiles[3 * pix + c] = have ? A.hv[(3u * A.which + c) * ns + slot] : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(PT_BLOCK) void halves_kernel(const HalvesArgs A) { halves_body<false>(A, AdaptTable{nullptr, nullptr, 0u}); }
+
+__global__ __launch_bounds__(PT_BLOCK) void halves_adaptive_kernel(const HalvesArgs A, const AdaptTable T) { halves_body<true>(A, T); }
+
 // Frame noise (pt_noise_estimate, the metric of include/ptcore.h): per slot inside the frame, with n samples done, sums S
 // (resolve_kernel's) and Q (moments_kernel's):
 //   m_c = S_c / n,  v_c = max(0, Q_c / n - m_c * m_c) / (n - 1),  e2 = ((v_r + v_g + v_b) / 3) / max((m_r + m_g + m_b) / 3, 0.01)^2
@@ -3392,6 +3460,105 @@ __global__ __launch_bounds__(PT_BLOCK) void atrous_finish_kernel(const double *_
     if (i >= npix) return;
     const double c[3] = {col[3 * (size_t)i], col[3 * (size_t)i + 1], col[3 * (size_t)i + 2]};
     reinterpret_cast<uint32_t *>(rgba)[i] = pta::finish_pack(c);
+}
+
+// pt_atrous_halves (pt_atrous.h HALVES): the filter on each half of the samples and the combine, over plane-per-component buffers on
+// devices[0] -- guide [8][npix], colour [6][npix] (half A's r, g, b, then half B's) and variance [2][npix], the last two ping-pong --
+// so that the lanes of a wave read neighbouring words of every plane.  One thread per pixel, both halves in it: a tap's guide
+// values are loaded once and its feature terms computed once for the two halves.
+struct AtrousPairPrepArgs {
+    const double *sa, *qa, *sb, *qb;  // [npix][3] the four raw sums
+    const uint32_t *cnt;              // [npix] the pixel's own count (adaptive frames) or null: n
+    const double *fn, *fa, *fd;       // [npix][3] feature sums, or null (no features)
+    double *guide, *col, *var;        // [8][npix], [6][npix], [2][npix]
+    uint32_t npix, n;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void atrous_pair_prep_kernel(const AtrousPairPrepArgs A) {
+    const uint32_t i = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (i >= A.npix) return;
+    const size_t i3 = 3 * (size_t)i;
+    const double SA[3] = {A.sa[i3], A.sa[i3 + 1], A.sa[i3 + 2]}, QA[3] = {A.qa[i3], A.qa[i3 + 1], A.qa[i3 + 2]};
+    const double SB[3] = {A.sb[i3], A.sb[i3 + 1], A.sb[i3 + 2]}, QB[3] = {A.qb[i3], A.qb[i3 + 1], A.qb[i3 + 2]};
+    pta::prep_pair_pixel(SA, QA, SB, QB, A.cnt ? A.cnt[i] : A.n, A.fn ? A.fn + i3 : nullptr, A.fa ? A.fa + i3 : nullptr,
+                         A.fd ? A.fd + i3 : nullptr, A.npix, i, A.guide, A.col, A.var);
+}
+
+struct AtrousPairArgs {
+    pta::Params P;
+    const double *col, *var;   // the iteration's input
+    const double *guide;
+    double *col_out, *var_out;
+    int32_t W, H, step;
+};
+
+// One iteration of both halves; the block shape of atrous_kernel (32 x 8 pixels, a wave = two rows of 32).
+__global__ __launch_bounds__(PT_BLOCK) void atrous_pair_kernel(const AtrousPairArgs A) {
+    const int32_t x = (int32_t)(blockIdx.x * 32u + (threadIdx.x & 31u));
+    const int32_t y = (int32_t)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    if (x >= A.W || y >= A.H) return;
+    double c[6], v[2];
+    pta::filter_pair_pixel(A.P, A.W, A.H, x, y, A.step, A.col, A.var, A.guide, c, v);
+    const size_t np = (size_t)A.W * (size_t)A.H, i = (size_t)y * (size_t)A.W + (size_t)x;
+    for (int k = 0; k < 6; k++) A.col_out[(size_t)k * np + i] = c[k];
+    A.var_out[i] = v[0];
+    A.var_out[np + i] = v[1];
+}
+
+// The block's partial sums of the two figures of pt_atrous_halves over noise_kernel's tree, and its bad pixels.
+struct HalvesPartial {
+    double sum, sum_model;
+    unsigned long long bad;
+};
+
+struct HalvesCombineArgs {
+    const double *col, *var, *guide;  // the planes of the last iteration
+    double *mean;                     // [npix][3] row-major, like accum
+    double *err;                      // [npix]
+    double *half_means;               // [2][npix][3] fA then fB, or null
+    HalvesPartial *partial;           // [gridDim.x]
+    uint32_t npix;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void halves_combine_kernel(const HalvesCombineArgs A) {
+    __shared__ double s_sum[PT_BLOCK / PT_WAVE], s_mod[PT_BLOCK / PT_WAVE];
+    __shared__ uint32_t s_bad[PT_BLOCK / PT_WAVE];
+    const uint32_t i = blockIdx.x * PT_BLOCK + threadIdx.x;
+    double sum = 0.0, mod = 0.0;
+    uint32_t bad = 0;
+    if (i < A.npix) {
+        const size_t np = A.npix;
+        const double fA[3] = {A.col[i], A.col[np + i], A.col[2 * np + i]}, fB[3] = {A.col[3 * np + i], A.col[4 * np + i], A.col[5 * np + i]};
+        double mean[3], err;
+        bad = pta::combine_pixel(fA, fB, A.var[i], A.var[np + i], (int)A.guide[(size_t)PTA_GUIDE_BAD * np + i], mean, err, sum, mod) ? 1u : 0u;
+        for (int k = 0; k < 3; k++) A.mean[3 * (size_t)i + k] = mean[k];
+        A.err[i] = err;
+        if (A.half_means)
+            for (int k = 0; k < 3; k++) {
+                A.half_means[3 * (size_t)i + k] = fA[k];
+                A.half_means[3 * (np + i) + k] = fB[k];
+            }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off, 64);
+        mod += __shfl_xor(mod, off, 64);
+        bad += __shfl_xor(bad, off, 64);
+    }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) {
+        s_sum[wave] = sum;
+        s_mod[wave] = mod;
+        s_bad[wave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        HalvesPartial r;
+        r.sum = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+        r.sum_model = ((s_mod[0] + s_mod[1]) + s_mod[2]) + s_mod[3];
+        r.bad = 0;
+        for (int w = 0; w < PT_BLOCK / PT_WAVE; w++) r.bad += s_bad[w];
+        A.partial[blockIdx.x] = r;
+    }
 }
 
 // The fog's in-scatter term (pt_fog.h) of every job of a chunk, added in place to the job's radiance record after the chunk's

@@ -130,7 +130,7 @@ struct EventList {
     }
     void swap(EventList &o) { v.swap(o.v); std::swap(n, o.n); }
 };
-enum EventKind { EV_TRACE, EV_RESOLVE, EV_RAYGEN, EV_GLASS, EV_FOG, EV_MOMENTS, EV_CHECK, EV_FEATURE, EV_KINDS };
+enum EventKind { EV_TRACE, EV_RESOLVE, EV_RAYGEN, EV_GLASS, EV_FOG, EV_MOMENTS, EV_CHECK, EV_FEATURE, EV_HALVES, EV_KINDS };
 
 // Storage of one path-state queue (PathQueue, pt_device.h): per entry 10 doubles, the stream state and 4 words -- job, depth, hit
 // object, answer -- or 6 with pixel stats (+ the job's two counters); every plane of `u` is as long as the queue.
@@ -188,6 +188,8 @@ struct Device {
     DevBuf<ptk::NoisePartial> noise_part;  // pt_noise_estimate: one partial per block of noise_kernel
     DevBuf<double> feat;              // pt_set_features: [9][nslots] running first-hit feature sums (allocated only then)
     DevBuf<double> tiles_feat;        // ... and the tile-major copy of one plane of them for the gather
+    DevBuf<double> hv;                // pt_set_halves: [12][nslots] running half-buffer sums SA, QA, SB, QB (allocated only then)
+    DevBuf<double> tiles_hv;          // ... and the tile-major copy of one plane of them for the gather
     // pt_set_adaptive (allocated only then): the active list (two buffers, the check compacts from one into the other), the
     // samples per block, the check's per-block decision and noise, and the word the host reads back after every check
     DevBuf<uint32_t> act[2], blk_spp, blk_keep;
@@ -260,6 +262,7 @@ struct Frame {
     bool moments = false;  // pt_set_moments: moments_kernel runs after every chunk's resolve add (pt_begin / pt_render frames only)
     bool adaptive = false; // pt_set_adaptive: the frame's jobs are those of the active blocks, a check ends every pt_step (implies moments)
     pt_adaptive ad{};
+    bool halves = false;   // pt_set_halves: halves_kernel runs after every chunk's moments_kernel (pt_begin / pt_render frames only; implies moments)
     int32_t features = 0;  // pt_set_features: feature_kernel runs after the chunks that hold samples below this index (pt_begin / pt_render frames only)
     double worst_active = 0.0;  // largest block noise among the blocks the last check kept
     std::vector<ptg::GlObj> gl_objs;
@@ -319,6 +322,12 @@ struct pt_ctx {
     DevBuf<double> at_col[2], at_var[2];
     DevBuf<pta::Guide> at_guide;
     DevBuf<ptk::NoisePartial> at_part;
+    bool halves_on = false;           // pt_set_halves
+    DevBuf<double> g_tiles_hv, f_hv_sa, f_hv_qa, f_hv_sb, f_hv_qb;  // pt_read_halves / pt_atrous_halves: one gathered plane, the four row-major frames
+    // pt_atrous_halves (allocated on the first call): the guide planes, colour and variance planes of both halves (ping-pong), the
+    // combined mean, err and the two filtered halves row-major, the partials of the two figures
+    DevBuf<double> ah_guide, ah_col[2], ah_var[2], ah_mean, ah_err, ah_half;
+    DevBuf<ptk::HalvesPartial> ah_part;
     pt_adaptive adaptive{};
     DevBuf<uint32_t> f_seg, f_draw;
     size_t l_budget_bytes = (size_t)48 << 30;  // per-chunk job buffers (radiance, primary rays, path-state queues): a sixth of the 288 GB
@@ -1416,6 +1425,23 @@ int32_t step_accumulate(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeo
             }))
             return rc;
     }
+    if (fr.halves) {
+        ptk::HalvesArgs HA;
+        std::memset(&HA, 0, sizeof HA);
+        HA.L = d.L.p;
+        HA.hv = d.hv.p;
+        HA.nslots = d.nslots;
+        HA.S = F.S;
+        HA.s0 = F.s0;
+        HA.first = R.first;
+        HA.have_chunk = 1;
+        HA.G = G;
+        if (int32_t rc = timed(d, EV_HALVES, [&] {
+                if (fr.adaptive) hipLaunchKernelGGL(ptk::halves_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, HA, AT);
+                else hipLaunchKernelGGL(ptk::halves_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, HA);
+            }))
+            return rc;
+    }
     d.acc_started = true;
     return PT_OK;
 }
@@ -1544,6 +1570,25 @@ int32_t dev_finish_moments(pt_ctx *ctx, Device &d, double *tiles_m2) {
     M.finish = 1;
     M.G = tile_geom(fr, d);
     hipLaunchKernelGGL(ptk::moments_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, M);
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
+// Writes plane `which` (0 SA, 1 QA, 2 SB, 3 QB) of this device's half-buffer sums tile-major, the layout of tiles_accum.
+int32_t dev_finish_halves(pt_ctx *ctx, Device &d, uint32_t which, double *tiles) {
+    const Frame &fr = ctx->frame;
+    if (d.nlocal == 0) return PT_OK;
+    HIP_TRY(hipSetDevice(d.ordinal));
+    ptk::HalvesArgs HA;
+    std::memset(&HA, 0, sizeof HA);
+    HA.hv = d.hv.p;
+    HA.tiles = tiles;
+    HA.nslots = d.nslots;
+    HA.first = d.acc_started ? 0 : 1;
+    HA.finish = 1;
+    HA.which = which;
+    HA.G = tile_geom(fr, d);
+    hipLaunchKernelGGL(ptk::halves_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, HA);
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
@@ -2537,7 +2582,8 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
     if (int32_t rc = frame_open(ctx, scene, cfg, max_slots)) return rc;
     ctx->frame.adaptive = ctx->adaptive_on;
     ctx->frame.ad = ctx->adaptive;
-    ctx->frame.moments = ctx->moments_on || ctx->adaptive_on;
+    ctx->frame.halves = ctx->halves_on;
+    ctx->frame.moments = ctx->moments_on || ctx->adaptive_on || ctx->halves_on;
     if (ctx->features_k > 0) {  // refused before anything is launched; the context stays usable
         const bool bvh = ctx->frame.scan == ptk::SCAN_BVH || ctx->frame.scan == ptk::SCAN_VERIFY_BVH;
         if (bvh || ctx->frame.gl) {
@@ -2555,6 +2601,11 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
             hipError_t e = hipSetDevice(d.ordinal);
             if (e == hipSuccess) e = d.feat.reserve(9 * (size_t)d.nslots);
             if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("features: ") + hipGetErrorString(e));
+        }
+        if (rc == PT_OK && ctx->frame.halves && d.nlocal > 0) {  // outside PTCORE_L_BUDGET_MB, on the first frame that asks
+            hipError_t e = hipSetDevice(d.ordinal);
+            if (e == hipSuccess) e = d.hv.reserve(12 * (size_t)d.nslots);
+            if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("halves: ") + hipGetErrorString(e));
         }
         if (rc) {
             ctx->frame.open = false;
@@ -2660,6 +2711,7 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
     if (ctx->frame.moments && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_MOMENTS, "moments_kernel");
     if (ctx->frame.adaptive && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_CHECK, "adaptive check");
     if (ctx->frame.features > 0 && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_FEATURE, "feature_kernel");
+    if (ctx->frame.halves && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_HALVES, "halves_kernel");
     if (ctx->frame.fog_vol) {
         ctx->fog_pending = 1;
         if (int32_t r = collect_fog(ctx)) rc = rc != PT_OK ? rc : r;
@@ -3013,6 +3065,174 @@ int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32
     (void)hipEventDestroy(ev[1]);
     if (rc == PT_OK && std::getenv("PTCORE_VERBOSE"))
         std::fprintf(stderr, "ptcore: pt_atrous %d iterations, %.3f ms host wall (gathers included)\n", c.iterations,
+                     std::chrono::duration<double, std::milli>(clk::now() - t0).count());
+    return rc;
+}
+
+int32_t pt_set_halves(pt_ctx *ctx, int32_t on) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_halves while a frame is open");
+    ctx->halves_on = on != 0;
+    return PT_OK;
+}
+
+static int32_t halves_frame(pt_ctx *ctx, const char *who) {
+    if (int32_t rc = moments_frame(ctx, who)) return rc;
+    if (!ctx->frame.halves) return fail(PT_ERR_STATE, std::string(who) + ": the frame was rendered with halves off (pt_set_halves)");
+    return PT_OK;
+}
+
+// one plane of the half-buffer sums (0 SA, 1 QA, 2 SB, 3 QB) through the gather, into the context's row-major frame and, when asked for, to the host
+static int32_t gather_halves(pt_ctx *ctx, uint32_t which, double *host) {
+    static void *(*const frames[4])(pt_ctx &, size_t, hipError_t &) = {reserved<pt_ctx, &pt_ctx::f_hv_sa>, reserved<pt_ctx, &pt_ctx::f_hv_qa>,
+                                                                       reserved<pt_ctx, &pt_ctx::f_hv_sb>, reserved<pt_ctx, &pt_ctx::f_hv_qb>};
+    const Plane planes[] = {{true, PLANE_F64X3, reserved<Device, &Device::tiles_hv>, reserved<pt_ctx, &pt_ctx::g_tiles_hv>, frames[which], host, 0}};
+    return gather_planes(ctx, planes, [&](Device &d, void *const *dst) { return dev_finish_halves(ctx, d, which, static_cast<double *>(dst[0])); });
+}
+
+int32_t pt_read_halves(pt_ctx *ctx, double *sa, double *qa, double *sb, double *qb) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (int32_t rc = halves_frame(ctx, "pt_read_halves")) return rc;
+    double *const host[4] = {sa, qa, sb, qb};
+    for (uint32_t k = 0; k < 4u; k++)
+        if (host[k])
+            if (int32_t rc = gather_halves(ctx, k, host[k])) return rc;
+    return PT_OK;
+}
+
+int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean, double *err, double *half_means, pt_halves_stats *stats) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    pt_atrous_config c = {5, 0, 4.0, 0.1, 0.1, 0.2};
+    if (cfg) c = *cfg;
+    if (c.iterations < 0 || c.iterations > PTA_MAX_ITERATIONS) return fail(PT_ERR_INVALID, "pt_atrous_halves: iterations must be 0..6");
+    if (!(c.sigma_l > 0.0) || !(c.sigma_n >= 0.0) || !(c.sigma_z >= 0.0) || !(c.sigma_a >= 0.0))
+        return fail(PT_ERR_INVALID, "pt_atrous_halves: sigma_l must be > 0, sigma_n, sigma_z and sigma_a >= 0 (0 = term off)");
+    if (int32_t rc = halves_frame(ctx, "pt_atrous_halves")) return rc;
+    Frame &fr = ctx->frame;
+    if (fr.gl) return fail(PT_ERR_STATE, "pt_atrous_halves: not available for a frame rendered with GL shading (pt_set_shading)");
+    int32_t spp_min = fr.done_spp;  // the smallest count the frame holds: every half needs two samples for its variance
+    if (fr.adaptive) {
+        struct pt_adaptive_state as;
+        if (int32_t rc = pt_adaptive_state(ctx, &as)) return rc;
+        spp_min = as.spp_min;
+    }
+    if (spp_min < 4)
+        return fail(PT_ERR_STATE, "pt_atrous_halves: every pixel needs at least 4 samples (the frame's smallest count is " + std::to_string(spp_min) + ")");
+    const int32_t W = fr.cfg.width, H = fr.cfg.height;
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    // the inputs as row-major planes on devices[0], all reads: the four sums, the counts of an adaptive frame, the features of a frame that has them
+    for (uint32_t k = 0; k < 4u; k++)
+        if (int32_t rc = gather_halves(ctx, k, nullptr)) return rc;
+    if (fr.adaptive) {
+        const Plane planes[] = {
+            {true, PLANE_U32A, reserved<Device, &Device::tiles_seg>, reserved<pt_ctx, &pt_ctx::g_tiles_seg>, reserved<pt_ctx, &pt_ctx::f_seg>, nullptr, 0}};
+        if (int32_t rc = gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
+                hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p,
+                                   static_cast<uint32_t *>(dst[0]), d.nslots, tile_geom(fr, d));
+                HIP_TRY(hipGetLastError());
+                return PT_OK;
+            }))
+            return rc;
+    }
+    const bool feat = fr.features > 0;
+    if (feat)
+        for (uint32_t k = 0; k < 3u; k++)
+            if (int32_t rc = gather_feature(ctx, k, nullptr)) return rc;
+    Device &d0 = ctx->devs[0];
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    const size_t npix = (size_t)W * (size_t)H;
+    const uint32_t grid1 = (uint32_t)((npix + PT_BLOCK - 1) / PT_BLOCK);
+    for (int k = 0; k < 2; k++) {
+        HIP_TRY(ctx->ah_col[k].reserve(6 * npix));
+        HIP_TRY(ctx->ah_var[k].reserve(2 * npix));
+    }
+    HIP_TRY(ctx->ah_guide.reserve(PTA_GUIDE_PLANES * npix));
+    HIP_TRY(ctx->ah_mean.reserve(3 * npix));
+    HIP_TRY(ctx->ah_err.reserve(npix));
+    if (half_means) HIP_TRY(ctx->ah_half.reserve(6 * npix));
+    HIP_TRY(ctx->ah_part.reserve(grid1));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    HIP_TRY(hipEventCreate(&ev[0]));
+    if (hipError_t e = hipEventCreate(&ev[1]); e != hipSuccess) {
+        (void)hipEventDestroy(ev[0]);
+        return fail(PT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+    }
+    auto run = [&]() -> int32_t {
+        HIP_TRY(hipEventRecord(ev[0], d0.stream));
+        ptk::AtrousPairPrepArgs PA;
+        std::memset(&PA, 0, sizeof PA);
+        PA.sa = ctx->f_hv_sa.p; PA.qa = ctx->f_hv_qa.p; PA.sb = ctx->f_hv_sb.p; PA.qb = ctx->f_hv_qb.p;
+        PA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
+        PA.fn = feat ? ctx->f_feat_n.p : nullptr;
+        PA.fa = feat ? ctx->f_feat_a.p : nullptr;
+        PA.fd = feat ? ctx->f_feat_d.p : nullptr;
+        PA.guide = ctx->ah_guide.p;
+        PA.col = ctx->ah_col[0].p;
+        PA.var = ctx->ah_var[0].p;
+        PA.npix = (uint32_t)npix;
+        PA.n = (uint32_t)fr.done_spp;
+        hipLaunchKernelGGL(ptk::atrous_pair_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, PA);
+        ptk::AtrousPairArgs A;
+        std::memset(&A, 0, sizeof A);
+        A.P.sigma_l = c.sigma_l; A.P.sigma_n = c.sigma_n; A.P.sigma_z = c.sigma_z; A.P.sigma_a = c.sigma_a;
+        A.P.iterations = c.iterations;
+        A.P.n_on = feat && c.sigma_n > 0.0;
+        A.P.z_on = feat && c.sigma_z > 0.0;
+        A.P.a_on = feat && c.sigma_a > 0.0;
+        A.guide = ctx->ah_guide.p;
+        A.W = W;
+        A.H = H;
+        int cur = 0;
+        for (int32_t t = 0; t < c.iterations; t++, cur ^= 1) {
+            A.col = ctx->ah_col[cur].p; A.var = ctx->ah_var[cur].p;
+            A.col_out = ctx->ah_col[cur ^ 1].p; A.var_out = ctx->ah_var[cur ^ 1].p;
+            A.step = 1 << t;
+            hipLaunchKernelGGL(ptk::atrous_pair_kernel, dim3((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8)), dim3(PT_BLOCK), 0, d0.stream, A);
+        }
+        ptk::HalvesCombineArgs CA;
+        std::memset(&CA, 0, sizeof CA);
+        CA.col = ctx->ah_col[cur].p; CA.var = ctx->ah_var[cur].p; CA.guide = ctx->ah_guide.p;
+        CA.mean = ctx->ah_mean.p;
+        CA.err = ctx->ah_err.p;
+        CA.half_means = half_means ? ctx->ah_half.p : nullptr;
+        CA.partial = ctx->ah_part.p;
+        CA.npix = (uint32_t)npix;
+        hipLaunchKernelGGL(ptk::halves_combine_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, CA);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[1], d0.stream));
+        std::vector<ptk::HalvesPartial> part(grid1);
+        HIP_TRY(hipMemcpyAsync(part.data(), ctx->ah_part.p, part.size() * sizeof(ptk::HalvesPartial), hipMemcpyDeviceToHost, d0.stream));
+        if (mean) HIP_TRY(hipMemcpyAsync(mean, ctx->ah_mean.p, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+        if (err) HIP_TRY(hipMemcpyAsync(err, ctx->ah_err.p, npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+        if (half_means) HIP_TRY(hipMemcpyAsync(half_means, ctx->ah_half.p, 6 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+        HIP_TRY(hipStreamSynchronize(d0.stream));
+        if (stats) {
+            pt_halves_stats st;
+            std::memset(&st, 0, sizeof st);
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            st.atrous_ms = ms;
+            st.launches = c.iterations + 2;
+            st.iterations = c.iterations;
+            st.spp_min = spp_min;
+            double sum = 0.0, sum_model = 0.0;
+            for (const ptk::HalvesPartial &p : part) {  // partials in block order
+                sum += p.sum;
+                sum_model += p.sum_model;
+                st.bad_pixels += p.bad;
+            }
+            st.noise = std::sqrt(sum / (double)npix);
+            st.noise_model = std::sqrt(sum_model / (double)npix);
+            *stats = st;
+        }
+        return PT_OK;
+    };
+    const int32_t rc = run();
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    if (rc == PT_OK && std::getenv("PTCORE_VERBOSE"))
+        std::fprintf(stderr, "ptcore: pt_atrous_halves %d iterations, %.3f ms host wall (gathers included)\n", c.iterations,
                      std::chrono::duration<double, std::milli>(clk::now() - t0).count());
     return rc;
 }

@@ -62,7 +62,8 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 progress: Optional[Callable[[], None]] = None, shading: Optional[str] = None,
                 moments: Optional[np.ndarray] = None, noise: Optional[float] = None, noise_step: Optional[int] = None,
                 adaptive: Optional[bool] = None, min_spp: Optional[int] = None, counts: Optional[np.ndarray] = None,
-                features: Optional[int] = None, atrous: Optional["hip.AtrousConfig"] = None) -> dict:
+                features: Optional[int] = None, atrous: Optional["hip.AtrousConfig"] = None,
+                filtered_noise: Optional[float] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
@@ -71,7 +72,10 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     itself; None takes PATHTRACER_GPU_ADAPTIVE / PATHTRACER_GPU_ADAPTIVE_MIN_SPP (hip.AdaptiveConfig.from_env).  Without a
     noise target adaptive has nothing to adapt to and the frame is a plain one.  `features` and `atrous` are hip.render's as well
     (DESIGN 3.11): the first-hit feature samples per pixel and the a-trous filter that replaces the image; None takes
-    PATHTRACER_GPU_FEATURES and PATHTRACER_GPU_ATROUS / PATHTRACER_GPU_ATROUS_ITERS (hip.AtrousConfig.from_env), both off by default."""
+    PATHTRACER_GPU_FEATURES and PATHTRACER_GPU_ATROUS / PATHTRACER_GPU_ATROUS_ITERS (hip.AtrousConfig.from_env), both off by default.
+    `filtered_noise` is hip.render's: with the filter on, render until the measured noise of the filtered frame is at or
+    below it; None takes PATHTRACER_GPU_FILTERED_NOISE (hip.filtered_noise_from_env), off by default and ignored without the filter
+    or beside a noise target."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -88,9 +92,11 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
         atrous = hip.AtrousConfig.from_env()
     if features is None:
         features = hip.features_from_env()
+    if filtered_noise is None and atrous is not None and noise is None:
+        filtered_noise = hip.filtered_noise_from_env()
     return hip.render(sc, gcfg, img, progress, shading=model, features=features, atrous=atrous, moments=moments, noise=noise,
                       noise_step=noise_step if noise_step is not None else ncfg.step, adaptive=bool(adaptive) and noise is not None,
-                      min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts)
+                      min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts, filtered_noise=filtered_noise)
 
 
 def render(sc: scn.Scene, cfg: RenderConfig) -> np.ndarray:

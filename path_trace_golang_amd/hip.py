@@ -377,6 +377,68 @@ def atrous(ctx: capi.Context, cfg: Optional[AtrousConfig], img: Optional[np.ndar
 _atrous = atrous  # (`render` has an argument of that name)
 
 
+def set_halves(ctx: capi.Context, on: bool) -> None:
+    """pt_set_halves: later frames on ctx also collect the half-buffer sums SA, QA (even-indexed samples) and SB, QB (odd-indexed
+    ones) of every pixel; off by default.  Such frames collect second moments too."""
+    if not capi.has("pt_set_halves"):
+        if on:
+            raise RuntimeError("this libptcore.so has no pt_set_halves (rebuild it)")
+        return
+    capi.check(capi.load().pt_set_halves(ctx.handle, 1 if on else 0))
+
+
+def read_halves(ctx: capi.Context, sa: Optional[np.ndarray] = None, qa: Optional[np.ndarray] = None, sb: Optional[np.ndarray] = None,
+                qb: Optional[np.ndarray] = None) -> None:
+    """pt_read_halves into the arrays given (contiguous float64 [H, W, 3] each): the raw sums of the sample radiances and of
+    their squares over the even-indexed samples (sa, qa) and over the odd-indexed ones (sb, qb)."""
+    for a in (sa, qa, sb, qb):
+        if a is not None and (a.dtype != np.float64 or a.ndim != 3 or a.shape[2] != 3 or not a.flags.c_contiguous):
+            raise ValueError("half-buffer sums must be contiguous float64 [H, W, 3]")
+    p = [a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None for a in (sa, qa, sb, qb)]
+    capi.check(capi.load().pt_read_halves(ctx.handle, *p))
+
+
+def atrous_halves(ctx: capi.Context, cfg: Optional[AtrousConfig], mean: Optional[np.ndarray] = None, err: Optional[np.ndarray] = None,
+                  half_means: Optional[np.ndarray] = None) -> dict:
+    """pt_atrous_halves on ctx's open or last frame (cfg None = the defaults): the a-trous filter on each half of the samples;
+    mean (float64 [H, W, 3]) receives (fA + fB) / 2, err (float64 [H, W]) the per-pixel ((fA - fB) / 2)^2 averaged over the channels,
+    half_means (float64 [2, H, W, 3]) fA and fB.  Returns the pt_halves_stats: atrous_ms, launches, iterations, noise (measured),
+    noise_model (propagated), bad_pixels, spp_min.  Neither figure sees the bias the filter adds."""
+    if not capi.has("pt_atrous_halves"):
+        raise RuntimeError("this libptcore.so has no pt_atrous_halves (rebuild it)")
+    if mean is not None and (mean.dtype != np.float64 or mean.ndim != 3 or mean.shape[2] != 3 or not mean.flags.c_contiguous):
+        raise ValueError("mean must be contiguous float64 [H, W, 3]")
+    if err is not None and (err.dtype != np.float64 or err.ndim != 2 or not err.flags.c_contiguous):
+        raise ValueError("err must be contiguous float64 [H, W]")
+    if half_means is not None and (half_means.dtype != np.float64 or half_means.ndim != 4 or half_means.shape[0] != 2
+                                   or half_means.shape[3] != 3 or not half_means.flags.c_contiguous):
+        raise ValueError("half_means must be contiguous float64 [2, H, W, 3]")
+    shapes = {a.shape[:2] for a in (mean, err) if a is not None} | ({half_means.shape[1:3]} if half_means is not None else set())
+    if len(shapes) > 1:
+        raise ValueError("mean / err / half_means must have the same height and width")
+    c = cfg.c() if cfg is not None else None
+    st = capi.PtHalvesStats()
+    dp = C.POINTER(C.c_double)
+    capi.check(capi.load().pt_atrous_halves(ctx.handle, C.byref(c) if c is not None else None,
+                                            *(a.ctypes.data_as(dp) if a is not None else None for a in (mean, err, half_means)),
+                                            C.byref(st)))
+    return st.as_dict()
+
+
+def filtered_noise_from_env(environ=None) -> Optional[float]:
+    """PATHTRACER_GPU_FILTERED_NOISE=<float > 0>: the noise target on the filtered frame (used with PATHTRACER_GPU_ATROUS; the step
+    is PATHTRACER_GPU_NOISE_STEP); None when unset or not such a number."""
+    import math
+    import os
+
+    env = os.environ if environ is None else environ
+    try:
+        f = float(env["PATHTRACER_GPU_FILTERED_NOISE"])
+        return f if f > 0 and math.isfinite(f) else None
+    except (KeyError, ValueError):
+        return None
+
+
 def scene_allows_features(sc, shading: str = "cpu") -> bool:
     """Does a frame of this scene accept pt_set_features(k > 0)?  Not with GL shading, and not on the bounding-volume-hierarchy
     path (more than 128 spheres or 128 boxes, or PTCORE_SCAN=bvh)."""
@@ -428,7 +490,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            ndraw: Optional[np.ndarray] = None, ctx: Optional[capi.Context] = None, fog: bool = False,
            shading: str = "cpu", moments: Optional[np.ndarray] = None, noise: Optional[float] = None,
            noise_step: int = 16, adaptive: bool = False, min_spp: int = 0, counts: Optional[np.ndarray] = None,
-           features: Optional[int] = None, atrous: Optional["AtrousConfig"] = None) -> dict:
+           features: Optional[int] = None, atrous: Optional["AtrousConfig"] = None,
+           filtered_noise: Optional[float] = None, halves: bool = False) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -455,10 +518,25 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     scene allows features (scene_allows_features) and 0 where it does not.  The returned dict gains "atrous": the pt_atrous_stats.
     Without the two arguments features are off for the call.
 
+    filtered_noise=T (with atrous=) renders until the *filtered* frame is good enough: the frame collects the
+    half-buffer sums (pt_set_halves), samples are added noise_step at a time, after every step with at least 4 samples done
+    pt_atrous_halves runs with the filter's configuration, and the frame stops at the first check whose measured `noise` is at or
+    below T, or at the cap cfg.samples_per_px.  The image is pt_atrous on the full sums: that of a plain frame of the samples done.
+    It excludes noise= and adaptive=True.  The returned dict gains filtered_noise and noise_model (the last check's two figures;
+    inf when no check ran) and spp_done.  Neither figure sees the bias the filter adds.  halves=True collects the half-buffer
+    sums without the stop rule (read them with read_halves / atrous_halves afterwards); without the two arguments halves are off.
+
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
     Returns the pt_stats of the frame as a dict.
     """
+    if filtered_noise is not None:
+        if atrous is None:
+            raise ValueError("filtered_noise needs the filter whose output it measures (atrous=)")
+        if noise is not None or adaptive:
+            raise ValueError("filtered_noise excludes noise= and adaptive=True: one stop rule per frame")
+        if shading != "cpu":
+            raise ValueError("filtered_noise is not available with GL shading (pt_atrous_halves refuses such frames)")
     L = capi.load()
     ctx = ctx or context()
     if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4:
@@ -478,8 +556,10 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
                                or not counts.flags.c_contiguous):
         raise ValueError("counts needs adaptive=True and a contiguous uint32 [H, W] array")
     set_adaptive(ctx, noise if adaptive else None, min_spp, noise_step)
-    want_moments = moments is not None or noise is not None or atrous is not None
+    want_moments = moments is not None or noise is not None or atrous is not None or halves
     set_moments(ctx, want_moments)
+    set_halves(ctx, halves or filtered_noise is not None)
+    fstats = {"filtered_noise": float("inf"), "noise_model": float("inf")}
     if features is None:
         features = 0
         if atrous is not None:
@@ -505,6 +585,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
             d.update(noise=noise_estimate(ctx)["noise"])
             if atrous is not None:  # the filtered image takes the place of the plain finish
                 d["atrous"] = _atrous(ctx, atrous, img)
+            if filtered_noise is not None:
+                d.update(fstats)
             if adaptive:
                 d["adaptive"] = adaptive_state(ctx)
                 d["spp_done"] = d["adaptive"]["spp_max"]
@@ -512,9 +594,11 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
                     read_sample_counts(ctx, counts)
         elif want_moments:
             d.update(noise=float("inf"))
+            if filtered_noise is not None:
+                d.update(fstats)
         return d
 
-    if progress is None and (noise is None or adaptive):  # (an adaptive frame steps inside pt_render)
+    if progress is None and (noise is None or adaptive) and filtered_noise is None:  # (an adaptive frame steps inside pt_render)
         capi.check(L.pt_render(ctx.handle, C.byref(flat.c), C.byref(pc), _ptr(img), stride, _ptr(accum), _ptr(nseg),
                                _ptr(ndraw), C.byref(st)))
         d = st.as_dict()
@@ -535,6 +619,19 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
                     capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
                     progress()
             if cfg.samples_per_px <= 0:
+                capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
+        elif filtered_noise is not None:  # render until the measured noise of the filtered frame is at the target
+            while done.value < cfg.samples_per_px:
+                capi.check(L.pt_step(ctx.handle, max(1, min(int(noise_step), cfg.samples_per_px - done.value)), C.byref(done)))
+                if progress is not None:
+                    capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
+                    progress()
+                if done.value >= 4:
+                    hs = atrous_halves(ctx, atrous)
+                    fstats = {"filtered_noise": hs["noise"], "noise_model": hs["noise_model"]}
+                    if hs["noise"] <= filtered_noise:
+                        break
+            if progress is None or cfg.samples_per_px <= 0:
                 capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
         elif noise is not None:  # render until the noise target, cfg.samples_per_px as the cap
             nz = capi.PtNoise()
