@@ -65,6 +65,9 @@ var (
 	atrousIters = 5
 	featuresK   = -1         // -1: not said, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows)
 	lastAtrous  AtrousStats // pt_atrous_stats of the last frame (zero unless it was filtered)
+	temporalSet bool        // false: PATHTRACER_GPU_TEMPORAL decides
+	temporalOn  bool
+	lastTemporal TemporalStats // pt_temporal_stats of the last frame (zero unless it was accumulated)
 
 	filteredSet    bool        // false: PATHTRACER_GPU_FILTERED_NOISE decides
 	filteredTarget float64     // the noise target on the filtered frame (0 = off)
@@ -195,6 +198,67 @@ func filteredRule() float64 {
 	return 0
 }
 
+// TemporalStats mirrors pt_temporal_stats: what the temporal accumulation did to the last frame.
+type TemporalStats struct {
+	Ms                                   float64
+	Launches, Iterations                 int
+	Reprojected, Disoccluded, BadPixels  uint64
+	MeanLen                              float64
+	NoiseBefore, NoiseBlended, NoiseAfter float64
+}
+
+// SetTemporal turns the temporal accumulation on (pt_temporal, DESIGN 3.13), for a caller that renders frame after frame while the
+// camera moves: the context of this package keeps a history from Render to Render, and Render's image is the frame blended into the
+// reprojected history, then filtered, in place of pt_atrous's.  On brings the moments, the filter and 4 feature samples per pixel with
+// it (unless SetFeatures / PATHTRACER_GPU_FEATURES name another number).  Change cfg.Seed from frame to frame -- the blended variance
+// assumes independent frames -- and call ResetTemporal after a scene edit or a cut.  Not set: PATHTRACER_GPU_TEMPORAL decides.
+func SetTemporal(on bool) {
+	mu.Lock()
+	defer mu.Unlock()
+	temporalSet, temporalOn = true, on
+}
+
+// Temporal reports whether the accumulation is in force.
+func Temporal() bool {
+	mu.Lock()
+	defer mu.Unlock()
+	return temporalRule()
+}
+
+// ResetTemporal empties the history (pt_temporal_reset).
+func ResetTemporal() error {
+	mu.Lock()
+	defer mu.Unlock()
+	if ctx == nil {
+		return nil
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.pt_temporal_reset(ctx); rc != C.PT_OK {
+		return lastError("pt_temporal_reset")
+	}
+	return nil
+}
+
+// LastTemporal reports the accumulation's figures for the last frame Render finished (the zero value unless it was accumulated).
+func LastTemporal() TemporalStats {
+	mu.Lock()
+	defer mu.Unlock()
+	return lastTemporal
+}
+
+// temporalRule: whether the accumulation is in force (SetTemporal, else the environment).
+func temporalRule() bool {
+	if temporalSet {
+		return temporalOn
+	}
+	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_TEMPORAL"))) {
+	case "1", "true", "on", "yes":
+		return true
+	}
+	return false
+}
+
 // SetFeatures sets the first-hit feature samples per pixel (pt_set_features); k < 0 = not said.
 func SetFeatures(k int) {
 	mu.Lock()
@@ -215,9 +279,9 @@ func LastAtrous() AtrousStats {
 // atrousRule: whether the filter is in force and its iterations (SetAtrous, else the environment).
 func atrousRule() (bool, int) {
 	if atrousSet {
-		return atrousOn, atrousIters
+		return atrousOn || temporalRule(), atrousIters
 	}
-	on, iters := false, 5
+	on, iters := temporalRule(), 5 // the accumulation brings the filter with it
 	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_ATROUS"))) {
 	case "1", "true", "on", "yes":
 		on = true
@@ -236,6 +300,9 @@ func featuresRule(sc *scene.Scene, atrous bool) int {
 	}
 	if v, err := strconv.Atoi(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_FEATURES"))); err == nil && v >= 0 {
 		return v
+	}
+	if temporalRule() {
+		return 4 // pt_temporal needs them: where the frame refuses features, pt_begin says so
 	}
 	if !atrous || glShading() {
 		return 0
@@ -510,6 +577,24 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 	runtime.LockOSThread()
 	defer runtime.UnlockOSThread()
 	lastAtrous = AtrousStats{}
+	lastTemporal = TemporalStats{}
+	if _, iters := atrousRule(); temporalRule() && ctx != nil && img.Bounds().Dx() == cfg.Width && img.Bounds().Dy() == cfg.Height {
+		// the frame blended into the context's reprojected history, then filtered, takes the place of the plain finish
+		ac := C.pt_atrous_config{iterations: C.int32_t(iters), sigma_l: 4, sigma_n: 0.1, sigma_z: 0.1, sigma_a: 0.2}
+		var tc *C.pt_temporal_config // nil: the defaults
+		var st C.pt_temporal_stats
+		if rc := C.pt_temporal(ctx, tc, &ac, (*C.uint8_t)(unsafe.Pointer(&img.Pix[0])), C.int32_t(img.Stride), nil, nil, &st); rc != C.PT_OK {
+			return lastError("pt_temporal")
+		}
+		lastTemporal = TemporalStats{Ms: float64(st.temporal_ms), Launches: int(st.launches), Iterations: int(st.iterations),
+			Reprojected: uint64(st.reprojected), Disoccluded: uint64(st.disoccluded), BadPixels: uint64(st.bad_pixels),
+			MeanLen: float64(st.mean_len), NoiseBefore: float64(st.noise_before), NoiseBlended: float64(st.noise_blended),
+			NoiseAfter: float64(st.noise_after)}
+		if progress != nil {
+			progress()
+		}
+		return nil
+	}
 	if on, iters := atrousRule(); on && ctx != nil && img.Bounds().Dx() == cfg.Width && img.Bounds().Dy() == cfg.Height {
 		// the filtered image takes the place of the plain finish (the sums stay readable after pt_end)
 		ac := C.pt_atrous_config{iterations: C.int32_t(iters), sigma_l: 4, sigma_n: 0.1, sigma_z: 0.1, sigma_a: 0.2}

@@ -535,6 +535,66 @@ int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean,
                          pt_halves_stats *stats);
 
 /*
+ * Temporal accumulation (additive to ABI 4; the model and its order of evaluation are stated in csrc/pt_temporal.h):
+ * for a caller that renders frame after frame while the camera moves.  The context keeps a history -- per pixel a blended mean, the
+ * variance of that mean, the number of frames behind it, and the first-hit normal, albedo and distance it belongs to -- with the camera
+ * it was seen from.  pt_temporal finds, for every pixel of the current frame, where its first hit (or, for a pixel that sees the sky,
+ * its direction) lay in the previous frame, reads the history there (bilinear; a tap counts only where distance, normal and albedo
+ * agree), blends the frame's own mean into it with weight a = max(alpha, 1 / (len + 1)), stores the result as the new history and
+ * then, unless `filter` is NULL, runs pt_atrous's filter on the blended mean and variance with this frame's feature planes.  Off
+ * unless called: until the first pt_temporal nothing is allocated or launched.
+ *   cfg == NULL : alpha 0.2, max_len 32, tol_z 0.1, n_min 0.9, tol_a 0.05.  A NaN, alpha outside [0, 1], max_len < 1 or a negative
+ *                 tolerance is PT_ERR_INVALID.
+ *   filter      : NULL = no filter (the output is the blended frame); otherwise as pt_atrous's cfg, with the same PT_ERR_INVALID
+ *                 refusals.  (pt_atrous's defaults: pass a config with 5, 0, 4.0, 0.1, 0.1, 0.2.)
+ *   rgba, stride, mean, var : as pt_atrous's, of the blended (and filtered) frame; any may be NULL
+ *   reprojected / disoccluded : good pixels that found history / that did not although the history was not empty
+ *   mean_len    : the mean of the new history's len over the frame's pixels (a bad pixel counts 0)
+ *   noise_before / noise_blended / noise_after : pt_atrous's figure of the frame's own (mean, variance) -- pt_noise_estimate's
+ *                 figure --, of the blended state and of the output (= noise_blended when filter is NULL).  The blended variance
+ *                 (1 - a)^2 var_history + a^2 var_frame assumes that the frames are independent: CHANGE THE SEED FROM FRAME TO FRAME.
+ * Valid when pt_atrous is -- also between two pt_steps -- on a frame rendered with features on (pt_set_features, k > 0); otherwise
+ * PT_ERR_STATE: features off, GL shading, a pixel with fewer than 2 samples.  A second call for the same frame at the same number
+ * of samples done is PT_ERR_STATE too ("already accumulated": it would blend the frame into itself); after a further pt_step the
+ * call is valid again.  Every refusal leaves the context and the history as they were, and the new history replaces the old one
+ * only when the call succeeds.  A pure read of the frame: sums, counts and later pt_steps are unaffected.  Runs on devices[0]; the
+ * history takes 192 B per pixel there (two sets of 12 planes), outside PTCORE_L_BUDGET_MB, allocated on the first call.
+ *   pt_temporal_read  : the stored history, row-major: mean = width*height*3 doubles, var = width*height doubles,
+ *                       len = width*height int32 (0: a bad pixel, never read as a tap); any may be NULL.  PT_ERR_STATE when empty.
+ *   pt_temporal_reset : empties the history (after a scene edit, a cut).  The history is also empty after pt_create and is dropped
+ *                       by a call whose width x height differs from the history's.
+ * The history is keyed by geometry alone: moving or edited objects are caught only by the distance, normal and albedo tests, so
+ * the caller resets after an edit.  Known limit: a firefly in one frame stays in the history for several frames (no outlier
+ * rejection before the blend).
+ */
+typedef struct pt_temporal_config {
+    double alpha;         /* 0..1: the least weight of the current frame */
+    double tol_z;         /* >= 0: relative first-hit distance a tap may be off by */
+    double n_min;         /* the least N_i . N_h of a tap */
+    double tol_a;         /* >= 0: the albedo distance a tap may be off by */
+    int32_t max_len;      /* >= 1: the history length saturates here */
+    int32_t reserved;
+} pt_temporal_config;
+
+typedef struct pt_temporal_stats {
+    double temporal_ms;   /* device time first launch -> last launch complete (the gathers are not in it) */
+    int32_t launches;     /* temporal + noise [+ iterations + noise] + finish */
+    int32_t iterations;   /* of the filter; 0 without one */
+    uint64_t reprojected;
+    uint64_t disoccluded;
+    uint64_t bad_pixels;
+    double mean_len;
+    double noise_before;
+    double noise_blended;
+    double noise_after;
+} pt_temporal_stats;
+
+int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_config *filter, uint8_t *rgba, int32_t stride,
+                    double *mean, double *var, pt_temporal_stats *stats);
+int32_t pt_temporal_read(pt_ctx *ctx, double *mean, double *var, int32_t *len);
+int32_t pt_temporal_reset(pt_ctx *ctx);
+
+/*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the
  * environment at pt_create, the trace kernel runs a build that counts, per code
  * section, wave executions, active lanes and shader-clock cycles.  Copies up to n

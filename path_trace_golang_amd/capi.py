@@ -137,6 +137,20 @@ class PtHalvesStats(C.Structure):  # pt_halves_stats
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class PtTemporalConfig(C.Structure):  # pt_temporal_config: the blend weight, the tap tests and the history length of pt_temporal
+    _fields_ = [("alpha", C.c_double), ("tol_z", C.c_double), ("n_min", C.c_double), ("tol_a", C.c_double),
+                ("max_len", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PtTemporalStats(C.Structure):  # pt_temporal_stats
+    _fields_ = [("temporal_ms", C.c_double), ("launches", C.c_int32), ("iterations", C.c_int32), ("reprojected", C.c_uint64),
+                ("disoccluded", C.c_uint64), ("bad_pixels", C.c_uint64), ("mean_len", C.c_double), ("noise_before", C.c_double),
+                ("noise_blended", C.c_double), ("noise_after", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PtShard(C.Structure):
     _fields_ = [("index", C.c_int32), ("count", C.c_int32)]
 
@@ -196,6 +210,10 @@ SYMBOLS = [
     ("pt_read_halves", C.c_int32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("pt_atrous_halves", C.c_int32, [_vp, C.POINTER(PtAtrousConfig), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.POINTER(PtHalvesStats)]),
+    ("pt_temporal", C.c_int32, [_vp, C.POINTER(PtTemporalConfig), C.POINTER(PtAtrousConfig), _vp, C.c_int32, C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double), C.POINTER(PtTemporalStats)]),  # additive to ABI 4 (see has())
+    ("pt_temporal_read", C.c_int32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    ("pt_temporal_reset", C.c_int32, [_vp]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
@@ -238,7 +256,8 @@ def load():
 
 ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_rays", "pt_set_moments", "pt_read_moments",
             "pt_noise_estimate", "pt_set_adaptive", "pt_adaptive_state", "pt_read_sample_counts", "pt_set_features",
-            "pt_read_features", "pt_atrous", "pt_set_halves", "pt_read_halves", "pt_atrous_halves")  # added within ABI 4: detected by presence
+            "pt_read_features", "pt_atrous", "pt_set_halves", "pt_read_halves", "pt_atrous_halves", "pt_temporal", "pt_temporal_read",
+            "pt_temporal_reset")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:

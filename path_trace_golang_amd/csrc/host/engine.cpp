@@ -68,6 +68,8 @@ struct Core {
     decltype(&pt_atrous) atrous = nullptr;
     decltype(&pt_set_halves) set_halves = nullptr;  // optional, as set_shading (the filtered noise target needs both)
     decltype(&pt_atrous_halves) atrous_halves = nullptr;
+    decltype(&pt_temporal) temporal = nullptr;  // optional, as set_shading
+    decltype(&pt_temporal_reset) temporal_reset = nullptr;
     std::string error;  // sticky load error, like the reference's cached GL init failure (gpu.go:279-286)
 };
 
@@ -84,6 +86,7 @@ int g_adaptive_min_spp = 0;
 int g_atrous = -1;  // -1: not set yet, PATHTRACER_GPU_ATROUS / _ITERS decide
 int g_atrous_iters = 5;
 double g_filtered_noise = -1;  // < 0: not set yet, PATHTRACER_GPU_FILTERED_NOISE decides
+int g_temporal = -1;  // -1: not set yet, PATHTRACER_GPU_TEMPORAL decides
 int g_features = -1;  // -1: not set yet, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows, else 0)
 std::mutex g_mu;  // requests are serialised, like the reference's single GL worker (gpu.go:2534-2546)
 
@@ -139,6 +142,8 @@ bool load_core() {
     c.atrous = reinterpret_cast<decltype(c.atrous)>(dlsym(h, "pt_atrous"));
     c.set_halves = reinterpret_cast<decltype(c.set_halves)>(dlsym(h, "pt_set_halves"));
     c.atrous_halves = reinterpret_cast<decltype(c.atrous_halves)>(dlsym(h, "pt_atrous_halves"));
+    c.temporal = reinterpret_cast<decltype(c.temporal)>(dlsym(h, "pt_temporal"));
+    c.temporal_reset = reinterpret_cast<decltype(c.temporal_reset)>(dlsym(h, "pt_temporal_reset"));
     if (c.abi_version() != PT_ABI_VERSION) {
         g_core.error = "libptcore.so ABI version mismatch";
         dlclose(h);
@@ -437,6 +442,29 @@ double GetFilteredNoise() {
     return g_filtered_noise < 0 ? FilteredNoiseFromEnv() : g_filtered_noise;
 }
 
+bool TemporalFromEnv() {
+    const char *e = std::getenv("PATHTRACER_GPU_TEMPORAL");
+    if (!e) return false;
+    std::string v(e);
+    for (char &c : v) c = (char)std::tolower((unsigned char)c);
+    return v == "1" || v == "true" || v == "on" || v == "yes";
+}
+
+void SetTemporal(bool on) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_temporal = on ? 1 : 0;
+}
+
+bool Temporal() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_temporal < 0 ? TemporalFromEnv() : g_temporal == 1;
+}
+
+void ResetTemporal() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_ctx && g_core.temporal_reset) (void)g_core.temporal_reset(g_ctx);
+}
+
 void SetFeatures(int k) {
     std::lock_guard<std::mutex> lk(g_mu);
     g_features = k >= 0 ? k : -1;
@@ -500,6 +528,10 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     bool atrous = g_atrous == 1;
     int atrous_iters = g_atrous_iters;
     if (g_atrous < 0) AtrousFromEnv(atrous, atrous_iters);
+    // temporal accumulation (SetTemporal / PATHTRACER_GPU_TEMPORAL) brings the filter, the moments and the feature planes with it
+    const bool temporal = g_temporal < 0 ? TemporalFromEnv() : g_temporal == 1;
+    if (temporal && !g_core.temporal) return "temporal accumulation: libptcore.so lacks pt_temporal";
+    atrous = atrous || temporal;
     if (atrous && !(g_core.atrous && g_core.set_moments)) return "a-trous filter: libptcore.so lacks pt_atrous / pt_set_moments";
     // a noise target on the filtered frame (SetFilteredNoise / PATHTRACER_GPU_FILTERED_NOISE): the half-buffer sums and pt_atrous_halves
     const double filtered_target = atrous ? (g_filtered_noise < 0 ? FilteredNoiseFromEnv() : g_filtered_noise) : 0;
@@ -509,6 +541,7 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (to_filtered && !(g_core.set_halves && g_core.atrous_halves)) return "filtered noise target: libptcore.so lacks pt_set_halves / pt_atrous_halves";
     if (g_core.set_halves && g_core.set_halves(g_ctx, to_filtered ? 1 : 0) != PT_OK) return std::string("pt_set_halves: ") + g_core.last_error();
     int features = g_features >= 0 ? g_features : FeaturesFromEnv();
+    if (features < 0 && temporal) features = 4;  // (pt_temporal needs them: where the frame refuses features, pt_begin says so)
     if (features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path), else off
         features = 0;
         if (atrous && !gl_model) {
@@ -615,7 +648,15 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     }
     pt_atrous_stats ats;
     std::memset(&ats, 0, sizeof ats);
-    if (atrous && err.empty()) {  // the filtered image takes the place of the plain finish (the sums stay readable after pt_end)
+    pt_temporal_stats tst;
+    std::memset(&tst, 0, sizeof tst);
+    if (temporal && err.empty()) {  // the frame blended into the context's reprojected history, then filtered
+        pt_atrous_config ac = {atrous_iters, 0, 4.0, 0.1, 0.1, 0.2};
+        if (g_core.temporal(g_ctx, nullptr, &ac, img.Pix.data(), img.Stride, nullptr, nullptr, &tst) != PT_OK) err = std::string("pt_temporal: ") + g_core.last_error();
+        ats.atrous_ms = tst.temporal_ms;
+        ats.noise_before = tst.noise_before;
+        ats.noise_after = tst.noise_after;
+    } else if (atrous && err.empty()) {  // the filtered image takes the place of the plain finish (the sums stay readable after pt_end)
         pt_atrous_config ac = {atrous_iters, 0, 4.0, 0.1, 0.1, 0.2};
         if (g_core.atrous(g_ctx, &ac, img.Pix.data(), img.Stride, nullptr, nullptr, &ats) != PT_OK) err = std::string("pt_atrous: ") + g_core.last_error();
     }
@@ -625,6 +666,12 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         stats->atrous_ms = ats.atrous_ms;
         stats->noise_before = ats.noise_before;
         stats->noise_after = ats.noise_after;
+        stats->temporal = temporal;
+        stats->reprojected = tst.reprojected;
+        stats->disoccluded = tst.disoccluded;
+        stats->temporal_ms = tst.temporal_ms;
+        stats->mean_len = tst.mean_len;
+        stats->noise_blended = tst.noise_blended;
         stats->to_filtered_noise = to_filtered;
         stats->filtered_noise = hs.noise;
         stats->noise_model = hs.noise_model;

@@ -44,6 +44,9 @@ struct Stats {
     double atrous_ms = 0, noise_before = 0, noise_after = 0;
     bool to_filtered_noise = false;  // the stop rule was the measured noise of the filtered frame (SetFilteredNoise); spp_done is the count
     double filtered_noise = 0, noise_model = 0;  // pt_halves_stats' noise and noise_model at the last check (0: no check ran)
+    bool temporal = false;  // the image is pt_temporal's (SetTemporal): the frame blended into the reprojected history, then filtered
+    uint64_t reprojected = 0, disoccluded = 0;  // pt_temporal_stats of the frame
+    double temporal_ms = 0, mean_len = 0, noise_blended = 0;
 };
 
 namespace hip {
@@ -92,6 +95,15 @@ void AtrousFromEnv(bool &on, int &iterations);  // PATHTRACER_GPU_ATROUS = 1 / t
 void SetFilteredNoise(double target);
 double GetFilteredNoise();
 double FilteredNoiseFromEnv();  // PATHTRACER_GPU_FILTERED_NOISE = float > 0, else 0: off
+// Temporal accumulation, for a caller that renders frame after frame while the camera moves: the process-wide context
+// keeps a history, and after the frame Render calls pt_temporal -- the frame blended into the reprojected history, then filtered
+// -- in place of pt_atrous.  On turns on moments, the filter and 4 feature samples per pixel (unless SetFeatures /
+// PATHTRACER_GPU_FEATURES name another number).  Change cfg.Seed from frame to frame (the blended variance assumes independent
+// frames) and call ResetTemporal after a scene edit or a cut.  The initial value is PATHTRACER_GPU_TEMPORAL (TemporalFromEnv).
+void SetTemporal(bool on);
+bool Temporal();
+bool TemporalFromEnv();  // PATHTRACER_GPU_TEMPORAL = 1 / true / on / yes
+void ResetTemporal();    // pt_temporal_reset on the process-wide context
 void SetFeatures(int k);
 int GetFeatures();     // -1: not said
 int FeaturesFromEnv(); // PATHTRACER_GPU_FEATURES = int >= 0, else -1

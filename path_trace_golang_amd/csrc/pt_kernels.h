@@ -51,6 +51,8 @@
 //                   and over the odd-indexed samples, after moments_kernel.
 //   atrous_pair_prep_kernel / atrous_pair_kernel / halves_combine_kernel   pt_atrous_halves: the filter on each half, both halves
 //                   in one launch over plane-per-component buffers, and the measured noise figure of their mean.
+//   temporal_kernel pt_temporal: prep, the previous frame's history reprojected and blended (pt_temporal.h), the new history, and
+//                   the buffers atrous_prep_kernel would have left for the filter's kernels.
 //
 // FP64 throughout; built with -ffp-contract=off so every product and sum rounds
 // exactly as the reference's Go code does on amd64.
@@ -63,6 +65,7 @@
 #include "pt_fog.h"
 #include "pt_glshade.h"
 #include "pt_math.h"
+#include "pt_temporal.h"
 
 namespace ptk {
 
@@ -3558,6 +3561,91 @@ __global__ __launch_bounds__(PT_BLOCK) void halves_combine_kernel(const HalvesCo
         r.bad = 0;
         for (int w = 0; w < PT_BLOCK / PT_WAVE; w++) r.bad += s_bad[w];
         A.partial[blockIdx.x] = r;
+    }
+}
+
+// pt_temporal (pt_temporal.h): prep, reprojection of the previous frame's history and the blend, one lane per pixel in atrous_kernel's
+// block shape (32 x 8 pixels, a wave = two rows of 32: the four bilinear taps of a wave's lanes fall into two or three rows of every
+// history plane).  Both cameras ride in the argument block.  The kernel leaves the new history (plane per component) and the colour,
+// variance and guide buffers exactly as atrous_prep_kernel does, so atrous_kernel, atrous_noise_kernel and atrous_finish_kernel run on
+// them as they are.  The block's partial of the frame's own noise figure goes over noise_kernel's tree; the counts are integers.
+struct TemporalPartial {
+    double sum_before;            // the block's sum of e2 of (c_i, var_i)
+    unsigned long long len_sum;   // ... of len'
+    uint32_t reprojected, disoccluded;
+};
+
+struct TemporalArgs {
+    ptt::Config C;
+    ptt::View V;
+    DevCamera cam_h;
+    const double *acc, *m2;       // [npix][3] raw sums S, Q
+    const uint32_t *cnt;          // [npix] the pixel's own count (adaptive frames) or null: n
+    const double *fn, *fa, *fd;   // [npix][3] feature sums
+    const double *hist;           // the previous history: [PTT_PLANES][npix] (not read when C.have_history == 0)
+    double *hist_out;             // the new one
+    double *col, *var;            // [npix][3], [npix]: atrous_prep_kernel's layout
+    pta::Guide *guide;            // [npix]
+    TemporalPartial *partial;     // [gridDim.y * gridDim.x]
+    uint32_t n;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A) {
+    __shared__ double s_sum[PT_BLOCK / PT_WAVE];
+    __shared__ uint32_t s_cnt[PT_BLOCK / PT_WAVE][3];
+    const int32_t x = (int32_t)(blockIdx.x * 32u + (threadIdx.x & 31u));
+    const int32_t y = (int32_t)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    const size_t np = (size_t)A.V.W * (size_t)A.V.H;
+    double e2 = 0.0;
+    uint32_t rep = 0, dis = 0, lens = 0;
+    if (x < A.V.W && y < A.V.H) {
+        const size_t i = (size_t)y * (size_t)A.V.W + (size_t)x, i3 = 3 * i;
+        const double S[3] = {A.acc[i3], A.acc[i3 + 1], A.acc[i3 + 2]};
+        const double Q[3] = {A.m2[i3], A.m2[i3 + 1], A.m2[i3 + 2]};
+        double c[3], var, co[3], vo;
+        pta::Guide g;
+        pta::prep_pixel(S, Q, A.cnt ? A.cnt[i] : A.n, A.fn + i3, A.fa + i3, A.fd + i3, c, var, g);
+        const bool hit = A.fd[i3 + 1] > 0.0;
+        int32_t len;
+        const ptt::Status st = ptt::blend_pixel(A.C, A.V, A.cam_h, A.hist, reinterpret_cast<const int32_t *>(A.hist + (size_t)PTT_LH * np), x, y,
+                                                c, var, g, hit, co, vo, len);
+        ptt::store_history(A.hist_out, reinterpret_cast<int32_t *>(A.hist_out + (size_t)PTT_LH * np), np, i, co, vo, len, g, hit);
+        A.col[i3] = co[0];
+        A.col[i3 + 1] = co[1];
+        A.col[i3 + 2] = co[2];
+        A.var[i] = vo;
+        A.guide[i] = g;
+        e2 = pta::noise_term(c, var);
+        rep = st == ptt::ST_REPROJECTED ? 1u : 0u;
+        dis = st == ptt::ST_DISOCCLUDED ? 1u : 0u;
+        lens = (uint32_t)len;
+    }
+    double sum = e2;
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off, 64);
+        rep += __shfl_xor(rep, off, 64);
+        dis += __shfl_xor(dis, off, 64);
+        lens += __shfl_xor(lens, off, 64);
+    }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) {
+        s_sum[wave] = sum;
+        s_cnt[wave][0] = rep;
+        s_cnt[wave][1] = dis;
+        s_cnt[wave][2] = lens;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        TemporalPartial r;
+        r.sum_before = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+        r.reprojected = r.disoccluded = 0;
+        r.len_sum = 0;
+        for (int w = 0; w < PT_BLOCK / PT_WAVE; w++) {
+            r.reprojected += s_cnt[w][0];
+            r.disoccluded += s_cnt[w][1];
+            r.len_sum += s_cnt[w][2];
+        }
+        A.partial[blockIdx.y * gridDim.x + blockIdx.x] = r;
     }
 }
 

@@ -263,6 +263,7 @@ struct Frame {
     bool adaptive = false; // pt_set_adaptive: the frame's jobs are those of the active blocks, a check ends every pt_step (implies moments)
     pt_adaptive ad{};
     bool halves = false;   // pt_set_halves: halves_kernel runs after every chunk's moments_kernel (pt_begin / pt_render frames only; implies moments)
+    uint64_t serial = 0;   // pt_ctx::frames_opened when the frame opened: tells two frames of a context apart
     int32_t features = 0;  // pt_set_features: feature_kernel runs after the chunks that hold samples below this index (pt_begin / pt_render frames only)
     double worst_active = 0.0;  // largest block noise among the blocks the last check kept
     std::vector<ptg::GlObj> gl_objs;
@@ -328,6 +329,17 @@ struct pt_ctx {
     // combined mean, err and the two filtered halves row-major, the partials of the two figures
     DevBuf<double> ah_guide, ah_col[2], ah_var[2], ah_mean, ah_err, ah_half;
     DevBuf<ptk::HalvesPartial> ah_part;
+    // pt_temporal (allocated on the first call): two sets of history planes, tp_hist[tp_cur] the stored one; the block partials; the
+    // history's size and camera; the frame and the samples done of the last call that succeeded ("already accumulated")
+    DevBuf<double> tp_hist[2];
+    DevBuf<ptk::TemporalPartial> tp_part;
+    int tp_cur = 0;
+    bool tp_valid = false;            // the history is not empty
+    int32_t tp_w = 0, tp_h = 0;
+    DevCamera tp_cam{};
+    uint64_t tp_serial = 0;
+    int32_t tp_spp = 0;
+    uint64_t frames_opened = 0;       // pt_begin / pt_render frames of this context so far
     pt_adaptive adaptive{};
     DevBuf<uint32_t> f_seg, f_draw;
     size_t l_budget_bytes = (size_t)48 << 30;  // per-chunk job buffers (radiance, primary rays, path-state queues): a sixth of the 288 GB
@@ -1977,6 +1989,7 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
     if (cfg->spp_chunk <= 0) balance_chunk(fr);
     fr.done_spp = 0;
     fr.t0 = std::chrono::steady_clock::now();
+    fr.serial = ++ctx->frames_opened;
     fr.open = true;
     return PT_OK;
 }
@@ -2922,22 +2935,9 @@ int32_t pt_read_features(pt_ctx *ctx, double *normal, double *albedo, double *de
     return PT_OK;
 }
 
-int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32_t stride, double *mean, double *var, pt_atrous_stats *stats) {
-    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
-    pt_atrous_config c = {5, 0, 4.0, 0.1, 0.1, 0.2};
-    if (cfg) c = *cfg;
-    if (c.iterations < 0 || c.iterations > PTA_MAX_ITERATIONS) return fail(PT_ERR_INVALID, "pt_atrous: iterations must be 0..6");
-    if (!(c.sigma_l > 0.0) || !(c.sigma_n >= 0.0) || !(c.sigma_z >= 0.0) || !(c.sigma_a >= 0.0))
-        return fail(PT_ERR_INVALID, "pt_atrous: sigma_l must be > 0, sigma_n, sigma_z and sigma_a >= 0 (0 = term off)");
-    if (int32_t rc = moments_frame(ctx, "pt_atrous")) return rc;
+// The inputs of pt_atrous and pt_temporal as row-major planes on devices[0] (f_accum, f_m2, f_seg, f_feat_*).
+static int32_t gather_filter_inputs(pt_ctx *ctx) {
     Frame &fr = ctx->frame;
-    if (fr.gl) return fail(PT_ERR_STATE, "pt_atrous: not available for a frame rendered with GL shading (pt_set_shading)");
-    // (an adaptive block stops at two samples or more, so every pixel holds at least min(done, 2))
-    if (fr.done_spp < 2) return fail(PT_ERR_STATE, "pt_atrous: every pixel needs at least 2 samples");
-    const int32_t W = fr.cfg.width, H = fr.cfg.height;
-    if (rgba && stride < W * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
     // the inputs as row-major planes on devices[0]: S, Q, the counts of an adaptive frame, the features of a frame that has them.  All
     // reads: the sums, the block table and the event lists of the frame stay as they are.
     {
@@ -2975,10 +2975,30 @@ int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32
             }))
             return rc;
     }
-    const bool feat = fr.features > 0;
-    if (feat)
+    if (fr.features > 0)
         for (uint32_t k = 0; k < 3u; k++)
             if (int32_t rc = gather_feature(ctx, k, nullptr)) return rc;
+    return PT_OK;
+}
+
+int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32_t stride, double *mean, double *var, pt_atrous_stats *stats) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    pt_atrous_config c = {5, 0, 4.0, 0.1, 0.1, 0.2};
+    if (cfg) c = *cfg;
+    if (c.iterations < 0 || c.iterations > PTA_MAX_ITERATIONS) return fail(PT_ERR_INVALID, "pt_atrous: iterations must be 0..6");
+    if (!(c.sigma_l > 0.0) || !(c.sigma_n >= 0.0) || !(c.sigma_z >= 0.0) || !(c.sigma_a >= 0.0))
+        return fail(PT_ERR_INVALID, "pt_atrous: sigma_l must be > 0, sigma_n, sigma_z and sigma_a >= 0 (0 = term off)");
+    if (int32_t rc = moments_frame(ctx, "pt_atrous")) return rc;
+    Frame &fr = ctx->frame;
+    if (fr.gl) return fail(PT_ERR_STATE, "pt_atrous: not available for a frame rendered with GL shading (pt_set_shading)");
+    // (an adaptive block stops at two samples or more, so every pixel holds at least min(done, 2))
+    if (fr.done_spp < 2) return fail(PT_ERR_STATE, "pt_atrous: every pixel needs at least 2 samples");
+    const int32_t W = fr.cfg.width, H = fr.cfg.height;
+    if (rgba && stride < W * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    if (int32_t rc = gather_filter_inputs(ctx)) return rc;
+    const bool feat = fr.features > 0;
     Device &d0 = ctx->devs[0];
     HIP_TRY(hipSetDevice(d0.ordinal));
     const size_t npix = (size_t)W * (size_t)H;
@@ -3067,6 +3087,191 @@ int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32
         std::fprintf(stderr, "ptcore: pt_atrous %d iterations, %.3f ms host wall (gathers included)\n", c.iterations,
                      std::chrono::duration<double, std::milli>(clk::now() - t0).count());
     return rc;
+}
+
+int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_config *filter, uint8_t *rgba, int32_t stride, double *mean,
+                    double *var, pt_temporal_stats *stats) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    pt_temporal_config c = {0.2, 0.1, 0.9, 0.05, 32, 0};
+    if (cfg) c = *cfg;
+    if (!(c.alpha >= 0.0 && c.alpha <= 1.0) || !(c.tol_z >= 0.0) || !(c.tol_a >= 0.0) || c.n_min != c.n_min || c.max_len < 1)
+        return fail(PT_ERR_INVALID, "pt_temporal: alpha must be 0..1, tol_z and tol_a >= 0, n_min a number, max_len >= 1");
+    pt_atrous_config f = {0, 0, 4.0, 0.1, 0.1, 0.2};
+    if (filter) f = *filter;
+    if (f.iterations < 0 || f.iterations > PTA_MAX_ITERATIONS) return fail(PT_ERR_INVALID, "pt_temporal: filter iterations must be 0..6");
+    if (!(f.sigma_l > 0.0) || !(f.sigma_n >= 0.0) || !(f.sigma_z >= 0.0) || !(f.sigma_a >= 0.0))
+        return fail(PT_ERR_INVALID, "pt_temporal: filter sigma_l must be > 0, sigma_n, sigma_z and sigma_a >= 0 (0 = term off)");
+    if (int32_t rc = moments_frame(ctx, "pt_temporal")) return rc;
+    Frame &fr = ctx->frame;
+    const int32_t W = fr.cfg.width, H = fr.cfg.height;
+    if (rgba && stride < W * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
+    if (fr.gl) return fail(PT_ERR_STATE, "pt_temporal: not available for a frame rendered with GL shading (pt_set_shading)");
+    if (fr.features <= 0) return fail(PT_ERR_STATE, "pt_temporal: the frame was rendered with features off (pt_set_features)");
+    if (fr.done_spp < 2) return fail(PT_ERR_STATE, "pt_temporal: every pixel needs at least 2 samples");
+    if (ctx->tp_serial == fr.serial && ctx->tp_spp == fr.done_spp)
+        return fail(PT_ERR_STATE, "pt_temporal: already accumulated (this frame, at this number of samples, is in the history)");
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    if (int32_t rc = gather_filter_inputs(ctx)) return rc;
+    Device &d0 = ctx->devs[0];
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    const size_t npix = (size_t)W * (size_t)H;
+    const uint32_t grid1 = (uint32_t)((npix + PT_BLOCK - 1) / PT_BLOCK);
+    const dim3 grid2((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8));
+    const size_t nblk = (size_t)grid2.x * grid2.y;
+    const bool have = ctx->tp_valid && ctx->tp_w == W && ctx->tp_h == H;  // another size: the history is dropped (when the call succeeds)
+    // Both sets are kept at the size of this frame.  A set that has to grow loses its contents, which is what a change of size means;
+    // a smaller frame after a larger one keeps the memory and is caught by `have`.
+    for (int k = 0; k < 2; k++) {
+        if (ctx->tp_hist[k].cap < (size_t)PTT_PLANES * npix) ctx->tp_valid = false;
+        if (hipError_t e = ctx->tp_hist[k].reserve((size_t)PTT_PLANES * npix); e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("pt_temporal: history: ") + hipGetErrorString(e));
+        HIP_TRY(ctx->at_col[k].reserve(3 * npix));
+        HIP_TRY(ctx->at_var[k].reserve(npix));
+    }
+    HIP_TRY(ctx->tp_part.reserve(nblk));
+    HIP_TRY(ctx->at_guide.reserve(npix));
+    HIP_TRY(ctx->at_part.reserve(2 * (size_t)grid1));
+    HIP_TRY(ctx->f_rgba.reserve(npix * 4));
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // first launch, last launch complete, temporal_kernel complete
+    for (int k = 0; k < 3; k++)
+        if (hipError_t e = hipEventCreate(&ev[k]); e != hipSuccess) {
+            for (int j = 0; j < k; j++) (void)hipEventDestroy(ev[j]);
+            return fail(PT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+        }
+    float kernel_ms = 0;
+    const int next = ctx->tp_cur ^ 1;
+    auto run = [&]() -> int32_t {
+        HIP_TRY(hipEventRecord(ev[0], d0.stream));
+        ptk::TemporalArgs TA;
+        std::memset(&TA, 0, sizeof TA);
+        TA.C.alpha = c.alpha; TA.C.tol_z = c.tol_z; TA.C.n_min = c.n_min; TA.C.tol_a = c.tol_a;
+        TA.C.max_len = c.max_len;
+        TA.C.have_history = have ? 1 : 0;
+        TA.V.cam = fr.cam;
+        TA.V.inv_width = fr.F.inv_width;
+        TA.V.inv_height = fr.F.inv_height;
+        TA.V.W = W;
+        TA.V.H = H;
+        TA.cam_h = ctx->tp_cam;
+        TA.acc = ctx->f_accum.p;
+        TA.m2 = ctx->f_m2.p;
+        TA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
+        TA.fn = ctx->f_feat_n.p;
+        TA.fa = ctx->f_feat_a.p;
+        TA.fd = ctx->f_feat_d.p;
+        TA.hist = ctx->tp_hist[ctx->tp_cur].p;
+        TA.hist_out = ctx->tp_hist[next].p;
+        TA.col = ctx->at_col[0].p;
+        TA.var = ctx->at_var[0].p;
+        TA.guide = ctx->at_guide.p;
+        TA.partial = ctx->tp_part.p;
+        TA.n = (uint32_t)fr.done_spp;
+        hipLaunchKernelGGL(ptk::temporal_kernel, grid2, dim3(PT_BLOCK), 0, d0.stream, TA);
+        HIP_TRY(hipEventRecord(ev[2], d0.stream));
+        hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[0].p, ctx->at_var[0].p, ctx->at_guide.p,
+                           ctx->at_part.p, (uint32_t)npix);
+        int cur = 0;
+        if (filter) {
+            ptk::AtrousArgs A;
+            std::memset(&A, 0, sizeof A);
+            A.P.sigma_l = f.sigma_l; A.P.sigma_n = f.sigma_n; A.P.sigma_z = f.sigma_z; A.P.sigma_a = f.sigma_a;
+            A.P.iterations = f.iterations;
+            A.P.n_on = f.sigma_n > 0.0;
+            A.P.z_on = f.sigma_z > 0.0;
+            A.P.a_on = f.sigma_a > 0.0;
+            A.guide = ctx->at_guide.p;
+            A.W = W;
+            A.H = H;
+            for (int32_t t = 0; t < f.iterations; t++, cur ^= 1) {
+                A.col = ctx->at_col[cur].p; A.var = ctx->at_var[cur].p;
+                A.col_out = ctx->at_col[cur ^ 1].p; A.var_out = ctx->at_var[cur ^ 1].p;
+                A.step = 1 << t;
+                hipLaunchKernelGGL(ptk::atrous_kernel, grid2, dim3(PT_BLOCK), 0, d0.stream, A);
+            }
+            hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[cur].p, ctx->at_var[cur].p,
+                               ctx->at_guide.p, ctx->at_part.p + grid1, (uint32_t)npix);
+        }
+        hipLaunchKernelGGL(ptk::atrous_finish_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[cur].p, ctx->f_rgba.p, (uint32_t)npix);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[1], d0.stream));
+        std::vector<ptk::NoisePartial> part(2 * (size_t)grid1);
+        std::vector<ptk::TemporalPartial> tpart(nblk);
+        HIP_TRY(hipMemcpyAsync(part.data(), ctx->at_part.p, (filter ? 2 : 1) * (size_t)grid1 * sizeof(ptk::NoisePartial), hipMemcpyDeviceToHost, d0.stream));
+        HIP_TRY(hipMemcpyAsync(tpart.data(), ctx->tp_part.p, nblk * sizeof(ptk::TemporalPartial), hipMemcpyDeviceToHost, d0.stream));
+        if (rgba) HIP_TRY(hipMemcpy2DAsync(rgba, (size_t)stride, ctx->f_rgba.p, (size_t)W * 4, (size_t)W * 4, (size_t)H, hipMemcpyDeviceToHost, d0.stream));
+        if (mean) HIP_TRY(hipMemcpyAsync(mean, ctx->at_col[cur].p, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+        if (var) HIP_TRY(hipMemcpyAsync(var, ctx->at_var[cur].p, npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+        HIP_TRY(hipStreamSynchronize(d0.stream));
+        HIP_TRY(hipEventElapsedTime(&kernel_ms, ev[0], ev[2]));
+        if (stats) {
+            pt_temporal_stats st;
+            std::memset(&st, 0, sizeof st);
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            st.temporal_ms = ms;
+            st.iterations = filter ? f.iterations : 0;
+            st.launches = filter ? f.iterations + 4 : 3;
+            double sum[3] = {0.0, 0.0, 0.0};
+            unsigned long long lens = 0;
+            for (const ptk::TemporalPartial &p : tpart) {  // partials in block order
+                sum[0] += p.sum_before;
+                st.reprojected += p.reprojected;
+                st.disoccluded += p.disoccluded;
+                lens += p.len_sum;
+            }
+            for (uint32_t b = 0; b < grid1; b++) {
+                sum[1] += part[b].sum;
+                st.bad_pixels += part[b].bad;
+                if (filter) sum[2] += part[(size_t)grid1 + b].sum;
+            }
+            st.mean_len = (double)lens / (double)npix;
+            st.noise_before = std::sqrt(sum[0] / (double)npix);
+            st.noise_blended = std::sqrt(sum[1] / (double)npix);
+            st.noise_after = filter ? std::sqrt(sum[2] / (double)npix) : st.noise_blended;
+            *stats = st;
+        }
+        return PT_OK;
+    };
+    const int32_t rc = run();
+    for (int k = 0; k < 3; k++) (void)hipEventDestroy(ev[k]);
+    if (rc != PT_OK) return rc;  // the stored history is untouched: the kernel wrote the other set
+    ctx->tp_cur = next;
+    ctx->tp_valid = true;
+    ctx->tp_w = W;
+    ctx->tp_h = H;
+    ctx->tp_cam = fr.cam;
+    ctx->tp_serial = fr.serial;
+    ctx->tp_spp = fr.done_spp;
+    if (std::getenv("PTCORE_VERBOSE"))
+        std::fprintf(stderr, "ptcore: pt_temporal %d filter iterations, temporal_kernel %.3f ms, %.3f ms host wall (gathers included)\n",
+                     filter ? f.iterations : 0, kernel_ms, std::chrono::duration<double, std::milli>(clk::now() - t0).count());
+    return PT_OK;
+}
+
+int32_t pt_temporal_read(pt_ctx *ctx, double *mean, double *var, int32_t *len) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!ctx->tp_valid) return fail(PT_ERR_STATE, "pt_temporal_read: the history is empty (pt_temporal first)");
+    const size_t np = (size_t)ctx->tp_w * (size_t)ctx->tp_h;
+    Device &d0 = ctx->devs[0];
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    std::vector<double> h((size_t)PTT_PLANES * np);
+    HIP_TRY(hipMemcpyAsync(h.data(), ctx->tp_hist[ctx->tp_cur].p, h.size() * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+    HIP_TRY(hipStreamSynchronize(d0.stream));
+    for (size_t i = 0; i < np; i++) {
+        if (mean)
+            for (size_t k = 0; k < 3; k++) mean[3 * i + k] = h[k * np + i];
+        if (var) var[i] = h[(size_t)PTT_VAR * np + i];
+        if (len) std::memcpy(&len[i], reinterpret_cast<const char *>(&h[(size_t)PTT_LH * np]) + 8 * i, sizeof(int32_t));
+    }
+    return PT_OK;
+}
+
+int32_t pt_temporal_reset(pt_ctx *ctx) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    ctx->tp_valid = false;
+    ctx->tp_serial = 0;
+    return PT_OK;
 }
 
 int32_t pt_set_halves(pt_ctx *ctx, int32_t on) {

@@ -63,7 +63,7 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 moments: Optional[np.ndarray] = None, noise: Optional[float] = None, noise_step: Optional[int] = None,
                 adaptive: Optional[bool] = None, min_spp: Optional[int] = None, counts: Optional[np.ndarray] = None,
                 features: Optional[int] = None, atrous: Optional["hip.AtrousConfig"] = None,
-                filtered_noise: Optional[float] = None) -> dict:
+                filtered_noise: Optional[float] = None, temporal: Optional["hip.TemporalConfig"] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
@@ -75,7 +75,9 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     PATHTRACER_GPU_FEATURES and PATHTRACER_GPU_ATROUS / PATHTRACER_GPU_ATROUS_ITERS (hip.AtrousConfig.from_env), both off by default.
     `filtered_noise` is hip.render's: with the filter on, render until the measured noise of the filtered frame is at or
     below it; None takes PATHTRACER_GPU_FILTERED_NOISE (hip.filtered_noise_from_env), off by default and ignored without the filter
-    or beside a noise target."""
+    or beside a noise target.  `temporal` is hip.render's: the frame is blended into the history the process-wide
+    context keeps from call to call (change cfg.seed from frame to frame); None takes PATHTRACER_GPU_TEMPORAL (temporal_setup),
+    which also turns on moments, 4 feature samples (unless PATHTRACER_GPU_FEATURES says otherwise) and the filter."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -88,6 +90,11 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     acfg = hip.AdaptiveConfig.from_env()
     if adaptive is None:
         adaptive = acfg.enabled
+    if temporal is None:
+        temporal, t_atrous, t_features = temporal_setup()
+        if temporal is not None:
+            atrous = atrous if atrous is not None else t_atrous
+            features = features if features is not None else t_features
     if atrous is None:
         atrous = hip.AtrousConfig.from_env()
     if features is None:
@@ -96,7 +103,23 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
         filtered_noise = hip.filtered_noise_from_env()
     return hip.render(sc, gcfg, img, progress, shading=model, features=features, atrous=atrous, moments=moments, noise=noise,
                       noise_step=noise_step if noise_step is not None else ncfg.step, adaptive=bool(adaptive) and noise is not None,
-                      min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts, filtered_noise=filtered_noise)
+                      min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts, filtered_noise=filtered_noise,
+                      temporal=temporal)
+
+
+def temporal_setup(environ=None):
+    """PATHTRACER_GPU_TEMPORAL=1: (the accumulation's config, the filter's, the feature samples) that the switch turns on -- the
+    filter with PATHTRACER_GPU_ATROUS_ITERS, k = PATHTRACER_GPU_FEATURES or 4; (None, None, None) when it is off."""
+    import os
+
+    env = os.environ if environ is None else environ
+    t = hip.TemporalConfig.from_env(env)
+    if t is None:
+        return None, None, None
+    a = hip.AtrousConfig.from_env(dict(env, PATHTRACER_GPU_ATROUS="1"))
+    k = a.features if a.features is not None else 4
+    a.features = None
+    return t, a, k
 
 
 def render(sc: scn.Scene, cfg: RenderConfig) -> np.ndarray:

@@ -377,6 +377,88 @@ def atrous(ctx: capi.Context, cfg: Optional[AtrousConfig], img: Optional[np.ndar
 _atrous = atrous  # (`render` has an argument of that name)
 
 
+@dataclass
+class TemporalConfig:
+    """The temporal accumulation of pt_temporal: alpha = the least weight of the current frame, max_len = where the
+    history length saturates, and the three tests a history tap has to pass (relative first-hit distance, normal, albedo)."""
+    alpha: float = 0.2
+    max_len: int = 32
+    tol_z: float = 0.1
+    n_min: float = 0.9
+    tol_a: float = 0.05
+
+    @classmethod
+    def from_env(cls, environ=None) -> Optional["TemporalConfig"]:
+        """PATHTRACER_GPU_TEMPORAL=1 (or true / on / yes) turns the accumulation on (None otherwise)."""
+        import os
+
+        env = os.environ if environ is None else environ
+        if env.get("PATHTRACER_GPU_TEMPORAL", "").lower() not in ("1", "true", "on", "yes"):
+            return None
+        return cls()
+
+    def c(self) -> capi.PtTemporalConfig:
+        return capi.PtTemporalConfig(float(self.alpha), float(self.tol_z), float(self.n_min), float(self.tol_a), int(self.max_len), 0)
+
+
+def temporal(ctx: capi.Context, cfg: Optional[TemporalConfig], filter: Optional[AtrousConfig], img: Optional[np.ndarray],
+             mean: Optional[np.ndarray] = None, var: Optional[np.ndarray] = None) -> dict:
+    """pt_temporal on ctx's open or last frame (cfg None = the defaults; filter None = no filter): blends the frame into the
+    context's reprojected history, stores the result as the new history and filters it.  img (uint8 [H, W, 4] or None) receives the
+    finished image, mean (float64 [H, W, 3]) and var (float64 [H, W]) the output and its variance.  Returns the pt_temporal_stats.
+    The frame needs features on, and the caller changes the seed from frame to frame (the blended variance assumes independent
+    frames)."""
+    if not capi.has("pt_temporal"):
+        raise RuntimeError("this libptcore.so has no pt_temporal (rebuild it)")
+    stride = 0
+    if img is not None:
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4 or img.strides[2] != 1 or img.strides[1] != 4:
+            raise ValueError("img must be uint8 [H, W, 4] with contiguous RGBA rows")
+        stride = int(img.strides[0])
+    if mean is not None and (mean.dtype != np.float64 or mean.ndim != 3 or mean.shape[2] != 3 or not mean.flags.c_contiguous):
+        raise ValueError("mean must be contiguous float64 [H, W, 3]")
+    if var is not None and (var.dtype != np.float64 or var.ndim != 2 or not var.flags.c_contiguous):
+        raise ValueError("var must be contiguous float64 [H, W]")
+    for a in (mean, var):
+        if a is not None and img is not None and a.shape[:2] != img.shape[:2]:
+            raise ValueError("mean / var must have the image's height and width")
+    c = cfg.c() if cfg is not None else None
+    f = filter.c() if filter is not None else None
+    st = capi.PtTemporalStats()
+    dp = C.POINTER(C.c_double)
+    capi.check(capi.load().pt_temporal(ctx.handle, C.byref(c) if c is not None else None, C.byref(f) if f is not None else None,
+                                       _ptr(img), stride, mean.ctypes.data_as(dp) if mean is not None else None,
+                                       var.ctypes.data_as(dp) if var is not None else None, C.byref(st)))
+    return st.as_dict()
+
+
+_temporal = temporal  # (`render` has an argument of that name)
+
+
+def temporal_read(ctx: capi.Context, mean: Optional[np.ndarray] = None, var: Optional[np.ndarray] = None,
+                  length: Optional[np.ndarray] = None) -> None:
+    """pt_temporal_read: the stored history into mean (float64 [H, W, 3]), var (float64 [H, W]) and length (int32 [H, W]: the
+    frames behind each pixel, 0 = a bad pixel).  Raises PtError (PT_ERR_STATE) when the history is empty."""
+    if mean is not None and (mean.dtype != np.float64 or mean.ndim != 3 or mean.shape[2] != 3 or not mean.flags.c_contiguous):
+        raise ValueError("mean must be contiguous float64 [H, W, 3]")
+    if var is not None and (var.dtype != np.float64 or var.ndim != 2 or not var.flags.c_contiguous):
+        raise ValueError("var must be contiguous float64 [H, W]")
+    if length is not None and (length.dtype != np.int32 or length.ndim != 2 or not length.flags.c_contiguous):
+        raise ValueError("length must be contiguous int32 [H, W]")
+    if len({a.shape[:2] for a in (mean, var, length) if a is not None}) > 1:
+        raise ValueError("mean / var / length must have the same height and width")
+    dp = C.POINTER(C.c_double)
+    capi.check(capi.load().pt_temporal_read(ctx.handle, mean.ctypes.data_as(dp) if mean is not None else None,
+                                            var.ctypes.data_as(dp) if var is not None else None,
+                                            length.ctypes.data_as(C.POINTER(C.c_int32)) if length is not None else None))
+
+
+def temporal_reset(ctx: capi.Context) -> None:
+    """pt_temporal_reset: empties the context's history (after a scene edit or a cut)."""
+    if capi.has("pt_temporal_reset"):
+        capi.check(capi.load().pt_temporal_reset(ctx.handle))
+
+
 def set_halves(ctx: capi.Context, on: bool) -> None:
     """pt_set_halves: later frames on ctx also collect the half-buffer sums SA, QA (even-indexed samples) and SB, QB (odd-indexed
     ones) of every pixel; off by default.  Such frames collect second moments too."""
@@ -491,7 +573,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            shading: str = "cpu", moments: Optional[np.ndarray] = None, noise: Optional[float] = None,
            noise_step: int = 16, adaptive: bool = False, min_spp: int = 0, counts: Optional[np.ndarray] = None,
            features: Optional[int] = None, atrous: Optional["AtrousConfig"] = None,
-           filtered_noise: Optional[float] = None, halves: bool = False) -> dict:
+           filtered_noise: Optional[float] = None, halves: bool = False,
+           temporal: Optional["TemporalConfig"] = None) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -526,6 +609,12 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     inf when no check ran) and spp_done.  Neither figure sees the bias the filter adds.  halves=True collects the half-buffer
     sums without the stop rule (read them with read_halves / atrous_halves afterwards); without the two arguments halves are off.
 
+    temporal=TemporalConfig() is for a caller that renders frame after frame on one context while the camera
+    moves: it turns moments and features on (k = 4 unless features= or the filter's config says otherwise), renders, and then
+    calls pt_temporal with atrous= as its filter (None: no filter); img is its output and the returned dict gains "temporal": the
+    pt_temporal_stats.  It excludes nothing that atrous= allows.  Change cfg.seed from frame to frame; call temporal_reset(ctx)
+    after editing the scene.
+
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
     Returns the pt_stats of the frame as a dict.
@@ -556,7 +645,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
                                or not counts.flags.c_contiguous):
         raise ValueError("counts needs adaptive=True and a contiguous uint32 [H, W] array")
     set_adaptive(ctx, noise if adaptive else None, min_spp, noise_step)
-    want_moments = moments is not None or noise is not None or atrous is not None or halves
+    want_moments = moments is not None or noise is not None or atrous is not None or halves or temporal is not None
     set_moments(ctx, want_moments)
     set_halves(ctx, halves or filtered_noise is not None)
     fstats = {"filtered_noise": float("inf"), "noise_model": float("inf")}
@@ -564,6 +653,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
         features = 0
         if atrous is not None:
             features = atrous.features if atrous.features is not None else (4 if scene_allows_features(sc, shading) else 0)
+        if temporal is not None and not features:  # (where the scene refuses features, pt_temporal says so)
+            features = 4
     set_features(ctx, features)
     if moments is not None and (moments.dtype != np.float64 or moments.shape != (cfg.height, cfg.width, 3)
                                 or not moments.flags.c_contiguous):
@@ -583,7 +674,9 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
             if moments is not None:
                 read_moments(ctx, moments)
             d.update(noise=noise_estimate(ctx)["noise"])
-            if atrous is not None:  # the filtered image takes the place of the plain finish
+            if temporal is not None:  # the accumulated (and filtered) image takes the place of the plain finish
+                d["temporal"] = _temporal(ctx, temporal, atrous, img)
+            elif atrous is not None:  # the filtered image takes the place of the plain finish
                 d["atrous"] = _atrous(ctx, atrous, img)
             if filtered_noise is not None:
                 d.update(fstats)
