@@ -1,6 +1,9 @@
 """Helpers of the adaptive-sampling tests (test_adaptive_cpu.py, test_adaptive_gpu.py): the case the issue fixes, a plain-Python
 restatement of the block rule on per-sample radiances (independent of hip.adaptive_plan_host), and the self-consistency check
-that needs no oracle: every block of an adaptive frame is bit-equal to the same block of a plain frame of the block's count."""
+that needs no oracle: every block of an adaptive frame is bit-equal to the same block of a plain frame of the block's count.
+For test_adaptive_scale_gpu.py and the probe of the two check kernels (adaptive_probe_support.py): the NumPy statement of
+block_noise_kernel's arithmetic in its own order (pixel_e2, butterfly), the order of a device's active list (block_order) and
+the predictor of an adaptive frame from the plain frames of its checks (predict)."""
 from __future__ import annotations
 
 import math
@@ -176,3 +179,123 @@ def assert_same_planes(got: dict, ref: dict, tag=""):
         a, b = got[k], ref[k]
         assert a.dtype == b.dtype and a.shape == b.shape, (tag, k)
         assert np.array_equal(a.view(np.uint64) if a.dtype == np.float64 else a, b.view(np.uint64) if b.dtype == np.float64 else b), (tag, k)
+
+
+# ---------------------------------------------------------------- the check in NumPy, and frames whose lists outgrow a wave and a strip
+def pixel_e2(acc, m2, n: int) -> np.ndarray:
+    """pixel_e2 of csrc/pt_kernels.h with its operations in its order, elementwise over acc, m2 = [3, ...] (n >= 2): bit-equal to the
+    device by IEEE arithmetic.  A NaN or infinite e2 comes back as 0."""
+    nn, n1 = float(n), float(n - 1)
+    msum, vsum = 0.0, 0.0
+    with np.errstate(all="ignore"):
+        for c in range(3):
+            m = acc[c] / nn
+            d = m2[c] / nn - m * m
+            d = np.where(d < 0.0, 0.0, d)  # (a NaN stays a NaN)
+            msum = msum + m
+            vsum = vsum + d / n1
+        den = msum / 3.0
+        den = np.where(den < 0.01, 0.01, den)
+        e2 = (vsum / 3.0) / (den * den)
+        bad = ~((e2 - e2) == 0.0)
+    return np.where(bad, 0.0, e2)
+
+
+def butterfly(e2: np.ndarray) -> np.ndarray:
+    """Lane 0's value after the xor butterfly of block_noise_kernel over [..., 64] lanes (zeros in the lanes outside the frame)."""
+    idx = np.arange(64)
+    s = np.array(e2, np.float64)
+    for off in (32, 16, 8, 4, 2, 1):
+        s = s + s[..., idx ^ off]
+    return s[..., 0]
+
+
+def block_order(w: int, h: int, shard_index: int, shard_count: int) -> np.ndarray:
+    """The blocks of one device that have a pixel inside the frame, in the order of its first active list: tile
+    t = shard_index + lt * shard_count, then sub-block sb = 0..15.  int64 [n, 3]: (blk = lt * 16 + sb, by, bx), by and bx being
+    the block's row and column in the frame's 8 x 8 grid."""
+    ntx, nty = (w + 31) // 32, (h + 31) // 32
+    out = []
+    for lt, t in enumerate(range(shard_index, ntx * nty, shard_count)):
+        ty, tx = divmod(t, ntx)
+        for sb in range(16):
+            by, bx = ty * 4 + (sb >> 2), tx * 4 + (sb & 3)
+            if by * 8 < h and bx * 8 < w:
+                out.append((lt * 16 + sb, by, bx))
+    return np.asarray(out, np.int64).reshape(-1, 3)
+
+
+def block_noise_map(acc: np.ndarray, m2: np.ndarray, n: int) -> np.ndarray:
+    """b of every 8 x 8 block of a plain n-sample frame (acc, m2 = [h, w, 3]) as block_noise_kernel computes it, [nby, nbx]."""
+    h, w = acc.shape[:2]
+    nby, nbx = (h + 7) // 8, (w + 7) // 8
+    e2 = np.zeros((nby * 8, nbx * 8))
+    inside = np.zeros((nby * 8, nbx * 8), bool)
+    inside[:h, :w] = True
+    if n >= 2:
+        e2[:h, :w] = pixel_e2(np.moveaxis(acc, 2, 0), np.moveaxis(m2, 2, 0), n)
+
+    def lanes(a):  # [nby, nbx, 64], lane p = row * 8 + column inside the block
+        return a.reshape(nby, 8, nbx, 8).transpose(0, 2, 1, 3).reshape(nby, nbx, 64)
+
+    k = lanes(inside).sum(axis=2)
+    return np.sqrt(butterfly(lanes(e2)) / k) if n >= 2 else np.full((nby, nbx), np.inf)
+
+
+def predict(frames: dict, target: float, step: int, min_spp: int, cap: int, ndev: int = 1) -> dict:
+    """An adaptive frame from plain ones.  frames = {n: (acc, m2)} of the plain frames at n = step, 2 * step, ..., cap.  Returns
+    counts [nby, nbx], noise {n: [nby, nbx]}, lists {device: [the (by, bx) rows of its list after each check]}, margin (the
+    smallest relative distance of a deciding (block, check) from the target), worst (the largest noise among the blocks the
+    last check kept, 0 with none), active (their number) and samples."""
+    h, w = next(iter(frames.values()))[0].shape[:2]
+    nby, nbx = (h + 7) // 8, (w + 7) // 8
+    checks = list(range(step, cap, step)) + [cap]
+    assert sorted(frames) == checks
+    counts = np.zeros((nby, nbx), np.int64)
+    active = np.ones((nby, nbx), bool)
+    noise, after = {}, []
+    margin = np.inf
+    for n in checks:
+        counts[active] = n
+        noise[n] = b = block_noise_map(frames[n][0], frames[n][1], n)
+        if n >= max(min_spp, 2):
+            margin = min(margin, float(np.min(np.abs(b[active] - target) / target))) if active.any() and target > 0 else margin
+            active = active & ~(b <= target)
+        after.append(active.copy())
+        if not active.any():
+            break
+    lists = {}
+    for d in range(ndev):
+        order = block_order(w, h, d, ndev)
+        lists[d] = [order[a[order[:, 1], order[:, 2]]][:, 1:] for a in after]
+    last = noise[max(noise)]
+    return {"counts": counts, "noise": noise, "lists": lists, "margin": margin, "worst": float(last[active].max()) if active.any() else 0.0,
+            "active": int(active.sum()), "samples": int(expand(counts, w, h).astype(np.uint64).sum()), "checks": checks[:len(after)]}
+
+
+# scene, width, height, depth, seed, cap, step, min_spp: example_simple at 293 x 253 = 32 rows of 37 blocks in 8 rows of 10 tiles, both edges cut.
+# SCALE_LISTS: the list lengths after the checks at 8, 16, 24 and 32 samples per (target, devices), device by device, computed from
+# the oracle's per-sample radiances on the CPU (the nearest (block, check) is 2.9e-4 of the target away at 0.30, 3.9e-5 at 0.45).
+SCALE = ("example_simple", 293, 253, 4, 1, 32, 8, 0)
+SCALE_LISTS = {(0.30, 1): [[1035, 801, 599, 439]],
+               (0.30, 3): [[364, 289, 216, 153], [348, 282, 206, 157], [323, 230, 177, 129]],
+               (0.45, 3): [[265, 114, 60, 35], [257, 98, 51, 34], [209, 89, 38, 32]]}
+
+
+def scale_frames(ctx, sc=None) -> dict:
+    """{n: (rgba, accum, m2)} of the plain frames of SCALE at every check's count, rendered on ctx."""
+    from conftest import scene_path
+    from path_trace_golang_amd import hip, scene
+
+    name, w, h, depth, seed, cap, step, _ = SCALE
+    sc = sc or scene.load(scene_path(name))
+    out = {}
+    for n in range(step, cap + 1, step):
+        img = np.zeros((h, w, 4), np.uint8)
+        acc = np.zeros((h, w, 3))
+        m2 = np.zeros((h, w, 3))
+        hip.render(sc, hip.RenderConfig(w, h, n, depth, seed), img, None, acc, ctx=ctx, moments=m2)
+        for a in (img, acc, m2):
+            a.setflags(write=False)
+        out[n] = (img, acc, m2)
+    return out

@@ -2,7 +2,11 @@
 resolve, moments, fog and noise).  The reference of the main case is the oracle: the count map predicted from its
 per-sample radiances (adaptive_support.CASE, preconditions in test_adaptive_cpu.py) must come back exactly, and every block must
 hold the oracle's n-sample pixels.  Where the oracle is slow or absent the check is self-consistency: a block that stopped at n
-is bit-equal to the same block of a plain n-sample frame of the same context."""
+is bit-equal to the same block of a plain n-sample frame of the same context.
+
+No frame here has more than 54 blocks on a device.  Lists longer than one wave and one strip of compact_kernel are in
+test_adaptive_scale_gpu.py (frames of 1184 blocks) and test_adaptive_probe_gpu.py (the two check kernels by themselves, through
+tests/adaptive_probe.hip, built by adaptive_probe_support.py)."""
 from __future__ import annotations
 
 import copy
