@@ -14,41 +14,9 @@ import pytest
 import atrous_support as at
 import moments_support as ms
 from conftest import ROOT, SCENE_NAMES
+from denoise_probe_support import CONFIGS, random_inputs
 
 ENTRY_POINTS = ("pt_set_features", "pt_read_features", "pt_atrous")
-
-
-def random_inputs(w, h, seed):
-    """Sums of a frame with every special case the model names: counts 2..64, pixels with var = 0, with Q/n < c^2, with NaN and
-    infinite sums, pixels whose feature samples all missed (h = 0), smooth regions and edges in every guide."""
-    r = np.random.default_rng(seed)
-    n = r.integers(2, 65, (h, w)).astype(np.uint32)
-    base = np.where(np.arange(w)[None, :, None] < w // 2, 0.2, 1.5) + 0.3 * r.random((h, w, 3))
-    mean = base * (1 + 0.4 * r.standard_normal((h, w, 3)))
-    S = mean * n[..., None]
-    Q = (mean * mean + (0.5 * base * r.random((h, w, 3))) ** 2 * n[..., None]) * n[..., None]
-    S[1, 2] = 0.0; Q[1, 2] = 0.0                      # var = 0 exactly, l = 0
-    S[3, 5] = 3.0 * n[3, 5]; Q[3, 5] = 9.0 * n[3, 5]  # var = 0 exactly
-    Q[4, 7] = 0.0; Q[h - 1, w - 1] = 0.0              # Q/n < c^2: counts as 0
-    S[6, 9, 1] = np.nan
-    S[7, 11, 0] = np.inf
-    Q[8, 13, 2] = np.inf                              # var infinite, mean finite
-    Q[0, 0, 0] = np.nan
-    S[h - 2, w - 3, 2] = -np.inf
-    k = 4.0
-    hits = r.integers(0, 5, (h, w)).astype(np.float64)
-    hits[2, 2] = 0; hits[5, 20] = 0
-    nrm = r.standard_normal((h, w, 3))
-    nrm /= np.linalg.norm(nrm, axis=2, keepdims=True)
-    nrm[:, : w // 3] = (0.0, 1.0, 0.0)
-    fn = nrm * hits[..., None]
-    fa = np.where(np.arange(h)[:, None, None] < h // 2, 0.8, 0.1) * r.random((h, w, 3)) * hits[..., None]
-    fd = np.stack([hits * (2.0 + 5.0 * r.random((h, w))), hits, np.full((h, w), k)], axis=2)
-    return S, Q, n, (fn, fa, fd)
-
-
-CONFIGS = [dict(), dict(sigma_n=0.0), dict(sigma_z=0.0), dict(sigma_a=0.0), dict(sigma_n=0.0, sigma_z=0.0, sigma_a=0.0),
-           dict(sigma_l=0.5, sigma_n=2.0, sigma_z=1.0, sigma_a=5.0)]
 
 
 @pytest.mark.parametrize("size", [(40, 24), (37, 21)])

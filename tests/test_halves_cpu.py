@@ -21,10 +21,10 @@ ENTRY_POINTS = ("pt_set_halves", "pt_read_halves", "pt_atrous_halves")
 
 
 def random_halves(w, h, seed):
-    """The four sums of a frame with counts 4..64 and, per half, every special case test_atrous_cpu.random_inputs names: pixels
+    """The four sums of a frame with counts 4..64 and, per half, every special case denoise_probe_support.random_inputs names: pixels
     with var = 0, with Q/n < c^2, with NaN and infinite sums -- in both halves, in half A only and in half B only -- and the
     feature planes of that function (pixels whose feature samples all missed, smooth regions and edges in every guide)."""
-    from test_atrous_cpu import random_inputs
+    from denoise_probe_support import random_inputs
 
     r = np.random.default_rng(seed)
     _, _, _, feats = random_inputs(w, h, seed)

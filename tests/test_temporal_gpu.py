@@ -248,3 +248,44 @@ def test_render_with_temporal_returns_the_accumulated_image():
         st = hip.render(ts.product_scene(name, 1), hip.RenderConfig(W, H, SPP, depth, 2), plain, ctx=ctx)
         assert "temporal" not in st and not np.array_equal(plain, img)  # off again without the argument
     ref.close()
+
+
+# ---------------------------------------------------------------- 5. more than one device, and past the clamp
+def test_three_virtual_devices_give_the_history_of_one():
+    """pt_temporal gathers its inputs to devices[0] first: a moving sequence on three virtual devices (40 x 24 is two tiles, so the
+    third holds none) against the one-device context and against the restatement."""
+    from path_trace_golang_amd import capi
+
+    name, depth = "metal_glass_room", 6
+    ref = ts.Accumulator("ref")
+    with capi.Context(ndev=1) as one, capi.Context(devices=[0, 0, 0]) as three:
+        for f in range(3):
+            fr1 =_frame(one, name, f, W, H, SPP, depth)
+            fr3 = _frame(three, name, f, W, H, SPP, depth)
+            assert at.same_bits(fr1["S"], fr3["S"]) and at.same_bits(fr1["Q"], fr3["Q"])
+            assert all(at.same_bits(x, y) for x, y in zip(fr1["feats"], fr3["feats"]))
+            a = ts.gpu_frame(one, ts.temporal_config(), at.atrous_config(), W, H)
+            b = _check(three, ref, fr3, W, H, dict(), ("three devices", f))
+            ts.assert_same_frame(a, b, ("one device vs three", f))
+            for k in ("noise_before", "noise_blended", "noise_after", "mean_len"):  # devices[0] runs the kernels over the gathered planes: the same tree
+                assert a[k] == b[k], (f, k)
+        assert b["reprojected"] > W * H // 2 and b["hist_len"].max() == 3
+    ref.close()
+
+
+def test_eight_frames_pass_the_clamp_and_reach_the_exponential_regime():
+    """example_simple at 37 x 21, 8 spp, alpha = 0.5, max_len = 3: from the fourth frame on len' is cut to 3, and alpha > 1 / (L + 1)
+    holds wherever L >= 2 -- the product's own pt_temporal against the restatement, frame by frame."""
+    from path_trace_golang_amd import capi
+
+    name, depth, w, h, spp = "example_simple", 4, 37, 21, 8
+    tcfg = dict(alpha=0.5, max_len=3)
+    ref = ts.Accumulator("ref")
+    with capi.Context(ndev=1) as ctx:
+        for f in range(8):
+            got = _check(ctx, ref, _frame(ctx, name, f, w, h, spp, depth), w, h, dict(), (name, f), **tcfg)
+            assert got["hist_len"].max() == min(f + 1, 3) and got["bad_pixels"] == 0
+            if f > 0:
+                assert got["reprojected"] > w * h // 2 and got["reprojected"] + got["disoccluded"] == w * h
+        assert np.count_nonzero(got["hist_len"] == 3) > w * h // 2
+    ref.close()
