@@ -68,6 +68,8 @@ var (
 	temporalSet bool        // false: PATHTRACER_GPU_TEMPORAL decides
 	temporalOn  bool
 	lastTemporal TemporalStats // pt_temporal_stats of the last frame (zero unless it was accumulated)
+	clipSet      bool          // false: PATHTRACER_GPU_TEMPORAL_CLIP decides
+	clipGamma    float64
 
 	filteredSet    bool        // false: PATHTRACER_GPU_FILTERED_NOISE decides
 	filteredTarget float64     // the noise target on the filtered frame (0 = off)
@@ -245,6 +247,54 @@ func LastTemporal() TemporalStats {
 	mu.Lock()
 	defer mu.Unlock()
 	return lastTemporal
+}
+
+// TemporalClip mirrors struct pt_temporal_clip_stats: the history clip of the last accumulated frame.
+type TemporalClip struct {
+	Gamma                float64
+	Clipped, Reprojected uint64
+}
+
+// SetTemporalClip sets the history clip of the accumulation (pt_temporal_set_clip, DESIGN 3.13a): before the blend the reprojected
+// history is clamped to the frame's mean +- gamma * sqrt(var_frame + var_history).  0 = off (the default); 2.5 is the recommended
+// value; a NaN, a negative or an infinite gamma is taken as 0.  Read by Render when the accumulation is on.  Not set:
+// PATHTRACER_GPU_TEMPORAL_CLIP decides.
+func SetTemporalClip(gamma float64) {
+	mu.Lock()
+	defer mu.Unlock()
+	if math.IsNaN(gamma) || math.IsInf(gamma, 0) || gamma < 0 {
+		gamma = 0
+	}
+	clipSet, clipGamma = true, gamma
+}
+
+// TemporalClipStats reports pt_temporal_clip_stats of the package's context: the gamma, the clipped and the reprojected pixels of
+// the last accumulated frame.  An error while the history is empty.
+func TemporalClipStats() (TemporalClip, error) {
+	mu.Lock()
+	defer mu.Unlock()
+	if ctx == nil {
+		return TemporalClip{}, errors.New("pt_temporal_clip_stats: no context yet")
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	var cs C.struct_pt_temporal_clip_stats
+	if rc := C.pt_temporal_clip_stats(ctx, &cs); rc != C.PT_OK {
+		return TemporalClip{}, lastError("pt_temporal_clip_stats")
+	}
+	return TemporalClip{Gamma: float64(cs.gamma), Clipped: uint64(cs.clipped), Reprojected: uint64(cs.reprojected)}, nil
+}
+
+// clipRule: the gamma in force (SetTemporalClip, else PATHTRACER_GPU_TEMPORAL_CLIP; unset or not a finite number >= 0: off).
+func clipRule() float64 {
+	if clipSet {
+		return clipGamma
+	}
+	g, err := strconv.ParseFloat(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_TEMPORAL_CLIP")), 64)
+	if err != nil || math.IsNaN(g) || math.IsInf(g, 0) || g < 0 {
+		return 0
+	}
+	return g
 }
 
 // temporalRule: whether the accumulation is in force (SetTemporal, else the environment).
@@ -583,6 +633,9 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 		ac := C.pt_atrous_config{iterations: C.int32_t(iters), sigma_l: 4, sigma_n: 0.1, sigma_z: 0.1, sigma_a: 0.2}
 		var tc *C.pt_temporal_config // nil: the defaults
 		var st C.pt_temporal_stats
+		if rc := C.pt_temporal_set_clip(ctx, C.double(clipRule())); rc != C.PT_OK {
+			return lastError("pt_temporal_set_clip")
+		}
 		if rc := C.pt_temporal(ctx, tc, &ac, (*C.uint8_t)(unsafe.Pointer(&img.Pix[0])), C.int32_t(img.Stride), nil, nil, &st); rc != C.PT_OK {
 			return lastError("pt_temporal")
 		}

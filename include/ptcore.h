@@ -564,8 +564,22 @@ int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean,
  *   pt_temporal_reset : empties the history (after a scene edit, a cut).  The history is also empty after pt_create and is dropped
  *                       by a call whose width x height differs from the history's.
  * The history is keyed by geometry alone: moving or edited objects are caught only by the distance, normal and albedo tests, so
- * the caller resets after an edit.  Known limit: a firefly in one frame stays in the history for several frames (no outlier
- * rejection before the blend).
+ * the caller resets after an edit.  Known limit: ghosting of view-dependent content.  Where what is seen at a pixel changes while
+ * its first-hit normal, distance and albedo still agree (a reflection, a refraction, a moving shadow edge), every tap passes and the
+ * history overrules the frame with another view's radiance; on test_scene that costs more than the history gains.
+ * The answer is the clip below.  (Firefly rejection in the frame is not done; the test sequences contain no firefly.)
+ *
+ * The history clip (additive to ABI 4; step 7a of csrc/pt_temporal.h): before the blend the reprojected history
+ * mean is clamped, per channel, to the frame's mean +- gamma * sqrt(var_frame + var_history).  It rectifies the history and rejects
+ * nothing in the frame: a noisy frame pixel has a wide interval.  Where both variances are zero the history becomes the frame.
+ *   pt_temporal_set_clip   : gamma for later pt_temporal calls of this context; it may change between frames of one history.
+ *                            0 = off, the default after pt_create: pt_temporal then gives the bits it gave before the clip existed.
+ *                            RECOMMENDED: 2.5 (the smallest of 2, 2.5, 3 that gains on test_scene and costs no other shipped scene
+ *                            more than a twentieth).  NaN, negative or infinite: PT_ERR_INVALID.
+ *   pt_temporal_clip_stats : of the last pt_temporal that succeeded: the gamma it ran with, the reprojected pixels and those of them
+ *                            whose history the clip changed (0 when it ran with the clip off).  PT_ERR_STATE while the history is
+ *                            empty.  The struct shares its name with the function: write `struct pt_temporal_clip_stats`.
+ * Every refusal leaves the context and the history as they were.
  */
 typedef struct pt_temporal_config {
     double alpha;         /* 0..1: the least weight of the current frame */
@@ -593,6 +607,15 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
                     double *mean, double *var, pt_temporal_stats *stats);
 int32_t pt_temporal_read(pt_ctx *ctx, double *mean, double *var, int32_t *len);
 int32_t pt_temporal_reset(pt_ctx *ctx);
+
+struct pt_temporal_clip_stats {
+    double gamma;         /* what the call ran with; 0 = the clip was off */
+    uint64_t clipped;     /* reprojected pixels with at least one channel of the history changed */
+    uint64_t reprojected;
+};
+
+int32_t pt_temporal_set_clip(pt_ctx *ctx, double gamma);
+int32_t pt_temporal_clip_stats(pt_ctx *ctx, struct pt_temporal_clip_stats *out);
 
 /*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the

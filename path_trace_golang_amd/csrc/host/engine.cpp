@@ -4,6 +4,7 @@
 
 #include <cctype>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -70,6 +71,8 @@ struct Core {
     decltype(&pt_atrous_halves) atrous_halves = nullptr;
     decltype(&pt_temporal) temporal = nullptr;  // optional, as set_shading
     decltype(&pt_temporal_reset) temporal_reset = nullptr;
+    decltype(&pt_temporal_set_clip) temporal_set_clip = nullptr;  // optional, as set_shading
+    int32_t (*temporal_clip_stats)(pt_ctx *, struct pt_temporal_clip_stats *) = nullptr;
     std::string error;  // sticky load error, like the reference's cached GL init failure (gpu.go:279-286)
 };
 
@@ -87,6 +90,7 @@ int g_atrous = -1;  // -1: not set yet, PATHTRACER_GPU_ATROUS / _ITERS decide
 int g_atrous_iters = 5;
 double g_filtered_noise = -1;  // < 0: not set yet, PATHTRACER_GPU_FILTERED_NOISE decides
 int g_temporal = -1;  // -1: not set yet, PATHTRACER_GPU_TEMPORAL decides
+double g_temporal_clip = -1;  // < 0: not set yet, PATHTRACER_GPU_TEMPORAL_CLIP decides
 int g_features = -1;  // -1: not set yet, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows, else 0)
 std::mutex g_mu;  // requests are serialised, like the reference's single GL worker (gpu.go:2534-2546)
 
@@ -144,6 +148,8 @@ bool load_core() {
     c.atrous_halves = reinterpret_cast<decltype(c.atrous_halves)>(dlsym(h, "pt_atrous_halves"));
     c.temporal = reinterpret_cast<decltype(c.temporal)>(dlsym(h, "pt_temporal"));
     c.temporal_reset = reinterpret_cast<decltype(c.temporal_reset)>(dlsym(h, "pt_temporal_reset"));
+    c.temporal_set_clip = reinterpret_cast<decltype(c.temporal_set_clip)>(dlsym(h, "pt_temporal_set_clip"));
+    c.temporal_clip_stats = reinterpret_cast<decltype(c.temporal_clip_stats)>(dlsym(h, "pt_temporal_clip_stats"));
     if (c.abi_version() != PT_ABI_VERSION) {
         g_core.error = "libptcore.so ABI version mismatch";
         dlclose(h);
@@ -465,6 +471,29 @@ void ResetTemporal() {
     if (g_ctx && g_core.temporal_reset) (void)g_core.temporal_reset(g_ctx);
 }
 
+double TemporalClipFromEnv() {
+    const char *e = std::getenv("PATHTRACER_GPU_TEMPORAL_CLIP");
+    if (!e || !*e) return 0;
+    char *end = nullptr;
+    const double g = std::strtod(e, &end);
+    return end != e && *end == 0 && std::isfinite(g) && g >= 0 ? g : 0;
+}
+
+void SetTemporalClip(double gamma) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_temporal_clip = std::isfinite(gamma) && gamma >= 0 ? gamma : 0;
+}
+
+bool TemporalClipStats(double &gamma, uint64_t &clipped, uint64_t &reprojected) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    struct pt_temporal_clip_stats cs;
+    if (!g_ctx || !g_core.temporal_clip_stats || g_core.temporal_clip_stats(g_ctx, &cs) != PT_OK) return false;
+    gamma = cs.gamma;
+    clipped = cs.clipped;
+    reprojected = cs.reprojected;
+    return true;
+}
+
 void SetFeatures(int k) {
     std::lock_guard<std::mutex> lk(g_mu);
     g_features = k >= 0 ? k : -1;
@@ -531,6 +560,8 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     // temporal accumulation (SetTemporal / PATHTRACER_GPU_TEMPORAL) brings the filter, the moments and the feature planes with it
     const bool temporal = g_temporal < 0 ? TemporalFromEnv() : g_temporal == 1;
     if (temporal && !g_core.temporal) return "temporal accumulation: libptcore.so lacks pt_temporal";
+    const double clip = temporal ? (g_temporal_clip < 0 ? TemporalClipFromEnv() : g_temporal_clip) : 0;
+    if (clip > 0 && !(g_core.temporal_set_clip && g_core.temporal_clip_stats)) return "temporal clip: libptcore.so lacks pt_temporal_set_clip";
     atrous = atrous || temporal;
     if (atrous && !(g_core.atrous && g_core.set_moments)) return "a-trous filter: libptcore.so lacks pt_atrous / pt_set_moments";
     // a noise target on the filtered frame (SetFilteredNoise / PATHTRACER_GPU_FILTERED_NOISE): the half-buffer sums and pt_atrous_halves
@@ -650,9 +681,13 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     std::memset(&ats, 0, sizeof ats);
     pt_temporal_stats tst;
     std::memset(&tst, 0, sizeof tst);
+    struct pt_temporal_clip_stats tcs;
+    std::memset(&tcs, 0, sizeof tcs);
     if (temporal && err.empty()) {  // the frame blended into the context's reprojected history, then filtered
         pt_atrous_config ac = {atrous_iters, 0, 4.0, 0.1, 0.1, 0.2};
-        if (g_core.temporal(g_ctx, nullptr, &ac, img.Pix.data(), img.Stride, nullptr, nullptr, &tst) != PT_OK) err = std::string("pt_temporal: ") + g_core.last_error();
+        if (g_core.temporal_set_clip && g_core.temporal_set_clip(g_ctx, clip) != PT_OK) err = std::string("pt_temporal_set_clip: ") + g_core.last_error();
+        if (err.empty() && g_core.temporal(g_ctx, nullptr, &ac, img.Pix.data(), img.Stride, nullptr, nullptr, &tst) != PT_OK) err = std::string("pt_temporal: ") + g_core.last_error();
+        if (err.empty() && clip > 0 && g_core.temporal_clip_stats(g_ctx, &tcs) != PT_OK) err = std::string("pt_temporal_clip_stats: ") + g_core.last_error();
         ats.atrous_ms = tst.temporal_ms;
         ats.noise_before = tst.noise_before;
         ats.noise_after = tst.noise_after;
@@ -672,6 +707,8 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         stats->temporal_ms = tst.temporal_ms;
         stats->mean_len = tst.mean_len;
         stats->noise_blended = tst.noise_blended;
+        stats->temporal_clip = tcs.gamma;
+        stats->clipped = tcs.clipped;
         stats->to_filtered_noise = to_filtered;
         stats->filtered_noise = hs.noise;
         stats->noise_model = hs.noise_model;

@@ -47,6 +47,8 @@ struct Stats {
     bool temporal = false;  // the image is pt_temporal's (SetTemporal): the frame blended into the reprojected history, then filtered
     uint64_t reprojected = 0, disoccluded = 0;  // pt_temporal_stats of the frame
     double temporal_ms = 0, mean_len = 0, noise_blended = 0;
+    double temporal_clip = 0;  // gamma of the history clip the frame ran with (SetTemporalClip; 0 = off)
+    uint64_t clipped = 0;      // pt_temporal_clip_stats of the frame: reprojected pixels whose history the clip changed
 };
 
 namespace hip {
@@ -104,6 +106,15 @@ void SetTemporal(bool on);
 bool Temporal();
 bool TemporalFromEnv();  // PATHTRACER_GPU_TEMPORAL = 1 / true / on / yes
 void ResetTemporal();    // pt_temporal_reset on the process-wide context
+// The history clip of the accumulation (pt_temporal_set_clip): before the blend the reprojected history is clamped to
+// the frame's mean +- gamma * sqrt(var_frame + var_history).  0 = off (the default); 2.5 is the recommended value; a NaN, a negative
+// or an infinite gamma is taken as 0.  Read by Render when the accumulation is on.  The initial value is
+// PATHTRACER_GPU_TEMPORAL_CLIP (TemporalClipFromEnv).
+void SetTemporalClip(double gamma);
+double TemporalClipFromEnv();  // PATHTRACER_GPU_TEMPORAL_CLIP = finite float >= 0, else 0: off
+// pt_temporal_clip_stats of the process-wide context: the gamma, the clipped and the reprojected pixels of the last accumulated
+// frame.  False while the history is empty (or the library lacks the entry point).
+bool TemporalClipStats(double &gamma, uint64_t &clipped, uint64_t &reprojected);
 void SetFeatures(int k);
 int GetFeatures();     // -1: not said
 int FeaturesFromEnv(); // PATHTRACER_GPU_FEATURES = int >= 0, else -1

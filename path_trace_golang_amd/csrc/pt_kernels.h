@@ -3569,10 +3569,13 @@ __global__ __launch_bounds__(PT_BLOCK) void halves_combine_kernel(const HalvesCo
 // history plane).  Both cameras ride in the argument block.  The kernel leaves the new history (plane per component) and the colour,
 // variance and guide buffers exactly as atrous_prep_kernel does, so atrous_kernel, atrous_noise_kernel and atrous_finish_kernel run on
 // them as they are.  The block's partial of the frame's own noise figure goes over noise_kernel's tree; the counts are integers.
+// The history clip (step 7a, C.clip_gamma > 0) works on c_r, var_r and var_i where blend_pixel already holds them; its count rides
+// the same reduction.
 struct TemporalPartial {
     double sum_before;            // the block's sum of e2 of (c_i, var_i)
     unsigned long long len_sum;   // ... of len'
     uint32_t reprojected, disoccluded;
+    uint32_t clipped;             // reprojected pixels whose history step 7a changed (0 with C.clip_gamma == 0)
 };
 
 struct TemporalArgs {
@@ -3592,12 +3595,12 @@ struct TemporalArgs {
 
 __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A) {
     __shared__ double s_sum[PT_BLOCK / PT_WAVE];
-    __shared__ uint32_t s_cnt[PT_BLOCK / PT_WAVE][3];
+    __shared__ uint32_t s_cnt[PT_BLOCK / PT_WAVE][4];
     const int32_t x = (int32_t)(blockIdx.x * 32u + (threadIdx.x & 31u));
     const int32_t y = (int32_t)(blockIdx.y * 8u + (threadIdx.x >> 5));
     const size_t np = (size_t)A.V.W * (size_t)A.V.H;
     double e2 = 0.0;
-    uint32_t rep = 0, dis = 0, lens = 0;
+    uint32_t rep = 0, dis = 0, lens = 0, clp = 0;
     if (x < A.V.W && y < A.V.H) {
         const size_t i = (size_t)y * (size_t)A.V.W + (size_t)x, i3 = 3 * i;
         const double S[3] = {A.acc[i3], A.acc[i3 + 1], A.acc[i3 + 2]};
@@ -3607,8 +3610,9 @@ __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A
         pta::prep_pixel(S, Q, A.cnt ? A.cnt[i] : A.n, A.fn + i3, A.fa + i3, A.fd + i3, c, var, g);
         const bool hit = A.fd[i3 + 1] > 0.0;
         int32_t len;
+        bool clipped;
         const ptt::Status st = ptt::blend_pixel(A.C, A.V, A.cam_h, A.hist, reinterpret_cast<const int32_t *>(A.hist + (size_t)PTT_LH * np), x, y,
-                                                c, var, g, hit, co, vo, len);
+                                                c, var, g, hit, co, vo, len, &clipped);
         ptt::store_history(A.hist_out, reinterpret_cast<int32_t *>(A.hist_out + (size_t)PTT_LH * np), np, i, co, vo, len, g, hit);
         A.col[i3] = co[0];
         A.col[i3 + 1] = co[1];
@@ -3619,6 +3623,7 @@ __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A
         rep = st == ptt::ST_REPROJECTED ? 1u : 0u;
         dis = st == ptt::ST_DISOCCLUDED ? 1u : 0u;
         lens = (uint32_t)len;
+        clp = clipped ? 1u : 0u;
     }
     double sum = e2;
     for (int off = 32; off > 0; off >>= 1) {
@@ -3626,6 +3631,7 @@ __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A
         rep += __shfl_xor(rep, off, 64);
         dis += __shfl_xor(dis, off, 64);
         lens += __shfl_xor(lens, off, 64);
+        clp += __shfl_xor(clp, off, 64);
     }
     const uint32_t wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63u) == 0) {
@@ -3633,17 +3639,19 @@ __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A
         s_cnt[wave][0] = rep;
         s_cnt[wave][1] = dis;
         s_cnt[wave][2] = lens;
+        s_cnt[wave][3] = clp;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         TemporalPartial r;
         r.sum_before = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
-        r.reprojected = r.disoccluded = 0;
+        r.reprojected = r.disoccluded = r.clipped = 0;
         r.len_sum = 0;
         for (int w = 0; w < PT_BLOCK / PT_WAVE; w++) {
             r.reprojected += s_cnt[w][0];
             r.disoccluded += s_cnt[w][1];
             r.len_sum += s_cnt[w][2];
+            r.clipped += s_cnt[w][3];
         }
         A.partial[blockIdx.y * gridDim.x + blockIdx.x] = r;
     }

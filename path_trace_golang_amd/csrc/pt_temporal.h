@@ -37,6 +37,20 @@
 //          |z_h - zexp| <= tol_z * zexp,   N_i . N_h >= n_min,   dr*dr + dg*dg + db*db <= tol_a * tol_a   ((dr, dg, db) = A_i - A_h).
 //   7. Over the valid taps, in tap order from 0:  sw = sw + w;  sc_k = sc_k + w * c_h,k;  sv = sv + (w * w) * var_h;
 //      L = the smallest len_h.  Unless sw > 0.01 there is no history.   c_r,k = sc_k / sw;  var_r = sv / (sw * sw).
+//  7a. Clip (gamma > 0 only; gamma = 0, the default, skips this step and leaves every bit as it is without it):
+//          s = var_i + var_r;   half = gamma * sqrt(s > 0 ? s : 0)
+//          per channel k:  lo = c_i,k - half;  hi = c_i,k + half;
+//                          c_r,k = c_r,k < lo ? lo : (c_r,k > hi ? hi : c_r,k)
+//      var_r and L stay as they are.  A reprojected pixel is `clipped` when any channel changed (a c_r,k that lies exactly on a
+//      bound did not).  Both comparisons are false on a NaN, so a NaN half changes nothing.  The variances are the
+//      model's channel-mean variances, applied to every channel.  The clip rectifies the HISTORY: the reprojection is keyed by
+//      first-hit geometry alone, and where what is seen at a pixel changed although normal, distance and albedo still agree (a
+//      reflection, a refraction, a shadow that moved) the history holds another view's radiance -- ghosting.  The frame says, with
+//      its own variance, how far the truth can lie from c_i; the history is pulled to within that.  Consequences:
+//        - Where frame and history both have zero variance (emitters, sky) half = 0 and the history becomes the frame exactly.
+//        - A firefly in the FRAME has a large var_i, so the clip is loose there: it rejects no frame outliers.
+//        - A dark pixel whose samples are all zero (c_i = 0, var_i = 0) pulls its history to within gamma * sqrt(var_r) of zero.
+//          That is a bias, and it is inside the measured tables.
 //   8. Blend:  r = 1 / (L + 1);  a = alpha > r ? alpha : r;   c'_k = c_r,k + a * (c_i,k - c_r,k);
 //          var' = ((1 - a) * (1 - a)) * var_r + (a * a) * var_i;   len' = min(L + 1, max_len).
 //      No history:  out = (c_i, var_i), len' = 1.
@@ -48,7 +62,7 @@
 // figure of a state is FILTER's.
 //
 // Counted: a pixel of step 1 is `bad`; a good pixel that reaches step 8 with history is `reprojected`; a good pixel that does not,
-// while the history is not empty, is `disoccluded`.
+// while the history is not empty, is `disoccluded`; a reprojected pixel that step 7a changed is also `clipped`.
 #pragma once
 
 #include <stdint.h>
@@ -70,6 +84,7 @@ struct Config {
     double alpha, tol_z, n_min, tol_a;
     int32_t max_len;
     int32_t have_history;  // 0: the history is empty
+    double clip_gamma = 0.0;  // step 7a; 0 = off (also what a zero-filled or default-constructed Config has)
 };
 
 // The frame's camera and size.
@@ -130,12 +145,13 @@ PT_HD int32_t floor_i(double f) {
 }
 
 // Steps 1 - 8 of pixel (x, y): c, var, g = the prep of the pixel, hit = h > 0; hd, hl = the history planes (read when
-// C.have_history) and ch its camera -> c', var', len'.
+// C.have_history) and ch its camera -> c', var', len'; *clipped (when asked for) = whether step 7a changed the history.
 PT_HD Status blend_pixel(const Config &C, const View &V, const ptd::DevCamera &ch, const double *__restrict__ hd, const int32_t *__restrict__ hl,
                          int32_t x, int32_t y, const double c[3], double var, const pta::Guide &g, bool hit, double co[3], double &vo,
-                         int32_t &len) {
+                         int32_t &len, bool *clipped = nullptr) {
     co[0] = c[0]; co[1] = c[1]; co[2] = c[2];
     vo = var;
+    if (clipped) *clipped = false;
     if (g.bad != 0.0) {
         len = 0;
         return ST_BAD;
@@ -179,8 +195,20 @@ PT_HD Status blend_pixel(const Config &C, const View &V, const ptd::DevCamera &c
         }
     }
     if (!(sw > 0.01)) return ST_DISOCCLUDED;
-    const double cr[3] = {s0 / sw, s1 / sw, s2 / sw};
+    double cr[3] = {s0 / sw, s1 / sw, s2 / sw};
     const double vr = sv / (sw * sw);
+    if (C.clip_gamma > 0.0) {
+        const double s = var + vr;
+        const double half = C.clip_gamma * ptm::f_sqrt(s > 0.0 ? s : 0.0);
+        bool any = false;
+        for (int k = 0; k < 3; k++) {
+            const double lo = c[k] - half, hi = c[k] + half;
+            const bool below = cr[k] < lo, above = cr[k] > hi;
+            cr[k] = below ? lo : (above ? hi : cr[k]);
+            any = any || below || above;
+        }
+        if (clipped) *clipped = any;
+    }
     const double r = 1.0 / (double)(L + 1);
     const double a = C.alpha > r ? C.alpha : r;
     const double om = 1.0 - a;

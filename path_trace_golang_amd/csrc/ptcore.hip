@@ -339,7 +339,9 @@ struct pt_ctx {
     DevCamera tp_cam{};
     uint64_t tp_serial = 0;
     int32_t tp_spp = 0;
-    uint64_t frames_opened = 0;       // pt_begin / pt_render frames of this context so far
+    double tp_clip = 0.0;             // pt_temporal_set_clip: gamma of step 7a for later calls (0 = off)
+    struct pt_temporal_clip_stats tp_clip_stats{};  // of the last pt_temporal that succeeded
+    uint64_t frames_opened = 0;      // pt_begin / pt_render frames of this context so far
     pt_adaptive adaptive{};
     DevBuf<uint32_t> f_seg, f_draw;
     size_t l_budget_bytes = (size_t)48 << 30;  // per-chunk job buffers (radiance, primary rays, path-state queues): a sixth of the 288 GB
@@ -3141,6 +3143,7 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
         }
     float kernel_ms = 0;
     const int next = ctx->tp_cur ^ 1;
+    struct pt_temporal_clip_stats cs = {ctx->tp_clip, 0, 0};
     auto run = [&]() -> int32_t {
         HIP_TRY(hipEventRecord(ev[0], d0.stream));
         ptk::TemporalArgs TA;
@@ -3148,6 +3151,7 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
         TA.C.alpha = c.alpha; TA.C.tol_z = c.tol_z; TA.C.n_min = c.n_min; TA.C.tol_a = c.tol_a;
         TA.C.max_len = c.max_len;
         TA.C.have_history = have ? 1 : 0;
+        TA.C.clip_gamma = ctx->tp_clip;
         TA.V.cam = fr.cam;
         TA.V.inv_width = fr.F.inv_width;
         TA.V.inv_height = fr.F.inv_height;
@@ -3204,6 +3208,10 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
         if (var) HIP_TRY(hipMemcpyAsync(var, ctx->at_var[cur].p, npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
         HIP_TRY(hipStreamSynchronize(d0.stream));
         HIP_TRY(hipEventElapsedTime(&kernel_ms, ev[0], ev[2]));
+        for (const ptk::TemporalPartial &p : tpart) {
+            cs.clipped += p.clipped;
+            cs.reprojected += p.reprojected;
+        }
         if (stats) {
             pt_temporal_stats st;
             std::memset(&st, 0, sizeof st);
@@ -3243,9 +3251,28 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
     ctx->tp_cam = fr.cam;
     ctx->tp_serial = fr.serial;
     ctx->tp_spp = fr.done_spp;
+    ctx->tp_clip_stats = cs;
     if (std::getenv("PTCORE_VERBOSE"))
-        std::fprintf(stderr, "ptcore: pt_temporal %d filter iterations, temporal_kernel %.3f ms, %.3f ms host wall (gathers included)\n",
-                     filter ? f.iterations : 0, kernel_ms, std::chrono::duration<double, std::milli>(clk::now() - t0).count());
+        std::fprintf(stderr,
+                     "ptcore: pt_temporal %d filter iterations, clip gamma %g: clipped %llu of %llu reprojected, temporal_kernel %.3f ms, "
+                     "%.3f ms host wall (gathers included)\n",
+                     filter ? f.iterations : 0, cs.gamma, (unsigned long long)cs.clipped, (unsigned long long)cs.reprojected, kernel_ms,
+                     std::chrono::duration<double, std::milli>(clk::now() - t0).count());
+    return PT_OK;
+}
+
+int32_t pt_temporal_set_clip(pt_ctx *ctx, double gamma) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!(gamma >= 0.0) || std::isinf(gamma)) return fail(PT_ERR_INVALID, "pt_temporal_set_clip: gamma must be a finite number >= 0 (0 = off)");
+    ctx->tp_clip = gamma;
+    return PT_OK;
+}
+
+int32_t pt_temporal_clip_stats(pt_ctx *ctx, struct pt_temporal_clip_stats *out) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!out) return fail(PT_ERR_INVALID, "pt_temporal_clip_stats: out is null");
+    if (!ctx->tp_valid) return fail(PT_ERR_STATE, "pt_temporal_clip_stats: the history is empty (pt_temporal first)");
+    *out = ctx->tp_clip_stats;
     return PT_OK;
 }
 

@@ -63,7 +63,8 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 moments: Optional[np.ndarray] = None, noise: Optional[float] = None, noise_step: Optional[int] = None,
                 adaptive: Optional[bool] = None, min_spp: Optional[int] = None, counts: Optional[np.ndarray] = None,
                 features: Optional[int] = None, atrous: Optional["hip.AtrousConfig"] = None,
-                filtered_noise: Optional[float] = None, temporal: Optional["hip.TemporalConfig"] = None) -> dict:
+                filtered_noise: Optional[float] = None, temporal: Optional["hip.TemporalConfig"] = None,
+                temporal_clip: Optional[float] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
@@ -77,7 +78,9 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     below it; None takes PATHTRACER_GPU_FILTERED_NOISE (hip.filtered_noise_from_env), off by default and ignored without the filter
     or beside a noise target.  `temporal` is hip.render's: the frame is blended into the history the process-wide
     context keeps from call to call (change cfg.seed from frame to frame); None takes PATHTRACER_GPU_TEMPORAL (temporal_setup),
-    which also turns on moments, 4 feature samples (unless PATHTRACER_GPU_FEATURES says otherwise) and the filter."""
+    which also turns on moments, 4 feature samples (unless PATHTRACER_GPU_FEATURES says otherwise) and the filter.  `temporal_clip`
+    is hip.render's; None takes PATHTRACER_GPU_TEMPORAL_CLIP=<gamma> (hip.temporal_clip_from_env; unset = off),
+    which is read only when PATHTRACER_GPU_TEMPORAL turned the accumulation on."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -95,6 +98,8 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
         if temporal is not None:
             atrous = atrous if atrous is not None else t_atrous
             features = features if features is not None else t_features
+            if temporal_clip is None:
+                temporal_clip = hip.temporal_clip_from_env()
     if atrous is None:
         atrous = hip.AtrousConfig.from_env()
     if features is None:
@@ -104,7 +109,7 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     return hip.render(sc, gcfg, img, progress, shading=model, features=features, atrous=atrous, moments=moments, noise=noise,
                       noise_step=noise_step if noise_step is not None else ncfg.step, adaptive=bool(adaptive) and noise is not None,
                       min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts, filtered_noise=filtered_noise,
-                      temporal=temporal)
+                      temporal=temporal, temporal_clip=temporal_clip if temporal is not None else None)
 
 
 def temporal_setup(environ=None):

@@ -459,6 +459,39 @@ def temporal_reset(ctx: capi.Context) -> None:
         capi.check(capi.load().pt_temporal_reset(ctx.handle))
 
 
+def temporal_set_clip(ctx: capi.Context, gamma: float) -> None:
+    """pt_temporal_set_clip: later pt_temporal calls on ctx clamp the reprojected history to the frame's mean
+    +- gamma * sqrt(var_frame + var_history) before the blend.  0 = off, the default; 2.5 is the recommended value.
+    Raises PtError (PT_ERR_INVALID) for a NaN, a negative or an infinite gamma."""
+    if not capi.has("pt_temporal_set_clip"):
+        raise RuntimeError("this libptcore.so has no pt_temporal_set_clip (rebuild it)")
+    capi.check(capi.load().pt_temporal_set_clip(ctx.handle, float(gamma)))
+
+
+def temporal_clip_stats(ctx: capi.Context) -> dict:
+    """pt_temporal_clip_stats: dict(gamma, clipped, reprojected) of the last pt_temporal that succeeded on ctx.  Raises PtError
+    (PT_ERR_STATE) while the history is empty."""
+    if not capi.has("pt_temporal_clip_stats"):
+        raise RuntimeError("this libptcore.so has no pt_temporal_clip_stats (rebuild it)")
+    st = capi.PtTemporalClipStats()
+    capi.check(capi.load().pt_temporal_clip_stats(ctx.handle, C.byref(st)))
+    return st.as_dict()
+
+
+def temporal_clip_from_env(environ=None) -> float:
+    """PATHTRACER_GPU_TEMPORAL_CLIP=<gamma>: the clip of the RenderInto path when PATHTRACER_GPU_TEMPORAL is on.  Unset, empty or
+    not a finite number >= 0: 0.0 (off)."""
+    import math
+    import os
+
+    env = os.environ if environ is None else environ
+    try:
+        g = float(env.get("PATHTRACER_GPU_TEMPORAL_CLIP", "") or 0.0)
+    except ValueError:
+        return 0.0
+    return g if math.isfinite(g) and g >= 0.0 else 0.0
+
+
 def set_halves(ctx: capi.Context, on: bool) -> None:
     """pt_set_halves: later frames on ctx also collect the half-buffer sums SA, QA (even-indexed samples) and SB, QB (odd-indexed
     ones) of every pixel; off by default.  Such frames collect second moments too."""
@@ -574,7 +607,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            noise_step: int = 16, adaptive: bool = False, min_spp: int = 0, counts: Optional[np.ndarray] = None,
            features: Optional[int] = None, atrous: Optional["AtrousConfig"] = None,
            filtered_noise: Optional[float] = None, halves: bool = False,
-           temporal: Optional["TemporalConfig"] = None) -> dict:
+           temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -613,12 +646,16 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     moves: it turns moments and features on (k = 4 unless features= or the filter's config says otherwise), renders, and then
     calls pt_temporal with atrous= as its filter (None: no filter); img is its output and the returned dict gains "temporal": the
     pt_temporal_stats.  It excludes nothing that atrous= allows.  Change cfg.seed from frame to frame; call temporal_reset(ctx)
-    after editing the scene.
+    after editing the scene.  temporal_clip=gamma (with temporal=) sets the context's history clip first (temporal_set_clip,
+    DESIGN 3.13a; 2.5 is the recommended value, 0 turns it off) and the "temporal" dict gains "clipped"; None leaves the context's
+    setting as it is, which is off unless temporal_set_clip was called.
 
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
     Returns the pt_stats of the frame as a dict.
     """
+    if temporal_clip is not None and temporal is None:
+        raise ValueError("temporal_clip needs the accumulation it clips (temporal=)")
     if filtered_noise is not None:
         if atrous is None:
             raise ValueError("filtered_noise needs the filter whose output it measures (atrous=)")
@@ -644,6 +681,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     if counts is not None and (not adaptive or counts.dtype != np.uint32 or counts.shape != (cfg.height, cfg.width)
                                or not counts.flags.c_contiguous):
         raise ValueError("counts needs adaptive=True and a contiguous uint32 [H, W] array")
+    if temporal_clip is not None:
+        temporal_set_clip(ctx, temporal_clip)
     set_adaptive(ctx, noise if adaptive else None, min_spp, noise_step)
     want_moments = moments is not None or noise is not None or atrous is not None or halves or temporal is not None
     set_moments(ctx, want_moments)
@@ -676,6 +715,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
             d.update(noise=noise_estimate(ctx)["noise"])
             if temporal is not None:  # the accumulated (and filtered) image takes the place of the plain finish
                 d["temporal"] = _temporal(ctx, temporal, atrous, img)
+                if temporal_clip is not None:
+                    d["temporal"]["clipped"] = temporal_clip_stats(ctx)["clipped"]
             elif atrous is not None:  # the filtered image takes the place of the plain finish
                 d["atrous"] = _atrous(ctx, atrous, img)
             if filtered_noise is not None:

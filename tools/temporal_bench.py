@@ -8,8 +8,10 @@
              timed call of the second frame reprojects the first: pt_temporal_stats.temporal_ms (all launches), the time inside
              temporal_kernel (libptcore's PTCORE_VERBOSE note), the call's wall time, and the kernel's achieved bytes per second
              on the bytes each pixel has to move once (--bytes-per-pixel) against --hbm-peak.
+             --clip GAMMA runs it with the history clip (pt_temporal_set_clip; 0 = off, the default) and adds
+             clipped and clipped / reprojected to every row; a library without the entry point runs with 0 only.
 
-    python tools/temporal_bench.py --part atrous|temporal [--out FILE]
+    python tools/temporal_bench.py --part atrous|temporal [--clip GAMMA] [--out FILE]
 """
 from __future__ import annotations
 
@@ -48,6 +50,7 @@ def main() -> None:
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--k", type=int, default=4)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--clip", type=float, default=0.0, help="gamma of the history clip; 0 = off")
     ap.add_argument("--bytes-per-pixel", type=int, default=BYTES_PER_PIXEL)
     ap.add_argument("--hbm-peak", type=float, default=8.0e12, help="bytes per second")
     ap.add_argument("--tag", default="")
@@ -86,6 +89,8 @@ def main() -> None:
                 if rep > 0:
                     emit(st)
         else:
+            if a.clip != 0.0 or capi.has("pt_temporal_set_clip"):
+                hip.temporal_set_clip(ctx, a.clip)
             for rep in range(a.reps + 1):
                 hip.temporal_reset(ctx)
                 for i in (0, 1):
@@ -95,7 +100,10 @@ def main() -> None:
                         st = hip.temporal(ctx, hip.TemporalConfig(), hip.AtrousConfig(), img)
                         wall = (time.perf_counter() - t0) * 1e3
                     m = NOTE.search(err.text)
-                    st.update(part="temporal", rep=rep, frame=i, wall_ms=wall, kernel_ms=float(m.group(1)) if m else -1.0)
+                    st.update(part="temporal", rep=rep, frame=i, wall_ms=wall, kernel_ms=float(m.group(1)) if m else -1.0, clip=a.clip)
+                    if capi.has("pt_temporal_clip_stats"):
+                        st["clipped"] = hip.temporal_clip_stats(ctx)["clipped"]
+                        st["clipped_fraction"] = st["clipped"] / max(st["reprojected"], 1)
                     if m:
                         st["kernel_bytes_per_s"] = a.bytes_per_pixel * W * H / (st["kernel_ms"] * 1e-3)
                         st["kernel_fraction_of_hbm_peak"] = st["kernel_bytes_per_s"] / a.hbm_peak
