@@ -115,6 +115,25 @@ def lib():
         L.ora_hit.argtypes = [C.c_int32, dp, dp, C.c_double, dp, dp, C.c_double, C.c_double, dp]
         L.ora_convert_material.restype = None
         L.ora_convert_material.argtypes = [C.POINTER(OraMaterial), dp]
+        L.ora_material_derived.restype = None
+        L.ora_material_derived.argtypes = [C.POINTER(OraMaterial), dp]
+        u64p, vp = C.POINTER(C.c_uint64), C.c_void_p
+        L.ora_scatter_step.restype = C.c_int
+        L.ora_scatter_step.argtypes = [C.POINTER(OraMaterial), dp, dp, dp, u64p, dp, u32p]
+        L.ora_exit_step.restype = None
+        L.ora_exit_step.argtypes = [C.POINTER(OraMaterial), dp, dp, dp, dp]
+        L.ora_roulette_step.restype = C.c_int
+        L.ora_roulette_step.argtypes = [C.c_int32, dp, u64p, u32p]
+        L.ora_scatter_steps.restype = None
+        L.ora_scatter_steps.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.ora_exit_steps.restype = None
+        L.ora_exit_steps.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp, vp]
+        L.ora_roulette_steps.restype = None
+        L.ora_roulette_steps.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp]
+        L.ora_hits.restype = None
+        L.ora_hits.argtypes = [C.c_int64, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp]
+        L.ora_reflects.restype = None
+        L.ora_reflects.argtypes = [C.c_int64, vp, vp, vp]
         L.ora_camera_setup.restype = None
         L.ora_camera_setup.argtypes = [C.POINTER(OraCamera), C.c_int32, C.c_int32, dp]
         L.ora_post_process.restype = None
@@ -294,6 +313,115 @@ def hit(kind: int, a, b, radius, orig, dir_, tmin, tmax):
     ok = L.ora_hit(kind, d3(*a), d3(*b), radius, d3(*orig), d3(*dir_), tmin, tmax, out)
     return bool(ok), {"t": out[0], "p": [out[1], out[2], out[3]], "n": [out[4], out[5], out[6]],
                       "front": bool(out[7])}
+
+
+# ---------------------------------------------------------------- the surface step, one call or one table at a time
+
+def material_array(mats):
+    """A ctypes array of OraMaterial from OraMaterial structs (copied)."""
+    arr = (OraMaterial * max(1, len(mats)))()
+    for i, m in enumerate(mats):
+        C.memmove(C.byref(arr[i]), C.byref(m), C.sizeof(OraMaterial))
+    return arr
+
+
+def scatter_step(mat, rec, orig, dir_, state: int):
+    """renderer.go:308-311 on the record `hit` returned.  mat: an OraMaterial or None (the zero material).  Returns dict(ok,
+    emitted, att, orig, dir, state, draws)."""
+    L = lib()
+    d3 = C.c_double * 3
+    h = (C.c_double * 8)(rec["t"], *rec["p"], *rec["n"], float(rec["front"]))
+    out = (C.c_double * 12)()
+    st, nd = C.c_uint64(state), C.c_uint32()
+    ok = L.ora_scatter_step(C.byref(mat) if mat is not None else None, h, d3(*orig), d3(*dir_), C.byref(st), out, C.byref(nd))
+    return {"ok": bool(ok), "emitted": list(out[0:3]), "att": list(out[3:6]), "orig": list(out[6:9]), "dir": list(out[9:12]),
+            "state": st.value, "draws": nd.value}
+
+
+def exit_step(mat, entry, exit_p, att, orig):
+    """renderer.go:352-370; exit_p None = no exit found.  Returns (att, orig) afterwards."""
+    L = lib()
+    d3 = C.c_double * 3
+    a, o = d3(*att), d3(*orig)
+    L.ora_exit_step(C.byref(mat) if mat is not None else None, d3(*entry), d3(*exit_p) if exit_p is not None else None, a, o)
+    return list(a), list(o)
+
+
+def roulette_step(depth: int, att, state: int):
+    """renderer.go:375-393.  Returns (ended 0 / 1 / 2, att afterwards, state afterwards, draws)."""
+    L = lib()
+    a = (C.c_double * 3)(*att)
+    st, nd = C.c_uint64(state), C.c_uint32()
+    e = L.ora_roulette_step(depth, a, C.byref(st), C.byref(nd))
+    return e, list(a), st.value, nd.value
+
+
+def hits(kind, a, b, radius, rays, tmin, tmax):
+    """n cases of `hit`, one object each.  Returns (ok i32 [n], out f64 [n, 8] = t, p, normal, frontFace)."""
+    L = lib()
+    kind = np.ascontiguousarray(kind, np.int32)
+    a, b, radius, rays = (np.ascontiguousarray(x, np.float64) for x in (a, b, radius, rays))
+    n = len(kind)
+    assert a.shape == (n, 3) and b.shape == (n, 3) and radius.shape == (n,) and rays.shape == (n, 6)
+    out, ok = np.zeros((n, 8)), np.zeros(n, np.int32)
+    L.ora_hits(n, kind.ctypes.data, a.ctypes.data, b.ctypes.data, radius.ctypes.data, rays.ctypes.data, tmin, tmax, out.ctypes.data,
+               ok.ctypes.data)
+    return ok, out
+
+
+def reflects(v, nrm):
+    """reflectVec on n pairs: f64 [n, 3]."""
+    L = lib()
+    v, nrm = np.ascontiguousarray(v, np.float64), np.ascontiguousarray(nrm, np.float64)
+    assert v.shape == nrm.shape and v.shape[1:] == (3,)
+    out = np.zeros_like(v)
+    L.ora_reflects(len(v), v.ctypes.data, nrm.ctypes.data, out.ctypes.data)
+    return out
+
+
+def scatter_steps(mats, mat, hits, rays, states):
+    """n cases of scatter_step: mats a material_array, mat int32 [n] (-1: the zero material), hits f64 [n, 8], rays f64 [n, 6],
+    states u64 [n].  Returns dict(ok i32 [n], out f64 [n, 12] = emitted, att, orig, dir; state u64 [n]; draws u32 [n])."""
+    L = lib()
+    mat = np.ascontiguousarray(mat, np.int32)
+    hits = np.ascontiguousarray(hits, np.float64)
+    rays = np.ascontiguousarray(rays, np.float64)
+    st = np.array(states, np.uint64)
+    n = len(mat)
+    assert hits.shape == (n, 8) and rays.shape == (n, 6) and st.shape == (n,)
+    out, ok, nd = np.zeros((n, 12)), np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    L.ora_scatter_steps(n, C.addressof(mats), mat.ctypes.data, hits.ctypes.data, rays.ctypes.data, st.ctypes.data, out.ctypes.data,
+                        ok.ctypes.data, nd.ctypes.data)
+    return {"ok": ok, "out": out, "state": st, "draws": nd}
+
+
+def exit_steps(mats, mat, rays, t, best, att):
+    """n cases of exit_step on the scattered rays f64 [n, 6], the exit hit (t f64 [n], best i32 [n], < 0: none) and att f64 [n, 3].
+    Returns (att, orig) afterwards, f64 [n, 3] each."""
+    L = lib()
+    mat = np.ascontiguousarray(mat, np.int32)
+    rays = np.ascontiguousarray(rays, np.float64)
+    t = np.ascontiguousarray(t, np.float64)
+    best = np.ascontiguousarray(best, np.int32)
+    a = np.array(att, np.float64)
+    n = len(mat)
+    assert rays.shape == (n, 6) and t.shape == (n,) and best.shape == (n,) and a.shape == (n, 3)
+    o = np.zeros((n, 3))
+    L.ora_exit_steps(n, C.addressof(mats), mat.ctypes.data, rays.ctypes.data, t.ctypes.data, best.ctypes.data, a.ctypes.data, o.ctypes.data)
+    return a, o
+
+
+def roulette_steps(depth, att, T, states):
+    """n cases of roulette_step and the step to the next level.  Returns dict(ended i32 [n]: 0 goes on, 1 maxAtt < 1e-6, 2 the
+    draw, 3 depth reached 0; att, T f64 [n, 3]; state u64 [n]; draws u32 [n])."""
+    L = lib()
+    depth = np.ascontiguousarray(depth, np.int32)
+    a, tt, st = np.array(att, np.float64), np.array(T, np.float64), np.array(states, np.uint64)
+    n = len(depth)
+    assert a.shape == (n, 3) and tt.shape == (n, 3) and st.shape == (n,)
+    e, nd = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    L.ora_roulette_steps(n, depth.ctypes.data, a.ctypes.data, tt.ctypes.data, st.ctypes.data, e.ctypes.data, nd.ctypes.data)
+    return {"ended": e, "att": a, "T": tt, "state": st, "draws": nd}
 
 
 def post_process(img, tonemap=False, denoise=False, sigma_s=1.0, sigma_r=0.15, smooth=False, smooth_radius=2,

@@ -375,9 +375,13 @@ static vec3 emitted(const material *m) {
 }
 
 /* materials.go:226-231 */
-static double reflectance(double cosine, double refIdx) {
+static double reflectanceR0(double refIdx) { /* :227-228 */
     double r0 = (1 - refIdx) / (1 + refIdx);
     r0 = r0 * r0;
+    return r0;
+}
+static double reflectance(double cosine, double refIdx) {
+    double r0 = reflectanceR0(refIdx);
     return r0 + (1 - r0) * ora_pow(1 - cosine, 5);
 }
 
@@ -691,6 +695,37 @@ static vec3 background(const ora_sky *sky, ray r) {
     return v(sky->background[0], sky->background[1], sky->background[2]);
 }
 
+/* renderer.go:352-370, the `if hitExit` block: Beer-Lambert attenuation over the distance travelled inside the glass (only with
+ * a positive absorption component, :360) and the scattered ray moved to the exit point */
+static void exitStep(const material *m, vec3 entryP, vec3 exitP, vec3 *attenuation, ray *scattered) {
+    double dx = exitP.x - entryP.x;
+    double dy = exitP.y - entryP.y;
+    double dz = exitP.z - entryP.z;
+    double distance = sqrt(dx * dx + dy * dy + dz * dz);
+    if (m->absorption.x > 0 || m->absorption.y > 0 || m->absorption.z > 0) {
+        attenuation->x = ora_exp(-m->absorption.x * distance);
+        attenuation->y = ora_exp(-m->absorption.y * distance);
+        attenuation->z = ora_exp(-m->absorption.z * distance);
+    }
+    scattered->orig = exitP;
+}
+
+/* renderer.go:375-393, the `depth <= rrThreshold` block.  Returns 0: the path goes on (attenuation divided by the survival
+ * probability when the block ran); 1: ended by maxAttenuation < 1e-6 (no draw); 2: ended by the draw. */
+static int rouletteStep(int depth, vec3 *attenuation, randSource *rng) {
+    const int rrThreshold = 3;
+    if (depth <= rrThreshold) {
+        double maxAttenuation = ora_max(attenuation->x, ora_max(attenuation->y, attenuation->z));
+        if (maxAttenuation < 1e-6) return 1;
+        double rrProb = ora_min(maxAttenuation, 0.95);
+        if (Float64(rng) > rrProb) return 2;
+        attenuation->x /= rrProb;
+        attenuation->y /= rrProb;
+        attenuation->z /= rrProb;
+    }
+    return 0;
+}
+
 /* renderer.go:286-404 */
 static vec3 rayColorOpt(tracer *tr, ray r, int depth, randSource *rng, hitRecord *rec) {
     if (depth <= 0) return v(0, 0, 0);
@@ -737,31 +772,11 @@ static vec3 rayColorOpt(tracer *tr, ray r, int depth, randSource *rng, hitRecord
                     }
                 }
             }
-            if (hitExit) {
-                double dx = exitRec.p.x - rec->p.x;
-                double dy = exitRec.p.y - rec->p.y;
-                double dz = exitRec.p.z - rec->p.z;
-                double distance = sqrt(dx * dx + dy * dy + dz * dz);
-                if (rec->mat.absorption.x > 0 || rec->mat.absorption.y > 0 || rec->mat.absorption.z > 0) {
-                    attenuation.x = ora_exp(-rec->mat.absorption.x * distance);
-                    attenuation.y = ora_exp(-rec->mat.absorption.y * distance);
-                    attenuation.z = ora_exp(-rec->mat.absorption.z * distance);
-                }
-                scattered.orig = exitRec.p;
-            }
+            if (hitExit) exitStep(&rec->mat, rec->p, exitRec.p, &attenuation, &scattered);
         }
     }
 
-    const int rrThreshold = 3;
-    if (depth <= rrThreshold) {
-        double maxAttenuation = ora_max(attenuation.x, ora_max(attenuation.y, attenuation.z));
-        if (maxAttenuation < 1e-6) return em;
-        double rrProb = ora_min(maxAttenuation, 0.95);
-        if (Float64(rng) > rrProb) return em;
-        attenuation.x /= rrProb;
-        attenuation.y /= rrProb;
-        attenuation.z /= rrProb;
-    }
+    if (rouletteStep(depth, &attenuation, rng)) return em;
 
     hitRecord nextRec;
     memset(&nextRec, 0, sizeof nextRec);
@@ -1040,6 +1055,111 @@ int ora_hit(int32_t kind, const double a[3], const double b[3], double radius, c
     out[4] = rec.normal.x; out[5] = rec.normal.y; out[6] = rec.normal.z;
     out[7] = (double)rec.frontFace;
     return ok;
+}
+
+void ora_hits(int64_t n, const int32_t *kind, const double *a, const double *b, const double *radius, const double *rays,
+              double tmin, double tmax, double *out, int32_t *ok) {
+    for (int64_t i = 0; i < n; i++)
+        ok[i] = ora_hit(kind[i], a + 3 * i, b + 3 * i, radius[i], rays + 6 * i, rays + 6 * i + 3, tmin, tmax, out + 8 * i);
+}
+
+void ora_reflects(int64_t n, const double *vv, const double *nn, double *out) {
+    for (int64_t i = 0; i < n; i++) {
+        vec3 r = reflectVec(v(vv[3 * i], vv[3 * i + 1], vv[3 * i + 2]), v(nn[3 * i], nn[3 * i + 1], nn[3 * i + 2]));
+        out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+    }
+}
+
+/* ---- the surface step, one call at a time (tests/shade_probe_support.py) ---- */
+
+static material material_of(const ora_material *m) {
+    material r;
+    memset(&r, 0, sizeof r); /* NULL: the zero material of a missing id (objects.go:233) */
+    if (m) r = convertMaterial(m);
+    return r;
+}
+
+int ora_scatter_step(const ora_material *m, const double hit[8], const double orig[3], const double dir[3], uint64_t *state,
+                     double out[12], uint32_t *ndraw) {
+    hitRecord rec;
+    memset(&rec, 0, sizeof rec);
+    rec.t = hit[0];
+    rec.p = v(hit[1], hit[2], hit[3]);
+    rec.normal = v(hit[4], hit[5], hit[6]);
+    rec.frontFace = hit[7] != 0;
+    rec.mat = material_of(m);
+    ray r = {v(orig[0], orig[1], orig[2]), v(dir[0], dir[1], dir[2])};
+    randSource rng = {*state, 0};
+    vec3 em = emitted(&rec.mat); /* renderer.go:308 */
+    vec3 attenuation = v(0, 0, 0);
+    ray scattered;
+    memset(&scattered, 0, sizeof scattered);
+    int ok = scatter(&rec.mat, &rng, r, &rec, &attenuation, &scattered); /* renderer.go:311 */
+    out[0] = em.x; out[1] = em.y; out[2] = em.z;
+    out[3] = attenuation.x; out[4] = attenuation.y; out[5] = attenuation.z;
+    out[6] = scattered.orig.x; out[7] = scattered.orig.y; out[8] = scattered.orig.z;
+    out[9] = scattered.dir.x; out[10] = scattered.dir.y; out[11] = scattered.dir.z;
+    *state = rng.state;
+    if (ndraw) *ndraw = rng.draws;
+    return ok;
+}
+
+void ora_exit_step(const ora_material *m, const double entry[3], const double *exit_p, double att[3], double orig[3]) {
+    if (!exit_p) return; /* no exit found: renderer.go:352 is not entered */
+    material mat = material_of(m);
+    vec3 attenuation = v(att[0], att[1], att[2]);
+    ray scattered = {v(orig[0], orig[1], orig[2]), v(0, 0, 0)};
+    exitStep(&mat, v(entry[0], entry[1], entry[2]), v(exit_p[0], exit_p[1], exit_p[2]), &attenuation, &scattered);
+    att[0] = attenuation.x; att[1] = attenuation.y; att[2] = attenuation.z;
+    orig[0] = scattered.orig.x; orig[1] = scattered.orig.y; orig[2] = scattered.orig.z;
+}
+
+int ora_roulette_step(int32_t depth, double att[3], uint64_t *state, uint32_t *ndraw) {
+    randSource rng = {*state, 0};
+    vec3 attenuation = v(att[0], att[1], att[2]);
+    int ended = rouletteStep(depth, &attenuation, &rng);
+    att[0] = attenuation.x; att[1] = attenuation.y; att[2] = attenuation.z;
+    *state = rng.state;
+    if (ndraw) *ndraw = rng.draws;
+    return ended;
+}
+
+void ora_scatter_steps(int64_t n, const ora_material *mats, const int32_t *mat, const double *hits, const double *rays,
+                       uint64_t *states, double *out, int32_t *ok, uint32_t *ndraw) {
+    for (int64_t i = 0; i < n; i++)
+        ok[i] = ora_scatter_step(mat[i] >= 0 ? &mats[mat[i]] : NULL, hits + 8 * i, rays + 6 * i, rays + 6 * i + 3, &states[i],
+                                 out + 12 * i, &ndraw[i]);
+}
+
+void ora_exit_steps(int64_t n, const ora_material *mats, const int32_t *mat, const double *rays, const double *t,
+                    const int32_t *best, double *att, double *orig) {
+    for (int64_t i = 0; i < n; i++) {
+        const double *r = rays + 6 * i;
+        orig[3 * i] = r[0]; orig[3 * i + 1] = r[1]; orig[3 * i + 2] = r[2];
+        if (best[i] < 0) continue;
+        vec3 p = vadd(v(r[0], r[1], r[2]), vmul(v(r[3], r[4], r[5]), t[i])); /* ray.at, math.go:138-140 */
+        const double ep[3] = {p.x, p.y, p.z};
+        ora_exit_step(mat[i] >= 0 ? &mats[mat[i]] : NULL, r, ep, att + 3 * i, orig + 3 * i);
+    }
+}
+
+void ora_roulette_steps(int64_t n, const int32_t *depth, double *att, double *T, uint64_t *states, int32_t *ended, uint32_t *ndraw) {
+    for (int64_t i = 0; i < n; i++) {
+        ended[i] = ora_roulette_step(depth[i], att + 3 * i, &states[i], &ndraw[i]);
+        if (ended[i]) continue;
+        /* renderer.go:403: em + attenuation * next, i.e. everything deeper is scaled by the product so far */
+        T[3 * i] *= att[3 * i]; T[3 * i + 1] *= att[3 * i + 1]; T[3 * i + 2] *= att[3 * i + 2];
+        if (depth[i] - 1 <= 0) ended[i] = 3; /* renderer.go:287-289 of the callee */
+    }
+}
+
+void ora_material_derived(const ora_material *m, double out[5]) {
+    material r = material_of(m);
+    out[0] = 1.0 / r.ior;               /* materials.go:183, front face */
+    out[1] = reflectanceR0(1.0 / r.ior); /* materials.go:227-228 with ratio = 1/ior */
+    out[2] = reflectanceR0(r.ior);       /* ... with ratio = ior */
+    out[3] = r.rough * r.rough;          /* materials.go:121 */
+    out[4] = (r.absorption.x > 0 || r.absorption.y > 0 || r.absorption.z > 0) ? 1.0 : 0.0; /* renderer.go:360 */
 }
 
 void ora_convert_material(const ora_material *m, double out[12]) {

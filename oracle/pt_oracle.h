@@ -133,8 +133,37 @@ double ora_stream_next(uint64_t *state);
  * out = {t, p[3], normal[3], frontFace}. Returns 1 on hit. */
 int ora_hit(int32_t kind, const double a[3], const double b[3], double radius, const double orig[3],
             const double dir[3], double tmin, double tmax, double out[8]);
+/* n cases of ora_hit, one object each: kind [n], a / b [n][3], radius [n], rays [n][6] (origin, direction), out [n][8], ok [n] */
+void ora_hits(int64_t n, const int32_t *kind, const double *a, const double *b, const double *radius, const double *rays,
+              double tmin, double tmax, double *out, int32_t *ok);
+/* reflectVec (math.go:39-46) on n pairs (v, n): out [n][3] */
+void ora_reflects(int64_t n, const double *v, const double *nrm, double *out);
 /* converted material: out = {typ, albedo[3], rough, ior, emit[3], absorption[3]} (12 doubles) */
 void ora_convert_material(const ora_material *m, double out[12]);
+/* what the reference forms from a converted material on every hit: out = {1/ior, reflectance's r0 with ratio = 1/ior, r0 with
+ * ratio = ior (materials.go:183, :227-228), rough*rough (materials.go:121), renderer.go:360's absorption test as 0 / 1} */
+void ora_material_derived(const ora_material *m, double out[5]);
+
+/* ---- the surface step of rayColorOpt, one call at a time: the same static functions rayColorOpt calls ----
+ * ora_scatter_step: renderer.go:308-311 on the record ora_hit returned (hit = its out[8]) and the incoming ray, with the stream
+ *   at *state.  out = {emitted[3], attenuation[3], scattered origin[3], scattered direction[3]}; *state and *ndraw (draws taken)
+ *   are written; returns scatter's ok.  m == NULL is the zero material of a missing id.
+ * ora_exit_step: renderer.go:352-370 with the entry point and the exit record's point, exit_p == NULL when no exit was found;
+ *   att and orig (the scattered ray's origin) are updated in place.
+ * ora_roulette_step: renderer.go:375-393 at `depth`; att is updated in place.  Returns 0 when the path goes on, 1 when
+ *   maxAttenuation < 1e-6 ended it, 2 when the draw did.
+ * The array forms run n independent cases.  ora_exit_steps takes the scattered ray [n][6], the exit hit's t and best (< 0: none),
+ *   forms the exit point as ray.at does and writes orig [n][3]; ora_roulette_steps also multiplies T [n][3] by the attenuation
+ *   of a surviving path (renderer.go:403) and reports 3 when depth - 1 reaches 0 (renderer.go:287-289 of the callee). */
+int ora_scatter_step(const ora_material *m, const double hit[8], const double orig[3], const double dir[3], uint64_t *state,
+                     double out[12], uint32_t *ndraw);
+void ora_exit_step(const ora_material *m, const double entry[3], const double *exit_p, double att[3], double orig[3]);
+int ora_roulette_step(int32_t depth, double att[3], uint64_t *state, uint32_t *ndraw);
+void ora_scatter_steps(int64_t n, const ora_material *mats, const int32_t *mat, const double *hits, const double *rays,
+                       uint64_t *states, double *out, int32_t *ok, uint32_t *ndraw);
+void ora_exit_steps(int64_t n, const ora_material *mats, const int32_t *mat, const double *rays, const double *t,
+                    const int32_t *best, double *att, double *orig);
+void ora_roulette_steps(int64_t n, const int32_t *depth, double *att, double *T, uint64_t *states, int32_t *ended, uint32_t *ndraw);
 /* camera: out = origin[3], lowerLeft[3], horizontal[3], vertical[3], u[3], v[3], w[3], lensRadius (22) */
 void ora_camera_setup(const ora_camera *c, int32_t width, int32_t height, double out[22]);
 /* ---- post-process passes of the reference's GPU backend, CPU restatement ----

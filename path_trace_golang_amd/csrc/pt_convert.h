@@ -1,0 +1,67 @@
+// pt_convert.h -- host-side conversion of a scene material to the device record (included by ptcore.hip; tests build it for
+// the host with g++ -ffp-contract=off and for the device probe, so that what they check is this text and not a copy).
+#pragma once
+
+#include <cstring>
+
+#include "../../include/ptcore.h"
+#include "pt_device.h"
+
+namespace ptd {
+
+inline double clampd(double x, double lo, double hi) {  // materials.go:57-65
+    if (x < lo) return lo;
+    if (x > hi) return hi;
+    return x;
+}
+
+inline DevMat convert_material(const pt_material &m) {  // materials.go:28-55
+    DevMat r;
+    std::memset(&r, 0, sizeof r);
+    switch (m.type) {
+        case PT_MAT_METAL: {
+            double rough = m.rough;
+            if (m.smoothness > 0) rough = 1.0 - clampd(m.smoothness, 0, 1);
+            r.typ = MAT_METAL;
+            for (int i = 0; i < 3; i++) r.albedo[i] = m.albedo[i];
+            r.rough = clampd(rough, 0, 1);
+            break;
+        }
+        case PT_MAT_DIELECTRIC: {
+            double ior = m.ior;
+            if (ior == 0) ior = 1.5;
+            r.typ = MAT_DIELECTRIC;
+            for (int i = 0; i < 3; i++) { r.albedo[i] = m.albedo[i]; r.absorption[i] = m.absorption[i]; }
+            r.ior = ior;
+            // reflectance's r0 for both faces (materials.go:183, :226-229): the reference recomputes these on every hit
+            // from the same operands; done once here with the same IEEE operations (this file is built with
+            // -ffp-contract=off like the kernels)
+            r.inv_ior = 1.0 / ior;
+            {
+                double a = (1 - r.inv_ior) / (1 + r.inv_ior);
+                r.r0_front = a * a;
+                double b = (1 - ior) / (1 + ior);
+                r.r0_back = b * b;
+            }
+            break;
+        }
+        case PT_MAT_EMISSIVE:
+            r.typ = MAT_EMISSIVE;
+            for (int i = 0; i < 3; i++) r.emit[i] = m.emit[i] * m.power;
+            break;
+        case PT_MAT_MIRROR:
+            r.typ = MAT_MIRROR;
+            for (int i = 0; i < 3; i++) r.albedo[i] = m.albedo[i];
+            break;
+        default:
+            r.typ = MAT_LAMBERT;
+            for (int i = 0; i < 3; i++) r.albedo[i] = m.albedo[i];
+            r.rough = clampd(m.rough, 0, 1);
+            break;
+    }
+    r.absorbs = (r.absorption[0] > 0 || r.absorption[1] > 0 || r.absorption[2] > 0) ? 1 : 0;
+    r.rough_sq = r.rough * r.rough;
+    return r;
+}
+
+}  // namespace ptd

@@ -1814,6 +1814,8 @@ __device__ __forceinline__ bool roulette_advance(int &depth, double attx, double
 //                exit_mat = the material
 //   otherwise    o, d hold the scattered ray, att its attenuation: Russian roulette comes next
 // GLASS = false: the caller never passes a dielectric hit (split passes park those for glass_kernel).
+// glass_kernel carries its own copy of the hit record and of the dielectric branch: the two must stay the same (both are run
+// against the reference, one lane per case, by tests/shade_probe.hip).
 template <bool STATS, bool GLASS>
 __device__ __forceinline__ void shade_hit(const DevObj &o, const DevMat *s_mat, double tmax, double &ox, double &oy, double &oz, double &dx,
                                           double &dy, double &dz, uint64_t &rs, uint32_t &c_draw, uint32_t &j_draw, bool &finished,
@@ -2643,6 +2645,8 @@ __global__ __launch_bounds__(PT_BLOCK, (WIDE && PT_FLAT_WAVES > 4) ? 4 : PT_FLAT
             int best;
             queue_load<ENTRY_HIT, STATS>(gq, (size_t)i0, lane, ox, oy, oz, dx, dy, dz, Tx, Ty, Tz, tmax, rs, job, depth, best, j_seg, j_draw);
 
+            // (from here to the attenuation: the dielectric branch of shade_hit, written out.  tests/shade_probe.hip runs a copy of
+            // these lines one lane per case against the reference: THAT COPY AND THESE LINES MUST STAY THE SAME)
             // hit record of the winner
             const DevObj &o = lds_obj[best];
             const int kind = o.kind & 0xff;

@@ -371,3 +371,135 @@ def test_stream_independent_of_tiling_and_workers(oracle):
     one, nseg, ndraw = oracle.sample(sc, 48, 40, 2, 5, 11, 20, 17, 1)
     z, _, _ = oracle.sample(sc, 48, 40, 2, 5, 11, 20, 17, 0)
     assert np.allclose(np.array(one) + np.array(z), full["accum"][17, 20], rtol=0, atol=0)
+
+
+# ----------------------------------------------------------------- the surface step, one call at a time
+
+def _v3(x, y, z):
+    return {"x": x, "y": y, "z": z}
+
+
+def _rgb(r, g, b):
+    return {"r": r, "g": g, "b": b}
+
+
+_STEP_MATS = [
+    {"id": "floor", "type": "lambert", "albedo": _rgb(0.6, 0.5, 0.4), "rough": 0.3},
+    {"id": "matte", "type": "lambert", "albedo": _rgb(0.2, 0.7, 0.9)},
+    {"id": "steel", "type": "metal", "albedo": _rgb(0.9, 0.85, 0.8), "rough": 0.4},
+    {"id": "chrome", "type": "metal", "albedo": _rgb(0.95, 0.95, 0.95), "smoothness": 1.0},
+    {"id": "mirror", "type": "mirror", "albedo": _rgb(0.9, 0.9, 0.9)},
+    {"id": "lamp", "type": "emissive", "emit": _rgb(1.0, 0.8, 0.6), "power": 3.0},
+    {"id": "glass", "type": "dielectric", "ior": 1.5, "albedo": _rgb(1, 1, 1), "absorption": _rgb(0.3, 0.1, 0.0)},
+    {"id": "clear", "type": "dielectric", "ior": 0.0, "albedo": _rgb(1, 1, 1)},
+]
+
+
+def _step_scene(glass):
+    objs = [{"id": "f", "type": "plane", "position": _v3(0, -1, 0), "size": _v3(0, 0, 0), "material_id": "floor"},
+            {"id": "a", "type": "sphere", "position": _v3(-1.6, 0, 0), "size": _v3(1, 0, 0), "material_id": "matte"},
+            {"id": "b", "type": "sphere", "position": _v3(1.7, -0.2, -0.5), "size": _v3(0.8, 0, 0), "material_id": "steel"},
+            {"id": "c", "type": "box", "position": _v3(0, -0.5, -2.5), "size": _v3(1.5, 1.0, 1.0), "material_id": "chrome"},
+            {"id": "d", "type": "box", "position": _v3(-0.3, 1.6, -1.0), "size": _v3(1.0, 0.2, 1.0), "material_id": "mirror"},
+            {"id": "e", "type": "sphere_light", "position": _v3(2.5, 2.5, 1.0), "size": _v3(0.7, 0, 0), "material_id": "lamp"},
+            {"id": "m", "type": "sphere", "position": _v3(0.6, 0.1, 2.2), "size": _v3(0.3, 0, 0), "material_id": "nobody"}]
+    if glass:
+        objs += [{"id": "g", "type": "sphere", "position": _v3(0.1, -0.1, 1.2), "size": _v3(0.9, 0, 0), "material_id": "glass"},
+                 {"id": "h", "type": "box", "position": _v3(-1.2, -0.4, 2.0), "size": _v3(0.8, 1.2, 0.8), "material_id": "clear"}]
+    cam = {"position": _v3(0.3, 0.8, 6), "target": _v3(0, 0, 0), "up": _v3(0, 1, 0), "fov": 45, "aperture": 0, "focus_dist": 6,
+           "aspect_ratio": 0}
+    return _doc(objs, _STEP_MATS, {"type": "solid", "color": _rgb(0.7, 0.8, 1.0)}, cam)
+
+
+def _chained_sample(oracle, sc, world, sky, o, d, depth, state):
+    """rayColorOpt (renderer.go:286-404) with every piece an oracle call: the closest-hit scan and the exit scan as loops of
+    ora_hit over the object list, the rest through the step wrappers.  Returns (rgb, segments, exit scans, draws)."""
+    levels, nseg, nexit, ndraw = [], 0, 0, 0
+    while True:
+        if depth <= 0:
+            final = [0.0, 0.0, 0.0]
+            break
+        nseg += 1
+        closest, rec, who = MAXF, None, None
+        for w in world:
+            ok, h = oracle.hit(w["kind"], w["a"], w["b"], w["radius"], o, d, 0.001, closest)
+            if ok:
+                closest, rec, who = h["t"], h, w
+        if rec is None:
+            final = list(sky)
+            break
+        s = oracle.scatter_step(who["mat"], rec, o, d, state)
+        state, ndraw = s["state"], ndraw + s["draws"]
+        if not s["ok"]:
+            final = s["emitted"]
+            break
+        att, so, sd = s["att"], s["orig"], s["dir"]
+        if who["diel"] and rec["front"]:
+            nexit += 1
+            exit_t, exit_p = MAXF, None
+            for w in world:
+                ok, h = oracle.hit(w["kind"], w["a"], w["b"], w["radius"], so, sd, 0.0001, exit_t)
+                if ok and w["diel"] and not h["front"] and h["t"] < exit_t:
+                    dx, dy, dz = (h["p"][k] - rec["p"][k] for k in range(3))
+                    dist_sq = dx * dx + dy * dy + dz * dz
+                    if 1e-8 < dist_sq < 1000.0:
+                        exit_t, exit_p = h["t"], h["p"]
+            att, so = oracle.exit_step(who["mat"], rec["p"], exit_p, att, so)
+        ended, att, state, nd = oracle.roulette_step(depth, att, state)
+        ndraw += nd
+        if ended:
+            final = s["emitted"]
+            break
+        levels.append((s["emitted"], att))
+        o, d, depth = so, sd, depth - 1
+    col = final
+    for em, att in reversed(levels):  # em + att * next, innermost first (renderer.go:403)
+        col = [em[k] + att[k] * col[k] for k in range(3)]
+    return col, nseg, nexit, ndraw
+
+
+def _world_of(oracle, sc):
+    """sceneToWorld (objects.go:225-269) for ora_hit: kind, a, b, radius, the scene material (None: missing id), dielectric or not."""
+    world = []
+    for i in range(sc.c.nobjects):
+        ob = sc.c.objects[i]
+        pos, size = list(ob.position), list(ob.size)
+        mat = sc.c.materials[ob.material] if 0 <= ob.material < sc.c.nmaterials else None
+        w = {"mat": mat, "diel": mat is not None and mat.type == 2, "a": pos, "b": [0.0, 0.0, 0.0], "radius": 0.0}
+        if ob.type in (0, 3):
+            w.update(kind=0, radius=size[0])
+        elif ob.type == 1:
+            w.update(kind=1, b=[0.0, 1.0, 0.0])
+        elif ob.type == 2:
+            w.update(kind=2, a=[pos[k] - size[k] * 0.5 for k in range(3)], b=[pos[k] + size[k] * 0.5 for k in range(3)])
+        else:
+            continue
+        world.append(w)
+    return world
+
+
+@pytest.mark.parametrize("glass", [False, True], ids=["no_glass", "glass"])
+def test_step_wrappers_chained_by_hand_are_the_sample(oracle, glass):
+    # ora_hit + ora_scatter_step + ora_exit_step + ora_roulette_step chained in Python reproduce ora_sample, ray by ray: the
+    # wrappers are what rayColorOpt does.  depth 6, so that the roulette levels are reached with and without a draw.
+    L = oracle.lib()
+    sc = oracle.Scene(_step_scene(glass))
+    W, H, spp, depth, seed = 34, 30, 2, 6, 77
+    world = _world_of(oracle, sc)
+    sky = list(sc.c.sky.color)
+    full = oracle.render(sc, W, H, spp, depth, seed=seed, workers=2)
+    nrays, texit, kinds = 0, 0, set()
+    for y in range(H):
+        for x in range(W):
+            for s in range(spp):
+                want, wseg, wdraw = oracle.sample(sc, W, H, spp, depth, seed, x, y, s)
+                o, d = oracle.primary_ray(sc, W, H, spp, depth, seed, x, y, s)
+                st = C.c_uint64(L.ora_stream_init(seed, y * W + x, s))
+                L.ora_stream_next(C.byref(st)); L.ora_stream_next(C.byref(st))  # u, v (renderer.go:182-183); no lens
+                got, nseg, nexit, ndraw = _chained_sample(oracle, sc, world, sky, o, d, depth, st.value)
+                assert (nseg, ndraw + 2) == (wseg, wdraw), (x, y, s)
+                assert np.array_equal(np.array(got).view(np.uint64), np.array(want).view(np.uint64)), (x, y, s, got, want)
+                nrays, texit = nrays + 1, texit + nexit
+                kinds.add(nseg)
+    assert nrays >= 2000 and len(kinds) > 3
+    assert texit == full["stats"]["exit_scans"] and (texit > 0) == glass
