@@ -30,6 +30,7 @@
 #include "pt_convert.h"
 #include "pt_device.h"
 #include "pt_kernels.h"
+#include "pt_filter_launch.h"
 #include "pt_wavefront.h"
 #include "pt_walk32.h"
 #include "pt_primary.h"
@@ -320,28 +321,30 @@ struct pt_ctx {
     bool adaptive_on = false;         // pt_set_adaptive
     int32_t features_k = 0;           // pt_set_features: feature samples per pixel (0 = off)
     DevBuf<double> g_tiles_feat, f_feat_n, f_feat_a, f_feat_d;  // pt_read_features / pt_atrous: one gathered plane, the three row-major frames
-    // pt_atrous (allocated on the first call): colour and variance ping-pong, the guide records, the noise partials
-    DevBuf<double> at_col[2], at_var[2];
-    DevBuf<pta::Guide> at_guide;
-    DevBuf<ptk::NoisePartial> at_part;
+    // The buffers of the post-frame filters, on devices[0]: allocated on the first call, never shrunk.
+    struct Atrous {  // pt_atrous, pt_temporal: colour and variance ping-pong, the guide records, the noise partials
+        DevBuf<double> col[2], var[2];
+        DevBuf<pta::Guide> guide;
+        DevBuf<ptk::NoisePartial> part;
+    } at;
     bool halves_on = false;           // pt_set_halves
     DevBuf<double> g_tiles_hv, f_hv_sa, f_hv_qa, f_hv_sb, f_hv_qb;  // pt_read_halves / pt_atrous_halves: one gathered plane, the four row-major frames
-    // pt_atrous_halves (allocated on the first call): the guide planes, colour and variance planes of both halves (ping-pong), the
-    // combined mean, err and the two filtered halves row-major, the partials of the two figures
-    DevBuf<double> ah_guide, ah_col[2], ah_var[2], ah_mean, ah_err, ah_half;
-    DevBuf<ptk::HalvesPartial> ah_part;
-    // pt_temporal (allocated on the first call): two sets of history planes, tp_hist[tp_cur] the stored one; the block partials; the
-    // history's size and camera; the frame and the samples done of the last call that succeeded ("already accumulated")
-    DevBuf<double> tp_hist[2];
-    DevBuf<ptk::TemporalPartial> tp_part;
-    int tp_cur = 0;
-    bool tp_valid = false;            // the history is not empty
-    int32_t tp_w = 0, tp_h = 0;
-    DevCamera tp_cam{};
-    uint64_t tp_serial = 0;
-    int32_t tp_spp = 0;
-    double tp_clip = 0.0;             // pt_temporal_set_clip: gamma of step 7a for later calls (0 = off)
-    struct pt_temporal_clip_stats tp_clip_stats{};  // of the last pt_temporal that succeeded
+    struct Halves {  // pt_atrous_halves: guide, colour and variance planes of both halves (ping-pong), the combined mean, err and the two
+        DevBuf<double> guide, col[2], var[2], mean, err, half;  // filtered halves row-major, the partials of the two figures
+        DevBuf<ptk::HalvesPartial> part;
+    } ah;
+    struct Temporal {  // pt_temporal: two sets of history planes, hist[cur] the stored one, and the block partials
+        DevBuf<double> hist[2];
+        DevBuf<ptk::TemporalPartial> part;
+        int cur = 0;
+        bool valid = false;           // the history is not empty
+        int32_t w = 0, h = 0;         // its size and camera
+        DevCamera cam{};
+        uint64_t serial = 0;          // the frame and the samples done of the last call that succeeded ("already accumulated")
+        int32_t spp = 0;
+        double clip = 0.0;            // pt_temporal_set_clip: gamma of step 7a for later calls (0 = off)
+        struct pt_temporal_clip_stats clip_stats{};  // of the last pt_temporal that succeeded
+    } tp;
     uint64_t frames_opened = 0;      // pt_begin / pt_render frames of this context so far
     pt_adaptive adaptive{};
     DevBuf<uint32_t> f_seg, f_draw;
@@ -1516,15 +1519,15 @@ int32_t dev_adaptive_check(pt_ctx *ctx, Device &d, ptk::AdaptResult *host_res) {
     return PT_OK;
 }
 
-// Writes this device's second moments tile-major (zeros outside the frame), the layout of tiles_accum.
-int32_t dev_finish_moments(pt_ctx *ctx, Device &d, double *tiles_m2) {
+// Writes this device's second moments tile-major (zeros outside the frame), the layout of tiles_accum.  (A Gathered fill.)
+int32_t dev_finish_moments(pt_ctx *ctx, Device &d, uint32_t, void *tiles_m2) {
     const Frame &fr = ctx->frame;
     if (d.nlocal == 0) return PT_OK;
     HIP_TRY(hipSetDevice(d.ordinal));
     ptk::MomentsArgs M;
     std::memset(&M, 0, sizeof M);
     M.m2 = d.m2.p;
-    M.tiles_m2 = tiles_m2;
+    M.tiles_m2 = static_cast<double *>(tiles_m2);
     M.nslots = d.nslots;
     M.first = d.acc_started ? 0 : 1;
     M.finish = 1;
@@ -1534,15 +1537,15 @@ int32_t dev_finish_moments(pt_ctx *ctx, Device &d, double *tiles_m2) {
     return PT_OK;
 }
 
-// Writes plane `which` (0 SA, 1 QA, 2 SB, 3 QB) of this device's half-buffer sums tile-major, the layout of tiles_accum.
-int32_t dev_finish_halves(pt_ctx *ctx, Device &d, uint32_t which, double *tiles) {
+// Writes plane `which` (0 SA, 1 QA, 2 SB, 3 QB) of this device's half-buffer sums tile-major, the layout of tiles_accum.  (A Gathered fill.)
+int32_t dev_finish_halves(pt_ctx *ctx, Device &d, uint32_t which, void *tiles) {
     const Frame &fr = ctx->frame;
     if (d.nlocal == 0) return PT_OK;
     HIP_TRY(hipSetDevice(d.ordinal));
     ptk::HalvesArgs HA;
     std::memset(&HA, 0, sizeof HA);
     HA.hv = d.hv.p;
-    HA.tiles = tiles;
+    HA.tiles = static_cast<double *>(tiles);
     HA.nslots = d.nslots;
     HA.first = d.acc_started ? 0 : 1;
     HA.finish = 1;
@@ -2166,6 +2169,168 @@ int32_t gather_planes(pt_ctx *ctx, const Plane (&planes)[N], Fill &&fill) {
     return PT_OK;
 }
 
+// ---- The quantities that travel through gather_planes one plane at a time: the plane's row and what has device d write its tiles
+// of it to dst, on d's stream.  gather_one runs one of them into its row-major frame on devices[0] and, when asked for, to the host.
+struct Gathered {
+    Plane row;
+    int32_t (*fill)(pt_ctx *ctx, Device &d, uint32_t which, void *dst);
+    uint32_t which;  // the feature or half-sum plane
+};
+
+int32_t gather_one(pt_ctx *ctx, const Gathered &g, void *host) {
+    Plane planes[] = {g.row};
+    planes[0].host = host;
+    return gather_planes(ctx, planes, [&](Device &d, void *const *dst) { return g.fill(ctx, d, g.which, dst[0]); });
+}
+
+template <auto Tiles, auto Gather, auto Framed>
+Plane plane_row(PlaneKind kind) {
+    return {true, kind, reserved<Device, Tiles>, reserved<pt_ctx, Gather>, reserved<pt_ctx, Framed>, nullptr, 0};
+}
+
+// The fills: the finished sums S (dev_finish's resolve for accum alone, untimed); Q and half-sum plane `which` are
+// dev_finish_moments and dev_finish_halves
+int32_t fill_sums(pt_ctx *ctx, Device &d, uint32_t, void *dst) {
+    ptk::ResolveArgs R;
+    std::memset(&R, 0, sizeof R);
+    R.acc = d.acc.p;
+    R.tiles_accum = static_cast<double *>(dst);
+    R.nslots = d.nslots;
+    R.first = d.acc_started ? 0 : 1;
+    R.finish = 1;
+    R.G = tile_geom(ctx->frame, d);
+    hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+// the counts of an adaptive frame, through untile_kernel's u32a plane (the buffers of read_frame's nseg)
+int32_t fill_counts(pt_ctx *ctx, Device &d, uint32_t, void *dst) {
+    hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p,
+                       static_cast<uint32_t *>(dst), d.nslots, tile_geom(ctx->frame, d));
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+// feature plane `which`: 0 normal, 1 albedo, 2 depth
+int32_t fill_feature(pt_ctx *ctx, Device &d, uint32_t which, void *dst) {
+    hipLaunchKernelGGL(ptk::feature_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.feat.p,
+                       static_cast<double *>(dst), d.nslots, which, tile_geom(ctx->frame, d));
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
+const Gathered g_sums = {plane_row<&Device::tiles_accum, &pt_ctx::g_tiles_accum, &pt_ctx::f_accum>(PLANE_F64X3), fill_sums, 0};
+const Gathered g_m2 = {plane_row<&Device::tiles_m2, &pt_ctx::g_tiles_m2, &pt_ctx::f_m2>(PLANE_F64X3), dev_finish_moments, 0};
+const Gathered g_counts = {plane_row<&Device::tiles_seg, &pt_ctx::g_tiles_seg, &pt_ctx::f_seg>(PLANE_U32A), fill_counts, 0};
+const Gathered g_feature[3] = {{plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_n>(PLANE_F64X3), fill_feature, 0},
+                               {plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_a>(PLANE_F64X3), fill_feature, 1},
+                               {plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_d>(PLANE_F64X3), fill_feature, 2}};
+const Gathered g_half[4] = {{plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_sa>(PLANE_F64X3), dev_finish_halves, 0},
+                            {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_qa>(PLANE_F64X3), dev_finish_halves, 1},
+                            {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_sb>(PLANE_F64X3), dev_finish_halves, 2},
+                            {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_qb>(PLANE_F64X3), dev_finish_halves, 3}};
+
+// The inputs of the post-frame filters as row-major planes on devices[0]: the four half sums or S and Q, the counts of an adaptive
+// frame, the features of a frame that has them.  All reads: the sums, the block table and the event lists of the frame stay as they are.
+int32_t gather_filter_inputs(pt_ctx *ctx, bool halves) {
+    const Frame &fr = ctx->frame;
+    if (halves) {
+        for (const Gathered &g : g_half)
+            if (int32_t rc = gather_one(ctx, g, nullptr)) return rc;
+    } else {
+        if (int32_t rc = gather_one(ctx, g_sums, nullptr)) return rc;
+        if (int32_t rc = gather_one(ctx, g_m2, nullptr)) return rc;
+    }
+    if (fr.adaptive)
+        if (int32_t rc = gather_one(ctx, g_counts, nullptr)) return rc;
+    if (fr.features > 0)
+        for (const Gathered &g : g_feature)
+            if (int32_t rc = gather_one(ctx, g, nullptr)) return rc;
+    return PT_OK;
+}
+
+// ---- What the entry points that read a finished frame ask of it.  The frame is the open one, or the last one finished on ctx (its
+// sums stay on the devices until the next frame opens), with at least one step done; then the needs, tested in the order given.
+enum FrameNeed { NEED_MOMENTS, NEED_ADAPTIVE, NEED_HALVES, NEED_FEATURES, NEED_NOT_GL, NEED_2_SAMPLES };
+
+int32_t frame_needs(pt_ctx *ctx, const char *who, std::initializer_list<FrameNeed> needs) {
+    const Frame &fr = ctx->frame;
+    const std::string w = std::string(who) + ": ";
+    if (fr.done_spp <= 0 || fr.chunk == 0) return fail(PT_ERR_STATE, w + "no frame with samples on this context (pt_step or pt_render first)");
+    // (an adaptive block stops at two samples or more, so every pixel holds at least min(done, 2))
+    const struct { bool met; const char *text; } table[] = {
+        {fr.moments, "the frame was rendered with moments off (pt_set_moments)"},
+        {fr.adaptive, "the frame was rendered with adaptive sampling off (pt_set_adaptive)"},
+        {fr.halves, "the frame was rendered with halves off (pt_set_halves)"},
+        {fr.features > 0, "the frame was rendered with features off (pt_set_features)"},
+        {!fr.gl, "not available for a frame rendered with GL shading (pt_set_shading)"},
+        {fr.done_spp >= 2, "every pixel needs at least 2 samples"}};
+    for (FrameNeed n : needs)
+        if (!table[n].met) return fail(PT_ERR_STATE, w + table[n].text);
+    return PT_OK;
+}
+
+int32_t stride_fits(const Frame &fr, const uint8_t *rgba, int32_t stride) {
+    if (rgba && stride < fr.cfg.width * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
+    return PT_OK;
+}
+
+// The filter configuration of entry point `who`: the caller's, or the defaults with `iterations`; `what` is "" or, where the filter
+// is one argument among others, "filter ".
+int32_t filter_config(const char *who, const char *what, const pt_atrous_config *cfg, int32_t iterations, pt_atrous_config &c) {
+    c = {iterations, 0, 4.0, 0.1, 0.1, 0.2};
+    if (cfg) c = *cfg;
+    const std::string w = std::string(who) + ": " + what;
+    if (c.iterations < 0 || c.iterations > PTA_MAX_ITERATIONS) return fail(PT_ERR_INVALID, w + "iterations must be 0..6");
+    if (!(c.sigma_l > 0.0) || !(c.sigma_n >= 0.0) || !(c.sigma_z >= 0.0) || !(c.sigma_a >= 0.0))
+        return fail(PT_ERR_INVALID, w + "sigma_l must be > 0, sigma_n, sigma_z and sigma_a >= 0 (0 = term off)");
+    return PT_OK;
+}
+
+// The wall clock and the N events of one filter call: created where the call is about to launch, destroyed with the scope, on every
+// path.  (Not Device::ev: those lists are the open frame's statistics.)
+template <int N>
+struct FilterClock {
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    hipEvent_t ev[N] = {};
+    FilterClock() = default;
+    FilterClock(const FilterClock &) = delete;
+    FilterClock &operator=(const FilterClock &) = delete;
+    ~FilterClock() {
+        if (g_leave_device_memory) return;
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int32_t create() {
+        for (hipEvent_t &e : ev)
+            if (hipError_t err = hipEventCreate(&e); err != hipSuccess) return fail(PT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(err));
+        return PT_OK;
+    }
+    double wall_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// What pt_atrous and pt_temporal filter in and into, for a frame of npix pixels (devices[0] is current).
+int32_t reserve_filter(pt_ctx *ctx, size_t npix) {
+    pt_ctx::Atrous &B = ctx->at;
+    for (int k = 0; k < 2; k++) {
+        HIP_TRY(B.col[k].reserve(3 * npix));
+        HIP_TRY(B.var[k].reserve(npix));
+    }
+    HIP_TRY(B.guide.reserve(npix));
+    HIP_TRY(B.part.reserve(2 * (size_t)ptl::grid_1d(npix)));
+    HIP_TRY(ctx->f_rgba.reserve(npix * 4));
+    return PT_OK;
+}
+
+// rgba (rows `stride` bytes apart), mean and var of pt_atrous and pt_temporal to the host, each when asked for, on devices[0]'s stream
+int32_t copy_filtered(pt_ctx *ctx, int cur, uint8_t *rgba, int32_t stride, double *mean, double *var) {
+    const size_t W = (size_t)ctx->frame.cfg.width, H = (size_t)ctx->frame.cfg.height;
+    const hipStream_t s = ctx->devs[0].stream;
+    if (rgba) HIP_TRY(hipMemcpy2DAsync(rgba, (size_t)stride, ctx->f_rgba.p, W * 4, W * 4, H, hipMemcpyDeviceToHost, s));
+    if (mean) HIP_TRY(hipMemcpyAsync(mean, ctx->at.col[cur].p, 3 * W * H * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (var) HIP_TRY(hipMemcpyAsync(var, ctx->at.var[cur].p, W * H * sizeof(double), hipMemcpyDeviceToHost, s));
+    return PT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2339,7 +2504,7 @@ int32_t pt_post_process(pt_ctx *ctx, const pt_post_config *post, const double *a
     HIP_TRY(ctx->g_tiles_rgba.reserve(npix * 4));  // second frame-sized byte buffer (ping-pong)
     uint8_t *cur = ctx->f_rgba.p, *other = ctx->g_tiles_rgba.p;
     hipStream_t s = d.own_stream;
-    const unsigned grid = (unsigned)((npix + PT_BLOCK - 1) / PT_BLOCK);
+    const unsigned grid = ptl::grid_1d(npix);
     if (post->tonemap) {
         HIP_TRY(ctx->f_accum.reserve(npix * 3));
         HIP_TRY(hipMemcpyAsync(ctx->f_accum.p, accum, npix * 3 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -2620,7 +2785,7 @@ int32_t pt_step(pt_ctx *ctx, int32_t nspp, int32_t *done_spp) {
 // the frame so far: rgba (always gathered; copied when asked for), the sums, the per-pixel counters
 static int32_t read_frame(pt_ctx *ctx, uint8_t *rgba, int32_t stride, double *accum, uint32_t *nseg, uint32_t *ndraw) {
     Frame &fr = ctx->frame;
-    if (rgba && stride < fr.cfg.width * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
+    if (int32_t rc = stride_fits(fr, rgba, stride)) return rc;
     const bool want_stats = fr.stats_on && (nseg || ndraw);
     const int32_t spp_done = fr.done_spp;
     const Plane planes[] = {
@@ -2736,25 +2901,9 @@ int32_t pt_set_adaptive(pt_ctx *ctx, const pt_adaptive *a) {
     return PT_OK;
 }
 
-// The frame whose sums pt_read_moments / pt_noise_estimate read: the open one, or the last one finished on ctx (its sums stay
-// on the devices until the next frame opens), with at least one step done and moments collected.
-static int32_t moments_frame(pt_ctx *ctx, const char *who) {
-    const Frame &fr = ctx->frame;
-    if (fr.done_spp <= 0 || fr.chunk == 0)
-        return fail(PT_ERR_STATE, std::string(who) + ": no frame with samples on this context (pt_step or pt_render first)");
-    if (!fr.moments) return fail(PT_ERR_STATE, std::string(who) + ": the frame was rendered with moments off (pt_set_moments)");
-    return PT_OK;
-}
-
-static int32_t adaptive_frame(pt_ctx *ctx, const char *who) {
-    if (int32_t rc = moments_frame(ctx, who)) return rc;
-    if (!ctx->frame.adaptive) return fail(PT_ERR_STATE, std::string(who) + ": the frame was rendered with adaptive sampling off (pt_set_adaptive)");
-    return PT_OK;
-}
-
 int32_t pt_adaptive_state(pt_ctx *ctx, struct pt_adaptive_state *out) {
     if (!ctx || !out) return fail(PT_ERR_INVALID, "null argument");
-    if (int32_t rc = adaptive_frame(ctx, "pt_adaptive_state")) return rc;
+    if (int32_t rc = frame_needs(ctx, "pt_adaptive_state", {NEED_MOMENTS, NEED_ADAPTIVE})) return rc;
     const Frame &fr = ctx->frame;
     struct pt_adaptive_state r;
     std::memset(&r, 0, sizeof r);
@@ -2782,32 +2931,21 @@ int32_t pt_adaptive_state(pt_ctx *ctx, struct pt_adaptive_state *out) {
     return PT_OK;
 }
 
-// the counts plane: per device tile-major by counts_tiles_kernel, through untile_kernel's u32a plane (the buffers of read_frame's nseg)
 int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp) {
     if (!ctx || !spp) return fail(PT_ERR_INVALID, "null argument");
-    if (int32_t rc = adaptive_frame(ctx, "pt_read_sample_counts")) return rc;
-    const Plane planes[] = {
-        {true, PLANE_U32A, reserved<Device, &Device::tiles_seg>, reserved<pt_ctx, &pt_ctx::g_tiles_seg>, reserved<pt_ctx, &pt_ctx::f_seg>, spp, 0}};
-    return gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
-        hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p,
-                           static_cast<uint32_t *>(dst[0]), d.nslots, tile_geom(ctx->frame, d));
-        HIP_TRY(hipGetLastError());
-        return PT_OK;
-    });
+    if (int32_t rc = frame_needs(ctx, "pt_read_sample_counts", {NEED_MOMENTS, NEED_ADAPTIVE})) return rc;
+    return gather_one(ctx, g_counts, spp);
 }
 
-// the second moments, in the layout of accum
 int32_t pt_read_moments(pt_ctx *ctx, double *m2) {
     if (!ctx || !m2) return fail(PT_ERR_INVALID, "null argument");
-    if (int32_t rc = moments_frame(ctx, "pt_read_moments")) return rc;
-    const Plane planes[] = {
-        {true, PLANE_F64X3, reserved<Device, &Device::tiles_m2>, reserved<pt_ctx, &pt_ctx::g_tiles_m2>, reserved<pt_ctx, &pt_ctx::f_m2>, m2, 0}};
-    return gather_planes(ctx, planes, [&](Device &d, void *const *dst) { return dev_finish_moments(ctx, d, static_cast<double *>(dst[0])); });
+    if (int32_t rc = frame_needs(ctx, "pt_read_moments", {NEED_MOMENTS})) return rc;
+    return gather_one(ctx, g_m2, m2);
 }
 
 int32_t pt_noise_estimate(pt_ctx *ctx, pt_noise *out) {
     if (!ctx || !out) return fail(PT_ERR_INVALID, "null argument");
-    if (int32_t rc = moments_frame(ctx, "pt_noise_estimate")) return rc;
+    if (int32_t rc = frame_needs(ctx, "pt_noise_estimate", {NEED_MOMENTS})) return rc;
     const Frame &fr = ctx->frame;
     pt_noise r;
     std::memset(&r, 0, sizeof r);
@@ -2858,183 +2996,75 @@ int32_t pt_set_features(pt_ctx *ctx, int32_t k) {
     return PT_OK;
 }
 
-// one feature plane (0 normal, 1 albedo, 2 depth) through the gather, into the context's row-major frame and, when asked for, to the host
-static int32_t gather_feature(pt_ctx *ctx, uint32_t which, double *host) {
-    static void *(*const frames[3])(pt_ctx &, size_t, hipError_t &) = {reserved<pt_ctx, &pt_ctx::f_feat_n>, reserved<pt_ctx, &pt_ctx::f_feat_a>,
-                                                                       reserved<pt_ctx, &pt_ctx::f_feat_d>};
-    const Plane planes[] = {{true, PLANE_F64X3, reserved<Device, &Device::tiles_feat>, reserved<pt_ctx, &pt_ctx::g_tiles_feat>, frames[which], host, 0}};
-    return gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
-        hipLaunchKernelGGL(ptk::feature_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.feat.p,
-                           static_cast<double *>(dst[0]), d.nslots, which, tile_geom(ctx->frame, d));
-        HIP_TRY(hipGetLastError());
-        return PT_OK;
-    });
-}
-
 int32_t pt_read_features(pt_ctx *ctx, double *normal, double *albedo, double *depth) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
-    if (int32_t rc = moments_frame(ctx, "pt_read_features")) return rc;
-    const Frame &fr = ctx->frame;
-    if (fr.features <= 0) return fail(PT_ERR_STATE, "pt_read_features: the frame was rendered with features off (pt_set_features)");
+    if (int32_t rc = frame_needs(ctx, "pt_read_features", {NEED_MOMENTS, NEED_FEATURES})) return rc;
     double *const host[3] = {normal, albedo, depth};
     for (uint32_t k = 0; k < 3u; k++)
         if (host[k])
-            if (int32_t rc = gather_feature(ctx, k, host[k])) return rc;
-    return PT_OK;
-}
-
-// The inputs of pt_atrous and pt_temporal as row-major planes on devices[0] (f_accum, f_m2, f_seg, f_feat_*).
-static int32_t gather_filter_inputs(pt_ctx *ctx) {
-    Frame &fr = ctx->frame;
-    // the inputs as row-major planes on devices[0]: S, Q, the counts of an adaptive frame, the features of a frame that has them.  All
-    // reads: the sums, the block table and the event lists of the frame stay as they are.
-    {
-        const Plane planes[] = {
-            {true, PLANE_F64X3, reserved<Device, &Device::tiles_accum>, reserved<pt_ctx, &pt_ctx::g_tiles_accum>, reserved<pt_ctx, &pt_ctx::f_accum>, nullptr, 0}};
-        if (int32_t rc = gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
-                ptk::ResolveArgs R;
-                std::memset(&R, 0, sizeof R);
-                R.acc = d.acc.p;
-                R.tiles_accum = static_cast<double *>(dst[0]);
-                R.nslots = d.nslots;
-                R.first = d.acc_started ? 0 : 1;
-                R.finish = 1;
-                R.G = tile_geom(fr, d);
-                hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
-                HIP_TRY(hipGetLastError());
-                return PT_OK;
-            }))
-            return rc;
-    }
-    {
-        const Plane planes[] = {
-            {true, PLANE_F64X3, reserved<Device, &Device::tiles_m2>, reserved<pt_ctx, &pt_ctx::g_tiles_m2>, reserved<pt_ctx, &pt_ctx::f_m2>, nullptr, 0}};
-        if (int32_t rc = gather_planes(ctx, planes, [&](Device &d, void *const *dst) { return dev_finish_moments(ctx, d, static_cast<double *>(dst[0])); }))
-            return rc;
-    }
-    if (fr.adaptive) {
-        const Plane planes[] = {
-            {true, PLANE_U32A, reserved<Device, &Device::tiles_seg>, reserved<pt_ctx, &pt_ctx::g_tiles_seg>, reserved<pt_ctx, &pt_ctx::f_seg>, nullptr, 0}};
-        if (int32_t rc = gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
-                hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p,
-                                   static_cast<uint32_t *>(dst[0]), d.nslots, tile_geom(fr, d));
-                HIP_TRY(hipGetLastError());
-                return PT_OK;
-            }))
-            return rc;
-    }
-    if (fr.features > 0)
-        for (uint32_t k = 0; k < 3u; k++)
-            if (int32_t rc = gather_feature(ctx, k, nullptr)) return rc;
+            if (int32_t rc = gather_one(ctx, g_feature[k], host[k])) return rc;
     return PT_OK;
 }
 
 int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32_t stride, double *mean, double *var, pt_atrous_stats *stats) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
-    pt_atrous_config c = {5, 0, 4.0, 0.1, 0.1, 0.2};
-    if (cfg) c = *cfg;
-    if (c.iterations < 0 || c.iterations > PTA_MAX_ITERATIONS) return fail(PT_ERR_INVALID, "pt_atrous: iterations must be 0..6");
-    if (!(c.sigma_l > 0.0) || !(c.sigma_n >= 0.0) || !(c.sigma_z >= 0.0) || !(c.sigma_a >= 0.0))
-        return fail(PT_ERR_INVALID, "pt_atrous: sigma_l must be > 0, sigma_n, sigma_z and sigma_a >= 0 (0 = term off)");
-    if (int32_t rc = moments_frame(ctx, "pt_atrous")) return rc;
+    pt_atrous_config c;
+    if (int32_t rc = filter_config("pt_atrous", "", cfg, 5, c)) return rc;
+    if (int32_t rc = frame_needs(ctx, "pt_atrous", {NEED_MOMENTS, NEED_NOT_GL, NEED_2_SAMPLES})) return rc;
     Frame &fr = ctx->frame;
-    if (fr.gl) return fail(PT_ERR_STATE, "pt_atrous: not available for a frame rendered with GL shading (pt_set_shading)");
-    // (an adaptive block stops at two samples or more, so every pixel holds at least min(done, 2))
-    if (fr.done_spp < 2) return fail(PT_ERR_STATE, "pt_atrous: every pixel needs at least 2 samples");
+    if (int32_t rc = stride_fits(fr, rgba, stride)) return rc;
     const int32_t W = fr.cfg.width, H = fr.cfg.height;
-    if (rgba && stride < W * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    if (int32_t rc = gather_filter_inputs(ctx)) return rc;
+    FilterClock<2> clock;
+    if (int32_t rc = gather_filter_inputs(ctx, false)) return rc;
     const bool feat = fr.features > 0;
     Device &d0 = ctx->devs[0];
+    pt_ctx::Atrous &B = ctx->at;
     HIP_TRY(hipSetDevice(d0.ordinal));
     const size_t npix = (size_t)W * (size_t)H;
-    const uint32_t grid1 = (uint32_t)((npix + PT_BLOCK - 1) / PT_BLOCK);
-    for (int k = 0; k < 2; k++) {
-        HIP_TRY(ctx->at_col[k].reserve(3 * npix));
-        HIP_TRY(ctx->at_var[k].reserve(npix));
+    const uint32_t grid1 = ptl::grid_1d(npix);
+    if (int32_t rc = reserve_filter(ctx, npix)) return rc;
+    if (int32_t rc = clock.create()) return rc;
+    HIP_TRY(hipEventRecord(clock.ev[0], d0.stream));
+    ptk::AtrousPrepArgs PA;
+    std::memset(&PA, 0, sizeof PA);
+    PA.acc = ctx->f_accum.p;
+    PA.m2 = ctx->f_m2.p;
+    PA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
+    PA.fn = feat ? ctx->f_feat_n.p : nullptr;
+    PA.fa = feat ? ctx->f_feat_a.p : nullptr;
+    PA.fd = feat ? ctx->f_feat_d.p : nullptr;
+    PA.col = B.col[0].p;
+    PA.var = B.var[0].p;
+    PA.guide = B.guide.p;
+    PA.npix = (uint32_t)npix;
+    PA.n = (uint32_t)fr.done_spp;
+    hipLaunchKernelGGL(ptk::atrous_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, PA);
+    double *const col[2] = {B.col[0].p, B.col[1].p}, *const vr[2] = {B.var[0].p, B.var[1].p};
+    const pta::Params P = ptl::filter_params(c, feat);
+    const int cur = ptl::filter_sequence(&P, col, vr, B.guide.p, B.part.p, ctx->f_rgba.p, W, H, d0.stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(clock.ev[1], d0.stream));
+    std::vector<ptk::NoisePartial> part(2 * (size_t)grid1);
+    HIP_TRY(hipMemcpyAsync(part.data(), B.part.p, part.size() * sizeof(ptk::NoisePartial), hipMemcpyDeviceToHost, d0.stream));
+    if (int32_t rc = copy_filtered(ctx, cur, rgba, stride, mean, var)) return rc;
+    HIP_TRY(hipStreamSynchronize(d0.stream));
+    if (stats) {
+        pt_atrous_stats st;
+        std::memset(&st, 0, sizeof st);
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, clock.ev[0], clock.ev[1]));
+        st.atrous_ms = ms;
+        st.launches = c.iterations + 4;
+        st.iterations = c.iterations;
+        const ptl::NoiseFigures f = ptl::noise_figures(part.data(), grid1, true, npix);
+        st.bad_pixels = f.bad;
+        st.noise_before = f.before;
+        st.noise_after = f.after;
+        *stats = st;
     }
-    HIP_TRY(ctx->at_guide.reserve(npix));
-    HIP_TRY(ctx->at_part.reserve(2 * (size_t)grid1));
-    HIP_TRY(ctx->f_rgba.reserve(npix * 4));
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev[0]));
-    if (hipError_t e = hipEventCreate(&ev[1]); e != hipSuccess) {
-        (void)hipEventDestroy(ev[0]);
-        return fail(PT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-    }
-    auto run = [&]() -> int32_t {
-        HIP_TRY(hipEventRecord(ev[0], d0.stream));
-        ptk::AtrousPrepArgs PA;
-        std::memset(&PA, 0, sizeof PA);
-        PA.acc = ctx->f_accum.p;
-        PA.m2 = ctx->f_m2.p;
-        PA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
-        PA.fn = feat ? ctx->f_feat_n.p : nullptr;
-        PA.fa = feat ? ctx->f_feat_a.p : nullptr;
-        PA.fd = feat ? ctx->f_feat_d.p : nullptr;
-        PA.col = ctx->at_col[0].p;
-        PA.var = ctx->at_var[0].p;
-        PA.guide = ctx->at_guide.p;
-        PA.npix = (uint32_t)npix;
-        PA.n = (uint32_t)fr.done_spp;
-        hipLaunchKernelGGL(ptk::atrous_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, PA);
-        hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[0].p, ctx->at_var[0].p, ctx->at_guide.p,
-                           ctx->at_part.p, (uint32_t)npix);
-        ptk::AtrousArgs A;
-        std::memset(&A, 0, sizeof A);
-        A.P.sigma_l = c.sigma_l; A.P.sigma_n = c.sigma_n; A.P.sigma_z = c.sigma_z; A.P.sigma_a = c.sigma_a;
-        A.P.iterations = c.iterations;
-        A.P.n_on = feat && c.sigma_n > 0.0;
-        A.P.z_on = feat && c.sigma_z > 0.0;
-        A.P.a_on = feat && c.sigma_a > 0.0;
-        A.guide = ctx->at_guide.p;
-        A.W = W;
-        A.H = H;
-        int cur = 0;
-        for (int32_t t = 0; t < c.iterations; t++, cur ^= 1) {
-            A.col = ctx->at_col[cur].p; A.var = ctx->at_var[cur].p;
-            A.col_out = ctx->at_col[cur ^ 1].p; A.var_out = ctx->at_var[cur ^ 1].p;
-            A.step = 1 << t;
-            hipLaunchKernelGGL(ptk::atrous_kernel, dim3((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8)), dim3(PT_BLOCK), 0, d0.stream, A);
-        }
-        hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[cur].p, ctx->at_var[cur].p, ctx->at_guide.p,
-                           ctx->at_part.p + grid1, (uint32_t)npix);
-        hipLaunchKernelGGL(ptk::atrous_finish_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[cur].p, ctx->f_rgba.p, (uint32_t)npix);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[1], d0.stream));
-        std::vector<ptk::NoisePartial> part(2 * (size_t)grid1);
-        HIP_TRY(hipMemcpyAsync(part.data(), ctx->at_part.p, part.size() * sizeof(ptk::NoisePartial), hipMemcpyDeviceToHost, d0.stream));
-        if (rgba) HIP_TRY(hipMemcpy2DAsync(rgba, (size_t)stride, ctx->f_rgba.p, (size_t)W * 4, (size_t)W * 4, (size_t)H, hipMemcpyDeviceToHost, d0.stream));
-        if (mean) HIP_TRY(hipMemcpyAsync(mean, ctx->at_col[cur].p, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
-        if (var) HIP_TRY(hipMemcpyAsync(var, ctx->at_var[cur].p, npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
-        HIP_TRY(hipStreamSynchronize(d0.stream));
-        if (stats) {
-            pt_atrous_stats st;
-            std::memset(&st, 0, sizeof st);
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            st.atrous_ms = ms;
-            st.launches = c.iterations + 4;
-            st.iterations = c.iterations;
-            double sum[2] = {0.0, 0.0};
-            for (int k = 0; k < 2; k++)
-                for (uint32_t b = 0; b < grid1; b++) sum[k] += part[(size_t)k * grid1 + b].sum;  // partials in block order
-            for (uint32_t b = 0; b < grid1; b++) st.bad_pixels += part[b].bad;
-            st.noise_before = std::sqrt(sum[0] / (double)npix);
-            st.noise_after = std::sqrt(sum[1] / (double)npix);
-            *stats = st;
-        }
-        return PT_OK;
-    };
-    const int32_t rc = run();
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-    if (rc == PT_OK && std::getenv("PTCORE_VERBOSE"))
-        std::fprintf(stderr, "ptcore: pt_atrous %d iterations, %.3f ms host wall (gathers included)\n", c.iterations,
-                     std::chrono::duration<double, std::milli>(clk::now() - t0).count());
-    return rc;
+    if (std::getenv("PTCORE_VERBOSE"))
+        std::fprintf(stderr, "ptcore: pt_atrous %d iterations, %.3f ms host wall (gathers included)\n", c.iterations, clock.wall_ms());
+    return PT_OK;
 }
 
 int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_config *filter, uint8_t *rgba, int32_t stride, double *mean,
@@ -3044,192 +3074,137 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
     if (cfg) c = *cfg;
     if (!(c.alpha >= 0.0 && c.alpha <= 1.0) || !(c.tol_z >= 0.0) || !(c.tol_a >= 0.0) || c.n_min != c.n_min || c.max_len < 1)
         return fail(PT_ERR_INVALID, "pt_temporal: alpha must be 0..1, tol_z and tol_a >= 0, n_min a number, max_len >= 1");
-    pt_atrous_config f = {0, 0, 4.0, 0.1, 0.1, 0.2};
-    if (filter) f = *filter;
-    if (f.iterations < 0 || f.iterations > PTA_MAX_ITERATIONS) return fail(PT_ERR_INVALID, "pt_temporal: filter iterations must be 0..6");
-    if (!(f.sigma_l > 0.0) || !(f.sigma_n >= 0.0) || !(f.sigma_z >= 0.0) || !(f.sigma_a >= 0.0))
-        return fail(PT_ERR_INVALID, "pt_temporal: filter sigma_l must be > 0, sigma_n, sigma_z and sigma_a >= 0 (0 = term off)");
-    if (int32_t rc = moments_frame(ctx, "pt_temporal")) return rc;
+    pt_atrous_config f;
+    if (int32_t rc = filter_config("pt_temporal", "filter ", filter, 0, f)) return rc;
+    if (int32_t rc = frame_needs(ctx, "pt_temporal", {NEED_MOMENTS})) return rc;
     Frame &fr = ctx->frame;
-    const int32_t W = fr.cfg.width, H = fr.cfg.height;
-    if (rgba && stride < W * 4) return fail(PT_ERR_INVALID, "stride smaller than 4*width");
-    if (fr.gl) return fail(PT_ERR_STATE, "pt_temporal: not available for a frame rendered with GL shading (pt_set_shading)");
-    if (fr.features <= 0) return fail(PT_ERR_STATE, "pt_temporal: the frame was rendered with features off (pt_set_features)");
-    if (fr.done_spp < 2) return fail(PT_ERR_STATE, "pt_temporal: every pixel needs at least 2 samples");
-    if (ctx->tp_serial == fr.serial && ctx->tp_spp == fr.done_spp)
+    pt_ctx::Temporal &T = ctx->tp;
+    if (int32_t rc = stride_fits(fr, rgba, stride)) return rc;
+    if (int32_t rc = frame_needs(ctx, "pt_temporal", {NEED_NOT_GL, NEED_FEATURES, NEED_2_SAMPLES})) return rc;
+    if (T.serial == fr.serial && T.spp == fr.done_spp)
         return fail(PT_ERR_STATE, "pt_temporal: already accumulated (this frame, at this number of samples, is in the history)");
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    if (int32_t rc = gather_filter_inputs(ctx)) return rc;
+    const int32_t W = fr.cfg.width, H = fr.cfg.height;
+    FilterClock<3> clock;  // events: first launch, last launch complete, temporal_kernel complete
+    if (int32_t rc = gather_filter_inputs(ctx, false)) return rc;
     Device &d0 = ctx->devs[0];
+    pt_ctx::Atrous &B = ctx->at;
     HIP_TRY(hipSetDevice(d0.ordinal));
     const size_t npix = (size_t)W * (size_t)H;
-    const uint32_t grid1 = (uint32_t)((npix + PT_BLOCK - 1) / PT_BLOCK);
-    const dim3 grid2((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8));
+    const uint32_t grid1 = ptl::grid_1d(npix);
+    const dim3 grid2 = ptl::grid_2d(W, H);
     const size_t nblk = (size_t)grid2.x * grid2.y;
-    const bool have = ctx->tp_valid && ctx->tp_w == W && ctx->tp_h == H;  // another size: the history is dropped (when the call succeeds)
+    const bool have = T.valid && T.w == W && T.h == H;  // another size: the history is dropped (when the call succeeds)
     // Both sets are kept at the size of this frame.  A set that has to grow loses its contents, which is what a change of size means;
     // a smaller frame after a larger one keeps the memory and is caught by `have`.
     for (int k = 0; k < 2; k++) {
-        if (ctx->tp_hist[k].cap < (size_t)PTT_PLANES * npix) ctx->tp_valid = false;
-        if (hipError_t e = ctx->tp_hist[k].reserve((size_t)PTT_PLANES * npix); e != hipSuccess)
+        if (T.hist[k].cap < (size_t)PTT_PLANES * npix) T.valid = false;
+        if (hipError_t e = T.hist[k].reserve((size_t)PTT_PLANES * npix); e != hipSuccess)
             return fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("pt_temporal: history: ") + hipGetErrorString(e));
-        HIP_TRY(ctx->at_col[k].reserve(3 * npix));
-        HIP_TRY(ctx->at_var[k].reserve(npix));
     }
-    HIP_TRY(ctx->tp_part.reserve(nblk));
-    HIP_TRY(ctx->at_guide.reserve(npix));
-    HIP_TRY(ctx->at_part.reserve(2 * (size_t)grid1));
-    HIP_TRY(ctx->f_rgba.reserve(npix * 4));
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // first launch, last launch complete, temporal_kernel complete
-    for (int k = 0; k < 3; k++)
-        if (hipError_t e = hipEventCreate(&ev[k]); e != hipSuccess) {
-            for (int j = 0; j < k; j++) (void)hipEventDestroy(ev[j]);
-            return fail(PT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-        }
+    HIP_TRY(T.part.reserve(nblk));
+    if (int32_t rc = reserve_filter(ctx, npix)) return rc;
+    if (int32_t rc = clock.create()) return rc;
+    const int next = T.cur ^ 1;  // a failed call leaves the stored history untouched: the kernel writes the other set
+    HIP_TRY(hipEventRecord(clock.ev[0], d0.stream));
+    ptk::TemporalArgs TA;
+    std::memset(&TA, 0, sizeof TA);
+    TA.C.alpha = c.alpha; TA.C.tol_z = c.tol_z; TA.C.n_min = c.n_min; TA.C.tol_a = c.tol_a;
+    TA.C.max_len = c.max_len;
+    TA.C.have_history = have ? 1 : 0;
+    TA.C.clip_gamma = T.clip;
+    TA.V.cam = fr.cam;
+    TA.V.inv_width = fr.F.inv_width;
+    TA.V.inv_height = fr.F.inv_height;
+    TA.V.W = W;
+    TA.V.H = H;
+    TA.cam_h = T.cam;
+    TA.acc = ctx->f_accum.p;
+    TA.m2 = ctx->f_m2.p;
+    TA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
+    TA.fn = ctx->f_feat_n.p;
+    TA.fa = ctx->f_feat_a.p;
+    TA.fd = ctx->f_feat_d.p;
+    TA.hist = T.hist[T.cur].p;
+    TA.hist_out = T.hist[next].p;
+    TA.col = B.col[0].p;
+    TA.var = B.var[0].p;
+    TA.guide = B.guide.p;
+    TA.partial = T.part.p;
+    TA.n = (uint32_t)fr.done_spp;
+    hipLaunchKernelGGL(ptk::temporal_kernel, grid2, dim3(PT_BLOCK), 0, d0.stream, TA);
+    HIP_TRY(hipEventRecord(clock.ev[2], d0.stream));
+    double *const col[2] = {B.col[0].p, B.col[1].p}, *const vr[2] = {B.var[0].p, B.var[1].p};
+    const pta::Params P = ptl::filter_params(f, true);
+    const int cur = ptl::filter_sequence(filter ? &P : nullptr, col, vr, B.guide.p, B.part.p, ctx->f_rgba.p, W, H, d0.stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(clock.ev[1], d0.stream));
+    std::vector<ptk::NoisePartial> part(2 * (size_t)grid1);
+    std::vector<ptk::TemporalPartial> tpart(nblk);
+    HIP_TRY(hipMemcpyAsync(part.data(), B.part.p, (filter ? 2 : 1) * (size_t)grid1 * sizeof(ptk::NoisePartial), hipMemcpyDeviceToHost, d0.stream));
+    HIP_TRY(hipMemcpyAsync(tpart.data(), T.part.p, nblk * sizeof(ptk::TemporalPartial), hipMemcpyDeviceToHost, d0.stream));
+    if (int32_t rc = copy_filtered(ctx, cur, rgba, stride, mean, var)) return rc;
+    HIP_TRY(hipStreamSynchronize(d0.stream));
     float kernel_ms = 0;
-    const int next = ctx->tp_cur ^ 1;
-    struct pt_temporal_clip_stats cs = {ctx->tp_clip, 0, 0};
-    auto run = [&]() -> int32_t {
-        HIP_TRY(hipEventRecord(ev[0], d0.stream));
-        ptk::TemporalArgs TA;
-        std::memset(&TA, 0, sizeof TA);
-        TA.C.alpha = c.alpha; TA.C.tol_z = c.tol_z; TA.C.n_min = c.n_min; TA.C.tol_a = c.tol_a;
-        TA.C.max_len = c.max_len;
-        TA.C.have_history = have ? 1 : 0;
-        TA.C.clip_gamma = ctx->tp_clip;
-        TA.V.cam = fr.cam;
-        TA.V.inv_width = fr.F.inv_width;
-        TA.V.inv_height = fr.F.inv_height;
-        TA.V.W = W;
-        TA.V.H = H;
-        TA.cam_h = ctx->tp_cam;
-        TA.acc = ctx->f_accum.p;
-        TA.m2 = ctx->f_m2.p;
-        TA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
-        TA.fn = ctx->f_feat_n.p;
-        TA.fa = ctx->f_feat_a.p;
-        TA.fd = ctx->f_feat_d.p;
-        TA.hist = ctx->tp_hist[ctx->tp_cur].p;
-        TA.hist_out = ctx->tp_hist[next].p;
-        TA.col = ctx->at_col[0].p;
-        TA.var = ctx->at_var[0].p;
-        TA.guide = ctx->at_guide.p;
-        TA.partial = ctx->tp_part.p;
-        TA.n = (uint32_t)fr.done_spp;
-        hipLaunchKernelGGL(ptk::temporal_kernel, grid2, dim3(PT_BLOCK), 0, d0.stream, TA);
-        HIP_TRY(hipEventRecord(ev[2], d0.stream));
-        hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[0].p, ctx->at_var[0].p, ctx->at_guide.p,
-                           ctx->at_part.p, (uint32_t)npix);
-        int cur = 0;
-        if (filter) {
-            ptk::AtrousArgs A;
-            std::memset(&A, 0, sizeof A);
-            A.P.sigma_l = f.sigma_l; A.P.sigma_n = f.sigma_n; A.P.sigma_z = f.sigma_z; A.P.sigma_a = f.sigma_a;
-            A.P.iterations = f.iterations;
-            A.P.n_on = f.sigma_n > 0.0;
-            A.P.z_on = f.sigma_z > 0.0;
-            A.P.a_on = f.sigma_a > 0.0;
-            A.guide = ctx->at_guide.p;
-            A.W = W;
-            A.H = H;
-            for (int32_t t = 0; t < f.iterations; t++, cur ^= 1) {
-                A.col = ctx->at_col[cur].p; A.var = ctx->at_var[cur].p;
-                A.col_out = ctx->at_col[cur ^ 1].p; A.var_out = ctx->at_var[cur ^ 1].p;
-                A.step = 1 << t;
-                hipLaunchKernelGGL(ptk::atrous_kernel, grid2, dim3(PT_BLOCK), 0, d0.stream, A);
-            }
-            hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[cur].p, ctx->at_var[cur].p,
-                               ctx->at_guide.p, ctx->at_part.p + grid1, (uint32_t)npix);
-        }
-        hipLaunchKernelGGL(ptk::atrous_finish_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, ctx->at_col[cur].p, ctx->f_rgba.p, (uint32_t)npix);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[1], d0.stream));
-        std::vector<ptk::NoisePartial> part(2 * (size_t)grid1);
-        std::vector<ptk::TemporalPartial> tpart(nblk);
-        HIP_TRY(hipMemcpyAsync(part.data(), ctx->at_part.p, (filter ? 2 : 1) * (size_t)grid1 * sizeof(ptk::NoisePartial), hipMemcpyDeviceToHost, d0.stream));
-        HIP_TRY(hipMemcpyAsync(tpart.data(), ctx->tp_part.p, nblk * sizeof(ptk::TemporalPartial), hipMemcpyDeviceToHost, d0.stream));
-        if (rgba) HIP_TRY(hipMemcpy2DAsync(rgba, (size_t)stride, ctx->f_rgba.p, (size_t)W * 4, (size_t)W * 4, (size_t)H, hipMemcpyDeviceToHost, d0.stream));
-        if (mean) HIP_TRY(hipMemcpyAsync(mean, ctx->at_col[cur].p, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
-        if (var) HIP_TRY(hipMemcpyAsync(var, ctx->at_var[cur].p, npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
-        HIP_TRY(hipStreamSynchronize(d0.stream));
-        HIP_TRY(hipEventElapsedTime(&kernel_ms, ev[0], ev[2]));
-        for (const ptk::TemporalPartial &p : tpart) {
-            cs.clipped += p.clipped;
-            cs.reprojected += p.reprojected;
-        }
-        if (stats) {
-            pt_temporal_stats st;
-            std::memset(&st, 0, sizeof st);
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            st.temporal_ms = ms;
-            st.iterations = filter ? f.iterations : 0;
-            st.launches = filter ? f.iterations + 4 : 3;
-            double sum[3] = {0.0, 0.0, 0.0};
-            unsigned long long lens = 0;
-            for (const ptk::TemporalPartial &p : tpart) {  // partials in block order
-                sum[0] += p.sum_before;
-                st.reprojected += p.reprojected;
-                st.disoccluded += p.disoccluded;
-                lens += p.len_sum;
-            }
-            for (uint32_t b = 0; b < grid1; b++) {
-                sum[1] += part[b].sum;
-                st.bad_pixels += part[b].bad;
-                if (filter) sum[2] += part[(size_t)grid1 + b].sum;
-            }
-            st.mean_len = (double)lens / (double)npix;
-            st.noise_before = std::sqrt(sum[0] / (double)npix);
-            st.noise_blended = std::sqrt(sum[1] / (double)npix);
-            st.noise_after = filter ? std::sqrt(sum[2] / (double)npix) : st.noise_blended;
-            *stats = st;
-        }
-        return PT_OK;
-    };
-    const int32_t rc = run();
-    for (int k = 0; k < 3; k++) (void)hipEventDestroy(ev[k]);
-    if (rc != PT_OK) return rc;  // the stored history is untouched: the kernel wrote the other set
-    ctx->tp_cur = next;
-    ctx->tp_valid = true;
-    ctx->tp_w = W;
-    ctx->tp_h = H;
-    ctx->tp_cam = fr.cam;
-    ctx->tp_serial = fr.serial;
-    ctx->tp_spp = fr.done_spp;
-    ctx->tp_clip_stats = cs;
+    HIP_TRY(hipEventElapsedTime(&kernel_ms, clock.ev[0], clock.ev[2]));
+    const ptl::TemporalFigures tf = ptl::temporal_figures(tpart.data(), nblk, npix);
+    if (stats) {
+        pt_temporal_stats st;
+        std::memset(&st, 0, sizeof st);
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, clock.ev[0], clock.ev[1]));
+        st.temporal_ms = ms;
+        st.iterations = filter ? f.iterations : 0;
+        st.launches = filter ? f.iterations + 4 : 3;
+        const ptl::NoiseFigures nf = ptl::noise_figures(part.data(), grid1, filter != nullptr, npix);
+        st.reprojected = tf.reprojected;
+        st.disoccluded = tf.disoccluded;
+        st.bad_pixels = nf.bad;
+        st.mean_len = (double)tf.len_sum / (double)npix;
+        st.noise_before = tf.noise_before;
+        st.noise_blended = nf.before;
+        st.noise_after = nf.after;
+        *stats = st;
+    }
+    T.cur = next;
+    T.valid = true;
+    T.w = W;
+    T.h = H;
+    T.cam = fr.cam;
+    T.serial = fr.serial;
+    T.spp = fr.done_spp;
+    T.clip_stats = {T.clip, tf.clipped, tf.reprojected};
     if (std::getenv("PTCORE_VERBOSE"))
         std::fprintf(stderr,
                      "ptcore: pt_temporal %d filter iterations, clip gamma %g: clipped %llu of %llu reprojected, temporal_kernel %.3f ms, "
                      "%.3f ms host wall (gathers included)\n",
-                     filter ? f.iterations : 0, cs.gamma, (unsigned long long)cs.clipped, (unsigned long long)cs.reprojected, kernel_ms,
-                     std::chrono::duration<double, std::milli>(clk::now() - t0).count());
+                     filter ? f.iterations : 0, T.clip, (unsigned long long)tf.clipped, (unsigned long long)tf.reprojected, kernel_ms,
+                     clock.wall_ms());
     return PT_OK;
 }
 
 int32_t pt_temporal_set_clip(pt_ctx *ctx, double gamma) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
     if (!(gamma >= 0.0) || std::isinf(gamma)) return fail(PT_ERR_INVALID, "pt_temporal_set_clip: gamma must be a finite number >= 0 (0 = off)");
-    ctx->tp_clip = gamma;
+    ctx->tp.clip = gamma;
     return PT_OK;
 }
 
 int32_t pt_temporal_clip_stats(pt_ctx *ctx, struct pt_temporal_clip_stats *out) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
     if (!out) return fail(PT_ERR_INVALID, "pt_temporal_clip_stats: out is null");
-    if (!ctx->tp_valid) return fail(PT_ERR_STATE, "pt_temporal_clip_stats: the history is empty (pt_temporal first)");
-    *out = ctx->tp_clip_stats;
+    if (!ctx->tp.valid) return fail(PT_ERR_STATE, "pt_temporal_clip_stats: the history is empty (pt_temporal first)");
+    *out = ctx->tp.clip_stats;
     return PT_OK;
 }
 
 int32_t pt_temporal_read(pt_ctx *ctx, double *mean, double *var, int32_t *len) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
-    if (!ctx->tp_valid) return fail(PT_ERR_STATE, "pt_temporal_read: the history is empty (pt_temporal first)");
-    const size_t np = (size_t)ctx->tp_w * (size_t)ctx->tp_h;
+    if (!ctx->tp.valid) return fail(PT_ERR_STATE, "pt_temporal_read: the history is empty (pt_temporal first)");
+    const size_t np = (size_t)ctx->tp.w * (size_t)ctx->tp.h;
     Device &d0 = ctx->devs[0];
     HIP_TRY(hipSetDevice(d0.ordinal));
     std::vector<double> h((size_t)PTT_PLANES * np);
-    HIP_TRY(hipMemcpyAsync(h.data(), ctx->tp_hist[ctx->tp_cur].p, h.size() * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), ctx->tp.hist[ctx->tp.cur].p, h.size() * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
     HIP_TRY(hipStreamSynchronize(d0.stream));
     for (size_t i = 0; i < np; i++) {
         if (mean)
@@ -3242,8 +3217,8 @@ int32_t pt_temporal_read(pt_ctx *ctx, double *mean, double *var, int32_t *len) {
 
 int32_t pt_temporal_reset(pt_ctx *ctx) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
-    ctx->tp_valid = false;
-    ctx->tp_serial = 0;
+    ctx->tp.valid = false;
+    ctx->tp.serial = 0;
     return PT_OK;
 }
 
@@ -3254,40 +3229,22 @@ int32_t pt_set_halves(pt_ctx *ctx, int32_t on) {
     return PT_OK;
 }
 
-static int32_t halves_frame(pt_ctx *ctx, const char *who) {
-    if (int32_t rc = moments_frame(ctx, who)) return rc;
-    if (!ctx->frame.halves) return fail(PT_ERR_STATE, std::string(who) + ": the frame was rendered with halves off (pt_set_halves)");
-    return PT_OK;
-}
-
-// one plane of the half-buffer sums (0 SA, 1 QA, 2 SB, 3 QB) through the gather, into the context's row-major frame and, when asked for, to the host
-static int32_t gather_halves(pt_ctx *ctx, uint32_t which, double *host) {
-    static void *(*const frames[4])(pt_ctx &, size_t, hipError_t &) = {reserved<pt_ctx, &pt_ctx::f_hv_sa>, reserved<pt_ctx, &pt_ctx::f_hv_qa>,
-                                                                       reserved<pt_ctx, &pt_ctx::f_hv_sb>, reserved<pt_ctx, &pt_ctx::f_hv_qb>};
-    const Plane planes[] = {{true, PLANE_F64X3, reserved<Device, &Device::tiles_hv>, reserved<pt_ctx, &pt_ctx::g_tiles_hv>, frames[which], host, 0}};
-    return gather_planes(ctx, planes, [&](Device &d, void *const *dst) { return dev_finish_halves(ctx, d, which, static_cast<double *>(dst[0])); });
-}
-
 int32_t pt_read_halves(pt_ctx *ctx, double *sa, double *qa, double *sb, double *qb) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
-    if (int32_t rc = halves_frame(ctx, "pt_read_halves")) return rc;
+    if (int32_t rc = frame_needs(ctx, "pt_read_halves", {NEED_MOMENTS, NEED_HALVES})) return rc;
     double *const host[4] = {sa, qa, sb, qb};
     for (uint32_t k = 0; k < 4u; k++)
         if (host[k])
-            if (int32_t rc = gather_halves(ctx, k, host[k])) return rc;
+            if (int32_t rc = gather_one(ctx, g_half[k], host[k])) return rc;
     return PT_OK;
 }
 
 int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean, double *err, double *half_means, pt_halves_stats *stats) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
-    pt_atrous_config c = {5, 0, 4.0, 0.1, 0.1, 0.2};
-    if (cfg) c = *cfg;
-    if (c.iterations < 0 || c.iterations > PTA_MAX_ITERATIONS) return fail(PT_ERR_INVALID, "pt_atrous_halves: iterations must be 0..6");
-    if (!(c.sigma_l > 0.0) || !(c.sigma_n >= 0.0) || !(c.sigma_z >= 0.0) || !(c.sigma_a >= 0.0))
-        return fail(PT_ERR_INVALID, "pt_atrous_halves: sigma_l must be > 0, sigma_n, sigma_z and sigma_a >= 0 (0 = term off)");
-    if (int32_t rc = halves_frame(ctx, "pt_atrous_halves")) return rc;
+    pt_atrous_config c;
+    if (int32_t rc = filter_config("pt_atrous_halves", "", cfg, 5, c)) return rc;
+    if (int32_t rc = frame_needs(ctx, "pt_atrous_halves", {NEED_MOMENTS, NEED_HALVES, NEED_NOT_GL})) return rc;
     Frame &fr = ctx->frame;
-    if (fr.gl) return fail(PT_ERR_STATE, "pt_atrous_halves: not available for a frame rendered with GL shading (pt_set_shading)");
     int32_t spp_min = fr.done_spp;  // the smallest count the frame holds: every half needs two samples for its variance
     if (fr.adaptive) {
         struct pt_adaptive_state as;
@@ -3297,122 +3254,75 @@ int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean,
     if (spp_min < 4)
         return fail(PT_ERR_STATE, "pt_atrous_halves: every pixel needs at least 4 samples (the frame's smallest count is " + std::to_string(spp_min) + ")");
     const int32_t W = fr.cfg.width, H = fr.cfg.height;
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    // the inputs as row-major planes on devices[0], all reads: the four sums, the counts of an adaptive frame, the features of a frame that has them
-    for (uint32_t k = 0; k < 4u; k++)
-        if (int32_t rc = gather_halves(ctx, k, nullptr)) return rc;
-    if (fr.adaptive) {
-        const Plane planes[] = {
-            {true, PLANE_U32A, reserved<Device, &Device::tiles_seg>, reserved<pt_ctx, &pt_ctx::g_tiles_seg>, reserved<pt_ctx, &pt_ctx::f_seg>, nullptr, 0}};
-        if (int32_t rc = gather_planes(ctx, planes, [&](Device &d, void *const *dst) -> int32_t {
-                hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p,
-                                   static_cast<uint32_t *>(dst[0]), d.nslots, tile_geom(fr, d));
-                HIP_TRY(hipGetLastError());
-                return PT_OK;
-            }))
-            return rc;
-    }
+    FilterClock<2> clock;
+    if (int32_t rc = gather_filter_inputs(ctx, true)) return rc;
     const bool feat = fr.features > 0;
-    if (feat)
-        for (uint32_t k = 0; k < 3u; k++)
-            if (int32_t rc = gather_feature(ctx, k, nullptr)) return rc;
     Device &d0 = ctx->devs[0];
+    pt_ctx::Halves &B = ctx->ah;
     HIP_TRY(hipSetDevice(d0.ordinal));
     const size_t npix = (size_t)W * (size_t)H;
-    const uint32_t grid1 = (uint32_t)((npix + PT_BLOCK - 1) / PT_BLOCK);
+    const uint32_t grid1 = ptl::grid_1d(npix);
     for (int k = 0; k < 2; k++) {
-        HIP_TRY(ctx->ah_col[k].reserve(6 * npix));
-        HIP_TRY(ctx->ah_var[k].reserve(2 * npix));
+        HIP_TRY(B.col[k].reserve(6 * npix));
+        HIP_TRY(B.var[k].reserve(2 * npix));
     }
-    HIP_TRY(ctx->ah_guide.reserve(PTA_GUIDE_PLANES * npix));
-    HIP_TRY(ctx->ah_mean.reserve(3 * npix));
-    HIP_TRY(ctx->ah_err.reserve(npix));
-    if (half_means) HIP_TRY(ctx->ah_half.reserve(6 * npix));
-    HIP_TRY(ctx->ah_part.reserve(grid1));
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev[0]));
-    if (hipError_t e = hipEventCreate(&ev[1]); e != hipSuccess) {
-        (void)hipEventDestroy(ev[0]);
-        return fail(PT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+    HIP_TRY(B.guide.reserve(PTA_GUIDE_PLANES * npix));
+    HIP_TRY(B.mean.reserve(3 * npix));
+    HIP_TRY(B.err.reserve(npix));
+    if (half_means) HIP_TRY(B.half.reserve(6 * npix));
+    HIP_TRY(B.part.reserve(grid1));
+    if (int32_t rc = clock.create()) return rc;
+    HIP_TRY(hipEventRecord(clock.ev[0], d0.stream));
+    ptk::AtrousPairPrepArgs PA;
+    std::memset(&PA, 0, sizeof PA);
+    PA.sa = ctx->f_hv_sa.p; PA.qa = ctx->f_hv_qa.p; PA.sb = ctx->f_hv_sb.p; PA.qb = ctx->f_hv_qb.p;
+    PA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
+    PA.fn = feat ? ctx->f_feat_n.p : nullptr;
+    PA.fa = feat ? ctx->f_feat_a.p : nullptr;
+    PA.fd = feat ? ctx->f_feat_d.p : nullptr;
+    PA.guide = B.guide.p;
+    PA.col = B.col[0].p;
+    PA.var = B.var[0].p;
+    PA.npix = (uint32_t)npix;
+    PA.n = (uint32_t)fr.done_spp;
+    hipLaunchKernelGGL(ptk::atrous_pair_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, PA);
+    double *const col[2] = {B.col[0].p, B.col[1].p}, *const vr[2] = {B.var[0].p, B.var[1].p};
+    const int cur = ptl::pair_iterations(ptl::filter_params(c, feat), col, vr, B.guide.p, W, H, d0.stream);
+    ptk::HalvesCombineArgs CA;
+    std::memset(&CA, 0, sizeof CA);
+    CA.col = col[cur]; CA.var = vr[cur]; CA.guide = B.guide.p;
+    CA.mean = B.mean.p;
+    CA.err = B.err.p;
+    CA.half_means = half_means ? B.half.p : nullptr;
+    CA.partial = B.part.p;
+    CA.npix = (uint32_t)npix;
+    hipLaunchKernelGGL(ptk::halves_combine_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, CA);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(clock.ev[1], d0.stream));
+    std::vector<ptk::HalvesPartial> part(grid1);
+    HIP_TRY(hipMemcpyAsync(part.data(), B.part.p, part.size() * sizeof(ptk::HalvesPartial), hipMemcpyDeviceToHost, d0.stream));
+    if (mean) HIP_TRY(hipMemcpyAsync(mean, B.mean.p, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+    if (err) HIP_TRY(hipMemcpyAsync(err, B.err.p, npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+    if (half_means) HIP_TRY(hipMemcpyAsync(half_means, B.half.p, 6 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+    HIP_TRY(hipStreamSynchronize(d0.stream));
+    if (stats) {
+        pt_halves_stats st;
+        std::memset(&st, 0, sizeof st);
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, clock.ev[0], clock.ev[1]));
+        st.atrous_ms = ms;
+        st.launches = c.iterations + 2;
+        st.iterations = c.iterations;
+        st.spp_min = spp_min;
+        const ptl::HalvesFigures f = ptl::halves_figures(part.data(), grid1, npix);
+        st.bad_pixels = f.bad;
+        st.noise = f.noise;
+        st.noise_model = f.noise_model;
+        *stats = st;
     }
-    auto run = [&]() -> int32_t {
-        HIP_TRY(hipEventRecord(ev[0], d0.stream));
-        ptk::AtrousPairPrepArgs PA;
-        std::memset(&PA, 0, sizeof PA);
-        PA.sa = ctx->f_hv_sa.p; PA.qa = ctx->f_hv_qa.p; PA.sb = ctx->f_hv_sb.p; PA.qb = ctx->f_hv_qb.p;
-        PA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
-        PA.fn = feat ? ctx->f_feat_n.p : nullptr;
-        PA.fa = feat ? ctx->f_feat_a.p : nullptr;
-        PA.fd = feat ? ctx->f_feat_d.p : nullptr;
-        PA.guide = ctx->ah_guide.p;
-        PA.col = ctx->ah_col[0].p;
-        PA.var = ctx->ah_var[0].p;
-        PA.npix = (uint32_t)npix;
-        PA.n = (uint32_t)fr.done_spp;
-        hipLaunchKernelGGL(ptk::atrous_pair_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, PA);
-        ptk::AtrousPairArgs A;
-        std::memset(&A, 0, sizeof A);
-        A.P.sigma_l = c.sigma_l; A.P.sigma_n = c.sigma_n; A.P.sigma_z = c.sigma_z; A.P.sigma_a = c.sigma_a;
-        A.P.iterations = c.iterations;
-        A.P.n_on = feat && c.sigma_n > 0.0;
-        A.P.z_on = feat && c.sigma_z > 0.0;
-        A.P.a_on = feat && c.sigma_a > 0.0;
-        A.guide = ctx->ah_guide.p;
-        A.W = W;
-        A.H = H;
-        int cur = 0;
-        for (int32_t t = 0; t < c.iterations; t++, cur ^= 1) {
-            A.col = ctx->ah_col[cur].p; A.var = ctx->ah_var[cur].p;
-            A.col_out = ctx->ah_col[cur ^ 1].p; A.var_out = ctx->ah_var[cur ^ 1].p;
-            A.step = 1 << t;
-            hipLaunchKernelGGL(ptk::atrous_pair_kernel, dim3((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8)), dim3(PT_BLOCK), 0, d0.stream, A);
-        }
-        ptk::HalvesCombineArgs CA;
-        std::memset(&CA, 0, sizeof CA);
-        CA.col = ctx->ah_col[cur].p; CA.var = ctx->ah_var[cur].p; CA.guide = ctx->ah_guide.p;
-        CA.mean = ctx->ah_mean.p;
-        CA.err = ctx->ah_err.p;
-        CA.half_means = half_means ? ctx->ah_half.p : nullptr;
-        CA.partial = ctx->ah_part.p;
-        CA.npix = (uint32_t)npix;
-        hipLaunchKernelGGL(ptk::halves_combine_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, CA);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[1], d0.stream));
-        std::vector<ptk::HalvesPartial> part(grid1);
-        HIP_TRY(hipMemcpyAsync(part.data(), ctx->ah_part.p, part.size() * sizeof(ptk::HalvesPartial), hipMemcpyDeviceToHost, d0.stream));
-        if (mean) HIP_TRY(hipMemcpyAsync(mean, ctx->ah_mean.p, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
-        if (err) HIP_TRY(hipMemcpyAsync(err, ctx->ah_err.p, npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
-        if (half_means) HIP_TRY(hipMemcpyAsync(half_means, ctx->ah_half.p, 6 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
-        HIP_TRY(hipStreamSynchronize(d0.stream));
-        if (stats) {
-            pt_halves_stats st;
-            std::memset(&st, 0, sizeof st);
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            st.atrous_ms = ms;
-            st.launches = c.iterations + 2;
-            st.iterations = c.iterations;
-            st.spp_min = spp_min;
-            double sum = 0.0, sum_model = 0.0;
-            for (const ptk::HalvesPartial &p : part) {  // partials in block order
-                sum += p.sum;
-                sum_model += p.sum_model;
-                st.bad_pixels += p.bad;
-            }
-            st.noise = std::sqrt(sum / (double)npix);
-            st.noise_model = std::sqrt(sum_model / (double)npix);
-            *stats = st;
-        }
-        return PT_OK;
-    };
-    const int32_t rc = run();
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-    if (rc == PT_OK && std::getenv("PTCORE_VERBOSE"))
-        std::fprintf(stderr, "ptcore: pt_atrous_halves %d iterations, %.3f ms host wall (gathers included)\n", c.iterations,
-                     std::chrono::duration<double, std::milli>(clk::now() - t0).count());
-    return rc;
+    if (std::getenv("PTCORE_VERBOSE"))
+        std::fprintf(stderr, "ptcore: pt_atrous_halves %d iterations, %.3f ms host wall (gathers included)\n", c.iterations, clock.wall_ms());
+    return PT_OK;
 }
 
 int32_t pt_render_tiles_device(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, const pt_shard *shard,

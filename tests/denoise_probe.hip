@@ -1,21 +1,22 @@
 // denoise_probe.hip -- test-only: the kernels of the a-trous filter, of the pair filter and of the temporal accumulation
 // (csrc/pt_kernels.h) on the gfx950 device, on frames the caller makes up: any size, any sums, any camera.
 //
-// pt_kernels.h is included unchanged and compiled with the library's own flags (tests/denoise_probe_support.py), so what runs here
-// is the code libptcore.so ships.  Each extern "C" entry point uploads its host arrays, launches the product kernels in the order
-// and with the grid expressions of the host function it names (ptcore.hip), copies the results back and returns the first HIP status
-// that was not hipSuccess (0 = fine; a negative value: the arguments were refused before anything was launched).  Every output
-// buffer has its full size and is filled with 0xFF bytes before the launch, so what a kernel did not write reads as a NaN.  The
-// figures and the counts are summed from the kernels' partials in block order, as the host functions sum them.  No inline assembly.
+// pt_kernels.h and pt_filter_launch.h are included unchanged and compiled with the library's own flags
+// (tests/denoise_probe_support.py), so what runs here is the code libptcore.so ships.  Each extern "C" entry point uploads its host
+// arrays, launches the first kernel of the host function it names (ptcore.hip) and then that function's own launch sequence
+// (pt_filter_launch.h), copies the results back and returns the first HIP status that was not hipSuccess (0 = fine; a negative
+// value: the arguments were refused before anything was launched).  Every output buffer has its full size and is filled with 0xFF
+// bytes before the launch, so what a kernel did not write reads as a NaN.  The figures and the counts come from the kernels'
+// partials through the product's own sums.  No inline assembly.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "probe_common.h"
+#include "pt_filter_launch.h"
 #include "pt_kernels.h"
 
 namespace {
@@ -32,18 +33,9 @@ bool counts_ok(const uint32_t *cnt, uint32_t n, size_t np, uint32_t least) {
     return true;
 }
 
-pta::Params params(const double *sig, int32_t T, bool feat) {
-    pta::Params P;
-    std::memset(&P, 0, sizeof P);
-    P.sigma_l = sig[0]; P.sigma_n = sig[1]; P.sigma_z = sig[2]; P.sigma_a = sig[3];
-    P.iterations = T;
-    P.n_on = feat && sig[1] > 0.0;
-    P.z_on = feat && sig[2] > 0.0;
-    P.a_on = feat && sig[3] > 0.0;
-    return P;
-}
+pt_atrous_config config(const double *sig, int32_t T) { return {T, 0, sig[0], sig[1], sig[2], sig[3]}; }
 
-// The buffers pt_atrous and pt_temporal run the filter on (ctx->at_col, at_var, at_guide, at_part, f_rgba).
+// The buffers pt_atrous and pt_temporal run the filter on (ctx->at, f_rgba).
 struct FilterBufs {
     size_t np;
     uint32_t grid1;
@@ -52,40 +44,21 @@ struct FilterBufs {
     Buf<ptk::NoisePartial> part;
     Buf<uint8_t> rgba;
     explicit FilterBufs(size_t npix)
-        : np(npix), grid1((uint32_t)((npix + PT_BLOCK - 1) / PT_BLOCK)), col0(nullptr, 3 * npix), col1(nullptr, 3 * npix), var0(nullptr, npix),
+        : np(npix), grid1(ptl::grid_1d(npix)), col0(nullptr, 3 * npix), col1(nullptr, 3 * npix), var0(nullptr, npix),
           var1(nullptr, npix), guide(nullptr, npix), part(nullptr, 2 * (size_t)grid1), rgba(nullptr, 4 * npix) {}
     hipError_t status() const {
         hipError_t st = hipSuccess;
         for (hipError_t e : {col0.st, col1.st, var0.st, var1.st, guide.st, part.st, rgba.st}) PROBE_TRY(e);
         return st;
     }
-    double *col(int k) { return k ? col1.d : col0.d; }
-    double *var(int k) { return k ? var1.d : var0.d; }
 };
 
-// What follows the kernel that leaves (col0, var0, guide): the figure of that state, then -- with a filter (T >= 0) -- T iterations and
-// the figure of their result, then the finish.  Returns the index of the buffers that hold the result.
-int filter_tail(FilterBufs &B, int32_t W, int32_t H, int32_t T, const pta::Params &P) {
-    const uint32_t npix = (uint32_t)B.np;
-    hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(B.grid1), dim3(PT_BLOCK), 0, 0, B.col(0), B.var(0), B.guide.d, B.part.d, npix);
-    int cur = 0;
-    if (T >= 0) {
-        ptk::AtrousArgs A;
-        std::memset(&A, 0, sizeof A);
-        A.P = P;
-        A.guide = B.guide.d;
-        A.W = W;
-        A.H = H;
-        for (int32_t t = 0; t < T; t++, cur ^= 1) {
-            A.col = B.col(cur); A.var = B.var(cur);
-            A.col_out = B.col(cur ^ 1); A.var_out = B.var(cur ^ 1);
-            A.step = 1 << t;
-            hipLaunchKernelGGL(ptk::atrous_kernel, dim3((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8)), dim3(PT_BLOCK), 0, 0, A);
-        }
-        hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(B.grid1), dim3(PT_BLOCK), 0, 0, B.col(cur), B.var(cur), B.guide.d, B.part.d + B.grid1, npix);
-    }
-    hipLaunchKernelGGL(ptk::atrous_finish_kernel, dim3(B.grid1), dim3(PT_BLOCK), 0, 0, B.col(cur), B.rgba.d, npix);
-    return cur;
+// What follows the kernel that leaves (col0, var0, guide): the product's sequence, without a filter when T < 0.  Returns the index of
+// the buffers that hold the result.
+int filter_tail(FilterBufs &B, int32_t W, int32_t H, int32_t T, const double *sig, bool feat) {
+    double *const col[2] = {B.col0.d, B.col1.d}, *const var[2] = {B.var0.d, B.var1.d};
+    const pta::Params P = ptl::filter_params(config(sig, T), feat);
+    return ptl::filter_sequence(T >= 0 ? &P : nullptr, col, var, B.guide.d, B.part.d, B.rgba.d, W, H, 0);
 }
 
 // mean, var and rgba of the result, and the partials.
@@ -147,25 +120,22 @@ int probe_filter(int32_t W, int32_t H, const double *S, const double *Q, const u
     PA.fn = feat ? dfn.d : nullptr;
     PA.fa = feat ? dfa.d : nullptr;
     PA.fd = feat ? dfd.d : nullptr;
-    PA.col = B.col(0);
-    PA.var = B.var(0);
+    PA.col = B.col0.d;
+    PA.var = B.var0.d;
     PA.guide = B.guide.d;
     PA.npix = (uint32_t)np;
     PA.n = n;
     hipLaunchKernelGGL(ptk::atrous_prep_kernel, dim3(B.grid1), dim3(PT_BLOCK), 0, 0, PA);
-    const int cur = filter_tail(B, W, H, T, params(sig, T, feat));
+    const int cur = filter_tail(B, W, H, T, sig, feat);
     int rc = finish(st);
     if (rc) return rc;
     std::vector<ptk::NoisePartial> part;
     rc = filter_results(B, cur, mean, var, rgba, part);
     if (rc) return rc;
-    double sum[2] = {0.0, 0.0};
-    for (int k = 0; k < 2; k++)
-        for (uint32_t b = 0; b < B.grid1; b++) sum[k] += part[(size_t)k * B.grid1 + b].sum;  // partials in block order
-    *bad = 0;
-    for (uint32_t b = 0; b < B.grid1; b++) *bad += part[b].bad;
-    noise[0] = std::sqrt(sum[0] / (double)np);
-    noise[1] = std::sqrt(sum[1] / (double)np);
+    const ptl::NoiseFigures f = ptl::noise_figures(part.data(), B.grid1, true, np);
+    *bad = f.bad;
+    noise[0] = f.before;
+    noise[1] = f.after;
     return 0;
 }
 
@@ -181,7 +151,7 @@ int probe_pair(int32_t W, int32_t H, const double *SA, const double *QA, const d
     if (!(sig[0] > 0.0) || !(sig[1] >= 0.0) || !(sig[2] >= 0.0) || !(sig[3] >= 0.0)) return -4;
     const size_t np = (size_t)W * (size_t)H;
     if (!counts_ok(cnt, n, np, 4)) return -5;
-    const uint32_t grid1 = (uint32_t)((np + PT_BLOCK - 1) / PT_BLOCK);
+    const uint32_t grid1 = ptl::grid_1d(np);
     Buf<double> dSA(SA, 3 * np), dQA(QA, 3 * np), dSB(SB, 3 * np), dQB(QB, 3 * np);
     Buf<double> dfn(fn, feat ? 3 * np : 0), dfa(fa, feat ? 3 * np : 0), dfd(fd, feat ? 3 * np : 0);
     Buf<uint32_t> dcnt(cnt, cnt ? np : 0);
@@ -193,7 +163,7 @@ int probe_pair(int32_t W, int32_t H, const double *SA, const double *QA, const d
                          derr.st, dhalf.st, dpart.st})
         PROBE_TRY(e);
     if (st != hipSuccess) return (int)st;
-    double *col[2] = {col0.d, col1.d}, *var[2] = {var0.d, var1.d};
+    double *const col[2] = {col0.d, col1.d}, *const var[2] = {var0.d, var1.d};
     ptk::AtrousPairPrepArgs PA;
     std::memset(&PA, 0, sizeof PA);
     PA.sa = dSA.d; PA.qa = dQA.d; PA.sb = dSB.d; PA.qb = dQB.d;
@@ -207,19 +177,7 @@ int probe_pair(int32_t W, int32_t H, const double *SA, const double *QA, const d
     PA.npix = (uint32_t)np;
     PA.n = n;
     hipLaunchKernelGGL(ptk::atrous_pair_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, 0, PA);
-    ptk::AtrousPairArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.P = params(sig, T, feat);
-    A.guide = guide.d;
-    A.W = W;
-    A.H = H;
-    int cur = 0;
-    for (int32_t t = 0; t < T; t++, cur ^= 1) {
-        A.col = col[cur]; A.var = var[cur];
-        A.col_out = col[cur ^ 1]; A.var_out = var[cur ^ 1];
-        A.step = 1 << t;
-        hipLaunchKernelGGL(ptk::atrous_pair_kernel, dim3((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8)), dim3(PT_BLOCK), 0, 0, A);
-    }
+    const int cur = ptl::pair_iterations(ptl::filter_params(config(sig, T), feat), col, var, guide.d, W, H, 0);
     ptk::HalvesCombineArgs CA;
     std::memset(&CA, 0, sizeof CA);
     CA.col = col[cur]; CA.var = var[cur]; CA.guide = guide.d;
@@ -237,15 +195,10 @@ int probe_pair(int32_t W, int32_t H, const double *SA, const double *QA, const d
     if (!rc) rc = (int)derr.download(err);
     if (!rc) rc = (int)dhalf.download(half_means);
     if (rc) return rc;
-    double sum = 0.0, sum_model = 0.0;
-    *bad = 0;
-    for (const ptk::HalvesPartial &p : part) {  // partials in block order
-        sum += p.sum;
-        sum_model += p.sum_model;
-        *bad += p.bad;
-    }
-    noise[0] = std::sqrt(sum / (double)np);
-    noise[1] = std::sqrt(sum_model / (double)np);
+    const ptl::HalvesFigures f = ptl::halves_figures(part.data(), grid1, np);
+    *bad = f.bad;
+    noise[0] = f.noise;
+    noise[1] = f.noise_model;
     return 0;
 }
 
@@ -298,7 +251,7 @@ int probe_temporal_frame(void *sp, int32_t W, int32_t H, const double *S, const 
     State &s = *static_cast<State *>(sp);
     const size_t np = (size_t)W * (size_t)H;
     if (!counts_ok(cnt, n, np, 2)) return -5;
-    const dim3 grid2((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8));
+    const dim3 grid2 = ptl::grid_2d(W, H);
     const size_t nblk = (size_t)grid2.x * grid2.y;
     const bool have = s.valid && s.W == W && s.H == H;  // another size: the history is dropped (when the call succeeds)
     hipError_t st = hipSuccess;
@@ -342,13 +295,13 @@ int probe_temporal_frame(void *sp, int32_t W, int32_t H, const double *S, const 
     TA.fd = dfd.d;
     TA.hist = s.hist[s.cur];
     TA.hist_out = s.hist[next];
-    TA.col = B.col(0);
-    TA.var = B.var(0);
+    TA.col = B.col0.d;
+    TA.var = B.var0.d;
     TA.guide = B.guide.d;
     TA.partial = tpart.d;
     TA.n = n;
     hipLaunchKernelGGL(ptk::temporal_kernel, grid2, dim3(PT_BLOCK), 0, 0, TA);
-    const int cur = filter_tail(B, W, H, T, params(sig, T, true));
+    const int cur = filter_tail(B, W, H, T, sig, true);
     int rc = finish(st);
     if (rc) return rc;  // the stored history is untouched: the kernel wrote the other set
     std::vector<ptk::NoisePartial> part;
@@ -361,22 +314,15 @@ int probe_temporal_frame(void *sp, int32_t W, int32_t H, const double *S, const 
     s.W = W;
     s.H = H;
     s.cam = TA.V.cam;
-    double sum[3] = {0.0, 0.0, 0.0};
-    counts[0] = counts[1] = counts[2] = counts[3] = 0;
-    for (const ptk::TemporalPartial &p : tp) {  // partials in block order
-        sum[0] += p.sum_before;
-        counts[0] += p.reprojected;
-        counts[1] += p.disoccluded;
-        counts[3] += p.len_sum;
-    }
-    for (uint32_t b = 0; b < B.grid1; b++) {
-        sum[1] += part[b].sum;
-        counts[2] += part[b].bad;
-        if (T >= 0) sum[2] += part[(size_t)B.grid1 + b].sum;
-    }
-    noise[0] = std::sqrt(sum[0] / (double)np);
-    noise[1] = std::sqrt(sum[1] / (double)np);
-    noise[2] = T >= 0 ? std::sqrt(sum[2] / (double)np) : noise[1];
+    const ptl::TemporalFigures tf = ptl::temporal_figures(tp.data(), nblk, np);
+    const ptl::NoiseFigures nf = ptl::noise_figures(part.data(), B.grid1, T >= 0, np);
+    counts[0] = tf.reprojected;
+    counts[1] = tf.disoccluded;
+    counts[2] = nf.bad;
+    counts[3] = tf.len_sum;
+    noise[0] = tf.noise_before;
+    noise[1] = nf.before;
+    noise[2] = nf.after;
     return 0;
 }
 

@@ -1,12 +1,13 @@
 // temporal_clip_probe.hip -- test-only: temporal_kernel with the history clip (C.clip_gamma, step 7a of csrc/pt_temporal.h) and the
 // a-trous kernels behind it on the gfx950 device, on frames the caller makes up.
 //
-// pt_kernels.h is included unchanged and compiled with the library's own flags (tests/temporal_clip_support.py), so what runs here
-// is the code libptcore.so ships.  clip_probe_frame uploads its host arrays, launches the product kernels in the order and with the
-// grid expressions of pt_temporal (ptcore.hip), copies the results back and returns the first HIP status that was not hipSuccess
-// (0 = fine; a negative value: the arguments were refused before anything was launched).  Every output buffer has its full size and
-// is filled with 0xFF bytes before the launch, so what a kernel did not write reads as a NaN.  The figures and the counts are summed
-// from the kernels' partials in block order, as pt_temporal sums them.  No inline assembly.
+// pt_kernels.h and pt_filter_launch.h are included unchanged and compiled with the library's own flags
+// (tests/temporal_clip_support.py), so what runs here is the code libptcore.so ships.  clip_probe_frame uploads its host arrays,
+// launches temporal_kernel as pt_temporal does (ptcore.hip) and then pt_temporal's own launch sequence (pt_filter_launch.h), copies
+// the results back and returns the first HIP status that was not hipSuccess (0 = fine; a negative value: the arguments were refused
+// before anything was launched).  Every output buffer has its full size and is filled with 0xFF bytes before the launch, so what a
+// kernel did not write reads as a NaN.  The figures and the counts come from the kernels' partials through the product's own sums.
+// No inline assembly.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "probe_common.h"
+#include "pt_filter_launch.h"
 #include "pt_kernels.h"
 
 namespace {
@@ -97,8 +99,8 @@ int clip_probe_frame(void *hp, int32_t W, int32_t H, const double *S, const doub
     const size_t np = (size_t)W * (size_t)H;
     for (size_t i = 0; i < np; i++)
         if ((cnt ? cnt[i] : n) < 2) return -5;
-    const uint32_t grid1 = (uint32_t)((np + PT_BLOCK - 1) / PT_BLOCK);
-    const dim3 grid2((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8));
+    const uint32_t grid1 = ptl::grid_1d(np);
+    const dim3 grid2 = ptl::grid_2d(W, H);
     const size_t nblk = (size_t)grid2.x * grid2.y;
     const bool have = h.valid && h.W == W && h.H == H;  // another size: the history is dropped (when the call succeeds)
     hipError_t st = hipSuccess;
@@ -125,7 +127,7 @@ int clip_probe_frame(void *hp, int32_t W, int32_t H, const double *S, const doub
     for (hipError_t e : {dS.st, dQ.st, dfn.st, dfa.st, dfd.st, dcnt.st, tpart.st, col0.st, col1.st, var0.st, var1.st, guide.st, part.st, drgba.st})
         PROBE_TRY(e);
     if (st != hipSuccess) return (int)st;
-    double *col[2] = {col0.d, col1.d}, *vr[2] = {var0.d, var1.d};
+    double *const col[2] = {col0.d, col1.d}, *const vr[2] = {var0.d, var1.d};
     ptk::TemporalArgs TA;
     std::memset(&TA, 0, sizeof TA);
     TA.C.alpha = tcfg[0]; TA.C.tol_z = tcfg[1]; TA.C.n_min = tcfg[2]; TA.C.tol_a = tcfg[3];
@@ -152,28 +154,8 @@ int clip_probe_frame(void *hp, int32_t W, int32_t H, const double *S, const doub
     TA.partial = tpart.d;
     TA.n = n;
     hipLaunchKernelGGL(ptk::temporal_kernel, grid2, dim3(PT_BLOCK), 0, 0, TA);
-    hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, 0, col[0], vr[0], guide.d, part.d, (uint32_t)np);
-    int cur = 0;
-    if (T >= 0) {
-        ptk::AtrousArgs A;
-        std::memset(&A, 0, sizeof A);
-        A.P.sigma_l = sig[0]; A.P.sigma_n = sig[1]; A.P.sigma_z = sig[2]; A.P.sigma_a = sig[3];
-        A.P.iterations = T;
-        A.P.n_on = sig[1] > 0.0;
-        A.P.z_on = sig[2] > 0.0;
-        A.P.a_on = sig[3] > 0.0;
-        A.guide = guide.d;
-        A.W = W;
-        A.H = H;
-        for (int32_t t = 0; t < T; t++, cur ^= 1) {
-            A.col = col[cur]; A.var = vr[cur];
-            A.col_out = col[cur ^ 1]; A.var_out = vr[cur ^ 1];
-            A.step = 1 << t;
-            hipLaunchKernelGGL(ptk::atrous_kernel, grid2, dim3(PT_BLOCK), 0, 0, A);
-        }
-        hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid1), dim3(PT_BLOCK), 0, 0, col[cur], vr[cur], guide.d, part.d + grid1, (uint32_t)np);
-    }
-    hipLaunchKernelGGL(ptk::atrous_finish_kernel, dim3(grid1), dim3(PT_BLOCK), 0, 0, col[cur], drgba.d, (uint32_t)np);
+    const pta::Params P = ptl::filter_params({T, 0, sig[0], sig[1], sig[2], sig[3]}, true);
+    const int cur = ptl::filter_sequence(T >= 0 ? &P : nullptr, col, vr, guide.d, part.d, drgba.d, W, H, 0);
     int rc = finish(st);
     if (rc) return rc;  // the stored history is untouched: the kernel wrote the other set
     std::vector<ptk::NoisePartial> hp_part(2 * (size_t)grid1);
@@ -189,23 +171,16 @@ int clip_probe_frame(void *hp, int32_t W, int32_t H, const double *S, const doub
     h.W = W;
     h.H = H;
     h.cam = TA.V.cam;
-    double sum[3] = {0.0, 0.0, 0.0};
-    for (int k = 0; k < 5; k++) counts[k] = 0;
-    for (const ptk::TemporalPartial &p : tp) {  // partials in block order
-        sum[0] += p.sum_before;
-        counts[0] += p.reprojected;
-        counts[1] += p.disoccluded;
-        counts[3] += p.len_sum;
-        counts[4] += p.clipped;
-    }
-    for (uint32_t b = 0; b < grid1; b++) {
-        sum[1] += hp_part[b].sum;
-        counts[2] += hp_part[b].bad;
-        if (T >= 0) sum[2] += hp_part[(size_t)grid1 + b].sum;
-    }
-    noise[0] = std::sqrt(sum[0] / (double)np);
-    noise[1] = std::sqrt(sum[1] / (double)np);
-    noise[2] = T >= 0 ? std::sqrt(sum[2] / (double)np) : noise[1];
+    const ptl::TemporalFigures tf = ptl::temporal_figures(tp.data(), nblk, np);
+    const ptl::NoiseFigures nf = ptl::noise_figures(hp_part.data(), grid1, T >= 0, np);
+    counts[0] = tf.reprojected;
+    counts[1] = tf.disoccluded;
+    counts[2] = nf.bad;
+    counts[3] = tf.len_sum;
+    counts[4] = tf.clipped;
+    noise[0] = tf.noise_before;
+    noise[1] = nf.before;
+    noise[2] = nf.after;
     return 0;
 }
 

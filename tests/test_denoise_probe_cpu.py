@@ -6,6 +6,7 @@ pixel where the blocks and waves meet, that the temporal sequences reach every r
 edge, the clamp of len' and both sides of alpha > 1 / (L + 1) -- are asserted on the restatement's results alone."""
 from __future__ import annotations
 
+import os
 import re
 import subprocess
 
@@ -17,6 +18,7 @@ import atrous_support as at
 import denoise_probe_support as dp
 import halves_support as hv
 import temporal_support as ts
+from fog_support import CSRC
 
 SHAPE_IDS = ["%dx%d" % s for s in dp.SHAPES]
 
@@ -37,20 +39,38 @@ def test_probe_compiles_for_gfx950_with_the_library_flags():
 
 
 def test_probe_source_launches_the_product_kernels_and_has_no_inline_assembly():
+    def code_of(path):
+        with open(path) as f:
+            return re.sub(r"//.*", "", f.read())
+
     with open(dp.SOURCE) as f:
         src = f.read()
-    code = re.sub(r"//.*", "", src)
+    code = code_of(dp.SOURCE)
     assert "asm" not in code and "__global__" not in code
     assert '#include "pt_kernels.h"' in src and '#include "probe_common.h"' in src
+    # The probe runs the product's launch sequence itself: the header ptcore.hip includes holds the filter's launches, its iteration
+    # loop and the two grids of a frame, and neither the probe nor ptcore.hip has a copy of any of them.
+    assert '#include "pt_filter_launch.h"' in src
+    header = code_of(os.path.join(CSRC, "pt_filter_launch.h"))
+    core = code_of(os.path.join(CSRC, "ptcore.hip"))
+    assert '#include "pt_filter_launch.h"' in core and "asm" not in header and "__global__" not in header
+    grids = ("(npix + PT_BLOCK - 1) / PT_BLOCK", "((W + 31) / 32), (unsigned)((H + 7) / 8)")
+    for text in grids + ("A.step = 1 << t",):
+        assert header.count(text) == 1, text
+    for where, text in (("probe", code), ("ptcore.hip", core)):
+        for kernel in ("atrous_kernel", "atrous_pair_kernel", "atrous_noise_kernel", "atrous_finish_kernel"):
+            assert not re.search(r"\b%s\b" % kernel, text), (where, kernel)        # not launched, not even named
+        for expr in grids + ("(np + PT_BLOCK - 1) / PT_BLOCK", "+ 7) / 8", "1 << t"):
+            assert expr not in text, (where, expr)
     for name in dp.KERNELS:
-        assert "ptk::" + name in code, name
+        assert "ptk::" + name in code or "ptk::" + name in header, name
     for name in ("ptk::AtrousPrepArgs", "ptk::AtrousArgs", "ptk::AtrousPairPrepArgs", "ptk::AtrousPairArgs", "ptk::HalvesCombineArgs",
                  "ptk::TemporalArgs", "ptk::NoisePartial", "ptk::HalvesPartial", "ptk::TemporalPartial"):
-        assert name in code, name
-    # the product's own grid expressions (pt_atrous, pt_atrous_halves, pt_temporal in ptcore.hip)
-    assert code.count("((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8))") == 3
-    assert "(npix + PT_BLOCK - 1) / PT_BLOCK" in code and "(np + PT_BLOCK - 1) / PT_BLOCK" in code
-    assert "1.0 / (double)(W - 1)" in code and "A.step = 1 << t" in code
+        assert name in code or name in header, name
+    for name in ("ptl::filter_sequence", "ptl::pair_iterations", "ptl::filter_params", "ptl::noise_figures", "ptl::halves_figures",
+                 "ptl::temporal_figures", "ptl::grid_1d", "ptl::grid_2d"):
+        assert name in code and name in core, name
+    assert "1.0 / (double)(W - 1)" in code
 
 
 def test_the_shared_header_leaves_the_adaptive_probe_compiling():
