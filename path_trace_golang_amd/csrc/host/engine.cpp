@@ -11,7 +11,9 @@
 #include <fstream>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
+#include <utility>
 
 #include "../../../include/ptcore.h"
 #include "png.hpp"
@@ -48,50 +50,51 @@ Backend GetBackend() { return g_backend; }
 // ---------------------------------------------------------------- libptcore binding (dlopen)
 namespace {
 
+// One row per entry point of include/ptcore.h that the host layer binds: the Core member carries the entry point's own name.
+// REQUIRED: part of ABI 4 from the start, load_core fails without it.  OPTIONAL: added within ABI 4, null in an older build.
+#define PT_ENTRY_POINTS(REQUIRED, OPTIONAL)                                                                                      \
+    REQUIRED(pt_abi_version) REQUIRED(pt_last_error) REQUIRED(pt_create) REQUIRED(pt_destroy) REQUIRED(pt_render)               \
+    REQUIRED(pt_begin) REQUIRED(pt_step) REQUIRED(pt_read) REQUIRED(pt_end) REQUIRED(pt_set_fog)                                 \
+    OPTIONAL(pt_set_shading) OPTIONAL(pt_set_moments) OPTIONAL(pt_noise_estimate) OPTIONAL(pt_set_adaptive)                      \
+    OPTIONAL(pt_adaptive_state) OPTIONAL(pt_set_features) OPTIONAL(pt_atrous) OPTIONAL(pt_set_halves) OPTIONAL(pt_atrous_halves) \
+    OPTIONAL(pt_temporal) OPTIONAL(pt_temporal_reset) OPTIONAL(pt_temporal_set_clip) OPTIONAL(pt_temporal_clip_stats)
+
 struct Core {
     void *handle = nullptr;
-    decltype(&pt_abi_version) abi_version = nullptr;
-    decltype(&pt_last_error) last_error = nullptr;
-    decltype(&pt_create) create = nullptr;
-    decltype(&pt_destroy) destroy = nullptr;
-    decltype(&pt_render) render = nullptr;
-    decltype(&pt_begin) begin = nullptr;
-    decltype(&pt_step) step = nullptr;
-    decltype(&pt_read) read = nullptr;
-    decltype(&pt_end) end = nullptr;
-    decltype(&pt_set_fog) set_fog = nullptr;
-    decltype(&pt_set_shading) set_shading = nullptr;  // optional (additive to ABI 4): null in an older build
-    decltype(&pt_set_moments) set_moments = nullptr;  // optional, as set_shading (the noise target needs all three)
-    decltype(&pt_noise_estimate) noise_estimate = nullptr;
-    decltype(&pt_set_adaptive) set_adaptive = nullptr;  // optional, as set_shading (adaptive sampling needs both)
-    int32_t (*adaptive_state)(pt_ctx *, struct pt_adaptive_state *) = nullptr;
-    decltype(&pt_set_features) set_features = nullptr;  // optional, as set_shading (the a-trous filter needs pt_atrous and moments)
-    decltype(&pt_atrous) atrous = nullptr;
-    decltype(&pt_set_halves) set_halves = nullptr;  // optional, as set_shading (the filtered noise target needs both)
-    decltype(&pt_atrous_halves) atrous_halves = nullptr;
-    decltype(&pt_temporal) temporal = nullptr;  // optional, as set_shading
-    decltype(&pt_temporal_reset) temporal_reset = nullptr;
-    decltype(&pt_temporal_set_clip) temporal_set_clip = nullptr;  // optional, as set_shading
-    int32_t (*temporal_clip_stats)(pt_ctx *, struct pt_temporal_clip_stats *) = nullptr;
+#define MEMBER(fn) decltype(&::fn) fn = nullptr;
+    PT_ENTRY_POINTS(MEMBER, MEMBER)
+#undef MEMBER
     std::string error;  // sticky load error, like the reference's cached GL init failure (gpu.go:279-286)
+};
+
+// What a frame setting needs from the library beyond the required entry points, and what Render answers when it is not there.
+enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE };
+const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
+    {[](const Core &c) { return c.pt_set_shading != nullptr; }, "GL shading: libptcore.so lacks pt_set_shading"},
+    {[](const Core &c) { return c.pt_set_moments && c.pt_noise_estimate; }, "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate"},
+    {[](const Core &c) { return c.pt_temporal != nullptr; }, "temporal accumulation: libptcore.so lacks pt_temporal"},
+    {[](const Core &c) { return c.pt_temporal_set_clip && c.pt_temporal_clip_stats; }, "temporal clip: libptcore.so lacks pt_temporal_set_clip"},
+    {[](const Core &c) { return c.pt_atrous && c.pt_set_moments; }, "a-trous filter: libptcore.so lacks pt_atrous / pt_set_moments"},
+    {[](const Core &c) { return c.pt_set_halves && c.pt_atrous_halves; }, "filtered noise target: libptcore.so lacks pt_set_halves / pt_atrous_halves"},
+    {[](const Core &c) { return c.pt_set_features != nullptr; }, "features: libptcore.so lacks pt_set_features"},
+    {[](const Core &c) { return c.pt_set_adaptive && c.pt_adaptive_state; }, "adaptive sampling: libptcore.so lacks pt_set_adaptive / pt_adaptive_state"},
+};
+
+// What the Set* calls said; an empty field leaves the matter to the environment (the *FromEnv rules).
+struct NoiseRule { double target; int step; };
+struct Switch { bool on; int n; };  // adaptive + min_spp, a-trous + iterations
+struct Settings {
+    std::optional<bool> fog, temporal;
+    std::optional<int> shading, features;
+    std::optional<NoiseRule> noise;
+    std::optional<Switch> adaptive, atrous;
+    std::optional<double> filtered_noise, temporal_clip;
 };
 
 Core g_core;
 pt_ctx *g_ctx = nullptr;
 std::vector<int> g_devices;
-int g_fog = -1;  // -1: not set yet, PATHTRACER_GPU_FOG decides
-int g_shading = -1;  // -1: not set yet, PATHTRACER_GPU_SHADING decides; else PT_SHADING_*
-bool g_noise_set = false;  // false: PATHTRACER_GPU_NOISE / _STEP decide
-double g_noise_target = 0;
-int g_noise_step = 16;
-int g_adaptive = -1;  // -1: not set yet, PATHTRACER_GPU_ADAPTIVE / _MIN_SPP decide
-int g_adaptive_min_spp = 0;
-int g_atrous = -1;  // -1: not set yet, PATHTRACER_GPU_ATROUS / _ITERS decide
-int g_atrous_iters = 5;
-double g_filtered_noise = -1;  // < 0: not set yet, PATHTRACER_GPU_FILTERED_NOISE decides
-int g_temporal = -1;  // -1: not set yet, PATHTRACER_GPU_TEMPORAL decides
-double g_temporal_clip = -1;  // < 0: not set yet, PATHTRACER_GPU_TEMPORAL_CLIP decides
-int g_features = -1;  // -1: not set yet, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows, else 0)
+Settings g_set;
 std::mutex g_mu;  // requests are serialised, like the reference's single GL worker (gpu.go:2534-2546)
 
 std::string self_dir() {
@@ -102,13 +105,6 @@ std::string self_dir() {
         if (k != std::string::npos) return p.substr(0, k);
     }
     return ".";
-}
-
-template <typename F>
-bool sym(void *h, const char *name, F &out, std::string &err) {
-    out = reinterpret_cast<F>(dlsym(h, name));
-    if (!out) { err = std::string("libptcore.so lacks symbol ") + name; return false; }
-    return true;
 }
 
 bool load_core() {
@@ -126,38 +122,55 @@ bool load_core() {
         errs += std::string(dlerror() ? dlerror() : "dlopen failed") + "; ";
     }
     if (!h) { g_core.error = "cannot load libptcore.so (" + errs + ")"; return false; }
-    std::string err;
     Core c;
     c.handle = h;
-    if (!(sym(h, "pt_abi_version", c.abi_version, err) && sym(h, "pt_last_error", c.last_error, err) &&
-          sym(h, "pt_create", c.create, err) && sym(h, "pt_destroy", c.destroy, err) && sym(h, "pt_render", c.render, err) &&
-          sym(h, "pt_begin", c.begin, err) && sym(h, "pt_step", c.step, err) && sym(h, "pt_read", c.read, err) &&
-          sym(h, "pt_end", c.end, err) && sym(h, "pt_set_fog", c.set_fog, err))) {
+    std::string err;
+#define OPTIONAL(fn) c.fn = reinterpret_cast<decltype(c.fn)>(dlsym(h, #fn));
+#define REQUIRED(fn) OPTIONAL(fn) if (!c.fn && err.empty()) err = "libptcore.so lacks symbol " #fn;
+    PT_ENTRY_POINTS(REQUIRED, OPTIONAL)
+#undef REQUIRED
+#undef OPTIONAL
+    if (err.empty() && c.pt_abi_version() != PT_ABI_VERSION) err = "libptcore.so ABI version mismatch";
+    if (!err.empty()) {
         g_core.error = err;
-        dlclose(h);
-        return false;
-    }
-    c.set_shading = reinterpret_cast<decltype(c.set_shading)>(dlsym(h, "pt_set_shading"));
-    c.set_moments = reinterpret_cast<decltype(c.set_moments)>(dlsym(h, "pt_set_moments"));
-    c.noise_estimate = reinterpret_cast<decltype(c.noise_estimate)>(dlsym(h, "pt_noise_estimate"));
-    c.set_adaptive = reinterpret_cast<decltype(c.set_adaptive)>(dlsym(h, "pt_set_adaptive"));
-    c.adaptive_state = reinterpret_cast<decltype(c.adaptive_state)>(dlsym(h, "pt_adaptive_state"));
-    c.set_features = reinterpret_cast<decltype(c.set_features)>(dlsym(h, "pt_set_features"));
-    c.atrous = reinterpret_cast<decltype(c.atrous)>(dlsym(h, "pt_atrous"));
-    c.set_halves = reinterpret_cast<decltype(c.set_halves)>(dlsym(h, "pt_set_halves"));
-    c.atrous_halves = reinterpret_cast<decltype(c.atrous_halves)>(dlsym(h, "pt_atrous_halves"));
-    c.temporal = reinterpret_cast<decltype(c.temporal)>(dlsym(h, "pt_temporal"));
-    c.temporal_reset = reinterpret_cast<decltype(c.temporal_reset)>(dlsym(h, "pt_temporal_reset"));
-    c.temporal_set_clip = reinterpret_cast<decltype(c.temporal_set_clip)>(dlsym(h, "pt_temporal_set_clip"));
-    c.temporal_clip_stats = reinterpret_cast<decltype(c.temporal_clip_stats)>(dlsym(h, "pt_temporal_clip_stats"));
-    if (c.abi_version() != PT_ABI_VERSION) {
-        g_core.error = "libptcore.so ABI version mismatch";
         dlclose(h);
         return false;
     }
     g_core = c;
     return true;
 }
+
+// The text of a failed call: "pt_x: " + what the library says about it; "" when the call succeeded.
+std::string call(const char *name, int32_t rc) { return rc == PT_OK ? std::string() : std::string(name) + ": " + g_core.pt_last_error(); }
+#define PT_CALL(fn, ...) call(#fn, g_core.fn(__VA_ARGS__))
+
+// ---- the three environment parsers every *FromEnv goes through
+std::string env_lower(const char *name) {
+    const char *e = std::getenv(name);
+    std::string v(e ? e : "");
+    for (char &ch : v) ch = (char)std::tolower((unsigned char)ch);
+    return v;
+}
+bool env_switch(const char *name) {  // 1 / true / on / yes in any case, nothing else
+    const std::string v = env_lower(name);
+    return v == "1" || v == "true" || v == "on" || v == "yes";
+}
+int env_int(const char *name, long lo, long hi, int fallback) {  // the whole string a decimal integer in [lo, hi]
+    const char *e = std::getenv(name);
+    if (!e) return fallback;
+    char *end = nullptr;
+    const long v = std::strtol(e, &end, 10);
+    return end != e && *end == 0 && v >= lo && v <= hi ? (int)v : fallback;
+}
+double env_double(const char *name, bool (*ok)(double), double fallback) {  // the whole string a number that `ok` accepts
+    const char *e = std::getenv(name);
+    if (!e) return fallback;
+    char *end = nullptr;
+    const double v = std::strtod(e, &end);
+    return end != e && *end == 0 && ok(v) ? v : fallback;
+}
+bool positive_finite(double v) { return v > 0 && v <= 1.7976931348623157e308; }
+bool finite_not_negative(double v) { return std::isfinite(v) && v >= 0; }
 
 struct Flat {
     std::vector<pt_material> materials;
@@ -268,245 +281,203 @@ namespace hip {
 
 void SetDevices(const std::vector<int> &ordinals) {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx && g_core.handle) { g_core.destroy(g_ctx); g_ctx = nullptr; }
+    if (g_ctx && g_core.handle) { g_core.pt_destroy(g_ctx); g_ctx = nullptr; }
     g_devices = ordinals;
 }
 
-int ShadingFromEnv() {
-    const char *e = std::getenv("PATHTRACER_GPU_SHADING");
-    if (!e) return PT_SHADING_CPU;
-    std::string v(e);
-    for (char &ch : v) ch = (char)std::tolower((unsigned char)ch);
-    return v == "gl" ? PT_SHADING_GL : PT_SHADING_CPU;
+bool FogFromEnv() { return env_switch("PATHTRACER_GPU_FOG"); }
+int ShadingFromEnv() { return env_lower("PATHTRACER_GPU_SHADING") == "gl" ? PT_SHADING_GL : PT_SHADING_CPU; }
+void NoiseFromEnv(double &target, int &step) {
+    target = env_double("PATHTRACER_GPU_NOISE", positive_finite, 0);
+    step = env_int("PATHTRACER_GPU_NOISE_STEP", 1, 0x7fffffffL, 16);
 }
+void AdaptiveFromEnv(bool &on, int &min_spp) {
+    on = env_switch("PATHTRACER_GPU_ADAPTIVE");
+    min_spp = env_int("PATHTRACER_GPU_ADAPTIVE_MIN_SPP", 0, 0x7fffffffL, 0);
+}
+void AtrousFromEnv(bool &on, int &iterations) {
+    on = env_switch("PATHTRACER_GPU_ATROUS");
+    iterations = env_int("PATHTRACER_GPU_ATROUS_ITERS", 0, 6, 5);
+}
+int FeaturesFromEnv() { return env_int("PATHTRACER_GPU_FEATURES", 0, 0x7fffffffL, -1); }
+double FilteredNoiseFromEnv() { return env_double("PATHTRACER_GPU_FILTERED_NOISE", positive_finite, 0); }
+bool TemporalFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL"); }
+double TemporalClipFromEnv() { return env_double("PATHTRACER_GPU_TEMPORAL_CLIP", finite_not_negative, 0); }
+
+namespace {
+
+// What one frame does, from what was set and, where nothing was, from the environment.  Computed once per Render, under the lock.
+struct FramePlan {
+    bool fog;             // the scene has a fog block and it was asked for
+    int shading;          // PT_SHADING_*
+    NoiseRule noise;      // target > 0: render until the frame noise is there
+    Switch adaptive;      // on only with a noise target: without one there is nothing to adapt to
+    Switch atrous;        // on also under temporal accumulation, which brings the filter with it
+    bool temporal;
+    double clip;          // > 0 only under temporal accumulation
+    double filtered;      // > 0 only under the filter
+    int features;
+    bool moments, halves;
+};
+
+NoiseRule noise_rule(const Settings &s) {
+    NoiseRule r;
+    NoiseFromEnv(r.target, r.step);
+    return s.noise.value_or(r);
+}
+Switch adaptive_switch(const Settings &s) {
+    Switch r;
+    AdaptiveFromEnv(r.on, r.n);
+    return s.adaptive.value_or(r);
+}
+Switch atrous_switch(const Settings &s) {
+    Switch r;
+    AtrousFromEnv(r.on, r.n);
+    return s.atrous.value_or(r);
+}
+
+FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects, const Settings &s) {
+    FramePlan p;
+    p.fog = s.fog.value_or(FogFromEnv()) && sc.FogPtr;
+    p.shading = s.shading.value_or(ShadingFromEnv());
+    p.noise = noise_rule(s);
+    p.adaptive = adaptive_switch(s);
+    p.adaptive.on = p.adaptive.on && p.noise.target > 0;
+    p.atrous = atrous_switch(s);
+    p.temporal = s.temporal.value_or(TemporalFromEnv());
+    p.clip = p.temporal ? s.temporal_clip.value_or(TemporalClipFromEnv()) : 0;
+    p.atrous.on = p.atrous.on || p.temporal;
+    p.filtered = p.atrous.on ? s.filtered_noise.value_or(FilteredNoiseFromEnv()) : 0;
+    p.features = s.features.value_or(FeaturesFromEnv());
+    if (p.features < 0 && p.temporal) p.features = 4;  // (pt_temporal needs them: where the frame refuses features, pt_begin says so)
+    if (p.features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path), else off
+        p.features = 0;
+        if (p.atrous.on && p.shading != PT_SHADING_GL) {
+            size_t spheres = 0, boxes = 0;
+            for (const pt_object &o : objects) {
+                spheres += o.type == PT_OBJ_SPHERE || o.type == PT_OBJ_SPHERE_LIGHT;
+                boxes += o.type == PT_OBJ_BOX;
+            }
+            const char *scan = std::getenv("PTCORE_SCAN");
+            const bool forced_bvh = scan && (!std::strcmp(scan, "bvh") || !std::strcmp(scan, "verify_bvh"));
+            if (spheres <= 128 && boxes <= 128 && !forced_bvh) p.features = 4;
+        }
+    }
+    p.moments = p.noise.target > 0 || p.atrous.on;
+    p.halves = p.filtered > 0;
+    return p;
+}
+
+// How the stepping loop of a frame advances and what ends it before the cap.
+struct StopRule {
+    enum Check { NONE, FRAME_NOISE, FILTERED_NOISE } check;
+    int32_t step;          // samples per pt_step
+    bool clip_step;        // clipped to what is left of the cap (the noise rules), or not (the preview cadence)
+    bool ends_when_stalled;  // adaptive: every block has stopped once a step adds nothing
+    int32_t measure_from, stop_from;  // samples done from which the check runs / from which it may end the frame
+    double target;
+};
+
+}  // namespace
 
 void SetShading(int model) {
     std::lock_guard<std::mutex> lk(g_mu);
-    g_shading = model == PT_SHADING_GL ? PT_SHADING_GL : PT_SHADING_CPU;
+    g_set.shading = model == PT_SHADING_GL ? PT_SHADING_GL : PT_SHADING_CPU;
 }
-
 int GetShading() {
     std::lock_guard<std::mutex> lk(g_mu);
-    return g_shading < 0 ? ShadingFromEnv() : g_shading;
+    return g_set.shading.value_or(ShadingFromEnv());
 }
-
-bool FogFromEnv() {
-    const char *e = std::getenv("PATHTRACER_GPU_FOG");
-    if (!e) return false;
-    std::string v(e);
-    for (char &ch : v) ch = (char)std::tolower((unsigned char)ch);
-    return v == "1" || v == "true" || v == "on" || v == "yes";
-}
-
 void SetFog(bool on) {
     std::lock_guard<std::mutex> lk(g_mu);
-    g_fog = on ? 1 : 0;
+    g_set.fog = on;
 }
-
 bool GetFog() {
     std::lock_guard<std::mutex> lk(g_mu);
-    return g_fog < 0 ? FogFromEnv() : g_fog == 1;
+    return g_set.fog.value_or(FogFromEnv());
 }
-
-void NoiseFromEnv(double &target, int &step) {
-    target = 0;
-    step = 16;
-    if (const char *e = std::getenv("PATHTRACER_GPU_NOISE")) {
-        char *end = nullptr;
-        const double v = std::strtod(e, &end);
-        if (end != e && *end == 0 && v > 0 && v <= 1.7976931348623157e308) target = v;
-    }
-    if (const char *e = std::getenv("PATHTRACER_GPU_NOISE_STEP")) {
-        char *end = nullptr;
-        const long v = std::strtol(e, &end, 10);
-        if (end != e && *end == 0 && v >= 1 && v <= 0x7fffffffL) step = (int)v;
-    }
-}
-
 void SetNoiseTarget(double target, int step) {
     std::lock_guard<std::mutex> lk(g_mu);
-    g_noise_set = true;
-    g_noise_target = target > 0 ? target : 0;
-    g_noise_step = step >= 1 ? step : 16;
+    g_set.noise = NoiseRule{target > 0 ? target : 0, step >= 1 ? step : 16};
 }
-
 double GetNoiseTarget() {
     std::lock_guard<std::mutex> lk(g_mu);
-    double t;
-    int s;
-    NoiseFromEnv(t, s);
-    return g_noise_set ? g_noise_target : t;
+    return noise_rule(g_set).target;
 }
-
 int GetNoiseStep() {
     std::lock_guard<std::mutex> lk(g_mu);
-    double t;
-    int s;
-    NoiseFromEnv(t, s);
-    return g_noise_set ? g_noise_step : s;
+    return noise_rule(g_set).step;
 }
-
-void AdaptiveFromEnv(bool &on, int &min_spp) {
-    on = false;
-    min_spp = 0;
-    if (const char *e = std::getenv("PATHTRACER_GPU_ADAPTIVE")) {
-        std::string v(e);
-        for (char &ch : v) ch = (char)std::tolower((unsigned char)ch);
-        on = v == "1" || v == "true" || v == "on" || v == "yes";
-    }
-    if (const char *e = std::getenv("PATHTRACER_GPU_ADAPTIVE_MIN_SPP")) {
-        char *end = nullptr;
-        const long v = std::strtol(e, &end, 10);
-        if (end != e && *end == 0 && v >= 0 && v <= 0x7fffffffL) min_spp = (int)v;
-    }
-}
-
 void SetAdaptive(bool on, int min_spp) {
     std::lock_guard<std::mutex> lk(g_mu);
-    g_adaptive = on ? 1 : 0;
-    g_adaptive_min_spp = min_spp >= 0 ? min_spp : 0;
+    g_set.adaptive = Switch{on, min_spp >= 0 ? min_spp : 0};
 }
-
 bool GetAdaptive() {
     std::lock_guard<std::mutex> lk(g_mu);
-    bool on;
-    int m;
-    AdaptiveFromEnv(on, m);
-    return g_adaptive < 0 ? on : g_adaptive == 1;
+    return adaptive_switch(g_set).on;
 }
-
 int GetAdaptiveMinSpp() {
     std::lock_guard<std::mutex> lk(g_mu);
-    bool on;
-    int m;
-    AdaptiveFromEnv(on, m);
-    return g_adaptive < 0 ? m : g_adaptive_min_spp;
+    return adaptive_switch(g_set).n;
 }
-
-void AtrousFromEnv(bool &on, int &iterations) {
-    on = false;
-    iterations = 5;
-    if (const char *e = std::getenv("PATHTRACER_GPU_ATROUS")) {
-        std::string v(e);
-        for (char &ch : v) ch = (char)std::tolower((unsigned char)ch);
-        on = v == "1" || v == "true" || v == "on" || v == "yes";
-    }
-    if (const char *e = std::getenv("PATHTRACER_GPU_ATROUS_ITERS")) {
-        char *end = nullptr;
-        const long v = std::strtol(e, &end, 10);
-        if (end != e && *end == 0 && v >= 0 && v <= 6) iterations = (int)v;
-    }
-}
-
-int FeaturesFromEnv() {
-    if (const char *e = std::getenv("PATHTRACER_GPU_FEATURES")) {
-        char *end = nullptr;
-        const long v = std::strtol(e, &end, 10);
-        if (end != e && *end == 0 && v >= 0 && v <= 0x7fffffffL) return (int)v;
-    }
-    return -1;
-}
-
 void SetAtrous(bool on, int iterations) {
     std::lock_guard<std::mutex> lk(g_mu);
-    g_atrous = on ? 1 : 0;
-    g_atrous_iters = iterations >= 0 && iterations <= 6 ? iterations : 5;
+    g_set.atrous = Switch{on, iterations >= 0 && iterations <= 6 ? iterations : 5};
 }
-
 bool GetAtrous() {
     std::lock_guard<std::mutex> lk(g_mu);
-    bool on;
-    int it;
-    AtrousFromEnv(on, it);
-    return g_atrous < 0 ? on : g_atrous == 1;
+    return atrous_switch(g_set).on;
 }
-
 int GetAtrousIterations() {
     std::lock_guard<std::mutex> lk(g_mu);
-    bool on;
-    int it;
-    AtrousFromEnv(on, it);
-    return g_atrous < 0 ? it : g_atrous_iters;
+    return atrous_switch(g_set).n;
 }
-
-double FilteredNoiseFromEnv() {
-    if (const char *e = std::getenv("PATHTRACER_GPU_FILTERED_NOISE")) {
-        char *end = nullptr;
-        const double v = std::strtod(e, &end);
-        if (end != e && *end == 0 && v > 0 && v <= 1.7976931348623157e308) return v;
-    }
-    return 0;
-}
-
 void SetFilteredNoise(double target) {
     std::lock_guard<std::mutex> lk(g_mu);
-    g_filtered_noise = target > 0 ? target : 0;
+    g_set.filtered_noise = target > 0 ? target : 0;
 }
-
 double GetFilteredNoise() {
     std::lock_guard<std::mutex> lk(g_mu);
-    return g_filtered_noise < 0 ? FilteredNoiseFromEnv() : g_filtered_noise;
+    return g_set.filtered_noise.value_or(FilteredNoiseFromEnv());
 }
-
-bool TemporalFromEnv() {
-    const char *e = std::getenv("PATHTRACER_GPU_TEMPORAL");
-    if (!e) return false;
-    std::string v(e);
-    for (char &c : v) c = (char)std::tolower((unsigned char)c);
-    return v == "1" || v == "true" || v == "on" || v == "yes";
-}
-
 void SetTemporal(bool on) {
     std::lock_guard<std::mutex> lk(g_mu);
-    g_temporal = on ? 1 : 0;
+    g_set.temporal = on;
 }
-
 bool Temporal() {
     std::lock_guard<std::mutex> lk(g_mu);
-    return g_temporal < 0 ? TemporalFromEnv() : g_temporal == 1;
+    return g_set.temporal.value_or(TemporalFromEnv());
 }
-
 void ResetTemporal() {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx && g_core.temporal_reset) (void)g_core.temporal_reset(g_ctx);
+    if (g_ctx && g_core.pt_temporal_reset) (void)g_core.pt_temporal_reset(g_ctx);
 }
-
-double TemporalClipFromEnv() {
-    const char *e = std::getenv("PATHTRACER_GPU_TEMPORAL_CLIP");
-    if (!e || !*e) return 0;
-    char *end = nullptr;
-    const double g = std::strtod(e, &end);
-    return end != e && *end == 0 && std::isfinite(g) && g >= 0 ? g : 0;
-}
-
 void SetTemporalClip(double gamma) {
     std::lock_guard<std::mutex> lk(g_mu);
-    g_temporal_clip = std::isfinite(gamma) && gamma >= 0 ? gamma : 0;
+    g_set.temporal_clip = finite_not_negative(gamma) ? gamma : 0;
 }
-
 bool TemporalClipStats(double &gamma, uint64_t &clipped, uint64_t &reprojected) {
     std::lock_guard<std::mutex> lk(g_mu);
     struct pt_temporal_clip_stats cs;
-    if (!g_ctx || !g_core.temporal_clip_stats || g_core.temporal_clip_stats(g_ctx, &cs) != PT_OK) return false;
+    if (!g_ctx || !g_core.pt_temporal_clip_stats || g_core.pt_temporal_clip_stats(g_ctx, &cs) != PT_OK) return false;
     gamma = cs.gamma;
     clipped = cs.clipped;
     reprojected = cs.reprojected;
     return true;
 }
-
 void SetFeatures(int k) {
     std::lock_guard<std::mutex> lk(g_mu);
-    g_features = k >= 0 ? k : -1;
+    if (k >= 0) g_set.features = k;
+    else g_set.features.reset();
 }
-
 int GetFeatures() {
     std::lock_guard<std::mutex> lk(g_mu);
-    return g_features >= 0 ? g_features : FeaturesFromEnv();
+    return g_set.features.value_or(FeaturesFromEnv());
 }
 
 void Shutdown() {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx && g_core.handle) g_core.destroy(g_ctx);
+    if (g_ctx && g_core.handle) g_core.pt_destroy(g_ctx);
     g_ctx = nullptr;
 }
 
@@ -515,95 +486,59 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     std::lock_guard<std::mutex> lk(g_mu);
     if (img.Width != cfg.Width || img.Height != cfg.Height) return "";  // renderIntoCPU: silently do nothing (renderer.go:46-49)
     if (!load_core()) return g_core.error;
+    std::string err;
+    auto failed = [&err](std::string text) { return !(err = std::move(text)).empty(); };  // keeps the text of the call that failed
     if (!g_ctx) {
         int32_t n = g_devices.empty() ? 1 : (int32_t)g_devices.size();
         std::vector<int32_t> ords(g_devices.begin(), g_devices.end());
-        if (g_core.create(ords.empty() ? nullptr : ords.data(), n, &g_ctx) != PT_OK)
-            return std::string("pt_create: ") + g_core.last_error();
+        if (failed(PT_CALL(pt_create, ords.empty() ? nullptr : ords.data(), n, &g_ctx))) return err;
     }
     Flat flat;
     FlattenScene(sc, flat.materials, flat.objects, flat.sc);
-    {  // the scene's fog block when asked for (SetFog / PATHTRACER_GPU_FOG), else off
-        const bool fog_on = (g_fog < 0 ? FogFromEnv() : g_fog == 1) && sc.FogPtr;
-        pt_fog fog;
-        if (fog_on) FlattenFog(*sc.FogPtr, fog);
-        if (g_core.set_fog(g_ctx, fog_on ? &fog : nullptr) != PT_OK) return std::string("pt_set_fog: ") + g_core.last_error();
-    }
+    const FramePlan p = resolve(sc, flat.objects, g_set);
+    const bool gl = p.shading == PT_SHADING_GL, to_noise = p.noise.target > 0, to_filtered = p.filtered > 0;
+    const char *missing = nullptr;  // the text of the last need that was not met
+    auto lacks = [&missing](bool wanted, Feature f) { return wanted && !kNeeds[f].have(g_core) && (missing = kNeeds[f].lacks); };
+
+    // ---- the plan onto the context: each check stands in front of the first call that depends on it
+    pt_fog fog;
+    if (p.fog) FlattenFog(*sc.FogPtr, fog);
+    if (failed(PT_CALL(pt_set_fog, g_ctx, p.fog ? &fog : nullptr))) return err;
+    if (lacks(gl, GL_SHADING)) return missing;
     std::vector<pt_gl_material> gl_mats;
-    bool gl_model = false;
-    {  // the shading model (SetShading / PATHTRACER_GPU_SHADING): the CPU engine unless GL is asked for
-        const int model = g_shading < 0 ? ShadingFromEnv() : g_shading;
-        gl_model = model == PT_SHADING_GL;
-        if (model == PT_SHADING_GL && !g_core.set_shading) return "GL shading: libptcore.so lacks pt_set_shading";
-        if (g_core.set_shading) {
-            pt_shading sh;
-            std::memset(&sh, 0, sizeof sh);
-            sh.model = model;
-            if (model == PT_SHADING_GL) {
-                FlattenGlMaterials(sc, gl_mats);
-                sh.num_materials = (int32_t)gl_mats.size();
-                sh.materials = gl_mats.data();
-            }
-            if (g_core.set_shading(g_ctx, model == PT_SHADING_GL ? &sh : nullptr) != PT_OK)
-                return std::string("pt_set_shading: ") + g_core.last_error();
+    if (g_core.pt_set_shading) {
+        pt_shading sh;
+        std::memset(&sh, 0, sizeof sh);
+        sh.model = p.shading;
+        if (gl) {
+            FlattenGlMaterials(sc, gl_mats);
+            sh.num_materials = (int32_t)gl_mats.size();
+            sh.materials = gl_mats.data();
         }
+        if (failed(PT_CALL(pt_set_shading, g_ctx, gl ? &sh : nullptr))) return err;
     }
-    double noise_target = g_noise_target;
-    int noise_step = g_noise_step;
-    if (!g_noise_set) NoiseFromEnv(noise_target, noise_step);
-    const bool to_noise = noise_target > 0;
-    if (to_noise && !(g_core.set_moments && g_core.noise_estimate)) return "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate";
-    // the a-trous filter (SetAtrous / PATHTRACER_GPU_ATROUS) reads the moments, and the feature planes where the scene allows them
-    bool atrous = g_atrous == 1;
-    int atrous_iters = g_atrous_iters;
-    if (g_atrous < 0) AtrousFromEnv(atrous, atrous_iters);
-    // temporal accumulation (SetTemporal / PATHTRACER_GPU_TEMPORAL) brings the filter, the moments and the feature planes with it
-    const bool temporal = g_temporal < 0 ? TemporalFromEnv() : g_temporal == 1;
-    if (temporal && !g_core.temporal) return "temporal accumulation: libptcore.so lacks pt_temporal";
-    const double clip = temporal ? (g_temporal_clip < 0 ? TemporalClipFromEnv() : g_temporal_clip) : 0;
-    if (clip > 0 && !(g_core.temporal_set_clip && g_core.temporal_clip_stats)) return "temporal clip: libptcore.so lacks pt_temporal_set_clip";
-    atrous = atrous || temporal;
-    if (atrous && !(g_core.atrous && g_core.set_moments)) return "a-trous filter: libptcore.so lacks pt_atrous / pt_set_moments";
-    // a noise target on the filtered frame (SetFilteredNoise / PATHTRACER_GPU_FILTERED_NOISE): the half-buffer sums and pt_atrous_halves
-    const double filtered_target = atrous ? (g_filtered_noise < 0 ? FilteredNoiseFromEnv() : g_filtered_noise) : 0;
-    const bool to_filtered = filtered_target > 0;
+    if (lacks(to_noise, NOISE_TARGET)) return missing;
+    if (lacks(p.temporal, TEMPORAL)) return missing;
+    if (lacks(p.clip > 0, TEMPORAL_CLIP)) return missing;
+    if (lacks(p.atrous.on, ATROUS)) return missing;
     if (to_filtered && to_noise) return "filtered noise target: excludes a frame noise target (-noise) and adaptive sampling: one stop rule per frame";
-    if (to_filtered && gl_model) return "filtered noise target: not available with GL shading";
-    if (to_filtered && !(g_core.set_halves && g_core.atrous_halves)) return "filtered noise target: libptcore.so lacks pt_set_halves / pt_atrous_halves";
-    if (g_core.set_halves && g_core.set_halves(g_ctx, to_filtered ? 1 : 0) != PT_OK) return std::string("pt_set_halves: ") + g_core.last_error();
-    int features = g_features >= 0 ? g_features : FeaturesFromEnv();
-    if (features < 0 && temporal) features = 4;  // (pt_temporal needs them: where the frame refuses features, pt_begin says so)
-    if (features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path), else off
-        features = 0;
-        if (atrous && !gl_model) {
-            size_t spheres = 0, boxes = 0;
-            for (const pt_object &o : flat.objects) {
-                spheres += o.type == PT_OBJ_SPHERE || o.type == PT_OBJ_SPHERE_LIGHT;
-                boxes += o.type == PT_OBJ_BOX;
-            }
-            const char *scan = std::getenv("PTCORE_SCAN");
-            const bool forced_bvh = scan && (!std::strcmp(scan, "bvh") || !std::strcmp(scan, "verify_bvh"));
-            if (spheres <= 128 && boxes <= 128 && !forced_bvh) features = 4;
-        }
-    }
-    if (features > 0 && !g_core.set_features) return "features: libptcore.so lacks pt_set_features";
-    if (g_core.set_features && g_core.set_features(g_ctx, features) != PT_OK) return std::string("pt_set_features: ") + g_core.last_error();
-    if (g_core.set_moments && g_core.set_moments(g_ctx, to_noise || atrous ? 1 : 0) != PT_OK) return std::string("pt_set_moments: ") + g_core.last_error();
-    bool adaptive = g_adaptive == 1;
-    int min_spp = g_adaptive_min_spp;
-    if (g_adaptive < 0) AdaptiveFromEnv(adaptive, min_spp);
-    adaptive = adaptive && to_noise;  // the noise target is the blocks' target; without one there is nothing to adapt to
-    if (adaptive && !(g_core.set_adaptive && g_core.adaptive_state)) return "adaptive sampling: libptcore.so lacks pt_set_adaptive / pt_adaptive_state";
-    if (g_core.set_adaptive) {
+    if (to_filtered && gl) return "filtered noise target: not available with GL shading";
+    if (lacks(to_filtered, FILTERED_NOISE)) return missing;
+    if (g_core.pt_set_halves && failed(PT_CALL(pt_set_halves, g_ctx, p.halves ? 1 : 0))) return err;
+    if (lacks(p.features > 0, FEATURES)) return missing;
+    if (g_core.pt_set_features && failed(PT_CALL(pt_set_features, g_ctx, p.features))) return err;
+    if (g_core.pt_set_moments && failed(PT_CALL(pt_set_moments, g_ctx, p.moments ? 1 : 0))) return err;
+    if (lacks(p.adaptive.on, ADAPTIVE)) return missing;
+    if (g_core.pt_set_adaptive) {
         pt_adaptive ad;
         std::memset(&ad, 0, sizeof ad);
-        ad.target = noise_target;
-        ad.min_spp = min_spp;
-        ad.step = noise_step;
-        if (g_core.set_adaptive(g_ctx, adaptive ? &ad : nullptr) != PT_OK) return std::string("pt_set_adaptive: ") + g_core.last_error();
+        ad.target = p.noise.target;
+        ad.min_spp = p.adaptive.n;
+        ad.step = p.noise.step;
+        if (failed(PT_CALL(pt_set_adaptive, g_ctx, p.adaptive.on ? &ad : nullptr))) return err;
     }
-    struct pt_adaptive_state as;
-    std::memset(&as, 0, sizeof as);
+
+    // ---- the frame: pt_render, or one stepping loop under the frame's stop rule
     pt_config pc;
     std::memset(&pc, 0, sizeof pc);
     pc.width = cfg.Width;
@@ -611,97 +546,79 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     pc.samples_per_px = cfg.SamplesPerPx;
     pc.max_depth = cfg.MaxDepth;
     pc.seed = cfg.Seed;
+    const pt_atrous_config filter = {p.atrous.n, 0, 4.0, 0.1, 0.1, 0.2};  // the filter's configuration, for the check and the finish alike
     pt_stats st;
     std::memset(&st, 0, sizeof st);
-    std::string err;
-    int32_t spp_done = cfg.SamplesPerPx > 0 ? cfg.SamplesPerPx : 0;
     pt_noise nz;
     std::memset(&nz, 0, sizeof nz);
     pt_halves_stats hs;
     std::memset(&hs, 0, sizeof hs);
-    if (to_filtered) {  // render until the measured noise of the filtered frame is at the target, SamplesPerPx as the cap
-        if (g_core.begin(g_ctx, &flat.sc, &pc) != PT_OK) return std::string("pt_begin: ") + g_core.last_error();
-        const pt_atrous_config ac = {atrous_iters, 0, 4.0, 0.1, 0.1, 0.2};
-        int32_t done = 0;
-        while (err.empty() && done < cfg.SamplesPerPx) {
-            const int32_t left = cfg.SamplesPerPx - done;
-            if (g_core.step(g_ctx, noise_step < left ? noise_step : left, &done) != PT_OK) { err = std::string("pt_step: ") + g_core.last_error(); break; }
-            if (progress) {
-                if (g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK) { err = std::string("pt_read: ") + g_core.last_error(); break; }
-                progress();
-            }
-            if (done < 4) continue;  // each half needs two samples for its variance
-            if (g_core.atrous_halves(g_ctx, &ac, nullptr, nullptr, nullptr, &hs) != PT_OK) { err = std::string("pt_atrous_halves: ") + g_core.last_error(); break; }
-            if (hs.noise <= filtered_target) break;
-        }
-        if (err.empty() && (!progress || cfg.SamplesPerPx <= 0) && g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK)
-            err = std::string("pt_read: ") + g_core.last_error();
-        if (g_core.end(g_ctx, &st) != PT_OK && err.empty()) err = std::string("pt_end: ") + g_core.last_error();
-        if (err.empty() && progress) progress();
-        spp_done = done;
-    } else if (to_noise) {  // render until the noise target, SamplesPerPx as the cap; the check follows every step
-        if (g_core.begin(g_ctx, &flat.sc, &pc) != PT_OK) return std::string("pt_begin: ") + g_core.last_error();
-        int32_t done = 0;
+    struct pt_adaptive_state as;
+    std::memset(&as, 0, sizeof as);
+    int32_t done = cfg.SamplesPerPx > 0 ? cfg.SamplesPerPx : 0;
+    if (!to_filtered && !to_noise && !progress) {
+        err = PT_CALL(pt_render, g_ctx, &flat.sc, &pc, img.Pix.data(), img.Stride, nullptr, nullptr, nullptr, &st);
+    } else {
+        // filtered noise: each half needs two samples for its variance, so the check runs from 4 on.  frame noise: the check follows
+        // every step and may end the frame from 2 on -- never when adaptive, where the blocks stop inside pt_step.  Otherwise the
+        // preview cadence: a refresh every spp/10 samples and once at the end (gpu.go:2209-2212, :2229, :2523-2525).
+        const int32_t never = INT32_MAX, preview_step = cfg.SamplesPerPx / 10 > 0 ? cfg.SamplesPerPx / 10 : 1;
+        //                                 check                     step          clip_step  ends_when_stalled  measure_from  stop_from  target
+        const StopRule rule = to_filtered ? StopRule{StopRule::FILTERED_NOISE, p.noise.step, true,  false,         4, 4,                         p.filtered}
+                              : to_noise  ? StopRule{StopRule::FRAME_NOISE,    p.noise.step, true,  p.adaptive.on, 0, p.adaptive.on ? never : 2, p.noise.target}
+                                          : StopRule{StopRule::NONE,           preview_step, false, false,         0, 0,                         0};
+        if (failed(PT_CALL(pt_begin, g_ctx, &flat.sc, &pc))) return err;
+        done = 0;
         while (err.empty() && done < cfg.SamplesPerPx) {
             const int32_t left = cfg.SamplesPerPx - done, before = done;
-            if (g_core.step(g_ctx, noise_step < left ? noise_step : left, &done) != PT_OK) { err = std::string("pt_step: ") + g_core.last_error(); break; }
-            if (adaptive && done == before) break;  // every block has stopped: the step added nothing
+            if (failed(PT_CALL(pt_step, g_ctx, rule.clip_step && left < rule.step ? left : rule.step, &done))) break;
+            if (rule.ends_when_stalled && done == before) break;
             if (progress) {
-                if (g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK) { err = std::string("pt_read: ") + g_core.last_error(); break; }
+                if (failed(PT_CALL(pt_read, g_ctx, img.Pix.data(), img.Stride, nullptr))) break;
                 progress();
             }
-            if (g_core.noise_estimate(g_ctx, &nz) != PT_OK) { err = std::string("pt_noise_estimate: ") + g_core.last_error(); break; }
-            if (!adaptive && done >= 2 && nz.noise <= noise_target) break;  // (adaptive: the blocks stop inside pt_step)
+            if (rule.check == StopRule::NONE || done < rule.measure_from) continue;
+            double measured;
+            if (rule.check == StopRule::FRAME_NOISE) {
+                err = PT_CALL(pt_noise_estimate, g_ctx, &nz);
+                measured = nz.noise;
+            } else {
+                err = PT_CALL(pt_atrous_halves, g_ctx, &filter, nullptr, nullptr, nullptr, &hs);
+                measured = hs.noise;
+            }
+            if (err.empty() && done >= rule.stop_from && measured <= rule.target) break;
         }
-        if (adaptive && err.empty() && g_core.adaptive_state(g_ctx, &as) != PT_OK) err = std::string("pt_adaptive_state: ") + g_core.last_error();
-        if (err.empty() && (!progress || cfg.SamplesPerPx <= 0) && g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK)
-            err = std::string("pt_read: ") + g_core.last_error();
-        if (g_core.end(g_ctx, &st) != PT_OK && err.empty()) err = std::string("pt_end: ") + g_core.last_error();
+        if (p.adaptive.on && err.empty()) err = PT_CALL(pt_adaptive_state, g_ctx, &as);
+        if (err.empty() && (!progress || cfg.SamplesPerPx <= 0)) err = PT_CALL(pt_read, g_ctx, img.Pix.data(), img.Stride, nullptr);
+        const int32_t end_rc = g_core.pt_end(g_ctx, &st);  // (the frame is released whatever went wrong before)
+        if (err.empty()) err = call("pt_end", end_rc);
         if (err.empty() && progress) progress();
-        spp_done = done;
-    } else if (!progress) {
-        if (g_core.render(g_ctx, &flat.sc, &pc, img.Pix.data(), img.Stride, nullptr, nullptr, nullptr, &st) != PT_OK)
-            err = std::string("pt_render: ") + g_core.last_error();
-    } else {
-        if (g_core.begin(g_ctx, &flat.sc, &pc) != PT_OK) return std::string("pt_begin: ") + g_core.last_error();
-        // refresh the preview every spp/10 samples and once at the end (gpu.go:2209-2212, :2229, :2523-2525)
-        const int32_t step = cfg.SamplesPerPx / 10 > 0 ? cfg.SamplesPerPx / 10 : 1;
-        int32_t done = 0;
-        while (err.empty() && done < cfg.SamplesPerPx) {
-            if (g_core.step(g_ctx, step, &done) != PT_OK) { err = std::string("pt_step: ") + g_core.last_error(); break; }
-            if (g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK) { err = std::string("pt_read: ") + g_core.last_error(); break; }
-            progress();
-        }
-        if (err.empty() && cfg.SamplesPerPx <= 0 && g_core.read(g_ctx, img.Pix.data(), img.Stride, nullptr) != PT_OK)
-            err = std::string("pt_read: ") + g_core.last_error();
-        if (g_core.end(g_ctx, &st) != PT_OK && err.empty()) err = std::string("pt_end: ") + g_core.last_error();
-        if (err.empty()) progress();
     }
+
+    // ---- the finish: the accumulated or the filtered image takes the place of the plain one (the sums stay readable after pt_end)
     pt_atrous_stats ats;
     std::memset(&ats, 0, sizeof ats);
     pt_temporal_stats tst;
     std::memset(&tst, 0, sizeof tst);
     struct pt_temporal_clip_stats tcs;
     std::memset(&tcs, 0, sizeof tcs);
-    if (temporal && err.empty()) {  // the frame blended into the context's reprojected history, then filtered
-        pt_atrous_config ac = {atrous_iters, 0, 4.0, 0.1, 0.1, 0.2};
-        if (g_core.temporal_set_clip && g_core.temporal_set_clip(g_ctx, clip) != PT_OK) err = std::string("pt_temporal_set_clip: ") + g_core.last_error();
-        if (err.empty() && g_core.temporal(g_ctx, nullptr, &ac, img.Pix.data(), img.Stride, nullptr, nullptr, &tst) != PT_OK) err = std::string("pt_temporal: ") + g_core.last_error();
-        if (err.empty() && clip > 0 && g_core.temporal_clip_stats(g_ctx, &tcs) != PT_OK) err = std::string("pt_temporal_clip_stats: ") + g_core.last_error();
+    if (p.temporal && err.empty()) {  // the frame blended into the context's reprojected history, then filtered
+        if (g_core.pt_temporal_set_clip) err = PT_CALL(pt_temporal_set_clip, g_ctx, p.clip);
+        if (err.empty()) err = PT_CALL(pt_temporal, g_ctx, nullptr, &filter, img.Pix.data(), img.Stride, nullptr, nullptr, &tst);
+        if (err.empty() && p.clip > 0) err = PT_CALL(pt_temporal_clip_stats, g_ctx, &tcs);
         ats.atrous_ms = tst.temporal_ms;
         ats.noise_before = tst.noise_before;
         ats.noise_after = tst.noise_after;
-    } else if (atrous && err.empty()) {  // the filtered image takes the place of the plain finish (the sums stay readable after pt_end)
-        pt_atrous_config ac = {atrous_iters, 0, 4.0, 0.1, 0.1, 0.2};
-        if (g_core.atrous(g_ctx, &ac, img.Pix.data(), img.Stride, nullptr, nullptr, &ats) != PT_OK) err = std::string("pt_atrous: ") + g_core.last_error();
+    } else if (p.atrous.on && err.empty()) {
+        err = PT_CALL(pt_atrous, g_ctx, &filter, img.Pix.data(), img.Stride, nullptr, nullptr, &ats);
     }
     if (stats && err.empty()) {
-        stats->atrous = atrous;
-        stats->features = features;
+        stats->atrous = p.atrous.on;
+        stats->features = p.features;
         stats->atrous_ms = ats.atrous_ms;
         stats->noise_before = ats.noise_before;
         stats->noise_after = ats.noise_after;
-        stats->temporal = temporal;
+        stats->temporal = p.temporal;
         stats->reprojected = tst.reprojected;
         stats->disoccluded = tst.disoccluded;
         stats->temporal_ms = tst.temporal_ms;
@@ -715,9 +632,9 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         stats->samples = st.samples; stats->segments = st.segments; stats->exit_scans = st.exit_scans; stats->draws = st.draws;
         stats->seconds = st.seconds; stats->trace_ms = st.trace_ms; stats->resolve_ms = st.resolve_ms;
         stats->device_ms = st.device_ms; stats->num_devices = st.num_devices; stats->spp_chunk = st.spp_chunk;
-        stats->spp_done = spp_done;
-        stats->noise = to_noise ? nz.noise : 0;
-        stats->adaptive = adaptive;
+        stats->spp_done = done;
+        stats->noise = nz.noise;  // (stays 0 without a noise target: the check never ran)
+        stats->adaptive = p.adaptive.on;
         stats->blocks = as.blocks;
         stats->active_blocks = as.active_blocks;
         stats->spp_min = as.spp_min;

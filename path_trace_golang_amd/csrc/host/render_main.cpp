@@ -20,6 +20,7 @@
 // samples, with -spp as the cap (also env PATHTRACER_GPU_FILTERED_NOISE); it excludes -noise.
 #include <cerrno>
 #include <chrono>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -110,8 +111,34 @@ bool parse_bool(const std::string &v, bool &out) {
     return false;
 }
 
+// One row per flag: its name, how its value is read, and where it goes.  INT rows keep a value inside [lo, hi] and take `fallback`
+// for one outside (the plain sizes take any value, as Go's flag.Int does).
+enum Kind { BOOL, STRING, SHADING, INT, NOT_NEGATIVE, UINT };
+struct FlagRow {
+    const char *name;
+    Kind kind;
+    void *dst;
+    long long lo = LLONG_MIN, hi = LLONG_MAX;
+    int fallback = 0;
+};
+
+int bad_flag(const char *fmt, const std::string &a, const std::string &b = "") {
+    std::fprintf(stderr, fmt, a.c_str(), b.c_str());
+    usage();
+    return 2;
+}
+
 // Go's flag package rules
 int parse(int argc, char **argv, Flags &f) {
+    const FlagRow table[] = {
+        {"gpu", BOOL, &f.gpu}, {"headless", BOOL, &f.headless}, {"scene-settings", BOOL, &f.scene_settings}, {"fog", BOOL, &f.fog},
+        {"adaptive", BOOL, &f.adaptive}, {"atrous", BOOL, &f.atrous},
+        {"scene", STRING, &f.scene}, {"mode", STRING, &f.mode}, {"out", STRING, &f.out}, {"shading", SHADING, &f.shading},
+        {"width", INT, &f.width}, {"height", INT, &f.height}, {"spp", INT, &f.spp}, {"depth", INT, &f.depth}, {"devices", INT, &f.devices},
+        {"noise-step", INT, &f.noise_step, 1, 0x7fffffffLL, 16}, {"min-spp", INT, &f.min_spp, 0, 0x7fffffffLL, 0},
+        {"atrous-iters", INT, &f.atrous_iters, 0, 6, 5}, {"features", INT, &f.features, 0, 0x7fffffffLL, -1},
+        {"noise", NOT_NEGATIVE, &f.noise}, {"filtered-noise", NOT_NEGATIVE, &f.filtered_noise}, {"seed", UINT, &f.seed},
+    };
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a.size() < 2 || a[0] != '-') break;  // first non-flag argument ends parsing
@@ -122,73 +149,42 @@ int parse(int argc, char **argv, Flags &f) {
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         if (name == "h" || name == "help") { usage(); return 0; }
-        if (name == "gpu" || name == "headless" || name == "scene-settings" || name == "fog" || name == "adaptive" || name == "atrous") {
+        const FlagRow *row = nullptr;
+        for (const FlagRow &r : table)
+            if (name == r.name) row = &r;
+        if (!row) return bad_flag("flag provided but not defined: -%s\n", name);
+        if (row->kind == BOOL) {
             bool b = true;
-            if (has_val && !parse_bool(val, b)) {
-                std::fprintf(stderr, "invalid boolean value \"%s\" for -%s: parse error\n", val.c_str(), name.c_str());
-                usage();
-                return 2;
-            }
-            (name == "gpu" ? f.gpu : name == "headless" ? f.headless : name == "fog" ? f.fog : name == "adaptive" ? f.adaptive : name == "atrous" ? f.atrous : f.scene_settings) = b;
+            if (has_val && !parse_bool(val, b)) return bad_flag("invalid boolean value \"%s\" for -%s: parse error\n", val, name);
+            *static_cast<bool *>(row->dst) = b;
             continue;
         }
-        static const char *known[] = {"scene", "mode", "out", "width", "height", "spp", "depth", "seed", "devices", "shading", "noise", "noise-step", "min-spp", "atrous-iters", "features", "filtered-noise"};
-        bool ok = false;
-        for (const char *k : known) ok = ok || name == k;
-        if (!ok) {
-            std::fprintf(stderr, "flag provided but not defined: -%s\n", name.c_str());
-            usage();
-            return 2;
-        }
         if (!has_val) {
-            if (i + 1 >= argc) {
-                std::fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
-                usage();
-                return 2;
-            }
+            if (i + 1 >= argc) return bad_flag("flag needs an argument: -%s\n", name);
             val = argv[++i];
         }
-        if (name == "scene") f.scene = val;
-        else if (name == "mode") f.mode = val;
-        else if (name == "out") f.out = val;
-        else if (name == "shading") {
-            if (val != "cpu" && val != "gl") {
-                std::fprintf(stderr, "invalid value \"%s\" for flag -shading: want cpu or gl\n", val.c_str());
-                usage();
-                return 2;
+        char *end = nullptr;
+        errno = 0;
+        switch (row->kind) {
+            case STRING:
+                *static_cast<std::string *>(row->dst) = val;
+                break;
+            case SHADING:
+                if (val != "cpu" && val != "gl") return bad_flag("invalid value \"%s\" for flag -%s: want cpu or gl\n", val, name);
+                *static_cast<std::string *>(row->dst) = val;
+                break;
+            case NOT_NEGATIVE: {
+                const double v = std::strtod(val.c_str(), &end);
+                if (errno || end == val.c_str() || *end || !(v >= 0)) return bad_flag("invalid value \"%s\" for flag -%s: parse error\n", val, name);
+                *static_cast<double *>(row->dst) = v;
+                break;
             }
-            f.shading = val;
-        }
-        else if (name == "noise" || name == "filtered-noise") {
-            char *end = nullptr;
-            errno = 0;
-            const double v = std::strtod(val.c_str(), &end);
-            if (errno || end == val.c_str() || *end || !(v >= 0)) {
-                std::fprintf(stderr, "invalid value \"%s\" for flag -%s: parse error\n", val.c_str(), name.c_str());
-                usage();
-                return 2;
+            default: {
+                const long long n = std::strtoll(val.c_str(), &end, 10);
+                if (errno || end == val.c_str() || *end) return bad_flag("invalid value \"%s\" for flag -%s: parse error\n", val, name);
+                if (row->kind == UINT) *static_cast<unsigned long long *>(row->dst) = (unsigned long long)n;
+                else *static_cast<int *>(row->dst) = n >= row->lo && n <= row->hi ? (int)n : row->fallback;
             }
-            (name == "noise" ? f.noise : f.filtered_noise) = v;
-        }
-        else {
-            char *end = nullptr;
-            errno = 0;
-            long long n = std::strtoll(val.c_str(), &end, 10);
-            if (errno || end == val.c_str() || *end) {
-                std::fprintf(stderr, "invalid value \"%s\" for flag -%s: parse error\n", val.c_str(), name.c_str());
-                usage();
-                return 2;
-            }
-            if (name == "width") f.width = (int)n;
-            else if (name == "height") f.height = (int)n;
-            else if (name == "spp") f.spp = (int)n;
-            else if (name == "depth") f.depth = (int)n;
-            else if (name == "devices") f.devices = (int)n;
-            else if (name == "noise-step") f.noise_step = n >= 1 && n <= 0x7fffffffLL ? (int)n : 16;
-            else if (name == "min-spp") f.min_spp = n >= 0 && n <= 0x7fffffffLL ? (int)n : 0;
-            else if (name == "atrous-iters") f.atrous_iters = n >= 0 && n <= 6 ? (int)n : 5;
-            else if (name == "features") f.features = n >= 0 && n <= 0x7fffffffLL ? (int)n : -1;
-            else f.seed = (unsigned long long)n;
         }
     }
     return -1;

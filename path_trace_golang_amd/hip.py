@@ -13,6 +13,8 @@ engine (renderer.go:257-262).
 from __future__ import annotations
 
 import ctypes as C
+import math
+import os
 from dataclasses import dataclass
 from typing import Callable, Optional
 
@@ -26,6 +28,30 @@ _MAT = {scn.MATERIAL_LAMBERT: capi.PT_MAT_LAMBERT, scn.MATERIAL_METAL: capi.PT_M
         scn.MATERIAL_MIRROR: capi.PT_MAT_MIRROR}
 _OBJ = {scn.OBJECT_SPHERE: capi.PT_OBJ_SPHERE, scn.OBJECT_PLANE: capi.PT_OBJ_PLANE, scn.OBJECT_BOX: capi.PT_OBJ_BOX,
         scn.OBJECT_SPHERE_LIGHT: capi.PT_OBJ_SPHERE_LIGHT}
+
+
+# ---- the environment parsers of the *from_env rules (environ None = os.environ)
+def _env_on(environ, key: str) -> bool:
+    """1 / true / on / yes in any case, nothing else."""
+    return (os.environ if environ is None else environ).get(key, "").lower() in ("1", "true", "on", "yes")
+
+
+def _env_int(environ, key: str, lo: int, hi: Optional[int] = None) -> Optional[int]:
+    """The integer the variable holds when it lies in [lo, hi] (hi None: no upper bound), else None."""
+    try:
+        i = int((os.environ if environ is None else environ)[key])
+    except (KeyError, ValueError):
+        return None
+    return i if i >= lo and (hi is None or i <= hi) else None
+
+
+def _env_positive(environ, key: str) -> Optional[float]:
+    """The finite float > 0 the variable holds, else None."""
+    try:
+        f = float((os.environ if environ is None else environ)[key])
+    except (KeyError, ValueError):
+        return None
+    return f if f > 0 and math.isfinite(f) else None
 
 
 @dataclass
@@ -312,22 +338,10 @@ class AtrousConfig:
     def from_env(cls, environ=None) -> Optional["AtrousConfig"]:
         """PATHTRACER_GPU_ATROUS=1 (or true / on / yes) turns the filter on (None otherwise); PATHTRACER_GPU_ATROUS_ITERS=<0..6>
         and PATHTRACER_GPU_FEATURES=<int >= 0> set the iterations and the feature samples, anything else keeps the default."""
-        import os
-
-        env = os.environ if environ is None else environ
-        if env.get("PATHTRACER_GPU_ATROUS", "").lower() not in ("1", "true", "on", "yes"):
+        if not _env_on(environ, "PATHTRACER_GPU_ATROUS"):
             return None
-        cfg = cls()
-        try:
-            i = int(env["PATHTRACER_GPU_ATROUS_ITERS"])
-            if 0 <= i <= 6:
-                cfg.iterations = i
-        except (KeyError, ValueError):
-            pass
-        k = features_from_env(env)
-        if k is not None:
-            cfg.features = k
-        return cfg
+        i = _env_int(environ, "PATHTRACER_GPU_ATROUS_ITERS", 0, 6)
+        return cls(iterations=5 if i is None else i, features=features_from_env(environ))
 
     def c(self) -> capi.PtAtrousConfig:
         return capi.PtAtrousConfig(int(self.iterations), 0, float(self.sigma_l), float(self.sigma_n), float(self.sigma_z),
@@ -336,14 +350,7 @@ class AtrousConfig:
 
 def features_from_env(environ=None) -> Optional[int]:
     """PATHTRACER_GPU_FEATURES=<int >= 0>: the feature samples per pixel, None when unset or not such a number."""
-    import os
-
-    env = os.environ if environ is None else environ
-    try:
-        k = int(env["PATHTRACER_GPU_FEATURES"])
-        return k if k >= 0 else None
-    except (KeyError, ValueError):
-        return None
+    return _env_int(environ, "PATHTRACER_GPU_FEATURES", 0)
 
 
 def atrous(ctx: capi.Context, cfg: Optional[AtrousConfig], img: Optional[np.ndarray], mean: Optional[np.ndarray] = None,
@@ -390,12 +397,7 @@ class TemporalConfig:
     @classmethod
     def from_env(cls, environ=None) -> Optional["TemporalConfig"]:
         """PATHTRACER_GPU_TEMPORAL=1 (or true / on / yes) turns the accumulation on (None otherwise)."""
-        import os
-
-        env = os.environ if environ is None else environ
-        if env.get("PATHTRACER_GPU_TEMPORAL", "").lower() not in ("1", "true", "on", "yes"):
-            return None
-        return cls()
+        return cls() if _env_on(environ, "PATHTRACER_GPU_TEMPORAL") else None
 
     def c(self) -> capi.PtTemporalConfig:
         return capi.PtTemporalConfig(float(self.alpha), float(self.tol_z), float(self.n_min), float(self.tol_a), int(self.max_len), 0)
@@ -481,9 +483,6 @@ def temporal_clip_stats(ctx: capi.Context) -> dict:
 def temporal_clip_from_env(environ=None) -> float:
     """PATHTRACER_GPU_TEMPORAL_CLIP=<gamma>: the clip of the RenderInto path when PATHTRACER_GPU_TEMPORAL is on.  Unset, empty or
     not a finite number >= 0: 0.0 (off)."""
-    import math
-    import os
-
     env = os.environ if environ is None else environ
     try:
         g = float(env.get("PATHTRACER_GPU_TEMPORAL_CLIP", "") or 0.0)
@@ -543,22 +542,12 @@ def atrous_halves(ctx: capi.Context, cfg: Optional[AtrousConfig], mean: Optional
 def filtered_noise_from_env(environ=None) -> Optional[float]:
     """PATHTRACER_GPU_FILTERED_NOISE=<float > 0>: the noise target on the filtered frame (used with PATHTRACER_GPU_ATROUS; the step
     is PATHTRACER_GPU_NOISE_STEP); None when unset or not such a number."""
-    import math
-    import os
-
-    env = os.environ if environ is None else environ
-    try:
-        f = float(env["PATHTRACER_GPU_FILTERED_NOISE"])
-        return f if f > 0 and math.isfinite(f) else None
-    except (KeyError, ValueError):
-        return None
+    return _env_positive(environ, "PATHTRACER_GPU_FILTERED_NOISE")
 
 
 def scene_allows_features(sc, shading: str = "cpu") -> bool:
     """Does a frame of this scene accept pt_set_features(k > 0)?  Not with GL shading, and not on the bounding-volume-hierarchy
     path (more than 128 spheres or 128 boxes, or PTCORE_SCAN=bvh)."""
-    import os
-
     if shading != "cpu" or os.environ.get("PTCORE_SCAN", "") in ("bvh", "verify_bvh"):
         return False
     if isinstance(sc, FlatScene):
@@ -594,6 +583,18 @@ def context() -> capi.Context:
     if _default_ctx is None:
         _default_ctx = capi.Context(devices=_default_devices) if _default_devices else capi.Context(ndev=1)
     return _default_ctx
+
+
+@dataclass
+class _StopRule:
+    """How the stepping loop of `render` advances and what ends a frame before the cap."""
+    step: int                                    # samples per pt_step
+    clip: bool = False                           # ... clipped to what is left of the cap
+    stalls: bool = False                         # a step that adds nothing ends the frame (adaptive: every block has stopped)
+    check: Optional[Callable[[], float]] = None  # measured after a step once measure_from samples are done; from stop_from
+    measure_from: int = 0                        # samples on, a figure at or below target ends the frame
+    stop_from: int = 0
+    target: float = 0.0
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -741,52 +742,42 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
         return with_moments(d)
     if nseg is not None or ndraw is not None:
         raise ValueError("per-pixel stats are only available without a progress callback and without a noise target")
+    nz = capi.PtNoise()
+
+    def frame_noise() -> float:
+        capi.check(L.pt_noise_estimate(ctx.handle, C.byref(nz)))
+        return nz.noise
+
+    def filtered_frame_noise() -> float:
+        nonlocal fstats
+        hs = atrous_halves(ctx, atrous)
+        fstats = {"filtered_noise": hs["noise"], "noise_model": hs["noise_model"]}
+        return hs["noise"]
+
+    nstep = max(1, int(noise_step))
+    if adaptive:  # the blocks stop inside pt_step
+        rule = _StopRule(nstep, stalls=True)
+    elif filtered_noise is not None:  # each half needs two samples for its variance
+        rule = _StopRule(nstep, clip=True, check=filtered_frame_noise, measure_from=4, stop_from=4, target=filtered_noise)
+    elif noise is not None:  # the check follows every step
+        rule = _StopRule(nstep, clip=True, check=frame_noise, stop_from=2, target=noise)
+    else:  # the preview cadence: ~10 steps
+        rule = _StopRule(max(1, cfg.samples_per_px // 10))
     capi.check(L.pt_begin(ctx.handle, C.byref(flat.c), C.byref(pc)))
     done = C.c_int32(0)
     try:
-        if adaptive:  # the blocks stop inside pt_step; the frame ends when a step adds nothing
-            before = -1
-            while done.value < cfg.samples_per_px and done.value != before:
-                before = done.value
-                capi.check(L.pt_step(ctx.handle, max(1, int(noise_step)), C.byref(done)))
-                if done.value != before:
-                    capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
-                    progress()
-            if cfg.samples_per_px <= 0:
-                capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
-        elif filtered_noise is not None:  # render until the measured noise of the filtered frame is at the target
-            while done.value < cfg.samples_per_px:
-                capi.check(L.pt_step(ctx.handle, max(1, min(int(noise_step), cfg.samples_per_px - done.value)), C.byref(done)))
-                if progress is not None:
-                    capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
-                    progress()
-                if done.value >= 4:
-                    hs = atrous_halves(ctx, atrous)
-                    fstats = {"filtered_noise": hs["noise"], "noise_model": hs["noise_model"]}
-                    if hs["noise"] <= filtered_noise:
-                        break
-            if progress is None or cfg.samples_per_px <= 0:
-                capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
-        elif noise is not None:  # render until the noise target, cfg.samples_per_px as the cap
-            nz = capi.PtNoise()
-            while done.value < cfg.samples_per_px:
-                capi.check(L.pt_step(ctx.handle, max(1, min(int(noise_step), cfg.samples_per_px - done.value)), C.byref(done)))
-                if progress is not None:
-                    capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
-                    progress()
-                capi.check(L.pt_noise_estimate(ctx.handle, C.byref(nz)))
-                if done.value >= 2 and nz.noise <= noise:
-                    break
-            if progress is None or cfg.samples_per_px <= 0:
-                capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
-        else:
-            step = max(1, cfg.samples_per_px // 10)
-            while done.value < cfg.samples_per_px:
-                capi.check(L.pt_step(ctx.handle, step, C.byref(done)))
+        while done.value < cfg.samples_per_px:
+            before = done.value
+            capi.check(L.pt_step(ctx.handle, min(rule.step, cfg.samples_per_px - before) if rule.clip else rule.step, C.byref(done)))
+            if rule.stalls and done.value == before:
+                break
+            if progress is not None:
                 capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
                 progress()
-            if cfg.samples_per_px <= 0:
-                capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
+            if rule.check is not None and done.value >= rule.measure_from and rule.check() <= rule.target and done.value >= rule.stop_from:
+                break
+        if progress is None or cfg.samples_per_px <= 0:
+            capi.check(L.pt_read(ctx.handle, _ptr(img), stride, _ptr(accum)))
     finally:
         rc = L.pt_end(ctx.handle, C.byref(st))
     capi.check(rc)
@@ -814,8 +805,6 @@ class PostConfig:
     def from_env(cls, environ=None) -> "PostConfig":
         """The reference's switches: PATHTRACER_GPU_DENOISE (default on there), _SIGMA_S, _SIGMA_R (gpu.go:77-95),
         PATHTRACER_GPU_SMOOTH (default off), _RADIUS, _STRENGTH (gpu.go:140-175); tone mapping always on."""
-        import os
-
         env = os.environ if environ is None else environ
         cfg = cls(tonemap=True, denoise=True)
         v = env.get("PATHTRACER_GPU_DENOISE", "").lower()
@@ -828,9 +817,7 @@ class PostConfig:
                     setattr(cfg, attr, f)
             except (KeyError, ValueError):
                 pass
-        v = env.get("PATHTRACER_GPU_SMOOTH", "").lower()
-        if v in ("1", "true", "on", "yes"):
-            cfg.smooth = True
+        cfg.smooth = _env_on(env, "PATHTRACER_GPU_SMOOTH")
         try:
             cfg.smooth_radius = max(1, min(5, int(env["PATHTRACER_GPU_SMOOTH_RADIUS"])))
         except (KeyError, ValueError):
@@ -850,10 +837,7 @@ class FogConfig:
     @classmethod
     def from_env(cls, environ=None) -> "FogConfig":
         """PATHTRACER_GPU_FOG=1 (or true / on / yes) turns it on, like the PATHTRACER_GPU_* switches of PostConfig."""
-        import os
-
-        env = os.environ if environ is None else environ
-        return cls(enabled=env.get("PATHTRACER_GPU_FOG", "").lower() in ("1", "true", "on", "yes"))
+        return cls(enabled=_env_on(environ, "PATHTRACER_GPU_FOG"))
 
 
 @dataclass
@@ -866,24 +850,7 @@ class NoiseConfig:
     @classmethod
     def from_env(cls, environ=None) -> "NoiseConfig":
         """PATHTRACER_GPU_NOISE=<float > 0> and PATHTRACER_GPU_NOISE_STEP=<int >= 1>; anything else keeps the default."""
-        import math
-        import os
-
-        env = os.environ if environ is None else environ
-        cfg = cls()
-        try:
-            f = float(env["PATHTRACER_GPU_NOISE"])
-            if f > 0 and math.isfinite(f):
-                cfg.target = f
-        except (KeyError, ValueError):
-            pass
-        try:
-            i = int(env["PATHTRACER_GPU_NOISE_STEP"])
-            if i >= 1:
-                cfg.step = i
-        except (KeyError, ValueError):
-            pass
-        return cfg
+        return cls(target=_env_positive(environ, "PATHTRACER_GPU_NOISE") or 0.0, step=_env_int(environ, "PATHTRACER_GPU_NOISE_STEP", 1) or 16)
 
     @property
     def enabled(self) -> bool:
@@ -901,17 +868,7 @@ class AdaptiveConfig:
     def from_env(cls, environ=None) -> "AdaptiveConfig":
         """PATHTRACER_GPU_ADAPTIVE=1 (or true / on / yes) and PATHTRACER_GPU_ADAPTIVE_MIN_SPP=<int >= 0>; it takes effect
         together with PATHTRACER_GPU_NOISE, whose value is then the block target."""
-        import os
-
-        env = os.environ if environ is None else environ
-        cfg = cls(enabled=env.get("PATHTRACER_GPU_ADAPTIVE", "").lower() in ("1", "true", "on", "yes"))
-        try:
-            i = int(env["PATHTRACER_GPU_ADAPTIVE_MIN_SPP"])
-            if i >= 0:
-                cfg.min_spp = i
-        except (KeyError, ValueError):
-            pass
-        return cfg
+        return cls(enabled=_env_on(environ, "PATHTRACER_GPU_ADAPTIVE"), min_spp=_env_int(environ, "PATHTRACER_GPU_ADAPTIVE_MIN_SPP", 0) or 0)
 
 
 @dataclass
@@ -922,10 +879,7 @@ class ShadingConfig:
     @classmethod
     def from_env(cls, environ=None) -> "ShadingConfig":
         """PATHTRACER_GPU_SHADING=gl (or cpu; case-insensitive, anything else is cpu), like the other PATHTRACER_GPU_* switches."""
-        import os
-
-        env = os.environ if environ is None else environ
-        v = env.get("PATHTRACER_GPU_SHADING", "").strip().lower()
+        v = (os.environ if environ is None else environ).get("PATHTRACER_GPU_SHADING", "").strip().lower()
         return cls(model=v if v in SHADING_MODELS else "cpu")
 
 

@@ -140,6 +140,76 @@ def test_png_encoder(host, tmp_path):
     assert b"create png" in host.pth_last_error()
 
 
+# every PATHTRACER_GPU_* variable set to the value -> what each *FromEnv of engine.hpp gives; the literals are the rules as they stood
+# before the parsers were written once (on/off: exactly 1 / true / on / yes in any case, no trimming; integers: the whole string
+# through strtol, in range; floats: the whole string through strtod -- which takes leading blanks and hex -- under the rule's predicate)
+_D = dict(fog=0, shading=0, noise=0.0, step=16, adaptive=0, min_spp=0, atrous=0, iters=5, features=-1, filtered=0.0, temporal=0, clip=0.0)
+_ON = dict(fog=1, adaptive=1, atrous=1, temporal=1)
+ENV_RULES = [
+    ("<unset>", _D), ("", _D), (" 1 ", _D), ("1 ", _D), ("7x", _D), ("inf", _D), ("nan", _D), ("-1", _D), ("1e309", _D), (" GL ", _D),
+    (" 1", dict(_D, noise=1.0, step=1, min_spp=1, iters=1, features=1, filtered=1.0, clip=1.0)),
+    ("1", dict(_D, **_ON, noise=1.0, step=1, min_spp=1, iters=1, features=1, filtered=1.0, clip=1.0)),
+    ("TRUE", dict(_D, **_ON)), ("On", dict(_D, **_ON)), ("yes", dict(_D, **_ON)), ("y", _D), ("GL", dict(_D, shading=1)), ("gl", dict(_D, shading=1)),
+    ("0", dict(_D, iters=0, features=0)),
+    ("7", dict(_D, noise=7.0, step=7, min_spp=7, features=7, filtered=7.0, clip=7.0)),
+    ("6", dict(_D, noise=6.0, step=6, min_spp=6, iters=6, features=6, filtered=6.0, clip=6.0)),
+    ("2.5", dict(_D, noise=2.5, filtered=2.5, clip=2.5)),
+    ("0x10", dict(_D, noise=16.0, filtered=16.0, clip=16.0)),
+    ("2147483647", dict(_D, noise=2147483647.0, step=2147483647, min_spp=2147483647, features=2147483647, filtered=2147483647.0, clip=2147483647.0)),
+    ("2147483648", dict(_D, noise=2147483648.0, filtered=2147483648.0, clip=2147483648.0)),  # 0x7fffffff + 1
+    ("1.7976931348623157e308", dict(_D, noise=1.7976931348623157e308, filtered=1.7976931348623157e308, clip=1.7976931348623157e308)),
+    ("-0", dict(_D, iters=0, features=0)),
+]
+
+
+def _probe_line(line):
+    label, rest = line[1:].split("] ", 1)
+    return label, {k: float(v) if k in ("noise", "filtered", "clip") else int(v) for k, v in (f.split("=") for f in rest.split())}
+
+
+@pytest.fixture(scope="module")
+def env_probe(tmp_path_factory):
+    import host_trace_support as hts
+
+    return hts.build_probe(str(tmp_path_factory.mktemp("host_env_probe")))
+
+
+def test_cpp_env_rules(env_probe):
+    r = subprocess.run([env_probe, "env", *[v for v, _ in ENV_RULES]], capture_output=True, text=True, check=True)
+    lines = r.stdout.split("\n")[:-1]
+    assert len(lines) == len(ENV_RULES)
+    for line, (value, want) in zip(lines, ENV_RULES):
+        label, got = _probe_line(line)
+        assert label == value and got == want, (value, got, want)
+
+
+def test_cpp_setters_clamp_and_fall_back_to_the_environment(env_probe):
+    r = subprocess.run([env_probe, "set"], capture_output=True, text=True, check=True)
+    got = dict(_probe_line(ln) for ln in r.stdout.split("\n")[:-1])
+    env1 = dict(fog=1, shading=0, noise=1.0, step=1, adaptive=1, min_spp=1, atrous=1, iters=1, features=1, filtered=1.0, temporal=1)
+    assert got["nothing set, environment 1"] == env1
+    assert got["nothing set, environment empty"] == {k: v for k, v in _D.items() if k != "clip"}
+    assert got["out of range over environment 1"] == dict(fog=0, shading=0, noise=0.0, step=16, adaptive=0, min_spp=0, atrous=0, iters=5, features=1,
+                                                          filtered=0.0, temporal=0)
+    assert got["in range over environment empty"] == dict(fog=1, shading=1, noise=0.25, step=3, adaptive=1, min_spp=2, atrous=1, iters=0, features=0,
+                                                          filtered=0.5, temporal=1)
+    assert got["NaN target, 6 iterations"] == dict(got["in range over environment empty"], noise=0.0, step=16, iters=6)
+
+
+def test_cpp_env_probe_is_clean_under_asan_and_ubsan(tmp_path, env_probe):
+    """Host code on the CPU: the same stand-alone program once more with the sanitizers, the env table and one frame against the fake."""
+    import host_trace_support as hts
+
+    exe = hts.build_probe(str(tmp_path), ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "host_env_probe_san")
+    args = ["env", *[v for v, _ in ENV_RULES]]
+    a = subprocess.run([exe, *args], capture_output=True, text=True, check=True)
+    assert a.stderr == "" and a.stdout == subprocess.run([env_probe, *args], capture_output=True, text=True, check=True).stdout
+    libs = hts.build_fakes(str(tmp_path), probe=False)
+    env = dict(os.environ, PTCORE_LIB=libs["full"], PATHTRACER_GPU_TEMPORAL="1", PATHTRACER_GPU_TEMPORAL_CLIP="2.5", PATHTRACER_GPU_NOISE="0.1")
+    b = subprocess.run([exe, "stats", hts.SIMPLE, "40", "1"], capture_output=True, text=True, cwd=ROOT, env=env)
+    assert b.returncode == 0 and b.stderr == "", b.stderr
+
+
 def _cli(*args):
     exe = os.path.join(ROOT, "path_trace_golang_amd", "render")
     return subprocess.run([exe, *args], capture_output=True, text=True, cwd=ROOT, timeout=120)

@@ -64,3 +64,61 @@ def test_render_into_with_progress(oracle, gpu_ctx):
     assert np.all(small == 5)
     L.pth_scene_free(h)
     L.pth_shutdown()
+
+
+# The stop rule of a frame, as both hosts read it from the environment.  The targets lie between the figures libptcore reports for
+# this frame (test_scene, 40x24, depth 4, seed 7) at 8 and at 12 samples -- frame noise 0.552 and 0.526, measured noise of the filtered
+# frame 0.391 and 0.355 -- so both rules end the frame at the third of four steps; at block target 0.7 some 8x8 blocks stop after the
+# first step and the last ones later.
+HOST_RULES = {
+    "plain": {},
+    "noise": {"PATHTRACER_GPU_NOISE": "0.54", "PATHTRACER_GPU_NOISE_STEP": "4"},
+    "adaptive": {"PATHTRACER_GPU_NOISE": "0.7", "PATHTRACER_GPU_NOISE_STEP": "4", "PATHTRACER_GPU_ADAPTIVE": "1"},
+    "filtered": {"PATHTRACER_GPU_ATROUS": "1", "PATHTRACER_GPU_FILTERED_NOISE": "0.37", "PATHTRACER_GPU_NOISE_STEP": "4"},
+}
+
+
+def test_cpp_and_python_hosts_make_the_same_frame_under_every_stop_rule(gpu_ctx, monkeypatch):
+    """One process, 40x24 (more than one tile row of 8x8 blocks), depth 4, cap 16 spp: under each stop rule the frame through
+    pth_render_into and the frame through engine.render_into, both with a counting progress callback, are the same bytes after the
+    same number of callbacks.  Exact: both hosts make the same calls to the same library."""
+    from path_trace_golang_amd import engine, scene
+
+    L = C.CDLL(os.path.join(ROOT, "path_trace_golang_amd", "libpthost.so"))
+    L.pth_last_error.restype = C.c_char_p
+    L.pth_scene_load.restype = C.c_void_p
+    L.pth_scene_load.argtypes = [C.c_char_p]
+    L.pth_scene_free.argtypes = [C.c_void_p]
+    L.pth_render_into.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p,
+                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    L.pth_set_backend(1)
+    for k in os.environ:
+        if k.startswith("PATHTRACER_GPU_"):
+            monkeypatch.delenv(k)
+    w, hh, spp, depth, seed = 40, 24, 16, 4, 7
+    h = L.pth_scene_load(scene_path("test_scene").encode())
+    sc = scene.load(scene_path("test_scene"))
+    counts = {}
+    try:
+        for rule, env in HOST_RULES.items():
+            with monkeypatch.context() as m:
+                for k, v in env.items():
+                    m.setenv(k, v)
+                calls = []
+                cb = C.CFUNCTYPE(None)(lambda: calls.append(1))
+                cpp = np.zeros((hh, w, 4), np.uint8)
+                rc = L.pth_render_into(h, w, hh, spp, depth, seed, cpp.ctypes.data_as(C.c_void_p), w, hh, w * 4, C.cast(cb, C.c_void_p))
+                assert rc == 0, (rule, L.pth_last_error())
+                py_calls = []
+                py = engine.new_image(w, hh)
+                engine.render_into(sc, engine.RenderConfig(w, hh, spp, depth, seed), py, lambda: py_calls.append(1))
+            counts[rule] = (len(calls), len(py_calls))
+            print("host rule %s: %d callbacks through pth_render_into, %d through engine.render_into, %d differing bytes"
+                  % (rule, len(calls), len(py_calls), int(np.count_nonzero(cpp != py))))
+            assert len(calls) == len(py_calls) and len(calls) >= 2, rule
+            assert np.array_equal(cpp, py), rule
+    finally:
+        L.pth_scene_free(h)
+        L.pth_shutdown()
+    assert counts["plain"] == (17, 17)  # 16 / 10 = 1 sample per step, and once at the end
+    assert counts["noise"] == (4, 4) and counts["filtered"] == (4, 4)  # three steps and once at the end: stopped before the cap
