@@ -25,6 +25,7 @@ import (
 	"image"
 	"math"
 	"os"
+	"reflect"
 	"runtime"
 	"strconv"
 	"strings"
@@ -60,16 +61,21 @@ var (
 	adaptiveMinSpp int
 	lastAdaptive   AdaptiveState // pt_adaptive_state of the last frame (zero unless it was adaptive)
 
-	atrousSet   bool // false: PATHTRACER_GPU_ATROUS / PATHTRACER_GPU_ATROUS_ITERS decide
-	atrousOn    bool
-	atrousIters = 5
-	featuresK   = -1         // -1: not said, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows)
-	lastAtrous  AtrousStats // pt_atrous_stats of the last frame (zero unless it was filtered)
-	temporalSet bool        // false: PATHTRACER_GPU_TEMPORAL decides
-	temporalOn  bool
+	atrousSet    bool // false: PATHTRACER_GPU_ATROUS / PATHTRACER_GPU_ATROUS_ITERS decide
+	atrousOn     bool
+	atrousIters  = 5
+	featuresK    = -1        // -1: not said, PATHTRACER_GPU_FEATURES decides (and without it: 4 under the filter where the scene allows)
+	lastAtrous   AtrousStats // pt_atrous_stats of the last frame (zero unless it was filtered)
+	temporalSet  bool        // false: PATHTRACER_GPU_TEMPORAL decides
+	temporalOn   bool
 	lastTemporal TemporalStats // pt_temporal_stats of the last frame (zero unless it was accumulated)
 	clipSet      bool          // false: PATHTRACER_GPU_TEMPORAL_CLIP decides
 	clipGamma    float64
+	motionSet    bool // false: PATHTRACER_GPU_TEMPORAL_MOTION decides
+	motionOn     bool
+	idsOn        bool           // pt_set_object_ids(1) was the last thing said to the context
+	accumulated  *scene.Scene   // a copy of the scene of the last frame accumulated with displaced reprojection on (nil: none)
+	lastMotion   TemporalMotion // pt_temporal_motion_stats of the last frame (zero unless it was accumulated with the rule on)
 
 	filteredSet    bool        // false: PATHTRACER_GPU_FILTERED_NOISE decides
 	filteredTarget float64     // the noise target on the filtered frame (0 = off)
@@ -115,6 +121,7 @@ func SetDevices(n int) {
 	if ctx != nil {
 		C.pt_destroy(ctx)
 		ctx = nil
+		idsOn, accumulated = false, nil
 	}
 	initErr = nil
 	if n > 0 {
@@ -236,6 +243,7 @@ func ResetTemporal() error {
 	}
 	runtime.LockOSThread()
 	defer runtime.UnlockOSThread()
+	accumulated = nil
 	if rc := C.pt_temporal_reset(ctx); rc != C.PT_OK {
 		return lastError("pt_temporal_reset")
 	}
@@ -283,6 +291,84 @@ func TemporalClipStats() (TemporalClip, error) {
 		return TemporalClip{}, lastError("pt_temporal_clip_stats")
 	}
 	return TemporalClip{Gamma: float64(cs.gamma), Clipped: uint64(cs.clipped), Reprojected: uint64(cs.reprojected)}, nil
+}
+
+// TemporalMotion mirrors struct pt_temporal_motion_stats, and says whether the history was reset before the frame because more than
+// positions and the camera had changed.
+type TemporalMotion struct {
+	Objects                 int // the length of the table the frame ran with; 0 = without one
+	Moved, MovedReprojected uint64
+	Reset                   bool
+}
+
+// SetTemporalMotion turns displaced reprojection on (pt_temporal_set_motion, DESIGN 3.13b), for an editor whose user drags objects.
+// Read by Render when the accumulation is on: the frame records the object index plane (pt_set_object_ids), Render remembers the
+// scene of the last frame it accumulated and compares the next one with it -- when only object positions and the camera differ, the
+// displacements go to pt_temporal (nothing is passed when none is non-zero); when anything else differs the history is reset
+// first.  Not set: PATHTRACER_GPU_TEMPORAL_MOTION decides.
+func SetTemporalMotion(on bool) {
+	mu.Lock()
+	defer mu.Unlock()
+	motionSet, motionOn = true, on
+}
+
+// LastTemporalMotion reports the rule's figures for the last frame Render finished (the zero value unless the rule was in force).
+func LastTemporalMotion() TemporalMotion {
+	mu.Lock()
+	defer mu.Unlock()
+	return lastMotion
+}
+
+// motionRule: whether displaced reprojection is in force (SetTemporalMotion, else the environment); only under the accumulation.
+func motionRule() bool {
+	if !temporalRule() {
+		return false
+	}
+	if motionSet {
+		return motionOn
+	}
+	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_TEMPORAL_MOTION"))) {
+	case "1", "true", "on", "yes":
+		return true
+	}
+	return false
+}
+
+// copyScene: what sceneMotion compares, detached from the caller's scene (which the editor edits in place).
+func copyScene(sc *scene.Scene) *scene.Scene {
+	c := *sc
+	c.Materials = append(c.Materials[:0:0], sc.Materials...)
+	c.Objects = append(c.Objects[:0:0], sc.Objects...)
+	if sc.Sky != nil {
+		sky := *sc.Sky
+		c.Sky = &sky
+	}
+	if sc.Fog != nil {
+		fog := *sc.Fog
+		c.Fog = &fog
+	}
+	return &c
+}
+
+// sceneMotion: delta [n][3], cur's object positions minus prev's, when the two scenes differ in object positions and the camera
+// only; ok = false when anything else differs -- the number, order, type, size or material of the objects, the material table,
+// sky, background or fog.
+func sceneMotion(prev, cur *scene.Scene) (delta []C.double, ok bool) {
+	if len(prev.Objects) != len(cur.Objects) || !reflect.DeepEqual(prev.Materials, cur.Materials) ||
+		!reflect.DeepEqual(prev.Sky, cur.Sky) || !reflect.DeepEqual(prev.Fog, cur.Fog) || prev.Background != cur.Background {
+		return nil, false
+	}
+	delta = make([]C.double, 3*len(cur.Objects))
+	for i := range cur.Objects {
+		a, b := prev.Objects[i], cur.Objects[i]
+		if a.Type != b.Type || a.MaterialID != b.MaterialID || a.Size != b.Size {
+			return nil, false
+		}
+		delta[3*i] = C.double(b.Position.X - a.Position.X)
+		delta[3*i+1] = C.double(b.Position.Y - a.Position.Y)
+		delta[3*i+2] = C.double(b.Position.Z - a.Position.Z)
+	}
+	return delta, true
 }
 
 // clipRule: the gamma in force (SetTemporalClip, else PATHTRACER_GPU_TEMPORAL_CLIP; unset or not a finite number >= 0: off).
@@ -628,6 +714,7 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 	defer runtime.UnlockOSThread()
 	lastAtrous = AtrousStats{}
 	lastTemporal = TemporalStats{}
+	lastMotion = TemporalMotion{}
 	if _, iters := atrousRule(); temporalRule() && ctx != nil && img.Bounds().Dx() == cfg.Width && img.Bounds().Dy() == cfg.Height {
 		// the frame blended into the context's reprojected history, then filtered, takes the place of the plain finish
 		ac := C.pt_atrous_config{iterations: C.int32_t(iters), sigma_l: 4, sigma_n: 0.1, sigma_z: 0.1, sigma_a: 0.2}
@@ -636,6 +723,25 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 		if rc := C.pt_temporal_set_clip(ctx, C.double(clipRule())); rc != C.PT_OK {
 			return lastError("pt_temporal_set_clip")
 		}
+		motion, table := motionRule(), false
+		if motion && accumulated != nil { // the host rule of displaced reprojection (DESIGN 3.13b)
+			delta, ok := sceneMotion(accumulated, sc)
+			moved := false
+			for _, d := range delta {
+				moved = moved || d != 0
+			}
+			if !ok {
+				lastMotion.Reset = true
+				if rc := C.pt_temporal_reset(ctx); rc != C.PT_OK {
+					return lastError("pt_temporal_reset")
+				}
+			} else if moved { // (a Go slice of C.double holds no Go pointers: it may be passed directly)
+				if rc := C.pt_temporal_set_motion(ctx, &delta[0], C.int32_t(len(delta)/3)); rc != C.PT_OK {
+					return lastError("pt_temporal_set_motion")
+				}
+				table = true
+			}
+		}
 		if rc := C.pt_temporal(ctx, tc, &ac, (*C.uint8_t)(unsafe.Pointer(&img.Pix[0])), C.int32_t(img.Stride), nil, nil, &st); rc != C.PT_OK {
 			return lastError("pt_temporal")
 		}
@@ -643,6 +749,17 @@ func Render(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress func())
 			Reprojected: uint64(st.reprojected), Disoccluded: uint64(st.disoccluded), BadPixels: uint64(st.bad_pixels),
 			MeanLen: float64(st.mean_len), NoiseBefore: float64(st.noise_before), NoiseBlended: float64(st.noise_blended),
 			NoiseAfter: float64(st.noise_after)}
+		accumulated = nil // (a frame accumulated without the rule is not what the next table is against)
+		if table {
+			var ms C.struct_pt_temporal_motion_stats
+			if rc := C.pt_temporal_motion_stats(ctx, &ms); rc != C.PT_OK {
+				return lastError("pt_temporal_motion_stats")
+			}
+			lastMotion.Objects, lastMotion.Moved, lastMotion.MovedReprojected = int(ms.objects), uint64(ms.moved), uint64(ms.moved_reprojected)
+		}
+		if motion {
+			accumulated = copyScene(sc)
+		}
 		if progress != nil {
 			progress()
 		}
@@ -712,6 +829,16 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 	}
 	if rc := C.pt_set_features(ctx, C.int32_t(featuresRule(sc, atrous))); rc != C.PT_OK {
 		return lastError("pt_set_features")
+	}
+	if motion := motionRule(); motion != idsOn { // (said only when the switch changes: with it never on, the calls are what they were)
+		var ids C.int32_t
+		if motion {
+			ids = 1
+		}
+		if rc := C.pt_set_object_ids(ctx, ids); rc != C.PT_OK {
+			return lastError("pt_set_object_ids")
+		}
+		idsOn = motion
 	}
 	var on C.int32_t
 	if toNoise || atrous { // the filter reads the second moments

@@ -441,6 +441,17 @@ int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp);
  *                             boxes) and with GL shading (pt_set_shading).
  *   pt_read_features        : normal / albedo / depth = width*height*3 doubles each, row-major, any of them NULL.  Valid exactly
  *                             when pt_read_moments is (so the frame collects moments); PT_ERR_STATE otherwise and for a frame with k = 0.
+ *   pt_set_object_ids(ctx, on) : default 0; PT_ERR_STATE while a frame is open.  Later frames on ctx with features on (k > 0) also
+ *                             record, per in-frame pixel, the index into pt_scene.objects (file order) of the first hit of the pixel's
+ *                             sample 0, or -1 on a miss: the hit that sample's normal, albedo and depth come from, the same test
+ *                             and the same winner.  An object of unknown type keeps its index and is never hit.  With injected
+ *                             primary rays the id is that of the injected ray, as the features are.  4 B per pixel on the devices,
+ *                             outside PTCORE_L_BUDGET_MB, allocated on the first frame that asks.  A frame with ids on and k = 0 is
+ *                             PT_ERR_INVALID before anything is launched (the context stays usable); the BVH and GL-shading refusals
+ *                             are the features' own.  pt_render_tiles_device neither collects nor fails.  For picking, and for
+ *                             pt_temporal_set_motion below.
+ *   pt_read_object_ids      : ids = width*height int32, row-major.  Valid exactly when pt_read_features is and the frame recorded
+ *                             ids; PT_ERR_STATE otherwise.  Gathered on devices[0] like the sample counts.
  *
  * Variance-guided a-trous filter on linear radiance (additive to ABI 4; the model and its order of evaluation are
  * stated in csrc/pt_atrous.h).  With c = S / n the pixel's mean and var the variance of that mean (the (v_r + v_g + v_b) / 3 of
@@ -482,6 +493,8 @@ typedef struct pt_atrous_stats {
 
 int32_t pt_set_features(pt_ctx *ctx, int32_t k);
 int32_t pt_read_features(pt_ctx *ctx, double *normal, double *albedo, double *depth);
+int32_t pt_set_object_ids(pt_ctx *ctx, int32_t on);
+int32_t pt_read_object_ids(pt_ctx *ctx, int32_t *ids);
 int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32_t stride, double *mean, double *var,
                   pt_atrous_stats *stats);
 
@@ -564,7 +577,8 @@ int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean,
  *   pt_temporal_reset : empties the history (after a scene edit, a cut).  The history is also empty after pt_create and is dropped
  *                       by a call whose width x height differs from the history's.
  * The history is keyed by geometry alone: moving or edited objects are caught only by the distance, normal and albedo tests, so
- * the caller resets after an edit.  Known limit: ghosting of view-dependent content.  Where what is seen at a pixel changes while
+ * the caller resets after an edit -- or, where the edit moved objects and nothing else, passes their displacements
+ * (pt_temporal_set_motion below).  Known limit: ghosting of view-dependent content.  Where what is seen at a pixel changes while
  * its first-hit normal, distance and albedo still agree (a reflection, a refraction, a moving shadow edge), every tap passes and the
  * history overrules the frame with another view's radiance; on test_scene that costs more than the history gains.
  * The answer is the clip below.  (Firefly rejection in the frame is not done; the test sequences contain no firefly.)
@@ -580,6 +594,30 @@ int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean,
  *                            whose history the clip changed (0 when it ran with the clip off).  PT_ERR_STATE while the history is
  *                            empty.  The struct shares its name with the function: write `struct pt_temporal_clip_stats`.
  * Every refusal leaves the context and the history as they were.
+ *
+ * Displaced reprojection (additive to ABI 4; step 4a of csrc/pt_temporal.h): for an editor whose user drags objects.
+ * A half-pixel move of an object passes the distance, normal and albedo tests, so without this the history of the place where the
+ * object was is blended into the place where it is.  The scene schema has positions and sizes and no rotations: a translation per
+ * object is every edit of geometry short of a resize.
+ *   pt_temporal_set_motion   : delta = [num_objects][3] doubles: for object i of pt_scene.objects, its position in the frame about to
+ *                              be accumulated minus its position in the frame the history was stored from.  The table is copied.
+ *                              NULL or 0 clears it.  A NaN or infinite entry, or num_objects < 0, is PT_ERR_INVALID.  (A table
+ *                              that cannot be held is PT_ERR_NOMEM and leaves the pending one as it was.)  ONE-SHOT: the
+ *                              table is consumed by the next pt_temporal that succeeds, also when that call finds the history empty;
+ *                              a refused pt_temporal leaves it set, pt_temporal_reset drops it.  With a table pending, pt_temporal is
+ *                              refused with PT_ERR_STATE when the frame recorded no object ids (pt_set_object_ids) and with
+ *                              PT_ERR_INVALID when num_objects differs from the frame's scene.  On a pixel whose sample 0 hit object o
+ *                              with delta[o] != 0 the point that is projected into the previous frame is the hit point minus
+ *                              delta[o]; everything else -- taps, tests, clip, blend, the stored history -- is unchanged, and an
+ *                              all-zero table gives the bits of no table.  RECOMMENDED with it: the clip at 2.5, since the radiance on
+ *                              and near a moved object changes (its reflections, its shadow).  Limits: the id is sample 0's while
+ *                              normal, albedo and depth are means over k samples, so silhouette pixels are left to the tap tests;
+ *                              the strip an object uncovers is disoccluded and starts at len 1; resizes, material edits and sky
+ *                              edits are not motion -- reset.
+ *   pt_temporal_motion_stats : of the last pt_temporal that succeeded: objects = the table's length (0: it ran without one), moved =
+ *                              good hit pixels whose object had a non-zero delta, moved_reprojected = those of them that found
+ *                              history.  PT_ERR_STATE while the history is empty.  The struct shares its name with the function.
+ * Every refusal leaves the context, the history and the table as they were.
  */
 typedef struct pt_temporal_config {
     double alpha;         /* 0..1: the least weight of the current frame */
@@ -616,6 +654,16 @@ struct pt_temporal_clip_stats {
 
 int32_t pt_temporal_set_clip(pt_ctx *ctx, double gamma);
 int32_t pt_temporal_clip_stats(pt_ctx *ctx, struct pt_temporal_clip_stats *out);
+
+struct pt_temporal_motion_stats {
+    int32_t objects;      /* the length of the table the call ran with; 0 = without one */
+    int32_t reserved;
+    uint64_t moved;       /* good hit pixels whose object had a non-zero delta */
+    uint64_t moved_reprojected;
+};
+
+int32_t pt_temporal_set_motion(pt_ctx *ctx, const double *delta, int32_t num_objects);
+int32_t pt_temporal_motion_stats(pt_ctx *ctx, struct pt_temporal_motion_stats *out);
 
 /*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the

@@ -149,6 +149,13 @@ class PtTemporalClipStats(C.Structure):  # struct pt_temporal_clip_stats: of the
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PtTemporalMotionStats(C.Structure):  # struct pt_temporal_motion_stats: of the last pt_temporal that succeeded
+    _fields_ = [("objects", C.c_int32), ("reserved", C.c_int32), ("moved", C.c_uint64), ("moved_reprojected", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class PtTemporalStats(C.Structure):  # pt_temporal_stats
     _fields_ = [("temporal_ms", C.c_double), ("launches", C.c_int32), ("iterations", C.c_int32), ("reprojected", C.c_uint64),
                 ("disoccluded", C.c_uint64), ("bad_pixels", C.c_uint64), ("mean_len", C.c_double), ("noise_before", C.c_double),
@@ -211,6 +218,8 @@ SYMBOLS = [
     ("pt_read_sample_counts", C.c_int32, [_vp, C.POINTER(C.c_uint32)]),
     ("pt_set_features", C.c_int32, [_vp, C.c_int32]),                     # additive to ABI 4 (see has())
     ("pt_read_features", C.c_int32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("pt_set_object_ids", C.c_int32, [_vp, C.c_int32]),                   # additive to ABI 4 (see has())
+    ("pt_read_object_ids", C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     ("pt_atrous", C.c_int32, [_vp, C.POINTER(PtAtrousConfig), _vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(PtAtrousStats)]),
     ("pt_set_halves", C.c_int32, [_vp, C.c_int32]),                       # additive to ABI 4 (see has())
@@ -223,6 +232,8 @@ SYMBOLS = [
     ("pt_temporal_reset", C.c_int32, [_vp]),
     ("pt_temporal_set_clip", C.c_int32, [_vp, C.c_double]),
     ("pt_temporal_clip_stats", C.c_int32, [_vp, C.POINTER(PtTemporalClipStats)]),
+    ("pt_temporal_set_motion", C.c_int32, [_vp, C.POINTER(C.c_double), C.c_int32]),
+    ("pt_temporal_motion_stats", C.c_int32, [_vp, C.POINTER(PtTemporalMotionStats)]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
@@ -266,7 +277,8 @@ def load():
 ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_rays", "pt_set_moments", "pt_read_moments",
             "pt_noise_estimate", "pt_set_adaptive", "pt_adaptive_state", "pt_read_sample_counts", "pt_set_features",
             "pt_read_features", "pt_atrous", "pt_set_halves", "pt_read_halves", "pt_atrous_halves", "pt_temporal", "pt_temporal_read",
-            "pt_temporal_reset", "pt_temporal_set_clip", "pt_temporal_clip_stats")  # added within ABI 4: detected by presence
+            "pt_temporal_reset", "pt_temporal_set_clip", "pt_temporal_clip_stats", "pt_set_object_ids", "pt_read_object_ids",
+            "pt_temporal_set_motion", "pt_temporal_motion_stats")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:

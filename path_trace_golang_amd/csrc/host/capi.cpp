@@ -149,6 +149,11 @@ int pth_save_png(const char *path, const uint8_t *pix, int32_t width, int32_t he
     }
 }
 
+// engine::hip::SetDevices: the HIP ordinals later frames render on; the process-wide context is dropped
+void pth_set_devices(const int32_t *ordinals, int32_t n) {
+    pthost::engine::hip::SetDevices(std::vector<int>(ordinals, ordinals + (ordinals && n > 0 ? n : 0)));
+}
+
 void pth_shutdown(void) { pthost::engine::hip::Shutdown(); }
 
 }  // extern "C"

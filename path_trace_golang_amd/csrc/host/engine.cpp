@@ -2,6 +2,7 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cctype>
 #include <cerrno>
 #include <cmath>
@@ -57,7 +58,8 @@ namespace {
     REQUIRED(pt_begin) REQUIRED(pt_step) REQUIRED(pt_read) REQUIRED(pt_end) REQUIRED(pt_set_fog)                                 \
     OPTIONAL(pt_set_shading) OPTIONAL(pt_set_moments) OPTIONAL(pt_noise_estimate) OPTIONAL(pt_set_adaptive)                      \
     OPTIONAL(pt_adaptive_state) OPTIONAL(pt_set_features) OPTIONAL(pt_atrous) OPTIONAL(pt_set_halves) OPTIONAL(pt_atrous_halves) \
-    OPTIONAL(pt_temporal) OPTIONAL(pt_temporal_reset) OPTIONAL(pt_temporal_set_clip) OPTIONAL(pt_temporal_clip_stats)
+    OPTIONAL(pt_temporal) OPTIONAL(pt_temporal_reset) OPTIONAL(pt_temporal_set_clip) OPTIONAL(pt_temporal_clip_stats)           \
+    OPTIONAL(pt_set_object_ids) OPTIONAL(pt_temporal_set_motion) OPTIONAL(pt_temporal_motion_stats)
 
 struct Core {
     void *handle = nullptr;
@@ -68,7 +70,7 @@ struct Core {
 };
 
 // What a frame setting needs from the library beyond the required entry points, and what Render answers when it is not there.
-enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE };
+enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION };
 const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_shading != nullptr; }, "GL shading: libptcore.so lacks pt_set_shading"},
     {[](const Core &c) { return c.pt_set_moments && c.pt_noise_estimate; }, "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate"},
@@ -78,13 +80,15 @@ const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_halves && c.pt_atrous_halves; }, "filtered noise target: libptcore.so lacks pt_set_halves / pt_atrous_halves"},
     {[](const Core &c) { return c.pt_set_features != nullptr; }, "features: libptcore.so lacks pt_set_features"},
     {[](const Core &c) { return c.pt_set_adaptive && c.pt_adaptive_state; }, "adaptive sampling: libptcore.so lacks pt_set_adaptive / pt_adaptive_state"},
+    {[](const Core &c) { return c.pt_set_object_ids && c.pt_temporal_set_motion && c.pt_temporal_motion_stats && c.pt_temporal_reset; },
+     "temporal motion: libptcore.so lacks pt_set_object_ids / pt_temporal_set_motion"},
 };
 
 // What the Set* calls said; an empty field leaves the matter to the environment (the *FromEnv rules).
 struct NoiseRule { double target; int step; };
 struct Switch { bool on; int n; };  // adaptive + min_spp, a-trous + iterations
 struct Settings {
-    std::optional<bool> fog, temporal;
+    std::optional<bool> fog, temporal, temporal_motion;
     std::optional<int> shading, features;
     std::optional<NoiseRule> noise;
     std::optional<Switch> adaptive, atrous;
@@ -279,9 +283,13 @@ void FlattenScene(const scene::Scene &sc, std::vector<pt_material> &materials, s
 
 namespace hip {
 
+namespace {
+void drop_context();  // destroys the process-wide context and forgets what was said to it (defined beside that state, below)
+}
+
 void SetDevices(const std::vector<int> &ordinals) {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx && g_core.handle) { g_core.pt_destroy(g_ctx); g_ctx = nullptr; }
+    drop_context();
     g_devices = ordinals;
 }
 
@@ -303,6 +311,7 @@ int FeaturesFromEnv() { return env_int("PATHTRACER_GPU_FEATURES", 0, 0x7fffffffL
 double FilteredNoiseFromEnv() { return env_double("PATHTRACER_GPU_FILTERED_NOISE", positive_finite, 0); }
 bool TemporalFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL"); }
 double TemporalClipFromEnv() { return env_double("PATHTRACER_GPU_TEMPORAL_CLIP", finite_not_negative, 0); }
+bool TemporalMotionFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL_MOTION"); }
 
 namespace {
 
@@ -315,6 +324,7 @@ struct FramePlan {
     Switch atrous;        // on also under temporal accumulation, which brings the filter with it
     bool temporal;
     double clip;          // > 0 only under temporal accumulation
+    bool motion;          // displaced reprojection: on only under temporal accumulation
     double filtered;      // > 0 only under the filter
     int features;
     bool moments, halves;
@@ -346,6 +356,7 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
     p.atrous = atrous_switch(s);
     p.temporal = s.temporal.value_or(TemporalFromEnv());
     p.clip = p.temporal ? s.temporal_clip.value_or(TemporalClipFromEnv()) : 0;
+    p.motion = p.temporal && s.temporal_motion.value_or(TemporalMotionFromEnv());
     p.atrous.on = p.atrous.on || p.temporal;
     p.filtered = p.atrous.on ? s.filtered_noise.value_or(FilteredNoiseFromEnv()) : 0;
     p.features = s.features.value_or(FeaturesFromEnv());
@@ -366,6 +377,54 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
     p.moments = p.noise.target > 0 || p.atrous.on;
     p.halves = p.filtered > 0;
     return p;
+}
+
+// The scene of the last frame Render accumulated with displaced reprojection on: what scene_motion compares.
+struct AccumulatedScene {
+    bool valid = false;
+    std::vector<pt_material> materials;
+    std::vector<pt_object> objects;
+    pt_sky sky;
+    bool has_fog = false;
+    pt_fog fog;
+};
+AccumulatedScene g_accumulated;
+bool g_object_ids_on = false;  // pt_set_object_ids(1) was the last thing said to the context
+
+// Both belong to the context: a new one has object ids off and an empty history.  Called with g_mu held.
+void drop_context() {
+    if (g_ctx && g_core.handle) g_core.pt_destroy(g_ctx);
+    g_ctx = nullptr;
+    g_accumulated.valid = false;
+    g_object_ids_on = false;
+}
+
+void remember(const scene::Scene &sc, const Flat &flat, AccumulatedScene &a) {
+    a.valid = true;
+    a.materials = flat.materials;
+    a.objects = flat.objects;
+    a.sky = flat.sc.sky;
+    a.has_fog = sc.FogPtr != nullptr;
+    std::memset(&a.fog, 0, sizeof a.fog);
+    if (sc.FogPtr) FlattenFog(*sc.FogPtr, a.fog);
+}
+
+// What moved between the remembered scene and this one: true and delta [n][3] (this frame's position minus the remembered one)
+// when the two differ in object positions and the camera only; false when anything else differs -- the number, order, type, size
+// or material of the objects, the material table, sky, background or fog.
+bool scene_motion(const AccumulatedScene &a, const scene::Scene &sc, const Flat &flat, std::vector<double> &delta) {
+    AccumulatedScene b;
+    remember(sc, flat, b);
+    if (a.objects.size() != b.objects.size() || a.materials.size() != b.materials.size() || a.has_fog != b.has_fog) return false;
+    if (std::memcmp(&a.sky, &b.sky, sizeof a.sky) || std::memcmp(&a.fog, &b.fog, sizeof a.fog)) return false;
+    if (!a.materials.empty() && std::memcmp(a.materials.data(), b.materials.data(), a.materials.size() * sizeof(pt_material))) return false;
+    delta.assign(3 * a.objects.size(), 0.0);
+    for (size_t i = 0; i < a.objects.size(); i++) {
+        const pt_object &x = a.objects[i], &y = b.objects[i];
+        if (x.type != y.type || x.material != y.material || std::memcmp(x.size, y.size, sizeof x.size)) return false;
+        for (int k = 0; k < 3; k++) delta[3 * i + (size_t)k] = y.position[k] - x.position[k];
+    }
+    return true;
 }
 
 // How the stepping loop of a frame advances and what ends it before the cap.
@@ -451,6 +510,7 @@ bool Temporal() {
 void ResetTemporal() {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_ctx && g_core.pt_temporal_reset) (void)g_core.pt_temporal_reset(g_ctx);
+    g_accumulated.valid = false;
 }
 void SetTemporalClip(double gamma) {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -465,6 +525,14 @@ bool TemporalClipStats(double &gamma, uint64_t &clipped, uint64_t &reprojected) 
     reprojected = cs.reprojected;
     return true;
 }
+void SetTemporalMotion(bool on) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_set.temporal_motion = on;
+}
+bool TemporalMotion() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_set.temporal_motion.value_or(TemporalMotionFromEnv());
+}
 void SetFeatures(int k) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (k >= 0) g_set.features = k;
@@ -477,8 +545,7 @@ int GetFeatures() {
 
 void Shutdown() {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx && g_core.handle) g_core.pt_destroy(g_ctx);
-    g_ctx = nullptr;
+    drop_context();
 }
 
 std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, const std::function<void()> &progress,
@@ -520,6 +587,7 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (lacks(to_noise, NOISE_TARGET)) return missing;
     if (lacks(p.temporal, TEMPORAL)) return missing;
     if (lacks(p.clip > 0, TEMPORAL_CLIP)) return missing;
+    if (lacks(p.motion, TEMPORAL_MOTION)) return missing;
     if (lacks(p.atrous.on, ATROUS)) return missing;
     if (to_filtered && to_noise) return "filtered noise target: excludes a frame noise target (-noise) and adaptive sampling: one stop rule per frame";
     if (to_filtered && gl) return "filtered noise target: not available with GL shading";
@@ -527,6 +595,10 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (g_core.pt_set_halves && failed(PT_CALL(pt_set_halves, g_ctx, p.halves ? 1 : 0))) return err;
     if (lacks(p.features > 0, FEATURES)) return missing;
     if (g_core.pt_set_features && failed(PT_CALL(pt_set_features, g_ctx, p.features))) return err;
+    if (p.motion != g_object_ids_on) {  // (said only when the switch changes: with it never on, the calls are what they were)
+        if (failed(PT_CALL(pt_set_object_ids, g_ctx, p.motion ? 1 : 0))) return err;
+        g_object_ids_on = p.motion;
+    }
     if (g_core.pt_set_moments && failed(PT_CALL(pt_set_moments, g_ctx, p.moments ? 1 : 0))) return err;
     if (lacks(p.adaptive.on, ADAPTIVE)) return missing;
     if (g_core.pt_set_adaptive) {
@@ -602,10 +674,26 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     std::memset(&tst, 0, sizeof tst);
     struct pt_temporal_clip_stats tcs;
     std::memset(&tcs, 0, sizeof tcs);
+    struct pt_temporal_motion_stats tms;
+    std::memset(&tms, 0, sizeof tms);
+    bool motion_reset = false, motion_table = false;
     if (p.temporal && err.empty()) {  // the frame blended into the context's reprojected history, then filtered
         if (g_core.pt_temporal_set_clip) err = PT_CALL(pt_temporal_set_clip, g_ctx, p.clip);
+        if (p.motion && err.empty() && g_accumulated.valid) {  // the host rule of displaced reprojection
+            std::vector<double> delta;
+            if (!scene_motion(g_accumulated, sc, flat, delta)) {
+                err = PT_CALL(pt_temporal_reset, g_ctx);
+                motion_reset = true;
+            } else if (std::any_of(delta.begin(), delta.end(), [](double d) { return d != 0.0; })) {
+                err = PT_CALL(pt_temporal_set_motion, g_ctx, delta.data(), (int32_t)(delta.size() / 3));
+                motion_table = true;
+            }
+        }
         if (err.empty()) err = PT_CALL(pt_temporal, g_ctx, nullptr, &filter, img.Pix.data(), img.Stride, nullptr, nullptr, &tst);
         if (err.empty() && p.clip > 0) err = PT_CALL(pt_temporal_clip_stats, g_ctx, &tcs);
+        if (err.empty() && motion_table) err = PT_CALL(pt_temporal_motion_stats, g_ctx, &tms);
+        if (err.empty() && p.motion) remember(sc, flat, g_accumulated);
+        if (!p.motion) g_accumulated.valid = false;  // (frames accumulated without the rule are not what the next table is against)
         ats.atrous_ms = tst.temporal_ms;
         ats.noise_before = tst.noise_before;
         ats.noise_after = tst.noise_after;
@@ -626,6 +714,10 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         stats->noise_blended = tst.noise_blended;
         stats->temporal_clip = tcs.gamma;
         stats->clipped = tcs.clipped;
+        stats->motion_objects = tms.objects;
+        stats->moved = tms.moved;
+        stats->moved_reprojected = tms.moved_reprojected;
+        stats->motion_reset = motion_reset;
         stats->to_filtered_noise = to_filtered;
         stats->filtered_noise = hs.noise;
         stats->noise_model = hs.noise_model;

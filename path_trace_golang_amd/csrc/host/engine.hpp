@@ -49,6 +49,11 @@ struct Stats {
     double temporal_ms = 0, mean_len = 0, noise_blended = 0;
     double temporal_clip = 0;  // gamma of the history clip the frame ran with (SetTemporalClip; 0 = off)
     uint64_t clipped = 0;      // pt_temporal_clip_stats of the frame: reprojected pixels whose history the clip changed
+    // displaced reprojection (SetTemporalMotion): pt_temporal_motion_stats of the frame (motion_objects 0: it ran without a table),
+    // and whether the history was reset before it because more than positions and the camera had changed
+    int motion_objects = 0;
+    uint64_t moved = 0, moved_reprojected = 0;
+    bool motion_reset = false;
 };
 
 namespace hip {
@@ -115,6 +120,15 @@ double TemporalClipFromEnv();  // PATHTRACER_GPU_TEMPORAL_CLIP = finite float >=
 // pt_temporal_clip_stats of the process-wide context: the gamma, the clipped and the reprojected pixels of the last accumulated
 // frame.  False while the history is empty (or the library lacks the entry point).
 bool TemporalClipStats(double &gamma, uint64_t &clipped, uint64_t &reprojected);
+// Displaced reprojection (pt_temporal_set_motion), for an editor whose user drags objects.  Read by Render when the
+// accumulation is on: the frame records the object index plane (pt_set_object_ids), Render remembers the scene of the last frame it
+// accumulated and compares the next one with it -- when only object positions and the camera differ, the displacements go to
+// pt_temporal (nothing is passed when none is non-zero); when anything else differs (the number, order, type, size or material of
+// the objects, the material table, sky, background or fog) the history is reset first.  The initial value is
+// PATHTRACER_GPU_TEMPORAL_MOTION (TemporalMotionFromEnv).
+void SetTemporalMotion(bool on);
+bool TemporalMotion();
+bool TemporalMotionFromEnv();  // PATHTRACER_GPU_TEMPORAL_MOTION = 1 / true / on / yes
 void SetFeatures(int k);
 int GetFeatures();     // -1: not said
 int FeaturesFromEnv(); // PATHTRACER_GPU_FEATURES = int >= 0, else -1

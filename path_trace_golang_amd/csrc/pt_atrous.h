@@ -73,13 +73,15 @@ namespace pta {
 // ---------------------------------------------------------------- features
 
 // The first hit of the primary ray (o, d) against the world: false on a miss; n = the face-forward normal, a = the albedo of the
-// hit object's converted material, dist = t * |d|.
+// hit object's converted material, dist = t * |d|; *index (when asked for) = the winner's index into objs, -1 on a miss.
 PT_HD bool first_hit(const ptd::DevObj *objs, const ptd::DevMat *mats, int32_t nobj, const double o[3], const double d[3], double n[3],
-                     double a[3], double &dist) {
+                     double a[3], double &dist, int32_t *index = nullptr) {
     const ptf::FRay r = ptf::make_fray(o[0], o[1], o[2], d[0], d[1], d[2]);
     double t;
     int32_t best;
-    if (!ptf::closest_hit(objs, nobj, r, t, best)) return false;
+    const bool any = ptf::closest_hit(objs, nobj, r, t, best);
+    if (index) *index = best;
+    if (!any) return false;
     const ptd::DevObj &ob = objs[best];
     const int kind = ob.kind & 0xff;
     double nx, ny, nz;

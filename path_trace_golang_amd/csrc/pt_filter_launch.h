@@ -113,16 +113,19 @@ inline HalvesFigures halves_figures(const ptk::HalvesPartial *part, uint32_t gri
 struct TemporalFigures {
     double noise_before;
     uint64_t reprojected, disoccluded, clipped, len_sum;
+    uint64_t moved, moved_reprojected;  // step 4a's counts (0 without a motion table)
 };
 inline TemporalFigures temporal_figures(const ptk::TemporalPartial *part, size_t nblk, size_t npix) {
     double sum = 0.0;
-    TemporalFigures r = {0.0, 0, 0, 0, 0};
+    TemporalFigures r = {0.0, 0, 0, 0, 0, 0, 0};
     for (size_t b = 0; b < nblk; b++) {
         sum += part[b].sum_before;
         r.reprojected += part[b].reprojected;
         r.disoccluded += part[b].disoccluded;
         r.clipped += part[b].clipped;
         r.len_sum += part[b].len_sum;
+        r.moved += part[b].moved;
+        r.moved_reprojected += part[b].moved_reprojected;
     }
     r.noise_before = std::sqrt(sum / (double)npix);
     return r;

@@ -45,6 +45,8 @@
 //                   between a chunk's last trace pass and resolve_kernel.
 //   feature_kernel  opt-in (pt_set_features): per pixel slot the running sums of the first-hit normal, albedo and distance of
 //                   the chunk's samples with index below k (pt_atrous.h), beside fog_kernel.
+//                   With pt_set_object_ids also the index of the object sample 0 hit first; ids_tiles_kernel lays that plane out
+//                   for the gather, in scene indices.
 //   atrous_prep_kernel / atrous_kernel / atrous_noise_kernel / atrous_finish_kernel   pt_atrous: the variance-guided a-trous
 //                   filter of pt_atrous.h over the gathered row-major planes on devices[0].
 //   halves_kernel   opt-in (pt_set_halves): per pixel slot the running sums of the radiances and of their squares over the even-
@@ -53,6 +55,7 @@
 //                   in one launch over plane-per-component buffers, and the measured noise figure of their mean.
 //   temporal_kernel pt_temporal: prep, the previous frame's history reprojected and blended (pt_temporal.h), the new history, and
 //                   the buffers atrous_prep_kernel would have left for the filter's kernels.
+//                   With a motion table (pt_temporal_set_motion) a pixel on a moved object is projected from where it was.
 //
 // FP64 throughout; built with -ffp-contract=off so every product and sum rounds
 // exactly as the reference's Go code does on amd64.
@@ -3574,12 +3577,16 @@ __global__ __launch_bounds__(PT_BLOCK) void halves_combine_kernel(const HalvesCo
 // variance and guide buffers exactly as atrous_prep_kernel does, so atrous_kernel, atrous_noise_kernel and atrous_finish_kernel run on
 // them as they are.  The block's partial of the frame's own noise figure goes over noise_kernel's tree; the counts are integers.
 // The history clip (step 7a, C.clip_gamma > 0) works on c_r, var_r and var_i where blend_pixel already holds them; its count rides
-// the same reduction.
+// the same reduction.  Displaced reprojection (step 4a, A.delta non-null): the pixel's object index and its row of the motion table
+// are read where the pixel's prep is done -- one int load and, for an object in the table, three double loads -- and the two counts
+// it adds ride the same reduction; with A.delta null nothing of it is read.
 struct TemporalPartial {
     double sum_before;            // the block's sum of e2 of (c_i, var_i)
     unsigned long long len_sum;   // ... of len'
     uint32_t reprojected, disoccluded;
     uint32_t clipped;             // reprojected pixels whose history step 7a changed (0 with C.clip_gamma == 0)
+    uint32_t moved, moved_reprojected;  // good hit pixels that step 4a displaced, and those of them that found history (0 without a table)
+    uint32_t reserved;
 };
 
 struct TemporalArgs {
@@ -3595,16 +3602,19 @@ struct TemporalArgs {
     pta::Guide *guide;            // [npix]
     TemporalPartial *partial;     // [gridDim.y * gridDim.x]
     uint32_t n;
+    const int32_t *ids;           // step 4a: [npix] row-major object index of the pixel's sample 0 (-1: a miss), or null
+    const double *delta;          // ... the motion table [ndelta][3] in the indices of ids, or null: no displacement
+    int32_t ndelta;
 };
 
 __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A) {
     __shared__ double s_sum[PT_BLOCK / PT_WAVE];
-    __shared__ uint32_t s_cnt[PT_BLOCK / PT_WAVE][4];
+    __shared__ uint32_t s_cnt[PT_BLOCK / PT_WAVE][6];
     const int32_t x = (int32_t)(blockIdx.x * 32u + (threadIdx.x & 31u));
     const int32_t y = (int32_t)(blockIdx.y * 8u + (threadIdx.x >> 5));
     const size_t np = (size_t)A.V.W * (size_t)A.V.H;
     double e2 = 0.0;
-    uint32_t rep = 0, dis = 0, lens = 0, clp = 0;
+    uint32_t rep = 0, dis = 0, lens = 0, clp = 0, mov = 0, mrp = 0;
     if (x < A.V.W && y < A.V.H) {
         const size_t i = (size_t)y * (size_t)A.V.W + (size_t)x, i3 = 3 * i;
         const double S[3] = {A.acc[i3], A.acc[i3 + 1], A.acc[i3 + 2]};
@@ -3615,8 +3625,9 @@ __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A
         const bool hit = A.fd[i3 + 1] > 0.0;
         int32_t len;
         bool clipped;
+        const double *disp = ptt::displacement(A.ids, A.delta, A.ndelta, i, hit);
         const ptt::Status st = ptt::blend_pixel(A.C, A.V, A.cam_h, A.hist, reinterpret_cast<const int32_t *>(A.hist + (size_t)PTT_LH * np), x, y,
-                                                c, var, g, hit, co, vo, len, &clipped);
+                                                c, var, g, hit, co, vo, len, &clipped, disp);
         ptt::store_history(A.hist_out, reinterpret_cast<int32_t *>(A.hist_out + (size_t)PTT_LH * np), np, i, co, vo, len, g, hit);
         A.col[i3] = co[0];
         A.col[i3 + 1] = co[1];
@@ -3628,6 +3639,8 @@ __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A
         dis = st == ptt::ST_DISOCCLUDED ? 1u : 0u;
         lens = (uint32_t)len;
         clp = clipped ? 1u : 0u;
+        mov = (disp && st != ptt::ST_BAD) ? 1u : 0u;
+        mrp = (disp && st == ptt::ST_REPROJECTED) ? 1u : 0u;
     }
     double sum = e2;
     for (int off = 32; off > 0; off >>= 1) {
@@ -3636,6 +3649,8 @@ __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A
         dis += __shfl_xor(dis, off, 64);
         lens += __shfl_xor(lens, off, 64);
         clp += __shfl_xor(clp, off, 64);
+        mov += __shfl_xor(mov, off, 64);
+        mrp += __shfl_xor(mrp, off, 64);
     }
     const uint32_t wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63u) == 0) {
@@ -3644,18 +3659,22 @@ __global__ __launch_bounds__(PT_BLOCK) void temporal_kernel(const TemporalArgs A
         s_cnt[wave][1] = dis;
         s_cnt[wave][2] = lens;
         s_cnt[wave][3] = clp;
+        s_cnt[wave][4] = mov;
+        s_cnt[wave][5] = mrp;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         TemporalPartial r;
         r.sum_before = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
-        r.reprojected = r.disoccluded = r.clipped = 0;
+        r.reprojected = r.disoccluded = r.clipped = r.moved = r.moved_reprojected = r.reserved = 0;
         r.len_sum = 0;
         for (int w = 0; w < PT_BLOCK / PT_WAVE; w++) {
             r.reprojected += s_cnt[w][0];
             r.disoccluded += s_cnt[w][1];
             r.len_sum += s_cnt[w][2];
             r.clipped += s_cnt[w][3];
+            r.moved += s_cnt[w][4];
+            r.moved_reprojected += s_cnt[w][5];
         }
         A.partial[blockIdx.y * gridDim.x + blockIdx.x] = r;
     }
@@ -3730,6 +3749,7 @@ struct FeatureArgs {
     const double *ray;                // [6][njobs]
     const uint16_t *ray_ndraw;        // 0xffff: pixel outside the frame
     double *feat;                     // [9][nslots]
+    int32_t *ids;                     // pt_set_object_ids: [nslots] the index into objs of the first hit of global sample 0 (-1: a miss), or null
     int32_t nobj;
     int32_t first;                    // 1: the running sums start at zero
     uint32_t nslots, njobs, S, take;
@@ -3750,7 +3770,10 @@ __device__ __forceinline__ void feature_body(const FeatureArgs &A, const AdaptTa
         const double o[3] = {A.ray[job], A.ray[nj + job], A.ray[2 * nj + job]};
         const double d[3] = {A.ray[3 * nj + job], A.ray[4 * nj + job], A.ray[5 * nj + job]};
         double n[3], a[3], dist;
-        if (pta::first_hit(A.objs, A.mats, A.nobj, o, d, n, a, dist)) {
+        int32_t best;
+        const bool any = pta::first_hit(A.objs, A.mats, A.nobj, o, d, n, a, dist, &best);
+        if (A.ids && A.first && s == 0u) A.ids[slot] = best;  // the chunk that starts the sums holds global sample 0
+        if (any) {
             f[0] += n[0]; f[1] += n[1]; f[2] += n[2];
             f[3] += a[0]; f[4] += a[1]; f[5] += a[2];
             f[6] += dist;
@@ -3773,6 +3796,21 @@ __global__ __launch_bounds__(PT_BLOCK) void feature_tiles_kernel(const double *_
     if (slot >= nslots) return;
     const Pixel px = slot_pixel(G, slot);
     for (uint32_t c = 0; c < 3u; c++) tiles[3 * px.pix + c] = px.inside ? feat[(3u * which + c) * (size_t)nslots + slot] : 0.0;
+}
+
+// The object index plane tile-major with -1 outside the frame, for untile_kernel's u32a plane (the bits of an int32).  ids holds
+// indices into the device world; map [nobj] turns them into indices into pt_scene.objects (the device world skips unknown types).
+__global__ __launch_bounds__(PT_BLOCK) void ids_tiles_kernel(const int32_t *__restrict__ ids, const int32_t *__restrict__ map, int32_t nobj,
+                                                               uint32_t *__restrict__ tiles_u32, uint32_t nslots, const TileGeom G) {
+    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (slot >= nslots) return;
+    const Pixel px = slot_pixel(G, slot);
+    int32_t o = -1;
+    if (px.inside) {
+        const int32_t w = ids[slot];
+        o = (w >= 0 && w < nobj) ? map[w] : -1;
+    }
+    tiles_u32[px.pix] = (uint32_t)o;
 }
 
 // One GL-shading pass per job (pt_glshade.h): pixel (x, y) of the job as in raygen_kernel, pass s0 + sample, the 16 strata

@@ -24,6 +24,21 @@
 //      rays, exact in the plane of focus.
 //   4. The vector to project:  hit:  P = origin + d * (z / sqrt(d . d));  q = P - origin_h;  zexp = sqrt(q . q)
 //                              miss: q = d                                (the sky is reprojected by direction; zexp unused)
+//  4a. Displacement (a motion table only: pt_temporal_set_motion; without one this step does not exist and every bit is as it is
+//      without it).  The frame carries, per pixel, the object index o of its sample 0's first hit (-1: a miss) and the table
+//      delta[n][3]: per object its position in this frame minus its position in the frame the history was stored from.  On a hit
+//      with 0 <= o < n and delta[o] != (0, 0, 0), step 4's P becomes, per component k,
+//          P_k = (origin_k + d_k * s) - delta[o][k]          (s = z / sqrt(d . d); then q = P - origin_h and zexp as in step 4)
+//      -- where the point now seen lay when the history was stored.  A miss, o < 0, o >= n and a zero delta change nothing (P - 0 = P:
+//      an all-zero table gives the bits of no table).  Taps, validity tests, clip, blend and the stored history are unchanged.
+//      Limits:
+//        - o is sample 0's while N, A and z are means over the k feature samples: a pixel on a silhouette is ambiguous, and is left to
+//          the tap tests.
+//        - The radiance on and near a moved object changes (its reflections, its shadow).  That is the clip's work: gamma = 2.5
+//          whenever motion is on.
+//        - The strip a moved object uncovers is disoccluded and starts again at len 1.
+//        - A resize, a material edit and a sky edit are not motion: the caller resets the history.
+//      Counted: a good hit pixel with such an o is `moved`, and `moved_reprojected` when it reaches step 8 with history.
 //   5. The inverse of the previous camera:
 //          e = lower_left_h - origin_h;  nrm = horizontal_h x vertical_h   (nrm.x = hor.y*ver.z - hor.z*ver.y, and cyclically)
 //          den = q . nrm;  num = e . nrm;  unless den * num > 0 there is no history (behind the camera, parallel, NaN)
@@ -99,8 +114,10 @@ enum Status { ST_BAD = 0, ST_NEW = 1, ST_DISOCCLUDED = 2, ST_REPROJECTED = 3 };
 PT_HD double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 // Steps 3 - 5: where pixel (x, y) of the view V, whose first hit lies z away along the centre ray (hit) or which sees the sky, was in
-// the frame of cam_h.  False: no history.
-PT_HD bool reproject(const View &V, const ptd::DevCamera &ch, int32_t x, int32_t y, bool hit, double z, double &fx, double &fy, double &zexp) {
+// the frame of cam_h.  False: no history.  disp (step 4a) = the displacement of the pixel's object since the history was stored, or
+// null: the object did not move, or nothing is known about it.
+PT_HD bool reproject(const View &V, const ptd::DevCamera &ch, int32_t x, int32_t y, bool hit, double z, double &fx, double &fy, double &zexp,
+                     const double *disp = nullptr) {
     const ptd::DevCamera &cm = V.cam;
     const double hm1 = (double)(V.H - 1), wm1 = (double)(V.W - 1);
     const double u = ((double)x + 0.5) * V.inv_width;
@@ -114,7 +131,8 @@ PT_HD bool reproject(const View &V, const ptd::DevCamera &ch, int32_t x, int32_t
     if (hit) {
         const double s = z / ptm::f_sqrt(dot3(d, d));
         for (int k = 0; k < 3; k++) {
-            const double P = cm.origin[k] + d[k] * s;
+            double P = cm.origin[k] + d[k] * s;
+            if (disp) P = P - disp[k];
             q[k] = P - ch.origin[k];
         }
         zexp = ptm::f_sqrt(dot3(q, q));
@@ -137,6 +155,16 @@ PT_HD bool reproject(const View &V, const ptd::DevCamera &ch, int32_t x, int32_t
     return fx >= -1.0 && fx <= (double)V.W && fy >= -1.0 && fy <= (double)V.H;
 }
 
+// Step 4a's lookup for pixel i: the row of delta [n][3] that displaces it, or null (no table, a miss, an index outside the table,
+// a zero row).  ids = the frame's object index plane, row-major.
+PT_HD const double *displacement(const int32_t *__restrict__ ids, const double *__restrict__ delta, int32_t n, size_t i, bool hit) {
+    if (!delta || !ids || !hit) return nullptr;
+    const int32_t o = ids[i];
+    if (o < 0 || o >= n) return nullptr;
+    const double *r = delta + 3 * (size_t)o;
+    return (r[0] != 0.0 || r[1] != 0.0 || r[2] != 0.0) ? r : nullptr;
+}
+
 // floor of a value in [-1, 2^31)
 PT_HD int32_t floor_i(double f) {
     int32_t i = (int32_t)f;
@@ -145,10 +173,11 @@ PT_HD int32_t floor_i(double f) {
 }
 
 // Steps 1 - 8 of pixel (x, y): c, var, g = the prep of the pixel, hit = h > 0; hd, hl = the history planes (read when
-// C.have_history) and ch its camera -> c', var', len'; *clipped (when asked for) = whether step 7a changed the history.
+// C.have_history) and ch its camera -> c', var', len'; *clipped (when asked for) = whether step 7a changed the history; disp =
+// reproject's.
 PT_HD Status blend_pixel(const Config &C, const View &V, const ptd::DevCamera &ch, const double *__restrict__ hd, const int32_t *__restrict__ hl,
                          int32_t x, int32_t y, const double c[3], double var, const pta::Guide &g, bool hit, double co[3], double &vo,
-                         int32_t &len, bool *clipped = nullptr) {
+                         int32_t &len, bool *clipped = nullptr, const double *disp = nullptr) {
     co[0] = c[0]; co[1] = c[1]; co[2] = c[2];
     vo = var;
     if (clipped) *clipped = false;
@@ -159,7 +188,7 @@ PT_HD Status blend_pixel(const Config &C, const View &V, const ptd::DevCamera &c
     len = 1;
     if (!C.have_history) return ST_NEW;
     double fx, fy, zexp;
-    if (!reproject(V, ch, x, y, hit, g.z, fx, fy, zexp)) return ST_DISOCCLUDED;
+    if (!reproject(V, ch, x, y, hit, g.z, fx, fy, zexp, disp)) return ST_DISOCCLUDED;
     const size_t np = (size_t)V.W * (size_t)V.H;
     const int32_t x0 = floor_i(fx), y0 = floor_i(fy);
     const double ax = fx - (double)x0, ay = fy - (double)y0;

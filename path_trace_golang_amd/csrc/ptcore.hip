@@ -190,6 +190,8 @@ struct Device {
     DevBuf<ptk::NoisePartial> noise_part;  // pt_noise_estimate: one partial per block of noise_kernel
     DevBuf<double> feat;              // pt_set_features: [9][nslots] running first-hit feature sums (allocated only then)
     DevBuf<double> tiles_feat;        // ... and the tile-major copy of one plane of them for the gather
+    DevBuf<int32_t> obj_ids;          // pt_set_object_ids: [nslots] sample 0's first hit as an index into the device world (allocated only then)
+    DevBuf<int32_t> obj_map;          // ... and [nobj] the world's indices into pt_scene.objects (the world skips unknown types)
     DevBuf<double> hv;                // pt_set_halves: [12][nslots] running half-buffer sums SA, QA, SB, QB (allocated only then)
     DevBuf<double> tiles_hv;          // ... and the tile-major copy of one plane of them for the gather
     // pt_set_adaptive (allocated only then): the active list (two buffers, the check compacts from one into the other), the
@@ -267,6 +269,9 @@ struct Frame {
     bool halves = false;   // pt_set_halves: halves_kernel runs after every chunk's moments_kernel (pt_begin / pt_render frames only; implies moments)
     uint64_t serial = 0;   // pt_ctx::frames_opened when the frame opened: tells two frames of a context apart
     int32_t features = 0;  // pt_set_features: feature_kernel runs after the chunks that hold samples below this index (pt_begin / pt_render frames only)
+    bool object_ids = false;  // pt_set_object_ids: feature_kernel also records the object of sample 0's first hit
+    int32_t scene_objects = 0;  // ... pt_scene.num_objects of the frame, the length a motion table must have
+    std::vector<int32_t> world_scene;  // ... per object of the device world its index into pt_scene.objects
     double worst_active = 0.0;  // largest block noise among the blocks the last check kept
     std::vector<ptg::GlObj> gl_objs;
     std::vector<ptg::GlMat> gl_mats;
@@ -321,6 +326,8 @@ struct pt_ctx {
     bool adaptive_on = false;         // pt_set_adaptive
     int32_t features_k = 0;           // pt_set_features: feature samples per pixel (0 = off)
     DevBuf<double> g_tiles_feat, f_feat_n, f_feat_a, f_feat_d;  // pt_read_features / pt_atrous: one gathered plane, the three row-major frames
+    bool object_ids_on = false;       // pt_set_object_ids
+    DevBuf<uint32_t> f_ids;           // pt_read_object_ids / pt_temporal with a motion table: the row-major plane (the bits of int32, scene indices)
     // The buffers of the post-frame filters, on devices[0]: allocated on the first call, never shrunk.
     struct Atrous {  // pt_atrous, pt_temporal: colour and variance ping-pong, the guide records, the noise partials
         DevBuf<double> col[2], var[2];
@@ -344,6 +351,11 @@ struct pt_ctx {
         int32_t spp = 0;
         double clip = 0.0;            // pt_temporal_set_clip: gamma of step 7a for later calls (0 = off)
         struct pt_temporal_clip_stats clip_stats{};  // of the last pt_temporal that succeeded
+        // pt_temporal_set_motion: the pending table [motion_n][3] (step 4a), consumed by the next pt_temporal that succeeds
+        std::vector<double> motion;
+        int32_t motion_n = 0;         // 0 = no table pending
+        DevBuf<double> delta;         // its copy on devices[0] for the call that consumes it
+        struct pt_temporal_motion_stats motion_stats{};  // of the last pt_temporal that succeeded
     } tp;
     uint64_t frames_opened = 0;      // pt_begin / pt_render frames of this context so far
     pt_adaptive adaptive{};
@@ -1334,6 +1346,7 @@ int32_t step_features(pt_ctx *ctx, Device &d, const DevFrame &F, const ptk::Adap
     A.ray = d.ray.p;
     A.ray_ndraw = d.ray_ndraw.p;
     A.feat = d.feat.p;
+    A.ids = fr.object_ids ? d.obj_ids.p : nullptr;
     A.nobj = fr.nobj;
     A.first = F.s0 == 0 ? 1 : 0;
     A.nslots = d.nslots;
@@ -2217,6 +2230,13 @@ int32_t fill_feature(pt_ctx *ctx, Device &d, uint32_t which, void *dst) {
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
+// the object index plane in scene indices, through untile_kernel's u32a plane like the counts
+int32_t fill_ids(pt_ctx *ctx, Device &d, uint32_t, void *dst) {
+    hipLaunchKernelGGL(ptk::ids_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.obj_ids.p, d.obj_map.p,
+                       ctx->frame.nobj, static_cast<uint32_t *>(dst), d.nslots, tile_geom(ctx->frame, d));
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
 
 const Gathered g_sums = {plane_row<&Device::tiles_accum, &pt_ctx::g_tiles_accum, &pt_ctx::f_accum>(PLANE_F64X3), fill_sums, 0};
 const Gathered g_m2 = {plane_row<&Device::tiles_m2, &pt_ctx::g_tiles_m2, &pt_ctx::f_m2>(PLANE_F64X3), dev_finish_moments, 0};
@@ -2224,6 +2244,7 @@ const Gathered g_counts = {plane_row<&Device::tiles_seg, &pt_ctx::g_tiles_seg, &
 const Gathered g_feature[3] = {{plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_n>(PLANE_F64X3), fill_feature, 0},
                                {plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_a>(PLANE_F64X3), fill_feature, 1},
                                {plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_d>(PLANE_F64X3), fill_feature, 2}};
+const Gathered g_ids = {plane_row<&Device::tiles_seg, &pt_ctx::g_tiles_seg, &pt_ctx::f_ids>(PLANE_U32A), fill_ids, 0};
 const Gathered g_half[4] = {{plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_sa>(PLANE_F64X3), dev_finish_halves, 0},
                             {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_qa>(PLANE_F64X3), dev_finish_halves, 1},
                             {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_sb>(PLANE_F64X3), dev_finish_halves, 2},
@@ -2720,6 +2741,24 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
         }
         ctx->frame.features = ctx->features_k;
     }
+    if (ctx->object_ids_on) {
+        if (ctx->frame.features <= 0) {  // refused before anything is launched; the context stays usable
+            ctx->frame.open = false;
+            return fail(PT_ERR_INVALID, "object ids: the frame needs features on (pt_set_features, k > 0): the id is the first hit of feature sample 0");
+        }
+        Frame &fr = ctx->frame;
+        fr.object_ids = true;
+        fr.scene_objects = scene->num_objects;
+        fr.world_scene.clear();
+        for (int32_t i = 0; i < scene->num_objects; i++) {  // scene_to_world's rule: unknown types have no object in the world
+            const int32_t t = scene->objects[i].type;
+            if (t == PT_OBJ_SPHERE || t == PT_OBJ_SPHERE_LIGHT || t == PT_OBJ_PLANE || t == PT_OBJ_BOX) fr.world_scene.push_back(i);
+        }
+        if ((int32_t)fr.world_scene.size() != fr.nobj) {
+            fr.open = false;
+            return fail(PT_ERR_INVALID, "object ids: the device world and the scene's object list disagree");
+        }
+    }
     for (int32_t i = 0; i < ndev; i++) {
         Device &d = ctx->devs[(size_t)i];
         int32_t rc = dev_begin(ctx, d, pt_shard{i, ndev}, nullptr);
@@ -2727,6 +2766,14 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
             hipError_t e = hipSetDevice(d.ordinal);
             if (e == hipSuccess) e = d.feat.reserve(9 * (size_t)d.nslots);
             if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("features: ") + hipGetErrorString(e));
+        }
+        if (rc == PT_OK && ctx->frame.object_ids && d.nlocal > 0) {  // outside PTCORE_L_BUDGET_MB, on the first frame that asks
+            const std::vector<int32_t> &map = ctx->frame.world_scene;
+            hipError_t e = hipSetDevice(d.ordinal);
+            if (e == hipSuccess) e = d.obj_ids.reserve((size_t)d.nslots);
+            if (e == hipSuccess) e = d.obj_map.reserve(std::max<size_t>(1, map.size()));
+            if (e == hipSuccess && !map.empty()) e = hipMemcpyAsync(d.obj_map.p, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, d.stream);
+            if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("object ids: ") + hipGetErrorString(e));
         }
         if (rc == PT_OK && ctx->frame.halves && d.nlocal > 0) {  // outside PTCORE_L_BUDGET_MB, on the first frame that asks
             hipError_t e = hipSetDevice(d.ordinal);
@@ -3006,6 +3053,21 @@ int32_t pt_read_features(pt_ctx *ctx, double *normal, double *albedo, double *de
     return PT_OK;
 }
 
+int32_t pt_set_object_ids(pt_ctx *ctx, int32_t on) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_object_ids while a frame is open");
+    ctx->object_ids_on = on != 0;
+    return PT_OK;
+}
+
+int32_t pt_read_object_ids(pt_ctx *ctx, int32_t *ids) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!ids) return fail(PT_ERR_INVALID, "pt_read_object_ids: ids is null");
+    if (int32_t rc = frame_needs(ctx, "pt_read_object_ids", {NEED_MOMENTS, NEED_FEATURES})) return rc;
+    if (!ctx->frame.object_ids) return fail(PT_ERR_STATE, "pt_read_object_ids: the frame was rendered with object ids off (pt_set_object_ids)");
+    return gather_one(ctx, g_ids, ids);
+}
+
 int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32_t stride, double *mean, double *var, pt_atrous_stats *stats) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
     pt_atrous_config c;
@@ -3083,9 +3145,18 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
     if (int32_t rc = frame_needs(ctx, "pt_temporal", {NEED_NOT_GL, NEED_FEATURES, NEED_2_SAMPLES})) return rc;
     if (T.serial == fr.serial && T.spp == fr.done_spp)
         return fail(PT_ERR_STATE, "pt_temporal: already accumulated (this frame, at this number of samples, is in the history)");
+    const int32_t motion_n = T.motion_n;  // step 4a's table, pending since pt_temporal_set_motion
+    if (motion_n > 0) {
+        if (!fr.object_ids) return fail(PT_ERR_STATE, "pt_temporal: a motion table is pending and the frame was rendered with object ids off (pt_set_object_ids)");
+        if (motion_n != fr.scene_objects)
+            return fail(PT_ERR_INVALID, "pt_temporal: the pending motion table has " + std::to_string(motion_n) + " objects, the frame's scene " +
+                                            std::to_string(fr.scene_objects));
+    }
     const int32_t W = fr.cfg.width, H = fr.cfg.height;
     FilterClock<3> clock;  // events: first launch, last launch complete, temporal_kernel complete
     if (int32_t rc = gather_filter_inputs(ctx, false)) return rc;
+    if (motion_n > 0)
+        if (int32_t rc = gather_one(ctx, g_ids, nullptr)) return rc;
     Device &d0 = ctx->devs[0];
     pt_ctx::Atrous &B = ctx->at;
     HIP_TRY(hipSetDevice(d0.ordinal));
@@ -3102,6 +3173,10 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
             return fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("pt_temporal: history: ") + hipGetErrorString(e));
     }
     HIP_TRY(T.part.reserve(nblk));
+    if (motion_n > 0) {
+        HIP_TRY(T.delta.reserve(3 * (size_t)motion_n));
+        HIP_TRY(hipMemcpyAsync(T.delta.p, T.motion.data(), 3 * (size_t)motion_n * sizeof(double), hipMemcpyHostToDevice, d0.stream));
+    }
     if (int32_t rc = reserve_filter(ctx, npix)) return rc;
     if (int32_t rc = clock.create()) return rc;
     const int next = T.cur ^ 1;  // a failed call leaves the stored history untouched: the kernel writes the other set
@@ -3131,6 +3206,11 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
     TA.guide = B.guide.p;
     TA.partial = T.part.p;
     TA.n = (uint32_t)fr.done_spp;
+    if (motion_n > 0) {
+        TA.ids = reinterpret_cast<const int32_t *>(ctx->f_ids.p);
+        TA.delta = T.delta.p;
+        TA.ndelta = motion_n;
+    }
     hipLaunchKernelGGL(ptk::temporal_kernel, grid2, dim3(PT_BLOCK), 0, d0.stream, TA);
     HIP_TRY(hipEventRecord(clock.ev[2], d0.stream));
     double *const col[2] = {B.col[0].p, B.col[1].p}, *const vr[2] = {B.var[0].p, B.var[1].p};
@@ -3173,6 +3253,9 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
     T.serial = fr.serial;
     T.spp = fr.done_spp;
     T.clip_stats = {T.clip, tf.clipped, tf.reprojected};
+    T.motion_stats = {motion_n, 0, tf.moved, tf.moved_reprojected};
+    T.motion.clear();  // one-shot: consumed, also when the history was empty
+    T.motion_n = 0;
     if (std::getenv("PTCORE_VERBOSE"))
         std::fprintf(stderr,
                      "ptcore: pt_temporal %d filter iterations, clip gamma %g: clipped %llu of %llu reprojected, temporal_kernel %.3f ms, "
@@ -3194,6 +3277,34 @@ int32_t pt_temporal_clip_stats(pt_ctx *ctx, struct pt_temporal_clip_stats *out) 
     if (!out) return fail(PT_ERR_INVALID, "pt_temporal_clip_stats: out is null");
     if (!ctx->tp.valid) return fail(PT_ERR_STATE, "pt_temporal_clip_stats: the history is empty (pt_temporal first)");
     *out = ctx->tp.clip_stats;
+    return PT_OK;
+}
+
+int32_t pt_temporal_set_motion(pt_ctx *ctx, const double *delta, int32_t num_objects) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (num_objects < 0) return fail(PT_ERR_INVALID, "pt_temporal_set_motion: num_objects must be >= 0");
+    if (!delta || num_objects == 0) {
+        ctx->tp.motion.clear();
+        ctx->tp.motion_n = 0;
+        return PT_OK;
+    }
+    for (size_t i = 0; i < 3 * (size_t)num_objects; i++)
+        if (!std::isfinite(delta[i])) return fail(PT_ERR_INVALID, "pt_temporal_set_motion: every delta must be a finite number");
+    try {  // (a copy first: a table that cannot be held leaves the pending one as it was)
+        std::vector<double> table(delta, delta + 3 * (size_t)num_objects);
+        ctx->tp.motion.swap(table);
+    } catch (const std::bad_alloc &) {
+        return fail(PT_ERR_NOMEM, "pt_temporal_set_motion: out of host memory");
+    }
+    ctx->tp.motion_n = num_objects;
+    return PT_OK;
+}
+
+int32_t pt_temporal_motion_stats(pt_ctx *ctx, struct pt_temporal_motion_stats *out) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!out) return fail(PT_ERR_INVALID, "pt_temporal_motion_stats: out is null");
+    if (!ctx->tp.valid) return fail(PT_ERR_STATE, "pt_temporal_motion_stats: the history is empty (pt_temporal first)");
+    *out = ctx->tp.motion_stats;
     return PT_OK;
 }
 
@@ -3219,6 +3330,8 @@ int32_t pt_temporal_reset(pt_ctx *ctx) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
     ctx->tp.valid = false;
     ctx->tp.serial = 0;
+    ctx->tp.motion.clear();  // a table describes a move since the history that is now gone
+    ctx->tp.motion_n = 0;
     return PT_OK;
 }
 

@@ -9,6 +9,7 @@ this package: selecting it raises instead of silently rendering somewhere else.
 """
 from __future__ import annotations
 
+import copy
 import enum
 from dataclasses import dataclass
 from typing import Callable, Optional
@@ -64,7 +65,7 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 adaptive: Optional[bool] = None, min_spp: Optional[int] = None, counts: Optional[np.ndarray] = None,
                 features: Optional[int] = None, atrous: Optional["hip.AtrousConfig"] = None,
                 filtered_noise: Optional[float] = None, temporal: Optional["hip.TemporalConfig"] = None,
-                temporal_clip: Optional[float] = None) -> dict:
+                temporal_clip: Optional[float] = None, temporal_motion: Optional[bool] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
@@ -80,7 +81,11 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     context keeps from call to call (change cfg.seed from frame to frame); None takes PATHTRACER_GPU_TEMPORAL (temporal_setup),
     which also turns on moments, 4 feature samples (unless PATHTRACER_GPU_FEATURES says otherwise) and the filter.  `temporal_clip`
     is hip.render's; None takes PATHTRACER_GPU_TEMPORAL_CLIP=<gamma> (hip.temporal_clip_from_env; unset = off),
-    which is read only when PATHTRACER_GPU_TEMPORAL turned the accumulation on."""
+    which is read only when PATHTRACER_GPU_TEMPORAL turned the accumulation on.  `temporal_motion` is for an
+    editor that drags objects: True records the object index plane, remembers the scene of the last accumulated frame and, frame by
+    frame, hands hip.scene_motion's answer on -- a table of displacements goes to pt_temporal, None (anything but positions and the
+    camera changed) resets the history, an all-zero table passes nothing; None takes PATHTRACER_GPU_TEMPORAL_MOTION
+    (hip.temporal_motion_from_env), which too is read only when PATHTRACER_GPU_TEMPORAL turned the accumulation on."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -100,16 +105,42 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
             features = features if features is not None else t_features
             if temporal_clip is None:
                 temporal_clip = hip.temporal_clip_from_env()
+            if temporal_motion is None:
+                temporal_motion = hip.temporal_motion_from_env()
     if atrous is None:
         atrous = hip.AtrousConfig.from_env()
     if features is None:
         features = hip.features_from_env()
     if filtered_noise is None and atrous is not None and noise is None:
         filtered_noise = hip.filtered_noise_from_env()
-    return hip.render(sc, gcfg, img, progress, shading=model, features=features, atrous=atrous, moments=moments, noise=noise,
-                      noise_step=noise_step if noise_step is not None else ncfg.step, adaptive=bool(adaptive) and noise is not None,
-                      min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts, filtered_noise=filtered_noise,
-                      temporal=temporal, temporal_clip=temporal_clip if temporal is not None else None)
+    motion = {}
+    if temporal is not None and temporal_motion:
+        motion = _motion_for(sc)
+    out = hip.render(sc, gcfg, img, progress, shading=model, features=features, atrous=atrous, moments=moments, noise=noise,
+                     noise_step=noise_step if noise_step is not None else ncfg.step, adaptive=bool(adaptive) and noise is not None,
+                     min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts, filtered_noise=filtered_noise,
+                     temporal=temporal, temporal_clip=temporal_clip if temporal is not None else None, **motion)
+    if "temporal" in out:
+        global _accumulated_scene
+        # (the caller edits its scene in place; a frame accumulated without the rule is not what the next table is against)
+        _accumulated_scene = copy.deepcopy(sc) if motion else None
+    return out
+
+
+# The scene of the last frame that render_into accumulated with temporal_motion on, on the process-wide context (None: none yet).
+_accumulated_scene: Optional[scn.Scene] = None
+
+
+def _motion_for(sc: scn.Scene) -> dict:
+    """The host rule of displaced reprojection: hip.render's arguments for a frame of `sc` after the remembered
+    scene.  Object ids are on; a table of displacements is passed on, an all-zero one is not, and when anything but positions and
+    the camera changed the history is reset here."""
+    delta = hip.scene_motion(_accumulated_scene, sc) if _accumulated_scene is not None else None
+    if _accumulated_scene is not None and delta is None:
+        hip.temporal_reset(hip.context())
+    if delta is not None and not delta.any():
+        delta = None
+    return dict(object_ids=True, temporal_motion=delta)
 
 
 def temporal_setup(environ=None):

@@ -12,6 +12,7 @@ engine (renderer.go:257-262).
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import math
 import os
@@ -113,6 +114,8 @@ class FlatScene:
         s.materials = C.cast(self.materials, C.POINTER(capi.PtMaterial))
         s.objects = C.cast(self.objects, C.POINTER(capi.PtObject))
         self.c = s
+        # a copy of the scene's fog block, for scene_motion alone (rendering fog still takes the Scene: see `render`)
+        self.fog_block = copy.deepcopy(getattr(sc, "fog", None))
 
 
 def pt_fog(fog: scn.Fog) -> capi.PtFog:
@@ -323,6 +326,26 @@ def read_features(ctx: capi.Context, normal: Optional[np.ndarray] = None, albedo
     capi.check(capi.load().pt_read_features(ctx.handle, *p))
 
 
+def set_object_ids(ctx: capi.Context, on: bool) -> None:
+    """pt_set_object_ids: later frames on ctx with features on also record, per pixel, the index into the scene's object list of
+    the first hit of the pixel's sample 0 (-1: a miss).  A library without the entry point takes False only."""
+    if not capi.has("pt_set_object_ids"):
+        if on:
+            raise RuntimeError("this libptcore.so has no pt_set_object_ids (rebuild it)")
+        return
+    capi.check(capi.load().pt_set_object_ids(ctx.handle, 1 if on else 0))
+    ctx._object_ids_on = bool(on)  # what `render` compares with: it says the setting only when it changes
+
+
+def read_object_ids(ctx: capi.Context, ids: np.ndarray) -> None:
+    """pt_read_object_ids into ids (contiguous int32 [H, W]): scene indices, -1 where sample 0 missed."""
+    if not capi.has("pt_read_object_ids"):
+        raise RuntimeError("this libptcore.so has no pt_read_object_ids (rebuild it)")
+    if ids.dtype != np.int32 or ids.ndim != 2 or not ids.flags.c_contiguous:
+        raise ValueError("ids must be contiguous int32 [H, W]")
+    capi.check(capi.load().pt_read_object_ids(ctx.handle, ids.ctypes.data_as(C.POINTER(C.c_int32))))
+
+
 @dataclass
 class AtrousConfig:
     """The a-trous filter of pt_atrous: iterations 0..6 and the four sigmas (a feature sigma of 0 turns its term
@@ -480,6 +503,58 @@ def temporal_clip_stats(ctx: capi.Context) -> dict:
     return st.as_dict()
 
 
+def temporal_set_motion(ctx: capi.Context, delta) -> None:
+    """pt_temporal_set_motion: delta = [n, 3], per scene object its position in the frame about to be accumulated minus its position
+    in the frame the history was stored from (None or empty clears the table).  One-shot: the next pt_temporal that succeeds
+    consumes it.  The frame must have recorded object ids (set_object_ids); DESIGN 3.13b."""
+    if not capi.has("pt_temporal_set_motion"):
+        raise RuntimeError("this libptcore.so has no pt_temporal_set_motion (rebuild it)")
+    if delta is None:
+        capi.check(capi.load().pt_temporal_set_motion(ctx.handle, None, 0))
+        return
+    d = np.ascontiguousarray(delta, np.float64)
+    if d.size and (d.ndim != 2 or d.shape[1] != 3):
+        raise ValueError("delta must be [num_objects, 3]")
+    n = d.shape[0] if d.size else 0
+    capi.check(capi.load().pt_temporal_set_motion(ctx.handle, d.ctypes.data_as(C.POINTER(C.c_double)) if n else None, n))
+
+
+def temporal_motion_stats(ctx: capi.Context) -> dict:
+    """pt_temporal_motion_stats: dict(objects, moved, moved_reprojected) of the last pt_temporal that succeeded on ctx.  Raises
+    PtError (PT_ERR_STATE) while the history is empty."""
+    if not capi.has("pt_temporal_motion_stats"):
+        raise RuntimeError("this libptcore.so has no pt_temporal_motion_stats (rebuild it)")
+    st = capi.PtTemporalMotionStats()
+    capi.check(capi.load().pt_temporal_motion_stats(ctx.handle, C.byref(st)))
+    return st.as_dict()
+
+
+def scene_motion(prev, cur) -> Optional[np.ndarray]:
+    """What moved between two scenes, for temporal_set_motion: the [n, 3] array of cur's object positions minus prev's when the two
+    differ in object positions and the camera only; None when anything else differs -- the number, order, type, size or material
+    id of the objects, the material table, the sky, the background or the fog -- and the history has to be reset.  A pure
+    function of the two scenes (Scene or FlatScene each; a FlatScene keeps a copy of the fog block of the Scene it was made from)."""
+    a = prev if isinstance(prev, FlatScene) else FlatScene(prev)
+    b = cur if isinstance(cur, FlatScene) else FlatScene(cur)
+    ca, cb = a.c, b.c
+    if ca.num_objects != cb.num_objects or ca.num_materials != cb.num_materials:
+        return None
+    if C.string_at(C.addressof(ca.sky), C.sizeof(ca.sky)) != C.string_at(C.addressof(cb.sky), C.sizeof(cb.sky)):
+        return None
+    msz = C.sizeof(capi.PtMaterial) * ca.num_materials
+    if msz and C.string_at(ca.materials, msz) != C.string_at(cb.materials, msz):
+        return None
+    if a.fog_block != b.fog_block:
+        return None
+    out = np.zeros((ca.num_objects, 3))
+    for i in range(ca.num_objects):
+        oa, ob = ca.objects[i], cb.objects[i]
+        if oa.type != ob.type or oa.material != ob.material or tuple(oa.size) != tuple(ob.size):
+            return None
+        out[i] = np.array(tuple(ob.position)) - np.array(tuple(oa.position))
+    return out
+
+
 def temporal_clip_from_env(environ=None) -> float:
     """PATHTRACER_GPU_TEMPORAL_CLIP=<gamma>: the clip of the RenderInto path when PATHTRACER_GPU_TEMPORAL is on.  Unset, empty or
     not a finite number >= 0: 0.0 (off)."""
@@ -489,6 +564,12 @@ def temporal_clip_from_env(environ=None) -> float:
     except ValueError:
         return 0.0
     return g if math.isfinite(g) and g >= 0.0 else 0.0
+
+
+def temporal_motion_from_env(environ=None) -> bool:
+    """PATHTRACER_GPU_TEMPORAL_MOTION=1 (or true / on / yes): the RenderInto path passes the objects' displacements to the
+    accumulation.  Read only when PATHTRACER_GPU_TEMPORAL turned the accumulation on."""
+    return _env_on(environ, "PATHTRACER_GPU_TEMPORAL_MOTION")
 
 
 def set_halves(ctx: capi.Context, on: bool) -> None:
@@ -608,7 +689,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            noise_step: int = 16, adaptive: bool = False, min_spp: int = 0, counts: Optional[np.ndarray] = None,
            features: Optional[int] = None, atrous: Optional["AtrousConfig"] = None,
            filtered_noise: Optional[float] = None, halves: bool = False,
-           temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None) -> dict:
+           temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None,
+           object_ids: bool = False, temporal_motion=None) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -651,12 +733,19 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     DESIGN 3.13a; 2.5 is the recommended value, 0 turns it off) and the "temporal" dict gains "clipped"; None leaves the context's
     setting as it is, which is off unless temporal_set_clip was called.
 
+    object_ids=True also records the per-pixel object index plane (pt_set_object_ids; read it with
+    read_object_ids(ctx, ...) afterwards); it turns features on (k = 4) where nothing else did.  temporal_motion=delta (with
+    temporal=; [n, 3], see scene_motion) turns object ids on and passes the objects' displacements since the last accumulated
+    frame to pt_temporal (temporal_set_motion); the "temporal" dict gains "objects", "moved" and "moved_reprojected".
+
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
     Returns the pt_stats of the frame as a dict.
     """
     if temporal_clip is not None and temporal is None:
         raise ValueError("temporal_clip needs the accumulation it clips (temporal=)")
+    if temporal_motion is not None and temporal is None:
+        raise ValueError("temporal_motion needs the accumulation it displaces (temporal=)")
     if filtered_noise is not None:
         if atrous is None:
             raise ValueError("filtered_noise needs the filter whose output it measures (atrous=)")
@@ -695,7 +784,12 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
             features = atrous.features if atrous.features is not None else (4 if scene_allows_features(sc, shading) else 0)
         if temporal is not None and not features:  # (where the scene refuses features, pt_temporal says so)
             features = 4
+        if (object_ids or temporal_motion is not None) and not features:
+            features = 4
     set_features(ctx, features)
+    want_ids = object_ids or temporal_motion is not None
+    if want_ids != getattr(ctx, "_object_ids_on", False):  # (said only when it changes: with it never on, the calls are what they were)
+        set_object_ids(ctx, want_ids)
     if moments is not None and (moments.dtype != np.float64 or moments.shape != (cfg.height, cfg.width, 3)
                                 or not moments.flags.c_contiguous):
         raise ValueError("moments must be contiguous float64 [H, W, 3]")
@@ -715,9 +809,13 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
                 read_moments(ctx, moments)
             d.update(noise=noise_estimate(ctx)["noise"])
             if temporal is not None:  # the accumulated (and filtered) image takes the place of the plain finish
+                if temporal_motion is not None:
+                    temporal_set_motion(ctx, temporal_motion)
                 d["temporal"] = _temporal(ctx, temporal, atrous, img)
                 if temporal_clip is not None:
                     d["temporal"]["clipped"] = temporal_clip_stats(ctx)["clipped"]
+                if temporal_motion is not None:
+                    d["temporal"].update(temporal_motion_stats(ctx))
             elif atrous is not None:  # the filtered image takes the place of the plain finish
                 d["atrous"] = _atrous(ctx, atrous, img)
             if filtered_noise is not None:

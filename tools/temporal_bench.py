@@ -10,8 +10,12 @@
              on the bytes each pixel has to move once (--bytes-per-pixel) against --hbm-peak.
              --clip GAMMA runs it with the history clip (pt_temporal_set_clip; 0 = off, the default) and adds
              clipped and clipped / reprojected to every row; a library without the entry point runs with 0 only.
+             --motion runs it with displaced reprojection (pt_temporal_set_motion): in the second frame one sphere
+             and one box of the scene stand 0.08 further along x, the frames record object ids, the table of all 27 objects goes in
+             front of the second pt_temporal, and every row gains moved and moved_reprojected.  Without the flag nothing of it is
+             touched, so the parent commit's library measures the same calls.
 
-    python tools/temporal_bench.py --part atrous|temporal [--clip GAMMA] [--out FILE]
+    python tools/temporal_bench.py --part atrous|temporal [--clip GAMMA] [--motion] [--out FILE]
 """
 from __future__ import annotations
 
@@ -51,6 +55,7 @@ def main() -> None:
     ap.add_argument("--k", type=int, default=4)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--clip", type=float, default=0.0, help="gamma of the history clip; 0 = off")
+    ap.add_argument("--motion", action="store_true", help="displaced reprojection: two objects moved, the table of 27 passed")
     ap.add_argument("--bytes-per-pixel", type=int, default=BYTES_PER_PIXEL)
     ap.add_argument("--hbm-peak", type=float, default=8.0e12, help="bytes per second")
     ap.add_argument("--tag", default="")
@@ -64,6 +69,12 @@ def main() -> None:
     right = np.cross(t - p, u)
     q = p + right / np.linalg.norm(right) * (0.01 * np.linalg.norm(t - p))
     moved.camera.position = scene.Vec3(float(q[0]), float(q[1]), float(q[2]))
+    delta = None
+    if a.motion:
+        for i in (8, 15):  # the rough copper sphere and the white box
+            moved.objects[i].position.x += 0.08
+        delta = hip.scene_motion(base, moved)
+        assert delta is not None and delta.shape == (27, 3)
     flats = [hip.FlatScene(base), hip.FlatScene(moved)]
     img = np.zeros((H, W, 4), np.uint8)
     rows = []
@@ -76,6 +87,8 @@ def main() -> None:
     def frame(ctx, i):
         hip.set_moments(ctx, True)
         hip.set_features(ctx, a.k)
+        if a.motion:
+            hip.set_object_ids(ctx, True)
         pc = hip.pt_config(hip.RenderConfig(W, H, a.spp, a.depth, 1 + i))
         capi.check(L.pt_render(ctx.handle, C.byref(flats[i].c), C.byref(pc), img.ctypes.data_as(C.c_void_p), int(img.strides[0]), None, None, None, None))
 
@@ -95,6 +108,8 @@ def main() -> None:
                 hip.temporal_reset(ctx)
                 for i in (0, 1):
                     frame(ctx, i)
+                    if a.motion and i == 1:
+                        hip.temporal_set_motion(ctx, delta)
                     with Stderr() as err:
                         t0 = time.perf_counter()
                         st = hip.temporal(ctx, hip.TemporalConfig(), hip.AtrousConfig(), img)
@@ -104,6 +119,8 @@ def main() -> None:
                     if capi.has("pt_temporal_clip_stats"):
                         st["clipped"] = hip.temporal_clip_stats(ctx)["clipped"]
                         st["clipped_fraction"] = st["clipped"] / max(st["reprojected"], 1)
+                    if a.motion:
+                        st.update(hip.temporal_motion_stats(ctx))
                     if m:
                         st["kernel_bytes_per_s"] = a.bytes_per_pixel * W * H / (st["kernel_ms"] * 1e-3)
                         st["kernel_fraction_of_hbm_peak"] = st["kernel_bytes_per_s"] / a.hbm_peak
