@@ -80,6 +80,11 @@ var (
 	filteredSet    bool        // false: PATHTRACER_GPU_FILTERED_NOISE decides
 	filteredTarget float64     // the noise target on the filtered frame (0 = off)
 	lastHalves     HalvesStats // pt_halves_stats of the last check of the last frame (zero unless that stop rule was in force)
+
+	filteredAdaptiveSet    bool // false: PATHTRACER_GPU_FILTERED_ADAPTIVE and PATHTRACER_GPU_POOL decide
+	filteredAdaptiveTarget float64
+	filteredAdaptivePool   = 1
+	filteredAdaptiveOn     bool // pt_set_adaptive_filtered is in force on ctx (said only where it was ever on)
 )
 
 // HalvesStats mirrors pt_halves_stats: the measured and the propagated noise of the filtered frame at the last check.
@@ -205,6 +210,64 @@ func filteredRule() float64 {
 		return v
 	}
 	return 0
+}
+
+// SetFilteredAdaptive makes the frame adaptive with the blocks stopped by the filtered frame's pooled noise (pt_set_adaptive_filtered,
+// DESIGN 3.12a): with the filter on (SetAtrous), every 8x8 block stops once the noise measured in the filtered frame over the blocks
+// within pool blocks (0..4, anything else counts as 1) of it is at or below target; the step and minSpp are SetNoiseTarget's and
+// SetAdaptive's.  target <= 0 turns the rule off.  It is ignored without the filter and is an error beside a frame noise target, the
+// filtered noise target or GL shading.  Not set: PATHTRACER_GPU_FILTERED_ADAPTIVE and PATHTRACER_GPU_POOL decide.
+func SetFilteredAdaptive(target float64, pool int) {
+	mu.Lock()
+	defer mu.Unlock()
+	filteredAdaptiveSet = true
+	if target < 0 {
+		target = 0
+	}
+	if pool < 0 || pool > 4 {
+		pool = 1
+	}
+	filteredAdaptiveTarget, filteredAdaptivePool = target, pool
+}
+
+// filteredAdaptiveRule: the block target on the filtered frame's pooled noise in force and the pool radius (0 = off, also without the filter).
+func filteredAdaptiveRule() (float64, int) {
+	if on, _ := atrousRule(); !on {
+		return 0, 1
+	}
+	if filteredAdaptiveSet {
+		return filteredAdaptiveTarget, filteredAdaptivePool
+	}
+	pool := 1
+	if v, err := strconv.Atoi(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_POOL"))); err == nil && v >= 0 && v <= 4 {
+		pool = v
+	}
+	if v, err := strconv.ParseFloat(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_FILTERED_ADAPTIVE")), 64); err == nil && v > 0 && !math.IsInf(v, 0) {
+		return v, pool
+	}
+	return 0, pool
+}
+
+// ReadBlockFigures reads pt_read_block_figures of the last frame rendered under SetFilteredAdaptive: the last deciding check's pooled
+// figure and the block's own, row-major over the grid of ((width + 7) / 8) x ((height + 7) / 8) blocks, and the checks that decided.
+func ReadBlockFigures(width, height int) (pooled, own []float64, checks int, err error) {
+	mu.Lock()
+	defer mu.Unlock()
+	if ctx == nil {
+		return nil, nil, 0, errors.New("pt_read_block_figures: no context yet")
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	n := ((width + 7) / 8) * ((height + 7) / 8)
+	if n <= 0 {
+		return nil, nil, 0, errors.New("pt_read_block_figures: empty frame")
+	}
+	pooled, own = make([]float64, n), make([]float64, n)
+	var c C.int32_t
+	if rc := C.pt_read_block_figures(ctx, (*C.double)(unsafe.Pointer(&pooled[0])), (*C.double)(unsafe.Pointer(&own[0])), &c); rc != C.PT_OK {
+		return nil, nil, 0, lastError("pt_read_block_figures")
+	}
+	return pooled, own, int(c), nil
 }
 
 // TemporalStats mirrors pt_temporal_stats: what the temporal accumulation did to the last frame.
@@ -814,6 +877,13 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 	toNoise := target > 0
 	atrous, atrousN := atrousRule()
 	filtered := filteredRule()
+	blockTarget, pool := filteredAdaptiveRule()
+	if blockTarget > 0 && (toNoise || filtered > 0) {
+		return errors.New("hip.Render: the filtered adaptive target excludes a frame noise target, adaptive sampling and the filtered noise target: one stop rule per frame")
+	}
+	if blockTarget > 0 && glShading() {
+		return errors.New("hip.Render: the filtered adaptive target is not available with GL shading")
+	}
 	if filtered > 0 && toNoise {
 		return errors.New("hip.Render: the filtered noise target excludes a frame noise target and adaptive sampling: one stop rule per frame")
 	}
@@ -849,6 +919,21 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 	}
 	adaptive, minSpp := adaptiveRule()
 	adaptive = adaptive && toNoise // the noise target is the blocks' target
+	if blockTarget > 0 { // an adaptive frame whose blocks stop by the filtered frame's pooled noise
+		adaptive, toNoise, target = true, true, blockTarget
+	}
+	if blockTarget > 0 || filteredAdaptiveOn {
+		if blockTarget > 0 {
+			fa := C.pt_adaptive_filtered{filter: C.pt_atrous_config{iterations: C.int32_t(atrousN), sigma_l: 4, sigma_n: 0.1, sigma_z: 0.1, sigma_a: 0.2},
+				pool: C.int32_t(pool)}
+			if rc := C.pt_set_adaptive_filtered(ctx, &fa); rc != C.PT_OK {
+				return lastError("pt_set_adaptive_filtered")
+			}
+		} else if rc := C.pt_set_adaptive_filtered(ctx, nil); rc != C.PT_OK {
+			return lastError("pt_set_adaptive_filtered")
+		}
+		filteredAdaptiveOn = blockTarget > 0
+	}
 	if adaptive {
 		ad := C.pt_adaptive{target: C.double(target), min_spp: C.int32_t(minSpp), step: C.int32_t(nstep)}
 		if rc := C.pt_set_adaptive(ctx, &ad); rc != C.PT_OK {
@@ -862,7 +947,7 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 		samples_per_px: C.int32_t(cfg.SamplesPerPx), max_depth: C.int32_t(cfg.MaxDepth), seed: C.uint64_t(seed)}
 	pix := (*C.uint8_t)(unsafe.Pointer(&img.Pix[0]))
 	if toNoise {
-		return renderToNoise(cs, &pc, cfg, img, pix, progress, target, nstep, adaptive)
+		return renderToNoise(cs, &pc, cfg, img, pix, progress, target, nstep, adaptive, blockTarget <= 0)
 	}
 	if filtered > 0 {
 		return renderToFilteredNoise(cs, &pc, cfg, img, pix, progress, filtered, nstep, atrousN)
@@ -973,7 +1058,7 @@ func renderToFilteredNoise(cs *C.pt_scene, pc *C.pt_config, cfg RenderConfig, im
 // samples done.  With adaptive the blocks stop inside pt_step and the loop ends when a step adds nothing.  Called with mu held
 // on a locked OS thread.
 func renderToNoise(cs *C.pt_scene, pc *C.pt_config, cfg RenderConfig, img *image.RGBA, pix *C.uint8_t, progress func(),
-	target float64, nstep int, adaptive bool) error {
+	target float64, nstep int, adaptive bool, measure bool) error {
 	if rc := C.pt_begin(ctx, cs, pc); rc != C.PT_OK {
 		return lastError("pt_begin")
 	}
@@ -999,6 +1084,9 @@ func renderToNoise(cs *C.pt_scene, pc *C.pt_config, cfg RenderConfig, img *image
 				break
 			}
 			progress()
+		}
+		if !measure { // the blocks stop inside pt_step by the filtered frame's pooled noise: the frame noise decides nothing
+			continue
 		}
 		if rc := C.pt_noise_estimate(ctx, &nz); rc != C.PT_OK {
 			err = lastError("pt_noise_estimate")

@@ -548,6 +548,45 @@ int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean,
                          pt_halves_stats *stats);
 
 /*
+ * Adaptive sampling by the pooled noise of the filtered frame (additive to ABI 4; the model and its order of
+ * evaluation are stated in csrc/pt_atrous.h, BLOCKS).  pt_set_adaptive stops a block by the noise of its unfiltered pixels, and
+ * pt_atrous_halves' measured figure can only stop a whole frame; this rule stops the 8x8 blocks of an adaptive frame by the noise that is
+ * left in the filtered frame around them.  Off unless asked for: with the rule off nothing is allocated or launched.
+ *   pt_set_adaptive_filtered(ctx, &f) : later adaptive frames on ctx take their block decisions from this rule; NULL = off (the
+ *                             default).  The target, min_spp and step are pt_set_adaptive's; a min_spp below 4 counts as 4.  Such a
+ *                             frame is adaptive in every respect (counts, pt_read / pt_end by each pixel's own count, pt_adaptive_state,
+ *                             pt_read_sample_counts) and collects the half-buffer sums whether or not pt_set_halves asked.  At the end of
+ *                             every pt_step, once the samples done reach max(min_spp, 4): pt_atrous_halves' model with `filter` on the
+ *                             frame as it stands gives err per pixel; per block B of the frame's 8x8 grid, s_B = the sum of
+ *                             err / max(l, 0.01)^2 over its k_B pixels inside the frame (pt_atrous_halves' `noise` term: a pixel that is
+ *                             bad or whose term is not finite adds 0 and still counts);
+ *                             P_B = sqrt(sum of s_B' / sum of k_B') over the blocks within `pool` blocks of B in x and in y that lie inside
+ *                             the grid, stopped blocks included with the samples they hold; every still-active block with
+ *                             P_B <= target becomes inactive and stays so.  Every sum has a stated order: the same bits for every
+ *                             spp_chunk, buffer budget, scan form and device count.  Unlike pt_set_adaptive's rule, neighbouring blocks
+ *                             do keep each other alive: that is what the pool is for, since err has one degree of freedom per pixel.
+ *                             pool = 0 judges every block by itself.  The figure inherits the limit of `noise`: where rare bright paths
+ *                             were missed it overstates or misses them, and it does not see the filter's bias.
+ *                             PT_ERR_STATE while a frame is open; PT_ERR_INVALID for a pool outside 0..4 and for pt_atrous's own
+ *                             refusals of `filter`.  A frame opened with the rule on and pt_set_adaptive off is PT_ERR_INVALID, before
+ *                             anything is launched and with the context left usable; the refusals of adaptive frames stay as they are.
+ *   pt_read_block_figures   : of the last check that decided, row-major over the frame's grid of ((width + 7) / 8) x ((height + 7) / 8)
+ *                             blocks: pooled = P_B, own = sqrt(s_B / k_B), either of them NULL; *checks = the checks that have decided
+ *                             so far in the frame.  PT_ERR_STATE when the open or last frame did not use the rule or no check has
+ *                             decided yet.
+ *   pt_adaptive_state.worst_active is, for such frames, the largest P_B among the active blocks (+inf before the first decision).
+ * The check runs on devices[0]; the map of flags and figures travels to the other devices through the host.
+ */
+typedef struct pt_adaptive_filtered {
+    pt_atrous_config filter;
+    int32_t pool;      /* radius of the window in blocks, 0..4 */
+    int32_t reserved;
+} pt_adaptive_filtered;
+
+int32_t pt_set_adaptive_filtered(pt_ctx *ctx, const pt_adaptive_filtered *f);
+int32_t pt_read_block_figures(pt_ctx *ctx, double *pooled, double *own, int32_t *checks);
+
+/*
  * Temporal accumulation (additive to ABI 4; the model and its order of evaluation are stated in csrc/pt_temporal.h):
  * for a caller that renders frame after frame while the camera moves.  The context keeps a history -- per pixel a blended mean, the
  * variance of that mean, the number of frames behind it, and the first-hit normal, albedo and distance it belongs to -- with the camera

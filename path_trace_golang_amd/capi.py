@@ -137,6 +137,10 @@ class PtHalvesStats(C.Structure):  # pt_halves_stats
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class PtAdaptiveFiltered(C.Structure):  # pt_adaptive_filtered: the filter whose output is measured and the pool radius in blocks
+    _fields_ = [("filter", PtAtrousConfig), ("pool", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PtTemporalConfig(C.Structure):  # pt_temporal_config: the blend weight, the tap tests and the history length of pt_temporal
     _fields_ = [("alpha", C.c_double), ("tol_z", C.c_double), ("n_min", C.c_double), ("tol_a", C.c_double),
                 ("max_len", C.c_int32), ("reserved", C.c_int32)]
@@ -226,6 +230,8 @@ SYMBOLS = [
     ("pt_read_halves", C.c_int32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("pt_atrous_halves", C.c_int32, [_vp, C.POINTER(PtAtrousConfig), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.POINTER(PtHalvesStats)]),
+    ("pt_set_adaptive_filtered", C.c_int32, [_vp, C.POINTER(PtAdaptiveFiltered)]),  # additive to ABI 4 (see has())
+    ("pt_read_block_figures", C.c_int32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     ("pt_temporal", C.c_int32, [_vp, C.POINTER(PtTemporalConfig), C.POINTER(PtAtrousConfig), _vp, C.c_int32, C.POINTER(C.c_double),
                                  C.POINTER(C.c_double), C.POINTER(PtTemporalStats)]),  # additive to ABI 4 (see has())
     ("pt_temporal_read", C.c_int32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
@@ -278,7 +284,7 @@ ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_ray
             "pt_noise_estimate", "pt_set_adaptive", "pt_adaptive_state", "pt_read_sample_counts", "pt_set_features",
             "pt_read_features", "pt_atrous", "pt_set_halves", "pt_read_halves", "pt_atrous_halves", "pt_temporal", "pt_temporal_read",
             "pt_temporal_reset", "pt_temporal_set_clip", "pt_temporal_clip_stats", "pt_set_object_ids", "pt_read_object_ids",
-            "pt_temporal_set_motion", "pt_temporal_motion_stats")  # added within ABI 4: detected by presence
+            "pt_temporal_set_motion", "pt_temporal_motion_stats", "pt_set_adaptive_filtered", "pt_read_block_figures")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:

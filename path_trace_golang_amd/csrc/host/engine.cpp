@@ -59,7 +59,8 @@ namespace {
     OPTIONAL(pt_set_shading) OPTIONAL(pt_set_moments) OPTIONAL(pt_noise_estimate) OPTIONAL(pt_set_adaptive)                      \
     OPTIONAL(pt_adaptive_state) OPTIONAL(pt_set_features) OPTIONAL(pt_atrous) OPTIONAL(pt_set_halves) OPTIONAL(pt_atrous_halves) \
     OPTIONAL(pt_temporal) OPTIONAL(pt_temporal_reset) OPTIONAL(pt_temporal_set_clip) OPTIONAL(pt_temporal_clip_stats)           \
-    OPTIONAL(pt_set_object_ids) OPTIONAL(pt_temporal_set_motion) OPTIONAL(pt_temporal_motion_stats)
+    OPTIONAL(pt_set_object_ids) OPTIONAL(pt_temporal_set_motion) OPTIONAL(pt_temporal_motion_stats)                              \
+    OPTIONAL(pt_set_adaptive_filtered) OPTIONAL(pt_read_block_figures)
 
 struct Core {
     void *handle = nullptr;
@@ -70,7 +71,7 @@ struct Core {
 };
 
 // What a frame setting needs from the library beyond the required entry points, and what Render answers when it is not there.
-enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION };
+enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE };
 const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_shading != nullptr; }, "GL shading: libptcore.so lacks pt_set_shading"},
     {[](const Core &c) { return c.pt_set_moments && c.pt_noise_estimate; }, "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate"},
@@ -82,17 +83,21 @@ const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_adaptive && c.pt_adaptive_state; }, "adaptive sampling: libptcore.so lacks pt_set_adaptive / pt_adaptive_state"},
     {[](const Core &c) { return c.pt_set_object_ids && c.pt_temporal_set_motion && c.pt_temporal_motion_stats && c.pt_temporal_reset; },
      "temporal motion: libptcore.so lacks pt_set_object_ids / pt_temporal_set_motion"},
+    {[](const Core &c) { return c.pt_set_adaptive_filtered && c.pt_read_block_figures && c.pt_set_adaptive && c.pt_adaptive_state; },
+     "filtered adaptive target: libptcore.so lacks pt_set_adaptive_filtered / pt_read_block_figures"},
 };
 
 // What the Set* calls said; an empty field leaves the matter to the environment (the *FromEnv rules).
 struct NoiseRule { double target; int step; };
 struct Switch { bool on; int n; };  // adaptive + min_spp, a-trous + iterations
+struct BlockRule { double target; int pool; };
 struct Settings {
     std::optional<bool> fog, temporal, temporal_motion;
     std::optional<int> shading, features;
     std::optional<NoiseRule> noise;
     std::optional<Switch> adaptive, atrous;
     std::optional<double> filtered_noise, temporal_clip;
+    std::optional<BlockRule> filtered_adaptive;
 };
 
 Core g_core;
@@ -309,6 +314,10 @@ void AtrousFromEnv(bool &on, int &iterations) {
 }
 int FeaturesFromEnv() { return env_int("PATHTRACER_GPU_FEATURES", 0, 0x7fffffffL, -1); }
 double FilteredNoiseFromEnv() { return env_double("PATHTRACER_GPU_FILTERED_NOISE", positive_finite, 0); }
+void FilteredAdaptiveFromEnv(double &target, int &pool) {
+    target = env_double("PATHTRACER_GPU_FILTERED_ADAPTIVE", positive_finite, 0);
+    pool = env_int("PATHTRACER_GPU_POOL", 0, 4, 1);
+}
 bool TemporalFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL"); }
 double TemporalClipFromEnv() { return env_double("PATHTRACER_GPU_TEMPORAL_CLIP", finite_not_negative, 0); }
 bool TemporalMotionFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL_MOTION"); }
@@ -326,6 +335,7 @@ struct FramePlan {
     double clip;          // > 0 only under temporal accumulation
     bool motion;          // displaced reprojection: on only under temporal accumulation
     double filtered;      // > 0 only under the filter
+    BlockRule blocks;     // target > 0 only under the filter: an adaptive frame whose blocks stop by the filtered frame's pooled noise
     int features;
     bool moments, halves;
 };
@@ -339,6 +349,11 @@ Switch adaptive_switch(const Settings &s) {
     Switch r;
     AdaptiveFromEnv(r.on, r.n);
     return s.adaptive.value_or(r);
+}
+BlockRule block_rule(const Settings &s) {
+    BlockRule r;
+    FilteredAdaptiveFromEnv(r.target, r.pool);
+    return s.filtered_adaptive.value_or(r);
 }
 Switch atrous_switch(const Settings &s) {
     Switch r;
@@ -359,6 +374,8 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
     p.motion = p.temporal && s.temporal_motion.value_or(TemporalMotionFromEnv());
     p.atrous.on = p.atrous.on || p.temporal;
     p.filtered = p.atrous.on ? s.filtered_noise.value_or(FilteredNoiseFromEnv()) : 0;
+    p.blocks = block_rule(s);
+    if (!p.atrous.on) p.blocks.target = 0;
     p.features = s.features.value_or(FeaturesFromEnv());
     if (p.features < 0 && p.temporal) p.features = 4;  // (pt_temporal needs them: where the frame refuses features, pt_begin says so)
     if (p.features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path), else off
@@ -375,7 +392,7 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
         }
     }
     p.moments = p.noise.target > 0 || p.atrous.on;
-    p.halves = p.filtered > 0;
+    p.halves = p.filtered > 0;  // (the block rule's frames collect the half sums by themselves)
     return p;
 }
 
@@ -390,6 +407,7 @@ struct AccumulatedScene {
 };
 AccumulatedScene g_accumulated;
 bool g_object_ids_on = false;  // pt_set_object_ids(1) was the last thing said to the context
+bool g_block_rule_on = false;  // pt_set_adaptive_filtered(&f) was the last thing said to the context
 
 // Both belong to the context: a new one has object ids off and an empty history.  Called with g_mu held.
 void drop_context() {
@@ -397,6 +415,7 @@ void drop_context() {
     g_ctx = nullptr;
     g_accumulated.valid = false;
     g_object_ids_on = false;
+    g_block_rule_on = false;
 }
 
 void remember(const scene::Scene &sc, const Flat &flat, AccumulatedScene &a) {
@@ -499,6 +518,18 @@ double GetFilteredNoise() {
     std::lock_guard<std::mutex> lk(g_mu);
     return g_set.filtered_noise.value_or(FilteredNoiseFromEnv());
 }
+void SetFilteredAdaptive(double target, int pool) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_set.filtered_adaptive = BlockRule{target > 0 ? target : 0, pool >= 0 && pool <= 4 ? pool : 1};
+}
+double GetFilteredAdaptive() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return block_rule(g_set).target;
+}
+int GetPool() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return block_rule(g_set).pool;
+}
 void SetTemporal(bool on) {
     std::lock_guard<std::mutex> lk(g_mu);
     g_set.temporal = on;
@@ -563,7 +594,8 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     Flat flat;
     FlattenScene(sc, flat.materials, flat.objects, flat.sc);
     const FramePlan p = resolve(sc, flat.objects, g_set);
-    const bool gl = p.shading == PT_SHADING_GL, to_noise = p.noise.target > 0, to_filtered = p.filtered > 0;
+    const bool gl = p.shading == PT_SHADING_GL, to_noise = p.noise.target > 0, to_filtered = p.filtered > 0, to_blocks = p.blocks.target > 0;
+    const bool adaptive = p.adaptive.on || to_blocks;  // the block rule's frame is an adaptive one, with its own target
     const char *missing = nullptr;  // the text of the last need that was not met
     auto lacks = [&missing](bool wanted, Feature f) { return wanted && !kNeeds[f].have(g_core) && (missing = kNeeds[f].lacks); };
 
@@ -592,6 +624,10 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (to_filtered && to_noise) return "filtered noise target: excludes a frame noise target (-noise) and adaptive sampling: one stop rule per frame";
     if (to_filtered && gl) return "filtered noise target: not available with GL shading";
     if (lacks(to_filtered, FILTERED_NOISE)) return missing;
+    if (to_blocks && (to_noise || to_filtered))
+        return "filtered adaptive target: excludes a frame noise target (-noise), adaptive sampling and the filtered noise target: one stop rule per frame";
+    if (to_blocks && gl) return "filtered adaptive target: not available with GL shading";
+    if (lacks(to_blocks, FILTERED_ADAPTIVE)) return missing;
     if (g_core.pt_set_halves && failed(PT_CALL(pt_set_halves, g_ctx, p.halves ? 1 : 0))) return err;
     if (lacks(p.features > 0, FEATURES)) return missing;
     if (g_core.pt_set_features && failed(PT_CALL(pt_set_features, g_ctx, p.features))) return err;
@@ -604,10 +640,18 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (g_core.pt_set_adaptive) {
         pt_adaptive ad;
         std::memset(&ad, 0, sizeof ad);
-        ad.target = p.noise.target;
+        ad.target = to_blocks ? p.blocks.target : p.noise.target;
         ad.min_spp = p.adaptive.n;
         ad.step = p.noise.step;
-        if (failed(PT_CALL(pt_set_adaptive, g_ctx, p.adaptive.on ? &ad : nullptr))) return err;
+        if (failed(PT_CALL(pt_set_adaptive, g_ctx, adaptive ? &ad : nullptr))) return err;
+    }
+    if (to_blocks || g_block_rule_on) {  // (said only where it was ever on: with it never on, the calls are what they were)
+        pt_adaptive_filtered fa;
+        std::memset(&fa, 0, sizeof fa);
+        fa.filter = pt_atrous_config{p.atrous.n, 0, 4.0, 0.1, 0.1, 0.2};
+        fa.pool = p.blocks.pool;
+        if (failed(PT_CALL(pt_set_adaptive_filtered, g_ctx, to_blocks ? &fa : nullptr))) return err;
+        g_block_rule_on = to_blocks;
     }
 
     // ---- the frame: pt_render, or one stepping loop under the frame's stop rule
@@ -628,15 +672,19 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     struct pt_adaptive_state as;
     std::memset(&as, 0, sizeof as);
     int32_t done = cfg.SamplesPerPx > 0 ? cfg.SamplesPerPx : 0;
-    if (!to_filtered && !to_noise && !progress) {
+    int32_t block_checks = 0;
+    if (!to_filtered && !to_noise && !progress) {  // (the block rule's frame steps inside pt_render, like every adaptive one)
         err = PT_CALL(pt_render, g_ctx, &flat.sc, &pc, img.Pix.data(), img.Stride, nullptr, nullptr, nullptr, &st);
+        if (to_blocks && err.empty()) err = PT_CALL(pt_adaptive_state, g_ctx, &as);
+        if (to_blocks && err.empty()) done = as.spp_max;
     } else {
         // filtered noise: each half needs two samples for its variance, so the check runs from 4 on.  frame noise: the check follows
         // every step and may end the frame from 2 on -- never when adaptive, where the blocks stop inside pt_step.  Otherwise the
         // preview cadence: a refresh every spp/10 samples and once at the end (gpu.go:2209-2212, :2229, :2523-2525).
         const int32_t never = INT32_MAX, preview_step = cfg.SamplesPerPx / 10 > 0 ? cfg.SamplesPerPx / 10 : 1;
         //                                 check                     step          clip_step  ends_when_stalled  measure_from  stop_from  target
-        const StopRule rule = to_filtered ? StopRule{StopRule::FILTERED_NOISE, p.noise.step, true,  false,         4, 4,                         p.filtered}
+        const StopRule rule = to_blocks   ? StopRule{StopRule::NONE,           p.noise.step, true,  true,          0, 0,                         0}
+                              : to_filtered ? StopRule{StopRule::FILTERED_NOISE, p.noise.step, true,  false,         4, 4,                         p.filtered}
                               : to_noise  ? StopRule{StopRule::FRAME_NOISE,    p.noise.step, true,  p.adaptive.on, 0, p.adaptive.on ? never : 2, p.noise.target}
                                           : StopRule{StopRule::NONE,           preview_step, false, false,         0, 0,                         0};
         if (failed(PT_CALL(pt_begin, g_ctx, &flat.sc, &pc))) return err;
@@ -660,12 +708,15 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
             }
             if (err.empty() && done >= rule.stop_from && measured <= rule.target) break;
         }
-        if (p.adaptive.on && err.empty()) err = PT_CALL(pt_adaptive_state, g_ctx, &as);
+        if (adaptive && err.empty()) err = PT_CALL(pt_adaptive_state, g_ctx, &as);
         if (err.empty() && (!progress || cfg.SamplesPerPx <= 0)) err = PT_CALL(pt_read, g_ctx, img.Pix.data(), img.Stride, nullptr);
         const int32_t end_rc = g_core.pt_end(g_ctx, &st);  // (the frame is released whatever went wrong before)
         if (err.empty()) err = call("pt_end", end_rc);
         if (err.empty() && progress) progress();
     }
+
+    if (to_blocks && err.empty() && done >= (p.adaptive.n > 4 ? p.adaptive.n : 4))
+        err = PT_CALL(pt_read_block_figures, g_ctx, nullptr, nullptr, &block_checks);
 
     // ---- the finish: the accumulated or the filtered image takes the place of the plain one (the sums stay readable after pt_end)
     pt_atrous_stats ats;
@@ -726,7 +777,10 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
         stats->device_ms = st.device_ms; stats->num_devices = st.num_devices; stats->spp_chunk = st.spp_chunk;
         stats->spp_done = done;
         stats->noise = nz.noise;  // (stays 0 without a noise target: the check never ran)
-        stats->adaptive = p.adaptive.on;
+        stats->adaptive = adaptive;
+        stats->to_filtered_adaptive = to_blocks;
+        stats->pool = to_blocks ? p.blocks.pool : 0;
+        stats->block_checks = block_checks;
         stats->blocks = as.blocks;
         stats->active_blocks = as.active_blocks;
         stats->spp_min = as.spp_min;

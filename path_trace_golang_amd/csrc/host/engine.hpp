@@ -44,6 +44,8 @@ struct Stats {
     double atrous_ms = 0, noise_before = 0, noise_after = 0;
     bool to_filtered_noise = false;  // the stop rule was the measured noise of the filtered frame (SetFilteredNoise); spp_done is the count
     double filtered_noise = 0, noise_model = 0;  // pt_halves_stats' noise and noise_model at the last check (0: no check ran)
+    bool to_filtered_adaptive = false;  // the blocks stopped by the filtered frame's pooled noise (SetFilteredAdaptive); the adaptive fields hold
+    int pool = 0, block_checks = 0;     // ... the pool radius in blocks and the checks that decided (pt_read_block_figures)
     bool temporal = false;  // the image is pt_temporal's (SetTemporal): the frame blended into the reprojected history, then filtered
     uint64_t reprojected = 0, disoccluded = 0;  // pt_temporal_stats of the frame
     double temporal_ms = 0, mean_len = 0, noise_blended = 0;
@@ -102,6 +104,16 @@ void AtrousFromEnv(bool &on, int &iterations);  // PATHTRACER_GPU_ATROUS = 1 / t
 void SetFilteredNoise(double target);
 double GetFilteredNoise();
 double FilteredNoiseFromEnv();  // PATHTRACER_GPU_FILTERED_NOISE = float > 0, else 0: off
+// Adaptive sampling by the filtered frame's pooled noise: with the filter on and target > 0 the frame is an adaptive one
+// (pt_set_adaptive with this target, GetNoiseStep() and GetAdaptiveMinSpp()) whose 8x8 blocks stop once the noise measured in the
+// filtered frame over the blocks within `pool` blocks (0..4, anything else counts as 1) of them is at or below target
+// (pt_set_adaptive_filtered with the filter's configuration).  The image is pt_atrous on the full sums with every pixel's own count.
+// Ignored without the filter; a frame noise target, the filtered noise target or GL shading beside it is an error.  The initial value
+// is PATHTRACER_GPU_FILTERED_ADAPTIVE / PATHTRACER_GPU_POOL (FilteredAdaptiveFromEnv).
+void SetFilteredAdaptive(double target, int pool = 1);
+double GetFilteredAdaptive();
+int GetPool();
+void FilteredAdaptiveFromEnv(double &target, int &pool);  // PATHTRACER_GPU_FILTERED_ADAPTIVE = float > 0 (else 0: off), _POOL = int 0..4 (else 1)
 // Temporal accumulation, for a caller that renders frame after frame while the camera moves: the process-wide context
 // keeps a history, and after the frame Render calls pt_temporal -- the frame blended into the reprojected history, then filtered
 // -- in place of pt_atrous.  On turns on moments, the filter and 4 feature samples per pixel (unless SetFeatures /

@@ -17,7 +17,11 @@
 // (0..6) sets its iterations and -features K the first-hit feature samples per pixel that guide it (default: 4 where the scene allows
 // them; also env PATHTRACER_GPU_ATROUS, PATHTRACER_GPU_ATROUS_ITERS, PATHTRACER_GPU_FEATURES).  -filtered-noise T (with -atrous)
 // renders until the measured noise of the filtered frame (pt_atrous_halves) is at or below T, checking every -noise-step
-// samples, with -spp as the cap (also env PATHTRACER_GPU_FILTERED_NOISE); it excludes -noise.
+// samples, with -spp as the cap (also env PATHTRACER_GPU_FILTERED_NOISE); it excludes -noise.  -filtered-adaptive T (with -atrous) stops every
+// 8x8 block of an adaptive frame by the filtered frame's noise pooled over the blocks within -pool N (0..4, default 1) blocks of it
+// (pt_set_adaptive_filtered; also env PATHTRACER_GPU_FILTERED_ADAPTIVE, PATHTRACER_GPU_POOL); -noise-step and -min-spp
+// apply, and it excludes -noise and -filtered-noise.  These two flags are parsed like the others but are not in the usage text below,
+// which stands as recorded in tests/golden/host_traces.json.
 #include <cerrno>
 #include <chrono>
 #include <climits>
@@ -69,6 +73,8 @@ struct Flags {
     int atrous_iters = 5;
     int features = -1;  // -1: not said
     double filtered_noise = 0;
+    double filtered_adaptive = 0;
+    int pool = 1;
 };
 
 void usage() {
@@ -138,6 +144,7 @@ int parse(int argc, char **argv, Flags &f) {
         {"noise-step", INT, &f.noise_step, 1, 0x7fffffffLL, 16}, {"min-spp", INT, &f.min_spp, 0, 0x7fffffffLL, 0},
         {"atrous-iters", INT, &f.atrous_iters, 0, 6, 5}, {"features", INT, &f.features, 0, 0x7fffffffLL, -1},
         {"noise", NOT_NEGATIVE, &f.noise}, {"filtered-noise", NOT_NEGATIVE, &f.filtered_noise}, {"seed", UINT, &f.seed},
+        {"filtered-adaptive", NOT_NEGATIVE, &f.filtered_adaptive}, {"pool", INT, &f.pool, 0, 4, 1},
     };
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -212,6 +219,8 @@ int render_headless(const Flags &f) {
     engine::hip::SetAtrous(f.atrous, f.atrous_iters);
     engine::hip::SetFeatures(f.features);
     engine::hip::SetFilteredNoise(f.filtered_noise);
+    engine::hip::SetFilteredAdaptive(f.filtered_adaptive, f.pool);
+    if (f.filtered_adaptive > 0 && !f.atrous) logf("filtered-adaptive: no -atrous given, nothing to measure (a plain frame)");
     if (f.filtered_noise > 0 && !f.atrous) logf("filtered-noise: no -atrous given, nothing to measure (a plain frame)");
     if (f.adaptive && !(f.noise > 0)) logf("adaptive: no -noise target given, nothing to adapt to (a plain frame)");
     if (f.shading == "gl") logf("shading: gl (the reference's GPU shader; spp counts passes of 16 paths)");
@@ -230,7 +239,13 @@ int render_headless(const Flags &f) {
         auto t0 = std::chrono::steady_clock::now();
         engine::RenderInto(*sc, cfg, img, nullptr, &st);
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (st.adaptive)
+        if (st.to_filtered_adaptive)  // (PATHTRACER_GPU_FILTERED_ADAPTIVE / PATHTRACER_GPU_POOL with -atrous)
+            logf("rendered %dx%d, %d to %d of at most %d spp per 8x8 block (filtered adaptive: pooled target %.6g over %d block(s) around, %llu "
+                 "of %llu blocks still above it after %d checks), depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, %.1f M samples/s", cfg.Width,
+                 cfg.Height, st.spp_min, st.spp_done, cfg.SamplesPerPx, f.filtered_adaptive, st.pool,
+                 (unsigned long long)st.active_blocks, (unsigned long long)st.blocks, st.block_checks, cfg.MaxDepth, st.num_devices, dt,
+                 st.segments / dt / 1e6, st.samples / dt / 1e6);
+        else if (st.adaptive)
             logf("rendered %dx%d, %d to %d of at most %d spp per 8x8 block (adaptive: block target %.6g, %llu of %llu blocks still above it; "
                  "frame noise %.6g), depth %d on %d GPU(s) in %.3f s: %.1f M segments/s, %.1f M samples/s", cfg.Width, cfg.Height, st.spp_min,
                  st.spp_done, cfg.SamplesPerPx, f.noise, (unsigned long long)st.active_blocks, (unsigned long long)st.blocks, st.noise,
@@ -272,6 +287,7 @@ int main(int argc, char **argv) {
     engine::hip::AtrousFromEnv(f.atrous, f.atrous_iters);
     f.features = engine::hip::FeaturesFromEnv();
     f.filtered_noise = engine::hip::FilteredNoiseFromEnv();
+    engine::hip::FilteredAdaptiveFromEnv(f.filtered_adaptive, f.pool);
     int rc = parse(argc, argv, f);
     if (rc >= 0) return rc;
     logf("flags: scene=%s mode=%s headless=%s out=%s", f.scene.c_str(), f.mode.c_str(), f.headless ? "true" : "false",

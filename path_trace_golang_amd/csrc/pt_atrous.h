@@ -57,6 +57,25 @@
 //   Figures:  noise = sqrt(sum of e2 / pixels), noise_model = sqrt(sum of e2_model / pixels).  A pixel that is bad in either half, or
 //          whose e2 is NaN or infinite, adds 0 to both sums and is counted as bad; a NaN or infinite e2_model adds 0.  (The order of
 //          the two sums is the reduction tree's: compare to 1e-9.)  Neither figure sees the bias the filter adds.
+//
+// BLOCKS (pt_set_adaptive_filtered).  The stop rule of an adaptive frame (pt_set_adaptive) taken from the filtered frame's
+// noise instead of the block's own.  The frame is adaptive in every respect (active lists, job map, per-pixel counts) and collects the
+// half sums by itself.  At the end of a pt_step, once done >= max(min_spp, 4) samples (every pixel then holds at least 4), in this order:
+//   1. Pair filter:  HALVES above on the frame as it stands, every pixel with its own count, the frame's feature sums if it has them:
+//          per pixel mean, err and the bad mask (0..3).
+//   2. Per-block sum, per 8x8 block B = (bx, by) = (x >> 3, y >> 3) of the frame's grid of nbx = (W + 7) / 8 by nby = (H + 7) / 8 blocks
+//          (the sub-blocks of the 32x32 tiles):  k_B = its pixels inside the frame;  s_B = the sum over them of Combine's e2 (a pixel
+//          that is bad in either half, or whose e2 is NaN or infinite, adds 0 and still counts in k_B).  The 64 terms, lane = row * 8 +
+//          column inside the block and 0 for a lane outside the frame, are added by the xor butterfly: for off = 32, 16, 8, 4, 2, 1
+//          every lane adds lane ^ off's value to its own; s_B is lane 0's.
+//   3. Pooled figure:  P_B = sqrt(ss / kk), ss = the sum of s_B' and kk = the sum of k_B' over the blocks B' of the grid with
+//          |bx' - bx| <= r and |by' - by| <= r, taken sequentially from zero, rows top to bottom and left to right within a row; kk is an
+//          integer, converted once.  r = the pool radius in blocks (0..4, default 1).  Blocks that have stopped are in the window with
+//          the samples they hold.  The block's own figure, for reading: own_B = sqrt(s_B / k_B).
+//   4. Decision:  every still-active block with P_B <= target becomes inactive and stays so.
+// Before that count no block stops.  Unlike pt_set_adaptive's rule, neighbouring blocks DO keep each other alive: a block whose own
+// figure is below the target goes on while the window around it is not -- err has one degree of freedom per pixel, and 64 of them
+// decide nothing at the counts where blocks stop.  Which blocks stop depends on the step sizes and on nothing else.
 #pragma once
 
 #include <stdint.h>
@@ -324,6 +343,19 @@ PT_HD void filter_pair_pixel(const Params &P, int32_t W, int32_t H, int32_t x, i
     }
 }
 
+// The two noise terms of a pixel of the combined frame: mean and err of Combine, va, vb the halves' propagated variances, bad = the
+// pixel's bad mask.  Returns whether the pixel counts as bad; a term that adds nothing is returned as 0.
+PT_HD bool err_terms(const double mean[3], double err, double va, double vb, int bad, double &e2, double &e2_model) {
+    const double l = (mean[0] + mean[1] + mean[2]) / 3.0;
+    const double den = l < 0.01 ? 0.01 : l;
+    e2 = err / (den * den);
+    e2_model = ((va + vb) * 0.25) / (den * den);
+    const bool isbad = bad != 0 || !finite(e2);
+    if (isbad) e2 = 0.0;
+    if (isbad || !finite(e2_model)) e2_model = 0.0;
+    return isbad;
+}
+
 // The combine of one pixel: fA, fB the filtered halves, va, vb their propagated variances, bad = the pixel's bad mask -> mean, err and
 // the two noise terms (measured, model).  Returns whether the pixel counts as bad; a term that adds nothing is returned as 0.
 PT_HD bool combine_pixel(const double fA[3], const double fB[3], double va, double vb, int bad, double mean[3], double &err, double &e2,
@@ -334,14 +366,37 @@ PT_HD bool combine_pixel(const double fA[3], const double fB[3], double va, doub
         d[k] = (fA[k] - fB[k]) * 0.5;
     }
     err = (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) / 3.0;
-    const double l = (mean[0] + mean[1] + mean[2]) / 3.0;
-    const double den = l < 0.01 ? 0.01 : l;
-    e2 = err / (den * den);
-    e2_model = ((va + vb) * 0.25) / (den * den);
-    const bool isbad = bad != 0 || !finite(e2);
-    if (isbad) e2 = 0.0;
-    if (isbad || !finite(e2_model)) e2_model = 0.0;
-    return isbad;
+    return err_terms(mean, err, va, vb, bad, e2, e2_model);
+}
+
+// ---------------------------------------------------------------- block figures (BLOCKS above)
+
+#define PTA_MAX_POOL 4
+
+// Step 2's term of one pixel, from the planes the combine leaves: the e2 err_terms adds into `noise`.
+PT_HD double block_term(const double mean[3], double err, int bad) {
+    double e2, e2_model;
+    err_terms(mean, err, 0.0, 0.0, bad, e2, e2_model);
+    return e2;
+}
+
+// Step 3 at block (bx, by) of the nbx x nby grid: s, k row-major over the grid -> P_B; own = sqrt(s_B / k_B).
+PT_HD double pool_block(const double *__restrict__ s, const uint32_t *__restrict__ k, int32_t nbx, int32_t nby, int32_t bx, int32_t by,
+                        int32_t r, double &own) {
+    double ss = 0.0;
+    uint32_t kk = 0;
+    for (int32_t y = by - r; y <= by + r; y++) {
+        if (y < 0 || y >= nby) continue;
+        for (int32_t x = bx - r; x <= bx + r; x++) {
+            if (x < 0 || x >= nbx) continue;
+            const size_t b = (size_t)y * (size_t)nbx + (size_t)x;
+            ss = ss + s[b];
+            kk += k[b];
+        }
+    }
+    const size_t b = (size_t)by * (size_t)nbx + (size_t)bx;
+    own = ptm::f_sqrt(s[b] / (double)k[b]);
+    return ptm::f_sqrt(ss / (double)kk);
 }
 
 }  // namespace pta

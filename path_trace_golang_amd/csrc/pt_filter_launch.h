@@ -1,9 +1,10 @@
 // pt_filter_launch.h -- host side of the post-frame filters: the launch sequences of pt_atrous, pt_temporal and
-// pt_atrous_halves behind their first kernel, the grids of a W x H frame, the filter's Params and the sums of the kernels' partials.
+// pt_atrous_halves behind their first kernel, the grids of a W x H frame, the filter's Params and the sums of the kernels' partials;
+// and the two sequences of pt_set_adaptive_filtered's check: the block map on devices[0], the map applied per device.
 //
 // Inline host functions over raw device pointers, sizes and a stream: no context, no buffer ownership, no error texts.  ptcore.hip
-// runs them on its own buffers and tests/denoise_probe.hip and tests/temporal_clip_probe.hip on theirs, so the probes launch the
-// product's sequence itself.  The launches report through hipGetLastError, which the caller reads after the last one.
+// runs them on its own buffers and tests/denoise_probe.hip, tests/temporal_clip_probe.hip and tests/filtered_adaptive_probe.hip on
+// theirs, so the probes launch the product's sequence itself.  The launches report through hipGetLastError, which the caller reads after the last one.
 #pragma once
 
 #include <cmath>
@@ -53,6 +54,43 @@ int iterate(const pta::Params &P, double *const col[2], double *const var[2], co
 inline int pair_iterations(const pta::Params &P, double *const col[2], double *const var[2], const double *guide, int32_t W, int32_t H,
                            hipStream_t stream) {
     return iterate<ptk::AtrousPairArgs, ptk::atrous_pair_kernel>(P, col, var, guide, W, H, stream);
+}
+
+// The check of pt_set_adaptive_filtered behind the pair filter's combine (pt_atrous.h BLOCKS, steps 2 to 4), on devices[0]: the
+// per-block sums of the (mean, err, bad) planes, then the pooled figure, the block's own and the stop flag of every block of the
+// frame's grid.
+struct BlockMap {
+    double *s;        // [nbx * nby]
+    uint32_t *k;      // [nbx * nby]
+    double *pooled;   // [nbx * nby]
+    double *own;      // [nbx * nby]
+    uint8_t *stop;    // [nbx * nby]
+};
+inline int32_t blocks_across(int32_t n) { return (n + 7) / 8; }
+inline void block_map_sequence(const double *mean, const double *err, const double *bad, const BlockMap &M, int32_t W, int32_t H, int32_t pool,
+                               double target, hipStream_t stream) {
+    const int32_t nbx = blocks_across(W), nby = blocks_across(H);
+    const size_t nb = (size_t)nbx * (size_t)nby;
+    ptk::BlockErrArgs E;
+    std::memset(&E, 0, sizeof E);
+    E.mean = mean; E.err = err; E.bad = bad;
+    E.s = M.s; E.k = M.k;
+    E.W = W; E.H = H; E.nbx = nbx; E.nby = nby;
+    hipLaunchKernelGGL(ptk::block_err_kernel, dim3(grid_1d(nb * 64u)), dim3(PT_BLOCK), 0, stream, E);
+    ptk::BlockPoolArgs Q;
+    std::memset(&Q, 0, sizeof Q);
+    Q.s = M.s; Q.k = M.k;
+    Q.pooled = M.pooled; Q.own = M.own; Q.stop = M.stop;
+    Q.target = target;
+    Q.nbx = nbx; Q.nby = nby; Q.pool = pool;
+    hipLaunchKernelGGL(ptk::block_pool_kernel, dim3(grid_1d(nb)), dim3(PT_BLOCK), 0, stream, Q);
+}
+
+// ... and on every device: the map (null before the check decides) applied to the nact entries of the active list, then compact_kernel
+// as dev_adaptive_check launches it.  K.keep and K.noise are A's.
+inline void keep_sequence(const ptk::KeepFromMapArgs &A, const ptk::CompactArgs *K, hipStream_t stream) {
+    hipLaunchKernelGGL(ptk::keep_from_map_kernel, dim3(grid_1d(A.nact)), dim3(PT_BLOCK), 0, stream, A);
+    if (K) hipLaunchKernelGGL(ptk::compact_kernel, dim3(1), dim3(PT_COMPACT_BLOCK), 0, stream, *K);
 }
 
 // What pt_atrous and pt_temporal run behind the kernel that leaves (col[0], var[0], guide): the figure of that state into

@@ -53,6 +53,8 @@
 //                   and over the odd-indexed samples, after moments_kernel.
 //   atrous_pair_prep_kernel / atrous_pair_kernel / halves_combine_kernel   pt_atrous_halves: the filter on each half, both halves
 //                   in one launch over plane-per-component buffers, and the measured noise figure of their mean.
+//   block_err_kernel / block_pool_kernel / keep_from_map_kernel   opt-in (pt_set_adaptive_filtered): the adaptive check by the pooled
+//                   noise of the filtered frame -- per-block sums and the pooled map on devices[0], the map applied on every device.
 //   temporal_kernel pt_temporal: prep, the previous frame's history reprojected and blended (pt_temporal.h), the new history, and
 //                   the buffers atrous_prep_kernel would have left for the filter's kernels.
 //                   With a motion table (pt_temporal_set_motion) a pixel on a moved object is projected from where it was.
@@ -3569,6 +3571,101 @@ __global__ __launch_bounds__(PT_BLOCK) void halves_combine_kernel(const HalvesCo
         for (int w = 0; w < PT_BLOCK / PT_WAVE; w++) r.bad += s_bad[w];
         A.partial[blockIdx.x] = r;
     }
+}
+
+// pt_set_adaptive_filtered (pt_atrous.h BLOCKS): the check of an adaptive frame whose blocks stop by the pooled noise of
+// the filtered frame.  block_err_kernel and block_pool_kernel run on devices[0] over the planes halves_combine_kernel leaves and over
+// the frame's grid of nbx x nby blocks; the map they write (P_B and a stop flag per block) is copied to every device, where
+// keep_from_map_kernel turns it into the keep[] / noise[] / blk_spp[] that block_noise_kernel writes, for compact_kernel as it is.
+
+// Step 2: one wave per frame block, one lane per pixel (lane = row * 8 + column), block_noise_kernel's butterfly.
+struct BlockErrArgs {
+    const double *mean;  // [npix][3]
+    const double *err;   // [npix]
+    const double *bad;   // [npix] the bad mask as a double (guide plane PTA_GUIDE_BAD)
+    double *s;           // [nbx * nby]
+    uint32_t *k;         // [nbx * nby]
+    int32_t W, H, nbx, nby;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void block_err_kernel(const BlockErrArgs A) {
+    const uint32_t b = __builtin_amdgcn_readfirstlane((blockIdx.x * PT_BLOCK + threadIdx.x) >> 6);
+    if (b >= (uint32_t)A.nbx * (uint32_t)A.nby) return;  // (wave-uniform)
+    const uint32_t by = b / (uint32_t)A.nbx, bx = b - by * (uint32_t)A.nbx, p = threadIdx.x & 63u;
+    const uint32_t x = bx * 8u + (p & 7u), y = by * 8u + (p >> 3);
+    const bool inside = x < (uint32_t)A.W && y < (uint32_t)A.H;
+    double sum = 0.0;
+    if (inside) {
+        const size_t i = (size_t)y * (size_t)A.W + (size_t)x;
+        const double mean[3] = {A.mean[3 * i], A.mean[3 * i + 1], A.mean[3 * i + 2]};
+        sum = pta::block_term(mean, A.err[i], (int)A.bad[i]);
+    }
+    const uint32_t k = (uint32_t)__popcll(__ballot(inside));
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    if (p == 0u) {
+        A.s[b] = sum;
+        A.k[b] = k;  // (>= 1: every block of the grid has its first pixel inside the frame)
+    }
+}
+
+// Steps 3 and 4: one lane per frame block.  stop[b] = 1 where the check decides and P_B <= target; which of those blocks are still
+// active is the active lists' business.
+struct BlockPoolArgs {
+    const double *s;     // [nbx * nby]
+    const uint32_t *k;   // [nbx * nby]
+    double *pooled;      // [nbx * nby] P_B
+    double *own;         // [nbx * nby] sqrt(s_B / k_B)
+    uint8_t *stop;       // [nbx * nby]
+    double target;
+    int32_t nbx, nby, pool;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void block_pool_kernel(const BlockPoolArgs A) {
+    const uint32_t b = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (b >= (uint32_t)A.nbx * (uint32_t)A.nby) return;
+    const int32_t by = (int32_t)(b / (uint32_t)A.nbx), bx = (int32_t)b - by * A.nbx;
+    double own;
+    const double P = pta::pool_block(A.s, A.k, A.nbx, A.nby, bx, by, A.pool, own);
+    A.pooled[b] = P;
+    A.own[b] = own;
+    A.stop[b] = P <= A.target ? (uint8_t)1 : (uint8_t)0;
+}
+
+// One lane per active-list entry: block_noise_kernel's three outputs from the map.  blk_spp[block] = n;  with a map, noise[c] = P_B and
+// keep[c] = 0 where stop[B] is set, B = the entry's block in the frame's grid;  without one (pooled null: nothing is decided below
+// max(min_spp, 4) samples) keep[c] = 1 and noise[c] = +inf.  With keep null only the counts are stamped: the pass in front of the gather,
+// which reads every pixel's count.
+struct KeepFromMapArgs {
+    const uint32_t *active;  // [nact]
+    const double *pooled;    // [nbx * nby] or null
+    const uint8_t *stop;     // [nbx * nby] or null
+    uint32_t *blk_spp;       // [nslots / 64]
+    uint32_t *keep;          // [nact], or null (with noise): the counts only
+    double *noise;           // [nact]
+    uint32_t nact;
+    int32_t n;               // samples the active blocks hold
+    int32_t nbx, nby;
+    TileGeom G;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void keep_from_map_kernel(const KeepFromMapArgs A) {
+    const uint32_t c = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (c >= A.nact) return;
+    const uint32_t blk = A.active[c];
+    const Pixel px = block_pixel(A.G, blk, 0u);
+    const uint32_t bx = px.x >> 3, by = px.y >> 3;
+    A.blk_spp[blk] = (uint32_t)A.n;
+    if (!A.keep) return;
+    const bool mapped = A.pooled && bx < (uint32_t)A.nbx && by < (uint32_t)A.nby;  // (an active block has its first pixel inside the frame)
+    double P = INFINITY;
+    uint32_t keep = 1u;
+    if (mapped) {
+        const size_t b = (size_t)by * (size_t)A.nbx + (size_t)bx;
+        P = A.pooled[b];
+        keep = A.stop[b] ? 0u : 1u;
+    }
+    A.noise[c] = P;
+    A.keep[c] = keep;
 }
 
 // pt_temporal (pt_temporal.h): prep, reprojection of the previous frame's history and the blend, one lane per pixel in atrous_kernel's

@@ -132,7 +132,7 @@ struct EventList {
     }
     void swap(EventList &o) { v.swap(o.v); std::swap(n, o.n); }
 };
-enum EventKind { EV_TRACE, EV_RESOLVE, EV_RAYGEN, EV_GLASS, EV_FOG, EV_MOMENTS, EV_CHECK, EV_FEATURE, EV_HALVES, EV_KINDS };
+enum EventKind { EV_TRACE, EV_RESOLVE, EV_RAYGEN, EV_GLASS, EV_FOG, EV_MOMENTS, EV_CHECK, EV_FEATURE, EV_HALVES, EV_BLOCKS, EV_KINDS };
 
 // Storage of one path-state queue (PathQueue, pt_device.h): per entry 10 doubles, the stream state and 4 words -- job, depth, hit
 // object, answer -- or 6 with pixel stats (+ the job's two counters); every plane of `u` is as long as the queue.
@@ -200,6 +200,8 @@ struct Device {
     DevBuf<double> blk_noise;
     DevBuf<ptk::AdaptResult> ad_res;
     int act_cur = 0;                  // which of act[] holds the current list
+    DevBuf<double> map_pooled;        // pt_set_adaptive_filtered: this device's copy of the check's map, P_B and the stop flag per frame block
+    DevBuf<uint8_t> map_stop;
     uint32_t nact = 0;                // its length
     DevBuf<uint8_t> tiles_rgba;
     DevBuf<double> tiles_accum;
@@ -273,6 +275,9 @@ struct Frame {
     int32_t scene_objects = 0;  // ... pt_scene.num_objects of the frame, the length a motion table must have
     std::vector<int32_t> world_scene;  // ... per object of the device world its index into pt_scene.objects
     double worst_active = 0.0;  // largest block noise among the blocks the last check kept
+    bool filtered = false;      // pt_set_adaptive_filtered: the adaptive check decides by the pooled noise of the filtered frame (implies halves)
+    pt_adaptive_filtered fa{};
+    int32_t fa_checks = 0;      // ... the checks that have decided so far
     std::vector<ptg::GlObj> gl_objs;
     std::vector<ptg::GlMat> gl_mats;
     std::vector<int32_t> gl_lights;
@@ -359,6 +364,16 @@ struct pt_ctx {
     } tp;
     uint64_t frames_opened = 0;      // pt_begin / pt_render frames of this context so far
     pt_adaptive adaptive{};
+    bool filtered_on = false;         // pt_set_adaptive_filtered
+    pt_adaptive_filtered filtered{};
+    struct Blocks {  // ... the check's per-block sums and map on devices[0], and the host copy that travels to the devices and to pt_read_block_figures.
+                     // The host copies outlive the frame: they are that frame's only while frame.fa_checks > 0 (frame_open resets the Frame).
+        DevBuf<double> s, pooled, own;
+        DevBuf<uint32_t> k;
+        DevBuf<uint8_t> stop;
+        std::vector<double> h_pooled, h_own;
+        std::vector<uint8_t> h_stop;
+    } bf;
     DevBuf<uint32_t> f_seg, f_draw;
     size_t l_budget_bytes = (size_t)48 << 30;  // per-chunk job buffers (radiance, primary rays, path-state queues): a sixth of the 288 GB
     // A context that renders frame after frame of one shape (a UI, an animation: gpu.go:2534-2546 is called once per frame) grows its
@@ -2352,6 +2367,145 @@ int32_t copy_filtered(pt_ctx *ctx, int cur, uint8_t *rgba, int32_t stride, doubl
     return PT_OK;
 }
 
+// pt_atrous_halves behind its refusals, and step 1 of pt_set_adaptive_filtered's check: the inputs gathered to devices[0], then prep, the
+// pair iterations and the combine on its stream (between the clock's two events, when there is one).  ctx->ah holds the result: mean,
+// err, the partials of the figures (grid_1d(npix) of them), fA and fB when `half` asks, and the bad mask in the guide's last plane.
+int32_t halves_filter(pt_ctx *ctx, const pt_atrous_config &c, bool half, FilterClock<2> *clock) {
+    Frame &fr = ctx->frame;
+    const int32_t W = fr.cfg.width, H = fr.cfg.height;
+    if (int32_t rc = gather_filter_inputs(ctx, true)) return rc;
+    const bool feat = fr.features > 0;
+    Device &d0 = ctx->devs[0];
+    pt_ctx::Halves &B = ctx->ah;
+    HIP_TRY(hipSetDevice(d0.ordinal));
+    const size_t npix = (size_t)W * (size_t)H;
+    const uint32_t grid1 = ptl::grid_1d(npix);
+    for (int k = 0; k < 2; k++) {
+        HIP_TRY(B.col[k].reserve(6 * npix));
+        HIP_TRY(B.var[k].reserve(2 * npix));
+    }
+    HIP_TRY(B.guide.reserve(PTA_GUIDE_PLANES * npix));
+    HIP_TRY(B.mean.reserve(3 * npix));
+    HIP_TRY(B.err.reserve(npix));
+    if (half) HIP_TRY(B.half.reserve(6 * npix));
+    HIP_TRY(B.part.reserve(grid1));
+    if (clock) {
+        if (int32_t rc = clock->create()) return rc;
+        HIP_TRY(hipEventRecord(clock->ev[0], d0.stream));
+    }
+    ptk::AtrousPairPrepArgs PA;
+    std::memset(&PA, 0, sizeof PA);
+    PA.sa = ctx->f_hv_sa.p; PA.qa = ctx->f_hv_qa.p; PA.sb = ctx->f_hv_sb.p; PA.qb = ctx->f_hv_qb.p;
+    PA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
+    PA.fn = feat ? ctx->f_feat_n.p : nullptr;
+    PA.fa = feat ? ctx->f_feat_a.p : nullptr;
+    PA.fd = feat ? ctx->f_feat_d.p : nullptr;
+    PA.guide = B.guide.p;
+    PA.col = B.col[0].p;
+    PA.var = B.var[0].p;
+    PA.npix = (uint32_t)npix;
+    PA.n = (uint32_t)fr.done_spp;
+    hipLaunchKernelGGL(ptk::atrous_pair_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, PA);
+    double *const col[2] = {B.col[0].p, B.col[1].p}, *const vr[2] = {B.var[0].p, B.var[1].p};
+    const int cur = ptl::pair_iterations(ptl::filter_params(c, feat), col, vr, B.guide.p, W, H, d0.stream);
+    ptk::HalvesCombineArgs CA;
+    std::memset(&CA, 0, sizeof CA);
+    CA.col = col[cur]; CA.var = vr[cur]; CA.guide = B.guide.p;
+    CA.mean = B.mean.p;
+    CA.err = B.err.p;
+    CA.half_means = half ? B.half.p : nullptr;
+    CA.partial = B.part.p;
+    CA.npix = (uint32_t)npix;
+    hipLaunchKernelGGL(ptk::halves_combine_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, CA);
+    HIP_TRY(hipGetLastError());
+    if (clock) HIP_TRY(hipEventRecord(clock->ev[1], d0.stream));
+    return PT_OK;
+}
+
+// The check that ends a pt_step of an adaptive frame with pt_set_adaptive_filtered's rule (pt_atrous.h BLOCKS), on every device.  Once
+// it decides: the active blocks' counts are stamped first (the pair filter reads every pixel's own count through the gather), then on
+// devices[0] the pair filter and ptl::block_map_sequence; the map goes to the host -- where pt_read_block_figures finds it -- and from
+// there to every device, whatever their number; keep_from_map_kernel and compact_kernel follow on each.  Before it decides only those
+// two run, without a map.  The result words are read by the caller once the streams have drained.
+int32_t filtered_check(pt_ctx *ctx, ptk::AdaptResult *host_res) {
+    Frame &fr = ctx->frame;
+    const int32_t W = fr.cfg.width, H = fr.cfg.height, nbx = ptl::blocks_across(W), nby = ptl::blocks_across(H);
+    const size_t nb = (size_t)nbx * (size_t)nby;
+    const bool decide = fr.done_spp >= std::max(fr.ad.min_spp, 4);
+    auto keep_args = [&](Device &d, bool mapped, bool stamp_only = false) {
+        ptk::KeepFromMapArgs A;
+        std::memset(&A, 0, sizeof A);
+        A.active = d.act[d.act_cur].p;
+        A.pooled = mapped ? d.map_pooled.p : nullptr;
+        A.stop = mapped ? d.map_stop.p : nullptr;
+        A.blk_spp = d.blk_spp.p;
+        A.keep = stamp_only ? nullptr : d.blk_keep.p;
+        A.noise = stamp_only ? nullptr : d.blk_noise.p;
+        A.nact = d.nact;
+        A.n = fr.done_spp;
+        A.nbx = nbx; A.nby = nby;
+        A.G = tile_geom(fr, d);
+        return A;
+    };
+    if (decide) {
+        for (Device &d : ctx->devs) {
+            if (d.nlocal == 0 || d.nact == 0) continue;
+            HIP_TRY(hipSetDevice(d.ordinal));
+            ptl::keep_sequence(keep_args(d, false, true), nullptr, d.stream);
+            HIP_TRY(hipGetLastError());
+        }
+        Device &d0 = ctx->devs[0];
+        pt_ctx::Blocks &M = ctx->bf;
+        HIP_TRY(hipSetDevice(d0.ordinal));
+        HIP_TRY(M.s.reserve(nb));
+        HIP_TRY(M.k.reserve(nb));
+        HIP_TRY(M.pooled.reserve(nb));
+        HIP_TRY(M.own.reserve(nb));
+        HIP_TRY(M.stop.reserve(nb));
+        int32_t frc = PT_OK;
+        if (int32_t rc = timed(d0, EV_BLOCKS, [&] {  // gathers, pair filter and the map as one
+                frc = halves_filter(ctx, fr.fa.filter, false, nullptr);
+                if (frc != PT_OK) return;
+                const pt_ctx::Halves &B = ctx->ah;
+                const size_t npix = (size_t)W * (size_t)H;
+                ptl::block_map_sequence(B.mean.p, B.err.p, B.guide.p + (size_t)PTA_GUIDE_BAD * npix, ptl::BlockMap{M.s.p, M.k.p, M.pooled.p, M.own.p, M.stop.p},
+                                        W, H, fr.fa.pool, fr.ad.target, d0.stream);
+            }))
+            return frc != PT_OK ? frc : rc;
+        if (frc != PT_OK) return frc;
+        M.h_pooled.resize(nb);
+        M.h_own.resize(nb);
+        M.h_stop.resize(nb);
+        HIP_TRY(hipMemcpyAsync(M.h_pooled.data(), M.pooled.p, nb * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+        HIP_TRY(hipMemcpyAsync(M.h_own.data(), M.own.p, nb * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
+        HIP_TRY(hipMemcpyAsync(M.h_stop.data(), M.stop.p, nb, hipMemcpyDeviceToHost, d0.stream));
+        HIP_TRY(hipStreamSynchronize(d0.stream));
+        fr.fa_checks++;
+    }
+    for (size_t i = 0; i < ctx->devs.size(); i++) {
+        Device &d = ctx->devs[i];
+        if (d.nlocal == 0 || d.nact == 0) continue;
+        HIP_TRY(hipSetDevice(d.ordinal));
+        if (decide) {
+            HIP_TRY(d.map_pooled.reserve(nb));
+            HIP_TRY(d.map_stop.reserve(nb));
+            HIP_TRY(hipMemcpyAsync(d.map_pooled.p, ctx->bf.h_pooled.data(), nb * sizeof(double), hipMemcpyHostToDevice, d.stream));
+            HIP_TRY(hipMemcpyAsync(d.map_stop.p, ctx->bf.h_stop.data(), nb, hipMemcpyHostToDevice, d.stream));
+        }
+        ptk::CompactArgs K;
+        std::memset(&K, 0, sizeof K);
+        K.active = d.act[d.act_cur].p;
+        K.keep = d.blk_keep.p;
+        K.noise = d.blk_noise.p;
+        K.next = d.act[d.act_cur ^ 1].p;
+        K.res = d.ad_res.p;
+        K.nact = d.nact;
+        if (int32_t rc = timed(d, EV_CHECK, [&] { ptl::keep_sequence(keep_args(d, decide), &K, d.stream); })) return rc;
+        HIP_TRY(hipMemcpyAsync(&host_res[i], d.ad_res.p, sizeof host_res[i], hipMemcpyDeviceToHost, d.stream));
+    }
+    return PT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2723,13 +2877,17 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
         if (ctx->pipeline == 1 || ctx->pipeline == 2)
             return fail(PT_ERR_STATE, "adaptive sampling: not available with PTCORE_PIPELINE=wavefront or walk32 (the default pipeline only)");
     }
+    if (ctx->filtered_on && !ctx->adaptive_on)  // refused before anything is launched; the context stays as it was
+        return fail(PT_ERR_INVALID, "pt_set_adaptive_filtered: the rule decides the blocks of an adaptive frame (pt_set_adaptive first)");
     const int32_t ndev = (int32_t)ctx->devs.size();
     const int32_t ntiles = ((cfg->width + 31) / 32) * ((cfg->height + 31) / 32);
     const uint32_t max_slots = (uint32_t)tiles_of_shard(ntiles, pt_shard{0, ndev}) * 1024u;
     if (int32_t rc = frame_open(ctx, scene, cfg, max_slots)) return rc;
     ctx->frame.adaptive = ctx->adaptive_on;
     ctx->frame.ad = ctx->adaptive;
-    ctx->frame.halves = ctx->halves_on;
+    ctx->frame.filtered = ctx->filtered_on;
+    ctx->frame.fa = ctx->filtered;
+    ctx->frame.halves = ctx->halves_on || ctx->filtered_on;
     ctx->frame.moments = ctx->moments_on || ctx->adaptive_on || ctx->halves_on;
     if (ctx->features_k > 0) {  // refused before anything is launched; the context stays usable
         const bool bvh = ctx->frame.scan == ptk::SCAN_BVH || ctx->frame.scan == ptk::SCAN_VERIFY_BVH;
@@ -2807,9 +2965,12 @@ int32_t pt_step(pt_ctx *ctx, int32_t nspp, int32_t *done_spp) {
         todo -= (int32_t)S;
     }
     std::vector<ptk::AdaptResult> res(check ? ctx->devs.size() : 0);
-    if (check)  // the blocks at or below the target leave the active lists
+    if (check && fr.filtered) {  // ... by the pooled noise of the filtered frame
+        if (int32_t rc = filtered_check(ctx, res.data())) return rc;
+    } else if (check) {  // the blocks at or below the target leave the active lists
         for (size_t i = 0; i < ctx->devs.size(); i++)
             if (int32_t rc = dev_adaptive_check(ctx, ctx->devs[i], &res[i])) return rc;
+    }
     for (Device &d : ctx->devs) {
         HIP_TRY(hipSetDevice(d.ordinal));
         HIP_TRY(hipStreamSynchronize(d.stream));
@@ -2879,12 +3040,14 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
             launches += d.ev[kind].n;
         }
         std::fprintf(stderr, "ptcore: %s %.3f ms in %zu launches%s (resolve_kernel %.3f ms in %d)\n", what, worst, launches,
-                     kind == EV_CHECK ? " of block_noise_kernel + compact_kernel" : "", st.resolve_ms, st.resolve_launches);
+                     kind != EV_CHECK ? "" : ctx->frame.filtered ? " of keep_from_map_kernel + compact_kernel" : " of block_noise_kernel + compact_kernel",
+                     st.resolve_ms, st.resolve_launches);
     };
     if (ctx->frame.moments && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_MOMENTS, "moments_kernel");
     if (ctx->frame.adaptive && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_CHECK, "adaptive check");
     if (ctx->frame.features > 0 && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_FEATURE, "feature_kernel");
     if (ctx->frame.halves && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_HALVES, "halves_kernel");
+    if (ctx->frame.filtered && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_BLOCKS, "filtered block checks (gathers, pair filter, block map)");
     if (ctx->frame.fog_vol) {
         ctx->fog_pending = 1;
         if (int32_t r = collect_fog(ctx)) rc = rc != PT_OK ? rc : r;
@@ -3368,50 +3531,11 @@ int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean,
         return fail(PT_ERR_STATE, "pt_atrous_halves: every pixel needs at least 4 samples (the frame's smallest count is " + std::to_string(spp_min) + ")");
     const int32_t W = fr.cfg.width, H = fr.cfg.height;
     FilterClock<2> clock;
-    if (int32_t rc = gather_filter_inputs(ctx, true)) return rc;
-    const bool feat = fr.features > 0;
+    if (int32_t rc = halves_filter(ctx, c, half_means != nullptr, &clock)) return rc;
     Device &d0 = ctx->devs[0];
     pt_ctx::Halves &B = ctx->ah;
-    HIP_TRY(hipSetDevice(d0.ordinal));
     const size_t npix = (size_t)W * (size_t)H;
     const uint32_t grid1 = ptl::grid_1d(npix);
-    for (int k = 0; k < 2; k++) {
-        HIP_TRY(B.col[k].reserve(6 * npix));
-        HIP_TRY(B.var[k].reserve(2 * npix));
-    }
-    HIP_TRY(B.guide.reserve(PTA_GUIDE_PLANES * npix));
-    HIP_TRY(B.mean.reserve(3 * npix));
-    HIP_TRY(B.err.reserve(npix));
-    if (half_means) HIP_TRY(B.half.reserve(6 * npix));
-    HIP_TRY(B.part.reserve(grid1));
-    if (int32_t rc = clock.create()) return rc;
-    HIP_TRY(hipEventRecord(clock.ev[0], d0.stream));
-    ptk::AtrousPairPrepArgs PA;
-    std::memset(&PA, 0, sizeof PA);
-    PA.sa = ctx->f_hv_sa.p; PA.qa = ctx->f_hv_qa.p; PA.sb = ctx->f_hv_sb.p; PA.qb = ctx->f_hv_qb.p;
-    PA.cnt = fr.adaptive ? ctx->f_seg.p : nullptr;
-    PA.fn = feat ? ctx->f_feat_n.p : nullptr;
-    PA.fa = feat ? ctx->f_feat_a.p : nullptr;
-    PA.fd = feat ? ctx->f_feat_d.p : nullptr;
-    PA.guide = B.guide.p;
-    PA.col = B.col[0].p;
-    PA.var = B.var[0].p;
-    PA.npix = (uint32_t)npix;
-    PA.n = (uint32_t)fr.done_spp;
-    hipLaunchKernelGGL(ptk::atrous_pair_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, PA);
-    double *const col[2] = {B.col[0].p, B.col[1].p}, *const vr[2] = {B.var[0].p, B.var[1].p};
-    const int cur = ptl::pair_iterations(ptl::filter_params(c, feat), col, vr, B.guide.p, W, H, d0.stream);
-    ptk::HalvesCombineArgs CA;
-    std::memset(&CA, 0, sizeof CA);
-    CA.col = col[cur]; CA.var = vr[cur]; CA.guide = B.guide.p;
-    CA.mean = B.mean.p;
-    CA.err = B.err.p;
-    CA.half_means = half_means ? B.half.p : nullptr;
-    CA.partial = B.part.p;
-    CA.npix = (uint32_t)npix;
-    hipLaunchKernelGGL(ptk::halves_combine_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, CA);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(clock.ev[1], d0.stream));
     std::vector<ptk::HalvesPartial> part(grid1);
     HIP_TRY(hipMemcpyAsync(part.data(), B.part.p, part.size() * sizeof(ptk::HalvesPartial), hipMemcpyDeviceToHost, d0.stream));
     if (mean) HIP_TRY(hipMemcpyAsync(mean, B.mean.p, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, d0.stream));
@@ -3435,6 +3559,34 @@ int32_t pt_atrous_halves(pt_ctx *ctx, const pt_atrous_config *cfg, double *mean,
     }
     if (std::getenv("PTCORE_VERBOSE"))
         std::fprintf(stderr, "ptcore: pt_atrous_halves %d iterations, %.3f ms host wall (gathers included)\n", c.iterations, clock.wall_ms());
+    return PT_OK;
+}
+
+int32_t pt_set_adaptive_filtered(pt_ctx *ctx, const pt_adaptive_filtered *f) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_adaptive_filtered while a frame is open");
+    pt_adaptive_filtered r;
+    std::memset(&r, 0, sizeof r);
+    if (f) {
+        if (int32_t rc = filter_config("pt_set_adaptive_filtered", "filter ", &f->filter, 5, r.filter)) return rc;
+        if (f->pool < 0 || f->pool > PTA_MAX_POOL) return fail(PT_ERR_INVALID, "pt_set_adaptive_filtered: pool must be 0..4");
+        r.pool = f->pool;
+    }
+    ctx->filtered_on = f != nullptr;
+    ctx->filtered = r;
+    return PT_OK;
+}
+
+int32_t pt_read_block_figures(pt_ctx *ctx, double *pooled, double *own, int32_t *checks) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (int32_t rc = frame_needs(ctx, "pt_read_block_figures", {NEED_MOMENTS, NEED_ADAPTIVE})) return rc;
+    const Frame &fr = ctx->frame;
+    if (!fr.filtered) return fail(PT_ERR_STATE, "pt_read_block_figures: the frame was rendered with the rule off (pt_set_adaptive_filtered)");
+    if (fr.fa_checks <= 0) return fail(PT_ERR_STATE, "pt_read_block_figures: no check of the frame has decided yet");
+    const size_t nb = (size_t)ptl::blocks_across(fr.cfg.width) * (size_t)ptl::blocks_across(fr.cfg.height);
+    if (pooled) std::memcpy(pooled, ctx->bf.h_pooled.data(), nb * sizeof(double));
+    if (own) std::memcpy(own, ctx->bf.h_own.data(), nb * sizeof(double));
+    if (checks) *checks = fr.fa_checks;
     return PT_OK;
 }
 

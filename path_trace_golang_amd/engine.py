@@ -65,7 +65,8 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 adaptive: Optional[bool] = None, min_spp: Optional[int] = None, counts: Optional[np.ndarray] = None,
                 features: Optional[int] = None, atrous: Optional["hip.AtrousConfig"] = None,
                 filtered_noise: Optional[float] = None, temporal: Optional["hip.TemporalConfig"] = None,
-                temporal_clip: Optional[float] = None, temporal_motion: Optional[bool] = None) -> dict:
+                temporal_clip: Optional[float] = None, temporal_motion: Optional[bool] = None,
+                filtered_adaptive: Optional[float] = None, pool: Optional[int] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
@@ -85,7 +86,11 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     editor that drags objects: True records the object index plane, remembers the scene of the last accumulated frame and, frame by
     frame, hands hip.scene_motion's answer on -- a table of displacements goes to pt_temporal, None (anything but positions and the
     camera changed) resets the history, an all-zero table passes nothing; None takes PATHTRACER_GPU_TEMPORAL_MOTION
-    (hip.temporal_motion_from_env), which too is read only when PATHTRACER_GPU_TEMPORAL turned the accumulation on."""
+    (hip.temporal_motion_from_env), which too is read only when PATHTRACER_GPU_TEMPORAL turned the accumulation on.
+    `filtered_adaptive` and `pool` are hip.render's: with the filter on, an adaptive frame whose 8x8 blocks stop by the
+    filtered frame's pooled noise; None takes PATHTRACER_GPU_FILTERED_ADAPTIVE / PATHTRACER_GPU_POOL (hip.filtered_adaptive_from_env),
+    off by default and ignored without the filter; beside a noise target or a filtered noise target it is an error, as in the other host
+    layers: one stop rule per frame."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -113,13 +118,20 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
         features = hip.features_from_env()
     if filtered_noise is None and atrous is not None and noise is None:
         filtered_noise = hip.filtered_noise_from_env()
+    rule = {}
+    if filtered_adaptive is None and atrous is not None:  # (beside a noise target or a filtered noise target hip.render refuses it)
+        filtered_adaptive, env_pool = hip.filtered_adaptive_from_env()
+        pool = pool if pool is not None else env_pool
+    if filtered_adaptive is not None:
+        rule = dict(filtered_adaptive=filtered_adaptive, pool=1 if pool is None else pool)
+        adaptive = False  # (the rule brings its own adaptive frame; PATHTRACER_GPU_ADAPTIVE has no noise target to adapt to here)
     motion = {}
     if temporal is not None and temporal_motion:
         motion = _motion_for(sc)
     out = hip.render(sc, gcfg, img, progress, shading=model, features=features, atrous=atrous, moments=moments, noise=noise,
                      noise_step=noise_step if noise_step is not None else ncfg.step, adaptive=bool(adaptive) and noise is not None,
                      min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts, filtered_noise=filtered_noise,
-                     temporal=temporal, temporal_clip=temporal_clip if temporal is not None else None, **motion)
+                     temporal=temporal, temporal_clip=temporal_clip if temporal is not None else None, **motion, **rule)
     if "temporal" in out:
         global _accumulated_scene
         # (the caller edits its scene in place; a frame accumulated without the rule is not what the next table is against)

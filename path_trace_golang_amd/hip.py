@@ -626,6 +626,44 @@ def filtered_noise_from_env(environ=None) -> Optional[float]:
     return _env_positive(environ, "PATHTRACER_GPU_FILTERED_NOISE")
 
 
+def set_adaptive_filtered(ctx: capi.Context, cfg: Optional[AtrousConfig] = None, pool: int = 1, on: bool = True) -> None:
+    """pt_set_adaptive_filtered: later adaptive frames on ctx (set_adaptive gives the target, min_spp and step) stop their 8x8 blocks
+    by the noise left in the filtered frame, pooled over the blocks within `pool` blocks (0..4) of each; cfg None = the
+    filter's defaults.  on=False turns the rule off."""
+    if not capi.has("pt_set_adaptive_filtered"):
+        if on:
+            raise RuntimeError("this libptcore.so has no pt_set_adaptive_filtered (rebuild it)")
+        return
+    if not on:
+        capi.check(capi.load().pt_set_adaptive_filtered(ctx.handle, None))
+        return
+    f = capi.PtAdaptiveFiltered((cfg or AtrousConfig()).c(), int(pool), 0)
+    capi.check(capi.load().pt_set_adaptive_filtered(ctx.handle, C.byref(f)))
+
+
+def read_block_figures(ctx: capi.Context, pooled: Optional[np.ndarray] = None, own: Optional[np.ndarray] = None) -> int:
+    """pt_read_block_figures of ctx's open or last frame into the arrays given (contiguous float64 [ceil(H / 8), ceil(W / 8)] each):
+    the last deciding check's pooled figure P_B and the block's own sqrt(s_B / k_B).  Returns the number of checks that have decided."""
+    if not capi.has("pt_read_block_figures"):
+        raise RuntimeError("this libptcore.so has no pt_read_block_figures (rebuild it)")
+    for a in (pooled, own):
+        if a is not None and (a.dtype != np.float64 or a.ndim != 2 or not a.flags.c_contiguous):
+            raise ValueError("block figures must be contiguous float64 [blocks down, blocks across]")
+    n = C.c_int32(0)
+    dp = C.POINTER(C.c_double)
+    capi.check(capi.load().pt_read_block_figures(ctx.handle, *(a.ctypes.data_as(dp) if a is not None else None for a in (pooled, own)),
+                                                 C.byref(n)))
+    return n.value
+
+
+def filtered_adaptive_from_env(environ=None):
+    """PATHTRACER_GPU_FILTERED_ADAPTIVE=<float > 0>: the block target on the filtered frame's pooled noise (used with
+    PATHTRACER_GPU_ATROUS; the step is PATHTRACER_GPU_NOISE_STEP) and PATHTRACER_GPU_POOL=<0..4>, the pool radius in blocks (1 when
+    unset or not such a number).  Returns (target or None, pool)."""
+    pool = _env_int(environ, "PATHTRACER_GPU_POOL", 0, 4)
+    return _env_positive(environ, "PATHTRACER_GPU_FILTERED_ADAPTIVE"), 1 if pool is None else pool
+
+
 def scene_allows_features(sc, shading: str = "cpu") -> bool:
     """Does a frame of this scene accept pt_set_features(k > 0)?  Not with GL shading, and not on the bounding-volume-hierarchy
     path (more than 128 spheres or 128 boxes, or PTCORE_SCAN=bvh)."""
@@ -690,7 +728,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            features: Optional[int] = None, atrous: Optional["AtrousConfig"] = None,
            filtered_noise: Optional[float] = None, halves: bool = False,
            temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None,
-           object_ids: bool = False, temporal_motion=None) -> dict:
+           object_ids: bool = False, temporal_motion=None, filtered_adaptive: Optional[float] = None, pool: int = 1) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -725,6 +763,12 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     inf when no check ran) and spp_done.  Neither figure sees the bias the filter adds.  halves=True collects the half-buffer
     sums without the stop rule (read them with read_halves / atrous_halves afterwards); without the two arguments halves are off.
 
+    filtered_adaptive=T (with atrous=) is adaptive sampling by the filtered frame's noise: an adaptive frame (counts=,
+    "adaptive" in the returned dict, noise_step and min_spp as above, a min_spp below 4 counting as 4) whose blocks stop when the noise
+    measured in the filtered frame, pooled over the blocks within `pool` blocks (0..4) of each, is at or below T
+    (pt_set_adaptive_filtered).  The image is pt_atrous on the full sums with every pixel's own count.  It excludes noise=,
+    adaptive=True and filtered_noise=.  The returned dict gains "block_checks", the checks that decided.
+
     temporal=TemporalConfig() is for a caller that renders frame after frame on one context while the camera
     moves: it turns moments and features on (k = 4 unless features= or the filter's config says otherwise), renders, and then
     calls pt_temporal with atrous= as its filter (None: no filter); img is its output and the returned dict gains "temporal": the
@@ -753,6 +797,16 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
             raise ValueError("filtered_noise excludes noise= and adaptive=True: one stop rule per frame")
         if shading != "cpu":
             raise ValueError("filtered_noise is not available with GL shading (pt_atrous_halves refuses such frames)")
+    if filtered_adaptive is not None:
+        if atrous is None:
+            raise ValueError("filtered_adaptive needs the filter whose output it measures (atrous=)")
+        if noise is not None or adaptive or filtered_noise is not None:
+            raise ValueError("filtered_adaptive excludes noise=, adaptive=True and filtered_noise=: one stop rule per frame")
+        if shading != "cpu":
+            raise ValueError("filtered_adaptive is not available with GL shading (adaptive frames refuse it)")
+        if not 0 <= int(pool) <= 4:
+            raise ValueError("pool must be 0..4 blocks")
+        adaptive, noise = True, filtered_adaptive  # from here on an adaptive frame with T as its block target
     L = capi.load()
     ctx = ctx or context()
     if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4:
@@ -774,6 +828,9 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     if temporal_clip is not None:
         temporal_set_clip(ctx, temporal_clip)
     set_adaptive(ctx, noise if adaptive else None, min_spp, noise_step)
+    if (filtered_adaptive is not None) or getattr(ctx, "_filtered_adaptive_on", False):  # (said only where it was ever on)
+        set_adaptive_filtered(ctx, atrous, pool, on=filtered_adaptive is not None)
+        ctx._filtered_adaptive_on = filtered_adaptive is not None
     want_moments = moments is not None or noise is not None or atrous is not None or halves or temporal is not None
     set_moments(ctx, want_moments)
     set_halves(ctx, halves or filtered_noise is not None)
@@ -825,6 +882,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
                 d["spp_done"] = d["adaptive"]["spp_max"]
                 if counts is not None:
                     read_sample_counts(ctx, counts)
+                if filtered_adaptive is not None:
+                    d["block_checks"] = read_block_figures(ctx) if d["spp_done"] >= max(min_spp, 4) else 0
         elif want_moments:
             d.update(noise=float("inf"))
             if filtered_noise is not None:
