@@ -40,7 +40,7 @@
 //                   chunk's resolve add; noise_kernel reduces both sums to the frame noise figure (pt_noise_estimate).
 //   gl_trace_kernel opt-in (pt_set_shading, GL model): one pass of GL shading (pt_glshade.h) per job, 16 paths with their own
 //                   camera rays, the pass sum written into the job's radiance record; replaces ray generation and the trace
-//                   kernels for the frame.  resolve_kernel then finishes with GL's tone map (gl_spp).
+//                   kernels for the frame.  finish_kernel then finishes with GL's tone map (gl_spp).
 //   fog_kernel      opt-in (pt_set_fog): the fog's in-scatter term of every job (pt_fog.h), added into its radiance record
 //                   between a chunk's last trace pass and resolve_kernel.
 //   feature_kernel  opt-in (pt_set_features): per pixel slot the running sums of the first-hit normal, albedo and distance of
@@ -2719,45 +2719,23 @@ __device__ __forceinline__ uint32_t quantise(double v) {
     return (uint32_t)v;
 }
 
-struct ResolveArgs {
-    const double *L;         // [njobs][4]: r, g, b, 0
-    const uint32_t *job_seg; // [njobs] or null
-    const uint32_t *job_draw;
-    double *acc;             // [3][nslots]
-    uint32_t *acc_seg;       // [nslots] or null
-    uint32_t *acc_draw;
-    uint8_t *tiles_rgba;     // [nlocal][32][32][4] or null (no finish)
-    double *tiles_accum;     // [nlocal][32][32][3] or null
-    uint32_t *tiles_seg;     // [nlocal][32][32] or null
-    uint32_t *tiles_draw;
-    uint32_t nslots;         // nlocal*1024
-    uint32_t njobs;
-    uint32_t S;
-    int32_t first;           // 1: the running sum starts at zero
-    int32_t finish;          // 1: write tiles_rgba / tiles_accum
-    int32_t have_chunk;      // 0: no chunk to add (pure finish, pt_read)
-    double inv_samples;      // 1/spp_done
-    TileGeom G;
-    int32_t gl_spp;          // GL shading: spp_done, and the finish is GL's tone map (post_tonemap_kernel); 0: the CPU engine's
-};
-
 __device__ __forceinline__ uint32_t tonemap_pack(double cx, double cy, double cz, int32_t spp);
 
-// The tables of an adaptive frame (pt_set_adaptive), per device: active[c] = block index of compact block c (ascending),
-// blk_spp[b] = samples block b holds.  Job buffers are compact (row (c * S + s) of 64 jobs), acc / m2 keep their full-frame slots.
+// The active list of an adaptive frame (pt_set_adaptive), per device: active[c] = block index of compact block c
+// (ascending).  Job buffers are compact (row (c * S + s) of 64 jobs), the per-slot sums keep their full-frame slots.  (The samples a
+// block holds, blk_spp[b], are read by the kernels that run over every slot: finish_kernel, noise_adaptive_kernel, counts_tiles_kernel.)
 struct AdaptTable {
     const uint32_t *active;   // [nact]
-    const uint32_t *blk_spp;  // [nslots / 64]
     uint32_t nact;
 };
 
-// The slot a thread of resolve_body / moments_body works on, and cblk: the slot's rows in the job buffers start at cblk * S.  One thread
-// per slot of the shard -- but where an adaptive frame adds a chunk, one per slot of the nact active blocks: compact row cblk is block
-// active[cblk].  false: the thread has no slot.
+// The slot a thread of a per-slot add works on, and cblk: the slot's rows in the job buffers start at cblk * S.  One thread per slot of
+// the shard -- in an adaptive frame one per slot of the nact active blocks: compact row cblk is block active[cblk].  false: the thread
+// has no slot.
 template <bool ADAPT>
-__device__ __forceinline__ bool chunk_slot(int32_t have_chunk, const AdaptTable &T, uint32_t nslots, uint32_t &slot, uint32_t &cblk) {
+__device__ __forceinline__ bool chunk_slot(const AdaptTable &T, uint32_t nslots, uint32_t &slot, uint32_t &cblk) {
     slot = blockIdx.x * PT_BLOCK + threadIdx.x;
-    if (ADAPT && have_chunk) {
+    if (ADAPT) {
         if (slot >= T.nact * 64u) return false;
         cblk = __builtin_amdgcn_readfirstlane(slot >> 6);
         slot = T.active[cblk] * 64u + (slot & 63u);  // wave-uniform index: a scalar load
@@ -2768,72 +2746,135 @@ __device__ __forceinline__ bool chunk_slot(int32_t have_chunk, const AdaptTable 
     return true;
 }
 
-// (ADAPT: resolve_adaptive_kernel below.  Its add runs over the nact * 64 slots of the active blocks, its finish over every slot with
-// 1 / n of the slot's own block.)
+// Channel planes 3k .. 3k + 2 of a [3n][nslots] array of per-slot sums: group k of the slot
+__device__ __forceinline__ void load3(const double *a, uint32_t k, uint32_t nslots, uint32_t slot, double (&v)[3]) {
+    for (uint32_t c = 0; c < 3u; c++) v[c] = a[(3u * k + c) * (size_t)nslots + slot];
+}
+__device__ __forceinline__ void store3(double *a, uint32_t k, uint32_t nslots, uint32_t slot, const double (&v)[3]) {
+    for (uint32_t c = 0; c < 3u; c++) a[(3u * k + c) * (size_t)nslots + slot] = v[c];
+}
+
+// What every add of a chunk's radiance records into per-slot running sums is given, and the walk of such an add (chunk_walk): one lane
+// per slot; a slot inside the frame loads its sums unless the chunk is the frame's first, visits its records base + s * 64, s < S, in
+// sample order -- col = col.add(sample), renderer.go:186 -- and stores the sums.  An add states its sums and the three steps:
+// load(slot), add(record, its index in the job buffers), store(slot).
+struct ChunkArgs {
+    const double *L;         // [njobs][4]: r, g, b, 0
+    uint32_t nslots;         // nlocal*1024
+    uint32_t S;
+    int32_t first;           // 1: the running sums start at zero
+    TileGeom G;
+};
+
+template <bool ADAPT, typename Load, typename Add, typename Store>
+__device__ __forceinline__ void chunk_walk(const ChunkArgs &C, const AdaptTable &T, Load &&load, Add &&add, Store &&store) {
+    uint32_t slot, cblk;
+    if (!chunk_slot<ADAPT>(T, C.nslots, slot, cblk)) return;
+    if (!slot_pixel(C.G, slot).inside) return;
+    if (!C.first) load(slot);
+    const size_t base = (size_t)cblk * C.S * 64u + (slot & 63u);
+    for (uint32_t s = 0; s < C.S; s++) {
+        const size_t j = base + (size_t)s * 64u;
+        add(reinterpret_cast<const double4 *>(C.L)[j], j);
+    }
+    store(slot);
+}
+
+// The frame's sums themselves: the radiance, and with pixel stats the segment and draw counts of the slot's paths.
+struct ResolveArgs {
+    ChunkArgs C;
+    const uint32_t *job_seg; // [njobs] or null
+    const uint32_t *job_draw;
+    double *acc;             // [3][nslots]
+    uint32_t *acc_seg;       // [nslots] or null
+    uint32_t *acc_draw;
+};
+
 template <bool ADAPT>
 __device__ __forceinline__ void resolve_body(const ResolveArgs &R, const AdaptTable &T) {
-    uint32_t slot, cblk;
-    if (!chunk_slot<ADAPT>(R.have_chunk, T, R.nslots, slot, cblk)) return;
-    const uint32_t blk = slot >> 6, p = slot & 63u;
-    const Pixel px = block_pixel(R.G, blk, p);
-    const bool inside = px.inside;
-    const size_t pix = px.pix;
-
-    double cx = 0, cy = 0, cz = 0;
+    double col[3] = {0, 0, 0};
     uint32_t nseg = 0, ndraw = 0;
-    if (inside) {
-        if (!R.first) {
-            cx = R.acc[slot];
-            cy = R.acc[(size_t)R.nslots + slot];
-            cz = R.acc[2 * (size_t)R.nslots + slot];
+    chunk_walk<ADAPT>(
+        R.C, T,
+        [&](uint32_t slot) {
+            load3(R.acc, 0, R.C.nslots, slot, col);
             if (R.acc_seg) { nseg = R.acc_seg[slot]; ndraw = R.acc_draw[slot]; }
-        }
-        if (R.have_chunk) {
-            const size_t base = (size_t)cblk * R.S * 64u + p;
-            for (uint32_t s = 0; s < R.S; s++) {  // col = col.add(sample), renderer.go:186, in sample order
-                const size_t j = base + (size_t)s * 64u;
-                const double4 l = reinterpret_cast<const double4 *>(R.L)[j];
-                cx += l.x;
-                cy += l.y;
-                cz += l.z;
-                if (R.job_seg) { nseg += R.job_seg[j]; ndraw += R.job_draw[j]; }
-            }
-            R.acc[slot] = cx;
-            R.acc[(size_t)R.nslots + slot] = cy;
-            R.acc[2 * (size_t)R.nslots + slot] = cz;
+        },
+        [&](const double4 &l, size_t j) {
+            col[0] += l.x;
+            col[1] += l.y;
+            col[2] += l.z;
+            if (R.job_seg) { nseg += R.job_seg[j]; ndraw += R.job_draw[j]; }
+        },
+        [&](uint32_t slot) {
+            store3(R.acc, 0, R.C.nslots, slot, col);
             if (R.acc_seg) { R.acc_seg[slot] = nseg; R.acc_draw[slot] = ndraw; }
+        });
+}
+
+__global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) { resolve_body<false>(R, AdaptTable{nullptr, 0u}); }
+
+__global__ __launch_bounds__(PT_BLOCK) void resolve_adaptive_kernel(const ResolveArgs R, const AdaptTable T) { resolve_body<true>(R, T); }
+
+// The frame's finish (pt_read, pt_render_tiles_device): the running sums of every slot, tile-major with zeros outside the frame, and
+// the 8-bit image of the current estimate.  zero: nothing was added yet, the sums read as zero.
+struct FinishArgs {
+    const double *acc;        // [3][nslots]
+    const uint32_t *acc_seg;  // [nslots] (read where tiles_seg is asked for)
+    const uint32_t *acc_draw;
+    const uint32_t *blk_spp;  // adaptive frame: [nslots / 64], a slot is normalised by the samples of its own block; null: by inv_samples
+    uint8_t *tiles_rgba;      // [nlocal][32][32][4] or null
+    double *tiles_accum;      // [nlocal][32][32][3] or null
+    uint32_t *tiles_seg;      // [nlocal][32][32] or null
+    uint32_t *tiles_draw;
+    uint32_t nslots;          // nlocal*1024
+    int32_t zero;
+    double inv_samples;       // 1/spp_done
+    TileGeom G;
+    int32_t gl_spp;           // GL shading: spp_done, and the image is GL's tone map (post_tonemap_kernel); 0: the CPU engine's
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void finish_kernel(const FinishArgs A) {
+    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (slot >= A.nslots) return;
+    const Pixel px = slot_pixel(A.G, slot);
+    const bool inside = px.inside, have = inside && !A.zero;
+    const size_t pix = px.pix;
+    double col[3] = {0, 0, 0};
+    if (have) load3(A.acc, 0, A.nslots, slot, col);
+    if (A.tiles_rgba) {
+        uint32_t packed = 0;
+        if (inside && A.gl_spp) {
+            packed = tonemap_pack(col[0], col[1], col[2], A.gl_spp);
+        } else if (inside) {
+            // renderer.go:190-221
+            const double inv_samples = A.blk_spp ? 1.0 / (double)A.blk_spp[slot >> 6] : A.inv_samples;
+            const double r = ptm::f_sqrt(col[0] * inv_samples) * 255.999;
+            const double g = ptm::f_sqrt(col[1] * inv_samples) * 255.999;
+            const double b = ptm::f_sqrt(col[2] * inv_samples) * 255.999;
+            packed = quantise(r) | (quantise(g) << 8) | (quantise(b) << 16) | (255u << 24);
         }
+        reinterpret_cast<uint32_t *>(A.tiles_rgba)[pix] = packed;
     }
-    if (R.finish) {
-        if (R.tiles_rgba) {
-            uint32_t packed = 0;
-            if (inside && R.gl_spp) {
-                packed = tonemap_pack(cx, cy, cz, R.gl_spp);
-            } else if (inside) {
-                // renderer.go:190-221
-                const double inv_samples = ADAPT ? 1.0 / (double)T.blk_spp[blk] : R.inv_samples;
-                const double r = ptm::f_sqrt(cx * inv_samples) * 255.999;
-                const double g = ptm::f_sqrt(cy * inv_samples) * 255.999;
-                const double b = ptm::f_sqrt(cz * inv_samples) * 255.999;
-                packed = quantise(r) | (quantise(g) << 8) | (quantise(b) << 16) | (255u << 24);
-            }
-            reinterpret_cast<uint32_t *>(R.tiles_rgba)[pix] = packed;
-        }
-        if (R.tiles_accum) {
-            R.tiles_accum[3 * pix] = inside ? cx : 0.0;
-            R.tiles_accum[3 * pix + 1] = inside ? cy : 0.0;
-            R.tiles_accum[3 * pix + 2] = inside ? cz : 0.0;
-        }
-        if (R.tiles_seg) {
-            R.tiles_seg[pix] = inside ? nseg : 0u;
-            R.tiles_draw[pix] = inside ? ndraw : 0u;
-        }
+    if (A.tiles_accum)
+        for (uint32_t c = 0; c < 3u; c++) A.tiles_accum[3 * pix + c] = col[c];
+    if (A.tiles_seg) {
+        A.tiles_seg[pix] = have ? A.acc_seg[slot] : 0u;
+        A.tiles_draw[pix] = have ? A.acc_draw[slot] : 0u;
     }
 }
 
-__global__ __launch_bounds__(PT_BLOCK) void resolve_kernel(const ResolveArgs R) { resolve_body<false>(R, AdaptTable{nullptr, nullptr, 0u}); }
-
-__global__ __launch_bounds__(PT_BLOCK) void resolve_adaptive_kernel(const ResolveArgs R, const AdaptTable T) { resolve_body<true>(R, T); }
+// Group `which` of a [3n][nslots] array of per-slot sums (load3) tile-major with zeros outside the frame, the layout of tiles_accum, for
+// untile_kernel: the second moments, a half-buffer sum, a feature plane, the radiance sums alone.  zero: nothing was added yet.
+__global__ __launch_bounds__(PT_BLOCK) void planes_tiles_kernel(const double *__restrict__ src, double *__restrict__ tiles, uint32_t nslots, uint32_t which,
+                                                                  int32_t zero, const TileGeom G) {
+    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (slot >= nslots) return;
+    const Pixel px = slot_pixel(G, slot);
+    double v[3] = {0, 0, 0};
+    if (px.inside && !zero) load3(src, which, nslots, slot, v);
+    for (uint32_t c = 0; c < 3u; c++) tiles[3 * px.pix + c] = v[c];
+}
 
 // The inverse of block_pixel, over the tiles of every shard at once: pixel (x, y) lies in tile t, which shard k = t % shard_count holds as its
 // tile lt = t / shard_count, at pix = lt * 1024 + ly * 32 + lx of that shard's planes -- block_pixel's pix, with t = k + lt * shard_count.
@@ -2877,124 +2918,65 @@ __global__ __launch_bounds__(PT_BLOCK) void untile_kernel(const UntileArgs U) {
 }
 
 // Second moments (pt_set_moments): per accumulation slot the running sum of the squares of the sample radiances, next to
-// resolve_kernel's running sum of the radiances themselves.  Same slot -> (tile, sub-block, pixel) map and the same walk
-// over the chunk's records in sample order as resolve_kernel, which stays as it is: this kernel reads the records a second
-// time, right after the chunk's resolve add (so after fog_kernel and gl_trace_kernel: the squares are those of the
-// radiance the pixel receives).  finish = 1 writes the sums tile-major with zeros outside the frame, the layout of
-// tiles_accum, for untile_kernel.
+// resolve_kernel's running sum of the radiances themselves.  The walk of resolve_kernel (chunk_walk), which stays as it is: this
+// kernel reads the records a second time, right after the chunk's resolve add (so after fog_kernel and gl_trace_kernel: the squares
+// are those of the radiance the pixel receives).
 struct MomentsArgs {
-    const double *L;         // [njobs][4]: r, g, b, 0
+    ChunkArgs C;
     double *m2;              // [3][nslots]
-    double *tiles_m2;        // [nlocal][32][32][3] or null (no finish)
-    uint32_t nslots;         // nlocal*1024
-    uint32_t S;
-    int32_t first;           // 1: the running sum starts at zero
-    int32_t finish;          // 1: write tiles_m2
-    int32_t have_chunk;      // 0: no chunk to add (pure finish)
-    TileGeom G;
 };
 
 template <bool ADAPT>
 __device__ __forceinline__ void moments_body(const MomentsArgs &M, const AdaptTable &T) {
-    uint32_t slot, cblk;
-    if (!chunk_slot<ADAPT>(M.have_chunk, T, M.nslots, slot, cblk)) return;
-    const uint32_t p = slot & 63u;
-    const Pixel px = slot_pixel(M.G, slot);
-    const bool inside = px.inside;
-
-    double qx = 0, qy = 0, qz = 0;
-    if (inside) {
-        if (!M.first) {
-            qx = M.m2[slot];
-            qy = M.m2[(size_t)M.nslots + slot];
-            qz = M.m2[2 * (size_t)M.nslots + slot];
-        }
-        if (M.have_chunk) {
-            const size_t base = (size_t)cblk * M.S * 64u + p;
-            for (uint32_t s = 0; s < M.S; s++) {  // in sample order, like the sum itself
-                const double4 l = reinterpret_cast<const double4 *>(M.L)[base + (size_t)s * 64u];
-                qx += l.x * l.x;
-                qy += l.y * l.y;
-                qz += l.z * l.z;
-            }
-            M.m2[slot] = qx;
-            M.m2[(size_t)M.nslots + slot] = qy;
-            M.m2[2 * (size_t)M.nslots + slot] = qz;
-        }
-    }
-    if (M.finish) {
-        const size_t pix = px.pix;
-        M.tiles_m2[3 * pix] = inside ? qx : 0.0;
-        M.tiles_m2[3 * pix + 1] = inside ? qy : 0.0;
-        M.tiles_m2[3 * pix + 2] = inside ? qz : 0.0;
-    }
+    double q[3] = {0, 0, 0};
+    chunk_walk<ADAPT>(
+        M.C, T, [&](uint32_t slot) { load3(M.m2, 0, M.C.nslots, slot, q); },
+        [&](const double4 &l, size_t) {
+            q[0] += l.x * l.x;
+            q[1] += l.y * l.y;
+            q[2] += l.z * l.z;
+        },
+        [&](uint32_t slot) { store3(M.m2, 0, M.C.nslots, slot, q); });
 }
 
-__global__ __launch_bounds__(PT_BLOCK) void moments_kernel(const MomentsArgs M) { moments_body<false>(M, AdaptTable{nullptr, nullptr, 0u}); }
+__global__ __launch_bounds__(PT_BLOCK) void moments_kernel(const MomentsArgs M) { moments_body<false>(M, AdaptTable{nullptr, 0u}); }
 
 __global__ __launch_bounds__(PT_BLOCK) void moments_adaptive_kernel(const MomentsArgs M, const AdaptTable T) { moments_body<true>(M, T); }
 
 // Half-buffer sums (pt_set_halves, pt_atrous.h HALVES): per accumulation slot twelve running sums -- SA, QA, SB, QB, three channels
-// each -- of the radiances and their squares over the slot's even-indexed (A) and odd-indexed (B) samples.  The walk of moments_kernel:
-// one lane per slot, the chunk's records in sample order, right after the chunk's resolve add.  Record s of the chunk is sample
-// s0 + s of its pixel -- in adaptive frames too, where every active block holds s0 samples -- so the half is wave-uniform.
-// finish = 1 writes plane `which` (0 SA, 1 QA, 2 SB, 3 QB) tile-major with zeros outside the frame, the layout of tiles_accum.
+// each -- of the radiances and their squares over the slot's even-indexed (A) and odd-indexed (B) samples.  The walk of moments_kernel,
+// right after the chunk's resolve add.  Record s of the chunk is sample s0 + s of its pixel -- in adaptive frames too, where every
+// active block holds s0 samples -- so the half is wave-uniform.  (The steps of chunk_walk, written out: as a lambda under it the branch
+// on the half compiles to selects, 36 v_cndmask per record, and the kernel takes 7 % longer)
 struct HalvesArgs {
-    const double *L;         // [njobs][4]: r, g, b, 0
-    double *hv;              // [12][nslots]: SA, QA, SB, QB, three channel planes each
-    double *tiles;           // [nlocal][32][32][3] or null (no finish)
-    uint32_t nslots;         // nlocal*1024
-    uint32_t S, s0;          // the chunk's samples, and the index of its first one
-    int32_t first;           // 1: the running sums start at zero
-    int32_t finish;          // 1: write plane `which` to tiles
-    int32_t have_chunk;      // 0: no chunk to add (pure finish)
-    uint32_t which;
-    TileGeom G;
+    ChunkArgs C;
+    double *hv;              // [12][nslots]: groups 0 SA, 1 QA, 2 SB, 3 QB, three channel planes each
+    uint32_t s0;             // the index of the chunk's first sample
 };
 
 template <bool ADAPT>
 __device__ __forceinline__ void halves_body(const HalvesArgs &A, const AdaptTable &T) {
     uint32_t slot, cblk;
-    if (!chunk_slot<ADAPT>(A.have_chunk, T, A.nslots, slot, cblk)) return;
-    const uint32_t p = slot & 63u;
-    const Pixel px = slot_pixel(A.G, slot);
-    const bool inside = px.inside;
-    const size_t ns = A.nslots;
-    if (A.have_chunk && inside) {
-        double sa[3] = {0, 0, 0}, qa[3] = {0, 0, 0}, sb[3] = {0, 0, 0}, qb[3] = {0, 0, 0};
-        if (!A.first)
-            for (uint32_t c = 0; c < 3u; c++) {
-                sa[c] = A.hv[c * ns + slot];
-                qa[c] = A.hv[(3u + c) * ns + slot];
-                sb[c] = A.hv[(6u + c) * ns + slot];
-                qb[c] = A.hv[(9u + c) * ns + slot];
-            }
-        const size_t base = (size_t)cblk * A.S * 64u + p;
-        for (uint32_t s = 0; s < A.S; s++) {  // in sample order, like the sum itself
-            const double4 l = reinterpret_cast<const double4 *>(A.L)[base + (size_t)s * 64u];
-            if (((A.s0 + s) & 1u) == 0u) {
-                sa[0] += l.x; sa[1] += l.y; sa[2] += l.z;
-                qa[0] += l.x * l.x; qa[1] += l.y * l.y; qa[2] += l.z * l.z;
-            } else {
-                sb[0] += l.x; sb[1] += l.y; sb[2] += l.z;
-                qb[0] += l.x * l.x; qb[1] += l.y * l.y; qb[2] += l.z * l.z;
-            }
-        }
-        for (uint32_t c = 0; c < 3u; c++) {
-            A.hv[c * ns + slot] = sa[c];
-            A.hv[(3u + c) * ns + slot] = qa[c];
-            A.hv[(6u + c) * ns + slot] = sb[c];
-            A.hv[(9u + c) * ns + slot] = qb[c];
+    if (!chunk_slot<ADAPT>(T, A.C.nslots, slot, cblk)) return;
+    if (!slot_pixel(A.C.G, slot).inside) return;
+    const uint32_t ns = A.C.nslots;
+    double sa[3] = {0, 0, 0}, qa[3] = {0, 0, 0}, sb[3] = {0, 0, 0}, qb[3] = {0, 0, 0};
+    if (!A.C.first) { load3(A.hv, 0, ns, slot, sa); load3(A.hv, 1, ns, slot, qa); load3(A.hv, 2, ns, slot, sb); load3(A.hv, 3, ns, slot, qb); }
+    const size_t base = (size_t)cblk * A.C.S * 64u + (slot & 63u);
+    for (uint32_t s = 0; s < A.C.S; s++) {  // in sample order, like the sum itself
+        const double4 l = reinterpret_cast<const double4 *>(A.C.L)[base + (size_t)s * 64u];
+        if (((A.s0 + s) & 1u) == 0u) {
+            sa[0] += l.x; sa[1] += l.y; sa[2] += l.z;
+            qa[0] += l.x * l.x; qa[1] += l.y * l.y; qa[2] += l.z * l.z;
+        } else {
+            sb[0] += l.x; sb[1] += l.y; sb[2] += l.z;
+            qb[0] += l.x * l.x; qb[1] += l.y * l.y; qb[2] += l.z * l.z;
         }
     }
-    if (A.finish) {
-        const size_t pix = px.pix;
-        const bool have = inside && !A.first;
-        for (uint32_t c = 0; c < 3u; c++) A.tiles[3 * pix + c] = have ? A.hv[(3u * A.which + c) * ns + slot] : 0.0;
-    }
+    store3(A.hv, 0, ns, slot, sa); store3(A.hv, 1, ns, slot, qa); store3(A.hv, 2, ns, slot, sb); store3(A.hv, 3, ns, slot, qb);
 }
 
-__global__ __launch_bounds__(PT_BLOCK) void halves_kernel(const HalvesArgs A) { halves_body<false>(A, AdaptTable{nullptr, nullptr, 0u}); }
+__global__ __launch_bounds__(PT_BLOCK) void halves_kernel(const HalvesArgs A) { halves_body<false>(A, AdaptTable{nullptr, 0u}); }
 
 __global__ __launch_bounds__(PT_BLOCK) void halves_adaptive_kernel(const HalvesArgs A, const AdaptTable T) { halves_body<true>(A, T); }
 
@@ -3267,7 +3249,7 @@ __device__ __forceinline__ float aces_tonemap(float x) {
 }
 
 // gpu.go:2309-2350: clamp, ACES, sqrt gamma, uint8(g*255.0 + 0.5) in float32 arithmetic, for one pixel's sum over spp
-// (also the finish of GL shading in resolve_kernel)
+// (also the finish of GL shading in finish_kernel)
 __device__ __forceinline__ uint32_t tonemap_pack(double cx, double cy, double cz, int32_t spp) {
     const double sum[3] = {cx, cy, cz};
     uint32_t packed = 255u << 24;
@@ -3855,7 +3837,7 @@ struct FeatureArgs {
 template <bool ADAPT>
 __device__ __forceinline__ void feature_body(const FeatureArgs &A, const AdaptTable &T) {
     uint32_t slot, cblk;
-    if (!chunk_slot<ADAPT>(1, T, A.nslots, slot, cblk)) return;
+    if (!chunk_slot<ADAPT>(T, A.nslots, slot, cblk)) return;
     const uint32_t p = slot & 63u;
     const size_t base = (size_t)cblk * A.S * 64u + p;
     if (A.ray_ndraw[base] == 0xffffu) return;  // outside the frame (the same for every sample of the slot)
@@ -3881,19 +3863,9 @@ __device__ __forceinline__ void feature_body(const FeatureArgs &A, const AdaptTa
     for (uint32_t q = 0; q < 9u; q++) A.feat[q * (size_t)A.nslots + slot] = f[q];
 }
 
-__global__ __launch_bounds__(PT_BLOCK) void feature_kernel(const FeatureArgs A) { feature_body<false>(A, AdaptTable{nullptr, nullptr, 0u}); }
+__global__ __launch_bounds__(PT_BLOCK) void feature_kernel(const FeatureArgs A) { feature_body<false>(A, AdaptTable{nullptr, 0u}); }
 
 __global__ __launch_bounds__(PT_BLOCK) void feature_adaptive_kernel(const FeatureArgs A, const AdaptTable T) { feature_body<true>(A, T); }
-
-// One of the three feature planes (which = 0 normal, 1 albedo, 2 depth) tile-major with zeros outside the frame, the layout of
-// tiles_accum, for untile_kernel.
-__global__ __launch_bounds__(PT_BLOCK) void feature_tiles_kernel(const double *__restrict__ feat, double *__restrict__ tiles, uint32_t nslots, uint32_t which,
-                                                                   const TileGeom G) {
-    const uint32_t slot = blockIdx.x * PT_BLOCK + threadIdx.x;
-    if (slot >= nslots) return;
-    const Pixel px = slot_pixel(G, slot);
-    for (uint32_t c = 0; c < 3u; c++) tiles[3 * px.pix + c] = px.inside ? feat[(3u * which + c) * (size_t)nslots + slot] : 0.0;
-}
 
 // The object index plane tile-major with -1 outside the frame, for untile_kernel's u32a plane (the bits of an int32).  ids holds
 // indices into the device world; map [nobj] turns them into indices into pt_scene.objects (the device world skips unknown types).

@@ -762,6 +762,23 @@ int32_t timed(Device &d, EventKind kind, Launch &&launch) {
     return PT_OK;
 }
 
+// A pass that has an adaptive form (pt_set_adaptive), one lane for each of `lanes`: `plain(args...)`, or in an adaptive frame
+// `adapt(args..., table)`, the same body working through the frame's block tables.  Timed under `kind`; EV_KINDS: not timed.
+template <typename Plain, typename Adapt, typename Table, typename... Args>
+int32_t launch_pass(Device &d, bool adaptive, EventKind kind, uint32_t lanes, Plain plain, Adapt adapt, const Table &table, const Args &...args) {
+    const dim3 grid((lanes + PT_BLOCK - 1) / PT_BLOCK), block(PT_BLOCK);
+    auto launch = [&] {
+        if (adaptive) hipLaunchKernelGGL(adapt, grid, block, 0, d.stream, args..., table);
+        else hipLaunchKernelGGL(plain, grid, block, 0, d.stream, args...);
+    };
+    if (kind != EV_KINDS) return timed(d, kind, launch);
+    launch();
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+// The lanes of a pass over the slots a chunk adds to: every slot of the shard, in an adaptive frame those of the active blocks
+uint32_t live_slots(const Frame &fr, const Device &d) { return fr.adaptive ? d.nact * 64u : d.nslots; }
+
 // A timed launch of a trace pass (EV_TRACE), marked as the split form or not for pt_stats.trace_split_ms / trace_split_launches.
 template <typename Launch>
 int32_t timed_trace(Device &d, bool split, Launch &&launch) {
@@ -1190,19 +1207,18 @@ int32_t step_raygen(pt_ctx *ctx, Device &d, const DevFrame &F, const uint32_t *a
     const dim3 block(PT_BLOCK), per_job((F.njobs + PT_BLOCK - 1) / PT_BLOCK);
     const char *rg_form = std::getenv("PTCORE_RAYGEN");  // A/B: "column" = round 2's walk down a lane's column, "simple" = one job per lane
     const bool rg_simple = std::getenv("PTCORE_RAYGEN_SIMPLE") || (rg_form && !std::strcmp(rg_form, "simple"));
-    if (int32_t rc = timed(d, EV_RAYGEN, [&] {
-            if (fr.adaptive)
-                hipLaunchKernelGGL(ptk::raygen_adaptive_kernel, per_job, block, 0, d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p, active);
-            else if (fr.cam.lens_radius > 0 && !rg_simple && !(rg_form && !std::strcmp(rg_form, "column")))  // thin lens: the rejection loop over a wave's pool of jobs
-                hipLaunchKernelGGL(ptk::raygen_lens_pool_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_POOL_ROWS - 1) / (PT_BLOCK * PT_RG_POOL_ROWS)), block, 0,
+    if (!fr.adaptive && fr.cam.lens_radius > 0 && !rg_simple) {  // thin lens: the rejection loop over a wave's pool of jobs, or down a lane's column
+        const bool pool = !(rg_form && !std::strcmp(rg_form, "column"));
+        const uint32_t per_block = PT_BLOCK * (pool ? PT_RG_POOL_ROWS : PT_RG_ROWS);
+        if (int32_t rc = timed(d, EV_RAYGEN, [&] {
+                hipLaunchKernelGGL(pool ? ptk::raygen_lens_pool_kernel : ptk::raygen_lens_kernel, dim3((F.njobs + per_block - 1) / per_block), block, 0,
                                    d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
-            else if (fr.cam.lens_radius > 0 && !rg_simple)
-                hipLaunchKernelGGL(ptk::raygen_lens_kernel, dim3((F.njobs + PT_BLOCK * PT_RG_ROWS - 1) / (PT_BLOCK * PT_RG_ROWS)), block, 0,
-                                   d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
-            else
-                hipLaunchKernelGGL(ptk::raygen_kernel, per_job, block, 0, d.stream, F, fr.cam, d.ray.p, d.ray_rng.p, d.ray_ndraw.p);
-        }))
+            }))
+            return rc;
+    } else if (int32_t rc = launch_pass(d, fr.adaptive, EV_RAYGEN, F.njobs, ptk::raygen_kernel, ptk::raygen_adaptive_kernel, active, F, fr.cam, d.ray.p,
+                                        d.ray_rng.p, d.ray_ndraw.p)) {
         return rc;
+    }
     if (ctx->inject_rays.empty()) return PT_OK;
     if (d.inject_gen != ctx->inject_gen) {
         HIP_TRY(hipStreamSynchronize(d.stream));
@@ -1345,10 +1361,7 @@ int32_t step_fog(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G, c
     FA.S = F.S;
     FA.s0 = F.s0;
     FA.G = G;
-    return timed(d, EV_FOG, [&] {
-        if (fr.adaptive) hipLaunchKernelGGL(ptk::fog_adaptive_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA, active);
-        else hipLaunchKernelGGL(ptk::fog_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, FA);
-    });
+    return launch_pass(d, fr.adaptive, EV_FOG, F.njobs, ptk::fog_kernel, ptk::fog_adaptive_kernel, active, FA);
 }
 
 // The first-hit features of the chunk's samples with index below k into their running sums (pt_set_features)
@@ -1368,71 +1381,24 @@ int32_t step_features(pt_ctx *ctx, Device &d, const DevFrame &F, const ptk::Adap
     A.njobs = F.njobs;
     A.S = F.S;
     A.take = std::min(F.S, (uint32_t)fr.features - F.s0);
-    const uint32_t grid = ((fr.adaptive ? d.nact * 64u : d.nslots) + PT_BLOCK - 1) / PT_BLOCK;
-    return timed(d, EV_FEATURE, [&] {
-        if (fr.adaptive) hipLaunchKernelGGL(ptk::feature_adaptive_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A, AT);
-        else hipLaunchKernelGGL(ptk::feature_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A);
-    });
+    return launch_pass(d, fr.adaptive, EV_FEATURE, live_slots(fr, d), ptk::feature_kernel, ptk::feature_adaptive_kernel, AT, A);
 }
 
-// The chunk's radiance records into the running sums (resolve_kernel), and their squares, in the same order (pt_set_moments)
+// The chunk's radiance records into the running sums (resolve_kernel), then into the sums the frame opted into, each over the same
+// records in the same order: their squares (pt_set_moments), the half-buffer sums (pt_set_halves)
 int32_t step_accumulate(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G, const ptk::AdaptTable &AT) {
     const Frame &fr = ctx->frame;
-    ptk::ResolveArgs R;
-    std::memset(&R, 0, sizeof R);
-    R.L = d.L.p;
-    R.job_seg = fr.stats_on ? d.job_seg.p : nullptr;
-    R.job_draw = fr.stats_on ? d.job_draw.p : nullptr;
-    R.acc = d.acc.p;
-    R.acc_seg = fr.stats_on ? d.acc_seg.p : nullptr;
-    R.acc_draw = fr.stats_on ? d.acc_draw.p : nullptr;
-    R.nslots = d.nslots;
-    R.njobs = F.njobs;
-    R.S = F.S;
-    R.first = d.acc_started ? 0 : 1;
-    R.finish = 0;
-    R.have_chunk = 1;
-    R.inv_samples = 0;
-    R.G = G;
-    const uint32_t add_grid = ((fr.adaptive ? d.nact * 64u : d.nslots) + PT_BLOCK - 1) / PT_BLOCK;
-    if (int32_t rc = timed(d, EV_RESOLVE, [&] {
-            if (fr.adaptive) hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R, AT);
-            else hipLaunchKernelGGL(ptk::resolve_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, R);
-        }))
-        return rc;
-    if (fr.moments) {
-        ptk::MomentsArgs M;
-        std::memset(&M, 0, sizeof M);
-        M.L = d.L.p;
-        M.m2 = d.m2.p;
-        M.nslots = d.nslots;
-        M.S = F.S;
-        M.first = R.first;
-        M.have_chunk = 1;
-        M.G = G;
-        if (int32_t rc = timed(d, EV_MOMENTS, [&] {
-                if (fr.adaptive) hipLaunchKernelGGL(ptk::moments_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M, AT);
-                else hipLaunchKernelGGL(ptk::moments_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, M);
-            }))
+    const ptk::ChunkArgs C{d.L.p, d.nslots, F.S, d.acc_started ? 0 : 1, G};
+    const uint32_t lanes = live_slots(fr, d);
+    const bool st = fr.stats_on;
+    const ptk::ResolveArgs R{C, st ? d.job_seg.p : nullptr, st ? d.job_draw.p : nullptr, d.acc.p, st ? d.acc_seg.p : nullptr, st ? d.acc_draw.p : nullptr};
+    if (int32_t rc = launch_pass(d, fr.adaptive, EV_RESOLVE, lanes, ptk::resolve_kernel, ptk::resolve_adaptive_kernel, AT, R)) return rc;
+    if (fr.moments)
+        if (int32_t rc = launch_pass(d, fr.adaptive, EV_MOMENTS, lanes, ptk::moments_kernel, ptk::moments_adaptive_kernel, AT, ptk::MomentsArgs{C, d.m2.p}))
             return rc;
-    }
-    if (fr.halves) {
-        ptk::HalvesArgs HA;
-        std::memset(&HA, 0, sizeof HA);
-        HA.L = d.L.p;
-        HA.hv = d.hv.p;
-        HA.nslots = d.nslots;
-        HA.S = F.S;
-        HA.s0 = F.s0;
-        HA.first = R.first;
-        HA.have_chunk = 1;
-        HA.G = G;
-        if (int32_t rc = timed(d, EV_HALVES, [&] {
-                if (fr.adaptive) hipLaunchKernelGGL(ptk::halves_adaptive_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, HA, AT);
-                else hipLaunchKernelGGL(ptk::halves_kernel, dim3(add_grid), dim3(PT_BLOCK), 0, d.stream, HA);
-            }))
+    if (fr.halves)
+        if (int32_t rc = launch_pass(d, fr.adaptive, EV_HALVES, lanes, ptk::halves_kernel, ptk::halves_adaptive_kernel, AT, ptk::HalvesArgs{C, d.hv.p, F.s0}))
             return rc;
-    }
     d.acc_started = true;
     return PT_OK;
 }
@@ -1449,8 +1415,8 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     F.nlocal = d.nlocal;
     F.s0 = s0;
     F.S = S;
-    F.njobs = (fr.adaptive ? d.nact * 64u : d.nslots) * S;  // adaptive: the active blocks' jobs only, compact
-    const ptk::AdaptTable AT{d.act[d.act_cur].p, d.blk_spp.p, d.nact};
+    F.njobs = live_slots(fr, d) * S;  // adaptive: the active blocks' jobs only, compact
+    const ptk::AdaptTable AT{d.act[d.act_cur].p, d.nact};
     const TileGeom G = tile_geom(fr, d);
     // jobs a wave claims per pop of the item cursor: 256, and 512 for the bitmask scans once a pass holds 128 samples per pixel
     // or more (same-box sweeps, profiles/r02_claim_sweep.txt: C4 at 265 spp per pass 664 / 653 / 654 / 659 / 673 ms for 256 / 512 /
@@ -1547,71 +1513,29 @@ int32_t dev_adaptive_check(pt_ctx *ctx, Device &d, ptk::AdaptResult *host_res) {
     return PT_OK;
 }
 
-// Writes this device's second moments tile-major (zeros outside the frame), the layout of tiles_accum.  (A Gathered fill.)
-int32_t dev_finish_moments(pt_ctx *ctx, Device &d, uint32_t, void *tiles_m2) {
-    const Frame &fr = ctx->frame;
-    if (d.nlocal == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(d.ordinal));
-    ptk::MomentsArgs M;
-    std::memset(&M, 0, sizeof M);
-    M.m2 = d.m2.p;
-    M.tiles_m2 = static_cast<double *>(tiles_m2);
-    M.nslots = d.nslots;
-    M.first = d.acc_started ? 0 : 1;
-    M.finish = 1;
-    M.G = tile_geom(fr, d);
-    hipLaunchKernelGGL(ptk::moments_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, M);
-    HIP_TRY(hipGetLastError());
-    return PT_OK;
-}
-
-// Writes plane `which` (0 SA, 1 QA, 2 SB, 3 QB) of this device's half-buffer sums tile-major, the layout of tiles_accum.  (A Gathered fill.)
-int32_t dev_finish_halves(pt_ctx *ctx, Device &d, uint32_t which, void *tiles) {
-    const Frame &fr = ctx->frame;
-    if (d.nlocal == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(d.ordinal));
-    ptk::HalvesArgs HA;
-    std::memset(&HA, 0, sizeof HA);
-    HA.hv = d.hv.p;
-    HA.tiles = static_cast<double *>(tiles);
-    HA.nslots = d.nslots;
-    HA.first = d.acc_started ? 0 : 1;
-    HA.finish = 1;
-    HA.which = which;
-    HA.G = tile_geom(fr, d);
-    hipLaunchKernelGGL(ptk::halves_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, HA);
-    HIP_TRY(hipGetLastError());
-    return PT_OK;
-}
-
-// Writes the current estimate of this device's tiles (normalised by spp_done).
+// Writes the current estimate of this device's tiles (normalised by spp_done; in an adaptive frame every pixel by the count of its own block).
 int32_t dev_finish(pt_ctx *ctx, Device &d, int32_t spp_done, uint8_t *tiles_rgba, double *tiles_accum,
                    uint32_t *tiles_seg, uint32_t *tiles_draw) {
     Frame &fr = ctx->frame;
     if (d.nlocal == 0) return PT_OK;
     HIP_TRY(hipSetDevice(d.ordinal));
-    ptk::ResolveArgs R;
-    std::memset(&R, 0, sizeof R);
-    R.acc = d.acc.p;
-    R.acc_seg = fr.stats_on ? d.acc_seg.p : nullptr;
-    R.acc_draw = fr.stats_on ? d.acc_draw.p : nullptr;
-    R.tiles_rgba = tiles_rgba;
-    R.tiles_accum = tiles_accum;
-    R.tiles_seg = fr.stats_on ? tiles_seg : nullptr;
-    R.tiles_draw = fr.stats_on ? tiles_draw : nullptr;
-    R.nslots = d.nslots;
-    R.first = d.acc_started ? 0 : 1;
-    R.finish = 1;
-    R.have_chunk = 0;
-    R.inv_samples = 1.0 / (double)spp_done;  // renderer.go:97
-    R.gl_spp = fr.gl ? std::max(1, spp_done) : 0;  // GL shading: tone-mapped finish of accum / passes
-    R.G = tile_geom(fr, d);
+    ptk::FinishArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.acc = d.acc.p;
+    A.acc_seg = d.acc_seg.p;
+    A.acc_draw = d.acc_draw.p;
+    A.blk_spp = fr.adaptive ? d.blk_spp.p : nullptr;
+    A.tiles_rgba = tiles_rgba;
+    A.tiles_accum = tiles_accum;
+    A.tiles_seg = fr.stats_on ? tiles_seg : nullptr;
+    A.tiles_draw = fr.stats_on ? tiles_draw : nullptr;
+    A.nslots = d.nslots;
+    A.zero = d.acc_started ? 0 : 1;
+    A.inv_samples = 1.0 / (double)spp_done;  // renderer.go:97
+    A.gl_spp = fr.gl ? std::max(1, spp_done) : 0;  // GL shading: tone-mapped finish of accum / passes
+    A.G = tile_geom(fr, d);
     if (int32_t rc = timed(d, EV_RESOLVE, [&] {
-            if (fr.adaptive)  // every pixel by the count of its own block
-                hipLaunchKernelGGL(ptk::resolve_adaptive_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R,
-                                   ptk::AdaptTable{d.act[d.act_cur].p, d.blk_spp.p, d.nact});
-            else
-                hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
+            hipLaunchKernelGGL(ptk::finish_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, A);
         }))
         return rc;
     HIP_TRY(hipEventRecord(d.ev_last, d.stream));
@@ -2216,18 +2140,12 @@ Plane plane_row(PlaneKind kind) {
     return {true, kind, reserved<Device, Tiles>, reserved<pt_ctx, Gather>, reserved<pt_ctx, Framed>, nullptr, 0};
 }
 
-// The fills: the finished sums S (dev_finish's resolve for accum alone, untimed); Q and half-sum plane `which` are
-// dev_finish_moments and dev_finish_halves
-int32_t fill_sums(pt_ctx *ctx, Device &d, uint32_t, void *dst) {
-    ptk::ResolveArgs R;
-    std::memset(&R, 0, sizeof R);
-    R.acc = d.acc.p;
-    R.tiles_accum = static_cast<double *>(dst);
-    R.nslots = d.nslots;
-    R.first = d.acc_started ? 0 : 1;
-    R.finish = 1;
-    R.G = tile_geom(ctx->frame, d);
-    hipLaunchKernelGGL(ptk::resolve_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, R);
+// The fills.  Group `which` of one of the device's arrays of per-slot double sums (planes_tiles_kernel): the radiance sums S, their
+// squares Q, a half-buffer sum (0 SA, 1 QA, 2 SB, 3 QB), a feature plane (0 normal, 1 albedo, 2 depth); zeros before the first chunk
+template <auto Sums>
+int32_t fill_sum(pt_ctx *ctx, Device &d, uint32_t which, void *dst) {
+    hipLaunchKernelGGL(ptk::planes_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, (d.*Sums).p,
+                       static_cast<double *>(dst), d.nslots, which, d.acc_started ? 0 : 1, tile_geom(ctx->frame, d));
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
@@ -2235,13 +2153,6 @@ int32_t fill_sums(pt_ctx *ctx, Device &d, uint32_t, void *dst) {
 int32_t fill_counts(pt_ctx *ctx, Device &d, uint32_t, void *dst) {
     hipLaunchKernelGGL(ptk::counts_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.blk_spp.p,
                        static_cast<uint32_t *>(dst), d.nslots, tile_geom(ctx->frame, d));
-    HIP_TRY(hipGetLastError());
-    return PT_OK;
-}
-// feature plane `which`: 0 normal, 1 albedo, 2 depth
-int32_t fill_feature(pt_ctx *ctx, Device &d, uint32_t which, void *dst) {
-    hipLaunchKernelGGL(ptk::feature_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.feat.p,
-                       static_cast<double *>(dst), d.nslots, which, tile_geom(ctx->frame, d));
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
@@ -2253,17 +2164,17 @@ int32_t fill_ids(pt_ctx *ctx, Device &d, uint32_t, void *dst) {
     return PT_OK;
 }
 
-const Gathered g_sums = {plane_row<&Device::tiles_accum, &pt_ctx::g_tiles_accum, &pt_ctx::f_accum>(PLANE_F64X3), fill_sums, 0};
-const Gathered g_m2 = {plane_row<&Device::tiles_m2, &pt_ctx::g_tiles_m2, &pt_ctx::f_m2>(PLANE_F64X3), dev_finish_moments, 0};
+const Gathered g_sums = {plane_row<&Device::tiles_accum, &pt_ctx::g_tiles_accum, &pt_ctx::f_accum>(PLANE_F64X3), fill_sum<&Device::acc>, 0};
+const Gathered g_m2 = {plane_row<&Device::tiles_m2, &pt_ctx::g_tiles_m2, &pt_ctx::f_m2>(PLANE_F64X3), fill_sum<&Device::m2>, 0};
 const Gathered g_counts = {plane_row<&Device::tiles_seg, &pt_ctx::g_tiles_seg, &pt_ctx::f_seg>(PLANE_U32A), fill_counts, 0};
-const Gathered g_feature[3] = {{plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_n>(PLANE_F64X3), fill_feature, 0},
-                               {plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_a>(PLANE_F64X3), fill_feature, 1},
-                               {plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_d>(PLANE_F64X3), fill_feature, 2}};
+const Gathered g_feature[3] = {{plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_n>(PLANE_F64X3), fill_sum<&Device::feat>, 0},
+                               {plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_a>(PLANE_F64X3), fill_sum<&Device::feat>, 1},
+                               {plane_row<&Device::tiles_feat, &pt_ctx::g_tiles_feat, &pt_ctx::f_feat_d>(PLANE_F64X3), fill_sum<&Device::feat>, 2}};
 const Gathered g_ids = {plane_row<&Device::tiles_seg, &pt_ctx::g_tiles_seg, &pt_ctx::f_ids>(PLANE_U32A), fill_ids, 0};
-const Gathered g_half[4] = {{plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_sa>(PLANE_F64X3), dev_finish_halves, 0},
-                            {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_qa>(PLANE_F64X3), dev_finish_halves, 1},
-                            {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_sb>(PLANE_F64X3), dev_finish_halves, 2},
-                            {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_qb>(PLANE_F64X3), dev_finish_halves, 3}};
+const Gathered g_half[4] = {{plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_sa>(PLANE_F64X3), fill_sum<&Device::hv>, 0},
+                            {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_qa>(PLANE_F64X3), fill_sum<&Device::hv>, 1},
+                            {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_sb>(PLANE_F64X3), fill_sum<&Device::hv>, 2},
+                            {plane_row<&Device::tiles_hv, &pt_ctx::g_tiles_hv, &pt_ctx::f_hv_qb>(PLANE_F64X3), fill_sum<&Device::hv>, 3}};
 
 // The inputs of the post-frame filters as row-major planes on devices[0]: the four half sums or S and Q, the counts of an adaptive
 // frame, the features of a frame that has them.  All reads: the sums, the block table and the event lists of the frame stay as they are.
@@ -3181,9 +3092,8 @@ int32_t pt_noise_estimate(pt_ctx *ctx, pt_noise *out) {
         A.nslots = d.nslots;
         A.n = fr.done_spp;
         A.G = tile_geom(fr, d);
-        if (fr.adaptive) hipLaunchKernelGGL(ptk::noise_adaptive_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A, d.blk_spp.p);  // every pixel with its own n
-        else hipLaunchKernelGGL(ptk::noise_kernel, dim3(grid), dim3(PT_BLOCK), 0, d.stream, A);
-        HIP_TRY(hipGetLastError());
+        // (adaptive: every slot of the shard too, each pixel with the n of its own block)
+        if (int32_t rc = launch_pass(d, fr.adaptive, EV_KINDS, d.nslots, ptk::noise_kernel, ptk::noise_adaptive_kernel, d.blk_spp.p, A)) return rc;
         part.resize(grid);
         HIP_TRY(hipMemcpyAsync(part.data(), d.noise_part.p, grid * sizeof(ptk::NoisePartial), hipMemcpyDeviceToHost, d.stream));
         HIP_TRY(hipStreamSynchronize(d.stream));
