@@ -8,6 +8,7 @@
 // -adaptive -min-spp (with -noise: every 8x8 block stops at the target by itself; DESIGN 3.10).
 // -atrous -atrous-iters -features (the variance-guided a-trous filtered image and its first-hit feature samples; DESIGN 3.11).
 // -filtered-noise (with -atrous: render until the measured noise of the filtered frame is at or below the target; DESIGN 3.12).
+// -feature-walk (features on scenes that take the BVH path, by a wave-shared walk of the tree; DESIGN 3.11a).
 package main
 
 import (
@@ -43,6 +44,7 @@ func main() {
 	atrousIters := flag.Int("atrous-iters", 5, "with -atrous: iterations 0..6 (or PATHTRACER_GPU_ATROUS_ITERS)")
 	features := flag.Int("features", -1, "first-hit feature samples per pixel (default: 4 with -atrous where the scene allows them, else 0; or PATHTRACER_GPU_FEATURES)")
 	filteredNoise := flag.Float64("filtered-noise", 0, "with -atrous: render until the measured noise of the filtered frame is at or below this target, checking every -noise-step samples, -spp being the cap (0 = off, or PATHTRACER_GPU_FILTERED_NOISE)")
+	featureWalk := flag.Bool("feature-walk", false, "collect features on scenes beyond 128 spheres or 128 boxes too, by a wave-shared walk of the tree (or PATHTRACER_GPU_FEATURE_WALK)")
 	flag.Parse()
 	log.Printf("flags: scene=%s mode=%s headless=%v out=%s\n", *scenePath, *mode, *headless, *output)
 
@@ -70,6 +72,11 @@ func main() {
 		}
 		if featuresGiven {
 			hip.SetFeatures(*features)
+		}
+		walkGiven := false
+		flag.Visit(func(f *flag.Flag) { walkGiven = walkGiven || f.Name == "feature-walk" })
+		if walkGiven { // else the environment decides
+			hip.SetFeatureWalk(*featureWalk)
 		}
 		filteredGiven := false
 		flag.Visit(func(f *flag.Flag) { filteredGiven = filteredGiven || f.Name == "filtered-noise" })

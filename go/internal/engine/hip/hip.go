@@ -74,6 +74,9 @@ var (
 	motionSet    bool // false: PATHTRACER_GPU_TEMPORAL_MOTION decides
 	motionOn     bool
 	idsOn        bool           // pt_set_object_ids(1) was the last thing said to the context
+	walkSet      bool           // false: PATHTRACER_GPU_FEATURE_WALK decides
+	walkWanted   bool
+	walkOn       bool           // pt_set_feature_walk(1) was the last thing said to the context
 	accumulated  *scene.Scene   // a copy of the scene of the last frame accumulated with displaced reprojection on (nil: none)
 	lastMotion   TemporalMotion // pt_temporal_motion_stats of the last frame (zero unless it was accumulated with the rule on)
 
@@ -127,6 +130,7 @@ func SetDevices(n int) {
 		C.pt_destroy(ctx)
 		ctx = nil
 		idsOn, accumulated = false, nil
+		walkOn = false
 	}
 	initErr = nil
 	if n > 0 {
@@ -375,6 +379,27 @@ func SetTemporalMotion(on bool) {
 	motionSet, motionOn = true, on
 }
 
+// SetFeatureWalk lets scenes on the BVH path (more than 128 spheres or 128 boxes) collect the first-hit feature planes, by a
+// wave-shared walk of the tree (pt_set_feature_walk, DESIGN 3.11a): the filter's feature terms, the accumulation and the object ids
+// then work there too.  Not set: PATHTRACER_GPU_FEATURE_WALK decides.
+func SetFeatureWalk(on bool) {
+	mu.Lock()
+	defer mu.Unlock()
+	walkSet, walkWanted = true, on
+}
+
+// walkRule: whether features on the BVH path are in force (SetFeatureWalk, else the environment).
+func walkRule() bool {
+	if walkSet {
+		return walkWanted
+	}
+	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_FEATURE_WALK"))) {
+	case "1", "true", "on", "yes":
+		return true
+	}
+	return false
+}
+
 // LastTemporalMotion reports the rule's figures for the last frame Render finished (the zero value unless the rule was in force).
 func LastTemporalMotion() TemporalMotion {
 	mu.Lock()
@@ -492,7 +517,7 @@ func atrousRule() (bool, int) {
 }
 
 // featuresRule: the feature samples per pixel of the next frame.  Not said (SetFeatures, PATHTRACER_GPU_FEATURES): 4 under the
-// filter unless the frame would refuse them (GL shading, a scene on the BVH path), else 0.
+// filter unless the frame would refuse them (GL shading, a scene on the BVH path without SetFeatureWalk), else 0.
 func featuresRule(sc *scene.Scene, atrous bool) int {
 	if featuresK >= 0 {
 		return featuresK
@@ -505,6 +530,9 @@ func featuresRule(sc *scene.Scene, atrous bool) int {
 	}
 	if !atrous || glShading() {
 		return 0
+	}
+	if walkRule() {
+		return 4
 	}
 	spheres, boxes := 0, 0
 	for _, o := range sc.Objects {
@@ -896,6 +924,16 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 	}
 	if rc := C.pt_set_halves(ctx, halvesOn); rc != C.PT_OK {
 		return lastError("pt_set_halves")
+	}
+	if walk := walkRule(); walk != walkOn { // (said only when the switch changes: with it never on, the calls are what they were)
+		var w C.int32_t
+		if walk {
+			w = 1
+		}
+		if rc := C.pt_set_feature_walk(ctx, w); rc != C.PT_OK {
+			return lastError("pt_set_feature_walk")
+		}
+		walkOn = walk
 	}
 	if rc := C.pt_set_features(ctx, C.int32_t(featuresRule(sc, atrous))); rc != C.PT_OK {
 		return lastError("pt_set_features")

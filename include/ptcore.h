@@ -438,7 +438,18 @@ int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp);
  *                             72 B per pixel on the devices, outside PTCORE_L_BUDGET_MB.  pt_render_tiles_device neither collects
  *                             nor fails.  A frame with k > 0 is refused with PT_ERR_INVALID, before anything is launched and with the
  *                             context left usable, for scenes on the bounding-volume-hierarchy path (more than 128 spheres or 128
- *                             boxes) and with GL shading (pt_set_shading).
+ *                             boxes) and with GL shading (pt_set_shading).  pt_set_feature_walk lifts the first refusal.
+ *   pt_set_feature_walk(ctx, on) : default 0; PT_ERR_STATE while a frame is open.  With it on, a frame with k > 0 on the bounding-
+ *                             volume-hierarchy path is accepted: the first hit of a feature sample is found by one walk of the tree
+ *                             per wave of 64 coherent primary rays (an 8 x 8 pixel block) instead of a linear scan,
+ *                             with the same tests and the same winner -- the planes and ids are those of the definition above, bit
+ *                             for bit.  A wave that holds a ray outside the range the walk was analysed for (non-finite or absurd
+ *                             components, an origin beyond 3.5 scene sizes) takes the plain scan for that sample.  Frames on the
+ *                             other scans ignore the setting.  GL shading, and volumetric fog on that path, stay refused.
+ *   pt_feature_walk_stats   : out[0] = (wave, feature sample) pairs of the last frame walked by the wave, out[1] = those sent to the
+ *                             plain scan, out[2] = node visits of the walks, out[3] = the deepest wave stack seen; summed over the
+ *                             devices (out[3]: their largest).  PT_ERR_STATE when the last frame did not run the walk.  Waits for
+ *                             the devices' streams.
  *   pt_read_features        : normal / albedo / depth = width*height*3 doubles each, row-major, any of them NULL.  Valid exactly
  *                             when pt_read_moments is (so the frame collects moments); PT_ERR_STATE otherwise and for a frame with k = 0.
  *   pt_set_object_ids(ctx, on) : default 0; PT_ERR_STATE while a frame is open.  Later frames on ctx with features on (k > 0) also
@@ -493,6 +504,8 @@ typedef struct pt_atrous_stats {
 
 int32_t pt_set_features(pt_ctx *ctx, int32_t k);
 int32_t pt_read_features(pt_ctx *ctx, double *normal, double *albedo, double *depth);
+int32_t pt_set_feature_walk(pt_ctx *ctx, int32_t on);
+int32_t pt_feature_walk_stats(pt_ctx *ctx, uint64_t out[4]);
 int32_t pt_set_object_ids(pt_ctx *ctx, int32_t on);
 int32_t pt_read_object_ids(pt_ctx *ctx, int32_t *ids);
 int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32_t stride, double *mean, double *var,

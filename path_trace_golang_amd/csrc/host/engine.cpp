@@ -60,7 +60,7 @@ namespace {
     OPTIONAL(pt_adaptive_state) OPTIONAL(pt_set_features) OPTIONAL(pt_atrous) OPTIONAL(pt_set_halves) OPTIONAL(pt_atrous_halves) \
     OPTIONAL(pt_temporal) OPTIONAL(pt_temporal_reset) OPTIONAL(pt_temporal_set_clip) OPTIONAL(pt_temporal_clip_stats)           \
     OPTIONAL(pt_set_object_ids) OPTIONAL(pt_temporal_set_motion) OPTIONAL(pt_temporal_motion_stats)                              \
-    OPTIONAL(pt_set_adaptive_filtered) OPTIONAL(pt_read_block_figures)
+    OPTIONAL(pt_set_adaptive_filtered) OPTIONAL(pt_read_block_figures) OPTIONAL(pt_set_feature_walk)
 
 struct Core {
     void *handle = nullptr;
@@ -71,7 +71,7 @@ struct Core {
 };
 
 // What a frame setting needs from the library beyond the required entry points, and what Render answers when it is not there.
-enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE };
+enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE, FEATURE_WALK };
 const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_shading != nullptr; }, "GL shading: libptcore.so lacks pt_set_shading"},
     {[](const Core &c) { return c.pt_set_moments && c.pt_noise_estimate; }, "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate"},
@@ -85,6 +85,7 @@ const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
      "temporal motion: libptcore.so lacks pt_set_object_ids / pt_temporal_set_motion"},
     {[](const Core &c) { return c.pt_set_adaptive_filtered && c.pt_read_block_figures && c.pt_set_adaptive && c.pt_adaptive_state; },
      "filtered adaptive target: libptcore.so lacks pt_set_adaptive_filtered / pt_read_block_figures"},
+    {[](const Core &c) { return c.pt_set_feature_walk != nullptr; }, "feature walk: libptcore.so lacks pt_set_feature_walk"},
 };
 
 // What the Set* calls said; an empty field leaves the matter to the environment (the *FromEnv rules).
@@ -92,7 +93,7 @@ struct NoiseRule { double target; int step; };
 struct Switch { bool on; int n; };  // adaptive + min_spp, a-trous + iterations
 struct BlockRule { double target; int pool; };
 struct Settings {
-    std::optional<bool> fog, temporal, temporal_motion;
+    std::optional<bool> fog, temporal, temporal_motion, feature_walk;
     std::optional<int> shading, features;
     std::optional<NoiseRule> noise;
     std::optional<Switch> adaptive, atrous;
@@ -321,6 +322,7 @@ void FilteredAdaptiveFromEnv(double &target, int &pool) {
 bool TemporalFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL"); }
 double TemporalClipFromEnv() { return env_double("PATHTRACER_GPU_TEMPORAL_CLIP", finite_not_negative, 0); }
 bool TemporalMotionFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL_MOTION"); }
+bool FeatureWalkFromEnv() { return env_switch("PATHTRACER_GPU_FEATURE_WALK"); }
 
 namespace {
 
@@ -337,6 +339,7 @@ struct FramePlan {
     double filtered;      // > 0 only under the filter
     BlockRule blocks;     // target > 0 only under the filter: an adaptive frame whose blocks stop by the filtered frame's pooled noise
     int features;
+    bool walk;            // features on the BVH path too (pt_set_feature_walk)
     bool moments, halves;
 };
 
@@ -377,8 +380,9 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
     p.blocks = block_rule(s);
     if (!p.atrous.on) p.blocks.target = 0;
     p.features = s.features.value_or(FeaturesFromEnv());
+    p.walk = s.feature_walk.value_or(FeatureWalkFromEnv());
     if (p.features < 0 && p.temporal) p.features = 4;  // (pt_temporal needs them: where the frame refuses features, pt_begin says so)
-    if (p.features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path), else off
+    if (p.features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path without the walk), else off
         p.features = 0;
         if (p.atrous.on && p.shading != PT_SHADING_GL) {
             size_t spheres = 0, boxes = 0;
@@ -388,7 +392,7 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
             }
             const char *scan = std::getenv("PTCORE_SCAN");
             const bool forced_bvh = scan && (!std::strcmp(scan, "bvh") || !std::strcmp(scan, "verify_bvh"));
-            if (spheres <= 128 && boxes <= 128 && !forced_bvh) p.features = 4;
+            if (p.walk || (spheres <= 128 && boxes <= 128 && !forced_bvh)) p.features = 4;
         }
     }
     p.moments = p.noise.target > 0 || p.atrous.on;
@@ -408,6 +412,7 @@ struct AccumulatedScene {
 AccumulatedScene g_accumulated;
 bool g_object_ids_on = false;  // pt_set_object_ids(1) was the last thing said to the context
 bool g_block_rule_on = false;  // pt_set_adaptive_filtered(&f) was the last thing said to the context
+bool g_feature_walk_on = false;  // pt_set_feature_walk(1) was the last thing said to the context
 
 // Both belong to the context: a new one has object ids off and an empty history.  Called with g_mu held.
 void drop_context() {
@@ -416,6 +421,7 @@ void drop_context() {
     g_accumulated.valid = false;
     g_object_ids_on = false;
     g_block_rule_on = false;
+    g_feature_walk_on = false;
 }
 
 void remember(const scene::Scene &sc, const Flat &flat, AccumulatedScene &a) {
@@ -564,6 +570,14 @@ bool TemporalMotion() {
     std::lock_guard<std::mutex> lk(g_mu);
     return g_set.temporal_motion.value_or(TemporalMotionFromEnv());
 }
+void SetFeatureWalk(bool on) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_set.feature_walk = on;
+}
+bool FeatureWalk() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_set.feature_walk.value_or(FeatureWalkFromEnv());
+}
 void SetFeatures(int k) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (k >= 0) g_set.features = k;
@@ -630,6 +644,11 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (lacks(to_blocks, FILTERED_ADAPTIVE)) return missing;
     if (g_core.pt_set_halves && failed(PT_CALL(pt_set_halves, g_ctx, p.halves ? 1 : 0))) return err;
     if (lacks(p.features > 0, FEATURES)) return missing;
+    if (lacks(p.walk, FEATURE_WALK)) return missing;
+    if (p.walk != g_feature_walk_on) {  // (said only when the switch changes: with it never on, the calls are what they were)
+        if (failed(PT_CALL(pt_set_feature_walk, g_ctx, p.walk ? 1 : 0))) return err;
+        g_feature_walk_on = p.walk;
+    }
     if (g_core.pt_set_features && failed(PT_CALL(pt_set_features, g_ctx, p.features))) return err;
     if (p.motion != g_object_ids_on) {  // (said only when the switch changes: with it never on, the calls are what they were)
         if (failed(PT_CALL(pt_set_object_ids, g_ctx, p.motion ? 1 : 0))) return err;

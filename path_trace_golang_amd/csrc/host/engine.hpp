@@ -141,6 +141,12 @@ bool TemporalClipStats(double &gamma, uint64_t &clipped, uint64_t &reprojected);
 void SetTemporalMotion(bool on);
 bool TemporalMotion();
 bool TemporalMotionFromEnv();  // PATHTRACER_GPU_TEMPORAL_MOTION = 1 / true / on / yes
+// Features on the BVH path (pt_set_feature_walk): scenes beyond 128 spheres or 128 boxes collect the feature planes by a
+// wave-shared walk of the tree, so the filter's feature terms, the accumulation and the object ids work there too.  Off unless said
+// or PATHTRACER_GPU_FEATURE_WALK (FeatureWalkFromEnv); with it on, the unsaid feature count is 4 under the filter on those scenes too.
+void SetFeatureWalk(bool on);
+bool FeatureWalk();
+bool FeatureWalkFromEnv();  // PATHTRACER_GPU_FEATURE_WALK = 1 / true / on / yes
 void SetFeatures(int k);
 int GetFeatures();     // -1: not said
 int FeaturesFromEnv(); // PATHTRACER_GPU_FEATURES = int >= 0, else -1

@@ -20,8 +20,10 @@
 // samples, with -spp as the cap (also env PATHTRACER_GPU_FILTERED_NOISE); it excludes -noise.  -filtered-adaptive T (with -atrous) stops every
 // 8x8 block of an adaptive frame by the filtered frame's noise pooled over the blocks within -pool N (0..4, default 1) blocks of it
 // (pt_set_adaptive_filtered; also env PATHTRACER_GPU_FILTERED_ADAPTIVE, PATHTRACER_GPU_POOL); -noise-step and -min-spp
-// apply, and it excludes -noise and -filtered-noise.  These two flags are parsed like the others but are not in the usage text below,
-// which stands as recorded in tests/golden/host_traces.json.
+// apply, and it excludes -noise and -filtered-noise.  -feature-walk lets a scene on the bounding-volume-hierarchy path (more than 128
+// spheres or 128 boxes) collect features, by a wave-shared walk of the tree (pt_set_feature_walk; also env
+// PATHTRACER_GPU_FEATURE_WALK).  These three flags are parsed like the others but are not in the usage text below, which stands as
+// recorded in tests/golden/host_traces.json.
 #include <cerrno>
 #include <chrono>
 #include <climits>
@@ -75,6 +77,7 @@ struct Flags {
     double filtered_noise = 0;
     double filtered_adaptive = 0;
     int pool = 1;
+    bool feature_walk = false;
 };
 
 void usage() {
@@ -138,7 +141,7 @@ int bad_flag(const char *fmt, const std::string &a, const std::string &b = "") {
 int parse(int argc, char **argv, Flags &f) {
     const FlagRow table[] = {
         {"gpu", BOOL, &f.gpu}, {"headless", BOOL, &f.headless}, {"scene-settings", BOOL, &f.scene_settings}, {"fog", BOOL, &f.fog},
-        {"adaptive", BOOL, &f.adaptive}, {"atrous", BOOL, &f.atrous},
+        {"adaptive", BOOL, &f.adaptive}, {"atrous", BOOL, &f.atrous}, {"feature-walk", BOOL, &f.feature_walk},
         {"scene", STRING, &f.scene}, {"mode", STRING, &f.mode}, {"out", STRING, &f.out}, {"shading", SHADING, &f.shading},
         {"width", INT, &f.width}, {"height", INT, &f.height}, {"spp", INT, &f.spp}, {"depth", INT, &f.depth}, {"devices", INT, &f.devices},
         {"noise-step", INT, &f.noise_step, 1, 0x7fffffffLL, 16}, {"min-spp", INT, &f.min_spp, 0, 0x7fffffffLL, 0},
@@ -218,6 +221,7 @@ int render_headless(const Flags &f) {
     engine::hip::SetAdaptive(f.adaptive, f.min_spp);
     engine::hip::SetAtrous(f.atrous, f.atrous_iters);
     engine::hip::SetFeatures(f.features);
+    engine::hip::SetFeatureWalk(f.feature_walk);
     engine::hip::SetFilteredNoise(f.filtered_noise);
     engine::hip::SetFilteredAdaptive(f.filtered_adaptive, f.pool);
     if (f.filtered_adaptive > 0 && !f.atrous) logf("filtered-adaptive: no -atrous given, nothing to measure (a plain frame)");
@@ -286,6 +290,7 @@ int main(int argc, char **argv) {
     engine::hip::AdaptiveFromEnv(f.adaptive, f.min_spp);
     engine::hip::AtrousFromEnv(f.atrous, f.atrous_iters);
     f.features = engine::hip::FeaturesFromEnv();
+    f.feature_walk = engine::hip::FeatureWalkFromEnv();
     f.filtered_noise = engine::hip::FilteredNoiseFromEnv();
     engine::hip::FilteredAdaptiveFromEnv(f.filtered_adaptive, f.pool);
     int rc = parse(argc, argv, f);

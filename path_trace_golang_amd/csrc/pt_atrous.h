@@ -91,16 +91,11 @@ namespace pta {
 
 // ---------------------------------------------------------------- features
 
-// The first hit of the primary ray (o, d) against the world: false on a miss; n = the face-forward normal, a = the albedo of the
-// hit object's converted material, dist = t * |d|; *index (when asked for) = the winner's index into objs, -1 on a miss.
-PT_HD bool first_hit(const ptd::DevObj *objs, const ptd::DevMat *mats, int32_t nobj, const double o[3], const double d[3], double n[3],
-                     double a[3], double &dist, int32_t *index = nullptr) {
-    const ptf::FRay r = ptf::make_fray(o[0], o[1], o[2], d[0], d[1], d[2]);
-    double t;
-    int32_t best;
-    const bool any = ptf::closest_hit(objs, nobj, r, t, best);
-    if (index) *index = best;
-    if (!any) return false;
+// The feature record of the hit of the ray (o, d) on objs[best] at parameter t: n = the face-forward normal, a = the albedo of the
+// object's converted material, dist = t * |d|.  The one statement of the record: first_hit and the BVH walk's kernels
+// (pt_feature_walk.h) both end here.
+PT_HD void hit_record(const ptd::DevObj *objs, const ptd::DevMat *mats, int32_t best, double t, const double o[3], const double d[3], double n[3],
+                      double a[3], double &dist) {
     const ptd::DevObj &ob = objs[best];
     const int kind = ob.kind & 0xff;
     double nx, ny, nz;
@@ -136,6 +131,19 @@ PT_HD bool first_hit(const ptd::DevObj *objs, const ptd::DevMat *mats, int32_t n
     const ptd::DevMat &mt = mats[ob.mat];
     a[0] = mt.albedo[0]; a[1] = mt.albedo[1]; a[2] = mt.albedo[2];
     dist = t * ptm::f_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+}
+
+// The first hit of the primary ray (o, d) against the world: false on a miss; n, a, dist = the hit's record (hit_record); *index
+// (when asked for) = the winner's index into objs, -1 on a miss.
+PT_HD bool first_hit(const ptd::DevObj *objs, const ptd::DevMat *mats, int32_t nobj, const double o[3], const double d[3], double n[3],
+                     double a[3], double &dist, int32_t *index = nullptr) {
+    const ptf::FRay r = ptf::make_fray(o[0], o[1], o[2], d[0], d[1], d[2]);
+    double t;
+    int32_t best;
+    const bool any = ptf::closest_hit(objs, nobj, r, t, best);
+    if (index) *index = best;
+    if (!any) return false;
+    hit_record(objs, mats, best, t, o, d, n, a, dist);
     return true;
 }
 

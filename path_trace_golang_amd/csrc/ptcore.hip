@@ -34,6 +34,7 @@
 #include "pt_wavefront.h"
 #include "pt_walk32.h"
 #include "pt_primary.h"
+#include "pt_feature_walk.h"
 #include "pt_math.h"
 
 using namespace ptd;
@@ -222,6 +223,7 @@ struct Device {
     EventList ev[EV_KINDS];
     DevBuf<ptf::FogLight> fog_lights;        // the frame's light list (fog on)
     DevBuf<unsigned long long> fog_counters; // [3] shadow rays, draws, march steps of the frame
+    DevBuf<unsigned long long> walk_counters; // [4] pt_set_feature_walk: (wave, sample) pairs walked, ... scanned plainly, node visits, deepest stack
     DevBuf<ptg::GlObj> gl_objs;              // GL shading: the frame's objects, materials and light list
     DevBuf<ptg::GlMat> gl_mats;
     DevBuf<int32_t> gl_lights;
@@ -271,6 +273,7 @@ struct Frame {
     bool halves = false;   // pt_set_halves: halves_kernel runs after every chunk's moments_kernel (pt_begin / pt_render frames only; implies moments)
     uint64_t serial = 0;   // pt_ctx::frames_opened when the frame opened: tells two frames of a context apart
     int32_t features = 0;  // pt_set_features: feature_kernel runs after the chunks that hold samples below this index (pt_begin / pt_render frames only)
+    bool feature_walk = false;  // pt_set_feature_walk on a BVH scan: feature_bvh_kernel (pt_feature_walk.h) in feature_kernel's place
     bool object_ids = false;  // pt_set_object_ids: feature_kernel also records the object of sample 0's first hit
     int32_t scene_objects = 0;  // ... pt_scene.num_objects of the frame, the length a motion table must have
     std::vector<int32_t> world_scene;  // ... per object of the device world its index into pt_scene.objects
@@ -331,6 +334,7 @@ struct pt_ctx {
     bool adaptive_on = false;         // pt_set_adaptive
     int32_t features_k = 0;           // pt_set_features: feature samples per pixel (0 = off)
     DevBuf<double> g_tiles_feat, f_feat_n, f_feat_a, f_feat_d;  // pt_read_features / pt_atrous: one gathered plane, the three row-major frames
+    bool feature_walk_on = false;     // pt_set_feature_walk: features on the BVH path, by the wave-shared walk
     bool object_ids_on = false;       // pt_set_object_ids
     DevBuf<uint32_t> f_ids;           // pt_read_object_ids / pt_temporal with a motion table: the row-major plane (the bits of int32, scene indices)
     // The buffers of the post-frame filters, on devices[0]: allocated on the first call, never shrunk.
@@ -1381,6 +1385,10 @@ int32_t step_features(pt_ctx *ctx, Device &d, const DevFrame &F, const ptk::Adap
     A.njobs = F.njobs;
     A.S = F.S;
     A.take = std::min(F.S, (uint32_t)fr.features - F.s0);
+    if (fr.feature_walk) {  // BVH scans with pt_set_feature_walk: the same slots, the first hit by the wave's walk of the tree
+        const ptk::FeatureWalkArgs W{A, F, d.bvh_nodes.p, d.bvh_objs.p, d.plane_idx.p, d.walk_counters.p};
+        return launch_pass(d, fr.adaptive, EV_FEATURE, live_slots(fr, d), ptk::feature_bvh_kernel, ptk::feature_bvh_adaptive_kernel, AT, W);
+    }
     return launch_pass(d, fr.adaptive, EV_FEATURE, live_slots(fr, d), ptk::feature_kernel, ptk::feature_adaptive_kernel, AT, A);
 }
 
@@ -2802,13 +2810,14 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
     ctx->frame.moments = ctx->moments_on || ctx->adaptive_on || ctx->halves_on;
     if (ctx->features_k > 0) {  // refused before anything is launched; the context stays usable
         const bool bvh = ctx->frame.scan == ptk::SCAN_BVH || ctx->frame.scan == ptk::SCAN_VERIFY_BVH;
-        if (bvh || ctx->frame.gl) {
+        if ((bvh && !ctx->feature_walk_on) || ctx->frame.gl) {
             ctx->frame.open = false;
             return fail(PT_ERR_INVALID, bvh ? "features: not available for scenes on the BVH path (more than 128 spheres or 128 boxes): a linear "
                                               "scan per feature sample"
                                             : "features: not available with GL shading (pt_set_shading), where a sample is a pass of 16 paths");
         }
         ctx->frame.features = ctx->features_k;
+        ctx->frame.feature_walk = bvh;  // (only with pt_set_feature_walk; the other scans ignore the setting)
     }
     if (ctx->object_ids_on) {
         if (ctx->frame.features <= 0) {  // refused before anything is launched; the context stays usable
@@ -2835,6 +2844,12 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
             hipError_t e = hipSetDevice(d.ordinal);
             if (e == hipSuccess) e = d.feat.reserve(9 * (size_t)d.nslots);
             if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("features: ") + hipGetErrorString(e));
+        }
+        if (rc == PT_OK && ctx->frame.feature_walk && d.nlocal > 0) {  // the walk's counters, zeroed when the frame opens
+            hipError_t e = hipSetDevice(d.ordinal);
+            if (e == hipSuccess) e = d.walk_counters.reserve(4);
+            if (e == hipSuccess) e = hipMemsetAsync(d.walk_counters.p, 0, 4 * sizeof(unsigned long long), d.stream);
+            if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, std::string("feature walk: ") + hipGetErrorString(e));
         }
         if (rc == PT_OK && ctx->frame.object_ids && d.nlocal > 0) {  // outside PTCORE_L_BUDGET_MB, on the first frame that asks
             const std::vector<int32_t> &map = ctx->frame.world_scene;
@@ -2956,7 +2971,7 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
     };
     if (ctx->frame.moments && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_MOMENTS, "moments_kernel");
     if (ctx->frame.adaptive && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_CHECK, "adaptive check");
-    if (ctx->frame.features > 0 && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_FEATURE, "feature_kernel");
+    if (ctx->frame.features > 0 && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_FEATURE, ctx->frame.feature_walk ? "feature_bvh_kernel" : "feature_kernel");
     if (ctx->frame.halves && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_HALVES, "halves_kernel");
     if (ctx->frame.filtered && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_BLOCKS, "filtered block checks (gathers, pair filter, block map)");
     if (ctx->frame.fog_vol) {
@@ -3113,6 +3128,32 @@ int32_t pt_set_features(pt_ctx *ctx, int32_t k) {
     if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_features while a frame is open");
     if (k < 0) return fail(PT_ERR_INVALID, "pt_set_features: k must be >= 0");
     ctx->features_k = k;
+    return PT_OK;
+}
+
+int32_t pt_set_feature_walk(pt_ctx *ctx, int32_t on) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_feature_walk while a frame is open");
+    ctx->feature_walk_on = on != 0;
+    return PT_OK;
+}
+
+int32_t pt_feature_walk_stats(pt_ctx *ctx, uint64_t out[4]) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!out) return fail(PT_ERR_INVALID, "pt_feature_walk_stats: out is null");
+    if (!ctx->frame.feature_walk)
+        return fail(PT_ERR_STATE, "pt_feature_walk_stats: the last frame did not run the walk (pt_set_feature_walk and pt_set_features on a BVH scene)");
+    uint64_t sum[4] = {0, 0, 0, 0};
+    for (Device &d : ctx->devs) {
+        if (d.nlocal == 0 || !d.walk_counters.p) continue;
+        HIP_TRY(hipSetDevice(d.ordinal));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        unsigned long long c[4] = {};
+        HIP_TRY(hipMemcpy(c, d.walk_counters.p, sizeof c, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 3; k++) sum[k] += c[k];
+        sum[3] = std::max<uint64_t>(sum[3], c[3]);  // the deepest stack: the largest of the devices'
+    }
+    for (int k = 0; k < 4; k++) out[k] = sum[k];
     return PT_OK;
 }
 

@@ -66,7 +66,8 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 features: Optional[int] = None, atrous: Optional["hip.AtrousConfig"] = None,
                 filtered_noise: Optional[float] = None, temporal: Optional["hip.TemporalConfig"] = None,
                 temporal_clip: Optional[float] = None, temporal_motion: Optional[bool] = None,
-                filtered_adaptive: Optional[float] = None, pool: Optional[int] = None) -> dict:
+                filtered_adaptive: Optional[float] = None, pool: Optional[int] = None,
+                feature_walk: Optional[bool] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
@@ -90,7 +91,9 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     `filtered_adaptive` and `pool` are hip.render's: with the filter on, an adaptive frame whose 8x8 blocks stop by the
     filtered frame's pooled noise; None takes PATHTRACER_GPU_FILTERED_ADAPTIVE / PATHTRACER_GPU_POOL (hip.filtered_adaptive_from_env),
     off by default and ignored without the filter; beside a noise target or a filtered noise target it is an error, as in the other host
-    layers: one stop rule per frame."""
+    layers: one stop rule per frame.  `feature_walk` is hip.render's: features, and with them the filter's feature terms,
+    the accumulation and the object ids, on scenes that take the bounding-volume hierarchy; None takes PATHTRACER_GPU_FEATURE_WALK=1
+    (hip.feature_walk_from_env), off by default."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -125,13 +128,16 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     if filtered_adaptive is not None:
         rule = dict(filtered_adaptive=filtered_adaptive, pool=1 if pool is None else pool)
         adaptive = False  # (the rule brings its own adaptive frame; PATHTRACER_GPU_ADAPTIVE has no noise target to adapt to here)
+    if feature_walk is None:
+        feature_walk = hip.feature_walk_from_env()
+    walk = dict(feature_walk=True) if feature_walk else {}  # (passed only when on: with it off the call is what it was)
     motion = {}
     if temporal is not None and temporal_motion:
         motion = _motion_for(sc)
     out = hip.render(sc, gcfg, img, progress, shading=model, features=features, atrous=atrous, moments=moments, noise=noise,
                      noise_step=noise_step if noise_step is not None else ncfg.step, adaptive=bool(adaptive) and noise is not None,
                      min_spp=min_spp if min_spp is not None else acfg.min_spp, counts=counts, filtered_noise=filtered_noise,
-                     temporal=temporal, temporal_clip=temporal_clip if temporal is not None else None, **motion, **rule)
+                     temporal=temporal, temporal_clip=temporal_clip if temporal is not None else None, **motion, **rule, **walk)
     if "temporal" in out:
         global _accumulated_scene
         # (the caller edits its scene in place; a frame accumulated without the rule is not what the next table is against)

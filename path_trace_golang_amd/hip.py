@@ -326,6 +326,33 @@ def read_features(ctx: capi.Context, normal: Optional[np.ndarray] = None, albedo
     capi.check(capi.load().pt_read_features(ctx.handle, *p))
 
 
+def set_feature_walk(ctx: capi.Context, on: bool) -> None:
+    """pt_set_feature_walk: later frames on ctx with features on are accepted on the bounding-volume-hierarchy path too, the first
+    hit found by one walk of the tree per 8x8 block and feature sample.  A library without the entry point takes
+    False only."""
+    if not capi.has("pt_set_feature_walk"):
+        if on:
+            raise RuntimeError("this libptcore.so has no pt_set_feature_walk (rebuild it)")
+        return
+    capi.check(capi.load().pt_set_feature_walk(ctx.handle, 1 if on else 0))
+    ctx._feature_walk_on = bool(on)  # what `render` compares with: it says the setting only when it changes
+
+
+def feature_walk_stats(ctx: capi.Context) -> dict:
+    """pt_feature_walk_stats of the last frame: (wave, feature sample) pairs walked by the wave and sent to the plain scan, the
+    walks' node visits, the deepest wave stack."""
+    if not capi.has("pt_feature_walk_stats"):
+        raise RuntimeError("this libptcore.so has no pt_feature_walk_stats (rebuild it)")
+    out = (C.c_uint64 * 4)()
+    capi.check(capi.load().pt_feature_walk_stats(ctx.handle, out))
+    return {"walked": int(out[0]), "plain": int(out[1]), "node_visits": int(out[2]), "deepest_stack": int(out[3])}
+
+
+def feature_walk_from_env(environ=None) -> bool:
+    """PATHTRACER_GPU_FEATURE_WALK=1 (or true / on / yes): features on the bounding-volume-hierarchy path (pt_set_feature_walk)."""
+    return _env_on(environ, "PATHTRACER_GPU_FEATURE_WALK")
+
+
 def set_object_ids(ctx: capi.Context, on: bool) -> None:
     """pt_set_object_ids: later frames on ctx with features on also record, per pixel, the index into the scene's object list of
     the first hit of the pixel's sample 0 (-1: a miss).  A library without the entry point takes False only."""
@@ -664,10 +691,15 @@ def filtered_adaptive_from_env(environ=None):
     return _env_positive(environ, "PATHTRACER_GPU_FILTERED_ADAPTIVE"), 1 if pool is None else pool
 
 
-def scene_allows_features(sc, shading: str = "cpu") -> bool:
+def scene_allows_features(sc, shading: str = "cpu", feature_walk: bool = False) -> bool:
     """Does a frame of this scene accept pt_set_features(k > 0)?  Not with GL shading, and not on the bounding-volume-hierarchy
-    path (more than 128 spheres or 128 boxes, or PTCORE_SCAN=bvh)."""
-    if shading != "cpu" or os.environ.get("PTCORE_SCAN", "") in ("bvh", "verify_bvh"):
+    path (more than 128 spheres or 128 boxes, or PTCORE_SCAN=bvh) unless the context walks the tree for them (feature_walk:
+    pt_set_feature_walk)."""
+    if shading != "cpu":
+        return False
+    if feature_walk:
+        return True
+    if os.environ.get("PTCORE_SCAN", "") in ("bvh", "verify_bvh"):
         return False
     if isinstance(sc, FlatScene):
         types = [sc.objects[i].type for i in range(sc.c.num_objects)]
@@ -728,7 +760,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            features: Optional[int] = None, atrous: Optional["AtrousConfig"] = None,
            filtered_noise: Optional[float] = None, halves: bool = False,
            temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None,
-           object_ids: bool = False, temporal_motion=None, filtered_adaptive: Optional[float] = None, pool: int = 1) -> dict:
+           object_ids: bool = False, temporal_motion=None, filtered_adaptive: Optional[float] = None, pool: int = 1,
+           feature_walk: bool = False) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -781,6 +814,10 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     read_object_ids(ctx, ...) afterwards); it turns features on (k = 4) where nothing else did.  temporal_motion=delta (with
     temporal=; [n, 3], see scene_motion) turns object ids on and passes the objects' displacements since the last accumulated
     frame to pt_temporal (temporal_set_motion); the "temporal" dict gains "objects", "moved" and "moved_reprojected".
+
+    feature_walk=True (DESIGN 3.11a) lets a scene on the bounding-volume-hierarchy path collect features (pt_set_feature_walk;
+    feature_walk_stats(ctx) afterwards says what the walk did): atrous=, temporal= and object_ids= then work there as on the small
+    scenes.  Without it such a scene has features refused, and atrous= alone filters it with k = 0.
 
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
@@ -838,11 +875,13 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     if features is None:
         features = 0
         if atrous is not None:
-            features = atrous.features if atrous.features is not None else (4 if scene_allows_features(sc, shading) else 0)
+            features = atrous.features if atrous.features is not None else (4 if scene_allows_features(sc, shading, feature_walk) else 0)
         if temporal is not None and not features:  # (where the scene refuses features, pt_temporal says so)
             features = 4
         if (object_ids or temporal_motion is not None) and not features:
             features = 4
+    if bool(feature_walk) != getattr(ctx, "_feature_walk_on", False):  # (said only when it changes: with it never on, the calls are what they were)
+        set_feature_walk(ctx, bool(feature_walk))
     set_features(ctx, features)
     want_ids = object_ids or temporal_motion is not None
     if want_ids != getattr(ctx, "_object_ids_on", False):  # (said only when it changes: with it never on, the calls are what they were)
