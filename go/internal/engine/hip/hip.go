@@ -77,6 +77,9 @@ var (
 	walkSet      bool           // false: PATHTRACER_GPU_FEATURE_WALK decides
 	walkWanted   bool
 	walkOn       bool           // pt_set_feature_walk(1) was the last thing said to the context
+	refitSet     bool           // false: PATHTRACER_GPU_BVH_REFIT decides
+	refitWanted  float64
+	refitSaid    float64        // the bound pt_set_bvh_refit was last given (0: never said, or off)
 	accumulated  *scene.Scene   // a copy of the scene of the last frame accumulated with displaced reprojection on (nil: none)
 	lastMotion   TemporalMotion // pt_temporal_motion_stats of the last frame (zero unless it was accumulated with the rule on)
 
@@ -131,6 +134,7 @@ func SetDevices(n int) {
 		ctx = nil
 		idsOn, accumulated = false, nil
 		walkOn = false
+		refitSaid = 0
 	}
 	initErr = nil
 	if n > 0 {
@@ -386,6 +390,30 @@ func SetFeatureWalk(on bool) {
 	mu.Lock()
 	defer mu.Unlock()
 	walkSet, walkWanted = true, on
+}
+
+// SetBvhRefit lets a frame whose scene differs from the previous frame's only in where its objects are keep the hierarchy's topology
+// and recompute its boxes on the devices (pt_set_bvh_refit, DESIGN 3.4c).  maxGrowth >= 1 (or +Inf) bounds how far the refitted tree's
+// quality figure may exceed the built one's before the next frame rebuilds; anything below 1 is off.  Not set:
+// PATHTRACER_GPU_BVH_REFIT decides.  The library detects the refittable edits by itself.
+func SetBvhRefit(maxGrowth float64) {
+	mu.Lock()
+	defer mu.Unlock()
+	if !(maxGrowth >= 1) {
+		maxGrowth = 0
+	}
+	refitSet, refitWanted = true, maxGrowth
+}
+
+// refitRule: the growth bound in force (SetBvhRefit, else the environment); 0: off.
+func refitRule() float64 {
+	if refitSet {
+		return refitWanted
+	}
+	if g, err := strconv.ParseFloat(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_BVH_REFIT")), 64); err == nil && g >= 1 {
+		return g
+	}
+	return 0
 }
 
 // walkRule: whether features on the BVH path are in force (SetFeatureWalk, else the environment).
@@ -934,6 +962,12 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 			return lastError("pt_set_feature_walk")
 		}
 		walkOn = walk
+	}
+	if g := refitRule(); g != refitSaid { // (the same: said only when the bound changes)
+		if rc := C.pt_set_bvh_refit(ctx, C.double(g)); rc != C.PT_OK {
+			return lastError("pt_set_bvh_refit")
+		}
+		refitSaid = g
 	}
 	if rc := C.pt_set_features(ctx, C.int32_t(featuresRule(sc, atrous))); rc != C.PT_OK {
 		return lastError("pt_set_features")

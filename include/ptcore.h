@@ -718,6 +718,54 @@ int32_t pt_temporal_set_motion(pt_ctx *ctx, const double *delta, int32_t num_obj
 int32_t pt_temporal_motion_stats(pt_ctx *ctx, struct pt_temporal_motion_stats *out);
 
 /*
+ * Refit of the bounding-volume hierarchy on the devices (additive to ABI 4).  Off by default: with it off every
+ * call, launch and bit is what it is without these entry points.
+ * A scene on the bounding-volume-hierarchy path (more than 128 spheres or 128 boxes) has its hierarchy built on the host whenever
+ * the scene changed.  With the refit on, a frame whose scene differs from the previous frame's only in where its objects are --
+ * the same materials, the same object count, every object's type and material unchanged, every coordinate below 1e37, the same
+ * scan -- keeps the hierarchy's topology: each device recomputes the boxes of the tree it holds from the moved objects, level by
+ * level from the leaves (one small launch per level of the tree; csrc/pt_bvh_refit.h states the bits).  The boxes hold their objects, so
+ * the frame is the one a full build gives, bit for bit; what degrades is how fast it is traced.  Any other edit, PTCORE_PIPELINE=
+ * walk32 and scenes on the other scans build in full as before.
+ *   pt_set_bvh_refit(ctx, max_growth) : 0 = off (the default); >= 1 or +inf = on; NaN, negative values and values in (0, 1) are
+ *                             PT_ERR_INVALID; PT_ERR_STATE while a frame is open.  The quality figure of a tree is the sum over the
+ *                             main tree's nodes of the half areas dx dy + dy dz + dz dx of their slots' exact boxes, added in a
+ *                             fixed order.  When the tree a frame was rendered with is a refitted one whose figure exceeds
+ *                             max_growth x the figure at the last full build, the next frame -- also one with an unchanged scene --
+ *                             builds in full first: a degraded tree serves one frame at the most.  Recommended: 1.25, the ratio at which
+ *                             one rebuild of a 10^5-object scene repays itself within about 12 frames.
+ *   pt_bvh_refit_stats      : since pt_create; PT_ERR_STATE before the first frame.  cost_now is that of devices[0]'s tree.
+ *   pt_debug_bvh_refit_check: diagnostics only, no GPU needed.  Builds the hierarchy of `before`, refits it to `after` on the
+ *                             host and reports out = {nodes, objects, 0 or the PT_BVH_REASON_* that forbids the refit (the checks
+ *                             then run on a full build of `after`), objects not inside their slot's box, child boxes not inside
+ *                             their parent's, nodes (and object records) whose bytes differ from a fresh encode of the same
+ *                             topology, the figure ratio x 1000, nodes whose topology words changed (must be 0)}.
+ */
+enum {
+    PT_BVH_REASON_NONE = 0,       /* no full build yet / the edit is refittable */
+    PT_BVH_REASON_FIRST = 1,      /* the context's first scene */
+    PT_BVH_REASON_OFF = 2,        /* pt_set_bvh_refit is off */
+    PT_BVH_REASON_CHANGED = 3,    /* materials, object count, an object's type or material changed */
+    PT_BVH_REASON_NOT_BVH = 4,    /* not on the bounding-volume-hierarchy path, another scan asked for, or walk32 */
+    PT_BVH_REASON_GROWTH = 5,     /* the refitted tree's figure exceeded max_growth x the built one's */
+    PT_BVH_REASON_NONFINITE = 6   /* a coordinate of 1e37 or more */
+};
+
+struct pt_bvh_refit_stats {
+    uint64_t builds;              /* full scene preparations */
+    uint64_t refits;              /* preparations served by a refit */
+    int32_t last_action;          /* of the last frame's preparation: 0 = nothing (scene unchanged), 1 = full build, 2 = refit */
+    int32_t last_build_reason;    /* PT_BVH_REASON_* of the last full build */
+    double cost_built;            /* the figure at the last full build (0 unless the refit was on, or a refit has run since) */
+    double cost_now;              /* ... and of the tree the last frame was rendered with */
+    double refit_ms;              /* device time of the last refit on devices[0] */
+};
+
+int32_t pt_set_bvh_refit(pt_ctx *ctx, double max_growth);
+int32_t pt_bvh_refit_stats(pt_ctx *ctx, struct pt_bvh_refit_stats *out);
+int32_t pt_debug_bvh_refit_check(const pt_scene *before, const pt_scene *after, int32_t out[8]);
+
+/*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the
  * environment at pt_create, the trace kernel runs a build that counts, per code
  * section, wave executions, active lanes and shader-clock cycles.  Copies up to n

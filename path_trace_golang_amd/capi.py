@@ -160,6 +160,18 @@ class PtTemporalMotionStats(C.Structure):  # struct pt_temporal_motion_stats: of
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+PT_BVH_REASON_NONE, PT_BVH_REASON_FIRST, PT_BVH_REASON_OFF, PT_BVH_REASON_CHANGED, PT_BVH_REASON_NOT_BVH, PT_BVH_REASON_GROWTH, \
+    PT_BVH_REASON_NONFINITE = range(7)
+
+
+class PtBvhRefitStats(C.Structure):  # struct pt_bvh_refit_stats: what the scene preparations of a context did (pt_set_bvh_refit)
+    _fields_ = [("builds", C.c_uint64), ("refits", C.c_uint64), ("last_action", C.c_int32), ("last_build_reason", C.c_int32),
+                ("cost_built", C.c_double), ("cost_now", C.c_double), ("refit_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PtTemporalStats(C.Structure):  # pt_temporal_stats
     _fields_ = [("temporal_ms", C.c_double), ("launches", C.c_int32), ("iterations", C.c_int32), ("reprojected", C.c_uint64),
                 ("disoccluded", C.c_uint64), ("bad_pixels", C.c_uint64), ("mean_len", C.c_double), ("noise_before", C.c_double),
@@ -242,6 +254,9 @@ SYMBOLS = [
     ("pt_temporal_clip_stats", C.c_int32, [_vp, C.POINTER(PtTemporalClipStats)]),
     ("pt_temporal_set_motion", C.c_int32, [_vp, C.POINTER(C.c_double), C.c_int32]),
     ("pt_temporal_motion_stats", C.c_int32, [_vp, C.POINTER(PtTemporalMotionStats)]),
+    ("pt_set_bvh_refit", C.c_int32, [_vp, C.c_double]),                    # additive to ABI 4 (see has())
+    ("pt_bvh_refit_stats", C.c_int32, [_vp, C.POINTER(PtBvhRefitStats)]),
+    ("pt_debug_bvh_refit_check", C.c_int32, [C.POINTER(PtScene), C.POINTER(PtScene), C.POINTER(C.c_int32)]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
@@ -287,7 +302,8 @@ ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_ray
             "pt_read_features", "pt_atrous", "pt_set_halves", "pt_read_halves", "pt_atrous_halves", "pt_temporal", "pt_temporal_read",
             "pt_temporal_reset", "pt_temporal_set_clip", "pt_temporal_clip_stats", "pt_set_object_ids", "pt_read_object_ids",
             "pt_temporal_set_motion", "pt_temporal_motion_stats", "pt_set_adaptive_filtered", "pt_read_block_figures",
-            "pt_set_feature_walk", "pt_feature_walk_stats")  # added within ABI 4: detected by presence
+            "pt_set_feature_walk", "pt_feature_walk_stats", "pt_set_bvh_refit", "pt_bvh_refit_stats",
+            "pt_debug_bvh_refit_check")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:

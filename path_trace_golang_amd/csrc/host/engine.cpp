@@ -60,7 +60,8 @@ namespace {
     OPTIONAL(pt_adaptive_state) OPTIONAL(pt_set_features) OPTIONAL(pt_atrous) OPTIONAL(pt_set_halves) OPTIONAL(pt_atrous_halves) \
     OPTIONAL(pt_temporal) OPTIONAL(pt_temporal_reset) OPTIONAL(pt_temporal_set_clip) OPTIONAL(pt_temporal_clip_stats)           \
     OPTIONAL(pt_set_object_ids) OPTIONAL(pt_temporal_set_motion) OPTIONAL(pt_temporal_motion_stats)                              \
-    OPTIONAL(pt_set_adaptive_filtered) OPTIONAL(pt_read_block_figures) OPTIONAL(pt_set_feature_walk)
+    OPTIONAL(pt_set_adaptive_filtered) OPTIONAL(pt_read_block_figures) OPTIONAL(pt_set_feature_walk) \
+    OPTIONAL(pt_set_bvh_refit)
 
 struct Core {
     void *handle = nullptr;
@@ -71,7 +72,7 @@ struct Core {
 };
 
 // What a frame setting needs from the library beyond the required entry points, and what Render answers when it is not there.
-enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE, FEATURE_WALK };
+enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE, FEATURE_WALK, BVH_REFIT };
 const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_shading != nullptr; }, "GL shading: libptcore.so lacks pt_set_shading"},
     {[](const Core &c) { return c.pt_set_moments && c.pt_noise_estimate; }, "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate"},
@@ -86,6 +87,7 @@ const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_adaptive_filtered && c.pt_read_block_figures && c.pt_set_adaptive && c.pt_adaptive_state; },
      "filtered adaptive target: libptcore.so lacks pt_set_adaptive_filtered / pt_read_block_figures"},
     {[](const Core &c) { return c.pt_set_feature_walk != nullptr; }, "feature walk: libptcore.so lacks pt_set_feature_walk"},
+    {[](const Core &c) { return c.pt_set_bvh_refit != nullptr; }, "BVH refit: libptcore.so lacks pt_set_bvh_refit"},
 };
 
 // What the Set* calls said; an empty field leaves the matter to the environment (the *FromEnv rules).
@@ -97,7 +99,7 @@ struct Settings {
     std::optional<int> shading, features;
     std::optional<NoiseRule> noise;
     std::optional<Switch> adaptive, atrous;
-    std::optional<double> filtered_noise, temporal_clip;
+    std::optional<double> filtered_noise, temporal_clip, bvh_refit;
     std::optional<BlockRule> filtered_adaptive;
 };
 
@@ -323,6 +325,9 @@ bool TemporalFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL"); }
 double TemporalClipFromEnv() { return env_double("PATHTRACER_GPU_TEMPORAL_CLIP", finite_not_negative, 0); }
 bool TemporalMotionFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL_MOTION"); }
 bool FeatureWalkFromEnv() { return env_switch("PATHTRACER_GPU_FEATURE_WALK"); }
+double BvhRefitFromEnv() {  // PATHTRACER_GPU_BVH_REFIT=<G>: a growth bound of at least 1, or inf; anything else is off
+    return env_double("PATHTRACER_GPU_BVH_REFIT", [](double g) { return g >= 1.0; }, 0);
+}
 
 namespace {
 
@@ -340,6 +345,7 @@ struct FramePlan {
     BlockRule blocks;     // target > 0 only under the filter: an adaptive frame whose blocks stop by the filtered frame's pooled noise
     int features;
     bool walk;            // features on the BVH path too (pt_set_feature_walk)
+    double refit;         // >= 1: the growth bound of pt_set_bvh_refit; 0: off
     bool moments, halves;
 };
 
@@ -381,6 +387,7 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
     if (!p.atrous.on) p.blocks.target = 0;
     p.features = s.features.value_or(FeaturesFromEnv());
     p.walk = s.feature_walk.value_or(FeatureWalkFromEnv());
+    p.refit = s.bvh_refit.value_or(BvhRefitFromEnv());
     if (p.features < 0 && p.temporal) p.features = 4;  // (pt_temporal needs them: where the frame refuses features, pt_begin says so)
     if (p.features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path without the walk), else off
         p.features = 0;
@@ -413,6 +420,7 @@ AccumulatedScene g_accumulated;
 bool g_object_ids_on = false;  // pt_set_object_ids(1) was the last thing said to the context
 bool g_block_rule_on = false;  // pt_set_adaptive_filtered(&f) was the last thing said to the context
 bool g_feature_walk_on = false;  // pt_set_feature_walk(1) was the last thing said to the context
+double g_bvh_refit = 0;          // the bound pt_set_bvh_refit was last given (0: never said, or off)
 
 // Both belong to the context: a new one has object ids off and an empty history.  Called with g_mu held.
 void drop_context() {
@@ -422,6 +430,7 @@ void drop_context() {
     g_object_ids_on = false;
     g_block_rule_on = false;
     g_feature_walk_on = false;
+    g_bvh_refit = 0;
 }
 
 void remember(const scene::Scene &sc, const Flat &flat, AccumulatedScene &a) {
@@ -578,6 +587,14 @@ bool FeatureWalk() {
     std::lock_guard<std::mutex> lk(g_mu);
     return g_set.feature_walk.value_or(FeatureWalkFromEnv());
 }
+void SetBvhRefit(double max_growth) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_set.bvh_refit = max_growth >= 1.0 ? max_growth : 0.0;
+}
+double BvhRefit() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_set.bvh_refit.value_or(BvhRefitFromEnv());
+}
 void SetFeatures(int k) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (k >= 0) g_set.features = k;
@@ -648,6 +665,11 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (p.walk != g_feature_walk_on) {  // (said only when the switch changes: with it never on, the calls are what they were)
         if (failed(PT_CALL(pt_set_feature_walk, g_ctx, p.walk ? 1 : 0))) return err;
         g_feature_walk_on = p.walk;
+    }
+    if (lacks(p.refit > 0, BVH_REFIT)) return missing;
+    if (p.refit != g_bvh_refit) {  // (the same: said only when the bound changes)
+        if (failed(PT_CALL(pt_set_bvh_refit, g_ctx, p.refit))) return err;
+        g_bvh_refit = p.refit;
     }
     if (g_core.pt_set_features && failed(PT_CALL(pt_set_features, g_ctx, p.features))) return err;
     if (p.motion != g_object_ids_on) {  // (said only when the switch changes: with it never on, the calls are what they were)

@@ -147,6 +147,13 @@ bool TemporalMotionFromEnv();  // PATHTRACER_GPU_TEMPORAL_MOTION = 1 / true / on
 void SetFeatureWalk(bool on);
 bool FeatureWalk();
 bool FeatureWalkFromEnv();  // PATHTRACER_GPU_FEATURE_WALK = 1 / true / on / yes
+// Refit of the hierarchy on the devices (pt_set_bvh_refit): a frame whose scene differs from the previous frame's only in
+// where its objects are keeps the tree's topology and recomputes its boxes on the GPU; max_growth >= 1 (or inf) bounds how far the
+// refitted tree's quality figure may exceed the built one's before the next frame rebuilds.  0 (and anything below 1) is off, the
+// default; not said: PATHTRACER_GPU_BVH_REFIT (BvhRefitFromEnv).  The library detects the refittable edits by itself.
+void SetBvhRefit(double max_growth);
+double BvhRefit();
+double BvhRefitFromEnv();  // PATHTRACER_GPU_BVH_REFIT = a number >= 1 or inf, else 0
 void SetFeatures(int k);
 int GetFeatures();     // -1: not said
 int FeaturesFromEnv(); // PATHTRACER_GPU_FEATURES = int >= 0, else -1

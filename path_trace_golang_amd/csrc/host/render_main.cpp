@@ -22,8 +22,10 @@
 // (pt_set_adaptive_filtered; also env PATHTRACER_GPU_FILTERED_ADAPTIVE, PATHTRACER_GPU_POOL); -noise-step and -min-spp
 // apply, and it excludes -noise and -filtered-noise.  -feature-walk lets a scene on the bounding-volume-hierarchy path (more than 128
 // spheres or 128 boxes) collect features, by a wave-shared walk of the tree (pt_set_feature_walk; also env
-// PATHTRACER_GPU_FEATURE_WALK).  These three flags are parsed like the others but are not in the usage text below, which stands as
-// recorded in tests/golden/host_traces.json.
+// PATHTRACER_GPU_FEATURE_WALK).  -bvh-refit G (G >= 1 or inf) lets a frame whose scene differs from the previous frame's only in where
+// its objects are refit the hierarchy on the devices instead of rebuilding it; G bounds how far the tree may degrade before it is
+// rebuilt (pt_set_bvh_refit; also env PATHTRACER_GPU_BVH_REFIT).  These four flags are parsed like the others but are
+// not in the usage text below, which stands as recorded in tests/golden/host_traces.json.
 #include <cerrno>
 #include <chrono>
 #include <climits>
@@ -78,6 +80,7 @@ struct Flags {
     double filtered_adaptive = 0;
     int pool = 1;
     bool feature_walk = false;
+    double bvh_refit = 0;
 };
 
 void usage() {
@@ -148,6 +151,7 @@ int parse(int argc, char **argv, Flags &f) {
         {"atrous-iters", INT, &f.atrous_iters, 0, 6, 5}, {"features", INT, &f.features, 0, 0x7fffffffLL, -1},
         {"noise", NOT_NEGATIVE, &f.noise}, {"filtered-noise", NOT_NEGATIVE, &f.filtered_noise}, {"seed", UINT, &f.seed},
         {"filtered-adaptive", NOT_NEGATIVE, &f.filtered_adaptive}, {"pool", INT, &f.pool, 0, 4, 1},
+        {"bvh-refit", NOT_NEGATIVE, &f.bvh_refit},
     };
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -222,6 +226,7 @@ int render_headless(const Flags &f) {
     engine::hip::SetAtrous(f.atrous, f.atrous_iters);
     engine::hip::SetFeatures(f.features);
     engine::hip::SetFeatureWalk(f.feature_walk);
+    engine::hip::SetBvhRefit(f.bvh_refit);
     engine::hip::SetFilteredNoise(f.filtered_noise);
     engine::hip::SetFilteredAdaptive(f.filtered_adaptive, f.pool);
     if (f.filtered_adaptive > 0 && !f.atrous) logf("filtered-adaptive: no -atrous given, nothing to measure (a plain frame)");
@@ -291,6 +296,7 @@ int main(int argc, char **argv) {
     engine::hip::AtrousFromEnv(f.atrous, f.atrous_iters);
     f.features = engine::hip::FeaturesFromEnv();
     f.feature_walk = engine::hip::FeatureWalkFromEnv();
+    f.bvh_refit = engine::hip::BvhRefitFromEnv();
     f.filtered_noise = engine::hip::FilteredNoiseFromEnv();
     engine::hip::FilteredAdaptiveFromEnv(f.filtered_adaptive, f.pool);
     int rc = parse(argc, argv, f);

@@ -12,6 +12,12 @@
 // the internal children of a node are consecutive (node_base + rank), its object children are
 // consecutive in the object array (obj_base + rank), and the top of the tree is one prefix that
 // the kernel stages in LDS.
+//
+// The bits of a slot's box -- inflate, centre, half extent rounded up, payload byte -- are stated once, in pt_bvh_refit.h, and
+// called from here: a slot's box is a pure function of the objects beneath it, so when a scene's objects only moved the devices
+// recompute the boxes of this topology themselves (pt_set_bvh_refit).  build() keeps the level table for that
+// (Built::level_start), build_scene_trees() makes the two trees a render uses, and refit() is the host restatement of what the
+// device kernels do.
 #pragma once
 
 #include <algorithm>
@@ -20,6 +26,7 @@
 #include <cstring>
 #include <vector>
 
+#include "pt_bvh_refit.h"
 #include "pt_device.h"
 
 namespace ptbvh {
@@ -43,18 +50,10 @@ struct Aabb {
     }
 };
 
-inline Aabb object_bounds(const DevObj &o) {
+inline Aabb object_bounds(const DevObj &o) {  // (the one definition is ptrf::object_box: the device refit computes the same)
+    const ptrf::Box x = ptrf::object_box(o);
     Aabb b;
-    const int kind = o.kind & 0xff;
-    if (kind == KIND_SPHERE) {
-        const double r = std::fabs(o.radius);
-        for (int k = 0; k < 3; k++) { b.lo[k] = o.a[k] - r; b.hi[k] = o.a[k] + r; }
-    } else {
-        for (int k = 0; k < 3; k++) { b.lo[k] = std::min(o.a[k], o.b[k]); b.hi[k] = std::max(o.a[k], o.b[k]); }
-    }
-    for (int k = 0; k < 3; k++) {  // non-finite geometry: unbounded box, always descended into
-        if (!(b.lo[k] == b.lo[k]) || !(b.hi[k] == b.hi[k])) { b.lo[k] = -INFINITY; b.hi[k] = INFINITY; }
-    }
+    for (int k = 0; k < 3; k++) { b.lo[k] = x.lo[k]; b.hi[k] = x.hi[k]; }
     return b;
 }
 
@@ -63,6 +62,7 @@ struct Built {
     std::vector<int32_t> order;      // object slot -> index into the world array
     int depth = 0;                   // levels of wide nodes
     int stack_need = 0;              // most internal-node entries a traversal can have pushed at once
+    std::vector<int32_t> level_start;  // [depth + 1] first node of every level of wide nodes (breadth-first numbering), then nodes.size()
 };
 
 namespace detail {
@@ -251,18 +251,7 @@ inline Built build(const std::vector<DevObj> &world, const std::vector<int32_t> 
                 continue;
             }
             const detail::BinNode &c = bl.bin[(size_t)slot[s]];
-            for (int k = 0; k < 3; k++) {
-                const double lo = c.box.lo[k] - margin, hi = c.box.hi[k] + margin;
-                const float cf = (float)(0.5 * lo + 0.5 * hi);
-                if (lo == lo && hi == hi && std::isfinite(cf)) {
-                    nd.c[k][s] = cf;
-                    nd.h[k][s] = detail::up(std::max((double)cf - lo, hi - (double)cf));  // [c - h, c + h] holds [lo, hi]
-                    if (!(nd.h[k][s] == nd.h[k][s])) nd.h[k][s] = INFINITY;
-                } else {  // absurd or non-finite bounds: the slab constrains nothing
-                    nd.c[k][s] = 0.0f;
-                    nd.h[k][s] = INFINITY;
-                }
-            }
+            for (int k = 0; k < 3; k++) ptrf::encode_axis(c.box.lo[k], c.box.hi[k], margin, nd.c[k][s], nd.h[k][s]);  // inflated, [c - h, c + h] holds it
             if (c.obj >= 0) {
                 ranks |= (uint32_t)no << (2 * s);
                 objm |= 1u << s;
@@ -280,7 +269,9 @@ inline Built build(const std::vector<DevObj> &world, const std::vector<int32_t> 
         nd.meta = ranks | (intm << 8) | (objm << 12) | (boxm << 16);
         out.nodes.push_back(nd);
         out.depth = std::max(out.depth, level[q]);
+        if ((int)out.level_start.size() < level[q]) out.level_start.push_back((int32_t)q);  // (levels are consecutive: breadth-first)
     }
+    out.level_start.push_back((int32_t)out.nodes.size());
     // deepest stack: a node with k internal children leaves at most k-1 entries below the subtree being walked
     std::vector<int32_t> need(out.nodes.size(), 0);
     for (size_t q = out.nodes.size(); q-- > 0;) {
@@ -360,6 +351,152 @@ inline std::vector<BvhNode> build_cores(Built &b, const std::vector<DevObj> &wor
         cores[q] = tw;
     }
     return cores;
+}
+
+// ---------------------------------------------------------------- the two trees of a scene, and their refit
+
+// The hierarchy a scene on the BVH path renders with: the tree of every finite object, then the tree of the dielectric ones,
+// appended in both arrays, with scene_prepare's payload bytes in place.
+struct SceneTrees {
+    std::vector<BvhNode> nodes;
+    std::vector<BvhObj> objs;
+    std::vector<BvhNode> cores;         // walk32 only
+    std::vector<int32_t> level_start;   // first node of every level of the main tree, then of the dielectric tree, then nodes.size()
+    int depth = 0, stack_need = 0;
+    int32_t main_nodes = 0, main_objs = 0;
+    int32_t root = -1, root_exit = -1;
+    double margin = 0.0;
+};
+
+// the inflation of the hierarchy's boxes: 2^-12 of the bound of every finite object's coordinates
+inline double scene_margin(const std::vector<DevObj> &w) {
+    double Bnd = 1.0;
+    for (size_t i = 0; i < w.size(); i++) {
+        if ((w[i].kind & 0xff) == KIND_PLANE) continue;
+        const Aabb bb = object_bounds(w[i]);
+        for (int k = 0; k < 3; k++) Bnd = std::max(Bnd, std::max(std::fabs(bb.lo[k]), std::fabs(bb.hi[k])));
+    }
+    if (!(Bnd < 1e30)) Bnd = INFINITY;
+    return Bnd * (1.0 / 4096.0);
+}
+
+// The walk of scan_bvh reads the first 96 bytes of a node only (six 16-byte requests per lane and visit instead of seven: the
+// CU's address unit, not the caches, is what its visits wait for -- DESIGN 10.3): node_base, obj_base and meta ride in the LOW BYTES
+// of the twelve half extents, which are rounded up to a multiple of 256 ulp first (they only ever had to be upper bounds).
+// The fields themselves stay where they were for everything else that reads a node (host tools, the walk32 form, the refit).
+inline void embed_payload(BvhNode &nd) {
+    const uint32_t payload[3] = {(uint32_t)nd.node_base, (uint32_t)nd.obj_base, nd.meta & 0xffffffu};
+    for (int k = 0; k < 3; k++)
+        for (int sl = 0; sl < 4; sl++) nd.h[k][sl] = ptrf::bits_float(ptrf::h_word(nd.h[k][sl], payload[k] >> (8 * sl)));
+}
+
+// Builds both trees of `w`.  A tree too deep for a per-lane stack of `stack_limit` entries (adversarial spacing) is rebuilt with
+// fewer SAH levels; false when that does not help.
+inline bool build_scene_trees(const std::vector<DevObj> &w, bool with_cores, int stack_limit, SceneTrees &T) {
+    T = SceneTrees();
+    std::vector<int32_t> finite, glass;
+    for (size_t i = 0; i < w.size(); i++)
+        if ((w[i].kind & 0xff) != KIND_PLANE) finite.push_back((int32_t)i);
+    // two hierarchies: every finite object (closest-hit scans) and the dielectric ones only (exit
+    // searches accept nothing else, renderer.go:333, and would otherwise walk the whole line of sight)
+    for (int32_t i : finite)
+        if (w[(size_t)i].kind & 0x100) glass.push_back(i);
+    const double margin = scene_margin(w);
+    T.margin = margin;
+    Built built = build(w, finite, margin);
+    Built builtd = build(w, glass, margin);
+    for (int lv = 16; built.stack_need >= stack_limit && lv >= 0; lv -= 16) built = build(w, finite, margin, lv);
+    for (int lv = 16; builtd.stack_need >= stack_limit && lv >= 0; lv -= 16) builtd = build(w, glass, margin, lv);
+    T.depth = std::max(built.depth, builtd.depth);
+    T.stack_need = std::max(built.stack_need, builtd.stack_need);
+    if (T.stack_need >= stack_limit) return false;
+    // core twins (the FP32 walk of pt_walk32.h): inside-the-object boxes of the main tree's object slots; the dielectric
+    // tree's twins are empty (an exit search takes no FP32 bound)
+    if (with_cores) {
+        T.cores = build_cores(built, w, margin);
+        T.cores.resize(built.nodes.size() + builtd.nodes.size());
+        for (size_t q = built.nodes.size(); q < T.cores.size(); q++) std::memset(&T.cores[q], 0, sizeof(BvhNode));
+    }
+    const int32_t node_off = (int32_t)built.nodes.size(), obj_off = (int32_t)built.order.size();
+    T.main_nodes = node_off;
+    T.main_objs = obj_off;
+    T.nodes = std::move(built.nodes);
+    for (BvhNode nd : builtd.nodes) {  // the dielectric tree follows the main one in both arrays
+        nd.node_base += node_off;
+        nd.obj_base += obj_off;
+        T.nodes.push_back(nd);
+    }
+    for (BvhNode &nd : T.nodes) embed_payload(nd);
+    for (size_t l = 0; l + 1 < built.level_start.size(); l++) T.level_start.push_back(built.level_start[l]);
+    for (size_t l = 0; l + 1 < builtd.level_start.size(); l++) T.level_start.push_back(builtd.level_start[l] + node_off);
+    T.level_start.push_back((int32_t)T.nodes.size());
+    T.objs.resize(built.order.size() + builtd.order.size());
+    for (size_t k = 0; k < T.objs.size(); k++) {
+        const int32_t oi = k < built.order.size() ? built.order[k] : builtd.order[k - built.order.size()];
+        std::memset(&T.objs[k], 0, sizeof(BvhObj));
+        T.objs[k].o = w[(size_t)oi];
+        T.objs[k].index = oi;
+    }
+    T.root_exit = builtd.nodes.empty() ? -1 : node_off;
+    T.root = T.nodes.empty() || built.order.empty() ? -1 : 0;
+    return true;
+}
+
+// The refit, restated on the host (the product runs ptrf::refit_launch): nodes and records of unchanged topology brought to
+// `world` and `margin`, level by level from the last to the first.  node_box [n][6] and node_area [n] receive every node's
+// exact box and a[q].
+inline void refit(std::vector<BvhNode> &nodes, std::vector<BvhObj> &objs, const std::vector<DevObj> &world, double margin,
+                  const std::vector<int32_t> &level_start, std::vector<double> &node_box, std::vector<double> &node_area) {
+    for (BvhObj &bo : objs) bo.o = world[(size_t)bo.index];
+    node_box.assign(nodes.size() * 6, 0.0);
+    node_area.assign(nodes.size(), 0.0);
+    for (size_t l = level_start.size() - 1; l-- > 0;)
+        for (int32_t q = level_start[l]; q < level_start[l + 1]; q++) {
+            BvhNode &nd = nodes[(size_t)q];
+            ptrf::Box bx[4];
+            double area[4];
+            for (int s = 0; s < WIDTH; s++) {
+                bx[s] = ptrf::empty_box();
+                area[s] = 0.0;
+                const int rank = ptrf::slot_rank(nd.meta, s);
+                if (ptrf::slot_object(nd.meta, s)) {
+                    bx[s] = ptrf::object_box(objs[(size_t)(nd.obj_base + rank)].o);
+                } else if (ptrf::slot_internal(nd.meta, s)) {
+                    const double *p = &node_box[6 * (size_t)(nd.node_base + rank)];
+                    for (int k = 0; k < 3; k++) { bx[s].lo[k] = p[k]; bx[s].hi[k] = p[3 + k]; }
+                } else {
+                    continue;
+                }
+                ptrf::encode_slot(nd, s, bx[s], margin);
+                area[s] = ptrf::half_area(bx[s]);
+            }
+            ptrf::grow(bx[0], bx[1]);
+            ptrf::grow(bx[2], bx[3]);
+            ptrf::grow(bx[0], bx[2]);
+            for (int k = 0; k < 3; k++) { node_box[6 * (size_t)q + k] = bx[0].lo[k]; node_box[6 * (size_t)q + 3 + k] = bx[0].hi[k]; }
+            node_area[(size_t)q] = ((area[0] + area[1]) + area[2]) + area[3];
+        }
+}
+
+// Why a scene edit cannot be served by a refit (pt_bvh_refit_stats.last_build_reason; 0: it can).
+enum RefitReason { REFIT_OK = 0, REFIT_FIRST = 1, REFIT_OFF = 2, REFIT_CHANGED = 3, REFIT_NOT_BVH = 4, REFIT_GROWTH = 5, REFIT_NONFINITE = 6 };
+
+// The scene-side conditions of a refit from `before` to `after` (converted worlds and materials): the same materials, the same
+// objects by count, kind (bit 8 included) and material, and every coordinate below 1e37.
+inline int refit_reason(const std::vector<DevObj> &before, const std::vector<DevMat> &mats_before, const std::vector<DevObj> &after,
+                        const std::vector<DevMat> &mats_after) {
+    if (mats_before.size() != mats_after.size() ||
+        (!mats_after.empty() && std::memcmp(mats_before.data(), mats_after.data(), mats_after.size() * sizeof(DevMat)) != 0))
+        return REFIT_CHANGED;
+    if (before.size() != after.size()) return REFIT_CHANGED;
+    for (size_t i = 0; i < after.size(); i++)
+        if (before[i].kind != after[i].kind || before[i].mat != after[i].mat) return REFIT_CHANGED;
+    for (const DevObj &o : after) {
+        bool fin = std::fabs(o.radius) < 1e37;
+        for (int k = 0; k < 3; k++) fin = fin && std::fabs(o.a[k]) < 1e37 && std::fabs(o.b[k]) < 1e37;
+        if (!fin) return REFIT_NONFINITE;
+    }
+    return REFIT_OK;
 }
 
 }  // namespace ptbvh

@@ -133,7 +133,7 @@ struct EventList {
     }
     void swap(EventList &o) { v.swap(o.v); std::swap(n, o.n); }
 };
-enum EventKind { EV_TRACE, EV_RESOLVE, EV_RAYGEN, EV_GLASS, EV_FOG, EV_MOMENTS, EV_CHECK, EV_FEATURE, EV_HALVES, EV_BLOCKS, EV_KINDS };
+enum EventKind { EV_TRACE, EV_RESOLVE, EV_RAYGEN, EV_GLASS, EV_FOG, EV_MOMENTS, EV_CHECK, EV_FEATURE, EV_HALVES, EV_BLOCKS, EV_REFIT, EV_KINDS };
 
 // Storage of one path-state queue (PathQueue, pt_device.h): per entry 10 doubles, the stream state and 4 words -- job, depth, hit
 // object, answer -- or 6 with pixel stats (+ the job's two counters); every plane of `u` is as long as the queue.
@@ -239,6 +239,8 @@ struct Device {
     bool acc_started = false;
     int blocks_per_cu = 0, blocks_per_cu_split = 0, blocks_per_cu_glass = 0, blocks_per_cu_primary = 0;
     uint64_t scene_gen = 0;  // SceneData generation resident on this device (0 = none)
+    uint64_t topo_gen = 0;   // ... and the generation of the hierarchy's topology (pt_set_bvh_refit: a moved world keeps it)
+    DevBuf<double> rf_box, rf_area, rf_part;  // the refit's scratch: exact box and a[q] per node, the figure's block sums
 };
 
 struct Frame {
@@ -308,6 +310,10 @@ struct SceneData {
     std::vector<BvhNode> bvh_nodes;
     std::vector<BvhObj> bvh_objs;
     std::vector<BvhNode> bvh_cores;   // core twins of bvh_nodes (the FP32 walk's certain bounds)
+    std::vector<int32_t> bvh_levels;  // first node of every level of both trees, then the node count (the refit's launch table)
+    uint64_t topo_gen = 0;            // advances with every full build; a refit (pt_set_bvh_refit) advances gen only
+    bool tree_moved = false;          // the world is not the one bvh_nodes / bvh_objs were built from: the devices refit their copies
+    double bvh_margin = 0.0;          // the inflation of the hierarchy's boxes for the current world
     int bvh_depth = 0;
     int bvh_stack_need = 0;
     bool has_glass = false;           // some object is dielectric
@@ -335,6 +341,11 @@ struct pt_ctx {
     int32_t features_k = 0;           // pt_set_features: feature samples per pixel (0 = off)
     DevBuf<double> g_tiles_feat, f_feat_n, f_feat_a, f_feat_d;  // pt_read_features / pt_atrous: one gathered plane, the three row-major frames
     bool feature_walk_on = false;     // pt_set_feature_walk: features on the BVH path, by the wave-shared walk
+    struct Refit {  // pt_set_bvh_refit
+        double max_growth = 0.0;      // 0 = off
+        struct pt_bvh_refit_stats st{};
+        bool figure_pending = false;  // a refit was prepared and no device has run it yet: cost_now is not known
+    } rf;
     bool object_ids_on = false;       // pt_set_object_ids
     DevBuf<uint32_t> f_ids;           // pt_read_object_ids / pt_temporal with a motion table: the row-major plane (the bits of int32, scene indices)
     // The buffers of the post-frame filters, on devices[0]: allocated on the first call, never shrunk.
@@ -915,11 +926,41 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
         if (int32_t rc = upload(d, d.plane_idx, sd.plane_idx)) return rc;
         if (int32_t rc = upload(d, d.bsph_diel, sd.bsph_diel)) return rc;
         if (int32_t rc = upload(d, d.bbox_diel, sd.bbox_diel)) return rc;
-        if (int32_t rc = upload(d, d.bvh_nodes, sd.bvh_nodes)) return rc;
-        if (int32_t rc = upload(d, d.bvh_objs, sd.bvh_objs)) return rc;
-        if (int32_t rc = upload(d, d.bvh_cores, sd.bvh_cores)) return rc;
+        if (d.topo_gen != sd.topo_gen) {  // (a world that only moved, pt_set_bvh_refit, keeps the hierarchy this device holds)
+            if (int32_t rc = upload(d, d.bvh_nodes, sd.bvh_nodes)) return rc;
+            if (int32_t rc = upload(d, d.bvh_objs, sd.bvh_objs)) return rc;
+            if (int32_t rc = upload(d, d.bvh_cores, sd.bvh_cores)) return rc;
+        }
+        // ... and is brought to the moved world here, from the world just uploaded: every device refits its own copy, and the
+        // result depends on the topology and this world only (pt_bvh_refit.h)
+        const bool refit = sd.tree_moved && !sd.bvh_nodes.empty();
+        const int32_t n_nodes = (int32_t)sd.bvh_nodes.size(), cost_nodes = sd.Fs.bvh_main_nodes;
+        if (refit) {
+            HIP_TRY(d.rf_box.reserve(6 * (size_t)n_nodes));
+            HIP_TRY(d.rf_area.reserve((size_t)n_nodes));
+            HIP_TRY(d.rf_part.reserve(std::max<size_t>(1, ptrf::cost_blocks(cost_nodes))));
+            hipError_t e = hipSuccess;
+            if (int32_t rc = timed(d, EV_REFIT, [&] {
+                    e = ptrf::refit_launch(d.stream, d.bvh_nodes.p, d.bvh_objs.p, d.objs.p, (int32_t)sd.bvh_objs.size(), sd.bvh_levels.data(),
+                                           (int)sd.bvh_levels.size() - 1, sd.bvh_margin, d.rf_box.p, d.rf_area.p, cost_nodes, d.rf_part.p);
+                }))
+                return rc;
+            HIP_TRY(e);
+        }
         HIP_TRY(hipStreamSynchronize(d.stream));
         d.scene_gen = sd.gen;
+        d.topo_gen = sd.topo_gen;
+        if (refit && &d == &ctx->devs[0]) {  // the figure of the refitted tree and the time it took, from devices[0]
+            std::vector<double> part(ptrf::cost_blocks(cost_nodes));
+            if (!part.empty()) HIP_TRY(hipMemcpy(part.data(), d.rf_part.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+            double total = 0.0;
+            for (double p : part) total += p;
+            double ms = 0.0;
+            if (int32_t rc = sum_ms(d.ev[EV_REFIT], ms)) return rc;
+            ctx->rf.st.cost_now = total;
+            ctx->rf.st.refit_ms = ms;
+            ctx->rf.figure_pending = false;
+        }
     }
     HIP_TRY(d.queue.reserve(8));
     HIP_TRY(d.counters.reserve(48));
@@ -1604,6 +1645,12 @@ int32_t dev_collect(Device &d, pt_stats *st, int slot) {
 // (Re)builds ctx->sd when the scene or the requested scan strategy changed.
 int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     SceneData &sd = ctx->sd;
+    pt_ctx::Refit &rf = ctx->rf;
+    const bool refit_on = rf.max_growth >= 1.0;
+    rf.st.last_action = 0;
+    // pt_set_bvh_refit: the tree in use is a refitted one that has degraded past the bound (its figure is known since the last
+    // dev_begin): this preparation rebuilds, also for an unchanged scene -- a degraded tree serves one frame at the most
+    const bool outgrown = refit_on && sd.valid && sd.tree_moved && !rf.figure_pending && rf.st.cost_now > rf.max_growth * rf.st.cost_built;
     // fast path for a scene that has not changed since the last frame (progressive previews, benchmark loops): compare the
     // caller's arrays with the copy kept from then; converting a 10^6-object world just to find it unchanged cost 25 ms a frame
     {
@@ -1611,7 +1658,7 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
         const bool raw_same = sd.valid && sd.scan_req == ctx->scan_mode && sd.raw_mats.size() == nm && sd.raw_objs.size() == no &&
                               (nm == 0 || std::memcmp(sd.raw_mats.data(), scene->materials, nm * sizeof(pt_material)) == 0) &&
                               (no == 0 || std::memcmp(sd.raw_objs.data(), scene->objects, no * sizeof(pt_object)) == 0);
-        if (raw_same) return PT_OK;
+        if (raw_same && !outgrown) return PT_OK;
         sd.raw_mats.assign(scene->materials, scene->materials + nm);
         sd.raw_objs.assign(scene->objects, scene->objects + no);
     }
@@ -1622,7 +1669,40 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
                       mats.size() == sd.mats.size() &&
                       (world.empty() || std::memcmp(world.data(), sd.world.data(), world.size() * sizeof(DevObj)) == 0) &&
                       std::memcmp(mats.data(), sd.mats.data(), mats.size() * sizeof(DevMat)) == 0;
-    if (same) return PT_OK;
+    if (same && !outgrown) return PT_OK;
+    // Why this preparation builds in full; REFIT_OK: the objects only moved and the devices refit the tree they hold.
+    int reason = ptbvh::REFIT_OK;
+    if (!sd.valid) reason = ptbvh::REFIT_FIRST;
+    else if (!refit_on) reason = ptbvh::REFIT_OFF;
+    else if (outgrown) reason = ptbvh::REFIT_GROWTH;
+    else if (!(sd.scan == ptk::SCAN_BVH || sd.scan == ptk::SCAN_VERIFY_BVH) || sd.scan_req != ctx->scan_mode || ctx->pipeline == 2)
+        reason = ptbvh::REFIT_NOT_BVH;  // (the walk32 core twins are not refitted)
+    else reason = ptbvh::refit_reason(sd.world, sd.mats, world, mats);
+    if (reason == ptbvh::REFIT_OK) {
+        // Same objects by kind and material, all finite: the scan, the counts, the depth, the stack and the LDS plan stay.  The
+        // broad-phase fields and the margin follow the move; bvh_nodes / bvh_objs stay those of the last full build, the topology
+        // the devices refit from.
+        if (!sd.tree_moved && !(rf.st.cost_built > 0.0)) {  // built while the feature was off: the figure of the tree as built, late
+            std::vector<double> box, area;
+            ptbvh::refit(sd.bvh_nodes, sd.bvh_objs, sd.world, sd.bvh_margin, sd.bvh_levels, box, area);  // (to its own world: no byte changes)
+            rf.st.cost_built = ptrf::cost_of(area.data(), (size_t)sd.Fs.bvh_main_nodes);
+        }
+        sd.world = std::move(world);
+        build_broad(sd.world, sd);
+        sd.bvh_margin = ptbvh::scene_margin(sd.world);
+        sd.tree_moved = true;
+        sd.gen++;
+        rf.figure_pending = true;
+        rf.st.refits++;
+        rf.st.last_action = 2;
+        return PT_OK;
+    }
+    rf.st.builds++;
+    rf.st.last_action = 1;
+    rf.st.last_build_reason = reason;
+    rf.st.cost_built = rf.st.cost_now = 0.0;
+    rf.figure_pending = false;
+    sd.tree_moved = false;
     sd.valid = false;
     sd.world = std::move(world);
     sd.mats = std::move(mats);
@@ -1662,79 +1742,30 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     sd.bvh_nodes.clear();
     sd.bvh_objs.clear();
     sd.bvh_cores.clear();
+    sd.bvh_levels.clear();
     F.bvh_root = F.bvh_root_exit = -1;
     const std::vector<DevObj> &w = sd.world;
     if (big) {
-        std::vector<int32_t> finite;
-        double Bnd = 1.0;
-        for (size_t i = 0; i < w.size(); i++) {
-            const int kind = w[i].kind & 0xff;
-            if (kind == KIND_PLANE) continue;
-            finite.push_back((int32_t)i);
-            const ptbvh::Aabb bb = ptbvh::object_bounds(w[i]);
-            for (int k = 0; k < 3; k++) Bnd = std::max(Bnd, std::max(std::fabs(bb.lo[k]), std::fabs(bb.hi[k])));
+        // Only PTCORE_PIPELINE=walk32 reads the core twins (and the bits 20-23 build_cores sets in the nodes' meta): the default loop
+        // neither builds nor uploads 128 B per node for nothing.
+        ptbvh::SceneTrees T;
+        const bool fits = ptbvh::build_scene_trees(w, ctx->pipeline == 2, PT_BVH_STACK, T);
+        sd.bvh_depth = T.depth;
+        sd.bvh_stack_need = T.stack_need;
+        if (!fits) return fail(PT_ERR_INVALID, "BVH deeper than the traversal stack");
+        if (refit_on) {  // the figure later refits are held against: a refit to the world it was built from changes no byte
+            std::vector<double> box, area;
+            ptbvh::refit(T.nodes, T.objs, w, T.margin, T.level_start, box, area);
+            rf.st.cost_built = rf.st.cost_now = ptrf::cost_of(area.data(), (size_t)T.main_nodes);
         }
-        if (!(Bnd < 1e30)) Bnd = INFINITY;
-        // two hierarchies: every finite object (closest-hit scans) and the dielectric ones only (exit
-        // searches accept nothing else, renderer.go:333, and would otherwise walk the whole line of sight)
-        std::vector<int32_t> glass;
-        for (int32_t i : finite)
-            if (w[(size_t)i].kind & 0x100) glass.push_back(i);
-        const double margin = Bnd * (1.0 / 4096.0);
-        ptbvh::Built built = ptbvh::build(w, finite, margin);
-        ptbvh::Built builtd = ptbvh::build(w, glass, margin);
-        // a tree too deep for the per-lane stack (adversarial spacing) is rebuilt with fewer SAH levels
-        for (int lv = 16; built.stack_need >= PT_BVH_STACK && lv >= 0; lv -= 16) built = ptbvh::build(w, finite, margin, lv);
-        for (int lv = 16; builtd.stack_need >= PT_BVH_STACK && lv >= 0; lv -= 16) builtd = ptbvh::build(w, glass, margin, lv);
-        sd.bvh_depth = std::max(built.depth, builtd.depth);
-        sd.bvh_stack_need = std::max(built.stack_need, builtd.stack_need);
-        if (sd.bvh_stack_need >= PT_BVH_STACK)
-            return fail(PT_ERR_INVALID, "BVH deeper than the traversal stack");
-        // core twins (the FP32 walk of pt_walk32.h): inside-the-object boxes of the main tree's object slots; the dielectric
-        // tree's twins are empty (an exit search takes no FP32 bound)
-        // Only PTCORE_PIPELINE=walk32 reads them (and the bits 20-23 build_cores sets in the nodes' meta): the default loop neither
-        // builds nor uploads 128 B per node for nothing.
-        if (ctx->pipeline == 2) {
-            sd.bvh_cores = ptbvh::build_cores(built, w, margin);
-            sd.bvh_cores.resize(built.nodes.size() + builtd.nodes.size());
-            for (size_t q = built.nodes.size(); q < sd.bvh_cores.size(); q++) {
-                std::memset(&sd.bvh_cores[q], 0, sizeof(BvhNode));
-            }
-        }
-        const int32_t node_off = (int32_t)built.nodes.size(), obj_off = (int32_t)built.order.size();
-        F.bvh_main_nodes = node_off;
-        sd.bvh_nodes = std::move(built.nodes);
-        for (BvhNode nd : builtd.nodes) {  // the dielectric tree follows the main one in both arrays
-            nd.node_base += node_off;
-            nd.obj_base += obj_off;
-            sd.bvh_nodes.push_back(nd);
-        }
-        // The walk of scan_bvh reads the first 96 bytes of a node only (six 16-byte requests per lane and visit instead of seven: the
-        // CU's address unit, not the caches, is what its visits wait for -- DESIGN 10.3): node_base, obj_base and meta ride in the LOW BYTES
-        // of the twelve half extents, which are rounded up to a multiple of 256 ulp first (they only ever had to be upper bounds).
-        // The fields themselves stay where they were for everything else that reads a node (host tools, the walk32 form).
-        for (BvhNode &nd : sd.bvh_nodes) {
-            const uint32_t payload[3] = {(uint32_t)nd.node_base, (uint32_t)nd.obj_base, nd.meta & 0xffffffu};
-            for (int k = 0; k < 3; k++)
-                for (int sl = 0; sl < 4; sl++) {
-                    uint32_t b;
-                    std::memcpy(&b, &nd.h[k][sl], 4);
-                    if ((b & 0x7f800000u) == 0x7f800000u || (b >> 31)) b = 0x7f7fff00u;  // inf (unbounded slab) / NaN: the largest finite float
-                    else b = (b + 0xffu) & ~0xffu;                                          // up to the next multiple of 256 ulp
-                    if (b >= 0x7f800000u) b = 0x7f7fff00u;
-                    b |= (payload[k] >> (8 * sl)) & 0xffu;
-                    std::memcpy(&nd.h[k][sl], &b, 4);
-                }
-        }
-        sd.bvh_objs.resize(built.order.size() + builtd.order.size());
-        for (size_t k = 0; k < sd.bvh_objs.size(); k++) {
-            const int32_t oi = k < built.order.size() ? built.order[k] : builtd.order[k - built.order.size()];
-            std::memset(&sd.bvh_objs[k], 0, sizeof(BvhObj));
-            sd.bvh_objs[k].o = w[(size_t)oi];
-            sd.bvh_objs[k].index = oi;
-        }
-        F.bvh_root_exit = builtd.nodes.empty() ? -1 : node_off;
-        F.bvh_root = sd.bvh_nodes.empty() || built.order.empty() ? -1 : 0;
+        F.bvh_main_nodes = T.main_nodes;
+        sd.bvh_nodes = std::move(T.nodes);
+        sd.bvh_objs = std::move(T.objs);
+        sd.bvh_cores = std::move(T.cores);
+        sd.bvh_levels = std::move(T.level_start);
+        sd.bvh_margin = T.margin;
+        F.bvh_root_exit = T.root_exit;
+        F.bvh_root = T.root;
     }
     F.n_bvh_nodes = (int32_t)sd.bvh_nodes.size();
     F.n_bvh_objs = (int32_t)sd.bvh_objs.size();
@@ -1772,6 +1803,7 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     sd.has_glass = false;
     for (const DevObj &o : sd.world) sd.has_glass = sd.has_glass || (o.kind & 0x100);
     sd.gen++;
+    sd.topo_gen = sd.gen;
     sd.valid = true;
     return PT_OK;
 }
@@ -3154,6 +3186,94 @@ int32_t pt_feature_walk_stats(pt_ctx *ctx, uint64_t out[4]) {
         sum[3] = std::max<uint64_t>(sum[3], c[3]);  // the deepest stack: the largest of the devices'
     }
     for (int k = 0; k < 4; k++) out[k] = sum[k];
+    return PT_OK;
+}
+
+int32_t pt_set_bvh_refit(pt_ctx *ctx, double max_growth) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_bvh_refit while a frame is open");
+    if (!(max_growth == 0.0 || max_growth >= 1.0))  // (NaN compares false)
+        return fail(PT_ERR_INVALID, "pt_set_bvh_refit: max_growth must be 0 (off), at least 1, or +inf");
+    ctx->rf.max_growth = max_growth;
+    return PT_OK;
+}
+
+int32_t pt_bvh_refit_stats(pt_ctx *ctx, struct pt_bvh_refit_stats *out) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!out) return fail(PT_ERR_INVALID, "pt_bvh_refit_stats: out is null");
+    if (ctx->frames_opened == 0) return fail(PT_ERR_STATE, "pt_bvh_refit_stats before the first frame");
+    *out = ctx->rf.st;
+    return PT_OK;
+}
+
+// Host-only: builds the hierarchy of `before` as a render would, refits it to `after` by the host restatement (ptbvh::refit) and
+// checks the result.  Where `after` is not a refittable edit of `before` (out[2] says why) the checks run on a full build of `after`.
+// out = {nodes, objects, 0 or the ptbvh::RefitReason, objects not inside their slot's box, child boxes not inside their parent's,
+// nodes whose bytes differ from a fresh encode of the same topology, the figure ratio x 1000, nodes whose topology words changed}.
+int32_t pt_debug_bvh_refit_check(const pt_scene *before, const pt_scene *after, int32_t out[8]) {
+    if (!before || !after || !out) return fail(PT_ERR_INVALID, "null argument");
+    for (const pt_scene *s : {before, after})
+        if (s->num_materials < 0 || s->num_objects < 0) return fail(PT_ERR_INVALID, "negative scene counts");
+    std::vector<DevObj> w0, w1;
+    std::vector<DevMat> m0, m1;
+    scene_to_world(*before, w0, m0);
+    scene_to_world(*after, w1, m1);
+    const int reason = ptbvh::refit_reason(w0, m0, w1, m1);
+    ptbvh::SceneTrees T;
+    if (!ptbvh::build_scene_trees(reason == ptbvh::REFIT_OK ? w0 : w1, false, PT_BVH_STACK, T))
+        return fail(PT_ERR_INVALID, "BVH deeper than the traversal stack");
+    std::vector<double> box, area;
+    ptbvh::refit(T.nodes, T.objs, reason == ptbvh::REFIT_OK ? w0 : w1, T.margin, T.level_start, box, area);
+    const double cost0 = ptrf::cost_of(area.data(), (size_t)T.main_nodes);
+    const std::vector<BvhNode> built = T.nodes;
+    const double margin = ptbvh::scene_margin(w1);
+    ptbvh::refit(T.nodes, T.objs, w1, margin, T.level_start, box, area);
+    const double cost1 = ptrf::cost_of(area.data(), (size_t)T.main_nodes);
+    int outside = 0, nested = 0, differ = 0, topo = 0;
+    const double held = std::isfinite(margin) ? margin * 0.999 : 0.0;  // (an infinite margin: the slabs constrain nothing)
+    // a fresh encode of the same topology: every node's subtree box gathered top-down from the objects, not level by level
+    std::vector<ptrf::Box> sub(T.nodes.size());
+    for (size_t q = T.nodes.size(); q-- > 0;) {  // (children carry larger numbers than their parents)
+        const BvhNode &nd = T.nodes[q];
+        BvhNode fresh = built[q];
+        ptrf::Box all = ptrf::empty_box();
+        for (int s = 0; s < 4; s++) {
+            const int rank = ptrf::slot_rank(nd.meta, s);
+            ptrf::Box b;
+            if (ptrf::slot_object(nd.meta, s)) b = ptrf::object_box(w1[(size_t)T.objs[(size_t)(nd.obj_base + rank)].index]);
+            else if (ptrf::slot_internal(nd.meta, s)) b = sub[(size_t)(nd.node_base + rank)];
+            else continue;
+            ptrf::grow(all, b);
+            ptrf::encode_slot(fresh, s, b, margin);
+            for (int k = 0; k < 3; k++) {
+                const double slo = bvh_slot_lo(nd, k, s), shi = bvh_slot_hi(nd, k, s);
+                if (ptrf::slot_object(nd.meta, s)) {
+                    if (slo > b.lo[k] - held || shi < b.hi[k] + held) { outside++; break; }
+                } else if (slo > b.lo[k] - held || shi < b.hi[k] + held) {  // the child's content, by the margin
+                    nested++;
+                    break;
+                }
+            }
+        }
+        sub[q] = all;
+        if (std::memcmp(&fresh, &nd, sizeof(BvhNode)) != 0) differ++;
+        if (nd.node_base != built[q].node_base || nd.obj_base != built[q].obj_base || nd.meta != built[q].meta ||
+            std::memcmp(nd.pad, built[q].pad, sizeof nd.pad) != 0)
+            topo++;
+        for (int k = 0; k < 3; k++)
+            for (int s = 0; s < 4; s++)
+                if ((ptrf::float_bits(nd.h[k][s]) ^ ptrf::float_bits(built[q].h[k][s])) & 0xffu) { topo++; k = 3; break; }
+    }
+    for (size_t k = 0; k < T.objs.size(); k++)
+        if (std::memcmp(&T.objs[k].o, &w1[(size_t)T.objs[k].index], sizeof(DevObj)) != 0) differ++;
+    out[0] = (int32_t)T.nodes.size();
+    out[1] = (int32_t)T.objs.size();
+    out[2] = reason;
+    out[3] = outside;
+    out[4] = nested;
+    out[5] = differ;
+    out[6] = cost0 > 0.0 ? (int32_t)std::min(2.0e9, cost1 / cost0 * 1000.0) : 0;
+    out[7] = topo;
     return PT_OK;
 }
 

@@ -67,7 +67,7 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 filtered_noise: Optional[float] = None, temporal: Optional["hip.TemporalConfig"] = None,
                 temporal_clip: Optional[float] = None, temporal_motion: Optional[bool] = None,
                 filtered_adaptive: Optional[float] = None, pool: Optional[int] = None,
-                feature_walk: Optional[bool] = None) -> dict:
+                feature_walk: Optional[bool] = None, bvh_refit: Optional[float] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
@@ -93,7 +93,9 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     off by default and ignored without the filter; beside a noise target or a filtered noise target it is an error, as in the other host
     layers: one stop rule per frame.  `feature_walk` is hip.render's: features, and with them the filter's feature terms,
     the accumulation and the object ids, on scenes that take the bounding-volume hierarchy; None takes PATHTRACER_GPU_FEATURE_WALK=1
-    (hip.feature_walk_from_env), off by default."""
+    (hip.feature_walk_from_env), off by default.  `bvh_refit` is hip.render's: the growth bound under which a frame whose
+    scene differs from the previous frame's only in where its objects are refits the hierarchy on the devices; None takes
+    PATHTRACER_GPU_BVH_REFIT=<G> (hip.bvh_refit_from_env), off by default."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -131,6 +133,10 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     if feature_walk is None:
         feature_walk = hip.feature_walk_from_env()
     walk = dict(feature_walk=True) if feature_walk else {}  # (passed only when on: with it off the call is what it was)
+    if bvh_refit is None:
+        bvh_refit = hip.bvh_refit_from_env()
+    if bvh_refit:  # (the same: hip.render leaves the context's setting alone unless told)
+        walk["bvh_refit"] = float(bvh_refit)
     motion = {}
     if temporal is not None and temporal_motion:
         motion = _motion_for(sc)

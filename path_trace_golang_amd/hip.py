@@ -353,6 +353,51 @@ def feature_walk_from_env(environ=None) -> bool:
     return _env_on(environ, "PATHTRACER_GPU_FEATURE_WALK")
 
 
+def set_bvh_refit(ctx: capi.Context, max_growth: float) -> None:
+    """pt_set_bvh_refit: with max_growth >= 1 (or inf) a later frame on ctx whose scene differs from the previous
+    frame's only in where its objects are keeps the bounding-volume hierarchy's topology and recomputes its boxes on the devices;
+    a refitted tree whose quality figure exceeds max_growth x the built one's is rebuilt before the next frame.  0 turns it off.  A
+    library without the entry point takes 0 only."""
+    if not capi.has("pt_set_bvh_refit"):
+        if max_growth:
+            raise RuntimeError("this libptcore.so has no pt_set_bvh_refit (rebuild it)")
+        return
+    capi.check(capi.load().pt_set_bvh_refit(ctx.handle, float(max_growth)))
+    ctx._bvh_refit = float(max_growth)  # what `render` compares with: it says the setting only when it changes
+
+
+def bvh_refit_stats(ctx: capi.Context) -> dict:
+    """pt_bvh_refit_stats: builds and refits since the context was made, what the last frame's scene preparation did
+    (last_action: 0 nothing, 1 build, 2 refit), why the last full build happened (capi.PT_BVH_REASON_*), the quality figure at the
+    last full build and now, and the device milliseconds of the last refit."""
+    if not capi.has("pt_bvh_refit_stats"):
+        raise RuntimeError("this libptcore.so has no pt_bvh_refit_stats (rebuild it)")
+    st = capi.PtBvhRefitStats()
+    capi.check(capi.load().pt_bvh_refit_stats(ctx.handle, C.byref(st)))
+    return st.as_dict()
+
+
+def bvh_refit_check(before, after) -> dict:
+    """pt_debug_bvh_refit_check (no GPU needed): the hierarchy of scene `before` refitted to `after` on the host, checked."""
+    a = before if isinstance(before, FlatScene) else FlatScene(before)
+    b = after if isinstance(after, FlatScene) else FlatScene(after)
+    out = (C.c_int32 * 8)()
+    capi.check(capi.load().pt_debug_bvh_refit_check(C.byref(a.c), C.byref(b.c), out))
+    keys = ("nodes", "objects", "reason", "objects_outside", "children_outside", "bytes_differ", "cost_ratio_x1000", "topology_changed")
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+def bvh_refit_from_env(environ=None) -> float:
+    """PATHTRACER_GPU_BVH_REFIT=<G>: the growth bound of pt_set_bvh_refit (a number >= 1 or "inf"); unset, empty or 0: off."""
+    v = (os.environ if environ is None else environ).get("PATHTRACER_GPU_BVH_REFIT", "").strip()
+    if not v:
+        return 0.0
+    g = float(v)
+    if not (g == 0.0 or g >= 1.0):
+        raise ValueError("PATHTRACER_GPU_BVH_REFIT must be 0, at least 1 or inf")
+    return g
+
+
 def set_object_ids(ctx: capi.Context, on: bool) -> None:
     """pt_set_object_ids: later frames on ctx with features on also record, per pixel, the index into the scene's object list of
     the first hit of the pixel's sample 0 (-1: a miss).  A library without the entry point takes False only."""
@@ -761,7 +806,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            filtered_noise: Optional[float] = None, halves: bool = False,
            temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None,
            object_ids: bool = False, temporal_motion=None, filtered_adaptive: Optional[float] = None, pool: int = 1,
-           feature_walk: bool = False) -> dict:
+           feature_walk: bool = False, bvh_refit: Optional[float] = None) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -818,6 +863,11 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     feature_walk=True (DESIGN 3.11a) lets a scene on the bounding-volume-hierarchy path collect features (pt_set_feature_walk;
     feature_walk_stats(ctx) afterwards says what the walk did): atrous=, temporal= and object_ids= then work there as on the small
     scenes.  Without it such a scene has features refused, and atrous= alone filters it with k = 0.
+
+    bvh_refit=G (G >= 1 or inf, 0 = off) lets a frame whose scene differs from the context's previous frame only in
+    where its objects are refit the bounding-volume hierarchy on the devices instead of rebuilding it on the host
+    (pt_set_bvh_refit; bvh_refit_stats(ctx) afterwards says what happened).  The frame is the one a rebuild gives, bit for bit.
+    None leaves the context's setting as it is, which is off unless set_bvh_refit was called.
 
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
@@ -882,6 +932,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
             features = 4
     if bool(feature_walk) != getattr(ctx, "_feature_walk_on", False):  # (said only when it changes: with it never on, the calls are what they were)
         set_feature_walk(ctx, bool(feature_walk))
+    if bvh_refit is not None and float(bvh_refit) != getattr(ctx, "_bvh_refit", 0.0):  # (said only when it changes: with it never on, the calls are what they were)
+        set_bvh_refit(ctx, float(bvh_refit))
     set_features(ctx, features)
     want_ids = object_ids or temporal_motion is not None
     if want_ids != getattr(ctx, "_object_ids_on", False):  # (said only when it changes: with it never on, the calls are what they were)
