@@ -721,10 +721,11 @@ int32_t pt_temporal_motion_stats(pt_ctx *ctx, struct pt_temporal_motion_stats *o
  * Refit of the bounding-volume hierarchy on the devices (additive to ABI 4).  Off by default: with it off every
  * call, launch and bit is what it is without these entry points.
  * A scene on the bounding-volume-hierarchy path (more than 128 spheres or 128 boxes) has its hierarchy built on the host whenever
- * the scene changed.  With the refit on, a frame whose scene differs from the previous frame's only in where its objects are --
- * the same materials, the same object count, every object's type and material unchanged, every coordinate below 1e37, the same
- * scan -- keeps the hierarchy's topology: each device recomputes the boxes of the tree it holds from the moved objects, level by
- * level from the leaves (one small launch per level of the tree; csrc/pt_bvh_refit.h states the bits).  The boxes hold their objects, so
+ * the scene changed.  With the refit on, a frame whose scene differs from the previous frame's only in where its objects are and
+ * how large -- positions and sizes of spheres and boxes (a zero or negative radius included), glass objects among them, and the
+ * positions of planes; the same materials, the same object count, every object's type and material unchanged, every coordinate
+ * below 1e37, the same scan -- keeps the hierarchy's topology: each device recomputes the boxes of the tree it holds from the edited
+ * objects, level by level from the leaves (one small launch per level of the tree; csrc/pt_bvh_refit.h states the bits).  The boxes hold their objects, so
  * the frame is the one a full build gives, bit for bit; what degrades is how fast it is traced.  Any other edit, PTCORE_PIPELINE=
  * walk32 and scenes on the other scans build in full as before.
  *   pt_set_bvh_refit(ctx, max_growth) : 0 = off (the default); >= 1 or +inf = on; NaN, negative values and values in (0, 1) are

@@ -14,7 +14,7 @@
 // the kernel stages in LDS.
 //
 // The bits of a slot's box -- inflate, centre, half extent rounded up, payload byte -- are stated once, in pt_bvh_refit.h, and
-// called from here: a slot's box is a pure function of the objects beneath it, so when a scene's objects only moved the devices
+// called from here: a slot's box is a pure function of the objects beneath it, so when only positions and sizes changed the devices
 // recompute the boxes of this topology themselves (pt_set_bvh_refit).  build() keeps the level table for that
 // (Built::level_start), build_scene_trees() makes the two trees a render uses, and refit() is the host restatement of what the
 // device kernels do.

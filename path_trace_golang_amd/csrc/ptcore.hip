@@ -1670,7 +1670,7 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
                       (world.empty() || std::memcmp(world.data(), sd.world.data(), world.size() * sizeof(DevObj)) == 0) &&
                       std::memcmp(mats.data(), sd.mats.data(), mats.size() * sizeof(DevMat)) == 0;
     if (same && !outgrown) return PT_OK;
-    // Why this preparation builds in full; REFIT_OK: the objects only moved and the devices refit the tree they hold.
+    // Why this preparation builds in full; REFIT_OK: only positions and sizes changed and the devices refit the tree they hold.
     int reason = ptbvh::REFIT_OK;
     if (!sd.valid) reason = ptbvh::REFIT_FIRST;
     else if (!refit_on) reason = ptbvh::REFIT_OFF;

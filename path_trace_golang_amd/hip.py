@@ -355,7 +355,8 @@ def feature_walk_from_env(environ=None) -> bool:
 
 def set_bvh_refit(ctx: capi.Context, max_growth: float) -> None:
     """pt_set_bvh_refit: with max_growth >= 1 (or inf) a later frame on ctx whose scene differs from the previous
-    frame's only in where its objects are keeps the bounding-volume hierarchy's topology and recomputes its boxes on the devices;
+    frame's only in where its objects are and how large (planes included; types, materials and the count stay) keeps the
+    bounding-volume hierarchy's topology and recomputes its boxes on the devices;
     a refitted tree whose quality figure exceeds max_growth x the built one's is rebuilt before the next frame.  0 turns it off.  A
     library without the entry point takes 0 only."""
     if not capi.has("pt_set_bvh_refit"):

@@ -1,5 +1,6 @@
-"""Helpers of the BVH refit tests (test_bvh_refit_cpu.py, test_bvh_refit_probe_gpu.py, test_bvh_refit_gpu.py): the
-device worlds and scenes the cases are made from, the moves, tests/bvh_refit_probe.cpp as a ctypes library (the host build of
+"""Helpers of the BVH refit tests (test_bvh_refit_cpu.py, test_bvh_refit_probe_gpu.py, test_bvh_refit_gpu.py,
+test_bvh_refit_edits_gpu.py): the device worlds and scenes the cases are made from, the moves, the edits that are no
+translations (resizes for worlds, edited_scenes for scenes), tests/bvh_refit_probe.cpp as a ctypes library (the host build of
 csrc/pt_bvh_refit.h and of the builder) and tests/bvh_refit_probe.hip (the product's kernels on arrays a test hands in)."""
 from __future__ import annotations
 
@@ -106,6 +107,56 @@ def moves(w: np.ndarray, seed: int = 5):
     yield "one far away: the margin grows", w3
     w4 = shifted(w3, [far], [-2.5 * bound, 0.0, 0.0])
     yield "the far one back: the margin shrinks", w4
+
+
+def with_radius(w: np.ndarray, idx, radius) -> np.ndarray:
+    """A copy of world w with the spheres idx given `radius` ([len(idx)]); radius_sq and inv_radius as the scene conversion forms
+    them (r * r, 1 / r: infinite for a zero radius)."""
+    out = w.copy()
+    idx = np.asarray(idx, np.int64)
+    assert np.all((w["kind"][idx] & 0xff) == KIND_SPHERE)
+    r = np.broadcast_to(np.asarray(radius, np.float64), (len(idx),))
+    out["radius"][idx] = r
+    out["radius_sq"][idx] = r * r
+    with np.errstate(divide="ignore"):
+        out["inv_radius"][idx] = 1.0 / r
+    return out
+
+
+def with_box_scale(w: np.ndarray, idx, factor) -> np.ndarray:
+    """A copy of world w with the boxes idx scaled about their centres by factor ([3], per axis)."""
+    out = w.copy()
+    idx = np.asarray(idx, np.int64)
+    assert np.all((w["kind"][idx] & 0xff) == KIND_BOX)
+    c, half = 0.5 * (w["a"][idx] + w["b"][idx]), 0.5 * (w["b"][idx] - w["a"][idx]) * np.asarray(factor, np.float64)
+    out["a"][idx], out["b"][idx] = c - half, c + half
+    return out
+
+
+RESIZES = ("spheres grown x1.7", "spheres shrunk x0.01", "boxes x2.5 on x, x0.2 on y", "two radii negated", "two radii zero",
+           "dielectrics moved and grown x1.3", "back to the built world")
+DIELECTRIC_MOVE = (0.4, 0.25, -0.3)
+
+
+def resizes(w: np.ndarray):
+    """The edits of a world that are no translations, each made to w itself (RESIZES, in order): every sphere grown, every sphere
+    shrunk, every box stretched on x and flattened on y, two spheres given the negative of their radius, two spheres a zero radius,
+    every dielectric (bit 8 of `kind`: also in the second tree) moved and grown about its centre, then w again.  Yields (name, world).
+    Kinds and materials never change, so ptbvh::refit_reason accepts every step."""
+    sph = np.flatnonzero((w["kind"] & 0xff) == KIND_SPHERE)
+    box = np.flatnonzero((w["kind"] & 0xff) == KIND_BOX)
+    yield RESIZES[0], with_radius(w, sph, w["radius"][sph] * 1.7)
+    yield RESIZES[1], with_radius(w, sph, w["radius"][sph] * 0.01)
+    yield RESIZES[2], with_box_scale(w, box, [2.5, 0.2, 1.0])
+    two, other = sph[:2], sph[-2:]
+    yield RESIZES[3], with_radius(w, two, -w["radius"][two])
+    yield RESIZES[4], with_radius(w, other, [0.0, 0.0])
+    die = np.flatnonzero((w["kind"] & 0x100) != 0)
+    wd = shifted(w, die, DIELECTRIC_MOVE)
+    ds, db = die[(w["kind"][die] & 0xff) == KIND_SPHERE], die[(w["kind"][die] & 0xff) == KIND_BOX]
+    wd = with_box_scale(with_radius(wd, ds, w["radius"][ds] * 1.3), db, [1.3, 1.3, 1.3])
+    yield RESIZES[5], wd
+    yield RESIZES[6], w.copy()
 
 
 # ---------------------------------------------------------------- the host build
@@ -270,6 +321,51 @@ def moved_scene(sc, moves_by_index: dict):
 
 def finite_indices(sc, kinds=("sphere", "box", "sphere_light")):
     return [i for i, o in enumerate(sc.objects) if o.type in kinds and not o.id.startswith("wall-")]
+
+
+EDITS = ("spheres grown", "spheres shrunk", "boxes resized", "radii negated", "radii zero", "plane lowered", "dielectrics moved and grown")
+DIELECTRIC_EDIT = "dielectrics moved and grown"
+
+
+def dielectric_indices(sc):
+    kinds = {m.id: m.type for m in sc.materials}
+    return [i for i in finite_indices(sc) if kinds.get(sc.objects[i].material_id) == "dielectric"]
+
+
+def edited_scenes(sc):
+    """The edits of resizes() on a scene.Scene, each made to sc itself (EDITS, in order), and the ground plane lowered by 0.5: the
+    free spheres (lights among them) grown x1.7; shrunk x0.01; the free boxes x2.5 on x and x0.2 on y; two spheres' radii negated (one of them glass);
+    two spheres' radii zero; the plane; every free dielectric moved by DIELECTRIC_MOVE and grown x1.3.  The room's walls stay.
+    Yields (name, scene)."""
+    sph = finite_indices(sc, ("sphere", "sphere_light"))
+    box = finite_indices(sc, ("box",))
+
+    def scaled(idx, fx, fy=None, fz=None):
+        out = copy.deepcopy(sc)
+        for i in idx:
+            s = out.objects[i].size
+            s.x, s.y, s.z = s.x * fx, s.y * (fx if fy is None else fy), s.z * (fx if fz is None else fz)
+        return out
+
+    yield EDITS[0], scaled(sph, 1.7)
+    yield EDITS[1], scaled(sph, 0.01)
+    yield EDITS[2], scaled(box, 2.5, 0.2, 1.0)
+    die = dielectric_indices(sc)
+    # a negative radius keeps the hits (radius_sq) and turns the outward normal (inv_radius) round: an opaque sphere looks the same,
+    # a glass one swaps its inside and outside -- so the two are the glass sphere and the other sphere that look largest from the camera
+    def apparent(i):
+        p, c = sc.objects[i].position, sc.camera.position
+        return sc.objects[i].size.x / float(np.linalg.norm([p.x - c.x, p.y - c.y, p.z - c.z]))
+
+    yield EDITS[3], scaled([max((i for i in sph if i in die), key=apparent), max((i for i in sph if i not in die), key=apparent)], -1.0)
+    yield EDITS[4], scaled(sph[-2:], 0.0)
+    low = copy.deepcopy(sc)
+    planes = [o for o in low.objects if o.type == "plane"]
+    assert len(planes) == 1
+    planes[0].position.y -= 0.5
+    yield EDITS[5], low
+    grown = moved_scene(scaled(die, 1.3), {i: DIELECTRIC_MOVE for i in die})
+    yield EDITS[6], grown
 
 
 def teleported(sc):

@@ -1,7 +1,8 @@
 """The BVH refit on the host: csrc/pt_bvh_refit.h is the one statement of a slot's bits, called by the builder, by the
 scene preparation's payload step and by the refit.  Here its host build (tests/bvh_refit_probe.cpp) is held to: a refit to the same
 world changes no byte; a refit after a move holds every object, keeps the topology, equals a fresh encode and finds the linear
-scan's winner for 20 000 rays; edits that are no moves are refused with their reason; the quality figure has the shape it states."""
+scan's winner for 20 000 rays; the same after resizes, negative and zero radii and edited dielectrics (T2b), which the rule accepts
+as it accepts moves; edits of kind, material or count are refused with their reason; the quality figure has the shape it states."""
 import math
 import struct
 import subprocess
@@ -160,6 +161,91 @@ def test_t2_the_library_check_on_moved_scenes():
     r = hip.bvh_refit_check(sc, moved)
     assert (r["reason"], r["objects_outside"], r["children_outside"], r["bytes_differ"], r["topology_changed"]) == (0, 0, 0, 0, 0)
     assert 500 < r["cost_ratio_x1000"] < 2000  # a fifth of the objects by a third of a unit: the same tree, a little looser or tighter
+
+
+# ---------------------------------------------------------------- T2b: edits that are no translations, and that the rule accepts
+ZEROS = dict(objects_outside=0, children_outside=0, bytes_differ=0, topology_changed=0, records_differ=0)
+
+
+def test_t2b_the_resizes_are_what_they_say():
+    w = rs.world_of(300, 7)
+    steps = list(rs.resizes(w))
+    assert tuple(name for name, _ in steps) == rs.RESIZES
+    sph, box, die = (w["kind"] & 0xff) == rs.KIND_SPHERE, (w["kind"] & 0xff) == rs.KIND_BOX, (w["kind"] & 0x100) != 0
+    assert sph.sum() > 100 and box.sum() > 50 and die.sum() == 7 and (die & sph).any() and (die & box).any()
+    for name, wm in steps:
+        assert np.array_equal(wm["kind"], w["kind"]) and np.array_equal(wm["mat"], w["mat"]), name  # what refit_reason holds on to
+        r = wm["radius"][sph]
+        with np.errstate(divide="ignore"):
+            assert np.array_equal(wm["radius_sq"][sph], r * r) and np.array_equal(wm["inv_radius"][sph], 1.0 / r), name
+        assert not wm[box]["radius"].any() and np.all(wm["b"][box] >= wm["a"][box]), name
+    by = dict(steps)
+    assert np.allclose(by[rs.RESIZES[0]]["radius"][sph], 1.7 * w["radius"][sph]) and np.array_equal(by[rs.RESIZES[0]][box], w[box])
+    assert np.allclose(by[rs.RESIZES[1]]["radius"][sph], 0.01 * w["radius"][sph])
+    ext, ext0 = by[rs.RESIZES[2]]["b"][box] - by[rs.RESIZES[2]]["a"][box], w["b"][box] - w["a"][box]
+    assert np.allclose(ext, ext0 * [2.5, 0.2, 1.0]) and np.allclose(by[rs.RESIZES[2]]["a"][box] + 0.5 * ext, w["a"][box] + 0.5 * ext0)
+    assert np.count_nonzero(by[rs.RESIZES[3]]["radius"] < 0) == 2 and np.count_nonzero(by[rs.RESIZES[3]] != w) == 2
+    zero = by[rs.RESIZES[4]]
+    assert np.count_nonzero(sph & (zero["radius"] == 0)) == 2 and np.count_nonzero(np.isinf(zero["inv_radius"])) == 2
+    d = by[rs.RESIZES[5]]
+    assert np.array_equal(d[~die], w[~die]) and np.all(d[die] != w[die])
+    assert np.allclose(d["a"][die & sph], w["a"][die & sph] + rs.DIELECTRIC_MOVE) and np.allclose(d["radius"][die & sph], 1.3 * w["radius"][die & sph])
+    assert np.allclose(d["b"][die & box] - d["a"][die & box], 1.3 * (w["b"][die & box] - w["a"][die & box]))
+    assert by[rs.RESIZES[6]].tobytes() == w.tobytes()
+
+
+@pytest.mark.parametrize("n,ndiel", [(17, 1), (300, 7), (3000, 7)])
+def test_t2b_a_refit_after_a_resize_holds_its_objects_and_equals_a_fresh_encode(n, ndiel):
+    w = rs.world_of(n, ndiel)
+    t = rs.Tree(w)
+    assert t.n_objs > t.main_objs  # a second tree, of the dielectrics
+    for name, wm in rs.resizes(w):
+        t.refit(wm)
+        assert t.check(wm) == ZEROS, (name, t.check(wm))
+    assert np.array_equal(t.state()["nodes"], t.built)  # the last step is the built world: the built bytes
+    t.close()
+
+
+@pytest.mark.parametrize("n,ndiel,least", [(17, 1, 2000), (300, 7, 3000), (3000, 7, 3000)])
+def test_t2b_the_tree_finds_the_linear_scans_winner_after_every_resize(n, ndiel, least):
+    """`least`: of 20 000 rays from inside the world's bounds at least this many hit something after every step -- also with every
+    sphere at a hundredth of its size, where the boxes (two objects in five) still stand."""
+    w = rs.world_of(n, ndiel)
+    t = rs.Tree(w)
+    for k, (name, wm) in enumerate(rs.resizes(w)):
+        t.refit(wm)
+        bad, hits = t.rays(wm, 20000, 200 + k)
+        assert bad == 0 and hits > least, (name, bad, hits)
+    t.close()
+
+
+def test_t2b_a_stale_tree_is_caught_after_a_resize():
+    """The checks can fail: the built tree against the world with every sphere grown, without the refit."""
+    w = rs.world_of(300, 7)
+    t = rs.Tree(w)
+    name, wm = next(iter(rs.resizes(w)))
+    c = t.check(wm)
+    assert c["objects_outside"] > 0 and c["bytes_differ"] > 0 and c["records_differ"] > 0
+    assert t.rays(wm, 20000, 9)[0] > 0
+    t.close()
+
+
+def test_t2b_the_library_check_on_every_edited_scene():
+    from path_trace_golang_amd import hip
+
+    sc = _scene(300, 4)
+    edits = list(rs.edited_scenes(sc))
+    assert tuple(name for name, _ in edits) == rs.EDITS and len(rs.dielectric_indices(sc)) >= 10
+    ratios = {}
+    for name, edit in edits:
+        assert [o.type for o in edit.objects] == [o.type for o in sc.objects] and [o.material_id for o in edit.objects] == [o.material_id for o in sc.objects]
+        assert edit.encode() != sc.encode(), name
+        r = hip.bvh_refit_check(sc, edit)
+        assert (r["reason"], r["objects_outside"], r["children_outside"], r["bytes_differ"], r["topology_changed"]) == (0, 0, 0, 0, 0), (name, r)
+        ratios[name] = r["cost_ratio_x1000"]
+    print("figure ratios x1000:", ratios)
+    assert ratios["plane lowered"] == 1000  # the plane is in no tree
+    assert ratios["spheres grown"] > 1000 > ratios["spheres shrunk"] and ratios["radii negated"] == 1000 and ratios["radii zero"] < 1000
 
 
 # ---------------------------------------------------------------- T3

@@ -65,6 +65,30 @@ def test_t5_the_device_refit_equals_the_host_restatement(n, ndiel):
     t.close()
 
 
+def test_t5_the_device_refit_equals_the_host_restatement_after_every_resize():
+    """The edits that are no translations (rs.resizes: radius, radius_sq and inv_radius change in the records the device copies, box
+    extents, negative and zero radii, the dielectrics of the second tree), each from the state the one before left on the device."""
+    w = rs.world_of(300, 7)
+    t = rs.Tree(w)
+    assert t.n_objs == t.main_objs + 7
+    state = t.state()
+    built_objs = state["objs"].copy()
+    figures = []
+    for name, wm in rs.resizes(w):
+        cost = t.refit(wm)
+        host = t.state()
+        state = rs.gpu_refit(state, wm, t.margin, t.main_nodes)
+        _same(state, host, name)
+        assert struct.pack("<d", state["cost"]) == struct.pack("<d", cost), (name, state["cost"], cost)
+        assert t.check(wm) == dict(objects_outside=0, children_outside=0, bytes_differ=0, topology_changed=0, records_differ=0), name
+        changed = (state["objs"].reshape(-1, rs.OBJ_BYTES) != built_objs.reshape(-1, rs.OBJ_BYTES)).any(axis=1)
+        figures.append(cost)
+        print("refit probe, %-34s figure %.6f, %d of %d records changed" % (name, cost, int(changed.sum()), len(changed)))
+    assert np.array_equal(state["nodes"], t.built) and np.array_equal(state["objs"], built_objs)
+    assert figures[0] > figures[-1] > figures[1]  # grown > built > shrunk
+    t.close()
+
+
 def test_t5_a_tree_of_more_than_one_cost_block():
     """20 000 objects: more than 4096 nodes, so the figure adds block sums."""
     w = rs.world_of(20000, 7)
