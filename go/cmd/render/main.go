@@ -45,6 +45,7 @@ func main() {
 	features := flag.Int("features", -1, "first-hit feature samples per pixel (default: 4 with -atrous where the scene allows them, else 0; or PATHTRACER_GPU_FEATURES)")
 	filteredNoise := flag.Float64("filtered-noise", 0, "with -atrous: render until the measured noise of the filtered frame is at or below this target, checking every -noise-step samples, -spp being the cap (0 = off, or PATHTRACER_GPU_FILTERED_NOISE)")
 	bvhRefit := flag.Float64("bvh-refit", 0, "refit the bounding-volume hierarchy on the GPU when a scene's objects only moved; the value (>= 1, or +Inf) bounds how far the tree may degrade before it is rebuilt (or PATHTRACER_GPU_BVH_REFIT)")
+	bvhBuild := flag.String("bvh-build", "host", "who builds the bounding-volume hierarchy when a full build is due: host, or device (the GPU, in Morton order; or PATHTRACER_GPU_BVH_BUILD)")
 	featureWalk := flag.Bool("feature-walk", false, "collect features on scenes beyond 128 spheres or 128 boxes too, by a wave-shared walk of the tree (or PATHTRACER_GPU_FEATURE_WALK)")
 	flag.Parse()
 	log.Printf("flags: scene=%s mode=%s headless=%v out=%s\n", *scenePath, *mode, *headless, *output)
@@ -83,6 +84,14 @@ func main() {
 		flag.Visit(func(f *flag.Flag) { refitGiven = refitGiven || f.Name == "bvh-refit" })
 		if refitGiven { // else the environment decides
 			hip.SetBvhRefit(*bvhRefit)
+		}
+		buildGiven := false
+		flag.Visit(func(f *flag.Flag) { buildGiven = buildGiven || f.Name == "bvh-build" })
+		if buildGiven { // else the environment decides
+			if *bvhBuild != "host" && *bvhBuild != "device" {
+				log.Fatalf("invalid value %q for flag -bvh-build: want host or device", *bvhBuild)
+			}
+			hip.SetBvhBuild(*bvhBuild == "device")
 		}
 		filteredGiven := false
 		flag.Visit(func(f *flag.Flag) { filteredGiven = filteredGiven || f.Name == "filtered-noise" })

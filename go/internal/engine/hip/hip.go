@@ -80,6 +80,9 @@ var (
 	refitSet     bool           // false: PATHTRACER_GPU_BVH_REFIT decides
 	refitWanted  float64
 	refitSaid    float64        // the bound pt_set_bvh_refit was last given (0: never said, or off)
+	buildSet     bool           // false: PATHTRACER_GPU_BVH_BUILD decides
+	buildWanted  bool
+	buildSaid    bool           // pt_set_bvh_build(1) was the last thing said to the context
 	accumulated  *scene.Scene   // a copy of the scene of the last frame accumulated with displaced reprojection on (nil: none)
 	lastMotion   TemporalMotion // pt_temporal_motion_stats of the last frame (zero unless it was accumulated with the rule on)
 
@@ -135,6 +138,7 @@ func SetDevices(n int) {
 		idsOn, accumulated = false, nil
 		walkOn = false
 		refitSaid = 0
+		buildSaid = false
 	}
 	initErr = nil
 	if n > 0 {
@@ -403,6 +407,22 @@ func SetBvhRefit(maxGrowth float64) {
 		maxGrowth = 0
 	}
 	refitSet, refitWanted = true, maxGrowth
+}
+
+// SetBvhBuild chooses who builds the hierarchy when a full build is due (pt_set_bvh_build, DESIGN 3.4d): the host's builder (false,
+// the default) or devices[0], in Morton order (true).  The frame is the same, bit for bit.  Not set: PATHTRACER_GPU_BVH_BUILD decides.
+func SetBvhBuild(device bool) {
+	mu.Lock()
+	defer mu.Unlock()
+	buildSet, buildWanted = true, device
+}
+
+// buildRule: whether the device build is in force (SetBvhBuild, else the environment).
+func buildRule() bool {
+	if buildSet {
+		return buildWanted
+	}
+	return strings.TrimSpace(os.Getenv("PATHTRACER_GPU_BVH_BUILD")) == "device"
 }
 
 // refitRule: the growth bound in force (SetBvhRefit, else the environment); 0: off.
@@ -968,6 +988,16 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 			return lastError("pt_set_bvh_refit")
 		}
 		refitSaid = g
+	}
+	if b := buildRule(); b != buildSaid { // (the same: said only when the mode changes)
+		mode := C.int32_t(0)
+		if b {
+			mode = 1
+		}
+		if rc := C.pt_set_bvh_build(ctx, mode); rc != C.PT_OK {
+			return lastError("pt_set_bvh_build")
+		}
+		buildSaid = b
 	}
 	if rc := C.pt_set_features(ctx, C.int32_t(featuresRule(sc, atrous))); rc != C.PT_OK {
 		return lastError("pt_set_features")

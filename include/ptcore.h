@@ -767,6 +767,59 @@ int32_t pt_bvh_refit_stats(pt_ctx *ctx, struct pt_bvh_refit_stats *out);
 int32_t pt_debug_bvh_refit_check(const pt_scene *before, const pt_scene *after, int32_t out[8]);
 
 /*
+ * Build of the bounding-volume hierarchy on the device (additive to ABI 4).  Off by default: with it off every
+ * call, launch and bit is what it is without these entry points.
+ * Whenever a scene on the bounding-volume-hierarchy path changed in a way a refit cannot serve -- an object added or removed, a
+ * material or a type changed, a context's first frame, a refitted tree that outgrew its bound -- the hierarchy is built on the host,
+ * single-threaded, by a binned surface-area-heuristic builder.  With mode 1 devices[0] builds it instead, in Morton order (keys from
+ * the objects' centroids, a stable radix sort, a binary radix tree, boxes bottom-up, a collapse to 4-wide nodes level by level;
+ * csrc/pt_bvh_build.h states every step once for the host and the device), in the same node format, numbering and payload bytes.
+ * The tree is read back and from there on handled as the host builder's: the other devices receive it, a refit keeps its topology
+ * and is held against its figure.  Its boxes hold their objects, so the frame is the one the host-built tree gives, bit for bit;
+ * what differs is how long the build takes and how fast the tree is traced (DESIGN.md 3.4d has the figures).
+ *   pt_set_bvh_build(ctx, mode): 0 = host (the default), 1 = device; other values PT_ERR_INVALID; PT_ERR_STATE while a frame is open.
+ *                             Takes effect at the next full build.  The host builder still serves, by reason and never as an error:
+ *                             a device-built tree too deep for the traversal stack, PTCORE_PIPELINE=walk32 (its core twins are
+ *                             not built on the device), and scenes on the other scans, which have no tree.
+ *   pt_bvh_build_stats      : since pt_create; PT_ERR_STATE before the first frame.  builder, nodes, depth, stack_need and cost
+ *                             describe the tree of the last full preparation (builder 0: that scene has none).  cost is the refit's
+ *                             figure (pt_set_bvh_refit) of the tree as built; it is computed when the device build or the refit is
+ *                             on and is 0 otherwise.
+ *   pt_debug_bvh_build_check: diagnostics only, no GPU needed.  Runs the host restatement of the device build on `scene` and reports
+ *                             out = {nodes, objects, depth, stack_need, objects not reached exactly once, objects not inside their
+ *                             slot's box, child boxes not inside their parent's, structural faults (children or objects not
+ *                             consecutive, a level table that does not increase, bytes a refit to the same world changes)}.
+ */
+enum { PT_BVH_BUILDER_NONE = 0, PT_BVH_BUILDER_HOST = 1, PT_BVH_BUILDER_DEVICE = 2 };
+enum {
+    PT_BVH_BUILD_FALLBACK_NONE = 0,     /* the selected builder built the tree */
+    PT_BVH_BUILD_FALLBACK_STACK = 1,    /* the device-built tree is too deep for the traversal stack */
+    PT_BVH_BUILD_FALLBACK_WALK32 = 2,   /* PTCORE_PIPELINE=walk32 */
+    PT_BVH_BUILD_FALLBACK_NOT_BVH = 3   /* the scene is not on the bounding-volume-hierarchy path: no tree */
+};
+
+struct pt_bvh_build_stats {
+    uint64_t host_builds;         /* hierarchies built by the host builder */
+    uint64_t device_builds;       /* ... and on devices[0] */
+    int32_t builder;              /* PT_BVH_BUILDER_* of the tree of the last full preparation */
+    int32_t last_fallback;        /* PT_BVH_BUILD_FALLBACK_* of the last full preparation while mode 1 was set */
+    int32_t nodes;                /* both trees */
+    int32_t depth;                /* levels of wide nodes */
+    int32_t stack_need;           /* entries a traversal can have pushed at once */
+    int32_t reserved;
+    double cost;                  /* the figure of the main tree as built */
+    double device_ms;             /* device time of the last device build, first launch to last */
+    double prepare_ms;            /* wall time of the last full scene preparation, from its first line: converting the scene,
+                                     comparing it with the previous one, the build */
+    double upload_ms;             /* of the last device build: host wall time of its allocations and the world's upload */
+    double readback_ms;           /* ... and of reading nodes and records back, from the end of the last launch */
+};
+
+int32_t pt_set_bvh_build(pt_ctx *ctx, int32_t mode);
+int32_t pt_bvh_build_stats(pt_ctx *ctx, struct pt_bvh_build_stats *out);
+int32_t pt_debug_bvh_build_check(const pt_scene *scene, int32_t out[8]);
+
+/*
  * Diagnostics only (not part of the rendering boundary): with PTCORE_PROFILE=1 in the
  * environment at pt_create, the trace kernel runs a build that counts, per code
  * section, wave executions, active lanes and shader-clock cycles.  Copies up to n

@@ -172,6 +172,19 @@ class PtBvhRefitStats(C.Structure):  # struct pt_bvh_refit_stats: what the scene
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+PT_BVH_BUILDER_NONE, PT_BVH_BUILDER_HOST, PT_BVH_BUILDER_DEVICE = range(3)
+PT_BVH_BUILD_FALLBACK_NONE, PT_BVH_BUILD_FALLBACK_STACK, PT_BVH_BUILD_FALLBACK_WALK32, PT_BVH_BUILD_FALLBACK_NOT_BVH = range(4)
+
+
+class PtBvhBuildStats(C.Structure):  # struct pt_bvh_build_stats: who built the hierarchy of a context's scenes (pt_set_bvh_build)
+    _fields_ = [("host_builds", C.c_uint64), ("device_builds", C.c_uint64), ("builder", C.c_int32), ("last_fallback", C.c_int32),
+                ("nodes", C.c_int32), ("depth", C.c_int32), ("stack_need", C.c_int32), ("reserved", C.c_int32), ("cost", C.c_double),
+                ("device_ms", C.c_double), ("prepare_ms", C.c_double), ("upload_ms", C.c_double), ("readback_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class PtTemporalStats(C.Structure):  # pt_temporal_stats
     _fields_ = [("temporal_ms", C.c_double), ("launches", C.c_int32), ("iterations", C.c_int32), ("reprojected", C.c_uint64),
                 ("disoccluded", C.c_uint64), ("bad_pixels", C.c_uint64), ("mean_len", C.c_double), ("noise_before", C.c_double),
@@ -257,6 +270,9 @@ SYMBOLS = [
     ("pt_set_bvh_refit", C.c_int32, [_vp, C.c_double]),                    # additive to ABI 4 (see has())
     ("pt_bvh_refit_stats", C.c_int32, [_vp, C.POINTER(PtBvhRefitStats)]),
     ("pt_debug_bvh_refit_check", C.c_int32, [C.POINTER(PtScene), C.POINTER(PtScene), C.POINTER(C.c_int32)]),
+    ("pt_set_bvh_build", C.c_int32, [_vp, C.c_int32]),                     # additive to ABI 4 (see has())
+    ("pt_bvh_build_stats", C.c_int32, [_vp, C.POINTER(PtBvhBuildStats)]),
+    ("pt_debug_bvh_build_check", C.c_int32, [C.POINTER(PtScene), C.POINTER(C.c_int32)]),
     ("pt_debug_profile", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.c_int32]),
     ("pt_debug_scan_mismatches", C.c_int64, [_vp]),
     ("pt_debug_div_selftest", C.c_int64, [_vp, C.c_int32, C.c_uint64]),
@@ -303,7 +319,8 @@ ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_ray
             "pt_temporal_reset", "pt_temporal_set_clip", "pt_temporal_clip_stats", "pt_set_object_ids", "pt_read_object_ids",
             "pt_temporal_set_motion", "pt_temporal_motion_stats", "pt_set_adaptive_filtered", "pt_read_block_figures",
             "pt_set_feature_walk", "pt_feature_walk_stats", "pt_set_bvh_refit", "pt_bvh_refit_stats",
-            "pt_debug_bvh_refit_check")  # added within ABI 4: detected by presence
+            "pt_debug_bvh_refit_check", "pt_set_bvh_build", "pt_bvh_build_stats",
+            "pt_debug_bvh_build_check")  # added within ABI 4: detected by presence
 
 
 def has(name: str) -> bool:

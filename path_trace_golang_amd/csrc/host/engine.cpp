@@ -61,7 +61,7 @@ namespace {
     OPTIONAL(pt_temporal) OPTIONAL(pt_temporal_reset) OPTIONAL(pt_temporal_set_clip) OPTIONAL(pt_temporal_clip_stats)           \
     OPTIONAL(pt_set_object_ids) OPTIONAL(pt_temporal_set_motion) OPTIONAL(pt_temporal_motion_stats)                              \
     OPTIONAL(pt_set_adaptive_filtered) OPTIONAL(pt_read_block_figures) OPTIONAL(pt_set_feature_walk) \
-    OPTIONAL(pt_set_bvh_refit)
+    OPTIONAL(pt_set_bvh_refit) OPTIONAL(pt_set_bvh_build)
 
 struct Core {
     void *handle = nullptr;
@@ -72,7 +72,7 @@ struct Core {
 };
 
 // What a frame setting needs from the library beyond the required entry points, and what Render answers when it is not there.
-enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE, FEATURE_WALK, BVH_REFIT };
+enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE, FEATURE_WALK, BVH_REFIT, BVH_BUILD };
 const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_shading != nullptr; }, "GL shading: libptcore.so lacks pt_set_shading"},
     {[](const Core &c) { return c.pt_set_moments && c.pt_noise_estimate; }, "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate"},
@@ -88,6 +88,7 @@ const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
      "filtered adaptive target: libptcore.so lacks pt_set_adaptive_filtered / pt_read_block_figures"},
     {[](const Core &c) { return c.pt_set_feature_walk != nullptr; }, "feature walk: libptcore.so lacks pt_set_feature_walk"},
     {[](const Core &c) { return c.pt_set_bvh_refit != nullptr; }, "BVH refit: libptcore.so lacks pt_set_bvh_refit"},
+    {[](const Core &c) { return c.pt_set_bvh_build != nullptr; }, "BVH device build: libptcore.so lacks pt_set_bvh_build"},
 };
 
 // What the Set* calls said; an empty field leaves the matter to the environment (the *FromEnv rules).
@@ -96,7 +97,7 @@ struct Switch { bool on; int n; };  // adaptive + min_spp, a-trous + iterations
 struct BlockRule { double target; int pool; };
 struct Settings {
     std::optional<bool> fog, temporal, temporal_motion, feature_walk;
-    std::optional<int> shading, features;
+    std::optional<int> shading, features, bvh_build;
     std::optional<NoiseRule> noise;
     std::optional<Switch> adaptive, atrous;
     std::optional<double> filtered_noise, temporal_clip, bvh_refit;
@@ -325,6 +326,10 @@ bool TemporalFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL"); }
 double TemporalClipFromEnv() { return env_double("PATHTRACER_GPU_TEMPORAL_CLIP", finite_not_negative, 0); }
 bool TemporalMotionFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL_MOTION"); }
 bool FeatureWalkFromEnv() { return env_switch("PATHTRACER_GPU_FEATURE_WALK"); }
+int BvhBuildFromEnv() {  // PATHTRACER_GPU_BVH_BUILD=host|device: anything else is host
+    const char *e = std::getenv("PATHTRACER_GPU_BVH_BUILD");
+    return e && std::string(e) == "device" ? 1 : 0;
+}
 double BvhRefitFromEnv() {  // PATHTRACER_GPU_BVH_REFIT=<G>: a growth bound of at least 1, or inf; anything else is off
     return env_double("PATHTRACER_GPU_BVH_REFIT", [](double g) { return g >= 1.0; }, 0);
 }
@@ -346,6 +351,7 @@ struct FramePlan {
     int features;
     bool walk;            // features on the BVH path too (pt_set_feature_walk)
     double refit;         // >= 1: the growth bound of pt_set_bvh_refit; 0: off
+    int build;            // the mode of pt_set_bvh_build: 0 host, 1 device
     bool moments, halves;
 };
 
@@ -388,6 +394,7 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
     p.features = s.features.value_or(FeaturesFromEnv());
     p.walk = s.feature_walk.value_or(FeatureWalkFromEnv());
     p.refit = s.bvh_refit.value_or(BvhRefitFromEnv());
+    p.build = s.bvh_build.value_or(BvhBuildFromEnv());
     if (p.features < 0 && p.temporal) p.features = 4;  // (pt_temporal needs them: where the frame refuses features, pt_begin says so)
     if (p.features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path without the walk), else off
         p.features = 0;
@@ -421,6 +428,7 @@ bool g_object_ids_on = false;  // pt_set_object_ids(1) was the last thing said t
 bool g_block_rule_on = false;  // pt_set_adaptive_filtered(&f) was the last thing said to the context
 bool g_feature_walk_on = false;  // pt_set_feature_walk(1) was the last thing said to the context
 double g_bvh_refit = 0;          // the bound pt_set_bvh_refit was last given (0: never said, or off)
+int g_bvh_build = 0;             // the mode pt_set_bvh_build was last given (0: never said, or host)
 
 // Both belong to the context: a new one has object ids off and an empty history.  Called with g_mu held.
 void drop_context() {
@@ -431,6 +439,7 @@ void drop_context() {
     g_block_rule_on = false;
     g_feature_walk_on = false;
     g_bvh_refit = 0;
+    g_bvh_build = 0;
 }
 
 void remember(const scene::Scene &sc, const Flat &flat, AccumulatedScene &a) {
@@ -595,6 +604,14 @@ double BvhRefit() {
     std::lock_guard<std::mutex> lk(g_mu);
     return g_set.bvh_refit.value_or(BvhRefitFromEnv());
 }
+void SetBvhBuild(int mode) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_set.bvh_build = mode == 1 ? 1 : 0;
+}
+int BvhBuild() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_set.bvh_build.value_or(BvhBuildFromEnv());
+}
 void SetFeatures(int k) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (k >= 0) g_set.features = k;
@@ -670,6 +687,11 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (p.refit != g_bvh_refit) {  // (the same: said only when the bound changes)
         if (failed(PT_CALL(pt_set_bvh_refit, g_ctx, p.refit))) return err;
         g_bvh_refit = p.refit;
+    }
+    if (lacks(p.build != 0, BVH_BUILD)) return missing;
+    if (p.build != g_bvh_build) {  // (the same: said only when the mode changes)
+        if (failed(PT_CALL(pt_set_bvh_build, g_ctx, p.build))) return err;
+        g_bvh_build = p.build;
     }
     if (g_core.pt_set_features && failed(PT_CALL(pt_set_features, g_ctx, p.features))) return err;
     if (p.motion != g_object_ids_on) {  // (said only when the switch changes: with it never on, the calls are what they were)

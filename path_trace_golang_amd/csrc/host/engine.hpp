@@ -154,6 +154,12 @@ bool FeatureWalkFromEnv();  // PATHTRACER_GPU_FEATURE_WALK = 1 / true / on / yes
 void SetBvhRefit(double max_growth);
 double BvhRefit();
 double BvhRefitFromEnv();  // PATHTRACER_GPU_BVH_REFIT = a number >= 1 or inf, else 0
+// Build of the hierarchy on the device (pt_set_bvh_build): with mode 1 every full build of a scene's tree -- an object
+// added or removed, a material or a type changed, the first frame, a refitted tree that outgrew its bound -- runs on devices[0] in
+// Morton order instead of on the host.  0 is the host builder, the default; not said: PATHTRACER_GPU_BVH_BUILD (BvhBuildFromEnv).
+void SetBvhBuild(int mode);
+int BvhBuild();
+int BvhBuildFromEnv();  // PATHTRACER_GPU_BVH_BUILD = device: 1, else 0
 void SetFeatures(int k);
 int GetFeatures();     // -1: not said
 int FeaturesFromEnv(); // PATHTRACER_GPU_FEATURES = int >= 0, else -1

@@ -24,7 +24,9 @@
 // spheres or 128 boxes) collect features, by a wave-shared walk of the tree (pt_set_feature_walk; also env
 // PATHTRACER_GPU_FEATURE_WALK).  -bvh-refit G (G >= 1 or inf) lets a frame whose scene differs from the previous frame's only in where
 // its objects are refit the hierarchy on the devices instead of rebuilding it; G bounds how far the tree may degrade before it is
-// rebuilt (pt_set_bvh_refit; also env PATHTRACER_GPU_BVH_REFIT).  These four flags are parsed like the others but are
+// rebuilt (pt_set_bvh_refit; also env PATHTRACER_GPU_BVH_REFIT).  -bvh-build host|device
+// chooses who builds the hierarchy when a full build is due: the host's builder (the default) or devices[0], in Morton order
+// (pt_set_bvh_build; also env PATHTRACER_GPU_BVH_BUILD).  These five flags are parsed like the others but are
 // not in the usage text below, which stands as recorded in tests/golden/host_traces.json.
 #include <cerrno>
 #include <chrono>
@@ -81,6 +83,7 @@ struct Flags {
     int pool = 1;
     bool feature_walk = false;
     double bvh_refit = 0;
+    std::string bvh_build = "host";
 };
 
 void usage() {
@@ -125,7 +128,7 @@ bool parse_bool(const std::string &v, bool &out) {
 
 // One row per flag: its name, how its value is read, and where it goes.  INT rows keep a value inside [lo, hi] and take `fallback`
 // for one outside (the plain sizes take any value, as Go's flag.Int does).
-enum Kind { BOOL, STRING, SHADING, INT, NOT_NEGATIVE, UINT };
+enum Kind { BOOL, STRING, SHADING, BUILDER, INT, NOT_NEGATIVE, UINT };
 struct FlagRow {
     const char *name;
     Kind kind;
@@ -151,7 +154,7 @@ int parse(int argc, char **argv, Flags &f) {
         {"atrous-iters", INT, &f.atrous_iters, 0, 6, 5}, {"features", INT, &f.features, 0, 0x7fffffffLL, -1},
         {"noise", NOT_NEGATIVE, &f.noise}, {"filtered-noise", NOT_NEGATIVE, &f.filtered_noise}, {"seed", UINT, &f.seed},
         {"filtered-adaptive", NOT_NEGATIVE, &f.filtered_adaptive}, {"pool", INT, &f.pool, 0, 4, 1},
-        {"bvh-refit", NOT_NEGATIVE, &f.bvh_refit},
+        {"bvh-refit", NOT_NEGATIVE, &f.bvh_refit}, {"bvh-build", BUILDER, &f.bvh_build},
     };
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -185,6 +188,10 @@ int parse(int argc, char **argv, Flags &f) {
                 break;
             case SHADING:
                 if (val != "cpu" && val != "gl") return bad_flag("invalid value \"%s\" for flag -%s: want cpu or gl\n", val, name);
+                *static_cast<std::string *>(row->dst) = val;
+                break;
+            case BUILDER:
+                if (val != "host" && val != "device") return bad_flag("invalid value \"%s\" for flag -%s: want host or device\n", val, name);
                 *static_cast<std::string *>(row->dst) = val;
                 break;
             case NOT_NEGATIVE: {
@@ -227,6 +234,7 @@ int render_headless(const Flags &f) {
     engine::hip::SetFeatures(f.features);
     engine::hip::SetFeatureWalk(f.feature_walk);
     engine::hip::SetBvhRefit(f.bvh_refit);
+    engine::hip::SetBvhBuild(f.bvh_build == "device" ? 1 : 0);
     engine::hip::SetFilteredNoise(f.filtered_noise);
     engine::hip::SetFilteredAdaptive(f.filtered_adaptive, f.pool);
     if (f.filtered_adaptive > 0 && !f.atrous) logf("filtered-adaptive: no -atrous given, nothing to measure (a plain frame)");
@@ -297,6 +305,7 @@ int main(int argc, char **argv) {
     f.features = engine::hip::FeaturesFromEnv();
     f.feature_walk = engine::hip::FeatureWalkFromEnv();
     f.bvh_refit = engine::hip::BvhRefitFromEnv();
+    f.bvh_build = engine::hip::BvhBuildFromEnv() ? "device" : "host";
     f.filtered_noise = engine::hip::FilteredNoiseFromEnv();
     engine::hip::FilteredAdaptiveFromEnv(f.filtered_adaptive, f.pool);
     int rc = parse(argc, argv, f);

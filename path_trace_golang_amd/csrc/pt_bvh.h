@@ -26,6 +26,7 @@
 #include <cstring>
 #include <vector>
 
+#include "pt_bvh_build.h"
 #include "pt_bvh_refit.h"
 #include "pt_device.h"
 
@@ -182,35 +183,35 @@ struct Builder {
         return me;
     }
 
-    // the (up to WIDTH) binary nodes that become the slots of the wide node made from binary node b
-    int gather(int32_t b, int32_t out[WIDTH]) const {
-        int n = 0;
-        if (bin[(size_t)b].obj >= 0) {  // a tree of one object: the root holds it in slot 0
-            out[n++] = b;
-            return n;
-        }
-        out[n++] = bin[(size_t)b].left;
-        out[n++] = bin[(size_t)b].right;
-        while (n < WIDTH) {
-            int pick = -1;
-            double area = -1;
-            for (int k = 0; k < n; k++) {
-                const BinNode &c = bin[(size_t)out[k]];
-                if (c.obj >= 0) continue;
-                double ar = c.box.area();
-                if (!(ar == ar)) ar = INFINITY;  // unbounded boxes first
-                if (ar > area) { area = ar; pick = k; }
-            }
-            if (pick < 0) break;
-            const BinNode &c = bin[(size_t)out[pick]];
-            out[pick] = c.left;
-            out[n++] = c.right;
-        }
-        return n;
+    // the (up to WIDTH) binary nodes that become the slots of the wide node made from binary node b: the rule is stated once, in
+    // pt_bvh_build.h (ptbb::gather4), for this builder and for the device build
+    bool leaf(int32_t b) const { return bin[(size_t)b].obj >= 0; }
+    int32_t left(int32_t b) const { return bin[(size_t)b].left; }
+    int32_t right(int32_t b) const { return bin[(size_t)b].right; }
+    double area(int32_t b) const { return bin[(size_t)b].box.area(); }
+    int32_t object(int32_t b) const { return bin[(size_t)b].obj; }
+    void box6(int32_t b, double out[6]) const {
+        for (int k = 0; k < 3; k++) { out[k] = bin[(size_t)b].box.lo[k]; out[3 + k] = bin[(size_t)b].box.hi[k]; }
     }
+    int gather(int32_t b, int32_t out[WIDTH]) const { return ptbb::gather4(*this, b, out); }
 };
 
 }  // namespace detail
+
+// deepest stack of the tree whose nodes are [first, last) of `nodes`, its root `first` (children carry larger numbers than their
+// parents): a node with k internal children leaves at most k-1 entries below the subtree being walked
+inline int stack_need_of(const std::vector<BvhNode> &nodes, size_t first, size_t last) {
+    if (last <= first) return 0;
+    std::vector<int32_t> need(last - first, 0);
+    for (size_t q = last; q-- > first;) {
+        const BvhNode &nd = nodes[q];
+        const int k = __builtin_popcount((nd.meta >> 8) & 0xfu);
+        int deepest = 0;
+        for (int c = 0; c < k; c++) deepest = std::max(deepest, need[(size_t)(nd.node_base + c) - first]);
+        need[q - first] = k > 0 ? (k - 1) + deepest : 0;
+    }
+    return need[0];
+}
 
 // `finite` lists the world indices of the spheres and boxes (planes stay outside the tree).
 inline Built build(const std::vector<DevObj> &world, const std::vector<int32_t> &finite, double margin, int sah_levels = 40) {
@@ -232,56 +233,11 @@ inline Built build(const std::vector<DevObj> &world, const std::vector<int32_t> 
     bl.bin.reserve((size_t)2 * n);
     const int32_t root = bl.build(0, n);
 
-    // breadth-first collapse: queue entry = binary node that becomes wide node number q
-    std::vector<int32_t> queue{root};
-    std::vector<int32_t> level{1};
+    // breadth-first collapse into wide nodes: stated once, in pt_bvh_build.h, for this builder and for the device build's restatement
     out.order.reserve((size_t)n);
-    for (size_t q = 0; q < queue.size(); q++) {
-        int32_t slot[WIDTH];
-        const int ns = bl.gather(queue[q], slot);
-        BvhNode nd;
-        std::memset(&nd, 0, sizeof nd);
-        nd.node_base = (int32_t)queue.size();
-        nd.obj_base = (int32_t)out.order.size();
-        uint32_t ranks = 0, intm = 0, objm = 0, boxm = 0;
-        int ni = 0, no = 0;
-        for (int s = 0; s < WIDTH; s++) {
-            if (s >= ns) {  // empty slot: never flagged in the masks; the box is a far-away point
-                for (int k = 0; k < 3; k++) { nd.c[k][s] = 3.0e38f; nd.h[k][s] = 0.0f; }
-                continue;
-            }
-            const detail::BinNode &c = bl.bin[(size_t)slot[s]];
-            for (int k = 0; k < 3; k++) ptrf::encode_axis(c.box.lo[k], c.box.hi[k], margin, nd.c[k][s], nd.h[k][s]);  // inflated, [c - h, c + h] holds it
-            if (c.obj >= 0) {
-                ranks |= (uint32_t)no << (2 * s);
-                objm |= 1u << s;
-                if ((world[(size_t)c.obj].kind & 0xff) == KIND_BOX) boxm |= 1u << s;
-                out.order.push_back(c.obj);
-                no++;
-            } else {
-                ranks |= (uint32_t)ni << (2 * s);
-                intm |= 1u << s;
-                queue.push_back(slot[s]);
-                level.push_back(level[q] + 1);
-                ni++;
-            }
-        }
-        nd.meta = ranks | (intm << 8) | (objm << 12) | (boxm << 16);
-        out.nodes.push_back(nd);
-        out.depth = std::max(out.depth, level[q]);
-        if ((int)out.level_start.size() < level[q]) out.level_start.push_back((int32_t)q);  // (levels are consecutive: breadth-first)
-    }
-    out.level_start.push_back((int32_t)out.nodes.size());
-    // deepest stack: a node with k internal children leaves at most k-1 entries below the subtree being walked
-    std::vector<int32_t> need(out.nodes.size(), 0);
-    for (size_t q = out.nodes.size(); q-- > 0;) {
-        const BvhNode &nd = out.nodes[q];
-        const int k = __builtin_popcount((nd.meta >> 8) & 0xfu);
-        int deepest = 0;
-        for (int c = 0; c < k; c++) deepest = std::max(deepest, need[(size_t)(nd.node_base + c)]);
-        need[q] = k > 0 ? (k - 1) + deepest : 0;
-    }
-    out.stack_need = need[0];
+    ptbb::collapse(bl, root, world.data(), margin, 0, 0, false, out.nodes, out.order, out.level_start);
+    out.depth = (int)out.level_start.size() - 1;
+    out.stack_need = stack_need_of(out.nodes, 0, out.nodes.size());
     return out;
 }
 
@@ -442,6 +398,58 @@ inline bool build_scene_trees(const std::vector<DevObj> &w, bool with_cores, int
     return true;
 }
 
+// The same two trees by the Morton-order build of pt_bvh_build.h, restated on the host (the product runs ptbb::build_tree_launch):
+// what pt_set_bvh_build(ctx, 1) renders with, byte for byte.  There are no core twins (walk32 builds on the host).  False when
+// the tree is too deep for a per-lane stack of `stack_limit` entries: the caller falls back to build_scene_trees.
+using ptbb::build_lbvh;
+inline void scene_object_lists(const std::vector<DevObj> &w, std::vector<int32_t> &finite, std::vector<int32_t> &glass) {
+    finite.clear();
+    glass.clear();
+    for (size_t i = 0; i < w.size(); i++)
+        if ((w[i].kind & 0xff) != KIND_PLANE) finite.push_back((int32_t)i);
+    for (int32_t i : finite)
+        if (w[(size_t)i].kind & 0x100) glass.push_back(i);
+}
+// depth, stack_need, the roots and the counts of T from its nodes, order counts and level tables (both builders' last step)
+inline bool finish_lbvh_trees(SceneTrees &T, int32_t main_nodes, int32_t main_objs, const std::vector<int32_t> &levels_main,
+                              const std::vector<int32_t> &levels_glass, int stack_limit) {
+    T.main_nodes = main_nodes;
+    T.main_objs = main_objs;
+    const int dm = levels_main.empty() ? 0 : (int)levels_main.size() - 1, dg = levels_glass.empty() ? 0 : (int)levels_glass.size() - 1;
+    T.depth = std::max(dm, dg);
+    T.stack_need = std::max(stack_need_of(T.nodes, 0, (size_t)main_nodes), stack_need_of(T.nodes, (size_t)main_nodes, T.nodes.size()));
+    T.level_start.clear();
+    for (size_t l = 0; l + 1 < levels_main.size(); l++) T.level_start.push_back(levels_main[l]);
+    for (size_t l = 0; l + 1 < levels_glass.size(); l++) T.level_start.push_back(levels_glass[l] + main_nodes);
+    T.level_start.push_back((int32_t)T.nodes.size());
+    T.root_exit = (size_t)main_nodes == T.nodes.size() ? -1 : main_nodes;
+    T.root = T.nodes.empty() || main_objs == 0 ? -1 : 0;
+    return T.stack_need < stack_limit;
+}
+inline bool build_scene_trees_lbvh(const std::vector<DevObj> &w, int stack_limit, SceneTrees &T, ptbb::Lbvh *main_out = nullptr,
+                                   ptbb::Lbvh *glass_out = nullptr) {
+    T = SceneTrees();
+    std::vector<int32_t> finite, glass;
+    scene_object_lists(w, finite, glass);
+    T.margin = scene_margin(w);
+    ptbb::Lbvh A, B;
+    build_lbvh(w.data(), finite.data(), (int32_t)finite.size(), T.margin, 0, 0, A);
+    build_lbvh(w.data(), glass.data(), (int32_t)glass.size(), T.margin, (int32_t)A.nodes.size(), (int32_t)A.order.size(), B);
+    T.nodes = A.nodes;
+    T.nodes.insert(T.nodes.end(), B.nodes.begin(), B.nodes.end());
+    T.objs.resize(A.order.size() + B.order.size());
+    for (size_t k = 0; k < T.objs.size(); k++) {
+        const int32_t oi = k < A.order.size() ? A.order[k] : B.order[k - A.order.size()];
+        std::memset(&T.objs[k], 0, sizeof(BvhObj));
+        T.objs[k].o = w[(size_t)oi];
+        T.objs[k].index = oi;
+    }
+    const bool fits = finish_lbvh_trees(T, (int32_t)A.nodes.size(), (int32_t)A.order.size(), A.level_start, B.level_start, stack_limit);
+    if (main_out) *main_out = std::move(A);
+    if (glass_out) *glass_out = std::move(B);
+    return fits;
+}
+
 // The refit, restated on the host (the product runs ptrf::refit_launch): nodes and records of unchanged topology brought to
 // `world` and `margin`, level by level from the last to the first.  node_box [n][6] and node_area [n] receive every node's
 // exact box and a[q].
@@ -476,6 +484,90 @@ inline void refit(std::vector<BvhNode> &nodes, std::vector<BvhObj> &objs, const 
             for (int k = 0; k < 3; k++) { node_box[6 * (size_t)q + k] = bx[0].lo[k]; node_box[6 * (size_t)q + 3 + k] = bx[0].hi[k]; }
             node_area[(size_t)q] = ((area[0] + area[1]) + area[2]) + area[3];
         }
+}
+
+// The invariants of a scene's two trees, whoever built them.  out = {nodes, objects, depth, stack_need, objects not reached exactly
+// once, objects not inside their slot's box, child boxes not inside their parent's, structural faults: children or objects not
+// consecutive in the breadth-first numbering, a level table that does not increase strictly, a slot count above 4 (by the masks),
+// and nodes or records whose bytes a refit to the build's own world changes}.
+inline void check_trees(const SceneTrees &T, const std::vector<DevObj> &w, int32_t out[8]) {
+    int reached = 0, outside = 0, nested = 0, faults = 0;
+    std::vector<int32_t> finite, glass;
+    scene_object_lists(w, finite, glass);
+    const double held = std::isfinite(T.margin) ? T.margin * 0.999 : 0.0;
+    std::vector<ptrf::Box> sub(T.nodes.size());
+    for (size_t q = T.nodes.size(); q-- > 0;) {
+        const BvhNode &nd = T.nodes[q];
+        ptrf::Box all = ptrf::empty_box();
+        if (((nd.meta >> 8) & 0xfu) & ((nd.meta >> 12) & 0xfu)) faults++;
+        for (int s = 0; s < WIDTH; s++) {
+            const int rank = ptrf::slot_rank(nd.meta, s);
+            ptrf::Box b;
+            const bool is_obj = ptrf::slot_object(nd.meta, s);
+            if (is_obj) {
+                const size_t k = (size_t)(nd.obj_base + rank);
+                if (k >= T.objs.size()) { faults++; continue; }
+                b = ptrf::object_box(w[(size_t)T.objs[k].index]);
+            } else if (ptrf::slot_internal(nd.meta, s)) {
+                const size_t c = (size_t)(nd.node_base + rank);
+                if (c <= q || c >= T.nodes.size()) { faults++; continue; }
+                b = sub[c];
+            } else {
+                continue;
+            }
+            ptrf::grow(all, b);
+            for (int k = 0; k < 3; k++)
+                if (bvh_slot_lo(nd, k, s) > b.lo[k] - held || bvh_slot_hi(nd, k, s) < b.hi[k] + held) {
+                    (is_obj ? outside : nested)++;
+                    break;
+                }
+        }
+        sub[q] = all;
+    }
+    // breadth-first numbering, tree by tree: the children of node q follow those of the nodes before it, and so do its objects
+    const size_t first[3] = {0, (size_t)T.main_nodes, T.nodes.size()};
+    const int32_t obj_first[3] = {0, T.main_objs, (int32_t)T.objs.size()};
+    for (int t = 0; t < 2; t++) {
+        int32_t kids = (int32_t)first[t] + 1, objs = obj_first[t];
+        for (size_t q = first[t]; q < first[t + 1]; q++) {
+            const BvhNode &nd = T.nodes[q];
+            if (nd.node_base != kids || nd.obj_base != objs) faults++;
+            kids += __builtin_popcount((nd.meta >> 8) & 0xfu);
+            objs += __builtin_popcount((nd.meta >> 12) & 0xfu);
+        }
+        if (first[t] < first[t + 1] && (kids != (int32_t)first[t + 1] || objs != obj_first[t + 1])) faults++;
+        std::vector<int32_t> seen(w.size(), 0);
+        for (int32_t k = obj_first[t]; k < obj_first[t + 1]; k++) {
+            const int32_t oi = T.objs[(size_t)k].index;
+            if (oi < 0 || (size_t)oi >= w.size()) reached++;
+            else seen[(size_t)oi]++;
+        }
+        for (int32_t oi : t == 0 ? finite : glass)
+            if (seen[(size_t)oi]-- != 1) reached++;
+        for (int32_t c : seen)
+            if (c > 0) reached++;
+    }
+    for (size_t l = 0; l + 1 < T.level_start.size(); l++)
+        if (T.level_start[l] >= T.level_start[l + 1]) faults++;
+    if (!T.nodes.empty() && (T.level_start.empty() || T.level_start.front() != 0 || T.level_start.back() != (int32_t)T.nodes.size())) faults++;
+    if (!T.nodes.empty() && !T.level_start.empty()) {
+        std::vector<BvhNode> nodes = T.nodes;
+        std::vector<BvhObj> objs = T.objs;
+        std::vector<double> box, area;
+        refit(nodes, objs, w, T.margin, T.level_start, box, area);
+        for (size_t q = 0; q < nodes.size(); q++)
+            if (std::memcmp(&nodes[q], &T.nodes[q], sizeof(BvhNode)) != 0) faults++;
+        for (size_t k = 0; k < objs.size(); k++)
+            if (std::memcmp(&objs[k], &T.objs[k], sizeof(BvhObj)) != 0) faults++;
+    }
+    out[0] = (int32_t)T.nodes.size();
+    out[1] = (int32_t)T.objs.size();
+    out[2] = T.depth;
+    out[3] = T.stack_need;
+    out[4] = reached;
+    out[5] = outside;
+    out[6] = nested;
+    out[7] = faults;
 }
 
 // Why a scene edit cannot be served by a refit (pt_bvh_refit_stats.last_build_reason; 0: it can).

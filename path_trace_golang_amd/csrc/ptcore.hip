@@ -346,7 +346,11 @@ struct pt_ctx {
         struct pt_bvh_refit_stats st{};
         bool figure_pending = false;  // a refit was prepared and no device has run it yet: cost_now is not known
     } rf;
-    bool object_ids_on = false;       // pt_set_object_ids
+    struct Build {  // pt_set_bvh_build
+        int32_t mode = 0;             // 0 = the host builder, 1 = the device build
+        struct pt_bvh_build_stats st{};
+    } bb;
+    bool object_ids_on = false;      // pt_set_object_ids
     DevBuf<uint32_t> f_ids;           // pt_read_object_ids / pt_temporal with a motion table: the row-major plane (the bits of int32, scene indices)
     // The buffers of the post-frame filters, on devices[0]: allocated on the first call, never shrunk.
     struct Atrous {  // pt_atrous, pt_temporal: colour and variance ping-pong, the guide records, the noise partials
@@ -1642,10 +1646,79 @@ int32_t dev_collect(Device &d, pt_stats *st, int slot) {
     return PT_OK;
 }
 
+// pt_set_bvh_build(ctx, 1): both trees of world `w` built on devices[0] by the launch sequence of pt_bvh_build.h, on a stream of
+// their own, and read back into T (nodes with their payload bytes, records, level table; depth and stack_need from the nodes, on
+// the host).  ms = {the device time between the first and the last launch; the host's wall time of the allocations and the world's
+// upload in front of it; of the readback behind it, from the last launch's end}.  The world is uploaded for the build alone:
+// dev_begin uploads what it always did afterwards.
+struct DeviceBuildHold {
+    hipStream_t stream = nullptr;
+    hipEvent_t a = nullptr, b = nullptr;
+    void *world = nullptr, *nodes = nullptr, *order = nullptr, *objs = nullptr;
+    ~DeviceBuildHold() {
+        for (void *p : {world, nodes, order, objs})
+            if (p) (void)hipFree(p);
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+int32_t device_build_trees(pt_ctx *ctx, const std::vector<DevObj> &w, ptbvh::SceneTrees &T, double ms[3]) {
+    T = ptbvh::SceneTrees();
+    ms[0] = ms[1] = ms[2] = 0.0;
+    const auto wall = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    std::vector<int32_t> finite, glass;
+    ptbvh::scene_object_lists(w, finite, glass);
+    T.margin = ptbvh::scene_margin(w);
+    const int32_t nf = (int32_t)finite.size(), ng = (int32_t)glass.size();
+    if (nf == 0) return PT_OK;
+    HIP_TRY(hipSetDevice(ctx->devs[0].ordinal));
+    const auto t_up = std::chrono::steady_clock::now();
+    DeviceBuildHold H;
+    HIP_TRY(hipStreamCreate(&H.stream));
+    HIP_TRY(hipEventCreate(&H.a));
+    HIP_TRY(hipEventCreate(&H.b));
+    const size_t room = (size_t)nf + (size_t)ng;  // (a tree of n objects has at most n nodes)
+    HIP_TRY(hipMalloc(&H.world, w.size() * sizeof(DevObj)));
+    HIP_TRY(hipMalloc(&H.nodes, room * sizeof(BvhNode)));
+    HIP_TRY(hipMalloc(&H.order, room * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&H.objs, room * sizeof(BvhObj)));
+    HIP_TRY(hipMemcpyAsync(H.world, w.data(), w.size() * sizeof(DevObj), hipMemcpyHostToDevice, H.stream));
+    HIP_TRY(hipStreamSynchronize(H.stream));
+    ms[1] = wall(t_up);
+    HIP_TRY(hipEventRecord(H.a, H.stream));
+    std::vector<int32_t> levels_main, levels_glass;
+    ptbb::Scratch S;
+    BvhNode *nodes = static_cast<BvhNode *>(H.nodes);
+    int32_t *order = static_cast<int32_t *>(H.order);
+    const DevObj *objs = static_cast<const DevObj *>(H.world);
+    HIP_TRY(ptbb::build_tree_launch(H.stream, S, objs, finite.data(), nf, T.margin, nodes, order, 0, 0, levels_main));
+    const int32_t main_nodes = levels_main.empty() ? 0 : levels_main.back();
+    HIP_TRY(ptbb::build_tree_launch(H.stream, S, objs, glass.data(), ng, T.margin, nodes, order, main_nodes, nf, levels_glass));
+    const int32_t n_nodes = main_nodes + (levels_glass.empty() ? 0 : levels_glass.back());
+    ptbb::objs_launch(H.stream, static_cast<BvhObj *>(H.objs), order, objs, nf + ng);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(H.b, H.stream));
+    HIP_TRY(hipStreamSynchronize(H.stream));
+    const auto t_back = std::chrono::steady_clock::now();
+    T.nodes.resize((size_t)n_nodes);
+    T.objs.resize(room);
+    HIP_TRY(hipMemcpyAsync(T.nodes.data(), H.nodes, T.nodes.size() * sizeof(BvhNode), hipMemcpyDeviceToHost, H.stream));
+    HIP_TRY(hipMemcpyAsync(T.objs.data(), H.objs, T.objs.size() * sizeof(BvhObj), hipMemcpyDeviceToHost, H.stream));
+    HIP_TRY(hipStreamSynchronize(H.stream));
+    ms[2] = wall(t_back);
+    float fms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&fms, H.a, H.b));
+    ms[0] = fms;
+    (void)ptbvh::finish_lbvh_trees(T, main_nodes, nf, levels_main, levels_glass, PT_BVH_STACK);
+    return PT_OK;
+}
+
 // (Re)builds ctx->sd when the scene or the requested scan strategy changed.
 int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     SceneData &sd = ctx->sd;
     pt_ctx::Refit &rf = ctx->rf;
+    const auto prepare_t0 = std::chrono::steady_clock::now();  // (pt_bvh_build_stats.prepare_ms: the conversion and the comparisons count)
     const bool refit_on = rf.max_growth >= 1.0;
     rf.st.last_action = 0;
     // pt_set_bvh_refit: the tree in use is a refitted one that has degraded past the bound (its figure is known since the last
@@ -1702,6 +1775,11 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     rf.st.last_build_reason = reason;
     rf.st.cost_built = rf.st.cost_now = 0.0;
     rf.figure_pending = false;
+    pt_ctx::Build &bb = ctx->bb;
+    bb.st.builder = PT_BVH_BUILDER_NONE;
+    bb.st.last_fallback = PT_BVH_BUILD_FALLBACK_NONE;
+    bb.st.nodes = bb.st.depth = bb.st.stack_need = 0;
+    bb.st.cost = 0.0;
     sd.tree_moved = false;
     sd.valid = false;
     sd.world = std::move(world);
@@ -1749,14 +1827,42 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
         // Only PTCORE_PIPELINE=walk32 reads the core twins (and the bits 20-23 build_cores sets in the nodes' meta): the default loop
         // neither builds nor uploads 128 B per node for nothing.
         ptbvh::SceneTrees T;
-        const bool fits = ptbvh::build_scene_trees(w, ctx->pipeline == 2, PT_BVH_STACK, T);
+        // pt_set_bvh_build(ctx, 1): the Morton-order build on devices[0] (pt_bvh_build.h), read back; everything below and every
+        // device take it as they take the host builder's.  A tree too deep for the stack and walk32 (no core twins) build on the host.
+        bool on_device = false;
+        if (bb.mode == 1) {
+            if (ctx->pipeline == 2) {
+                bb.st.last_fallback = PT_BVH_BUILD_FALLBACK_WALK32;
+            } else {
+                double ms[3];
+                if (int32_t rc = device_build_trees(ctx, w, T, ms)) return rc;
+                bb.st.device_ms = ms[0];
+                bb.st.upload_ms = ms[1];
+                bb.st.readback_ms = ms[2];
+                on_device = T.stack_need < PT_BVH_STACK;
+                if (!on_device) bb.st.last_fallback = PT_BVH_BUILD_FALLBACK_STACK;
+            }
+        }
+        if (!on_device) {
+            if (!ptbvh::build_scene_trees(w, ctx->pipeline == 2, PT_BVH_STACK, T)) {
+                sd.bvh_depth = T.depth;
+                sd.bvh_stack_need = T.stack_need;
+                return fail(PT_ERR_INVALID, "BVH deeper than the traversal stack");
+            }
+        }
         sd.bvh_depth = T.depth;
         sd.bvh_stack_need = T.stack_need;
-        if (!fits) return fail(PT_ERR_INVALID, "BVH deeper than the traversal stack");
-        if (refit_on) {  // the figure later refits are held against: a refit to the world it was built from changes no byte
+        if (on_device) bb.st.device_builds++;
+        else bb.st.host_builds++;
+        bb.st.builder = on_device ? PT_BVH_BUILDER_DEVICE : PT_BVH_BUILDER_HOST;
+        bb.st.nodes = (int32_t)T.nodes.size();
+        bb.st.depth = T.depth;
+        bb.st.stack_need = T.stack_need;
+        if (refit_on || bb.mode == 1) {  // the figure later refits are held against: a refit to the world it was built from changes no byte
             std::vector<double> box, area;
             ptbvh::refit(T.nodes, T.objs, w, T.margin, T.level_start, box, area);
-            rf.st.cost_built = rf.st.cost_now = ptrf::cost_of(area.data(), (size_t)T.main_nodes);
+            bb.st.cost = ptrf::cost_of(area.data(), (size_t)T.main_nodes);
+            if (refit_on) rf.st.cost_built = rf.st.cost_now = bb.st.cost;
         }
         F.bvh_main_nodes = T.main_nodes;
         sd.bvh_nodes = std::move(T.nodes);
@@ -1766,6 +1872,8 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
         sd.bvh_margin = T.margin;
         F.bvh_root_exit = T.root_exit;
         F.bvh_root = T.root;
+    } else if (bb.mode == 1) {
+        bb.st.last_fallback = PT_BVH_BUILD_FALLBACK_NOT_BVH;  // (no tree at all)
     }
     F.n_bvh_nodes = (int32_t)sd.bvh_nodes.size();
     F.n_bvh_objs = (int32_t)sd.bvh_objs.size();
@@ -1805,6 +1913,7 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     sd.gen++;
     sd.topo_gen = sd.gen;
     sd.valid = true;
+    bb.st.prepare_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - prepare_t0).count();
     return PT_OK;
 }
 
@@ -3203,6 +3312,38 @@ int32_t pt_bvh_refit_stats(pt_ctx *ctx, struct pt_bvh_refit_stats *out) {
     if (!out) return fail(PT_ERR_INVALID, "pt_bvh_refit_stats: out is null");
     if (ctx->frames_opened == 0) return fail(PT_ERR_STATE, "pt_bvh_refit_stats before the first frame");
     *out = ctx->rf.st;
+    return PT_OK;
+}
+
+int32_t pt_set_bvh_build(pt_ctx *ctx, int32_t mode) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_bvh_build while a frame is open");
+    if (mode != 0 && mode != 1) return fail(PT_ERR_INVALID, "pt_set_bvh_build: mode must be 0 (host) or 1 (device)");
+    ctx->bb.mode = mode;
+    return PT_OK;
+}
+
+int32_t pt_bvh_build_stats(pt_ctx *ctx, struct pt_bvh_build_stats *out) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!out) return fail(PT_ERR_INVALID, "pt_bvh_build_stats: out is null");
+    if (ctx->frames_opened == 0) return fail(PT_ERR_STATE, "pt_bvh_build_stats before the first frame");
+    *out = ctx->bb.st;
+    return PT_OK;
+}
+
+// Host-only: the Morton-order build of `scene` by the host restatement (ptbvh::build_scene_trees_lbvh), checked the way
+// pt_debug_bvh_check checks the host builder's tree.  out = {nodes, objects, depth, stack_need, objects not reached exactly once,
+// objects not inside their slot's box, child boxes not inside their parent's, structural faults (children or objects not consecutive,
+// a level table that does not increase, a node whose bytes a refit to the build's own world changes)}.
+int32_t pt_debug_bvh_build_check(const pt_scene *scene, int32_t out[8]) {
+    if (!scene || !out) return fail(PT_ERR_INVALID, "null argument");
+    if (scene->num_materials < 0 || scene->num_objects < 0) return fail(PT_ERR_INVALID, "negative scene counts");
+    std::vector<DevObj> w;
+    std::vector<DevMat> m;
+    scene_to_world(*scene, w, m);
+    ptbvh::SceneTrees T;
+    (void)ptbvh::build_scene_trees_lbvh(w, PT_BVH_STACK, T);
+    ptbvh::check_trees(T, w, out);
     return PT_OK;
 }
 

@@ -399,6 +399,65 @@ def bvh_refit_from_env(environ=None) -> float:
     return g
 
 
+BVH_BUILD_MODES = {"host": 0, "device": 1}
+
+
+def _bvh_build_mode(mode) -> int:
+    """0 / 1, "host" / "device", False / True as the mode of pt_set_bvh_build."""
+    if isinstance(mode, str):
+        if mode.strip().lower() not in BVH_BUILD_MODES:
+            raise ValueError("bvh_build must be 'host' or 'device', not %r" % (mode,))
+        return BVH_BUILD_MODES[mode.strip().lower()]
+    if int(mode) not in (0, 1):
+        raise ValueError("bvh_build must be 0 (host) or 1 (device), not %r" % (mode,))
+    return int(mode)
+
+
+def set_bvh_build(ctx: capi.Context, mode) -> None:
+    """pt_set_bvh_build: with "device" (1) a later full build of the bounding-volume hierarchy on ctx -- an object added
+    or removed, a material or a type changed, the first frame, a refitted tree that outgrew its bound -- runs on devices[0] in Morton
+    order instead of on the host; "host" (0) is the default.  The frame is the same, bit for bit.  A library without the entry point
+    takes "host" only."""
+    m = _bvh_build_mode(mode)
+    if not capi.has("pt_set_bvh_build"):
+        if m:
+            raise RuntimeError("this libptcore.so has no pt_set_bvh_build (rebuild it)")
+        return
+    capi.check(capi.load().pt_set_bvh_build(ctx.handle, m))
+    ctx._bvh_build = m  # what `render` compares with: it says the setting only when it changes
+
+
+def bvh_build_stats(ctx: capi.Context) -> dict:
+    """pt_bvh_build_stats: host and device builds since the context was made, the builder of the tree in use (capi.PT_BVH_BUILDER_*),
+    why the last build fell back to the host (capi.PT_BVH_BUILD_FALLBACK_*), the tree's nodes, depth, stack need and quality figure,
+    the device milliseconds of the last device build, the host's wall milliseconds of its upload and of its readback, and the wall
+    milliseconds of the last full scene preparation."""
+    if not capi.has("pt_bvh_build_stats"):
+        raise RuntimeError("this libptcore.so has no pt_bvh_build_stats (rebuild it)")
+    st = capi.PtBvhBuildStats()
+    capi.check(capi.load().pt_bvh_build_stats(ctx.handle, C.byref(st)))
+    return st.as_dict()
+
+
+def bvh_build_check(sc) -> dict:
+    """pt_debug_bvh_build_check (no GPU needed): the Morton-order hierarchy of scene `sc` by the host restatement, checked."""
+    a = sc if isinstance(sc, FlatScene) else FlatScene(sc)
+    out = (C.c_int32 * 8)()
+    capi.check(capi.load().pt_debug_bvh_build_check(C.byref(a.c), out))
+    keys = ("nodes", "objects", "depth", "stack_need", "not_reached_once", "objects_outside", "children_outside", "faults")
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+def bvh_build_from_env(environ=None) -> int:
+    """PATHTRACER_GPU_BVH_BUILD=host|device: the mode of pt_set_bvh_build; unset or empty: host."""
+    v = (os.environ if environ is None else environ).get("PATHTRACER_GPU_BVH_BUILD", "").strip().lower()
+    if not v:
+        return 0
+    if v not in BVH_BUILD_MODES:
+        raise ValueError("PATHTRACER_GPU_BVH_BUILD must be host or device")
+    return BVH_BUILD_MODES[v]
+
+
 def set_object_ids(ctx: capi.Context, on: bool) -> None:
     """pt_set_object_ids: later frames on ctx with features on also record, per pixel, the index into the scene's object list of
     the first hit of the pixel's sample 0 (-1: a miss).  A library without the entry point takes False only."""
@@ -807,7 +866,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            filtered_noise: Optional[float] = None, halves: bool = False,
            temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None,
            object_ids: bool = False, temporal_motion=None, filtered_adaptive: Optional[float] = None, pool: int = 1,
-           feature_walk: bool = False, bvh_refit: Optional[float] = None) -> dict:
+           feature_walk: bool = False, bvh_refit: Optional[float] = None, bvh_build=None) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -869,6 +928,10 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     where its objects are refit the bounding-volume hierarchy on the devices instead of rebuilding it on the host
     (pt_set_bvh_refit; bvh_refit_stats(ctx) afterwards says what happened).  The frame is the one a rebuild gives, bit for bit.
     None leaves the context's setting as it is, which is off unless set_bvh_refit was called.
+
+    bvh_build="device" ("host" = 0 is the default) lets every full build of the hierarchy on the context run on
+    devices[0] in Morton order instead of on the host (pt_set_bvh_build; bvh_build_stats(ctx) afterwards says who built the tree).
+    The frame is the one the host-built tree gives, bit for bit.  None leaves the context's setting as it is.
 
     With `progress`, samples are added in ~10 steps and progress() is called after each
     (the cadence of gpu.go:2209-2212, :2229) and once at the end (gpu.go:2523-2525).
@@ -935,6 +998,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
         set_feature_walk(ctx, bool(feature_walk))
     if bvh_refit is not None and float(bvh_refit) != getattr(ctx, "_bvh_refit", 0.0):  # (said only when it changes: with it never on, the calls are what they were)
         set_bvh_refit(ctx, float(bvh_refit))
+    if bvh_build is not None and _bvh_build_mode(bvh_build) != getattr(ctx, "_bvh_build", 0):  # (the same rule)
+        set_bvh_build(ctx, bvh_build)
     set_features(ctx, features)
     want_ids = object_ids or temporal_motion is not None
     if want_ids != getattr(ctx, "_object_ids_on", False):  # (said only when it changes: with it never on, the calls are what they were)

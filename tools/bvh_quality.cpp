@@ -1,12 +1,14 @@
 // bvh_quality.cpp -- host-only measure of the tree pt_bvh.h builds: node visits and exact tests per closest-hit
 // query over random rays in a synthetic scene of the shape of path_trace_golang_amd/synth.py (no GPU needed).
 //   g++ -O2 -std=c++17 -Ipath_trace_golang_amd/csrc tools/bvh_quality.cpp -o /tmp/bvh_quality && /tmp/bvh_quality 100000
+//   /tmp/bvh_quality 100000 200000 lbvh     the same rays through the Morton-order tree of pt_bvh_build.h
 // The walk follows scan_bvh's order (internal children nearest first, the rest stacked far to near, objects of a
 // node tested exactly before the walk goes on); it is a yardstick for builder changes, not a model of the kernel.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "pt_bvh.h"
@@ -78,7 +80,21 @@ int main(int argc, char **argv) {
     std::vector<int32_t> finite(world.size());
     for (size_t i = 0; i < world.size(); i++) finite[i] = (int32_t)i;
     const auto t0 = std::chrono::steady_clock::now();
-    ptbvh::Built b = ptbvh::build(world, finite, 1e-4);
+    ptbvh::Built b;
+    if (argc > 3 && std::string(argv[3]) == "lbvh") {
+        // the Morton-order tree of pt_bvh_build.h (what pt_set_bvh_build(ctx, 1) builds on the device: the host restatement agrees with
+        // it byte for byte), collapsed without the payload bytes like the tree of ptbvh::build above, so the two arms compare
+        ptbb::Lbvh L;
+        ptbb::build_lbvh(world.data(), finite.data(), (int32_t)finite.size(), 1e-4, 0, 0, L);
+        std::vector<int32_t> leaf_obj(finite.size());
+        for (size_t k = 0; k < finite.size(); k++) leaf_obj[k] = finite[(size_t)L.sorted[k]];
+        const ptbb::BinView tr{L.child.data(), L.box.data(), leaf_obj.data(), (int32_t)finite.size()};
+        ptbb::collapse(tr, 0, world.data(), 1e-4, 0, 0, false, b.nodes, b.order, b.level_start);
+        b.depth = (int)b.level_start.size() - 1;
+        b.stack_need = ptbvh::stack_need_of(b.nodes, 0, b.nodes.size());
+    } else {
+        b = ptbvh::build(world, finite, 1e-4);
+    }
     const double build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     size_t slots = 0;
     for (const BvhNode &nd : b.nodes) slots += (size_t)__builtin_popcount((nd.meta >> 8) & 0xffu);
