@@ -65,6 +65,27 @@ void bp_tree_get(void *h, int32_t t, uint64_t *keys, int32_t *sorted, int32_t *c
     copy(levels, L.level_start.data(), L.level_start.size() * 4);
 }
 
+// ... and the binary nodes ptbb::gather4 puts into the four slots of its wide nodes, breadth-first as ptbb::collapse takes them:
+// out [nodes][4], -1 for an empty slot
+void bp_tree_slots(void *h, int32_t t, int32_t *out) {
+    const ptbb::Lbvh &L = static_cast<BuildProbe *>(h)->tree[t];
+    const int32_t n = (int32_t)L.sorted.size();
+    if (n == 0) return;
+    const ptbb::BinView tr{L.child.data(), L.box.data(), nullptr, n};  // (gather4 asks for no leaf's object)
+    std::vector<int32_t> cur{0}, next;
+    size_t q = 0;
+    while (!cur.empty() && q < L.nodes.size()) {
+        next.clear();
+        for (size_t i = 0; i < cur.size() && q < L.nodes.size(); i++, q++) {
+            int32_t *slot = out + 4 * q;
+            ptbb::gather4(tr, cur[i], slot);
+            for (int s = 0; s < 4; s++)
+                if (slot[s] >= 0 && !tr.leaf(slot[s])) next.push_back(slot[s]);
+        }
+        cur.swap(next);
+    }
+}
+
 // ptbvh::check_trees on the trees
 void bp_check(void *h, int32_t out[8]) {
     const BuildProbe *B = static_cast<BuildProbe *>(h);

@@ -1,6 +1,7 @@
-"""Helpers of the device BVH build's tests (test_bvh_build_cpu.py, test_bvh_build_probe_gpu.py, test_bvh_build_gpu.py):
-the worlds of the cases, tests/bvh_build_probe.cpp as a ctypes library and as a program (the host restatement of csrc/pt_bvh_build.h)
-and tests/bvh_build_probe.hip (the product's launch sequence on a world a test hands in)."""
+"""Helpers of the device BVH build's tests (test_bvh_build_cpu.py, test_bvh_build_reference_cpu.py, test_bvh_build_probe_gpu.py,
+test_bvh_build_gpu.py, test_bvh_build_edges_gpu.py): the worlds and scenes of the cases, tests/bvh_build_probe.cpp as a
+ctypes library and as a program (the host restatement of csrc/pt_bvh_build.h) and tests/bvh_build_probe.hip (the product's launch
+sequence on a world a test hands in).  The independent statement of the build is bvh_build_reference.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,6 +10,7 @@ import subprocess
 
 import numpy as np
 
+import bvh_build_reference as ref
 import bvh_refit_support as rs
 from fog_support import CSRC, CXXFLAGS, ROOT, ptr
 
@@ -41,10 +43,11 @@ def _spheres(centres, radii) -> np.ndarray:
 def special_world(name: str) -> np.ndarray:
     """The smallest worlds where the radix tree, the tie-break and the collapse can go wrong; every ninth object dielectric."""
     if name not in _worlds:
-        n = 300
-        if name == "one centroid":  # all keys equal: the tree is the tie-break's alone
+        kind, _, size = name.partition(", ")
+        n = int(size) if size.isdigit() else 300
+        if kind == "one centroid":  # all keys equal: the tree is the tie-break's alone
             w = _spheres(np.tile([1.0, 2.0, 3.0], (n, 1)), 0.5 + np.arange(n) / 256.0)  # (binary fractions: every centroid is exact)
-        elif name == "a line":  # extent 0 on two axes
+        elif kind == "a line":  # extent 0 on two axes
             w = _spheres(np.stack([np.arange(n) * 1.0, np.full(n, 2.0), np.full(n, -1.0)], axis=1), np.full(n, 0.4))
         elif name == "64 identical among 300":
             base = rs.world_of(300, 0).copy()
@@ -53,6 +56,13 @@ def special_world(name: str) -> np.ndarray:
         elif name == "geometric ratio 2":  # x = 2^(i - 200): all but the last 21 share the lowest cell of the key
             x = np.ldexp(1.0, np.arange(n) - 200)
             w = _spheres(np.stack([x, np.zeros(n), np.zeros(n)], axis=1), 0.25 * x)
+        elif kind == "three centroids interleaved":  # object i at centroid i mod 3: every sort tile holds all three keys
+            x = np.array([1.0, 2.0, 0.0])[np.arange(n) % 3]  # (the key order 2, 0, 1 is not the order of the residues)
+            w = _spheres(np.stack([x, np.full(n, 2.0), np.full(n, -1.0)], axis=1), 0.5 + np.arange(n) / 8192.0)
+        elif name == "duplicates over the seams":
+            w = seam_world()
+        elif kind == "deep":
+            w = deep_world(n)
         else:
             raise KeyError(name)
         w = np.ascontiguousarray(w)
@@ -60,6 +70,95 @@ def special_world(name: str) -> np.ndarray:
         w.setflags(write=False)
         _worlds[name] = w
     return _worlds[name]
+
+
+SEAM_COPIES = tuple(range(1000, 1101)) + tuple(range(4090, 4111))  # positions in `finite` over the first tile seam and the first sort-block seam
+
+
+def seam_world() -> np.ndarray:
+    """rs.world_of(5000, 0) with one object copied to the positions SEAM_COPIES: 123 equal keys that enter the sort from both sides of
+    position 1024 and of position 4096.  The copied object is the one at position 7 if the run of its key then lies over positions
+    1023 / 1024 of the sorted order as well; else the first object by sorted rank for which it does (bvh_build_reference says)."""
+    base = rs.world_of(5000, 0)
+    lo, hi = ref.object_boxes(base)
+    rank = np.argsort(ref.keys_of(ref.centroids(lo, hi)), kind="stable")
+    for src in [7] + [int(i) for i in rank[900:1024] if int(i) not in SEAM_COPIES]:
+        w = base.copy()
+        w[list(SEAM_COPIES)] = base[src]
+        lo, hi = ref.object_boxes(w)
+        keys = ref.keys_of(ref.centroids(lo, hi))
+        run = np.flatnonzero(np.sort(keys, kind="stable") == keys[src])
+        if run[0] <= 1023 and run[-1] >= 1024:
+            return w
+    raise AssertionError("no object of the world gives a run of equal keys over sorted positions 1023 / 1024")
+
+
+def deep_keys(ties: int) -> list:
+    """The keys of deep_world(ties), sorted: a chain that peels one small group off per binary level for 60 levels."""
+    keys = [(1 << 63) - 1]
+    for k in range(60):
+        bit = 62 - k
+        base = 1 << bit
+        low = base - 1
+        keys += [base, base | low, base | low >> 1, base | (low >> 1) + 1] if bit >= 2 else [base]
+    return [0] * ties + sorted(set(keys))
+
+
+def deep_world(ties: int, extra=()) -> np.ndarray:
+    """Spheres of radius 0.25 whose keys are deep_keys(ties): the centroid of key K is its three de-interleaved 21-bit coordinates, with
+    2097151 replaced by 2097152, so that every extent is exactly 2^21 and every scale exactly 1.  `extra` rows of (x, y, z, radius)
+    are appended (their centroids must lie inside the extent: the keys of the others then stay)."""
+    cen = []
+    for key in deep_keys(ties):
+        q = [sum(((key >> (3 * b + 2 - a)) & 1) << b for b in range(21)) for a in range(3)]
+        cen.append([2097152.0 if v == 2097151 else float(v) for v in q])
+    cen, rad = np.array(cen), np.full(len(cen), 0.25)
+    if len(extra):
+        e = np.asarray(extra, np.float64)
+        cen, rad = np.concatenate([cen, e[:, :3]]), np.concatenate([rad, e[:, 3]])
+    return _spheres(cen, rad)
+
+
+DEEP_SCALE = 2.0 ** -18  # a power of two, so exact: the chain's extent of 2^21 becomes 8
+# (x, y, z, radius, material) in the scaled frame: a radius does not move a centroid, and these centroids lie inside the chain's extent
+DEEP_BIG = ((4.0, 4.0, 4.0, 2.5, "chrome"), (1.5, 6.0, 2.0, 2.0, "red"), (6.0, 2.0, 5.0, 2.0, "glass"), (2.0, 1.5, 6.0, 1.5, "green"))
+
+
+def deep_scene(ties: int, big: bool = True):
+    """deep_world(ties) scaled by DEEP_SCALE as a scene.Scene (every ninth sphere glass), with the spheres DEEP_BIG in front of a
+    camera that sees them (`big`) or without them."""
+    from path_trace_golang_amd import scene as scn
+    from path_trace_golang_amd import synth
+
+    sc = synth.make_scene(0, 1)  # its camera block, sky and materials
+    sc.name = "deep-%d" % ties
+    sc.camera = scn.Camera(position=scn.Vec3(4.0, 4.0, 22.0), target=scn.Vec3(4.0, 4.0, 4.0), up=scn.Vec3(0, 1, 0), fov=35.0, aperture=0.0,
+                           focus_dist=18.0, aspect_ratio=0.0)
+    w = deep_world(ties)
+    surf = ("red", "green", "blue", "gold", "glass", "chrome", "mirror", "red", "green")
+    sc.objects = [scn.Object(id="c%d" % i, type="sphere", position=scn.Vec3(*(float(v) * DEEP_SCALE for v in o["a"])),
+                             size=scn.Vec3(float(o["radius"]) * DEEP_SCALE, 0, 0), material_id=surf[i % 9]) for i, o in enumerate(w)]
+    if big:
+        sc.objects += [scn.Object(id="big%d" % i, type="sphere", position=scn.Vec3(x, y, z), size=scn.Vec3(r, 0, 0), material_id=m)
+                       for i, (x, y, z, r, m) in enumerate(DEEP_BIG)]
+    return sc
+
+
+def scene_world(sc) -> np.ndarray:
+    """The finite objects of a scene.Scene as device records, in scene order (what the library's scene conversion gives, planes left
+    out): the world whose trees a render of `sc` builds, up to the world indices."""
+    glass = {m.id: m.type == "dielectric" for m in sc.materials}
+    rows = [o for o in sc.objects if o.type in ("sphere", "sphere_light", "box")]
+    w = np.zeros(len(rows), DEVOBJ)
+    for i, o in enumerate(rows):
+        p, s = np.array(o.position.as_list()), np.array(o.size.as_list())
+        if o.type == "box":
+            w[i]["a"], w[i]["b"], w[i]["kind"] = p - s * 0.5, p + s * 0.5, rs.KIND_BOX
+        else:
+            with np.errstate(divide="ignore"):
+                w[i]["a"], w[i]["radius"], w[i]["radius_sq"], w[i]["inv_radius"], w[i]["kind"] = p, s[0], s[0] * s[0], np.float64(1.0) / s[0], rs.KIND_SPHERE
+        w[i]["kind"] |= 0x100 if glass.get(o.material_id, False) else 0
+    return w
 
 
 def large_world() -> np.ndarray:
@@ -90,11 +189,21 @@ def cases():
 
 CASE_NAMES = [name for name, _ in cases()]
 
+# The worlds on the boundaries of the build's kernels (test_bvh_build_reference_cpu.py asserts what each is chosen for).
+BOUNDARY_SIZES = (255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 5121)  # a block of 256, a tile of 1024, a sort block of 4096, a fifth tile
+TIE_WORLDS = ("one centroid, 5000", "a line, 5000", "three centroids interleaved, 4500", "duplicates over the seams")
+DEEP_TIES = 26  # the smallest number of equal keys in front of the chain for which the tree does not fit the stack (found on the host)
+DEEP_FITS, DEEP_TOO_DEEP = "deep, 1", "deep, %d" % DEEP_TIES
+NEW_CASE_NAMES = ["n=%d diel=7" % n for n in BOUNDARY_SIZES] + list(TIE_WORLDS) + [DEEP_FITS, DEEP_TOO_DEEP]
+
 
 def case_world(name: str) -> np.ndarray:
     if name == "large":
         return large_world()
-    return dict(cases())[name]
+    if name.startswith("n="):
+        n, nd = (int(part.split("=")[1]) for part in name.split())
+        return rs.world_of(n, nd)
+    return special_world(name)
 
 
 # ---------------------------------------------------------------- the host build
@@ -118,6 +227,8 @@ def host():
         L.bp_tree_counts.restype = None
         L.bp_tree_get.argtypes = [_vp, C.c_int32] + [_vp] * 8
         L.bp_tree_get.restype = None
+        L.bp_tree_slots.argtypes = [_vp, C.c_int32, _vp]
+        L.bp_tree_slots.restype = None
         L.bp_check.argtypes = [_vp, _vp]
         L.bp_check.restype = None
         L.bp_rays.argtypes = [_vp, C.c_int32, C.c_uint64, _vp]
@@ -185,6 +296,9 @@ class Trees:
         if n:
             self.L.bp_tree_get(self.h, t, ptr(d["keys"]), ptr(d["sorted"]), ptr(d["child"]) if n > 1 else None, ptr(d["parent"]), ptr(d["box"]),
                                ptr(d["nodes"]), ptr(d["order"]), ptr(d["levels"]))
+        d["slots"] = np.full((nn, 4), -1, np.int32)  # the binary nodes gather4 put into every wide node
+        if n:
+            self.L.bp_tree_slots(self.h, t, ptr(d["slots"]))
         return d
 
     def check(self) -> dict:

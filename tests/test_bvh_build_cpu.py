@@ -14,38 +14,13 @@ import pytest
 
 import bvh_build_support as bs
 import bvh_refit_support as rs
+from bvh_build_reference import py_morton, py_quantise, py_scale  # B1's Python restatement of the key routines lives with the rest of it
 from fog_support import ptr
 
 RAYS = 20000
 
 
 # ---------------------------------------------------------------- B1
-def py_scale(cmin: float, cmax: float) -> float:
-    e = cmax - cmin
-    if not (e > 0.0) or not math.isfinite(e):
-        return 0.0
-    s = 2097152.0 / e
-    return s if math.isfinite(s) else 0.0
-
-
-def py_quantise(c: float, cmin: float, scale: float) -> int:
-    if not math.isfinite(c):
-        c = 0.0
-    t = (c - cmin) * scale
-    if not (t > 0.0):
-        return 0
-    if t >= 2097151.0:
-        return 2097151
-    return int(t)
-
-
-def py_morton(qx: int, qy: int, qz: int) -> int:
-    key = 0
-    for b in range(21):
-        key |= ((qx >> b) & 1) << (3 * b + 2) | ((qy >> b) & 1) << (3 * b + 1) | ((qz >> b) & 1) << (3 * b)
-    return key
-
-
 def axis_values(cmin: float, cmax: float, seed: int) -> np.ndarray:
     """4096 values of one axis: the ends, one ulp inside each, a non-finite centroid, and the rest spread over the extent."""
     rng = np.random.default_rng(seed)
@@ -185,7 +160,7 @@ def test_b3_this_probes_build_of_the_host_builder_agrees():
 def test_b4_standalone_probe_under_sanitizers(tmp_path):
     exe = bs.standalone(("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"), "bvh_build_probe_san")
     files = []
-    for i, (name, w) in enumerate(bs.cases()):
+    for i, (name, w) in enumerate(list(bs.cases()) + [(name, bs.case_world(name)) for name in bs.NEW_CASE_NAMES]):
         p = tmp_path / ("world%02d.bin" % i)
         np.ascontiguousarray(w).tofile(p)
         files.append(str(p))
