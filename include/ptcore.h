@@ -749,7 +749,7 @@ enum {
     PT_BVH_REASON_CHANGED = 3,    /* materials, object count, an object's type or material changed */
     PT_BVH_REASON_NOT_BVH = 4,    /* not on the bounding-volume-hierarchy path, another scan asked for, or walk32 */
     PT_BVH_REASON_GROWTH = 5,     /* the refitted tree's figure exceeded max_growth x the built one's */
-    PT_BVH_REASON_NONFINITE = 6   /* a coordinate of 1e37 or more */
+    PT_BVH_REASON_NONFINITE = 6   /* a coordinate of 1e37 or more (also when the last scene was off the hierarchy for it) */
 };
 
 struct pt_bvh_refit_stats {

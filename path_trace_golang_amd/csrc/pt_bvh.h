@@ -573,6 +573,16 @@ inline void check_trees(const SceneTrees &T, const std::vector<DevObj> &w, int32
 // Why a scene edit cannot be served by a refit (pt_bvh_refit_stats.last_build_reason; 0: it can).
 enum RefitReason { REFIT_OK = 0, REFIT_FIRST = 1, REFIT_OFF = 2, REFIT_CHANGED = 3, REFIT_NOT_BVH = 4, REFIT_GROWTH = 5, REFIT_NONFINITE = 6 };
 
+// A coordinate or a size of 1e37 or more (or none at all: NaN): such a world is on the plain loop and has no tree to refit.
+inline bool world_beyond_fp32(const std::vector<DevObj> &w) {
+    for (const DevObj &o : w) {
+        bool fin = std::fabs(o.radius) < 1e37;
+        for (int k = 0; k < 3; k++) fin = fin && std::fabs(o.a[k]) < 1e37 && std::fabs(o.b[k]) < 1e37;
+        if (!fin) return true;
+    }
+    return false;
+}
+
 // The scene-side conditions of a refit from `before` to `after` (converted worlds and materials): the same materials, the same
 // objects by count, kind (bit 8 included) and material, and every coordinate below 1e37.
 inline int refit_reason(const std::vector<DevObj> &before, const std::vector<DevMat> &mats_before, const std::vector<DevObj> &after,
@@ -583,12 +593,7 @@ inline int refit_reason(const std::vector<DevObj> &before, const std::vector<Dev
     if (before.size() != after.size()) return REFIT_CHANGED;
     for (size_t i = 0; i < after.size(); i++)
         if (before[i].kind != after[i].kind || before[i].mat != after[i].mat) return REFIT_CHANGED;
-    for (const DevObj &o : after) {
-        bool fin = std::fabs(o.radius) < 1e37;
-        for (int k = 0; k < 3; k++) fin = fin && std::fabs(o.a[k]) < 1e37 && std::fabs(o.b[k]) < 1e37;
-        if (!fin) return REFIT_NONFINITE;
-    }
-    return REFIT_OK;
+    return world_beyond_fp32(after) ? REFIT_NONFINITE : REFIT_OK;
 }
 
 }  // namespace ptbvh

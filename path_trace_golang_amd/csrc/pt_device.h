@@ -194,7 +194,7 @@ struct DevFrame {
     uint32_t sph_all, box_all;    // (1 << n_bsph) - 1, (1 << n_bbox) - 1
     uint32_t sph_diel, box_diel;  // records whose object is dielectric (exit searches)
     float origin_bound;  // rays whose origin leaves [-origin_bound, origin_bound]^3 keep every candidate
-    float pad_f;
+    float dir_floor;     // 4 origin_bound / 3e38: a smaller |direction component| counts as zero in the FP32 slab tests (ptk::slab_dir)
     double scene_bound;  // Bs: every finite object (inflated) lies inside [-Bs, Bs]^3
     double clip_bound;   // 3.5 B: rays that start inside [-clip_bound, clip_bound]^3 are scanned from their origin, the others
                          // are clipped against the scene cube first (the FP32 bounds were analysed for origins within 4 B)

@@ -546,6 +546,11 @@ struct BroadLists {
                               pt_vmax(__builtin_fmaf(-bx.h[2], aivzf, tcz_), tminf));                                  \
     const float tf = pt_vmin3(__builtin_fmaf(bx.h[0], aivxf, tcx_), __builtin_fmaf(bx.h[1], aivyf, tcy_), __builtin_fmaf(bx.h[2], aivzf, tcz_));
 
+// The direction component a slab test takes its reciprocal of: zero below F.dir_floor (build_broad).  The reciprocal of zero is
+// infinite and gives NaN parameters, which are skipped; the reciprocal of a tiny component is finite, its products with the origin
+// and the centres pass FLT_MAX, and an infinite tf is no NaN: it culled every box of a ray whose origin lay inside the slab.
+__device__ __forceinline__ float slab_dir(float d, float floor) { return __builtin_fabsf(d) < floor ? 0.0f : d; }
+
 // v_max / v_max3 / v_min3 as instructions (NaN operands are skipped, like the builtins' lowering).  PT_BOX_SLABS uses them: through
 // __builtin_fmaxf the compiler quiets tminf again on every turn of the record loop (a v_max_f32 x, x per box: 0.5 % of a C4 frame).
 __device__ __forceinline__ float pt_vmax(float a, float b) {
@@ -759,6 +764,12 @@ __device__ __forceinline__ void scan_broad_narrow(const DevFrame &F, ObjPtr g_ob
     // -o/d: the extra rounding (~2^-24 |o| in distance) is far inside the margin, and inf - inf = NaN for a zero
     // direction component leaves that slab unconstrained
     const float noxf = -fox * ivxf, noyf = -foy * ivyf, nozf = -foz * ivzf;
+    // A component below F.dir_floor has a finite reciprocal whose products pass FLT_MAX (see slab_dir): such a ray keeps every box
+    // (two instructions per scan here, where the walks of the hierarchy zero the component instead: a box more or less is cheap
+    // among at most 32, a subtree is not)
+    float dir_min;  // (as one instruction: through __builtin_fminf the compiler quiets every operand first, see pt_vmax)
+    asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(dir_min) : "v"(fdx), "v"(fdy), "v"(fdz));
+    const bool flat_dir = dir_min < F.dir_floor;
     auto box_record = [&](const auto &bx) {
         PT_BOX_SLABS(bx, t0, t1)
         push_keep_bit(cb, t1, t0);
@@ -792,7 +803,8 @@ __device__ __forceinline__ void scan_broad_narrow(const DevFrame &F, ObjPtr g_ob
         }
         if (k < BL.n_bbox) box_record(BL.bb[k]);
     }
-    if (!trust) { cs = BL.sph_all; cb = BL.box_all; }
+    if (!trust) cs = BL.sph_all;
+    if (!trust || flat_dir) cb = BL.box_all;
     if (outside_all) { cs = 0; cb = 0; }
     if (MODE < 0) {
         if (mode != 0) { cs &= BL.sph_diel; cb &= BL.box_diel; }
@@ -906,7 +918,8 @@ __device__ __forceinline__ void scan_broad_narrow_wide(const DevFrame &F, ObjPtr
     float tminf = (float)(tmin - ts);
     tminf -= __builtin_fabsf(tminf) * 1e-2f + 1e-6f;
     const float inv_a = __builtin_amdgcn_rcpf(fa);
-    const float ivxf = __builtin_amdgcn_rcpf(fdx), ivyf = __builtin_amdgcn_rcpf(fdy), ivzf = __builtin_amdgcn_rcpf(fdz);
+    const float ivxf = __builtin_amdgcn_rcpf(slab_dir(fdx, F.dir_floor)), ivyf = __builtin_amdgcn_rcpf(slab_dir(fdy, F.dir_floor)),
+                ivzf = __builtin_amdgcn_rcpf(slab_dir(fdz, F.dir_floor));
     const float aivxf = __builtin_fabsf(ivxf), aivyf = __builtin_fabsf(ivyf), aivzf = __builtin_fabsf(ivzf);
     const float noxf = -fox * ivxf, noyf = -foy * ivyf, nozf = -foz * ivzf;
 
@@ -1112,7 +1125,8 @@ __device__ __forceinline__ bool scan_bvh(const DevFrame &F, ObjPtr g_obj, IdxPtr
     // A re-based ray starts on the scene cube, which keeps B/512 - m of clearance around every bound: nothing
     // begins before t' = 0.  With that every entry parameter below is >= 0 and its bit pattern orders like it.
     tminf = __builtin_fmaxf(tminf, 0.0f);
-    const float ivxf = __builtin_amdgcn_rcpf(fdx), ivyf = __builtin_amdgcn_rcpf(fdy), ivzf = __builtin_amdgcn_rcpf(fdz);
+    const float ivxf = __builtin_amdgcn_rcpf(slab_dir(fdx, F.dir_floor)), ivyf = __builtin_amdgcn_rcpf(slab_dir(fdy, F.dir_floor)),
+                ivzf = __builtin_amdgcn_rcpf(slab_dir(fdz, F.dir_floor));
     // slab parameters as bound * (1/d) - o/d (see scan_broad_narrow)
     const float noxf = -fox * ivxf, noyf = -foy * ivyf, nozf = -foz * ivzf;
     // widening of a slab by infl in parameter units (a little more than infl / |d|; inf or NaN for a zero

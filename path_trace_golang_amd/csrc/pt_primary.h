@@ -105,7 +105,8 @@ __global__ __launch_bounds__(PT_BLOCK, PT_PRIMARY_WAVES) void primary_bvh_kernel
                 float tminf = (float)tmin;
                 tminf -= __builtin_fabsf(tminf) * 1e-2f + 1e-6f;
                 tminf = __builtin_fmaxf(tminf, 0.0f);
-                const float ivxf = __builtin_amdgcn_rcpf(fdx), ivyf = __builtin_amdgcn_rcpf(fdy), ivzf = __builtin_amdgcn_rcpf(fdz);
+                const float ivxf = __builtin_amdgcn_rcpf(slab_dir(fdx, F.dir_floor)), ivyf = __builtin_amdgcn_rcpf(slab_dir(fdy, F.dir_floor)),
+                            ivzf = __builtin_amdgcn_rcpf(slab_dir(fdz, F.dir_floor));
                 const float aivxf = __builtin_fabsf(ivxf), aivyf = __builtin_fabsf(ivyf), aivzf = __builtin_fabsf(ivzf);
                 const float noxf = -fox * ivxf, noyf = -foy * ivyf, nozf = -foz * ivzf;
                 float tmaxf = (float)tmax;

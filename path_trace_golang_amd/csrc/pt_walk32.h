@@ -169,8 +169,8 @@ __global__ __launch_bounds__(PT_BLOCK, PT_WALK_WAVES) void wf_walk32_kernel(cons
                     } else {
                         const double ts = clip.ts;
                         const float fox = (float)(r.ox + r.dx * ts), foy = (float)(r.oy + r.dy * ts), foz = (float)(r.oz + r.dz * ts);
-                        const float ivx = __builtin_amdgcn_rcpf((float)r.dx), ivy = __builtin_amdgcn_rcpf((float)r.dy),
-                                    ivz = __builtin_amdgcn_rcpf((float)r.dz);
+                        const float ivx = __builtin_amdgcn_rcpf(slab_dir((float)r.dx, F.dir_floor)), ivy = __builtin_amdgcn_rcpf(slab_dir((float)r.dy, F.dir_floor)),
+                                    ivz = __builtin_amdgcn_rcpf(slab_dir((float)r.dz, F.dir_floor));
                         iv_xy = v2f{ivx, ivy};
                         iv_z_aiv_x = v2f{ivz, __builtin_fabsf(ivx)};
                         aiv_yz = v2f{__builtin_fabsf(ivy), __builtin_fabsf(ivz)};

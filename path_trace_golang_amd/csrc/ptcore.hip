@@ -646,6 +646,12 @@ void build_broad(const std::vector<DevObj> &world, SceneData &fr) {
     F.sph_all = fr.bsph.size() >= 32 ? 0xffffffffu : ((1u << fr.bsph.size()) - 1u);
     F.box_all = fr.bbox.size() >= 32 ? 0xffffffffu : ((1u << fr.bbox.size()) - 1u);
     F.origin_bound = (float)std::min(4.0 * B, 3.0e38);
+    // With |1/d| (4 origin_bound) < 3e38 no product of a slab test (a centre, a half extent or an origin within origin_bound times
+    // 1/d) leaves the finite range, nor does their sum.  A smaller component is taken for zero, whose slab constrains nothing (the
+    // walks of the hierarchy, the grouped scan), or the ray keeps every box (the scan of at most 32 records): a
+    // product past FLT_MAX is an INFINITY, not a NaN, and tf = -inf culled boxes the ray goes through (B = 8: 4.3e-37; from
+    // B = 2^61 on a component of 2^-60 is below it; in the keep-everything band every component is).
+    F.dir_floor = round_up_f(4.0 * (double)F.origin_bound / 3.0e38);
     F.scene_bound = B * (1.0 + 1.0 / 512.0);  // the inflation is B/4096
     F.clip_bound = B * 3.5;
     F.margin = m;
@@ -1749,7 +1755,8 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     else if (!refit_on) reason = ptbvh::REFIT_OFF;
     else if (outgrown) reason = ptbvh::REFIT_GROWTH;
     else if (!(sd.scan == ptk::SCAN_BVH || sd.scan == ptk::SCAN_VERIFY_BVH) || sd.scan_req != ctx->scan_mode || ctx->pipeline == 2)
-        reason = ptbvh::REFIT_NOT_BVH;  // (the walk32 core twins are not refitted)
+        // (the walk32 core twins are not refitted; a world kept off the hierarchy by the 1e37 rule says so, whatever the last one was)
+        reason = ptbvh::world_beyond_fp32(world) ? ptbvh::REFIT_NONFINITE : ptbvh::REFIT_NOT_BVH;
     else reason = ptbvh::refit_reason(sd.world, sd.mats, world, mats);
     if (reason == ptbvh::REFIT_OK) {
         // Same objects by kind and material, all finite: the scan, the counts, the depth, the stack and the LDS plan stay.  The
