@@ -550,6 +550,38 @@ struct BroadLists {
 // infinite and gives NaN parameters, which are skipped; the reciprocal of a tiny component is finite, its products with the origin
 // and the centres pass FLT_MAX, and an infinite tf is no NaN: it culled every box of a ray whose origin lay inside the slab.
 __device__ __forceinline__ float slab_dir(float d, float floor) { return __builtin_fabsf(d) < floor ? 0.0f : d; }
+// ... and the three reciprocals of a ray's slab tests (floor = F.dir_floor).
+__device__ __forceinline__ void slab_recips(float floor, float fdx, float fdy, float fdz, float &ivx, float &ivy, float &ivz) {
+    ivx = __builtin_amdgcn_rcpf(slab_dir(fdx, floor));
+    ivy = __builtin_amdgcn_rcpf(slab_dir(fdy, floor));
+    ivz = __builtin_amdgcn_rcpf(slab_dir(fdz, floor));
+}
+
+// The internal children of a 4-wide node nearest first: four keys in, sorted ascending out (5-exchange network).  A key is the
+// child's entry parameter (>= 0, so its bits order like the value) with the slot in its low bits; 0xffffffff = not a candidate.
+__device__ __forceinline__ void sort4_keys(uint32_t key0, uint32_t key1, uint32_t key2, uint32_t key3, uint32_t &k0, uint32_t &k1, uint32_t &k2,
+                                           uint32_t &k3) {
+    const uint32_t a0 = key0 < key1 ? key0 : key1, a1 = key0 < key1 ? key1 : key0;
+    const uint32_t a2 = key2 < key3 ? key2 : key3, a3 = key2 < key3 ? key3 : key2;
+    k0 = a0 < a2 ? a0 : a2;
+    const uint32_t m0 = a0 < a2 ? a2 : a0;
+    k3 = a1 < a3 ? a3 : a1;
+    const uint32_t m1 = a1 < a3 ? a1 : a3;
+    k1 = m0 < m1 ? m0 : m1;
+    k2 = m0 < m1 ? m1 : m0;
+}
+// The keys of a lane's own node visit (scan_bvh, wf_walk32_kernel), sorted: the entry parameter's bits with 2*slot in the low three;
+// a candidate only when the slot is pierced (hb) AND an internal node (meta bits 8-11).
+__device__ __forceinline__ void child_order(const float (&t0)[4], uint32_t hb, uint32_t meta, uint32_t &k0, uint32_t &k1, uint32_t &k2,
+                                            uint32_t &k3) {
+    uint32_t key[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const uint32_t bits = (__float_as_uint(t0[s]) & ~7u) | (uint32_t)(2 * s);
+        key[s] = ((hb & (meta >> 8)) & (1u << s)) ? bits : 0xffffffffu;
+    }
+    sort4_keys(key[0], key[1], key[2], key[3], k0, k1, k2, k3);
+}
 
 // v_max / v_max3 / v_min3 as instructions (NaN operands are skipped, like the builtins' lowering).  PT_BOX_SLABS uses them: through
 // __builtin_fmaxf the compiler quiets tminf again on every turn of the record loop (a v_max_f32 x, x per box: 0.5 % of a C4 frame).
@@ -918,8 +950,8 @@ __device__ __forceinline__ void scan_broad_narrow_wide(const DevFrame &F, ObjPtr
     float tminf = (float)(tmin - ts);
     tminf -= __builtin_fabsf(tminf) * 1e-2f + 1e-6f;
     const float inv_a = __builtin_amdgcn_rcpf(fa);
-    const float ivxf = __builtin_amdgcn_rcpf(slab_dir(fdx, F.dir_floor)), ivyf = __builtin_amdgcn_rcpf(slab_dir(fdy, F.dir_floor)),
-                ivzf = __builtin_amdgcn_rcpf(slab_dir(fdz, F.dir_floor));
+    float ivxf, ivyf, ivzf;
+    slab_recips(F.dir_floor, fdx, fdy, fdz, ivxf, ivyf, ivzf);
     const float aivxf = __builtin_fabsf(ivxf), aivyf = __builtin_fabsf(ivyf), aivzf = __builtin_fabsf(ivzf);
     const float noxf = -fox * ivxf, noyf = -foy * ivyf, nozf = -foz * ivzf;
 
@@ -1125,8 +1157,8 @@ __device__ __forceinline__ bool scan_bvh(const DevFrame &F, ObjPtr g_obj, IdxPtr
     // A re-based ray starts on the scene cube, which keeps B/512 - m of clearance around every bound: nothing
     // begins before t' = 0.  With that every entry parameter below is >= 0 and its bit pattern orders like it.
     tminf = __builtin_fmaxf(tminf, 0.0f);
-    const float ivxf = __builtin_amdgcn_rcpf(slab_dir(fdx, F.dir_floor)), ivyf = __builtin_amdgcn_rcpf(slab_dir(fdy, F.dir_floor)),
-                ivzf = __builtin_amdgcn_rcpf(slab_dir(fdz, F.dir_floor));
+    float ivxf, ivyf, ivzf;
+    slab_recips(F.dir_floor, fdx, fdy, fdz, ivxf, ivyf, ivzf);
     // slab parameters as bound * (1/d) - o/d (see scan_broad_narrow)
     const float noxf = -fox * ivxf, noyf = -foy * ivyf, nozf = -foz * ivzf;
     // widening of a slab by infl in parameter units (a little more than infl / |d|; inf or NaN for a zero
@@ -1229,27 +1261,9 @@ __device__ __forceinline__ bool scan_bvh(const DevFrame &F, ObjPtr g_obj, IdxPtr
            : __builtin_amdgcn_perm(0u, __float_as_uint(nd.h[a][2]), 0x0c000c0cu)))
             const uint32_t meta = PT_LOWBYTES(2, false);
             const uint32_t oh = hb & (meta >> 12) & 0xfu;  // object children pierced
-            // internal children nearest first: sort keys = entry parameter (>= 0, so its bits order like the
-            // value) with 2*slot in the low three bits; 0xffffffff = not a candidate
+            // internal children nearest first
             uint32_t k0, k1, k2, k3;
-            {
-                uint32_t key[4];
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const uint32_t bits = (__float_as_uint(t0[s]) & ~7u) | (uint32_t)(2 * s);
-                    // a candidate only when the slot is pierced AND an internal node (meta bits 8-11)
-                    key[s] = ((hb & (meta >> 8)) & (1u << s)) ? bits : 0xffffffffu;
-                }
-                // 5-exchange network
-                uint32_t a0 = key[0] < key[1] ? key[0] : key[1], a1 = key[0] < key[1] ? key[1] : key[0];
-                uint32_t a2 = key[2] < key[3] ? key[2] : key[3], a3 = key[2] < key[3] ? key[3] : key[2];
-                k0 = a0 < a2 ? a0 : a2;
-                const uint32_t m0 = a0 < a2 ? a2 : a0;
-                k3 = a1 < a3 ? a3 : a1;
-                const uint32_t m1 = a1 < a3 ? a1 : a3;
-                k1 = m0 < m1 ? m0 : m1;
-                k2 = m0 < m1 ? m1 : m0;
-            }
+            child_order(t0, hb, meta, k0, k1, k2, k3);
             const int nbase = (int)PT_LOWBYTES(0, true);
 #define PT_CHILD(k) (nbase + (int)((meta >> ((k) & 7u)) & 3u))
             if (k1 != 0xffffffffu) {  // sorted: k2 and k3 can only be candidates when k1 is

@@ -1,20 +1,9 @@
 // pt_primary.h -- the first segment of every path of a BVH scene, traversed by the WAVE instead of by the lane (round 4).
 //
-// A trace wave of the BVH path walks 64 unrelated rays, one stack per lane: divergent node fetches (six 16-byte requests per
-// lane and visit), a fifth to a half of the lanes waiting for the slowest walks of the wave.  The primary rays of
-// a pass are the one population for which none of that is necessary: 64 consecutive jobs are one sample of one 8 x 8 pixel
-// block (pt_device.h), i.e. 64 rays from (nearly) one point through (nearly) one direction.  primary_bvh_kernel gives each
-// such wave ONE stack:
-//   * a node is fetched once per wave by scalar loads (wave-uniform address, no vector memory request at all) and its four
-//     slot boxes feed the lanes' FP32 slab tests as scalar operands;
-//   * the wave descends into a child when ANY lane's ray pierces it before that lane's own tmax (ballot), nearest first
-//     by the entry parameter of the first lane that pierces it, the others pushed on the wave's stack (LDS, 96 words);
-//   * an object slot pierced by any lane is tested at once: the 96-byte record arrives by scalar loads, the kind is
-//     wave-uniform (no divergence between sphere and box code), the lanes whose own slab test passed run the reference's
-//     exact FP64 test (objects.go:37-61, :141-179) and take the winner by `wins` (order-free statement of the loop,
-//     renderer.go:297-302), each culling against its own tmax from then on.
-// Every lane therefore tests at least the objects its own per-lane walk would have tested (those whose inflated box its ray
-// pierces before its current tmax) -- the result is the sequential loop's winner, bit for bit; `verify_bvh` checks it.
+// The primary rays of a pass are a population the wave can walk the tree for: 64 consecutive jobs are one sample of one 8 x 8 pixel
+// block (pt_device.h), i.e. 64 rays from (nearly) one point through (nearly) one direction.  primary_bvh_kernel finds their first
+// hits with ONE stack per wave, by wave_first_hit (pt_wave_walk.h, which says how and why the result is the sequential loop's
+// winner, bit for bit; `verify_bvh` checks it).
 //
 // The kernel then shades the hit (renderer.go:304-403: sky, emitted, scatter, roulette) with the code the trace loop uses
 // and appends the paths that go on to the continuation queue (the split passes' PathQueue, windows of PT_CONT_BLOCK slots per
@@ -25,7 +14,7 @@
 // (their exit search walks the second tree; one object in ten of the synthetic scenes).
 #pragma once
 
-#include "pt_kernels.h"
+#include "pt_wave_walk.h"
 
 namespace ptk {
 
@@ -53,7 +42,6 @@ __global__ __launch_bounds__(PT_BLOCK, PT_PRIMARY_WAVES) void primary_bvh_kernel
     uint32_t q_cur = 0, q_end = 0;  // this wave's window of continuation slots (one atomic per PT_CONT_BLOCK slots, see trace_kernel)
     uint32_t c_seg = 0, c_draw = 0, c_samples = 0, c_mismatch = 0, c_cont = 0;
     uint32_t c_visits = 0, c_coop = 0, c_odd = 0;  // wave-uniform (diagnostics)
-    const double tmin = 0.001;  // renderer.go:292
 
     for (uint32_t wj = wave0; (size_t)wj * PT_WAVE < nj; wj += nwaves) {  // njobs is a multiple of 64: a wave's jobs all exist
         const uint32_t job = wj * PT_WAVE + lane;
@@ -68,131 +56,17 @@ __global__ __launch_bounds__(PT_BLOCK, PT_PRIMARY_WAVES) void primary_bvh_kernel
             if (have) store_path_end<STATS>(&B, job, 0.0, 0.0, 0.0, 0u, nd);
             continue;
         }
-        // ------------------------------------------------------------ is this a wave for the shared walk?
-        const RayD r{ox, oy, oz, dx, dy, dz};
+        // ------------------------------------------------------------ the wave's walk (pt_wave_walk.h), or none for an odd wave
         const double a = dx * dx + dy * dy + dz * dz;
-        const double Cb = F.clip_bound;
-        const bool tame = (a >= 1e-100) && (a <= 1e100) && (ptm::f_abs(ox) <= Cb) && (ptm::f_abs(oy) <= Cb) && (ptm::f_abs(oz) <= Cb);
-        const Clip noclip{0.0, 0.0, 0.0, false, false};  // origins within 3.5 scene sizes are scanned from where they are (clip_ray: `inside`)
-        const bool odd = have && !(tame && bvh_ray_trusted(F, r, noclip, a));
-        const bool coop = __ballot(odd) == 0;
+        const RayD r{ox, oy, oz, dx, dy, dz};
+        const bool coop = wave_walk_coop(F, have, r, a);
         if (coop) c_coop++;
         else c_odd++;
         int best = -1;
         double tmax = ptm::max_float64();
         if (coop && have) {
-            bool best_is_box = false;
-            // ---- planes: infinite, always tested exactly (scan_bvh does the same)
-            for (int k = 0; k < F.n_plane; k++) {
-                const int i = g_pl[k];
-                const auto &o = g_obj[i];
-                double t = 0;
-                if (F.planes_y ? plane_exact_y(o.a[1], r, tmin, tmax, t)
-                               : plane_exact(o.a[0], o.a[1], o.a[2], o.b[0], o.b[1], o.b[2], r, tmin, tmax, t)) {
-                    if (wins(0, false, i, t, best, best_is_box, tmax)) {
-                        best = i;
-                        tmax = t;
-                        best_is_box = false;
-                    }
-                }
-            }
-            if (F.bvh_root >= 0) {
-                const double ya = div_recip(a);
-                const double ivx = 1 / dx, ivy = 1 / dy, ivz = 1 / dz;  // objects.go:149,154,159
-                // FP32 quantities of the node tests, as scan_bvh derives them (ts = 0: the ray starts inside the clip bound)
-                const float fox = (float)ox, foy = (float)oy, foz = (float)oz;
-                const float fdx = (float)dx, fdy = (float)dy, fdz = (float)dz;
-                float tminf = (float)tmin;
-                tminf -= __builtin_fabsf(tminf) * 1e-2f + 1e-6f;
-                tminf = __builtin_fmaxf(tminf, 0.0f);
-                const float ivxf = __builtin_amdgcn_rcpf(slab_dir(fdx, F.dir_floor)), ivyf = __builtin_amdgcn_rcpf(slab_dir(fdy, F.dir_floor)),
-                            ivzf = __builtin_amdgcn_rcpf(slab_dir(fdz, F.dir_floor));
-                const float aivxf = __builtin_fabsf(ivxf), aivyf = __builtin_fabsf(ivyf), aivzf = __builtin_fabsf(ivzf);
-                const float noxf = -fox * ivxf, noyf = -foy * ivyf, nozf = -foz * ivzf;
-                float tmaxf = (float)tmax;
-                tmaxf += __builtin_fabsf(tmaxf) * 4.8e-7f;  // >= tmax (MaxFloat64 becomes +inf)
-                int sp = 0;
-                int cur = F.bvh_root;
-                while (cur >= 0) {
-                    c_visits++;
-                    const auto &nd_ = nodes[cur];  // wave-uniform: scalar loads
-                    const uint32_t meta = nd_.meta;
-                    const int nbase = nd_.node_base, obase = nd_.obj_base;
-                    uint32_t key[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-#pragma unroll
-                    for (int s = 0; s < 4; s++) {
-                        const bool is_node = (meta >> (8 + s)) & 1u, is_obj = (meta >> (12 + s)) & 1u;
-                        if (!(is_node || is_obj)) continue;  // empty slot (wave-uniform)
-                        // slab parameters from centre and half extent (see PT_BOX_SLABS); the half extents carry the embedded index
-                        // bytes of the per-lane walk in their low mantissa bits: still upper bounds
-                        const float tcx = __builtin_fmaf(nd_.c[0][s], ivxf, noxf), tcy = __builtin_fmaf(nd_.c[1][s], ivyf, noyf),
-                                    tcz = __builtin_fmaf(nd_.c[2][s], ivzf, nozf);
-                        const float t0 = pt_vmax3(__builtin_fmaf(-nd_.h[0][s], aivxf, tcx), __builtin_fmaf(-nd_.h[1][s], aivyf, tcy),
-                                                  pt_vmax(__builtin_fmaf(-nd_.h[2][s], aivzf, tcz), tminf));
-                        const float t1 = pt_vmin3(__builtin_fmaf(nd_.h[0][s], aivxf, tcx), __builtin_fmaf(nd_.h[1][s], aivyf, tcy),
-                                                  pt_vmin(__builtin_fmaf(nd_.h[2][s], aivzf, tcz), tmaxf));
-                        const bool pierced = !(t1 < t0);  // NaN slabs constrain nothing, like the per-lane walk
-                        const uint64_t pm = __ballot(pierced);
-                        if (pm == 0) continue;
-                        if (is_node) {
-                            // entry parameter of the first lane that pierces the slot (>= 0: its bits order like the value), slot in the low bits
-                            const int src = __ffsll((long long)pm) - 1;
-                            const uint32_t bits = (uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(t0), src);
-                            key[s] = (bits & ~3u) | (uint32_t)s;
-                        } else if (pierced) {
-                            // the slot's object, for every lane whose own slab test passed: the reference's exact test
-                            const auto &bo = bobjs[obase + (int)((meta >> (2 * s)) & 3u)];
-                            const int i = bo.index;
-                            const bool is_box = (bo.o.kind & 0xff) == KIND_BOX;  // wave-uniform
-                            double t = 0;
-                            bool valid;
-                            if (is_box)
-                                valid = box_exact<true>(bo.o.a[0], bo.o.a[1], bo.o.a[2], bo.o.b[0], bo.o.b[1], bo.o.b[2], r, ivx, ivy, ivz, tmin,
-                                                        ptm::max_float64(), t);
-                            else
-                                valid = sphere_exact_shared<false>(bo.o.a[0], bo.o.a[1], bo.o.a[2], bo.o.radius_sq, r, a, ya, tmin, tmax, t);
-                            if (valid && wins(0, is_box, i, t, best, best_is_box, tmax)) {
-                                best = i;
-                                tmax = t;
-                                best_is_box = is_box;
-                                tmaxf = (float)tmax;
-                                tmaxf += __builtin_fabsf(tmaxf) * 4.8e-7f;
-                            }
-                        }
-                    }
-                    // internal children nearest first (wave-uniform keys: scalar unit); 0xffffffff = not a candidate
-                    uint32_t k0, k1, k2, k3;
-                    {
-                        const uint32_t a0 = key[0] < key[1] ? key[0] : key[1], a1 = key[0] < key[1] ? key[1] : key[0];
-                        const uint32_t a2 = key[2] < key[3] ? key[2] : key[3], a3 = key[2] < key[3] ? key[3] : key[2];
-                        k0 = a0 < a2 ? a0 : a2;
-                        const uint32_t m0 = a0 < a2 ? a2 : a0;
-                        k3 = a1 < a3 ? a3 : a1;
-                        const uint32_t m1 = a1 < a3 ? a1 : a3;
-                        k1 = m0 < m1 ? m0 : m1;
-                        k2 = m0 < m1 ? m1 : m0;
-                    }
-#define PT_CHILD(k) (nbase + (int)((meta >> (2u * ((k) & 3u))) & 3u))
-                    if (k1 != 0xffffffffu) {
-                        if (k2 != 0xffffffffu) {
-                            if (k3 != 0xffffffffu) { wst[sp] = PT_CHILD(k3); sp++; }
-                            wst[sp] = PT_CHILD(k2);
-                            sp++;
-                        }
-                        wst[sp] = PT_CHILD(k1);
-                        sp++;
-                    }
-                    if (k0 != 0xffffffffu) {
-                        cur = PT_CHILD(k0);
-                    } else if (sp > 0) {
-                        sp--;
-                        cur = __builtin_amdgcn_readfirstlane(wst[sp]);
-                    } else {
-                        cur = -1;
-                    }
-#undef PT_CHILD
-                }
-            }
+            uint32_t no_deep = 0;
+            wave_first_hit<false>(F, nodes, bobjs, g_obj, g_pl, ox, oy, oz, dx, dy, dz, a, wst, best, tmax, c_visits, no_deep);
             if (VERIFY) {
                 int best2;
                 double tmax2;

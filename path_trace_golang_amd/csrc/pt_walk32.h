@@ -169,8 +169,8 @@ __global__ __launch_bounds__(PT_BLOCK, PT_WALK_WAVES) void wf_walk32_kernel(cons
                     } else {
                         const double ts = clip.ts;
                         const float fox = (float)(r.ox + r.dx * ts), foy = (float)(r.oy + r.dy * ts), foz = (float)(r.oz + r.dz * ts);
-                        const float ivx = __builtin_amdgcn_rcpf(slab_dir((float)r.dx, F.dir_floor)), ivy = __builtin_amdgcn_rcpf(slab_dir((float)r.dy, F.dir_floor)),
-                                    ivz = __builtin_amdgcn_rcpf(slab_dir((float)r.dz, F.dir_floor));
+                        float ivx, ivy, ivz;
+                        slab_recips(F.dir_floor, (float)r.dx, (float)r.dy, (float)r.dz, ivx, ivy, ivz);
                         iv_xy = v2f{ivx, ivy};
                         iv_z_aiv_x = v2f{ivz, __builtin_fabsf(ivx)};
                         aiv_yz = v2f{__builtin_fabsf(ivy), __builtin_fabsf(ivz)};
@@ -276,24 +276,9 @@ __global__ __launch_bounds__(PT_BLOCK, PT_WALK_WAVES) void wf_walk32_kernel(cons
                 cnt++;
                 if (DIAG) d_cand++;
             }
-            // ---- internal children nearest first (the sorting network of scan_bvh)
+            // ---- internal children nearest first (as scan_bvh)
             uint32_t k0, k1, k2, k3;
-            {
-                uint32_t key[4];
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const uint32_t bits = (__float_as_uint(t0[s]) & ~7u) | (uint32_t)(2 * s);
-                    key[s] = ((hb & (meta >> 8)) & (1u << s)) ? bits : 0xffffffffu;  // pierced AND an internal node
-                }
-                uint32_t a0 = key[0] < key[1] ? key[0] : key[1], a1 = key[0] < key[1] ? key[1] : key[0];
-                uint32_t a2 = key[2] < key[3] ? key[2] : key[3], a3 = key[2] < key[3] ? key[3] : key[2];
-                k0 = a0 < a2 ? a0 : a2;
-                const uint32_t m0 = a0 < a2 ? a2 : a0;
-                k3 = a1 < a3 ? a3 : a1;
-                const uint32_t m1 = a1 < a3 ? a1 : a3;
-                k1 = m0 < m1 ? m0 : m1;
-                k2 = m0 < m1 ? m1 : m0;
-            }
+            child_order(t0, hb, meta, k0, k1, k2, k3);
 #define PT_CHILD(k) (nbase + (int)((meta >> ((k) & 7u)) & 3u))
             bool deep = false;
             if (want_core != 0) {  // the core twin first (it may cull what follows); every child waits on the stack

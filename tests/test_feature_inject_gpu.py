@@ -1,7 +1,7 @@
 """Injected rays through feature_bvh_kernel (csrc/pt_feature_walk.h), record by record against the oracle.
 
-The kernel's walk is a second copy of primary_bvh_kernel's, and test_feature_walk_gpu.py feeds it camera rays: coherent waves of unit
-directions.  Here the seven tables of feature_inject_support.py -- direction lengths over 1200 binades, zero and denormal components,
+The kernel's walk is the function primary_bvh_kernel calls (csrc/pt_wave_walk.h), and test_feature_walk_gpu.py feeds it camera rays:
+coherent waves of unit directions.  Here the seven tables of feature_inject_support.py -- direction lengths over 1200 binades, zero and denormal components,
 origins on the geometry and around every bound, incoherent waves, waves with one odd lane, exactly axis-parallel rays beside many
 cores -- go through it on the 341-object scene of ray_inject_support.py, in their own layout (one odd lane in most waves: the plain
 scan) and in walk_layout (the degenerate rays in whole waves: the walk).  Every ray's normal, albedo, distance, hit flag and id is the
