@@ -47,6 +47,7 @@ func main() {
 	bvhRefit := flag.Float64("bvh-refit", 0, "refit the bounding-volume hierarchy on the GPU when a scene's objects only moved; the value (>= 1, or +Inf) bounds how far the tree may degrade before it is rebuilt (or PATHTRACER_GPU_BVH_REFIT)")
 	bvhBuild := flag.String("bvh-build", "host", "who builds the bounding-volume hierarchy when a full build is due: host, or device (the GPU, in Morton order; or PATHTRACER_GPU_BVH_BUILD)")
 	featureWalk := flag.Bool("feature-walk", false, "collect features on scenes beyond 128 spheres or 128 boxes too, by a wave-shared walk of the tree (or PATHTRACER_GPU_FEATURE_WALK)")
+	fogWalk := flag.Bool("fog-walk", false, "with -fog: draw a gpu_volumetric fog block on scenes beyond 128 spheres or 128 boxes too, the shadow rays by a wave-shared walk of the tree (or PATHTRACER_GPU_FOG_WALK)")
 	flag.Parse()
 	log.Printf("flags: scene=%s mode=%s headless=%v out=%s\n", *scenePath, *mode, *headless, *output)
 
@@ -79,6 +80,11 @@ func main() {
 		flag.Visit(func(f *flag.Flag) { walkGiven = walkGiven || f.Name == "feature-walk" })
 		if walkGiven { // else the environment decides
 			hip.SetFeatureWalk(*featureWalk)
+		}
+		fogWalkGiven := false
+		flag.Visit(func(f *flag.Flag) { fogWalkGiven = fogWalkGiven || f.Name == "fog-walk" })
+		if fogWalkGiven { // else the environment decides
+			hip.SetFogWalk(*fogWalk)
 		}
 		refitGiven := false
 		flag.Visit(func(f *flag.Flag) { refitGiven = refitGiven || f.Name == "bvh-refit" })

@@ -77,6 +77,9 @@ var (
 	walkSet      bool           // false: PATHTRACER_GPU_FEATURE_WALK decides
 	walkWanted   bool
 	walkOn       bool           // pt_set_feature_walk(1) was the last thing said to the context
+	fogWalkSet    bool          // false: PATHTRACER_GPU_FOG_WALK decides
+	fogWalkWanted bool
+	fogWalkOn     bool          // pt_set_fog_walk(1) was the last thing said to the context
 	refitSet     bool           // false: PATHTRACER_GPU_BVH_REFIT decides
 	refitWanted  float64
 	refitSaid    float64        // the bound pt_set_bvh_refit was last given (0: never said, or off)
@@ -137,6 +140,7 @@ func SetDevices(n int) {
 		ctx = nil
 		idsOn, accumulated = false, nil
 		walkOn = false
+		fogWalkOn = false
 		refitSaid = 0
 		buildSaid = false
 	}
@@ -396,6 +400,15 @@ func SetFeatureWalk(on bool) {
 	walkSet, walkWanted = true, on
 }
 
+// SetFogWalk lets scenes on the BVH path (more than 128 spheres or 128 boxes) draw a gpu_volumetric fog block, the closest hit and the
+// shadow rays of the term answered by wave-shared walks of the tree (pt_set_fog_walk, DESIGN 3.7a).  The frame is the model's, bit
+// for bit, at 24 x lights shadow rays per sample.  Not set: PATHTRACER_GPU_FOG_WALK decides.
+func SetFogWalk(on bool) {
+	mu.Lock()
+	defer mu.Unlock()
+	fogWalkSet, fogWalkWanted = true, on
+}
+
 // SetBvhRefit lets a frame whose scene differs from the previous frame's only in where its objects are keep the hierarchy's topology
 // and recompute its boxes on the devices (pt_set_bvh_refit, DESIGN 3.4c).  maxGrowth >= 1 (or +Inf) bounds how far the refitted tree's
 // quality figure may exceed the built one's before the next frame rebuilds; anything below 1 is off.  Not set:
@@ -442,6 +455,18 @@ func walkRule() bool {
 		return walkWanted
 	}
 	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_FEATURE_WALK"))) {
+	case "1", "true", "on", "yes":
+		return true
+	}
+	return false
+}
+
+// fogWalkRule: whether volumetric fog on the BVH path is in force (SetFogWalk, else the environment).
+func fogWalkRule() bool {
+	if fogWalkSet {
+		return fogWalkWanted
+	}
+	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_FOG_WALK"))) {
 	case "1", "true", "on", "yes":
 		return true
 	}
@@ -982,6 +1007,16 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 			return lastError("pt_set_feature_walk")
 		}
 		walkOn = walk
+	}
+	if walk := fogWalkRule(); walk != fogWalkOn { // (the same: said only when the switch changes)
+		var w C.int32_t
+		if walk {
+			w = 1
+		}
+		if rc := C.pt_set_fog_walk(ctx, w); rc != C.PT_OK {
+			return lastError("pt_set_fog_walk")
+		}
+		fogWalkOn = walk
 	}
 	if g := refitRule(); g != refitSaid { // (the same: said only when the bound changes)
 		if rc := C.pt_set_bvh_refit(ctx, C.double(g)); rc != C.PT_OK {

@@ -270,8 +270,22 @@ int32_t pt_post_process(pt_ctx *ctx, const pt_post_config *post, const double *a
  *                           (the default).  The block is copied.
  *   pt_fog_last_stats     : what the fog kernel did in the last finished frame of ctx (zeros when it did not run).
  * Scenes on the bounding-volume-hierarchy path (more than 128 spheres or 128 boxes) refuse gpu_volumetric with
- * PT_ERR_INVALID; affect_sky alone works on every scene.  Segment and draw counts (pt_stats, nseg / ndraw) stay those of the
- * surface paths: the fog term draws from a stream of its own.
+ * PT_ERR_INVALID unless pt_set_fog_walk is on; affect_sky alone works on every scene.  Segment and draw counts (pt_stats,
+ * nseg / ndraw) stay those of the surface paths: the fog term draws from a stream of its own.
+ *   pt_set_fog_walk(ctx, on) : additive to ABI 4; default 0; PT_ERR_STATE while a frame is open.  With it on, a frame with a
+ *                           gpu_volumetric block on the bounding-volume-hierarchy path is accepted: the closest hit of a sample's
+ *                           primary ray and every shadow ray of the term are answered by one walk of the tree per wave of 64
+ *                           coherent rays (an 8 x 8 pixel block) instead of a loop over all objects, with the same
+ *                           exact tests -- the image, the sums and pt_fog_last_stats are those of the model, bit for bit.  A wave
+ *                           that holds a ray outside the range the walk was analysed for (non-finite components, an origin beyond
+ *                           3.5 scene sizes -- march points of a camera far from the scene) takes the plain loop for that turn.  The
+ *                           cost stays 24 x lights shadow rays per sample.  Frames on the other scans ignore the setting; GL shading
+ *                           on that path and injected primary rays with fog on stay refused.
+ *   pt_fog_walk_stats     : out[0] = (wave, sample) pairs of the last frame whose primary rays were walked by the wave, out[1] = those
+ *                           sent to the plain scan, out[2] = shadow turns (one march step x one light of a wave) walked, out[3] =
+ *                           those sent to the plain loop, out[4] = node visits of the shadow walks, out[5] = the deepest wave stack
+ *                           seen; summed over the devices (out[5]: their largest).  PT_ERR_STATE when the last frame did not run the
+ *                           walk.  Waits for the devices' streams.
  */
 typedef struct pt_fog {
     double density;
@@ -289,7 +303,7 @@ typedef struct pt_fog {
 } pt_fog;
 
 typedef struct pt_fog_stats {
-    double fog_ms;          /* device time inside fog_kernel (longest device) */
+    double fog_ms;          /* device time inside fog_kernel / fog_bvh_kernel (longest device) */
     int32_t fog_launches;
     int32_t reserved;
     uint64_t shadow_rays;   /* light samples that reached the occlusion test */
@@ -299,6 +313,8 @@ typedef struct pt_fog_stats {
 
 int32_t pt_set_fog(pt_ctx *ctx, const pt_fog *fog);
 int32_t pt_fog_last_stats(pt_ctx *ctx, pt_fog_stats *out);
+int32_t pt_set_fog_walk(pt_ctx *ctx, int32_t on);
+int32_t pt_fog_walk_stats(pt_ctx *ctx, uint64_t out[6]);
 
 /*
  * GL shading (additive to ABI 4): the estimator of the reference's OpenGL compute shader (rayColor and main,
@@ -445,7 +461,8 @@ int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp);
  *                             with the same tests and the same winner -- the planes and ids are those of the definition above, bit
  *                             for bit.  A wave that holds a ray outside the range the walk was analysed for (non-finite or absurd
  *                             components, an origin beyond 3.5 scene sizes) takes the plain scan for that sample.  Frames on the
- *                             other scans ignore the setting.  GL shading, and volumetric fog on that path, stay refused.
+ *                             other scans ignore the setting.  GL shading on that path stays refused; volumetric fog has a switch
+ *                             of its own (pt_set_fog_walk).
  *   pt_feature_walk_stats   : out[0] = (wave, feature sample) pairs of the last frame walked by the wave, out[1] = those sent to the
  *                             plain scan, out[2] = node visits of the walks, out[3] = the deepest wave stack seen; summed over the
  *                             devices (out[3]: their largest).  PT_ERR_STATE when the last frame did not run the walk.  Waits for

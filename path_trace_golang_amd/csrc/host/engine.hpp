@@ -147,6 +147,13 @@ bool TemporalMotionFromEnv();  // PATHTRACER_GPU_TEMPORAL_MOTION = 1 / true / on
 void SetFeatureWalk(bool on);
 bool FeatureWalk();
 bool FeatureWalkFromEnv();  // PATHTRACER_GPU_FEATURE_WALK = 1 / true / on / yes
+// Volumetric fog on the BVH path (pt_set_fog_walk): scenes beyond 128 spheres or 128 boxes draw a gpu_volumetric fog
+// block, the closest hit and the shadow rays of the term answered by wave-shared walks of the tree; the frame is the model's, bit for
+// bit, at 24 x lights shadow rays per sample.  Off unless said or PATHTRACER_GPU_FOG_WALK (FogWalkFromEnv); without it such a frame
+// is refused by the library.
+void SetFogWalk(bool on);
+bool FogWalk();
+bool FogWalkFromEnv();  // PATHTRACER_GPU_FOG_WALK = 1 / true / on / yes
 // Refit of the hierarchy on the devices (pt_set_bvh_refit): a frame whose scene differs from the previous frame's only in
 // where its objects are keeps the tree's topology and recomputes its boxes on the GPU; max_growth >= 1 (or inf) bounds how far the
 // refitted tree's quality figure may exceed the built one's before the next frame rebuilds.  0 (and anything below 1) is off, the

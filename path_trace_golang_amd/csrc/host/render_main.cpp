@@ -26,7 +26,9 @@
 // its objects are refit the hierarchy on the devices instead of rebuilding it; G bounds how far the tree may degrade before it is
 // rebuilt (pt_set_bvh_refit; also env PATHTRACER_GPU_BVH_REFIT).  -bvh-build host|device
 // chooses who builds the hierarchy when a full build is due: the host's builder (the default) or devices[0], in Morton order
-// (pt_set_bvh_build; also env PATHTRACER_GPU_BVH_BUILD).  These five flags are parsed like the others but are
+// (pt_set_bvh_build; also env PATHTRACER_GPU_BVH_BUILD).  -fog-walk (with -fog) lets a scene on the
+// bounding-volume-hierarchy path draw a gpu_volumetric fog block, its shadow rays answered by a wave-shared walk of the tree
+// (pt_set_fog_walk; also env PATHTRACER_GPU_FOG_WALK).  These six flags are parsed like the others but are
 // not in the usage text below, which stands as recorded in tests/golden/host_traces.json.
 #include <cerrno>
 #include <chrono>
@@ -82,6 +84,7 @@ struct Flags {
     double filtered_adaptive = 0;
     int pool = 1;
     bool feature_walk = false;
+    bool fog_walk = false;
     double bvh_refit = 0;
     std::string bvh_build = "host";
 };
@@ -147,7 +150,7 @@ int bad_flag(const char *fmt, const std::string &a, const std::string &b = "") {
 int parse(int argc, char **argv, Flags &f) {
     const FlagRow table[] = {
         {"gpu", BOOL, &f.gpu}, {"headless", BOOL, &f.headless}, {"scene-settings", BOOL, &f.scene_settings}, {"fog", BOOL, &f.fog},
-        {"adaptive", BOOL, &f.adaptive}, {"atrous", BOOL, &f.atrous}, {"feature-walk", BOOL, &f.feature_walk},
+        {"adaptive", BOOL, &f.adaptive}, {"atrous", BOOL, &f.atrous}, {"feature-walk", BOOL, &f.feature_walk}, {"fog-walk", BOOL, &f.fog_walk},
         {"scene", STRING, &f.scene}, {"mode", STRING, &f.mode}, {"out", STRING, &f.out}, {"shading", SHADING, &f.shading},
         {"width", INT, &f.width}, {"height", INT, &f.height}, {"spp", INT, &f.spp}, {"depth", INT, &f.depth}, {"devices", INT, &f.devices},
         {"noise-step", INT, &f.noise_step, 1, 0x7fffffffLL, 16}, {"min-spp", INT, &f.min_spp, 0, 0x7fffffffLL, 0},
@@ -233,6 +236,7 @@ int render_headless(const Flags &f) {
     engine::hip::SetAtrous(f.atrous, f.atrous_iters);
     engine::hip::SetFeatures(f.features);
     engine::hip::SetFeatureWalk(f.feature_walk);
+    engine::hip::SetFogWalk(f.fog_walk);
     engine::hip::SetBvhRefit(f.bvh_refit);
     engine::hip::SetBvhBuild(f.bvh_build == "device" ? 1 : 0);
     engine::hip::SetFilteredNoise(f.filtered_noise);
@@ -304,6 +308,7 @@ int main(int argc, char **argv) {
     engine::hip::AtrousFromEnv(f.atrous, f.atrous_iters);
     f.features = engine::hip::FeaturesFromEnv();
     f.feature_walk = engine::hip::FeatureWalkFromEnv();
+    f.fog_walk = engine::hip::FogWalkFromEnv();
     f.bvh_refit = engine::hip::BvhRefitFromEnv();
     f.bvh_build = engine::hip::BvhBuildFromEnv() ? "device" : "host";
     f.filtered_noise = engine::hip::FilteredNoiseFromEnv();

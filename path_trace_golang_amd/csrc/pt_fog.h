@@ -14,7 +14,8 @@
 //     from GL's normalised ray: len = |dir|, u = dir / len, tMax = t_hit * len if that is < 40, else 40.
 //   * Vector divisions (u, wi, the light normal) divide each component by the scalar.
 //   * The draws come from a stream of their own (fog stream below), so the surface path and its draws do not change.
-//   * Scenes on the BVH path are refused for the volumetric term (the shadow rays scan every object).
+//   * Scenes on the BVH path are refused for the volumetric term (the shadow rays scan every object) unless pt_set_fog_walk is on:
+//     then fog_bvh_kernel (pt_fog_walk.h) answers the closest hit and every shadow ray by the wave's walk of the tree.
 //
 // Fog stream: stream_init(seed_key(seed XOR PTF_STREAM_SALT), y*W + x, s) -- the salt is ASCII "FOG_STRE".  Per
 // (pixel, sample) the draws are, march step by march step and light by light in object order, u1 then u2.
@@ -282,7 +283,50 @@ PT_HD bool occluded(const ptd::DevObj *objs, int32_t nobj, const FRay &r, double
     return blocked;
 }
 
-// estimateVolumeLight, gpu.go:1208-1303, at pos for the view direction u.  Draws u1, u2 per light from rs.
+// One light's sample as seen from the march point pos (gpu.go:1222-1262): the unit direction to the sampled point, the distance, the
+// cosine at the light and the area pdf.  false: the sample adds nothing and casts no shadow ray (the skips of the shader, in its order).
+struct LightSample {
+    double w[3], dist, dist_sq, cl, pdf;
+};
+PT_HD bool light_sample(const FogLight &l, double u1, double u2, double px, double py, double pz, LightSample &s) {
+    double lp[3], ln[3];
+    sample_sphere_light(l, u1, u2, lp, ln, s.pdf);
+    if (s.pdf <= 0) return false;
+    const double tx = lp[0] - px, ty = lp[1] - py, tz = lp[2] - pz;
+    s.dist_sq = tx * tx + ty * ty + tz * tz;
+    if (s.dist_sq <= 1e-6) return false;
+    s.dist = ptm::f_sqrt(s.dist_sq);
+    s.w[0] = tx / s.dist;
+    s.w[1] = ty / s.dist;
+    s.w[2] = tz / s.dist;
+    // cosLight = max(0, n . -wi) (a NaN counts as 0); tested before the shadow ray, which gives the same result
+    s.cl = ln[0] * -s.w[0] + ln[1] * -s.w[1] + ln[2] * -s.w[2];
+    return s.cl > 0;
+}
+// The shadow ray of a sample: from pos along w, occluded by anything in [0.001, shadow_tmax].
+PT_HD double shadow_tmax(const LightSample &s) { return s.dist - 0.002; }
+
+// An unoccluded sample's term into the lights' sum (gpu.go:1275-1290), for the view direction u.
+PT_HD void light_add(const FogParams &p, const FogLight &l, const LightSample &s, const double u[3], double sum[3]) {
+    const double cos_theta = -s.w[0] * u[0] + -s.w[1] * u[1] + -s.w[2] * u[2];
+    const double phase = phase_hg(cos_theta, p.g);
+    const double geometry = s.cl / ptm::go_max(1e-6, s.dist_sq);
+    const double ipdf = ptm::go_max(1e-6, s.pdf);
+    for (int c = 0; c < 3; c++) sum[c] += l.le[c] * geometry * phase / ipdf;
+}
+
+// The lights' sum into the step's light (gpu.go:1295-1302): times two, clamped to a luminance of 500.
+PT_HD void light_total(const double sum[3], double out[3]) {
+    for (int c = 0; c < 3; c++) out[c] = sum[c] * 2.0;
+    const double lum = 0.2126 * out[0] + 0.7152 * out[1] + 0.0722 * out[2];
+    if (lum > 500.0) {
+        const double scale = 500.0 / ptm::go_max(lum, 1e-6);
+        for (int c = 0; c < 3; c++) out[c] *= scale;
+    }
+}
+
+// estimateVolumeLight, gpu.go:1208-1303, at pos for the view direction u.  Draws u1, u2 per light from rs.  (fog_bvh_kernel,
+// pt_fog_walk.h, walks the same pieces with the lanes' skips as a predicate and the shadow ray answered by the wave's tree walk.)
 PT_HD void volume_light(const FogParams &p, const ptd::DevObj *objs, int32_t nobj, const FogLight *lights, int32_t nlight,
                         double px, double py, double pz, const double u[3], uint64_t &rs, FogCount &cnt, double out[3]) {
     out[0] = out[1] = out[2] = 0;
@@ -293,31 +337,13 @@ PT_HD void volume_light(const FogParams &p, const ptd::DevObj *objs, int32_t nob
         const double u1 = ptm::stream_next(rs);
         const double u2 = ptm::stream_next(rs);
         cnt.draws += 2;
-        double lp[3], ln[3], pdf;
-        sample_sphere_light(l, u1, u2, lp, ln, pdf);
-        if (pdf <= 0) continue;
-        const double tx = lp[0] - px, ty = lp[1] - py, tz = lp[2] - pz;
-        const double dist_sq = tx * tx + ty * ty + tz * tz;
-        if (dist_sq <= 1e-6) continue;
-        const double dist = ptm::f_sqrt(dist_sq);
-        const double wx = tx / dist, wy = ty / dist, wz = tz / dist;
-        // cosLight = max(0, n . -wi) (a NaN counts as 0); tested before the shadow ray, which gives the same result
-        const double cl = ln[0] * -wx + ln[1] * -wy + ln[2] * -wz;
-        if (!(cl > 0)) continue;
+        LightSample s;
+        if (!light_sample(l, u1, u2, px, py, pz, s)) continue;
         cnt.shadow_rays++;
-        if (occluded(objs, nobj, make_fray(px, py, pz, wx, wy, wz), dist - 0.002)) continue;
-        const double cos_theta = -wx * u[0] + -wy * u[1] + -wz * u[2];
-        const double phase = phase_hg(cos_theta, p.g);
-        const double geometry = cl / ptm::go_max(1e-6, dist_sq);
-        const double ipdf = ptm::go_max(1e-6, pdf);
-        for (int c = 0; c < 3; c++) sum[c] += l.le[c] * geometry * phase / ipdf;
+        if (occluded(objs, nobj, make_fray(px, py, pz, s.w[0], s.w[1], s.w[2]), shadow_tmax(s))) continue;
+        light_add(p, l, s, u, sum);
     }
-    for (int c = 0; c < 3; c++) out[c] = sum[c] * 2.0;
-    const double lum = 0.2126 * out[0] + 0.7152 * out[1] + 0.0722 * out[2];
-    if (lum > 500.0) {
-        const double scale = 500.0 / ptm::go_max(lum, 1e-6);
-        for (int c = 0; c < 3; c++) out[c] *= scale;
-    }
+    light_total(sum, out);
 }
 
 // The march of gpu.go:1319-1340: 24 steps over [0, tmax] along the unit direction u from orig.  `rs` is the sample's fog stream.
@@ -340,16 +366,25 @@ PT_HD void fog_march(const FogParams &p, const ptd::DevObj *objs, int32_t nobj, 
     }
 }
 
+// The march's unit direction u and its length along it (gpu.go:1311-1318 on the CPU engine's ray): to the closest hit, 40 at the most.
+PT_HD double march_range(const double dir[3], bool hit, double t_hit, double u[3]) {
+    const double len = ptm::f_sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
+    u[0] = dir[0] / len;
+    u[1] = dir[1] / len;
+    u[2] = dir[2] / len;
+    double tmax = PTF_TMAX;
+    if (hit && t_hit * len < PTF_TMAX) tmax = t_hit * len;
+    return tmax;
+}
+
 // The in-scatter term of one (pixel, sample) along its primary ray (orig, dir), gpu.go:1311-1341, on the CPU engine's ray and
 // its closest hit.  `rs` is the sample's fog stream.  Adds nothing unless fog_volumetric() holds (the caller checks).
 PT_HD void fog_inscatter(const FogParams &p, const ptd::DevObj *objs, int32_t nobj, const FogLight *lights, int32_t nlight,
                          const double orig[3], const double dir[3], uint64_t rs, FogCount &cnt, double L[3]) {
     double t_hit;
     const bool hit = closest_hit(objs, nobj, make_fray(orig[0], orig[1], orig[2], dir[0], dir[1], dir[2]), t_hit);
-    const double len = ptm::f_sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
-    const double u[3] = {dir[0] / len, dir[1] / len, dir[2] / len};
-    double tmax = PTF_TMAX;
-    if (hit && t_hit * len < PTF_TMAX) tmax = t_hit * len;
+    double u[3];
+    const double tmax = march_range(dir, hit, t_hit, u);
     fog_march(p, objs, nobj, lights, nlight, orig, u, tmax, rs, cnt, L);
 }
 

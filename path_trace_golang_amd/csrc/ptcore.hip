@@ -35,6 +35,7 @@
 #include "pt_walk32.h"
 #include "pt_primary.h"
 #include "pt_feature_walk.h"
+#include "pt_fog_walk.h"
 #include "pt_math.h"
 
 using namespace ptd;
@@ -223,6 +224,7 @@ struct Device {
     EventList ev[EV_KINDS];
     DevBuf<ptf::FogLight> fog_lights;        // the frame's light list (fog on)
     DevBuf<unsigned long long> fog_counters; // [3] shadow rays, draws, march steps of the frame
+    DevBuf<unsigned long long> fog_walk_counters; // [6] pt_set_fog_walk: primary pairs walked / scanned plainly, shadow turns walked / looped plainly, node visits, deepest stack
     DevBuf<unsigned long long> walk_counters; // [4] pt_set_feature_walk: (wave, sample) pairs walked, ... scanned plainly, node visits, deepest stack
     DevBuf<ptg::GlObj> gl_objs;              // GL shading: the frame's objects, materials and light list
     DevBuf<ptg::GlMat> gl_mats;
@@ -275,6 +277,7 @@ struct Frame {
     bool halves = false;   // pt_set_halves: halves_kernel runs after every chunk's moments_kernel (pt_begin / pt_render frames only; implies moments)
     uint64_t serial = 0;   // pt_ctx::frames_opened when the frame opened: tells two frames of a context apart
     int32_t features = 0;  // pt_set_features: feature_kernel runs after the chunks that hold samples below this index (pt_begin / pt_render frames only)
+    bool fog_walk = false;      // pt_set_fog_walk on a BVH scan with fog_vol: fog_bvh_kernel (pt_fog_walk.h) in fog_kernel's place
     bool feature_walk = false;  // pt_set_feature_walk on a BVH scan: feature_bvh_kernel (pt_feature_walk.h) in feature_kernel's place
     bool object_ids = false;  // pt_set_object_ids: feature_kernel also records the object of sample 0's first hit
     int32_t scene_objects = 0;  // ... pt_scene.num_objects of the frame, the length a motion table must have
@@ -340,6 +343,7 @@ struct pt_ctx {
     bool adaptive_on = false;         // pt_set_adaptive
     int32_t features_k = 0;           // pt_set_features: feature samples per pixel (0 = off)
     DevBuf<double> g_tiles_feat, f_feat_n, f_feat_a, f_feat_d;  // pt_read_features / pt_atrous: one gathered plane, the three row-major frames
+    bool fog_walk_on = false;         // pt_set_fog_walk: the volumetric fog term on the BVH path, by the wave-shared walks
     bool feature_walk_on = false;     // pt_set_feature_walk: features on the BVH path, by the wave-shared walk
     struct Refit {  // pt_set_bvh_refit
         double max_growth = 0.0;      // 0 = off
@@ -980,6 +984,10 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
         HIP_TRY(hipMemsetAsync(d.fog_counters.p, 0, 3 * sizeof(unsigned long long), d.stream));
         if (int32_t rc = upload(d, d.fog_lights, fr.fog_lights)) return rc;
     }
+    if (fr.fog_walk) {  // the walk's counters, zeroed when the frame opens
+        HIP_TRY(d.fog_walk_counters.reserve(6));
+        HIP_TRY(hipMemsetAsync(d.fog_walk_counters.p, 0, 6 * sizeof(unsigned long long), d.stream));
+    }
     if (fr.gl) {
         HIP_TRY(d.gl_counters.reserve(5));
         HIP_TRY(hipMemsetAsync(d.gl_counters.p, 0, 5 * sizeof(unsigned long long), d.stream));
@@ -1416,6 +1424,10 @@ int32_t step_fog(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G, c
     FA.S = F.S;
     FA.s0 = F.s0;
     FA.G = G;
+    if (fr.fog_walk) {  // BVH scans with pt_set_fog_walk: the same jobs, the closest hit and the shadow rays by the wave's walks of the tree
+        const ptk::FogWalkArgs W{FA, F, d.bvh_nodes.p, d.bvh_objs.p, d.plane_idx.p, d.fog_walk_counters.p};
+        return launch_pass(d, fr.adaptive, EV_FOG, F.njobs, ptk::fog_bvh_kernel, ptk::fog_bvh_adaptive_kernel, active, W);
+    }
     return launch_pass(d, fr.adaptive, EV_FOG, F.njobs, ptk::fog_kernel, ptk::fog_adaptive_kernel, active, FA);
 }
 
@@ -1973,12 +1985,16 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
         pt_sky sky = scene->sky;
         if (ctx->fog_on) {
             fr.fog = ptf::fog_resolve(ctx->fog_raw);
-            if (fr.fog.volumetric && (sd.scan == ptk::SCAN_BVH || sd.scan == ptk::SCAN_VERIFY_BVH))
+            const bool bvh = sd.scan == ptk::SCAN_BVH || sd.scan == ptk::SCAN_VERIFY_BVH;
+            if (bvh && ctx->fog_walk_on && ctx->shading_model == PT_SHADING_GL)  // stays refused, and refused first
+                return fail(PT_ERR_INVALID, "GL shading is not available for scenes on the BVH path (more than 128 spheres or 128 boxes)");
+            if (fr.fog.volumetric && bvh && !ctx->fog_walk_on)
                 return fail(PT_ERR_INVALID, "fog: gpu_volumetric is not available for scenes on the BVH path (more than 128 spheres or "
                                             "128 boxes); affect_sky alone is");
             if (ptf::fog_sky_applies(fr.fog))  // applyFog(bg, 50), gpu.go:1392-1393, as a rewrite of the sky constants
                 for (double *c : {sky.background, sky.color, sky.horizon, sky.zenith}) ptf::fog_sky_rewrite(fr.fog, c);
             fr.fog_vol = ptf::fog_volumetric(fr.fog, cfg->max_depth);
+            fr.fog_walk = fr.fog_vol && bvh;  // (only with pt_set_fog_walk; the other scans ignore the setting)
             if (fr.fog_vol)  // the emissive spheres, in object order
                 for (int32_t i = 0; i < scene->num_objects; i++) {
                     ptf::FogLight l;
@@ -3302,6 +3318,32 @@ int32_t pt_feature_walk_stats(pt_ctx *ctx, uint64_t out[4]) {
         sum[3] = std::max<uint64_t>(sum[3], c[3]);  // the deepest stack: the largest of the devices'
     }
     for (int k = 0; k < 4; k++) out[k] = sum[k];
+    return PT_OK;
+}
+
+int32_t pt_set_fog_walk(pt_ctx *ctx, int32_t on) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_fog_walk while a frame is open");
+    ctx->fog_walk_on = on != 0;
+    return PT_OK;
+}
+
+int32_t pt_fog_walk_stats(pt_ctx *ctx, uint64_t out[6]) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!out) return fail(PT_ERR_INVALID, "pt_fog_walk_stats: out is null");
+    if (!ctx->frame.fog_walk)
+        return fail(PT_ERR_STATE, "pt_fog_walk_stats: the last frame did not run the walk (pt_set_fog_walk and a gpu_volumetric fog block on a BVH scene)");
+    uint64_t sum[6] = {0, 0, 0, 0, 0, 0};
+    for (Device &d : ctx->devs) {
+        if (d.nlocal == 0 || !d.fog_walk_counters.p) continue;
+        HIP_TRY(hipSetDevice(d.ordinal));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        unsigned long long c[6] = {};
+        HIP_TRY(hipMemcpy(c, d.fog_walk_counters.p, sizeof c, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 5; k++) sum[k] += c[k];
+        sum[5] = std::max<uint64_t>(sum[5], c[5]);  // the deepest stack: the largest of the devices'
+    }
+    for (int k = 0; k < 6; k++) out[k] = sum[k];
     return PT_OK;
 }
 

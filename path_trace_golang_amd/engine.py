@@ -67,7 +67,8 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 filtered_noise: Optional[float] = None, temporal: Optional["hip.TemporalConfig"] = None,
                 temporal_clip: Optional[float] = None, temporal_motion: Optional[bool] = None,
                 filtered_adaptive: Optional[float] = None, pool: Optional[int] = None,
-                feature_walk: Optional[bool] = None, bvh_refit: Optional[float] = None, bvh_build=None) -> dict:
+                feature_walk: Optional[bool] = None, bvh_refit: Optional[float] = None, bvh_build=None,
+                fog_walk: Optional[bool] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
@@ -97,7 +98,9 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     scene differs from the previous frame's only in where its objects are refits the hierarchy on the devices; None takes
     PATHTRACER_GPU_BVH_REFIT=<G> (hip.bvh_refit_from_env), off by default.  `bvh_build` is hip.render's: "device" builds
     the hierarchy on devices[0] whenever a full build is due; None takes PATHTRACER_GPU_BVH_BUILD=host|device (hip.bvh_build_from_env),
-    host by default."""
+    host by default.  `fog_walk` is hip.render's: a gpu_volumetric fog block on scenes that take the bounding-volume
+    hierarchy, the shadow rays answered by the wave's walk of the tree; None takes PATHTRACER_GPU_FOG_WALK=1 (hip.fog_walk_from_env),
+    off by default."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -143,6 +146,10 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
         bvh_build = hip.bvh_build_from_env()
     if bvh_build:  # (the same)
         walk["bvh_build"] = bvh_build
+    if fog_walk is None:
+        fog_walk = hip.fog_walk_from_env()
+    if fog_walk:  # (the same)
+        walk["fog_walk"] = True
     motion = {}
     if temporal is not None and temporal_motion:
         motion = _motion_for(sc)

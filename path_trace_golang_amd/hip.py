@@ -353,6 +353,35 @@ def feature_walk_from_env(environ=None) -> bool:
     return _env_on(environ, "PATHTRACER_GPU_FEATURE_WALK")
 
 
+def set_fog_walk(ctx: capi.Context, on: bool) -> None:
+    """pt_set_fog_walk: later frames on ctx with a gpu_volumetric fog block are accepted on the bounding-volume-hierarchy path too,
+    the closest hit and every shadow ray of the term answered by one walk of the tree per 8x8 block.  A library without
+    the entry point takes False only."""
+    if not capi.has("pt_set_fog_walk"):
+        if on:
+            raise RuntimeError("this libptcore.so has no pt_set_fog_walk (rebuild it)")
+        return
+    capi.check(capi.load().pt_set_fog_walk(ctx.handle, 1 if on else 0))
+    ctx._fog_walk_on = bool(on)  # what `render` compares with: it says the setting only when it changes
+
+
+def fog_walk_stats(ctx: capi.Context) -> dict:
+    """pt_fog_walk_stats of the last frame: (wave, sample) pairs whose primary rays the wave walked and those sent to the plain scan,
+    shadow turns (one march step x one light of a wave) walked and sent to the plain loop, the shadow walks' node visits, the
+    deepest wave stack."""
+    if not capi.has("pt_fog_walk_stats"):
+        raise RuntimeError("this libptcore.so has no pt_fog_walk_stats (rebuild it)")
+    out = (C.c_uint64 * 6)()
+    capi.check(capi.load().pt_fog_walk_stats(ctx.handle, out))
+    return {"primary_walked": int(out[0]), "primary_plain": int(out[1]), "shadow_walked": int(out[2]), "shadow_plain": int(out[3]),
+            "node_visits": int(out[4]), "deepest_stack": int(out[5])}
+
+
+def fog_walk_from_env(environ=None) -> bool:
+    """PATHTRACER_GPU_FOG_WALK=1 (or true / on / yes): volumetric fog on the bounding-volume-hierarchy path (pt_set_fog_walk)."""
+    return _env_on(environ, "PATHTRACER_GPU_FOG_WALK")
+
+
 def set_bvh_refit(ctx: capi.Context, max_growth: float) -> None:
     """pt_set_bvh_refit: with max_growth >= 1 (or inf) a later frame on ctx whose scene differs from the previous
     frame's only in where its objects are and how large (planes included; types, materials and the count stay) keeps the
@@ -866,7 +895,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            filtered_noise: Optional[float] = None, halves: bool = False,
            temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None,
            object_ids: bool = False, temporal_motion=None, filtered_adaptive: Optional[float] = None, pool: int = 1,
-           feature_walk: bool = False, bvh_refit: Optional[float] = None, bvh_build=None) -> dict:
+           feature_walk: bool = False, bvh_refit: Optional[float] = None, bvh_build=None, fog_walk: bool = False) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -924,6 +953,10 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     feature_walk_stats(ctx) afterwards says what the walk did): atrous=, temporal= and object_ids= then work there as on the small
     scenes.  Without it such a scene has features refused, and atrous= alone filters it with k = 0.
 
+    fog_walk=True lets a scene on the bounding-volume-hierarchy path render a gpu_volumetric fog block
+    (pt_set_fog_walk; fog_walk_stats(ctx) afterwards says what the walks did).  The frame is the model's, bit for bit; the cost
+    stays 24 x lights shadow rays per sample.  Without it such a frame is refused.
+
     bvh_refit=G (G >= 1 or inf, 0 = off) lets a frame whose scene differs from the context's previous frame only in
     where its objects are refit the bounding-volume hierarchy on the devices instead of rebuilding it on the host
     (pt_set_bvh_refit; bvh_refit_stats(ctx) afterwards says what happened).  The frame is the one a rebuild gives, bit for bit.
@@ -969,6 +1002,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
         raise ValueError("img rows must be contiguous RGBA")
     flat = sc if isinstance(sc, FlatScene) else FlatScene(sc)  # callers that render one scene repeatedly flatten it once
     set_fog(ctx, getattr(sc, "fog", None) if fog else None)
+    if bool(fog_walk) != getattr(ctx, "_fog_walk_on", False):  # (said only when it changes: with it never on, the calls are what they were)
+        set_fog_walk(ctx, bool(fog_walk))
     if shading != "cpu" or capi.has("pt_set_shading"):
         set_shading(ctx, shading, sc)
     if adaptive and noise is None:
