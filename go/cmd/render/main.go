@@ -48,6 +48,7 @@ func main() {
 	bvhBuild := flag.String("bvh-build", "host", "who builds the bounding-volume hierarchy when a full build is due: host, or device (the GPU, in Morton order; or PATHTRACER_GPU_BVH_BUILD)")
 	featureWalk := flag.Bool("feature-walk", false, "collect features on scenes beyond 128 spheres or 128 boxes too, by a wave-shared walk of the tree (or PATHTRACER_GPU_FEATURE_WALK)")
 	fogWalk := flag.Bool("fog-walk", false, "with -fog: draw a gpu_volumetric fog block on scenes beyond 128 spheres or 128 boxes too, the shadow rays by a wave-shared walk of the tree (or PATHTRACER_GPU_FOG_WALK)")
+	shadingWalk := flag.Bool("shading-walk", false, "with -shading gl: render scenes beyond 128 spheres or 128 boxes too, the model's ray queries by the lane's own walk of the tree (or PATHTRACER_GPU_SHADING_WALK)")
 	flag.Parse()
 	log.Printf("flags: scene=%s mode=%s headless=%v out=%s\n", *scenePath, *mode, *headless, *output)
 
@@ -85,6 +86,11 @@ func main() {
 		flag.Visit(func(f *flag.Flag) { fogWalkGiven = fogWalkGiven || f.Name == "fog-walk" })
 		if fogWalkGiven { // else the environment decides
 			hip.SetFogWalk(*fogWalk)
+		}
+		shadingWalkGiven := false
+		flag.Visit(func(f *flag.Flag) { shadingWalkGiven = shadingWalkGiven || f.Name == "shading-walk" })
+		if shadingWalkGiven { // else the environment decides
+			hip.SetShadingWalk(*shadingWalk)
 		}
 		refitGiven := false
 		flag.Visit(func(f *flag.Flag) { refitGiven = refitGiven || f.Name == "bvh-refit" })

@@ -80,6 +80,9 @@ var (
 	fogWalkSet    bool          // false: PATHTRACER_GPU_FOG_WALK decides
 	fogWalkWanted bool
 	fogWalkOn     bool          // pt_set_fog_walk(1) was the last thing said to the context
+	shadingWalkSet    bool      // false: PATHTRACER_GPU_SHADING_WALK decides
+	shadingWalkWanted bool
+	shadingWalkOn     bool      // pt_set_shading_walk(1) was the last thing said to the context
 	refitSet     bool           // false: PATHTRACER_GPU_BVH_REFIT decides
 	refitWanted  float64
 	refitSaid    float64        // the bound pt_set_bvh_refit was last given (0: never said, or off)
@@ -141,6 +144,7 @@ func SetDevices(n int) {
 		idsOn, accumulated = false, nil
 		walkOn = false
 		fogWalkOn = false
+		shadingWalkOn = false
 		refitSaid = 0
 		buildSaid = false
 	}
@@ -409,6 +413,15 @@ func SetFogWalk(on bool) {
 	fogWalkSet, fogWalkWanted = true, on
 }
 
+// SetShadingWalk lets scenes on the BVH path (more than 128 spheres or 128 boxes) render with the GL model, every closest hit,
+// shadow ray and metal probe answered by the lane's own walk of the tree (pt_set_shading_walk, DESIGN 3.8a).  The frame is the
+// model's, bit for bit.  Not set: PATHTRACER_GPU_SHADING_WALK decides.
+func SetShadingWalk(on bool) {
+	mu.Lock()
+	defer mu.Unlock()
+	shadingWalkSet, shadingWalkWanted = true, on
+}
+
 // SetBvhRefit lets a frame whose scene differs from the previous frame's only in where its objects are keep the hierarchy's topology
 // and recompute its boxes on the devices (pt_set_bvh_refit, DESIGN 3.4c).  maxGrowth >= 1 (or +Inf) bounds how far the refitted tree's
 // quality figure may exceed the built one's before the next frame rebuilds; anything below 1 is off.  Not set:
@@ -467,6 +480,18 @@ func fogWalkRule() bool {
 		return fogWalkWanted
 	}
 	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_FOG_WALK"))) {
+	case "1", "true", "on", "yes":
+		return true
+	}
+	return false
+}
+
+// shadingWalkRule: whether GL shading on the BVH path is in force (SetShadingWalk, else the environment).
+func shadingWalkRule() bool {
+	if shadingWalkSet {
+		return shadingWalkWanted
+	}
+	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_SHADING_WALK"))) {
 	case "1", "true", "on", "yes":
 		return true
 	}
@@ -1017,6 +1042,16 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 			return lastError("pt_set_fog_walk")
 		}
 		fogWalkOn = walk
+	}
+	if walk := shadingWalkRule(); walk != shadingWalkOn { // (the same)
+		var w C.int32_t
+		if walk {
+			w = 1
+		}
+		if rc := C.pt_set_shading_walk(ctx, w); rc != C.PT_OK {
+			return lastError("pt_set_shading_walk")
+		}
+		shadingWalkOn = walk
 	}
 	if g := refitRule(); g != refitSaid { // (the same: said only when the bound changes)
 		if rc := C.pt_set_bvh_refit(ctx, C.double(g)); rc != C.PT_OK {

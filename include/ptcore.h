@@ -280,7 +280,8 @@ int32_t pt_post_process(pt_ctx *ctx, const pt_post_config *post, const double *a
  *                           that holds a ray outside the range the walk was analysed for (non-finite components, an origin beyond
  *                           3.5 scene sizes -- march points of a camera far from the scene) takes the plain loop for that turn.  The
  *                           cost stays 24 x lights shadow rays per sample.  Frames on the other scans ignore the setting; GL shading
- *                           on that path and injected primary rays with fog on stay refused.
+ *                           on that path stays refused unless pt_set_shading_walk (which refuses gpu_volumetric there); injected
+ *                           primary rays with fog on stay refused.
  *   pt_fog_walk_stats     : out[0] = (wave, sample) pairs of the last frame whose primary rays were walked by the wave, out[1] = those
  *                           sent to the plain scan, out[2] = shadow turns (one march step x one light of a wave) walked, out[3] =
  *                           those sent to the plain loop, out[4] = node visits of the shadow walks, out[5] = the deepest wave stack
@@ -329,7 +330,24 @@ int32_t pt_fog_walk_stats(pt_ctx *ctx, uint64_t out[6]);
  * finish of pt_post_process(tonemap = 1) on accum.  pt_stats.samples, segments and draws count GL paths, closest-hit scans
  * and draws; trace_ms is the GL kernel's time.  A GL render returns PT_ERR_INVALID without launching anything when the
  * scene's material count differs from num_materials, with PT_FLAG_PIXEL_STATS, and for scenes on the bounding-volume-
- * hierarchy path (more than 128 spheres or 128 boxes).
+ * hierarchy path (more than 128 spheres or 128 boxes) unless pt_set_shading_walk is on.
+ *   pt_set_shading_walk(ctx, on) : additive to ABI 4; default 0; PT_ERR_STATE while a frame is open.  With it on, a GL frame on
+ *                             the bounding-volume-hierarchy path is accepted: every segment's closest hit, every shadow ray and
+ *                             every metal probe is answered by the lane's own walk of the tree (csrc/pt_gl_walk.h, DESIGN.md
+ *                             3.8a) instead of a loop over all objects, with the same exact tests and the loop's winner under
+ *                             GL's tie rule -- the image, the sums and pt_shading_last_stats are those of the model, bit for
+ *                             bit.  A query whose ray lies outside the range the walk was analysed for (non-finite components,
+ *                             an origin beyond 3.5 scene sizes) takes the plain loop, per lane and per query.  Frames on the
+ *                             other scans ignore the setting.  Refused on that path, each with PT_ERR_INVALID or PT_ERR_STATE
+ *                             and a message of its own: a scene with an object of unknown type (or one whose GL objects are not
+ *                             the tree's: the message names the object and the rule), a gpu_volumetric fog block (its march
+ *                             still loops over all objects; affect_sky alone is accepted), PT_FLAG_PIXEL_STATS, features,
+ *                             adaptive sampling and injected primary rays.
+ *   pt_shading_walk_stats   : out[0] = closest-hit queries of the last frame answered by a walk, out[1] = those sent to the plain
+ *                             loop, out[2] = shadow queries walked, out[3] = those sent to the plain loop, out[4] = node visits
+ *                             of the closest walks, out[5] = of the shadow walks, out[6] = the deepest stack seen; summed over the
+ *                             devices (out[6]: their largest).  PT_ERR_STATE when the last frame did not run the walk.  Waits for
+ *                             the devices' streams.
  */
 enum { PT_SHADING_CPU = 0, PT_SHADING_GL = 1 };
 
@@ -347,7 +365,7 @@ typedef struct pt_shading {
 } pt_shading;
 
 typedef struct pt_shading_stats {
-    double gl_ms;          /* device time inside gl_trace_kernel (longest device) */
+    double gl_ms;          /* device time inside gl_trace_kernel / gl_bvh_kernel (longest device) */
     int32_t gl_launches;
     int32_t reserved;
     uint64_t paths;        /* GL paths traced (16 per pixel and pass) */
@@ -359,6 +377,8 @@ typedef struct pt_shading_stats {
 
 int32_t pt_set_shading(pt_ctx *ctx, const pt_shading *s);
 int32_t pt_shading_last_stats(pt_ctx *ctx, pt_shading_stats *out);
+int32_t pt_set_shading_walk(pt_ctx *ctx, int32_t on);
+int32_t pt_shading_walk_stats(pt_ctx *ctx, uint64_t out[7]);
 
 /*
  * Second moments and the frame noise figure (additive to ABI 4).  Off unless asked for: with moments off
@@ -461,8 +481,8 @@ int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp);
  *                             with the same tests and the same winner -- the planes and ids are those of the definition above, bit
  *                             for bit.  A wave that holds a ray outside the range the walk was analysed for (non-finite or absurd
  *                             components, an origin beyond 3.5 scene sizes) takes the plain scan for that sample.  Frames on the
- *                             other scans ignore the setting.  GL shading on that path stays refused; volumetric fog has a switch
- *                             of its own (pt_set_fog_walk).
+ *                             other scans ignore the setting.  GL shading on that path stays refused unless pt_set_shading_walk;
+ *                             volumetric fog has a switch of its own (pt_set_fog_walk).
  *   pt_feature_walk_stats   : out[0] = (wave, feature sample) pairs of the last frame walked by the wave, out[1] = those sent to the
  *                             plain scan, out[2] = node visits of the walks, out[3] = the deepest wave stack seen; summed over the
  *                             devices (out[3]: their largest).  PT_ERR_STATE when the last frame did not run the walk.  Waits for

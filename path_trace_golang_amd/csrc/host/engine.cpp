@@ -61,7 +61,8 @@ namespace {
     OPTIONAL(pt_temporal) OPTIONAL(pt_temporal_reset) OPTIONAL(pt_temporal_set_clip) OPTIONAL(pt_temporal_clip_stats)           \
     OPTIONAL(pt_set_object_ids) OPTIONAL(pt_temporal_set_motion) OPTIONAL(pt_temporal_motion_stats)                              \
     OPTIONAL(pt_set_adaptive_filtered) OPTIONAL(pt_read_block_figures) OPTIONAL(pt_set_feature_walk) \
-    OPTIONAL(pt_set_bvh_refit) OPTIONAL(pt_set_bvh_build) OPTIONAL(pt_set_fog_walk)
+    OPTIONAL(pt_set_bvh_refit) OPTIONAL(pt_set_bvh_build) OPTIONAL(pt_set_fog_walk) \
+    OPTIONAL(pt_set_shading_walk)
 
 struct Core {
     void *handle = nullptr;
@@ -72,7 +73,7 @@ struct Core {
 };
 
 // What a frame setting needs from the library beyond the required entry points, and what Render answers when it is not there.
-enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE, FEATURE_WALK, BVH_REFIT, BVH_BUILD, FOG_WALK };
+enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE, FEATURE_WALK, BVH_REFIT, BVH_BUILD, SHADING_WALK, FOG_WALK };
 const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_shading != nullptr; }, "GL shading: libptcore.so lacks pt_set_shading"},
     {[](const Core &c) { return c.pt_set_moments && c.pt_noise_estimate; }, "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate"},
@@ -89,6 +90,7 @@ const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_feature_walk != nullptr; }, "feature walk: libptcore.so lacks pt_set_feature_walk"},
     {[](const Core &c) { return c.pt_set_bvh_refit != nullptr; }, "BVH refit: libptcore.so lacks pt_set_bvh_refit"},
     {[](const Core &c) { return c.pt_set_bvh_build != nullptr; }, "BVH device build: libptcore.so lacks pt_set_bvh_build"},
+    {[](const Core &c) { return c.pt_set_shading_walk != nullptr; }, "shading walk: libptcore.so lacks pt_set_shading_walk"},
     {[](const Core &c) { return c.pt_set_fog_walk != nullptr; }, "fog walk: libptcore.so lacks pt_set_fog_walk"},
 };
 
@@ -97,7 +99,7 @@ struct NoiseRule { double target; int step; };
 struct Switch { bool on; int n; };  // adaptive + min_spp, a-trous + iterations
 struct BlockRule { double target; int pool; };
 struct Settings {
-    std::optional<bool> fog, temporal, temporal_motion, feature_walk, fog_walk;
+    std::optional<bool> fog, temporal, temporal_motion, feature_walk, fog_walk, shading_walk;
     std::optional<int> shading, features, bvh_build;
     std::optional<NoiseRule> noise;
     std::optional<Switch> adaptive, atrous;
@@ -328,6 +330,7 @@ double TemporalClipFromEnv() { return env_double("PATHTRACER_GPU_TEMPORAL_CLIP",
 bool TemporalMotionFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL_MOTION"); }
 bool FeatureWalkFromEnv() { return env_switch("PATHTRACER_GPU_FEATURE_WALK"); }
 bool FogWalkFromEnv() { return env_switch("PATHTRACER_GPU_FOG_WALK"); }
+bool ShadingWalkFromEnv() { return env_switch("PATHTRACER_GPU_SHADING_WALK"); }
 int BvhBuildFromEnv() {  // PATHTRACER_GPU_BVH_BUILD=host|device: anything else is host
     const char *e = std::getenv("PATHTRACER_GPU_BVH_BUILD");
     return e && std::string(e) == "device" ? 1 : 0;
@@ -353,6 +356,7 @@ struct FramePlan {
     int features;
     bool walk;            // features on the BVH path too (pt_set_feature_walk)
     bool fog_walk;        // volumetric fog on the BVH path too (pt_set_fog_walk)
+    bool shading_walk;    // GL shading on the BVH path too (pt_set_shading_walk)
     double refit;         // >= 1: the growth bound of pt_set_bvh_refit; 0: off
     int build;            // the mode of pt_set_bvh_build: 0 host, 1 device
     bool moments, halves;
@@ -397,6 +401,7 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
     p.features = s.features.value_or(FeaturesFromEnv());
     p.walk = s.feature_walk.value_or(FeatureWalkFromEnv());
     p.fog_walk = s.fog_walk.value_or(FogWalkFromEnv());
+    p.shading_walk = s.shading_walk.value_or(ShadingWalkFromEnv());
     p.refit = s.bvh_refit.value_or(BvhRefitFromEnv());
     p.build = s.bvh_build.value_or(BvhBuildFromEnv());
     if (p.features < 0 && p.temporal) p.features = 4;  // (pt_temporal needs them: where the frame refuses features, pt_begin says so)
@@ -432,6 +437,7 @@ bool g_object_ids_on = false;  // pt_set_object_ids(1) was the last thing said t
 bool g_block_rule_on = false;  // pt_set_adaptive_filtered(&f) was the last thing said to the context
 bool g_feature_walk_on = false;  // pt_set_feature_walk(1) was the last thing said to the context
 bool g_fog_walk_on = false;      // pt_set_fog_walk(1) was the last thing said to the context
+bool g_shading_walk_on = false;  // pt_set_shading_walk(1) was the last thing said to the context
 double g_bvh_refit = 0;          // the bound pt_set_bvh_refit was last given (0: never said, or off)
 int g_bvh_build = 0;             // the mode pt_set_bvh_build was last given (0: never said, or host)
 
@@ -444,6 +450,7 @@ void drop_context() {
     g_block_rule_on = false;
     g_feature_walk_on = false;
     g_fog_walk_on = false;
+    g_shading_walk_on = false;
     g_bvh_refit = 0;
     g_bvh_build = 0;
 }
@@ -610,6 +617,14 @@ bool FogWalk() {
     std::lock_guard<std::mutex> lk(g_mu);
     return g_set.fog_walk.value_or(FogWalkFromEnv());
 }
+void SetShadingWalk(bool on) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_set.shading_walk = on;
+}
+bool ShadingWalk() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_set.shading_walk.value_or(ShadingWalkFromEnv());
+}
 void SetBvhRefit(double max_growth) {
     std::lock_guard<std::mutex> lk(g_mu);
     g_set.bvh_refit = max_growth >= 1.0 ? max_growth : 0.0;
@@ -711,6 +726,11 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (p.fog_walk != g_fog_walk_on) {  // (the same: said only when the switch changes)
         if (failed(PT_CALL(pt_set_fog_walk, g_ctx, p.fog_walk ? 1 : 0))) return err;
         g_fog_walk_on = p.fog_walk;
+    }
+    if (lacks(p.shading_walk, SHADING_WALK)) return missing;
+    if (p.shading_walk != g_shading_walk_on) {  // (the same)
+        if (failed(PT_CALL(pt_set_shading_walk, g_ctx, p.shading_walk ? 1 : 0))) return err;
+        g_shading_walk_on = p.shading_walk;
     }
     if (g_core.pt_set_features && failed(PT_CALL(pt_set_features, g_ctx, p.features))) return err;
     if (p.motion != g_object_ids_on) {  // (said only when the switch changes: with it never on, the calls are what they were)

@@ -154,6 +154,12 @@ bool FeatureWalkFromEnv();  // PATHTRACER_GPU_FEATURE_WALK = 1 / true / on / yes
 void SetFogWalk(bool on);
 bool FogWalk();
 bool FogWalkFromEnv();  // PATHTRACER_GPU_FOG_WALK = 1 / true / on / yes
+// GL shading on the BVH path (pt_set_shading_walk): scenes beyond 128 spheres or 128 boxes render with the GL model,
+// its closest hits, shadow rays and metal probes answered by the lane's own walk of the tree; the frame is the model's, bit for
+// bit.  Off unless said or PATHTRACER_GPU_SHADING_WALK (ShadingWalkFromEnv); without it such a frame is refused by the library.
+void SetShadingWalk(bool on);
+bool ShadingWalk();
+bool ShadingWalkFromEnv();  // PATHTRACER_GPU_SHADING_WALK = 1 / true / on / yes
 // Refit of the hierarchy on the devices (pt_set_bvh_refit): a frame whose scene differs from the previous frame's only in
 // where its objects are keeps the tree's topology and recomputes its boxes on the GPU; max_growth >= 1 (or inf) bounds how far the
 // refitted tree's quality figure may exceed the built one's before the next frame rebuilds.  0 (and anything below 1) is off, the

@@ -336,6 +336,34 @@ inline double scene_margin(const std::vector<DevObj> &w) {
     return Bnd * (1.0 / 4096.0);
 }
 
+// B bounds every finite object's coordinates (scene_prepare's build_broad; a host build of a walk takes it from here too).
+inline double world_bound(const std::vector<DevObj> &world) {
+    double B = 1.0;
+    for (const DevObj &o : world) {
+        const int kind = o.kind & 0xff;
+        if (kind == KIND_SPHERE) {
+            for (int k = 0; k < 3; k++) B = std::max(B, std::fabs(o.a[k]) + std::fabs(o.radius));
+        } else if (kind == KIND_BOX) {
+            for (int k = 0; k < 3; k++) B = std::max(B, std::max(std::fabs(o.a[k]), std::fabs(o.b[k])));
+        }
+    }
+    if (!(B < 1e30)) B = INFINITY;  // absurd or non-finite geometry: every object stays a candidate
+    return B;
+}
+// ... and the fields of DevFrame the FP32 tests derive from it.
+inline void frame_bounds(double B, DevFrame &F) {
+    F.origin_bound = (float)std::min(4.0 * B, 3.0e38);
+    // With |1/d| (4 origin_bound) < 3e38 no product of a slab test (a centre, a half extent or an origin within origin_bound times
+    // 1/d) leaves the finite range, nor does their sum.  A smaller component is taken for zero, whose slab constrains nothing (the
+    // walks of the hierarchy, the grouped scan), or the ray keeps every box (the scan of at most 32 records): a
+    // product past FLT_MAX is an INFINITY, not a NaN, and tf = -inf culled boxes the ray goes through (B = 8: 4.3e-37; from
+    // B = 2^61 on a component of 2^-60 is below it; in the keep-everything band every component is).
+    F.dir_floor = detail::up(4.0 * (double)F.origin_bound / 3.0e38);
+    F.scene_bound = B * (1.0 + 1.0 / 512.0);  // the inflation is B/4096
+    F.clip_bound = B * 3.5;
+    F.margin = B * (1.0 / 4096.0);
+}
+
 // The walk of scan_bvh reads the first 96 bytes of a node only (six 16-byte requests per lane and visit instead of seven: the
 // CU's address unit, not the caches, is what its visits wait for -- DESIGN 10.3): node_base, obj_base and meta ride in the LOW BYTES
 // of the twelve half extents, which are rounded up to a multiple of 256 ulp first (they only ever had to be upper bounds).

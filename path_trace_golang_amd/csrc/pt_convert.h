@@ -1,8 +1,9 @@
-// pt_convert.h -- host-side conversion of a scene material to the device record (included by ptcore.hip; tests build it for
+// pt_convert.h -- host-side conversion of a scene's materials and objects to the device records (included by ptcore.hip; tests build it for
 // the host with g++ -ffp-contract=off and for the device probe, so that what they check is this text and not a copy).
 #pragma once
 
 #include <cstring>
+#include <vector>
 
 #include "../../include/ptcore.h"
 #include "pt_device.h"
@@ -62,6 +63,50 @@ inline DevMat convert_material(const pt_material &m) {  // materials.go:28-55
     r.absorbs = (r.absorption[0] > 0 || r.absorption[1] > 0 || r.absorption[2] > 0) ? 1 : 0;
     r.rough_sq = r.rough * r.rough;
     return r;
+}
+
+// objects.go:225-269; materials are converted once and indexed (the zero material
+// of a missing id is slot num_materials)
+inline void scene_to_world(const pt_scene &sc, std::vector<DevObj> &world, std::vector<DevMat> &mats) {
+    mats.clear();
+    for (int i = 0; i < sc.num_materials; i++) mats.push_back(convert_material(sc.materials[i]));
+    DevMat zero;
+    std::memset(&zero, 0, sizeof zero);
+    mats.push_back(zero);
+    world.clear();
+    for (int i = 0; i < sc.num_objects; i++) {
+        const pt_object &o = sc.objects[i];
+        DevObj d;
+        std::memset(&d, 0, sizeof d);
+        d.mat = (o.material >= 0 && o.material < sc.num_materials) ? o.material : sc.num_materials;
+        int kind;
+        switch (o.type) {
+            case PT_OBJ_SPHERE:
+            case PT_OBJ_SPHERE_LIGHT:
+                kind = KIND_SPHERE;
+                for (int k = 0; k < 3; k++) d.a[k] = o.position[k];
+                d.radius = o.size[0];
+                d.radius_sq = d.radius * d.radius;
+                d.inv_radius = 1.0 / d.radius;
+                break;
+            case PT_OBJ_PLANE:
+                kind = KIND_PLANE;
+                for (int k = 0; k < 3; k++) d.a[k] = o.position[k];
+                d.b[0] = 0; d.b[1] = 1; d.b[2] = 0;
+                break;
+            case PT_OBJ_BOX:
+                kind = KIND_BOX;
+                for (int k = 0; k < 3; k++) {
+                    d.a[k] = o.position[k] - o.size[k] * 0.5;
+                    d.b[k] = o.position[k] + o.size[k] * 0.5;
+                }
+                break;
+            default:
+                continue;  // unknown types are skipped
+        }
+        d.kind = kind | (mats[(size_t)d.mat].typ == MAT_DIELECTRIC ? 0x100 : 0);
+        world.push_back(d);
+    }
 }
 
 }  // namespace ptd

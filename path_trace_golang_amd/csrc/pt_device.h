@@ -20,6 +20,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#define PT_BVH_STACK 96  // upper bound of the per-lane traversal stack (sized per scene from the tree)
+
 namespace ptd {
 
 enum { KIND_SPHERE = 0, KIND_PLANE = 1, KIND_BOX = 2 };

@@ -3,7 +3,9 @@
 //
 // Opt-in per context (pt_set_shading); the CPU engine's image stays the default.  Everything here is PT_HD and built from
 // IEEE +,-,*,/, sqrt and the Go routines of pt_math.h (compile with -ffp-contract=off), so the gfx950 kernel
-// (gl_trace_kernel, pt_kernels.h) and a host build of this header give the same bits.
+// (gl_trace_kernel, pt_kernels.h) and a host build of this header give the same bits.  The model asks the scene two things -- the
+// closest hit of a ray and whether a shadow ray is blocked -- through a "world" policy (a template parameter of ray_color and gl_pass):
+// LinearWorld below is the loop over all objects, ptg::TreeWorld (pt_gl_walk.h, gl_bvh_kernel) a walk of the hierarchy.
 //
 // The shader, as the host drives it (uSamplesPerPx = 1 per dispatch, :2214-2216), traces 16 stratified paths per pixel and
 // pass and adds them WITHOUT dividing by 16 (samplesPerStratum = max(1, 1/16) = 1, col /= uSamplesPerPx = 1, :1685-1732).  A
@@ -319,6 +321,18 @@ PT_HD bool occluded(const GlObj *objs, int32_t nobj, const double ro[3], const d
     return blocked;
 }
 
+// The two ray queries of the model as a "world" policy: ray_color and gl_pass below take them through a template parameter.  This
+// one is the loop over all objects, what the non-template ray_color and gl_pass use; ptg::TreeWorld (pt_gl_walk.h) answers the same
+// queries by a walk of the resident hierarchy, bit for bit.
+struct LinearWorld {
+    const GlObj *objs;
+    int32_t nobj;
+    PT_HD int32_t closest(const double ro[3], const double rd[3], double tmin, double tmax_start, int32_t skip, double &t_hit) const {
+        return ptg::closest(objs, nobj, ro, rd, tmin, tmax_start, skip, t_hit);
+    }
+    PT_HD bool occluded(const double ro[3], const double rd[3], double tmax) const { return ptg::occluded(objs, nobj, ro, rd, tmax); }
+};
+
 // ---------------------------------------------------------------- the scene as the kernel sees it
 struct GlScene {
     const GlObj *objs;
@@ -337,7 +351,8 @@ struct GlScene {
 };
 
 // sampleLightGeometry + estimateDirectLightSingle (gpu.go:866-990) for light object `li`.
-PT_HD void direct_single(const GlScene &S, int32_t li, const GlHit &h, const double albedo[3], uint64_t &rs, GlCount &cnt,
+template <typename W>
+PT_HD void direct_single(const GlScene &S, const W &world, int32_t li, const GlHit &h, const double albedo[3], uint64_t &rs, GlCount &cnt,
                          double out[3]) {
     out[0] = out[1] = out[2] = 0.0;
     const GlObj &o = S.objs[li];
@@ -370,7 +385,7 @@ PT_HD void direct_single(const GlScene &S, int32_t li, const GlHit &h, const dou
     if (cos_s <= 0.0 || cos_l <= 0.0) return;
     const double so[3] = {h.p[0] + h.n[0] * 0.001, h.p[1] + h.n[1] * 0.001, h.p[2] + h.n[2] * 0.001};
     cnt.shadow_rays++;
-    if (occluded(S.objs, S.nobj, so, wi, dist - 0.002)) return;
+    if (world.occluded(so, wi, dist - 0.002)) return;
     const double inv_dsq = 1.0 / gmax(1e-6, dsq);
     const double inv_pdf = 1.0 / gmax(1e-6, pdf);
     const double geom = (cos_s * cos_l) * inv_dsq;
@@ -385,7 +400,8 @@ PT_HD void direct_single(const GlScene &S, int32_t li, const GlHit &h, const dou
 }
 
 // estimateDirectLight, gpu.go:995-1090: every light, or 8 from startIdx when there are more, scaled.
-PT_HD void direct_light(const GlScene &S, const GlHit &h, const double albedo[3], uint64_t &rs, GlCount &cnt, double out[3]) {
+template <typename W>
+PT_HD void direct_light(const GlScene &S, const W &world, const GlHit &h, const double albedo[3], uint64_t &rs, GlCount &cnt, double out[3]) {
     out[0] = out[1] = out[2] = 0.0;
     const int32_t L = S.nlight;
     if (L == 0) return;
@@ -404,7 +420,7 @@ PT_HD void direct_light(const GlScene &S, const GlHit &h, const double albedo[3]
         int32_t i = start + j;
         if (i >= L) i -= L;
         double c[3];
-        direct_single(S, S.lights[i], h, albedo, rs, cnt, c);
+        direct_single(S, world, S.lights[i], h, albedo, rs, cnt, c);
         for (int k = 0; k < 3; k++) tot[k] = tot[k] + c[k];
     }
     if (subset)
@@ -509,8 +525,10 @@ PT_HD void background(const GlSky &s, const double rd[3], double o[3]) {
     }
 }
 
-// rayColor, gpu.go:1300-1670, from the primary ray (ro, rd) with the path's stream; `L` starts at the fog term.
-PT_HD void ray_color(const GlScene &S, double ro[3], double rd[3], uint64_t &rs, GlCount &cnt, double L[3]) {
+// rayColor, gpu.go:1300-1670, from the primary ray (ro, rd) with the path's stream; `L` starts at the fog term.  `world` answers
+// the segment's closest hit, the shadow rays and the metal probe.
+template <typename W>
+PT_HD void ray_color(const GlScene &S, const W &world, double ro[3], double rd[3], uint64_t &rs, GlCount &cnt, double L[3]) {
     double thr[3] = {1.0, 1.0, 1.0};
     int32_t depth = S.max_depth;
     int32_t glass = -1;     // currentGlassObject
@@ -518,7 +536,7 @@ PT_HD void ray_color(const GlScene &S, double ro[3], double rd[3], uint64_t &rs,
     while (depth > 0) {
         cnt.segments++;
         double th;
-        const int32_t hi = closest(S.objs, S.nobj, ro, rd, 0.001, 1e20, glass, th);
+        const int32_t hi = world.closest(ro, rd, 0.001, 1e20, glass, th);
         if (hi < 0) {
             double bg[3];
             background(S.sky, rd, bg);
@@ -537,7 +555,7 @@ PT_HD void ray_color(const GlScene &S, double ro[3], double rd[3], uint64_t &rs,
         if (m.type == PT_MAT_LAMBERT) {
             cosine_dir(h.n, rs, cnt, nd);
             double dl[3];
-            direct_light(S, h, m.albedo, rs, cnt, dl);
+            direct_light(S, world, h, m.albedo, rs, cnt, dl);
             for (int i = 0; i < 3; i++) L[i] = L[i] + thr[i] * dl[i];
         } else if (m.type == PT_MAT_METAL || m.type == PT_MAT_MIRROR) {
             double view[3] = {rd[0], rd[1], rd[2]};
@@ -551,7 +569,7 @@ PT_HD void ray_color(const GlScene &S, double ro[3], double rd[3], uint64_t &rs,
                 const double sw = gclamp(1.0 / (1.0 + mr2 * 2.0), 0.1, 0.9);
                 const double dw = 1.0 - sw;
                 double dd[3];
-                direct_light(S, h, m.albedo, rs, cnt, dd);
+                direct_light(S, world, h, m.albedo, rs, cnt, dd);
                 for (int i = 0; i < 3; i++) L[i] = L[i] + thr[i] * dd[i] * dw * er * 0.5;
                 for (int i = 0; i < 3; i++) att[i] = m.albedo[i] * (sw * er + dw * 0.3);
             } else {
@@ -565,7 +583,7 @@ PT_HD void ray_color(const GlScene &S, double ro[3], double rd[3], uint64_t &rs,
                 for (int i = 0; i < 3; i++) po[i] = h.p[i] + h.n[i] * 0.001;
                 cnt.probe_rays++;
                 double pt;
-                const int32_t pi = closest(S.objs, S.nobj, po, pd, 0.001, 1e20, -1, pt);
+                const int32_t pi = world.closest(po, pd, 0.001, 1e20, -1, pt);
                 if (pi >= 0) {
                     const GlMat &pm = S.mats[S.objs[pi].mat];
                     if (pm.type == PT_MAT_EMISSIVE) {
@@ -654,7 +672,8 @@ PT_HD void ray_color(const GlScene &S, double ro[3], double rd[3], uint64_t &rs,
 
 // One pass of pixel (x, y): the 16 strata of main (gpu.go:1685-1732) summed in k = 4 sy + sx order, without the /16.
 // `key` = seed_key(seed ^ PTG_STREAM_SALT), `fog_key` = seed_key(seed ^ PTF_STREAM_SALT).
-PT_HD void gl_pass(const GlScene &S, uint64_t key, uint64_t fog_key, int32_t x, int32_t y, uint32_t pass, GlCount &cnt,
+template <typename W>
+PT_HD void gl_pass(const GlScene &S, const W &world, uint64_t key, uint64_t fog_key, int32_t x, int32_t y, uint32_t pass, GlCount &cnt,
                    ptf::FogCount &fcnt, double col[3]) {
     col[0] = col[1] = col[2] = 0.0;
     const uint64_t pix = (uint64_t)(uint32_t)y * (uint64_t)(uint32_t)S.width + (uint64_t)(uint32_t)x;
@@ -700,14 +719,25 @@ PT_HD void gl_pass(const GlScene &S, uint64_t key, uint64_t fog_key, int32_t x, 
         double L[3] = {0.0, 0.0, 0.0};
         if (S.fog_on && S.max_depth > 0) {  // in-scatter along the primary ray, before the path terms (gpu.go:1310-1340)
             double th;
-            const int32_t hi = closest(S.objs, S.nobj, ro, rd, 0.001, PTF_TMAX, -1, th);
+            const int32_t hi = world.closest(ro, rd, 0.001, PTF_TMAX, -1, th);
             const double tmax = hi >= 0 ? th : PTF_TMAX;
             const uint64_t frs = ptm::stream_init(fog_key, pix, (uint64_t)pass * 16u + (uint64_t)k);
             ptf::fog_march(S.fog, S.fog_objs, S.fog_nobj, S.fog_lights, S.fog_nlight, ro, rd, tmax, frs, fcnt, L);
         }
-        ray_color(S, ro, rd, rs, cnt, L);
+        ray_color(S, world, ro, rd, rs, cnt, L);
         for (int i = 0; i < 3; i++) col[i] = col[i] + L[i];
     }
+}
+
+// The model over the loop over all objects: the signatures gl_trace_kernel and the host builds call.
+PT_HD void ray_color(const GlScene &S, double ro[3], double rd[3], uint64_t &rs, GlCount &cnt, double L[3]) {
+    const LinearWorld world{S.objs, S.nobj};
+    ray_color(S, world, ro, rd, rs, cnt, L);
+}
+PT_HD void gl_pass(const GlScene &S, uint64_t key, uint64_t fog_key, int32_t x, int32_t y, uint32_t pass, GlCount &cnt,
+                   ptf::FogCount &fcnt, double col[3]) {
+    const LinearWorld world{S.objs, S.nobj};
+    gl_pass(S, world, key, fog_key, x, y, pass, cnt, fcnt, col);
 }
 
 }  // namespace ptg

@@ -41,6 +41,8 @@
 //   gl_trace_kernel opt-in (pt_set_shading, GL model): one pass of GL shading (pt_glshade.h) per job, 16 paths with their own
 //                   camera rays, the pass sum written into the job's radiance record; replaces ray generation and the trace
 //                   kernels for the frame.  finish_kernel then finishes with GL's tone map (gl_spp).
+//   gl_bvh_kernel   opt-in (pt_set_shading_walk): gl_trace_kernel on a BVH scan, the model's ray queries by the lane's own walk of
+//                   the resident tree (pt_gl_walk.h) instead of a loop over all objects.
 //   fog_kernel      opt-in (pt_set_fog): the fog's in-scatter term of every job (pt_fog.h), added into its radiance record
 //                   between a chunk's last trace pass and resolve_kernel.
 //   feature_kernel  opt-in (pt_set_features): per pixel slot the running sums of the first-hit normal, albedo and distance of
@@ -69,7 +71,9 @@
 #include "pt_atrous.h"
 #include "pt_fog.h"
 #include "pt_glshade.h"
+#include "pt_gl_walk.h"
 #include "pt_math.h"
+#include "pt_slab.h"
 #include "pt_temporal.h"
 
 namespace ptk {
@@ -169,7 +173,7 @@ enum { SEC_ITER = 0, SEC_RAYGEN /* loading the pre-generated ray */, SEC_HIST0 /
 
 
 enum { SCAN_UNIFORM = 0, SCAN_BROAD = 1, SCAN_VERIFY = 2, SCAN_BVH = 3, SCAN_VERIFY_BVH = 4, SCAN_BROAD_WIDE = 5, SCAN_VERIFY_WIDE = 6 };
-#define PT_BVH_STACK 96  // upper bound of the per-lane stack (sized per scene from the tree)
+// (PT_BVH_STACK, the upper bound of the per-lane stack: pt_device.h)
 
 // Diagnostic hooks handed to the scan routines (all no-ops unless PROF).
 struct ProfHooks {
@@ -546,16 +550,7 @@ struct BroadLists {
                               pt_vmax(__builtin_fmaf(-bx.h[2], aivzf, tcz_), tminf));                                  \
     const float tf = pt_vmin3(__builtin_fmaf(bx.h[0], aivxf, tcx_), __builtin_fmaf(bx.h[1], aivyf, tcy_), __builtin_fmaf(bx.h[2], aivzf, tcz_));
 
-// The direction component a slab test takes its reciprocal of: zero below F.dir_floor (build_broad).  The reciprocal of zero is
-// infinite and gives NaN parameters, which are skipped; the reciprocal of a tiny component is finite, its products with the origin
-// and the centres pass FLT_MAX, and an infinite tf is no NaN: it culled every box of a ray whose origin lay inside the slab.
-__device__ __forceinline__ float slab_dir(float d, float floor) { return __builtin_fabsf(d) < floor ? 0.0f : d; }
-// ... and the three reciprocals of a ray's slab tests (floor = F.dir_floor).
-__device__ __forceinline__ void slab_recips(float floor, float fdx, float fdy, float fdz, float &ivx, float &ivy, float &ivz) {
-    ivx = __builtin_amdgcn_rcpf(slab_dir(fdx, floor));
-    ivy = __builtin_amdgcn_rcpf(slab_dir(fdy, floor));
-    ivz = __builtin_amdgcn_rcpf(slab_dir(fdz, floor));
-}
+// (slab_dir and slab_recips, the reciprocals of a ray's slab tests with F.dir_floor: pt_slab.h)
 
 // The internal children of a 4-wide node nearest first: four keys in, sorted ascending out (5-exchange network).  A key is the
 // child's entry parameter (>= 0, so its bits order like the value) with the slot in its low bits; 0xffffffff = not a candidate.
@@ -3961,6 +3956,74 @@ __global__ __launch_bounds__(PT_BLOCK) void gl_trace_kernel(const GlArgs A) {
             atomicAdd(A.fog_counters + 1, (unsigned long long)fd);
             atomicAdd(A.fog_counters + 2, (unsigned long long)ft);
         }
+    }
+}
+
+// gl_trace_kernel on a BVH scene (pt_set_shading_walk): the same jobs, pixels, streams, radiance record and wave-summed counters,
+// the model's two ray queries answered by the lane's own walk of the resident tree (ptg::TreeWorld, pt_gl_walk.h) -- nodes by
+// vector loads, the lane's stack its column of the block's dynamic LDS (F.bvh_stack entries, stride PT_BLOCK).  The fog term's
+// march is not here (frame_open refuses gpu_volumetric with GL shading on this path), so S.fog_on is 0.
+struct GlWalkArgs {
+    GlArgs A;
+    DevFrame F;                    // bvh_root, n_plane, bvh_stack, clip_bound, origin_bound, dir_floor
+    const BvhNode *bvh_nodes;
+    const BvhObj *bvh_objs;
+    const int32_t *plane_idx;
+    unsigned long long *stats;     // [7]: closest queries walked, ... sent to the plain loop, shadow queries walked, ... sent to the plain
+                                   // loop, node visits of closest walks, of shadow walks, the deepest stack
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void gl_bvh_kernel(const GlWalkArgs W) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const GlArgs &A = W.A;
+    const uint32_t job = blockIdx.x * PT_BLOCK + threadIdx.x;
+    ptg::GlCount cnt = {0u, 0u, 0u, 0u, 0u};
+    ptg::WalkCount wc = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (job < A.njobs) {
+        const uint32_t p = job & 63u;
+        const uint32_t q = job >> 6;
+        const uint32_t blk = q / A.nS;
+        const uint32_t sl = q - blk * A.nS;
+        const Pixel px = block_pixel(TileGeom{A.S.width, A.S.height, A.ntx, A.shard_index, A.shard_count}, blk, p);
+        if (px.inside) {
+            const ptg::TreeWorld world{A.S.objs, A.S.nobj, W.F, W.bvh_nodes, W.bvh_objs, W.plane_idx,
+                                       reinterpret_cast<int *>(smem) + threadIdx.x, PT_BLOCK, wc};
+            ptf::FogCount fc = {0u, 0u, 0u};
+            double col[3];
+            ptg::gl_pass(A.S, world, A.key, A.fog_key, (int32_t)px.x, (int32_t)px.y, A.s0 + sl, cnt, fc, col);
+            reinterpret_cast<double4 *>(A.L)[job] = make_double4(col[0], col[1], col[2], 0.0);
+        }
+    }
+    const uint32_t pa = wave_sum(cnt.paths), sg = wave_sum(cnt.segments), sr = wave_sum(cnt.shadow_rays),
+                   pr = wave_sum(cnt.probe_rays), dr = wave_sum(cnt.draws);
+    const uint32_t cw = wave_sum(wc.closest_walked), cp = wave_sum(wc.closest_plain), sw = wave_sum(wc.shadow_walked),
+                   sp = wave_sum(wc.shadow_plain);
+    // (node visits of a wave: 64 lanes x 16 paths x depth x queries x visits can pass 2^32 only beyond any depth the host accepts)
+    unsigned long long cv = wc.closest_visits, sv = wc.shadow_visits;
+    uint32_t deep = wc.deepest;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        cv += __shfl_xor(cv, off);
+        sv += __shfl_xor(sv, off);
+        const uint32_t od = (uint32_t)__shfl_xor((int)deep, off);
+        deep = od > deep ? od : deep;
+    }
+    if ((threadIdx.x & 63u) == 0u && pa != 0u) {
+        atomicAdd(A.gl_counters + 0, (unsigned long long)pa);
+        atomicAdd(A.gl_counters + 1, (unsigned long long)sg);
+        atomicAdd(A.gl_counters + 2, (unsigned long long)sr);
+        atomicAdd(A.gl_counters + 3, (unsigned long long)pr);
+        atomicAdd(A.gl_counters + 4, (unsigned long long)dr);
+        atomicAdd(A.counters + 0, (unsigned long long)sg);
+        atomicAdd(A.counters + 2, (unsigned long long)dr);
+        atomicAdd(A.counters + 3, (unsigned long long)pa);
+        if (cw) atomicAdd(W.stats + 0, (unsigned long long)cw);
+        if (cp) atomicAdd(W.stats + 1, (unsigned long long)cp);
+        if (sw) atomicAdd(W.stats + 2, (unsigned long long)sw);
+        if (sp) atomicAdd(W.stats + 3, (unsigned long long)sp);
+        if (cv) atomicAdd(W.stats + 4, cv);
+        if (sv) atomicAdd(W.stats + 5, sv);
+        if (deep) atomicMax(W.stats + 6, (unsigned long long)deep);
     }
 }
 

@@ -230,6 +230,7 @@ struct Device {
     DevBuf<ptg::GlMat> gl_mats;
     DevBuf<int32_t> gl_lights;
     DevBuf<unsigned long long> gl_counters;  // [5] paths, segments, shadow rays, probe rays, draws of the frame
+    DevBuf<unsigned long long> gl_walk_counters;  // [7] pt_set_shading_walk: closest queries walked / looped plainly, shadow queries walked / looped plainly, node visits of either, deepest stack
     std::vector<char> trace_is_split;  // per trace launch of the frame: the split form?
     hipEvent_t ev_first = nullptr, ev_last = nullptr;
     bool first_recorded = false;
@@ -271,6 +272,7 @@ struct Frame {
     ptf::FogParams fog{};
     std::vector<ptf::FogLight> fog_lights;
     bool gl = false;  // GL shading (pt_set_shading): gl_trace_kernel replaces ray generation and the trace kernels
+    bool gl_walk = false;  // pt_set_shading_walk on a BVH scan with GL shading: gl_bvh_kernel (pt_gl_walk.h) in gl_trace_kernel's place
     bool moments = false;  // pt_set_moments: moments_kernel runs after every chunk's resolve add (pt_begin / pt_render frames only)
     bool adaptive = false; // pt_set_adaptive: the frame's jobs are those of the active blocks, a check ends every pt_step (implies moments)
     pt_adaptive ad{};
@@ -320,6 +322,9 @@ struct SceneData {
     int bvh_depth = 0;
     int bvh_stack_need = 0;
     bool has_glass = false;           // some object is dielectric
+    uint64_t gl_walk_gen = 0;         // pt_set_shading_walk: the generation ptg::walk_scene_check last looked at (0 = none), its answer
+    bool gl_walk_ok = false;          // ... and what it objected to
+    std::string gl_walk_why;
     size_t lds_bytes = 0;
     size_t glass_lds_bytes = 0;
     int scan = 0;
@@ -344,6 +349,7 @@ struct pt_ctx {
     int32_t features_k = 0;           // pt_set_features: feature samples per pixel (0 = off)
     DevBuf<double> g_tiles_feat, f_feat_n, f_feat_a, f_feat_d;  // pt_read_features / pt_atrous: one gathered plane, the three row-major frames
     bool fog_walk_on = false;         // pt_set_fog_walk: the volumetric fog term on the BVH path, by the wave-shared walks
+    bool shading_walk_on = false;     // pt_set_shading_walk: GL shading on the BVH path, its ray queries by the lane's walk
     bool feature_walk_on = false;     // pt_set_feature_walk: features on the BVH path, by the wave-shared walk
     struct Refit {  // pt_set_bvh_refit
         double max_growth = 0.0;      // 0 = off
@@ -452,49 +458,7 @@ namespace {
 
 // ---------------------------------------------------------------- scene conversion
 
-// objects.go:225-269; materials are converted once and indexed (the zero material
-// of a missing id is slot num_materials)
-void scene_to_world(const pt_scene &sc, std::vector<DevObj> &world, std::vector<DevMat> &mats) {
-    mats.clear();
-    for (int i = 0; i < sc.num_materials; i++) mats.push_back(convert_material(sc.materials[i]));
-    DevMat zero;
-    std::memset(&zero, 0, sizeof zero);
-    mats.push_back(zero);
-    world.clear();
-    for (int i = 0; i < sc.num_objects; i++) {
-        const pt_object &o = sc.objects[i];
-        DevObj d;
-        std::memset(&d, 0, sizeof d);
-        d.mat = (o.material >= 0 && o.material < sc.num_materials) ? o.material : sc.num_materials;
-        int kind;
-        switch (o.type) {
-            case PT_OBJ_SPHERE:
-            case PT_OBJ_SPHERE_LIGHT:
-                kind = KIND_SPHERE;
-                for (int k = 0; k < 3; k++) d.a[k] = o.position[k];
-                d.radius = o.size[0];
-                d.radius_sq = d.radius * d.radius;
-                d.inv_radius = 1.0 / d.radius;
-                break;
-            case PT_OBJ_PLANE:
-                kind = KIND_PLANE;
-                for (int k = 0; k < 3; k++) d.a[k] = o.position[k];
-                d.b[0] = 0; d.b[1] = 1; d.b[2] = 0;
-                break;
-            case PT_OBJ_BOX:
-                kind = KIND_BOX;
-                for (int k = 0; k < 3; k++) {
-                    d.a[k] = o.position[k] - o.size[k] * 0.5;
-                    d.b[k] = o.position[k] + o.size[k] * 0.5;
-                }
-                break;
-            default:
-                continue;  // unknown types are skipped
-        }
-        d.kind = kind | (mats[(size_t)d.mat].typ == MAT_DIELECTRIC ? 0x100 : 0);
-        world.push_back(d);
-    }
-}
+// (scene_to_world, objects.go:225-269: pt_convert.h)
 
 struct H3 {
     double x, y, z;
@@ -571,16 +535,7 @@ void build_broad(const std::vector<DevObj> &world, SceneData &fr) {
     fr.bbox_diel.clear();
     fr.plane_idx.clear();
     F.sph_all = F.box_all = F.sph_diel = F.box_diel = 0;
-    double B = 1.0;
-    for (const DevObj &o : world) {
-        const int kind = o.kind & 0xff;
-        if (kind == KIND_SPHERE) {
-            for (int k = 0; k < 3; k++) B = std::max(B, std::fabs(o.a[k]) + std::fabs(o.radius));
-        } else if (kind == KIND_BOX) {
-            for (int k = 0; k < 3; k++) B = std::max(B, std::max(std::fabs(o.a[k]), std::fabs(o.b[k])));
-        }
-    }
-    if (!(B < 1e30)) B = INFINITY;  // absurd or non-finite geometry: every object stays a candidate
+    const double B = ptbvh::world_bound(world);
     const double m = B * (1.0 / 4096.0);
     for (size_t i = 0; i < world.size(); i++) {
         const DevObj &o = world[i];
@@ -649,16 +604,7 @@ void build_broad(const std::vector<DevObj> &world, SceneData &fr) {
     F.broad_ok = (fr.bsph.size() <= 32 && fr.bbox.size() <= 32) ? 1 : (fr.bsph.size() <= 128 && fr.bbox.size() <= 128) ? 2 : 0;
     F.sph_all = fr.bsph.size() >= 32 ? 0xffffffffu : ((1u << fr.bsph.size()) - 1u);
     F.box_all = fr.bbox.size() >= 32 ? 0xffffffffu : ((1u << fr.bbox.size()) - 1u);
-    F.origin_bound = (float)std::min(4.0 * B, 3.0e38);
-    // With |1/d| (4 origin_bound) < 3e38 no product of a slab test (a centre, a half extent or an origin within origin_bound times
-    // 1/d) leaves the finite range, nor does their sum.  A smaller component is taken for zero, whose slab constrains nothing (the
-    // walks of the hierarchy, the grouped scan), or the ray keeps every box (the scan of at most 32 records): a
-    // product past FLT_MAX is an INFINITY, not a NaN, and tf = -inf culled boxes the ray goes through (B = 8: 4.3e-37; from
-    // B = 2^61 on a component of 2^-60 is below it; in the keep-everything band every component is).
-    F.dir_floor = round_up_f(4.0 * (double)F.origin_bound / 3.0e38);
-    F.scene_bound = B * (1.0 + 1.0 / 512.0);  // the inflation is B/4096
-    F.clip_bound = B * 3.5;
-    F.margin = m;
+    ptbvh::frame_bounds(B, F);  // origin_bound, dir_floor, scene_bound, clip_bound, margin
 }
 
 int32_t tiles_of_shard(int32_t ntiles, const pt_shard &sh) {
@@ -988,6 +934,10 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
         HIP_TRY(d.fog_walk_counters.reserve(6));
         HIP_TRY(hipMemsetAsync(d.fog_walk_counters.p, 0, 6 * sizeof(unsigned long long), d.stream));
     }
+    if (fr.gl_walk) {  // the walk's counters, zeroed when the frame opens
+        HIP_TRY(d.gl_walk_counters.reserve(7));
+        HIP_TRY(hipMemsetAsync(d.gl_walk_counters.p, 0, 7 * sizeof(unsigned long long), d.stream));
+    }
     if (fr.gl) {
         HIP_TRY(d.gl_counters.reserve(5));
         HIP_TRY(hipMemsetAsync(d.gl_counters.p, 0, 5 * sizeof(unsigned long long), d.stream));
@@ -1261,6 +1211,11 @@ int32_t step_gl(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G) {
     GA.ntx = G.ntx;  // (the frame size is GS's)
     GA.shard_index = G.shard_index;
     GA.shard_count = G.shard_count;
+    if (fr.gl_walk) {  // BVH scans with pt_set_shading_walk: the same jobs, the model's ray queries by the lane's walk of the resident tree
+        const ptk::GlWalkArgs W{GA, F, d.bvh_nodes.p, d.bvh_objs.p, d.plane_idx.p, d.gl_walk_counters.p};
+        const size_t stack_bytes = (size_t)F.bvh_stack * PT_BLOCK * sizeof(int);
+        return timed_trace(d, false, [&] { hipLaunchKernelGGL(ptk::gl_bvh_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), stack_bytes, d.stream, W); });
+    }
     return timed_trace(d, false, [&] { hipLaunchKernelGGL(ptk::gl_trace_kernel, dim3((F.njobs + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, GA); });
 }
 
@@ -1936,6 +1891,33 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     return PT_OK;
 }
 
+// pt_set_shading_walk: ptg::walk_scene_check on the tree the devices hold (a moved world's, pt_set_bvh_refit: the host's restatement
+// of their refit), cached with the scene's generation.
+int32_t gl_walk_check(pt_ctx *ctx, const pt_scene *scene, const std::vector<ptg::GlObj> &gl_objs) {
+    SceneData &sd = ctx->sd;
+    if (sd.gl_walk_gen != sd.gen) {
+        const std::vector<BvhNode> *nodes = &sd.bvh_nodes;
+        std::vector<BvhNode> moved_nodes;
+        if (sd.tree_moved && !sd.bvh_nodes.empty()) {
+            moved_nodes = sd.bvh_nodes;
+            std::vector<BvhObj> moved_objs = sd.bvh_objs;
+            std::vector<double> box, area;
+            ptbvh::refit(moved_nodes, moved_objs, sd.world, sd.bvh_margin, sd.bvh_levels, box, area);
+            nodes = &moved_nodes;
+        }
+        int32_t main_objs = 0;  // the main tree's records come first
+        for (int32_t q = 0; q < sd.Fs.bvh_main_nodes; q++)
+            for (int s = 0; s < 4; s++)
+                if (((*nodes)[(size_t)q].meta >> (12 + s)) & 1u) main_objs++;
+        sd.gl_walk_why.clear();
+        sd.gl_walk_ok = ptg::walk_scene_check(scene->objects, scene->num_objects, gl_objs.data(), nodes->data(), sd.Fs.bvh_main_nodes, sd.bvh_objs.data(),
+                                              main_objs, sd.plane_idx.data(), (int32_t)sd.plane_idx.size(), sd.gl_walk_why);
+        sd.gl_walk_gen = sd.gen;
+    }
+    if (!sd.gl_walk_ok) return fail(PT_ERR_INVALID, "GL shading on the BVH path (pt_set_shading_walk): " + sd.gl_walk_why);
+    return PT_OK;
+}
+
 int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uint32_t max_slots) {
     if (int32_t rc = scene_prepare(ctx, scene)) return rc;
     const SceneData &sd = ctx->sd;
@@ -1986,8 +1968,12 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
         if (ctx->fog_on) {
             fr.fog = ptf::fog_resolve(ctx->fog_raw);
             const bool bvh = sd.scan == ptk::SCAN_BVH || sd.scan == ptk::SCAN_VERIFY_BVH;
-            if (bvh && ctx->fog_walk_on && ctx->shading_model == PT_SHADING_GL)  // stays refused, and refused first
+            const bool gl = ctx->shading_model == PT_SHADING_GL;
+            if (bvh && ctx->fog_walk_on && gl && !ctx->shading_walk_on)  // stays refused, and refused first
                 return fail(PT_ERR_INVALID, "GL shading is not available for scenes on the BVH path (more than 128 spheres or 128 boxes)");
+            if (fr.fog.volumetric && bvh && gl && ctx->shading_walk_on)  // (fog_march's shadow tests are still the loop over all objects)
+                return fail(PT_ERR_INVALID, "fog: gpu_volumetric is not available with GL shading on the BVH path (pt_set_shading_walk); "
+                                            "affect_sky alone is");
             if (fr.fog.volumetric && bvh && !ctx->fog_walk_on)
                 return fail(PT_ERR_INVALID, "fog: gpu_volumetric is not available for scenes on the BVH path (more than 128 spheres or "
                                             "128 boxes); affect_sky alone is");
@@ -2004,7 +1990,8 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
         fr.sky = make_sky(sky);
         if (ctx->shading_model == PT_SHADING_GL) {
             if (cfg->flags & PT_FLAG_PIXEL_STATS) return fail(PT_ERR_INVALID, "GL shading: PT_FLAG_PIXEL_STATS is not available");
-            if (sd.scan == ptk::SCAN_BVH || sd.scan == ptk::SCAN_VERIFY_BVH)
+            const bool bvh = sd.scan == ptk::SCAN_BVH || sd.scan == ptk::SCAN_VERIFY_BVH;
+            if (bvh && !ctx->shading_walk_on)
                 return fail(PT_ERR_INVALID, "GL shading is not available for scenes on the BVH path (more than 128 spheres or 128 boxes)");
             if ((int32_t)ctx->gl_extras.size() != scene->num_materials)
                 return fail(PT_ERR_INVALID, "GL shading: " + std::to_string(ctx->gl_extras.size()) + " material entries for a scene with " +
@@ -2016,6 +2003,10 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
             for (int32_t i = 0; i < scene->num_objects; i++) {
                 fr.gl_objs.push_back(ptg::gl_object(scene->objects[i], nmat));
                 if (ptg::gl_is_light(*scene, i)) fr.gl_lights.push_back(i);
+            }
+            if (bvh) {  // pt_set_shading_walk: may the GL objects be found through the tree?  Asked once per scene generation.
+                if (int32_t rc = gl_walk_check(ctx, scene, fr.gl_objs)) return rc;
+                fr.gl_walk = true;
             }
             fr.gl_cam = ptg::gl_camera(scene->camera, cfg->width, cfg->height);
             fr.gl_sky = ptg::gl_sky(sky);
@@ -3344,6 +3335,32 @@ int32_t pt_fog_walk_stats(pt_ctx *ctx, uint64_t out[6]) {
         sum[5] = std::max<uint64_t>(sum[5], c[5]);  // the deepest stack: the largest of the devices'
     }
     for (int k = 0; k < 6; k++) out[k] = sum[k];
+    return PT_OK;
+}
+
+int32_t pt_set_shading_walk(pt_ctx *ctx, int32_t on) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_shading_walk while a frame is open");
+    ctx->shading_walk_on = on != 0;
+    return PT_OK;
+}
+
+int32_t pt_shading_walk_stats(pt_ctx *ctx, uint64_t out[7]) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (!out) return fail(PT_ERR_INVALID, "pt_shading_walk_stats: out is null");
+    if (!ctx->frame.gl_walk)
+        return fail(PT_ERR_STATE, "pt_shading_walk_stats: the last frame did not run the walk (pt_set_shading_walk and GL shading on a BVH scene)");
+    uint64_t sum[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (Device &d : ctx->devs) {
+        if (d.nlocal == 0 || !d.gl_walk_counters.p) continue;
+        HIP_TRY(hipSetDevice(d.ordinal));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        unsigned long long c[7] = {};
+        HIP_TRY(hipMemcpy(c, d.gl_walk_counters.p, sizeof c, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 6; k++) sum[k] += c[k];
+        sum[6] = std::max<uint64_t>(sum[6], c[6]);  // the deepest stack: the largest of the devices'
+    }
+    for (int k = 0; k < 7; k++) out[k] = sum[k];
     return PT_OK;
 }
 

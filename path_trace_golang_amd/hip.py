@@ -382,6 +382,37 @@ def fog_walk_from_env(environ=None) -> bool:
     return _env_on(environ, "PATHTRACER_GPU_FOG_WALK")
 
 
+def set_shading_walk(ctx: capi.Context, on: bool) -> None:
+    """pt_set_shading_walk: later GL frames on ctx (shading="gl") are accepted on the bounding-volume-hierarchy path too, every
+    closest hit, shadow ray and metal probe answered by the lane's own walk of the tree.  A library without the entry
+    point takes False only."""
+    if not capi.has("pt_set_shading_walk"):
+        if on:
+            raise RuntimeError("shading walk: libptcore.so lacks pt_set_shading_walk")
+        return
+    capi.check(capi.load().pt_set_shading_walk(ctx.handle, 1 if on else 0))
+    ctx._shading_walk_on = bool(on)  # what `render` compares with: it says the setting only when it changes
+
+
+SHADING_WALK_STATS = ("closest_walked", "closest_plain", "shadow_walked", "shadow_plain", "closest_visits", "shadow_visits",
+                      "deepest_stack")
+
+
+def shading_walk_stats(ctx: capi.Context) -> dict:
+    """pt_shading_walk_stats of the last frame: closest-hit queries answered by a walk and those sent to the plain loop, shadow
+    queries walked and sent to the plain loop, the node visits of either kind of walk, the deepest stack."""
+    if not capi.has("pt_shading_walk_stats"):
+        raise RuntimeError("shading walk: libptcore.so lacks pt_shading_walk_stats")
+    out = (C.c_uint64 * 7)()
+    capi.check(capi.load().pt_shading_walk_stats(ctx.handle, out))
+    return dict(zip(SHADING_WALK_STATS, (int(v) for v in out)))
+
+
+def shading_walk_from_env(environ=None) -> bool:
+    """PATHTRACER_GPU_SHADING_WALK=1 (or true / on / yes): GL shading on the bounding-volume-hierarchy path (pt_set_shading_walk)."""
+    return _env_on(environ, "PATHTRACER_GPU_SHADING_WALK")
+
+
 def set_bvh_refit(ctx: capi.Context, max_growth: float) -> None:
     """pt_set_bvh_refit: with max_growth >= 1 (or inf) a later frame on ctx whose scene differs from the previous
     frame's only in where its objects are and how large (planes included; types, materials and the count stay) keeps the
@@ -895,7 +926,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            filtered_noise: Optional[float] = None, halves: bool = False,
            temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None,
            object_ids: bool = False, temporal_motion=None, filtered_adaptive: Optional[float] = None, pool: int = 1,
-           feature_walk: bool = False, bvh_refit: Optional[float] = None, bvh_build=None, fog_walk: bool = False) -> dict:
+           feature_walk: bool = False, bvh_refit: Optional[float] = None, bvh_build=None, fog_walk: bool = False,
+           shading_walk: bool = False) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -957,6 +989,11 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     (pt_set_fog_walk; fog_walk_stats(ctx) afterwards says what the walks did).  The frame is the model's, bit for bit; the cost
     stays 24 x lights shadow rays per sample.  Without it such a frame is refused.
 
+    shading_walk=True lets a scene on the bounding-volume-hierarchy path render with shading="gl"
+    (pt_set_shading_walk; shading_walk_stats(ctx) afterwards says what the walks did).  The frame is the model's, bit for bit.
+    Without it such a frame is refused; with it a gpu_volumetric fog block, features, adaptive sampling and pixel statistics
+    stay refused there.
+
     bvh_refit=G (G >= 1 or inf, 0 = off) lets a frame whose scene differs from the context's previous frame only in
     where its objects are refit the bounding-volume hierarchy on the devices instead of rebuilding it on the host
     (pt_set_bvh_refit; bvh_refit_stats(ctx) afterwards says what happened).  The frame is the one a rebuild gives, bit for bit.
@@ -1004,6 +1041,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     set_fog(ctx, getattr(sc, "fog", None) if fog else None)
     if bool(fog_walk) != getattr(ctx, "_fog_walk_on", False):  # (said only when it changes: with it never on, the calls are what they were)
         set_fog_walk(ctx, bool(fog_walk))
+    if bool(shading_walk) != getattr(ctx, "_shading_walk_on", False):  # (the same)
+        set_shading_walk(ctx, bool(shading_walk))
     if shading != "cpu" or capi.has("pt_set_shading"):
         set_shading(ctx, shading, sc)
     if adaptive and noise is None:
