@@ -7,6 +7,7 @@
 
 #include "../../include/ptcore.h"
 #include "pt_device.h"
+#include "pt_math.h"
 
 namespace ptd {
 
@@ -63,6 +64,32 @@ inline DevMat convert_material(const pt_material &m) {  // materials.go:28-55
     r.absorbs = (r.absorption[0] > 0 || r.absorption[1] > 0 || r.absorption[2] > 0) ? 1 : 0;
     r.rough_sq = r.rough * r.rough;
     return r;
+}
+
+// Russian roulette on the attenuation (a0, a1, a2) (renderer.go:376-392), for the table beside mats[]: the operations of
+// ptk::roulette_advance on the same operands in the same order, so the same bits (this file is built with -ffp-contract=off like the
+// kernels; the device's division sequences are IEEE divisions, tests/test_div_shared_gpu.py).
+inline DevRoulette roulette_record(double a0, double a1, double a2) {
+    DevRoulette r;
+    const double maxAtt = ptm::go_max(a0, ptm::go_max(a1, a2));
+    if (maxAtt < 1e-6) {
+        r.prob = ROULETTE_ENDED;
+        r.q[0] = r.q[1] = r.q[2] = 0.0;  // never read
+        return r;
+    }
+    const double rrProb = ptm::go_min(maxAtt, 0.95);
+    r.prob = rrProb;
+    r.q[0] = a0 / rrProb;
+    r.q[1] = a1 / rrProb;
+    r.q[2] = a2 / rrProb;
+    return r;
+}
+
+// The table of a converted material list: mats[i]'s albedo at i, the attenuation (1, 1, 1) behind them.
+inline void roulette_table(const std::vector<DevMat> &mats, std::vector<DevRoulette> &tab) {
+    tab.clear();
+    for (const DevMat &m : mats) tab.push_back(roulette_record(m.albedo[0], m.albedo[1], m.albedo[2]));
+    tab.push_back(roulette_record(1.0, 1.0, 1.0));
 }
 
 // objects.go:225-269; materials are converted once and indexed (the zero material

@@ -5,6 +5,7 @@
 //   DevObj  objs[nobj]     80 B each   world after sceneToWorld (objects.go:225-269), file order
 //   DevMat  mats[nmat+1]  104 B each   materials after convertMaterial (materials.go:28-55);
 //                                      slot nmat is the zero material of a missing id
+//   DevRoulette roulette[nmat+2] 32 B each  Russian roulette of every material's albedo, then of (1, 1, 1), worked out on the host
 //   double  L[3][njobs]                per-job sample radiance of the current spp chunk (SoA)
 //   double  acc[3][nslots]             per-pixel-slot running sum over samples (SoA)
 //   uint8   tiles[ntiles][32][32][4]   resolved RGBA8, tile-major
@@ -53,6 +54,20 @@ struct alignas(8) DevMat {
     double r0_back;    // ((1 - ior) / (1 + ior))^2                (ratio = ior)
 };
 static_assert(sizeof(DevMat) == 128, "DevMat layout");
+
+// Russian roulette of an attenuation that depends on the material alone (renderer.go:375-393), worked out once on the host
+// (pt_convert.h: roulette_record) with the IEEE operations the reference performs on every hit.  One record per entry of mats[] (its
+// albedo: what every scatter but the dielectric one attenuates by) and one more, at index nmat, for the attenuation (1, 1, 1) of a
+// dielectric bounce that absorbed nothing.  DevMat is full (its size and layout are pinned), so the table stands beside it.
+//   prob   the survival probability min(max(att), 0.95); ROULETTE_ENDED (-1, which no probability is) when max(att) < 1e-6: the path
+//          ends on the last three levels without a draw.  A NaN stays a NaN: it compares false both ways, as in the reference.
+//   q      att / prob, component by component: what a survivor's throughput is multiplied by
+struct alignas(16) DevRoulette {
+    double prob;
+    double q[3];
+};
+static_assert(sizeof(DevRoulette) == 32, "DevRoulette layout");
+constexpr double ROULETTE_ENDED = -1.0;
 
 // Broad-phase records (FP32, read with scalar loads): conservative bounds of the finite
 // objects, inflated by `m = 2^-12 * scene bound` and rounded outward, so that an FP32 test
@@ -125,6 +140,16 @@ struct LdsLayout {
     // glass_kernel: the dielectric tables and records only, i.e. the trace shape without full lists
     static PT_HOST_DEVICE constexpr LdsLayout glass(size_t nobj, size_t nmat, size_t n_dsph, size_t n_dbox, bool rec_order) {
         return trace(nobj, nmat, 0, 0, n_dsph, n_dbox, rec_order);
+    }
+};
+
+// The roulette table of a block that stages the world: nmat + 1 records (nmat counts the zero material) behind everything LdsLayout
+// describes, 16-byte aligned.  `total` is what the launch asks for; scene_prepare holds the same figure against its LDS limits.
+struct RouletteLds {
+    size_t off, total;
+    static PT_HOST_DEVICE constexpr RouletteLds behind(const LdsLayout &lay, size_t nmat) {
+        const size_t off = (lay.total + 15) & ~(size_t)15;
+        return RouletteLds{off, off + (nmat + 1) * sizeof(DevRoulette)};
     }
 };
 
@@ -252,6 +277,7 @@ struct TraceBuffers {
     const uint32_t *cont_in;       // number of continuation entries this trace pass starts from (device word; 0 for a first pass)
     const BroadSphere *bsph_diel;  // broad-phase records of the dielectric objects only (exit searches of glass_kernel)
     const BroadBox *bbox_diel;
+    const DevRoulette *roulette;   // [nmat + 1] the roulette table: one record per entry of mats[], then the one of (1, 1, 1)
 };
 
 // The argument block of trace_kernel (one by-value kernel argument, i.e. the kernarg segment).

@@ -1835,6 +1835,55 @@ __device__ __forceinline__ bool roulette_advance(int &depth, double attx, double
     return finished;
 }
 
+// The same step for an attenuation that is a function of the material alone -- the albedo of a scatter, the (1, 1, 1) of a dielectric
+// bounce that absorbed nothing: `rec` is its record of the roulette table (DevRoulette, pt_device.h; built by roulette_record,
+// pt_convert.h, with the operations above on the same operands), (attx, atty, attz) the attenuation itself, which only the levels
+// above the roulette range multiply by.  No maximum, no minimum and no division per hit; the draws, the stream state and T are those
+// of roulette_advance bit for bit (tests/roulette_probe.hip runs both against the reference's own step).
+template <bool STATS>
+__device__ __forceinline__ bool roulette_table_advance(int &depth, const DevRoulette &rec, double attx, double atty, double attz, double &Tx,
+                                                       double &Ty, double &Tz, uint64_t &rs, uint32_t &c_draw, uint32_t &j_draw) {
+    bool finished = false;
+    if (depth <= 3) {
+        const double prob = rec.prob;
+        if (prob == ROULETTE_ENDED) {  // maxAtt < 1e-6: no draw
+            finished = true;
+        } else {
+            const double xi = draw_next<STATS>(rs, c_draw, j_draw);
+            if (xi > prob) {
+                finished = true;
+            } else {
+                attx = rec.q[0]; atty = rec.q[1]; attz = rec.q[2];
+            }
+        }
+    }
+    if (!finished) {
+        Tx *= attx; Ty *= atty; Tz *= attz;
+        depth--;
+        if (depth <= 0) finished = true;
+    }
+    return finished;
+}
+
+// The roulette step of a lane whose attenuation is known: rec >= 0 names its record of `tab`; rec < 0 is an attenuation only the
+// path knows (Beer-Lambert over the way through an absorbing glass) and takes roulette_advance -- which a wave without such a lane
+// does not execute.  Every lane that calls this takes the step.
+template <bool STATS>
+__device__ __forceinline__ bool roulette_step(const DevRoulette *tab, int rec, int &depth, double attx, double atty, double attz, double &Tx,
+                                              double &Ty, double &Tz, uint64_t &rs, uint32_t &c_draw, uint32_t &j_draw) {
+    bool finished = false;
+    if (rec >= 0) finished = roulette_table_advance<STATS>(depth, tab[rec], attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
+    if (__ballot(rec < 0) != 0) {
+        if (rec < 0) finished = roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
+    }
+    return finished;
+}
+// The record of a hit that shade_hit scattered: the material's, or the unit record (index nmat) for a dielectric
+__device__ __forceinline__ int roulette_record_of(const DevObj &o, int nmat) { return (o.kind & 0x100) ? nmat : o.mat; }
+// ... and of a dielectric bounce after its exit search (exit_post): Beer-Lambert applied (an absorbing material whose way out was
+// found) -> none, the attenuation is the path's own; else the unit record
+__device__ __forceinline__ int roulette_record_after_exit(const DevMat &m, int exit_best, int nmat) { return (exit_best >= 0 && m.absorbs) ? -1 : nmat; }
+
 // What the surface does with the path at its closest hit (renderer.go:308-319): the hit record of the winner
 // (objects.go:63-88, :114-132, :181-221), `emitted` and material.scatter (materials.go:67-224).
 //   finished     the path ends here with radiance `term` (an emissive surface: its emission; a failed scatter: 0)
@@ -2219,6 +2268,7 @@ __global__ __launch_bounds__(PT_BLOCK, PROF ? 1
     const LdsLayout lay = LdsLayout::trace(F.nobj, F.nmat, F.n_bsph, F.n_bbox, F.n_dsph, F.n_dbox, RO);
     DevObj *lds_obj = reinterpret_cast<DevObj *>(smem);
     DevMat *lds_mat = reinterpret_cast<DevMat *>(smem + lay.mat);
+    DevRoulette *lds_rr = reinterpret_cast<DevRoulette *>(smem + RouletteLds::behind(lay, F.nmat).off);
     int *lds_stack = reinterpret_cast<int *>(smem);
     BvhNode *lds_nodes = reinterpret_cast<BvhNode *>(smem + (size_t)F.bvh_stack * PT_BLOCK * sizeof(int));
     if (BIG) stage_lds(lds_nodes, B.bvh_nodes, F.bvh_lds_nodes * (int)(sizeof(BvhNode) / 8));
@@ -2229,6 +2279,7 @@ __global__ __launch_bounds__(PT_BLOCK, PROF ? 1
     if (!BIG) {
         stage_copy(lds_obj, B.objs, F.nobj * (int)(sizeof(DevObj) / 8));
         stage_copy(lds_mat, B.mats, F.nmat * (int)(sizeof(DevMat) / 8));
+        stage_copy(lds_rr, B.roulette, (F.nmat + 1) * (int)(sizeof(DevRoulette) / 8));
         if (SCAN == SCAN_BROAD || SCAN == SCAN_VERIFY || SCAN == SCAN_BROAD_WIDE || SCAN == SCAN_VERIFY_WIDE) {
             stage_record_index(lds_kidx, B.bsph, B.bbox, F.n_bsph, F.n_bbox);
             if (NEST) stage_record_index(lds_kidx_d, B.bsph_diel, B.bbox_diel, F.n_dsph, F.n_dbox);
@@ -2241,6 +2292,7 @@ __global__ __launch_bounds__(PT_BLOCK, PROF ? 1
     }
     const DevObj *const s_obj = BIG ? B.objs : lds_obj;
     const DevMat *const s_mat = BIG ? B.mats : lds_mat;
+    const DevRoulette *const s_rr = BIG ? B.roulette : lds_rr;  // the roulette table: staged behind the world, or from memory like the materials
 
     // The world is immutable for the whole launch: read it through the constant address
     // space so the wave-uniform scan index turns into scalar (SGPR) loads.
@@ -2493,6 +2545,7 @@ __global__ __launch_bounds__(PT_BLOCK, PROF ? 1
         if (active && scanned) {
             // -------------------------------------------------------- shade
             bool do_rr = false;
+            int rr_rec = 0;          // the lane's record of the roulette table; < 0: none (roulette_step)
             bool nest_exit = false;  // NEST: a dielectric front face was shaded, its exit search comes now
             double attx = 1, atty = 1, attz = 1;
             if (SPLIT || NEST || mode == 0) {
@@ -2517,6 +2570,7 @@ __global__ __launch_bounds__(PT_BLOCK, PROF ? 1
                         else mode = 1;
                     } else if (!finished) {
                         do_rr = true;
+                        rr_rec = SPLIT ? s_obj[best].mat : roulette_record_of(s_obj[best], F.nmat);
                     }
                     SEC_END(SEC_HITREC)
                 }
@@ -2526,6 +2580,7 @@ __global__ __launch_bounds__(PT_BLOCK, PROF ? 1
                 exit_post(s_mat[exit_mat], best, tmax, ox, oy, oz, dx, dy, dz, attx, atty, attz);
                 mode = 0;
                 do_rr = true;
+                rr_rec = roulette_record_after_exit(s_mat[exit_mat], best, F.nmat);
                 SEC_END(SEC_EXITPOST)
             }
 
@@ -2540,13 +2595,16 @@ __global__ __launch_bounds__(PT_BLOCK, PROF ? 1
                 if (VERIFY_ && eh.mismatch) c_mismatch++;
                 exit_post(s_mat[exit_mat], eh.best, eh.tmax, ox, oy, oz, dx, dy, dz, attx, atty, attz);
                 do_rr = true;
+                rr_rec = roulette_record_after_exit(s_mat[exit_mat], eh.best, F.nmat);
                 SEC_END(SEC_EXITPOST)
             }
 
             // ------------------------------------------------------------ roulette + advance
             if (do_rr) {
                 SEC_BEGIN(SEC_RR)
-                finished = roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
+                // (the split form shades no dielectric: every lane has its material's record)
+                if (SPLIT) finished = roulette_table_advance<STATS>(depth, s_rr[rr_rec], attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
+                else finished = roulette_step<STATS>(s_rr, rr_rec, depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
                 SEC_END(SEC_RR)
             }
 
@@ -2640,8 +2698,10 @@ __global__ __launch_bounds__(PT_BLOCK, (WIDE && PT_FLAT_WAVES > 4) ? 4 : PT_FLAT
     DevMat *lds_mat = reinterpret_cast<DevMat *>(smem + lay.mat);
     int *lds_kidx = reinterpret_cast<int *>(smem + lay.kidx_diel);
     DevObj *lds_rec = reinterpret_cast<DevObj *>(smem + lay.rec_diel);
+    DevRoulette *lds_rr = reinterpret_cast<DevRoulette *>(smem + RouletteLds::behind(lay, F.nmat).off);  // the roulette table, behind them
     stage_copy(lds_obj, B.objs, F.nobj * (int)(sizeof(DevObj) / 8));
     stage_copy(lds_mat, B.mats, F.nmat * (int)(sizeof(DevMat) / 8));
+    stage_copy(lds_rr, B.roulette, (F.nmat + 1) * (int)(sizeof(DevRoulette) / 8));
     stage_record_index(lds_kidx, B.bsph_diel, B.bbox_diel, F.n_dsph, F.n_dbox);
     if (!WIDE) stage_record_objects(lds_rec, B.objs, B.bsph_diel, B.bbox_diel, F.n_dsph, F.n_dbox);
     __syncthreads();
@@ -2701,6 +2761,7 @@ __global__ __launch_bounds__(PT_BLOCK, (WIDE && PT_FLAT_WAVES > 4) ? 4 : PT_FLAT
                 ox = px; oy = py; oz = pz;
                 dx = ndx; dy = ndy; dz = ndz;
                 double attx = 1, atty = 1, attz = 1;
+                int rr_rec = F.nmat;  // the unit record, unless the way through an absorbing glass attenuates (roulette_step)
                 if (ff) {  // renderer.go:316-371: the way out, before roulette
                     c_exit++;
                     const RayD ray{ox, oy, oz, dx, dy, dz};
@@ -2711,8 +2772,9 @@ __global__ __launch_bounds__(PT_BLOCK, (WIDE && PT_FLAT_WAVES > 4) ? 4 : PT_FLAT
                         record_mismatch(KB->counters, eh.scan_best, eh.best, eh.scan_tmax, eh.tmax, 1ull, ray);
                     }
                     exit_post(m, eh.best, eh.tmax, ox, oy, oz, dx, dy, dz, attx, atty, attz);
+                    rr_rec = roulette_record_after_exit(m, eh.best, F.nmat);
                 }
-                finished = roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
+                finished = roulette_step<STATS>(lds_rr, rr_rec, depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
             }
             if (finished) {
                 store_path_end<STATS>(KB, job, Tx * 0.0, Ty * 0.0, Tz * 0.0, j_seg, j_draw);

@@ -99,7 +99,8 @@ __global__ __launch_bounds__(PT_BLOCK, PT_PRIMARY_WAVES) void primary_bvh_kernel
                     uint32_t jd = j_draw;
                     shade_hit<true, false>(B.objs[best], B.mats, tmax, ox, oy, oz, dx, dy, dz, rs, c_draw, jd, finished, termx, termy, termz, attx,
                                            atty, attz, exit_search, exit_mat);
-                    if (!finished) finished = roulette_advance<true>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, jd);
+                    // (no dielectric is shaded here: the material's own record, from memory like the material)
+                    if (!finished) finished = roulette_table_advance<true>(depth, B.roulette[B.objs[best].mat], attx, atty, attz, Tx, Ty, Tz, rs, c_draw, jd);
                     j_draw = jd;
                 }
                 if (finished) store_path_end<STATS>(&B, job, Tx * termx, Ty * termy, Tz * termz, j_seg, j_draw);

@@ -440,7 +440,8 @@ __device__ __forceinline__ void shade_pass(const WfArgs &A, const DevObj *objs, 
                     to_exit = true;
                     c_exit++;
                 } else if (!finished) {
-                    finished = roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
+                    // (the roulette table from memory: these passes stage the materials only)
+                    finished = roulette_step<STATS>(B.roulette, roulette_record_of(objs[best], A.F.nmat), depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
                     go_on = !finished;
                 }
             }
@@ -493,7 +494,7 @@ __device__ __forceinline__ void exit_pass(const WfArgs &A, const DevMat *lds_mat
             const int exit_mat = Q.best[i];
             double attx = 1, atty = 1, attz = 1;
             exit_post(lds_mat[exit_mat], ebest, tmax, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, attx, atty, attz);
-            go_on = !roulette_advance<STATS>(depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
+            go_on = !roulette_step<STATS>(B.roulette, roulette_record_after_exit(lds_mat[exit_mat], ebest, A.F.nmat), depth, attx, atty, attz, Tx, Ty, Tz, rs, c_draw, j_draw);
             if (!go_on) store_path_end<STATS>(&B, job, Tx * 0.0, Ty * 0.0, Tz * 0.0, j_seg, j_draw);
         }
         if (const uint64_t pm = __ballot(go_on)) {

@@ -171,6 +171,7 @@ struct Device {
     hipStream_t stream = nullptr;  // own_stream or the caller's
     DevBuf<DevObj> objs;
     DevBuf<DevMat> mats;
+    DevBuf<DevRoulette> roulette;     // the roulette table of mats (pt_convert.h: roulette_table), uploaded with them
     DevBuf<BroadSphere> bsph;
     DevBuf<BroadBox> bbox;
     DevBuf<int32_t> plane_idx;
@@ -305,6 +306,7 @@ struct SceneData {
     uint64_t gen = 0;
     std::vector<DevObj> world;
     std::vector<DevMat> mats;
+    std::vector<DevRoulette> roulette;  // the roulette table of mats: rebuilt wherever mats is replaced
     std::vector<BroadSphere> bsph;
     std::vector<BroadBox> bbox;
     std::vector<BroadSphere> bsph_diel;
@@ -881,6 +883,7 @@ int32_t dev_begin(pt_ctx *ctx, Device &d, const pt_shard &shard, hipStream_t str
     if (d.scene_gen != sd.gen) {
         if (int32_t rc = upload(d, d.objs, sd.world)) return rc;
         if (int32_t rc = upload(d, d.mats, sd.mats)) return rc;
+        if (int32_t rc = upload(d, d.roulette, sd.roulette)) return rc;
         if (int32_t rc = upload(d, d.bsph, sd.bsph)) return rc;
         if (int32_t rc = upload(d, d.bbox, sd.bbox)) return rc;
         if (int32_t rc = upload(d, d.plane_idx, sd.plane_idx)) return rc;
@@ -1453,6 +1456,7 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     TraceBuffers B;
     B.objs = d.objs.p;
     B.mats = d.mats.p;
+    B.roulette = d.roulette.p;
     B.bsph = d.bsph.p;
     B.bbox = d.bbox.p;
     B.plane_idx = d.plane_idx.p;
@@ -1758,6 +1762,7 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     sd.valid = false;
     sd.world = std::move(world);
     sd.mats = std::move(mats);
+    roulette_table(sd.mats, sd.roulette);  // (a refit keeps mats -- refit_reason asks for the same bytes -- and so the table)
     sd.scan_req = ctx->scan_mode;
     DevFrame &F = sd.Fs;
     std::memset(&F, 0, sizeof F);
@@ -1767,8 +1772,8 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     // closest-hit strategy: at most 32 spheres and 32 boxes -> candidate bitmasks; at most 128 of each -> the same in
     // groups of 32; more -> BVH.  PTCORE_SCAN overrides.
     int scan = ctx->scan_mode;
-    // the LDS copy of the world (objects + materials + record indices) must leave room for five blocks per CU
-    const size_t world_lds = LdsLayout::trace(sd.world.size(), sd.mats.size(), sd.bsph.size(), sd.bbox.size(), sd.bsph_diel.size(), sd.bbox_diel.size(), false).world;
+    // the LDS copy of the world (objects + materials + record indices) and the roulette table behind it must leave room for five blocks per CU
+    const size_t world_lds = RouletteLds::behind(LdsLayout::trace(sd.world.size(), sd.mats.size(), sd.bsph.size(), sd.bbox.size(), sd.bsph_diel.size(), sd.bbox_diel.size(), false), sd.mats.size()).total;
     const bool wide_ok = F.broad_ok == 2 && world_lds <= 30 * 1024;
     if (scan < 0) scan = F.broad_ok == 1 ? ptk::SCAN_BROAD : wide_ok ? ptk::SCAN_BROAD_WIDE : ptk::SCAN_BVH;
     if ((scan == ptk::SCAN_BROAD || scan == ptk::SCAN_VERIFY) && F.broad_ok != 1) {
@@ -1872,8 +1877,8 @@ int32_t scene_prepare(pt_ctx *ctx, const pt_scene *scene) {
     // single-group scans keep the records' objects a second time, in record order (LdsLayout, pt_device.h); glass_kernel the dielectric ones
     const bool rec_order = scan == ptk::SCAN_BROAD || scan == ptk::SCAN_VERIFY;
     sd.lds_bytes = big ? stack_bytes + (size_t)F.bvh_lds_nodes * sizeof(BvhNode)
-                       : LdsLayout::trace((size_t)F.nobj, (size_t)F.nmat, sd.bsph.size(), sd.bbox.size(), sd.bsph_diel.size(), sd.bbox_diel.size(), rec_order).total;
-    sd.glass_lds_bytes = LdsLayout::glass((size_t)F.nobj, (size_t)F.nmat, sd.bsph_diel.size(), sd.bbox_diel.size(), rec_order).total;
+                       : RouletteLds::behind(LdsLayout::trace((size_t)F.nobj, (size_t)F.nmat, sd.bsph.size(), sd.bbox.size(), sd.bsph_diel.size(), sd.bbox_diel.size(), rec_order), (size_t)F.nmat).total;
+    sd.glass_lds_bytes = RouletteLds::behind(LdsLayout::glass((size_t)F.nobj, (size_t)F.nmat, sd.bsph_diel.size(), sd.bbox_diel.size(), rec_order), (size_t)F.nmat).total;
     // PTCORE_BVH_LDS_PAD=<bytes>: unused LDS on top of the BVH plan (occupancy experiments: 4 blocks per CU fit 40 KiB each)
     if (const char *e = std::getenv("PTCORE_BVH_LDS_PAD"))
         if (big) sd.lds_bytes += (size_t)std::max(0, std::min(120 * 1024, std::atoi(e)));
