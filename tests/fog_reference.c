@@ -425,3 +425,11 @@ void fr_ora_streams(const uint64_t *keys, int32_t ndraw, uint64_t *state0, doubl
         for (int32_t k = 0; k < ndraw; k++) out[i * ndraw + k] = ora_stream_next(&s);
     }
 }
+
+/* n shadow rays, rays[7i] = o, d, tmax: out[i] = any_hit, the shadow test of volume_light, over [0.001, tmax]. */
+void fr_occluded_many(const ora_scene *sc, int64_t n, const double *rays, int32_t *out) {
+    fr_world w;
+    world_build(sc, &w);
+    for (int64_t i = 0; i < n; i++) out[i] = any_hit(&w, rays + 7 * i, rays + 7 * i + 3, rays[7 * i + 6]);
+    world_free(&w);
+}

@@ -623,3 +623,24 @@ void gr_render(const ora_scene *sc, const gr_extra *ex, int32_t w, int32_t h, in
     for (int k = 0; k < 3; k++) stats[5 + k] = c.fcnt[k];
     ctx_close(&c);
 }
+
+/* n ray queries q[11i] = kind (0 closest, 1 occluded), ro, rd, tmin, tmax, skip, unused -- answered by hit_world, the loop over all
+ * objects above.  closest: idx = the object, t = its parameter; on a miss idx = -1 and t = tmax.  occluded (the shadow test of
+ * single_light: hit_world in [0.001, tmax] with nothing skipped): idx = 1 / 0, t = 0. */
+void gr_queries(const ora_scene *sc, const gr_extra *ex, int64_t n, const double *q, int32_t *idx, double *t) {
+    gr_ctx c;
+    ctx_open(&c, sc, ex, 1, 1, 1, 0, NULL);
+    for (int64_t i = 0; i < n; i++) {
+        const double *r = q + 11 * i;
+        gr_hit h;
+        if (r[0] == 0) {
+            int hit = hit_world(&c, r + 1, r + 4, r[7], r[8], (int)r[9], &h);
+            idx[i] = hit ? h.obj : -1;
+            t[i] = hit ? h.t : r[8];
+        } else {
+            idx[i] = hit_world(&c, r + 1, r + 4, 0.001, r[8], -1, &h) ? 1 : 0;
+            t[i] = 0.0;
+        }
+    }
+    ctx_close(&c);
+}
