@@ -49,6 +49,7 @@ func main() {
 	featureWalk := flag.Bool("feature-walk", false, "collect features on scenes beyond 128 spheres or 128 boxes too, by a wave-shared walk of the tree (or PATHTRACER_GPU_FEATURE_WALK)")
 	fogWalk := flag.Bool("fog-walk", false, "with -fog: draw a gpu_volumetric fog block on scenes beyond 128 spheres or 128 boxes too, the shadow rays by a wave-shared walk of the tree (or PATHTRACER_GPU_FOG_WALK)")
 	shadingWalk := flag.Bool("shading-walk", false, "with -shading gl: render scenes beyond 128 spheres or 128 boxes too, the model's ray queries by the lane's own walk of the tree (or PATHTRACER_GPU_SHADING_WALK)")
+	shadingFeatures := flag.Bool("shading-features", false, "with -shading gl: let the frame take -features and -atrous, the features being those of the GL pass's own camera rays (or PATHTRACER_GPU_SHADING_FEATURES)")
 	flag.Parse()
 	log.Printf("flags: scene=%s mode=%s headless=%v out=%s\n", *scenePath, *mode, *headless, *output)
 
@@ -91,6 +92,11 @@ func main() {
 		flag.Visit(func(f *flag.Flag) { shadingWalkGiven = shadingWalkGiven || f.Name == "shading-walk" })
 		if shadingWalkGiven { // else the environment decides
 			hip.SetShadingWalk(*shadingWalk)
+		}
+		shadingFeaturesGiven := false
+		flag.Visit(func(f *flag.Flag) { shadingFeaturesGiven = shadingFeaturesGiven || f.Name == "shading-features" })
+		if shadingFeaturesGiven { // else the environment decides
+			hip.SetShadingFeatures(*shadingFeatures)
 		}
 		refitGiven := false
 		flag.Visit(func(f *flag.Flag) { refitGiven = refitGiven || f.Name == "bvh-refit" })

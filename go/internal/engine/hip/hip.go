@@ -83,6 +83,9 @@ var (
 	shadingWalkSet    bool      // false: PATHTRACER_GPU_SHADING_WALK decides
 	shadingWalkWanted bool
 	shadingWalkOn     bool      // pt_set_shading_walk(1) was the last thing said to the context
+	shadingFeaturesSet    bool  // false: PATHTRACER_GPU_SHADING_FEATURES decides
+	shadingFeaturesWanted bool
+	shadingFeaturesOn     bool  // pt_set_shading_features(1) was the last thing said to the context
 	refitSet     bool           // false: PATHTRACER_GPU_BVH_REFIT decides
 	refitWanted  float64
 	refitSaid    float64        // the bound pt_set_bvh_refit was last given (0: never said, or off)
@@ -145,6 +148,7 @@ func SetDevices(n int) {
 		walkOn = false
 		fogWalkOn = false
 		shadingWalkOn = false
+		shadingFeaturesOn = false
 		refitSaid = 0
 		buildSaid = false
 	}
@@ -422,6 +426,15 @@ func SetShadingWalk(on bool) {
 	shadingWalkSet, shadingWalkWanted = true, on
 }
 
+// SetShadingFeatures lets a GL-shaded frame take features, the a-trous filter and the filtered noise target: the features are those
+// of the GL pass's own camera rays, k counts passes of 16 paths (1 under the filter unless said), and the image is GL's tone map of
+// the filtered mean (pt_set_shading_features, DESIGN 3.8b).  Not set: PATHTRACER_GPU_SHADING_FEATURES decides.
+func SetShadingFeatures(on bool) {
+	mu.Lock()
+	defer mu.Unlock()
+	shadingFeaturesSet, shadingFeaturesWanted = true, on
+}
+
 // SetBvhRefit lets a frame whose scene differs from the previous frame's only in where its objects are keep the hierarchy's topology
 // and recompute its boxes on the devices (pt_set_bvh_refit, DESIGN 3.4c).  maxGrowth >= 1 (or +Inf) bounds how far the refitted tree's
 // quality figure may exceed the built one's before the next frame rebuilds; anything below 1 is off.  Not set:
@@ -480,6 +493,18 @@ func fogWalkRule() bool {
 		return fogWalkWanted
 	}
 	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_FOG_WALK"))) {
+	case "1", "true", "on", "yes":
+		return true
+	}
+	return false
+}
+
+// shadingFeaturesRule: whether GL-shaded frames take features and the filter (SetShadingFeatures, else the environment).
+func shadingFeaturesRule() bool {
+	if shadingFeaturesSet {
+		return shadingFeaturesWanted
+	}
+	switch strings.ToLower(strings.TrimSpace(os.Getenv("PATHTRACER_GPU_SHADING_FEATURES"))) {
 	case "1", "true", "on", "yes":
 		return true
 	}
@@ -615,7 +640,8 @@ func atrousRule() (bool, int) {
 }
 
 // featuresRule: the feature samples per pixel of the next frame.  Not said (SetFeatures, PATHTRACER_GPU_FEATURES): 4 under the
-// filter unless the frame would refuse them (GL shading, a scene on the BVH path without SetFeatureWalk), else 0.
+// filter unless the frame would refuse them (GL shading without SetShadingFeatures, a scene on the BVH path without SetFeatureWalk --
+// with GL shading: without SetShadingWalk), else 0.  With GL shading k counts passes of 16 paths, and the filter's default is 1.
 func featuresRule(sc *scene.Scene, atrous bool) int {
 	if featuresK >= 0 {
 		return featuresK
@@ -626,11 +652,16 @@ func featuresRule(sc *scene.Scene, atrous bool) int {
 	if temporalRule() {
 		return 4 // pt_temporal needs them: where the frame refuses features, pt_begin says so
 	}
-	if !atrous || glShading() {
+	gl := glShading()
+	if !atrous || (gl && !shadingFeaturesRule()) {
 		return 0
 	}
-	if walkRule() {
-		return 4
+	k := 4
+	if gl {
+		k = 1
+	}
+	if (gl && shadingWalkRule()) || (!gl && walkRule()) {
+		return k
 	}
 	spheres, boxes := 0, 0
 	for _, o := range sc.Objects {
@@ -644,7 +675,7 @@ func featuresRule(sc *scene.Scene, atrous bool) int {
 	if scan := os.Getenv("PTCORE_SCAN"); spheres > 128 || boxes > 128 || scan == "bvh" || scan == "verify_bvh" {
 		return 0
 	}
-	return 4
+	return k
 }
 
 // LastAdaptive reports the block table of the last frame Render finished (the zero value unless it was adaptive).
@@ -1013,7 +1044,7 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 	if filtered > 0 && toNoise {
 		return errors.New("hip.Render: the filtered noise target excludes a frame noise target and adaptive sampling: one stop rule per frame")
 	}
-	if filtered > 0 && glShading() {
+	if filtered > 0 && glShading() && !shadingFeaturesRule() {
 		return errors.New("hip.Render: the filtered noise target is not available with GL shading")
 	}
 	var halvesOn C.int32_t
@@ -1052,6 +1083,16 @@ func renderFrame(sc *scene.Scene, cfg RenderConfig, img *image.RGBA, progress fu
 			return lastError("pt_set_shading_walk")
 		}
 		shadingWalkOn = walk
+	}
+	if feat := shadingFeaturesRule(); feat != shadingFeaturesOn { // (the same)
+		var w C.int32_t
+		if feat {
+			w = 1
+		}
+		if rc := C.pt_set_shading_features(ctx, w); rc != C.PT_OK {
+			return lastError("pt_set_shading_features")
+		}
+		shadingFeaturesOn = feat
 	}
 	if g := refitRule(); g != refitSaid { // (the same: said only when the bound changes)
 		if rc := C.pt_set_bvh_refit(ctx, C.double(g)); rc != C.PT_OK {

@@ -483,7 +483,29 @@ int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp);
  *                             components, an origin beyond 3.5 scene sizes) takes the plain scan for that sample.  Frames on the
  *                             other scans ignore the setting.  GL shading on that path stays refused unless pt_set_shading_walk;
  *                             volumetric fog has a switch of its own (pt_set_fog_walk).
- *   pt_feature_walk_stats   : out[0] = (wave, feature sample) pairs of the last frame walked by the wave, out[1] = those sent to the
+ *   pt_set_shading_features(ctx, on) : additive to ABI 4; default 0; PT_ERR_STATE while a frame is open, PT_ERR_INVALID for a null
+ *                             ctx.  With it off everything is as described above.  With it on, a frame rendered with GL shading
+ *                             (pt_set_shading) accepts pt_set_features(k > 0) and pt_set_object_ids -- on the hierarchy path together
+ *                             with pt_set_shading_walk, which GL shading needs there anyway; pt_set_feature_walk is not consulted --
+ *                             and pt_atrous and pt_atrous_halves accept the frame (with k = 0: on luminance alone).  In GL mode k
+ *                             counts passes, as samples_per_px, spp_chunk and pt_step do.  The definition (csrc/pt_gl_features.h):
+ *                             for pixel (x, y), pass p < k and stratum j = 0 .. 15, in (p, j) order,
+ *                                 ray    : the GL pass's own camera ray of path 16 p + j (its stream, its two jitter draws, its lens
+ *                                          rejection of at most 16 tries when aperture > 0), direction of unit length
+ *                                 hit    : GL's closest hit in [0.001, 1e20] -- GL's tests, a later object winning a tie, no object skipped
+ *                                 normal : the hit's face-forward unit normal (a miss adds nothing)
+ *                                 albedo : the hit material's albedo as GL packs it (emissive materials included; a missing id is material 0)
+ *                                 depth  : (sum of t, paths that hit, paths taken = 16 * min(k, passes done))
+ *                             and the object id is the first hit of (p = 0, j = 0) or -1.  GL's object list is the scene's -- an
+ *                             object of unknown type is a sphere there and can be hit -- so the id indexes pt_scene.objects.  The
+ *                             fog term does not enter.  pt_read_features and pt_read_object_ids are valid as documented below.
+ *                             pt_atrous finishes rgba by GL's tone map (pt_post_process's, of the mean); with 0 iterations the bytes
+ *                             are pt_read's.  Note that c is accum / passes there, 16 x the mean path radiance, so the 0.01 floor
+ *                             on l in the noise figures is 16 times tighter relative to the path radiance than on a CPU-model frame.
+ *                             Still refused, each with its message: pt_temporal on a GL frame (its projection is the CPU camera's),
+ *                             adaptive sampling with GL shading, PT_FLAG_PIXEL_STATS, injected rays, and gpu_volumetric fog with
+ *                             pt_set_shading_walk.
+ *   pt_feature_walk_stats  : out[0] = (wave, feature sample) pairs of the last frame walked by the wave, out[1] = those sent to the
  *                             plain scan, out[2] = node visits of the walks, out[3] = the deepest wave stack seen; summed over the
  *                             devices (out[3]: their largest).  PT_ERR_STATE when the last frame did not run the walk.  Waits for
  *                             the devices' streams.
@@ -511,12 +533,13 @@ int32_t pt_read_sample_counts(pt_ctx *ctx, uint32_t *spp);
  * variance along (var' = sum of w^2 var_j / (sum of w)^2).  A frame without features runs with the three feature terms off, whatever
  * the sigmas.  A pixel whose mean or variance is NaN or infinite is passed through and never read as a tap (bad_pixels counts them).
  *   rgba  : the CPU engine's finish of the filtered mean (sqrt, * 255.999, clamp, truncate, NaN -> 0, A = 255); may be NULL
+ *           (a GL-shaded frame, pt_set_shading_features: GL's tone map of the filtered mean)
  *   mean  : optional width*height*3 doubles, the filtered mean;  var : optional width*height doubles, its variance
  *   noise_before / noise_after : sqrt(sum of var / max(l, 0.01)^2 / pixels) of the input and of the output; noise_before is
  *                                pt_noise_estimate's figure.  Reduced over a fixed tree: the same bits every time.
  * cfg == NULL: 5 iterations, sigma_l 4, sigma_n 0.1, sigma_z 0.1, sigma_a 0.2.  NaN or negative sigmas, sigma_l <= 0 and iterations
  * outside 0..6 are PT_ERR_INVALID.  Valid when pt_read_moments is -- also between two pt_steps, for previews -- and every pixel holds
- * at least 2 samples; otherwise, and for a frame rendered with GL shading, PT_ERR_STATE.  A pure read: the sums, the counts and
+ * at least 2 samples; otherwise, and for a frame rendered with GL shading without pt_set_shading_features, PT_ERR_STATE.  A pure read: the sums, the counts and
  * whatever a later pt_step or read sees stay as they are.  Runs on devices[0].
  * Known limit: the weights are relative to each pixel's own noise, so the relative error falls while the plain, un-normalised squared
  * error of a frame dominated by a few very bright pixels (emitters seen directly) can rise.
@@ -543,6 +566,7 @@ int32_t pt_set_features(pt_ctx *ctx, int32_t k);
 int32_t pt_read_features(pt_ctx *ctx, double *normal, double *albedo, double *depth);
 int32_t pt_set_feature_walk(pt_ctx *ctx, int32_t on);
 int32_t pt_feature_walk_stats(pt_ctx *ctx, uint64_t out[4]);
+int32_t pt_set_shading_features(pt_ctx *ctx, int32_t on);
 int32_t pt_set_object_ids(pt_ctx *ctx, int32_t on);
 int32_t pt_read_object_ids(pt_ctx *ctx, int32_t *ids);
 int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32_t stride, double *mean, double *var,

@@ -253,6 +253,7 @@ SYMBOLS = [
     ("pt_fog_walk_stats", C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
     ("pt_set_shading_walk", C.c_int32, [_vp, C.c_int32]),                 # additive to ABI 4 (see has())
     ("pt_shading_walk_stats", C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
+    ("pt_set_shading_features", C.c_int32, [_vp, C.c_int32]),             # additive to ABI 4 (see has())
     ("pt_set_object_ids", C.c_int32, [_vp, C.c_int32]),                   # additive to ABI 4 (see has())
     ("pt_read_object_ids", C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     ("pt_atrous", C.c_int32, [_vp, C.POINTER(PtAtrousConfig), _vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -322,7 +323,7 @@ ADDITIVE = ("pt_set_shading", "pt_shading_last_stats", "pt_debug_set_primary_ray
             "pt_read_features", "pt_atrous", "pt_set_halves", "pt_read_halves", "pt_atrous_halves", "pt_temporal", "pt_temporal_read",
             "pt_temporal_reset", "pt_temporal_set_clip", "pt_temporal_clip_stats", "pt_set_object_ids", "pt_read_object_ids",
             "pt_temporal_set_motion", "pt_temporal_motion_stats", "pt_set_adaptive_filtered", "pt_read_block_figures",
-            "pt_set_feature_walk", "pt_feature_walk_stats", "pt_set_fog_walk", "pt_fog_walk_stats", "pt_set_shading_walk", "pt_shading_walk_stats", "pt_set_bvh_refit", "pt_bvh_refit_stats",
+            "pt_set_feature_walk", "pt_feature_walk_stats", "pt_set_fog_walk", "pt_fog_walk_stats", "pt_set_shading_walk", "pt_shading_walk_stats", "pt_set_shading_features", "pt_set_bvh_refit", "pt_bvh_refit_stats",
             "pt_debug_bvh_refit_check", "pt_set_bvh_build", "pt_bvh_build_stats",
             "pt_debug_bvh_build_check")  # added within ABI 4: detected by presence
 

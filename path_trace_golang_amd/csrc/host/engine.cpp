@@ -62,7 +62,7 @@ namespace {
     OPTIONAL(pt_set_object_ids) OPTIONAL(pt_temporal_set_motion) OPTIONAL(pt_temporal_motion_stats)                              \
     OPTIONAL(pt_set_adaptive_filtered) OPTIONAL(pt_read_block_figures) OPTIONAL(pt_set_feature_walk) \
     OPTIONAL(pt_set_bvh_refit) OPTIONAL(pt_set_bvh_build) OPTIONAL(pt_set_fog_walk) \
-    OPTIONAL(pt_set_shading_walk)
+    OPTIONAL(pt_set_shading_walk) OPTIONAL(pt_set_shading_features)
 
 struct Core {
     void *handle = nullptr;
@@ -73,7 +73,7 @@ struct Core {
 };
 
 // What a frame setting needs from the library beyond the required entry points, and what Render answers when it is not there.
-enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE, FEATURE_WALK, BVH_REFIT, BVH_BUILD, SHADING_WALK, FOG_WALK };
+enum Feature { GL_SHADING, NOISE_TARGET, TEMPORAL, TEMPORAL_CLIP, ATROUS, FILTERED_NOISE, FEATURES, ADAPTIVE, TEMPORAL_MOTION, FILTERED_ADAPTIVE, FEATURE_WALK, BVH_REFIT, BVH_BUILD, SHADING_FEATURES, SHADING_WALK, FOG_WALK };
 const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_shading != nullptr; }, "GL shading: libptcore.so lacks pt_set_shading"},
     {[](const Core &c) { return c.pt_set_moments && c.pt_noise_estimate; }, "noise target: libptcore.so lacks pt_set_moments / pt_noise_estimate"},
@@ -90,6 +90,7 @@ const struct { bool (*have)(const Core &); const char *lacks; } kNeeds[] = {
     {[](const Core &c) { return c.pt_set_feature_walk != nullptr; }, "feature walk: libptcore.so lacks pt_set_feature_walk"},
     {[](const Core &c) { return c.pt_set_bvh_refit != nullptr; }, "BVH refit: libptcore.so lacks pt_set_bvh_refit"},
     {[](const Core &c) { return c.pt_set_bvh_build != nullptr; }, "BVH device build: libptcore.so lacks pt_set_bvh_build"},
+    {[](const Core &c) { return c.pt_set_shading_features != nullptr; }, "shading features: libptcore.so lacks pt_set_shading_features"},
     {[](const Core &c) { return c.pt_set_shading_walk != nullptr; }, "shading walk: libptcore.so lacks pt_set_shading_walk"},
     {[](const Core &c) { return c.pt_set_fog_walk != nullptr; }, "fog walk: libptcore.so lacks pt_set_fog_walk"},
 };
@@ -99,7 +100,7 @@ struct NoiseRule { double target; int step; };
 struct Switch { bool on; int n; };  // adaptive + min_spp, a-trous + iterations
 struct BlockRule { double target; int pool; };
 struct Settings {
-    std::optional<bool> fog, temporal, temporal_motion, feature_walk, fog_walk, shading_walk;
+    std::optional<bool> fog, temporal, temporal_motion, feature_walk, fog_walk, shading_walk, shading_features;
     std::optional<int> shading, features, bvh_build;
     std::optional<NoiseRule> noise;
     std::optional<Switch> adaptive, atrous;
@@ -331,6 +332,7 @@ bool TemporalMotionFromEnv() { return env_switch("PATHTRACER_GPU_TEMPORAL_MOTION
 bool FeatureWalkFromEnv() { return env_switch("PATHTRACER_GPU_FEATURE_WALK"); }
 bool FogWalkFromEnv() { return env_switch("PATHTRACER_GPU_FOG_WALK"); }
 bool ShadingWalkFromEnv() { return env_switch("PATHTRACER_GPU_SHADING_WALK"); }
+bool ShadingFeaturesFromEnv() { return env_switch("PATHTRACER_GPU_SHADING_FEATURES"); }
 int BvhBuildFromEnv() {  // PATHTRACER_GPU_BVH_BUILD=host|device: anything else is host
     const char *e = std::getenv("PATHTRACER_GPU_BVH_BUILD");
     return e && std::string(e) == "device" ? 1 : 0;
@@ -357,6 +359,7 @@ struct FramePlan {
     bool walk;            // features on the BVH path too (pt_set_feature_walk)
     bool fog_walk;        // volumetric fog on the BVH path too (pt_set_fog_walk)
     bool shading_walk;    // GL shading on the BVH path too (pt_set_shading_walk)
+    bool shading_features;  // features and the a-trous filter for GL-shaded frames (pt_set_shading_features)
     double refit;         // >= 1: the growth bound of pt_set_bvh_refit; 0: off
     int build;            // the mode of pt_set_bvh_build: 0 host, 1 device
     bool moments, halves;
@@ -402,12 +405,14 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
     p.walk = s.feature_walk.value_or(FeatureWalkFromEnv());
     p.fog_walk = s.fog_walk.value_or(FogWalkFromEnv());
     p.shading_walk = s.shading_walk.value_or(ShadingWalkFromEnv());
+    p.shading_features = s.shading_features.value_or(ShadingFeaturesFromEnv());
     p.refit = s.bvh_refit.value_or(BvhRefitFromEnv());
     p.build = s.bvh_build.value_or(BvhBuildFromEnv());
     if (p.features < 0 && p.temporal) p.features = 4;  // (pt_temporal needs them: where the frame refuses features, pt_begin says so)
     if (p.features < 0) {  // not said: 4 under the filter unless the frame would refuse them (GL shading, the BVH path without the walk), else off
         p.features = 0;
-        if (p.atrous.on && p.shading != PT_SHADING_GL) {
+        const bool gl = p.shading == PT_SHADING_GL;  // (there k counts passes of 16 paths, and the walk that matters is the shading's)
+        if (p.atrous.on && (!gl || p.shading_features)) {
             size_t spheres = 0, boxes = 0;
             for (const pt_object &o : objects) {
                 spheres += o.type == PT_OBJ_SPHERE || o.type == PT_OBJ_SPHERE_LIGHT;
@@ -415,7 +420,7 @@ FramePlan resolve(const scene::Scene &sc, const std::vector<pt_object> &objects,
             }
             const char *scan = std::getenv("PTCORE_SCAN");
             const bool forced_bvh = scan && (!std::strcmp(scan, "bvh") || !std::strcmp(scan, "verify_bvh"));
-            if (p.walk || (spheres <= 128 && boxes <= 128 && !forced_bvh)) p.features = 4;
+            if ((gl ? p.shading_walk : p.walk) || (spheres <= 128 && boxes <= 128 && !forced_bvh)) p.features = gl ? 1 : 4;
         }
     }
     p.moments = p.noise.target > 0 || p.atrous.on;
@@ -438,6 +443,7 @@ bool g_block_rule_on = false;  // pt_set_adaptive_filtered(&f) was the last thin
 bool g_feature_walk_on = false;  // pt_set_feature_walk(1) was the last thing said to the context
 bool g_fog_walk_on = false;      // pt_set_fog_walk(1) was the last thing said to the context
 bool g_shading_walk_on = false;  // pt_set_shading_walk(1) was the last thing said to the context
+bool g_shading_features_on = false;  // pt_set_shading_features(1) was the last thing said to the context
 double g_bvh_refit = 0;          // the bound pt_set_bvh_refit was last given (0: never said, or off)
 int g_bvh_build = 0;             // the mode pt_set_bvh_build was last given (0: never said, or host)
 
@@ -451,6 +457,7 @@ void drop_context() {
     g_feature_walk_on = false;
     g_fog_walk_on = false;
     g_shading_walk_on = false;
+    g_shading_features_on = false;
     g_bvh_refit = 0;
     g_bvh_build = 0;
 }
@@ -625,6 +632,14 @@ bool ShadingWalk() {
     std::lock_guard<std::mutex> lk(g_mu);
     return g_set.shading_walk.value_or(ShadingWalkFromEnv());
 }
+void SetShadingFeatures(bool on) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_set.shading_features = on;
+}
+bool ShadingFeatures() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_set.shading_features.value_or(ShadingFeaturesFromEnv());
+}
 void SetBvhRefit(double max_growth) {
     std::lock_guard<std::mutex> lk(g_mu);
     g_set.bvh_refit = max_growth >= 1.0 ? max_growth : 0.0;
@@ -699,7 +714,7 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (lacks(p.motion, TEMPORAL_MOTION)) return missing;
     if (lacks(p.atrous.on, ATROUS)) return missing;
     if (to_filtered && to_noise) return "filtered noise target: excludes a frame noise target (-noise) and adaptive sampling: one stop rule per frame";
-    if (to_filtered && gl) return "filtered noise target: not available with GL shading";
+    if (to_filtered && gl && !p.shading_features) return "filtered noise target: not available with GL shading";
     if (lacks(to_filtered, FILTERED_NOISE)) return missing;
     if (to_blocks && (to_noise || to_filtered))
         return "filtered adaptive target: excludes a frame noise target (-noise), adaptive sampling and the filtered noise target: one stop rule per frame";
@@ -731,6 +746,11 @@ std::string Render(const scene::Scene &sc, const RenderConfig &cfg, RGBA &img, c
     if (p.shading_walk != g_shading_walk_on) {  // (the same)
         if (failed(PT_CALL(pt_set_shading_walk, g_ctx, p.shading_walk ? 1 : 0))) return err;
         g_shading_walk_on = p.shading_walk;
+    }
+    if (lacks(p.shading_features, SHADING_FEATURES)) return missing;
+    if (p.shading_features != g_shading_features_on) {  // (the same)
+        if (failed(PT_CALL(pt_set_shading_features, g_ctx, p.shading_features ? 1 : 0))) return err;
+        g_shading_features_on = p.shading_features;
     }
     if (g_core.pt_set_features && failed(PT_CALL(pt_set_features, g_ctx, p.features))) return err;
     if (p.motion != g_object_ids_on) {  // (said only when the switch changes: with it never on, the calls are what they were)

@@ -160,6 +160,13 @@ bool FogWalkFromEnv();  // PATHTRACER_GPU_FOG_WALK = 1 / true / on / yes
 void SetShadingWalk(bool on);
 bool ShadingWalk();
 bool ShadingWalkFromEnv();  // PATHTRACER_GPU_SHADING_WALK = 1 / true / on / yes
+// Features and the a-trous filter for GL-shaded frames (pt_set_shading_features): a GL frame collects the first-hit
+// features of its own camera rays (k counts passes of 16 paths; 1 under the filter unless said), and the filter and the filtered
+// noise target accept it, the image being GL's tone map of the filtered mean.  Off unless said or PATHTRACER_GPU_SHADING_FEATURES
+// (ShadingFeaturesFromEnv); without it such frames are refused as before.
+void SetShadingFeatures(bool on);
+bool ShadingFeatures();
+bool ShadingFeaturesFromEnv();  // PATHTRACER_GPU_SHADING_FEATURES = 1 / true / on / yes
 // Refit of the hierarchy on the devices (pt_set_bvh_refit): a frame whose scene differs from the previous frame's only in
 // where its objects are keeps the tree's topology and recomputes its boxes on the GPU; max_growth >= 1 (or inf) bounds how far the
 // refitted tree's quality figure may exceed the built one's before the next frame rebuilds.  0 (and anything below 1) is off, the

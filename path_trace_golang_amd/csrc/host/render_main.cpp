@@ -30,7 +30,9 @@
 // bounding-volume-hierarchy path draw a gpu_volumetric fog block, its shadow rays answered by a wave-shared walk of the tree
 // (pt_set_fog_walk; also env PATHTRACER_GPU_FOG_WALK).  -shading-walk (with -shading gl) lets such a scene render
 // with the GL model, its ray queries answered by the lane's own walk of the tree (pt_set_shading_walk; also env
-// PATHTRACER_GPU_SHADING_WALK).  These seven flags are parsed like the others but are
+// PATHTRACER_GPU_SHADING_WALK).  -shading-features (with -shading gl) lets a GL-shaded frame take -features and -atrous, the
+// features being those of the GL pass's own camera rays (pt_set_shading_features; also env
+// PATHTRACER_GPU_SHADING_FEATURES).  These eight flags are parsed like the others but are
 // not in the usage text below, which stands as recorded in tests/golden/host_traces.json.
 #include <cerrno>
 #include <chrono>
@@ -88,6 +90,7 @@ struct Flags {
     bool feature_walk = false;
     bool fog_walk = false;
     bool shading_walk = false;
+    bool shading_features = false;
     double bvh_refit = 0;
     std::string bvh_build = "host";
 };
@@ -154,7 +157,7 @@ int parse(int argc, char **argv, Flags &f) {
     const FlagRow table[] = {
         {"gpu", BOOL, &f.gpu}, {"headless", BOOL, &f.headless}, {"scene-settings", BOOL, &f.scene_settings}, {"fog", BOOL, &f.fog},
         {"adaptive", BOOL, &f.adaptive}, {"atrous", BOOL, &f.atrous}, {"feature-walk", BOOL, &f.feature_walk}, {"fog-walk", BOOL, &f.fog_walk},
-        {"shading-walk", BOOL, &f.shading_walk},
+        {"shading-walk", BOOL, &f.shading_walk}, {"shading-features", BOOL, &f.shading_features},
         {"scene", STRING, &f.scene}, {"mode", STRING, &f.mode}, {"out", STRING, &f.out}, {"shading", SHADING, &f.shading},
         {"width", INT, &f.width}, {"height", INT, &f.height}, {"spp", INT, &f.spp}, {"depth", INT, &f.depth}, {"devices", INT, &f.devices},
         {"noise-step", INT, &f.noise_step, 1, 0x7fffffffLL, 16}, {"min-spp", INT, &f.min_spp, 0, 0x7fffffffLL, 0},
@@ -242,6 +245,7 @@ int render_headless(const Flags &f) {
     engine::hip::SetFeatureWalk(f.feature_walk);
     engine::hip::SetFogWalk(f.fog_walk);
     engine::hip::SetShadingWalk(f.shading_walk);
+    engine::hip::SetShadingFeatures(f.shading_features);
     engine::hip::SetBvhRefit(f.bvh_refit);
     engine::hip::SetBvhBuild(f.bvh_build == "device" ? 1 : 0);
     engine::hip::SetFilteredNoise(f.filtered_noise);
@@ -315,6 +319,7 @@ int main(int argc, char **argv) {
     f.feature_walk = engine::hip::FeatureWalkFromEnv();
     f.fog_walk = engine::hip::FogWalkFromEnv();
     f.shading_walk = engine::hip::ShadingWalkFromEnv();
+    f.shading_features = engine::hip::ShadingFeaturesFromEnv();
     f.bvh_refit = engine::hip::BvhRefitFromEnv();
     f.bvh_build = engine::hip::BvhBuildFromEnv() ? "device" : "host";
     f.filtered_noise = engine::hip::FilteredNoiseFromEnv();

@@ -95,9 +95,10 @@ inline void keep_sequence(const ptk::KeepFromMapArgs &A, const ptk::CompactArgs 
 
 // What pt_atrous and pt_temporal run behind the kernel that leaves (col[0], var[0], guide): the figure of that state into
 // part[0 .. grid), then -- with a filter (P not null) -- its iterations and the figure of their result into part[grid .. 2 grid), then
-// the finish of the result into rgba.  Returns the index of the buffers that hold the result.
+// the finish of the result into rgba (gl_finish: by GL's tone map, for a frame rendered with GL shading).  Returns the index of the
+// buffers that hold the result.
 inline int filter_sequence(const pta::Params *P, double *const col[2], double *const var[2], const pta::Guide *guide, ptk::NoisePartial *part,
-                           uint8_t *rgba, int32_t W, int32_t H, hipStream_t stream) {
+                           uint8_t *rgba, int32_t W, int32_t H, hipStream_t stream, bool gl_finish = false) {
     const uint32_t npix = (uint32_t)((size_t)W * (size_t)H), grid = grid_1d(npix);
     hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid), dim3(PT_BLOCK), 0, stream, col[0], var[0], guide, part, npix);
     int cur = 0;
@@ -105,7 +106,8 @@ inline int filter_sequence(const pta::Params *P, double *const col[2], double *c
         cur = iterate<ptk::AtrousArgs, ptk::atrous_kernel>(*P, col, var, guide, W, H, stream);
         hipLaunchKernelGGL(ptk::atrous_noise_kernel, dim3(grid), dim3(PT_BLOCK), 0, stream, col[cur], var[cur], guide, part + grid, npix);
     }
-    hipLaunchKernelGGL(ptk::atrous_finish_kernel, dim3(grid), dim3(PT_BLOCK), 0, stream, col[cur], rgba, npix);
+    if (gl_finish) hipLaunchKernelGGL(ptk::atrous_finish_gl_kernel, dim3(grid), dim3(PT_BLOCK), 0, stream, col[cur], rgba, npix);
+    else hipLaunchKernelGGL(ptk::atrous_finish_kernel, dim3(grid), dim3(PT_BLOCK), 0, stream, col[cur], rgba, npix);
     return cur;
 }
 

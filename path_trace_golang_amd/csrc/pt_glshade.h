@@ -670,6 +670,52 @@ PT_HD void ray_color(const GlScene &S, const W &world, double ro[3], double rd[3
     }
 }
 
+// The primary ray of path (pass, k) of pixel (x, y): the stream of the path, the stratum jitter, buildCamera (gpu.go:1110-1124) with
+// the lens rejection of at most 16 tries, and the unit direction.  `rs` is left where ray_color goes on drawing.  gl_pass calls
+// this for every path; the first-hit features of a GL frame (pt_gl_features.h) are the features of exactly these rays.
+PT_HD void primary_ray(const GlScene &S, uint64_t key, int32_t x, int32_t y, uint32_t pass, int32_t k, uint64_t &rs, GlCount &cnt,
+                       double ro[3], double rd[3]) {
+    const uint64_t pix = (uint64_t)(uint32_t)y * (uint64_t)(uint32_t)S.width + (uint64_t)(uint32_t)x;
+    const double wm1 = (double)(S.width - 1), hm1 = (double)(S.height - 1);
+    const double fy = (double)(S.height - 1 - y);
+    const int32_t sy = k >> 2, sx = k & 3;
+    rs = ptm::stream_init(key, pix, (uint64_t)pass * 16u + (uint64_t)k);
+    cnt.paths++;
+    const double jx = ptm::stream_next(rs);
+    const double jy = ptm::stream_next(rs);
+    cnt.draws += 2;
+    const double u = ((double)x + ((double)sx + jx) / 4.0) / wm1;
+    const double v = (fy + ((double)sy + jy) / 4.0) / hm1;
+    // buildCamera, gpu.go:1110-1124
+    double off[3] = {0.0, 0.0, 0.0};
+    const GlCam &c = S.cam;
+    if (c.lens_radius > 0.0) {
+        double p[3] = {0.0, 0.0, 1.0};
+        for (int t = 0; t < 16; t++) {  // randomInUnitSphere, gpu.go:741-748
+            const double a = ptm::stream_next(rs);
+            const double b = ptm::stream_next(rs);
+            const double e = ptm::stream_next(rs);
+            cnt.draws += 3;
+            const double q[3] = {2.0 * a - 1.0, 2.0 * b - 1.0, 2.0 * e - 1.0};
+            if (dot3(q, q) >= 1.0) continue;
+            p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+            break;
+        }
+        const double rdx = c.lens_radius * p[0], rdy = c.lens_radius * p[1];
+        for (int i = 0; i < 3; i++) off[i] = c.u[i] * rdx + c.v[i] * rdy;
+        for (int i = 0; i < 3; i++) {
+            rd[i] = c.llc[i] + u * c.horizontal[i] + v * c.vertical[i] - c.origin[i] - off[i];
+            ro[i] = c.origin[i] + off[i];
+        }
+    } else {
+        for (int i = 0; i < 3; i++) {
+            rd[i] = c.llc[i] + u * c.horizontal[i] + v * c.vertical[i] - c.origin[i];
+            ro[i] = c.origin[i];
+        }
+    }
+    normalize3(rd);
+}
+
 // One pass of pixel (x, y): the 16 strata of main (gpu.go:1685-1732) summed in k = 4 sy + sx order, without the /16.
 // `key` = seed_key(seed ^ PTG_STREAM_SALT), `fog_key` = seed_key(seed ^ PTF_STREAM_SALT).
 template <typename W>
@@ -677,45 +723,10 @@ PT_HD void gl_pass(const GlScene &S, const W &world, uint64_t key, uint64_t fog_
                    ptf::FogCount &fcnt, double col[3]) {
     col[0] = col[1] = col[2] = 0.0;
     const uint64_t pix = (uint64_t)(uint32_t)y * (uint64_t)(uint32_t)S.width + (uint64_t)(uint32_t)x;
-    const double wm1 = (double)(S.width - 1), hm1 = (double)(S.height - 1);
-    const double fy = (double)(S.height - 1 - y);
     for (int32_t k = 0; k < PTG_STRATA * PTG_STRATA; k++) {
-        const int32_t sy = k >> 2, sx = k & 3;
-        uint64_t rs = ptm::stream_init(key, pix, (uint64_t)pass * 16u + (uint64_t)k);
-        cnt.paths++;
-        const double jx = ptm::stream_next(rs);
-        const double jy = ptm::stream_next(rs);
-        cnt.draws += 2;
-        const double u = ((double)x + ((double)sx + jx) / 4.0) / wm1;
-        const double v = (fy + ((double)sy + jy) / 4.0) / hm1;
-        // buildCamera, gpu.go:1110-1124
-        double ro[3], rd[3], off[3] = {0.0, 0.0, 0.0};
-        const GlCam &c = S.cam;
-        if (c.lens_radius > 0.0) {
-            double p[3] = {0.0, 0.0, 1.0};
-            for (int t = 0; t < 16; t++) {  // randomInUnitSphere, gpu.go:741-748
-                const double a = ptm::stream_next(rs);
-                const double b = ptm::stream_next(rs);
-                const double e = ptm::stream_next(rs);
-                cnt.draws += 3;
-                const double q[3] = {2.0 * a - 1.0, 2.0 * b - 1.0, 2.0 * e - 1.0};
-                if (dot3(q, q) >= 1.0) continue;
-                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-                break;
-            }
-            const double rdx = c.lens_radius * p[0], rdy = c.lens_radius * p[1];
-            for (int i = 0; i < 3; i++) off[i] = c.u[i] * rdx + c.v[i] * rdy;
-            for (int i = 0; i < 3; i++) {
-                rd[i] = c.llc[i] + u * c.horizontal[i] + v * c.vertical[i] - c.origin[i] - off[i];
-                ro[i] = c.origin[i] + off[i];
-            }
-        } else {
-            for (int i = 0; i < 3; i++) {
-                rd[i] = c.llc[i] + u * c.horizontal[i] + v * c.vertical[i] - c.origin[i];
-                ro[i] = c.origin[i];
-            }
-        }
-        normalize3(rd);
+        uint64_t rs;
+        double ro[3], rd[3];
+        primary_ray(S, key, x, y, pass, k, rs, cnt, ro, rd);
         double L[3] = {0.0, 0.0, 0.0};
         if (S.fog_on && S.max_depth > 0) {  // in-scatter along the primary ray, before the path terms (gpu.go:1310-1340)
             double th;

@@ -43,7 +43,9 @@
 //                   kernels for the frame.  finish_kernel then finishes with GL's tone map (gl_spp).
 //   gl_bvh_kernel   opt-in (pt_set_shading_walk): gl_trace_kernel on a BVH scan, the model's ray queries by the lane's own walk of
 //                   the resident tree (pt_gl_walk.h) instead of a loop over all objects.
-//   fog_kernel      opt-in (pt_set_fog): the fog's in-scatter term of every job (pt_fog.h), added into its radiance record
+//   gl_feature_kernel / gl_feature_bvh_kernel   opt-in (pt_set_shading_features): feature_kernel's sums for a GL-shaded frame, over
+//                   the camera rays gl_pass makes (pt_gl_features.h); atrous_finish_gl_kernel finishes the filtered mean by GL's tone map.
+//   fog_kernel     opt-in (pt_set_fog): the fog's in-scatter term of every job (pt_fog.h), added into its radiance record
 //                   between a chunk's last trace pass and resolve_kernel.
 //   feature_kernel  opt-in (pt_set_features): per pixel slot the running sums of the first-hit normal, albedo and distance of
 //                   the chunk's samples with index below k (pt_atrous.h), beside fog_kernel.
@@ -71,6 +73,7 @@
 #include "pt_atrous.h"
 #include "pt_fog.h"
 #include "pt_glshade.h"
+#include "pt_gl_features.h"
 #include "pt_gl_walk.h"
 #include "pt_math.h"
 #include "pt_slab.h"
@@ -3541,6 +3544,14 @@ __global__ __launch_bounds__(PT_BLOCK) void atrous_finish_kernel(const double *_
     reinterpret_cast<uint32_t *>(rgba)[i] = pta::finish_pack(c);
 }
 
+// ... of a GL-shaded frame (pt_set_shading_features): GL's tone map of the mean, as finish_kernel's of accum / passes.  The mean of an
+// unfiltered pixel is that very quotient, so with 0 iterations the bytes are pt_read's.
+__global__ __launch_bounds__(PT_BLOCK) void atrous_finish_gl_kernel(const double *__restrict__ col, uint8_t *__restrict__ rgba, uint32_t npix) {
+    const uint32_t i = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (i >= npix) return;
+    reinterpret_cast<uint32_t *>(rgba)[i] = tonemap_pack(col[3 * (size_t)i], col[3 * (size_t)i + 1], col[3 * (size_t)i + 2], 1);
+}
+
 // pt_atrous_halves (pt_atrous.h HALVES): the filter on each half of the samples and the combine, over plane-per-component buffers on
 // devices[0] -- guide [8][npix], colour [6][npix] (half A's r, g, b, then half B's) and variance [2][npix], the last two ping-pong --
 // so that the lanes of a wave read neighbouring words of every plane.  One thread per pixel, both halves in it: a tap's guide
@@ -4087,6 +4098,63 @@ __global__ __launch_bounds__(PT_BLOCK) void gl_bvh_kernel(const GlWalkArgs W) {
         if (sv) atomicAdd(W.stats + 5, sv);
         if (deep) atomicMax(W.stats + 6, (unsigned long long)deep);
     }
+}
+
+// First-hit feature sums of a GL-shaded frame (pt_set_shading_features, pt_gl_features.h): feature_kernel's nine running sums per
+// accumulation slot, over the 16 camera rays of each of the chunk's first `take` = min(S, k - s0) passes.  GL mode has no ray planes to
+// read back, so the lane makes the rays again with ptg::primary_ray -- gl_pass's own statement of them -- and asks the model's
+// closest-hit query once per ray.  One lane per slot (chunk_slot<false>: GL frames are never adaptive), a wave is one 8x8 block, a
+// slot outside the frame does nothing.  The sums stay in registers: read first unless `first`, written once.  The object loop has a
+// wave-uniform trip count, so objects and materials come in by scalar loads.  No atomics, and none of gl_pass's counters.
+struct GlFeatureArgs {
+    ptg::GlScene S;
+    double *feat;                  // [9][nslots]
+    int32_t *ids;                  // pt_set_object_ids: [nslots] the GL object (= scene index) of pass 0's path 0 (-1: a miss), or null
+    uint64_t key;                  // ptm::seed_key(seed ^ PTG_STREAM_SALT), gl_trace_kernel's
+    uint32_t nslots, s0, take;
+    int32_t first;                 // 1: the running sums start at zero (the chunk holds pass 0)
+    int32_t ntx, shard_index, shard_count;
+};
+
+template <typename MakeWorld>
+__device__ __forceinline__ void gl_feature_body(const GlFeatureArgs &A, MakeWorld &&make_world) {
+    uint32_t slot, cblk;
+    if (!chunk_slot<false>(AdaptTable{nullptr, 0u}, A.nslots, slot, cblk)) return;
+    const Pixel px = slot_pixel(TileGeom{A.S.width, A.S.height, A.ntx, A.shard_index, A.shard_count}, slot);
+    if (!px.inside) return;
+    double f[9];
+    for (uint32_t q = 0; q < 9u; q++) f[q] = A.first ? 0.0 : A.feat[q * (size_t)A.nslots + slot];
+    const auto world = make_world();
+    for (uint32_t s = 0; s < A.take; s++) {
+        int32_t id = -1;
+        ptg::feature_pass(A.S, world, A.key, (int32_t)px.x, (int32_t)px.y, A.s0 + s, f, &id);
+        if (A.ids && A.first && s == 0u) A.ids[slot] = id;  // the chunk that starts the sums holds pass 0
+    }
+    for (uint32_t q = 0; q < 9u; q++) A.feat[q * (size_t)A.nslots + slot] = f[q];
+}
+
+__global__ __launch_bounds__(PT_BLOCK) void gl_feature_kernel(const GlFeatureArgs A) {
+    gl_feature_body(A, [&] { return ptg::LinearWorld{A.S.objs, A.S.nobj}; });
+}
+
+// gl_feature_kernel on a BVH scene (pt_set_shading_walk): the same body, the closest hit by the lane's own walk of the resident tree
+// (ptg::TreeWorld) with its stack in the lane's column of the block's dynamic LDS, sized as gl_bvh_kernel's.  The walk's counters are
+// dropped: pt_shading_walk_stats counts the GL pass alone.
+struct GlFeatureWalkArgs {
+    GlFeatureArgs A;
+    DevFrame F;                    // bvh_root, n_plane, bvh_stack, clip_bound, origin_bound, dir_floor
+    const BvhNode *bvh_nodes;
+    const BvhObj *bvh_objs;
+    const int32_t *plane_idx;
+};
+
+__global__ __launch_bounds__(PT_BLOCK) void gl_feature_bvh_kernel(const GlFeatureWalkArgs W) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    ptg::WalkCount wc = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    gl_feature_body(W.A, [&] {
+        return ptg::TreeWorld{W.A.S.objs, W.A.S.nobj, W.F, W.bvh_nodes, W.bvh_objs, W.plane_idx, reinterpret_cast<int *>(smem) + threadIdx.x,
+                              PT_BLOCK, wc};
+    });
 }
 
 }  // namespace ptk

@@ -274,6 +274,7 @@ struct Frame {
     std::vector<ptf::FogLight> fog_lights;
     bool gl = false;  // GL shading (pt_set_shading): gl_trace_kernel replaces ray generation and the trace kernels
     bool gl_walk = false;  // pt_set_shading_walk on a BVH scan with GL shading: gl_bvh_kernel (pt_gl_walk.h) in gl_trace_kernel's place
+    bool gl_filter = false;  // pt_set_shading_features on a GL frame: features by gl_feature_kernel (pt_gl_features.h), pt_atrous / pt_atrous_halves accept it
     bool moments = false;  // pt_set_moments: moments_kernel runs after every chunk's resolve add (pt_begin / pt_render frames only)
     bool adaptive = false; // pt_set_adaptive: the frame's jobs are those of the active blocks, a check ends every pt_step (implies moments)
     pt_adaptive ad{};
@@ -352,6 +353,7 @@ struct pt_ctx {
     DevBuf<double> g_tiles_feat, f_feat_n, f_feat_a, f_feat_d;  // pt_read_features / pt_atrous: one gathered plane, the three row-major frames
     bool fog_walk_on = false;         // pt_set_fog_walk: the volumetric fog term on the BVH path, by the wave-shared walks
     bool shading_walk_on = false;     // pt_set_shading_walk: GL shading on the BVH path, its ray queries by the lane's walk
+    bool shading_features_on = false; // pt_set_shading_features: a GL frame takes features, object ids and the a-trous filter
     bool feature_walk_on = false;     // pt_set_feature_walk: features on the BVH path, by the wave-shared walk
     struct Refit {  // pt_set_bvh_refit
         double max_growth = 0.0;      // 0 = off
@@ -1181,11 +1183,7 @@ int32_t dev_step_wavefront(pt_ctx *ctx, Device &d, const DevFrame &F, const Trac
 // ---- dev_step's stages, in the order they run.  F is the chunk's DevFrame (F.s0, F.S, F.njobs), G the device's tile map.
 
 // GL shading: one pass per job, camera rays made in the kernel (pt_glshade.h)
-int32_t step_gl(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G) {
-    const Frame &fr = ctx->frame;
-    ptk::GlArgs GA;
-    std::memset(&GA, 0, sizeof GA);
-    ptg::GlScene &GS = GA.S;
+void gl_scene(const Frame &fr, const Device &d, const TileGeom &G, ptg::GlScene &GS) {
     GS.objs = d.gl_objs.p;
     GS.mats = d.gl_mats.p;
     GS.lights = d.gl_lights.p;
@@ -1202,6 +1200,13 @@ int32_t step_gl(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G) {
     GS.fog_lights = d.fog_lights.p;
     GS.fog_nobj = fr.nobj;
     GS.fog_nlight = (int32_t)fr.fog_lights.size();
+}
+
+int32_t step_gl(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G) {
+    const Frame &fr = ctx->frame;
+    ptk::GlArgs GA;
+    std::memset(&GA, 0, sizeof GA);
+    gl_scene(fr, d, G, GA.S);
     GA.L = d.L.p;
     GA.counters = d.counters.p;
     GA.gl_counters = d.gl_counters.p;
@@ -1413,6 +1418,32 @@ int32_t step_features(pt_ctx *ctx, Device &d, const DevFrame &F, const ptk::Adap
     return launch_pass(d, fr.adaptive, EV_FEATURE, live_slots(fr, d), ptk::feature_kernel, ptk::feature_adaptive_kernel, AT, A);
 }
 
+// ... of a GL-shaded frame (pt_set_shading_features): the features of the camera rays the chunk's GL kernel made, made again from
+// their streams (pt_gl_features.h); k counts passes
+int32_t step_gl_features(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G) {
+    const Frame &fr = ctx->frame;
+    ptk::GlFeatureArgs A;
+    std::memset(&A, 0, sizeof A);
+    gl_scene(fr, d, G, A.S);
+    A.feat = d.feat.p;
+    A.ids = fr.object_ids ? d.obj_ids.p : nullptr;
+    A.key = ptm::seed_key(fr.cfg.seed ^ PTG_STREAM_SALT);
+    A.nslots = d.nslots;
+    A.s0 = F.s0;
+    A.take = std::min(F.S, (uint32_t)fr.features - F.s0);
+    A.first = F.s0 == 0 ? 1 : 0;
+    A.ntx = G.ntx;
+    A.shard_index = G.shard_index;
+    A.shard_count = G.shard_count;
+    const dim3 grid((d.nslots + PT_BLOCK - 1) / PT_BLOCK), block(PT_BLOCK);
+    if (fr.gl_walk) {  // BVH scans: the closest hit by the lane's walk, its stack in LDS as gl_bvh_kernel's
+        const ptk::GlFeatureWalkArgs W{A, F, d.bvh_nodes.p, d.bvh_objs.p, d.plane_idx.p};
+        const size_t stack_bytes = (size_t)F.bvh_stack * PT_BLOCK * sizeof(int);
+        return timed(d, EV_FEATURE, [&] { hipLaunchKernelGGL(ptk::gl_feature_bvh_kernel, grid, block, stack_bytes, d.stream, W); });
+    }
+    return timed(d, EV_FEATURE, [&] { hipLaunchKernelGGL(ptk::gl_feature_kernel, grid, block, 0, d.stream, A); });
+}
+
 // The chunk's radiance records into the running sums (resolve_kernel), then into the sums the frame opted into, each over the same
 // records in the same order: their squares (pt_set_moments), the half-buffer sums (pt_set_halves)
 int32_t step_accumulate(pt_ctx *ctx, Device &d, const DevFrame &F, const TileGeom &G, const ptk::AdaptTable &AT) {
@@ -1494,6 +1525,8 @@ int32_t dev_step(pt_ctx *ctx, Device &d, uint32_t s0, uint32_t S) {
     }
     if (fr.gl) {
         if (int32_t rc = step_gl(ctx, d, F, G)) return rc;
+        if (fr.features > 0 && s0 < (uint32_t)fr.features)  // (only with pt_set_shading_features)
+            if (int32_t rc = step_gl_features(ctx, d, F, G)) return rc;
     } else {  // ray generation, then the trace passes (which also handle max_depth <= 0: black samples, camera draws counted)
         HIP_TRY(hipMemsetAsync(qw, 0, 8 * sizeof(unsigned int), d.stream));
         if (int32_t rc = step_raygen(ctx, d, F, AT.active)) return rc;
@@ -2002,6 +2035,7 @@ int32_t frame_open(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg, uin
                 return fail(PT_ERR_INVALID, "GL shading: " + std::to_string(ctx->gl_extras.size()) + " material entries for a scene with " +
                                                 std::to_string(scene->num_materials) + " materials");
             fr.gl = true;
+            fr.gl_filter = ctx->shading_features_on;
             const int32_t nmat = scene->num_materials;
             fr.gl_mats.assign((size_t)std::max(1, nmat), ptg::GlMat{});  // no materials: one zero material for every object
             for (int32_t i = 0; i < nmat; i++) fr.gl_mats[(size_t)i] = ptg::gl_material(scene->materials[i], ctx->gl_extras[(size_t)i]);
@@ -2327,7 +2361,7 @@ int32_t fill_counts(pt_ctx *ctx, Device &d, uint32_t, void *dst) {
 // the object index plane in scene indices, through untile_kernel's u32a plane like the counts
 int32_t fill_ids(pt_ctx *ctx, Device &d, uint32_t, void *dst) {
     hipLaunchKernelGGL(ptk::ids_tiles_kernel, dim3((d.nslots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, d.stream, d.obj_ids.p, d.obj_map.p,
-                       ctx->frame.nobj, static_cast<uint32_t *>(dst), d.nslots, tile_geom(ctx->frame, d));
+                       (int32_t)ctx->frame.world_scene.size(), static_cast<uint32_t *>(dst), d.nslots, tile_geom(ctx->frame, d));
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
@@ -2365,7 +2399,9 @@ int32_t gather_filter_inputs(pt_ctx *ctx, bool halves) {
 
 // ---- What the entry points that read a finished frame ask of it.  The frame is the open one, or the last one finished on ctx (its
 // sums stay on the devices until the next frame opens), with at least one step done; then the needs, tested in the order given.
-enum FrameNeed { NEED_MOMENTS, NEED_ADAPTIVE, NEED_HALVES, NEED_FEATURES, NEED_NOT_GL, NEED_2_SAMPLES };
+// (NEED_NOT_GL: the filters, which a GL frame opened with pt_set_shading_features meets; NEED_CPU_CAMERA: pt_temporal, whose projection
+// is the CPU engine's camera, which no GL frame meets)
+enum FrameNeed { NEED_MOMENTS, NEED_ADAPTIVE, NEED_HALVES, NEED_FEATURES, NEED_NOT_GL, NEED_2_SAMPLES, NEED_CPU_CAMERA };
 
 int32_t frame_needs(pt_ctx *ctx, const char *who, std::initializer_list<FrameNeed> needs) {
     const Frame &fr = ctx->frame;
@@ -2377,8 +2413,9 @@ int32_t frame_needs(pt_ctx *ctx, const char *who, std::initializer_list<FrameNee
         {fr.adaptive, "the frame was rendered with adaptive sampling off (pt_set_adaptive)"},
         {fr.halves, "the frame was rendered with halves off (pt_set_halves)"},
         {fr.features > 0, "the frame was rendered with features off (pt_set_features)"},
-        {!fr.gl, "not available for a frame rendered with GL shading (pt_set_shading)"},
-        {fr.done_spp >= 2, "every pixel needs at least 2 samples"}};
+        {!fr.gl || fr.gl_filter, "not available for a frame rendered with GL shading (pt_set_shading)"},
+        {fr.done_spp >= 2, "every pixel needs at least 2 samples"},
+        {!fr.gl, "not available for a frame rendered with GL shading (pt_set_shading)"}};
     for (FrameNeed n : needs)
         if (!table[n].met) return fail(PT_ERR_STATE, w + table[n].text);
     return PT_OK;
@@ -2970,14 +3007,15 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
     ctx->frame.moments = ctx->moments_on || ctx->adaptive_on || ctx->halves_on;
     if (ctx->features_k > 0) {  // refused before anything is launched; the context stays usable
         const bool bvh = ctx->frame.scan == ptk::SCAN_BVH || ctx->frame.scan == ptk::SCAN_VERIFY_BVH;
-        if ((bvh && !ctx->feature_walk_on) || ctx->frame.gl) {
+        const bool gl_feat = ctx->frame.gl && ctx->frame.gl_filter;  // pt_set_shading_features: GL's own features, on either GL kernel's path
+        if (!gl_feat && ((bvh && !ctx->feature_walk_on) || ctx->frame.gl)) {
             ctx->frame.open = false;
             return fail(PT_ERR_INVALID, bvh ? "features: not available for scenes on the BVH path (more than 128 spheres or 128 boxes): a linear "
                                               "scan per feature sample"
                                             : "features: not available with GL shading (pt_set_shading), where a sample is a pass of 16 paths");
         }
         ctx->frame.features = ctx->features_k;
-        ctx->frame.feature_walk = bvh;  // (only with pt_set_feature_walk; the other scans ignore the setting)
+        ctx->frame.feature_walk = bvh && !gl_feat;  // (only with pt_set_feature_walk; the other scans ignore the setting)
     }
     if (ctx->object_ids_on) {
         if (ctx->frame.features <= 0) {  // refused before anything is launched; the context stays usable
@@ -2989,10 +3027,10 @@ int32_t pt_begin(pt_ctx *ctx, const pt_scene *scene, const pt_config *cfg) {
         fr.scene_objects = scene->num_objects;
         fr.world_scene.clear();
         for (int32_t i = 0; i < scene->num_objects; i++) {  // scene_to_world's rule: unknown types have no object in the world
-            const int32_t t = scene->objects[i].type;
-            if (t == PT_OBJ_SPHERE || t == PT_OBJ_SPHERE_LIGHT || t == PT_OBJ_PLANE || t == PT_OBJ_BOX) fr.world_scene.push_back(i);
+            const int32_t t = scene->objects[i].type;  // (GL's list is the scene's: an unknown type is a sphere there, the map the identity)
+            if (fr.gl || t == PT_OBJ_SPHERE || t == PT_OBJ_SPHERE_LIGHT || t == PT_OBJ_PLANE || t == PT_OBJ_BOX) fr.world_scene.push_back(i);
         }
-        if ((int32_t)fr.world_scene.size() != fr.nobj) {
+        if ((int32_t)fr.world_scene.size() != (fr.gl ? (int32_t)fr.gl_objs.size() : fr.nobj)) {
             fr.open = false;
             return fail(PT_ERR_INVALID, "object ids: the device world and the scene's object list disagree");
         }
@@ -3131,7 +3169,7 @@ int32_t pt_end(pt_ctx *ctx, pt_stats *stats) {
     };
     if (ctx->frame.moments && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_MOMENTS, "moments_kernel");
     if (ctx->frame.adaptive && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_CHECK, "adaptive check");
-    if (ctx->frame.features > 0 && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_FEATURE, ctx->frame.feature_walk ? "feature_bvh_kernel" : "feature_kernel");
+    if (ctx->frame.features > 0 && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_FEATURE, ctx->frame.gl ? (ctx->frame.gl_walk ? "gl_feature_bvh_kernel" : "gl_feature_kernel") : ctx->frame.feature_walk ? "feature_bvh_kernel" : "feature_kernel");
     if (ctx->frame.halves && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_HALVES, "halves_kernel");
     if (ctx->frame.filtered && rc == PT_OK && std::getenv("PTCORE_VERBOSE")) report(EV_BLOCKS, "filtered block checks (gathers, pair filter, block map)");
     if (ctx->frame.fog_vol) {
@@ -3350,6 +3388,13 @@ int32_t pt_set_shading_walk(pt_ctx *ctx, int32_t on) {
     return PT_OK;
 }
 
+int32_t pt_set_shading_features(pt_ctx *ctx, int32_t on) {
+    if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
+    if (ctx->frame.open) return fail(PT_ERR_STATE, "pt_set_shading_features while a frame is open");
+    ctx->shading_features_on = on != 0;
+    return PT_OK;
+}
+
 int32_t pt_shading_walk_stats(pt_ctx *ctx, uint64_t out[7]) {
     if (!ctx) return fail(PT_ERR_INVALID, "ctx is null");
     if (!out) return fail(PT_ERR_INVALID, "pt_shading_walk_stats: out is null");
@@ -3549,7 +3594,7 @@ int32_t pt_atrous(pt_ctx *ctx, const pt_atrous_config *cfg, uint8_t *rgba, int32
     hipLaunchKernelGGL(ptk::atrous_prep_kernel, dim3(grid1), dim3(PT_BLOCK), 0, d0.stream, PA);
     double *const col[2] = {B.col[0].p, B.col[1].p}, *const vr[2] = {B.var[0].p, B.var[1].p};
     const pta::Params P = ptl::filter_params(c, feat);
-    const int cur = ptl::filter_sequence(&P, col, vr, B.guide.p, B.part.p, ctx->f_rgba.p, W, H, d0.stream);
+    const int cur = ptl::filter_sequence(&P, col, vr, B.guide.p, B.part.p, ctx->f_rgba.p, W, H, d0.stream, fr.gl);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(clock.ev[1], d0.stream));
     std::vector<ptk::NoisePartial> part(2 * (size_t)grid1);
@@ -3588,7 +3633,7 @@ int32_t pt_temporal(pt_ctx *ctx, const pt_temporal_config *cfg, const pt_atrous_
     Frame &fr = ctx->frame;
     pt_ctx::Temporal &T = ctx->tp;
     if (int32_t rc = stride_fits(fr, rgba, stride)) return rc;
-    if (int32_t rc = frame_needs(ctx, "pt_temporal", {NEED_NOT_GL, NEED_FEATURES, NEED_2_SAMPLES})) return rc;
+    if (int32_t rc = frame_needs(ctx, "pt_temporal", {NEED_CPU_CAMERA, NEED_FEATURES, NEED_2_SAMPLES})) return rc;
     if (T.serial == fr.serial && T.spp == fr.done_spp)
         return fail(PT_ERR_STATE, "pt_temporal: already accumulated (this frame, at this number of samples, is in the history)");
     const int32_t motion_n = T.motion_n;  // step 4a's table, pending since pt_temporal_set_motion

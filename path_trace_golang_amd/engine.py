@@ -68,7 +68,8 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
                 temporal_clip: Optional[float] = None, temporal_motion: Optional[bool] = None,
                 filtered_adaptive: Optional[float] = None, pool: Optional[int] = None,
                 feature_walk: Optional[bool] = None, bvh_refit: Optional[float] = None, bvh_build=None,
-                fog_walk: Optional[bool] = None, shading_walk: Optional[bool] = None) -> dict:
+                fog_walk: Optional[bool] = None, shading_walk: Optional[bool] = None,
+                shading_features: Optional[bool] = None) -> dict:
     """RenderInto, renderer.go:34-41.  `shading` is "cpu" (the CPU engine's image) or "gl" (the OpenGL backend's estimator,
     DESIGN 3.8); None takes PATHTRACER_GPU_SHADING (hip.ShadingConfig.from_env), which defaults to "cpu".  `moments`, `noise` and
     `noise_step` are hip.render's: render until the frame noise is at or below `noise`, cfg.samples_per_px as the
@@ -102,7 +103,9 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
     hierarchy, the shadow rays answered by the wave's walk of the tree; None takes PATHTRACER_GPU_FOG_WALK=1 (hip.fog_walk_from_env),
     off by default.  `shading_walk` is hip.render's: GL shading on scenes that take the bounding-volume hierarchy,
     the model's ray queries answered by the lane's walk of the tree; None takes PATHTRACER_GPU_SHADING_WALK=1
-    (hip.shading_walk_from_env), off by default."""
+    (hip.shading_walk_from_env), off by default.  `shading_features` is hip.render's: features, object ids and the
+    a-trous filter for GL-shaded frames, the features being those of the GL pass's own camera rays; None takes
+    PATHTRACER_GPU_SHADING_FEATURES=1 (hip.shading_features_from_env), off by default."""
     if get_backend() != Backend.GPU:
         raise NotImplementedError(
             "BackendCPU is the reference's Go renderer (renderIntoCPU) and is not shipped here; "
@@ -156,6 +159,10 @@ def render_into(sc: scn.Scene, cfg: RenderConfig, img: np.ndarray,
         shading_walk = hip.shading_walk_from_env()
     if shading_walk:  # (the same)
         walk["shading_walk"] = True
+    if shading_features is None:
+        shading_features = hip.shading_features_from_env()
+    if shading_features:  # (the same)
+        walk["shading_features"] = True
     motion = {}
     if temporal is not None and temporal_motion:
         motion = _motion_for(sc)

@@ -413,6 +413,24 @@ def shading_walk_from_env(environ=None) -> bool:
     return _env_on(environ, "PATHTRACER_GPU_SHADING_WALK")
 
 
+def set_shading_features(ctx: capi.Context, on: bool) -> None:
+    """pt_set_shading_features: later GL frames on ctx (shading="gl") accept features, object ids and the a-trous filter
+    (pt_atrous, pt_atrous_halves), the features being those of the GL pass's own camera rays.  A library without
+    the entry point takes False only."""
+    if not capi.has("pt_set_shading_features"):
+        if on:
+            raise RuntimeError("shading features: libptcore.so lacks pt_set_shading_features")
+        return
+    capi.check(capi.load().pt_set_shading_features(ctx.handle, 1 if on else 0))
+    ctx._shading_features_on = bool(on)  # what `render` compares with: it says the setting only when it changes
+
+
+def shading_features_from_env(environ=None) -> bool:
+    """PATHTRACER_GPU_SHADING_FEATURES=1 (or true / on / yes): features and the a-trous filter for GL-shaded frames
+    (pt_set_shading_features)."""
+    return _env_on(environ, "PATHTRACER_GPU_SHADING_FEATURES")
+
+
 def set_bvh_refit(ctx: capi.Context, max_growth: float) -> None:
     """pt_set_bvh_refit: with max_growth >= 1 (or inf) a later frame on ctx whose scene differs from the previous
     frame's only in where its objects are and how large (planes included; types, materials and the count stay) keeps the
@@ -856,12 +874,16 @@ def filtered_adaptive_from_env(environ=None):
     return _env_positive(environ, "PATHTRACER_GPU_FILTERED_ADAPTIVE"), 1 if pool is None else pool
 
 
-def scene_allows_features(sc, shading: str = "cpu", feature_walk: bool = False) -> bool:
-    """Does a frame of this scene accept pt_set_features(k > 0)?  Not with GL shading, and not on the bounding-volume-hierarchy
-    path (more than 128 spheres or 128 boxes, or PTCORE_SCAN=bvh) unless the context walks the tree for them (feature_walk:
-    pt_set_feature_walk)."""
+def scene_allows_features(sc, shading: str = "cpu", feature_walk: bool = False, shading_features: bool = False,
+                          shading_walk: bool = False) -> bool:
+    """Does a frame of this scene accept pt_set_features(k > 0)?  Not with GL shading unless the context collects GL's own
+    features (shading_features: pt_set_shading_features), and not on the bounding-volume-hierarchy path (more than 128 spheres or
+    128 boxes, or PTCORE_SCAN=bvh) unless the context walks the tree for them (feature_walk: pt_set_feature_walk; with GL shading
+    shading_walk: pt_set_shading_walk, which such a GL frame needs anyway)."""
     if shading != "cpu":
-        return False
+        if not shading_features:
+            return False
+        feature_walk = shading_walk  # (pt_set_feature_walk is not consulted in GL mode)
     if feature_walk:
         return True
     if os.environ.get("PTCORE_SCAN", "") in ("bvh", "verify_bvh"):
@@ -927,7 +949,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
            temporal: Optional["TemporalConfig"] = None, temporal_clip: Optional[float] = None,
            object_ids: bool = False, temporal_motion=None, filtered_adaptive: Optional[float] = None, pool: int = 1,
            feature_walk: bool = False, bvh_refit: Optional[float] = None, bvh_build=None, fog_walk: bool = False,
-           shading_walk: bool = False) -> dict:
+           shading_walk: bool = False, shading_features: bool = False) -> dict:
     """Fills img (uint8 [H, W, 4], C-contiguous rows; row stride may exceed 4*W).
 
     With fog=True and a scene that has a fog block (`sc.fog`), that block is rendered as the reference's OpenGL backend
@@ -994,6 +1016,11 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     Without it such a frame is refused; with it a gpu_volumetric fog block, features, adaptive sampling and pixel statistics
     stay refused there.
 
+    shading_features=True lets a shading="gl" frame take features=k (k counts passes of 16 paths; the planes are
+    those of the GL pass's own camera rays), object_ids=, atrous= (img is then GL's tone map of the filtered mean; features
+    defaults to 1 where the scene allows them), filtered_noise= and halves= (pt_set_shading_features).  Without it they stay
+    refused.  temporal=, adaptive=True and filtered_adaptive= stay refused with GL shading either way.
+
     bvh_refit=G (G >= 1 or inf, 0 = off) lets a frame whose scene differs from the context's previous frame only in
     where its objects are refit the bounding-volume hierarchy on the devices instead of rebuilding it on the host
     (pt_set_bvh_refit; bvh_refit_stats(ctx) afterwards says what happened).  The frame is the one a rebuild gives, bit for bit.
@@ -1016,7 +1043,7 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
             raise ValueError("filtered_noise needs the filter whose output it measures (atrous=)")
         if noise is not None or adaptive:
             raise ValueError("filtered_noise excludes noise= and adaptive=True: one stop rule per frame")
-        if shading != "cpu":
+        if shading != "cpu" and not shading_features:
             raise ValueError("filtered_noise is not available with GL shading (pt_atrous_halves refuses such frames)")
     if filtered_adaptive is not None:
         if atrous is None:
@@ -1043,6 +1070,8 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
         set_fog_walk(ctx, bool(fog_walk))
     if bool(shading_walk) != getattr(ctx, "_shading_walk_on", False):  # (the same)
         set_shading_walk(ctx, bool(shading_walk))
+    if bool(shading_features) != getattr(ctx, "_shading_features_on", False):  # (the same)
+        set_shading_features(ctx, bool(shading_features))
     if shading != "cpu" or capi.has("pt_set_shading"):
         set_shading(ctx, shading, sc)
     if adaptive and noise is None:
@@ -1063,7 +1092,12 @@ def render(sc, cfg: RenderConfig, img: np.ndarray, progress: Optional[Callable[[
     if features is None:
         features = 0
         if atrous is not None:
-            features = atrous.features if atrous.features is not None else (4 if scene_allows_features(sc, shading, feature_walk) else 0)
+            if atrous.features is not None:
+                features = atrous.features
+            elif shading != "cpu":  # (k counts passes there: 1 is 16 paths)
+                features = 1 if scene_allows_features(sc, shading, feature_walk, shading_features=shading_features, shading_walk=shading_walk) else 0
+            else:
+                features = 4 if scene_allows_features(sc, shading, feature_walk) else 0
         if temporal is not None and not features:  # (where the scene refuses features, pt_temporal says so)
             features = 4
         if (object_ids or temporal_motion is not None) and not features:
